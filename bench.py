@@ -24,12 +24,16 @@ drawn by the device packet source (BlackBodySimpleSource.create_pac
 reproduced by jump-ahead), so the host never builds the 4 GB of inputs; rank r draws packets [r P, (r+1) P) of the
 N P-packet stream.  `--config 2` selects configs[1] (tardis_example shape, 3e4 lines, downbranch, 1e7 packets).
 
-The JSON line carries `roofline` (algorithmic bytes of the dominant kernel -- the propagation kernel -- per launch over
+A plain run sets up, warms up, times the steps and prints the line (`value`, `ms_per_step` and the workload);
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs()).  Everything else runs only with
+`--full`:
+
+The `--full` JSON line carries `roofline` (algorithmic bytes of the dominant kernel -- the propagation kernel -- per launch over
 its HIP-event time, against the 8 TB/s HBM peak; the whole step beside it), `cpu_baseline` (the CPU oracle -- the
 parity-pinned C port of the reference algorithm -- timed on this box's cores on a bounded sample of the same
 workload, with the GPU-vs-CPU parity of that sample) and `boundary` (one full drop-in call
 `transport.montecarlo_transport_with_vpackets` -- host arrays in, upload, set_opacity, propagate, results out -- on
-a bounded packet count: the PCIe-inclusive rate; never `value`).  The default N = 1 line also carries `extra`: the same
+a bounded packet count: the PCIe-inclusive rate; never `value`).  The default N = 1 `--full` line also carries `extra`: the same
 timed-step structure on (a) the headline's tables with heavy-tailed macro-atom blocks and (b) BASELINE configs[4]'s table
 shape (100 shells, macroatom, ten v-packets per interaction) at 1e7 packets, each with its own `roofline` and the parity of a
 small sample against the CPU oracle (`--no-extra` skips them), and `strong_scaling_model`: one call of the headline workload at
@@ -124,12 +128,12 @@ def main():
                     help="N > 1: 'weak' = every rank owns the config's packets per step (N x packets per iteration); 'strong' = "
                          "the config's packets are shared by the N ranks (BASELINE configs[3]: 1e8 packets on 8 GPUs)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the extra legs of the default N = 1 line (uniform levels; the configs[4] table shape) and the strong_scaling_model call")
+                    help="--full: skip the extra legs of the default N = 1 line (uniform levels; the configs[4] table shape) and the strong_scaling_model call")
     ap.add_argument("--no-tracking", action="store_true", help="skip the last-interaction tracker outputs")
     ap.add_argument("--cpu-sample", type=int, default=None,
-                    help="packets in the CPU-baseline sample (0: skip; default sized for ~15 s of CPU work)")
+                    help="--full: packets in the CPU-baseline sample (0: skip; default sized for ~15 s of CPU work)")
     ap.add_argument("--boundary-packets", type=int, default=None,
-                    help="packets of the drop-in boundary call timed after the steps (0: skip; default 1e7 capped by --packets)")
+                    help="--full: packets of the drop-in boundary call timed after the steps (0: skip; default 1e7 capped by --packets)")
     ap.add_argument("--variant", type=int, default=None)
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="engine option (tardis_mc_set_option)")
     ap.add_argument("--all-on-device", type=int, default=None, metavar="D",
@@ -139,7 +143,15 @@ def main():
                          "fall-back); default: 1 when every rank has a GPU of its own (LOCAL_RANKs on distinct devices), 0 with --all-on-device")
     ap.add_argument("--dump-estimators", type=str, default=None, metavar="NPZ",
                     help="rank 0 writes the job's (all-reduced) J, nu_bar and per-shell sums of j_blue / Edotlu of the last step")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float64; a fixed seeded sample of the "
+                         "per-packet and [L,S] arrays, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (incl. the measured streaming peak), CPU baseline, "
+                         "drop-in boundary calls, strong_scaling_model and the extra legs of the default line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     pg = distributed.init_from_env()  # control plane only (TCP hub, standard library); the data-path collective is RCCL
     if pg.world_size != args.gpus:
@@ -220,10 +232,14 @@ def main():
     t1 = time.perf_counter()
     elapsed = pg.max_float(t1 - t0)
 
-    # kernel time of the last step (HIP events on the engine's streams) and its work counters
-    last_ms = eng.last_propagate_ms()
-    ktimes = eng.last_kernel_times()
-    counters = eng.last_counters()
+    if args.full:
+        # kernel time of the last step (HIP events on the engine's streams) and its work counters
+        last_ms = eng.last_propagate_ms()
+        ktimes = eng.last_kernel_times()
+        counters = eng.last_counters()
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, pg, n_gpus > 1 and not rccl_ok, not args.no_tracking)
 
     if args.dump_estimators:
         r = eng.get_results(track_last_interaction=False)
@@ -258,7 +274,7 @@ def main():
                                else "host-side sum of estimators per step through the control plane: RCCL communicator unavailable")) if n_gpus > 1 else "single GPU",
         },
     }
-    if pg.rank == 0:
+    if pg.rank == 0 and args.full:
         screened = (kw.get("n_vpackets", 0) > 0 and kw["n_lines"] >= 2500 * kw["n_shells"]
                     and not any(o.startswith("vpacket_screening=0") for o in args.option))
         crossings = guarded(traced_crossings, eng) if (screened and n_gpus == 1) else None  # (untimed: after the steps)
@@ -283,12 +299,12 @@ def main():
                 # the drop-in call at the headline's own packet count (16 GB of host arrays: only where the box has the memory to spare)
                 if args.boundary_packets is None and P > n_b and isinstance(out["boundary"], dict) and "error" not in out["boundary"]:
                     out["boundary"]["full_size"] = guarded(boundary_full_size, prob, eng, P, not args.no_tracking)
-    if pg.rank == 0 and n_gpus == 1 and args.config == 3 and args.scaling == "weak" and P >= 8_000_000 and not args.no_extra:
+    if pg.rank == 0 and args.full and n_gpus == 1 and args.config == 3 and args.scaling == "weak" and P >= 8_000_000 and not args.no_extra:
         out["strong_scaling_model"] = guarded(strong_scaling_model, eng, P, radius, value)
     eng.close()  # (frees the line-visit log before the extra legs allocate theirs)
     default_line = (n_gpus == 1 and args.config == 3 and level_default and not args.option and not args.no_tracking
                     and all(v is None for v in (args.packets, args.lines, args.shells, args.mode, args.vpackets, args.variant)))
-    if pg.rank == 0 and default_line and not args.no_extra:
+    if pg.rank == 0 and default_line and args.full and not args.no_extra:
         dev = pg.local_rank if args.all_on_device is None else args.all_on_device
         # (a) the headline's tables with heavy-tailed macro-atom blocks (what real atomic data looks like: a block is ALL
         #     transitions out of a level), same packet count; (b) BASELINE configs[4]'s table shape -- 100 shells, macroatom,
@@ -312,6 +328,57 @@ def main():
     if pg.rank == 0:
         print(json.dumps(out), flush=True)
     pg.destroy()
+
+
+DUMP_SEED = 20260916          # --dump-outputs: the sample is the same in every run with the same arguments
+DUMP_PACKETS = 1 << 18        # per-packet arrays (2 outputs + 14 tracker fields) x 2^18 x 8 B = 34 MB
+DUMP_LINE_CELLS = 1 << 19     # the two [L,S] line estimators x 2^19 x 8 B = 8 MB
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sample_index(n: int, k: int, salt: int):
+    """All of n elements, or the sorted indices of a fixed seeded choice of k of them."""
+    if n <= k:
+        return slice(None)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt]).choice(n, size=k, replace=False))
+
+
+def dump_outputs(path: str, eng, pg, host_sum: bool, track: bool) -> None:
+    """--dump-outputs: what a caller of the timed path receives after its last step (Engine.get_results) as DIR/<name>.npy in
+    float64: this rank's per-packet outputs and last-interaction trackers, the job's estimators.  Above DUMP_PACKETS packets the
+    per-packet arrays are one fixed seeded sample of packets; above DUMP_LINE_CELLS cells the [L,S] line estimators one fixed
+    seeded sample of (line, shell) cells (flat C-order indices)."""
+    if pg.rank != 0 and not host_sum:
+        return
+    if pg.rank == 0:
+        r = eng.get_results(track_last_interaction=track)
+    else:  # (the other ranks only add their estimators to rank 0's)
+        r = eng.get_results(track_last_interaction=False, want_packet_outputs=False)
+    if host_sum:  # (with RCCL the resident estimators are the all-reduced ones already)
+        pg.sum_arrays_([r.j_estimator, r.nu_bar_estimator, r.j_blue_estimator, r.edotlu_estimator])
+    if pg.rank != 0:
+        return
+    pick = _sample_index(len(r.output_nus), DUMP_PACKETS, 1)
+    arrays = {"output_nus": r.output_nus[pick], "output_energies": r.output_energies[pick]}
+    if r.trackers is not None:  # (all but `mu`, which the engine does not write: the tardis_mc.h result has no field for it)
+        t = r.trackers
+        # a packet without a recorded interaction (interaction_type INTERACTION_NONE) carries NaN in its floating-point fields; the
+        # dump holds 0.0 there instead -- that state is last_interaction_interaction_type == -1 -- so that every value written is finite
+        none = t.interaction_type[pick] == st.INTERACTION_NONE
+        for f in t.F64_FIELDS:
+            if f != "mu":
+                arrays["last_interaction_" + f] = np.where(none, 0.0, getattr(t, f)[pick])
+        for f in t.I64_FIELDS:
+            arrays["last_interaction_" + f] = getattr(t, f)[pick]
+    cells = _sample_index(r.j_blue_estimator.size, DUMP_LINE_CELLS, 2)
+    arrays.update(j_estimator=r.j_estimator, nu_bar_estimator=r.nu_bar_estimator, j_blue_estimator=r.j_blue_estimator.reshape(-1)[cells],
+                  edotlu_estimator=r.edotlu_estimator.reshape(-1)[cells], v_packets_energy_hist=r.v_packets_energy_hist)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def strong_scaling_model(eng, P: int, radius: float, headline_value: float, share: int = 8) -> dict:

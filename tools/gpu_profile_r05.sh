@@ -8,7 +8,7 @@ set -u
 CFG=${CFG:-3}; CALIB=${CALIB:-1}
 TAG=${1:-r05_config3}; shift || true
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 1 --warmup 1 --cpu-sample 0 --boundary-packets 0 --no-extra $*"
+BENCH="python $ROOT/bench.py --full --steps 1 --warmup 1 --cpu-sample 0 --boundary-packets 0 --no-extra $*"
 cd /tmp
 timeout -k 5 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace -- $BENCH > "$OUT/trace_bench.log" 2>&1
 i=0

@@ -2,7 +2,7 @@
 # the driver's command line, nothing else
 OUT=gpurun_out/r06_bench_final; mkdir -p $OUT; export TMPDIR=/tmp
 T0=$(date +%s.%N)
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$? wall $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $T0) s" >> $OUT/bench_driver_command.err
+timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$? wall $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $T0) s" >> $OUT/bench_driver_command.err
 tail -n 1 $OUT/bench_driver_command.err
 python - <<'PY'
 import json

@@ -6,8 +6,8 @@ timeout 2400 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "p
 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1
 bash tools/gpu_profile_r06.sh r06_config3 > $OUT/profile.log 2>&1
 cp gpurun_out/prof_r06_config3/pmc_traffic_config3.json profiles/pmc_traffic_config3.json 2>/dev/null
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$?" >> $OUT/bench_driver_command.err
-timeout 600 python bench.py --config 2 --steps 10 --warmup 3 > $OUT/bench_config2.json 2> $OUT/bench_config2.err
+timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$?" >> $OUT/bench_driver_command.err
+timeout 600 python bench.py --full --config 2 --steps 10 --warmup 3 > $OUT/bench_config2.json 2> $OUT/bench_config2.err
 tail -n 6 $OUT/pytest.log $OUT/smoke.log; tail -n 25 gpurun_out/prof_r06_config3/summary.txt; tail -n 3 $OUT/bench_driver_command.err
 python - <<'PY'
 import json

@@ -3,7 +3,7 @@
 OUT=gpurun_out/r06_final2; mkdir -p $OUT; export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest.log
 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1
-/usr/bin/time -v timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$?" >> $OUT/bench_driver_command.err
+/usr/bin/time -v timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$?" >> $OUT/bench_driver_command.err
 grep -E "passed|failed" $OUT/pytest.log | tail -2; tail -n 2 $OUT/smoke.log; grep -E "Elapsed|Maximum resident|bench rc" $OUT/bench_driver_command.err
 python - <<'PY'
 import json

@@ -4,7 +4,7 @@ OUT=gpurun_out/r06_final5; mkdir -p $OUT; export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest.log
 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1
 T0=$(date +%s.%N)
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$? wall $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $T0) s" >> $OUT/bench_driver_command.err
+timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$? wall $(python3 -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $T0) s" >> $OUT/bench_driver_command.err
 grep -E "passed|failed" $OUT/pytest.log | tail -2; tail -n 2 $OUT/smoke.log; tail -n 1 $OUT/bench_driver_command.err
 python - <<'PY'
 import json

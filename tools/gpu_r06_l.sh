@@ -8,6 +8,6 @@ for rep in 1 2; do for v in 2048 4096; do
   TARDIS_MC_LIB=$LIB EXP_LEVELS=heavy timeout 600 python tools/exp_cfg3.py 2e7 log_sets=1,ls_waves_per_simd=4 >> $OUT/part.log 2>&1
   TARDIS_MC_LIB=$LIB EXP_LEVELS=heavy timeout 600 python tools/exp_cfg3.py 1e8 ls_waves_per_simd=4 >> $OUT/part.log 2>&1
 done; done
-timeout 900 python bench.py --config 5 --steps 2 --warmup 1 > $OUT/bench_config5_full.json 2> $OUT/bench_config5_full.err
+timeout 900 python bench.py --full --config 5 --steps 2 --warmup 1 > $OUT/bench_config5_full.json 2> $OUT/bench_config5_full.err
 tail -n 4 $OUT/pytest_p4096.log; cat $OUT/part.log; python -c "
 import json; d=json.loads(open('$OUT/bench_config5_full.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['config']['workload'][:80])"

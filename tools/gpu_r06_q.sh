@@ -4,7 +4,7 @@ OUT=gpurun_out/r06_q; mkdir -p $OUT; export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest.log
 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1
 T0=$(date +%s.%N)
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$? wall $(echo "$(date +%s.%N) - $T0" | bc) s" >> $OUT/bench_driver_command.err
+timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err; echo "bench rc=$? wall $(echo "$(date +%s.%N) - $T0" | bc) s" >> $OUT/bench_driver_command.err
 grep -E "passed|failed" $OUT/pytest.log | tail -2; tail -n 2 $OUT/smoke.log; tail -n 1 $OUT/bench_driver_command.err
 python - <<'PY'
 import json
