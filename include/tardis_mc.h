@@ -138,6 +138,22 @@ typedef struct TardisMcResult {
     int32_t reserved;
 } TardisMcResult;
 
+/* Full r-packet tracking (option "track_full" = 1; TrackerFull, packets/trackers/tracker_full.py): one row per trace_packet
+ * outcome of every packet, in order, in a CSR layout -- packet p's rows are [offsets[p], offsets[p + 1]).  Row fields:
+ * event_id (ordinal within the packet), interaction_type (1 BOUNDARY, 2 LINE, 4 ESCATTERING), status after the event
+ * (0 IN_PROCESS, 1 EMITTED, 2 REABSORBED), shell_id (shell of the event), after_shell_id (shell after it: n_shells or -1 for a
+ * crossing out of the grid), radius, before_* (lab frame on arrival, after move_r_packet), after_* (after the event; equal to
+ * before_* for BOUNDARY rows), line_absorb_id / line_emit_id (LINE rows, -1 otherwise).  V-packets produce no rows. */
+typedef struct TardisMcEventLog {
+    int64_t capacity;                      /* in: rows available in each column array below */
+    int64_t count;                         /* out: rows of the last propagate call (offsets[n_packets]) */
+    int64_t dropped;                       /* out: rows the device pool could not hold (option event_log_capacity too small) */
+    int64_t *offsets;                      /* [n_packets + 1], or NULL */
+    /* [count] each, or NULL; written only when dropped == 0 and count <= capacity */
+    int64_t *event_id, *interaction_type, *status, *shell_id, *after_shell_id, *line_absorb_id, *line_emit_id;
+    double *radius, *before_nu, *before_mu, *before_energy, *after_nu, *after_mu, *after_energy;
+} TardisMcEventLog;
+
 typedef struct TardisMcContext TardisMcContext;
 
 /* ---- library / device ---------------------------------------------------------------------------- */
@@ -149,6 +165,12 @@ void tardis_mc_destroy(TardisMcContext *ctx);
 const char *tardis_mc_last_error(const TardisMcContext *ctx);   /* ctx may be NULL: last create() error */
 
 /* Tunables.  name: "track_last_interaction" (0/1, default 1), "vpacket_log_capacity" (entries),
+ * "track_full" (0/1, default 0: full r-packet tracking, TardisMcEventLog; whatever "variant" says, a call runs on the wave-owner
+ * kernel with group sweeps, variant 2, where that can run it -- sorted lines, monotone probabilities, <= 32 v-packets and no surviving
+ * ones, no cross-check debug flags -- else on the lane-per-packet kernel, variant 0), "event_log_capacity" (rows the device log holds, 0 = automatic: 32 per packet; a call whose log
+ * overflows drops rows, keeps the counts exact and reports them through tardis_mc_get_event_log), "event_log_max_bytes" (bound on
+ * the log's device memory, default 16 GiB: 96 B per pool row + 112 B per row for the columns + 12 B per packet; a call over it fails
+ * with TARDIS_MC_ERR_INVALID_ARGUMENT),
  * "variant" (kernel variant: -1 automatic, 0 lane-per-packet, 1 group-per-packet, 2 wave-owner with group sweeps, 3 wave-owner
  * with lane sweeps, 4 wave-owner with the volley queue: v-packets traced by a kernel of their own between its launches --
  * never the automatic choice; falls back to 2/3 without v-packets and to 1 with a survival probability > 0),
@@ -293,6 +315,12 @@ int tardis_mc_radiation_field(TardisMcContext *ctx, double time_of_simulation, c
 int tardis_mc_formal_integral(TardisMcContext *ctx, double inner_temperature, const double *frequencies, int64_t n_frequencies,
                               const double *att_S_ul, const double *Jred_lu, const double *Jblue_lu, int64_t n_impact_parameters,
                               double *luminosity_densities, double *intensities_nu_p);
+
+/* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
+ * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the
+ * last call ran without full tracking, when a packet of it failed, or when the resident packets were replaced since.  With dropped > 0 only count / dropped / offsets are written: run the call again with
+ * event_log_capacity >= count (the run is deterministic). */
+int tardis_mc_get_event_log(TardisMcContext *ctx, TardisMcEventLog *log);
 
 /* ---- result streaming (optional).  Registers the caller's per-packet result arrays (output_nus / output_energies and the fourteen li_* arrays of *dst; any may
  * be NULL; the other fields are ignored) as the destination of the NEXT tardis_mc_propagate: a call of the wave-owner kernel that runs as several launches copies the

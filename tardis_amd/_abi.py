@@ -96,6 +96,19 @@ class TardisMcResult(C.Structure):
     )
 
 
+_EV_I64 = ("event_id", "interaction_type", "status", "shell_id", "after_shell_id", "line_absorb_id", "line_emit_id")
+_EV_F64 = ("radius", "before_nu", "before_mu", "before_energy", "after_nu", "after_mu", "after_energy")
+
+
+class TardisMcEventLog(C.Structure):
+    """Full r-packet tracking: CSR offsets + packet-major columns (tardis_mc_get_event_log)."""
+    _fields_ = (
+        [("capacity", C.c_int64), ("count", C.c_int64), ("dropped", C.c_int64), ("offsets", _pi)]
+        + [(n, _pi) for n in _EV_I64]
+        + [(n, _pd) for n in _EV_F64]
+    )
+
+
 def _dp(a: np.ndarray):
     assert a.dtype == np.float64 and a.flags.c_contiguous
     return a.ctypes.data_as(_pd)

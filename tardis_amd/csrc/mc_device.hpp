@@ -49,6 +49,19 @@ struct EstimatorLog {
     int tiles_per_shell;
 };
 
+// Full r-packet tracking (event_log.hpp): one 96-byte row per trace_packet outcome, appended to a pool of chunks -- a wave
+// takes a chunk with one atomic and ranks its lanes inside it -- and scattered packet-major after the call.
+struct EventRow;
+struct EventLog {
+    EventRow *rows;                    // [n_chunks][chunk_rows]; null: full tracking is off
+    unsigned *chunk_fill;              // [n_chunks] rows written to each chunk (stored when its wave leaves it)
+    unsigned *pool_next;               // next free chunk of the pool
+    unsigned long long *dropped;       // rows that found the pool empty
+    int *counts;                       // [n_packets] rows of each packet (exact whether rows were dropped or not)
+    unsigned chunk_rows;               // rows per chunk (>= 64: one append of a wave spills into at most one new chunk)
+    unsigned n_chunks;
+};
+
 // Everything a propagation kernel needs, passed by value (kernarg segment -> SGPRs).
 struct DeviceProblem {
     // packets (SoA, coalesced by packet index)
@@ -104,6 +117,7 @@ struct DeviceProblem {
     unsigned long long *next_packet;  // work counter for persistent scheduling
     int debug_flags;                  // profiling experiments only: 1 = skip j_blue/Edotlu atomics, 2 = skip J/nu_bar
     EstimatorLog log;                 // line-visit log of the cooperative kernels (capacity 0: they add their terms directly)
+    EventLog evlog;                   // full r-packet tracking (lane kernel only; last, so that no other field moves)
 };
 
 // Slim by-value argument block of the cooperative kernel: only what the inner loops touch stays in SGPRs; everything

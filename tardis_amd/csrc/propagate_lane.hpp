@@ -7,6 +7,7 @@
 // into shell-major tables.
 #pragma once
 #include "mc_device.hpp"
+#include "event_log.hpp"
 
 namespace mc {
 
@@ -318,9 +319,10 @@ __device__ int trace_vpacket_volley(const DeviceProblem &P, const Packet &p, Rng
 }
 
 // ---- packet_propagation (classic/packet_propagation.py:52-318)
-template <bool FULL, bool VPK, bool TRACK>
+// FT: full r-packet tracking -- one event_log.hpp row per trace_packet outcome (ev_ws: the wave's append state in LDS)
+template <bool FULL, bool VPK, bool TRACK, bool FT = false>
 __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, double *lds_J, double *lds_nubar, double *jb,
-                             double *ed, LaneCounters &cn)
+                             double *ed, LaneCounters &cn, volatile int *ev_ws = nullptr)
 {
     const double t = P.t_exp;
     Packet p;
@@ -356,6 +358,7 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
     }
     if (VPK) { if ((err = trace_vpacket_volley<FULL>(P, p, rng, i, vseq, cn))) return err; }
     if (TRACK) trk.boundary_buffer += 1;
+    int n_ev = 0;
 
     while (p.status == ST_IN_PROCESS) {
         double velocity = p.r / t;
@@ -366,6 +369,9 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
         int type, delta;
         if ((err = trace_packet<FULL>(P, p, rng, chi_e, jb, ed, distance, type, delta, cn))) return err;
         move_r_packet<FULL>(P, p, distance, lds_J, lds_nubar);
+        double ev_nu = 0.0, ev_mu = 0.0, ev_e = 0.0;
+        int ev_shell = 0, ev_line = 0;
+        if (FT) { ev_nu = p.nu; ev_mu = p.mu; ev_e = p.energy; ev_shell = p.shell; ev_line = p.next_line_id; }
         if (type == IT_BOUNDARY) {
             if (TRACK) trk.boundary_buffer += 1;
             cross_shell(p.shell, p.status, delta, P.n_shells);
@@ -395,6 +401,13 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
                 trk.interaction_type = IT_ESCATTERING;
             }
         }
+        if (FT) {  // one append site for the three outcomes
+            const bool bnd = type == IT_BOUNDARY;
+            event_log_append(P.evlog, ev_ws, i, n_ev, type, p.status, ev_shell, bnd ? ev_shell + delta : ev_shell, p.r, ev_nu,
+                             ev_mu, ev_e, p.nu, p.mu, p.energy, type == IT_LINE ? ev_line : -1,
+                             type == IT_LINE ? p.next_line_id - 1 : -1);
+            ++n_ev;
+        }
         // one shared call site for the volley after a line or electron-scattering interaction: lanes of both kinds trace
         // their v-packets together instead of serialising two inlined copies of the volley
         if (VPK && type != IT_BOUNDARY) { if ((err = trace_vpacket_volley<FULL>(P, p, rng, i, vseq, cn))) return err; }
@@ -402,6 +415,7 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
     // set_packet_collection_output (modes/montecarlo_transport.py:70-90)
     P.out_nu[i] = p.nu;
     P.out_e[i] = (p.status == ST_REABSORBED) ? -p.energy : p.energy;
+    if (FT) P.evlog.counts[i] = n_ev;
     if (TRACK) {
         P.li_radius[i] = trk.radius; P.li_nu[i] = trk.nu; P.li_energy[i] = trk.energy;
         P.li_before_nu[i] = trk.before_nu; P.li_before_mu[i] = trk.before_mu; P.li_before_energy[i] = trk.before_energy;
@@ -419,12 +433,15 @@ __device__ __forceinline__ int xcc_id()
     return (int)(__builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11)) & 0xf);
 }
 
-template <bool FULL, bool VPK, bool TRACK>
+template <bool FULL, bool VPK, bool TRACK, bool FT = false>
 __global__ void __launch_bounds__(256) propagate_lane_kernel(DeviceProblem P)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *lds_J = lds, *lds_nubar = lds + P.n_shells;
     for (int s = threadIdx.x; s < 2 * P.n_shells; s += blockDim.x) lds[s] = 0.0;
+    // FT: after J / nu_bar, two ints per wave (the launch adds 8 * 4 bytes of LDS)
+    volatile int *ev_ws = FT ? reinterpret_cast<volatile int *>(lds + 2 * P.n_shells) + 2 * (threadIdx.x >> 6) : nullptr;
+    if (FT && (threadIdx.x & 63) == 0) event_log_wave_init(ev_ws);
     __syncthreads();
 
     const long long n_threads = (long long)gridDim.x * blockDim.x;
@@ -439,7 +456,7 @@ __global__ void __launch_bounds__(256) propagate_lane_kernel(DeviceProblem P)
     unsigned long long draws = 0;
     for (long long i = gtid; i < P.n_packets; i += n_threads) {
         rng.seed(state, P.seeds[i]);
-        int err = propagate_one<FULL, VPK, TRACK>(P, i, rng, lds_J, lds_nubar, jb, ed, cn);
+        int err = propagate_one<FULL, VPK, TRACK, FT>(P, i, rng, lds_J, lds_nubar, jb, ed, cn, ev_ws);
         draws += (unsigned long long)rng.draws;
         if (err) {
             long long prev = atomicMin(&P.first_error[0], i);
@@ -449,6 +466,7 @@ __global__ void __launch_bounds__(256) propagate_lane_kernel(DeviceProblem P)
         }
     }
     __syncthreads();
+    if (FT) event_log_wave_close(P.evlog, ev_ws);
     for (int s = threadIdx.x; s < P.n_shells; s += blockDim.x) {
         if (lds_J[s] != 0.0) atomic_add_f64(&P.J[s], lds_J[s]);
         if (lds_nubar[s] != 0.0) atomic_add_f64(&P.nubar[s], lds_nubar[s]);

@@ -25,6 +25,7 @@
 #include "propagate_group.hpp"
 #include "estimator_log.hpp"
 #include "walk_tables.hpp"
+#include "event_log.hpp"
 
 namespace mc {
 
@@ -804,9 +805,13 @@ __device__ __forceinline__ int vp_screen_step(const GroupArgs &P, Draw &&draw, i
 // a trace's record to the chunk of its shell (one LDS atomic on the shell's fill), so that every chunk of the log holds records of ONE shell and the estimator passes
 // start with the partition by bin: the pass that grouped the log by shell (a full read and write of the log: 21 of the 87 ms of passes per 2e9 records,
 // profiles/r04_estimator_partition.txt) is gone.
-template <bool FULL, bool TRACK, int G, bool VPK, bool LS = false, bool XWALK = true, int WPE = (VPK ? 3 : 4), int NT = 0, bool SL = false>
+// FT: full r-packet tracking (event_log.hpp) -- one row per trace outcome, the row's ordinal from trk_count + trk_boundary (which travel
+// with the lane through suspensions, epochs and drain compaction); needs TRACK
+template <bool FULL, bool TRACK, int G, bool VPK, bool LS = false, bool XWALK = true, int WPE = (VPK ? 3 : 4), int NT = 0, bool SL = false,
+          bool FT = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) propagate_wave_kernel(WaveHot H, const WaveCold *__restrict__ W)
 {
+    static_assert(!FT || TRACK, "the full tracking counts rows with the last-interaction tracker's counters");
     static_assert(NT == 0 || (LS && !VPK && !FULL), "the interleaved sweep table is read by the lane sweeps only");
     static_assert(!SL || !VPK, "the shell-sorted log is built for the instantiations without v-packets");
     static_assert(NT != 2 || WPE != 3, "aligned runs are eight lines long");
@@ -858,6 +863,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     bool vq_fresh = false;  // volley queue: this lane's round was requested in THIS launch (its results come with the next one)
     int trk_count = 0, trk_boundary = 0;  // interactions_count, boundary crossings since the last interaction
     bool trk_any = false;
+    // FT: the wave's open chunk of the event-row pool (wave-uniform; closed when the wave leaves the launch) and this lane's row of the pass
+    int ev_chunk = -1;  // -1: none yet; -2: the pool is empty
+    unsigned ev_used = 0;
+    bool ev_row = false;
+    int ev_type = 0, ev_shell = 0, ev_after = 0, ev_absorb = -1, ev_emit = -1;
+    double ev_bnu = 0.0, ev_bmu = 0.0, ev_be = 0.0;
     bool exhausted = false;  // wave-uniform: the chunk has no more packets to reserve
     long long res_next = 0, res_end = 0;  // wave-uniform: the block of packets this wave has reserved and not yet started
     int q_head = 0, q_tail = 0;  // wave-uniform: queue of prepared traces
@@ -1173,6 +1184,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             }
             if (type == IT_BOUNDARY) {
                 if (TRACK) trk_boundary += 1;
+                if (FT) {
+                    ev_row = true; ev_type = IT_BOUNDARY; ev_shell = p.shell; ev_after = p.shell + ((pflags >> 1) & 3) - 1;
+                    ev_bnu = p.nu; ev_bmu = p.mu; ev_be = p.energy; ev_absorb = -1; ev_emit = -1;
+                }
                 cross_shell(p.shell, p.status, ((pflags >> 1) & 3) - 1, P.n_shells);
             } else {
                 interacted = true;
@@ -1504,6 +1519,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     rec.shell = p.shell; rec.type = type; rec.absorb = absorb_id; rec.emit = emit_id;
                     rec.count = trk_count; rec.valid = 1;
                     gstore(reinterpret_cast<TrackerRecord *>(W->D.li_rec) + (chunk_first + pkt), rec);
+                    if (FT) {
+                        ev_row = true; ev_type = type; ev_shell = p.shell; ev_after = p.shell;
+                        ev_bnu = rec.before_nu; ev_bmu = rec.before_mu; ev_be = rec.before_energy; ev_absorb = absorb_id; ev_emit = emit_id;
+                    }
                 }
             }
             state = WS_NEED_TRACE;
@@ -1512,6 +1531,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             if (err || p.status != ST_IN_PROCESS) {
                 const long long i = chunk_first + pkt;
                 const DeviceProblem *C = &W->D;
+                if (FT) glob(C->evlog.counts)[i] = trk_count + trk_boundary;  // (rows written for the packet, also when it failed)
                 if (err) {
                     gatomic_min_i64(&C->first_error[0], i);
                     glob(C->out_nu)[i] = (double)err;
@@ -1529,6 +1549,44 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                 }
                 state = WS_NEED_PACKET;
             }
+        }
+        // ---- full tracking: the rows of this pass's finished events, ranked inside the wave's open chunk (the wave is converged here)
+        if (FT) {
+            const unsigned long long m = __ballot(ev_row);
+            if (m) {
+                const EventLog &L = W->D.evlog;
+                const unsigned n = (unsigned)__popcll(m);
+                const unsigned rank = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+                const unsigned room = ev_chunk >= 0 ? L.chunk_rows - ev_used : 0u;
+                int fresh = -2;
+                if (n > room && ev_chunk != -2) {
+                    unsigned c = 0;
+                    if (lane == 0) {
+                        if (ev_chunk >= 0) glob(L.chunk_fill)[ev_chunk] = L.chunk_rows;
+                        c = gatomic_add_u32(L.pool_next, 1u);
+                    }
+                    c = (unsigned)__builtin_amdgcn_readfirstlane((int)c);
+                    fresh = c < L.n_chunks ? (int)c : -2;
+                }
+                long long slot = -1;
+                if (rank < room) slot = (long long)ev_chunk * L.chunk_rows + ev_used + rank;
+                else if (fresh >= 0) slot = (long long)fresh * L.chunk_rows + (rank - room);
+                if (ev_row && slot >= 0) {
+                    double2 *d = reinterpret_cast<double2 *>(L.rows + slot);
+                    d[0] = make_double2(p.r, ev_bnu);
+                    d[1] = make_double2(ev_bmu, ev_be);
+                    d[2] = make_double2(p.nu, p.mu);
+                    d[3] = make_double2(p.energy, __longlong_as_double(chunk_first + pkt));
+                    int4 *q = reinterpret_cast<int4 *>(d + 4);
+                    q[0] = make_int4(trk_count + trk_boundary - 1, ev_shell, ev_after, ev_absorb);
+                    q[1] = make_int4(ev_emit, ev_type | (p.status << 8), 0, 0);
+                }
+                const unsigned long long lost = __ballot(ev_row && slot < 0);
+                if (lane == 0 && lost) gatomic_add_u64(L.dropped, (unsigned long long)__popcll(lost));
+                if (n > room) { ev_chunk = fresh; ev_used = fresh >= 0 ? n - room : 0u; }
+                else ev_used += n;
+            }
+            ev_row = false;
         }
         TMC_SEC(3)
         // ---- fetch packets (one global atomic per wave and pass)
@@ -2141,6 +2199,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     }
 
     if (!SL && lane == 0 && W->log.region_capacity > 0 && log_chunk >= 0) glob(W->log.region_count)[log_chunk] = min(log_used, W->log.region_capacity);
+    if (FT && lane == 0 && ev_chunk >= 0) glob(W->D.evlog.chunk_fill)[ev_chunk] = ev_used;
     if (SL && W->log.region_capacity > 0)
         for (int s = lane; s < H.n_shells; s += 64)
             if (lds_lchunk[s] >= 0) glob(W->log.region_count)[lds_lchunk[s]] = min(lds_lused[s], W->log.region_capacity);

@@ -22,6 +22,7 @@
 #include "../../include/tardis_mc.h"
 #include "mc_device.hpp"
 #include "propagate_lane.hpp"
+#include "event_log.hpp"
 #include "propagate_group.hpp"
 #include "estimator_log.hpp"
 #include "estimator_partition.hpp"
@@ -179,6 +180,15 @@ struct TardisMcContext {
     DevBuf vlog_count, vlog_packet, vlog_seq, vlog_nu, vlog_energy, vlog_mu, vlog_r;
     long long vlog_capacity = 0;
     bool vlog_capacity_user = false;  // set through the vpacket_log_capacity option (otherwise sized per propagate call)
+    // full r-packet tracking (option track_full, event_log.hpp): runs on the lane kernel; the row pool, its chunk fills, {pool_next, dropped},
+    // the per-packet counts, and for tardis_mc_get_event_log the offsets, the tile sums of their scan and the packet-major columns
+    bool track_full = false;
+    long long evlog_capacity = 0;                    // option event_log_capacity: rows (0: automatic, 32 per packet)
+    long long evlog_max_bytes = 16LL << 30;          // option event_log_max_bytes: the bound on the log's device memory
+    DevBuf ev_rows, ev_fill, ev_state, ev_counts, ev_offsets, ev_tiles, ev_cols;
+    bool ev_valid = false;                           // the last propagate call wrote an event log
+    long long ev_packets = 0, ev_capacity = 0, ev_slots = 0;
+    unsigned ev_chunk_rows = 128, ev_n_chunks = 0;
     // scratch
     DevBuf rng_state, counters, first_error, next_packet, seeded_states, problem_dev;
     mc::DeviceProblem problem_host{};
@@ -693,6 +703,7 @@ mc::DeviceProblem make_device_problem(TardisMcContext *ctx)
         for (int k = 0; k < 5; ++k) *g[k] = ctx->li_i64[k].as<long long>();
         P.li_rec = ctx->li_rec.as<uint4>();
     }
+    if (ctx->track_full) P.li_rec = ctx->li_rec.as<uint4>();  // (the tracked wave kernel counts rows with the tracker, TRACK on)
     P.n_shells = ctx->n_shells;
     P.r_inner = ctx->r_inner.as<double>(); P.r_outer = ctx->r_outer.as<double>();
     P.t_exp = ctx->t_exp;
@@ -741,10 +752,58 @@ mc::DeviceProblem make_device_problem(TardisMcContext *ctx)
 template <bool FULL, bool VPK>
 void launch_lane(TardisMcContext *ctx, const mc::DeviceProblem &P, int blocks, size_t lds)
 {
+    if (P.evlog.rows) {  // full r-packet tracking: 8 ints of LDS per workgroup for the waves' append state
+        if (ctx->track)
+            hipLaunchKernelGGL((mc::propagate_lane_kernel<FULL, VPK, true, true>), dim3(blocks), dim3(256), lds + 32, ctx->stream, P);
+        else
+            hipLaunchKernelGGL((mc::propagate_lane_kernel<FULL, VPK, false, true>), dim3(blocks), dim3(256), lds + 32, ctx->stream, P);
+        return;
+    }
     if (ctx->track)
         hipLaunchKernelGGL((mc::propagate_lane_kernel<FULL, VPK, true>), dim3(blocks), dim3(256), lds, ctx->stream, P);
     else
         hipLaunchKernelGGL((mc::propagate_lane_kernel<FULL, VPK, false>), dim3(blocks), dim3(256), lds, ctx->stream, P);
+}
+
+// Full r-packet tracking: size the row pool of this call (rows the caller asked for, plus one chunk per wave for the
+// partly filled last chunks), bound its device memory, clear the counts and the chunk fills, and point P at it.
+int setup_event_log(TardisMcContext *ctx, mc::DeviceProblem &P, long long n_waves)
+{
+    const long long n = ctx->n_packets;
+    const long long row_bytes = (long long)sizeof(mc::EventRow), col_bytes = 14 * 8;  // pool row; the fourteen int64 / float64 columns
+    long long cap = ctx->evlog_capacity;
+    const long long fixed = n * (4 + 8) + 64;  // counts, offsets
+    if (cap <= 0) {  // automatic: 32 rows per packet, within the bound (a re-run with the exact count fixes an overflow)
+        const long long fit = (ctx->evlog_max_bytes - fixed) / (row_bytes + col_bytes) - n_waves * (long long)ctx->ev_chunk_rows;
+        cap = std::max<long long>(1024, std::min<long long>(32 * std::max<long long>(n, 1), fit));
+    }
+    const long long chunks = (cap + ctx->ev_chunk_rows - 1) / ctx->ev_chunk_rows + n_waves;
+    const long long slots = chunks * (long long)ctx->ev_chunk_rows;
+    const long long need = slots * row_bytes + cap * col_bytes + fixed;
+    if (need > ctx->evlog_max_bytes || chunks >= (1LL << 31))
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT,
+                    "full r-packet tracking: an event log of %lld rows for %lld packets needs %.2f GiB of device memory, more than the "
+                    "bound of %.2f GiB (option event_log_max_bytes); propagate fewer packets per call or raise the bound",
+                    cap, n, need / 1073741824.0, ctx->evlog_max_bytes / 1073741824.0);
+    HIP_TRY(ctx, ctx->ev_rows.ensure((size_t)slots * row_bytes));
+    HIP_TRY(ctx, ctx->ev_fill.ensure((size_t)chunks * sizeof(unsigned)));
+    HIP_TRY(ctx, ctx->ev_state.ensure(2 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, ctx->ev_counts.ensure((size_t)std::max<long long>(n, 1) * sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ev_fill.p, 0, (size_t)chunks * sizeof(unsigned), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ev_state.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ev_counts.p, 0, (size_t)std::max<long long>(n, 1) * sizeof(int), ctx->stream));
+    P.evlog.rows = ctx->ev_rows.as<mc::EventRow>();
+    P.evlog.chunk_fill = ctx->ev_fill.as<unsigned>();
+    P.evlog.pool_next = ctx->ev_state.as<unsigned>();
+    P.evlog.dropped = ctx->ev_state.as<unsigned long long>() + 1;
+    P.evlog.counts = ctx->ev_counts.as<int>();
+    P.evlog.chunk_rows = ctx->ev_chunk_rows;
+    P.evlog.n_chunks = (unsigned)chunks;
+    ctx->ev_packets = n;
+    ctx->ev_capacity = cap;
+    ctx->ev_slots = slots;
+    ctx->ev_n_chunks = (unsigned)chunks;
+    return TARDIS_MC_OK;
 }
 
 }  // namespace
@@ -853,6 +912,9 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "track_last_interaction") ctx->track = value != 0;
     else if (n == "estimator_copies") { ctx->est_copies = std::max(1, std::min(8, (int)value)); ctx->est_valid = false; }
     else if (n == "vpacket_log_capacity") { ctx->vlog_capacity = value; ctx->vlog_capacity_user = value > 0; }
+    else if (n == "track_full") ctx->track_full = value != 0;
+    else if (n == "event_log_capacity") ctx->evlog_capacity = std::max<long long>(0, value);
+    else if (n == "event_log_max_bytes") ctx->evlog_max_bytes = std::max<long long>(1LL << 20, value);
     else if (n == "debug_flags") ctx->debug_flags = (int)value;
     else if (n == "drain_split") ctx->drain_split = value ? 1 : 0;
     else if (n == "drain_compact") ctx->drain_compact = (int)std::max<long long>(0, std::min<long long>(48, value));
@@ -1454,6 +1516,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         return fail(ctx, TARDIS_MC_ERR_STATE, "set_geometry/set_opacity/set_config/set_packets must precede propagate");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->compactions = 0;
+    ctx->ev_valid = false;
     const bool rs_armed = ctx->rs.armed;  // (tardis_mc_stream_results holds for one call)
     ctx->rs.armed = false; ctx->rs.valid = false; ctx->rs.upto = 0; ctx->rs.n_late = 0;
     const int tune_pending = ctx->ls_tune.pending;  // (the lane-sweep tuner: whether the previous propagate call was one of its timed ones: 2 * instantiation + sample)
@@ -1473,6 +1536,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         for (auto &b : ctx->li_i64) HIP_TRY(ctx, b.ensure(P * sizeof(long long)));
         HIP_TRY(ctx, ctx->li_rec.ensure(P * 64));
     }
+    if (ctx->track_full) HIP_TRY(ctx, ctx->li_rec.ensure((size_t)std::max<long long>(ctx->n_packets, 1) * 64));
     // v-packet log buffers
     if (c.enable_vpacket_tracking && vpk) {
         // (sized for the current call: the engine is cached per process, a later, larger run must not inherit a smaller log)
@@ -1562,6 +1626,15 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     // v-packets there is nothing to queue
     if (variant == 4 && !vpk) variant = prefer_lane_sweeps ? 3 : 2;
     if (ctx->prob_negative && variant == 4) variant = 1;
+    // full r-packet tracking: the wave-owner kernel with group sweeps (variant 2, its default launch shape) where it can run the call --
+    // sorted lines, monotone probabilities, no surviving v-packets, at most 32 v-packets, the compact walk tables, no cross-check flags --
+    // else the lane kernel (variants 1, 3 and 4 are not instrumented)
+    if (ctx->track_full) {
+        const bool wave_ok = ctx->lines_sorted && !ctx->prob_negative && !(vpk && (c.number_of_vpackets > 32 || c.survival_probability > 0.0)) &&
+                             (c.line_interaction_type == 0 || ctx->have_walk_tables) &&
+                             !(ctx->debug_flags & (128 | 8192 | 1048576 | mc::WV_DBG_FLAGS)) && ctx->n_packets < (1LL << 31);
+        variant = (wave_ok && variant != 0) ? 2 : 0;
+    }
     const bool cooperative = ctx->lines_sorted && (variant == 1 || variant == 2 || variant == 3 || variant == 4) && (!vpk || c.number_of_vpackets <= 32);
     ctx->last_variant = cooperative ? ((variant == 3 && c.enable_full_relativity) ? 2 : variant) : 0;
     if (screen_on && !cooperative) screen_on = false;  // (the lane kernel traces line by line)
@@ -1592,7 +1665,11 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         HIP_TRY(ctx, ctx->rng_state.ensure((size_t)blocks * 256 * mc::MT_N * sizeof(uint32_t)));
         mc::DeviceProblem P = make_device_problem(ctx);
         const size_t lds = 2 * (size_t)ctx->n_shells * sizeof(double);
-        if (lds > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
+        if (lds + (ctx->track_full ? 32 : 0) > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
+        if (ctx->track_full) {
+            rc = setup_event_log(ctx, P, (long long)blocks * 4);
+            if (rc) return rc;
+        }
         HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
         ctx->chunks_timed = 0;
         if (ctx->n_packets > 0) {
@@ -1683,7 +1760,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
             // G = 8, without the cross-check walks; option vpk_wide_registers 0 keeps the 168-VGPR one)
             // Measured (profiles/r05_vpk_wide_registers.txt): 3727-3766 vs 4442-4450 ms per 1e7 packets of the configs[4] shape (-16 %).  Option 2 forces
             // it (then eight waves per CU whatever the LDS allows), 0 keeps the 168-VGPR instantiation.
-            bool wide = vpk && !xwalk && (lane_sweep || GW == 16 || GW == 8) &&
+            bool wide = vpk && !xwalk && !ctx->track_full && (lane_sweep || GW == 16 || GW == 8) &&
                         ((ctx->vpk_wide_registers == 1 && wave_waves_per_cu <= 8) || ctx->vpk_wide_registers == 2);
 #define TMC_PICKWIDE(G_) (full ? (trk ? mc::propagate_wave_kernel<true, true, G_, true, false, false, 2> : mc::propagate_wave_kernel<true, false, G_, true, false, false, 2>) \
                                : (trk ? mc::propagate_wave_kernel<false, true, G_, true, false, false, 2> : mc::propagate_wave_kernel<false, false, G_, true, false, false, 2>))
@@ -1772,6 +1849,10 @@ int tardis_mc_propagate(TardisMcContext *ctx)
             const bool cu_split = ctx->pass_cus > 0 && !vq && ctx->log_sets != 1 && cus == 32 * n_xcd && n >= 30000000LL;
             const int cus_prop = cu_split ? cus - n_xcd * ctx->pass_cus : cus;
             const int waves = (int)std::max<long long>(1, std::min<long long>((n + 63) / 64, (long long)cus_prop * std::min(wave_waves_per_cu, wide ? 8 : (ls3 ? 12 : 16)) * (vq ? ctx->vq_oversubscribe : 1)));
+            if (ctx->track_full) {  // (a wave leaves a partly filled chunk behind at every launch it takes part in: room for four launches)
+                rc = setup_event_log(ctx, ctx->problem_host, 4LL * waves);
+                if (rc) return rc;
+            }
             // ---- the line-visit log (estimator_log.hpp): two buffer sets, one region per wave; an epoch ends when the regions
             // are full.  Sized for the whole call when that fits log_capacity (1.2x the traces per packet measured in the last
             // call, 128 per packet before anything was measured), else log_capacity.
@@ -1790,6 +1871,12 @@ int tardis_mc_propagate(TardisMcContext *ctx)
                 if (ls3) kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 3, 0, true> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 3, 0, true>;
                 else kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 4, 1, true> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 4, 1, true>;
                 wave_lds = mc::wave_kernel_lds_bytes<false, false, true, true>(ctx->n_shells);
+            }
+            if (ctx->track_full) {  // the tracked instantiations: group sweeps of 16 lanes, compact walks, default register budget
+                kw = full ? (vpk ? mc::propagate_wave_kernel<true, true, 16, true, false, false, 3, 0, false, true>
+                                 : mc::propagate_wave_kernel<true, true, 16, false, false, false, 4, 0, false, true>)
+                          : (vpk ? mc::propagate_wave_kernel<false, true, 16, true, false, false, 3, 0, false, true>
+                                 : mc::propagate_wave_kernel<false, true, 16, false, false, false, 4, 0, false, true>);
             }
             long long log_capacity = ctx->log_capacity;
             // One log set or two.  Two let the passes of an epoch run on a second stream beside the next launch -- but they do not fit beside sixteen resident waves per CU,
@@ -2446,6 +2533,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         HIP_TRY(ctx, hipEventRecord(ctx->ev_tune[1], ctx->stream));
         ctx->ls_tune.pending = tune_slot;
     }
+    ctx->ev_valid = ctx->track_full;  // (a call that failed half-way leaves no event log to read)
     return TARDIS_MC_OK;
 }
 
@@ -2690,6 +2778,66 @@ int tardis_mc_get_results(TardisMcContext *ctx, TardisMcResult *res)
         }
     }
     return res->error_code;
+}
+
+int tardis_mc_get_event_log(TardisMcContext *ctx, TardisMcEventLog *log)
+{
+    if (!ctx || !log) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    log->count = 0;
+    log->dropped = 0;
+    if (!ctx->ev_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "no event log: the last tardis_mc_propagate ran without the option track_full");
+    if (ctx->n_packets != ctx->ev_packets)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "no event log: the resident packets were replaced after the tracked tardis_mc_propagate");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    {   // a call in which a packet failed has no complete log (that packet's rows end at the error)
+        long long fe = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&fe, ctx->first_error.p, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (fe != 0x7fffffffffffffffLL)
+            return fail(ctx, TARDIS_MC_ERR_STATE, "no event log: packet %lld of the tracked tardis_mc_propagate failed", fe);
+    }
+    const long long n = ctx->ev_packets;
+    const long long tiles = std::max<long long>(1, (n + mc::EV_SCAN_TILE - 1) / mc::EV_SCAN_TILE);
+    HIP_TRY(ctx, ctx->ev_offsets.ensure((size_t)(n + 1) * sizeof(long long)));
+    HIP_TRY(ctx, ctx->ev_tiles.ensure((size_t)tiles * sizeof(long long)));
+    long long *offsets = ctx->ev_offsets.as<long long>();
+    hipLaunchKernelGGL(mc::event_scan_tiles_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->ev_counts.as<int>(), n,
+                       ctx->ev_tiles.as<long long>());
+    hipLaunchKernelGGL(mc::event_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->ev_tiles.as<long long>(), tiles, offsets, n);
+    hipLaunchKernelGGL(mc::event_scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->ev_counts.as<int>(), n,
+                       ctx->ev_tiles.as<long long>(), offsets);
+    HIP_TRY(ctx, hipGetLastError());
+    long long total = 0;
+    unsigned long long state[2] = {0, 0};  // {pool_next (low 32 bits), dropped}
+    HIP_TRY(ctx, hipMemcpyAsync(&total, offsets + n, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(state, ctx->ev_state.p, sizeof state, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    log->count = total;
+    log->dropped = (int64_t)state[1];
+    if (log->offsets) HIP_TRY(ctx, hipMemcpyAsync(log->offsets, offsets, (size_t)(n + 1) * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    // the columns only when every row is there and fits the caller's arrays (otherwise: re-run with event_log_capacity = count)
+    if (state[1] == 0 && total > 0 && total <= log->capacity) {
+        HIP_TRY(ctx, ctx->ev_cols.ensure((size_t)total * 14 * 8));
+        long long *ci = ctx->ev_cols.as<long long>();
+        double *cf = reinterpret_cast<double *>(ci + 7 * total);
+        mc::EventColumns col{ci, ci + total, ci + 2 * total, ci + 3 * total, ci + 4 * total, ci + 5 * total, ci + 6 * total,
+                             cf, cf + total, cf + 2 * total, cf + 3 * total, cf + 4 * total, cf + 5 * total, cf + 6 * total};
+        const unsigned used_chunks = std::min<unsigned>((unsigned)(state[0] & 0xffffffffull), ctx->ev_n_chunks);
+        const long long n_slots = (long long)used_chunks * ctx->ev_chunk_rows;
+        const int blocks = (int)std::max<long long>(1, std::min<long long>((n_slots + 255) / 256, 65536));
+        hipLaunchKernelGGL(mc::event_scatter_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ev_rows.as<mc::EventRow>(),
+                           ctx->ev_fill.as<unsigned>(), ctx->ev_chunk_rows, n_slots, offsets, col);
+        HIP_TRY(ctx, hipGetLastError());
+        int64_t *dst_i[7] = {log->event_id, log->interaction_type, log->status, log->shell_id, log->after_shell_id, log->line_absorb_id,
+                             log->line_emit_id};
+        double *dst_f[7] = {log->radius, log->before_nu, log->before_mu, log->before_energy, log->after_nu, log->after_mu, log->after_energy};
+        for (int k = 0; k < 7; ++k) {
+            if (dst_i[k]) HIP_TRY(ctx, hipMemcpyAsync(dst_i[k], ci + k * total, (size_t)total * 8, hipMemcpyDeviceToHost, ctx->stream));
+            if (dst_f[k]) HIP_TRY(ctx, hipMemcpyAsync(dst_f[k], cf + k * total, (size_t)total * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TARDIS_MC_OK;
 }
 
 int tardis_mc_stream_results(TardisMcContext *ctx, const TardisMcResult *dst)

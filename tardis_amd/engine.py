@@ -17,6 +17,16 @@ class MacroAtomError(ValueError):
     """Mirror of tardis.transport.montecarlo.macro_atom.MacroAtomError (macro_atom.py:15)."""
 
 
+class EventLogOverflow(RuntimeError):
+    """The device pool of the full r-packet log was too small for the last call: rows were dropped.  ``rows_needed`` is the
+    exact capacity (option ``event_log_capacity``) with which a re-run of the same call keeps every row."""
+
+    def __init__(self, rows_needed: int, dropped: int):
+        super().__init__(f"full r-packet log overflow: {dropped} of {rows_needed} rows dropped; re-run with "
+                         f"event_log_capacity={rows_needed}")
+        self.rows_needed, self.dropped = int(rows_needed), int(dropped)
+
+
 class Engine:
     def __init__(self, device_id: int = 0):
         self._L = _lib.lib()
@@ -150,8 +160,30 @@ class Engine:
         4 wave + volley queue (v-packets traced by vpacket_trace_kernel between its launches)."""
         return int(self._L.tardis_mc_last_variant(self._h))
 
+    def get_event_log(self) -> st.FullTrackers:
+        """The full r-packet log of the last propagate() (option ``track_full``), as ``state.FullTrackers``.  Raises
+        ``EventLogOverflow`` when the device pool dropped rows (re-run with ``event_log_capacity`` = its ``rows_needed``)."""
+        probe = _abi.TardisMcEventLog()
+        offsets = np.zeros(self.n_packets + 1, dtype=np.int64)
+        probe.offsets = _abi._ip(offsets)
+        self._check(self._L.tardis_mc_get_event_log(self._h, C.byref(probe)), "get_event_log")
+        if probe.dropped:
+            raise EventLogOverflow(probe.count, probe.dropped)
+        n = int(probe.count)
+        cols = {f: np.empty(n) for f in _abi._EV_F64}
+        cols.update({f: np.empty(n, dtype=np.int64) for f in _abi._EV_I64})
+        log = _abi.TardisMcEventLog()
+        log.capacity = n
+        for f in _abi._EV_F64:
+            setattr(log, f, _abi._dp(cols[f]))
+        for f in _abi._EV_I64:
+            setattr(log, f, _abi._ip(cols[f]))
+        self._check(self._L.tardis_mc_get_event_log(self._h, C.byref(log)), "get_event_log")
+        return st.FullTrackers(offsets, cols)
+
     def get_results(self, output_nus=None, output_energies=None, track_last_interaction=True,
-                    want_line_estimators=True, vpacket_log_capacity=None, want_packet_outputs=True, trackers=None) -> _abi.ResultBuffers:
+                    want_line_estimators=True, vpacket_log_capacity=None, want_packet_outputs=True, trackers=None,
+                    track_full=False) -> _abi.ResultBuffers:
         """Copy results out.  Every part is optional: per-packet outputs (`want_packet_outputs`), the last-interaction
         trackers, the [L,S] line estimators -- whatever is not asked for stays on the device (the resident outer-iteration
         path reads the spectrum and the radiation field through packet_spectrum() / radiation_field() instead)."""
@@ -168,6 +200,8 @@ class Engine:
                                  trackers, cap, want_line_estimators, want_packet_outputs)
         rc = self._L.tardis_mc_get_results(self._h, res.ref())
         self._check(rc, "get_results", int(res.struct.first_error_packet))
+        # (track_full: the full r-packet log of the call too -- it must have run with the option track_full)
+        res.full_trackers = self.get_event_log() if track_full else None
         return res
 
     def stream_results(self, output_nus=None, output_energies=None, trackers=None) -> None:
@@ -192,11 +226,13 @@ class Engine:
         return int(a.value), int(b.value)
 
     def run(self, packet_collection, geometry, time_explosion, opacity_state, montecarlo_configuration, spectrum_frequency_grid,
-            number_of_vpackets=None, track_last_interaction=True, vpacket_log_capacity=None) -> _abi.ResultBuffers:
+            number_of_vpackets=None, track_last_interaction=True, vpacket_log_capacity=None,
+            track_full=False) -> _abi.ResultBuffers:
         """The one-shot form of the boundary, `tardis_mc_run` (include/tardis_mc.h): geometry, opacity, configuration and packets in,
         one propagation, results out -- the call a ctypes binding inside `run_classic` makes when nothing is to stay resident
         (modes/classic/solver.py:223-234).  `vpacket_log_capacity`: entries of the caller's v-packet log arrays for THIS call (None:
-        sized like get_results does; the library restores the context's own setting when the call returns, however it ends)."""
+        sized like get_results does; the library restores the context's own setting when the call returns, however it ends).
+        `track_full`: also the full r-packet log, as ``res.full_trackers`` (state.FullTrackers)."""
         mp = _abi.marshal_packets(packet_collection)
         mg = _abi.marshal_geometry(geometry, time_explosion)
         mo = _abi.marshal_opacity(opacity_state)
@@ -211,10 +247,16 @@ class Engine:
         self.results_generation += 1
         self.estimators_generation += 1
         self.packets_generation += 1
-        rc = self._L.tardis_mc_run(self._h, mp.ref(), mg.ref(), mo.ref(), mc.ref(), res.ref())
+        prev_full = self.options.get("track_full", 0)
+        self.set_option("track_full", int(bool(track_full)))
+        try:
+            rc = self._L.tardis_mc_run(self._h, mp.ref(), mg.ref(), mo.ref(), mc.ref(), res.ref())
+        finally:
+            self.set_option("track_full", prev_full)
         self.n_packets, self.n_shells, self.n_lines, self.n_grid = P, S, L, int(mc.struct.n_spectrum_grid)
         self._n_v, self._vpk_log = n_v, log
         self._check(rc, "run", int(res.struct.first_error_packet))
+        res.full_trackers = self.get_event_log() if track_full else None
         self.resident_opacity = opacity_state
         self.results_generation += 1
         self.estimators_generation += 1

@@ -223,3 +223,84 @@ class LastInteractionTrackers:
 
     def __len__(self):
         return len(self.radius)
+
+
+class FullTrackers:
+    """Full r-packet tracking (the reference's ``TrackerFull``, packets/trackers/tracker_full.py), as one CSR table: packet ``p``'s
+    rows -- one per ``trace_packet`` outcome, in order -- are ``[offsets[p], offsets[p + 1])`` of every column.  Column names follow
+    ``LastInteractionTrackers``; ``after_shell_id`` is the shell after the event (``n_shells`` or -1 for a crossing out of the
+    grid), ``status`` the packet's status after it, ``line_absorb_id`` / ``line_emit_id`` are -1 except on LINE rows."""
+
+    F64_FIELDS = ("radius", "before_nu", "before_mu", "before_energy", "after_nu", "after_mu", "after_energy")
+    I64_FIELDS = ("event_id", "interaction_type", "status", "shell_id", "after_shell_id", "line_absorb_id", "line_emit_id")
+    INTERACTION_NAMES = {-1: "NO_INTERACTION", 1: "BOUNDARY", 2: "LINE", 4: "ESCATTERING", 8: "CONTINUUM_PROCESS"}
+    STATUS_NAMES = {0: "IN_PROCESS", 1: "EMITTED", 2: "REABSORBED", 3: "ADIABATIC_COOLING"}
+
+    def __init__(self, offsets, columns: dict | None = None):
+        self.offsets = _i64(offsets)
+        if self.offsets.ndim != 1 or len(self.offsets) < 1 or self.offsets[0] != 0 or np.any(np.diff(self.offsets) < 0):
+            raise ValueError("offsets must be a non-decreasing int64 array starting at 0")
+        n = int(self.offsets[-1])
+        columns = columns or {}
+        for f in self.F64_FIELDS:
+            setattr(self, f, _f64(columns[f]) if f in columns else np.full(n, np.nan))
+        for f in self.I64_FIELDS:
+            setattr(self, f, _i64(columns[f]) if f in columns else np.full(n, -1, dtype=np.int64))
+        for f in self.F64_FIELDS + self.I64_FIELDS:
+            if len(getattr(self, f)) != n:
+                raise ValueError(f"column {f} has {len(getattr(self, f))} rows, offsets say {n}")
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.offsets[-1])
+
+    @property
+    def counts(self) -> np.ndarray:
+        """Rows per packet."""
+        return np.diff(self.offsets)
+
+    @property
+    def packet_id(self) -> np.ndarray:
+        """Packet index of every row."""
+        return np.repeat(np.arange(len(self), dtype=np.int64), self.counts)
+
+    def packet(self, i: int) -> dict:
+        """Views (not copies) of packet ``i``'s rows, column by column."""
+        n = len(self)
+        if not -n <= i < n:
+            raise IndexError(f"packet {i} out of range for {n} packets")
+        i %= n
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        return {f: getattr(self, f)[a:b] for f in self.F64_FIELDS + self.I64_FIELDS}
+
+    def to_dataframe(self):
+        """One row per event, indexed by (packet_id, event_id); interaction_type and status are categoricals with the names and
+        categories of ``MonteCarloTransportState.tracker_last_interaction_df``."""
+        import pandas as pd
+
+        it_dtype = pd.CategoricalDtype(categories=["NO_INTERACTION", "BOUNDARY", "LINE", "ESCATTERING", "CONTINUUM_PROCESS"])
+        st_dtype = pd.CategoricalDtype(categories=["IN_PROCESS", "EMITTED", "REABSORBED", "ADIABATIC_COOLING"])
+        it_codes = {k: it_dtype.categories.get_loc(v) for k, v in self.INTERACTION_NAMES.items()}
+        st_codes = {k: st_dtype.categories.get_loc(v) for k, v in self.STATUS_NAMES.items()}
+
+        def cat(values, codes, dtype):
+            lut = np.full(16, -1, dtype=np.int64)
+            for k, c in codes.items():
+                lut[k + 1] = c  # (-1 -> slot 0)
+            return pd.Categorical.from_codes(lut[values + 1], dtype=dtype)
+
+        index = pd.MultiIndex.from_arrays([self.packet_id, self.event_id], names=["packet_id", "event_id"])
+        return pd.DataFrame(
+            {
+                "interaction_type": cat(self.interaction_type, it_codes, it_dtype),
+                "status": cat(self.status, st_codes, st_dtype),
+                "shell_id": self.shell_id, "after_shell_id": self.after_shell_id, "radius": self.radius,
+                "before_nu": self.before_nu, "before_mu": self.before_mu, "before_energy": self.before_energy,
+                "after_nu": self.after_nu, "after_mu": self.after_mu, "after_energy": self.after_energy,
+                "line_absorb_id": pd.array(self.line_absorb_id, dtype="int64"),
+                "line_emit_id": pd.array(self.line_emit_id, dtype="int64"),
+            },
+            index=index)

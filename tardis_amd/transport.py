@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import state as st
-from .engine import Engine, MacroAtomError, MonteCarloException  # noqa: F401  (re-exported)
+from .engine import Engine, EventLogOverflow, MacroAtomError, MonteCarloException  # noqa: F401  (re-exported)
 
 _engines: dict[int, Engine] = {}
 
@@ -39,17 +39,62 @@ def _fill_trackers(trackers, soa: st.LastInteractionTrackers):
     names = st.LastInteractionTrackers.F64_FIELDS + st.LastInteractionTrackers.I64_FIELDS
     if len(trackers) != len(soa):
         raise ValueError(f"{len(trackers)} trackers for {len(soa)} packets")
-    if len(trackers):
-        # enable_rpacket_tracking makes run_classic pass TrackerFull objects (array-valued fields, one row per event,
-        # packets/trackers/tracker_full.py): the engine records the last interaction only
-        first = trackers[0]
-        if type(first).__name__ == "TrackerFull" or any(np.ndim(getattr(first, n, 0.0)) != 0 for n in names):
-            raise NotImplementedError("full r-packet tracking (TrackerFull, montecarlo.tracking.track_rpacket) is not "
-                                      "implemented by the HIP engine; only TrackerLastInteraction is")
+    # enable_rpacket_tracking makes run_classic pass TrackerFull objects (array-valued fields, one row per event,
+    # packets/trackers/tracker_full.py): they are filled from the full r-packet log (_fill_full_trackers), never from this SoA
+    if _is_full_trackers(trackers):
+        raise NotImplementedError("TrackerFull objects (montecarlo.tracking.track_rpacket) are filled from the engine's full "
+                                  "r-packet log (track_full), not from the last-interaction SoA")
     cols = {n: getattr(soa, n).tolist() for n in names}
     for i, t in enumerate(trackers):
         for n in names:
             setattr(t, n, cols[n][i])
+
+
+def _is_full_trackers(trackers) -> bool:
+    """The reference's list of TrackerFull objects (enable_rpacket_tracking; array-valued fields, one row per event)."""
+    if trackers is None or isinstance(trackers, st.LastInteractionTrackers) or not len(trackers):
+        return False
+    names = st.LastInteractionTrackers.F64_FIELDS + st.LastInteractionTrackers.I64_FIELDS
+    first = trackers[0]
+    return type(first).__name__ == "TrackerFull" or any(np.ndim(getattr(first, n, 0.0)) != 0 for n in names)
+
+
+# attribute names of a TrackerFull-like object -> column of state.FullTrackers (the last-interaction tracker's names for the
+# same quantities map onto the same columns: its `nu` / `mu` / `energy` are the state after the event)
+_FULL_ALIASES = {
+    "r": "radius", "nu": "after_nu", "mu": "after_mu", "energy": "after_energy",
+    "interaction_line_absorb_id": "line_absorb_id", "interaction_line_emit_id": "line_emit_id",
+    "next_shell_id": "after_shell_id",
+}
+# scalar attributes that hold the number of valid rows of the arrays (the reference's finalize shrinks its arrays to it)
+_FULL_COUNT_NAMES = ("interactions_count", "event_count", "num_interactions", "n_events", "count")
+
+
+def _fill_full_trackers(trackers, log: st.FullTrackers):
+    """Fill the reference's per-packet TrackerFull-like objects in place from the engine's full r-packet log: every array-valued
+    attribute is replaced, by name, with the packet's rows (so its length is the packet's row count, as after the reference's
+    finalize), and a scalar count attribute is set to that count.  An array attribute the engine does not record raises
+    NotImplementedError naming it."""
+    if len(trackers) != len(log):
+        raise ValueError(f"{len(trackers)} trackers for {len(log)} packets")
+    columns = set(st.FullTrackers.F64_FIELDS + st.FullTrackers.I64_FIELDS)
+    for i, t in enumerate(trackers):
+        rows = log.packet(i)
+        n = len(rows["event_id"])
+        for name in dir(t):
+            if name.startswith("_"):
+                continue
+            value = getattr(t, name, None)
+            if callable(value) or np.ndim(value) == 0:
+                if name in _FULL_COUNT_NAMES and isinstance(value, (int, np.integer)):
+                    setattr(t, name, n)
+                continue
+            col = _FULL_ALIASES.get(name, name)
+            if col not in columns:
+                raise NotImplementedError(f"TrackerFull attribute {name!r} is not recorded by the HIP engine's full r-packet log "
+                                          f"(it records {', '.join(sorted(columns))})")
+            dtype = value.dtype if isinstance(value, np.ndarray) else rows[col].dtype
+            setattr(t, name, np.array(rows[col], dtype=dtype))
 
 
 class _PacketProgress:
@@ -120,13 +165,17 @@ class _PacketProgress:
 def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, time_explosion: float,
                                        opacity_state_numba, montecarlo_configuration, spectrum_frequency_grid,
                                        trackers, number_of_vpackets: int, show_progress_bars: bool = False,
-                                       packet_propagation_function=None, *, engine: Engine | None = None):
+                                       packet_propagation_function=None, *, engine: Engine | None = None,
+                                       track_full: bool = False):
     """Run the classic (line + electron scattering) Monte Carlo transport on the GPU.
 
     Returns ``(v_packets_energy_hist, vpacket_tracker, estimators_bulk, estimators_line)`` and mutates
     ``packet_collection.output_nus / output_energies`` and ``trackers`` in place, exactly like the reference.
     ``packet_propagation_function`` is accepted for signature compatibility; only the classic homologous mode
     is implemented by the engine (anything else must stay on the reference path).
+    Full r-packet tracking: ``trackers`` a list of the reference's ``TrackerFull`` objects (enable_rpacket_tracking) are filled
+    with every event of their packet; ``track_full=True`` records the same log beside last-interaction trackers.  Either way the
+    log is left in ``montecarlo_transport_with_vpackets.last_event_log`` (``state.FullTrackers``).
     """
     if packet_propagation_function is not None:
         name = getattr(packet_propagation_function, "__name__", "")
@@ -137,15 +186,20 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
     eng.set_geometry(geometry_state_numba, time_explosion)
     eng.set_opacity(opacity_state_numba)
     eng.set_config(montecarlo_configuration, spectrum_frequency_grid, number_of_vpackets)
-    track = trackers is not None
+    # full r-packet tracking: TrackerFull-like trackers, or `track_full` (the caller reads montecarlo_transport_with_vpackets.last_event_log)
+    full = _is_full_trackers(trackers)
+    track_full = full or bool(track_full)
+    track = trackers is not None and not full
     eng.set_option("track_last_interaction", int(track))
+    eng.set_option("track_full", int(track_full))
     eng.set_packets(packet_collection)
     out_nus, out_en = packet_collection.output_nus, packet_collection.output_energies
     in_place = all(isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous for a in (out_nus, out_en))
-    vlog_capacity = None
+    vlog_capacity = evlog_capacity = None
+    event_log = None
     progress = _PacketProgress(eng, show_progress_bars)  # (one bar per call, whatever the number of attempts)
     try:
-        for _attempt in range(2):
+        for _attempt in range(3):
             eng.reset_estimators()
             if in_place and _attempt == 0:  # (the caller's arrays are filled while the call runs, launch by launch)
                 eng.stream_results(out_nus, out_en, trackers if isinstance(trackers, st.LastInteractionTrackers) and len(trackers) == eng.n_packets else None)
@@ -153,23 +207,40 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
                 eng.propagate()
                 eng.synchronize()
             res = eng.get_results(out_nus if in_place else None, out_en if in_place else None, track_last_interaction=track,
-                                  vpacket_log_capacity=vlog_capacity, trackers=trackers)
-            if res.vpacket_log_count <= len(res.vpacket_nus):
+                                  vpacket_log_capacity=vlog_capacity, trackers=trackers if track else None)
+            retry = False
+            if res.vpacket_log_count > len(res.vpacket_nus):
+                # The v-packet log was sized from a guess and overflowed (the device then drops entries): the run is
+                # deterministic, so repeat it with the capacity it asked for -- the reference returns every v-packet.
+                vlog_capacity = res.vpacket_log_count
+                eng.set_option("vpacket_log_capacity", vlog_capacity)
+                retry = True
+            if track_full:
+                try:
+                    event_log = eng.get_event_log()
+                except EventLogOverflow as e:  # (the same for the full r-packet log: its counts are exact)
+                    # (the pool also holds each wave's partly filled last chunk per launch: a second overflow doubles the room)
+                    evlog_capacity = e.rows_needed if evlog_capacity is None else max(e.rows_needed, 2 * evlog_capacity)
+                    eng.set_option("event_log_capacity", evlog_capacity)
+                    retry = True
+            if not retry:
                 break
-            # The v-packet log was sized from a guess and overflowed (the device then drops entries): the run is
-            # deterministic, so repeat it with the capacity it asked for -- the reference returns every v-packet.
-            vlog_capacity = res.vpacket_log_count
-            eng.set_option("vpacket_log_capacity", vlog_capacity)
         else:
-            raise RuntimeError("v-packet log overflow persisted after resizing")
+            raise RuntimeError("v-packet / full r-packet log overflow persisted after resizing")
     finally:
         progress.close()
         if vlog_capacity is not None:
             eng.set_option("vpacket_log_capacity", 0)  # back to automatic sizing, whichever way the call ended
+        if evlog_capacity is not None:
+            eng.set_option("event_log_capacity", 0)
+        if track_full:
+            eng.set_option("track_full", 0)
     if not in_place:
         packet_collection.output_nus[:] = res.output_nus
         packet_collection.output_energies[:] = res.output_energies
-    if track:
+    if full:
+        _fill_full_trackers(trackers, event_log)
+    elif track:
         if res.trackers is trackers:
             pass  # (the library wrote into the caller's arrays)
         elif isinstance(trackers, st.LastInteractionTrackers):
@@ -193,6 +264,7 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
                                   cfg.VPACKET_SPAWN_END_FREQUENCY, -1, 1)
     montecarlo_transport_with_vpackets.last_counters = res.counters
     montecarlo_transport_with_vpackets.last_kernel_ms = eng.last_propagate_ms()
+    montecarlo_transport_with_vpackets.last_event_log = event_log
     return res.v_packets_energy_hist, vt, estimators_bulk, estimators_line
 
 
@@ -297,6 +369,7 @@ class MonteCarloTransportState:
         self.estimators_line = None
         self.vpacket_tracker = None
         self._tracker_last_interaction = None
+        self.tracker_full = None      # state.FullTrackers of a run with enable_rpacket_tracking
         self.tracker_full_df = None
         self.enable_full_relativity = False
         self.virt_logging = False
@@ -398,7 +471,7 @@ class MCTransportSolverHIP:
 
     def __init__(self, spectrum_frequency_grid, montecarlo_configuration=None, line_interaction_type="macroatom",
                  enable_full_relativity=False, device_id=None, nthreads=1, resident=False, reuse_opacity=True,
-                 enable_last_interaction_tracking=True, engine: Engine | None = None):
+                 enable_last_interaction_tracking=True, engine: Engine | None = None, enable_rpacket_tracking=False):
         self.spectrum_frequency_grid = np.ascontiguousarray(spectrum_frequency_grid, dtype=np.float64)
         self.montecarlo_configuration = montecarlo_configuration or st.MonteCarloConfiguration()
         self.line_interaction_type = line_interaction_type
@@ -408,6 +481,7 @@ class MCTransportSolverHIP:
         self.resident = bool(resident)
         self.reuse_opacity = bool(reuse_opacity)
         self.enable_last_interaction_tracking = bool(enable_last_interaction_tracking)
+        self.enable_rpacket_tracking = bool(enable_rpacket_tracking)  # full r-packet tracking -> transport_state.tracker_full_df
         self.transport_state = None
         self._engine = engine          # (default: the process-wide engine of the device)
 
@@ -447,7 +521,10 @@ class MCTransportSolverHIP:
         hist, vtracker, est_bulk, est_line = montecarlo_transport_with_vpackets(
             transport_state.packet_collection, transport_state.geometry_state_numba, float(transport_state.time_explosion),
             transport_state.opacity_state_numba, cfg, self.spectrum_frequency_grid, trackers, cfg.NUMBER_OF_VPACKETS,
-            show_progress_bars, None, engine=self._eng())
+            show_progress_bars, None, engine=self._eng(), track_full=self.enable_rpacket_tracking)
+        if self.enable_rpacket_tracking:
+            transport_state.tracker_full = montecarlo_transport_with_vpackets.last_event_log
+            transport_state.tracker_full_df = transport_state.tracker_full.to_dataframe()
         transport_state.estimators_bulk = est_bulk
         transport_state.estimators_line = est_line
         if cfg.ENABLE_VPACKET_TRACKING and cfg.NUMBER_OF_VPACKETS > 0:
@@ -461,6 +538,8 @@ class MCTransportSolverHIP:
         cfg = self.montecarlo_configuration
         if cfg.ENABLE_VPACKET_TRACKING and cfg.NUMBER_OF_VPACKETS > 0:
             raise NotImplementedError("the consolidated v-packet log is a per-v-packet host result: use resident=False with it")
+        if self.enable_rpacket_tracking:
+            raise NotImplementedError("full r-packet tracking (enable_rpacket_tracking) is a per-event host result: use resident=False with it")
         eng = self._eng()
         eng.set_geometry(ts.geometry_state_numba, float(ts.time_explosion))
         op = ts.opacity_state_numba
