@@ -171,6 +171,11 @@ const char *tardis_mc_last_error(const TardisMcContext *ctx);   /* ctx may be NU
  * overflows drops rows, keeps the counts exact and reports them through tardis_mc_get_event_log), "event_log_max_bytes" (bound on
  * the log's device memory, default 16 GiB: 96 B per pool row + 112 B per row for the columns + 12 B per packet; a call over it fails
  * with TARDIS_MC_ERR_INVALID_ARGUMENT),
+ * "table_offsets" (row offsets of the cooperative kernels, variants 1-3: -1, the default, 64-bit only where n_shells * n_lines or
+ * n_shells * n_trans reaches 2^28; 0 always 32-bit -- such tables then fail with TARDIS_MC_ERR_INVALID_ARGUMENT; 1 always 64-bit.  Per-packet
+ * results do not depend on it.  The 64-bit wave kernels need n_shells * n_lines < 2^32 (beyond, the automatic choice runs variant 1, or variant 0
+ * with "track_full"; a forced variant 2-4 fails) and the compact walk tables (macroatom / downbranch; where those are not built the call runs on
+ * variant 0); a forced variant 4 and the wave kernel's cross-check debug flags on 64-bit offsets fail),
  * "variant" (kernel variant: -1 automatic, 0 lane-per-packet, 1 group-per-packet, 2 wave-owner with group sweeps, 3 wave-owner
  * with lane sweeps, 4 wave-owner with the volley queue: v-packets traced by a kernel of their own between its launches --
  * never the automatic choice; falls back to 2/3 without v-packets and to 1 with a survival probability > 0),
@@ -258,6 +263,9 @@ int tardis_mc_last_counters(TardisMcContext *ctx, int64_t out_counters[TARDIS_MC
  * 1 group-per-packet, 2 wave-owner with group sweeps, 3 wave-owner with lane sweeps, 4 wave-owner with the volley queue;
  * -1 before the first call. */
 int tardis_mc_last_variant(TardisMcContext *ctx);
+/* Width of the table row offsets of the kernel the last tardis_mc_propagate ran (option "table_offsets"): 32 or 64; the lane-per-packet
+ * kernel (variant 0) always reports 64; -1 before the first call. */
+int tardis_mc_last_table_offsets(TardisMcContext *ctx);
 /* How often the last tardis_mc_propagate packed the live lanes of its drain into fewer waves (option "drain_compact" = T: once the packet supply has run out a wave
  * suspends when T or fewer of its lanes still hold a packet; the live lanes of all waves are packed into full waves and the rest of the call runs as a launch of
  * fewer waves, beside the line-estimator passes of the launch before; 0 = off.  Per-packet results do not depend on it). */

@@ -20,6 +20,14 @@ enum : int { ERR_MONTECARLO = -3, ERR_MACRO_ATOM = -4, ERR_UNSUPPORTED = -5 };
 
 constexpr int MT_N = 624;
 
+// Element offset of a shell's row in a shell-major table ([S][L] line tables, [S][T] transition tables).  The production
+// instantiations keep it 32-bit (one VGPR, and S x L, S x T < 2^28 is checked on the host); the WIDE instantiations (option
+// table_offsets) make the row base 64-bit, offsets inside a row stay 32-bit.
+template <bool WIDE> struct RowOffset { typedef unsigned type; };
+template <> struct RowOffset<true> { typedef unsigned long long type; };
+template <bool WIDE> using row_t = typename RowOffset<WIDE>::type;
+template <bool WIDE> __host__ __device__ __forceinline__ row_t<WIDE> row_of(int shell, int len) { return (row_t<WIDE>)(unsigned)shell * (row_t<WIDE>)(unsigned)len; }
+
 // ---- deferred line-estimator accumulation (estimator_log.hpp): one record per trace
 // In partial relativity the term update_line_estimators adds for a visited line, energy * (1 - (d_line + mu r) / (t c)),
 // is energy * nu_line / nu exactly (d_line is where the packet's comoving frequency equals nu_line), i.e. a per-trace
@@ -29,7 +37,7 @@ constexpr int MT_N = 624;
 // lines closer than 1e-14), far inside the summation-order tolerance the estimators are compared with.
 struct __attribute__((aligned(8))) LineVisitRecord {
     double c_e, c_jb;   // Edotlu / j_blue constants of the trace (energy / nu, energy / nu^2; full relativity: energy, energy / nu)
-    unsigned idx0;      // shell * n_lines + first line visited
+    unsigned idx0;      // shell * n_lines + first line visited (32-bit in every instantiation: S x L < 2^32 is checked on the host)
     unsigned n;         // number of lines visited
 };
 static_assert(sizeof(LineVisitRecord) == 24, "record layout");

@@ -198,14 +198,14 @@ struct GroupCounters { unsigned long long visits = 0; unsigned events = 0, macro
 
 // ---- one cooperative trace_packet (modes/homologous_rad_packet_transport.py:30-174)
 // All arguments / results are group-uniform except the lane index j.  Returns 0 or a negative error code.
-template <bool FULL, int G, bool FAST>
+template <bool FULL, int G, bool FAST, bool WIDE>
 __device__ __forceinline__ int sweep_lines(const GroupArgs &P, Packet &p, const int j, const double chi_cont,
                                            const double tau_event, const double comov_nu, const double d_boundary,
                                            int line, bool in_range, double nu_line, double tau_line,
                                            double *__restrict__ jb, double *__restrict__ ed, double &distance, int &type,
                                            GroupCounters &cn);
 
-template <bool FULL, int G>
+template <bool FULL, int G, bool WIDE>
 __device__ __forceinline__ int trace_packet_group(const GroupArgs &P, Packet &p, GroupRng<G> &rng, const int j,
                                                   const double chi_cont, const double r_inner, const double r_outer,
                                                   const double dop, double *__restrict__ jb, double *__restrict__ ed,
@@ -218,7 +218,7 @@ __device__ __forceinline__ int trace_packet_group(const GroupArgs &P, Packet &p,
     int line = start + j;
     bool in_range = line < L;
     double nu_line = in_range ? P.nu_line[(unsigned)line] : 0.0;
-    double tau_line = in_range ? P.tau_t[(unsigned)p.shell * (unsigned)L + (unsigned)line] : 0.0;
+    double tau_line = in_range ? P.tau_t[row_of<WIDE>(p.shell, L) + (unsigned)line] : 0.0;
 
     double d_boundary;
     distance_boundary(p.r, p.mu, r_inner, r_outer, d_boundary, delta_shell);
@@ -228,14 +228,14 @@ __device__ __forceinline__ int trace_packet_group(const GroupArgs &P, Packet &p,
     // the 3-instruction exact division needs operands away from the exponent limits (always true for physical input)
     const bool fast = mid_range(p.nu) && mid_range(chi_cont) && mid_range(tau_event) && mid_range(p.energy) &&
                       mid_range(p.r) && mid_range(comov_nu) && mid_range(P.t_exp) && !(P.debug_flags & 4);
-    if (fast) return sweep_lines<FULL, G, true>(P, p, j, chi_cont, tau_event, comov_nu, d_boundary, line, in_range, nu_line,
+    if (fast) return sweep_lines<FULL, G, true, WIDE>(P, p, j, chi_cont, tau_event, comov_nu, d_boundary, line, in_range, nu_line,
                                                tau_line, jb, ed, distance, type, cn);
-    return sweep_lines<FULL, G, false>(P, p, j, chi_cont, tau_event, comov_nu, d_boundary, line, in_range, nu_line, tau_line,
+    return sweep_lines<FULL, G, false, WIDE>(P, p, j, chi_cont, tau_event, comov_nu, d_boundary, line, in_range, nu_line, tau_line,
                                        jb, ed, distance, type, cn);
 }
 
 // The line sweep of trace_packet (lines 100-172 of homologous_rad_packet_transport.py), G lines per step.
-template <bool FULL, int G, bool FAST>
+template <bool FULL, int G, bool FAST, bool WIDE>
 __device__ __forceinline__ int sweep_lines(const GroupArgs &P, Packet &p, const int j, const double chi_cont,
                                            const double tau_event, const double comov_nu, const double d_boundary,
                                            int line, bool in_range, double nu_line, double tau_line,
@@ -245,7 +245,7 @@ __device__ __forceinline__ int sweep_lines(const GroupArgs &P, Packet &p, const 
     const int L = P.n_lines;
     const double t = P.t_exp;
     const int start = p.next_line_id;
-    const unsigned row = (unsigned)p.shell * (unsigned)L;  // 32-bit element offset of this shell's row (S*L < 2^28)
+    const row_t<WIDE> row = row_of<WIDE>(p.shell, L);  // element offset of this shell's row (32-bit: S*L < 2^28)
     const double *__restrict__ tau_t = P.tau_t;
     const double mur = p.mu * p.r;
     const double tc = P.tc, rcp_tc = P.rcp_tc;
@@ -262,7 +262,7 @@ __device__ __forceinline__ int sweep_lines(const GroupArgs &P, Packet &p, const 
     // wait would put their full memory-side latency on the critical path; issued just after it they overlap a whole
     // chunk of arithmetic.
     bool pend_valid = false;
-    unsigned pend_idx = 0;
+    row_t<WIDE> pend_idx = 0;
     double pend_energy = 0.0;
     auto flush_pending = [&]() {
         if (pend_valid && !(P.debug_flags & 1)) {
@@ -341,11 +341,11 @@ __device__ __forceinline__ int sweep_lines(const GroupArgs &P, Packet &p, const 
 // probabilities at a time (together with the packed transition records), accumulated in the reference's serial
 // order, and a ballot finds the selected row.  The record carries the destination level's block bounds, so an
 // internal jump costs ONE dependent memory round trip instead of three (edge, probability, destination).
-template <int G>
+template <int G, bool WIDE>
 __device__ __forceinline__ int macro_atom_group(const GroupArgs &P, GroupRng<G> &rng, const int j, int b0, int b1, int shell,
                                                 int &out_line, GroupCounters &cn)
 {
-    const unsigned row = (unsigned)shell * (unsigned)P.n_trans;
+    const row_t<WIDE> row = row_of<WIDE>(shell, P.n_trans);
     const double *__restrict__ prob_t = P.prob_t;
     const int gshift = (threadIdx.x & 63) & ~(G - 1);
     constexpr unsigned long long GMASK = (G == 16) ? 0xffffull : 0xffull;
@@ -429,7 +429,7 @@ __device__ __forceinline__ int vp_walk_to_stop(const MC_G double *__restrict__ n
     }
 }
 
-template <bool FULL, int G>
+template <bool FULL, int G, bool WIDE>
 __device__ __forceinline__ int vp_trace(const GroupArgs &P, const GroupRng<G> &rng, VpDraws &dr, double r, double mu, double nu,
                                         double &energy, int shell, int next_line, double &tau_out, unsigned &vvisits, const double *geo)
 {
@@ -456,7 +456,7 @@ __device__ __forceinline__ int vp_trace(const GroupArgs &P, const GroupRng<G> &r
         double chi_cont = chi_e;
         if (FULL) chi_cont *= dop;
         double tau_shell = chi_cont * d_boundary;
-        const unsigned row = (unsigned)shell * (unsigned)L;
+        const row_t<WIDE> row = row_of<WIDE>(shell, L);
         // approximate stopping frequency: nu_line ~ comov_nu - d_boundary nu / (c t)
         const double nu_thr = comov_nu - d_boundary * P.rcp_tc * nu;
         long long kk = (long long)((unsigned long long)__double_as_longlong(nu_thr > 0.0 ? nu_thr : 0.0) >> P.bucket_shift) - P.bucket_kmin;
@@ -677,7 +677,7 @@ __device__ __forceinline__ int vp_screen(const GroupArgs &P, const GroupRng<G> &
     }
 }
 
-template <bool FULL, int G>
+template <bool FULL, int G, bool WIDE>
 __device__ __forceinline__ int volley_group(const GroupArgs &P, const Packet &p, GroupRng<G> &rng, const int j, long long packet_index,
                                             int &vseq, unsigned &pred_bits, unsigned &vvisits, unsigned &vcount, unsigned long long &vtraced,
                                             const double *geo)
@@ -758,7 +758,7 @@ __device__ __forceinline__ int volley_group(const GroupArgs &P, const Packet &p,
             else if (screened < 0) err = screened;
             else {
                 double tau_v;
-                err = vp_trace<FULL, G>(P, rng, dr, p.r, v_mu, v_nu, v_energy, p.shell, p.next_line_id, tau_v, my_visits, geo);
+                err = vp_trace<FULL, G, WIDE>(P, rng, dr, p.r, v_mu, v_nu, v_energy, p.shell, p.next_line_id, tau_v, my_visits, geo);
                 if (!err) v_energy *= mcm::exp(-tau_v);
             }
             if (dr.overflow) err = ERR_UNSUPPORTED;
@@ -811,7 +811,8 @@ __host__ __device__ constexpr size_t group_kernel_lds_bytes(int n_shells)
     return (size_t)(BLOCK / G) * sizeof(LdsTracker) + 6 * (size_t)n_shells * sizeof(double);  // J, nu_bar; r_inner, r_outer, n_e, tau row sums for the v-packet traces
 }
 
-template <bool FULL, bool TRACK, int G, int BLOCK, int OCC, bool VPK>
+// WIDE: 64-bit row offsets into the shell-major tables (option table_offsets; mc_device.hpp)
+template <bool FULL, bool TRACK, int G, int BLOCK, int OCC, bool VPK, bool WIDE = false>
 __global__ void __launch_bounds__(BLOCK, OCC) propagate_group_kernel(GroupArgs P, uint32_t *__restrict__ seeded_states,
                                                                 long long chunk_first, long long chunk_count)
 {
@@ -953,7 +954,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) propagate_group_kernel(GroupArgs P
             const unsigned long long live_mask = __ballot(live), want_mask = __ballot(live && want_volley);
             if (want_mask != 0ull && want_mask == live_mask) {
                 if (live && want_volley) {
-                    const int verr = volley_group<FULL, G>(P, p, rng, j, chunk_first + pkt, vseq, pred_bits, vvisits, vcount, vtraced, lds_geo);
+                    const int verr = volley_group<FULL, G, WIDE>(P, p, rng, j, chunk_first + pkt, vseq, pred_bits, vvisits, vcount, vtraced, lds_geo);
                     want_volley = false;
                     if (verr) {
                         if (j == 0) {
@@ -977,7 +978,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) propagate_group_kernel(GroupArgs P
         if (FULL) chi_e *= dop;
         double distance;
         int type = 0, delta = 0;
-        int err = trace_packet_group<FULL, G>(P, p, rng, j, chi_e, P.r_inner[p.shell], P.r_outer[p.shell], dop, jb, ed, distance, type, delta, cn);
+        int err = trace_packet_group<FULL, G, WIDE>(P, p, rng, j, chi_e, P.r_inner[p.shell], P.r_outer[p.shell], dop, jb, ed, distance, type, delta, cn);
         if (!err) {
             // move_r_packet + update_estimators_bulk (packets/movement.py:31-76)
             double r = p.r;
@@ -1015,7 +1016,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) propagate_group_kernel(GroupArgs P
                     if (P.line_interaction_type != 0)
                     {
                         const int2 blk = P.line_block[(unsigned)p.next_line_id];
-                        err = macro_atom_group<G>(P, rng, j, blk.x, blk.y, p.shell, emit, cn);
+                        err = macro_atom_group<G, WIDE>(P, rng, j, blk.x, blk.y, p.shell, emit, cn);
                     }
                     if (!err) {  // line_emission (interaction_events.py:227-258); its inverse Doppler factor == inv_new
                         p.nu = P.nu_line[emit] * inv_new;

@@ -51,7 +51,7 @@ struct WaveShared {
     int res_info[64], res_line[64];
     unsigned rng_a[64], rng_b[64];  // lazy MT19937 seeding: init_genrand words mt[k] and mt[k+397] of the next block to regenerate
     // group sweeps only (the lane-sweep instantiations do not allocate the rest: 16 instead of 15 waves fit a CU's LDS)
-    int cursor[64], rowfast[64];  // first line of the trace; shell * n_lines | exact-division fast path << 31
+    int cursor[64], rowfast[64];  // first line of the trace; shell * n_lines (WIDE: shell) | exact-division fast path << 31
     int queue[64];                // lanes whose prepared trace waits for a worker group
 };
 constexpr size_t WAVE_SHARED_LS_BYTES = sizeof(WaveShared) - 3 * 64 * sizeof(int);
@@ -277,21 +277,21 @@ __global__ void __launch_bounds__(256) drain_compact_finish_kernel(LaneSave *__r
 }
 
 // One worker slot of a group: the trace it is sweeping (group-uniform values) and this lane's line of the current chunk.
-struct SweepSlot {
+template <bool WIDE> struct SweepSlot {
     int owner;  // lane (in this wave) of the packet being traced, -1: idle
     double nu, rcp_nu, comov_nu, chi, rcp_chi, tau_event, d_boundary, r, mu;
     double tau_carry, d_cont_carry;
     double nu_line, tau_line;
     int cur0;
-    unsigned row;
+    row_t<WIDE> row;
     bool fast;
 };
 
 // One G-line step of the line sweep of trace_packet (modes/homologous_rad_packet_transport.py:100-172); the loop body of
 // sweep_lines() in propagate_group.hpp with the loop turned inside out and without the estimator updates.  On a stop
 // (or when the list is exhausted) the result is handed to the owner lane through LDS and the slot becomes idle.
-template <bool FULL, int G, bool FAST>
-__device__ __forceinline__ void sweep_step(const WaveHot &P, SweepSlot &s, const int j, WaveShared &sh, unsigned long long &visits)
+template <bool FULL, int G, bool FAST, bool WIDE>
+__device__ __forceinline__ void sweep_step(const WaveHot &P, SweepSlot<WIDE> &s, const int j, WaveShared &sh, unsigned long long &visits)
 {
     const int L = P.n_lines;
     const int gshift = (threadIdx.x & 63) & ~(G - 1);
@@ -563,14 +563,14 @@ struct VpState {
 // enough), and the optical depths are added in wave-uniform chunks of 8 with exact no-op adds (+0.0) in the lanes that
 // have fewer lines.  rcp_nu = RN(1 / v.nu) serves the exact 3-instruction division (mc_device.hpp) of the resonance
 // distances; v.nu is constant along a v-packet.
-template <bool FULL, typename Draw>
+template <bool FULL, bool WIDE = false, typename Draw>
 __device__ __forceinline__ int vp_shell_step(const GroupArgs &P, Draw &&draw, int &draws_left, VpState &v, double rcp_nu, bool fast_nu,
                                              const double *__restrict__ geo /* LDS: r_inner | r_outer | n_e */, unsigned &vvisits)
 {
     const int L = P.n_lines, S = P.n_shells;
     const double t = P.t_exp;
     int status = ST_IN_PROCESS;
-    const unsigned row = (unsigned)v.shell * (unsigned)L;
+    const row_t<WIDE> row = row_of<WIDE>(v.shell, L);
     const int start = v.next_line;
     // The step is bound by the latency of its dependent, uncoalesced loads, so everything whose address is known now is
     // requested first: the line at `start` and -- speculatively -- the first eight optical depths of the sum.
@@ -808,9 +808,10 @@ __device__ __forceinline__ int vp_screen_step(const GroupArgs &P, Draw &&draw, i
 // FT: full r-packet tracking (event_log.hpp) -- one row per trace outcome, the row's ordinal from trk_count + trk_boundary (which travel
 // with the lane through suspensions, epochs and drain compaction); needs TRACK
 template <bool FULL, bool TRACK, int G, bool VPK, bool LS = false, bool XWALK = true, int WPE = (VPK ? 3 : 4), int NT = 0, bool SL = false,
-          bool FT = false>
+          bool FT = false, bool WIDE = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) propagate_wave_kernel(WaveHot H, const WaveCold *__restrict__ W)
 {
+    static_assert(!WIDE || (!XWALK && NT == 0 && !SL), "64-bit row offsets: the compact walks, the separate line and tau tables, the log by bin");
     static_assert(!FT || TRACK, "the full tracking counts rows with the last-interaction tracker's counters");
     static_assert(NT == 0 || (LS && !VPK && !FULL), "the interleaved sweep table is read by the lane sweeps only");
     static_assert(!SL || !VPK, "the shell-sorted log is built for the instantiations without v-packets");
@@ -888,7 +889,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     // result goes, too); the packet's nu and Doppler factor are the owner's p.nu and dop.
     bool s_active = false, s_fast = false;
     int s_line = 0;
-    unsigned s_row = 0;
+    row_t<WIDE> s_row = 0;  // (WIDE: not saved with the lane, recomputed from its shell: no interleaved table, the row is the shell's tau row)
     double s_tau = 0.0, s_tau_event = 0.0, s_kp = 0.0, s_xb = 0.0;
     int2 pre_blk = make_int2(0, 0);  // line_block[] of the line that stopped the trace, in flight since the sweep found it
 
@@ -997,7 +998,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             r_gpos = v.r_gpos; r_head = v.r_head; r_cnt = v.r_cnt;
             trk_count = v.trk_count; trk_boundary = v.trk_boundary;
             { const int fl = v.flags; trk_any = (fl & 1) != 0; s_active = (fl & 2) != 0; s_fast = (fl & 4) != 0; }
-            s_line = v.s_line; s_row = v.s_row;
+            s_line = v.s_line; s_row = WIDE ? row_of<WIDE>(v.shell, L) : (row_t<WIDE>)v.s_row;
             sh.res_info[lane] = v.res_info; sh.res_line[lane] = v.res_line; pre_blk = make_int2(v.pre_blk_x, v.pre_blk_y);
             sh.rng_a[lane] = v.rng_a; sh.rng_b[lane] = v.rng_b;
             vseq = v.vseq; pred_bits = v.pred_bits; vq_done = v.vdone;
@@ -1085,7 +1086,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             v.r_gpos = r_gpos; v.r_head = r_head; v.r_cnt = r_cnt;
             v.trk_count = trk_count; v.trk_boundary = trk_boundary;
             v.flags = (trk_any ? 1 : 0) | (s_active ? 2 : 0) | (s_fast ? 4 : 0);
-            v.s_line = s_line; v.s_row = s_row;
+            v.s_line = s_line; v.s_row = (unsigned)s_row;
             v.res_info = sh.res_info[lane]; v.res_line = sh.res_line[lane]; v.pre_blk_x = pre_blk.x; v.pre_blk_y = pre_blk.y;
             v.rng_a = sh.rng_a[lane]; v.rng_b = sh.rng_b[lane];
             v.vseq = vseq; v.pred_bits = pred_bits; v.vdone = vq_done; v.pad_v0 = v.pad_v1 = v.pad_v2 = 0;
@@ -1890,7 +1891,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                 my_visits = 0; w_used = 0; screening = false; st = 0;
                             }
                         } else
-                            st = vp_shell_step<FULL>(P, wdraw, draws_left, vs, v_rcp_nu, v_fast, lds_geo, my_visits);
+                            st = vp_shell_step<FULL, WIDE>(P, wdraw, draws_left, vs, v_rcp_nu, v_fast, lds_geo, my_visits);
                         if (st != 0) {
                             VpResult r;
                             r.nu = vs.nu; r.energy = st == 1 ? vs.energy * mcm::exp(-vs.tau) : 0.0; r.mu0 = vs.mu0;
@@ -1961,7 +1962,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                 if (LS) {
                     sh.d_cont0[lane] = chi_e; sh.d_boundary[lane] = d_boundary;
                     s_tau_event = tau_event;
-                    s_tau = 0.0; s_line = p.next_line_id; s_row = (unsigned)p.shell * (NT != 0 ? P.nt_stride : (unsigned)L);
+                    s_tau = 0.0; s_line = p.next_line_id; s_row = NT != 0 ? (row_t<WIDE>)((unsigned)p.shell * P.nt_stride) : row_of<WIDE>(p.shell, L);
                     s_kp = ((chi_e * P.tc) / p.nu) * (1.0 + 0x1p-40);
                     s_xb = ((d_boundary * p.nu) * P.rcp_tc) * (1.0 - 0x1p-40);
                     s_fast = fast && mid_range(s_kp);
@@ -1973,7 +1974,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     sh.d_cont0[lane] = tau_event / chi_e;  // distance_continuum in force at the first line
                     if (FULL) { shf.r[lane] = p.r; shf.mu[lane] = p.mu; }
                     sh.cursor[lane] = p.next_line_id;
-                    sh.rowfast[lane] = (int)(((unsigned)p.shell * (unsigned)L) | (fast ? 0x80000000u : 0u));
+                    sh.rowfast[lane] = (int)((WIDE ? (unsigned)p.shell : (unsigned)p.shell * (unsigned)L) | (fast ? 0x80000000u : 0u));
                 }
                 state = WS_SWEEP;
             }
@@ -2142,7 +2143,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 
         // ============================================================ sweep phase (G-lane groups work off the queue)
         // worker state of this lane's group; every group is idle again when the phase ends
-        SweepSlot cur;
+        SweepSlot<WIDE> cur;
         cur.owner = -1; cur.cur0 = 0; cur.row = 0; cur.fast = true;
         cur.nu = cur.rcp_nu = cur.comov_nu = cur.chi = cur.rcp_chi = cur.tau_event = cur.d_boundary = cur.r = cur.mu = 0.0;
         cur.tau_carry = cur.d_cont_carry = cur.nu_line = cur.tau_line = 0.0;
@@ -2167,7 +2168,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                 cur.chi = sh.chi[o]; cur.rcp_chi = sh.rcp_chi[o]; cur.tau_event = sh.tau_event[o]; cur.d_boundary = sh.d_boundary[o];
                 if (FULL) { cur.r = shf.r[o]; cur.mu = shf.mu[o]; }
                 cur.fast = (n_rowfast >> 31) != 0;
-                cur.cur0 = n_cursor; cur.row = n_rowfast & 0x7fffffffu;
+                cur.cur0 = n_cursor; cur.row = WIDE ? row_of<WIDE>((int)(n_rowfast & 0x7fffffffu), L) : (row_t<WIDE>)(n_rowfast & 0x7fffffffu);
                 cur.nu_line = n_nu; cur.tau_line = n_tau;
                 cur.tau_carry = 0.0;
                 cur.d_cont_carry = sh.d_cont0[o];
@@ -2184,15 +2185,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         const int line = n_cursor + j;
                         const bool in = line < L;
                         n_nu = in ? H.nu_line[(unsigned)line] : 0.0;
-                        n_tau = in ? H.tau_t[(n_rowfast & 0x7fffffffu) + (unsigned)line] : 0.0;
+                        const row_t<WIDE> n_row = WIDE ? row_of<WIDE>((int)(n_rowfast & 0x7fffffffu), L) : (row_t<WIDE>)(n_rowfast & 0x7fffffffu);
+                        n_tau = in ? H.tau_t[n_row + (unsigned)line] : 0.0;
                     }
                     q_head += min(__popcll(free_groups), avail);
                 }
             }
             // ---- one G-line step of every running sweep
             if (cur.owner >= 0) {
-                if (cur.fast) sweep_step<FULL, G, true>(H, cur, j, sh, visits);
-                else sweep_step<FULL, G, false>(H, cur, j, sh, visits);
+                if (cur.fast) sweep_step<FULL, G, true, WIDE>(H, cur, j, sh, visits);
+                else sweep_step<FULL, G, false, WIDE>(H, cur, j, sh, visits);
             }
         }
         TMC_SEC(6)

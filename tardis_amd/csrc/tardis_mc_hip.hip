@@ -156,7 +156,7 @@ struct TardisMcContext {
     // enqueued completely, so that neither another entry point's use of ev_start / ev_stop nor a failed call can leave a stale or unpaired
     // measurement behind -- and from call 5 on B only if the faster of its two calls beat the faster of A's by >= 3 %: boxes differ by more
     // than one noisy sample can tell apart)
-    struct { long long n = -1; int lines = 0, shells = 0, mode = 0, table = 0, phase = 0, pending = -1, choice = 0; double ms[2][2] = {{-1.0, -1.0}, {-1.0, -1.0}}; } ls_tune;
+    struct { long long n = -1; int lines = 0, shells = 0, mode = 0, table = 0, wide = 0, phase = 0, pending = -1, choice = 0; double ms[2][2] = {{-1.0, -1.0}, {-1.0, -1.0}}; } ls_tune;
     hipEvent_t ev_tune[2] = {nullptr, nullptr};
     int vpk_wide_registers = 1;       // option: the two-waves-per-SIMD v-packet instantiation where LDS bounds the occupancy at eight waves per CU anyway
     int bucket_lines_permille = 750;  // option: target lines per bucket x 1000 (takes effect in set_opacity)
@@ -261,6 +261,8 @@ struct TardisMcContext {
     int launches = 0;
     int log_sets = 0;  // 2: the estimator passes of an epoch run beside the next launch (two log sets); 1: before it (one set); 0: 1 for calls of several epochs, 2 otherwise
     int last_variant = -1;  // kernel of the last propagate call (see tardis_mc_last_variant)
+    int table_offsets = -1;       // option: row offsets of the cooperative kernels, -1 64-bit where S x L or S x T reaches 2^28, 0 always 32-bit, 1 always 64-bit
+    int last_table_offsets = -1;  // 32 / 64: row offsets of the last propagate call's kernel (see tardis_mc_last_table_offsets)
     int waves_per_simd = 4;  // register budget hint of the cooperative kernel (2: 256 VGPRs, 3: 168, 4: 128)
     // result streaming (tardis_mc_stream_results): the caller's per-packet arrays, what has been copied to them while the call ran, and the packets that were
     // in flight when their range was copied (their results are sent again by get_results)
@@ -944,6 +946,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "log_by_shell") ctx->log_by_shell = value < 0 ? -1 : (value ? 1 : 0);
     else if (n == "stream_min_packets") ctx->rs_min_packets = std::max<long long>(64, value);
     else if (n == "sweep_table") ctx->sweep_table = (int)std::max<long long>(-1, std::min<long long>(value, 2));
+    else if (n == "table_offsets") ctx->table_offsets = value < 0 ? -1 : (value ? 1 : 0);
     else if (n == "vpk_wide_registers") ctx->vpk_wide_registers = (int)std::max<long long>(0, std::min<long long>(value, 2));
     else if (n == "bucket_lines_permille") ctx->bucket_lines_permille = (int)std::max<long long>(50, std::min<long long>(value, 16000));
     else if (n == "vp_carry_min_active") ctx->vp_carry_min_active = (int)std::max<long long>(0, std::min<long long>(value, 63));
@@ -1635,7 +1638,37 @@ int tardis_mc_propagate(TardisMcContext *ctx)
                              !(ctx->debug_flags & (128 | 8192 | 1048576 | mc::WV_DBG_FLAGS)) && ctx->n_packets < (1LL << 31);
         variant = (wave_ok && variant != 0) ? 2 : 0;
     }
-    const bool cooperative = ctx->lines_sorted && (variant == 1 || variant == 2 || variant == 3 || variant == 4) && (!vpk || c.number_of_vpackets <= 32);
+    bool cooperative = ctx->lines_sorted && (variant == 1 || variant == 2 || variant == 3 || variant == 4) && (!vpk || c.number_of_vpackets <= 32);
+    // 64-bit row offsets (option table_offsets): the lane kernel always has them; the cooperative kernels have WIDE instantiations, used where
+    // a shell-major table reaches 2^28 entries (or always, option 1) -- the 32-bit ones save registers on the hot path
+    const bool big_tables = (long long)ctx->n_shells * ctx->n_lines >= (1LL << 28) || (long long)ctx->n_shells * ctx->n_trans >= (1LL << 28);
+    bool w64 = false;
+    if (cooperative && (ctx->table_offsets == 1 || (ctx->table_offsets < 0 && big_tables))) {
+        const bool wave_v = variant == 2 || variant == 3 || variant == 4;
+        if (variant == 4)
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "variant 4 (the volley queue) has no 64-bit table offsets: n_shells * n_lines or n_shells * n_trans "
+                                                             "reaches 2^28, or option table_offsets is 1; use the automatic variant");
+        if (wave_v && (ctx->debug_flags & (128 | 8192 | 1048576 | mc::WV_DBG_FLAGS)))
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "the cross-check instantiations of the wave kernel (debug flags 128, 8192, 1048576 and the counter "
+                                                             "flags) have no 64-bit table offsets");
+        if (wave_v && (long long)ctx->n_shells * ctx->n_lines >= (1LL << 32)) {
+            // (the line-visit log of the wave kernels indexes (shell, line) in 32 bits; the group kernel adds its terms directly)
+            if (ctx->variant >= 0)
+                return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells * n_lines reaches 2^32: the line-visit log of the wave kernels (variants 2-4) "
+                                                                 "indexes (shell, line) in 32 bits; use variant 1 or the automatic variant");
+            if (ctx->track_full) { cooperative = false; variant = 0; }  // (the group kernel has no full tracking)
+            else { variant = 1; w64 = true; }
+        } else if (wave_v && c.line_interaction_type != 0 && !ctx->have_walk_tables) {
+            // (the compact walk tables were not built for these tables: the fp64 walks are only in the 32-bit cross-check instantiations)
+            cooperative = false;
+            variant = 0;
+        } else
+            w64 = true;
+    }
+    if (cooperative && big_tables && !w64)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells * n_lines or n_shells * n_trans reaches 2^28, the limit of the cooperative kernels' 32-bit "
+                                                         "table offsets, and option table_offsets is 0");
+    ctx->last_table_offsets = (w64 || !cooperative) ? 64 : 32;
     ctx->last_variant = cooperative ? ((variant == 3 && c.enable_full_relativity) ? 2 : variant) : 0;
     if (screen_on && !cooperative) screen_on = false;  // (the lane kernel traces line by line)
     if (screen_on) {
@@ -1693,8 +1726,6 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         P.debug_flags = F.debug_flags; P.n_est_copies = F.n_est_copies;
         P.t_exp = F.t_exp; P.sigma_thomson = F.sigma_thomson;
         P.tc = F.t_exp * mc::C_LIGHT; P.rcp_tc = 1.0 / P.tc;
-        if ((long long)ctx->n_shells * ctx->n_lines >= (1LL << 28) || (long long)ctx->n_shells * ctx->n_trans >= (1LL << 28))
-            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells * n_lines exceeds the 32-bit table offsets of the cooperative kernel");
         if (wave_kernel && ctx->n_packets >= (1LL << 31))
             return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "more than 2^31 packets per propagate call");
         P.r_inner = F.r_inner; P.r_outer = F.r_outer; P.nu_line = F.nu_line; P.tau_t = F.tau_t; P.n_e = F.n_e; P.prob_t = F.prob_t;
@@ -1760,7 +1791,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
             // G = 8, without the cross-check walks; option vpk_wide_registers 0 keeps the 168-VGPR one)
             // Measured (profiles/r05_vpk_wide_registers.txt): 3727-3766 vs 4442-4450 ms per 1e7 packets of the configs[4] shape (-16 %).  Option 2 forces
             // it (then eight waves per CU whatever the LDS allows), 0 keeps the 168-VGPR instantiation.
-            bool wide = vpk && !xwalk && !ctx->track_full && (lane_sweep || GW == 16 || GW == 8) &&
+            bool wide = vpk && !xwalk && !w64 && !ctx->track_full && (lane_sweep || GW == 16 || GW == 8) &&
                         ((ctx->vpk_wide_registers == 1 && wave_waves_per_cu <= 8) || ctx->vpk_wide_registers == 2);
 #define TMC_PICKWIDE(G_) (full ? (trk ? mc::propagate_wave_kernel<true, true, G_, true, false, false, 2> : mc::propagate_wave_kernel<true, false, G_, true, false, false, 2>) \
                                : (trk ? mc::propagate_wave_kernel<false, true, G_, true, false, false, 2> : mc::propagate_wave_kernel<false, false, G_, true, false, false, 2>))
@@ -1777,8 +1808,9 @@ int tardis_mc_propagate(TardisMcContext *ctx)
                 if (ctx->ls_waves_per_simd == 3 || (ctx->ls_waves_per_simd == 0 && all_drain)) ls3 = true;
                 else if (ctx->ls_waves_per_simd == 0 && ctx->pass_cus == 0) {
                     if (tn.n != ctx->n_packets || tn.lines != ctx->n_lines || tn.shells != ctx->n_shells || tn.mode != c.line_interaction_type ||
-                        tn.table != ctx->sweep_table) {
+                        tn.table != ctx->sweep_table || tn.wide != (int)w64) {
                         tn.n = ctx->n_packets; tn.lines = ctx->n_lines; tn.shells = ctx->n_shells; tn.mode = c.line_interaction_type; tn.table = ctx->sweep_table;
+                        tn.wide = (int)w64;
                         tn.phase = 0; tn.choice = 0;
                         tn.ms[0][0] = tn.ms[0][1] = tn.ms[1][0] = tn.ms[1][1] = -1.0;
                     } else if (tune_pending >= 0) {  // the previous call of this key was a timed one: its duration (propagation + passes)
@@ -1807,7 +1839,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
             if (ls3) kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 3> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 3>;
             // the interleaved sweep table (option sweep_table; the production lane-sweep instantiations only)
             int nt_mode = 0;
-            if (lane_sweep && !vpk && !xwalk && ctx->sweep_table != 0) {
+            if (lane_sweep && !vpk && !xwalk && !w64 && ctx->sweep_table != 0) {
                 const unsigned long long stride = ((unsigned long long)ctx->n_lines + 7ull) & ~7ull;
                 if (stride * (unsigned long long)ctx->n_shells + 32ull < (1ull << 28)) {
                     if (!ctx->nt_valid) {
@@ -1865,7 +1897,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
             // to fit the partition kernel's local buckets
             const bool partition = ctx->est_pipeline == 1 && tiles <= mc::PART_LOCAL_BUCKETS && ctx->n_shells <= mc::PART_LOCAL_BUCKETS;
             // the shell-sorted log: instantiated for the two production lane-sweep kernels (sixteen waves on the interleaved table, twelve on the separate ones)
-            const bool shell_log = lane_sweep && !vpk && !xwalk && !vq && partition && ctx->log_by_shell != 0 && ctx->n_shells <= 64 &&
+            const bool shell_log = lane_sweep && !vpk && !xwalk && !w64 && !vq && partition && ctx->log_by_shell != 0 && ctx->n_shells <= 64 &&
                                    ((!ls3 && nt_mode == 1) || (ls3 && nt_mode == 0));
             if (shell_log) {
                 if (ls3) kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 3, 0, true> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 3, 0, true>;
@@ -1877,6 +1909,25 @@ int tardis_mc_propagate(TardisMcContext *ctx)
                                  : mc::propagate_wave_kernel<true, true, 16, false, false, false, 4, 0, false, true>)
                           : (vpk ? mc::propagate_wave_kernel<false, true, 16, true, false, false, 3, 0, false, true>
                                  : mc::propagate_wave_kernel<false, true, 16, false, false, false, 4, 0, false, true>);
+            }
+            // 64-bit row offsets: the production shapes above without the interleaved sweep table, the shell-sorted log and the two-waves-per-SIMD
+            // v-packet form (those keep 32-bit offsets); sweep width 4 runs as 8 (per-packet results do not depend on the width)
+            if (w64) {
+                if (xwalk) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "the fp64 macro-atom walks have no 64-bit table offsets");
+#define TMC_W64(F_, T_, G_, V_, LS_, WPE_, FT_) mc::propagate_wave_kernel<F_, T_, G_, V_, LS_, false, WPE_, 0, false, FT_, true>
+#define TMC_PICKW64(G_, V_) (full ? (trk ? TMC_W64(true, true, G_, V_, false, V_ ? 3 : 4, false) : TMC_W64(true, false, G_, V_, false, V_ ? 3 : 4, false)) \
+                                  : (trk ? TMC_W64(false, true, G_, V_, false, V_ ? 3 : 4, false) : TMC_W64(false, false, G_, V_, false, V_ ? 3 : 4, false)))
+                if (ctx->track_full)
+                    kw = full ? (vpk ? TMC_W64(true, true, 16, true, false, 3, true) : TMC_W64(true, true, 16, false, false, 4, true))
+                              : (vpk ? TMC_W64(false, true, 16, true, false, 3, true) : TMC_W64(false, true, 16, false, false, 4, true));
+                else if (lane_sweep)
+                    kw = vpk ? (trk ? TMC_W64(false, true, 16, true, true, 3, false) : TMC_W64(false, false, 16, true, true, 3, false))
+                             : ls3 ? (trk ? TMC_W64(false, true, 16, false, true, 3, false) : TMC_W64(false, false, 16, false, true, 3, false))
+                                   : (trk ? TMC_W64(false, true, 16, false, true, 4, false) : TMC_W64(false, false, 16, false, true, 4, false));
+                else
+                    kw = GW == 16 ? (vpk ? TMC_PICKW64(16, true) : TMC_PICKW64(16, false)) : (vpk ? TMC_PICKW64(8, true) : TMC_PICKW64(8, false));
+#undef TMC_PICKW64
+#undef TMC_W64
             }
             long long log_capacity = ctx->log_capacity;
             // One log set or two.  Two let the passes of an epoch run on a second stream beside the next launch -- but they do not fit beside sixteen resident waves per CU,
@@ -1939,6 +1990,19 @@ int tardis_mc_propagate(TardisMcContext *ctx)
                 region_capacity &= ~1u;  // even: a chunk of 24-byte records then starts on a 16-byte boundary (partition_kernel stages with 16-byte loads)
                 n_chunks = std::max<unsigned long long>(cap / region_capacity, (unsigned long long)waves * ((shell_log && !ctx->log_capacity_user) ? per_wave : 1ull));
                 if (n_chunks * region_capacity > 0xfffffff0ull) n_chunks = 0xfffffff0ull / region_capacity;
+            }
+            // Memory check: the tables are resident (set_opacity), what is left must hold the smallest log this grid runs with -- one chunk of 256 records per wave,
+            // 24 + 4 bytes a record and the partition's 24-byte scratch copy or the sort's 4-byte index (counting what the log holds already)
+            if (region_capacity > 0) {
+                size_t free_b = 0, total_b = 0;
+                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+                    const double have = (double)(ctx->log_records[0].cap + ctx->log_records[1].cap + ctx->log_keys[0].cap + ctx->log_keys[1].cap +
+                                                 ctx->log_sorted[0].cap + ctx->log_sorted[1].cap + ctx->log_part.cap);
+                    const double least = (double)waves * 256.0 * (partition ? 52.0 : 32.0);
+                    if (least > (double)free_b + have)
+                        return fail(ctx, TARDIS_MC_ERR_HIP, "device memory: the tables leave %.3f GiB of %.1f GiB free, the smallest line-visit log of this call needs "
+                                                            "%.3f GiB", ((double)free_b + have) / 1073741824.0, (double)total_b / 1073741824.0, least / 1073741824.0);
+                }
             }
             // (waves take chunks dynamically: every launch can suspend)
             const bool may_suspend = region_capacity > 0 || vq;
@@ -2483,8 +2547,12 @@ int tardis_mc_propagate(TardisMcContext *ctx)
             KernelFn k;
 #define TMC_PICK2(G_, V_) (full ? (trk ? mc::propagate_group_kernel<true, true, G_, 256, 4, V_> : mc::propagate_group_kernel<true, false, G_, 256, 4, V_>) \
                                 : (trk ? mc::propagate_group_kernel<false, true, G_, 256, 4, V_> : mc::propagate_group_kernel<false, false, G_, 256, 4, V_>))
-            if (G == 16) k = vpk ? TMC_PICK2(16, true) : TMC_PICK2(16, false);
+#define TMC_PICK2W(G_, V_) (full ? (trk ? mc::propagate_group_kernel<true, true, G_, 256, 4, V_, true> : mc::propagate_group_kernel<true, false, G_, 256, 4, V_, true>) \
+                                 : (trk ? mc::propagate_group_kernel<false, true, G_, 256, 4, V_, true> : mc::propagate_group_kernel<false, false, G_, 256, 4, V_, true>))
+            if (w64) k = G == 16 ? (vpk ? TMC_PICK2W(16, true) : TMC_PICK2W(16, false)) : (vpk ? TMC_PICK2W(8, true) : TMC_PICK2W(8, false));
+            else if (G == 16) k = vpk ? TMC_PICK2(16, true) : TMC_PICK2(16, false);
             else k = vpk ? TMC_PICK2(8, true) : TMC_PICK2(8, false);
+#undef TMC_PICK2W
 #undef TMC_PICK2
             hipStream_t st = ctx->stream;
             HIP_TRY(ctx, hipEventRecord(ctx->ev_start, st));
@@ -2643,6 +2711,7 @@ int tardis_mc_last_counters(TardisMcContext *ctx, int64_t out_counters[TARDIS_MC
 }
 
 int tardis_mc_last_variant(TardisMcContext *ctx) { return ctx ? ctx->last_variant : -1; }
+int tardis_mc_last_table_offsets(TardisMcContext *ctx) { return ctx ? ctx->last_table_offsets : -1; }
 int tardis_mc_last_compactions(TardisMcContext *ctx) { return ctx ? ctx->compactions : -1; }
 
 int tardis_mc_last_estimator_ms(TardisMcContext *ctx, double *out_ms)

@@ -160,6 +160,11 @@ class Engine:
         4 wave + volley queue (v-packets traced by vpacket_trace_kernel between its launches)."""
         return int(self._L.tardis_mc_last_variant(self._h))
 
+    def last_table_offsets(self) -> int:
+        """Width of the table row offsets of the last propagate()'s kernel (option ``table_offsets``): 32 or 64 (variant 0
+        always 64); -1 before the first call."""
+        return int(self._L.tardis_mc_last_table_offsets(self._h))
+
     def get_event_log(self) -> st.FullTrackers:
         """The full r-packet log of the last propagate() (option ``track_full``), as ``state.FullTrackers``.  Raises
         ``EventLogOverflow`` when the device pool dropped rows (re-run with ``event_log_capacity`` = its ``rows_needed``)."""
