@@ -30,6 +30,9 @@
 #include "packet_source.hpp"
 #include "formal_integral.hpp"
 #include "tau_prefix.hpp"
+#include "propagate_plan.hpp"
+
+static_assert(plan::DBG_WAVE_COUNTERS == mc::WV_DBG_FLAGS, "propagate_plan.hpp repeats the wave kernel's list of counter flags");
 
 namespace {
 
@@ -90,7 +93,7 @@ struct TardisMcContext {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    std::vector<hipEvent_t> ev_chunk;  // 3 per chunk of the cooperative path: before seed / after seed / after propagate
+    std::vector<hipEvent_t> ev_chunk;  // group kernel: 4 per chunk (before seed / after seed / after propagate, twice); wave kernel: 5 per call (prep, launch, read-back)
     int chunks_timed = 0;
     bool timed = false;
     std::string err;
@@ -180,7 +183,7 @@ struct TardisMcContext {
     DevBuf vlog_count, vlog_packet, vlog_seq, vlog_nu, vlog_energy, vlog_mu, vlog_r;
     long long vlog_capacity = 0;
     bool vlog_capacity_user = false;  // set through the vpacket_log_capacity option (otherwise sized per propagate call)
-    // full r-packet tracking (option track_full, event_log.hpp): runs on the lane kernel; the row pool, its chunk fills, {pool_next, dropped},
+    // full r-packet tracking (option track_full, event_log.hpp): runs on the wave kernel (variant 2) where that can run the call, else on the lane kernel; the row pool, its chunk fills, {pool_next, dropped},
     // the per-packet counts, and for tardis_mc_get_event_log the offsets, the tile sums of their scan and the packet-major columns
     bool track_full = false;
     long long evlog_capacity = 0;                    // option event_log_capacity: rows (0: automatic, 32 per packet)
@@ -194,7 +197,7 @@ struct TardisMcContext {
     mc::DeviceProblem problem_host{};
     long long chunk_packets = 16LL << 20;  // packets per seeded-state chunk (2496 B each) of the cooperative kernel
     // launch geometry
-    int variant = -1;  // 0: lane-per-packet kernel; 1: group-per-packet kernel; 2: wave-owner kernel, group sweeps; 3: wave-owner kernel, lane sweeps; -1: automatic
+    int variant = -1;  // 0: lane-per-packet kernel; 1: group-per-packet kernel; 2: wave-owner kernel, group sweeps; 3: wave-owner kernel, lane sweeps; 4: wave-owner kernel with the volley queue; -1: automatic
     bool prob_negative = false;  // a negative transition probability: the running sums are not monotone, no jump search
     bool walk_min_active_user = false, ls_min_active_user = false;  // (set through the options: no automatic choice then)
     int walk_min_active = 8;  // compact macro-atom walk: carry the longest chains over to the next pass once this few lanes still walk (-1: never)
@@ -231,7 +234,7 @@ struct TardisMcContext {
     hipStream_t stream_prop_m = nullptr, stream_pass_m = nullptr;
     hipEvent_t ev_fork_m = nullptr, ev_join_m = nullptr;
     DevBuf log_records[2], log_keys[2], log_cursor[2], log_bins[2], log_sorted[2], wave_cold_dev;
-    DevBuf seed_chk[2], vp_scratch[2];  // (vp_scratch: per buffer set -- chunks on the two streams overlap)
+    DevBuf seed_chk, vp_scratch;       // wave kernel: the launch records of a call's packets | the v-packet results handed from worker to owner lanes
     DevBuf vp_park;                     // pooled volleys with carry-over: one parked v-packet per lane
     int vp_carry_min_active = 16;       // pooled volleys: leave the volley phase once nothing waits and this few lanes still trace (0: never).  16: -7 % on the
                                         // configs[4] shape, -5 % on the tardis_example shape + 10 v-packets, flat from 16 to 32 (profiles/r05_volley_carry.txt)
@@ -751,20 +754,114 @@ mc::DeviceProblem make_device_problem(TardisMcContext *ctx)
     return P;
 }
 
-template <bool FULL, bool VPK>
-void launch_lane(TardisMcContext *ctx, const mc::DeviceProblem &P, int blocks, size_t lds)
+// ---- The kernel tables: every instantiation of the three propagation kernels that exists, keyed by its template arguments (in their order).
+// A call computes its key once and looks the kernel up; a key that is not in its table is a programming error, which the lookup reports.
+struct LaneKernelKey { bool full, vpk, track, full_tracking; };
+struct GroupKernelKey { bool full, track; int width, block, occupancy; bool vpk, wide; };
+struct WaveKernelKey {
+    bool full, track;
+    int width;  // lanes per sweep worker
+    bool vpk, lane_sweep, xwalk;
+    int waves_per_simd, nt;  // the register budget | the interleaved sweep table: 0 none, 1 runs from the current line, 2 aligned runs
+    bool shell_log, full_tracking, wide;  // (wide: 64-bit table offsets)
+};
+bool operator==(const LaneKernelKey &a, const LaneKernelKey &b) { return a.full == b.full && a.vpk == b.vpk && a.track == b.track && a.full_tracking == b.full_tracking; }
+bool operator==(const GroupKernelKey &a, const GroupKernelKey &b)
 {
-    if (P.evlog.rows) {  // full r-packet tracking: 8 ints of LDS per workgroup for the waves' append state
-        if (ctx->track)
-            hipLaunchKernelGGL((mc::propagate_lane_kernel<FULL, VPK, true, true>), dim3(blocks), dim3(256), lds + 32, ctx->stream, P);
-        else
-            hipLaunchKernelGGL((mc::propagate_lane_kernel<FULL, VPK, false, true>), dim3(blocks), dim3(256), lds + 32, ctx->stream, P);
-        return;
-    }
-    if (ctx->track)
-        hipLaunchKernelGGL((mc::propagate_lane_kernel<FULL, VPK, true>), dim3(blocks), dim3(256), lds, ctx->stream, P);
-    else
-        hipLaunchKernelGGL((mc::propagate_lane_kernel<FULL, VPK, false>), dim3(blocks), dim3(256), lds, ctx->stream, P);
+    return a.full == b.full && a.track == b.track && a.width == b.width && a.block == b.block && a.occupancy == b.occupancy && a.vpk == b.vpk && a.wide == b.wide;
+}
+bool operator==(const WaveKernelKey &a, const WaveKernelKey &b)
+{
+    return a.full == b.full && a.track == b.track && a.width == b.width && a.vpk == b.vpk && a.lane_sweep == b.lane_sweep && a.xwalk == b.xwalk &&
+           a.waves_per_simd == b.waves_per_simd && a.nt == b.nt && a.shell_log == b.shell_log && a.full_tracking == b.full_tracking && a.wide == b.wide;
+}
+using LaneKernelFn = void (*)(mc::DeviceProblem);
+using GroupKernelFn = void (*)(mc::GroupArgs, uint32_t *, long long, long long);
+using WaveKernelFn = void (*)(mc::WaveHot, const mc::WaveCold *);
+template <typename Key, typename Fn> struct KernelRow { Key key; Fn fn; };
+template <typename Key, typename Fn, size_t N>
+Fn find_kernel(const KernelRow<Key, Fn> (&table)[N], const Key &key)
+{
+    for (const auto &row : table)
+        if (row.key == key) return row.fn;
+    return nullptr;
+}
+#define KROW(KERNEL, ...) {{__VA_ARGS__}, mc::propagate_##KERNEL##_kernel<__VA_ARGS__>}
+const KernelRow<LaneKernelKey, LaneKernelFn> LANE_KERNELS[] = {  // FULL, VPK, TRACK, FT
+    // (the second half: full r-packet tracking)
+    KROW(lane, 0, 0, 0, 0), KROW(lane, 0, 0, 1, 0), KROW(lane, 0, 1, 0, 0), KROW(lane, 0, 1, 1, 0),
+    KROW(lane, 1, 0, 0, 0), KROW(lane, 1, 0, 1, 0), KROW(lane, 1, 1, 0, 0), KROW(lane, 1, 1, 1, 0),
+    KROW(lane, 0, 0, 0, 1), KROW(lane, 0, 0, 1, 1), KROW(lane, 0, 1, 0, 1), KROW(lane, 0, 1, 1, 1),
+    KROW(lane, 1, 0, 0, 1), KROW(lane, 1, 0, 1, 1), KROW(lane, 1, 1, 0, 1), KROW(lane, 1, 1, 1, 1),
+};
+const KernelRow<GroupKernelKey, GroupKernelFn> GROUP_KERNELS[] = {  // FULL, TRACK, G, BLOCK, OCC, VPK, WIDE
+    // (the second half: 64-bit table offsets)
+    KROW(group, 0, 0, 8, 256, 4, 0, 0), KROW(group, 0, 1, 8, 256, 4, 0, 0), KROW(group, 1, 0, 8, 256, 4, 0, 0), KROW(group, 1, 1, 8, 256, 4, 0, 0),
+    KROW(group, 0, 0, 16, 256, 4, 0, 0), KROW(group, 0, 1, 16, 256, 4, 0, 0), KROW(group, 1, 0, 16, 256, 4, 0, 0), KROW(group, 1, 1, 16, 256, 4, 0, 0),
+    KROW(group, 0, 0, 8, 256, 4, 1, 0), KROW(group, 0, 1, 8, 256, 4, 1, 0), KROW(group, 1, 0, 8, 256, 4, 1, 0), KROW(group, 1, 1, 8, 256, 4, 1, 0),
+    KROW(group, 0, 0, 16, 256, 4, 1, 0), KROW(group, 0, 1, 16, 256, 4, 1, 0), KROW(group, 1, 0, 16, 256, 4, 1, 0), KROW(group, 1, 1, 16, 256, 4, 1, 0),
+    KROW(group, 0, 0, 8, 256, 4, 0, 1), KROW(group, 0, 1, 8, 256, 4, 0, 1), KROW(group, 1, 0, 8, 256, 4, 0, 1), KROW(group, 1, 1, 8, 256, 4, 0, 1),
+    KROW(group, 0, 0, 16, 256, 4, 0, 1), KROW(group, 0, 1, 16, 256, 4, 0, 1), KROW(group, 1, 0, 16, 256, 4, 0, 1), KROW(group, 1, 1, 16, 256, 4, 0, 1),
+    KROW(group, 0, 0, 8, 256, 4, 1, 1), KROW(group, 0, 1, 8, 256, 4, 1, 1), KROW(group, 1, 0, 8, 256, 4, 1, 1), KROW(group, 1, 1, 8, 256, 4, 1, 1),
+    KROW(group, 0, 0, 16, 256, 4, 1, 1), KROW(group, 0, 1, 16, 256, 4, 1, 1), KROW(group, 1, 0, 16, 256, 4, 1, 1), KROW(group, 1, 1, 16, 256, 4, 1, 1),
+};
+const KernelRow<WaveKernelKey, WaveKernelFn> WAVE_KERNELS[] = {  // FULL, TRACK, G, VPK, LS, XWALK, WPE, NT, SL, FT, WIDE
+    // (XWALK: the instantiations with the macro-atom walks on the fp64 running sums compiled in -- only launched when the compact
+    // walk tables are not used: debug flags 128 / 8192, tables too large; the production ones are 22 % shorter without them)
+    // group sweeps, sweep width 4 / 8 / 16; XWALK: with the macro-atom walks on the fp64 running sums compiled in (cross-checks, no compact walk tables)
+    KROW(wave, 0, 0, 4, 0, 0, 0, 4, 0, 0, 0, 0), KROW(wave, 0, 1, 4, 0, 0, 0, 4, 0, 0, 0, 0), KROW(wave, 1, 0, 4, 0, 0, 0, 4, 0, 0, 0, 0), KROW(wave, 1, 1, 4, 0, 0, 0, 4, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 8, 0, 0, 0, 4, 0, 0, 0, 0), KROW(wave, 0, 1, 8, 0, 0, 0, 4, 0, 0, 0, 0), KROW(wave, 1, 0, 8, 0, 0, 0, 4, 0, 0, 0, 0), KROW(wave, 1, 1, 8, 0, 0, 0, 4, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 16, 0, 0, 0, 4, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 0, 0, 0, 4, 0, 0, 0, 0), KROW(wave, 1, 0, 16, 0, 0, 0, 4, 0, 0, 0, 0), KROW(wave, 1, 1, 16, 0, 0, 0, 4, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 4, 1, 0, 0, 3, 0, 0, 0, 0), KROW(wave, 0, 1, 4, 1, 0, 0, 3, 0, 0, 0, 0), KROW(wave, 1, 0, 4, 1, 0, 0, 3, 0, 0, 0, 0), KROW(wave, 1, 1, 4, 1, 0, 0, 3, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 8, 1, 0, 0, 3, 0, 0, 0, 0), KROW(wave, 0, 1, 8, 1, 0, 0, 3, 0, 0, 0, 0), KROW(wave, 1, 0, 8, 1, 0, 0, 3, 0, 0, 0, 0), KROW(wave, 1, 1, 8, 1, 0, 0, 3, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 16, 1, 0, 0, 3, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 1, 0, 0, 3, 0, 0, 0, 0), KROW(wave, 1, 0, 16, 1, 0, 0, 3, 0, 0, 0, 0), KROW(wave, 1, 1, 16, 1, 0, 0, 3, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 4, 0, 0, 1, 4, 0, 0, 0, 0), KROW(wave, 0, 1, 4, 0, 0, 1, 4, 0, 0, 0, 0), KROW(wave, 1, 0, 4, 0, 0, 1, 4, 0, 0, 0, 0), KROW(wave, 1, 1, 4, 0, 0, 1, 4, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 8, 0, 0, 1, 4, 0, 0, 0, 0), KROW(wave, 0, 1, 8, 0, 0, 1, 4, 0, 0, 0, 0), KROW(wave, 1, 0, 8, 0, 0, 1, 4, 0, 0, 0, 0), KROW(wave, 1, 1, 8, 0, 0, 1, 4, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 16, 0, 0, 1, 4, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 0, 0, 1, 4, 0, 0, 0, 0), KROW(wave, 1, 0, 16, 0, 0, 1, 4, 0, 0, 0, 0), KROW(wave, 1, 1, 16, 0, 0, 1, 4, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 4, 1, 0, 1, 3, 0, 0, 0, 0), KROW(wave, 0, 1, 4, 1, 0, 1, 3, 0, 0, 0, 0), KROW(wave, 1, 0, 4, 1, 0, 1, 3, 0, 0, 0, 0), KROW(wave, 1, 1, 4, 1, 0, 1, 3, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 8, 1, 0, 1, 3, 0, 0, 0, 0), KROW(wave, 0, 1, 8, 1, 0, 1, 3, 0, 0, 0, 0), KROW(wave, 1, 0, 8, 1, 0, 1, 3, 0, 0, 0, 0), KROW(wave, 1, 1, 8, 1, 0, 1, 3, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 16, 1, 0, 1, 3, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 1, 0, 1, 3, 0, 0, 0, 0), KROW(wave, 1, 0, 16, 1, 0, 1, 3, 0, 0, 0, 0), KROW(wave, 1, 1, 16, 1, 0, 1, 3, 0, 0, 0, 0),
+    // lane sweeps (partial relativity only; the sweep width is that of the cross-check walks)
+    KROW(wave, 0, 0, 16, 0, 1, 0, 4, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 0, 1, 0, 4, 0, 0, 0, 0), KROW(wave, 0, 0, 16, 1, 1, 0, 3, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 1, 1, 0, 3, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 16, 0, 1, 1, 4, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 0, 1, 1, 4, 0, 0, 0, 0), KROW(wave, 0, 0, 16, 1, 1, 1, 3, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 1, 1, 1, 3, 0, 0, 0, 0),
+    // v-packets with the register budget of two waves per SIMD (vpk_wide_registers)
+    KROW(wave, 0, 0, 8, 1, 0, 0, 2, 0, 0, 0, 0), KROW(wave, 0, 1, 8, 1, 0, 0, 2, 0, 0, 0, 0), KROW(wave, 1, 0, 8, 1, 0, 0, 2, 0, 0, 0, 0), KROW(wave, 1, 1, 8, 1, 0, 0, 2, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 16, 1, 0, 0, 2, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 1, 0, 0, 2, 0, 0, 0, 0), KROW(wave, 1, 0, 16, 1, 0, 0, 2, 0, 0, 0, 0), KROW(wave, 1, 1, 16, 1, 0, 0, 2, 0, 0, 0, 0),
+    KROW(wave, 0, 0, 16, 1, 1, 0, 2, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 1, 1, 0, 2, 0, 0, 0, 0),
+    // lane sweeps at three waves per SIMD (ls_waves_per_simd: B); the interleaved sweep table (sweep_table) at three and four
+    KROW(wave, 0, 0, 16, 0, 1, 0, 3, 0, 0, 0, 0), KROW(wave, 0, 1, 16, 0, 1, 0, 3, 0, 0, 0, 0), KROW(wave, 0, 0, 16, 0, 1, 0, 3, 1, 0, 0, 0), KROW(wave, 0, 1, 16, 0, 1, 0, 3, 1, 0, 0, 0),
+    KROW(wave, 0, 0, 16, 0, 1, 0, 4, 1, 0, 0, 0), KROW(wave, 0, 1, 16, 0, 1, 0, 4, 1, 0, 0, 0), KROW(wave, 0, 0, 16, 0, 1, 0, 4, 2, 0, 0, 0), KROW(wave, 0, 1, 16, 0, 1, 0, 4, 2, 0, 0, 0),
+    // the shell-sorted log (log_by_shell)
+    KROW(wave, 0, 0, 16, 0, 1, 0, 3, 0, 1, 0, 0), KROW(wave, 0, 1, 16, 0, 1, 0, 3, 0, 1, 0, 0), KROW(wave, 0, 0, 16, 0, 1, 0, 4, 1, 1, 0, 0), KROW(wave, 0, 1, 16, 0, 1, 0, 4, 1, 1, 0, 0),
+    // full r-packet tracking (track_full)
+    KROW(wave, 0, 1, 16, 0, 0, 0, 4, 0, 0, 1, 0), KROW(wave, 1, 1, 16, 0, 0, 0, 4, 0, 0, 1, 0), KROW(wave, 0, 1, 16, 1, 0, 0, 3, 0, 0, 1, 0), KROW(wave, 1, 1, 16, 1, 0, 0, 3, 0, 0, 1, 0),
+    // 64-bit table offsets (table_offsets): group sweeps of width 8 / 16, lane sweeps, full tracking
+    KROW(wave, 0, 0, 8, 0, 0, 0, 4, 0, 0, 0, 1), KROW(wave, 0, 1, 8, 0, 0, 0, 4, 0, 0, 0, 1), KROW(wave, 1, 0, 8, 0, 0, 0, 4, 0, 0, 0, 1), KROW(wave, 1, 1, 8, 0, 0, 0, 4, 0, 0, 0, 1),
+    KROW(wave, 0, 0, 16, 0, 0, 0, 4, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 0, 0, 0, 4, 0, 0, 0, 1), KROW(wave, 1, 0, 16, 0, 0, 0, 4, 0, 0, 0, 1), KROW(wave, 1, 1, 16, 0, 0, 0, 4, 0, 0, 0, 1),
+    KROW(wave, 0, 0, 8, 1, 0, 0, 3, 0, 0, 0, 1), KROW(wave, 0, 1, 8, 1, 0, 0, 3, 0, 0, 0, 1), KROW(wave, 1, 0, 8, 1, 0, 0, 3, 0, 0, 0, 1), KROW(wave, 1, 1, 8, 1, 0, 0, 3, 0, 0, 0, 1),
+    KROW(wave, 0, 0, 16, 1, 0, 0, 3, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 1, 0, 0, 3, 0, 0, 0, 1), KROW(wave, 1, 0, 16, 1, 0, 0, 3, 0, 0, 0, 1), KROW(wave, 1, 1, 16, 1, 0, 0, 3, 0, 0, 0, 1),
+    KROW(wave, 0, 0, 16, 1, 1, 0, 3, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 1, 1, 0, 3, 0, 0, 0, 1), KROW(wave, 0, 0, 16, 0, 1, 0, 3, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 0, 1, 0, 3, 0, 0, 0, 1),
+    KROW(wave, 0, 0, 16, 0, 1, 0, 4, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 0, 1, 0, 4, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 0, 0, 0, 4, 0, 0, 1, 1), KROW(wave, 1, 1, 16, 0, 0, 0, 4, 0, 0, 1, 1),
+    KROW(wave, 0, 1, 16, 1, 0, 0, 3, 0, 0, 1, 1), KROW(wave, 1, 1, 16, 1, 0, 0, 3, 0, 0, 1, 1),
+};
+#undef KROW
+
+size_t wave_kernel_lds(const WaveKernelKey &k, int n_shells)  // dynamic LDS of an instantiation of the wave kernel
+{
+    if (k.shell_log) return mc::wave_kernel_lds_bytes<false, false, true, true>(n_shells);
+    if (k.lane_sweep) return k.vpk ? mc::wave_kernel_lds_bytes<false, true, true>(n_shells) : mc::wave_kernel_lds_bytes<false, false, true>(n_shells);
+    return k.vpk ? (k.full ? mc::wave_kernel_lds_bytes<true, true>(n_shells) : mc::wave_kernel_lds_bytes<false, true>(n_shells))
+                 : (k.full ? mc::wave_kernel_lds_bytes<true, false>(n_shells) : mc::wave_kernel_lds_bytes<false, false>(n_shells));
+}
+
+int launch_lane(TardisMcContext *ctx, const mc::DeviceProblem &P, int blocks, size_t lds)
+{
+    const bool ft = P.evlog.rows != nullptr;  // full r-packet tracking: 8 ints of LDS per workgroup for the waves' append state
+    const LaneKernelFn k = find_kernel(LANE_KERNELS, LaneKernelKey{ctx->cfg.enable_full_relativity != 0, ctx->cfg.number_of_vpackets > 0, ctx->track, ft});
+    if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the lane kernel");
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds + (ft ? 32 : 0), ctx->stream, P);
+    HIP_TRY(ctx, hipGetLastError());
+    return TARDIS_MC_OK;
 }
 
 // Full r-packet tracking: size the row pool of this call (rows the caller asked for, plus one chunk per wave for the
@@ -806,6 +903,1012 @@ int setup_event_log(TardisMcContext *ctx, mc::DeviceProblem &P, long long n_wave
     ctx->ev_slots = slots;
     ctx->ev_n_chunks = (unsigned)chunks;
     return TARDIS_MC_OK;
+}
+
+// ---- tardis_mc_propagate: what the entry point hands to the runner of its call (run_lane_kernel / run_group_kernel / run_wave_kernel)
+struct PropagateCall {
+    plan::Plan plan;
+    int cus;
+    bool vpk, full;
+    bool rs_armed;      // result streaming was armed for this call (tardis_mc_stream_results holds for one call)
+    int tune_pending;   // the lane-sweep tuner: whether the previous propagate call was one of its timed ones: 2 * instantiation + sample, else -1
+    int tune_slot;      // this call is a timed one of the tuner (becomes ls_tune.pending once it has been enqueued completely)
+};
+
+plan::PlanInput plan_input(const TardisMcContext *ctx)
+{
+    const TardisMcConfig &c = ctx->cfg;
+    plan::PlanInput in{};
+    in.n_shells = ctx->n_shells; in.n_lines = ctx->n_lines; in.n_trans = ctx->n_trans; in.n_packets = ctx->n_packets;
+    in.number_of_vpackets = c.number_of_vpackets; in.survival_probability = c.survival_probability;
+    in.enable_full_relativity = c.enable_full_relativity; in.line_interaction_type = c.line_interaction_type;
+    in.lines_sorted = ctx->lines_sorted; in.prob_negative = ctx->prob_negative; in.have_walk_tables = ctx->have_walk_tables;
+    in.variant = ctx->variant; in.table_offsets = ctx->table_offsets; in.vpacket_screening = ctx->vpacket_screening;
+    in.vpk_wave_min_packets = ctx->vpk_wave_min_packets; in.track_full = ctx->track_full; in.debug_flags = ctx->debug_flags;
+    in.pfx_valid = ctx->pfx_valid; in.pfx_negative = ctx->pfx_negative;
+    return in;
+}
+
+// the v-packet screening tables (tau_prefix.hpp): built by the first v-packet call after set_opacity that screens; a launch and a read-back of the negative-depth flag
+int build_screening_tables(TardisMcContext *ctx)
+{
+    if (ctx->pfx_valid) return TARDIS_MC_OK;
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines;
+    HIP_TRY(ctx, ctx->tau_pfx.ensure((S * (L + 1) + 8) * sizeof(double)));  // (+8: the four-entry windows of the screening)
+    HIP_TRY(ctx, ctx->tau_rowsum.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pfx_flag.ensure(sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->pfx_flag.p, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(mc::tau_prefix_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, ctx->tau_t.as<double>(), (int)L,
+                       ctx->tau_pfx.as<double>(), ctx->tau_rowsum.as<double>(), ctx->pfx_flag.as<int>());
+    HIP_TRY(ctx, hipGetLastError());
+    int neg = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&neg, ctx->pfx_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->pfx_negative = neg != 0;
+    ctx->pfx_valid = true;
+    return TARDIS_MC_OK;
+}
+
+// the interleaved sweep table (option sweep_table): built by the first propagate call after set_opacity that uses it; like the screening tables a launch and a
+// read-back (nt_negative: the lean proof of the NT kernels does not apply).  Tables whose padded rows reach 2^28 entries have none.
+int build_sweep_table(TardisMcContext *ctx)
+{
+    const unsigned long long stride = ((unsigned long long)ctx->n_lines + 7ull) & ~7ull;
+    if (ctx->nt_valid || stride * (unsigned long long)ctx->n_shells + 32ull >= (1ull << 28)) return TARDIS_MC_OK;
+    const long long total = (long long)(stride * (unsigned long long)ctx->n_shells) + 32;  // (+ the slack of a step's loads behind the last row)
+    HIP_TRY(ctx, ctx->nt_t.ensure((size_t)total * 16));
+    HIP_TRY(ctx, ctx->pfx_flag.ensure(sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->pfx_flag.p, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(interleave_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 65536)), dim3(256), 0, ctx->stream, ctx->nu_line.as<double>(),
+                       ctx->tau_t.as<double>(), ctx->nt_t.as<double2>(), (long long)ctx->n_lines, (long long)ctx->n_shells, (long long)stride, total,
+                       ctx->pfx_flag.as<int>());
+    HIP_TRY(ctx, hipGetLastError());
+    int neg = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&neg, ctx->pfx_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->nt_negative = neg != 0;
+    ctx->nt_stride = (unsigned)stride;
+    ctx->nt_valid = true;
+    return TARDIS_MC_OK;
+}
+
+// The lane-sweep tuner (see ls_waves_per_simd and ls_tune in the context): which of the two production lane-sweep instantiations this call runs -- A (four waves per
+// SIMD) or B (three: *ls3) -- forced by the option, or timed on the first calls of this key; call.tune_slot says which timed slot this call is, if any.
+int lane_sweep_tuner(TardisMcContext *ctx, PropagateCall &call, bool *ls3)
+{
+    auto &tn = ctx->ls_tune;
+    const bool w64 = call.plan.w64;
+    const int mode = ctx->cfg.line_interaction_type;
+    *ls3 = false;
+    // (a call that does not even fill the grid's lanes four times over is nothing but the drain of its longest packets: B, measured -6 % on
+    // 1e5 - 1e6-packet calls of the tardis_example shape, without spending five calls of a 20-iteration run on finding that out)
+    const bool all_drain = ctx->n_packets < 4LL * 64 * 16 * call.cus;
+    if (ctx->ls_waves_per_simd == 3 || (ctx->ls_waves_per_simd == 0 && all_drain)) *ls3 = true;
+    else if (ctx->ls_waves_per_simd == 0 && ctx->pass_cus == 0) {
+        if (tn.n != ctx->n_packets || tn.lines != ctx->n_lines || tn.shells != ctx->n_shells || tn.mode != mode || tn.table != ctx->sweep_table || tn.wide != (int)w64) {
+            tn.n = ctx->n_packets; tn.lines = ctx->n_lines; tn.shells = ctx->n_shells; tn.mode = mode; tn.table = ctx->sweep_table;
+            tn.wide = (int)w64;
+            tn.phase = 0; tn.choice = 0;
+            tn.ms[0][0] = tn.ms[0][1] = tn.ms[1][0] = tn.ms[1][1] = -1.0;
+        } else if (call.tune_pending >= 0) {  // the previous call of this key was a timed one: its duration (propagation + passes)
+            float ms = 0.f;
+            HIP_TRY(ctx, hipEventSynchronize(ctx->ev_tune[1]));
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_tune[0], ctx->ev_tune[1]));
+            tn.ms[call.tune_pending >> 1][call.tune_pending & 1] = ms;
+        } else if (tn.phase >= 2 && tn.phase <= 5)
+            tn.phase -= 1;  // the previous phase was a timed call and left no measurement (the call failed half-way): again
+        // call 0: A, not timed (first-call allocations, the log sized from a guess); calls 1 / 3: A; calls 2 / 4: B; from call 5 on: the choice
+        if (tn.phase == 0) *ls3 = false;
+        else if (tn.phase <= 4) { *ls3 = (tn.phase & 1) == 0; call.tune_slot = 2 * (*ls3 ? 1 : 0) + ((tn.phase - 1) >> 1); }
+        else {
+            if (tn.phase == 5) {
+                const bool all = tn.ms[0][0] > 0.0 && tn.ms[0][1] > 0.0 && tn.ms[1][0] > 0.0 && tn.ms[1][1] > 0.0;
+                tn.choice = (all && std::min(tn.ms[1][0], tn.ms[1][1]) < 0.97 * std::min(tn.ms[0][0], tn.ms[0][1])) ? 1 : 0;
+            }
+            *ls3 = tn.choice == 1;
+        }
+        if (tn.phase < 6) ++tn.phase;
+        if (call.tune_slot >= 0)
+            for (int k = 0; k < 2; ++k)
+                if (!ctx->ev_tune[k]) HIP_TRY(ctx, hipEventCreate(&ctx->ev_tune[k]));
+    }
+    return TARDIS_MC_OK;
+}
+
+// ---- the wave kernel of a call: its key, computed once from the plan and the options before anything is launched, and what the host decided on the way
+struct WaveChoice {
+    WaveKernelKey key;
+    WaveKernelFn fn;
+    size_t lds;
+    int waves_per_cu;      // what the LDS and option waves_per_simd allow (the instantiation's own bound comes on top: max_waves_per_cu)
+    int max_waves_per_cu;
+    bool compact_walk, ls3;
+    int tiles, n_bins;     // tiles of EST_TILE lines per shell, (shell, tile) bins of the line-visit log
+    bool partition;        // est_pipeline 1 (estimator_partition.hpp): the records are grouped by shell, then by bin
+};
+
+int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P, WaveChoice &w)
+{
+    const TardisMcConfig &c = ctx->cfg;
+    const bool vpk = call.vpk, full = call.full, w64 = call.plan.w64, vq = call.plan.variant == 4;
+    WaveKernelKey &k = w.key;
+    k = WaveKernelKey{};
+    k.full = full; k.track = ctx->track; k.vpk = vpk;
+    k.lane_sweep = call.plan.variant == 3 && !full;  // (the bounds of the lane sweep are those of partial relativity)
+    k.waves_per_simd = vpk ? 3 : 4;
+    if (wave_kernel_lds(k, ctx->n_shells) > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
+    w.waves_per_cu = std::max(1, std::min(ctx->waves_per_simd > 0 ? 4 * ctx->waves_per_simd : 16, (int)((160 * 1024) / wave_kernel_lds(k, ctx->n_shells))));
+    // macro-atom jumps of the wave kernel (macroatom chains and the single jump of downbranch alike): per-lane walk on the
+    // compact tables (walk_tables.hpp); debug flag 8192 keeps the cooperative group scan of the fp64 running sums (macroatom) /
+    // the fp64 search (downbranch), 128 the per-lane search in them (both for cross-checks)
+    w.compact_walk = c.line_interaction_type != 0 && ctx->have_walk_tables && !(ctx->debug_flags & plan::DBG_FP64_WALKS);
+    // (flag 1048576: the long instantiations, for A/B; the flags that read the kernel's profiling / test counters: those are only compiled into the long ones)
+    k.xwalk = (c.line_interaction_type != 0 && !w.compact_walk) || (ctx->debug_flags & (plan::DBG_LONG_INSTANTIATIONS | plan::DBG_WAVE_COUNTERS)) != 0;
+    if (w64 && k.xwalk) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "the fp64 macro-atom walks have no 64-bit table offsets");
+    // (sweep-worker width of the wave kernel: 8 lanes for sparse line lists, 16 for long ones, like the group kernel; the lane-sweep
+    // instantiations only use it in the cross-check walks: one width)
+    const int GW = ctx->group_size ? ctx->group_size : (ctx->n_lines <= 100000 ? 8 : 16);
+    k.width = k.lane_sweep ? 16 : GW;
+    // v-packets on a grid so fine that the per-shell LDS arrays leave room for at most eight waves per CU (two per SIMD): the
+    // instantiation compiled for two waves per SIMD -- 239 VGPRs, no spills -- costs no occupancy there (built for the sweep widths G = 16 and
+    // G = 8, without the cross-check walks; option vpk_wide_registers 0 keeps the 168-VGPR one)
+    // Measured (profiles/r05_vpk_wide_registers.txt): 3727-3766 vs 4442-4450 ms per 1e7 packets of the configs[4] shape (-16 %).  Option 2 forces
+    // it (then eight waves per CU whatever the LDS allows), 0 keeps the 168-VGPR instantiation.
+    // (with lane sweeps: variant 3 under partial relativity)
+    if (vpk && !k.xwalk && !w64 && !ctx->track_full && (k.lane_sweep || GW == 16 || GW == 8) &&
+        ((ctx->vpk_wide_registers == 1 && w.waves_per_cu <= 8) || ctx->vpk_wide_registers == 2))
+        k.waves_per_simd = 2;
+    // which lane-sweep instantiation (see ls_waves_per_simd in the context), and whether on the interleaved sweep table: the production lane-sweep instantiations only
+    w.ls3 = false;
+    if (k.lane_sweep && !vpk && !k.xwalk) {
+        int rc = lane_sweep_tuner(ctx, call, &w.ls3);
+        if (rc) return rc;
+        if (w.ls3) k.waves_per_simd = 3;
+        if (!w64 && ctx->sweep_table != 0) {
+            rc = build_sweep_table(ctx);
+            if (rc) return rc;
+            if (ctx->nt_valid && !ctx->nt_negative) {
+                k.nt = (ctx->sweep_table == 2 && !w.ls3) ? 2 : 1;
+                P.nt_t = ctx->nt_t.as<double>(); P.nt_stride = ctx->nt_stride;
+            }
+        }
+    }
+    w.max_waves_per_cu = k.waves_per_simd == 2 ? 8 : (w.ls3 ? 12 : 16);
+    w.tiles = std::max((ctx->n_lines + mc::EST_TILE - 1) / mc::EST_TILE, 1);
+    w.n_bins = ctx->n_shells * w.tiles;
+    // est_pipeline 1 (estimator_partition.hpp): needs a shell's bins and all shells to fit the partition kernel's local buckets
+    w.partition = ctx->est_pipeline == 1 && w.tiles <= mc::PART_LOCAL_BUCKETS && ctx->n_shells <= mc::PART_LOCAL_BUCKETS;
+    // the shell-sorted log: instantiated for the two production lane-sweep kernels (sixteen waves on the interleaved table, twelve on the separate ones)
+    k.shell_log = k.lane_sweep && !vpk && !k.xwalk && !w64 && !vq && w.partition && ctx->log_by_shell != 0 && ctx->n_shells <= 64 &&
+                  ((!w.ls3 && k.nt == 1) || (w.ls3 && k.nt == 0));
+    if (ctx->track_full) {  // the tracked instantiations: group sweeps of 16 lanes, compact walks, default register budget
+        k.full_tracking = true; k.track = true; k.width = 16;
+    }
+    // 64-bit row offsets: the production shapes above without the interleaved sweep table, the shell-sorted log and the two-waves-per-SIMD
+    // v-packet form (those keep 32-bit offsets); sweep width 4 runs as 8 (per-packet results do not depend on the width)
+    if (w64) { k.wide = true; if (k.width == 4) k.width = 8; }
+    w.fn = find_kernel(WAVE_KERNELS, k);
+    if (!w.fn) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the wave kernel");
+    w.lds = wave_kernel_lds(k, ctx->n_shells);
+    return TARDIS_MC_OK;
+}
+
+// ---- The line-visit log (estimator_log.hpp): how much device memory it may take.  What is free plus what the log holds already (a context is cached: the
+// buffers of an earlier call are reused or replaced); known = false when the runtime does not say.
+struct LogMemory { bool known; double avail, total; };
+LogMemory log_memory(const TardisMcContext *ctx)
+{
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return LogMemory{false, 0.0, 0.0};
+    const double have = (double)(ctx->log_records[0].cap + ctx->log_records[1].cap + ctx->log_keys[0].cap + ctx->log_keys[1].cap +
+                                 ctx->log_sorted[0].cap + ctx->log_sorted[1].cap + ctx->log_part.cap);
+    return LogMemory{true, (double)free_b + have, (double)total_b};
+}
+// bytes per record of a set's capacity: every set holds the record and its key, and its own index (the sort) or a share of the one scratch copy (the partition)
+constexpr double LOG_RECORD_BYTES = (double)(sizeof(mc::LineVisitRecord) + sizeof(unsigned));
+double log_bytes_per_record(int sets, bool partition)
+{
+    return partition ? sets * LOG_RECORD_BYTES + (double)sizeof(mc::LineVisitRecord) : sets * (LOG_RECORD_BYTES + (double)sizeof(unsigned));
+}
+constexpr double LOG_MEMORY_SHARE = 0.6;  // never take more than 60 % of what is free, counting what the log holds already
+
+struct LogSizing {
+    bool one_set;
+    int n_sets;
+    unsigned region_capacity;    // records per chunk
+    unsigned long long n_chunks;
+    size_t set_records;
+    double tail_records;
+    bool tail_plan, tail_possible, want_split, want_compact, set1_inside;
+};
+
+// Two buffer sets, one region per wave; an epoch ends when the regions are full.  Sized for the whole call when that fits log_capacity (1.2x the traces
+// per packet measured in the last call, 128 per packet before anything was measured), else log_capacity.
+int size_line_log(TardisMcContext *ctx, const PropagateCall &call, const WaveChoice &w, long long n, int waves, bool cu_split, LogSizing &s)
+{
+    const bool vpk = call.vpk, vq = call.plan.variant == 4, partition = w.partition, shell_log = w.key.shell_log;
+    long long log_capacity = ctx->log_capacity;
+    // One log set or two.  Two let the passes of an epoch run on a second stream beside the next launch -- but they do not fit beside sixteen resident waves per CU,
+    // so "beside" means: contending with the next launch's first 0.1 s, both slower for it.  Measured at 1e8 packets (profiles/r06_log_sets.txt): the passes before
+    // the next launch, alone on the chip, are faster in total, and one set leaves room for epochs half as many again (three launches instead of five): -0.5 %.
+    // So a call of many epochs uses one set; shorter calls keep two (the passes of the bulk run beside the drain of the last launch).
+    s.one_set = ctx->log_sets == 1;
+    if (ctx->log_sets == 0 && partition && !vq && !vpk && ctx->drain_split == 0 && ctx->drain_compact == 0 && ctx->epoch_split == 0 && ctx->pass_cus == 0) {
+        double two_set_capacity = (double)ctx->log_capacity;
+        if (!ctx->log_capacity_user) {
+            const LogMemory m = log_memory(ctx);
+            if (m.known) two_set_capacity = std::min(two_set_capacity, LOG_MEMORY_SHARE * m.avail / log_bytes_per_record(2, true));
+        }
+        // (four epochs or more with two sets; at two or three the passes of the first epochs still find room beside the last launch's drain: 4e7 packets
+        // 1 292 - 1 308 ms with two sets, 1 320 - 1 351 with one)
+        const double per_packet = ctx->traces_per_packet > 0.0 ? 1.05 * ctx->traces_per_packet : ctx->log_budget_per_packet;
+        s.one_set = (double)n * per_packet > 3.0 * two_set_capacity;
+    }
+    if (s.one_set && !ctx->log_capacity_user) {
+        // (the second set of an earlier, smaller call is given back first)
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->stream2) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
+        ctx->log_records[1].release(); ctx->log_keys[1].release(); ctx->log_sorted[1].release(); ctx->log_bins[1].release(); ctx->log_cursor[1].release();
+        log_capacity = 4000000000LL;
+    }
+    LogMemory m{false, 0.0, 0.0};
+    bool asked = false;
+    if (!ctx->log_capacity_user) {
+        // (fewer, longer epochs are faster -- 25.8 vs 24.5 Mpkt/s at 1e8 packets with 2.5e9 instead of 1.5e9 records per set
+        // -- but two sets of 2.5e9 records are 160 GB)
+        m = log_memory(ctx);
+        asked = true;
+        if (m.known) log_capacity = std::min<long long>(log_capacity, (long long)(LOG_MEMORY_SHARE * m.avail / log_bytes_per_record(s.one_set ? 1 : 2, partition)));
+    }
+    unsigned long long cap = std::min<unsigned long long>((unsigned long long)log_capacity,
+                                                          (unsigned long long)((double)n * ctx->log_budget_per_packet) + 64ull * (unsigned long long)waves + 65536ull);
+    if (w.n_bins > mc::EST_MAX_BINS) cap = 0;  // too many tiles for the LDS histogram: the kernel adds its terms directly
+    cap = std::min<unsigned long long>(cap, 0xfffffff0ull);
+    // The log is a pool of chunks the waves take one after the other (EstimatorLog, mc_device.hpp): chunks of up to 4096 records
+    // (~90 passes of a wave: one pool atomic per 7 ms), at least four per wave on average so that the pool runs dry for all
+    // waves at nearly the same time, never fewer than one per wave; a chunk holds >= 256 records (a pass appends up to 64).
+    s.region_capacity = 0;
+    s.n_chunks = 0;
+    if (cap > 0) {
+        // (shell-sorted log: a wave holds an open chunk for every shell -- the pool needs a few more chunks per wave than there are shells; chunks of
+        // 2048 records are what the partition kernel stages at a time.  A caller's own log_capacity (tests) is respected: with fewer chunks than that
+        // the waves that find the pool empty suspend at once and the call takes more epochs)
+        const unsigned long long per_wave = shell_log ? (unsigned long long)(ctx->n_shells + 4) : 4ull;
+        s.region_capacity = ctx->log_chunk_records > 0 ? (unsigned)ctx->log_chunk_records : (shell_log ? 2048u : 4096u);
+        while (s.region_capacity > 256 && (unsigned long long)s.region_capacity * per_wave * (unsigned long long)waves > cap) s.region_capacity >>= 1;
+        s.region_capacity &= ~1u;  // even: a chunk of 24-byte records then starts on a 16-byte boundary (partition_kernel stages with 16-byte loads)
+        s.n_chunks = std::max<unsigned long long>(cap / s.region_capacity, (unsigned long long)waves * ((shell_log && !ctx->log_capacity_user) ? per_wave : 1ull));
+        if (s.n_chunks * s.region_capacity > 0xfffffff0ull) s.n_chunks = 0xfffffff0ull / s.region_capacity;
+    }
+    // Memory check: the tables are resident (set_opacity), what is left must hold the smallest log this grid runs with -- one chunk of 256 records per wave,
+    // in one set
+    if (s.region_capacity > 0) {
+        if (!asked) m = log_memory(ctx);
+        const double least = (double)waves * 256.0 * log_bytes_per_record(1, partition);
+        if (m.known && least > m.avail)
+            return fail(ctx, TARDIS_MC_ERR_HIP, "device memory: the tables leave %.3f GiB of %.1f GiB free, the smallest line-visit log of this call needs "
+                                                "%.3f GiB", m.avail / 1073741824.0, m.total / 1073741824.0, least / 1073741824.0);
+    }
+    const unsigned region_capacity = s.region_capacity;
+    const unsigned long long n_chunks = s.n_chunks;
+    // a second buffer set (the estimator passes of an epoch overlap the next epoch) only when the call may need several epochs
+    // ... or splits off its drain (WaveCold::drain_split): worth a second launch once the call is long enough for a drain to form
+    s.want_split = ctx->drain_split && !vq && !s.one_set && region_capacity > 0 && n >= 64LL * waves * 4;
+    // Tail split: the last epoch of a call should hold only the DRAIN (the ~4 % of the records the longest-lived packets log
+    // after the packet supply has run out, on a mostly idle chip), so that the passes over everything before it run beside the
+    // drain and only the passes of the tail -- milliseconds -- are left for after the call.  The host knows the call's records
+    // from the last call's traces per packet and hands the second-to-last epoch a pool of exactly "what is left minus the
+    // tail"; with the chunk pool that epoch ends for all waves at once.  Also for calls whose log fits ONE epoch (their passes
+    // were not overlapped with anything before).  A wrong estimate only moves the boundary.
+    // (the tail: what the packets in flight when the supply runs out still log -- lanes x ~8 packets' worth of traces, the mean
+    // residual life of a heavy-tailed population; only for calls whose passes are worth a second launch: >= 5e8 records)
+    s.tail_records = (double)ctx->log_tail_packets * ctx->traces_per_packet * 64.0 * (double)waves;
+    // Measured (profiles/r04_tail_split.txt): calls whose log fits one epoch -3 ... -5 % (1e7 - 2e7 packets: their passes ran
+    // after the call before); calls of several epochs +0.5 % (their passes overlap the next epoch already, the extra launch
+    // costs) -- so only the former.
+    const bool one_epoch = (double)region_capacity * (double)n_chunks >= (double)n * ctx->traces_per_packet * 1.05;
+    s.tail_plan = ctx->log_tail_split && !vq && !s.one_set && region_capacity > 0 && ctx->traces_per_packet > 0.0 && one_epoch &&
+                  (double)n * ctx->traces_per_packet >= 5e8 && (double)n * ctx->traces_per_packet > 2.0 * s.tail_records;
+    // (the second buffer set is allocated as soon as a tail split MAY be planned -- the first call of a context has no estimate yet
+    // -- so that no later call of the same size allocates tens of GB in the middle of an iteration)
+    s.tail_possible = ctx->log_tail_split && !vq && !s.one_set && region_capacity > 0 && (double)n * std::max(ctx->traces_per_packet, 16.0) >= 5e8;
+    // ... or packs the drain's live lanes into fewer waves (drain_compact): the passes of the launch before run beside the packed drain
+    s.want_compact = ctx->drain_compact > 0 && !vq && !vpk && !cu_split && !shell_log && !s.one_set && region_capacity > 0 && n > 64LL * (waves - 1) && waves >= 8;
+    const bool several_epochs = region_capacity > 0 && (unsigned long long)region_capacity * n_chunks < (unsigned long long)((double)n * ctx->log_budget_per_packet);
+    s.n_sets = (s.one_set || vq) ? 1 : ((s.tail_plan || s.tail_possible || s.want_split || s.want_compact || several_epochs) ? 2 : 1);
+    s.set_records = (size_t)std::max<unsigned long long>((unsigned long long)region_capacity * n_chunks, 1);
+    // (a two-set call on a context whose first set was sized by a larger one-set call: both sets lie in the first set's buffers -- a second allocation of
+    // tens of GB costs ~1 s the first time, the memory is cleared)
+    s.set1_inside = s.n_sets == 2 && !ctx->log_records[1].p && ctx->log_records[0].cap >= 2 * s.set_records * sizeof(mc::LineVisitRecord) &&
+                    ctx->log_keys[0].cap >= 2 * s.set_records * sizeof(unsigned) && (partition || ctx->log_sorted[0].cap >= 2 * s.set_records * sizeof(unsigned));
+    return TARDIS_MC_OK;
+}
+
+// ---- The wave kernel's call: epochs over one packet supply (see LaneSave).  What is fixed for the call, and below it what the epochs change.
+struct WaveCall {
+    const PropagateCall *call;
+    const WaveChoice *w;
+    const LogSizing *log;
+    mc::GroupArgs P;
+    mc::WaveHot hot;
+    long long n;
+    int waves;
+    bool vq, may_suspend, cu_masked, streaming;
+    hipStream_t st;  // the stream of the propagation launches
+    // -- state of the epoch loop
+    int waves_cur;   // (the grid of the next launch: smaller after a compaction)
+    mc::LaneSave *cur_save; mc::WaveSave *cur_wsave; uint32_t *cur_states;
+    bool split_armed, compact_armed;
+    bool vq_on;      // volley queue: on for the bulk of a call (see wave_epoch_tail_volley_queue)
+    bool call_complete;
+    int log_gen;     // (volley queue: the chunk pool of the shared log is reset after every run of the estimator passes)
+    double records_done;  // (tail split: what the call has logged so far)
+    long long rs_pending_lo, rs_pending_hi;  // result streaming: a range whose unpacking is queued and whose copy the host still has to issue
+    unsigned long long pool_chunks;  // chunks in the pool of the running epoch
+    double split_w2;                 // share of the grid in the second launch of a split epoch
+};
+
+template <typename T> T *log_set_ptr(const LogSizing &s, const DevBuf (&buf)[2], int b) { return s.set1_inside ? buf[0].as<T>() + (size_t)b * s.set_records : buf[b].as<T>(); }
+
+// the accumulate kernel of the estimator passes (option est_accumulate); BINNED: the records lie in bin order (partition pipeline), else `index` does (index sort)
+template <bool FULL, bool BINNED, typename... Args>
+void launch_accumulate_as(int est_accumulate, int cus, hipStream_t es, Args... args)
+{
+    if (est_accumulate == 3)  // the dyadic hierarchy, a lane per record (accumulate_dyadic_kernel<.., LOOP>: 73 KB of LDS, two workgroups per CU)
+        hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<FULL, BINNED, true>), dim3(cus * 2), dim3(64 * mc::ACCD_WAVES), 0, es, args...);
+    else if (est_accumulate == 2)  // the dyadic hierarchy of block sums (accumulate_dyadic_kernel): one workgroup per CU
+        hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<FULL, BINNED>), dim3(cus), dim3(64 * mc::ACCD_WAVES), 0, es, args...);
+    else if (BINNED || est_accumulate == 1)  // one add per aligned block of 8 lines (accumulate_blocks_kernel)
+        hipLaunchKernelGGL((mc::accumulate_blocks_kernel<FULL, BINNED>), dim3(cus * 2), dim3(64 * mc::ACCB_WAVES), 0, es, args...);
+    else if constexpr (!BINNED)  // one add per line visit (index pipeline only)
+        hipLaunchKernelGGL(mc::accumulate_kernel<FULL>, dim3(cus * 3), dim3(64 * mc::ACC_WAVES), 0, es, args...);
+}
+hipError_t launch_accumulate(bool full, bool binned, int est_accumulate, int cus, hipStream_t es, const mc::LineVisitRecord *records, const unsigned *index, const unsigned *bin_start,
+                             const unsigned *slice_start, int n_bins, int tiles_per_shell, int n_lines, const double *nu_line, double *jblue_t, double *edot_t)
+{
+    if (full) {
+        if (binned) launch_accumulate_as<true, true>(est_accumulate, cus, es, records, index, bin_start, slice_start, n_bins, tiles_per_shell, n_lines, nu_line, jblue_t, edot_t);
+        else launch_accumulate_as<true, false>(est_accumulate, cus, es, records, index, bin_start, slice_start, n_bins, tiles_per_shell, n_lines, nu_line, jblue_t, edot_t);
+    } else {
+        if (binned) launch_accumulate_as<false, true>(est_accumulate, cus, es, records, index, bin_start, slice_start, n_bins, tiles_per_shell, n_lines, nu_line, jblue_t, edot_t);
+        else launch_accumulate_as<false, false>(est_accumulate, cus, es, records, index, bin_start, slice_start, n_bins, tiles_per_shell, n_lines, nu_line, jblue_t, edot_t);
+    }
+    return hipGetLastError();
+}
+
+// binning + accumulation of one epoch's line-visit log (estimator_log.hpp): buffer set b, on stream es
+hipError_t estimator_passes(TardisMcContext *ctx, const WaveCall &E, const mc::EstimatorLog &lg, int b, hipStream_t es)
+{
+    if (lg.region_capacity == 0) return hipSuccess;
+    const int cus = E.call->cus, n_bins = E.w->n_bins;
+    const bool full = E.call->full, shell_log = E.w->key.shell_log;
+    unsigned *bin_count = ctx->log_bins[b].as<unsigned>(), *bin_start = bin_count + (n_bins + 1),
+             *bin_fill = bin_start + (n_bins + 1), *slice_start = bin_fill + (n_bins + 1);
+    hipError_t e = hipMemsetAsync(bin_count, 0, (size_t)(n_bins + 1) * sizeof(unsigned), es);
+    if (e != hipSuccess) return e;
+    const size_t hist_lds = (size_t)n_bins * sizeof(unsigned);
+    if (hist_lds > 64 * 1024) {  // more than the default dynamic-LDS limit: BASELINE config 5 has 100 shells x 245 tiles
+        e = hipFuncSetAttribute((const void *)mc::bin_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds);
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute((const void *)mc::bin_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds);
+        if (e != hipSuccess) return e;
+    }
+    const int bin_blocks = cus * 8;
+    hipLaunchKernelGGL(mc::bin_count_kernel, dim3(bin_blocks), dim3(256), hist_lds, es, lg.keys, lg.region_count, lg.n_regions,
+                       lg.region_capacity, n_bins, bin_count);
+    hipLaunchKernelGGL(mc::bin_scan_kernel, dim3(1), dim3(256), 0, es, bin_count, n_bins, bin_start, bin_fill, slice_start);
+    if (!E.w->partition) {  // index sort: the accumulate kernel gathers the records through the sorted index
+        unsigned *sorted = log_set_ptr<unsigned>(*E.log, ctx->log_sorted, b);
+        hipLaunchKernelGGL(mc::bin_scatter_kernel, dim3(bin_blocks), dim3(256), hist_lds, es, lg.keys, lg.region_count, lg.n_regions,
+                           lg.region_capacity, n_bins, bin_fill, sorted);
+        return launch_accumulate(full, false, ctx->est_accumulate, cus, es, lg.records, sorted, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, E.P.nu_line,
+                                 E.P.jblue_t, E.P.edot_t);
+    }
+    // estimator_partition.hpp: by shell into the scratch copy, by bin back into the set's own buffer
+    unsigned *shell_fill = slice_start + (n_bins + 2);
+    mc::LineVisitRecord *scratch = ctx->log_part.as<mc::LineVisitRecord>();
+    auto bits_of = [](int n) { int b = 0; while ((1 << b) < n) ++b; return b; };
+    const mc::LineVisitRecord *binned = lg.records;  // what the accumulate kernel reads
+    const int part_blocks = cus * 2;
+    if (!shell_log && ctx->est_one_level != 0 && n_bins <= mc::PART_LOCAL_BUCKETS) {
+        // few bins (short line lists: 300 on the tardis_example tables): ONE partition pass, log chunks -> scratch copy by bin.  (partition_kernel<2> with
+        // "one shell of n_bins tiles": every chunk's first bucket is bin 0, a staged segment ranks over all bins)
+        hipLaunchKernelGGL(mc::partition_kernel<2>, dim3(part_blocks), dim3(mc::PART_THREADS), 0, es, lg.records, lg.keys, lg.region_count, lg.n_regions,
+                           lg.region_capacity, (const unsigned *)nullptr, n_bins, ctx->n_lines, bits_of(n_bins), bin_fill, scratch);
+        binned = scratch;
+    } else if (shell_log) {  // the chunks hold one shell each: straight to the partition by bin, into the scratch copy
+        hipLaunchKernelGGL(mc::partition_kernel<2>, dim3(part_blocks), dim3(mc::PART_THREADS), 0, es, lg.records, lg.keys, lg.region_count, lg.n_regions,
+                           lg.region_capacity, (const unsigned *)nullptr, lg.tiles_per_shell, ctx->n_lines, bits_of(mc::PART_LOCAL_BUCKETS), bin_fill, scratch);
+        binned = scratch;
+    } else {
+        hipLaunchKernelGGL(mc::partition_shell_fill_kernel, dim3(1), dim3(256), 0, es, bin_start, lg.tiles_per_shell, ctx->n_shells, shell_fill);
+        hipLaunchKernelGGL(mc::partition_kernel<1>, dim3(part_blocks), dim3(mc::PART_THREADS), 0, es, lg.records, lg.keys, lg.region_count,
+                           lg.n_regions, lg.region_capacity, (const unsigned *)nullptr, lg.tiles_per_shell, ctx->n_lines, bits_of(ctx->n_shells),
+                           shell_fill, scratch);
+        hipLaunchKernelGGL(mc::partition_kernel<0>, dim3(part_blocks), dim3(mc::PART_THREADS), 0, es, scratch, (const unsigned *)nullptr,
+                           (const unsigned *)nullptr, 0, 0u, bin_start + n_bins, lg.tiles_per_shell, ctx->n_lines, bits_of(mc::PART_LOCAL_BUCKETS),
+                           bin_fill, lg.records);
+    }
+    return launch_accumulate(full, true, ctx->est_accumulate, cus, es, binned, nullptr, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, E.P.nu_line, E.P.jblue_t,
+                             E.P.edot_t);
+}
+
+// the host's part of a streamed range: sixteen copies into the caller's arrays, beside the running launch
+hipError_t rs_copy_pending(TardisMcContext *ctx, WaveCall &E)
+{
+    if (E.rs_pending_hi <= E.rs_pending_lo) return hipSuccess;
+    hipError_t e = hipStreamWaitEvent(ctx->rs_stream, ctx->rs_ev, 0);
+    void *dev[16];
+    per_packet_device_arrays(ctx, dev);
+    const size_t off = (size_t)E.rs_pending_lo * 8, bytes = (size_t)(E.rs_pending_hi - E.rs_pending_lo) * 8;
+    for (int a = 0; a < 16 && e == hipSuccess; ++a)
+        if (ctx->rs.dst[a] && dev[a]) e = hipMemcpyAsync((char *)ctx->rs.dst[a] + off, (char *)dev[a] + off, bytes, hipMemcpyDeviceToHost, ctx->rs_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->rs_stream);
+    ctx->rs.upto = E.rs_pending_hi;
+    E.rs_pending_lo = E.rs_pending_hi = 0;
+    return e;
+}
+
+// the argument block of an epoch's launch, stored at wc_dev
+int fill_wave_cold(TardisMcContext *ctx, const WaveCall &E, int epoch, const mc::EstimatorLog &lg, mc::WaveCold *wc_dev)
+{
+    const bool vq = E.vq, vpk = E.call->vpk;
+    mc::WaveCold &wc = ctx->wave_cold_host[epoch & 1];
+    wc.P = E.P; wc.D = ctx->problem_host; wc.log = lg; wc.seeded_states = E.cur_states;
+    wc.chunk_first = 0; wc.chunk_count = E.n;
+    wc.launch = ctx->seed_chk.as<mc::LaunchRec>();
+    wc.vp_scratch = ctx->vp_scratch.as<mc::VpResult>();
+    wc.vp_park = (vpk && !E.vq_on && ctx->vp_carry_min_active > 0) ? ctx->vp_park.as<mc::VpPark>() : nullptr;
+    wc.vp_carry_min_active = ctx->vp_carry_min_active; wc.vp_pad = 0;
+    wc.save = E.may_suspend ? E.cur_save : nullptr;
+    wc.wsave = E.may_suspend ? E.cur_wsave : nullptr;
+    wc.resume = epoch > 0 ? 1 : 0;
+    wc.drain_split = E.split_armed ? 64 : (E.compact_armed ? ctx->drain_compact : 0);  // (the most live lanes a wave whose supply has run out suspends with)
+    wc.suspended = ctx->suspended_dev.as<unsigned>();
+    wc.vq_req = E.vq_on ? ctx->vq_req.as<mc::VolleyRequest>() : nullptr;
+    wc.vq_items = E.vq_on ? ctx->vq_items.as<unsigned>() : nullptr;
+    wc.vq_count = vq ? ctx->vq_count.as<unsigned>() : nullptr;
+    wc.vq_jsave = vq ? ctx->vq_jsave.as<double>() : nullptr;
+    wc.log_continue = vq ? 1 : 0;
+    wc.log_gen = E.log_gen;
+    HIP_TRY(ctx, store_value(E.st, wc_dev, wc));
+    return TARDIS_MC_OK;
+}
+
+// Split launch (see epoch_split): the same epoch for waves [waves1, waves) on the passes' stream es, behind the estimator passes of the previous epoch
+int launch_second_half(TardisMcContext *ctx, WaveCall &E, int epoch, int waves1, hipStream_t es, mc::WaveCold *wc_dev)
+{
+    const mc::WaveCold &wc = ctx->wave_cold_host[epoch & 1];
+    mc::WaveCold wc2 = wc;  // every per-wave array starts waves1 waves further on
+    wc2.seeded_states = wc.seeded_states + (size_t)waves1 * 64 * mc::WV_STATE_STRIDE;
+    if (wc.save) wc2.save = wc.save + (size_t)waves1 * 64;
+    if (wc.wsave) wc2.wsave = wc.wsave + waves1;
+    if (wc.vp_scratch) wc2.vp_scratch = wc.vp_scratch + (size_t)waves1 * 64 * mc::VP_ROUND;
+    if (wc.vp_park) wc2.vp_park = wc.vp_park + (size_t)waves1 * 64;
+    HIP_TRY(ctx, hipStreamWaitEvent(es, ctx->ev_split[0], 0));
+    HIP_TRY(ctx, store_value(es, wc_dev + 1, wc2));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_split[1], es));
+    hipLaunchKernelGGL(E.w->fn, dim3(E.waves - waves1), dim3(64), E.w->lds, es, E.hot, (const mc::WaveCold *)(wc_dev + 1));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_split[2], es));
+    HIP_TRY(ctx, hipStreamWaitEvent(E.st, ctx->ev_split[2], 0));  // (what follows on the engine's stream -- the read-back, the next epoch -- follows both)
+    E.split_w2 = (double)(E.waves - waves1) / (double)E.waves;
+    return TARDIS_MC_OK;
+}
+
+// Volley queue, the rest of an epoch: the estimator passes run when a wave reports a full log region, and once at the end of the call.  The queue is on for the
+// bulk of a call; once a launch requests fewer v-packets than keep the tracer's lanes busy the launches are bound by their longest v-packet, not by work -- the
+// rest of the call (the drain of the longest-lived packets) runs in ONE launch with the wave kernel's own pooled volleys
+int wave_epoch_tail_volley_queue(TardisMcContext *ctx, WaveCall &E, const mc::EstimatorLog &lg)
+{
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_chunk[4]));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
+    ctx->sum_prop_ms += ms;
+    const bool last = ctx->suspended_host[0] == 0;
+    if (last || ctx->suspended_host[1] > 0) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_post[0], E.st));
+        HIP_TRY(ctx, estimator_passes(ctx, E, lg, 0, E.st));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_post[1], E.st));
+        HIP_TRY(ctx, hipMemsetAsync(lg.region_count, 0, (size_t)(E.log->n_chunks + 1) * sizeof(unsigned), E.st));
+        ++E.log_gen;
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_post[1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_post[0], ctx->ev_post[1]));
+        ctx->sum_post_ms += ms;
+    }
+    if (last) { E.call_complete = true; return TARDIS_MC_OK; }
+    const long long vq_min_items = ctx->vq_min_items >= 0 ? ctx->vq_min_items : (long long)E.call->cus * 4 * 64 * 8;
+    if (E.vq_on && (long long)ctx->suspended_host[4] < vq_min_items) E.vq_on = false;
+    return TARDIS_MC_OK;
+}
+
+// CU partition, the rest of an epoch: the host first learns whether this was the last epoch.  If not, its passes run on the pass stream's CUs beside
+// the next epoch; the last epoch's passes take the propagation stream (its CUs are idle now) -- after the passes still
+// running on the pass stream, with which they share the scratch copy of the records
+int wave_epoch_tail_cu_partition(TardisMcContext *ctx, WaveCall &E, const mc::EstimatorLog &lg, int b)
+{
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_chunk[4]));
+    float pms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&pms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
+    ctx->sum_prop_ms += pms;
+    const bool last = *ctx->suspended_host == 0;
+    hipStream_t ps = ctx->stream_pass_m;
+    if (last) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream_pass_m));
+        HIP_TRY(ctx, hipStreamWaitEvent(E.st, ctx->ev_join, 0));
+        ps = E.st;
+    } else HIP_TRY(ctx, hipStreamWaitEvent(ps, ctx->ev_chunk[3], 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b], ps));
+    HIP_TRY(ctx, estimator_passes(ctx, E, lg, b, ps));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b + 1], ps));
+    ctx->post_pending[b] = true;
+    if (last) { E.call_complete = true; return TARDIS_MC_OK; }
+    E.records_done += (double)std::min<unsigned long long>((unsigned long long)ctx->suspended_host[6], E.pool_chunks) * (double)E.log->region_capacity;
+    if (ctx->suspended_host[2] > 0) E.split_armed = false;
+    return TARDIS_MC_OK;
+}
+
+// Drain compaction (drain_compact): some waves have suspended with few live lanes -- what is left on the grid?  Packed into full waves when nothing is left to
+// hand out and it frees more than half of the grid
+int compact_drain(TardisMcContext *ctx, WaveCall &E)
+{
+    hipStream_t st = E.st;
+    unsigned *cen = ctx->drain_census.as<unsigned>();
+    HIP_TRY(ctx, hipMemsetAsync(cen, 0, 8 * sizeof(unsigned), st));
+    hipLaunchKernelGGL(mc::drain_census_kernel, dim3(E.waves_cur), dim3(64), 0, st, E.cur_save, E.cur_wsave, E.waves_cur, E.n, cen);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host + 8, cen, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    const unsigned live = ctx->suspended_host[8], reserved = ctx->suspended_host[9], waiting = ctx->suspended_host[11];
+    const unsigned density = (unsigned)ctx->drain_pack_lanes;
+    const int packed = (int)((live + density - 1u) / density);
+    if (!(reserved == 0 && waiting == 0 && live > 0 && 2 * packed <= E.waves_cur)) return TARDIS_MC_OK;
+    const int g = ctx->compactions & 1;
+    HIP_TRY(ctx, ctx->lane_save_c[g].ensure((size_t)packed * 64 * sizeof(mc::LaneSave)));
+    HIP_TRY(ctx, ctx->wave_save_c[g].ensure((size_t)packed * sizeof(mc::WaveSave)));
+    HIP_TRY(ctx, ctx->seeded_states_c[g].ensure((size_t)packed * 64 * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMemsetAsync(cen + 4, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(mc::drain_compact_kernel, dim3(E.waves_cur), dim3(64), 0, st, (const mc::LaneSave *)E.cur_save, (const mc::WaveSave *)E.cur_wsave,
+                       (const uint32_t *)E.cur_states, E.waves_cur, ctx->lane_save_c[g].as<mc::LaneSave>(), ctx->seeded_states_c[g].as<uint32_t>(), cen + 4, density);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(mc::drain_compact_finish_kernel, dim3((unsigned)((packed * 64 + 255) / 256)), dim3(256), 0, st, ctx->lane_save_c[g].as<mc::LaneSave>(),
+                       ctx->wave_save_c[g].as<mc::WaveSave>(), (const unsigned *)(cen + 4), E.n, density);
+    HIP_TRY(ctx, hipGetLastError());
+    E.cur_save = ctx->lane_save_c[g].as<mc::LaneSave>(); E.cur_wsave = ctx->wave_save_c[g].as<mc::WaveSave>(); E.cur_states = ctx->seeded_states_c[g].as<uint32_t>();
+    E.waves_cur = packed;
+    ctx->compactions += 1;
+    if (packed < 2 * E.call->cus || (int)density <= 2 * ctx->drain_compact) E.compact_armed = false;  // (nothing left worth freeing / the packed waves would suspend again at once)
+    return TARDIS_MC_OK;
+}
+
+// Result streaming, at a launch boundary: packets [0, handed) have been handed out; those of them still in flight (suspended lanes, reserved blocks) go on the late
+// list, the range [upto, handed) is unpacked now -- in front of the next launch on the same stream -- and copied by the host beside that launch
+int stream_range(TardisMcContext *ctx, WaveCall &E)
+{
+    const long long handed = (long long)std::min<unsigned long long>(*ctx->rs_next_host, (unsigned long long)E.n);
+    if (handed - ctx->rs.upto < ctx->rs_min_packets) return TARDIS_MC_OK;
+    hipLaunchKernelGGL(mc::late_list_kernel, dim3(E.waves_cur), dim3(64), 0, E.st, (const mc::LaneSave *)E.cur_save, (const mc::WaveSave *)E.cur_wsave, E.waves_cur, ctx->rs.upto, handed,
+                       ctx->rs_late.as<unsigned>(), ctx->rs_late_count.as<unsigned>(), ctx->rs.late_capacity);
+    HIP_TRY(ctx, hipGetLastError());
+    if (ctx->track) {
+        const long long cnt = handed - ctx->rs.upto;
+        hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, E.st, ctx->problem_host, ctx->rs.upto, cnt, (const unsigned *)nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->rs_ev, E.st));
+    E.rs_pending_lo = ctx->rs.upto; E.rs_pending_hi = handed;
+    return TARDIS_MC_OK;
+}
+
+// Result streaming, after the last launch: what was streamed is [0, upto) minus the late list, whose entries are gathered for get_results.  The list's length is
+// read back here (the call has synchronised with every launch already).  *unpack_from: the first packet whose tracker records are still to be unpacked.
+int gather_late_results(TardisMcContext *ctx, long long *unpack_from)
+{
+    unsigned n_late = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n_late, ctx->rs_late_count.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_late > ctx->rs.late_capacity) return TARDIS_MC_OK;  // (the list overflowed -- get_results copies everything)
+    ctx->rs.valid = true;
+    ctx->rs.n_late = n_late;
+    *unpack_from = ctx->rs.upto;
+    if (n_late == 0) return TARDIS_MC_OK;
+    if (ctx->track) {
+        hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((n_late + 255) / 256), dim3(256), 0, ctx->stream, ctx->problem_host, 0LL, (long long)n_late, ctx->rs_late.as<unsigned>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, ctx->rs_vals.ensure((size_t)16 * n_late * 8));
+    void *dev[16];
+    per_packet_device_arrays(ctx, dev);
+    for (int a = 0; a < 16; ++a)
+        if (ctx->rs.dst[a] && dev[a]) {
+            hipLaunchKernelGGL(mc::gather64_kernel, dim3((n_late + 255) / 256), dim3(256), 0, ctx->stream, (const unsigned long long *)dev[a],
+                               ctx->rs_late.as<unsigned>(), (long long)n_late, ctx->rs_vals.as<unsigned long long>() + (size_t)a * n_late);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    return TARDIS_MC_OK;
+}
+
+// One epoch: the pool of this epoch's log, the launch (or the two of a split epoch), the read-back of what is suspended, the estimator passes, and what the
+// modes of the call do between two launches.  Sets E.call_complete when nothing is left suspended.
+int run_wave_epoch(TardisMcContext *ctx, WaveCall &E, int epoch)
+{
+    const LogSizing &s = *E.log;
+    const int cus = E.call->cus, waves = E.waves;
+    const bool vq = E.vq;
+    hipStream_t st = E.st;
+    const int b = s.n_sets == 2 ? (epoch & 1) : 0;
+    hipStream_t es = s.n_sets == 2 ? ctx->stream2 : st;  // the estimator passes of an epoch run beside the next epoch
+    if (ctx->post_pending[b]) {  // this buffer set was used two epochs ago: its estimator passes must be over
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_post[2 * b + 1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_post[2 * b], ctx->ev_post[2 * b + 1]));
+        ctx->sum_post_ms += ms;
+        ctx->post_pending[b] = false;
+    }
+    mc::EstimatorLog lg{};
+    lg.tiles_per_shell = E.w->tiles;
+    lg.records = log_set_ptr<mc::LineVisitRecord>(s, ctx->log_records, b);
+    lg.keys = log_set_ptr<unsigned>(s, ctx->log_keys, b);
+    E.pool_chunks = s.n_chunks;
+    if (s.tail_plan) {
+        const double records_est = (double)E.n * ctx->traces_per_packet;  // (what the call will log, by the last call's measure)
+        const double bulk = records_est - E.records_done - s.tail_records;  // what is left before the tail
+        if (bulk > 0.0 && bulk <= (double)s.n_chunks * (double)s.region_capacity)
+            E.pool_chunks = std::min<unsigned long long>(s.n_chunks, std::max<unsigned long long>((unsigned long long)waves * (E.w->key.shell_log ? (unsigned long long)(ctx->n_shells + 4) : 1ull),
+                                                                                                  (unsigned long long)(bulk / (double)s.region_capacity) + 1ull));
+    }
+    lg.n_regions = (int)E.pool_chunks;
+    lg.region_capacity = s.region_capacity;
+    lg.region_count = ctx->log_cursor[b].as<unsigned>();
+    lg.pool_next = lg.region_count + s.n_chunks;
+    // (volley queue: the launches of a call go on appending to the same log regions until one of them is full)
+    if (!vq || epoch == 0) HIP_TRY(ctx, hipMemsetAsync(lg.region_count, 0, (size_t)(s.n_chunks + 1) * sizeof(unsigned), st));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->suspended_dev.p, 0, 4 * sizeof(unsigned), st));
+    if (vq) HIP_TRY(ctx, hipMemsetAsync(ctx->vq_count.p, 0, 2 * sizeof(unsigned), st));
+    mc::WaveCold *wc_dev = ctx->wave_cold_dev.as<mc::WaveCold>() + 2 * (epoch & 1);
+    int rc = fill_wave_cold(ctx, E, epoch, lg, wc_dev);
+    if (rc) return rc;
+    // split launch (see epoch_split): the estimator passes of the previous epoch are queued (or running) on the second stream
+    // (not the drain launch of a tail-split call: its lanes are the call's critical path, half of them would start behind the bulk's passes)
+    const bool split = ctx->epoch_split && !s.want_compact && !vq && !E.cu_masked && !s.tail_plan && s.n_sets == 2 && epoch > 0 && es != st && ctx->post_pending[b ^ 1] && waves >= 8 * cus;
+    const int waves1 = split ? waves / 2 : E.waves_cur;
+    if (split) HIP_TRY(ctx, hipEventRecord(ctx->ev_split[0], st));  // (pool, counters and argument block of this epoch are in place)
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[2], st));
+    hipLaunchKernelGGL(E.w->fn, dim3(waves1), dim3(64), E.w->lds, st, E.hot, (const mc::WaveCold *)wc_dev);
+    HIP_TRY(ctx, hipGetLastError());
+    E.split_w2 = 0.0;
+    if (split && (rc = launch_second_half(ctx, E, epoch, waves1, es, wc_dev))) return rc;
+    if (E.vq_on) {  // the v-packets this launch requested (the item count is read on the device: an empty list costs a launch)
+        const size_t geo_lds = (size_t)4 * (size_t)ctx->n_shells * sizeof(double);
+        const int tracer_waves = cus * 4 * ctx->vq_tracer_waves_per_simd;
+        if (E.call->full) hipLaunchKernelGGL(mc::vpacket_trace_kernel<true>, dim3(tracer_waves), dim3(64), geo_lds, st, (const mc::WaveCold *)wc_dev);
+        else hipLaunchKernelGGL(mc::vpacket_trace_kernel<false>, dim3(tracer_waves), dim3(64), geo_lds, st, (const mc::WaveCold *)wc_dev);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[3], st));
+    if (E.may_suspend) {  // (read back before the estimator passes are queued: the host learns early whether another epoch follows)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host, ctx->suspended_dev.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        if (vq) HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host + 4, ctx->vq_count.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        if (s.region_capacity > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host + 6, lg.pool_next, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        if (E.streaming) HIP_TRY(ctx, hipMemcpyAsync(ctx->rs_next_host, ctx->next_packet.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4], st));
+    }
+    ctx->launches += 1;
+    if (vq) return wave_epoch_tail_volley_queue(ctx, E, lg);
+    if (E.cu_masked) return wave_epoch_tail_cu_partition(ctx, E, lg, b);
+    if (es != st) HIP_TRY(ctx, hipStreamWaitEvent(es, ctx->ev_chunk[3], 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b], es));
+    HIP_TRY(ctx, estimator_passes(ctx, E, lg, b, es));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b + 1], es));
+    ctx->post_pending[b] = true;
+    ctx->prop_pending = true;
+    if (!E.may_suspend) { E.call_complete = true; return TARDIS_MC_OK; }  // (no log: the kernel adds its terms directly and never suspends; the call stays asynchronous)
+    // (result streaming: the range unpacked before this launch is copied to the caller's arrays now, while the launch runs)
+    if (E.streaming) HIP_TRY(ctx, rs_copy_pending(ctx, E));
+    // is anything suspended?  (the only host synchronisation of a call: once per epoch)
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_chunk[4]));
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
+    if (E.split_w2 > 0.0) {  // a split epoch counts with the wave-weighted duration of its two launches (= the time a launch of the whole grid stands for)
+        float ms2 = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms2, ctx->ev_split[1], ctx->ev_split[2]));
+        ms = (float)((1.0 - E.split_w2) * (double)ms + E.split_w2 * (double)ms2);
+    }
+    ctx->sum_prop_ms += ms;
+    ctx->prop_pending = false;
+    if (*ctx->suspended_host == 0) { E.call_complete = true; return TARDIS_MC_OK; }
+    E.records_done += (double)std::min<unsigned long long>((unsigned long long)ctx->suspended_host[6], E.pool_chunks) * (double)s.region_capacity;
+    if (ctx->suspended_host[2] > 0) E.split_armed = false;  // (the drain has been split off: the next launch runs to the end)
+    if (E.compact_armed && ctx->suspended_host[2] > 0 && (rc = compact_drain(ctx, E))) return rc;
+    if (E.streaming) return stream_range(ctx, E);
+    return TARDIS_MC_OK;
+}
+
+// The wave kernel (variants 2 / 3 / 4): one packet supply for the whole call, launched in epochs (see LaneSave)
+int run_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P)
+{
+    const bool vpk = call.vpk, full = call.full, vq = call.plan.variant == 4;
+    const int cus = call.cus;
+    const long long n = ctx->n_packets;
+    const mc::DeviceProblem &F = ctx->problem_host;
+    if (n >= (1LL << 31)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "more than 2^31 packets per propagate call");
+    WaveChoice w{};
+    int rc = choose_wave_kernel(ctx, call, P, w);
+    if (rc) return rc;
+    if (w.compact_walk) {
+        P.cum16 = ctx->cum16.as<unsigned short>(); P.rec16 = ctx->rec16.as<mc::WalkRec>(); P.quad_info = ctx->quad_info.as<int2>();
+        P.cum16_stride = ctx->cum16_stride;
+        P.line_block = ctx->line_block_c.as<int2>();
+        P.hot_sec = ctx->have_hot ? ctx->hot_sec.as<unsigned>() : nullptr;
+        P.blk_tab = ctx->blk_tab.as<int2>();
+        P.hot_stride = (unsigned)(16u * (unsigned)ctx->n_levels);
+    }
+    ctx->progress_wave = true;  // (one packet supply for the whole call: next_packet counts the packets handed out)
+    // (volley queue: more waves than the chip holds at once -- a wave that suspends frees its slot, and the more packets are
+    // in flight the more v-packets every tracer launch has to spread over its lanes)
+    // CU partition (pass_cus): only for calls long enough to run as several epochs -- the passes of an epoch then have the next one to hide behind
+    const int n_xcd = 8;  // gfx950: 8 XCDs x 32 CUs; the bits of a queue's CU mask are interleaved over the XCDs (bit k -> XCD k % 8)
+    const bool cu_split = ctx->pass_cus > 0 && !vq && ctx->log_sets != 1 && cus == 32 * n_xcd && n >= 30000000LL;
+    const int cus_prop = cu_split ? cus - n_xcd * ctx->pass_cus : cus;
+    const int waves = (int)std::max<long long>(1, std::min<long long>((n + 63) / 64, (long long)cus_prop * std::min(w.waves_per_cu, w.max_waves_per_cu) * (vq ? ctx->vq_oversubscribe : 1)));
+    if (ctx->track_full) {  // (a wave leaves a partly filled chunk behind at every launch it takes part in: room for four launches)
+        rc = setup_event_log(ctx, ctx->problem_host, 4LL * waves);
+        if (rc) return rc;
+    }
+    if (ctx->events_host && ctx->ev_events && hipEventQuery(ctx->ev_events) == hipSuccess && ctx->events_host[1] > 0)
+        ctx->traces_per_packet = (double)ctx->events_host[0] / (double)ctx->events_host[1];
+    if (1.1 * ctx->traces_per_packet > ctx->log_budget_per_packet) ctx->log_budget_per_packet = 1.3 * ctx->traces_per_packet;
+    LogSizing s{};
+    rc = size_line_log(ctx, call, w, n, waves, cu_split, s);
+    if (rc) return rc;
+    WaveCall E{};
+    E.call = &call; E.w = &w; E.log = &s; E.n = n; E.waves = waves; E.vq = vq;
+    E.may_suspend = s.region_capacity > 0 || vq;  // (waves take chunks dynamically: every launch can suspend)
+    E.split_armed = s.want_split && !s.want_compact;
+    E.compact_armed = s.want_compact;
+    E.waves_cur = waves;
+    ctx->compactions = 0;
+    for (int b = 0; b < s.n_sets; ++b) {
+        if (!(s.set1_inside && b == 1)) {
+            HIP_TRY(ctx, ctx->log_records[b].ensure(s.set_records * sizeof(mc::LineVisitRecord)));
+            HIP_TRY(ctx, ctx->log_keys[b].ensure(s.set_records * sizeof(unsigned)));
+            if (!w.partition) HIP_TRY(ctx, ctx->log_sorted[b].ensure(s.set_records * sizeof(unsigned)));
+        }
+        HIP_TRY(ctx, ctx->log_bins[b].ensure((size_t)(4 * (w.n_bins + 2) + ctx->n_shells + 2) * sizeof(unsigned)));
+        HIP_TRY(ctx, ctx->log_cursor[b].ensure((size_t)(s.n_chunks + 2) * sizeof(unsigned)));  // chunk counts | pool counter
+    }
+    if (w.partition) HIP_TRY(ctx, ctx->log_part.ensure(s.set_records * sizeof(mc::LineVisitRecord)));
+    if (s.n_sets == 2 && !ctx->stream2) {
+        int prio_lo = 0, prio_hi = 0;  // (the estimator passes' stream: highest priority, their workgroups are dispatched first)
+        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_hi));
+        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    }
+    E.cu_masked = cu_split && s.n_sets == 2;
+    if (E.cu_masked && ctx->pass_cus_built != ctx->pass_cus) {
+        if (ctx->stream_prop_m) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_prop_m)); HIP_TRY(ctx, hipStreamDestroy(ctx->stream_prop_m)); ctx->stream_prop_m = nullptr; }
+        if (ctx->stream_pass_m) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_pass_m)); HIP_TRY(ctx, hipStreamDestroy(ctx->stream_pass_m)); ctx->stream_pass_m = nullptr; }
+        uint32_t m_prop[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_pass[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int bit = 0; bit < cus; ++bit) {  // the first cus_prop bits = (32 - pass_cus) CUs of every XCD
+            if (bit < cus_prop) m_prop[bit >> 5] |= 1u << (bit & 31);
+            else m_pass[bit >> 5] |= 1u << (bit & 31);
+        }
+        HIP_TRY(ctx, hipExtStreamCreateWithCUMask(&ctx->stream_prop_m, 8, m_prop));
+        HIP_TRY(ctx, hipExtStreamCreateWithCUMask(&ctx->stream_pass_m, 8, m_pass));
+        if (!ctx->ev_fork_m) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork_m, hipEventDisableTiming));
+        if (!ctx->ev_join_m) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join_m, hipEventDisableTiming));
+        ctx->pass_cus_built = ctx->pass_cus;
+    }
+    for (int k = 0; k < 4; ++k)
+        if (!ctx->ev_post[k]) HIP_TRY(ctx, hipEventCreate(&ctx->ev_post[k]));
+    // ---- per-lane MT19937 state buffers, launch records, suspended lanes
+    HIP_TRY(ctx, ctx->seeded_states.ensure((size_t)waves * 64 * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
+    HIP_TRY(ctx, ctx->seed_chk.ensure((size_t)std::max<long long>(n, 1) * sizeof(mc::LaunchRec)));
+    HIP_TRY(ctx, ctx->lane_save.ensure((size_t)waves * 64 * sizeof(mc::LaneSave)));
+    HIP_TRY(ctx, ctx->wave_save.ensure((size_t)waves * sizeof(mc::WaveSave)));
+    HIP_TRY(ctx, ctx->suspended_dev.ensure(4 * sizeof(unsigned)));
+    E.cur_save = ctx->lane_save.as<mc::LaneSave>(); E.cur_wsave = ctx->wave_save.as<mc::WaveSave>(); E.cur_states = ctx->seeded_states.as<uint32_t>();
+    if (s.want_compact) HIP_TRY(ctx, ctx->drain_census.ensure(8 * sizeof(unsigned)));
+    if (!ctx->suspended_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->suspended_host, 16 * sizeof(unsigned), hipHostMallocDefault));
+    if (vq) {
+        HIP_TRY(ctx, ctx->vq_req.ensure((size_t)waves * 64 * sizeof(mc::VolleyRequest)));
+        HIP_TRY(ctx, ctx->vq_items.ensure((size_t)waves * 64 * mc::VP_ROUND * sizeof(unsigned)));
+        HIP_TRY(ctx, ctx->vq_count.ensure(2 * sizeof(unsigned)));
+        HIP_TRY(ctx, ctx->vq_jsave.ensure((size_t)waves * 2 * (size_t)ctx->n_shells * sizeof(double)));
+        if ((size_t)waves * 64 >= (1u << 29)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "too many lanes for the volley queue's item words");
+    }
+    if (vpk) HIP_TRY(ctx, ctx->vp_scratch.ensure((size_t)waves * 64 * mc::VP_ROUND * sizeof(mc::VpResult)));
+    if (vpk && ctx->vp_carry_min_active > 0) HIP_TRY(ctx, ctx->vp_park.ensure((size_t)waves * 64 * sizeof(mc::VpPark)));
+    HIP_TRY(ctx, ctx->wave_cold_dev.ensure(4 * sizeof(mc::WaveCold)));  // (per epoch parity: the launch's block and the second launch's of a split epoch)
+    ctx->wave_cold_host.resize(2);
+    for (hipEvent_t &e : ctx->ev_split)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, st));
+    if (call.tune_slot >= 0) HIP_TRY(ctx, hipEventRecord(ctx->ev_tune[0], st));
+    if (E.cu_masked) {  // everything of this call runs on the masked stream from here on; it is joined to the engine's stream at the end
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_fork_m, ctx->stream));
+        st = ctx->stream_prop_m;
+        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_fork_m, 0));
+    }
+    E.st = st;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[0], st));
+    if (n > 0) {
+        // lazy seeding: only word 397 of every start state is precomputed; the refills continue the init_genrand chains
+        mc::LaunchPrepArgs la{};
+        la.r0 = F.r0; la.mu0 = F.mu0; la.nu0 = F.nu0; la.e0 = F.e0; la.nu_line = P.nu_line;
+        la.seeds = ctx->seeds.as<uint32_t>();
+        la.bucket_first = P.bucket_first; la.bucket_shift = P.bucket_shift; la.bucket_n = P.bucket_n; la.n_lines = P.n_lines;
+        la.bucket_kmin = P.bucket_kmin; la.t_exp = P.t_exp;
+        la.out = ctx->seed_chk.as<mc::LaunchRec>(); la.first = 0; la.count = n;
+        if (full) hipLaunchKernelGGL(mc::launch_prep_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, la);
+        else hipLaunchKernelGGL(mc::launch_prep_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, la);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[1], st));
+    E.P = P;
+    mc::WaveHot &hot = E.hot;
+    hot.nu_line = P.nu_line; hot.tau_t = w.key.nt ? P.nt_t : P.tau_t; hot.n_lines = P.n_lines; hot.n_shells = P.n_shells;
+    hot.disable_line_scattering = P.disable_line_scattering; hot.debug_flags = P.debug_flags;
+    hot.t_exp = P.t_exp;
+    // cut-offs of the sweep / walk phases (lanes still busy when the wave moves on): 8 / 8 by default.  Where most blocks are
+    // entered through hot sectors the event phase is shorter and later cut-offs pay: 12 / 12 measured -2.5 % on the heavy-tailed
+    // configs[2] tables, +2 % on the uniform ones (profiles/r04_cutoffs.txt) -- hence only there, and never against an option
+    const bool mostly_hot = ctx->have_hot && 2 * ctx->n_hot_blocks > (long long)ctx->n_levels;
+    hot.ls_min_active = (!ctx->ls_min_active_user && mostly_hot) ? 12 : ctx->ls_min_active;
+    hot.ls_max_steps = ctx->ls_max_steps;
+    hot.walk_min_active = (!ctx->walk_min_active_user && mostly_hot) ? 16 : ctx->walk_min_active;  // (12 until round 6; with the leaner sweep 16: -1.2 %, profiles/r06_cutoffs.txt)
+    hot.vq_min_active = ctx->vq_min_active;
+    hot.line_block = P.line_interaction_type != 0 ? P.line_block : nullptr;
+    ctx->post_pending[0] = ctx->post_pending[1] = false;
+    ctx->prop_pending = false;
+    // result streaming: only the plain epoch loop (no volley queue, no CU partition), with the tracker unpacking it needs done per range
+    E.streaming = call.rs_armed && !vq && !E.cu_masked && E.may_suspend && n >= ctx->rs_min_packets;
+    if (E.streaming) {
+        ctx->rs.late_capacity = (unsigned)std::min<long long>(n, (long long)waves * 64 * 16);
+        HIP_TRY(ctx, ctx->rs_late.ensure((size_t)ctx->rs.late_capacity * sizeof(unsigned)));
+        HIP_TRY(ctx, ctx->rs_late_count.ensure(sizeof(unsigned)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->rs_late_count.p, 0, sizeof(unsigned), st));
+        if (!ctx->rs_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->rs_stream, hipStreamNonBlocking));
+        if (!ctx->rs_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->rs_ev, hipEventDisableTiming));
+        if (!ctx->rs_next_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->rs_next_host, sizeof(unsigned long long), hipHostMallocDefault));
+    }
+    const int max_epochs = 1 << 20;
+    E.vq_on = vq;
+    E.call_complete = n <= 0;
+    for (int epoch = 0; n > 0 && epoch < max_epochs && !E.call_complete; ++epoch)
+        if ((rc = run_wave_epoch(ctx, E, epoch))) return rc;
+    if (E.streaming && E.call_complete) HIP_TRY(ctx, rs_copy_pending(ctx, E));  // (a range queued before the last launch)
+    if (!E.call_complete)  // (packets would be left suspended in lane_save, outputs and estimators silently incomplete)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: %d launches did not finish the call (waves still suspended)", max_epochs);
+    if (E.cu_masked) {  // both masked streams join the engine's stream
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream_pass_m));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_join_m, st));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join_m, 0));
+    } else if (s.n_sets == 2 && (ctx->post_pending[0] || ctx->post_pending[1])) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    }
+    ctx->wave_epoch_mode = true;
+    ctx->progress_done = true;  // (every packet has been handed out and has ended: the host read "nothing suspended")
+    long long unpack_from = 0;
+    if (E.streaming && ctx->rs.upto > 0 && (rc = gather_late_results(ctx, &unpack_from))) return rc;
+    if (ctx->track && n > unpack_from) {  // the wave kernel's tracker records -> the boundary's arrays
+        hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((unsigned)((n - unpack_from + 255) / 256)), dim3(256), 0, ctx->stream, F, unpack_from, n - unpack_from,
+                           (const unsigned *)nullptr);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return TARDIS_MC_OK;
+}
+
+// The group kernel (variant 1), in chunks: the MT19937 states are seeded per chunk by a lane-per-packet kernel
+int run_group_kernel(TardisMcContext *ctx, const PropagateCall &call, const mc::GroupArgs &P)
+{
+    const bool vpk = call.vpk;
+    const int cus = call.cus;
+    ctx->wave_epoch_mode = false;
+    long long chunk = std::min<long long>(std::max<long long>(ctx->n_packets, 1), ctx->chunk_packets);
+    HIP_TRY(ctx, ctx->seeded_states.ensure((size_t)chunk * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
+    // group size: 8 lanes per packet pays off when the sweeps between events are short (sparse line lists)
+    const int G = ctx->group_size == 8 ? 8 : (ctx->group_size == 16 ? 16 : ((ctx->n_lines <= 100000 && !vpk) ? 8 : 16));
+    const int block = 256;
+    const size_t lds = G == 8 ? mc::group_kernel_lds_bytes<8, 256>(ctx->n_shells) : mc::group_kernel_lds_bytes<16, 256>(ctx->n_shells);
+    if (lds > 160 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
+    const int blocks_per_cu = std::max(1, std::min(std::min(ctx->blocks_per_cu, 8), (int)((160 * 1024) / lds)));
+    const GroupKernelFn k = find_kernel(GROUP_KERNELS, GroupKernelKey{call.full, ctx->track, G, block, 4, vpk, call.plan.w64});
+    if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the group kernel");
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, st));
+    uint32_t *seeded = ctx->seeded_states.as<uint32_t>();
+    for (long long first = 0; first < ctx->n_packets; first += chunk) {
+        const long long count = std::min(chunk, ctx->n_packets - first);
+        const int ci = ctx->chunks_timed;
+        while ((int)ctx->ev_chunk.size() < 4 * (ci + 1)) {
+            hipEvent_t e;
+            HIP_TRY(ctx, hipEventCreate(&e));
+            ctx->ev_chunk.push_back(e);
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci], st));
+        hipLaunchKernelGGL(mc::seed_states_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st,
+                           ctx->seeds.as<uint32_t>(), seeded, first, count, mc::MT_N);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemsetAsync(ctx->next_packet.p, 0, sizeof(unsigned long long), st));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci + 1], st));
+        const int groups_per_block = block / G;
+        long long want_blocks = (count + groups_per_block - 1) / groups_per_block;
+        int blocks = (int)std::max<long long>(1, std::min<long long>(want_blocks, (long long)cus * blocks_per_cu));
+        // (the group kernel updates the line estimators with atomics: logging its traces was measured and is a loss
+        // there -- the record bookkeeping costs its redundant-lane event loop more than the deferred atomics do)
+        hipLaunchKernelGGL(k, dim3(blocks), dim3(block), lds, st, P, seeded, first, count);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci + 2], st));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci + 3], st));
+        ctx->chunks_timed = ci + 1;
+    }
+    return TARDIS_MC_OK;
+}
+
+// The cooperative kernels (variants 1 - 4): the problem on the device and the argument block both kernels take by value, then the runner of the plan's variant
+int run_cooperative(TardisMcContext *ctx, PropagateCall &call)
+{
+    const bool wave_kernel = call.plan.variant == 2 || call.plan.variant == 3 || call.plan.variant == 4;
+    ctx->problem_host = make_device_problem(ctx);
+    const mc::DeviceProblem &F = ctx->problem_host;
+    HIP_TRY(ctx, ctx->problem_dev.ensure(sizeof(mc::DeviceProblem)));
+    HIP_TRY(ctx, store_value(ctx->stream, ctx->problem_dev.as<mc::DeviceProblem>(), ctx->problem_host));
+    mc::GroupArgs P{};
+    P.cold = ctx->problem_dev.as<mc::DeviceProblem>();
+    P.n_shells = F.n_shells; P.n_lines = F.n_lines; P.n_trans = F.n_trans;
+    P.line_interaction_type = F.line_interaction_type; P.disable_line_scattering = F.disable_line_scattering;
+    P.debug_flags = F.debug_flags; P.n_est_copies = F.n_est_copies;
+    P.t_exp = F.t_exp; P.sigma_thomson = F.sigma_thomson;
+    P.tc = F.t_exp * mc::C_LIGHT; P.rcp_tc = 1.0 / P.tc;
+    P.r_inner = F.r_inner; P.r_outer = F.r_outer; P.nu_line = F.nu_line; P.tau_t = F.tau_t; P.n_e = F.n_e; P.prob_t = F.prob_t;
+    P.line_block = ctx->line_block.as<int2>(); P.trans_rec = ctx->trans_rec.as<int4>();
+    P.cum_t = ctx->cum_t.as<double>(); P.trans_nu = ctx->trans_nu.as<double>();
+    P.jblue_t = F.jblue_t; P.edot_t = F.edot_t; P.est_copy_stride = F.est_copy_stride;
+    P.next_packet = F.next_packet;
+    P.n_vpackets = F.n_vpackets; P.survival_probability = F.survival_probability; P.tau_russian = F.tau_russian;
+    P.spawn_start = F.spawn_start; P.spawn_end = F.spawn_end; P.grid0 = F.grid0; P.grid_last = F.grid_last;
+    P.delta_nu = F.delta_nu; P.vhist = F.vhist;
+    P.bucket_first = ctx->bucket_first.as<int>(); P.bucket_shift = ctx->bucket_shift; P.bucket_n = ctx->bucket_n;
+    P.bucket_kmin = ctx->bucket_kmin;
+    P.tau_pfx = call.plan.screen_on ? ctx->tau_pfx.as<double>() : nullptr;
+    P.tau_rowsum = call.plan.screen_on ? ctx->tau_rowsum.as<double>() : nullptr;
+    while ((int)ctx->ev_chunk.size() < 8) {
+        hipEvent_t e;
+        HIP_TRY(ctx, hipEventCreate(&e));
+        ctx->ev_chunk.push_back(e);
+    }
+    ctx->chunks_timed = 0;
+    ctx->sum_seed_ms = ctx->sum_prop_ms = ctx->sum_post_ms = 0.0;
+    ctx->launches = 0;
+    return wave_kernel ? run_wave_kernel(ctx, call, P) : run_group_kernel(ctx, call, P);
+}
+
+// The lane kernel (variant 0): lane-per-packet, persistent-ish grid, static round-robin packet assignment
+int run_lane_kernel(TardisMcContext *ctx, const PropagateCall &call)
+{
+    // (the context is cached: the timing queries must not report the epochs of an earlier wave-kernel call)
+    ctx->wave_epoch_mode = false;
+    ctx->post_pending[0] = ctx->post_pending[1] = false;
+    ctx->prop_pending = false;
+    ctx->sum_seed_ms = ctx->sum_prop_ms = ctx->sum_post_ms = 0.0;
+    ctx->launches = 0;
+    long long want_blocks = (ctx->n_packets + 255) / 256;
+    int blocks = (int)std::max<long long>(1, std::min<long long>(want_blocks, (long long)call.cus * ctx->blocks_per_cu));
+    HIP_TRY(ctx, ctx->rng_state.ensure((size_t)blocks * 256 * mc::MT_N * sizeof(uint32_t)));
+    mc::DeviceProblem P = make_device_problem(ctx);
+    const size_t lds = 2 * (size_t)ctx->n_shells * sizeof(double);
+    if (lds + (ctx->track_full ? 32 : 0) > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
+    if (ctx->track_full) {
+        int rc = setup_event_log(ctx, P, (long long)blocks * 4);
+        if (rc) return rc;
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    ctx->chunks_timed = 0;
+    return ctx->n_packets > 0 ? launch_lane(ctx, P, blocks, lds) : TARDIS_MC_OK;
 }
 
 }  // namespace
@@ -866,7 +1969,7 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     }
     ctx->log_part.release();
     ctx->wave_cold_dev.release();
-    ctx->seed_chk[0].release(); ctx->seed_chk[1].release(); ctx->vp_scratch[0].release(); ctx->vp_scratch[1].release(); ctx->vp_park.release();
+    ctx->seed_chk.release(); ctx->vp_scratch.release(); ctx->vp_park.release();
     for (auto &b : ctx->li_f64) b.release();
     for (auto &b : ctx->li_i64) b.release();
     ctx->li_rec.release();
@@ -1520,19 +2623,22 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->compactions = 0;
     ctx->ev_valid = false;
-    const bool rs_armed = ctx->rs.armed;  // (tardis_mc_stream_results holds for one call)
+    const TardisMcConfig &c = ctx->cfg;
+    PropagateCall call{};
+    call.vpk = c.number_of_vpackets > 0;
+    call.full = c.enable_full_relativity != 0;
+    call.cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+    call.rs_armed = ctx->rs.armed;
     ctx->rs.armed = false; ctx->rs.valid = false; ctx->rs.upto = 0; ctx->rs.n_late = 0;
-    const int tune_pending = ctx->ls_tune.pending;  // (the lane-sweep tuner: whether the previous propagate call was one of its timed ones: 2 * instantiation + sample)
+    call.tune_pending = ctx->ls_tune.pending;
     ctx->ls_tune.pending = -1;
-    int tune_slot = -1;  // this call is a timed one of the tuner (becomes ls_tune.pending once it has been enqueued completely)
+    call.tune_slot = -1;
     int rc = ensure_estimators(ctx);
     if (rc) return rc;
     if (!ctx->counters.p) {
         HIP_TRY(ctx, ctx->counters.ensure(TARDIS_MC_N_COUNTERS * sizeof(unsigned long long)));
         HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, TARDIS_MC_N_COUNTERS * sizeof(unsigned long long), ctx->stream));
     }
-    const TardisMcConfig &c = ctx->cfg;
-    const bool vpk = c.number_of_vpackets > 0;
     if (ctx->track) {  // (tracking may have been switched on after the packets were set)
         const size_t P = (size_t)std::max<long long>(ctx->n_packets, 1);
         for (auto &b : ctx->li_f64) HIP_TRY(ctx, b.ensure(P * sizeof(double)));
@@ -1541,7 +2647,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     }
     if (ctx->track_full) HIP_TRY(ctx, ctx->li_rec.ensure((size_t)std::max<long long>(ctx->n_packets, 1) * 64));
     // v-packet log buffers
-    if (c.enable_vpacket_tracking && vpk) {
+    if (c.enable_vpacket_tracking && call.vpk) {
         // (sized for the current call: the engine is cached per process, a later, larger run must not inherit a smaller log)
         if (!ctx->vlog_capacity_user) ctx->vlog_capacity = std::max<long long>(1024, ctx->n_packets * c.number_of_vpackets * 64);
         size_t cap = (size_t)ctx->vlog_capacity;
@@ -1554,7 +2660,6 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         HIP_TRY(ctx, ctx->vlog_mu.ensure(cap * sizeof(double)));
         HIP_TRY(ctx, ctx->vlog_r.ensure(cap * sizeof(double)));
     }
-    const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
     HIP_TRY(ctx, ctx->first_error.ensure(2 * sizeof(long long)));
     // (argument blocks reach the device through store_value(): consecutive propagate calls -- iterations, chunks submitted by
     // the host -- are not serialised by a stream synchronisation here)
@@ -1567,1023 +2672,19 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     }
     HIP_TRY(ctx, hipMemsetAsync(ctx->next_packet.p, 0, sizeof(unsigned long long), ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_progress_reset, ctx->stream));
-    // the cooperative kernel relies on a sorted line list (bucket index, monotone stopping predicate); anything else --
-    // which the reference would also mis-handle -- goes through the sequential lane-per-packet kernel
-    // automatic choice: the wave-owner kernel (its pooled v-packet volleys take up to 32 v-packets per volley: one bit of
-    // the roulette predictor each; beyond that the lane-per-packet kernel); lane sweeps where their bounds hold (partial
-    // relativity) and no volleys run.  On the macroatom shape (5e5 lines, ~36 lines per trace) the lane sweeps overtook the
-    // group sweeps once the walk ran per lane on the compact tables and a call became epochs over one packet supply
-    // (19.3 vs 13.4 Mpkt/s at 2e7 packets): the group sweeps' 280 instructions per 16-line step had become the bound.
-    // v-packet screening (tau_prefix.hpp): with the default survival probability 0 a v-packet whose optical depth passes
-    // tau_russian is dropped whatever the depth was -- decided from prefix sums, two reads per shell crossing.
-    // It pays where a shell crossing passes many lines (two prefix reads against ~40 optical depths on the 100-shell x 5e5-line
-    // shape: 1.7x - 2.1x); on the tardis_example shape (~12 lines per crossing, most v-packets leave the grid alive) the
-    // screening is a second trace on top of the first: -36 % (profiles/r03_vpacket_screening.txt).  "vpacket_screening" 0 / 1
-    // overrides the automatic choice.
-    // (decided from cheap predicates first: whether the tables are BUILT depends on the kernel the call ends up on -- calls that
-    // take the lane kernel (more than 32 v-packets per volley, unsorted line list, variant 0) never read them: S x (L + 1)
-    // doubles, 400 MB at the configs[4] shape, and a blocking read-back of the negative-depth flag)
-    bool screen_on = false;
-    {
-        const bool screen_auto = (long long)ctx->n_lines >= 2500LL * (long long)ctx->n_shells;
-        const bool screen = ctx->vpacket_screening < 0 ? screen_auto : ctx->vpacket_screening != 0;
-        screen_on = vpk && c.survival_probability == 0.0 && screen && !(ctx->debug_flags & 33554432) &&
-                    !(ctx->pfx_valid && ctx->pfx_negative);
-    }
-    auto build_screening_tables = [&]() -> int {  // first v-packet call after set_opacity that screens
-        if (ctx->pfx_valid) return TARDIS_MC_OK;
-        const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines;
-        HIP_TRY(ctx, ctx->tau_pfx.ensure((S * (L + 1) + 8) * sizeof(double)));  // (+8: the four-entry windows of the screening)
-        HIP_TRY(ctx, ctx->tau_rowsum.ensure(S * sizeof(double)));
-        HIP_TRY(ctx, ctx->pfx_flag.ensure(sizeof(int)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->pfx_flag.p, 0, sizeof(int), ctx->stream));
-        hipLaunchKernelGGL(mc::tau_prefix_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, ctx->tau_t.as<double>(), (int)L,
-                           ctx->tau_pfx.as<double>(), ctx->tau_rowsum.as<double>(), ctx->pfx_flag.as<int>());
-        HIP_TRY(ctx, hipGetLastError());
-        int neg = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&neg, ctx->pfx_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->pfx_negative = neg != 0;
-        ctx->pfx_valid = true;
-        return TARDIS_MC_OK;
-    };
-    const bool prefer_lane_sweeps = !c.enable_full_relativity && !vpk;
-    // With v-packets the wave kernel's pooled volleys win where a v-packet crosses few shells and few lines (the tardis_example
-    // shape: 8.0 vs 5.2 Mpkt/s); on finer grids and longer line lists the group kernel -- every lane of a packet's group traces one
-    // v-packet of the volley, no speculation on the draw positions -- was measured 1.2x to 2.2x ahead
-    // (profiles/r02_vpacket_kernel_choice.txt).
-    // With the screening the v-packets of such a shape are half of the wave kernel's pass instead of nearly all of it, and its
-    // lane-per-packet event code wins once the call is long enough to amortise its drain: 1.39-1.46 vs 1.33 Mpkt/s at 3e6 packets of
-    // the configs[4] shape, 0.63 vs 1.10 at 1e6 (profiles/r03_vpacket_screening.txt).
-    // (round 5: with the finer bucket index, the carried walks and the cut-off of the volley phases the wave kernel is ahead from 1e6 packets per call on:
-    // 1.20 vs 1.81 s there, 4.5 vs 12.7 s at 1e7 -- and still at 1e5, 0.63 vs 0.74 s: profiles/r05_vpacket_kernel_choice.txt; the threshold was 2.5e6 in round 3)
-    const bool vpk_wave = vpk && ((ctx->n_shells <= 30 && ctx->n_lines <= 100000) || (screen_on && ctx->n_packets >= ctx->vpk_wave_min_packets));
-    int variant = ctx->variant >= 0 ? ctx->variant
-                                    : ((vpk && c.number_of_vpackets > 32) ? 0 : (vpk ? (vpk_wave ? 2 : 1) : (prefer_lane_sweeps ? 3 : 2)));
-    if (ctx->prob_negative && (variant == 2 || variant == 3)) variant = 1;  // (the wave kernel searches the monotone running sums)
-    // Russian roulette with survivors (virtual_packet.py:221-232; the reference's SURVIVAL_PROBABILITY is 0 in every run, nothing
-    // sets it): a surviving v-packet may play again in a later shell, so its draw count is unbounded, while the wave kernel's
-    // pooled volleys budget one roulette draw per v-packet -- such problems run on the group kernel
-    if (vpk && c.survival_probability > 0.0 && (variant == 2 || variant == 3 || variant == 4)) variant = 1;
-    // variant 4: the wave kernel with the volley queue (v-packets traced by vpacket_trace_kernel between its launches); without
-    // v-packets there is nothing to queue
-    if (variant == 4 && !vpk) variant = prefer_lane_sweeps ? 3 : 2;
-    if (ctx->prob_negative && variant == 4) variant = 1;
-    // full r-packet tracking: the wave-owner kernel with group sweeps (variant 2, its default launch shape) where it can run the call --
-    // sorted lines, monotone probabilities, no surviving v-packets, at most 32 v-packets, the compact walk tables, no cross-check flags --
-    // else the lane kernel (variants 1, 3 and 4 are not instrumented)
-    if (ctx->track_full) {
-        const bool wave_ok = ctx->lines_sorted && !ctx->prob_negative && !(vpk && (c.number_of_vpackets > 32 || c.survival_probability > 0.0)) &&
-                             (c.line_interaction_type == 0 || ctx->have_walk_tables) &&
-                             !(ctx->debug_flags & (128 | 8192 | 1048576 | mc::WV_DBG_FLAGS)) && ctx->n_packets < (1LL << 31);
-        variant = (wave_ok && variant != 0) ? 2 : 0;
-    }
-    bool cooperative = ctx->lines_sorted && (variant == 1 || variant == 2 || variant == 3 || variant == 4) && (!vpk || c.number_of_vpackets <= 32);
-    // 64-bit row offsets (option table_offsets): the lane kernel always has them; the cooperative kernels have WIDE instantiations, used where
-    // a shell-major table reaches 2^28 entries (or always, option 1) -- the 32-bit ones save registers on the hot path
-    const bool big_tables = (long long)ctx->n_shells * ctx->n_lines >= (1LL << 28) || (long long)ctx->n_shells * ctx->n_trans >= (1LL << 28);
-    bool w64 = false;
-    if (cooperative && (ctx->table_offsets == 1 || (ctx->table_offsets < 0 && big_tables))) {
-        const bool wave_v = variant == 2 || variant == 3 || variant == 4;
-        if (variant == 4)
-            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "variant 4 (the volley queue) has no 64-bit table offsets: n_shells * n_lines or n_shells * n_trans "
-                                                             "reaches 2^28, or option table_offsets is 1; use the automatic variant");
-        if (wave_v && (ctx->debug_flags & (128 | 8192 | 1048576 | mc::WV_DBG_FLAGS)))
-            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "the cross-check instantiations of the wave kernel (debug flags 128, 8192, 1048576 and the counter "
-                                                             "flags) have no 64-bit table offsets");
-        if (wave_v && (long long)ctx->n_shells * ctx->n_lines >= (1LL << 32)) {
-            // (the line-visit log of the wave kernels indexes (shell, line) in 32 bits; the group kernel adds its terms directly)
-            if (ctx->variant >= 0)
-                return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells * n_lines reaches 2^32: the line-visit log of the wave kernels (variants 2-4) "
-                                                                 "indexes (shell, line) in 32 bits; use variant 1 or the automatic variant");
-            if (ctx->track_full) { cooperative = false; variant = 0; }  // (the group kernel has no full tracking)
-            else { variant = 1; w64 = true; }
-        } else if (wave_v && c.line_interaction_type != 0 && !ctx->have_walk_tables) {
-            // (the compact walk tables were not built for these tables: the fp64 walks are only in the 32-bit cross-check instantiations)
-            cooperative = false;
-            variant = 0;
-        } else
-            w64 = true;
-    }
-    if (cooperative && big_tables && !w64)
-        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells * n_lines or n_shells * n_trans reaches 2^28, the limit of the cooperative kernels' 32-bit "
-                                                         "table offsets, and option table_offsets is 0");
-    ctx->last_table_offsets = (w64 || !cooperative) ? 64 : 32;
-    ctx->last_variant = cooperative ? ((variant == 3 && c.enable_full_relativity) ? 2 : variant) : 0;
-    if (screen_on && !cooperative) screen_on = false;  // (the lane kernel traces line by line)
-    if (screen_on) {
-        rc = build_screening_tables();
+    // which kernel (propagate_plan.hpp).  The screening tables are built by the first call whose plan screens; a negative optical depth in them
+    // means no screening, and the plan is made again knowing that
+    call.plan = plan::plan_propagate(plan_input(ctx));
+    if (!call.plan.error && call.plan.screen_on && !ctx->pfx_valid) {
+        rc = build_screening_tables(ctx);
         if (rc) return rc;
-        if (ctx->pfx_negative) {
-            // a negative optical depth: no screening (the prefix sums would not bound the serial sum).  The automatic kernel
-            // choice counted on it for long calls of the wave kernel: take what it picks without the screening.
-            screen_on = false;
-            if (ctx->variant < 0 && variant == 2 && vpk && !(ctx->n_shells <= 30 && ctx->n_lines <= 100000)) {
-                variant = 1;
-                ctx->last_variant = variant;
-            }
-        }
+        if (ctx->pfx_negative) call.plan = plan::plan_propagate(plan_input(ctx));
     }
-
-    if (!cooperative) {
-        // variant 0: lane-per-packet, persistent-ish grid, static round-robin packet assignment
-        // (the context is cached: the timing queries must not report the epochs of an earlier wave-kernel call)
-        ctx->wave_epoch_mode = false;
-        ctx->post_pending[0] = ctx->post_pending[1] = false;
-        ctx->prop_pending = false;
-        ctx->sum_seed_ms = ctx->sum_prop_ms = ctx->sum_post_ms = 0.0;
-        ctx->launches = 0;
-        long long want_blocks = (ctx->n_packets + 255) / 256;
-        int blocks = (int)std::max<long long>(1, std::min<long long>(want_blocks, (long long)cus * ctx->blocks_per_cu));
-        HIP_TRY(ctx, ctx->rng_state.ensure((size_t)blocks * 256 * mc::MT_N * sizeof(uint32_t)));
-        mc::DeviceProblem P = make_device_problem(ctx);
-        const size_t lds = 2 * (size_t)ctx->n_shells * sizeof(double);
-        if (lds + (ctx->track_full ? 32 : 0) > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
-        if (ctx->track_full) {
-            rc = setup_event_log(ctx, P, (long long)blocks * 4);
-            if (rc) return rc;
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-        ctx->chunks_timed = 0;
-        if (ctx->n_packets > 0) {
-            if (c.enable_full_relativity) { if (vpk) launch_lane<true, true>(ctx, P, blocks, lds); else launch_lane<true, false>(ctx, P, blocks, lds); }
-            else { if (vpk) launch_lane<false, true>(ctx, P, blocks, lds); else launch_lane<false, false>(ctx, P, blocks, lds); }
-            HIP_TRY(ctx, hipGetLastError());
-        }
-    } else {
-        // variant 1: group kernel, chunked (MT19937 states are seeded per chunk by a lane-per-packet kernel);
-        // variants 2 / 3: wave-owner kernel, one packet supply for the whole call, launched in epochs (see LaneSave)
-        const bool wave_kernel = variant == 2 || variant == 3 || variant == 4;
-        const bool vq = variant == 4;
-        ctx->problem_host = make_device_problem(ctx);
-        const mc::DeviceProblem &F = ctx->problem_host;
-        HIP_TRY(ctx, ctx->problem_dev.ensure(sizeof(mc::DeviceProblem)));
-        HIP_TRY(ctx, store_value(ctx->stream, ctx->problem_dev.as<mc::DeviceProblem>(), ctx->problem_host));
-        mc::GroupArgs P{};
-        P.cold = ctx->problem_dev.as<mc::DeviceProblem>();
-        P.n_shells = F.n_shells; P.n_lines = F.n_lines; P.n_trans = F.n_trans;
-        P.line_interaction_type = F.line_interaction_type; P.disable_line_scattering = F.disable_line_scattering;
-        P.debug_flags = F.debug_flags; P.n_est_copies = F.n_est_copies;
-        P.t_exp = F.t_exp; P.sigma_thomson = F.sigma_thomson;
-        P.tc = F.t_exp * mc::C_LIGHT; P.rcp_tc = 1.0 / P.tc;
-        if (wave_kernel && ctx->n_packets >= (1LL << 31))
-            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "more than 2^31 packets per propagate call");
-        P.r_inner = F.r_inner; P.r_outer = F.r_outer; P.nu_line = F.nu_line; P.tau_t = F.tau_t; P.n_e = F.n_e; P.prob_t = F.prob_t;
-        P.line_block = ctx->line_block.as<int2>(); P.trans_rec = ctx->trans_rec.as<int4>();
-        P.cum_t = ctx->cum_t.as<double>(); P.trans_nu = ctx->trans_nu.as<double>();
-        P.jblue_t = F.jblue_t; P.edot_t = F.edot_t; P.est_copy_stride = F.est_copy_stride;
-        P.next_packet = F.next_packet;
-        P.n_vpackets = F.n_vpackets; P.survival_probability = F.survival_probability; P.tau_russian = F.tau_russian;
-        P.spawn_start = F.spawn_start; P.spawn_end = F.spawn_end; P.grid0 = F.grid0; P.grid_last = F.grid_last;
-        P.delta_nu = F.delta_nu; P.vhist = F.vhist;
-        P.bucket_first = ctx->bucket_first.as<int>(); P.bucket_shift = ctx->bucket_shift; P.bucket_n = ctx->bucket_n;
-        P.bucket_kmin = ctx->bucket_kmin;
-        P.tau_pfx = screen_on ? ctx->tau_pfx.as<double>() : nullptr;
-        P.tau_rowsum = screen_on ? ctx->tau_rowsum.as<double>() : nullptr;
-        // macro-atom jumps of the wave kernel (macroatom chains and the single jump of downbranch alike): per-lane walk on the
-        // compact tables (walk_tables.hpp); debug flag 8192 keeps the cooperative group scan of the fp64 running sums (macroatom) /
-        // the fp64 search (downbranch), 128 the per-lane search in them (both for cross-checks)
-        const bool compact_walk = wave_kernel && c.line_interaction_type != 0 && ctx->have_walk_tables && !(ctx->debug_flags & (128 | 8192));
-        if (compact_walk) {
-            P.cum16 = ctx->cum16.as<unsigned short>(); P.rec16 = ctx->rec16.as<mc::WalkRec>(); P.quad_info = ctx->quad_info.as<int2>();
-            P.cum16_stride = ctx->cum16_stride;
-            P.line_block = ctx->line_block_c.as<int2>();
-            P.hot_sec = ctx->have_hot ? ctx->hot_sec.as<unsigned>() : nullptr;
-            P.blk_tab = ctx->blk_tab.as<int2>();
-            P.hot_stride = (unsigned)(16u * (unsigned)ctx->n_levels);
-        }
-        const bool full = c.enable_full_relativity != 0, trk = ctx->track;
-        while ((int)ctx->ev_chunk.size() < 8) {
-            hipEvent_t e;
-            HIP_TRY(ctx, hipEventCreate(&e));
-            ctx->ev_chunk.push_back(e);
-        }
-        ctx->chunks_timed = 0;
-        ctx->sum_seed_ms = ctx->sum_prop_ms = ctx->sum_post_ms = 0.0;
-        ctx->launches = 0;
-        if (wave_kernel) {
-            const bool lane_sweep = variant == 3 && !full;  // (the bounds of the lane sweep are those of partial relativity)
-            size_t wave_lds = lane_sweep ? (vpk ? mc::wave_kernel_lds_bytes<false, true, true>(ctx->n_shells) : mc::wave_kernel_lds_bytes<false, false, true>(ctx->n_shells))
-                                  : vpk ? (full ? mc::wave_kernel_lds_bytes<true, true>(ctx->n_shells) : mc::wave_kernel_lds_bytes<false, true>(ctx->n_shells))
-                                        : (full ? mc::wave_kernel_lds_bytes<true, false>(ctx->n_shells) : mc::wave_kernel_lds_bytes<false, false>(ctx->n_shells));
-            if (wave_lds > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
-            const int wave_waves_per_cu = std::max(1, std::min(ctx->waves_per_simd > 0 ? 4 * ctx->waves_per_simd : 16, (int)((160 * 1024) / wave_lds)));
-            using WaveKernelFn = void (*)(mc::WaveHot, const mc::WaveCold *);
-            WaveKernelFn kw = nullptr;
-            // (XW: the instantiations with the macro-atom walks on the fp64 running sums compiled in -- only launched when the compact
-            // walk tables are not used: debug flags 128 / 8192, tables too large; the production ones are 22 % shorter without them)
-#define TMC_PICKW3(G_, V_, X_) (full ? (trk ? mc::propagate_wave_kernel<true, true, G_, V_, false, X_> : mc::propagate_wave_kernel<true, false, G_, V_, false, X_>) \
-                                     : (trk ? mc::propagate_wave_kernel<false, true, G_, V_, false, X_> : mc::propagate_wave_kernel<false, false, G_, V_, false, X_>))
-#define TMC_PICKW2(G_, V_) (xwalk ? TMC_PICKW3(G_, V_, true) : TMC_PICKW3(G_, V_, false))
-#define TMC_PICKW(G_) (vpk ? TMC_PICKW2(G_, true) : TMC_PICKW2(G_, false))
-#define TMC_PICKLS2(V_, X_) (trk ? mc::propagate_wave_kernel<false, true, 16, V_, true, X_> : mc::propagate_wave_kernel<false, false, 16, V_, true, X_>)
-#define TMC_PICKLS(V_) (xwalk ? TMC_PICKLS2(V_, true) : TMC_PICKLS2(V_, false))
-            // (flag 1048576: the long instantiations, for A/B; the flags that read the kernel's profiling / test counters: those are only compiled into the long ones)
-            const int dbg_counter_flags = mc::WV_DBG_FLAGS;  // (defined next to the kernel's DBG-gated code: propagate_wave.hpp)
-            const bool xwalk = (c.line_interaction_type != 0 && !compact_walk) || (ctx->debug_flags & (1048576 | dbg_counter_flags)) != 0;
-            // (sweep-worker width of the wave kernel: 8 lanes for sparse line lists, 16 for long ones, like the group kernel; the lane-sweep
-            // instantiations only use it in the cross-check walks: one width)
-            const int GW = ctx->group_size ? ctx->group_size : (ctx->n_lines <= 100000 ? 8 : 16);
-            if (lane_sweep) kw = vpk ? TMC_PICKLS(true) : TMC_PICKLS(false);
-            else kw = (GW == 16) ? TMC_PICKW(16) : (GW == 4 ? TMC_PICKW(4) : TMC_PICKW(8));
-            // v-packets on a grid so fine that the per-shell LDS arrays leave room for at most eight waves per CU (two per SIMD): the
-            // instantiation compiled for two waves per SIMD -- 239 VGPRs, no spills -- costs no occupancy there (built for the sweep widths G = 16 and
-            // G = 8, without the cross-check walks; option vpk_wide_registers 0 keeps the 168-VGPR one)
-            // Measured (profiles/r05_vpk_wide_registers.txt): 3727-3766 vs 4442-4450 ms per 1e7 packets of the configs[4] shape (-16 %).  Option 2 forces
-            // it (then eight waves per CU whatever the LDS allows), 0 keeps the 168-VGPR instantiation.
-            bool wide = vpk && !xwalk && !w64 && !ctx->track_full && (lane_sweep || GW == 16 || GW == 8) &&
-                        ((ctx->vpk_wide_registers == 1 && wave_waves_per_cu <= 8) || ctx->vpk_wide_registers == 2);
-#define TMC_PICKWIDE(G_) (full ? (trk ? mc::propagate_wave_kernel<true, true, G_, true, false, false, 2> : mc::propagate_wave_kernel<true, false, G_, true, false, false, 2>) \
-                               : (trk ? mc::propagate_wave_kernel<false, true, G_, true, false, false, 2> : mc::propagate_wave_kernel<false, false, G_, true, false, false, 2>))
-            if (wide) kw = lane_sweep ? (trk ? mc::propagate_wave_kernel<false, true, 16, true, true, false, 2> : mc::propagate_wave_kernel<false, false, 16, true, true, false, 2>)
-                                      : (GW == 16 ? TMC_PICKWIDE(16) : TMC_PICKWIDE(8));  // (lane sweeps with v-packets: variant 3 under partial relativity)
-#undef TMC_PICKWIDE
-            // which lane-sweep instantiation (see ls_waves_per_simd above): forced by the option, or timed on the first calls of this key
-            bool ls3 = false;
-            if (lane_sweep && !vpk && !xwalk) {
-                auto &tn = ctx->ls_tune;
-                // (a call that does not even fill the grid's lanes four times over is nothing but the drain of its longest packets: B, measured -6 % on
-                // 1e5 - 1e6-packet calls of the tardis_example shape, without spending five calls of a 20-iteration run on finding that out)
-                const bool all_drain = ctx->n_packets < 4LL * 64 * 16 * cus;
-                if (ctx->ls_waves_per_simd == 3 || (ctx->ls_waves_per_simd == 0 && all_drain)) ls3 = true;
-                else if (ctx->ls_waves_per_simd == 0 && ctx->pass_cus == 0) {
-                    if (tn.n != ctx->n_packets || tn.lines != ctx->n_lines || tn.shells != ctx->n_shells || tn.mode != c.line_interaction_type ||
-                        tn.table != ctx->sweep_table || tn.wide != (int)w64) {
-                        tn.n = ctx->n_packets; tn.lines = ctx->n_lines; tn.shells = ctx->n_shells; tn.mode = c.line_interaction_type; tn.table = ctx->sweep_table;
-                        tn.wide = (int)w64;
-                        tn.phase = 0; tn.choice = 0;
-                        tn.ms[0][0] = tn.ms[0][1] = tn.ms[1][0] = tn.ms[1][1] = -1.0;
-                    } else if (tune_pending >= 0) {  // the previous call of this key was a timed one: its duration (propagation + passes)
-                        float ms = 0.f;
-                        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_tune[1]));
-                        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_tune[0], ctx->ev_tune[1]));
-                        tn.ms[tune_pending >> 1][tune_pending & 1] = ms;
-                    } else if (tn.phase >= 2 && tn.phase <= 5)
-                        tn.phase -= 1;  // the previous phase was a timed call and left no measurement (the call failed half-way): again
-                    // call 0: A, not timed (first-call allocations, the log sized from a guess); calls 1 / 3: A; calls 2 / 4: B; from call 5 on: the choice
-                    if (tn.phase == 0) ls3 = false;
-                    else if (tn.phase <= 4) { ls3 = (tn.phase & 1) == 0; tune_slot = 2 * (ls3 ? 1 : 0) + ((tn.phase - 1) >> 1); }
-                    else {
-                        if (tn.phase == 5) {
-                            const bool all = tn.ms[0][0] > 0.0 && tn.ms[0][1] > 0.0 && tn.ms[1][0] > 0.0 && tn.ms[1][1] > 0.0;
-                            tn.choice = (all && std::min(tn.ms[1][0], tn.ms[1][1]) < 0.97 * std::min(tn.ms[0][0], tn.ms[0][1])) ? 1 : 0;
-                        }
-                        ls3 = tn.choice == 1;
-                    }
-                    if (tn.phase < 6) ++tn.phase;
-                    if (tune_slot >= 0)
-                        for (int k = 0; k < 2; ++k)
-                            if (!ctx->ev_tune[k]) HIP_TRY(ctx, hipEventCreate(&ctx->ev_tune[k]));
-                }
-            }
-            if (ls3) kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 3> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 3>;
-            // the interleaved sweep table (option sweep_table; the production lane-sweep instantiations only)
-            int nt_mode = 0;
-            if (lane_sweep && !vpk && !xwalk && !w64 && ctx->sweep_table != 0) {
-                const unsigned long long stride = ((unsigned long long)ctx->n_lines + 7ull) & ~7ull;
-                if (stride * (unsigned long long)ctx->n_shells + 32ull < (1ull << 28)) {
-                    if (!ctx->nt_valid) {
-                        const long long total = (long long)(stride * (unsigned long long)ctx->n_shells) + 32;  // (+ the slack of a step's loads behind the last row)
-                        HIP_TRY(ctx, ctx->nt_t.ensure((size_t)total * 16));
-                        HIP_TRY(ctx, ctx->pfx_flag.ensure(sizeof(int)));
-                        HIP_TRY(ctx, hipMemsetAsync(ctx->pfx_flag.p, 0, sizeof(int), ctx->stream));
-                        hipLaunchKernelGGL(interleave_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 65536)), dim3(256), 0, ctx->stream, ctx->nu_line.as<double>(),
-                                           ctx->tau_t.as<double>(), ctx->nt_t.as<double2>(), (long long)ctx->n_lines, (long long)ctx->n_shells, (long long)stride, total,
-                                           ctx->pfx_flag.as<int>());
-                        HIP_TRY(ctx, hipGetLastError());
-                        int neg = 0;
-                        HIP_TRY(ctx, hipMemcpyAsync(&neg, ctx->pfx_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-                        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                        ctx->nt_negative = neg != 0;
-                        ctx->nt_stride = (unsigned)stride;
-                        ctx->nt_valid = true;
-                    }
-                }
-                if (ctx->nt_valid && !ctx->nt_negative) {
-                    nt_mode = (ctx->sweep_table == 2 && !ls3) ? 2 : 1;
-                    P.nt_t = ctx->nt_t.as<double>(); P.nt_stride = ctx->nt_stride;
-                    if (ls3) kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 3, 1> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 3, 1>;
-                    else if (nt_mode == 2) kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 4, 2> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 4, 2>;
-                    else kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 4, 1> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 4, 1>;
-                }
-            }
-#undef TMC_PICKLS2
-#undef TMC_PICKW3
-#undef TMC_PICKLS
-#undef TMC_PICKW2
-#undef TMC_PICKW
-            const long long n = ctx->n_packets;
-            ctx->progress_wave = true;  // (one packet supply for the whole call: next_packet counts the packets handed out)
-            // (volley queue: more waves than the chip holds at once -- a wave that suspends frees its slot, and the more packets are
-            // in flight the more v-packets every tracer launch has to spread over its lanes)
-            // CU partition (pass_cus): only for calls long enough to run as several epochs -- the passes of an epoch then have the next one to hide behind
-            const int n_xcd = 8;  // gfx950: 8 XCDs x 32 CUs; the bits of a queue's CU mask are interleaved over the XCDs (bit k -> XCD k % 8)
-            const bool cu_split = ctx->pass_cus > 0 && !vq && ctx->log_sets != 1 && cus == 32 * n_xcd && n >= 30000000LL;
-            const int cus_prop = cu_split ? cus - n_xcd * ctx->pass_cus : cus;
-            const int waves = (int)std::max<long long>(1, std::min<long long>((n + 63) / 64, (long long)cus_prop * std::min(wave_waves_per_cu, wide ? 8 : (ls3 ? 12 : 16)) * (vq ? ctx->vq_oversubscribe : 1)));
-            if (ctx->track_full) {  // (a wave leaves a partly filled chunk behind at every launch it takes part in: room for four launches)
-                rc = setup_event_log(ctx, ctx->problem_host, 4LL * waves);
-                if (rc) return rc;
-            }
-            // ---- the line-visit log (estimator_log.hpp): two buffer sets, one region per wave; an epoch ends when the regions
-            // are full.  Sized for the whole call when that fits log_capacity (1.2x the traces per packet measured in the last
-            // call, 128 per packet before anything was measured), else log_capacity.
-            if (ctx->events_host && ctx->ev_events && hipEventQuery(ctx->ev_events) == hipSuccess && ctx->events_host[1] > 0)
-                ctx->traces_per_packet = (double)ctx->events_host[0] / (double)ctx->events_host[1];
-            if (1.1 * ctx->traces_per_packet > ctx->log_budget_per_packet) ctx->log_budget_per_packet = 1.3 * ctx->traces_per_packet;
-            const int tiles = std::max((ctx->n_lines + mc::EST_TILE - 1) / mc::EST_TILE, 1);
-            const int n_bins = ctx->n_shells * tiles;
-            // est_pipeline 1 (estimator_partition.hpp): the records are grouped by shell, then by bin; needs a shell's bins and all shells
-            // to fit the partition kernel's local buckets
-            const bool partition = ctx->est_pipeline == 1 && tiles <= mc::PART_LOCAL_BUCKETS && ctx->n_shells <= mc::PART_LOCAL_BUCKETS;
-            // the shell-sorted log: instantiated for the two production lane-sweep kernels (sixteen waves on the interleaved table, twelve on the separate ones)
-            const bool shell_log = lane_sweep && !vpk && !xwalk && !w64 && !vq && partition && ctx->log_by_shell != 0 && ctx->n_shells <= 64 &&
-                                   ((!ls3 && nt_mode == 1) || (ls3 && nt_mode == 0));
-            if (shell_log) {
-                if (ls3) kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 3, 0, true> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 3, 0, true>;
-                else kw = trk ? mc::propagate_wave_kernel<false, true, 16, false, true, false, 4, 1, true> : mc::propagate_wave_kernel<false, false, 16, false, true, false, 4, 1, true>;
-                wave_lds = mc::wave_kernel_lds_bytes<false, false, true, true>(ctx->n_shells);
-            }
-            if (ctx->track_full) {  // the tracked instantiations: group sweeps of 16 lanes, compact walks, default register budget
-                kw = full ? (vpk ? mc::propagate_wave_kernel<true, true, 16, true, false, false, 3, 0, false, true>
-                                 : mc::propagate_wave_kernel<true, true, 16, false, false, false, 4, 0, false, true>)
-                          : (vpk ? mc::propagate_wave_kernel<false, true, 16, true, false, false, 3, 0, false, true>
-                                 : mc::propagate_wave_kernel<false, true, 16, false, false, false, 4, 0, false, true>);
-            }
-            // 64-bit row offsets: the production shapes above without the interleaved sweep table, the shell-sorted log and the two-waves-per-SIMD
-            // v-packet form (those keep 32-bit offsets); sweep width 4 runs as 8 (per-packet results do not depend on the width)
-            if (w64) {
-                if (xwalk) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "the fp64 macro-atom walks have no 64-bit table offsets");
-#define TMC_W64(F_, T_, G_, V_, LS_, WPE_, FT_) mc::propagate_wave_kernel<F_, T_, G_, V_, LS_, false, WPE_, 0, false, FT_, true>
-#define TMC_PICKW64(G_, V_) (full ? (trk ? TMC_W64(true, true, G_, V_, false, V_ ? 3 : 4, false) : TMC_W64(true, false, G_, V_, false, V_ ? 3 : 4, false)) \
-                                  : (trk ? TMC_W64(false, true, G_, V_, false, V_ ? 3 : 4, false) : TMC_W64(false, false, G_, V_, false, V_ ? 3 : 4, false)))
-                if (ctx->track_full)
-                    kw = full ? (vpk ? TMC_W64(true, true, 16, true, false, 3, true) : TMC_W64(true, true, 16, false, false, 4, true))
-                              : (vpk ? TMC_W64(false, true, 16, true, false, 3, true) : TMC_W64(false, true, 16, false, false, 4, true));
-                else if (lane_sweep)
-                    kw = vpk ? (trk ? TMC_W64(false, true, 16, true, true, 3, false) : TMC_W64(false, false, 16, true, true, 3, false))
-                             : ls3 ? (trk ? TMC_W64(false, true, 16, false, true, 3, false) : TMC_W64(false, false, 16, false, true, 3, false))
-                                   : (trk ? TMC_W64(false, true, 16, false, true, 4, false) : TMC_W64(false, false, 16, false, true, 4, false));
-                else
-                    kw = GW == 16 ? (vpk ? TMC_PICKW64(16, true) : TMC_PICKW64(16, false)) : (vpk ? TMC_PICKW64(8, true) : TMC_PICKW64(8, false));
-#undef TMC_PICKW64
-#undef TMC_W64
-            }
-            long long log_capacity = ctx->log_capacity;
-            // One log set or two.  Two let the passes of an epoch run on a second stream beside the next launch -- but they do not fit beside sixteen resident waves per CU,
-            // so "beside" means: contending with the next launch's first 0.1 s, both slower for it.  Measured at 1e8 packets (profiles/r06_log_sets.txt): the passes before
-            // the next launch, alone on the chip, are faster in total, and one set leaves room for epochs half as many again (three launches instead of five): -0.5 %.
-            // So a call of many epochs uses one set; shorter calls keep two (the passes of the bulk run beside the drain of the last launch).
-            bool one_set = ctx->log_sets == 1;
-            if (ctx->log_sets == 0 && partition && !vq && !vpk && ctx->drain_split == 0 && ctx->drain_compact == 0 && ctx->epoch_split == 0 && ctx->pass_cus == 0) {
-                double two_set_capacity = (double)ctx->log_capacity;
-                size_t free_b = 0, total_b = 0;
-                if (!ctx->log_capacity_user && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                    const double have = (double)(ctx->log_records[0].cap + ctx->log_records[1].cap + ctx->log_keys[0].cap + ctx->log_keys[1].cap +
-                                                 ctx->log_sorted[0].cap + ctx->log_sorted[1].cap + ctx->log_part.cap);
-                    two_set_capacity = std::min(two_set_capacity, 0.6 * ((double)free_b + have) / 80.0);
-                }
-                // (four epochs or more with two sets; at two or three the passes of the first epochs still find room beside the last launch's drain: 4e7 packets
-                // 1 292 - 1 308 ms with two sets, 1 320 - 1 351 with one)
-                const double per_packet = ctx->traces_per_packet > 0.0 ? 1.05 * ctx->traces_per_packet : ctx->log_budget_per_packet;
-                one_set = (double)n * per_packet > 3.0 * two_set_capacity;
-            }
-            if (one_set && !ctx->log_capacity_user) {
-                // (the second set of an earlier, smaller call is given back first; 24 + 4 bytes per record and the 24 of the scratch copy)
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->stream2) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
-                ctx->log_records[1].release(); ctx->log_keys[1].release(); ctx->log_sorted[1].release(); ctx->log_bins[1].release(); ctx->log_cursor[1].release();
-                size_t free_b = 0, total_b = 0;
-                log_capacity = 4000000000LL;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                    const double have = (double)(ctx->log_records[0].cap + ctx->log_keys[0].cap + ctx->log_sorted[0].cap + ctx->log_part.cap);
-                    log_capacity = std::min<long long>(log_capacity, (long long)(0.6 * ((double)free_b + have) / (partition ? 52.0 : 32.0)));
-                }
-            } else
-            if (!ctx->log_capacity_user) {
-                // (fewer, longer epochs are faster -- 25.8 vs 24.5 Mpkt/s at 1e8 packets with 2.5e9 instead of 1.5e9 records per set
-                // -- but two sets of 2.5e9 records are 160 GB: never take more than 60 % of what is free, counting what the log holds already)
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                    const double have = (double)(ctx->log_records[0].cap + ctx->log_records[1].cap + ctx->log_keys[0].cap + ctx->log_keys[1].cap +
-                                                 ctx->log_sorted[0].cap + ctx->log_sorted[1].cap + ctx->log_part.cap);
-                    // (bytes per record of capacity: two sets of 24 + 4 and an index of 4 each, or the shared scratch copy of 24)
-                    log_capacity = std::min<long long>(log_capacity, (long long)(0.6 * ((double)free_b + have) / (partition ? 80.0 : 64.0)));
-                }
-            }
-            unsigned long long cap = std::min<unsigned long long>((unsigned long long)log_capacity,
-                                                                  (unsigned long long)((double)n * ctx->log_budget_per_packet) + 64ull * (unsigned long long)waves + 65536ull);
-            if (n_bins > mc::EST_MAX_BINS) cap = 0;  // too many tiles for the LDS histogram: the kernel adds its terms directly
-            cap = std::min<unsigned long long>(cap, 0xfffffff0ull);
-            // The log is a pool of chunks the waves take one after the other (EstimatorLog, mc_device.hpp): chunks of up to 4096 records
-            // (~90 passes of a wave: one pool atomic per 7 ms), at least four per wave on average so that the pool runs dry for all
-            // waves at nearly the same time, never fewer than one per wave; a chunk holds >= 256 records (a pass appends up to 64).
-            unsigned region_capacity = 0;  // records per chunk
-            unsigned long long n_chunks = 0;
-            if (cap > 0) {
-                // (shell-sorted log: a wave holds an open chunk for every shell -- the pool needs a few more chunks per wave than there are shells; chunks of
-                // 2048 records are what the partition kernel stages at a time.  A caller's own log_capacity (tests) is respected: with fewer chunks than that
-                // the waves that find the pool empty suspend at once and the call takes more epochs)
-                const unsigned long long per_wave = shell_log ? (unsigned long long)(ctx->n_shells + 4) : 4ull;
-                region_capacity = ctx->log_chunk_records > 0 ? (unsigned)ctx->log_chunk_records : (shell_log ? 2048u : 4096u);
-                while (region_capacity > 256 && (unsigned long long)region_capacity * per_wave * (unsigned long long)waves > cap) region_capacity >>= 1;
-                region_capacity &= ~1u;  // even: a chunk of 24-byte records then starts on a 16-byte boundary (partition_kernel stages with 16-byte loads)
-                n_chunks = std::max<unsigned long long>(cap / region_capacity, (unsigned long long)waves * ((shell_log && !ctx->log_capacity_user) ? per_wave : 1ull));
-                if (n_chunks * region_capacity > 0xfffffff0ull) n_chunks = 0xfffffff0ull / region_capacity;
-            }
-            // Memory check: the tables are resident (set_opacity), what is left must hold the smallest log this grid runs with -- one chunk of 256 records per wave,
-            // 24 + 4 bytes a record and the partition's 24-byte scratch copy or the sort's 4-byte index (counting what the log holds already)
-            if (region_capacity > 0) {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                    const double have = (double)(ctx->log_records[0].cap + ctx->log_records[1].cap + ctx->log_keys[0].cap + ctx->log_keys[1].cap +
-                                                 ctx->log_sorted[0].cap + ctx->log_sorted[1].cap + ctx->log_part.cap);
-                    const double least = (double)waves * 256.0 * (partition ? 52.0 : 32.0);
-                    if (least > (double)free_b + have)
-                        return fail(ctx, TARDIS_MC_ERR_HIP, "device memory: the tables leave %.3f GiB of %.1f GiB free, the smallest line-visit log of this call needs "
-                                                            "%.3f GiB", ((double)free_b + have) / 1073741824.0, (double)total_b / 1073741824.0, least / 1073741824.0);
-                }
-            }
-            // (waves take chunks dynamically: every launch can suspend)
-            const bool may_suspend = region_capacity > 0 || vq;
-            // a second buffer set (the estimator passes of an epoch overlap the next epoch) only when the call may need several epochs
-            // ... or splits off its drain (WaveCold::drain_split): worth a second launch once the call is long enough for a drain to form
-            const bool want_split = ctx->drain_split && !vq && !one_set && region_capacity > 0 && n >= 64LL * waves * 4;
-            // Tail split: the last epoch of a call should hold only the DRAIN (the ~4 % of the records the longest-lived packets log
-            // after the packet supply has run out, on a mostly idle chip), so that the passes over everything before it run beside the
-            // drain and only the passes of the tail -- milliseconds -- are left for after the call.  The host knows the call's records
-            // from the last call's traces per packet and hands the second-to-last epoch a pool of exactly "what is left minus the
-            // tail"; with the chunk pool that epoch ends for all waves at once.  Also for calls whose log fits ONE epoch (their passes
-            // were not overlapped with anything before).  A wrong estimate only moves the boundary.
-            // (the tail: what the packets in flight when the supply runs out still log -- lanes x ~8 packets' worth of traces, the mean
-            // residual life of a heavy-tailed population; only for calls whose passes are worth a second launch: >= 5e8 records)
-            const double tail_records = (double)ctx->log_tail_packets * ctx->traces_per_packet * 64.0 * (double)waves;
-            // Measured (profiles/r04_tail_split.txt): calls whose log fits one epoch -3 ... -5 % (1e7 - 2e7 packets: their passes ran
-            // after the call before); calls of several epochs +0.5 % (their passes overlap the next epoch already, the extra launch
-            // costs) -- so only the former.
-            const bool one_epoch = (double)region_capacity * (double)n_chunks >= (double)n * ctx->traces_per_packet * 1.05;
-            const bool tail_plan = ctx->log_tail_split && !vq && !one_set && region_capacity > 0 && ctx->traces_per_packet > 0.0 && one_epoch &&
-                                   (double)n * ctx->traces_per_packet >= 5e8 && (double)n * ctx->traces_per_packet > 2.0 * tail_records;
-            // (the second buffer set is allocated as soon as a tail split MAY be planned -- the first call of a context has no estimate yet
-            // -- so that no later call of the same size allocates tens of GB in the middle of an iteration)
-            const bool tail_possible = ctx->log_tail_split && !vq && !one_set && region_capacity > 0 &&
-                                       (double)n * std::max(ctx->traces_per_packet, 16.0) >= 5e8;
-            // ... or packs the drain's live lanes into fewer waves (drain_compact): the passes of the launch before run beside the packed drain
-            const bool want_compact = ctx->drain_compact > 0 && !vq && !vpk && !cu_split && !shell_log && !one_set && region_capacity > 0 && n > 64LL * (waves - 1) && waves >= 8;
-            const int n_sets = (one_set || vq) ? 1 : ((tail_plan || tail_possible || want_split || want_compact || (region_capacity > 0 && (unsigned long long)region_capacity * n_chunks < (unsigned long long)((double)n * ctx->log_budget_per_packet))) ? 2 : 1);
-            bool split_armed = want_split && !want_compact;
-            bool compact_armed = want_compact;
-            int waves_cur = waves;  // (the grid of the next launch: smaller after a compaction)
-            mc::LaneSave *cur_save = nullptr; mc::WaveSave *cur_wsave = nullptr; uint32_t *cur_states = nullptr;  // (set below, once the buffers exist)
-            ctx->compactions = 0;
-            const size_t set_records = (size_t)std::max<unsigned long long>((unsigned long long)region_capacity * n_chunks, 1);
-            // (a two-set call on a context whose first set was sized by a larger one-set call: both sets lie in the first set's buffers -- a second allocation of
-            // tens of GB costs ~1 s the first time, the memory is cleared)
-            const bool set1_inside = n_sets == 2 && !ctx->log_records[1].p && ctx->log_records[0].cap >= 2 * set_records * sizeof(mc::LineVisitRecord) &&
-                                     ctx->log_keys[0].cap >= 2 * set_records * sizeof(unsigned) && (partition || ctx->log_sorted[0].cap >= 2 * set_records * sizeof(unsigned));
-            auto set_records_ptr = [&](int b) { return set1_inside ? ctx->log_records[0].as<mc::LineVisitRecord>() + (size_t)b * set_records : ctx->log_records[b].as<mc::LineVisitRecord>(); };
-            auto set_keys_ptr = [&](int b) { return set1_inside ? ctx->log_keys[0].as<unsigned>() + (size_t)b * set_records : ctx->log_keys[b].as<unsigned>(); };
-            auto set_sorted_ptr = [&](int b) { return set1_inside ? ctx->log_sorted[0].as<unsigned>() + (size_t)b * set_records : ctx->log_sorted[b].as<unsigned>(); };
-            for (int b = 0; b < n_sets; ++b) {
-                if (!(set1_inside && b == 1)) {
-                    HIP_TRY(ctx, ctx->log_records[b].ensure(set_records * sizeof(mc::LineVisitRecord)));
-                    HIP_TRY(ctx, ctx->log_keys[b].ensure(set_records * sizeof(unsigned)));
-                    if (!partition) HIP_TRY(ctx, ctx->log_sorted[b].ensure(set_records * sizeof(unsigned)));
-                }
-                HIP_TRY(ctx, ctx->log_bins[b].ensure((size_t)(4 * (n_bins + 2) + ctx->n_shells + 2) * sizeof(unsigned)));
-                HIP_TRY(ctx, ctx->log_cursor[b].ensure((size_t)(n_chunks + 2) * sizeof(unsigned)));  // chunk counts | pool counter
-            }
-            if (partition) HIP_TRY(ctx, ctx->log_part.ensure(set_records * sizeof(mc::LineVisitRecord)));
-            if (n_sets == 2 && !ctx->stream2) {
-                int prio_lo = 0, prio_hi = 0;  // (the estimator passes' stream: highest priority, their workgroups are dispatched first)
-                (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-                HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_hi));
-                HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-            }
-            const bool cu_masked = cu_split && n_sets == 2;
-            if (cu_masked && ctx->pass_cus_built != ctx->pass_cus) {
-                if (ctx->stream_prop_m) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_prop_m)); HIP_TRY(ctx, hipStreamDestroy(ctx->stream_prop_m)); ctx->stream_prop_m = nullptr; }
-                if (ctx->stream_pass_m) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_pass_m)); HIP_TRY(ctx, hipStreamDestroy(ctx->stream_pass_m)); ctx->stream_pass_m = nullptr; }
-                uint32_t m_prop[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_pass[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (int bit = 0; bit < cus; ++bit) {  // the first cus_prop bits = (32 - pass_cus) CUs of every XCD
-                    if (bit < cus_prop) m_prop[bit >> 5] |= 1u << (bit & 31);
-                    else m_pass[bit >> 5] |= 1u << (bit & 31);
-                }
-                HIP_TRY(ctx, hipExtStreamCreateWithCUMask(&ctx->stream_prop_m, 8, m_prop));
-                HIP_TRY(ctx, hipExtStreamCreateWithCUMask(&ctx->stream_pass_m, 8, m_pass));
-                if (!ctx->ev_fork_m) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork_m, hipEventDisableTiming));
-                if (!ctx->ev_join_m) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join_m, hipEventDisableTiming));
-                ctx->pass_cus_built = ctx->pass_cus;
-            }
-            for (int k = 0; k < 4; ++k)
-                if (!ctx->ev_post[k]) HIP_TRY(ctx, hipEventCreate(&ctx->ev_post[k]));
-            // ---- per-lane MT19937 state buffers, launch records, suspended lanes
-            HIP_TRY(ctx, ctx->seeded_states.ensure((size_t)waves * 64 * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
-            HIP_TRY(ctx, ctx->seed_chk[0].ensure((size_t)std::max<long long>(n, 1) * sizeof(mc::LaunchRec)));
-            HIP_TRY(ctx, ctx->lane_save.ensure((size_t)waves * 64 * sizeof(mc::LaneSave)));
-            HIP_TRY(ctx, ctx->wave_save.ensure((size_t)waves * sizeof(mc::WaveSave)));
-            HIP_TRY(ctx, ctx->suspended_dev.ensure(4 * sizeof(unsigned)));
-            cur_save = ctx->lane_save.as<mc::LaneSave>(); cur_wsave = ctx->wave_save.as<mc::WaveSave>(); cur_states = ctx->seeded_states.as<uint32_t>();
-            if (want_compact) HIP_TRY(ctx, ctx->drain_census.ensure(8 * sizeof(unsigned)));
-            if (!ctx->suspended_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->suspended_host, 16 * sizeof(unsigned), hipHostMallocDefault));
-            if (vq) {
-                HIP_TRY(ctx, ctx->vq_req.ensure((size_t)waves * 64 * sizeof(mc::VolleyRequest)));
-                HIP_TRY(ctx, ctx->vq_items.ensure((size_t)waves * 64 * mc::VP_ROUND * sizeof(unsigned)));
-                HIP_TRY(ctx, ctx->vq_count.ensure(2 * sizeof(unsigned)));
-                HIP_TRY(ctx, ctx->vq_jsave.ensure((size_t)waves * 2 * (size_t)ctx->n_shells * sizeof(double)));
-                if ((size_t)waves * 64 >= (1u << 29)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "too many lanes for the volley queue's item words");
-            }
-            if (vpk) HIP_TRY(ctx, ctx->vp_scratch[0].ensure((size_t)waves * 64 * mc::VP_ROUND * sizeof(mc::VpResult)));
-            if (vpk && ctx->vp_carry_min_active > 0) HIP_TRY(ctx, ctx->vp_park.ensure((size_t)waves * 64 * sizeof(mc::VpPark)));
-            HIP_TRY(ctx, ctx->wave_cold_dev.ensure(4 * sizeof(mc::WaveCold)));  // (per epoch parity: the launch's block and the second launch's of a split epoch)
-            ctx->wave_cold_host.resize(2);
-            for (hipEvent_t &e : ctx->ev_split)
-                if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-            hipStream_t st = ctx->stream;
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_start, st));
-            if (tune_slot >= 0) HIP_TRY(ctx, hipEventRecord(ctx->ev_tune[0], st));
-            if (cu_masked) {  // everything of this call runs on the masked stream from here on; it is joined to the engine's stream at the end
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_fork_m, ctx->stream));
-                st = ctx->stream_prop_m;
-                HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_fork_m, 0));
-            }
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[0], st));
-            if (n > 0) {
-                // lazy seeding: only word 397 of every start state is precomputed; the refills continue the init_genrand chains
-                mc::LaunchPrepArgs la{};
-                la.r0 = F.r0; la.mu0 = F.mu0; la.nu0 = F.nu0; la.e0 = F.e0; la.nu_line = P.nu_line;
-                la.seeds = ctx->seeds.as<uint32_t>();
-                la.bucket_first = P.bucket_first; la.bucket_shift = P.bucket_shift; la.bucket_n = P.bucket_n; la.n_lines = P.n_lines;
-                la.bucket_kmin = P.bucket_kmin; la.t_exp = P.t_exp;
-                la.out = ctx->seed_chk[0].as<mc::LaunchRec>(); la.first = 0; la.count = n;
-                if (full) hipLaunchKernelGGL(mc::launch_prep_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, la);
-                else hipLaunchKernelGGL(mc::launch_prep_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, la);
-                HIP_TRY(ctx, hipGetLastError());
-            }
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[1], st));
-            mc::WaveHot hot{};
-            hot.nu_line = P.nu_line; hot.tau_t = nt_mode ? P.nt_t : P.tau_t; hot.n_lines = P.n_lines; hot.n_shells = P.n_shells;
-            hot.disable_line_scattering = P.disable_line_scattering; hot.debug_flags = P.debug_flags;
-            hot.t_exp = P.t_exp;
-            // cut-offs of the sweep / walk phases (lanes still busy when the wave moves on): 8 / 8 by default.  Where most blocks are
-            // entered through hot sectors the event phase is shorter and later cut-offs pay: 12 / 12 measured -2.5 % on the heavy-tailed
-            // configs[2] tables, +2 % on the uniform ones (profiles/r04_cutoffs.txt) -- hence only there, and never against an option
-            const bool mostly_hot = ctx->have_hot && 2 * ctx->n_hot_blocks > (long long)ctx->n_levels;
-            hot.ls_min_active = (!ctx->ls_min_active_user && mostly_hot) ? 12 : ctx->ls_min_active;
-            hot.ls_max_steps = ctx->ls_max_steps;
-            hot.walk_min_active = (!ctx->walk_min_active_user && mostly_hot) ? 16 : ctx->walk_min_active;  // (12 until round 6; with the leaner sweep 16: -1.2 %, profiles/r06_cutoffs.txt)
-            hot.vq_min_active = ctx->vq_min_active;
-            hot.line_block = P.line_interaction_type != 0 ? P.line_block : nullptr;
-            // binning + accumulation of one epoch's line-visit log (estimator_log.hpp)
-            auto estimator_passes = [&](const mc::EstimatorLog &lg, int b, hipStream_t es) -> hipError_t {
-                if (lg.region_capacity == 0) return hipSuccess;
-                unsigned *bin_count = ctx->log_bins[b].as<unsigned>(), *bin_start = bin_count + (n_bins + 1),
-                         *bin_fill = bin_start + (n_bins + 1), *slice_start = bin_fill + (n_bins + 1);
-                unsigned *sorted = set_sorted_ptr(b);
-                hipError_t e = hipMemsetAsync(bin_count, 0, (size_t)(n_bins + 1) * sizeof(unsigned), es);
-                if (e != hipSuccess) return e;
-                const size_t hist_lds = (size_t)n_bins * sizeof(unsigned);
-                if (hist_lds > 64 * 1024) {  // more than the default dynamic-LDS limit: BASELINE config 5 has 100 shells x 245 tiles
-                    e = hipFuncSetAttribute((const void *)mc::bin_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds);
-                    if (e != hipSuccess) return e;
-                    e = hipFuncSetAttribute((const void *)mc::bin_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds);
-                    if (e != hipSuccess) return e;
-                }
-                const int bin_blocks = cus * 8;
-                hipLaunchKernelGGL(mc::bin_count_kernel, dim3(bin_blocks), dim3(256), hist_lds, es, lg.keys, lg.region_count, lg.n_regions,
-                                   lg.region_capacity, n_bins, bin_count);
-                hipLaunchKernelGGL(mc::bin_scan_kernel, dim3(1), dim3(256), 0, es, bin_count, n_bins, bin_start, bin_fill, slice_start);
-                if (partition) {  // estimator_partition.hpp: by shell into the scratch copy, by bin back into the set's own buffer
-                    unsigned *shell_fill = slice_start + (n_bins + 2);
-                    mc::LineVisitRecord *scratch = ctx->log_part.as<mc::LineVisitRecord>();
-                    auto bits_of = [](int n) { int b = 0; while ((1 << b) < n) ++b; return b; };
-                    const mc::LineVisitRecord *binned = lg.records;  // what the accumulate kernel reads
-                    if (!shell_log && ctx->est_one_level != 0 && n_bins <= mc::PART_LOCAL_BUCKETS) {
-                        // few bins (short line lists: 300 on the tardis_example tables): ONE partition pass, log chunks -> scratch copy by bin.  (partition_kernel<2> with
-                        // "one shell of n_bins tiles": every chunk's first bucket is bin 0, a staged segment ranks over all bins)
-                        hipLaunchKernelGGL(mc::partition_kernel<2>, dim3(cus * 2), dim3(mc::PART_THREADS), 0, es, lg.records, lg.keys, lg.region_count, lg.n_regions,
-                                           lg.region_capacity, (const unsigned *)nullptr, n_bins, ctx->n_lines, bits_of(n_bins), bin_fill, scratch);
-                        binned = scratch;
-                    } else
-                    if (shell_log) {  // the chunks hold one shell each: straight to the partition by bin, into the scratch copy
-                        hipLaunchKernelGGL(mc::partition_kernel<2>, dim3(cus * 2), dim3(mc::PART_THREADS), 0, es, lg.records, lg.keys, lg.region_count, lg.n_regions,
-                                           lg.region_capacity, (const unsigned *)nullptr, lg.tiles_per_shell, ctx->n_lines, bits_of(mc::PART_LOCAL_BUCKETS), bin_fill, scratch);
-                        binned = scratch;
-                    } else {
-                    hipLaunchKernelGGL(mc::partition_shell_fill_kernel, dim3(1), dim3(256), 0, es, bin_start, lg.tiles_per_shell, ctx->n_shells, shell_fill);
-                    const int part_blocks = cus * 2;
-                    hipLaunchKernelGGL(mc::partition_kernel<1>, dim3(part_blocks), dim3(mc::PART_THREADS), 0, es, lg.records, lg.keys, lg.region_count,
-                                       lg.n_regions, lg.region_capacity, (const unsigned *)nullptr, lg.tiles_per_shell, ctx->n_lines, bits_of(ctx->n_shells),
-                                       shell_fill, scratch);
-                    hipLaunchKernelGGL(mc::partition_kernel<0>, dim3(part_blocks), dim3(mc::PART_THREADS), 0, es, scratch, (const unsigned *)nullptr,
-                                       (const unsigned *)nullptr, 0, 0u, bin_start + n_bins, lg.tiles_per_shell, ctx->n_lines, bits_of(mc::PART_LOCAL_BUCKETS),
-                                       bin_fill, lg.records);
-                    }
-                    if (ctx->est_accumulate == 3) {  // the dyadic hierarchy, a lane per record (accumulate_dyadic_kernel<.., LOOP>: 73 KB of LDS, two workgroups per CU)
-                        if (full)
-                            hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<true, true, true>), dim3(cus * 2), dim3(64 * mc::ACCD_WAVES), 0, es, binned,
-                                               (const unsigned *)nullptr, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                        else
-                            hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<false, true, true>), dim3(cus * 2), dim3(64 * mc::ACCD_WAVES), 0, es, binned,
-                                               (const unsigned *)nullptr, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                        return hipGetLastError();
-                    }
-                    if (ctx->est_accumulate == 2) {  // the dyadic hierarchy of block sums (accumulate_dyadic_kernel): one workgroup per CU
-                        if (full)
-                            hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<true, true>), dim3(cus), dim3(64 * mc::ACCD_WAVES), 0, es, binned,
-                                               (const unsigned *)nullptr, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                        else
-                            hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<false, true>), dim3(cus), dim3(64 * mc::ACCD_WAVES), 0, es, binned,
-                                               (const unsigned *)nullptr, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                        return hipGetLastError();
-                    }
-                    if (full)
-                        hipLaunchKernelGGL((mc::accumulate_blocks_kernel<true, true>), dim3(cus * 2), dim3(64 * mc::ACCB_WAVES), 0, es, binned,
-                                           (const unsigned *)nullptr, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                    else
-                        hipLaunchKernelGGL((mc::accumulate_blocks_kernel<false, true>), dim3(cus * 2), dim3(64 * mc::ACCB_WAVES), 0, es, binned,
-                                           (const unsigned *)nullptr, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                    return hipGetLastError();
-                }
-                hipLaunchKernelGGL(mc::bin_scatter_kernel, dim3(bin_blocks), dim3(256), hist_lds, es, lg.keys, lg.region_count, lg.n_regions,
-                                   lg.region_capacity, n_bins, bin_fill, sorted);
-                if (ctx->est_accumulate == 3) {
-                    if (full)
-                        hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<true, false, true>), dim3(cus * 2), dim3(64 * mc::ACCD_WAVES), 0, es, lg.records, sorted, bin_start,
-                                           slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                    else
-                        hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<false, false, true>), dim3(cus * 2), dim3(64 * mc::ACCD_WAVES), 0, es, lg.records, sorted, bin_start,
-                                           slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                    return hipGetLastError();
-                }
-                if (ctx->est_accumulate == 2) {
-                    if (full)
-                        hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<true, false>), dim3(cus), dim3(64 * mc::ACCD_WAVES), 0, es, lg.records, sorted, bin_start,
-                                           slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                    else
-                        hipLaunchKernelGGL((mc::accumulate_dyadic_kernel<false, false>), dim3(cus), dim3(64 * mc::ACCD_WAVES), 0, es, lg.records, sorted, bin_start,
-                                           slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                    return hipGetLastError();
-                }
-                if (ctx->est_accumulate == 1) {  // one add per aligned block of 8 lines (accumulate_blocks_kernel)
-                    const unsigned acc_blocks = (unsigned)(cus * 2);
-                    if (full)
-                        hipLaunchKernelGGL((mc::accumulate_blocks_kernel<true, false>), dim3(acc_blocks), dim3(64 * mc::ACCB_WAVES), 0, es, lg.records, sorted, bin_start,
-                                           slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                    else
-                        hipLaunchKernelGGL((mc::accumulate_blocks_kernel<false, false>), dim3(acc_blocks), dim3(64 * mc::ACCB_WAVES), 0, es, lg.records, sorted, bin_start,
-                                           slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                    return hipGetLastError();
-                }
-                const unsigned acc_blocks = (unsigned)(cus * 3);
-                if (full)
-                    hipLaunchKernelGGL(mc::accumulate_kernel<true>, dim3(acc_blocks), dim3(64 * mc::ACC_WAVES), 0, es, lg.records, sorted, bin_start,
-                                       slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                else
-                    hipLaunchKernelGGL(mc::accumulate_kernel<false>, dim3(acc_blocks), dim3(64 * mc::ACC_WAVES), 0, es, lg.records, sorted, bin_start,
-                                       slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, P.nu_line, P.jblue_t, P.edot_t);
-                return hipGetLastError();
-            };
-            ctx->post_pending[0] = ctx->post_pending[1] = false;
-            ctx->prop_pending = false;
-            // result streaming: only the plain epoch loop (no volley queue, no CU partition), with the tracker unpacking it needs done per range
-            const bool streaming = rs_armed && !vq && !cu_masked && may_suspend && n >= ctx->rs_min_packets;
-            long long rs_pending_lo = 0, rs_pending_hi = 0;  // a range whose unpacking is queued and whose copy the host still has to issue
-            if (streaming) {
-                ctx->rs.late_capacity = (unsigned)std::min<long long>(n, (long long)waves * 64 * 16);
-                HIP_TRY(ctx, ctx->rs_late.ensure((size_t)ctx->rs.late_capacity * sizeof(unsigned)));
-                HIP_TRY(ctx, ctx->rs_late_count.ensure(sizeof(unsigned)));
-                HIP_TRY(ctx, hipMemsetAsync(ctx->rs_late_count.p, 0, sizeof(unsigned), st));
-                if (!ctx->rs_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->rs_stream, hipStreamNonBlocking));
-                if (!ctx->rs_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->rs_ev, hipEventDisableTiming));
-                if (!ctx->rs_next_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->rs_next_host, sizeof(unsigned long long), hipHostMallocDefault));
-            }
-            auto rs_copy_pending = [&]() -> hipError_t {  // the host's part of a streamed range: sixteen copies into the caller's arrays, beside the running launch
-                if (rs_pending_hi <= rs_pending_lo) return hipSuccess;
-                hipError_t e = hipStreamWaitEvent(ctx->rs_stream, ctx->rs_ev, 0);
-                void *dev[16];
-                per_packet_device_arrays(ctx, dev);
-                const size_t off = (size_t)rs_pending_lo * 8, bytes = (size_t)(rs_pending_hi - rs_pending_lo) * 8;
-                for (int a = 0; a < 16 && e == hipSuccess; ++a)
-                    if (ctx->rs.dst[a] && dev[a]) e = hipMemcpyAsync((char *)ctx->rs.dst[a] + off, (char *)dev[a] + off, bytes, hipMemcpyDeviceToHost, ctx->rs_stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->rs_stream);
-                ctx->rs.upto = rs_pending_hi;
-                rs_pending_lo = rs_pending_hi = 0;
-                return e;
-            };
-            const int max_epochs = 1 << 20;
-            // volley queue: on for the bulk of a call; once a launch requests fewer v-packets than keep the tracer's lanes busy the
-            // launches are bound by their longest v-packet, not by work -- the rest of the call (the drain of the longest-lived
-            // packets) runs in ONE launch with the wave kernel's own pooled volleys
-            bool vq_on = vq;
-            const long long vq_min_items = ctx->vq_min_items >= 0 ? ctx->vq_min_items : (long long)cus * 4 * 64 * 8;
-            bool call_complete = n <= 0;
-            int log_gen = 0;  // (volley queue: the chunk pool of the shared log is reset after every run of the estimator passes)
-            const double records_est = (double)n * ctx->traces_per_packet;  // (tail split: what the call will log, by the last call's measure)
-            double records_done = 0.0;
-            for (int epoch = 0; n > 0 && epoch < max_epochs; ++epoch) {
-                const int b = n_sets == 2 ? (epoch & 1) : 0;
-                hipStream_t es = n_sets == 2 ? ctx->stream2 : st;  // the estimator passes of an epoch run beside the next epoch
-                if (ctx->post_pending[b]) {  // this buffer set was used two epochs ago: its estimator passes must be over
-                    float ms = 0.f;
-                    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_post[2 * b + 1]));
-                    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_post[2 * b], ctx->ev_post[2 * b + 1]));
-                    ctx->sum_post_ms += ms;
-                    ctx->post_pending[b] = false;
-                }
-                mc::EstimatorLog lg{};
-                lg.tiles_per_shell = tiles;
-                lg.records = set_records_ptr(b);
-                lg.keys = set_keys_ptr(b);
-                unsigned long long pool_chunks = n_chunks;
-                if (tail_plan) {
-                    const double bulk = records_est - records_done - tail_records;  // what is left before the tail
-                    if (bulk > 0.0 && bulk <= (double)n_chunks * (double)region_capacity)
-                        pool_chunks = std::min<unsigned long long>(n_chunks, std::max<unsigned long long>((unsigned long long)waves * (shell_log ? (unsigned long long)(ctx->n_shells + 4) : 1ull),
-                                                                                                           (unsigned long long)(bulk / (double)region_capacity) + 1ull));
-                }
-                lg.n_regions = (int)pool_chunks;
-                lg.region_capacity = region_capacity;
-                lg.region_count = ctx->log_cursor[b].as<unsigned>();
-                lg.pool_next = lg.region_count + n_chunks;
-                // (volley queue: the launches of a call go on appending to the same log regions until one of them is full)
-                if (!vq || epoch == 0) HIP_TRY(ctx, hipMemsetAsync(lg.region_count, 0, (size_t)(n_chunks + 1) * sizeof(unsigned), st));
-                HIP_TRY(ctx, hipMemsetAsync(ctx->suspended_dev.p, 0, 4 * sizeof(unsigned), st));
-                if (vq) HIP_TRY(ctx, hipMemsetAsync(ctx->vq_count.p, 0, 2 * sizeof(unsigned), st));
-                mc::WaveCold &wc = ctx->wave_cold_host[epoch & 1];
-                wc.P = P; wc.D = F; wc.log = lg; wc.seeded_states = cur_states;
-                wc.chunk_first = 0; wc.chunk_count = n;
-                wc.launch = ctx->seed_chk[0].as<mc::LaunchRec>();
-                wc.vp_scratch = ctx->vp_scratch[0].as<mc::VpResult>();
-                wc.vp_park = (vpk && !vq_on && ctx->vp_carry_min_active > 0) ? ctx->vp_park.as<mc::VpPark>() : nullptr;
-                wc.vp_carry_min_active = ctx->vp_carry_min_active; wc.vp_pad = 0;
-                wc.save = may_suspend ? cur_save : nullptr;
-                wc.wsave = may_suspend ? cur_wsave : nullptr;
-                wc.resume = epoch > 0 ? 1 : 0;
-                wc.drain_split = split_armed ? 64 : (compact_armed ? ctx->drain_compact : 0);  // (the most live lanes a wave whose supply has run out suspends with)
-                wc.suspended = ctx->suspended_dev.as<unsigned>();
-                wc.vq_req = vq_on ? ctx->vq_req.as<mc::VolleyRequest>() : nullptr;
-                wc.vq_items = vq_on ? ctx->vq_items.as<unsigned>() : nullptr;
-                wc.vq_count = vq ? ctx->vq_count.as<unsigned>() : nullptr;
-                wc.vq_jsave = vq ? ctx->vq_jsave.as<double>() : nullptr;
-                wc.log_continue = vq ? 1 : 0;
-                wc.log_gen = log_gen;
-                mc::WaveCold *wc_dev = ctx->wave_cold_dev.as<mc::WaveCold>() + 2 * (epoch & 1);
-                HIP_TRY(ctx, store_value(st, wc_dev, wc));
-                // split launch (see epoch_split): the estimator passes of the previous epoch are queued (or running) on the second stream
-                // (not the drain launch of a tail-split call: its lanes are the call's critical path, half of them would start behind the bulk's passes)
-                const bool split = ctx->epoch_split && !want_compact && !vq && !cu_masked && !tail_plan && n_sets == 2 && epoch > 0 && es != st && ctx->post_pending[b ^ 1] && waves >= 8 * cus;
-                const int waves1 = split ? waves / 2 : waves_cur;
-                if (split) HIP_TRY(ctx, hipEventRecord(ctx->ev_split[0], st));  // (pool, counters and argument block of this epoch are in place)
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[2], st));
-                hipLaunchKernelGGL(kw, dim3(waves1), dim3(64), wave_lds, st, hot, (const mc::WaveCold *)wc_dev);
-                HIP_TRY(ctx, hipGetLastError());
-                double split_w2 = 0.0;  // share of the grid in the second launch
-                if (split) {
-                    mc::WaveCold wc2 = wc;  // the same epoch for waves [waves1, waves): every per-wave array starts waves1 waves further on
-                    wc2.seeded_states = wc.seeded_states + (size_t)waves1 * 64 * mc::WV_STATE_STRIDE;
-                    if (wc.save) wc2.save = wc.save + (size_t)waves1 * 64;
-                    if (wc.wsave) wc2.wsave = wc.wsave + waves1;
-                    if (wc.vp_scratch) wc2.vp_scratch = wc.vp_scratch + (size_t)waves1 * 64 * mc::VP_ROUND;
-                    if (wc.vp_park) wc2.vp_park = wc.vp_park + (size_t)waves1 * 64;
-                    HIP_TRY(ctx, hipStreamWaitEvent(es, ctx->ev_split[0], 0));
-                    HIP_TRY(ctx, store_value(es, wc_dev + 1, wc2));
-                    HIP_TRY(ctx, hipEventRecord(ctx->ev_split[1], es));
-                    hipLaunchKernelGGL(kw, dim3(waves - waves1), dim3(64), wave_lds, es, hot, (const mc::WaveCold *)(wc_dev + 1));
-                    HIP_TRY(ctx, hipGetLastError());
-                    HIP_TRY(ctx, hipEventRecord(ctx->ev_split[2], es));
-                    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_split[2], 0));  // (what follows on the engine's stream -- the read-back, the next epoch -- follows both)
-                    split_w2 = (double)(waves - waves1) / (double)waves;
-                }
-                if (vq_on) {  // the v-packets this launch requested (the item count is read on the device: an empty list costs a launch)
-                    const size_t geo_lds = (size_t)4 * (size_t)ctx->n_shells * sizeof(double);
-                    const int tracer_waves = cus * 4 * ctx->vq_tracer_waves_per_simd;
-                    if (full) hipLaunchKernelGGL(mc::vpacket_trace_kernel<true>, dim3(tracer_waves), dim3(64), geo_lds, st, (const mc::WaveCold *)wc_dev);
-                    else hipLaunchKernelGGL(mc::vpacket_trace_kernel<false>, dim3(tracer_waves), dim3(64), geo_lds, st, (const mc::WaveCold *)wc_dev);
-                    HIP_TRY(ctx, hipGetLastError());
-                }
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[3], st));
-                if (may_suspend) {  // (read back before the estimator passes are queued: the host learns early whether another epoch follows)
-                    HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host, ctx->suspended_dev.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-                    if (vq) HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host + 4, ctx->vq_count.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-                    if (region_capacity > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host + 6, lg.pool_next, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-                    if (streaming) HIP_TRY(ctx, hipMemcpyAsync(ctx->rs_next_host, ctx->next_packet.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-                    HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4], st));
-                }
-                ctx->launches += 1;
-                if (vq) {
-                    // volley queue: the estimator passes run when a wave reports a full log region, and once at the end of the call
-                    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_chunk[4]));
-                    float ms = 0.f;
-                    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
-                    ctx->sum_prop_ms += ms;
-                    const bool last = ctx->suspended_host[0] == 0;
-                    if (last || ctx->suspended_host[1] > 0) {
-                        HIP_TRY(ctx, hipEventRecord(ctx->ev_post[0], st));
-                        HIP_TRY(ctx, estimator_passes(lg, 0, st));
-                        HIP_TRY(ctx, hipEventRecord(ctx->ev_post[1], st));
-                        HIP_TRY(ctx, hipMemsetAsync(lg.region_count, 0, (size_t)(n_chunks + 1) * sizeof(unsigned), st));
-                        ++log_gen;
-                        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_post[1]));
-                        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_post[0], ctx->ev_post[1]));
-                        ctx->sum_post_ms += ms;
-                    }
-                    if (last) { call_complete = true; break; }
-                    if (vq_on && (long long)ctx->suspended_host[4] < vq_min_items) vq_on = false;
-                    continue;
-                }
-                if (cu_masked) {
-                    // CU partition: the host first learns whether this was the last epoch.  If not, its passes run on the pass stream's CUs beside
-                    // the next epoch; the last epoch's passes take the propagation stream (its CUs are idle now) -- after the passes still
-                    // running on the pass stream, with which they share the scratch copy of the records
-                    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_chunk[4]));
-                    float pms = 0.f;
-                    HIP_TRY(ctx, hipEventElapsedTime(&pms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
-                    ctx->sum_prop_ms += pms;
-                    const bool last = *ctx->suspended_host == 0;
-                    hipStream_t ps = ctx->stream_pass_m;
-                    if (last) {
-                        HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream_pass_m));
-                        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
-                        ps = st;
-                    } else HIP_TRY(ctx, hipStreamWaitEvent(ps, ctx->ev_chunk[3], 0));
-                    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b], ps));
-                    HIP_TRY(ctx, estimator_passes(lg, b, ps));
-                    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b + 1], ps));
-                    ctx->post_pending[b] = true;
-                    if (last) { call_complete = true; break; }
-                    records_done += (double)std::min<unsigned long long>((unsigned long long)ctx->suspended_host[6], pool_chunks) * (double)region_capacity;
-                    if (ctx->suspended_host[2] > 0) split_armed = false;
-                    continue;
-                }
-                if (es != st) HIP_TRY(ctx, hipStreamWaitEvent(es, ctx->ev_chunk[3], 0));
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b], es));
-                HIP_TRY(ctx, estimator_passes(lg, b, es));
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b + 1], es));
-                ctx->post_pending[b] = true;
-                ctx->prop_pending = true;
-                if (!may_suspend) { call_complete = true; break; }  // (no log: the kernel adds its terms directly and never suspends; the call stays asynchronous)
-                // (result streaming: the range unpacked before this launch is copied to the caller's arrays now, while the launch runs)
-                if (streaming) HIP_TRY(ctx, rs_copy_pending());
-                // is anything suspended?  (the only host synchronisation of a call: once per epoch)
-                HIP_TRY(ctx, hipEventSynchronize(ctx->ev_chunk[4]));
-                float ms = 0.f;
-                HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
-                if (split_w2 > 0.0) {  // a split epoch counts with the wave-weighted duration of its two launches (= the time a launch of the whole grid stands for)
-                    float ms2 = 0.f;
-                    HIP_TRY(ctx, hipEventElapsedTime(&ms2, ctx->ev_split[1], ctx->ev_split[2]));
-                    ms = (float)((1.0 - split_w2) * (double)ms + split_w2 * (double)ms2);
-                }
-                ctx->sum_prop_ms += ms;
-                ctx->prop_pending = false;
-                if (*ctx->suspended_host == 0) { call_complete = true; break; }
-                records_done += (double)std::min<unsigned long long>((unsigned long long)ctx->suspended_host[6], pool_chunks) * (double)region_capacity;
-                if (ctx->suspended_host[2] > 0) split_armed = false;  // (the drain has been split off: the next launch runs to the end)
-                if (compact_armed && ctx->suspended_host[2] > 0) {
-                    // some waves have suspended with few live lanes: what is left on the grid?
-                    unsigned *cen = ctx->drain_census.as<unsigned>();
-                    HIP_TRY(ctx, hipMemsetAsync(cen, 0, 8 * sizeof(unsigned), st));
-                    hipLaunchKernelGGL(mc::drain_census_kernel, dim3(waves_cur), dim3(64), 0, st, cur_save, cur_wsave, waves_cur, n, cen);
-                    HIP_TRY(ctx, hipGetLastError());
-                    HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host + 8, cen, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-                    HIP_TRY(ctx, hipStreamSynchronize(st));
-                    const unsigned live = ctx->suspended_host[8], reserved = ctx->suspended_host[9], waiting = ctx->suspended_host[11];
-                    const unsigned density = (unsigned)ctx->drain_pack_lanes;
-                    const int packed = (int)((live + density - 1u) / density);
-                    // (only when nothing is left to hand out, and when it frees more than half of the grid)
-                    if (reserved == 0 && waiting == 0 && live > 0 && 2 * packed <= waves_cur) {
-                        const int g = ctx->compactions & 1;
-                        HIP_TRY(ctx, ctx->lane_save_c[g].ensure((size_t)packed * 64 * sizeof(mc::LaneSave)));
-                        HIP_TRY(ctx, ctx->wave_save_c[g].ensure((size_t)packed * sizeof(mc::WaveSave)));
-                        HIP_TRY(ctx, ctx->seeded_states_c[g].ensure((size_t)packed * 64 * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
-                        HIP_TRY(ctx, hipMemsetAsync(cen + 4, 0, sizeof(unsigned), st));
-                        hipLaunchKernelGGL(mc::drain_compact_kernel, dim3(waves_cur), dim3(64), 0, st, (const mc::LaneSave *)cur_save, (const mc::WaveSave *)cur_wsave,
-                                           (const uint32_t *)cur_states, waves_cur, ctx->lane_save_c[g].as<mc::LaneSave>(), ctx->seeded_states_c[g].as<uint32_t>(), cen + 4, density);
-                        HIP_TRY(ctx, hipGetLastError());
-                        hipLaunchKernelGGL(mc::drain_compact_finish_kernel, dim3((unsigned)((packed * 64 + 255) / 256)), dim3(256), 0, st, ctx->lane_save_c[g].as<mc::LaneSave>(),
-                                           ctx->wave_save_c[g].as<mc::WaveSave>(), (const unsigned *)(cen + 4), n, density);
-                        HIP_TRY(ctx, hipGetLastError());
-                        cur_save = ctx->lane_save_c[g].as<mc::LaneSave>(); cur_wsave = ctx->wave_save_c[g].as<mc::WaveSave>(); cur_states = ctx->seeded_states_c[g].as<uint32_t>();
-                        waves_cur = packed;
-                        ctx->compactions += 1;
-                        if (packed < 2 * cus || (int)density <= 2 * ctx->drain_compact) compact_armed = false;  // (nothing left worth freeing / the packed waves would suspend again at once)
-                    }
-                }
-                if (streaming) {
-                    // packets [0, handed) have been handed out; those of them still in flight (suspended lanes, reserved blocks) go on the late list, the range
-                    // [upto, handed) is unpacked now -- in front of the next launch on the same stream -- and copied by the host beside that launch
-                    const long long handed = (long long)std::min<unsigned long long>(*ctx->rs_next_host, (unsigned long long)n);
-                    if (handed - ctx->rs.upto >= ctx->rs_min_packets) {
-                        hipLaunchKernelGGL(mc::late_list_kernel, dim3(waves_cur), dim3(64), 0, st, (const mc::LaneSave *)cur_save, (const mc::WaveSave *)cur_wsave, waves_cur, ctx->rs.upto, handed,
-                                           ctx->rs_late.as<unsigned>(), ctx->rs_late_count.as<unsigned>(), ctx->rs.late_capacity);
-                        HIP_TRY(ctx, hipGetLastError());
-                        if (ctx->track) {
-                            const long long cnt = handed - ctx->rs.upto;
-                            hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, F, ctx->rs.upto, cnt, (const unsigned *)nullptr);
-                            HIP_TRY(ctx, hipGetLastError());
-                        }
-                        HIP_TRY(ctx, hipEventRecord(ctx->rs_ev, st));
-                        rs_pending_lo = ctx->rs.upto; rs_pending_hi = handed;
-                    }
-                }
-            }
-            if (streaming && call_complete) HIP_TRY(ctx, rs_copy_pending());  // (a range queued before the last launch)
-            if (!call_complete)  // (packets would be left suspended in lane_save, outputs and estimators silently incomplete)
-                return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: %d launches did not finish the call (waves still suspended)", max_epochs);
-            if (cu_masked) {  // both masked streams join the engine's stream
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream_pass_m));
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_join_m, st));
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join_m, 0));
-            } else if (n_sets == 2 && (ctx->post_pending[0] || ctx->post_pending[1])) {
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-            }
-            ctx->wave_epoch_mode = true;
-            ctx->progress_done = true;  // (every packet has been handed out and has ended: the host read "nothing suspended")
-            long long unpack_from = 0;
-            if (streaming && ctx->rs.upto > 0) {
-                // what was streamed: [0, upto) minus the late list.  The list's length is read back here (the call has synchronised with every launch already)
-                unsigned n_late = 0;
-                HIP_TRY(ctx, hipMemcpyAsync(&n_late, ctx->rs_late_count.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                if (n_late <= ctx->rs.late_capacity) {
-                    ctx->rs.valid = true;
-                    ctx->rs.n_late = n_late;
-                    unpack_from = ctx->rs.upto;
-                    if (n_late > 0) {
-                        if (ctx->track) {
-                            hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((n_late + 255) / 256), dim3(256), 0, ctx->stream, F, 0LL, (long long)n_late, ctx->rs_late.as<unsigned>());
-                            HIP_TRY(ctx, hipGetLastError());
-                        }
-                        HIP_TRY(ctx, ctx->rs_vals.ensure((size_t)16 * n_late * 8));
-                        void *dev[16];
-                        per_packet_device_arrays(ctx, dev);
-                        for (int a = 0; a < 16; ++a)
-                            if (ctx->rs.dst[a] && dev[a]) {
-                                hipLaunchKernelGGL(mc::gather64_kernel, dim3((n_late + 255) / 256), dim3(256), 0, ctx->stream, (const unsigned long long *)dev[a],
-                                                   ctx->rs_late.as<unsigned>(), (long long)n_late, ctx->rs_vals.as<unsigned long long>() + (size_t)a * n_late);
-                                HIP_TRY(ctx, hipGetLastError());
-                            }
-                    }
-                }  // (else: the list overflowed -- get_results copies everything)
-            }
-            if (ctx->track && n > unpack_from) {  // the wave kernel's tracker records -> the boundary's arrays
-                hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((unsigned)((n - unpack_from + 255) / 256)), dim3(256), 0, ctx->stream, F, unpack_from, n - unpack_from,
-                                   (const unsigned *)nullptr);
-                HIP_TRY(ctx, hipGetLastError());
-            }
-        } else {
-            ctx->wave_epoch_mode = false;
-            long long chunk = std::min<long long>(std::max<long long>(ctx->n_packets, 1), ctx->chunk_packets);
-            HIP_TRY(ctx, ctx->seeded_states.ensure((size_t)chunk * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
-            // group size: 8 lanes per packet pays off when the sweeps between events are short (sparse line lists)
-            const int G = ctx->group_size == 8 ? 8 : (ctx->group_size == 16 ? 16 : ((ctx->n_lines <= 100000 && !vpk) ? 8 : 16));
-            const int block = 256;
-            const size_t lds = G == 8 ? mc::group_kernel_lds_bytes<8, 256>(ctx->n_shells) : mc::group_kernel_lds_bytes<16, 256>(ctx->n_shells);
-            if (lds > 160 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
-            const int blocks_per_cu = std::max(1, std::min(std::min(ctx->blocks_per_cu, 8), (int)((160 * 1024) / lds)));
-            using KernelFn = void (*)(mc::GroupArgs, uint32_t *, long long, long long);
-            KernelFn k;
-#define TMC_PICK2(G_, V_) (full ? (trk ? mc::propagate_group_kernel<true, true, G_, 256, 4, V_> : mc::propagate_group_kernel<true, false, G_, 256, 4, V_>) \
-                                : (trk ? mc::propagate_group_kernel<false, true, G_, 256, 4, V_> : mc::propagate_group_kernel<false, false, G_, 256, 4, V_>))
-#define TMC_PICK2W(G_, V_) (full ? (trk ? mc::propagate_group_kernel<true, true, G_, 256, 4, V_, true> : mc::propagate_group_kernel<true, false, G_, 256, 4, V_, true>) \
-                                 : (trk ? mc::propagate_group_kernel<false, true, G_, 256, 4, V_, true> : mc::propagate_group_kernel<false, false, G_, 256, 4, V_, true>))
-            if (w64) k = G == 16 ? (vpk ? TMC_PICK2W(16, true) : TMC_PICK2W(16, false)) : (vpk ? TMC_PICK2W(8, true) : TMC_PICK2W(8, false));
-            else if (G == 16) k = vpk ? TMC_PICK2(16, true) : TMC_PICK2(16, false);
-            else k = vpk ? TMC_PICK2(8, true) : TMC_PICK2(8, false);
-#undef TMC_PICK2W
-#undef TMC_PICK2
-            hipStream_t st = ctx->stream;
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_start, st));
-            uint32_t *seeded = ctx->seeded_states.as<uint32_t>();
-            for (long long first = 0; first < ctx->n_packets; first += chunk) {
-                const long long count = std::min(chunk, ctx->n_packets - first);
-                const int ci = ctx->chunks_timed;
-                while ((int)ctx->ev_chunk.size() < 4 * (ci + 1)) {
-                    hipEvent_t e;
-                    HIP_TRY(ctx, hipEventCreate(&e));
-                    ctx->ev_chunk.push_back(e);
-                }
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci], st));
-                hipLaunchKernelGGL(mc::seed_states_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st,
-                                   ctx->seeds.as<uint32_t>(), seeded, first, count, mc::MT_N);
-                HIP_TRY(ctx, hipGetLastError());
-                HIP_TRY(ctx, hipMemsetAsync(ctx->next_packet.p, 0, sizeof(unsigned long long), st));
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci + 1], st));
-                const int groups_per_block = block / G;
-                long long want_blocks = (count + groups_per_block - 1) / groups_per_block;
-                int blocks = (int)std::max<long long>(1, std::min<long long>(want_blocks, (long long)cus * blocks_per_cu));
-                // (the group kernel updates the line estimators with atomics: logging its traces was measured and is a loss
-                // there -- the record bookkeeping costs its redundant-lane event loop more than the deferred atomics do)
-                hipLaunchKernelGGL(k, dim3(blocks), dim3(block), lds, st, P, seeded, first, count);
-                HIP_TRY(ctx, hipGetLastError());
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci + 2], st));
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci + 3], st));
-                ctx->chunks_timed = ci + 1;
-            }
-        }
-    }
+    if (call.plan.error) return fail(ctx, call.plan.error, "%s", call.plan.message);
+    ctx->last_table_offsets = call.plan.last_table_offsets;
+    ctx->last_variant = call.plan.last_variant;
+    rc = call.plan.cooperative ? run_cooperative(ctx, call) : run_lane_kernel(ctx, call);
+    if (rc) return rc;
     {   // events per packet of this call, for the log sizing of the next one (asynchronous, pinned host memory)
         if (!ctx->events_host) {
             HIP_TRY(ctx, hipHostMalloc((void **)&ctx->events_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
@@ -2597,9 +2698,9 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     ctx->timed = true;
-    if (tune_slot >= 0) {
+    if (call.tune_slot >= 0) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_tune[1], ctx->stream));
-        ctx->ls_tune.pending = tune_slot;
+        ctx->ls_tune.pending = call.tune_slot;
     }
     ctx->ev_valid = ctx->track_full;  // (a call that failed half-way leaves no event log to read)
     return TARDIS_MC_OK;
