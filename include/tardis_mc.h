@@ -215,6 +215,8 @@ const char *tardis_mc_last_error(const TardisMcContext *ctx);   /* ctx may be NU
  * 100000), "ls_waves_per_simd" (which instantiation of the lane-sweep kernel: 4 = 128 VGPRs, sixteen waves per CU, eight lines per step; 3 = 166 VGPRs,
  * twelve waves per CU, twelve lines per step -- faster where a call is mostly the drain of its longest packets; 0, the default: the engine times both on
  * the first calls of a (packet count, tables) key and keeps the faster; per-packet results are bit-identical either way), "pass_cus" (CUs per XCD set aside for the line-estimator passes through CU-masked streams; default 0 = off: measured, never pays),
+ * "source_max_iterations" (tardis_mc_source_function: bound on the fixed-point iterations of the macro-atom level solve, default 20000; a solve
+ * that reaches it fails with TARDIS_MC_ERR_STATE),
  * "debug_flags" (profiling experiments / cross-checks only: 1 skips the j_blue/Edotlu updates, 2 the J/nu_bar updates, 128
  * walks the macro atom by a per-lane search in the fp64 running sums, 8192 by the cooperative group scan; tests: 16384 counts
  * the jumps out of blocks longer than one window of the compact walk tables into counters[7], 32768 the jumps decided by the
@@ -316,13 +318,43 @@ int tardis_mc_radiation_field(TardisMcContext *ctx, double time_of_simulation, c
 /* ---- consumer next to the path: the formal integral of the spectrum ----------------------------------------
  * NumbaFormalIntegrator.formal_integral / numba_formal_integral (tardis/spectrum/formal_integral/formal_integral_numba.py:
  * 375-560, 563-642; CUDA twin formal_integral_cuda.py:272-489) on the resident geometry, line list, tau_sobolev and electron
- * densities (set_geometry / set_opacity).  att_S_ul, Jred_lu, Jblue_lu: host, [n_shells * n_lines] in the shell-major flat
+ * densities (set_geometry / set_opacity).  (The three inputs can be computed on the device and stay there: tardis_mc_source_function /
+ * tardis_mc_formal_integral_resident below.)  att_S_ul, Jred_lu, Jblue_lu: host, [n_shells * n_lines] in the shell-major flat
  * order the reference passes them (make_source_function, source_function.py:71-75).  Outputs (host): luminosity_densities
  * [n_frequencies]; intensities_nu_p [n_frequencies * n_impact_parameters] or NULL.  tardis_mc_last_propagate_ms then
  * reports the device time of the integration kernels. */
 int tardis_mc_formal_integral(TardisMcContext *ctx, double inner_temperature, const double *frequencies, int64_t n_frequencies,
                               const double *att_S_ul, const double *Jred_lu, const double *Jblue_lu, int64_t n_impact_parameters,
                               double *luminosity_densities, double *intensities_nu_p);
+
+/* ---- producer of the formal integral's inputs: the line source function from the resident estimators ---------------------
+ * make_source_function (tardis/spectrum/formal_integral/source_function.py) on the resident probabilities, macro-atom index tables,
+ * tau_sobolev and the j_blue / Edotlu estimators; runs after tardis_mc_propagate (multi-GPU: after tardis_mc_allreduce_estimators).
+ * Per shell s:  Edotlu = (1 / (time_of_simulation volume[s])) (1 - exp(-tau)) Edotlu_estimator;  e_dot_u[k] = its sum over the lines
+ * with upper level k;  C = e_dot_u (downbranch) or the solution of (I - Q_s)^T C = e_dot_u (macroatom; Q_s[i][j] = sum of the
+ * probabilities of the rows of block i with transition_type >= 0 and destination level j), found by the fixed-point iteration
+ * C <- e_dot_u + Q_s^T C until max|dC| <= 1e-14 max|C| in every shell, tested every 16 iterations (option "source_max_iterations");
+ * att_S_ul[s][l] = wave[l] (prob[s][t] C[k]) time_of_simulation / (4 pi) for the emission row t (transition_type -1) of line l, in
+ * block k;  Jblue_lu[s][l] = j_blue_estimator[s][l] c t_exp / (4 pi time_of_simulation volume[s]) (bit for bit the j_blues of
+ * tardis_mc_radiation_field where the estimator is non-zero);  Jred_lu = Jblue_lu exp(-tau) + att_S_ul.
+ * volume: [n_shells] cm^3.  wavelength_cm: [n_lines], or NULL for c / line_list_nu.  Outputs (host, any may be NULL): att_S_ul, Jred_lu,
+ * Jblue_lu [n_shells * n_lines], flat shell-major as tardis_mc_formal_integral takes them; e_dot_u [levels * n_shells], level-major
+ * (for macroatom: C, as the reference returns it).  The three arrays also stay in HBM, marked valid for
+ * tardis_mc_formal_integral_resident until the next tardis_mc_set_opacity, _set_geometry, _reset_estimators, _propagate or
+ * _allreduce_estimators.  Errors: TARDIS_MC_ERR_UNSUPPORTED for scatter mode (no macro-atom tables; the reference refuses it too),
+ * TARDIS_MC_ERR_INVALID_ARGUMENT when some line has no emission row or several, TARDIS_MC_ERR_STATE without propagated estimators or when
+ * the solve reaches its iteration bound or meets NaN / infinite rates (the message names the worst shell; nothing is left valid).  No atomics: two calls give
+ * bit-identical results.  tardis_mc_last_propagate_ms then reports the device time of the call's kernels. */
+int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, const double *volume, const double *wavelength_cm,
+                              double *att_S_ul, double *Jred_lu, double *Jblue_lu, double *e_dot_u);
+/* Fixed-point iterations of the last tardis_mc_source_function (a multiple of 16 unless the bound cut it short); 0 for downbranch,
+ * -1 before the first call. */
+int tardis_mc_last_source_iterations(TardisMcContext *ctx);
+/* tardis_mc_formal_integral on the att_S_ul / Jred_lu / Jblue_lu that tardis_mc_source_function left in HBM: same kernels, same
+ * outputs, no [n_shells * n_lines] array crosses the bus, and exp(-tau) is the table the source function computed.
+ * TARDIS_MC_ERR_STATE when no valid resident source function exists. */
+int tardis_mc_formal_integral_resident(TardisMcContext *ctx, double inner_temperature, const double *frequencies, int64_t n_frequencies,
+                                       int64_t n_impact_parameters, double *luminosity_densities, double *intensities_nu_p);
 
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the

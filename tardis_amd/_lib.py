@@ -48,6 +48,9 @@ SYMBOLS = {
     "tardis_mc_packet_spectrum": (_i, [_vp, C.c_double, C.c_double, C.c_double, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tardis_mc_radiation_field": (_i, [_vp, C.c_double, _vp, C.c_double, C.c_int, _vp, _vp, _vp]),
     "tardis_mc_formal_integral": (_i, [_vp, C.c_double, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
+    "tardis_mc_source_function": (_i, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tardis_mc_last_source_iterations": (_i, [_vp]),
+    "tardis_mc_formal_integral_resident": (_i, [_vp, C.c_double, _vp, C.c_int64, C.c_int64, _vp, _vp]),
     "tardis_mc_get_event_log": (_i, [_vp, _vp]),
     "tardis_mc_stream_results": (_i, [_vp, _vp]),
     "tardis_mc_streamed_packets": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

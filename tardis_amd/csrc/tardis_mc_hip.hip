@@ -29,6 +29,7 @@
 #include "propagate_wave.hpp"
 #include "packet_source.hpp"
 #include "formal_integral.hpp"
+#include "source_function.hpp"
 #include "tau_prefix.hpp"
 #include "propagate_plan.hpp"
 
@@ -282,6 +283,19 @@ struct TardisMcContext {
     hipEvent_t rs_ev = nullptr;
     unsigned long long *rs_next_host = nullptr;  // pinned: the packet counter after a launch
     long long rs_min_packets = 1000000;  // a range worth sixteen copies of its own (option stream_min_packets; tests lower it)
+    // source function of the formal integral (source_function.hpp).  Per set_opacity: the CSR indices {lines of every upper level}, {internal rows
+    // ending in every level, with the level each leaves}, every line's emission row and its block (sf_topo_error: a line with none or several), and
+    // the exp(-tau) table shared with the formal integral.  Per call: the level vectors e / x[2], the gathered probabilities q, the outputs.
+    DevBuf sf_lvl_ptr, sf_lvl_line, sf_in_ptr, sf_in_row, sf_in_src, sf_emit_row, sf_emit_level;
+    bool sf_topo_valid = false;
+    std::string sf_topo_error;
+    long long sf_nnz = 0;
+    DevBuf sf_exp_tau, sf_e, sf_x[2], sf_q, sf_shell, sf_conv, sf_wave, sf_att, sf_jred, sf_jblue;
+    bool sf_exp_valid = false;
+    bool sf_valid = false;                     // the resident att_S_ul / Jred_lu / Jblue_lu belong to the resident estimators and tables
+    double *sf_conv_host = nullptr;            // pinned: {max |dx|, max |x|} per shell
+    long long source_max_iterations = 20000;   // option: bound on the iterations of a solve
+    int last_source_iterations = -1;
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -1990,6 +2004,10 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     if (ctx->events_host) (void)hipHostFree(ctx->events_host);
     if (ctx->ev_events) (void)hipEventDestroy(ctx->ev_events);
     ctx->rs_late.release(); ctx->rs_late_count.release(); ctx->rs_vals.release();
+    for (DevBuf *b : {&ctx->sf_lvl_ptr, &ctx->sf_lvl_line, &ctx->sf_in_ptr, &ctx->sf_in_row, &ctx->sf_in_src, &ctx->sf_emit_row, &ctx->sf_emit_level, &ctx->sf_exp_tau,
+                      &ctx->sf_e, &ctx->sf_x[0], &ctx->sf_x[1], &ctx->sf_q, &ctx->sf_shell, &ctx->sf_conv, &ctx->sf_wave, &ctx->sf_att, &ctx->sf_jred, &ctx->sf_jblue})
+        b->release();
+    if (ctx->sf_conv_host) (void)hipHostFree(ctx->sf_conv_host);
     if (ctx->rs_stream) (void)hipStreamDestroy(ctx->rs_stream);
     if (ctx->rs_ev) (void)hipEventDestroy(ctx->rs_ev);
     if (ctx->rs_next_host) (void)hipHostFree(ctx->rs_next_host);
@@ -2064,6 +2082,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "pipeline_chunks") {}  // (round 1: chunks on two streams; a call of the wave kernel now runs as epochs -- accepted, ignored)
     else if (n == "log_capacity") { ctx->log_capacity = std::max<long long>(0, value); ctx->log_capacity_user = true; }
     else if (n == "log_sets") ctx->log_sets = (value == 1 || value == 2) ? (int)value : 0;  // 1: the estimator passes of an epoch run before the next epoch, not beside it; 0: automatic
+    else if (n == "source_max_iterations") ctx->source_max_iterations = std::max<long long>(1, value);
     else if (n == "chunk_packets") ctx->chunk_packets = std::max<long long>(1024, value);
     else return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return TARDIS_MC_OK;
@@ -2074,6 +2093,7 @@ int tardis_mc_set_geometry(TardisMcContext *ctx, const TardisMcGeometry *g)
     if (!ctx || !g || g->n_shells <= 0 || !g->r_inner || !g->r_outer)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid geometry");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->sf_valid = false;
     int rc;
     if ((rc = upload(ctx, ctx->r_inner, g->r_inner, (size_t)g->n_shells))) return rc;
     if ((rc = upload(ctx, ctx->r_outer, g->r_outer, (size_t)g->n_shells))) return rc;
@@ -2092,6 +2112,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     if (o->n_lines > 0x7ffffff0LL || o->n_transitions > 0x7ffffff0LL)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "line / transition count exceeds 32-bit device indices");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->sf_valid = ctx->sf_topo_valid = ctx->sf_exp_valid = false;
     const bool tmark_on = getenv("TARDIS_MC_TIME_OPACITY") != nullptr;  // (diagnostic: wall time of the stages of this call on stderr)
     auto tmark_t0 = std::chrono::steady_clock::now();
     auto tmark = [&](const char *what) {
@@ -2605,6 +2626,7 @@ int tardis_mc_reset_estimators(TardisMcContext *ctx)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->sf_valid = false;
     int rc = ensure_estimators(ctx);
     if (rc) return rc;
     if (!ctx->est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_config must precede reset_estimators");
@@ -2623,6 +2645,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->compactions = 0;
     ctx->ev_valid = false;
+    ctx->sf_valid = false;
     const TardisMcConfig &c = ctx->cfg;
     PropagateCall call{};
     call.vpk = c.number_of_vpackets > 0;
@@ -3130,31 +3153,53 @@ int tardis_mc_radiation_field(TardisMcContext *ctx, double time_of_simulation, c
     return TARDIS_MC_OK;
 }
 
-int tardis_mc_formal_integral(TardisMcContext *ctx, double inner_temperature, const double *frequencies, int64_t n_frequencies,
-                              const double *att_S_ul, const double *Jred_lu, const double *Jblue_lu, int64_t n_impact_parameters,
-                              double *luminosity_densities, double *intensities_nu_p)
+// exp(-tau) in the layout of tau_t, kept until the next set_opacity: the source function and the resident formal integral after it read one table
+static int ensure_exp_tau(TardisMcContext *ctx)
+{
+    if (ctx->sf_exp_valid) return TARDIS_MC_OK;
+    const size_t n = (size_t)ctx->n_shells * (size_t)ctx->n_lines;
+    HIP_TRY(ctx, ctx->sf_exp_tau.ensure(n * sizeof(double)));
+    hipLaunchKernelGGL(mc::fi_exp_tau_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->tau_t.as<double>(), (long long)n, ctx->sf_exp_tau.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->sf_exp_valid = true;
+    return TARDIS_MC_OK;
+}
+
+// the formal integral on the caller's att_S_ul / Jred_lu / Jblue_lu (host), or -- `resident` -- on the copies tardis_mc_source_function left in HBM
+static int formal_integral_impl(TardisMcContext *ctx, bool resident, double inner_temperature, const double *frequencies, int64_t n_frequencies,
+                                const double *att_S_ul, const double *Jred_lu, const double *Jblue_lu, int64_t n_impact_parameters,
+                                double *luminosity_densities, double *intensities_nu_p)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_geometry || !ctx->have_opacity)
         return fail(ctx, TARDIS_MC_ERR_STATE, "formal integral needs set_geometry and set_opacity");
-    if (!frequencies || !att_S_ul || !Jred_lu || !Jblue_lu || !luminosity_densities || n_frequencies < 0 || n_impact_parameters < 2 ||
+    if (resident && !ctx->sf_valid)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "no resident source function: tardis_mc_source_function must follow the last propagate / all-reduce");
+    if (!frequencies || (!resident && (!att_S_ul || !Jred_lu || !Jblue_lu)) || !luminosity_densities || n_frequencies < 0 || n_impact_parameters < 2 ||
         n_frequencies > (1LL << 30) || n_impact_parameters > 65535)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid formal integral arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, n_nu = (size_t)n_frequencies, N = (size_t)n_impact_parameters;
     if (n_nu == 0) return TARDIS_MC_OK;
-    DevBuf work;  // [exp_tau | att | jred | jblue | freqs | z | I | Lum] doubles, then sid / n_int ints
-    const size_t n_d = 4 * S * L + n_nu + N * 2 * S + n_nu * N + n_nu;
+    DevBuf work;  // [exp_tau | att | jred | jblue | freqs | z | I | Lum] doubles, then sid / n_int ints (resident: no tables in front)
+    const size_t n_tab = resident ? 0 : S * L;
+    const size_t n_d = 4 * n_tab + n_nu + N * 2 * S + n_nu * N + n_nu;
     HIP_TRY(ctx, work.ensure(n_d * sizeof(double) + (N * 2 * S + N) * sizeof(int)));
-    double *d_exp = work.as<double>(), *d_att = d_exp + S * L, *d_jred = d_att + S * L, *d_jblue = d_jred + S * L,
-           *d_freq = d_jblue + S * L, *d_z = d_freq + n_nu, *d_I = d_z + N * 2 * S, *d_lum = d_I + n_nu * N;
+    double *d_exp = work.as<double>(), *d_att = d_exp + n_tab, *d_jred = d_att + n_tab, *d_jblue = d_jred + n_tab,
+           *d_freq = d_jblue + n_tab, *d_z = d_freq + n_nu, *d_I = d_z + N * 2 * S, *d_lum = d_I + n_nu * N;
     int *d_sid = reinterpret_cast<int *>(d_lum + n_nu), *d_nint = d_sid + N * 2 * S;
-    HIP_TRY(ctx, hipMemcpyAsync(d_att, att_S_ul, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_jred, Jred_lu, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_jblue, Jblue_lu, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (!resident) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_att, att_S_ul, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_jred, Jred_lu, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_jblue, Jblue_lu, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
     HIP_TRY(ctx, hipMemcpyAsync(d_freq, frequencies, n_nu * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    if (S * L > 0)
+    if (resident) {
+        int rc_exp = ensure_exp_tau(ctx);  // (the source function has computed it: set_opacity, which drops the table, drops sf_valid too)
+        if (rc_exp) return rc_exp;
+        d_exp = ctx->sf_exp_tau.as<double>(); d_att = ctx->sf_att.as<double>(); d_jred = ctx->sf_jred.as<double>(); d_jblue = ctx->sf_jblue.as<double>();
+    } else if (S * L > 0)
         hipLaunchKernelGGL(mc::fi_exp_tau_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->tau_t.as<double>(), (long long)(S * L), d_exp);
     hipLaunchKernelGGL(mc::fi_intersections_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, ctx->stream, (int)S,
                        ctx->r_inner.as<double>(), ctx->r_outer.as<double>(), ctx->t_exp, (int)N, d_z, d_sid, d_nint);
@@ -3185,6 +3230,218 @@ int tardis_mc_formal_integral(TardisMcContext *ctx, double inner_temperature, co
     work.release();
     return TARDIS_MC_OK;
 }
+
+int tardis_mc_formal_integral(TardisMcContext *ctx, double inner_temperature, const double *frequencies, int64_t n_frequencies,
+                              const double *att_S_ul, const double *Jred_lu, const double *Jblue_lu, int64_t n_impact_parameters,
+                              double *luminosity_densities, double *intensities_nu_p)
+{
+    return formal_integral_impl(ctx, false, inner_temperature, frequencies, n_frequencies, att_S_ul, Jred_lu, Jblue_lu, n_impact_parameters,
+                                luminosity_densities, intensities_nu_p);
+}
+
+int tardis_mc_formal_integral_resident(TardisMcContext *ctx, double inner_temperature, const double *frequencies, int64_t n_frequencies,
+                                       int64_t n_impact_parameters, double *luminosity_densities, double *intensities_nu_p)
+{
+    return formal_integral_impl(ctx, true, inner_temperature, frequencies, n_frequencies, nullptr, nullptr, nullptr, n_impact_parameters,
+                                luminosity_densities, intensities_nu_p);
+}
+
+/* ---- the source function of the formal integral from the resident estimators (source_function.hpp) ---------------- */
+// The two CSR indices and the emission row of every line, by counting sort over the index tables (once per set_opacity).
+static int build_source_topology(TardisMcContext *ctx)
+{
+    if (ctx->sf_topo_valid) return TARDIS_MC_OK;
+    const size_t L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans, K = (size_t)ctx->n_levels;
+    std::vector<int> l2l(L), edge(K + 1), ttype(T), dest(T), tline(T);
+    HIP_TRY(ctx, hipMemcpyAsync(l2l.data(), ctx->line2level.p, L * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(edge.data(), ctx->block_edge.p, (K + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ttype.data(), ctx->ttype.p, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dest.data(), ctx->dest.p, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(tline.data(), ctx->tline.p, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // lines by upper level (the tables were range-checked by set_opacity)
+    std::vector<int> lvl_ptr(K + 1, 0), lvl_line(L);
+    for (size_t l = 0; l < L; ++l) lvl_ptr[(size_t)l2l[l] + 1]++;
+    for (size_t k = 0; k < K; ++k) lvl_ptr[k + 1] += lvl_ptr[k];
+    {
+        std::vector<int> at(lvl_ptr.begin(), lvl_ptr.end() - 1);
+        for (size_t l = 0; l < L; ++l) lvl_line[(size_t)at[(size_t)l2l[l]]++] = (int)l;
+    }
+    // internal rows by destination level, each with the level (block) it leaves; emission rows by line
+    std::vector<int> in_ptr(K + 1, 0), emit_row(L, 0), emit_level(L, 0), emit_n(L, 0);
+    for (size_t k = 0; k < K; ++k)
+        for (int t = edge[k]; t < edge[k + 1]; ++t) {
+            if (ttype[(size_t)t] >= 0) in_ptr[(size_t)dest[(size_t)t] + 1]++;
+            else if (ttype[(size_t)t] == -1) {
+                const size_t l = (size_t)tline[(size_t)t];
+                if (emit_n[l]++ == 0) { emit_row[l] = t; emit_level[l] = (int)k; }
+            }
+        }
+    for (size_t k = 0; k < K; ++k) in_ptr[k + 1] += in_ptr[k];
+    const size_t nnz = (size_t)in_ptr[K];
+    std::vector<int> in_row(std::max<size_t>(nnz, 1)), in_src(std::max<size_t>(nnz, 1));
+    {
+        std::vector<int> at(in_ptr.begin(), in_ptr.end() - 1);
+        for (size_t k = 0; k < K; ++k)
+            for (int t = edge[k]; t < edge[k + 1]; ++t)
+                if (ttype[(size_t)t] >= 0) {
+                    const int j = at[(size_t)dest[(size_t)t]]++;
+                    in_row[(size_t)j] = t; in_src[(size_t)j] = (int)k;
+                }
+    }
+    ctx->sf_topo_error.clear();
+    for (size_t l = 0; l < L; ++l)
+        if (emit_n[l] != 1) {
+            char buf[128];
+            snprintf(buf, sizeof buf, "line %zu has %d emission rows (transition_type -1) in the macro-atom blocks, expected one", l, emit_n[l]);
+            ctx->sf_topo_error = buf;
+            break;
+        }
+    int rc;
+    if ((rc = upload(ctx, ctx->sf_lvl_ptr, lvl_ptr.data(), K + 1))) return rc;
+    if ((rc = upload(ctx, ctx->sf_lvl_line, lvl_line.data(), L))) return rc;
+    if ((rc = upload(ctx, ctx->sf_in_ptr, in_ptr.data(), K + 1))) return rc;
+    if ((rc = upload(ctx, ctx->sf_in_row, in_row.data(), in_row.size()))) return rc;
+    if ((rc = upload(ctx, ctx->sf_in_src, in_src.data(), in_src.size()))) return rc;
+    if ((rc = upload(ctx, ctx->sf_emit_row, emit_row.data(), L))) return rc;
+    if ((rc = upload(ctx, ctx->sf_emit_level, emit_level.data(), L))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors go out of scope)
+    ctx->sf_nnz = (long long)nnz;
+    ctx->sf_topo_valid = true;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, const double *volume, const double *wavelength_cm,
+                              double *att_S_ul, double *Jred_lu, double *Jblue_lu, double *e_dot_u)
+{
+    if (!ctx || !volume) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    ctx->sf_valid = false;
+    if (!ctx->est_valid || !ctx->have_opacity || !ctx->have_geometry || !ctx->have_config)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "source function needs propagated estimators");
+    if (!(time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "time_of_simulation must be positive");
+    const int mode = ctx->cfg.line_interaction_type;
+    if (mode == TARDIS_MC_LINE_SCATTER || ctx->n_levels <= 0 || ctx->n_trans <= 1)
+        return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "the source function needs macro-atom tables (line_interaction_type downbranch or macroatom)");
+    if (mode != TARDIS_MC_LINE_DOWNBRANCH && mode != TARDIS_MC_LINE_MACROATOM)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown line_interaction_type %d", mode);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = build_source_topology(ctx);
+    if (rc) return rc;
+    if (!ctx->sf_topo_error.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", ctx->sf_topo_error.c_str());
+    if ((rc = reduce_estimator_copies(ctx))) return rc;
+    const size_t S = ctx->est_S, L = ctx->est_L, K = (size_t)ctx->n_levels, T = (size_t)ctx->n_trans;
+    const long long nnz = ctx->sf_nnz;
+    const bool solve = mode == TARDIS_MC_LINE_MACROATOM && nnz > 0;
+    EstLayout lay = est_layout(S, L, ctx->est_G, ctx->est_copies);
+    const double *est = ctx->est.as<double>();
+    HIP_TRY(ctx, ctx->sf_shell.ensure(3 * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->sf_e.ensure(S * K * sizeof(double)));
+    HIP_TRY(ctx, ctx->sf_att.ensure(S * L * sizeof(double)));
+    HIP_TRY(ctx, ctx->sf_jred.ensure(S * L * sizeof(double)));
+    HIP_TRY(ctx, ctx->sf_jblue.ensure(S * L * sizeof(double)));
+    if (solve) {
+        HIP_TRY(ctx, ctx->sf_x[0].ensure(S * K * sizeof(double)));
+        HIP_TRY(ctx, ctx->sf_x[1].ensure(S * K * sizeof(double)));
+        HIP_TRY(ctx, ctx->sf_q.ensure(S * (size_t)nnz * sizeof(double)));
+        HIP_TRY(ctx, ctx->sf_conv.ensure(2 * S * sizeof(double)));
+        if (!ctx->sf_conv_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->sf_conv_host, 2 * 4096 * sizeof(double), hipHostMallocDefault));
+        if (S > 4096) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "source function: more than 4096 shells");
+    }
+    if (wavelength_cm && (rc = upload(ctx, ctx->sf_wave, wavelength_cm, L))) return rc;
+    double *d_vol = ctx->sf_shell.as<double>(), *d_ne = d_vol + S, *d_nj = d_ne + S;
+    HIP_TRY(ctx, hipMemcpyAsync(d_vol, volume, S * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    const double pi = 3.141592653589793;
+    hipLaunchKernelGGL(mc::sf_shell_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, ctx->stream, d_vol, (int)S, time_of_simulation,
+                       mc::C_LIGHT * ctx->t_exp, 4 * pi * time_of_simulation, d_ne, d_nj);
+    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = ensure_exp_tau(ctx))) return rc;
+    // lanes per CSR row of the two indices (a function of the tables alone: the summation order does not change from call to call)
+    const int g_lvl = mc::sf_group_width((long long)L, (long long)K), g_in = mc::sf_group_width(nnz, (long long)K);
+    auto row_grid = [&](int g) { return dim3((unsigned)((K * (size_t)g + 255) / 256), (unsigned)S); };
+    {
+        auto kernel = g_lvl == 1 ? mc::sf_level_sums_kernel<1> : (g_lvl == 4 ? mc::sf_level_sums_kernel<4> : mc::sf_level_sums_kernel<16>);
+        hipLaunchKernelGGL(kernel, row_grid(g_lvl), dim3(256), 0, ctx->stream, ctx->sf_lvl_ptr.as<int>(), ctx->sf_lvl_line.as<int>(), (int)K,
+                           (long long)L, ctx->sf_exp_tau.as<double>(), est + lay.edot, d_ne, ctx->sf_e.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    const double *c_level = ctx->sf_e.as<double>();
+    int iterations = 0;
+    if (solve) {
+        const unsigned gx = (unsigned)std::min<long long>((nnz + 255) / 256, 2048);
+        hipLaunchKernelGGL(mc::sf_gather_q_kernel, dim3(gx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->sf_in_row.as<int>(), nnz,
+                           ctx->prob_t.as<double>(), (long long)T, ctx->sf_q.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+        // x ping-pongs between sf_x[0] and sf_x[1]; the first iteration reads e itself.  Every 16 iterations (or at the cap) the per-shell
+        // {max |dx|, max |x|} of the last one come to the host.
+        auto iterate = g_in == 1 ? mc::sf_iterate_kernel<1> : (g_in == 4 ? mc::sf_iterate_kernel<4> : mc::sf_iterate_kernel<16>);
+        const double *cur = ctx->sf_e.as<double>();
+        const long long cap = ctx->source_max_iterations;
+        bool converged = false, diverged = false;
+        int worst = 0;
+        double worst_ratio = 0.0;
+        while (!converged && !diverged && iterations < cap) {
+            const int n = (int)std::min<long long>(16, cap - iterations);
+            const double *prev = cur;
+            for (int i = 0; i < n; ++i, ++iterations) {
+                double *next = ctx->sf_x[iterations & 1].as<double>();
+                hipLaunchKernelGGL(iterate, row_grid(g_in), dim3(256), 0, ctx->stream, ctx->sf_in_ptr.as<int>(), ctx->sf_in_src.as<int>(), (int)K,
+                                   nnz, ctx->sf_q.as<double>(), ctx->sf_e.as<double>(), cur, next);
+                prev = cur;
+                cur = next;
+            }
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(mc::sf_convergence_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, prev, cur, (int)K, ctx->sf_conv.as<double>());
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->sf_conv_host, ctx->sf_conv.p, 2 * S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            converged = true;
+            worst_ratio = -1.0;
+            for (size_t s = 0; s < S; ++s) {
+                const double dx = ctx->sf_conv_host[2 * s], xm = ctx->sf_conv_host[2 * s + 1];
+                if (!(dx <= 1e-14 * xm)) converged = false;
+                const bool finite = dx == dx && xm < __builtin_huge_val();  // (NaN or infinite rates: no later iteration repairs them)
+                const double ratio = (finite && xm > 0) ? dx / xm : __builtin_huge_val();
+                if (dx != 0 && ratio > worst_ratio) { worst_ratio = ratio; worst = (int)s; }
+                diverged |= !finite;
+            }
+        }
+        ctx->last_source_iterations = iterations;
+        if (!converged) {
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+            ctx->timed = true; ctx->chunks_timed = 0;
+            if (diverged)
+                return fail(ctx, TARDIS_MC_ERR_STATE, "source function: the level solve produced NaN or infinite rates in shell %d after %d iterations "
+                            "(estimators or transition probabilities not finite, or internal jumps that sum to more than one)", worst, iterations);
+            return fail(ctx, TARDIS_MC_ERR_STATE, "source function: the level solve has not converged after %d iterations (option source_max_iterations); "
+                        "worst shell %d with max|dx| / max|x| = %.3g", iterations, worst, worst_ratio);
+        }
+        c_level = cur;
+    } else
+        ctx->last_source_iterations = 0;
+    const unsigned lx = (unsigned)std::min<size_t>((L + 255) / 256, 1024);
+    hipLaunchKernelGGL(mc::sf_close_kernel, dim3(lx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->sf_emit_row.as<int>(), ctx->sf_emit_level.as<int>(),
+                       (long long)L, (long long)T, (int)K, ctx->prob_t.as<double>(), c_level, wavelength_cm ? ctx->sf_wave.as<double>() : nullptr,
+                       ctx->nu_line.as<double>(), ctx->sf_exp_tau.as<double>(), est + lay.jblue, d_nj, time_of_simulation, 4 * pi,
+                       ctx->sf_att.as<double>(), ctx->sf_jred.as<double>(), ctx->sf_jblue.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    ctx->timed = true;
+    ctx->chunks_timed = 0;
+    if (att_S_ul) HIP_TRY(ctx, hipMemcpyAsync(att_S_ul, ctx->sf_att.p, S * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (Jred_lu) HIP_TRY(ctx, hipMemcpyAsync(Jred_lu, ctx->sf_jred.p, S * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (Jblue_lu) HIP_TRY(ctx, hipMemcpyAsync(Jblue_lu, ctx->sf_jblue.p, S * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (e_dot_u) {  // [S][levels] -> level-major, as the reference returns it
+        HIP_TRY(ctx, ctx->staging.ensure(S * K * sizeof(double)));
+        HIP_TRY(ctx, launch_transpose(ctx->stream, c_level, ctx->staging.as<double>(), (long long)S, (long long)K));
+        HIP_TRY(ctx, hipMemcpyAsync(e_dot_u, ctx->staging.p, S * K * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->sf_valid = true;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_last_source_iterations(TardisMcContext *ctx) { return ctx ? ctx->last_source_iterations : -1; }
 
 /* ---- multi-GPU -------------------------------------------------------------------------------------- */
 int tardis_mc_comm_get_unique_id(uint8_t out_id[TARDIS_MC_UNIQUE_ID_BYTES])
@@ -3221,6 +3478,7 @@ int tardis_mc_allreduce_estimators(TardisMcContext *ctx)
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "no estimators allocated");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->sf_valid = false;
     int rc = reduce_estimator_copies(ctx);
     if (rc) return rc;
     if (!ctx->comm) {

@@ -38,6 +38,7 @@ class Engine:
         self._h = h
         self._keep = {}
         self.n_packets = self.n_shells = self.n_lines = self.n_grid = 0
+        self.n_levels = 0  # macro-atom levels (blocks) of the resident opacity tables
         self._vpk_log = False
         self._n_v = 0
         self.packets_generation = 0  # bumped whenever the resident packets are replaced (lazy host views check it)
@@ -100,6 +101,7 @@ class Engine:
         self.resident_opacity = None  # (a failed upload leaves the tables undefined)
         self._check(self._L.tardis_mc_set_opacity(self._h, m.ref()), "set_opacity")
         self.n_lines, self.n_shells = int(m.struct.n_lines), int(m.struct.n_shells)
+        self.n_levels = max(0, int(m.struct.n_macro_block_edges) - 1)
         self.resident_opacity = opacity_state
 
     def set_config(self, montecarlo_configuration, spectrum_frequency_grid, number_of_vpackets=None, sigma_thomson=None):
@@ -259,6 +261,7 @@ class Engine:
         finally:
             self.set_option("track_full", prev_full)
         self.n_packets, self.n_shells, self.n_lines, self.n_grid = P, S, L, int(mc.struct.n_spectrum_grid)
+        self.n_levels = max(0, int(mo.struct.n_macro_block_edges) - 1)
         self._n_v, self._vpk_log = n_v, log
         self._check(rc, "run", int(res.struct.first_error_packet))
         res.full_trackers = self.get_event_log() if track_full else None
@@ -337,6 +340,49 @@ class Engine:
         self._check(self._L.tardis_mc_formal_integral(self._h, float(inner_temperature), freqs.ctypes.data, freqs.size, att.ctypes.data,
                                                       jred.ctypes.data, jblue.ctypes.data, int(n_impact_parameters), lum.ctypes.data,
                                                       inten.ctypes.data if inten is not None else None), "formal_integral")
+        return lum, inten
+
+    def source_function(self, time_of_simulation: float, volume, wavelength_cm=None, want_arrays: bool = True):
+        """make_source_function (spectrum/formal_integral/source_function.py) on the resident estimators and tables
+        (`tardis_mc_source_function`): after propagate() and, multi-GPU, allreduce_estimators().  Leaves att_S_ul / Jred_lu / Jblue_lu in
+        HBM for formal_integral_resident().  Returns {"att_S_ul", "Jred_lu", "Jblue_lu": [n_shells * n_lines] shell-major, "e_dot_u":
+        [levels, n_shells]}, or None with ``want_arrays=False`` (nothing is downloaded)."""
+        volume = np.ascontiguousarray(volume, dtype=np.float64)
+        if volume.shape != (self.n_shells,):
+            raise ValueError("volume must have one entry per shell")
+        wave = None
+        if wavelength_cm is not None:
+            wave = np.ascontiguousarray(wavelength_cm, dtype=np.float64)
+            if wave.shape != (self.n_lines,):
+                raise ValueError("wavelength_cm must have one entry per line")
+        out = None
+        if want_arrays:
+            n = self.n_shells * self.n_lines
+            levels = self.n_levels
+            out = {"att_S_ul": np.empty(n), "Jred_lu": np.empty(n), "Jblue_lu": np.empty(n),
+                   "e_dot_u": np.empty((levels, self.n_shells)) if levels > 0 else None}
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        self._check(self._L.tardis_mc_source_function(
+            self._h, float(time_of_simulation), volume.ctypes.data, ptr(wave),
+            *((ptr(out["att_S_ul"]), ptr(out["Jred_lu"]), ptr(out["Jblue_lu"]), ptr(out["e_dot_u"])) if out else (None,) * 4)),
+            "source_function")
+        return out
+
+    def last_source_iterations(self) -> int:
+        """Fixed-point iterations of the last source_function() solve: 0 for downbranch, -1 before the first call."""
+        return int(self._L.tardis_mc_last_source_iterations(self._h))
+
+    def formal_integral_resident(self, inner_temperature: float, frequencies, n_impact_parameters: int = 1000,
+                                 want_intensities: bool = False):
+        """formal_integral() on the arrays source_function() left in HBM (`tardis_mc_formal_integral_resident`): returns
+        (luminosity_densities, intensities_nu_p or None)."""
+        freqs = np.ascontiguousarray(frequencies, dtype=np.float64).ravel()
+        lum = np.empty(freqs.size)
+        inten = np.empty((freqs.size, int(n_impact_parameters))) if want_intensities else None
+        self._check(self._L.tardis_mc_formal_integral_resident(self._h, float(inner_temperature), freqs.ctypes.data, freqs.size,
+                                                               int(n_impact_parameters), lum.ctypes.data,
+                                                               inten.ctypes.data if inten is not None else None),
+                    "formal_integral_resident")
         return lum, inten
 
     # -- multi-GPU

@@ -42,6 +42,17 @@ class FormalIntegratorHIP:
         return eng.formal_integral(inner_temperature, frequencies, att_S_ul, mean_intensity_red_lu, mean_intensity_blue_lu,
                                    n_impact_parameters, want_intensities=True)
 
+    def integrated_spectrum(self, inner_temperature, frequencies, time_of_simulation, volume, n_impact_parameters=None):
+        """The integrated spectrum straight from a run's estimators: the source function (make_source_function) and the formal
+        integral, both on the device, with no [n_shells * n_lines] array crossing the bus.  Needs the engine that ran the
+        propagation passed to the constructor (it holds the estimators).  Returns luminosity_densities [len(frequencies)]."""
+        if self._engine is None or self._owns:
+            raise RuntimeError("integrated_spectrum needs the engine that holds the run's estimators: pass engine=... to "
+                               "FormalIntegratorHIP (after its propagate and, multi-GPU, allreduce_estimators)")
+        n = self.n_impact_parameters if n_impact_parameters is None else int(n_impact_parameters)
+        self._engine.source_function(time_of_simulation, volume, want_arrays=False)
+        return self._engine.formal_integral_resident(inner_temperature, frequencies, n)[0]
+
     def close(self):
         if self._owns and self._engine is not None:
             self._engine.close()

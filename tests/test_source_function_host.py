@@ -1,0 +1,85 @@
+"""Source function of the formal integral (tardis_mc_source_function): what can be checked without a GPU -- the library and
+the Python wrapper carry the new entry points, the header documents the new option, and the fixed-point iteration the device
+runs agrees with a dense solve on the synthetic macro-atom tables (tests/source_function_ref.py)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import source_function_ref as ref  # noqa: E402
+from tardis_amd import _lib, synthetic  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("tardis_mc_source_function", "tardis_mc_formal_integral_resident", "tardis_mc_last_source_iterations")
+
+
+def test_library_exports_the_new_symbols():
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    L = _lib.lib()
+    for name in NEW_SYMBOLS:
+        assert name in _lib.SYMBOLS, name
+        assert hasattr(L, name), name
+
+
+def test_engine_has_the_new_methods():
+    from tardis_amd.engine import Engine
+    from tardis_amd.formal_integral import FormalIntegratorHIP
+    for name in ("source_function", "formal_integral_resident", "last_source_iterations"):
+        assert callable(getattr(Engine, name, None)), name
+    assert callable(getattr(FormalIntegratorHIP, "integrated_spectrum", None))
+
+
+def test_integrated_spectrum_needs_an_engine_with_estimators():
+    from tardis_amd.formal_integral import FormalIntegratorHIP
+    prob = synthetic.make_problem(n_packets=4, n_lines=40, n_shells=3)
+    fi = FormalIntegratorHIP(prob.geometry, prob.time_explosion, prob.opacity_state)
+    with pytest.raises(RuntimeError, match="engine"):
+        fi.integrated_spectrum(1e4, np.linspace(1e14, 2e14, 4), 1.0, prob.geometry.volume)
+
+
+def test_header_documents_the_option_and_the_symbols():
+    header = open(os.path.join(ROOT, "include", "tardis_mc.h")).read()
+    assert '"source_max_iterations"' in header
+    for name in NEW_SYMBOLS:
+        assert name + "(" in header, name
+
+
+@pytest.mark.parametrize("level_sizes", ["uniform", "heavy"])
+def test_fixed_point_agrees_with_dense_solve(level_sizes):
+    """x <- e + Q^T x against numpy.linalg.solve of (I - Q)^T on the 3e3-line tables, every shell, with a random positive
+    right-hand side.  Bound 1e-12 of the solution's max norm: the stopping rule leaves max|dx| <= 1e-14 max|x| and the error
+    is that times rho / (1 - rho) for a contraction rate rho; 2.7e-14 was measured between the two solvers on these tables,
+    the factor of 40 is room for another summation order."""
+    prob = synthetic.make_problem(seed=3, n_packets=1, n_shells=20, n_lines=3000, line_interaction_type="macroatom",
+                                  level_sizes=level_sizes)
+    op = prob.opacity_state
+    n_levels = len(op.macro_block_edge_index) - 1
+    rng = np.random.default_rng(11)
+    for s in range(20):
+        Q = ref.jump_matrix(op, s)
+        assert Q.shape == (n_levels, n_levels)
+        e = rng.random(n_levels)
+        dense = np.linalg.solve((np.eye(n_levels) - Q.toarray()).T, e)
+        x, it = ref.fixed_point(Q, e)
+        assert 1 < it < 2000
+        assert np.abs(x - dense).max() <= 1e-12 * np.abs(dense).max()
+
+
+def test_restatement_solvers_agree_end_to_end():
+    """make_source_function with the dense and the fixed-point solver on made-up estimators; and downbranch is C = e_dot_u."""
+    prob = synthetic.make_problem(seed=5, n_packets=1, n_shells=20, n_lines=3000, line_interaction_type="macroatom")
+    op, geo = prob.opacity_state, prob.geometry
+    rng = np.random.default_rng(2)
+    jb, ed = rng.random((3000, 20)) * 1e-8, rng.random((3000, 20)) * 1e-6
+    a = ref.make_source_function(op, jb, ed, 1.3e-4, geo.volume, prob.time_explosion, solver="dense")
+    b = ref.make_source_function(op, jb, ed, 1.3e-4, geo.volume, prob.time_explosion, solver="fixed_point")
+    for key in ("att_S_ul", "Jred_lu", "Jblue_lu", "e_dot_u"):
+        assert np.abs(a[key] - b[key]).max() <= 1e-12 * np.abs(a[key]).max(), key
+    assert np.array_equal(a["Jblue_lu"], b["Jblue_lu"])
+    c = ref.make_source_function(op, jb, ed, 1.3e-4, geo.volume, prob.time_explosion, solver="none")
+    assert (c["e_dot_u"] <= a["e_dot_u"] * (1 + 1e-12)).all()  # (the jumps only add to a level's rate)
+    assert a["att_S_ul"].shape == (20 * 3000,)
