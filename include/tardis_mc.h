@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define TARDIS_MC_ABI_VERSION 2  /* 2 (round 6): + tardis_mc_comm_check, tardis_mc_stream_results, tardis_mc_streamed_packets, tardis_mc_last_compactions, microbench 15 */
+#define TARDIS_MC_ABI_VERSION 2  /* 2 (round 6): + tardis_mc_comm_check, tardis_mc_stream_results, tardis_mc_streamed_packets, tardis_mc_last_compactions, microbench 15;
+                                    * additive since: tardis_mc_formal_integral_interpolated, tardis_mc_interpolated_source */
 
 enum {
     TARDIS_MC_OK = 0,
@@ -355,6 +356,39 @@ int tardis_mc_last_source_iterations(TardisMcContext *ctx);
  * TARDIS_MC_ERR_STATE when no valid resident source function exists. */
 int tardis_mc_formal_integral_resident(TardisMcContext *ctx, double inner_temperature, const double *frequencies, int64_t n_frequencies,
                                        int64_t n_impact_parameters, double *luminosity_densities, double *intensities_nu_p);
+
+/* ---- interpolate_shells: the formal integral on a refined (or coarsened) shell grid -----------------------------------------
+ * What FormalIntegralSolver / interpolate_integrator_quantities (tardis/spectrum/formal_integral/) do before they integrate when the
+ * configuration sets interpolate_shells = n > 0, here on the resident source function and without leaving the device.  With S the
+ * resident shells and S' = n - 1:
+ *   x[s]  = (r_inner[s] + r_outer[s]) / 2.0                                              the nodes
+ *   r     = numpy.linspace(r_inner[0], r_outer[S-1], n):  step = (stop - start) / (n - 1), r[i] = i * step + start, r[n-1] = stop
+ *   r_inner_i = r[:-1], r_outer_i = r[1:], xn[j] = (r_inner_i[j] + r_outer_i[j]) / 2.0    the new shells and their midpoints
+ *   att_S_ul, Jred_lu, Jblue_lu, e_dot_u -- linear with extrapolation (scipy interp1d, fill_value="extrapolate"), clipped at zero:
+ *       hi = clip(searchsorted(x, xn[j], side="left"), 1, S-1), lo = hi - 1
+ *       slope = (y[hi] - y[lo]) / (x[hi] - x[lo]);  v = slope * (xn[j] - x[lo]) + y[lo];  result max(v, 0.0)
+ *     in exactly this order -- one division, one product, one sum, no fused multiply-add -- so the tables are bit for bit scipy's
+ *     (the clip matters inside the grid too: with y[hi] = 0 and xn = x[hi], v can round to a tiny negative value);
+ *   tau_sobolev, electron_density -- the nearest node, ties to the lower shell ("constant within a shell, as in the MC simulation"):
+ *       near = searchsorted((x[1:] + x[:-1]) / 2.0, xn[j], side="left");  result y[near]
+ * and the formal integral runs unchanged on r_inner_i / r_outer_i, the nearest-shell tau and n_e and the three interpolated arrays,
+ * with impact parameters up to r_outer_i[S'-1] = r_outer[S-1].  The maps are computed on the host in double, the tables by one
+ * streaming kernel (csrc/formal_interpolate.hpp) into scratch memory that the call releases: nothing resident changes, the run's
+ * geometry, opacity, estimators and source function stay valid.
+ *
+ * tardis_mc_formal_integral_interpolated: tardis_mc_formal_integral_resident on that grid; same outputs, same
+ * TARDIS_MC_ERR_STATE without a valid resident source function, counters[0] and tardis_mc_last_propagate_ms as there (the device
+ * time includes the interpolation kernel).  TARDIS_MC_ERR_INVALID_ARGUMENT for interpolate_shells < 2 or > 65536 (a number of grid
+ * POINTS) and for a model of one shell (two nodes are needed; scipy refuses it too).
+ * tardis_mc_interpolated_source: the same tables, downloaded -- r_inner_i, r_outer_i, electron_density_i [S'], tau_sobolev_i (the
+ * gathered rows of the resident optical depths), att_S_ul_i, Jred_lu_i, Jblue_lu_i [S' * n_lines] flat shell-major, e_dot_u_i
+ * [levels * S'] level-major; any pointer may be NULL.  Same errors. */
+int tardis_mc_formal_integral_interpolated(TardisMcContext *ctx, int64_t interpolate_shells, double inner_temperature,
+                                           const double *frequencies, int64_t n_frequencies, int64_t n_impact_parameters,
+                                           double *luminosity_densities, double *intensities_nu_p);
+int tardis_mc_interpolated_source(TardisMcContext *ctx, int64_t interpolate_shells, double *r_inner_i, double *r_outer_i,
+                                  double *electron_density_i, double *tau_sobolev_i, double *att_S_ul_i, double *Jred_lu_i,
+                                  double *Jblue_lu_i, double *e_dot_u_i);
 
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the

@@ -51,6 +51,8 @@ SYMBOLS = {
     "tardis_mc_source_function": (_i, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tardis_mc_last_source_iterations": (_i, [_vp]),
     "tardis_mc_formal_integral_resident": (_i, [_vp, C.c_double, _vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "tardis_mc_formal_integral_interpolated": (_i, [_vp, C.c_int64, C.c_double, _vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "tardis_mc_interpolated_source": (_i, [_vp, C.c_int64] + [_vp] * 8),
     "tardis_mc_get_event_log": (_i, [_vp, _vp]),
     "tardis_mc_stream_results": (_i, [_vp, _vp]),
     "tardis_mc_streamed_packets": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -29,6 +29,7 @@
 #include "propagate_wave.hpp"
 #include "packet_source.hpp"
 #include "formal_integral.hpp"
+#include "formal_interpolate.hpp"
 #include "source_function.hpp"
 #include "tau_prefix.hpp"
 #include "propagate_plan.hpp"
@@ -293,6 +294,7 @@ struct TardisMcContext {
     DevBuf sf_exp_tau, sf_e, sf_x[2], sf_q, sf_shell, sf_conv, sf_wave, sf_att, sf_jred, sf_jblue;
     bool sf_exp_valid = false;
     bool sf_valid = false;                     // the resident att_S_ul / Jred_lu / Jblue_lu belong to the resident estimators and tables
+    const double *sf_c_level = nullptr;        // with sf_valid: the level rates [S][levels] of that source function (sf_e, or the sf_x the solve ended in)
     double *sf_conv_host = nullptr;            // pinned: {max |dx|, max |x|} per shell
     long long source_max_iterations = 20000;   // option: bound on the iterations of a solve
     int last_source_iterations = -1;
@@ -3165,53 +3167,71 @@ static int ensure_exp_tau(TardisMcContext *ctx)
     return TARDIS_MC_OK;
 }
 
-// the formal integral on the caller's att_S_ul / Jred_lu / Jblue_lu (host), or -- `resident` -- on the copies tardis_mc_source_function left in HBM
-static int formal_integral_impl(TardisMcContext *ctx, bool resident, double inner_temperature, const double *frequencies, int64_t n_frequencies,
-                                const double *att_S_ul, const double *Jred_lu, const double *Jblue_lu, int64_t n_impact_parameters,
-                                double *luminosity_densities, double *intensities_nu_p)
+// What a formal integral runs on -- the geometry, the electron densities and the four [n_shells][n_lines] tables, all on the device: the context's own
+// (host-fed and resident entry points) or the interpolated ones of a call (formal_interpolate.hpp).  The host-fed entry point has no tables yet
+// (exp_tau == nullptr): its three host arrays are uploaded into the call's scratch and exp(-tau) of the resident optical depths is tabulated beside them.
+struct FormalIntegralInput {
+    size_t n_shells = 0;
+    const double *r_inner = nullptr, *r_outer = nullptr, *n_e = nullptr;                        // [n_shells]
+    const double *exp_tau = nullptr, *att = nullptr, *jred = nullptr, *jblue = nullptr;         // [n_shells][n_lines]
+    const double *host_att = nullptr, *host_jred = nullptr, *host_jblue = nullptr;              // (exp_tau == nullptr)
+    bool timer_started = false;  // ev_start is recorded already, in front of kernels of the caller that belong to the call's device time
+};
+
+// state and arguments of the three formal integral entry points (`resident`: the call reads the resident source function)
+static int formal_integral_check(TardisMcContext *ctx, bool resident, const double *frequencies, bool have_tables, const double *luminosity_densities,
+                                 int64_t n_frequencies, int64_t n_impact_parameters)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_geometry || !ctx->have_opacity)
         return fail(ctx, TARDIS_MC_ERR_STATE, "formal integral needs set_geometry and set_opacity");
     if (resident && !ctx->sf_valid)
         return fail(ctx, TARDIS_MC_ERR_STATE, "no resident source function: tardis_mc_source_function must follow the last propagate / all-reduce");
-    if (!frequencies || (!resident && (!att_S_ul || !Jred_lu || !Jblue_lu)) || !luminosity_densities || n_frequencies < 0 || n_impact_parameters < 2 ||
+    if (!frequencies || !have_tables || !luminosity_densities || n_frequencies < 0 || n_impact_parameters < 2 ||
         n_frequencies > (1LL << 30) || n_impact_parameters > 65535)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid formal integral arguments");
+    return TARDIS_MC_OK;
+}
+
+// the formal integral on `in` (checked by formal_integral_check)
+static int formal_integral_impl(TardisMcContext *ctx, const FormalIntegralInput &in, double inner_temperature, const double *frequencies,
+                                int64_t n_frequencies, int64_t n_impact_parameters, double *luminosity_densities, double *intensities_nu_p)
+{
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, n_nu = (size_t)n_frequencies, N = (size_t)n_impact_parameters;
+    const size_t S = in.n_shells, L = (size_t)ctx->n_lines, n_nu = (size_t)n_frequencies, N = (size_t)n_impact_parameters;
     if (n_nu == 0) return TARDIS_MC_OK;
-    DevBuf work;  // [exp_tau | att | jred | jblue | freqs | z | I | Lum] doubles, then sid / n_int ints (resident: no tables in front)
-    const size_t n_tab = resident ? 0 : S * L;
+    const bool host_fed = in.exp_tau == nullptr;
+    DevBuf work;  // [exp_tau | att | jred | jblue | freqs | z | I | Lum] doubles, then sid / n_int ints (tables on the device already: none in front)
+    const size_t n_tab = host_fed ? S * L : 0;
     const size_t n_d = 4 * n_tab + n_nu + N * 2 * S + n_nu * N + n_nu;
     HIP_TRY(ctx, work.ensure(n_d * sizeof(double) + (N * 2 * S + N) * sizeof(int)));
     double *d_exp = work.as<double>(), *d_att = d_exp + n_tab, *d_jred = d_att + n_tab, *d_jblue = d_jred + n_tab,
            *d_freq = d_jblue + n_tab, *d_z = d_freq + n_nu, *d_I = d_z + N * 2 * S, *d_lum = d_I + n_nu * N;
     int *d_sid = reinterpret_cast<int *>(d_lum + n_nu), *d_nint = d_sid + N * 2 * S;
-    if (!resident) {
-        HIP_TRY(ctx, hipMemcpyAsync(d_att, att_S_ul, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_jred, Jred_lu, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_jblue, Jblue_lu, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (host_fed) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_att, in.host_att, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_jred, in.host_jred, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_jblue, in.host_jblue, S * L * 8, hipMemcpyHostToDevice, ctx->stream));
     }
     HIP_TRY(ctx, hipMemcpyAsync(d_freq, frequencies, n_nu * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    if (resident) {
-        int rc_exp = ensure_exp_tau(ctx);  // (the source function has computed it: set_opacity, which drops the table, drops sf_valid too)
-        if (rc_exp) return rc_exp;
-        d_exp = ctx->sf_exp_tau.as<double>(); d_att = ctx->sf_att.as<double>(); d_jred = ctx->sf_jred.as<double>(); d_jblue = ctx->sf_jblue.as<double>();
-    } else if (S * L > 0)
-        hipLaunchKernelGGL(mc::fi_exp_tau_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->tau_t.as<double>(), (long long)(S * L), d_exp);
+    if (!in.timer_started) HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    const double *t_exp_tau = in.exp_tau, *t_att = in.att, *t_jred = in.jred, *t_jblue = in.jblue;
+    if (host_fed) {
+        if (S * L > 0)
+            hipLaunchKernelGGL(mc::fi_exp_tau_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->tau_t.as<double>(), (long long)(S * L), d_exp);
+        t_exp_tau = d_exp; t_att = d_att; t_jred = d_jred; t_jblue = d_jblue;
+    }
     hipLaunchKernelGGL(mc::fi_intersections_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, ctx->stream, (int)S,
-                       ctx->r_inner.as<double>(), ctx->r_outer.as<double>(), ctx->t_exp, (int)N, d_z, d_sid, d_nint);
+                       in.r_inner, in.r_outer, ctx->t_exp, (int)N, d_z, d_sid, d_nint);
     std::vector<double> r_last(1);
-    HIP_TRY(ctx, hipMemcpyAsync(r_last.data(), ctx->r_outer.as<double>() + (S - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(r_last.data(), in.r_outer + (S - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     mc::FormalIntegralArgs a{};
     a.n_shells = (int)S; a.n_lines = (int)L; a.n_nu = (int)n_nu; a.N = (int)N;
     a.t_exp = ctx->t_exp; a.inner_temperature = inner_temperature; a.radius_max = r_last[0];
     a.sigma_thomson = 6.652458734e-25;  // SIGMA_THOMSON, transport/montecarlo/configuration/constants.py:3 (astropy const13)
-    a.r_inner = ctx->r_inner.as<double>(); a.nu_line = ctx->nu_line.as<double>(); a.n_e = ctx->n_e.as<double>();
-    a.exp_tau = d_exp; a.att_S_ul = d_att; a.Jred_lu = d_jred; a.Jblue_lu = d_jblue; a.frequencies = d_freq;
+    a.r_inner = in.r_inner; a.nu_line = ctx->nu_line.as<double>(); a.n_e = in.n_e;
+    a.exp_tau = t_exp_tau; a.att_S_ul = t_att; a.Jred_lu = t_jred; a.Jblue_lu = t_jblue; a.frequencies = d_freq;
     a.z = d_z; a.sid = d_sid; a.n_int = d_nint; a.intensities_nu_p = d_I;
     HIP_TRY(ctx, ctx->counters.ensure(TARDIS_MC_N_COUNTERS * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, TARDIS_MC_N_COUNTERS * sizeof(unsigned long long), ctx->stream));
@@ -3231,19 +3251,168 @@ static int formal_integral_impl(TardisMcContext *ctx, bool resident, double inne
     return TARDIS_MC_OK;
 }
 
+// the context's own geometry and electron densities (tables: the caller's)
+static FormalIntegralInput resident_formal_input(TardisMcContext *ctx)
+{
+    FormalIntegralInput in;
+    in.n_shells = (size_t)ctx->n_shells;
+    in.r_inner = ctx->r_inner.as<double>(); in.r_outer = ctx->r_outer.as<double>(); in.n_e = ctx->n_e.as<double>();
+    return in;
+}
+
 int tardis_mc_formal_integral(TardisMcContext *ctx, double inner_temperature, const double *frequencies, int64_t n_frequencies,
                               const double *att_S_ul, const double *Jred_lu, const double *Jblue_lu, int64_t n_impact_parameters,
                               double *luminosity_densities, double *intensities_nu_p)
 {
-    return formal_integral_impl(ctx, false, inner_temperature, frequencies, n_frequencies, att_S_ul, Jred_lu, Jblue_lu, n_impact_parameters,
-                                luminosity_densities, intensities_nu_p);
+    int rc = formal_integral_check(ctx, false, frequencies, att_S_ul && Jred_lu && Jblue_lu, luminosity_densities, n_frequencies, n_impact_parameters);
+    if (rc) return rc;
+    FormalIntegralInput in = resident_formal_input(ctx);
+    in.host_att = att_S_ul; in.host_jred = Jred_lu; in.host_jblue = Jblue_lu;
+    return formal_integral_impl(ctx, in, inner_temperature, frequencies, n_frequencies, n_impact_parameters, luminosity_densities, intensities_nu_p);
 }
 
 int tardis_mc_formal_integral_resident(TardisMcContext *ctx, double inner_temperature, const double *frequencies, int64_t n_frequencies,
                                        int64_t n_impact_parameters, double *luminosity_densities, double *intensities_nu_p)
 {
-    return formal_integral_impl(ctx, true, inner_temperature, frequencies, n_frequencies, nullptr, nullptr, nullptr, n_impact_parameters,
-                                luminosity_densities, intensities_nu_p);
+    int rc = formal_integral_check(ctx, true, frequencies, true, luminosity_densities, n_frequencies, n_impact_parameters);
+    if (rc) return rc;
+    // (the source function has computed exp(-tau): set_opacity, which drops the table, drops sf_valid too)
+    FormalIntegralInput in = resident_formal_input(ctx);
+    in.exp_tau = ctx->sf_exp_tau.as<double>(); in.att = ctx->sf_att.as<double>(); in.jred = ctx->sf_jred.as<double>(); in.jblue = ctx->sf_jblue.as<double>();
+    return formal_integral_impl(ctx, in, inner_temperature, frequencies, n_frequencies, n_impact_parameters, luminosity_densities, intensities_nu_p);
+}
+
+/* ---- interpolate_shells: the resident source function on the integrator's grid (formal_interpolate.hpp) ------------------- */
+// The scratch of one call: the grid and the maps on the host (they back the uploads until the call has synchronised) and on the device, the four
+// interpolated tables and, where asked for, the interpolated level rates.
+struct InterpolatedSource {
+    size_t n_shells = 0, table_stride = 0;  // (a table starts on a 16-byte boundary: the stride is even)
+    mc::FiInterpolationGrid grid;
+    std::vector<double> n_e;
+    DevBuf shells, tables, levels;
+    const double *d_dx = nullptr, *d_dxn = nullptr, *d_r_inner = nullptr, *d_r_outer = nullptr, *d_n_e = nullptr;
+    const int *d_lo = nullptr, *d_hi = nullptr, *d_near = nullptr;
+    double *table(int k) const { return tables.as<double>() + (size_t)k * table_stride; }  // 0 att, 1 jred, 2 jblue, 3 exp_tau
+    void release() { shells.release(); tables.release(); levels.release(); }
+};
+
+static int interpolate_check(TardisMcContext *ctx, int64_t interpolate_shells)
+{
+    if (interpolate_shells < 2 || interpolate_shells > 65536)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "interpolate_shells must be a number of grid points from 2 to 65536");
+    if (ctx->n_shells < 2)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "interpolate_shells needs a model of two shells or more (linear interpolation has two nodes)");
+    return TARDIS_MC_OK;
+}
+
+// Builds the interpolated tables of `interpolate_shells` grid points from the resident source function: records ev_start and launches the kernel(s) on
+// the context's stream, does not wait for them.  The caller releases `out`, whatever is returned.
+static int interpolate_source(TardisMcContext *ctx, int64_t interpolate_shells, bool want_levels, InterpolatedSource &out)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, Si = (size_t)interpolate_shells - 1, K = (size_t)ctx->n_levels;
+    std::vector<double> r_in(S), r_out(S), n_e(S);
+    HIP_TRY(ctx, hipMemcpyAsync(r_in.data(), ctx->r_inner.p, S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(r_out.data(), ctx->r_outer.p, S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(n_e.data(), ctx->n_e.p, S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    out.n_shells = Si;
+    out.grid = mc::fi_interpolation_grid(r_in, r_out, (int)interpolate_shells);
+    out.n_e.resize(Si);
+    for (size_t j = 0; j < Si; ++j) out.n_e[j] = n_e[(size_t)out.grid.near[j]];
+    out.table_stride = (Si * L + 1) & ~(size_t)1;
+    HIP_TRY(ctx, out.shells.ensure(5 * Si * sizeof(double) + 3 * Si * sizeof(int)));
+    HIP_TRY(ctx, out.tables.ensure(4 * out.table_stride * sizeof(double)));
+    double *d = out.shells.as<double>();
+    int *di = reinterpret_cast<int *>(d + 5 * Si);
+    out.d_dx = d; out.d_dxn = d + Si; out.d_r_inner = d + 2 * Si; out.d_r_outer = d + 3 * Si; out.d_n_e = d + 4 * Si;
+    out.d_lo = di; out.d_hi = di + Si; out.d_near = di + 2 * Si;
+    const mc::FiInterpolationGrid &g = out.grid;
+    const double *host_d[5] = {g.dx.data(), g.dxn.data(), g.r_inner.data(), g.r_outer.data(), out.n_e.data()};
+    const int *host_i[3] = {g.lo.data(), g.hi.data(), g.near.data()};
+    for (int k = 0; k < 5; ++k) HIP_TRY(ctx, hipMemcpyAsync(d + (size_t)k * Si, host_d[k], Si * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (int k = 0; k < 3; ++k) HIP_TRY(ctx, hipMemcpyAsync(di + (size_t)k * Si, host_i[k], Si * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    mc::FiInterpolateArgs a{};
+    a.L = (long long)L;
+    a.lo = out.d_lo; a.hi = out.d_hi; a.near = out.d_near; a.dx = out.d_dx; a.dxn = out.d_dxn;
+    a.att = ctx->sf_att.as<double>(); a.jred = ctx->sf_jred.as<double>(); a.jblue = ctx->sf_jblue.as<double>(); a.exp_tau = ctx->sf_exp_tau.as<double>();
+    a.att_i = out.table(0); a.jred_i = out.table(1); a.jblue_i = out.table(2); a.exp_tau_i = out.table(3);
+    // about 2048 blocks in all, each striding over the pairs of lines of one output row
+    const size_t row_blocks = std::max<size_t>(1, std::min<size_t>((L / 2 + 256) / 256, (2048 + Si - 1) / Si));
+    hipLaunchKernelGGL(mc::fi_interpolate_kernel, dim3((unsigned)row_blocks, (unsigned)Si), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    if (want_levels && K > 0) {
+        HIP_TRY(ctx, out.levels.ensure(Si * K * sizeof(double)));
+        hipLaunchKernelGGL(mc::fi_interpolate_levels_kernel, dim3((unsigned)std::min<size_t>((K + 255) / 256, 64), (unsigned)Si), dim3(256), 0, ctx->stream,
+                           out.d_lo, out.d_hi, out.d_dx, out.d_dxn, (long long)K, ctx->sf_c_level, out.levels.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_formal_integral_interpolated(TardisMcContext *ctx, int64_t interpolate_shells, double inner_temperature, const double *frequencies,
+                                           int64_t n_frequencies, int64_t n_impact_parameters, double *luminosity_densities, double *intensities_nu_p)
+{
+    int rc = formal_integral_check(ctx, true, frequencies, true, luminosity_densities, n_frequencies, n_impact_parameters);
+    if (rc || (rc = interpolate_check(ctx, interpolate_shells))) return rc;
+    if (n_frequencies == 0) return TARDIS_MC_OK;
+    InterpolatedSource src;
+    rc = interpolate_source(ctx, interpolate_shells, false, src);
+    if (!rc) {
+        FormalIntegralInput in;
+        in.n_shells = src.n_shells;
+        in.r_inner = src.d_r_inner; in.r_outer = src.d_r_outer; in.n_e = src.d_n_e;
+        in.att = src.table(0); in.jred = src.table(1); in.jblue = src.table(2); in.exp_tau = src.table(3);
+        in.timer_started = true;
+        rc = formal_integral_impl(ctx, in, inner_temperature, frequencies, n_frequencies, n_impact_parameters, luminosity_densities, intensities_nu_p);
+    }
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (nothing of the call is in flight when its scratch goes)
+    src.release();
+    return rc;
+}
+
+static int download_interpolated_source(TardisMcContext *ctx, const InterpolatedSource &src, double *r_inner_i, double *r_outer_i,
+                                        double *electron_density_i, double *tau_sobolev_i, double *att_S_ul_i, double *Jred_lu_i, double *Jblue_lu_i,
+                                        double *e_dot_u_i)
+{
+    const size_t Si = src.n_shells, L = (size_t)ctx->n_lines, K = (size_t)ctx->n_levels;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    ctx->timed = true;
+    ctx->chunks_timed = 0;
+    if (r_inner_i) memcpy(r_inner_i, src.grid.r_inner.data(), Si * 8);
+    if (r_outer_i) memcpy(r_outer_i, src.grid.r_outer.data(), Si * 8);
+    if (electron_density_i) memcpy(electron_density_i, src.n_e.data(), Si * 8);
+    double *const host[3] = {att_S_ul_i, Jred_lu_i, Jblue_lu_i};
+    for (int k = 0; k < 3; ++k)
+        if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k], src.table(k), Si * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (tau_sobolev_i)  // the rows of the resident optical depths, gathered by the copies themselves
+        for (size_t j = 0; j < Si; ++j)
+            HIP_TRY(ctx, hipMemcpyAsync(tau_sobolev_i + j * L, ctx->tau_t.as<double>() + (size_t)src.grid.near[j] * L, L * 8, hipMemcpyDeviceToHost,
+                                        ctx->stream));
+    if (e_dot_u_i && K > 0) {  // [S'][levels] -> level-major, as tardis_mc_source_function returns e_dot_u
+        HIP_TRY(ctx, ctx->staging.ensure(Si * K * sizeof(double)));
+        HIP_TRY(ctx, launch_transpose(ctx->stream, src.levels.as<double>(), ctx->staging.as<double>(), (long long)Si, (long long)K));
+        HIP_TRY(ctx, hipMemcpyAsync(e_dot_u_i, ctx->staging.p, Si * K * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_interpolated_source(TardisMcContext *ctx, int64_t interpolate_shells, double *r_inner_i, double *r_outer_i, double *electron_density_i,
+                                  double *tau_sobolev_i, double *att_S_ul_i, double *Jred_lu_i, double *Jblue_lu_i, double *e_dot_u_i)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_geometry || !ctx->have_opacity || !ctx->sf_valid)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "no resident source function: tardis_mc_source_function must follow the last propagate / all-reduce");
+    int rc = interpolate_check(ctx, interpolate_shells);
+    if (rc) return rc;
+    InterpolatedSource src;
+    rc = interpolate_source(ctx, interpolate_shells, e_dot_u_i != nullptr, src);
+    if (!rc) rc = download_interpolated_source(ctx, src, r_inner_i, r_outer_i, electron_density_i, tau_sobolev_i, att_S_ul_i, Jred_lu_i, Jblue_lu_i, e_dot_u_i);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    src.release();
+    return rc;
 }
 
 /* ---- the source function of the formal integral from the resident estimators (source_function.hpp) ---------------- */
@@ -3437,6 +3606,7 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
         HIP_TRY(ctx, hipMemcpyAsync(e_dot_u, ctx->staging.p, S * K * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->sf_c_level = c_level;
     ctx->sf_valid = true;
     return TARDIS_MC_OK;
 }

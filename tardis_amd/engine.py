@@ -385,6 +385,39 @@ class Engine:
                     "formal_integral_resident")
         return lum, inten
 
+    def formal_integral_interpolated(self, interpolate_shells: int, inner_temperature: float, frequencies,
+                                     n_impact_parameters: int = 1000, want_intensities: bool = False):
+        """formal_integral_resident() with the reference's ``interpolate_shells`` (`tardis_mc_formal_integral_interpolated`): the
+        arrays source_function() left in HBM are interpolated on the device onto ``interpolate_shells - 1`` equal shells
+        (interpolate_integrator_quantities) and integrated there.  The engine's resident state is left as it was.  Returns
+        (luminosity_densities, intensities_nu_p or None)."""
+        freqs = np.ascontiguousarray(frequencies, dtype=np.float64).ravel()
+        lum = np.empty(freqs.size)
+        inten = np.empty((freqs.size, int(n_impact_parameters))) if want_intensities else None
+        self._check(self._L.tardis_mc_formal_integral_interpolated(self._h, int(interpolate_shells), float(inner_temperature),
+                                                                   freqs.ctypes.data, freqs.size, int(n_impact_parameters),
+                                                                   lum.ctypes.data, inten.ctypes.data if inten is not None else None),
+                    "formal_integral_interpolated")
+        return lum, inten
+
+    def interpolated_source(self, interpolate_shells: int) -> dict:
+        """What formal_integral_interpolated() integrates (`tardis_mc_interpolated_source`), with S' = interpolate_shells - 1:
+        {"r_inner", "r_outer", "electron_density": [S'], "tau_sobolev", "att_S_ul", "Jred_lu", "Jblue_lu": [S' * n_lines]
+        shell-major, "e_dot_u": [levels, S']}."""
+        Si = int(interpolate_shells) - 1
+        if not 1 <= Si < 65536:  # (the library refuses it: nothing to size the arrays by)
+            Si = 0
+        n, levels = Si * self.n_lines, self.n_levels
+        out = {k: np.empty(Si) for k in ("r_inner", "r_outer", "electron_density")}
+        out.update({k: np.empty(n) for k in ("tau_sobolev", "att_S_ul", "Jred_lu", "Jblue_lu")})
+        out["e_dot_u"] = np.empty((levels, Si)) if levels > 0 else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        self._check(self._L.tardis_mc_interpolated_source(
+            self._h, int(interpolate_shells), *(ptr(out[k]) for k in ("r_inner", "r_outer", "electron_density", "tau_sobolev",
+                                                                      "att_S_ul", "Jred_lu", "Jblue_lu", "e_dot_u"))),
+            "interpolated_source")
+        return out
+
     # -- multi-GPU
     @staticmethod
     def comm_unique_id() -> bytes:

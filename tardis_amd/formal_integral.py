@@ -42,15 +42,20 @@ class FormalIntegratorHIP:
         return eng.formal_integral(inner_temperature, frequencies, att_S_ul, mean_intensity_red_lu, mean_intensity_blue_lu,
                                    n_impact_parameters, want_intensities=True)
 
-    def integrated_spectrum(self, inner_temperature, frequencies, time_of_simulation, volume, n_impact_parameters=None):
+    def integrated_spectrum(self, inner_temperature, frequencies, time_of_simulation, volume, n_impact_parameters=None,
+                            interpolate_shells=0):
         """The integrated spectrum straight from a run's estimators: the source function (make_source_function) and the formal
         integral, both on the device, with no [n_shells * n_lines] array crossing the bus.  Needs the engine that ran the
-        propagation passed to the constructor (it holds the estimators).  Returns luminosity_densities [len(frequencies)]."""
+        propagation passed to the constructor (it holds the estimators).  ``interpolate_shells`` > 0: the reference's setting
+        of that name -- the source function is interpolated onto that many grid points, on the device, before the integration
+        (0, None or negative: the model's own shells).  Returns luminosity_densities [len(frequencies)]."""
         if self._engine is None or self._owns:
             raise RuntimeError("integrated_spectrum needs the engine that holds the run's estimators: pass engine=... to "
                                "FormalIntegratorHIP (after its propagate and, multi-GPU, allreduce_estimators)")
         n = self.n_impact_parameters if n_impact_parameters is None else int(n_impact_parameters)
         self._engine.source_function(time_of_simulation, volume, want_arrays=False)
+        if interpolate_shells is not None and int(interpolate_shells) > 0:
+            return self._engine.formal_integral_interpolated(int(interpolate_shells), inner_temperature, frequencies, n)[0]
         return self._engine.formal_integral_resident(inner_temperature, frequencies, n)[0]
 
     def close(self):
