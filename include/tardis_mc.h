@@ -31,7 +31,8 @@ extern "C" {
 #endif
 
 #define TARDIS_MC_ABI_VERSION 2  /* 2 (round 6): + tardis_mc_comm_check, tardis_mc_stream_results, tardis_mc_streamed_packets, tardis_mc_last_compactions, microbench 15;
-                                    * additive since: tardis_mc_formal_integral_interpolated, tardis_mc_interpolated_source */
+                                    * additive since: tardis_mc_formal_integral_interpolated, tardis_mc_interpolated_source,
+                                    * tardis_mc_packet_decomposition, tardis_mc_decomposition_path */
 
 enum {
     TARDIS_MC_OK = 0,
@@ -154,6 +155,25 @@ typedef struct TardisMcEventLog {
     int64_t *event_id, *interaction_type, *status, *shell_id, *after_shell_id, *line_absorb_id, *line_emit_id;
     double *radius, *before_nu, *before_mu, *before_energy, *after_nu, *after_mu, *after_energy;
 } TardisMcEventLog;
+
+/* The emitted spectrum decomposed by last interaction (tardis_mc_packet_decomposition below). */
+typedef struct TardisMcDecomposition {
+    /* in */
+    int64_t n_classes;            /* C, 1 <= C < 2^31 */
+    const int64_t *line_class;    /* [n_lines], every value in [0, C): the caller's grouping of lines (species, ion, ...) */
+    double time_of_simulation;    /* > 0 */
+    double nu_start, nu_end;      /* packet filter on output_nu: nu_start < nu < nu_end (0, inf = all) */
+    /* out, host, any may be NULL.  B = n_spectrum_grid - 1, S = n_shells, L = n_lines */
+    double *emission;             /* [C*B] class-major */
+    double *absorption;           /* [C*B] class-major */
+    double *no_interaction;       /* [B] */
+    double *electron_scatter;     /* [B] */
+    int64_t *shell_packets;       /* [(C+1)*S]: rows 0..C-1 by emit class, row C electron scattering; column li_shell_id */
+    int64_t *line_emit_packets;   /* [L] */
+    int64_t *line_absorb_packets; /* [L] */
+    /* out */
+    int64_t n_selected, n_line, n_electron_scatter, n_no_interaction;
+} TardisMcDecomposition;
 
 typedef struct TardisMcContext TardisMcContext;
 
@@ -305,6 +325,32 @@ int tardis_mc_get_packets(TardisMcContext *ctx, double *initial_radii, double *i
 int tardis_mc_packet_spectrum(TardisMcContext *ctx, double time_of_simulation, double luminosity_nu_start,
                               double luminosity_nu_end, double *emitted_luminosity_hist, double *reabsorbed_luminosity_hist,
                               double *out_emitted_luminosity, double *out_reabsorbed_luminosity);
+
+/* ---- consumer next to the path: the emitted spectrum decomposed by last interaction ------------------------------------------
+ * What SDEC (emission and absorption by species), the last-interaction-velocity histogram (LIV) and LastLineInteraction compute on the
+ * host from the last-interaction tracker, reduced on the device from the seven per-packet arrays resident after a tardis_mc_propagate
+ * with "track_last_interaction" on: output_nu, output_energy, li_interaction_type, li_line_emit_id, li_line_absorb_id, li_before_nu,
+ * li_shell_id.  A packet is SELECTED when output_energy >= 0 (emitted) and nu_start < output_nu < nu_end; its weight is
+ * l = output_energy / time_of_simulation; its kind is li_interaction_type: 2 LINE, 4 ESCATTERING, -1 none (the tracker holds the last
+ * non-boundary interaction: a packet that last scattered on an electron has line ids -1 and is no line packet).  With bin() the bin
+ * of numpy.histogram on the spectrum_frequency_grid of tardis_mc_set_config (left-closed bins, the last one also right-closed, a
+ * value outside [edges[0], edges[B]] in no bin):
+ *   LINE         emission[line_class[li_line_emit_id]][bin(output_nu)] += l;  absorption[line_class[li_line_absorb_id]][bin(li_before_nu)] += l;
+ *                shell_packets[emit class][li_shell_id] += 1;  line_emit_packets[emit id] += 1;  line_absorb_packets[absorb id] += 1
+ *   ESCATTERING  electron_scatter[bin(output_nu)] += l;  shell_packets[C][li_shell_id] += 1
+ *   none         no_interaction[bin(output_nu)] += l
+ * n_selected, n_line, n_electron_scatter, n_no_interaction count the selected packets and the three kinds among them; a packet whose
+ * frequency is outside the grid still counts in every integer output.
+ * The double sums are accumulated with atomics (in LDS per workgroup where the matrices fit 64 KiB, csrc/decomposition_plan.hpp, else
+ * straight in HBM): all addends are non-negative, so two calls agree within (n - 1) 2^-53 relatively in a cell of n addends, and a cell
+ * without addends is exactly 0; the integer outputs agree exactly.  All outputs are additive over packet shards: ranks sum them on the host.
+ * Errors: TARDIS_MC_ERR_STATE when no propagate call has completed, when the last one ran with "track_last_interaction" 0, when a packet of
+ * it failed, when the resident packets were replaced since, or without a spectrum grid; TARDIS_MC_ERR_INVALID_ARGUMENT when d or
+ * line_class is NULL, C < 1, a class is outside [0, C) (checked on the host before anything is indexed with it) or time_of_simulation is
+ * not positive.  Nothing resident changes.  tardis_mc_last_propagate_ms then reports the device time of the call's kernels. */
+int tardis_mc_packet_decomposition(TardisMcContext *ctx, TardisMcDecomposition *d);
+/* Which accumulation path a call with C classes, B bins and S shells takes: 0 privatised (LDS), 1 direct (HBM).  Host only. */
+int tardis_mc_decomposition_path(int64_t n_classes, int64_t n_bins, int64_t n_shells);
 
 /* ---- consumer next to the path: radiation-field update from the resident estimators -------------------
  * MCRadiationFieldPropertiesSolver.solve (transport/montecarlo/estimators/mc_rad_field_solver.py:37-144):

@@ -109,6 +109,17 @@ class TardisMcEventLog(C.Structure):
     )
 
 
+class TardisMcDecomposition(C.Structure):
+    """The emitted spectrum decomposed by last interaction (tardis_mc_packet_decomposition): inputs, host output pointers, counts."""
+    _fields_ = (
+        [("n_classes", C.c_int64), ("line_class", _pi), ("time_of_simulation", C.c_double), ("nu_start", C.c_double),
+         ("nu_end", C.c_double)]
+        + [(n, _pd) for n in ("emission", "absorption", "no_interaction", "electron_scatter")]
+        + [(n, _pi) for n in ("shell_packets", "line_emit_packets", "line_absorb_packets")]
+        + [(n, C.c_int64) for n in ("n_selected", "n_line", "n_electron_scatter", "n_no_interaction")]
+    )
+
+
 def _dp(a: np.ndarray):
     assert a.dtype == np.float64 and a.flags.c_contiguous
     return a.ctypes.data_as(_pd)

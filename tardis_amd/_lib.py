@@ -46,6 +46,8 @@ SYMBOLS = {
                                                 C.POINTER(C.c_uint64), C.c_uint32, _vp, C.c_int64]),
     "tardis_mc_get_packets": (_i, [_vp] * 6),
     "tardis_mc_packet_spectrum": (_i, [_vp, C.c_double, C.c_double, C.c_double, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "tardis_mc_packet_decomposition": (_i, [_vp, _vp]),
+    "tardis_mc_decomposition_path": (_i, [C.c_int64, C.c_int64, C.c_int64]),
     "tardis_mc_radiation_field": (_i, [_vp, C.c_double, _vp, C.c_double, C.c_int, _vp, _vp, _vp]),
     "tardis_mc_formal_integral": (_i, [_vp, C.c_double, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
     "tardis_mc_source_function": (_i, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),

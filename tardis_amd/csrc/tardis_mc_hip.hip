@@ -33,6 +33,8 @@
 #include "source_function.hpp"
 #include "tau_prefix.hpp"
 #include "propagate_plan.hpp"
+#include "packet_decomposition.hpp"
+#include "decomposition_plan.hpp"
 
 static_assert(plan::DBG_WAVE_COUNTERS == mc::WV_DBG_FLAGS, "propagate_plan.hpp repeats the wave kernel's list of counter flags");
 
@@ -181,6 +183,8 @@ struct TardisMcContext {
     DevBuf r0, mu0, nu0, e0, seeds, out_nu, out_e;
     DevBuf li_f64[9], li_i64[5], li_rec;  // (li_rec: the wave kernel's 64-byte tracker records, unpacked into the arrays after the propagation)
     bool track = true;
+    bool li_valid = false;  // the last-interaction arrays are those of the last propagate call's packets (tardis_mc_packet_decomposition)
+    DevBuf dc_work;         // tardis_mc_packet_decomposition: the class table and the outputs of a call
     // v-packet log
     DevBuf vlog_count, vlog_packet, vlog_seq, vlog_nu, vlog_energy, vlog_mu, vlog_r;
     long long vlog_capacity = 0;
@@ -560,15 +564,8 @@ __global__ void spectrum_kernel(const double *__restrict__ out_nu, const double 
         const bool emitted = e >= 0;
         const double l = emitted ? (e / t_sim) : -(e / t_sim);
         if (nu > nu_start && nu < nu_end) { if (emitted) lum_e += l; else lum_r += l; }
-        if (nu >= e0 && nu <= eN) {
-            // numpy: bin k holds edges[k] <= x < edges[k+1], the last bin is closed on the right; start from the uniform
-            // estimate and pin it with the actual edge values
-            int k = (int)((nu - e0) * inv_delta);
-            k = k < 0 ? 0 : (k > B - 1 ? B - 1 : k);
-            while (k > 0 && nu < edges[k]) --k;
-            while (k < B - 1 && nu >= edges[k + 1]) ++k;
-            mc::atomic_add_f64(emitted ? &hist_emitted[k] : &hist_reabsorbed[k], l);
-        }
+        const int k = mc::spectrum_bin(edges, B, e0, eN, inv_delta, nu);  // numpy.histogram's bin, -1 outside the grid
+        if (k >= 0) mc::atomic_add_f64(emitted ? &hist_emitted[k] : &hist_reabsorbed[k], l);
     }
     // block reduction of the two luminosity sums
     __shared__ double sh[2][256];
@@ -1977,7 +1974,7 @@ void tardis_mc_destroy(TardisMcContext *ctx)
                      &ctx->block_edge, &ctx->ttype, &ctx->dest, &ctx->tline, &ctx->staging, &ctx->line_block, &ctx->trans_rec, &ctx->bucket_first, &ctx->est, &ctx->grid, &ctx->r0,
                      &ctx->mu0, &ctx->nu0, &ctx->e0, &ctx->seeds, &ctx->out_nu, &ctx->out_e, &ctx->vlog_count,
                      &ctx->vlog_packet, &ctx->vlog_seq, &ctx->vlog_nu, &ctx->vlog_energy, &ctx->vlog_mu, &ctx->vlog_r,
-                     &ctx->rng_state, &ctx->counters, &ctx->first_error, &ctx->next_packet, &ctx->seeded_states, &ctx->problem_dev};
+                     &ctx->dc_work, &ctx->rng_state, &ctx->counters, &ctx->first_error, &ctx->next_packet, &ctx->seeded_states, &ctx->problem_dev};
     for (DevBuf *b : all) b->release();
     for (int b = 0; b < 2; ++b) {
         ctx->log_records[b].release(); ctx->log_keys[b].release(); ctx->log_cursor[b].release(); ctx->log_bins[b].release();
@@ -2416,6 +2413,7 @@ int tardis_mc_set_packets(TardisMcContext *ctx, const TardisMcPackets *p)
         (p->n_packets > 0 && (!p->initial_radii || !p->initial_nus || !p->initial_mus || !p->initial_energies || !p->packet_seeds)))
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid packets");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->li_valid = false;  // (the resident results are no longer those of the resident packets)
     const size_t P = (size_t)p->n_packets;
     int rc;
     HIP_TRY(ctx, ctx->r0.ensure(P * 8)); HIP_TRY(ctx, ctx->mu0.ensure(P * 8)); HIP_TRY(ctx, ctx->nu0.ensure(P * 8)); HIP_TRY(ctx, ctx->e0.ensure(P * 8));
@@ -2523,6 +2521,7 @@ int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, in
         max_seed_val < 2 || (uint64_t)n_total >= (1ULL << 44))
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid packet source arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->li_valid = false;
     const size_t P = (size_t)count;
     int rc = ensure_packet_buffers(ctx, P);
     if (rc) return rc;
@@ -2647,6 +2646,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->compactions = 0;
     ctx->ev_valid = false;
+    ctx->li_valid = false;
     ctx->sf_valid = false;
     const TardisMcConfig &c = ctx->cfg;
     PropagateCall call{};
@@ -2728,6 +2728,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         ctx->ls_tune.pending = call.tune_slot;
     }
     ctx->ev_valid = ctx->track_full;  // (a call that failed half-way leaves no event log to read)
+    ctx->li_valid = ctx->track;
     return TARDIS_MC_OK;
 }
 
@@ -3103,6 +3104,95 @@ int tardis_mc_packet_spectrum(TardisMcContext *ctx, double time_of_simulation, d
     if (out_emitted_luminosity) *out_emitted_luminosity = lum[0];
     if (out_reabsorbed_luminosity) *out_reabsorbed_luminosity = lum[1];
     work.release();
+    return TARDIS_MC_OK;
+}
+
+/* ---- consumer next to the path: the emitted spectrum decomposed by last interaction (packet_decomposition.hpp) ------------------ */
+int tardis_mc_decomposition_path(int64_t n_classes, int64_t n_bins, int64_t n_shells)
+{
+    return decomp::choose_path(n_classes, n_bins, n_shells);
+}
+
+int tardis_mc_packet_decomposition(TardisMcContext *ctx, TardisMcDecomposition *d)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!d) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "packet decomposition: no argument block");
+    d->n_selected = d->n_line = d->n_electron_scatter = d->n_no_interaction = 0;
+    if (!d->line_class) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "packet decomposition: line_class is NULL");
+    if (d->n_classes < 1 || d->n_classes > 0x7fffffffLL)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "packet decomposition: n_classes must be in [1, 2^31)");
+    if (!(d->time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "time_of_simulation must be positive");
+    if (!ctx->have_packets || !ctx->have_opacity || !ctx->have_geometry || !ctx->li_valid)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "packet decomposition: no last-interaction results of the resident packets -- it follows a completed "
+                    "tardis_mc_propagate with track_last_interaction on, before the packets are replaced");
+    if (!ctx->have_config || ctx->cfg.n_spectrum_grid < 2) return fail(ctx, TARDIS_MC_ERR_STATE, "packet decomposition needs a spectrum grid");
+    const long long C = d->n_classes, B = ctx->cfg.n_spectrum_grid - 1, S = ctx->n_shells, L = ctx->n_lines, P = ctx->n_packets;
+    // the class table, narrowed to 32 bits; no class is used as an index before it has passed this check
+    std::vector<int> cls((size_t)L);
+    for (long long i = 0; i < L; ++i) {
+        const int64_t c = d->line_class[i];
+        if (c < 0 || c >= C)
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "packet decomposition: line_class[%lld] = %lld is outside [0, %lld)", i, (long long)c, C);
+        cls[(size_t)i] = (int)c;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    {   // a call in which a packet failed has no complete results (the failing lane's output_nu holds its error code)
+        long long fe = 0x7fffffffffffffffLL;
+        if (ctx->first_error.p) HIP_TRY(ctx, hipMemcpyAsync(&fe, ctx->first_error.p, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (fe != 0x7fffffffffffffffLL) return fail(ctx, TARDIS_MC_ERR_STATE, "packet decomposition: packet %lld of the last tardis_mc_propagate failed", fe);
+    }
+    // one allocation: cells [(2C+2)B] doubles | shell_packets [(C+1)S] | line_emit [L] | line_absorb [L] | counts [4] | line_class [L] int32
+    const size_t n_cells = (size_t)(2 * C + 2) * (size_t)B, n_shell = (size_t)(C + 1) * (size_t)S;
+    const size_t n_words = n_cells + n_shell + 2 * (size_t)L + 4;
+    HIP_TRY(ctx, ctx->dc_work.ensure(n_words * 8 + (size_t)L * sizeof(int)));
+    double *cells = ctx->dc_work.as<double>();
+    unsigned long long *shell = reinterpret_cast<unsigned long long *>(cells + n_cells), *line_emit = shell + n_shell, *line_absorb = line_emit + L,
+                       *counts = line_absorb + L;
+    int *d_cls = reinterpret_cast<int *>(counts + 4);
+    HIP_TRY(ctx, hipMemcpyAsync(d_cls, cls.data(), (size_t)L * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(cells, 0, n_words * 8, ctx->stream));
+    if (P > 0) {
+        mc::DecompositionArgs a{};
+        a.out_nu = ctx->out_nu.as<double>(); a.out_e = ctx->out_e.as<double>(); a.before_nu = ctx->li_f64[3].as<double>();
+        a.shell_id = ctx->li_i64[0].as<long long>(); a.type = ctx->li_i64[1].as<long long>();
+        a.absorb_id = ctx->li_i64[2].as<long long>(); a.emit_id = ctx->li_i64[3].as<long long>();
+        a.n_packets = P;
+        a.line_class = d_cls; a.n_lines = L; a.n_classes = C;
+        a.edges = ctx->grid.as<double>(); a.n_edges = (int)ctx->cfg.n_spectrum_grid; a.n_shells = (int)S;
+        a.t_sim = d->time_of_simulation; a.nu_start = d->nu_start; a.nu_end = d->nu_end;
+        a.cells = cells; a.shell_packets = shell; a.line_emit = line_emit; a.line_absorb = line_absorb; a.counts = counts;
+        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+        const long long want = (P + mc::DC_BLOCK - 1) / mc::DC_BLOCK;
+        if (decomp::choose_path(C, B, S) == decomp::PATH_PRIVATISED) {
+            // two workgroups per CU (the LDS budget allows it): each flushes its private copy once, so few of them
+            const size_t lds = (size_t)decomp::private_bytes(C, B, S);
+            hipLaunchKernelGGL(mc::packet_decomposition_kernel<true>, dim3((unsigned)std::min<long long>(want, 2LL * cus)), dim3(mc::DC_BLOCK), lds, ctx->stream, a);
+        } else {
+            hipLaunchKernelGGL(mc::packet_decomposition_kernel<false>, dim3((unsigned)std::min<long long>(want, 16LL * cus)), dim3(mc::DC_BLOCK), (size_t)decomp::FIXED_BYTES, ctx->stream, a);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    ctx->timed = true;
+    ctx->chunks_timed = 0;
+    auto d2h = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+        if (!dst || !bytes) return hipSuccess;
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    };
+    const size_t CB = (size_t)C * (size_t)B;
+    HIP_TRY(ctx, d2h(d->emission, cells, CB * 8));
+    HIP_TRY(ctx, d2h(d->absorption, cells + CB, CB * 8));
+    HIP_TRY(ctx, d2h(d->no_interaction, cells + 2 * CB, (size_t)B * 8));
+    HIP_TRY(ctx, d2h(d->electron_scatter, cells + 2 * CB + B, (size_t)B * 8));
+    HIP_TRY(ctx, d2h(d->shell_packets, shell, n_shell * 8));
+    HIP_TRY(ctx, d2h(d->line_emit_packets, line_emit, (size_t)L * 8));
+    HIP_TRY(ctx, d2h(d->line_absorb_packets, line_absorb, (size_t)L * 8));
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    HIP_TRY(ctx, d2h(cnt, counts, sizeof cnt));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    d->n_selected = (int64_t)cnt[0]; d->n_line = (int64_t)cnt[1]; d->n_electron_scatter = (int64_t)cnt[2]; d->n_no_interaction = (int64_t)cnt[3];
     return TARDIS_MC_OK;
 }
 

@@ -308,6 +308,44 @@ class Engine:
         return {"montecarlo_emitted_luminosity": he, "montecarlo_reabsorbed_luminosity": hr,
                 "emitted_luminosity": le.value, "reabsorbed_luminosity": lr.value}
 
+    def packet_decomposition(self, time_of_simulation: float, line_class, n_classes: int | None = None, nu_start: float = 0.0,
+                             nu_end: float = float("inf")) -> dict:
+        """The emitted spectrum decomposed by last interaction, reduced on the device from the per-packet results of the last
+        propagate() (`tardis_mc_packet_decomposition`; it must have run with track_last_interaction on): what SDEC, the
+        last-interaction-velocity histogram and LastLineInteraction compute from the tracker's dataframe.  ``line_class``: [n_lines]
+        integers in [0, C), the caller's grouping of the lines (``spectrum.species_classes``); C = ``n_classes``, or
+        ``line_class.max() + 1``.  Returns {"emission", "absorption": (C, B), "no_interaction", "electron_scatter": (B,),
+        "shell_packets": (C + 1, S) -- row C electron scattering --, "line_emit_packets", "line_absorb_packets": (L,),
+        "n_selected", "n_line", "n_electron_scatter", "n_no_interaction"}, B the bins of the spectrum grid; definitions in
+        include/tardis_mc.h.  No per-packet array leaves the device."""
+        cls = np.ascontiguousarray(line_class, dtype=np.int64)
+        if cls.shape != (self.n_lines,):
+            raise ValueError("line_class must have one entry per line")
+        if n_classes is None:
+            n_classes = int(cls.max()) + 1 if cls.size else 1
+        Cn, B, S, L = int(n_classes), max(self.n_grid - 1, 0), self.n_shells, self.n_lines
+        rows = max(Cn, 0)  # (a refused n_classes sizes nothing)
+        out = {"emission": np.zeros((rows, B)), "absorption": np.zeros((rows, B)), "no_interaction": np.zeros(B),
+               "electron_scatter": np.zeros(B), "shell_packets": np.zeros((rows + 1, S), dtype=np.int64),
+               "line_emit_packets": np.zeros(L, dtype=np.int64), "line_absorb_packets": np.zeros(L, dtype=np.int64)}
+        d = _abi.TardisMcDecomposition()
+        d.n_classes, d.line_class = Cn, _abi._ip(cls)
+        d.time_of_simulation, d.nu_start, d.nu_end = float(time_of_simulation), float(nu_start), float(nu_end)
+        for k in ("emission", "absorption", "no_interaction", "electron_scatter"):
+            setattr(d, k, _abi._dp(out[k]))
+        for k in ("shell_packets", "line_emit_packets", "line_absorb_packets"):
+            setattr(d, k, _abi._ip(out[k]))
+        self._check(self._L.tardis_mc_packet_decomposition(self._h, C.byref(d)), "packet_decomposition")
+        for k in ("n_selected", "n_line", "n_electron_scatter", "n_no_interaction"):
+            out[k] = int(getattr(d, k))
+        return out
+
+    @staticmethod
+    def decomposition_path(n_classes: int, n_bins: int, n_shells: int) -> str:
+        """The accumulation path packet_decomposition() takes for this shape: "privatised" (per-workgroup copies in LDS) or
+        "direct" (global atomics); csrc/decomposition_plan.hpp."""
+        return ("privatised", "direct")[int(_lib.lib().tardis_mc_decomposition_path(int(n_classes), int(n_bins), int(n_shells)))]
+
     def radiation_field(self, time_of_simulation: float, volume, w_epsilon: float = 1e-10,
                         detailed_optical_window: bool = False, want_j_blues: bool = True) -> dict:
         """MCRadiationFieldPropertiesSolver.solve (estimators/mc_rad_field_solver.py:37-144) on the resident estimators."""

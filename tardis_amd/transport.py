@@ -401,6 +401,25 @@ class MonteCarloTransportState:
                 "montecarlo_reabsorbed_luminosity": spectrum.reabsorbed_luminosity_histogram(nus, en, t, spectrum_frequency_grid),
                 "emitted_luminosity": float(np.sum(lum[win & (en >= 0)])), "reabsorbed_luminosity": float(-np.sum(lum[win & (en < 0)]))}
 
+    def packet_decomposition(self, spectrum_frequency_grid, line_class, n_classes=None, nu_start=0.0, nu_end=float("inf")):
+        """The emitted spectrum decomposed by last interaction -- emission / absorption by line class (SDEC; classes from
+        ``spectrum.species_classes``), the no-interaction and electron-scattering spectra, packets per (class, shell) (LIV) and per
+        line (LastLineInteraction); the dict of ``Engine.packet_decomposition``.  After a resident run with last-interaction tracking
+        it is reduced on the device from the resident trackers (on the engine's spectrum grid, the solver's; none is downloaded),
+        otherwise on the host from ``tracker_last_interaction`` (``spectrum.packet_decomposition``)."""
+        if self._est_engine is not None and self._device_estimators is not None and self._tracker_last_interaction is None:
+            self._device_estimators._fresh(estimators=False)
+            if self._engine is not None:
+                self.packet_collection._fresh(True)
+            return self._est_engine.packet_decomposition(self.time_of_simulation, line_class, n_classes, nu_start, nu_end)
+        from . import spectrum
+        t = self.tracker_last_interaction
+        if t is None or len(t) != len(self.output_nu):
+            raise RuntimeError("packet_decomposition() needs a run with last-interaction tracking")
+        return spectrum.packet_decomposition(self.output_nu, self.output_energy, self.time_of_simulation, spectrum_frequency_grid,
+                                             t.interaction_type, t.interaction_line_emit_id, t.interaction_line_absorb_id, t.before_nu,
+                                             t.shell_id, line_class, len(self.geometry_state_numba.r_inner), n_classes, nu_start, nu_end)
+
     def radiation_field(self, volume, w_epsilon=1e-10, detailed_optical_window=False, want_j_blues=True):
         """MCRadiationFieldPropertiesSolver.solve (estimators/mc_rad_field_solver.py:37-144) on the engine's resident (after
         an N-GPU step: all-reduced) estimators.  Only after a resident run."""
