@@ -32,7 +32,8 @@ extern "C" {
 
 #define TARDIS_MC_ABI_VERSION 2  /* 2 (round 6): + tardis_mc_comm_check, tardis_mc_stream_results, tardis_mc_streamed_packets, tardis_mc_last_compactions, microbench 15;
                                     * additive since: tardis_mc_formal_integral_interpolated, tardis_mc_interpolated_source,
-                                    * tardis_mc_packet_decomposition, tardis_mc_decomposition_path */
+                                    * tardis_mc_packet_decomposition, tardis_mc_decomposition_path, option "vpacket_last_interaction",
+                                    * TardisMcVpacketLog, tardis_mc_get_vpacket_log, tardis_mc_vpacket_decomposition */
 
 enum {
     TARDIS_MC_OK = 0,
@@ -175,6 +176,23 @@ typedef struct TardisMcDecomposition {
     int64_t n_selected, n_line, n_electron_scatter, n_no_interaction;
 } TardisMcDecomposition;
 
+/* The v-packet log of the last tardis_mc_propagate (ENABLE_VPACKET_TRACKING), consolidated on the device: packet order, then spawn order
+ * -- the order of the vpacket_* arrays of TardisMcResult -- in a CSR layout, packet p's entries are [offsets[p], offsets[p + 1]).  The six
+ * last_interaction_* columns (option "vpacket_last_interaction") hold the spawning r-packet's last-interaction tracker at the time of the
+ * volley, i.e. its last non-boundary interaction before it: in_nu (the tracker's before_nu), in_r (the radius of that interaction; bit for
+ * bit the entry's initial_r, the volley is traced from there), type (2 LINE, 4 ESCATTERING), in_id (absorb line), out_id (emit line),
+ * shell_id.  The entries of the launch volley have type = in_id = out_id = shell_id = -1 and in_nu = in_r = NaN, the conventions of
+ * LastInteractionTrackers. */
+typedef struct TardisMcVpacketLog {
+    int64_t capacity;        /* in: entries available in each column */
+    int64_t count;           /* out: entries the last propagate call produced */
+    int64_t *offsets;        /* [n_packets + 1] or NULL: packet p's entries are [offsets[p], offsets[p+1]) */
+    int64_t *source_packet;  /* [count] each below, any may be NULL */
+    double *nus, *energies, *initial_mus, *initial_rs;
+    double *last_interaction_in_nu, *last_interaction_in_r;
+    int64_t *last_interaction_type, *last_interaction_in_id, *last_interaction_out_id, *last_interaction_shell_id;
+} TardisMcVpacketLog;
+
 typedef struct TardisMcContext TardisMcContext;
 
 /* ---- library / device ---------------------------------------------------------------------------- */
@@ -186,6 +204,10 @@ void tardis_mc_destroy(TardisMcContext *ctx);
 const char *tardis_mc_last_error(const TardisMcContext *ctx);   /* ctx may be NULL: last create() error */
 
 /* Tunables.  name: "track_last_interaction" (0/1, default 1), "vpacket_log_capacity" (entries),
+ * "vpacket_last_interaction" (0/1, default 0: every v-packet log entry also carries the last-interaction tracker of its r-packet at the
+ * time of the volley, 24 B more per entry on the device, TardisMcVpacketLog; needs ENABLE_VPACKET_TRACKING, v-packets and a tracker --
+ * a propagate call with it, v-packet tracking and neither "track_last_interaction" nor "track_full" fails with TARDIS_MC_ERR_INVALID_ARGUMENT
+ * before anything is launched; without v-packet tracking it does nothing; per-packet results do not depend on it),
  * "track_full" (0/1, default 0: full r-packet tracking, TardisMcEventLog; whatever "variant" says, a call runs on the wave-owner
  * kernel with group sweeps, variant 2, where that can run it -- sorted lines, monotone probabilities, <= 32 v-packets and no surviving
  * ones, no cross-check debug flags -- else on the lane-per-packet kernel, variant 0), "event_log_capacity" (rows the device log holds, 0 = automatic: 32 per packet; a call whose log
@@ -349,6 +371,17 @@ int tardis_mc_packet_spectrum(TardisMcContext *ctx, double time_of_simulation, d
  * line_class is NULL, C < 1, a class is outside [0, C) (checked on the host before anything is indexed with it) or time_of_simulation is
  * not positive.  Nothing resident changes.  tardis_mc_last_propagate_ms then reports the device time of the call's kernels. */
 int tardis_mc_packet_decomposition(TardisMcContext *ctx, TardisMcDecomposition *d);
+/* The same decomposition of the VIRTUAL spectrum (SDEC / LIV with packets_mode="virtual"): packet_decomposition_kernel on the consolidated
+ * v-packet log of the last tardis_mc_propagate (consolidated here where tardis_mc_get_vpacket_log has not done it yet), one entry per
+ * v-packet with output_nu = nus, output_energy = energies, li_before_nu = last_interaction_in_nu, li_interaction_type = last_interaction_type,
+ * li_line_emit_id = last_interaction_out_id, li_line_absorb_id = last_interaction_in_id, li_shell_id = last_interaction_shell_id.  Same struct,
+ * outputs, accumulation paths, argument checks and additivity over packet shards.  A v-packet is selected when nu_start < nu < nu_end (its
+ * energy is never negative); one the roulette dropped has energy 0.0: it adds 0.0 to its cell and still counts in the integer outputs.  The sum
+ * of all double cells of emission, electron_scatter and no_interaction is sum(v_packets_energy_hist) / time_of_simulation to rounding.
+ * TARDIS_MC_ERR_STATE without a valid v-packet log with last-interaction columns (option "vpacket_last_interaction"), when the log overflowed
+ * (run again with vpacket_log_capacity >= the count tardis_mc_get_vpacket_log reports), when a packet failed, or without a spectrum grid.
+ * Nothing resident changes.  tardis_mc_last_propagate_ms then reports the device time of the call's kernels. */
+int tardis_mc_vpacket_decomposition(TardisMcContext *ctx, TardisMcDecomposition *d);
 /* Which accumulation path a call with C classes, B bins and S shells takes: 0 privatised (LDS), 1 direct (HBM).  Host only. */
 int tardis_mc_decomposition_path(int64_t n_classes, int64_t n_bins, int64_t n_shells);
 
@@ -441,6 +474,17 @@ int tardis_mc_interpolated_source(TardisMcContext *ctx, int64_t interpolate_shel
  * last call ran without full tracking, when a packet of it failed, or when the resident packets were replaced since.  With dropped > 0 only count / dropped / offsets are written: run the call again with
  * event_log_capacity >= count (the run is deterministic). */
 int tardis_mc_get_event_log(TardisMcContext *ctx, TardisMcEventLog *log);
+
+/* The v-packet log of the last tardis_mc_propagate, consolidated on the device (csrc/vpacket_log.hpp): one atomic per entry counts the
+ * entries per source packet, the event log's scan turns the counts into offsets, and entry k moves to offsets[packet] + seq -- seq is the
+ * entry's ordinal within its packet, so nothing is sorted.  The columns stay resident (tardis_mc_vpacket_decomposition reads them) until the
+ * next tardis_mc_propagate, tardis_mc_set_packets or tardis_mc_set_config.  tardis_mc_get_results keeps its own host path and outputs.
+ * If the call ran without "vpacket_last_interaction" the six last_interaction_* pointers must be NULL (else TARDIS_MC_ERR_STATE); the other
+ * columns work either way.  When the device log overflowed (count above vpacket_log_capacity) or count > capacity only count is written and
+ * the call returns 0: run again with vpacket_log_capacity >= count (the run is deterministic).  TARDIS_MC_ERR_STATE when the last call did
+ * not track v-packets, when a packet of it failed, when the resident packets were replaced since, or when an entry's packet, ordinal or
+ * position is out of range (every index is checked on the device before it is used). */
+int tardis_mc_get_vpacket_log(TardisMcContext *ctx, TardisMcVpacketLog *log);
 
 /* ---- result streaming (optional).  Registers the caller's per-packet result arrays (output_nus / output_energies and the fourteen li_* arrays of *dst; any may
  * be NULL; the other fields are ignored) as the destination of the NEXT tardis_mc_propagate: a call of the wave-owner kernel that runs as several launches copies the

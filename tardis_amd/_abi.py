@@ -109,6 +109,19 @@ class TardisMcEventLog(C.Structure):
     )
 
 
+_VL_F64 = ("nus", "energies", "initial_mus", "initial_rs", "last_interaction_in_nu", "last_interaction_in_r")
+_VL_I64 = ("last_interaction_type", "last_interaction_in_id", "last_interaction_out_id", "last_interaction_shell_id")
+
+
+class TardisMcVpacketLog(C.Structure):
+    """The v-packet log consolidated on the device: CSR offsets + packet-ordered columns (tardis_mc_get_vpacket_log)."""
+    _fields_ = (
+        [("capacity", C.c_int64), ("count", C.c_int64), ("offsets", _pi), ("source_packet", _pi)]
+        + [(n, _pd) for n in _VL_F64]
+        + [(n, _pi) for n in _VL_I64]
+    )
+
+
 class TardisMcDecomposition(C.Structure):
     """The emitted spectrum decomposed by last interaction (tardis_mc_packet_decomposition): inputs, host output pointers, counts."""
     _fields_ = (

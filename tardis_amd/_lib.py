@@ -47,6 +47,7 @@ SYMBOLS = {
     "tardis_mc_get_packets": (_i, [_vp] * 6),
     "tardis_mc_packet_spectrum": (_i, [_vp, C.c_double, C.c_double, C.c_double, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tardis_mc_packet_decomposition": (_i, [_vp, _vp]),
+    "tardis_mc_vpacket_decomposition": (_i, [_vp, _vp]),
     "tardis_mc_decomposition_path": (_i, [C.c_int64, C.c_int64, C.c_int64]),
     "tardis_mc_radiation_field": (_i, [_vp, C.c_double, _vp, C.c_double, C.c_int, _vp, _vp, _vp]),
     "tardis_mc_formal_integral": (_i, [_vp, C.c_double, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
@@ -56,6 +57,7 @@ SYMBOLS = {
     "tardis_mc_formal_integral_interpolated": (_i, [_vp, C.c_int64, C.c_double, _vp, C.c_int64, C.c_int64, _vp, _vp]),
     "tardis_mc_interpolated_source": (_i, [_vp, C.c_int64] + [_vp] * 8),
     "tardis_mc_get_event_log": (_i, [_vp, _vp]),
+    "tardis_mc_get_vpacket_log": (_i, [_vp, _vp]),
     "tardis_mc_stream_results": (_i, [_vp, _vp]),
     "tardis_mc_streamed_packets": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tardis_mc_run": (_i, [_vp] * 6),

@@ -402,4 +402,23 @@ __device__ __forceinline__ void gatomic_min_i64(long long *p, long long v)
     __hip_atomic_fetch_min((MC_AS1 __typeof__(*p) *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- v-packet log, option vpacket_last_interaction: the tracker state an entry carries -- the spawning r-packet's last interaction at
+// the time of the volley; the empty one is that of a packet without an interaction so far (LastInteractionTrackers' conventions: -1 / NaN).
+// 24 B per entry, {type, absorb line, emit line, shell} as 4 x int32 and before_nu (the radius of the interaction is the entry's vlog_r).
+// The two columns share vlog_r's allocation -- vlog_r [capacity] | before_nu [capacity] | ids [capacity] -- so that DeviceProblem, and with
+// it every argument block, keeps its layout: the kernels that do not write them compile from unchanged code.  Only the VLI instantiations
+// of the kernels call vlog_store_last; the host launches those exactly when it has allocated the longer buffer.
+struct VlogLast {
+    double in_nu;
+    int type, in_id, out_id, shell_id;
+};
+__device__ __forceinline__ VlogLast vlog_last_empty() { return VlogLast{__builtin_nan(""), -1, -1, -1, -1}; }
+__host__ __device__ __forceinline__ double *vlog_last_nu(double *vlog_r, long long capacity) { return vlog_r + capacity; }
+__host__ __device__ __forceinline__ int4 *vlog_last_ids(double *vlog_r, long long capacity) { return reinterpret_cast<int4 *>(vlog_r + 2 * capacity); }
+__device__ __forceinline__ void vlog_store_last(double *vlog_r, long long capacity, unsigned long long slot, const VlogLast &last)
+{   // (slot < capacity: the caller's test)
+    glob(vlog_last_nu(vlog_r, capacity))[slot] = last.in_nu;
+    gstore(vlog_last_ids(vlog_r, capacity) + slot, make_int4(last.type, last.in_id, last.out_id, last.shell_id));
+}
+
 }  // namespace mc

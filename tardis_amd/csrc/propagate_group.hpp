@@ -677,11 +677,11 @@ __device__ __forceinline__ int vp_screen(const GroupArgs &P, const GroupRng<G> &
     }
 }
 
-template <bool FULL, int G, bool WIDE>
+template <bool FULL, int G, bool WIDE, bool VLI>
 __device__ __forceinline__ int volley_group(const GroupArgs &P, const Packet &p, GroupRng<G> &rng, const int j, long long packet_index,
                                             int &vseq, unsigned &pred_bits, unsigned &vvisits, unsigned &vcount, unsigned long long &vtraced,
-                                            const double *geo)
-{   // trace_vpacket_volley (:248-386)
+                                            const double *geo, const LdsTracker *trk)
+{   // trace_vpacket_volley (:248-386); trk: the packet's tracker (null without one), for the log option vpacket_last_interaction
     if (p.nu < P.spawn_start || p.nu > P.spawn_end) return 0;
     const int n_v = (int)P.n_vpackets;
     if (n_v == 0) return 0;
@@ -786,6 +786,11 @@ __device__ __forceinline__ int volley_group(const GroupArgs &P, const Packet &p,
                 if ((long long)slot < C->vlog_capacity) {
                     glob(C->vlog_packet)[slot] = packet_index; glob(C->vlog_seq)[slot] = vseq + j;
                     glob(C->vlog_nu)[slot] = v_nu; glob(C->vlog_energy)[slot] = v_energy; glob(C->vlog_mu)[slot] = v_mu0; glob(C->vlog_r)[slot] = p.r;
+                    if constexpr (VLI) {  // the r-packet's tracker at the time of the volley (the launch volley: still -1 / NaN)
+                        VlogLast last = vlog_last_empty();
+                        if (trk) last = VlogLast{trk->before_nu, trk->interaction_type, trk->line_absorb_id, trk->line_emit_id, trk->shell_id};
+                        vlog_store_last(C->vlog_r, C->vlog_capacity, slot, last);
+                    }
                 }
             }
         }
@@ -812,7 +817,9 @@ __host__ __device__ constexpr size_t group_kernel_lds_bytes(int n_shells)
 }
 
 // WIDE: 64-bit row offsets into the shell-major tables (option table_offsets; mc_device.hpp)
-template <bool FULL, bool TRACK, int G, int BLOCK, int OCC, bool VPK, bool WIDE = false>
+// VLI: the v-packet log entries also carry the packet's tracker (option vpacket_last_interaction; its own instantiations, so that the
+// others compile from unchanged code); needs VPK and TRACK
+template <bool FULL, bool TRACK, int G, int BLOCK, int OCC, bool VPK, bool WIDE = false, bool VLI = false>
 __global__ void __launch_bounds__(BLOCK, OCC) propagate_group_kernel(GroupArgs P, uint32_t *__restrict__ seeded_states,
                                                                 long long chunk_first, long long chunk_count)
 {
@@ -954,7 +961,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) propagate_group_kernel(GroupArgs P
             const unsigned long long live_mask = __ballot(live), want_mask = __ballot(live && want_volley);
             if (want_mask != 0ull && want_mask == live_mask) {
                 if (live && want_volley) {
-                    const int verr = volley_group<FULL, G, WIDE>(P, p, rng, j, chunk_first + pkt, vseq, pred_bits, vvisits, vcount, vtraced, lds_geo);
+                    const int verr = volley_group<FULL, G, WIDE, VLI>(P, p, rng, j, chunk_first + pkt, vseq, pred_bits, vvisits, vcount, vtraced, lds_geo, (VLI && TRACK) ? &trk : nullptr);
                     want_volley = false;
                     if (verr) {
                         if (j == 0) {

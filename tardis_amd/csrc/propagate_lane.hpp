@@ -254,9 +254,10 @@ __device__ int trace_vpacket(const DeviceProblem &P, Packet &v, Rng &rng, double
     return 0;
 }
 
-template <bool FULL>
+// VLI: the log entries also carry `last`, the r-packet's tracker at the time of the volley (option vpacket_last_interaction)
+template <bool FULL, bool VLI>
 __device__ int trace_vpacket_volley(const DeviceProblem &P, const Packet &p, Rng &rng, long long packet_index,
-                                    int &vseq, LaneCounters &cn)
+                                    int &vseq, LaneCounters &cn, const VlogLast last)
 {
     if (p.nu < P.spawn_start || p.nu > P.spawn_end) return 0;
     const long long n_v = P.n_vpackets;
@@ -311,6 +312,7 @@ __device__ int trace_vpacket_volley(const DeviceProblem &P, const Packet &p, Rng
             if ((long long)slot < P.vlog_capacity) {
                 P.vlog_packet[slot] = packet_index; P.vlog_seq[slot] = vseq;
                 P.vlog_nu[slot] = v.nu; P.vlog_energy[slot] = v.energy; P.vlog_mu[slot] = v_mu; P.vlog_r[slot] = p.r;
+                if constexpr (VLI) vlog_store_last(P.vlog_r, P.vlog_capacity, slot, last);  // the r-packet's tracker at the time of the volley
             }
         }
         ++vseq;
@@ -320,7 +322,7 @@ __device__ int trace_vpacket_volley(const DeviceProblem &P, const Packet &p, Rng
 
 // ---- packet_propagation (classic/packet_propagation.py:52-318)
 // FT: full r-packet tracking -- one event_log.hpp row per trace_packet outcome (ev_ws: the wave's append state in LDS)
-template <bool FULL, bool VPK, bool TRACK, bool FT = false>
+template <bool FULL, bool VPK, bool TRACK, bool FT = false, bool VLI = false>
 __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, double *lds_J, double *lds_nubar, double *jb,
                              double *ed, LaneCounters &cn, volatile int *ev_ws = nullptr)
 {
@@ -328,8 +330,10 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
     Packet p;
     p.r = P.r0[i]; p.mu = P.mu0[i]; p.nu = P.nu0[i]; p.energy = P.e0[i];
     p.shell = 0; p.status = ST_IN_PROCESS; p.next_line_id = 0;
+    // (a tracked call without the last-interaction arrays still keeps the tracker for its v-packet log, option vpacket_last_interaction)
+    constexpr bool TRK = TRACK || (VLI && FT && VPK);
     Tracker trk;
-    if (TRACK) trk.init();
+    if (TRK) trk.init();
     int vseq = 0;
     int err;
     {   // set_packet_props_{partial,full}_relativity
@@ -356,7 +360,7 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
         if (lo == P.n_lines) lo -= 1;
         p.next_line_id = lo;
     }
-    if (VPK) { if ((err = trace_vpacket_volley<FULL>(P, p, rng, i, vseq, cn))) return err; }
+    if (VPK) { if ((err = trace_vpacket_volley<FULL, VLI>(P, p, rng, i, vseq, cn, vlog_last_empty()))) return err; }
     if (TRACK) trk.boundary_buffer += 1;
     int n_ev = 0;
 
@@ -376,12 +380,12 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
             if (TRACK) trk.boundary_buffer += 1;
             cross_shell(p.shell, p.status, delta, P.n_shells);
         } else if (type == IT_LINE) {
-            if (TRACK) {
+            if (TRK) {
                 trk.before_nu = p.nu; trk.before_mu = p.mu; trk.before_energy = p.energy;
                 trk.line_absorb_id = p.next_line_id;
             }
             if ((err = line_scatter_event<FULL>(P, p, rng, cn))) return err;
-            if (TRACK) {
+            if (TRK) {
                 trk.after_nu = p.nu; trk.after_mu = p.mu; trk.after_energy = p.energy;
                 trk.line_emit_id = p.next_line_id - 1;
                 trk.interactions_count += 1 + trk.pop();
@@ -389,12 +393,12 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
                 trk.interaction_type = IT_LINE;
             }
         } else {  // IT_ESCATTERING
-            if (TRACK) {
+            if (TRK) {
                 trk.before_mu = p.mu; trk.before_nu = p.nu; trk.before_energy = p.energy;
                 trk.line_absorb_id = -1; trk.line_emit_id = -1;
             }
             thomson_scatter<FULL>(P, p, rng);
-            if (TRACK) {
+            if (TRK) {
                 trk.after_mu = p.mu; trk.after_nu = p.nu; trk.after_energy = p.energy;
                 trk.interactions_count += 1 + trk.pop();
                 trk.radius = p.r; trk.nu = p.nu; trk.energy = p.energy; trk.shell_id = p.shell;
@@ -410,7 +414,11 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
         }
         // one shared call site for the volley after a line or electron-scattering interaction: lanes of both kinds trace
         // their v-packets together instead of serialising two inlined copies of the volley
-        if (VPK && type != IT_BOUNDARY) { if ((err = trace_vpacket_volley<FULL>(P, p, rng, i, vseq, cn))) return err; }
+        if (VPK && type != IT_BOUNDARY) {
+            const VlogLast last = (VLI && TRK) ? VlogLast{trk.before_nu, (int)trk.interaction_type, (int)trk.line_absorb_id, (int)trk.line_emit_id, (int)trk.shell_id}
+                                      : vlog_last_empty();
+            if ((err = trace_vpacket_volley<FULL, VLI>(P, p, rng, i, vseq, cn, last))) return err;
+        }
     }
     // set_packet_collection_output (modes/montecarlo_transport.py:70-90)
     P.out_nu[i] = p.nu;
@@ -433,7 +441,8 @@ __device__ __forceinline__ int xcc_id()
     return (int)(__builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11)) & 0xf);
 }
 
-template <bool FULL, bool VPK, bool TRACK, bool FT = false>
+// VLI: the instantiations a call with the option vpacket_last_interaction runs (the others compile from unchanged code)
+template <bool FULL, bool VPK, bool TRACK, bool FT = false, bool VLI = false>
 __global__ void __launch_bounds__(256) propagate_lane_kernel(DeviceProblem P)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -456,7 +465,7 @@ __global__ void __launch_bounds__(256) propagate_lane_kernel(DeviceProblem P)
     unsigned long long draws = 0;
     for (long long i = gtid; i < P.n_packets; i += n_threads) {
         rng.seed(state, P.seeds[i]);
-        int err = propagate_one<FULL, VPK, TRACK, FT>(P, i, rng, lds_J, lds_nubar, jb, ed, cn, ev_ws);
+        int err = propagate_one<FULL, VPK, TRACK, FT, VLI>(P, i, rng, lds_J, lds_nubar, jb, ed, cn, ev_ws);
         draws += (unsigned long long)rng.draws;
         if (err) {
             long long prev = atomicMin(&P.first_error[0], i);

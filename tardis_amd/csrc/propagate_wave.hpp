@@ -805,10 +805,11 @@ __device__ __forceinline__ int vp_screen_step(const GroupArgs &P, Draw &&draw, i
 // a trace's record to the chunk of its shell (one LDS atomic on the shell's fill), so that every chunk of the log holds records of ONE shell and the estimator passes
 // start with the partition by bin: the pass that grouped the log by shell (a full read and write of the log: 21 of the 87 ms of passes per 2e9 records,
 // profiles/r04_estimator_partition.txt) is gone.
+// VLI: the v-packet log entries also carry the r-packet's last interaction (option vpacket_last_interaction); needs VPK and TRACK
 // FT: full r-packet tracking (event_log.hpp) -- one row per trace outcome, the row's ordinal from trk_count + trk_boundary (which travel
 // with the lane through suspensions, epochs and drain compaction); needs TRACK
 template <bool FULL, bool TRACK, int G, bool VPK, bool LS = false, bool XWALK = true, int WPE = (VPK ? 3 : 4), int NT = 0, bool SL = false,
-          bool FT = false, bool WIDE = false>
+          bool FT = false, bool WIDE = false, bool VLI = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) propagate_wave_kernel(WaveHot H, const WaveCold *__restrict__ W)
 {
     static_assert(!WIDE || (!XWALK && NT == 0 && !SL), "64-bit row offsets: the compact walks, the separate line and tau tables, the log by bin");
@@ -1674,6 +1675,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                                 if ((long long)slot < C->vlog_capacity) {
                                     glob(C->vlog_packet)[slot] = chunk_first + pkt; glob(C->vlog_seq)[slot] = vseq;
                                     glob(C->vlog_nu)[slot] = r.nu; glob(C->vlog_energy)[slot] = r.energy; glob(C->vlog_mu)[slot] = r.mu0; glob(C->vlog_r)[slot] = p.r;
+                                    if constexpr (VLI) {
+                                        // option vpacket_last_interaction (VLI: its own instantiations, so that the others compile from unchanged code): the tracker record this lane stored at the interaction the volley
+                                        // follows, read back from memory (it survives a suspension); none yet at the launch volley
+                                        VlogLast last = vlog_last_empty();
+                                        if (TRACK && trk_any) {
+                                            const MC_G TrackerRecord *tr = glob(reinterpret_cast<const TrackerRecord *>(C->li_rec) + (chunk_first + pkt));
+                                            last = VlogLast{tr->before_nu, tr->type, tr->absorb, tr->emit, tr->shell};
+                                        }
+                                        vlog_store_last(C->vlog_r, C->vlog_capacity, slot, last);
+                                    }
                                 }
                             }
                             ++vseq;

@@ -35,6 +35,7 @@
 #include "propagate_plan.hpp"
 #include "packet_decomposition.hpp"
 #include "decomposition_plan.hpp"
+#include "vpacket_log.hpp"
 
 static_assert(plan::DBG_WAVE_COUNTERS == mc::WV_DBG_FLAGS, "propagate_plan.hpp repeats the wave kernel's list of counter flags");
 
@@ -189,6 +190,14 @@ struct TardisMcContext {
     DevBuf vlog_count, vlog_packet, vlog_seq, vlog_nu, vlog_energy, vlog_mu, vlog_r;
     long long vlog_capacity = 0;
     bool vlog_capacity_user = false;  // set through the vpacket_log_capacity option (otherwise sized per propagate call)
+    // option vpacket_last_interaction: 24 B more per entry, behind vlog_r in its allocation (mc_device.hpp); the log consolidated on the device (vpacket_log.hpp): the per-packet
+    // counts, their offsets, the scan's tile sums, the packet-ordered columns (five, or eleven with the last interaction), the error word
+    bool vlog_li = false;
+    DevBuf vl_counts, vl_offsets, vl_tiles, vl_cols, vl_errors;
+    bool vl_valid = false;         // the last propagate call wrote a v-packet log and nothing has replaced its packets or its configuration since
+    bool vl_li = false;            // ... with the last-interaction columns
+    bool vl_consolidated = false;  // vl_cols holds that log
+    long long vl_packets = 0, vl_capacity = 0, vl_count = 0;  // packets and device capacity of that call; entries it produced (once consolidated)
     // full r-packet tracking (option track_full, event_log.hpp): runs on the wave kernel (variant 2) where that can run the call, else on the lane kernel; the row pool, its chunk fills, {pool_next, dropped},
     // the per-packet counts, and for tardis_mc_get_event_log the offsets, the tile sums of their scan and the packet-major columns
     bool track_full = false;
@@ -705,6 +714,13 @@ __global__ void __launch_bounds__(256) narrow_seeds_kernel(const long long *__re
     if (i < n) out[i] = (uint32_t)in[i];
 }
 
+// whether the propagate call being set up writes the last-interaction columns of the v-packet log (option vpacket_last_interaction):
+// such a call runs the VLI instantiations of the kernels
+bool vlog_li_call(const TardisMcContext *ctx)
+{
+    return ctx->vlog_li && ctx->cfg.enable_vpacket_tracking && ctx->cfg.number_of_vpackets > 0 && ctx->vlog_capacity > 0;
+}
+
 mc::DeviceProblem make_device_problem(TardisMcContext *ctx)
 {
     mc::DeviceProblem P{};
@@ -769,24 +785,25 @@ mc::DeviceProblem make_device_problem(TardisMcContext *ctx)
 
 // ---- The kernel tables: every instantiation of the three propagation kernels that exists, keyed by its template arguments (in their order).
 // A call computes its key once and looks the kernel up; a key that is not in its table is a programming error, which the lookup reports.
-struct LaneKernelKey { bool full, vpk, track, full_tracking; };
-struct GroupKernelKey { bool full, track; int width, block, occupancy; bool vpk, wide; };
+struct LaneKernelKey { bool full, vpk, track, full_tracking, vli; };  // (vli: option vpacket_last_interaction; rows that leave it out: false)
+struct GroupKernelKey { bool full, track; int width, block, occupancy; bool vpk, wide, vli; };
 struct WaveKernelKey {
     bool full, track;
     int width;  // lanes per sweep worker
     bool vpk, lane_sweep, xwalk;
     int waves_per_simd, nt;  // the register budget | the interleaved sweep table: 0 none, 1 runs from the current line, 2 aligned runs
     bool shell_log, full_tracking, wide;  // (wide: 64-bit table offsets)
+    bool vli;  // the v-packet log with last interactions (option vpacket_last_interaction)
 };
-bool operator==(const LaneKernelKey &a, const LaneKernelKey &b) { return a.full == b.full && a.vpk == b.vpk && a.track == b.track && a.full_tracking == b.full_tracking; }
+bool operator==(const LaneKernelKey &a, const LaneKernelKey &b) { return a.full == b.full && a.vpk == b.vpk && a.track == b.track && a.full_tracking == b.full_tracking && a.vli == b.vli; }
 bool operator==(const GroupKernelKey &a, const GroupKernelKey &b)
 {
-    return a.full == b.full && a.track == b.track && a.width == b.width && a.block == b.block && a.occupancy == b.occupancy && a.vpk == b.vpk && a.wide == b.wide;
+    return a.full == b.full && a.track == b.track && a.width == b.width && a.block == b.block && a.occupancy == b.occupancy && a.vpk == b.vpk && a.wide == b.wide && a.vli == b.vli;
 }
 bool operator==(const WaveKernelKey &a, const WaveKernelKey &b)
 {
     return a.full == b.full && a.track == b.track && a.width == b.width && a.vpk == b.vpk && a.lane_sweep == b.lane_sweep && a.xwalk == b.xwalk &&
-           a.waves_per_simd == b.waves_per_simd && a.nt == b.nt && a.shell_log == b.shell_log && a.full_tracking == b.full_tracking && a.wide == b.wide;
+           a.waves_per_simd == b.waves_per_simd && a.nt == b.nt && a.shell_log == b.shell_log && a.full_tracking == b.full_tracking && a.wide == b.wide && a.vli == b.vli;
 }
 using LaneKernelFn = void (*)(mc::DeviceProblem);
 using GroupKernelFn = void (*)(mc::GroupArgs, uint32_t *, long long, long long);
@@ -806,6 +823,8 @@ const KernelRow<LaneKernelKey, LaneKernelFn> LANE_KERNELS[] = {  // FULL, VPK, T
     KROW(lane, 1, 0, 0, 0), KROW(lane, 1, 0, 1, 0), KROW(lane, 1, 1, 0, 0), KROW(lane, 1, 1, 1, 0),
     KROW(lane, 0, 0, 0, 1), KROW(lane, 0, 0, 1, 1), KROW(lane, 0, 1, 0, 1), KROW(lane, 0, 1, 1, 1),
     KROW(lane, 1, 0, 0, 1), KROW(lane, 1, 0, 1, 1), KROW(lane, 1, 1, 0, 1), KROW(lane, 1, 1, 1, 1),
+    // the v-packet log with last interactions (vpacket_last_interaction): v-packets and a tracker -- TRACK, or full tracking
+    KROW(lane, 0, 1, 1, 0, 1), KROW(lane, 1, 1, 1, 0, 1), KROW(lane, 0, 1, 0, 1, 1), KROW(lane, 0, 1, 1, 1, 1), KROW(lane, 1, 1, 0, 1, 1), KROW(lane, 1, 1, 1, 1, 1),
 };
 const KernelRow<GroupKernelKey, GroupKernelFn> GROUP_KERNELS[] = {  // FULL, TRACK, G, BLOCK, OCC, VPK, WIDE
     // (the second half: 64-bit table offsets)
@@ -817,6 +836,8 @@ const KernelRow<GroupKernelKey, GroupKernelFn> GROUP_KERNELS[] = {  // FULL, TRA
     KROW(group, 0, 0, 16, 256, 4, 0, 1), KROW(group, 0, 1, 16, 256, 4, 0, 1), KROW(group, 1, 0, 16, 256, 4, 0, 1), KROW(group, 1, 1, 16, 256, 4, 0, 1),
     KROW(group, 0, 0, 8, 256, 4, 1, 1), KROW(group, 0, 1, 8, 256, 4, 1, 1), KROW(group, 1, 0, 8, 256, 4, 1, 1), KROW(group, 1, 1, 8, 256, 4, 1, 1),
     KROW(group, 0, 0, 16, 256, 4, 1, 1), KROW(group, 0, 1, 16, 256, 4, 1, 1), KROW(group, 1, 0, 16, 256, 4, 1, 1), KROW(group, 1, 1, 16, 256, 4, 1, 1),
+    // the v-packet log with last interactions (vpacket_last_interaction): the tracked v-packet instantiations again
+    KROW(group, 0, 1, 8, 256, 4, 1, 0, 1), KROW(group, 1, 1, 8, 256, 4, 1, 0, 1), KROW(group, 0, 1, 16, 256, 4, 1, 0, 1), KROW(group, 1, 1, 16, 256, 4, 1, 0, 1), KROW(group, 0, 1, 8, 256, 4, 1, 1, 1), KROW(group, 1, 1, 8, 256, 4, 1, 1, 1), KROW(group, 0, 1, 16, 256, 4, 1, 1, 1), KROW(group, 1, 1, 16, 256, 4, 1, 1, 1),
 };
 const KernelRow<WaveKernelKey, WaveKernelFn> WAVE_KERNELS[] = {  // FULL, TRACK, G, VPK, LS, XWALK, WPE, NT, SL, FT, WIDE
     // (XWALK: the instantiations with the macro-atom walks on the fp64 running sums compiled in -- only launched when the compact
@@ -856,6 +877,14 @@ const KernelRow<WaveKernelKey, WaveKernelFn> WAVE_KERNELS[] = {  // FULL, TRACK,
     KROW(wave, 0, 0, 16, 1, 1, 0, 3, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 1, 1, 0, 3, 0, 0, 0, 1), KROW(wave, 0, 0, 16, 0, 1, 0, 3, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 0, 1, 0, 3, 0, 0, 0, 1),
     KROW(wave, 0, 0, 16, 0, 1, 0, 4, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 0, 1, 0, 4, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 0, 0, 0, 4, 0, 0, 1, 1), KROW(wave, 1, 1, 16, 0, 0, 0, 4, 0, 0, 1, 1),
     KROW(wave, 0, 1, 16, 1, 0, 0, 3, 0, 0, 1, 1), KROW(wave, 1, 1, 16, 1, 0, 0, 3, 0, 0, 1, 1),
+    // the v-packet log with last interactions (vpacket_last_interaction): every tracked v-packet instantiation above again, with VLI
+    KROW(wave, 0, 1, 4, 1, 0, 0, 3, 0, 0, 0, 0, 1), KROW(wave, 1, 1, 4, 1, 0, 0, 3, 0, 0, 0, 0, 1), KROW(wave, 0, 1, 8, 1, 0, 0, 3, 0, 0, 0, 0, 1), KROW(wave, 1, 1, 8, 1, 0, 0, 3, 0, 0, 0, 0, 1),
+    KROW(wave, 0, 1, 16, 1, 0, 0, 3, 0, 0, 0, 0, 1), KROW(wave, 1, 1, 16, 1, 0, 0, 3, 0, 0, 0, 0, 1), KROW(wave, 0, 1, 4, 1, 0, 1, 3, 0, 0, 0, 0, 1), KROW(wave, 1, 1, 4, 1, 0, 1, 3, 0, 0, 0, 0, 1),
+    KROW(wave, 0, 1, 8, 1, 0, 1, 3, 0, 0, 0, 0, 1), KROW(wave, 1, 1, 8, 1, 0, 1, 3, 0, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 1, 0, 1, 3, 0, 0, 0, 0, 1), KROW(wave, 1, 1, 16, 1, 0, 1, 3, 0, 0, 0, 0, 1),
+    KROW(wave, 0, 1, 16, 1, 1, 0, 3, 0, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 1, 1, 1, 3, 0, 0, 0, 0, 1), KROW(wave, 0, 1, 8, 1, 0, 0, 2, 0, 0, 0, 0, 1), KROW(wave, 1, 1, 8, 1, 0, 0, 2, 0, 0, 0, 0, 1),
+    KROW(wave, 0, 1, 16, 1, 0, 0, 2, 0, 0, 0, 0, 1), KROW(wave, 1, 1, 16, 1, 0, 0, 2, 0, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 1, 1, 0, 2, 0, 0, 0, 0, 1), KROW(wave, 0, 1, 16, 1, 0, 0, 3, 0, 0, 1, 0, 1),
+    KROW(wave, 1, 1, 16, 1, 0, 0, 3, 0, 0, 1, 0, 1), KROW(wave, 0, 1, 8, 1, 0, 0, 3, 0, 0, 0, 1, 1), KROW(wave, 1, 1, 8, 1, 0, 0, 3, 0, 0, 0, 1, 1), KROW(wave, 0, 1, 16, 1, 0, 0, 3, 0, 0, 0, 1, 1),
+    KROW(wave, 1, 1, 16, 1, 0, 0, 3, 0, 0, 0, 1, 1), KROW(wave, 0, 1, 16, 1, 1, 0, 3, 0, 0, 0, 1, 1), KROW(wave, 0, 1, 16, 1, 0, 0, 3, 0, 0, 1, 1, 1), KROW(wave, 1, 1, 16, 1, 0, 0, 3, 0, 0, 1, 1, 1),
 };
 #undef KROW
 
@@ -870,7 +899,7 @@ size_t wave_kernel_lds(const WaveKernelKey &k, int n_shells)  // dynamic LDS of 
 int launch_lane(TardisMcContext *ctx, const mc::DeviceProblem &P, int blocks, size_t lds)
 {
     const bool ft = P.evlog.rows != nullptr;  // full r-packet tracking: 8 ints of LDS per workgroup for the waves' append state
-    const LaneKernelFn k = find_kernel(LANE_KERNELS, LaneKernelKey{ctx->cfg.enable_full_relativity != 0, ctx->cfg.number_of_vpackets > 0, ctx->track, ft});
+    const LaneKernelFn k = find_kernel(LANE_KERNELS, LaneKernelKey{ctx->cfg.enable_full_relativity != 0, ctx->cfg.number_of_vpackets > 0, ctx->track, ft, vlog_li_call(ctx)});
     if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the lane kernel");
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds + (ft ? 32 : 0), ctx->stream, P);
     HIP_TRY(ctx, hipGetLastError());
@@ -1100,6 +1129,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
     // 64-bit row offsets: the production shapes above without the interleaved sweep table, the shell-sorted log and the two-waves-per-SIMD
     // v-packet form (those keep 32-bit offsets); sweep width 4 runs as 8 (per-packet results do not depend on the width)
     if (w64) { k.wide = true; if (k.width == 4) k.width = 8; }
+    k.vli = vlog_li_call(ctx);
     w.fn = find_kernel(WAVE_KERNELS, k);
     if (!w.fn) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the wave kernel");
     w.lds = wave_kernel_lds(k, ctx->n_shells);
@@ -1829,7 +1859,7 @@ int run_group_kernel(TardisMcContext *ctx, const PropagateCall &call, const mc::
     const size_t lds = G == 8 ? mc::group_kernel_lds_bytes<8, 256>(ctx->n_shells) : mc::group_kernel_lds_bytes<16, 256>(ctx->n_shells);
     if (lds > 160 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
     const int blocks_per_cu = std::max(1, std::min(std::min(ctx->blocks_per_cu, 8), (int)((160 * 1024) / lds)));
-    const GroupKernelFn k = find_kernel(GROUP_KERNELS, GroupKernelKey{call.full, ctx->track, G, block, 4, vpk, call.plan.w64});
+    const GroupKernelFn k = find_kernel(GROUP_KERNELS, GroupKernelKey{call.full, ctx->track, G, block, 4, vpk, call.plan.w64, vlog_li_call(ctx)});
     if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the group kernel");
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, st));
@@ -1974,6 +2004,7 @@ void tardis_mc_destroy(TardisMcContext *ctx)
                      &ctx->block_edge, &ctx->ttype, &ctx->dest, &ctx->tline, &ctx->staging, &ctx->line_block, &ctx->trans_rec, &ctx->bucket_first, &ctx->est, &ctx->grid, &ctx->r0,
                      &ctx->mu0, &ctx->nu0, &ctx->e0, &ctx->seeds, &ctx->out_nu, &ctx->out_e, &ctx->vlog_count,
                      &ctx->vlog_packet, &ctx->vlog_seq, &ctx->vlog_nu, &ctx->vlog_energy, &ctx->vlog_mu, &ctx->vlog_r,
+                     &ctx->vl_counts, &ctx->vl_offsets, &ctx->vl_tiles, &ctx->vl_cols, &ctx->vl_errors,
                      &ctx->dc_work, &ctx->rng_state, &ctx->counters, &ctx->first_error, &ctx->next_packet, &ctx->seeded_states, &ctx->problem_dev};
     for (DevBuf *b : all) b->release();
     for (int b = 0; b < 2; ++b) {
@@ -2035,6 +2066,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "estimator_copies") { ctx->est_copies = std::max(1, std::min(8, (int)value)); ctx->est_valid = false; }
     else if (n == "vpacket_log_capacity") { ctx->vlog_capacity = value; ctx->vlog_capacity_user = value > 0; }
     else if (n == "track_full") ctx->track_full = value != 0;
+    else if (n == "vpacket_last_interaction") ctx->vlog_li = value != 0;
     else if (n == "event_log_capacity") ctx->evlog_capacity = std::max<long long>(0, value);
     else if (n == "event_log_max_bytes") ctx->evlog_max_bytes = std::max<long long>(1LL << 20, value);
     else if (n == "debug_flags") ctx->debug_flags = (int)value;
@@ -2397,6 +2429,7 @@ int tardis_mc_set_config(TardisMcContext *ctx, const TardisMcConfig *c)
     if (c->line_interaction_type < 0 || c->line_interaction_type > 2)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "line_interaction_type must be 0, 1 or 2");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->vl_valid = ctx->vl_consolidated = false;  // (the consolidated v-packet log belongs to the configuration it was written under)
     ctx->cfg = *c;
     ctx->grid_host.assign(c->spectrum_frequency_grid, c->spectrum_frequency_grid + c->n_spectrum_grid);
     ctx->cfg.spectrum_frequency_grid = ctx->grid_host.data();
@@ -2414,6 +2447,7 @@ int tardis_mc_set_packets(TardisMcContext *ctx, const TardisMcPackets *p)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid packets");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->li_valid = false;  // (the resident results are no longer those of the resident packets)
+    ctx->vl_valid = ctx->vl_consolidated = false;
     const size_t P = (size_t)p->n_packets;
     int rc;
     HIP_TRY(ctx, ctx->r0.ensure(P * 8)); HIP_TRY(ctx, ctx->mu0.ensure(P * 8)); HIP_TRY(ctx, ctx->nu0.ensure(P * 8)); HIP_TRY(ctx, ctx->e0.ensure(P * 8));
@@ -2522,6 +2556,7 @@ int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, in
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid packet source arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->li_valid = false;
+    ctx->vl_valid = ctx->vl_consolidated = false;
     const size_t P = (size_t)count;
     int rc = ensure_packet_buffers(ctx, P);
     if (rc) return rc;
@@ -2648,7 +2683,10 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     ctx->ev_valid = false;
     ctx->li_valid = false;
     ctx->sf_valid = false;
+    ctx->vl_valid = ctx->vl_consolidated = false;
     const TardisMcConfig &c = ctx->cfg;
+    if (ctx->vlog_li && c.enable_vpacket_tracking && c.number_of_vpackets > 0 && !ctx->track && !ctx->track_full)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "the option vpacket_last_interaction needs a tracker: track_last_interaction 1 or track_full 1");
     PropagateCall call{};
     call.vpk = c.number_of_vpackets > 0;
     call.full = c.enable_full_relativity != 0;
@@ -2683,7 +2721,8 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         HIP_TRY(ctx, ctx->vlog_nu.ensure(cap * sizeof(double)));
         HIP_TRY(ctx, ctx->vlog_energy.ensure(cap * sizeof(double)));
         HIP_TRY(ctx, ctx->vlog_mu.ensure(cap * sizeof(double)));
-        HIP_TRY(ctx, ctx->vlog_r.ensure(cap * sizeof(double)));
+        // (option vpacket_last_interaction: vlog_r [cap] | before_nu [cap] | ids [cap] x 16 B in one allocation, mc_device.hpp -- what the VLI instantiations write)
+        HIP_TRY(ctx, ctx->vlog_r.ensure(cap * sizeof(double) * (vlog_li_call(ctx) ? 4 : 1)));
     }
     HIP_TRY(ctx, ctx->first_error.ensure(2 * sizeof(long long)));
     // (argument blocks reach the device through store_value(): consecutive propagate calls -- iterations, chunks submitted by
@@ -2729,6 +2768,10 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     }
     ctx->ev_valid = ctx->track_full;  // (a call that failed half-way leaves no event log to read)
     ctx->li_valid = ctx->track;
+    ctx->vl_valid = c.enable_vpacket_tracking && call.vpk && ctx->vlog_capacity > 0;
+    ctx->vl_li = vlog_li_call(ctx);
+    ctx->vl_packets = ctx->n_packets;
+    ctx->vl_capacity = ctx->vlog_capacity;
     return TARDIS_MC_OK;
 }
 
@@ -3113,7 +3156,11 @@ int tardis_mc_decomposition_path(int64_t n_classes, int64_t n_bins, int64_t n_sh
     return decomp::choose_path(n_classes, n_bins, n_shells);
 }
 
-int tardis_mc_packet_decomposition(TardisMcContext *ctx, TardisMcDecomposition *d)
+// The two decompositions share everything but the seven input columns: the resident per-packet results (tardis_mc_packet_decomposition) or
+// the consolidated v-packet log (tardis_mc_vpacket_decomposition, virtual = true; consolidated first where it is not yet).
+static int consolidate_vpacket_log(TardisMcContext *ctx, const char *who);
+
+static int decomposition_impl(TardisMcContext *ctx, TardisMcDecomposition *d, const bool virt)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!d) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "packet decomposition: no argument block");
@@ -3122,11 +3169,15 @@ int tardis_mc_packet_decomposition(TardisMcContext *ctx, TardisMcDecomposition *
     if (d->n_classes < 1 || d->n_classes > 0x7fffffffLL)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "packet decomposition: n_classes must be in [1, 2^31)");
     if (!(d->time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "time_of_simulation must be positive");
-    if (!ctx->have_packets || !ctx->have_opacity || !ctx->have_geometry || !ctx->li_valid)
+    if (virt && (!ctx->have_packets || !ctx->have_opacity || !ctx->have_geometry || !ctx->vl_valid || !ctx->vl_li))
+        return fail(ctx, TARDIS_MC_ERR_STATE, "v-packet decomposition: no v-packet log with last-interaction columns -- it follows a completed "
+                    "tardis_mc_propagate with v-packet tracking and the option vpacket_last_interaction on, before the packets or the configuration are replaced");
+    if (!virt && (!ctx->have_packets || !ctx->have_opacity || !ctx->have_geometry || !ctx->li_valid))
         return fail(ctx, TARDIS_MC_ERR_STATE, "packet decomposition: no last-interaction results of the resident packets -- it follows a completed "
                     "tardis_mc_propagate with track_last_interaction on, before the packets are replaced");
     if (!ctx->have_config || ctx->cfg.n_spectrum_grid < 2) return fail(ctx, TARDIS_MC_ERR_STATE, "packet decomposition needs a spectrum grid");
-    const long long C = d->n_classes, B = ctx->cfg.n_spectrum_grid - 1, S = ctx->n_shells, L = ctx->n_lines, P = ctx->n_packets;
+    const long long C = d->n_classes, B = ctx->cfg.n_spectrum_grid - 1, S = ctx->n_shells, L = ctx->n_lines;
+    long long P = ctx->n_packets;
     // the class table, narrowed to 32 bits; no class is used as an index before it has passed this check
     std::vector<int> cls((size_t)L);
     for (long long i = 0; i < L; ++i) {
@@ -3142,6 +3193,19 @@ int tardis_mc_packet_decomposition(TardisMcContext *ctx, TardisMcDecomposition *
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (fe != 0x7fffffffffffffffLL) return fail(ctx, TARDIS_MC_ERR_STATE, "packet decomposition: packet %lld of the last tardis_mc_propagate failed", fe);
     }
+    bool timing_open = false;  // (a consolidation inside this call is part of its device time)
+    if (virt) {
+        if (!ctx->vl_consolidated) {
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+            timing_open = true;
+            const int rc = consolidate_vpacket_log(ctx, "v-packet decomposition");
+            if (rc) return rc;
+        }
+        if (!ctx->vl_consolidated)
+            return fail(ctx, TARDIS_MC_ERR_STATE, "v-packet decomposition: the v-packet log overflowed (%lld entries, capacity %lld): run the call again with "
+                        "vpacket_log_capacity >= %lld", ctx->vl_count, ctx->vl_capacity, ctx->vl_count);
+        P = ctx->vl_count;
+    }
     // one allocation: cells [(2C+2)B] doubles | shell_packets [(C+1)S] | line_emit [L] | line_absorb [L] | counts [4] | line_class [L] int32
     const size_t n_cells = (size_t)(2 * C + 2) * (size_t)B, n_shell = (size_t)(C + 1) * (size_t)S;
     const size_t n_words = n_cells + n_shell + 2 * (size_t)L + 4;
@@ -3151,13 +3215,20 @@ int tardis_mc_packet_decomposition(TardisMcContext *ctx, TardisMcDecomposition *
                        *counts = line_absorb + L;
     int *d_cls = reinterpret_cast<int *>(counts + 4);
     HIP_TRY(ctx, hipMemcpyAsync(d_cls, cls.data(), (size_t)L * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    if (!timing_open) HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(cells, 0, n_words * 8, ctx->stream));
     if (P > 0) {
         mc::DecompositionArgs a{};
-        a.out_nu = ctx->out_nu.as<double>(); a.out_e = ctx->out_e.as<double>(); a.before_nu = ctx->li_f64[3].as<double>();
-        a.shell_id = ctx->li_i64[0].as<long long>(); a.type = ctx->li_i64[1].as<long long>();
-        a.absorb_id = ctx->li_i64[2].as<long long>(); a.emit_id = ctx->li_i64[3].as<long long>();
+        if (virt) {  // the columns of the consolidated log, vl_cols: source_packet | nu | energy | mu | r | in_nu | in_r | type | in_id | out_id | shell_id
+            double *f = ctx->vl_cols.as<double>();
+            long long *g = ctx->vl_cols.as<long long>();
+            a.out_nu = f + 1 * P; a.out_e = f + 2 * P; a.before_nu = f + 5 * P;
+            a.type = g + 7 * P; a.absorb_id = g + 8 * P; a.emit_id = g + 9 * P; a.shell_id = g + 10 * P;
+        } else {
+            a.out_nu = ctx->out_nu.as<double>(); a.out_e = ctx->out_e.as<double>(); a.before_nu = ctx->li_f64[3].as<double>();
+            a.shell_id = ctx->li_i64[0].as<long long>(); a.type = ctx->li_i64[1].as<long long>();
+            a.absorb_id = ctx->li_i64[2].as<long long>(); a.emit_id = ctx->li_i64[3].as<long long>();
+        }
         a.n_packets = P;
         a.line_class = d_cls; a.n_lines = L; a.n_classes = C;
         a.edges = ctx->grid.as<double>(); a.n_edges = (int)ctx->cfg.n_spectrum_grid; a.n_shells = (int)S;
@@ -3193,6 +3264,98 @@ int tardis_mc_packet_decomposition(TardisMcContext *ctx, TardisMcDecomposition *
     HIP_TRY(ctx, d2h(cnt, counts, sizeof cnt));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     d->n_selected = (int64_t)cnt[0]; d->n_line = (int64_t)cnt[1]; d->n_electron_scatter = (int64_t)cnt[2]; d->n_no_interaction = (int64_t)cnt[3];
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_packet_decomposition(TardisMcContext *ctx, TardisMcDecomposition *d) { return decomposition_impl(ctx, d, false); }
+int tardis_mc_vpacket_decomposition(TardisMcContext *ctx, TardisMcDecomposition *d) { return decomposition_impl(ctx, d, true); }
+
+/* ---- the v-packet log, consolidated on the device (vpacket_log.hpp) ------------------------------------------------------------- */
+// Checks the state, counts, scans and scatters.  On success vl_count holds the entries of the call; vl_consolidated says whether the
+// columns are there (not when the device log overflowed: the caller then reports the count).
+static int consolidate_vpacket_log(TardisMcContext *ctx, const char *who)
+{
+    if (!ctx->vl_valid || !ctx->have_packets || ctx->n_packets != ctx->vl_packets)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "%s: no v-packet log -- it follows a completed tardis_mc_propagate with v-packet tracking, before the "
+                    "packets or the configuration are replaced", who);
+    if (ctx->vl_consolidated) return TARDIS_MC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    long long fe = 0x7fffffffffffffffLL;
+    unsigned long long vcount = 0;
+    if (ctx->first_error.p) HIP_TRY(ctx, hipMemcpyAsync(&fe, ctx->first_error.p, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&vcount, ctx->vlog_count.p, sizeof vcount, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (fe != 0x7fffffffffffffffLL) return fail(ctx, TARDIS_MC_ERR_STATE, "%s: packet %lld of the last tardis_mc_propagate failed", who, fe);
+    ctx->vl_count = (long long)vcount;
+    if (ctx->vl_count > ctx->vl_capacity) return TARDIS_MC_OK;  // overflowed: only the count is known
+    const long long n = ctx->vl_packets, m = ctx->vl_count;
+    const long long tiles = std::max<long long>(1, (n + mc::EV_SCAN_TILE - 1) / mc::EV_SCAN_TILE);
+    const int n_cols = ctx->vl_li ? 11 : 5;
+    HIP_TRY(ctx, ctx->vl_counts.ensure((size_t)std::max<long long>(n, 1) * sizeof(int)));
+    HIP_TRY(ctx, ctx->vl_offsets.ensure((size_t)(n + 1) * sizeof(long long)));
+    HIP_TRY(ctx, ctx->vl_tiles.ensure((size_t)tiles * sizeof(long long)));
+    HIP_TRY(ctx, ctx->vl_errors.ensure(sizeof(unsigned long long)));
+    HIP_TRY(ctx, ctx->vl_cols.ensure((size_t)std::max<long long>(m, 1) * n_cols * 8));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->vl_counts.p, 0, (size_t)std::max<long long>(n, 1) * sizeof(int), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->vl_errors.p, 0, sizeof(unsigned long long), ctx->stream));
+    const int blocks = (int)std::max<long long>(1, std::min<long long>((m + 255) / 256, 65536));
+    long long *offsets = ctx->vl_offsets.as<long long>();
+    unsigned long long *errors = ctx->vl_errors.as<unsigned long long>();
+    if (m > 0) hipLaunchKernelGGL(mc::vpacket_log_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->vlog_packet.as<long long>(), m, n, ctx->vl_counts.as<int>(), errors);
+    hipLaunchKernelGGL(mc::event_scan_tiles_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->vl_counts.as<int>(), n, ctx->vl_tiles.as<long long>());
+    hipLaunchKernelGGL(mc::event_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->vl_tiles.as<long long>(), tiles, offsets, n);
+    hipLaunchKernelGGL(mc::event_scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->vl_counts.as<int>(), n, ctx->vl_tiles.as<long long>(), offsets);
+    if (m > 0) {
+        mc::VpacketLogRaw raw{ctx->vlog_packet.as<long long>(), ctx->vlog_seq.as<int>(), ctx->vlog_nu.as<double>(), ctx->vlog_energy.as<double>(),
+                              ctx->vlog_mu.as<double>(), ctx->vlog_r.as<double>(), ctx->vl_li ? mc::vlog_last_ids(ctx->vlog_r.as<double>(), ctx->vl_capacity) : nullptr,
+                              ctx->vl_li ? mc::vlog_last_nu(ctx->vlog_r.as<double>(), ctx->vl_capacity) : nullptr};
+        double *f = ctx->vl_cols.as<double>();
+        long long *g = ctx->vl_cols.as<long long>();
+        mc::VpacketLogColumns col{g, f + m, f + 2 * m, f + 3 * m, f + 4 * m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (ctx->vl_li) { col.li_in_nu = f + 5 * m; col.li_in_r = f + 6 * m; col.li_type = g + 7 * m; col.li_in_id = g + 8 * m; col.li_out_id = g + 9 * m; col.li_shell_id = g + 10 * m; }
+        hipLaunchKernelGGL(mc::vpacket_log_scatter_kernel, dim3(blocks), dim3(256), 0, ctx->stream, raw, m, n, m, ctx->vl_counts.as<int>(), offsets, col, errors);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long bad = 0;
+    long long total = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, errors, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&total, offsets + n, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad != 0 || total != m)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "%s: the v-packet log is inconsistent (%llu entries with a packet, an ordinal or a position out of range; %lld of %lld "
+                    "entries counted)", who, bad, total, m);
+    ctx->vl_consolidated = true;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_vpacket_log(TardisMcContext *ctx, TardisMcVpacketLog *log)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!log) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "v-packet log: no argument block");
+    log->count = 0;
+    void *li_dst[6] = {log->last_interaction_in_nu, log->last_interaction_in_r, log->last_interaction_type, log->last_interaction_in_id,
+                       log->last_interaction_out_id, log->last_interaction_shell_id};
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = consolidate_vpacket_log(ctx, "v-packet log");  // (the timers of the propagate call stay as they are)
+    if (rc) return rc;
+    if (!ctx->vl_li)
+        for (void *q : li_dst)
+            if (q) return fail(ctx, TARDIS_MC_ERR_STATE, "v-packet log: the last tardis_mc_propagate ran without the option vpacket_last_interaction, the six "
+                               "last_interaction_* columns must be NULL");
+    const long long m = ctx->vl_count, n = ctx->vl_packets;
+    log->count = m;
+    if (!ctx->vl_consolidated || m > log->capacity) return TARDIS_MC_OK;  // overflow: only the count (run again with vpacket_log_capacity >= count)
+    auto d2h = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+        if (!dst || !bytes) return hipSuccess;
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    };
+    HIP_TRY(ctx, d2h(log->offsets, ctx->vl_offsets.p, (size_t)(n + 1) * 8));
+    const char *cols = static_cast<const char *>(ctx->vl_cols.p);
+    void *dst[5] = {log->source_packet, log->nus, log->energies, log->initial_mus, log->initial_rs};
+    for (int k = 0; k < 5; ++k) HIP_TRY(ctx, d2h(dst[k], cols + (size_t)k * m * 8, (size_t)m * 8));
+    if (ctx->vl_li)
+        for (int k = 0; k < 6; ++k) HIP_TRY(ctx, d2h(li_dst[k], cols + (size_t)(5 + k) * m * 8, (size_t)m * 8));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TARDIS_MC_OK;
 }
 

@@ -27,6 +27,15 @@ class EventLogOverflow(RuntimeError):
         self.rows_needed, self.dropped = int(rows_needed), int(dropped)
 
 
+class VPacketLogOverflow(RuntimeError):
+    """The device v-packet log was too small for the last call: entries were dropped.  ``entries_needed`` is the capacity (option
+    ``vpacket_log_capacity``) with which a re-run of the same call keeps every entry."""
+
+    def __init__(self, entries_needed: int):
+        super().__init__(f"v-packet log overflow: re-run with vpacket_log_capacity={entries_needed}")
+        self.entries_needed = int(entries_needed)
+
+
 class Engine:
     def __init__(self, device_id: int = 0):
         self._L = _lib.lib()
@@ -188,6 +197,34 @@ class Engine:
         self._check(self._L.tardis_mc_get_event_log(self._h, C.byref(log)), "get_event_log")
         return st.FullTrackers(offsets, cols)
 
+    def get_vpacket_log(self) -> st.VPacketCollection:
+        """The v-packet log of the last propagate() (ENABLE_VPACKET_TRACKING), consolidated on the device (`tardis_mc_get_vpacket_log`): a
+        ``state.VPacketCollection`` in packet order, then spawn order, plus ``offsets`` ([n_packets + 1]: packet p's entries are
+        [offsets[p], offsets[p + 1])) and ``source_packet``.  After a call with the option ``vpacket_last_interaction`` the six
+        ``last_interaction_*`` fields hold the spawning r-packet's last interaction (launch volley: -1 / NaN), otherwise the reference's
+        -99 placeholders.  Raises ``VPacketLogOverflow`` when the device log dropped entries."""
+        probe = _abi.TardisMcVpacketLog()
+        self._check(self._L.tardis_mc_get_vpacket_log(self._h, C.byref(probe)), "get_vpacket_log")
+        n = int(probe.count)
+        vt = st.VPacketCollection(-1, None, None, None, self._n_v, n)
+        vt.offsets = np.zeros(self.n_packets + 1, dtype=np.int64)
+        vt.source_packet = np.empty(n, dtype=np.int64)
+        log = _abi.TardisMcVpacketLog()
+        log.capacity = n
+        log.offsets, log.source_packet = _abi._ip(vt.offsets), _abi._ip(vt.source_packet)
+        f64, i64 = _abi._VL_F64, _abi._VL_I64
+        if not self.options.get("vpacket_last_interaction", 0):
+            f64, i64 = f64[:4], ()
+        for f in f64:
+            setattr(log, f, _abi._dp(getattr(vt, f)))
+        for f in i64:
+            setattr(log, f, _abi._ip(getattr(vt, f)))
+        vt.offsets[-1] = -1  # (the library writes no column when the device log overflowed)
+        self._check(self._L.tardis_mc_get_vpacket_log(self._h, C.byref(log)), "get_vpacket_log")
+        if vt.offsets[-1] != n:
+            raise VPacketLogOverflow(n)
+        return vt
+
     def get_results(self, output_nus=None, output_energies=None, track_last_interaction=True,
                     want_line_estimators=True, vpacket_log_capacity=None, want_packet_outputs=True, trackers=None,
                     track_full=False) -> _abi.ResultBuffers:
@@ -309,7 +346,7 @@ class Engine:
                 "emitted_luminosity": le.value, "reabsorbed_luminosity": lr.value}
 
     def packet_decomposition(self, time_of_simulation: float, line_class, n_classes: int | None = None, nu_start: float = 0.0,
-                             nu_end: float = float("inf")) -> dict:
+                             nu_end: float = float("inf"), *, _virtual: bool = False) -> dict:
         """The emitted spectrum decomposed by last interaction, reduced on the device from the per-packet results of the last
         propagate() (`tardis_mc_packet_decomposition`; it must have run with track_last_interaction on): what SDEC, the
         last-interaction-velocity histogram and LastLineInteraction compute from the tracker's dataframe.  ``line_class``: [n_lines]
@@ -335,10 +372,20 @@ class Engine:
             setattr(d, k, _abi._dp(out[k]))
         for k in ("shell_packets", "line_emit_packets", "line_absorb_packets"):
             setattr(d, k, _abi._ip(out[k]))
-        self._check(self._L.tardis_mc_packet_decomposition(self._h, C.byref(d)), "packet_decomposition")
+        if _virtual:
+            self._check(self._L.tardis_mc_vpacket_decomposition(self._h, C.byref(d)), "vpacket_decomposition")
+        else:
+            self._check(self._L.tardis_mc_packet_decomposition(self._h, C.byref(d)), "packet_decomposition")
         for k in ("n_selected", "n_line", "n_electron_scatter", "n_no_interaction"):
             out[k] = int(getattr(d, k))
         return out
+
+    def vpacket_decomposition(self, time_of_simulation: float, line_class, n_classes: int | None = None, nu_start: float = 0.0,
+                              nu_end: float = float("inf")) -> dict:
+        """packet_decomposition() of the VIRTUAL spectrum (SDEC / LIV with ``packets_mode="virtual"``), reduced on the device from the
+        consolidated v-packet log of the last propagate() (`tardis_mc_vpacket_decomposition`; the call must have run with v-packet
+        tracking and the option ``vpacket_last_interaction``).  Same arguments, same dict; no per-v-packet array leaves the device."""
+        return self.packet_decomposition(time_of_simulation, line_class, n_classes, nu_start, nu_end, _virtual=True)
 
     @staticmethod
     def decomposition_path(n_classes: int, n_bins: int, n_shells: int) -> str:

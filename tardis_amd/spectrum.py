@@ -91,6 +91,18 @@ def packet_decomposition(output_nus, output_energies, time_of_simulation, spectr
     return out
 
 
+def vpacket_decomposition(vpacket_nus, vpacket_energies, time_of_simulation, spectrum_frequency_grid, last_interaction_type,
+                          last_interaction_out_id, last_interaction_in_id, last_interaction_in_nu, last_interaction_shell_id, line_class,
+                          n_shells, n_classes=None, nu_start=0.0, nu_end=np.inf):
+    """The VIRTUAL spectrum decomposed by last interaction on the host (SDEC / LIV with ``packets_mode="virtual"``), with the
+    definitions of ``tardis_mc_vpacket_decomposition`` and the dict of ``Engine.vpacket_decomposition``: ``packet_decomposition`` on the
+    columns of a v-packet log with last-interaction columns -- one entry per v-packet, its frequency and energy as outputs (never
+    negative; a v-packet the roulette dropped adds 0.0 and still counts), the emitting line ``out_id``, the absorbing line ``in_id``."""
+    return packet_decomposition(vpacket_nus, vpacket_energies, time_of_simulation, spectrum_frequency_grid, last_interaction_type,
+                                last_interaction_out_id, last_interaction_in_id, last_interaction_in_nu, last_interaction_shell_id,
+                                line_class, n_shells, n_classes, nu_start, nu_end)
+
+
 def calculate_filtered_luminosity(packet_nu, packet_luminosity, luminosity_nu_start=0.0, luminosity_nu_end=np.inf):
     """tardis/spectrum/luminosity.py:5-30 on plain arrays."""
     f = (packet_nu > luminosity_nu_start) & (packet_nu < luminosity_nu_end)

@@ -166,7 +166,7 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
                                        opacity_state_numba, montecarlo_configuration, spectrum_frequency_grid,
                                        trackers, number_of_vpackets: int, show_progress_bars: bool = False,
                                        packet_propagation_function=None, *, engine: Engine | None = None,
-                                       track_full: bool = False):
+                                       track_full: bool = False, track_vpacket_last_interaction: bool = False):
     """Run the classic (line + electron scattering) Monte Carlo transport on the GPU.
 
     Returns ``(v_packets_energy_hist, vpacket_tracker, estimators_bulk, estimators_line)`` and mutates
@@ -176,6 +176,9 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
     Full r-packet tracking: ``trackers`` a list of the reference's ``TrackerFull`` objects (enable_rpacket_tracking) are filled
     with every event of their packet; ``track_full=True`` records the same log beside last-interaction trackers.  Either way the
     log is left in ``montecarlo_transport_with_vpackets.last_event_log`` (``state.FullTrackers``).
+    ``track_vpacket_last_interaction=True`` (with ENABLE_VPACKET_TRACKING, v-packets and trackers): the six ``last_interaction_*``
+    fields of the returned VPacketCollection hold the spawning r-packet's last interaction instead of the reference's -99
+    placeholders, and it carries ``offsets`` / ``source_packet`` (``Engine.get_vpacket_log``).
     """
     if packet_propagation_function is not None:
         name = getattr(packet_propagation_function, "__name__", "")
@@ -192,11 +195,15 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
     track = trackers is not None and not full
     eng.set_option("track_last_interaction", int(track))
     eng.set_option("track_full", int(track_full))
+    cfg = montecarlo_configuration
+    vlog_li = bool(track_vpacket_last_interaction) and bool(cfg.ENABLE_VPACKET_TRACKING) and number_of_vpackets > 0
+    if vlog_li:
+        eng.set_option("vpacket_last_interaction", 1)
     eng.set_packets(packet_collection)
     out_nus, out_en = packet_collection.output_nus, packet_collection.output_energies
     in_place = all(isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous for a in (out_nus, out_en))
     vlog_capacity = evlog_capacity = None
-    event_log = None
+    event_log = vpacket_log = None
     progress = _PacketProgress(eng, show_progress_bars)  # (one bar per call, whatever the number of attempts)
     try:
         for _attempt in range(3):
@@ -215,6 +222,8 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
                 vlog_capacity = res.vpacket_log_count
                 eng.set_option("vpacket_log_capacity", vlog_capacity)
                 retry = True
+            elif vlog_li:  # (the consolidated log of the same call: it fits whenever the one above did)
+                vpacket_log = eng.get_vpacket_log()
             if track_full:
                 try:
                     event_log = eng.get_event_log()
@@ -235,6 +244,8 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
             eng.set_option("event_log_capacity", 0)
         if track_full:
             eng.set_option("track_full", 0)
+        if vlog_li:
+            eng.set_option("vpacket_last_interaction", 0)
     if not in_place:
         packet_collection.output_nus[:] = res.output_nus
         packet_collection.output_energies[:] = res.output_energies
@@ -250,8 +261,13 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
             _fill_trackers(trackers, res.trackers)
     estimators_bulk = st.EstimatorsBulk(res.j_estimator, res.nu_bar_estimator)
     estimators_line = st.EstimatorsLine(res.j_blue_estimator, res.edotlu_estimator)
-    cfg = montecarlo_configuration
-    if cfg.ENABLE_VPACKET_TRACKING and number_of_vpackets > 0:
+    if vlog_li:
+        vt = vpacket_log
+        vt.spectrum_frequency_grid = spectrum_frequency_grid
+        vt.v_packet_spawn_start_frequency = cfg.VPACKET_SPAWN_START_FREQUENCY
+        vt.v_packet_spawn_end_frequency = cfg.VPACKET_SPAWN_END_FREQUENCY
+        vt.number_of_vpackets = -1
+    elif cfg.ENABLE_VPACKET_TRACKING and number_of_vpackets > 0:
         n = min(res.vpacket_log_count, len(res.vpacket_nus))
         vt = st.VPacketCollection(-1, spectrum_frequency_grid, cfg.VPACKET_SPAWN_START_FREQUENCY,
                                   cfg.VPACKET_SPAWN_END_FREQUENCY, -1, n)
@@ -419,6 +435,19 @@ class MonteCarloTransportState:
         return spectrum.packet_decomposition(self.output_nu, self.output_energy, self.time_of_simulation, spectrum_frequency_grid,
                                              t.interaction_type, t.interaction_line_emit_id, t.interaction_line_absorb_id, t.before_nu,
                                              t.shell_id, line_class, len(self.geometry_state_numba.r_inner), n_classes, nu_start, nu_end)
+
+    def vpacket_decomposition(self, spectrum_frequency_grid, line_class, n_classes=None, nu_start=0.0, nu_end=float("inf")):
+        """packet_decomposition() of the VIRTUAL spectrum (SDEC / LIV with ``packets_mode="virtual"``), from the v-packet log of a run
+        with ``track_vpacket_last_interaction`` (``spectrum.vpacket_decomposition`` on ``vpacket_tracker``; the engine that ran the call
+        gives the same from its resident log, ``Engine.vpacket_decomposition``)."""
+        from . import spectrum
+        vt = self.vpacket_tracker
+        if vt is None or not len(vt.last_interaction_type) or np.any(vt.last_interaction_type == -99):
+            raise RuntimeError("vpacket_decomposition() needs a run with v-packet tracking and track_vpacket_last_interaction")
+        return spectrum.vpacket_decomposition(vt.nus, vt.energies, self.time_of_simulation, spectrum_frequency_grid, vt.last_interaction_type,
+                                              vt.last_interaction_out_id, vt.last_interaction_in_id, vt.last_interaction_in_nu,
+                                              vt.last_interaction_shell_id, line_class, len(self.geometry_state_numba.r_inner), n_classes,
+                                              nu_start, nu_end)
 
     def radiation_field(self, volume, w_epsilon=1e-10, detailed_optical_window=False, want_j_blues=True):
         """MCRadiationFieldPropertiesSolver.solve (estimators/mc_rad_field_solver.py:37-144) on the engine's resident (after
