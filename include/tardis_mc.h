@@ -469,6 +469,82 @@ int tardis_mc_interpolated_source(TardisMcContext *ctx, int64_t interpolate_shel
                                   double *electron_density_i, double *tau_sobolev_i, double *att_S_ul_i, double *Jred_lu_i,
                                   double *Jblue_lu_i, double *e_dot_u_i);
 
+/* ---- producer of the next iteration's opacity state: tau_sobolev and the transition probabilities from level populations ----
+ * What the legacy plasma's StimulatedEmissionFactor, TauSobolev, BetaSobolev, JBluesDiluteBlackBody and
+ * calculate_transition_probabilities compute between two iterations, on the device and in their operation order (fp64, no
+ * contraction, exp as the transport evaluates it).  The atomic data are set once per topology (tardis_mc_set_line_data); every iteration
+ * then uploads the populations [K,S] instead of tau_sobolev [L,S] and the probabilities [T,S].  Per line l and shell s, with
+ * n_l = n[level_lower[l]][s], n_u = n[level_upper[l]][s]:
+ *   sef  = 1.0 - (g_lower[l] n_u) / (g_upper[l] n_l);  0.0 where n_l == 0.0 and where the result is negative (the NLTE exception that
+ *          keeps inversions is not part of this)
+ *   tau  = ((((sobolev_coefficient f_lu[l]) wavelength_cm[l]) time_explosion) n_l) sef
+ *   beta = 1.0 / tau where tau > 1e3;  1.0 - 0.5 tau where tau < 1e-4;  (1.0 - exp(-tau)) / tau otherwise
+ *   j    = j_blues_mode 0, dilute black body: dilution_factor[s] (2h/c^2 nu^3 / (exp(h nu / (k_B t_radiative[s])) - 1)), the expression
+ *          and constants of tardis_mc_radiation_field;  j_blues_mode 1, detailed: bit for bit the j_blues tardis_mc_radiation_field
+ *          returns for the same (time_of_simulation, volume, w_epsilon, detailed_optical_window), from the resident estimators
+ * and per transition row t of block b, with line = transition_line_id[t]:
+ *   p = transition_probability_coef[t] beta[line][s];  for transition_type[t] == 1: p = p (sef[line][s] j[line][s]);
+ *   the result is p / norm, norm the serial left-to-right sum of the block's p from 0.0;  0.0 where norm == 0.0.
+ * No atomics anywhere: two calls give identical bits.
+ *
+ * TardisMcLineData: n_lines, n_transitions must equal the resident topology; n_levels = K, the rows of level_number_density.
+ * level_lower / level_upper index those rows.  transition_probability_coef is NULL in scatter mode (no macro-atom tables): only tau,
+ * beta, sef and j are then computed, the resident probabilities stay as they are. */
+typedef struct TardisMcLineData {
+    int64_t n_lines;                            /* L */
+    int64_t n_transitions;                      /* T */
+    int64_t n_levels;                           /* K */
+    const double *f_lu;                         /* [L] */
+    const double *wavelength_cm;                /* [L] */
+    const double *g_lower;                      /* [L] statistical weight of the lower level */
+    const double *g_upper;                      /* [L] ... of the upper level */
+    const int64_t *level_lower;                 /* [L] in [0, K) */
+    const int64_t *level_upper;                 /* [L] in [0, K) */
+    const double *transition_probability_coef;  /* [T], or NULL (scatter mode) */
+    double sobolev_coefficient;                 /* the plasma's constant: no constant is duplicated here */
+} TardisMcLineData;
+
+typedef struct TardisMcOpacityUpdate {
+    const double *level_number_density;         /* [K,S] */
+    const double *electron_density;             /* [S], or NULL to keep the resident values */
+    int32_t j_blues_mode;                       /* 0 dilute black body, 1 detailed */
+    const double *t_radiative;                  /* [S], mode 0 */
+    const double *dilution_factor;              /* [S], mode 0 */
+    double time_of_simulation;                  /* mode 1, as tardis_mc_radiation_field takes them */
+    const double *volume;                       /* [S], mode 1 */
+    double w_epsilon;                           /* mode 1 */
+    int32_t detailed_optical_window;            /* mode 1 */
+} TardisMcOpacityUpdate;
+
+/* Static line data of the resident topology; after tardis_mc_set_opacity, which drops them (a later set_opacity: call this again).
+ * Everything is checked on the host before anything is indexed: TARDIS_MC_ERR_INVALID_ARGUMENT when n_lines / n_transitions differ
+ * from the resident tables, when a level index is outside [0, K), when ANY row's transition_line_id is outside [0, L) (set_opacity
+ * checks only the emission rows), or when coefficients are given although no macro-atom tables are resident;
+ * TARDIS_MC_ERR_UNSUPPORTED for a transition type outside {-1, 0, 1}; TARDIS_MC_ERR_STATE before set_opacity. */
+int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *line_data);
+/* One iteration's update: uploads the populations (and electron densities), rewrites tau_sobolev in place, computes beta, sef, j
+ * ([S][L] each, resident until the next update or set_opacity) and the probabilities, and derives from those every table that
+ * tardis_mc_set_opacity derives -- afterwards the context is indistinguishable from a fresh one given the same tau_sobolev and
+ * probabilities through tardis_mc_set_opacity.  The geometry's time_explosion is the one resident at the call.  Estimators and packets
+ * stay valid; the resident source function is invalidated, exactly as set_opacity does.  TARDIS_MC_ERR_STATE without line data, without
+ * geometry, and in mode 1 without propagated estimators (multi-GPU: call it after tardis_mc_allreduce_estimators);
+ * TARDIS_MC_ERR_INVALID_ARGUMENT for an unknown mode or a missing array of the mode.  tardis_mc_last_propagate_ms then reports the
+ * device time of the call's kernels. */
+int tardis_mc_update_opacity(TardisMcContext *ctx, const TardisMcOpacityUpdate *update);
+/* Device time of the stages of the last tardis_mc_update_opacity, in ms (any pointer may be NULL): the transpose of the populations, the
+ * j_blues of mode 1 and the line kernel | the block kernels | the derived tables (with the host work between their kernels).  Their sum
+ * is what tardis_mc_last_propagate_ms reports after the update.  TARDIS_MC_ERR_STATE before the first update. */
+int tardis_mc_last_opacity_update_ms(TardisMcContext *ctx, double *out_line_ms, double *out_block_ms, double *out_derive_ms);
+/* Downloads the resident opacity state, line-major as tardis_mc_set_opacity takes it: tau_sobolev, beta_sobolev,
+ * stimulated_emission_factor, j_blues [L,S]; transition_probabilities [T,S].  Any pointer may be NULL.  The last three return
+ * TARDIS_MC_ERR_STATE unless a tardis_mc_update_opacity produced them since the last set_opacity. */
+int tardis_mc_get_opacity(TardisMcContext *ctx, double *tau_sobolev, double *transition_probabilities, double *beta_sobolev,
+                          double *stimulated_emission_factor, double *j_blues);
+/* Which form of the update's block kernel a macro-atom block of `rows` transition rows takes (csrc/opacity_update_plan.hpp): 0 a lane per
+ * (block, shell), 1 a 16-lane row per (block, shell).  Host only; both forms add in the same order.  Option "opacity_update_long_rows"
+ * (tardis_mc_set_option; -1, the default: this rule; n >= 0: blocks of n rows or more take the row form -- measurements only). */
+int tardis_mc_opacity_update_path(int64_t rows);
+
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the
  * last call ran without full tracking, when a packet of it failed, or when the resident packets were replaced since.  With dropped > 0 only count / dropped / offsets are written: run the call again with

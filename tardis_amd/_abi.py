@@ -78,6 +78,41 @@ class TardisMcOpacity(C.Structure):
     ]
 
 
+class TardisMcLineData(C.Structure):
+    """Static line data of the opacity update (tardis_mc_set_line_data)."""
+    _fields_ = [
+        ("n_lines", C.c_int64),
+        ("n_transitions", C.c_int64),
+        ("n_levels", C.c_int64),
+        ("f_lu", _pd),
+        ("wavelength_cm", _pd),
+        ("g_lower", _pd),
+        ("g_upper", _pd),
+        ("level_lower", _pi),
+        ("level_upper", _pi),
+        ("transition_probability_coef", _pd),
+        ("sobolev_coefficient", C.c_double),
+    ]
+
+
+class TardisMcOpacityUpdate(C.Structure):
+    """One iteration's inputs of tardis_mc_update_opacity."""
+    _fields_ = [
+        ("level_number_density", _pd),
+        ("electron_density", _pd),
+        ("j_blues_mode", C.c_int32),
+        ("t_radiative", _pd),
+        ("dilution_factor", _pd),
+        ("time_of_simulation", C.c_double),
+        ("volume", _pd),
+        ("w_epsilon", C.c_double),
+        ("detailed_optical_window", C.c_int32),
+    ]
+
+
+J_BLUES_DILUTE_BLACKBODY, J_BLUES_DETAILED = 0, 1
+
+
 _LI_F64 = ("li_radius", "li_nu", "li_energy", "li_before_nu", "li_before_mu", "li_before_energy", "li_after_nu",
            "li_after_mu", "li_after_energy")
 _LI_I64 = ("li_shell_id", "li_interaction_type", "li_line_absorb_id", "li_line_emit_id", "li_interactions_count")
@@ -197,6 +232,53 @@ def marshal_opacity(op) -> Marshalled:
     s = TardisMcOpacity(L, S, T, len(edge), _dp(ne), _dp(nu), _dp(tau), _dp(prob), _ip(l2m), _ip(edge), _ip(ttype),
                         _ip(dest), _ip(tline))
     return Marshalled(s, [ne, nu, tau, prob, l2m, edge, ttype, dest, tline])
+
+
+def marshal_line_data(ld, n_transitions) -> Marshalled:
+    """ld: an object with f_lu, wavelength_cm, g_lower, g_upper, level_lower, level_upper, n_levels, sobolev_coefficient and
+    transition_probability_coef (None in scatter mode), e.g. synthetic.LineData."""
+    f = [np.ascontiguousarray(getattr(ld, n), dtype=np.float64) for n in ("f_lu", "wavelength_cm", "g_lower", "g_upper")]
+    lv = [np.ascontiguousarray(getattr(ld, n), dtype=np.int64) for n in ("level_lower", "level_upper")]
+    L = len(f[0])
+    if not all(len(a) == L for a in f + lv):
+        raise ValueError("line data arrays must have n_lines entries")
+    coef = ld.transition_probability_coef
+    keep = f + lv
+    s = TardisMcLineData(L, int(n_transitions), int(ld.n_levels), _dp(f[0]), _dp(f[1]), _dp(f[2]), _dp(f[3]), _ip(lv[0]), _ip(lv[1]),
+                         None, float(ld.sobolev_coefficient))
+    if coef is not None:
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if len(coef) != int(n_transitions):
+            raise ValueError("transition_probability_coef must have n_transitions entries")
+        s.transition_probability_coef = _dp(coef)
+        keep.append(coef)
+    return Marshalled(s, keep)
+
+
+def marshal_opacity_update(level_number_density, n_shells, electron_density=None, j_blues_mode=J_BLUES_DILUTE_BLACKBODY, t_radiative=None,
+                           dilution_factor=None, time_of_simulation=0.0, volume=None, w_epsilon=0.0,
+                           detailed_optical_window=False) -> Marshalled:
+    S = int(n_shells)
+    n = np.ascontiguousarray(level_number_density, dtype=np.float64)
+    if n.ndim != 2 or n.shape[1] != S:
+        raise ValueError("level_number_density must be [n_levels, n_shells]")
+    s = TardisMcOpacityUpdate()
+    s.level_number_density = _dp(n)
+    s.j_blues_mode = int(j_blues_mode)
+    s.time_of_simulation = float(time_of_simulation)
+    s.w_epsilon = float(w_epsilon)
+    s.detailed_optical_window = int(bool(detailed_optical_window))
+    keep = [n]
+    for name, value in (("electron_density", electron_density), ("t_radiative", t_radiative), ("dilution_factor", dilution_factor),
+                        ("volume", volume)):
+        if value is None:
+            continue
+        a = np.ascontiguousarray(value, dtype=np.float64)
+        if a.shape != (S,):
+            raise ValueError(f"{name} must have n_shells entries")
+        setattr(s, name, _dp(a))
+        keep.append(a)
+    return Marshalled(s, keep)
 
 
 def marshal_config(cfg, spectrum_frequency_grid, number_of_vpackets=None, sigma_thomson=None) -> Marshalled:

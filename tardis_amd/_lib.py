@@ -56,6 +56,11 @@ SYMBOLS = {
     "tardis_mc_formal_integral_resident": (_i, [_vp, C.c_double, _vp, C.c_int64, C.c_int64, _vp, _vp]),
     "tardis_mc_formal_integral_interpolated": (_i, [_vp, C.c_int64, C.c_double, _vp, C.c_int64, C.c_int64, _vp, _vp]),
     "tardis_mc_interpolated_source": (_i, [_vp, C.c_int64] + [_vp] * 8),
+    "tardis_mc_set_line_data": (_i, [_vp, _vp]),
+    "tardis_mc_update_opacity": (_i, [_vp, _vp]),
+    "tardis_mc_get_opacity": (_i, [_vp] * 6),
+    "tardis_mc_last_opacity_update_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 3),
+    "tardis_mc_opacity_update_path": (_i, [C.c_int64]),
     "tardis_mc_get_event_log": (_i, [_vp, _vp]),
     "tardis_mc_get_vpacket_log": (_i, [_vp, _vp]),
     "tardis_mc_stream_results": (_i, [_vp, _vp]),

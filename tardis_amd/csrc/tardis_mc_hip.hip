@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <numeric>
 #include <atomic>
 #include <mutex>
@@ -36,6 +37,8 @@
 #include "packet_decomposition.hpp"
 #include "decomposition_plan.hpp"
 #include "vpacket_log.hpp"
+#include "opacity_update.hpp"
+#include "opacity_update_plan.hpp"
 
 static_assert(plan::DBG_WAVE_COUNTERS == mc::WV_DBG_FLAGS, "propagate_plan.hpp repeats the wave kernel's list of counter flags");
 
@@ -175,6 +178,7 @@ struct TardisMcContext {
     size_t est_S = 0, est_L = 0, est_G = 0;
     int est_copies = 1;
     bool est_valid = false;
+    bool est_propagated = false;  // a propagate call has added to the estimators since they were last zeroed (the detailed mode of tardis_mc_update_opacity)
     // config
     TardisMcConfig cfg{};
     std::vector<double> grid_host;
@@ -311,6 +315,21 @@ struct TardisMcContext {
     double *sf_conv_host = nullptr;            // pinned: {max |dx|, max |x|} per shell
     long long source_max_iterations = 20000;   // option: bound on the iterations of a solve
     int last_source_iterations = -1;
+    // Opacity update (opacity_update.hpp).  Per set_opacity: host copies of the five index tables (line2macro_level_upper, macro_block_edge_index,
+    // transition_type, destination_level_id, transition_line_id; int32, the staging vectors of their upload) and of the line list, from which
+    // derive_opacity_tables builds every table that depends on the probabilities, with or without the caller's pointers.  Per set_line_data: the static
+    // line data and the list of the blocks that take the row form.  Per update_opacity: n_t[S][K], the [S] inputs, beta_t / sef_t / j_t [S][L].
+    std::vector<int> h_idx[5];
+    std::vector<double> h_nu;
+    bool h_macro = false;
+    DevBuf ou_f_lu, ou_wave, ou_g_lower, ou_g_upper, ou_level_lower, ou_level_upper, ou_coef, ou_long_blocks;
+    DevBuf ou_n_t, ou_shell, ou_beta_t, ou_sef_t, ou_j_t;
+    bool have_line_data = false, ou_have_coef = false, ou_valid = false;  // (ou_valid: beta_t / sef_t / j_t belong to the resident tau_t / prob_t)
+    long long ou_levels = 0, ou_n_long = 0, ou_long_rows_built = -1;
+    long long ou_long_rows = -1;  // option opacity_update_long_rows: -1 the rule of opacity_update_plan.hpp, else the threshold itself
+    double ou_sobolev_coefficient = 0.0;
+    hipEvent_t ev_ou[4] = {nullptr, nullptr, nullptr, nullptr};  // start | behind the line kernel | behind the block kernels | end of the last update (tardis_mc_last_opacity_update_ms)
+    bool ou_timed = false;
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -663,6 +682,7 @@ int ensure_estimators(TardisMcContext *ctx)
     HIP_TRY(ctx, hipMemsetAsync(ctx->est.p, 0, e.total * sizeof(double), ctx->stream));
     ctx->est_S = S; ctx->est_L = L; ctx->est_G = G;
     ctx->est_valid = true;
+    ctx->est_propagated = false;
     return TARDIS_MC_OK;
 }
 
@@ -2023,6 +2043,10 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     ctx->lane_save.release(); ctx->wave_save.release(); ctx->suspended_dev.release();
     for (int k = 0; k < 2; ++k) { ctx->lane_save_c[k].release(); ctx->wave_save_c[k].release(); ctx->seeded_states_c[k].release(); }
     ctx->drain_census.release();
+    for (hipEvent_t e : ctx->ev_ou) if (e) (void)hipEventDestroy(e);
+    for (DevBuf *b : {&ctx->ou_f_lu, &ctx->ou_wave, &ctx->ou_g_lower, &ctx->ou_g_upper, &ctx->ou_level_lower, &ctx->ou_level_upper, &ctx->ou_coef,
+                      &ctx->ou_long_blocks, &ctx->ou_n_t, &ctx->ou_shell, &ctx->ou_beta_t, &ctx->ou_sef_t, &ctx->ou_j_t})
+        b->release();
     ctx->vq_req.release(); ctx->vq_items.release(); ctx->vq_count.release(); ctx->vq_jsave.release();
     if (ctx->suspended_host) (void)hipHostFree(ctx->suspended_host);
     for (hipEvent_t e : ctx->ev_post) if (e) (void)hipEventDestroy(e);
@@ -2115,6 +2139,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "log_sets") ctx->log_sets = (value == 1 || value == 2) ? (int)value : 0;  // 1: the estimator passes of an epoch run before the next epoch, not beside it; 0: automatic
     else if (n == "source_max_iterations") ctx->source_max_iterations = std::max<long long>(1, value);
     else if (n == "chunk_packets") ctx->chunk_packets = std::max<long long>(1024, value);
+    else if (n == "opacity_update_long_rows") ctx->ou_long_rows = value < 0 ? -1 : value;
     else return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return TARDIS_MC_OK;
 }
@@ -2135,6 +2160,161 @@ int tardis_mc_set_geometry(TardisMcContext *ctx, const TardisMcGeometry *g)
     return TARDIS_MC_OK;
 }
 
+// Every table that depends on the resident probabilities prob_t[S][T] -- the running sums cum_t, the negative-probability flag, the choice of the hot
+// sectors, rec16 / line_block_c / cum16 -- and the invalidation of what is built lazily from the opacity state (the prefix sums of tau, the interleaved
+// sweep table, the source function with its exp(-tau)).  Shared by tardis_mc_set_opacity and tardis_mc_update_opacity: it reads the context's host
+// copies of the index tables and of the line list, not the caller's pointers.
+static int derive_opacity_tables(TardisMcContext *ctx, const size_t L, const size_t S, const size_t T, const std::function<void(const char *)> &tmark)
+{
+    const std::vector<int> &l2l = ctx->h_idx[0], &edge = ctx->h_idx[1], &ttype = ctx->h_idx[2], &dest = ctx->h_idx[3], &tline = ctx->h_idx[4];
+    const std::vector<double> &nu = ctx->h_nu;
+    const bool macro = ctx->h_macro;
+    const size_t E = macro ? edge.size() : 1;
+    int rc;
+    ctx->sf_valid = ctx->sf_exp_valid = false;
+    {   // running sums of the transition probabilities within their blocks (macro_cumulative_kernel)
+        HIP_TRY(ctx, ctx->cum_t.ensure((T * S + 8) * sizeof(double)));  // (+8: the jump search reads eight entries at a time)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->cum_t.p, ctx->prob_t.p, T * S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->prob_negative = false;
+        if (macro && E > 1) {
+            HIP_TRY(ctx, ctx->pfx_flag.ensure(sizeof(int)));  // (a flag word the context keeps: no hipMalloc / hipFree per opacity state)
+            int *flag = ctx->pfx_flag.as<int>();
+            HIP_TRY(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
+            const long long n = (long long)(E - 1) * (long long)S;
+            hipLaunchKernelGGL(mc::macro_cumulative_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->prob_t.as<double>(),
+                               ctx->cum_t.as<double>(), ctx->block_edge.as<int>(), (int)(E - 1), (long long)T, (int)S, flag);
+            int neg = 0;
+            hipError_t e1 = hipGetLastError();
+            hipError_t e2 = hipMemcpyAsync(&neg, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+            hipError_t e3 = hipStreamSynchronize(ctx->stream);
+            HIP_TRY(ctx, e1); HIP_TRY(ctx, e2); HIP_TRY(ctx, e3);
+            ctx->prob_negative = neg != 0;
+        }
+    }
+    tmark("running sums");
+    ctx->have_walk_tables = false;
+    ctx->have_hot = false;
+    ctx->n_hot_blocks = 0;
+    ctx->pfx_valid = false;  // (the prefix sums of the new tau table are built by the first propagate call that traces v-packets)
+    ctx->nt_valid = false;   // (likewise the interleaved sweep table: by the first call that sweeps on it)
+    if (macro && E > 1 && !ctx->prob_negative) {
+        // compact tables of the per-lane macro-atom walk (walk_tables.hpp): blocks at 16-byte aligned compact offsets.  The walk is
+        // bound by the number of memory requests, and a block's window of running sums is fetched in 64-byte sectors: a block of
+        // up to 32 entries (one window) that would straddle a sector boundary starts at the next boundary instead (the skipped
+        // quads are padding no block owns), longer blocks start on a boundary -- one request per jump instead of 1.5.
+        const size_t n_levels = E - 1;
+        std::vector<long long> c0(n_levels + 1);
+        long long tc = 0;
+        for (size_t b = 0; b < n_levels; ++b) {
+            const long long len = (edge[b + 1] - edge[b] + 7) / 8 * 8;
+            if (ctx->walk_sector_packing && len > 0) {
+                const long long in_sector = tc & 31;  // (32 entries of 2 bytes per 64-byte sector)
+                if (in_sector != 0 && (len > 32 || in_sector + len > 32)) tc += 32 - in_sector;
+            }
+            c0[b] = tc;
+            tc += len;
+        }
+        c0[n_levels] = tc;
+        const long long n_quads = tc / 8;
+        const unsigned long long stride = ((unsigned long long)tc + 31ull) / 32ull * 32ull + mc::WALK_SLACK;  // (rows start on sector boundaries)
+        if (tc > 0 && stride * S < (1ull << 32) && tc < (1LL << 30)) {
+            // hot sectors (walk_tables.hpp): measured on the device (total width of a block's six widest intervals, per shell),
+            // chosen here (mean over the shells), then built once more with the destinations' flags in place
+            std::vector<unsigned char> hot(n_levels, 0);
+            if (ctx->walk_hot != 0 && n_levels < (size_t)mc::WALK_HOT) {
+                const long long nb = (long long)n_levels * (long long)S;
+                HIP_TRY(ctx, ctx->hot_sec.ensure((size_t)nb * 64));
+                HIP_TRY(ctx, ctx->hot_mass.ensure((size_t)nb * sizeof(unsigned)));
+                HIP_TRY(ctx, ctx->hot_flag.ensure(n_levels));
+                auto launch_hot = [&](const unsigned char *flags, unsigned *mass) {
+                    hipLaunchKernelGGL(mc::walk_hot_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cum_t.as<double>(),
+                                       ctx->block_edge.as<int>(), ctx->ttype.as<int>(), ctx->dest.as<int>(), ctx->tline.as<int>(), flags,
+                                       (int)n_levels, (long long)T, (int)S, ctx->hot_sec.as<unsigned>(), mass);
+                    return hipGetLastError();
+                };
+                HIP_TRY(ctx, launch_hot(nullptr, ctx->hot_mass.as<unsigned>()));
+                std::vector<unsigned> mass((size_t)nb);
+                HIP_TRY(ctx, hipMemcpyAsync(mass.data(), ctx->hot_mass.p, (size_t)nb * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                for (size_t b = 0; b < n_levels; ++b) {
+                    const long long rows = edge[b + 1] - edge[b];
+                    if (rows <= 0) continue;
+                    double m = 0.0;
+                    for (size_t sh = 0; sh < S; ++sh) m += (double)mass[sh * n_levels + b];
+                    m /= 65536.0 * (double)S;
+                    const double need = 1e-3 * (double)(rows > 8 * mc::WALK_WINDOW_QUADS ? ctx->walk_hot_min_mass_long : ctx->walk_hot_min_mass);
+                    if (ctx->walk_hot == 1 || m >= need) { hot[b] = 1; ctx->n_hot_blocks += 1; }
+                }
+                if (ctx->n_hot_blocks > 0) {
+                    HIP_TRY(ctx, hipMemcpyAsync(ctx->hot_flag.p, hot.data(), n_levels, hipMemcpyHostToDevice, ctx->stream));
+                    hipLaunchKernelGGL(mc::walk_hot_flag_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, ctx->hot_flag.as<unsigned char>(), nb,
+                                       ctx->hot_sec.as<unsigned>());  // (the destinations of the first pass's records, marked; no second walk over the blocks)
+                    HIP_TRY(ctx, hipGetLastError());
+                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                    ctx->have_hot = true;
+                } else {  // no block qualifies (uniform short blocks): S x levels x 64 B -- 0.5 GB at the configs[4] shape -- are not kept for nothing
+                    ctx->hot_sec.release();
+                    ctx->hot_flag.release();
+                }
+                ctx->hot_mass.release();  // (only the choice above read it)
+            }
+            {
+                std::vector<int> bt(2 * n_levels);
+                for (size_t b = 0; b < n_levels; ++b) {
+                    bt[2 * b] = (int)c0[b];
+                    bt[2 * b + 1] = (int)(edge[b + 1] - edge[b]);
+                }
+                if ((rc = upload(ctx, ctx->blk_tab, bt.data(), bt.size()))) return rc;
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            }
+            std::vector<int> qi(2 * (size_t)n_quads, 0), lbc(2 * L, 0);  // (quads of the sector padding: {0, 0} -> eight 0xffff entries)
+            std::vector<mc::WalkRec> r16((size_t)tc + 1, mc::WalkRec{0u, 0u, 0.0});
+            for (size_t b = 0; b < n_levels; ++b) {
+                const long long b0 = edge[b], b1 = edge[b + 1];
+                for (long long q = c0[b] / 8, k = b0; k < b1; ++q, k += 8) { qi[2 * q] = (int)k; qi[2 * q + 1] = (int)(b1 - k); }
+                for (long long k = b0; k < b1; ++k) {
+                    const long long c = c0[b] + (k - b0);
+                    const int64_t tt = ttype[k];
+                    if (tt >= 0) {
+                        const int64_t lvl = dest[k];
+                        if (hot[lvl]) { r16[c].a = (unsigned)lvl; r16[c].b = mc::WALK_HOT; }
+                        else {
+                            r16[c].a = (unsigned)c0[lvl];
+                            r16[c].b = (unsigned)(edge[lvl + 1] - edge[lvl]);
+                        }
+                    } else if (tt == -1) {
+                        r16[c].a = (unsigned)tline[k];
+                        r16[c].b = mc::WALK_EMIT;
+                        r16[c].nu = nu[tline[k]];
+                    } else
+                        r16[c].b = mc::WALK_EMIT | mc::WALK_UNSUPPORTED;
+                }
+            }
+            for (size_t i = 0; i < L; ++i) {
+                const int64_t lvl = l2l[i];
+                if (hot[lvl]) { lbc[2 * i] = (int)lvl; lbc[2 * i + 1] = -1; }
+                else {
+                    lbc[2 * i] = (int)c0[lvl];
+                    lbc[2 * i + 1] = (int)(edge[lvl + 1] - edge[lvl]);
+                }
+            }
+            if ((rc = upload(ctx, ctx->quad_info, qi.data(), qi.size()))) return rc;
+            if ((rc = upload(ctx, ctx->rec16, r16.data(), r16.size()))) return rc;
+            if ((rc = upload(ctx, ctx->line_block_c, lbc.data(), lbc.size()))) return rc;
+            HIP_TRY(ctx, ctx->cum16.ensure((size_t)stride * S * sizeof(unsigned short)));
+            HIP_TRY(ctx, hipMemsetAsync(ctx->cum16.p, 0xff, (size_t)stride * S * sizeof(unsigned short), ctx->stream));
+            const long long n = n_quads * (long long)S;
+            hipLaunchKernelGGL(mc::walk_cum16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cum_t.as<double>(),
+                               ctx->quad_info.as<int2>(), n_quads, (long long)T, (int)S, (unsigned)stride, ctx->cum16.as<unsigned short>());
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the host vectors above are the sources of asynchronous copies)
+            ctx->cum16_stride = (unsigned)stride;
+            ctx->have_walk_tables = true;
+        }
+    }
+    return TARDIS_MC_OK;
+}
+
 int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
 {
     if (!ctx || !o || o->n_lines <= 0 || o->n_shells <= 0 || o->n_transitions <= 0 || !o->electron_density ||
@@ -2146,7 +2326,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     ctx->sf_valid = ctx->sf_topo_valid = ctx->sf_exp_valid = false;
     const bool tmark_on = getenv("TARDIS_MC_TIME_OPACITY") != nullptr;  // (diagnostic: wall time of the stages of this call on stderr)
     auto tmark_t0 = std::chrono::steady_clock::now();
-    auto tmark = [&](const char *what) {
+    const std::function<void(const char *)> tmark = [&](const char *what) {
         if (!tmark_on) return;
         const auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "set_opacity: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - tmark_t0).count());
@@ -2196,7 +2376,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     tmark("probabilities up + transpose");
     static const int64_t zero64 = 0;
-    std::vector<int> idx32[5];  // (one staging vector per table: the copies are asynchronous, ONE synchronisation below covers them all)
+    std::vector<int> (&idx32)[5] = ctx->h_idx;  // (one staging vector per table: the copies are asynchronous, ONE synchronisation below covers them all; kept for derive_opacity_tables)
     auto up32 = [&](int k, DevBuf &buf, const int64_t *host, size_t n) -> int {
         idx32[k].resize(n);
         for (size_t i = 0; i < n; ++i) idx32[k][i] = (int)host[i];
@@ -2207,6 +2387,9 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     if ((rc = up32(2, ctx->ttype, macro ? o->transition_type : &zero64, macro ? T : 1))) return rc;
     if ((rc = up32(3, ctx->dest, macro ? o->destination_level_id : &zero64, macro ? T : 1))) return rc;
     if ((rc = up32(4, ctx->tline, macro ? o->transition_line_id : &zero64, macro ? T : 1))) return rc;
+    ctx->h_nu.assign(o->line_list_nu, o->line_list_nu + L);
+    ctx->h_macro = macro;
+    ctx->have_line_data = ctx->ou_valid = false;  // (the line data belong to one topology: tardis_mc_set_line_data again)
     tmark("index tables int32 up");
     {   // packed macro-atom tables of the cooperative kernel
         std::vector<int> lb(2 * (macro ? L : 1), 0), rec(4 * (macro ? T : 1), 0);
@@ -2237,146 +2420,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     tmark("packed tables lb / rec / tnu");
-    {   // running sums of the transition probabilities within their blocks (macro_cumulative_kernel)
-        HIP_TRY(ctx, ctx->cum_t.ensure((T * S + 8) * sizeof(double)));  // (+8: the jump search reads eight entries at a time)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->cum_t.p, ctx->prob_t.p, T * S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        ctx->prob_negative = false;
-        if (macro && E > 1) {
-            HIP_TRY(ctx, ctx->pfx_flag.ensure(sizeof(int)));  // (a flag word the context keeps: no hipMalloc / hipFree per opacity state)
-            int *flag = ctx->pfx_flag.as<int>();
-            HIP_TRY(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
-            const long long n = (long long)(E - 1) * (long long)S;
-            hipLaunchKernelGGL(mc::macro_cumulative_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->prob_t.as<double>(),
-                               ctx->cum_t.as<double>(), ctx->block_edge.as<int>(), (int)(E - 1), (long long)T, (int)S, flag);
-            int neg = 0;
-            hipError_t e1 = hipGetLastError();
-            hipError_t e2 = hipMemcpyAsync(&neg, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-            hipError_t e3 = hipStreamSynchronize(ctx->stream);
-            HIP_TRY(ctx, e1); HIP_TRY(ctx, e2); HIP_TRY(ctx, e3);
-            ctx->prob_negative = neg != 0;
-        }
-    }
-    tmark("running sums");
-    ctx->have_walk_tables = false;
-    ctx->have_hot = false;
-    ctx->n_hot_blocks = 0;
-    ctx->pfx_valid = false;  // (the prefix sums of the new tau table are built by the first propagate call that traces v-packets)
-    ctx->nt_valid = false;   // (likewise the interleaved sweep table: by the first call that sweeps on it)
-    if (macro && E > 1 && !ctx->prob_negative) {
-        // compact tables of the per-lane macro-atom walk (walk_tables.hpp): blocks at 16-byte aligned compact offsets.  The walk is
-        // bound by the number of memory requests, and a block's window of running sums is fetched in 64-byte sectors: a block of
-        // up to 32 entries (one window) that would straddle a sector boundary starts at the next boundary instead (the skipped
-        // quads are padding no block owns), longer blocks start on a boundary -- one request per jump instead of 1.5.
-        const size_t n_levels = E - 1;
-        std::vector<long long> c0(n_levels + 1);
-        long long tc = 0;
-        for (size_t b = 0; b < n_levels; ++b) {
-            const long long len = (o->macro_block_edge_index[b + 1] - o->macro_block_edge_index[b] + 7) / 8 * 8;
-            if (ctx->walk_sector_packing && len > 0) {
-                const long long in_sector = tc & 31;  // (32 entries of 2 bytes per 64-byte sector)
-                if (in_sector != 0 && (len > 32 || in_sector + len > 32)) tc += 32 - in_sector;
-            }
-            c0[b] = tc;
-            tc += len;
-        }
-        c0[n_levels] = tc;
-        const long long n_quads = tc / 8;
-        const unsigned long long stride = ((unsigned long long)tc + 31ull) / 32ull * 32ull + mc::WALK_SLACK;  // (rows start on sector boundaries)
-        if (tc > 0 && stride * S < (1ull << 32) && tc < (1LL << 30)) {
-            // hot sectors (walk_tables.hpp): measured on the device (total width of a block's six widest intervals, per shell),
-            // chosen here (mean over the shells), then built once more with the destinations' flags in place
-            std::vector<unsigned char> hot(n_levels, 0);
-            if (ctx->walk_hot != 0 && n_levels < (size_t)mc::WALK_HOT) {
-                const long long nb = (long long)n_levels * (long long)S;
-                HIP_TRY(ctx, ctx->hot_sec.ensure((size_t)nb * 64));
-                HIP_TRY(ctx, ctx->hot_mass.ensure((size_t)nb * sizeof(unsigned)));
-                HIP_TRY(ctx, ctx->hot_flag.ensure(n_levels));
-                auto launch_hot = [&](const unsigned char *flags, unsigned *mass) {
-                    hipLaunchKernelGGL(mc::walk_hot_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cum_t.as<double>(),
-                                       ctx->block_edge.as<int>(), ctx->ttype.as<int>(), ctx->dest.as<int>(), ctx->tline.as<int>(), flags,
-                                       (int)n_levels, (long long)T, (int)S, ctx->hot_sec.as<unsigned>(), mass);
-                    return hipGetLastError();
-                };
-                HIP_TRY(ctx, launch_hot(nullptr, ctx->hot_mass.as<unsigned>()));
-                std::vector<unsigned> mass((size_t)nb);
-                HIP_TRY(ctx, hipMemcpyAsync(mass.data(), ctx->hot_mass.p, (size_t)nb * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                for (size_t b = 0; b < n_levels; ++b) {
-                    const long long rows = o->macro_block_edge_index[b + 1] - o->macro_block_edge_index[b];
-                    if (rows <= 0) continue;
-                    double m = 0.0;
-                    for (size_t sh = 0; sh < S; ++sh) m += (double)mass[sh * n_levels + b];
-                    m /= 65536.0 * (double)S;
-                    const double need = 1e-3 * (double)(rows > 8 * mc::WALK_WINDOW_QUADS ? ctx->walk_hot_min_mass_long : ctx->walk_hot_min_mass);
-                    if (ctx->walk_hot == 1 || m >= need) { hot[b] = 1; ctx->n_hot_blocks += 1; }
-                }
-                if (ctx->n_hot_blocks > 0) {
-                    HIP_TRY(ctx, hipMemcpyAsync(ctx->hot_flag.p, hot.data(), n_levels, hipMemcpyHostToDevice, ctx->stream));
-                    hipLaunchKernelGGL(mc::walk_hot_flag_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, ctx->hot_flag.as<unsigned char>(), nb,
-                                       ctx->hot_sec.as<unsigned>());  // (the destinations of the first pass's records, marked; no second walk over the blocks)
-                    HIP_TRY(ctx, hipGetLastError());
-                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                    ctx->have_hot = true;
-                } else {  // no block qualifies (uniform short blocks): S x levels x 64 B -- 0.5 GB at the configs[4] shape -- are not kept for nothing
-                    ctx->hot_sec.release();
-                    ctx->hot_flag.release();
-                }
-                ctx->hot_mass.release();  // (only the choice above read it)
-            }
-            {
-                std::vector<int> bt(2 * n_levels);
-                for (size_t b = 0; b < n_levels; ++b) {
-                    bt[2 * b] = (int)c0[b];
-                    bt[2 * b + 1] = (int)(o->macro_block_edge_index[b + 1] - o->macro_block_edge_index[b]);
-                }
-                if ((rc = upload(ctx, ctx->blk_tab, bt.data(), bt.size()))) return rc;
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            }
-            std::vector<int> qi(2 * (size_t)n_quads, 0), lbc(2 * L, 0);  // (quads of the sector padding: {0, 0} -> eight 0xffff entries)
-            std::vector<mc::WalkRec> r16((size_t)tc + 1, mc::WalkRec{0u, 0u, 0.0});
-            for (size_t b = 0; b < n_levels; ++b) {
-                const long long b0 = o->macro_block_edge_index[b], b1 = o->macro_block_edge_index[b + 1];
-                for (long long q = c0[b] / 8, k = b0; k < b1; ++q, k += 8) { qi[2 * q] = (int)k; qi[2 * q + 1] = (int)(b1 - k); }
-                for (long long k = b0; k < b1; ++k) {
-                    const long long c = c0[b] + (k - b0);
-                    const int64_t tt = o->transition_type[k];
-                    if (tt >= 0) {
-                        const int64_t lvl = o->destination_level_id[k];
-                        if (hot[lvl]) { r16[c].a = (unsigned)lvl; r16[c].b = mc::WALK_HOT; }
-                        else {
-                            r16[c].a = (unsigned)c0[lvl];
-                            r16[c].b = (unsigned)(o->macro_block_edge_index[lvl + 1] - o->macro_block_edge_index[lvl]);
-                        }
-                    } else if (tt == -1) {
-                        r16[c].a = (unsigned)o->transition_line_id[k];
-                        r16[c].b = mc::WALK_EMIT;
-                        r16[c].nu = o->line_list_nu[o->transition_line_id[k]];
-                    } else
-                        r16[c].b = mc::WALK_EMIT | mc::WALK_UNSUPPORTED;
-                }
-            }
-            for (size_t i = 0; i < L; ++i) {
-                const int64_t lvl = o->line2macro_level_upper[i];
-                if (hot[lvl]) { lbc[2 * i] = (int)lvl; lbc[2 * i + 1] = -1; }
-                else {
-                    lbc[2 * i] = (int)c0[lvl];
-                    lbc[2 * i + 1] = (int)(o->macro_block_edge_index[lvl + 1] - o->macro_block_edge_index[lvl]);
-                }
-            }
-            if ((rc = upload(ctx, ctx->quad_info, qi.data(), qi.size()))) return rc;
-            if ((rc = upload(ctx, ctx->rec16, r16.data(), r16.size()))) return rc;
-            if ((rc = upload(ctx, ctx->line_block_c, lbc.data(), lbc.size()))) return rc;
-            HIP_TRY(ctx, ctx->cum16.ensure((size_t)stride * S * sizeof(unsigned short)));
-            HIP_TRY(ctx, hipMemsetAsync(ctx->cum16.p, 0xff, (size_t)stride * S * sizeof(unsigned short), ctx->stream));
-            const long long n = n_quads * (long long)S;
-            hipLaunchKernelGGL(mc::walk_cum16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cum_t.as<double>(),
-                               ctx->quad_info.as<int2>(), n_quads, (long long)T, (int)S, (unsigned)stride, ctx->cum16.as<unsigned short>());
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the host vectors above are the sources of asynchronous copies)
-            ctx->cum16_stride = (unsigned)stride;
-            ctx->have_walk_tables = true;
-        }
-    }
+    if ((rc = derive_opacity_tables(ctx, L, S, T, tmark))) return rc;
     tmark("compact walk tables + hot sectors");
     ctx->lines_sorted = true;
     for (size_t i = 0; i < L; ++i)
@@ -2668,6 +2712,7 @@ int tardis_mc_reset_estimators(TardisMcContext *ctx)
     if (!ctx->est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_config must precede reset_estimators");
     EstLayout e = est_layout(ctx->est_S, ctx->est_L, ctx->est_G, ctx->est_copies);
     HIP_TRY(ctx, hipMemsetAsync(ctx->est.p, 0, e.total * sizeof(double), ctx->stream));
+    ctx->est_propagated = false;
     HIP_TRY(ctx, ctx->counters.ensure(TARDIS_MC_N_COUNTERS * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, TARDIS_MC_N_COUNTERS * sizeof(unsigned long long), ctx->stream));
     return TARDIS_MC_OK;
@@ -2762,6 +2807,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     ctx->timed = true;
+    ctx->est_propagated = true;
     if (call.tune_slot >= 0) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_tune[1], ctx->stream));
         ctx->ls_tune.pending = call.tune_slot;
@@ -3359,14 +3405,11 @@ int tardis_mc_get_vpacket_log(TardisMcContext *ctx, TardisMcVpacketLog *log)
     return TARDIS_MC_OK;
 }
 
-int tardis_mc_radiation_field(TardisMcContext *ctx, double time_of_simulation, const double *volume, double w_epsilon,
-                              int detailed_optical_window, double *t_radiative, double *dilution_factor, double *j_blues)
+// The kernels of tardis_mc_radiation_field, enqueued on the context's stream: t_rad, W and the j_blue normalisation into work ([4 S]: volume, t_rad, W, norm),
+// and, where out_t is given, the j_blues [S][L] into it.  Shared with the detailed mode of tardis_mc_update_opacity, whose j are these bits.
+static int radiation_field_enqueue(TardisMcContext *ctx, double time_of_simulation, const double *volume, double w_epsilon, int detailed_optical_window,
+                                   DevBuf &work, double *out_t)
 {
-    if (!ctx || !volume) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->est_valid || !ctx->have_opacity || !ctx->have_geometry)
-        return fail(ctx, TARDIS_MC_ERR_STATE, "radiation field update needs propagated estimators");
-    if (!(time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "time_of_simulation must be positive");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = reduce_estimator_copies(ctx);
     if (rc) return rc;
     const size_t S = ctx->est_S, L = ctx->est_L;
@@ -3383,23 +3426,42 @@ int tardis_mc_radiation_field(TardisMcContext *ctx, double time_of_simulation, c
     k.tsim = time_of_simulation;
     k.planck_coef = 2 * h / (c * c);
     k.h = h; k.k_b = k_b; k.w_epsilon = w_epsilon; k.c_ang = c * 1e8;
-    DevBuf work, out_t;
     HIP_TRY(ctx, work.ensure(4 * S * sizeof(double)));
     double *d_vol = work.as<double>(), *d_t = d_vol + S, *d_w = d_t + S, *d_norm = d_w + S;
     HIP_TRY(ctx, hipMemcpyAsync(d_vol, volume, S * 8, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(radfield_shell_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, ctx->stream, base + e.J, base + e.nubar,
                        d_vol, (int)S, k, d_t, d_w, d_norm);
     HIP_TRY(ctx, hipGetLastError());
-    if (t_radiative) HIP_TRY(ctx, hipMemcpyAsync(t_radiative, d_t, S * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (dilution_factor) HIP_TRY(ctx, hipMemcpyAsync(dilution_factor, d_w, S * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (j_blues && L > 0) {
-        HIP_TRY(ctx, out_t.ensure(L * S * sizeof(double)));
-        HIP_TRY(ctx, ctx->staging.ensure(L * S * sizeof(double)));
+    if (out_t && L > 0) {
         const unsigned bx = (unsigned)std::min<size_t>((L + 255) / 256, 1024);
         hipLaunchKernelGGL(radfield_jblue_kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, base + e.jblue,
-                           ctx->nu_line.as<double>(), d_t, d_w, d_norm, (int)S, (long long)L, k, detailed_optical_window,
-                           out_t.as<double>());
+                           ctx->nu_line.as<double>(), d_t, d_w, d_norm, (int)S, (long long)L, k, detailed_optical_window, out_t);
         HIP_TRY(ctx, hipGetLastError());
+    }
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_radiation_field(TardisMcContext *ctx, double time_of_simulation, const double *volume, double w_epsilon,
+                              int detailed_optical_window, double *t_radiative, double *dilution_factor, double *j_blues)
+{
+    if (!ctx || !volume) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->est_valid || !ctx->have_opacity || !ctx->have_geometry)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "radiation field update needs propagated estimators");
+    if (!(time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "time_of_simulation must be positive");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t S = ctx->est_S, L = ctx->est_L;
+    const bool want_j = j_blues && L > 0;
+    DevBuf work, out_t;
+    if (want_j) {
+        HIP_TRY(ctx, out_t.ensure(L * S * sizeof(double)));
+        HIP_TRY(ctx, ctx->staging.ensure(L * S * sizeof(double)));
+    }
+    int rc = radiation_field_enqueue(ctx, time_of_simulation, volume, w_epsilon, detailed_optical_window, work, want_j ? out_t.as<double>() : nullptr);
+    if (rc) { work.release(); out_t.release(); return rc; }
+    const double *d_t = work.as<double>() + S, *d_w = d_t + S;
+    if (t_radiative) HIP_TRY(ctx, hipMemcpyAsync(t_radiative, d_t, S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (dilution_factor) HIP_TRY(ctx, hipMemcpyAsync(dilution_factor, d_w, S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (want_j) {
         HIP_TRY(ctx, launch_transpose(ctx->stream, out_t.as<double>(), ctx->staging.as<double>(), (long long)S, (long long)L));
         HIP_TRY(ctx, hipMemcpyAsync(j_blues, ctx->staging.p, L * S * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
@@ -3865,6 +3927,201 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
 }
 
 int tardis_mc_last_source_iterations(TardisMcContext *ctx) { return ctx ? ctx->last_source_iterations : -1; }
+
+/* ---- opacity update from level populations (opacity_update.hpp) --------------------------------------- */
+int tardis_mc_opacity_update_path(int64_t rows) { return opup::choose_path((long long)rows); }
+
+int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
+{
+    if (!ctx || !d) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_opacity) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity must precede set_line_data");
+    ctx->have_line_data = ctx->ou_valid = false;
+    const size_t L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans;
+    if (d->n_lines != (int64_t)L || d->n_transitions != (int64_t)T)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "line data of %lld lines / %lld transitions, the resident opacity state has %zu / %zu",
+                    (long long)d->n_lines, (long long)d->n_transitions, L, T);
+    if (d->n_levels <= 0 || d->n_levels > 0x7ffffff0LL || !d->f_lu || !d->wavelength_cm || !d->g_lower || !d->g_upper || !d->level_lower || !d->level_upper)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid line data");
+    const bool coef = d->transition_probability_coef != nullptr;
+    if (coef && !ctx->h_macro)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "transition_probability_coef given, but the resident opacity state has no macro-atom tables");
+    // everything the kernels index with is checked here, on the host
+    std::vector<int> lo(L), up(L);
+    for (size_t i = 0; i < L; ++i) {
+        if (d->level_lower[i] < 0 || d->level_lower[i] >= d->n_levels) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "level_lower[%zu] out of range", i);
+        if (d->level_upper[i] < 0 || d->level_upper[i] >= d->n_levels) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "level_upper[%zu] out of range", i);
+        lo[i] = (int)d->level_lower[i];
+        up[i] = (int)d->level_upper[i];
+    }
+    if (coef) {
+        const std::vector<int> &ttype = ctx->h_idx[2], &tline = ctx->h_idx[4];
+        if (ttype.size() != T || tline.size() != T) return fail(ctx, TARDIS_MC_ERR_STATE, "the resident index tables do not match the transition count");
+        for (size_t t = 0; t < T; ++t)
+            if (tline[t] < 0 || tline[t] >= (int)L) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "transition_line_id[%zu] out of range", t);
+        for (size_t t = 0; t < T; ++t)
+            if (ttype[t] < -1 || ttype[t] > 1)
+                return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "transition_type[%zu] = %d: the opacity update knows -1, 0 and 1", t, ttype[t]);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->ou_f_lu, d->f_lu, L))) return rc;
+    if ((rc = upload(ctx, ctx->ou_wave, d->wavelength_cm, L))) return rc;
+    if ((rc = upload(ctx, ctx->ou_g_lower, d->g_lower, L))) return rc;
+    if ((rc = upload(ctx, ctx->ou_g_upper, d->g_upper, L))) return rc;
+    if ((rc = upload(ctx, ctx->ou_level_lower, lo.data(), L))) return rc;
+    if ((rc = upload(ctx, ctx->ou_level_upper, up.data(), L))) return rc;
+    if (coef && (rc = upload(ctx, ctx->ou_coef, d->transition_probability_coef, T))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (lo / up are the sources of asynchronous copies)
+    ctx->ou_levels = d->n_levels;
+    ctx->ou_have_coef = coef;
+    ctx->ou_sobolev_coefficient = d->sobolev_coefficient;
+    ctx->ou_long_rows_built = -2;  // (the list of the long blocks is made by the first update)
+    ctx->have_line_data = true;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_update_opacity(TardisMcContext *ctx, const TardisMcOpacityUpdate *u)
+{
+    if (!ctx || !u || !u->level_number_density) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid opacity update");
+    if (!ctx->have_opacity || !ctx->have_line_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_line_data must precede update_opacity");
+    if (!ctx->have_geometry) return fail(ctx, TARDIS_MC_ERR_STATE, "update_opacity needs the geometry (time_explosion)");
+    const int mode = u->j_blues_mode;
+    if (mode != 0 && mode != 1) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown j_blues_mode %d", mode);
+    if (mode == 0 && (!u->t_radiative || !u->dilution_factor))
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "j_blues_mode 0 needs t_radiative and dilution_factor");
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans, K = (size_t)ctx->ou_levels;
+    if (mode == 1) {
+        if (!ctx->est_valid || !ctx->est_propagated || ctx->est_S != S || ctx->est_L != L)
+            return fail(ctx, TARDIS_MC_ERR_STATE, "j_blues_mode 1 needs propagated estimators");
+        if (!u->volume || !(u->time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "j_blues_mode 1 needs volume and a positive time_of_simulation");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->sf_valid = false;
+    ctx->ou_valid = false;
+    int rc;
+    const bool blocks = ctx->ou_have_coef && ctx->h_macro && ctx->n_levels > 0;
+    if (blocks && ctx->ou_long_rows_built != ctx->ou_long_rows) {  // which blocks take the row form (opacity_update_plan.hpp)
+        const std::vector<int> &edge = ctx->h_idx[1];
+        std::vector<int> list;
+        for (size_t b = 0; b + 1 < edge.size(); ++b)
+            if (opup::choose_path((long long)edge[b + 1] - edge[b], ctx->ou_long_rows) == opup::PATH_ROW) list.push_back((int)b);
+        if ((rc = upload(ctx, ctx->ou_long_blocks, list.data(), list.size()))) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->ou_n_long = (long long)list.size();
+        ctx->ou_long_rows_built = ctx->ou_long_rows;
+    }
+    HIP_TRY(ctx, ctx->ou_n_t.ensure(K * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ou_shell.ensure(4 * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ou_beta_t.ensure(L * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ou_sef_t.ensure(L * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ou_j_t.ensure(L * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->staging.ensure(K * S * sizeof(double)));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // populations [K,S] -> [S][K]
+    HIP_TRY(ctx, host_copy(ctx, {{(void *)u->level_number_density, ctx->staging.p, K * S * sizeof(double)}}, true));
+    if (u->electron_density && (rc = upload(ctx, ctx->n_e, u->electron_density, S))) return rc;
+    double *d_t = ctx->ou_shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
+    if (mode == 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_t, u->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_w, u->dilution_factor, S * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    ctx->ou_timed = false;
+    for (hipEvent_t &e : ctx->ev_ou)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[0], ctx->stream));
+    HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->staging.as<double>(), ctx->ou_n_t.as<double>(), (long long)K, (long long)S));
+    if (mode == 1 && (rc = radiation_field_enqueue(ctx, u->time_of_simulation, u->volume, u->w_epsilon, u->detailed_optical_window, ctx->ou_shell,
+                                                   ctx->ou_j_t.as<double>())))
+        return rc;
+    mc::OpacityUpdateConsts k;
+    {   // constants, tardis/constants.py:1 (CODATA 2010, cgs): those of tardis_mc_radiation_field
+        const double h = 6.62606957e-27, k_b = 1.3806488e-16, c = mc::C_LIGHT;
+        k.coef_sobolev = ctx->ou_sobolev_coefficient; k.t_exp = ctx->t_exp; k.planck_coef = 2 * h / (c * c); k.h = h; k.k_b = k_b;
+    }
+    {
+        const unsigned bx = (unsigned)std::min<size_t>((L + 255) / 256, 1024);
+        auto kernel = mode == 0 ? mc::opacity_line_kernel<true> : mc::opacity_line_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->ou_n_t.as<double>(), ctx->ou_level_lower.as<int>(),
+                           ctx->ou_level_upper.as<int>(), ctx->ou_f_lu.as<double>(), ctx->ou_wave.as<double>(), ctx->ou_g_lower.as<double>(),
+                           ctx->ou_g_upper.as<double>(), ctx->nu_line.as<double>(), d_t, d_w, (long long)K, (long long)L, k, ctx->tau_t.as<double>(),
+                           ctx->ou_beta_t.as<double>(), ctx->ou_sef_t.as<double>(), ctx->ou_j_t.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[1], ctx->stream));
+    if (blocks) {
+        const long long n_blocks = ctx->n_levels, n_long = ctx->ou_n_long;
+        const long long long_rows = ctx->ou_long_rows < 0 ? opup::LONG_BLOCK_ROWS : ctx->ou_long_rows;
+        if (n_long < n_blocks) {
+            const long long n = n_blocks * (long long)S;
+            hipLaunchKernelGGL(mc::opacity_block_lane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->block_edge.as<int>(), (int)n_blocks,
+                               (long long)T, (long long)L, (int)S, long_rows, ctx->ou_coef.as<double>(), ctx->tline.as<int>(), ctx->ttype.as<int>(),
+                               ctx->ou_beta_t.as<double>(), ctx->ou_sef_t.as<double>(), ctx->ou_j_t.as<double>(), ctx->prob_t.as<double>());
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (n_long > 0) {
+            const long long n = n_long * (long long)S * 16;
+            hipLaunchKernelGGL(mc::opacity_block_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ou_long_blocks.as<int>(), (int)n_long,
+                               ctx->block_edge.as<int>(), (long long)T, (long long)L, (int)S, ctx->ou_coef.as<double>(), ctx->tline.as<int>(), ctx->ttype.as<int>(),
+                               ctx->ou_beta_t.as<double>(), ctx->ou_sef_t.as<double>(), ctx->ou_j_t.as<double>(), ctx->prob_t.as<double>());
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[2], ctx->stream));
+    rc = derive_opacity_tables(ctx, L, S, T, [](const char *) {});
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[3], ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->timed = true;
+    ctx->chunks_timed = 0;
+    ctx->ou_timed = true;
+    ctx->ou_valid = true;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_last_opacity_update_ms(TardisMcContext *ctx, double *out_line_ms, double *out_block_ms, double *out_derive_ms)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->ou_timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_opacity has been timed yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_ou[3]));
+    float a = 0.f, b = 0.f, c = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&a, ctx->ev_ou[0], ctx->ev_ou[1]));
+    HIP_TRY(ctx, hipEventElapsedTime(&b, ctx->ev_ou[1], ctx->ev_ou[2]));
+    HIP_TRY(ctx, hipEventElapsedTime(&c, ctx->ev_ou[2], ctx->ev_ou[3]));
+    if (out_line_ms) *out_line_ms = a;
+    if (out_block_ms) *out_block_ms = b;
+    if (out_derive_ms) *out_derive_ms = c;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_opacity(TardisMcContext *ctx, double *tau_sobolev, double *transition_probabilities, double *beta_sobolev,
+                          double *stimulated_emission_factor, double *j_blues)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_opacity) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity must precede get_opacity");
+    if ((beta_sobolev || stimulated_emission_factor || j_blues) && !ctx->ou_valid)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "beta_sobolev, stimulated_emission_factor and j_blues exist only after update_opacity");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans;
+    HIP_TRY(ctx, ctx->staging.ensure(std::max(L, T) * S * sizeof(double)));
+    auto down = [&](double *host, const double *table_t, size_t rows) -> int {  // [S][rows] -> [rows,S]
+        if (!host) return TARDIS_MC_OK;
+        HIP_TRY(ctx, launch_transpose(ctx->stream, table_t, ctx->staging.as<double>(), (long long)S, (long long)rows));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, host_copy(ctx, {{(void *)host, ctx->staging.p, rows * S * sizeof(double)}}, false));
+        return TARDIS_MC_OK;
+    };
+    int rc;
+    if ((rc = down(tau_sobolev, ctx->tau_t.as<double>(), L))) return rc;
+    if ((rc = down(transition_probabilities, ctx->prob_t.as<double>(), T))) return rc;
+    if ((rc = down(beta_sobolev, ctx->ou_beta_t.as<double>(), L))) return rc;
+    if ((rc = down(stimulated_emission_factor, ctx->ou_sef_t.as<double>(), L))) return rc;
+    if ((rc = down(j_blues, ctx->ou_j_t.as<double>(), L))) return rc;
+    return TARDIS_MC_OK;
+}
+
 
 /* ---- multi-GPU -------------------------------------------------------------------------------------- */
 int tardis_mc_comm_get_unique_id(uint8_t out_id[TARDIS_MC_UNIQUE_ID_BYTES])

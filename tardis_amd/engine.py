@@ -48,6 +48,9 @@ class Engine:
         self._keep = {}
         self.n_packets = self.n_shells = self.n_lines = self.n_grid = 0
         self.n_levels = 0  # macro-atom levels (blocks) of the resident opacity tables
+        self.n_transitions = 0
+        self.line_data = None        # the object whose data set_line_data() uploaded (None after every set_opacity / run)
+        self.opacity_generation = 0  # bumped whenever the resident opacity tables are replaced (lazy DeviceOpacityState views check it)
         self._vpk_log = False
         self._n_v = 0
         self.packets_generation = 0  # bumped whenever the resident packets are replaced (lazy host views check it)
@@ -92,8 +95,11 @@ class Engine:
             exc = NotImplementedError("macro-atom transition type outside classic mode (continuum processes)")
         if exc is not None:
             exc.packet_index = packet_index  # lowest failing packet index (the reference aborts on the first one)
+            exc.code = rc
             raise exc
-        raise RuntimeError(f"{what} failed ({rc}): {msg}")
+        exc = RuntimeError(f"{what} failed ({rc}): {msg}")
+        exc.code = rc  # (the TARDIS_MC_ERR_* value, _abi.ERR_*)
+        raise exc
 
     # -- staged API
     def set_option(self, name: str, value: int):
@@ -108,10 +114,65 @@ class Engine:
     def set_opacity(self, opacity_state):
         m = _abi.marshal_opacity(opacity_state)
         self.resident_opacity = None  # (a failed upload leaves the tables undefined)
+        self.line_data = None
+        self.opacity_generation += 1
         self._check(self._L.tardis_mc_set_opacity(self._h, m.ref()), "set_opacity")
         self.n_lines, self.n_shells = int(m.struct.n_lines), int(m.struct.n_shells)
         self.n_levels = max(0, int(m.struct.n_macro_block_edges) - 1)
+        self.n_transitions = int(m.struct.n_transitions)
         self.resident_opacity = opacity_state
+
+    def set_line_data(self, line_data):
+        """The static line data of update_opacity() (`tardis_mc_set_line_data`), after set_opacity(): an object with f_lu,
+        wavelength_cm, g_lower, g_upper, level_lower, level_upper [n_lines], n_levels, sobolev_coefficient and
+        transition_probability_coef [n_transitions] (None in scatter mode), e.g. ``synthetic.make_line_data``.  A later
+        set_opacity() drops them."""
+        m = _abi.marshal_line_data(line_data, self.n_transitions)
+        self.line_data = None
+        self._check(self._L.tardis_mc_set_line_data(self._h, m.ref()), "set_line_data")
+        self.line_data = line_data
+
+    def update_opacity(self, level_number_density, electron_density=None, j_blues_mode=_abi.J_BLUES_DILUTE_BLACKBODY, *,
+                       t_radiative=None, dilution_factor=None, time_of_simulation=0.0, volume=None, w_epsilon=1e-10,
+                       detailed_optical_window=False) -> None:
+        """tau_sobolev, beta_sobolev, the stimulated-emission factor, j_blues and the transition probabilities of the next iteration,
+        computed on the device from ``level_number_density`` [n_levels, n_shells] (`tardis_mc_update_opacity`): the resident tables
+        are replaced as set_opacity() would replace them, nothing of [n_lines, n_shells] crosses the bus.  ``j_blues_mode`` 0: dilute
+        black body of ``t_radiative`` / ``dilution_factor``; 1: the detailed j_blues radiation_field() returns for
+        (``time_of_simulation``, ``volume``, ``w_epsilon``, ``detailed_optical_window``), after propagate().  ``electron_density``
+        None keeps the resident values.  No host object describes the new tables: ``resident_opacity`` becomes None until the
+        caller names one (transport.MCTransportSolverHIP.update_opacity does)."""
+        m = _abi.marshal_opacity_update(level_number_density, self.n_shells, electron_density, j_blues_mode, t_radiative,
+                                        dilution_factor, time_of_simulation, volume, w_epsilon, detailed_optical_window)
+        self.resident_opacity = None
+        self.opacity_generation += 1
+        self._check(self._L.tardis_mc_update_opacity(self._h, m.ref()), "update_opacity")
+
+    def get_opacity(self, tau_sobolev=True, transition_probabilities=True, beta_sobolev=False, stimulated_emission_factor=False,
+                    j_blues=False) -> dict:
+        """The resident opacity tables, downloaded line-major as set_opacity() takes them (`tardis_mc_get_opacity`): a dict of the
+        arrays asked for -- tau_sobolev, beta_sobolev, stimulated_emission_factor, j_blues [n_lines, n_shells],
+        transition_probabilities [n_transitions, n_shells].  The last three exist only after update_opacity()."""
+        S, L, T = self.n_shells, self.n_lines, self.n_transitions
+        want = (("tau_sobolev", tau_sobolev, L), ("transition_probabilities", transition_probabilities, T),
+                ("beta_sobolev", beta_sobolev, L), ("stimulated_emission_factor", stimulated_emission_factor, L), ("j_blues", j_blues, L))
+        out = {name: np.empty((rows, S)) for name, on, rows in want if on}
+        self._check(self._L.tardis_mc_get_opacity(self._h, *(out[name].ctypes.data if on else None for name, on, _ in want)),
+                    "get_opacity")
+        return out
+
+    def last_opacity_update_ms(self) -> dict:
+        """Device time (ms) of the stages of the last update_opacity(): {"line_ms" (population transpose, detailed j_blues, line
+        kernel), "block_ms" (block kernels), "derive_ms" (the tables derived from the probabilities)}."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(self._L.tardis_mc_last_opacity_update_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "last_opacity_update_ms")
+        return {"line_ms": a.value, "block_ms": b.value, "derive_ms": c.value}
+
+    @staticmethod
+    def opacity_update_path(rows: int) -> str:
+        """The form of update_opacity()'s block kernel for a macro-atom block of ``rows`` transitions: "lane" (one lane per
+        (block, shell)) or "row" (a 16-lane row per (block, shell)); csrc/opacity_update_plan.hpp."""
+        return ("lane", "row")[int(_lib.lib().tardis_mc_opacity_update_path(int(rows)))]
 
     def set_config(self, montecarlo_configuration, spectrum_frequency_grid, number_of_vpackets=None, sigma_thomson=None):
         m = _abi.marshal_config(montecarlo_configuration, spectrum_frequency_grid, number_of_vpackets, sigma_thomson)
@@ -288,6 +349,8 @@ class Engine:
         trackers = st.LastInteractionTrackers(P) if track_last_interaction else None
         res = _abi.ResultBuffers(P, S, L, int(mc.struct.n_spectrum_grid), None, None, trackers, cap)
         self.resident_opacity = None
+        self.line_data = None
+        self.opacity_generation += 1
         self.results_generation += 1
         self.estimators_generation += 1
         self.packets_generation += 1
@@ -299,6 +362,7 @@ class Engine:
             self.set_option("track_full", prev_full)
         self.n_packets, self.n_shells, self.n_lines, self.n_grid = P, S, L, int(mc.struct.n_spectrum_grid)
         self.n_levels = max(0, int(mo.struct.n_macro_block_edges) - 1)
+        self.n_transitions = int(mo.struct.n_transitions)
         self._n_v, self._vpk_log = n_v, log
         self._check(rc, "run", int(res.struct.first_error_packet))
         res.full_trackers = self.get_event_log() if track_full else None

@@ -222,3 +222,70 @@ BASELINE_CONFIGS = {
     5: dict(n_packets=500_000_000, n_shells=100, n_lines=500_000, line_interaction_type="macroatom",
             n_vpackets=10),
 }
+
+
+# pi e^2 / (m_e c) [cm^2 / s], CODATA 2010 cgs: the plasma's TauSobolev.sobolev_coefficient
+SOBOLEV_COEFFICIENT = np.pi * 4.80320450e-10**2 / (9.10938291e-28 * st.C_SPEED_OF_LIGHT)
+
+
+@dataclass
+class LineData:
+    """Static line data of Engine.set_line_data plus one plasma state to feed Engine.update_opacity with."""
+    f_lu: np.ndarray
+    wavelength_cm: np.ndarray
+    g_lower: np.ndarray
+    g_upper: np.ndarray
+    level_lower: np.ndarray
+    level_upper: np.ndarray
+    n_levels: int
+    transition_probability_coef: np.ndarray | None
+    sobolev_coefficient: float
+    level_number_density: np.ndarray  # [n_levels, n_shells]
+    electron_density: np.ndarray      # [n_shells]
+    t_radiative: np.ndarray           # [n_shells]
+    dilution_factor: np.ndarray       # [n_shells]
+
+
+def make_line_data(seed: int, opacity_state: st.OpacityState, n_levels: int | None = None, level_sizes: str = "uniform",
+                   time_explosion: float = 13 * DAY) -> LineData:
+    """Atomic data and level populations for the device opacity update, on the topology of ``opacity_state`` (make_opacity_state):
+    oscillator strengths log-uniform over three decades, wavelengths c / nu, statistical weights 2J + 1, every line between two of
+    ``n_levels`` atomic levels (lower index < upper index), macro-atom coefficients per transition row (spread over many decades for
+    ``level_sizes="heavy"``, as the probabilities of make_opacity_state are; internal-up rows carry 1e4, the inverse of a typical
+    mean intensity) and populations that fall with the level index and the shell's density, with 1.5 dex of scatter -- enough for
+    inverted pairs -- and a few levels empty in some shells.  The populations are scaled so that the median Sobolev optical depth at
+    ``time_explosion`` is 1e-2: with their spread tau reaches both beyond 1e3 and below 1e-4, all three branches of beta."""
+    rng = np.random.default_rng(seed + 7919)
+    L = len(opacity_state.line_list_nu)
+    S = len(opacity_state.electron_density)
+    K = int(n_levels) if n_levels is not None else max(8, L // 10)
+    if K < 2:
+        raise ValueError("n_levels must be at least 2")
+    f_lu = 10.0 ** rng.uniform(-3.0, 0.0, L)
+    wavelength_cm = st.C_SPEED_OF_LIGHT / np.asarray(opacity_state.line_list_nu, dtype=np.float64)
+    a, b = rng.integers(0, K, L), rng.integers(0, K - 1, L)
+    b = np.where(b >= a, b + 1, b)  # (two different levels)
+    level_lower, level_upper = np.minimum(a, b).astype(np.int64), np.maximum(a, b).astype(np.int64)
+    g_level = 2.0 * rng.integers(0, 6, K) + 1.0
+    g_lower, g_upper = g_level[level_lower], g_level[level_upper]
+    rho = np.asarray(opacity_state.electron_density, dtype=np.float64) / float(opacity_state.electron_density[0])
+    log_n = 4.0 - 8.0 * np.arange(K) / K + rng.normal(0.0, 1.5, K)
+    n = 10.0 ** log_n[:, None] * rho[None, :] * 10.0 ** rng.normal(0.0, 0.2, (K, S))
+    raw = SOBOLEV_COEFFICIENT * f_lu[:, None] * wavelength_cm[:, None] * time_explosion * n[level_lower]
+    n *= 1e-2 / np.median(raw)
+    empty = rng.choice(K, max(2, K // 50), replace=False)
+    n[empty[0], :] = 0.0                 # a level empty everywhere
+    n[empty[1:], rng.integers(0, S, len(empty) - 1)] = 0.0  # ... and some empty in one shell
+    coef = None
+    ttype = np.asarray(opacity_state.transition_type)
+    if len(ttype) > 1:
+        T = len(ttype)
+        coef = rng.random(T) + 0.05
+        if level_sizes == "heavy":
+            coef *= 10.0 ** rng.normal(0.0, 2.0, T)
+        coef[ttype == 1] *= 1e4
+    S_idx = np.arange(S)
+    t_rad = 10000.0 - 150.0 * S_idx
+    w = 0.4 / (1.0 + 0.2 * S_idx)
+    return LineData(f_lu, wavelength_cm, g_lower, g_upper, level_lower, level_upper, K, coef, float(SOBOLEV_COEFFICIENT), n,
+                    np.asarray(opacity_state.electron_density, dtype=np.float64).copy(), t_rad, w)

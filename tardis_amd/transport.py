@@ -373,6 +373,40 @@ class _DeviceEstimators:
         return self._trk
 
 
+class DeviceOpacityState:
+    """The opacity state MCTransportSolverHIP.update_opacity() left in the engine: the attribute names of the reference's
+    OpacityStateNumba, the static ones (line list, macro-atom index tables) taken from the state the topology was uploaded with,
+    ``electron_density`` as given to the update, and ``tau_sobolev`` / ``transition_probabilities`` (also ``beta_sobolev``,
+    ``stimulated_emission_factor``, ``j_blues``) fetched from the engine on first access, like _DeviceEstimators.  Passing it to
+    the next ``initialize_transport_state`` of a resident solver runs on the resident tables without an upload.  Reading a table
+    that was not fetched before the engine's tables were replaced raises."""
+
+    _STATIC = ("t_electrons", "line_list_nu", "line2macro_level_upper", "macro_block_edge_index", "transition_type",
+               "destination_level_id", "transition_line_id")
+    _TABLES = ("tau_sobolev", "transition_probabilities", "beta_sobolev", "stimulated_emission_factor", "j_blues")
+
+    def __init__(self, engine: Engine, base_opacity_state, electron_density):
+        self._eng = engine
+        self._gen = engine.opacity_generation
+        for n in self._STATIC:
+            setattr(self, n, getattr(base_opacity_state, n))
+        self.electron_density = np.ascontiguousarray(electron_density, dtype=np.float64)
+        self._cache = {}
+
+    def _table(self, name):
+        if name not in self._cache:
+            if self._gen != self._eng.opacity_generation:
+                raise RuntimeError("the engine's opacity tables were replaced since this update: they are gone")
+            self._cache.update(self._eng.get_opacity(**{n: n == name for n in self._TABLES}))
+        return self._cache[name]
+
+    tau_sobolev = property(lambda self: self._table("tau_sobolev"))
+    transition_probabilities = property(lambda self: self._table("transition_probabilities"))
+    beta_sobolev = property(lambda self: self._table("beta_sobolev"))
+    stimulated_emission_factor = property(lambda self: self._table("stimulated_emission_factor"))
+    j_blues = property(lambda self: self._table("j_blues"))
+
+
 class MonteCarloTransportState:
     """Result holder with the reference's property names (montecarlo_transport_state.py:15-317), unit-less."""
 
@@ -532,6 +566,47 @@ class MCTransportSolverHIP:
         self.enable_rpacket_tracking = bool(enable_rpacket_tracking)  # full r-packet tracking -> transport_state.tracker_full_df
         self.transport_state = None
         self._engine = engine          # (default: the process-wide engine of the device)
+        self.line_data = None          # static line data of update_opacity() (set_line_data)
+
+    def set_line_data(self, line_data):
+        """The atomic data update_opacity() computes the tables from (the fields of ``synthetic.LineData`` /
+        ``Engine.set_line_data``); they reach the engine with the next upload of an opacity state, or with the next update."""
+        self.line_data = line_data
+
+    def update_opacity(self, level_number_density, electron_density=None, radiative_rates_type="dilute-blackbody", *,
+                       t_radiative=None, dilution_factor=None, volume=None, w_epsilon=1e-10, time_of_simulation=None):
+        """The plasma's opacity step of an outer iteration on the device (``resident=True``): tau_sobolev and the macro-atom
+        transition probabilities of the next iteration from ``level_number_density`` [levels, shells], with the mean intensities of
+        ``radiative_rates_type`` -- "dilute-blackbody" (``t_radiative``, ``dilution_factor``) or "detailed" (the last run's j_blue
+        estimators, normalised as ``transport_state.radiation_field(volume, w_epsilon)`` does; "blackbody" is the first with
+        ``dilution_factor`` of ones).  Returns a ``DeviceOpacityState``; it becomes the engine's resident opacity, so the next
+        ``initialize_transport_state(..., opacity_state=<it>, ...)`` / ``run`` uploads nothing."""
+        if not self.resident:
+            raise RuntimeError("update_opacity() needs resident=True")
+        if self.line_data is None:
+            raise RuntimeError("update_opacity() needs set_line_data() first")
+        eng = self._eng()
+        base = eng.resident_opacity
+        if base is None:
+            raise RuntimeError("update_opacity() needs an opacity state in the engine (run an iteration first)")
+        if eng.line_data is not self.line_data:
+            eng.set_line_data(self.line_data)
+        if radiative_rates_type == "detailed":
+            if time_of_simulation is None:
+                if self.transport_state is None:
+                    raise RuntimeError('radiative_rates_type="detailed" needs a run, or time_of_simulation')
+                time_of_simulation = self.transport_state.time_of_simulation
+            eng.update_opacity(level_number_density, electron_density, 1, time_of_simulation=time_of_simulation, volume=volume,
+                               w_epsilon=w_epsilon, detailed_optical_window=False)
+        elif radiative_rates_type in ("dilute-blackbody", "blackbody"):
+            if radiative_rates_type == "blackbody":
+                dilution_factor = np.ones(eng.n_shells)
+            eng.update_opacity(level_number_density, electron_density, 0, t_radiative=t_radiative, dilution_factor=dilution_factor)
+        else:
+            raise ValueError(f"unknown radiative_rates_type {radiative_rates_type!r}")
+        handle = DeviceOpacityState(eng, base, base.electron_density if electron_density is None else electron_density)
+        eng.resident_opacity = handle
+        return handle
 
     def _eng(self) -> Engine:
         return self._engine if self._engine is not None else get_engine(self.device_id)
@@ -595,6 +670,8 @@ class MCTransportSolverHIP:
         # entry point may have uploaded different tables since this solver's last run)
         if not (self.reuse_opacity and eng.resident_opacity is op):
             eng.set_opacity(op)
+        if self.line_data is not None and eng.line_data is not self.line_data:
+            eng.set_line_data(self.line_data)
         eng.set_config(cfg, self.spectrum_frequency_grid, cfg.NUMBER_OF_VPACKETS)
         eng.set_option("track_last_interaction", int(self.enable_last_interaction_tracking))
         pc = ts.packet_collection
