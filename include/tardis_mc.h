@@ -545,6 +545,109 @@ int tardis_mc_get_opacity(TardisMcContext *ctx, double *tau_sobolev, double *tra
  * (tardis_mc_set_option; -1, the default: this rule; n >= 0: blocks of n rows or more take the row form -- measurements only). */
 int tardis_mc_opacity_update_path(int64_t rows);
 
+/* ---- producer of the next iteration's populations: ion and level number densities from (t_rad, W) ------------------------------
+ * What the legacy plasma computes between two iterations in its default configuration -- ionization nebular (or lte), excitation
+ * dilute-lte (or lte), no NLTE, no helium treatment, no continuum, delta_treatment unset: LevelBoltzmannFactor, PartitionFunction,
+ * GElectron, PhiSahaLTE / PhiSahaNebular with RadiationFieldCorrection and the interpolated zeta, IonNumberDensity.calculate and
+ * LevelNumberDensity -- on the device and in their operation order (fp64, no contraction, exp as the transport evaluates it, every
+ * product and sum a rounding of its own).  The populations never leave the device: they are written where tardis_mc_update_opacity's
+ * kernels read them, and the stages of that update run on them.  Constants: CODATA 2010 cgs, k_B = 1.3806488e-16,
+ * h = 6.62606957e-27, m_e = 9.10938291e-28.  Per shell s, level k of ion i of element e:
+ *   beta_rad = 1 / (k_B t_rad);  t_e = link_t_rad_t_electron t_rad;  beta_e = 1 / (k_B t_e)
+ *   x = (((2 pi) m_e) / beta_rad) / (h h);  g_e = x sqrt(x)
+ *       (the reference writes x ** 1.5.  No pow is bit-identical between a host libm and the device, while sqrt and the product are
+ *       correctly rounded everywhere; x sqrt(x) rounds twice where a correctly rounded pow rounds once, so the two differ by at most an
+ *       ulp of g_e, far below what the 5 % electron-density criterion resolves)
+ *   lbf[k] = level_g[k] exp(level_energy[k] (-beta_rad)), times W for a level with level_metastable[k] == 0 when excitation_mode is 0
+ *   Z[i]   = the serial sum of the ion's lbf in level order, from 0.0
+ *       (pandas' groupby().sum(), which the reference uses, is a compensated sum: agreement with TARDIS is to rounding, not bitwise)
+ *   per ion i that is not its element's last:  phi_lte = (Z[i+1] / Z[i]) ((2 g_e) exp(chi_i (-beta_rad))),  chi_i = ionization_energy[i]
+ *   ionization_mode 1 (lte):      phi = phi_lte
+ *   ionization_mode 0 (nebular):  phi = ((phi_lte W) ((zeta delta) + W (1 - zeta))) sqrt(t_e / t_rad)
+ *     zeta  = zeta[i][.] interpolated linearly in t_rad over zeta_temperatures as interpolate_shells interpolates above:
+ *             hi = clip(searchsorted(zeta_temperatures, t_rad, side="left"), 1, NT-1), lo = hi - 1,
+ *             slope = (y[hi] - y[lo]) / (x[hi] - x[lo]);  zeta = slope (t_rad - x[lo]) + y[lo]   (one division, one product, one sum; not clipped)
+ *     delta = RadiationFieldCorrection with departure_coefficient = 1 / W:  fa = t_e / (((1 / W) W) t_rad);
+ *             chi_i >= chi_0:  delta = fa exp(chi_i (beta_rad - beta_e))
+ *             otherwise:       delta = (1 - exp(chi_i beta_rad - beta_rad chi_0)) + fa exp(chi_i beta_rad - beta_e chi_0)
+ *   IonNumberDensity.calculate:  n_e = the serial sum of number_density over the elements;  then per pass, per element with ions a .. b:
+ *     pe_j = phi_j / n_e (NaN -> 0.0, +inf -> DBL_MAX: numpy.nan_to_num);  cp_j = pe_a ... pe_j, the running product;
+ *     N_a = number_density[e] / (1 + sum cp), the sum serial;  N_(j+1) = N_a cp_j;  populations below 1e-20 become 0.0;
+ *     new = sum_i N_i ion_charge[i], serial over all ion rows;  the pass count goes up by one;
+ *     stop when |new - n_e| / n_e < 0.05 in EVERY shell, otherwise n_e = 0.5 (new + n_e).
+ *     All shells run the same number of passes, as in the reference; the n_e handed out is the one the last pass used.
+ *   n[k] = (lbf[k] / Z[i]) N[i]
+ * Kernels (csrc/plasma_update.hpp): two streaming kernels over (level, shell); the partition functions by one lane per (ion, shell) or,
+ * for long ions, by a 16-lane row that carries the sum in level order (csrc/plasma_update_plan.hpp; same bits); phi and the iteration
+ * by ONE workgroup with a lane per shell, the all-shells vote a workgroup barrier -- which is why more than 1024 shells are refused
+ * (TARDIS_MC_ERR_UNSUPPORTED): a form with one launch per pass is not built.  No atomics: two calls give identical bits.
+ *
+ * TardisMcPlasmaData: levels sorted by (element, ion, level) -- an ion's levels are contiguous, ion_level_edge[i] .. ion_level_edge[i+1]
+ * -- and ions by (element, charge), element_ion_edge likewise.  The entries of an element's last ion in ionization_energy and zeta are
+ * ignored; zeta rows are 1.0 where the reference has no data. */
+typedef struct TardisMcPlasmaData {
+    int64_t n_levels;                    /* K, the line data's n_levels */
+    int64_t n_ions;                      /* I */
+    int64_t n_elements;                  /* E */
+    int64_t n_shells;                    /* S, the resident shells */
+    int64_t n_zeta_temperatures;         /* NT >= 2 */
+    const double *level_energy;          /* [K] erg */
+    const double *level_g;               /* [K] > 0 */
+    const int32_t *level_metastable;     /* [K] */
+    const int64_t *ion_level_edge;       /* [I+1] */
+    const int64_t *element_ion_edge;     /* [E+1] */
+    const double *ion_charge;            /* [I] 0, 1, 2, ... */
+    const double *ionization_energy;     /* [I] erg, from ion i to i + 1 */
+    const double *zeta_temperatures;     /* [NT] ascending */
+    const double *zeta;                  /* [I][NT] */
+    const double *number_density;        /* [E][S] */
+    double chi_0;                        /* erg (the reference takes the ionization energy of Ca II) */
+    double link_t_rad_t_electron;        /* 0.9 in the reference */
+} TardisMcPlasmaData;
+
+typedef struct TardisMcPlasmaUpdate {
+    const double *t_radiative;           /* [S] */
+    const double *dilution_factor;       /* [S] */
+    int32_t ionization_mode;             /* 0 nebular, 1 lte */
+    int32_t excitation_mode;             /* 0 dilute-lte, 1 lte */
+    int32_t j_blues_mode;                /* as in TardisMcOpacityUpdate (mode 0 uses t_radiative / dilution_factor above) */
+    double time_of_simulation;           /* mode 1 */
+    const double *volume;                /* [S], mode 1 */
+    double w_epsilon;                    /* mode 1 */
+    int32_t detailed_optical_window;     /* mode 1 */
+} TardisMcPlasmaUpdate;
+
+/* Static plasma data of the resident topology; after tardis_mc_set_line_data, and dropped like the line data by tardis_mc_set_opacity
+ * (and by a later set_line_data).  Everything is checked on the host before anything is indexed: TARDIS_MC_ERR_INVALID_ARGUMENT when
+ * n_levels differs from the line data's or n_shells from the resident tables', when an edge table does not run from 0 to its count or an
+ * ion has no level / an element no ion, when a level_g is not positive, when the first level of an ion has a negative energy, when
+ * NT < 2 or zeta_temperatures does not ascend, or a pointer is missing; TARDIS_MC_ERR_STATE without line data. */
+int tardis_mc_set_plasma_data(TardisMcContext *ctx, const TardisMcPlasmaData *plasma_data);
+/* One iteration's plasma: solves the populations, writes them over the resident n_t[S][K], installs the solved n_e as the resident
+ * electron density and runs the stages of tardis_mc_update_opacity on them -- afterwards the context is indistinguishable from one
+ * that received the same populations and n_e through tardis_mc_update_opacity.  TARDIS_MC_ERR_STATE without plasma data or geometry,
+ * in mode 1 without propagated estimators, when the electron density becomes NaN (the reference's PlasmaIonizationError) and when the
+ * iteration has not converged after option "plasma_max_iterations" passes (default 1000) -- in both cases the opacity state of before
+ * the call stays as it was (tables, electron densities, tardis_mc_last_opacity_update_ms; tardis_mc_last_propagate_ms then reports the
+ * failed solve's kernels, tardis_mc_get_plasma and tardis_mc_last_plasma_update_ms have nothing to report until the next successful
+ * update); TARDIS_MC_ERR_INVALID_ARGUMENT for an unknown mode and, with ionization_mode 0, when some t_radiative lies
+ * outside [zeta_temperatures[0], zeta_temperatures[NT-1]]; TARDIS_MC_ERR_UNSUPPORTED for more than 1024 shells. */
+int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *update);
+/* The solved plasma: level_number_density [K,S], ion_number_density [I,S], partition_function [I,S], electron_density [S], the
+ * passes of the iteration.  Any pointer may be NULL.  TARDIS_MC_ERR_STATE unless a tardis_mc_update_plasma produced the resident
+ * populations (before the first one, after a failed one, after tardis_mc_update_opacity or set_opacity). */
+int tardis_mc_get_plasma(TardisMcContext *ctx, double *level_number_density, double *ion_number_density, double *partition_function,
+                         double *electron_density, int32_t *iterations);
+/* Device time of the four plasma stages of the last tardis_mc_update_plasma, in ms (any pointer may be NULL): Boltzmann factors |
+ * partition functions | phi and the iteration | populations.  tardis_mc_last_opacity_update_ms reports the three stages behind them
+ * (no transpose in its first).  TARDIS_MC_ERR_STATE before the first update. */
+int tardis_mc_last_plasma_update_ms(TardisMcContext *ctx, double *out_boltzmann_ms, double *out_partition_ms, double *out_ionization_ms,
+                                    double *out_population_ms);
+/* Which form of the partition kernel an ion of `levels` levels takes (csrc/plasma_update_plan.hpp): 0 a lane per (ion, shell), 1 a
+ * 16-lane row per (ion, shell).  Host only; both forms add in the same order.  Option "plasma_update_long_rows" (-1, the default:
+ * this rule; n >= 0: ions of n levels or more take the row form -- measurements and tests only). */
+int tardis_mc_plasma_update_path(int64_t levels);
+
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the
  * last call ran without full tracking, when a packet of it failed, or when the resident packets were replaced since.  With dropped > 0 only count / dropped / offsets are written: run the call again with

@@ -113,6 +113,48 @@ class TardisMcOpacityUpdate(C.Structure):
 J_BLUES_DILUTE_BLACKBODY, J_BLUES_DETAILED = 0, 1
 
 
+class TardisMcPlasmaData(C.Structure):
+    """Static plasma data of the plasma update (tardis_mc_set_plasma_data)."""
+    _fields_ = [
+        ("n_levels", C.c_int64),
+        ("n_ions", C.c_int64),
+        ("n_elements", C.c_int64),
+        ("n_shells", C.c_int64),
+        ("n_zeta_temperatures", C.c_int64),
+        ("level_energy", _pd),
+        ("level_g", _pd),
+        ("level_metastable", C.POINTER(C.c_int32)),
+        ("ion_level_edge", _pi),
+        ("element_ion_edge", _pi),
+        ("ion_charge", _pd),
+        ("ionization_energy", _pd),
+        ("zeta_temperatures", _pd),
+        ("zeta", _pd),
+        ("number_density", _pd),
+        ("chi_0", C.c_double),
+        ("link_t_rad_t_electron", C.c_double),
+    ]
+
+
+class TardisMcPlasmaUpdate(C.Structure):
+    """One iteration's inputs of tardis_mc_update_plasma."""
+    _fields_ = [
+        ("t_radiative", _pd),
+        ("dilution_factor", _pd),
+        ("ionization_mode", C.c_int32),
+        ("excitation_mode", C.c_int32),
+        ("j_blues_mode", C.c_int32),
+        ("time_of_simulation", C.c_double),
+        ("volume", _pd),
+        ("w_epsilon", C.c_double),
+        ("detailed_optical_window", C.c_int32),
+    ]
+
+
+IONIZATION_MODES = {"nebular": 0, "lte": 1}
+EXCITATION_MODES = {"dilute-lte": 0, "lte": 1}
+
+
 _LI_F64 = ("li_radius", "li_nu", "li_energy", "li_before_nu", "li_before_mu", "li_before_energy", "li_after_nu",
            "li_after_mu", "li_after_energy")
 _LI_I64 = ("li_shell_id", "li_interaction_type", "li_line_absorb_id", "li_line_emit_id", "li_interactions_count")
@@ -271,6 +313,50 @@ def marshal_opacity_update(level_number_density, n_shells, electron_density=None
     keep = [n]
     for name, value in (("electron_density", electron_density), ("t_radiative", t_radiative), ("dilution_factor", dilution_factor),
                         ("volume", volume)):
+        if value is None:
+            continue
+        a = np.ascontiguousarray(value, dtype=np.float64)
+        if a.shape != (S,):
+            raise ValueError(f"{name} must have n_shells entries")
+        setattr(s, name, _dp(a))
+        keep.append(a)
+    return Marshalled(s, keep)
+
+
+def marshal_plasma_data(pd) -> Marshalled:
+    """pd: an object with the fields of TardisMcPlasmaData as arrays (level_energy, level_g, level_metastable [K]; ion_level_edge
+    [I+1]; element_ion_edge [E+1]; ion_charge, ionization_energy [I]; zeta_temperatures [NT]; zeta [I, NT]; number_density [E, S])
+    and the scalars chi_0 and link_t_rad_t_electron, e.g. synthetic.PlasmaData.  The counts are taken from the array shapes."""
+    f = {n: np.ascontiguousarray(getattr(pd, n), dtype=np.float64)
+         for n in ("level_energy", "level_g", "ion_charge", "ionization_energy", "zeta_temperatures", "zeta", "number_density")}
+    meta = np.ascontiguousarray(pd.level_metastable, dtype=np.int32)
+    ion_edge = np.ascontiguousarray(pd.ion_level_edge, dtype=np.int64)
+    elem_edge = np.ascontiguousarray(pd.element_ion_edge, dtype=np.int64)
+    K, I, E, NT = len(f["level_energy"]), len(ion_edge) - 1, len(elem_edge) - 1, len(f["zeta_temperatures"])
+    if f["number_density"].ndim != 2 or f["number_density"].shape[0] != E:
+        raise ValueError("number_density must be [n_elements, n_shells]")
+    if f["zeta"].shape != (I, NT):
+        raise ValueError("zeta must be [n_ions, n_zeta_temperatures]")
+    if len(f["level_g"]) != K or len(meta) != K or len(f["ion_charge"]) != I or len(f["ionization_energy"]) != I:
+        raise ValueError("level arrays must have n_levels entries, ion arrays n_ions")
+    s = TardisMcPlasmaData(K, I, E, f["number_density"].shape[1], NT, _dp(f["level_energy"]), _dp(f["level_g"]),
+                           meta.ctypes.data_as(C.POINTER(C.c_int32)), _ip(ion_edge), _ip(elem_edge), _dp(f["ion_charge"]),
+                           _dp(f["ionization_energy"]), _dp(f["zeta_temperatures"]), _dp(f["zeta"]), _dp(f["number_density"]),
+                           float(pd.chi_0), float(pd.link_t_rad_t_electron))
+    return Marshalled(s, list(f.values()) + [meta, ion_edge, elem_edge])
+
+
+def marshal_plasma_update(t_radiative, dilution_factor, n_shells, ionization_mode=0, excitation_mode=0,
+                          j_blues_mode=J_BLUES_DILUTE_BLACKBODY, time_of_simulation=0.0, volume=None, w_epsilon=0.0,
+                          detailed_optical_window=False) -> Marshalled:
+    S = int(n_shells)
+    s = TardisMcPlasmaUpdate()
+    s.ionization_mode, s.excitation_mode, s.j_blues_mode = int(ionization_mode), int(excitation_mode), int(j_blues_mode)
+    s.time_of_simulation = float(time_of_simulation)
+    s.w_epsilon = float(w_epsilon)
+    s.detailed_optical_window = int(bool(detailed_optical_window))
+    keep = []
+    for name, value in (("t_radiative", t_radiative), ("dilution_factor", dilution_factor), ("volume", volume)):
         if value is None:
             continue
         a = np.ascontiguousarray(value, dtype=np.float64)

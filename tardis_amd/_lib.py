@@ -61,6 +61,11 @@ SYMBOLS = {
     "tardis_mc_get_opacity": (_i, [_vp] * 6),
     "tardis_mc_last_opacity_update_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 3),
     "tardis_mc_opacity_update_path": (_i, [C.c_int64]),
+    "tardis_mc_set_plasma_data": (_i, [_vp, _vp]),
+    "tardis_mc_update_plasma": (_i, [_vp, _vp]),
+    "tardis_mc_get_plasma": (_i, [_vp] * 5 + [C.POINTER(C.c_int32)]),
+    "tardis_mc_last_plasma_update_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 4),
+    "tardis_mc_plasma_update_path": (_i, [C.c_int64]),
     "tardis_mc_get_event_log": (_i, [_vp, _vp]),
     "tardis_mc_get_vpacket_log": (_i, [_vp, _vp]),
     "tardis_mc_stream_results": (_i, [_vp, _vp]),

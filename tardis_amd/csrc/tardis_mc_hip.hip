@@ -39,6 +39,8 @@
 #include "vpacket_log.hpp"
 #include "opacity_update.hpp"
 #include "opacity_update_plan.hpp"
+#include "plasma_update.hpp"
+#include "plasma_update_plan.hpp"
 
 static_assert(plan::DBG_WAVE_COUNTERS == mc::WV_DBG_FLAGS, "propagate_plan.hpp repeats the wave kernel's list of counter flags");
 
@@ -330,6 +332,18 @@ struct TardisMcContext {
     double ou_sobolev_coefficient = 0.0;
     hipEvent_t ev_ou[4] = {nullptr, nullptr, nullptr, nullptr};  // start | behind the line kernel | behind the block kernels | end of the last update (tardis_mc_last_opacity_update_ms)
     bool ou_timed = false;
+    // Plasma update (plasma_update.hpp).  Per set_plasma_data: the atomic data of the levels and ions, the map level -> ion, the list of the ions that
+    // take the row form of the partition kernel.  Per update_plasma: lbf_t[S][K]; Z, phi, N [I][S]; the solved n_e [S]; {status, passes}.
+    DevBuf pl_energy, pl_g, pl_meta, pl_level_ion, pl_ion_edge, pl_elem_edge, pl_charge, pl_chi, pl_zeta_t, pl_zeta, pl_density, pl_long_ions;
+    DevBuf pl_lbf_t, pl_z, pl_phi, pl_n_ion, pl_n_e, pl_status;
+    std::vector<int> pl_h_ion_edge;
+    double pl_t_min = 0.0, pl_t_max = 0.0, pl_chi_0 = 0.0, pl_link = 0.0;
+    bool have_plasma_data = false, pl_valid = false, pl_timed = false;  // (pl_valid: Z / N / n_e belong to the resident n_t)
+    int pl_ions = 0, pl_elements = 0, pl_nt = 0, pl_iterations = 0;
+    long long pl_n_long = 0, pl_long_rows_built = -2;
+    long long pl_long_rows = -1;         // option plasma_update_long_rows: -1 the rule of plasma_update_plan.hpp, else the threshold itself
+    long long pl_max_iterations = 1000;  // option plasma_max_iterations: bound on the passes of the electron-density iteration
+    hipEvent_t ev_pl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // start | Boltzmann | partition | ionisation | populations (tardis_mc_last_plasma_update_ms)
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -2044,6 +2058,11 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     for (int k = 0; k < 2; ++k) { ctx->lane_save_c[k].release(); ctx->wave_save_c[k].release(); ctx->seeded_states_c[k].release(); }
     ctx->drain_census.release();
     for (hipEvent_t e : ctx->ev_ou) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ev_pl) if (e) (void)hipEventDestroy(e);
+    for (DevBuf *b : {&ctx->pl_energy, &ctx->pl_g, &ctx->pl_meta, &ctx->pl_level_ion, &ctx->pl_ion_edge, &ctx->pl_elem_edge, &ctx->pl_charge, &ctx->pl_chi,
+                      &ctx->pl_zeta_t, &ctx->pl_zeta, &ctx->pl_density, &ctx->pl_long_ions, &ctx->pl_lbf_t, &ctx->pl_z, &ctx->pl_phi, &ctx->pl_n_ion,
+                      &ctx->pl_n_e, &ctx->pl_status})
+        b->release();
     for (DevBuf *b : {&ctx->ou_f_lu, &ctx->ou_wave, &ctx->ou_g_lower, &ctx->ou_g_upper, &ctx->ou_level_lower, &ctx->ou_level_upper, &ctx->ou_coef,
                       &ctx->ou_long_blocks, &ctx->ou_n_t, &ctx->ou_shell, &ctx->ou_beta_t, &ctx->ou_sef_t, &ctx->ou_j_t})
         b->release();
@@ -2140,6 +2159,8 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "source_max_iterations") ctx->source_max_iterations = std::max<long long>(1, value);
     else if (n == "chunk_packets") ctx->chunk_packets = std::max<long long>(1024, value);
     else if (n == "opacity_update_long_rows") ctx->ou_long_rows = value < 0 ? -1 : value;
+    else if (n == "plasma_update_long_rows") ctx->pl_long_rows = value < 0 ? -1 : value;
+    else if (n == "plasma_max_iterations") ctx->pl_max_iterations = std::max<long long>(1, value);
     else return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return TARDIS_MC_OK;
 }
@@ -2390,6 +2411,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     ctx->h_nu.assign(o->line_list_nu, o->line_list_nu + L);
     ctx->h_macro = macro;
     ctx->have_line_data = ctx->ou_valid = false;  // (the line data belong to one topology: tardis_mc_set_line_data again)
+    ctx->have_plasma_data = ctx->pl_valid = false;  // (... and the plasma data to one set of line data)
     tmark("index tables int32 up");
     {   // packed macro-atom tables of the cooperative kernel
         std::vector<int> lb(2 * (macro ? L : 1), 0), rec(4 * (macro ? T : 1), 0);
@@ -3936,6 +3958,7 @@ int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
     if (!ctx || !d) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_opacity) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity must precede set_line_data");
     ctx->have_line_data = ctx->ou_valid = false;
+    ctx->have_plasma_data = ctx->pl_valid = false;  // (the plasma data sit on the levels of one set of line data)
     const size_t L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans;
     if (d->n_lines != (int64_t)L || d->n_transitions != (int64_t)T)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "line data of %lld lines / %lld transitions, the resident opacity state has %zu / %zu",
@@ -3980,24 +4003,28 @@ int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
     return TARDIS_MC_OK;
 }
 
-int tardis_mc_update_opacity(TardisMcContext *ctx, const TardisMcOpacityUpdate *u)
+// What both producers of an opacity state check before they touch anything: the call order and the j_blues_mode block of the update.
+static int opacity_update_check(TardisMcContext *ctx, const TardisMcOpacityUpdate *u)
 {
-    if (!ctx || !u || !u->level_number_density) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid opacity update");
     if (!ctx->have_opacity || !ctx->have_line_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_line_data must precede update_opacity");
     if (!ctx->have_geometry) return fail(ctx, TARDIS_MC_ERR_STATE, "update_opacity needs the geometry (time_explosion)");
     const int mode = u->j_blues_mode;
     if (mode != 0 && mode != 1) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown j_blues_mode %d", mode);
     if (mode == 0 && (!u->t_radiative || !u->dilution_factor))
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "j_blues_mode 0 needs t_radiative and dilution_factor");
-    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans, K = (size_t)ctx->ou_levels;
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines;
     if (mode == 1) {
         if (!ctx->est_valid || !ctx->est_propagated || ctx->est_S != S || ctx->est_L != L)
             return fail(ctx, TARDIS_MC_ERR_STATE, "j_blues_mode 1 needs propagated estimators");
         if (!u->volume || !(u->time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "j_blues_mode 1 needs volume and a positive time_of_simulation");
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->sf_valid = false;
-    ctx->ou_valid = false;
+    return TARDIS_MC_OK;
+}
+
+// The list of the blocks that take the row form, and the buffers of an update: n_t[S][K], the [S] inputs, beta_t / sef_t / j_t [S][L].
+static int opacity_update_buffers(TardisMcContext *ctx)
+{
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, K = (size_t)ctx->ou_levels;
     int rc;
     const bool blocks = ctx->ou_have_coef && ctx->h_macro && ctx->n_levels > 0;
     if (blocks && ctx->ou_long_rows_built != ctx->ou_long_rows) {  // which blocks take the row form (opacity_update_plan.hpp)
@@ -4015,6 +4042,23 @@ int tardis_mc_update_opacity(TardisMcContext *ctx, const TardisMcOpacityUpdate *
     HIP_TRY(ctx, ctx->ou_beta_t.ensure(L * S * sizeof(double)));
     HIP_TRY(ctx, ctx->ou_sef_t.ensure(L * S * sizeof(double)));
     HIP_TRY(ctx, ctx->ou_j_t.ensure(L * S * sizeof(double)));
+    return TARDIS_MC_OK;
+}
+
+static int opacity_update_stages(TardisMcContext *ctx, const TardisMcOpacityUpdate *u);
+
+int tardis_mc_update_opacity(TardisMcContext *ctx, const TardisMcOpacityUpdate *u)
+{
+    if (!ctx || !u || !u->level_number_density) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid opacity update");
+    int rc;
+    if ((rc = opacity_update_check(ctx, u))) return rc;
+    const int mode = u->j_blues_mode;
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou_levels;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->sf_valid = false;
+    ctx->ou_valid = false;
+    ctx->pl_valid = false;  // (the populations are the caller's from here on)
+    if ((rc = opacity_update_buffers(ctx))) return rc;
     HIP_TRY(ctx, ctx->staging.ensure(K * S * sizeof(double)));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // populations [K,S] -> [S][K]
@@ -4031,6 +4075,19 @@ int tardis_mc_update_opacity(TardisMcContext *ctx, const TardisMcOpacityUpdate *
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[0], ctx->stream));
     HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->staging.as<double>(), ctx->ou_n_t.as<double>(), (long long)K, (long long)S));
+    return opacity_update_stages(ctx, u);
+}
+
+// Everything of an opacity update behind the populations: with n_t[S][K], the electron densities and (mode 0) t_rad / W resident and ev_start / ev_ou[0]
+// recorded, the detailed j_blues of mode 1, the line kernel, the block kernels and the derived tables.  Shared by tardis_mc_update_opacity (populations
+// uploaded) and tardis_mc_update_plasma (populations solved on the device).
+static int opacity_update_stages(TardisMcContext *ctx, const TardisMcOpacityUpdate *u)
+{
+    const int mode = u->j_blues_mode;
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans, K = (size_t)ctx->ou_levels;
+    const bool blocks = ctx->ou_have_coef && ctx->h_macro && ctx->n_levels > 0;
+    double *d_t = ctx->ou_shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
+    int rc;
     if (mode == 1 && (rc = radiation_field_enqueue(ctx, u->time_of_simulation, u->volume, u->w_epsilon, u->detailed_optical_window, ctx->ou_shell,
                                                    ctx->ou_j_t.as<double>())))
         return rc;
@@ -4119,6 +4176,230 @@ int tardis_mc_get_opacity(TardisMcContext *ctx, double *tau_sobolev, double *tra
     if ((rc = down(beta_sobolev, ctx->ou_beta_t.as<double>(), L))) return rc;
     if ((rc = down(stimulated_emission_factor, ctx->ou_sef_t.as<double>(), L))) return rc;
     if ((rc = down(j_blues, ctx->ou_j_t.as<double>(), L))) return rc;
+    return TARDIS_MC_OK;
+}
+
+
+/* ---- plasma update: ion and level populations from (t_rad, W) (plasma_update.hpp) ----------------------- */
+int tardis_mc_plasma_update_path(int64_t levels) { return plup::choose_path((long long)levels); }
+
+int tardis_mc_set_plasma_data(TardisMcContext *ctx, const TardisMcPlasmaData *d)
+{
+    if (!ctx || !d) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_opacity || !ctx->have_line_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_line_data must precede set_plasma_data");
+    ctx->have_plasma_data = ctx->pl_valid = false;
+    if (d->n_levels != ctx->ou_levels)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "plasma data of %lld levels, the line data have %lld", (long long)d->n_levels, ctx->ou_levels);
+    if (d->n_shells != ctx->n_shells)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "plasma data of %lld shells, the resident opacity state has %d", (long long)d->n_shells, ctx->n_shells);
+    if (d->n_ions <= 0 || d->n_elements <= 0 || d->n_ions > d->n_levels || d->n_elements > d->n_ions || d->n_zeta_temperatures < 2 ||
+        d->n_zeta_temperatures > 0x7ffffff0LL || !d->level_energy || !d->level_g || !d->level_metastable || !d->ion_level_edge || !d->element_ion_edge ||
+        !d->ion_charge || !d->ionization_energy || !d->zeta_temperatures || !d->zeta || !d->number_density)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid plasma data");
+    if (!(d->link_t_rad_t_electron > 0) || !(d->chi_0 == d->chi_0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid link_t_rad_t_electron / chi_0");
+    const size_t K = (size_t)d->n_levels, I = (size_t)d->n_ions, E = (size_t)d->n_elements, NT = (size_t)d->n_zeta_temperatures, S = (size_t)d->n_shells;
+    // everything the kernels index with is checked here, on the host
+    if (d->ion_level_edge[0] != 0 || d->ion_level_edge[I] != (int64_t)K) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "ion_level_edge must run from 0 to n_levels");
+    for (size_t i = 0; i < I; ++i)
+        if (d->ion_level_edge[i + 1] <= d->ion_level_edge[i]) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "ion %zu has no level (ion_level_edge not increasing)", i);
+    if (d->element_ion_edge[0] != 0 || d->element_ion_edge[E] != (int64_t)I)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "element_ion_edge must run from 0 to n_ions");
+    for (size_t e = 0; e < E; ++e)
+        if (d->element_ion_edge[e + 1] <= d->element_ion_edge[e]) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "element %zu has no ion (element_ion_edge not increasing)", e);
+    for (size_t k = 0; k < K; ++k)
+        if (!(d->level_g[k] > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "level_g[%zu] is not positive", k);
+    for (size_t i = 0; i < I; ++i)
+        if (!(d->level_energy[d->ion_level_edge[i]] >= 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "the first level of ion %zu has a negative energy", i);
+    for (size_t t = 0; t + 1 < NT; ++t)
+        if (!(d->zeta_temperatures[t] < d->zeta_temperatures[t + 1])) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "zeta_temperatures must ascend");
+    std::vector<int> ion_edge(I + 1), elem_edge(E + 1), meta(K), level_ion(K);
+    for (size_t i = 0; i <= I; ++i) ion_edge[i] = (int)d->ion_level_edge[i];
+    for (size_t e = 0; e <= E; ++e) elem_edge[e] = (int)d->element_ion_edge[e];
+    for (size_t i = 0; i < I; ++i)
+        for (int k = ion_edge[i]; k < ion_edge[i + 1]; ++k) level_ion[k] = (int)i;
+    for (size_t k = 0; k < K; ++k) meta[k] = d->level_metastable[k] != 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->pl_energy, d->level_energy, K))) return rc;
+    if ((rc = upload(ctx, ctx->pl_g, d->level_g, K))) return rc;
+    if ((rc = upload(ctx, ctx->pl_meta, meta.data(), K))) return rc;
+    if ((rc = upload(ctx, ctx->pl_level_ion, level_ion.data(), K))) return rc;
+    if ((rc = upload(ctx, ctx->pl_ion_edge, ion_edge.data(), I + 1))) return rc;
+    if ((rc = upload(ctx, ctx->pl_elem_edge, elem_edge.data(), E + 1))) return rc;
+    if ((rc = upload(ctx, ctx->pl_charge, d->ion_charge, I))) return rc;
+    if ((rc = upload(ctx, ctx->pl_chi, d->ionization_energy, I))) return rc;
+    if ((rc = upload(ctx, ctx->pl_zeta_t, d->zeta_temperatures, NT))) return rc;
+    if ((rc = upload(ctx, ctx->pl_zeta, d->zeta, I * NT))) return rc;
+    if ((rc = upload(ctx, ctx->pl_density, d->number_density, E * S))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors are the sources of asynchronous copies)
+    ctx->pl_h_ion_edge.swap(ion_edge);
+    ctx->pl_ions = (int)I; ctx->pl_elements = (int)E; ctx->pl_nt = (int)NT;
+    ctx->pl_t_min = d->zeta_temperatures[0]; ctx->pl_t_max = d->zeta_temperatures[NT - 1];
+    ctx->pl_chi_0 = d->chi_0; ctx->pl_link = d->link_t_rad_t_electron;
+    ctx->pl_long_rows_built = -2;  // (the list of the long ions is made by the first update)
+    ctx->have_plasma_data = true;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
+{
+    if (!ctx || !p || !p->t_radiative || !p->dilution_factor) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid plasma update");
+    if (!ctx->have_opacity || !ctx->have_line_data || !ctx->have_plasma_data)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity, set_line_data and set_plasma_data must precede update_plasma");
+    if ((p->ionization_mode != 0 && p->ionization_mode != 1) || (p->excitation_mode != 0 && p->excitation_mode != 1))
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown ionization_mode %d / excitation_mode %d", p->ionization_mode, p->excitation_mode);
+    TardisMcOpacityUpdate u{};  // the opacity stages' view of this call: no host populations, the solved electron densities installed below
+    u.j_blues_mode = p->j_blues_mode;
+    u.t_radiative = p->t_radiative; u.dilution_factor = p->dilution_factor;
+    u.time_of_simulation = p->time_of_simulation; u.volume = p->volume; u.w_epsilon = p->w_epsilon;
+    u.detailed_optical_window = p->detailed_optical_window;
+    int rc;
+    if ((rc = opacity_update_check(ctx, &u))) return rc;
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou_levels, I = (size_t)ctx->pl_ions;
+    if ((long long)S > plup::MAX_SHELLS)
+        return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "update_plasma iterates the electron density inside one workgroup: at most %lld shells", plup::MAX_SHELLS);
+    if (p->ionization_mode == 0)
+        for (size_t s = 0; s < S; ++s)
+            if (!(p->t_radiative[s] >= ctx->pl_t_min && p->t_radiative[s] <= ctx->pl_t_max))
+                return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "t_radiative[%zu] = %g lies outside the zeta table [%g, %g]", s, p->t_radiative[s], ctx->pl_t_min,
+                            ctx->pl_t_max);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->pl_long_rows_built != ctx->pl_long_rows) {  // which ions take the row form (plasma_update_plan.hpp)
+        const std::vector<int> &edge = ctx->pl_h_ion_edge;
+        std::vector<int> list;
+        for (size_t i = 0; i + 1 < edge.size(); ++i)
+            if (plup::choose_path((long long)edge[i + 1] - edge[i], ctx->pl_long_rows) == plup::PATH_ROW) list.push_back((int)i);
+        if ((rc = upload(ctx, ctx->pl_long_ions, list.data(), list.size()))) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->pl_n_long = (long long)list.size();
+        ctx->pl_long_rows_built = ctx->pl_long_rows;
+    }
+    if ((rc = opacity_update_buffers(ctx))) return rc;
+    HIP_TRY(ctx, ctx->pl_lbf_t.ensure(K * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl_z.ensure(I * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl_phi.ensure(I * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl_n_ion.ensure(I * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl_n_e.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl_status.ensure(2 * sizeof(int)));
+    // Z, N and n_e are rewritten from here on; the resident n_t, the electron densities and the opacity tables only once the iteration has succeeded
+    ctx->pl_valid = false;
+    double *d_t = ctx->ou_shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
+    HIP_TRY(ctx, hipMemcpyAsync(d_t, p->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_w, p->dilution_factor, S * 8, hipMemcpyHostToDevice, ctx->stream));
+    ctx->pl_timed = false;  // (ou_timed and the ev_ou events stay the previous update's until this solve has succeeded)
+    for (hipEvent_t &e : ctx->ev_ou)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    for (hipEvent_t &e : ctx->ev_pl)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    const double k_b = 1.3806488e-16, h = 6.62606957e-27, m_e = 9.10938291e-28;  // tardis/constants.py (CODATA 2010, cgs)
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[0], ctx->stream));
+    {
+        const unsigned bx = (unsigned)std::min<size_t>((K + 255) / 256, 1024);
+        auto kernel = p->excitation_mode == 0 ? mc::plasma_boltzmann_kernel<true> : mc::plasma_boltzmann_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->pl_energy.as<double>(), ctx->pl_g.as<double>(), ctx->pl_meta.as<int>(), d_t,
+                           d_w, (long long)K, k_b, ctx->pl_lbf_t.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[1], ctx->stream));
+    {
+        const long long n_long = ctx->pl_n_long;
+        const long long long_levels = ctx->pl_long_rows < 0 ? plup::LONG_ION_LEVELS : ctx->pl_long_rows;
+        if (n_long < (long long)I) {
+            const long long n = (long long)I * (long long)S;
+            hipLaunchKernelGGL(mc::plasma_partition_lane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pl_ion_edge.as<int>(), (int)I,
+                               (long long)K, (int)S, long_levels, ctx->pl_lbf_t.as<double>(), ctx->pl_z.as<double>());
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (n_long > 0) {
+            const long long n = n_long * (long long)S * 16;
+            hipLaunchKernelGGL(mc::plasma_partition_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pl_long_ions.as<int>(), (int)n_long,
+                               ctx->pl_ion_edge.as<int>(), (long long)K, (int)S, ctx->pl_lbf_t.as<double>(), ctx->pl_z.as<double>());
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[2], ctx->stream));
+    {
+        mc::PlasmaIonArgs a;
+        a.S = (int)S; a.I = (int)I; a.E = ctx->pl_elements; a.NT = ctx->pl_nt;
+        a.nebular = p->ionization_mode == 0;
+        a.max_iter = ctx->pl_max_iterations;
+        a.link = ctx->pl_link; a.chi_0 = ctx->pl_chi_0; a.k_b = k_b; a.two_pi_me = 2 * M_PI * m_e; a.hh = h * h;
+        a.element_edge = ctx->pl_elem_edge.as<int>(); a.charge = ctx->pl_charge.as<double>(); a.chi = ctx->pl_chi.as<double>();
+        a.zeta_t = ctx->pl_zeta_t.as<double>(); a.zeta = ctx->pl_zeta.as<double>(); a.density = ctx->pl_density.as<double>();
+        a.t_rad = d_t; a.w = d_w; a.z = ctx->pl_z.as<double>();
+        a.phi = ctx->pl_phi.as<double>(); a.n_ion = ctx->pl_n_ion.as<double>(); a.n_e = ctx->pl_n_e.as<double>(); a.status = ctx->pl_status.as<int>();
+        hipLaunchKernelGGL(mc::plasma_ionization_kernel, dim3(1), dim3((unsigned)((S + 63) / 64 * 64)), 0, ctx->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[3], ctx->stream));
+    int status[2] = {mc::PLASMA_NAN, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(status, ctx->pl_status.p, sizeof status, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->pl_iterations = status[1];
+    if (status[0] != mc::PLASMA_OK) {  // a failed solve: tardis_mc_last_propagate_ms reports its kernels, a matching pair of events
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->timed = true;
+        ctx->chunks_timed = 0;
+    }
+    if (status[0] == mc::PLASMA_NAN)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the electron density became NaN in pass %d (PlasmaIonizationError); the opacity state is unchanged", status[1] + 1);
+    if (status[0] != mc::PLASMA_OK)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the electron density has not converged after %d passes (option plasma_max_iterations); the opacity state is unchanged",
+                    status[1]);
+    ctx->sf_valid = false;
+    ctx->ou_valid = false;
+    ctx->ou_timed = false;
+    {
+        const unsigned bx = (unsigned)std::min<size_t>((K + 255) / 256, 1024);
+        hipLaunchKernelGGL(mc::plasma_population_kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->pl_lbf_t.as<double>(), ctx->pl_level_ion.as<int>(),
+                           ctx->pl_z.as<double>(), ctx->pl_n_ion.as<double>(), (long long)K, (int)S, ctx->ou_n_t.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, ctx->n_e.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->n_e.p, ctx->pl_n_e.p, S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[4], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[0], ctx->stream));
+    if ((rc = opacity_update_stages(ctx, &u))) return rc;
+    ctx->pl_timed = true;
+    ctx->pl_valid = true;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_last_plasma_update_ms(TardisMcContext *ctx, double *out_boltzmann_ms, double *out_partition_ms, double *out_ionization_ms, double *out_population_ms)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->pl_timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_plasma has been timed yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_pl[4]));
+    double *out[4] = {out_boltzmann_ms, out_partition_ms, out_ionization_ms, out_population_ms};
+    for (int k = 0; k < 4; ++k) {
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_pl[k], ctx->ev_pl[k + 1]));
+        if (out[k]) *out[k] = ms;
+    }
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_plasma(TardisMcContext *ctx, double *level_number_density, double *ion_number_density, double *partition_function, double *electron_density,
+                         int32_t *iterations)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->pl_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "get_plasma needs an update_plasma since the last set_opacity / update_opacity");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou_levels, I = (size_t)ctx->pl_ions;
+    if (level_number_density) {  // [S][K] -> [K,S]
+        HIP_TRY(ctx, ctx->staging.ensure(K * S * sizeof(double)));
+        HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->ou_n_t.as<double>(), ctx->staging.as<double>(), (long long)S, (long long)K));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, host_copy(ctx, {{(void *)level_number_density, ctx->staging.p, K * S * sizeof(double)}}, false));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, host_copy(ctx, {{(void *)ion_number_density, ctx->pl_n_ion.p, I * S * sizeof(double)},
+                                 {(void *)partition_function, ctx->pl_z.p, I * S * sizeof(double)},
+                                 {(void *)electron_density, ctx->pl_n_e.p, S * sizeof(double)}}, false));
+    if (iterations) *iterations = ctx->pl_iterations;
     return TARDIS_MC_OK;
 }
 

@@ -50,6 +50,8 @@ class Engine:
         self.n_levels = 0  # macro-atom levels (blocks) of the resident opacity tables
         self.n_transitions = 0
         self.line_data = None        # the object whose data set_line_data() uploaded (None after every set_opacity / run)
+        self.plasma_data = None      # ... and set_plasma_data() (None after every set_opacity / set_line_data / run)
+        self.n_plasma_levels = self.n_ions = 0
         self.opacity_generation = 0  # bumped whenever the resident opacity tables are replaced (lazy DeviceOpacityState views check it)
         self._vpk_log = False
         self._n_v = 0
@@ -115,6 +117,7 @@ class Engine:
         m = _abi.marshal_opacity(opacity_state)
         self.resident_opacity = None  # (a failed upload leaves the tables undefined)
         self.line_data = None
+        self.plasma_data = None
         self.opacity_generation += 1
         self._check(self._L.tardis_mc_set_opacity(self._h, m.ref()), "set_opacity")
         self.n_lines, self.n_shells = int(m.struct.n_lines), int(m.struct.n_shells)
@@ -129,6 +132,7 @@ class Engine:
         set_opacity() drops them."""
         m = _abi.marshal_line_data(line_data, self.n_transitions)
         self.line_data = None
+        self.plasma_data = None
         self._check(self._L.tardis_mc_set_line_data(self._h, m.ref()), "set_line_data")
         self.line_data = line_data
 
@@ -173,6 +177,70 @@ class Engine:
         """The form of update_opacity()'s block kernel for a macro-atom block of ``rows`` transitions: "lane" (one lane per
         (block, shell)) or "row" (a 16-lane row per (block, shell)); csrc/opacity_update_plan.hpp."""
         return ("lane", "row")[int(_lib.lib().tardis_mc_opacity_update_path(int(rows)))]
+
+    def set_plasma_data(self, plasma_data):
+        """The static plasma data of update_plasma() (`tardis_mc_set_plasma_data`), after set_line_data(): an object with the
+        fields of ``synthetic.PlasmaData`` -- the levels' energies, weights and metastable flags, the ion and element edges, the ions'
+        charges, ionization energies and zeta rows, the elements' number densities per shell, chi_0 and link_t_rad_t_electron.  A
+        later set_opacity() or set_line_data() drops them."""
+        m = _abi.marshal_plasma_data(plasma_data)
+        self.plasma_data = None
+        self._check(self._L.tardis_mc_set_plasma_data(self._h, m.ref()), "set_plasma_data")
+        self.n_plasma_levels, self.n_ions = int(m.struct.n_levels), int(m.struct.n_ions)
+        self.plasma_data = plasma_data
+
+    def update_plasma(self, t_radiative, dilution_factor, ionization="nebular", excitation="dilute-lte",
+                      j_blues_mode=_abi.J_BLUES_DILUTE_BLACKBODY, *, time_of_simulation=0.0, volume=None, w_epsilon=1e-10,
+                      detailed_optical_window=False) -> None:
+        """The plasma of the next iteration solved on the device from two [n_shells] vectors (`tardis_mc_update_plasma`): level and
+        ion populations and the electron density of ``ionization`` "nebular" / "lte" and ``excitation`` "dilute-lte" / "lte", and on
+        them everything update_opacity() computes -- as if the populations and the solved electron density had been passed to it, but
+        nothing of [levels, shells] crosses the bus.  ``j_blues_mode`` and the keywords as in update_opacity().  A failed solve
+        (RuntimeError with ``code`` ERR_STATE: NaN, or no convergence within option "plasma_max_iterations") leaves the resident
+        tables as they were."""
+        try:
+            modes = _abi.IONIZATION_MODES[ionization], _abi.EXCITATION_MODES[excitation]
+        except KeyError as e:
+            raise ValueError(f"unknown ionization / excitation mode {e.args[0]!r}") from None
+        m = _abi.marshal_plasma_update(t_radiative, dilution_factor, self.n_shells, modes[0], modes[1], j_blues_mode,
+                                       time_of_simulation, volume, w_epsilon, detailed_optical_window)
+        previous = self.resident_opacity
+        self.resident_opacity = None
+        rc = self._L.tardis_mc_update_plasma(self._h, m.ref())
+        if rc in (_abi.ERR_STATE, _abi.ERR_INVALID_ARGUMENT, _abi.ERR_UNSUPPORTED):
+            self.resident_opacity = previous  # (refused before any table was touched)
+        else:
+            self.opacity_generation += 1
+        self._check(rc, "update_plasma")
+
+    def get_plasma(self, level_number_density=True, ion_number_density=True, partition_function=True, electron_density=True) -> dict:
+        """The plasma the last update_plasma() solved (`tardis_mc_get_plasma`): a dict of the arrays asked for --
+        level_number_density [n_levels, n_shells], ion_number_density, partition_function [n_ions, n_shells], electron_density
+        [n_shells] -- and "iterations", the passes of the electron-density iteration."""
+        S = self.n_shells
+        want = (("level_number_density", level_number_density, (self.n_plasma_levels, S)), ("ion_number_density", ion_number_density, (self.n_ions, S)),
+                ("partition_function", partition_function, (self.n_ions, S)), ("electron_density", electron_density, (S,)))
+        out = {name: np.empty(shape) for name, on, shape in want if on}
+        it = C.c_int32(-1)
+        self._check(self._L.tardis_mc_get_plasma(self._h, *(out[name].ctypes.data if on else None for name, on, _ in want), C.byref(it)),
+                    "get_plasma")
+        out["iterations"] = int(it.value)
+        return out
+
+    def last_plasma_update_ms(self) -> dict:
+        """Device time (ms) of the stages of the last update_plasma(): {"boltzmann_ms", "partition_ms", "ionization_ms",
+        "population_ms"}, then the three of last_opacity_update_ms()."""
+        v = [C.c_double() for _ in range(4)]
+        self._check(self._L.tardis_mc_last_plasma_update_ms(self._h, *(C.byref(x) for x in v)), "last_plasma_update_ms")
+        out = dict(zip(("boltzmann_ms", "partition_ms", "ionization_ms", "population_ms"), (x.value for x in v)))
+        out.update(self.last_opacity_update_ms())
+        return out
+
+    @staticmethod
+    def plasma_update_path(levels: int) -> str:
+        """The form of update_plasma()'s partition kernel for an ion of ``levels`` levels: "lane" (one lane per (ion, shell)) or
+        "row" (a 16-lane row per (ion, shell)); csrc/plasma_update_plan.hpp."""
+        return ("lane", "row")[int(_lib.lib().tardis_mc_plasma_update_path(int(levels)))]
 
     def set_config(self, montecarlo_configuration, spectrum_frequency_grid, number_of_vpackets=None, sigma_thomson=None):
         m = _abi.marshal_config(montecarlo_configuration, spectrum_frequency_grid, number_of_vpackets, sigma_thomson)
@@ -350,6 +418,7 @@ class Engine:
         res = _abi.ResultBuffers(P, S, L, int(mc.struct.n_spectrum_grid), None, None, trackers, cap)
         self.resident_opacity = None
         self.line_data = None
+        self.plasma_data = None
         self.opacity_generation += 1
         self.results_generation += 1
         self.estimators_generation += 1

@@ -289,3 +289,106 @@ def make_line_data(seed: int, opacity_state: st.OpacityState, n_levels: int | No
     w = 0.4 / (1.0 + 0.2 * S_idx)
     return LineData(f_lu, wavelength_cm, g_lower, g_upper, level_lower, level_upper, K, coef, float(SOBOLEV_COEFFICIENT), n,
                     np.asarray(opacity_state.electron_density, dtype=np.float64).copy(), t_rad, w)
+
+
+EV = 1.602176565e-12  # erg (CODATA 2010)
+# first ionization energies [eV] of the elements make_plasma_data draws from: (atomic number, I -> II, II -> III, ...), NIST ASD
+_IONIZATION_EV = (
+    (6, 11.260, 24.383, 47.888, 64.494, 392.09),
+    (8, 13.618, 35.121, 54.936, 77.414, 113.90),
+    (12, 7.646, 15.035, 80.144, 109.27, 141.33),
+    (14, 8.152, 16.346, 33.493, 45.142, 166.77),
+    (16, 10.360, 23.338, 34.86, 47.222, 72.59),
+    (20, 6.113, 11.872, 50.913, 67.27, 84.34),
+    (26, 7.902, 16.199, 30.651, 54.91, 75.0),
+    (28, 7.640, 18.169, 35.19, 54.9, 76.06),
+)
+CHI_0_CA_II = 11.872 * EV  # the reference's chi_0: the ionization energy of Ca II
+
+
+@dataclass
+class PlasmaData:
+    """Static plasma data of Engine.set_plasma_data plus one radiation field to feed Engine.update_plasma with."""
+    level_energy: np.ndarray        # [K] erg
+    level_g: np.ndarray             # [K]
+    level_metastable: np.ndarray    # [K] 0 / 1
+    ion_level_edge: np.ndarray      # [I+1]
+    element_ion_edge: np.ndarray    # [E+1]
+    ion_charge: np.ndarray          # [I]
+    ionization_energy: np.ndarray   # [I] erg
+    zeta_temperatures: np.ndarray   # [NT]
+    zeta: np.ndarray                # [I, NT]
+    number_density: np.ndarray      # [E, S]
+    chi_0: float
+    link_t_rad_t_electron: float
+    atomic_number: np.ndarray       # [E]
+    t_radiative: np.ndarray         # [S]
+    dilution_factor: np.ndarray     # [S]
+
+
+def make_plasma_data(seed: int, line_data: LineData, n_shells: int, n_elements: int = 6, ions_per_element: int = 5,
+                     largest_ion: int | None = None, density_inner: float = 1e9) -> PlasmaData:
+    """Atomic data and abundances for the device plasma update on the ``line_data.n_levels`` levels of make_line_data:
+    ``n_elements`` elements of ``ions_per_element`` ions each (neutral upward) with their NIST ionization energies; the levels dealt
+    to the ions with heavy-tailed counts -- an element's highest ion keeps a single level, like a closed shell or a bare nucleus,
+    singly ionized iron-group ions take hundreds; ``largest_ion`` plants an ion of exactly that many levels --, level energies rising
+    from 0 to below the ionization energy, weights 2J + 1, the ground and some low levels metastable, a smooth zeta table on
+    2000 K .. 40000 K with rows of 1.0 for the ions the reference has no data for, and number densities that fall outward as
+    (1 + 0.15 s)^-7."""
+    rng = np.random.default_rng(seed + 104729)
+    K, S, E = int(line_data.n_levels), int(n_shells), int(n_elements)
+    per = int(ions_per_element)
+    if not 2 <= per <= 6 or E < 1:
+        raise ValueError("ions_per_element must be 2 .. 6, n_elements positive")
+    I = E * per
+    if K < I:
+        raise ValueError("fewer levels than ions")
+    rows = [_IONIZATION_EV[e % len(_IONIZATION_EV)] for e in range(E)]
+    atomic_number = np.array([r[0] for r in rows], dtype=np.int64)
+    ion_charge = np.tile(np.arange(per, dtype=np.float64), E)
+    chi = np.array([[r[1 + j] if j < per - 1 else 0.0 for j in range(per)] for r in rows]).ravel() * EV
+    # level counts: one per ion, the rest dealt by log-normal weights; the last ion of an element keeps its single level
+    weight = 10.0 ** rng.normal(0.0, 0.8, I)
+    weight[per - 1::per] = 0.0
+    weight[1::per] *= 4.0  # (singly ionized species dominate a supernova's line list)
+    extra = np.floor(weight / weight.sum() * (K - I)).astype(np.int64)
+    big = int(np.argmax(weight))
+    if largest_ion is not None:
+        if not 1 <= largest_ion <= K - I + 1:
+            raise ValueError("largest_ion does not fit")
+        others = np.delete(np.arange(I), big)
+        left = K - I - (largest_ion - 1)
+        w = weight[others]
+        extra[others] = np.floor(w / w.sum() * left).astype(np.int64) if w.sum() > 0 else 0
+        extra[big] = largest_ion - 1
+    rest = K - I - int(extra.sum())
+    if largest_ion is None:
+        extra[big] += rest
+    else:
+        second = int(np.argmax(np.where(np.arange(I) == big, -1.0, weight)))
+        extra[second] += rest
+    counts = 1 + extra
+    ion_level_edge = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+    element_ion_edge = (per * np.arange(E + 1)).astype(np.int64)
+    level_energy, level_meta = np.zeros(K), np.zeros(K, dtype=np.int32)
+    for i in range(I):
+        a, b = ion_level_edge[i], ion_level_edge[i + 1]
+        top = chi[i] if chi[i] > 0 else 50.0 * EV
+        level_energy[a + 1:b] = np.sort(0.05 * top + 0.9 * top * rng.random(b - a - 1) ** 0.7)
+        level_meta[a] = 1
+        low = a + 1 + np.flatnonzero(rng.random(b - a - 1) < 3.0 / max(3, b - a))
+        level_meta[low] = 1
+    level_g = 2.0 * rng.integers(0, 6, K) + 1.0
+    zeta_t = np.arange(2000.0, 40001.0, 2000.0)
+    centre, width = rng.uniform(5000.0, 30000.0, I), rng.uniform(4000.0, 15000.0, I)
+    zeta = 0.05 + 0.9 / (1.0 + np.exp((zeta_t[None, :] - centre[:, None]) / width[:, None]))
+    zeta[rng.random(I) < 0.2] = 1.0
+    abundance = rng.dirichlet(np.full(E, 2.0))
+    total = density_inner * (1.0 + 0.15 * np.arange(S)) ** -7.0
+    number_density = abundance[:, None] * total[None, :]
+    t_rad = np.asarray(line_data.t_radiative, dtype=np.float64)
+    w = np.asarray(line_data.dilution_factor, dtype=np.float64)
+    if t_rad.shape != (S,):
+        t_rad, w = 10000.0 - 150.0 * np.arange(S), 0.4 / (1.0 + 0.2 * np.arange(S))
+    return PlasmaData(level_energy, level_g, level_meta, ion_level_edge, element_ion_edge, ion_charge, chi, zeta_t, zeta, number_density,
+                      float(CHI_0_CA_II), 0.9, atomic_number, t_rad.copy(), w.copy())

@@ -376,7 +376,7 @@ class _DeviceEstimators:
 class DeviceOpacityState:
     """The opacity state MCTransportSolverHIP.update_opacity() left in the engine: the attribute names of the reference's
     OpacityStateNumba, the static ones (line list, macro-atom index tables) taken from the state the topology was uploaded with,
-    ``electron_density`` as given to the update, and ``tau_sobolev`` / ``transition_probabilities`` (also ``beta_sobolev``,
+    ``electron_density`` as given to the update (after update_plasma(): the solved one, S doubles downloaded with the update), and ``tau_sobolev`` / ``transition_probabilities`` (also ``beta_sobolev``,
     ``stimulated_emission_factor``, ``j_blues``) fetched from the engine on first access, like _DeviceEstimators.  Passing it to
     the next ``initialize_transport_state`` of a resident solver runs on the resident tables without an upload.  Reading a table
     that was not fetched before the engine's tables were replaced raises."""
@@ -567,6 +567,7 @@ class MCTransportSolverHIP:
         self.transport_state = None
         self._engine = engine          # (default: the process-wide engine of the device)
         self.line_data = None          # static line data of update_opacity() (set_line_data)
+        self.plasma_data = None        # static plasma data of update_plasma() (set_plasma_data)
 
     def set_line_data(self, line_data):
         """The atomic data update_opacity() computes the tables from (the fields of ``synthetic.LineData`` /
@@ -605,6 +606,48 @@ class MCTransportSolverHIP:
         else:
             raise ValueError(f"unknown radiative_rates_type {radiative_rates_type!r}")
         handle = DeviceOpacityState(eng, base, base.electron_density if electron_density is None else electron_density)
+        eng.resident_opacity = handle
+        return handle
+
+    def set_plasma_data(self, plasma_data):
+        """The atomic data and abundances update_plasma() solves the populations from (the fields of ``synthetic.PlasmaData`` /
+        ``Engine.set_plasma_data``), on the levels of set_line_data(); they reach the engine with the next upload of an opacity state,
+        or with the next update."""
+        self.plasma_data = plasma_data
+
+    def update_plasma(self, t_radiative, dilution_factor, ionization="nebular", excitation="dilute-lte",
+                      radiative_rates_type="dilute-blackbody", *, volume=None, w_epsilon=1e-10, time_of_simulation=None):
+        """The whole plasma step of an outer iteration on the device (``resident=True``): from ``t_radiative`` and ``dilution_factor``
+        [shells] -- e.g. what ``transport_state.radiation_field()`` returned, damped by the caller -- the level populations and the
+        electron density of the legacy plasma's ``ionization`` "nebular" / "lte" and ``excitation`` "dilute-lte" / "lte", and from them
+        the opacity state as update_opacity() computes it.  No [levels, shells] or [lines, shells] array is passed.  Returns a
+        ``DeviceOpacityState`` whose ``electron_density`` is the solved one -- S doubles, downloaded here and not on first access, so
+        that no later update, successful or failed, can take it away --; it becomes the engine's resident opacity.  A failed solve
+        (RuntimeError, ``code`` ERR_STATE) leaves the engine's resident opacity, and the handle describing it, as they were."""
+        if not self.resident:
+            raise RuntimeError("update_plasma() needs resident=True")
+        if self.line_data is None or self.plasma_data is None:
+            raise RuntimeError("update_plasma() needs set_line_data() and set_plasma_data() first")
+        eng = self._eng()
+        base = eng.resident_opacity
+        if base is None:
+            raise RuntimeError("update_plasma() needs an opacity state in the engine (run an iteration first)")
+        if eng.line_data is not self.line_data:
+            eng.set_line_data(self.line_data)
+        if eng.plasma_data is not self.plasma_data:
+            eng.set_plasma_data(self.plasma_data)
+        if radiative_rates_type == "detailed":
+            if time_of_simulation is None:
+                if self.transport_state is None:
+                    raise RuntimeError('radiative_rates_type="detailed" needs a run, or time_of_simulation')
+                time_of_simulation = self.transport_state.time_of_simulation
+            eng.update_plasma(t_radiative, dilution_factor, ionization, excitation, 1, time_of_simulation=time_of_simulation, volume=volume,
+                              w_epsilon=w_epsilon, detailed_optical_window=False)
+        elif radiative_rates_type == "dilute-blackbody":
+            eng.update_plasma(t_radiative, dilution_factor, ionization, excitation, 0)
+        else:
+            raise ValueError(f"unknown radiative_rates_type {radiative_rates_type!r}")
+        handle = DeviceOpacityState(eng, base, eng.get_plasma(False, False, False, True)["electron_density"])
         eng.resident_opacity = handle
         return handle
 
@@ -672,6 +715,8 @@ class MCTransportSolverHIP:
             eng.set_opacity(op)
         if self.line_data is not None and eng.line_data is not self.line_data:
             eng.set_line_data(self.line_data)
+        if self.line_data is not None and self.plasma_data is not None and eng.plasma_data is not self.plasma_data:
+            eng.set_plasma_data(self.plasma_data)
         eng.set_config(cfg, self.spectrum_frequency_grid, cfg.NUMBER_OF_VPACKETS)
         eng.set_option("track_last_interaction", int(self.enable_last_interaction_tracking))
         pc = ts.packet_collection
