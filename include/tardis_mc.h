@@ -547,7 +547,7 @@ int tardis_mc_opacity_update_path(int64_t rows);
 
 /* ---- producer of the next iteration's populations: ion and level number densities from (t_rad, W) ------------------------------
  * What the legacy plasma computes between two iterations in its default configuration -- ionization nebular (or lte), excitation
- * dilute-lte (or lte), no NLTE, no helium treatment, no continuum, delta_treatment unset: LevelBoltzmannFactor, PartitionFunction,
+ * dilute-lte (or lte), NLTE excitation only through the section after this one, no helium treatment, no continuum, delta_treatment unset: LevelBoltzmannFactor, PartitionFunction,
  * GElectron, PhiSahaLTE / PhiSahaNebular with RadiationFieldCorrection and the interpolated zeta, IonNumberDensity.calculate and
  * LevelNumberDensity -- on the device and in their operation order (fp64, no contraction, exp as the transport evaluates it, every
  * product and sum a rounding of its own).  The populations never leave the device: they are written where tardis_mc_update_opacity's
@@ -647,6 +647,83 @@ int tardis_mc_last_plasma_update_ms(TardisMcContext *ctx, double *out_boltzmann_
  * 16-lane row per (ion, shell).  Host only; both forms add in the same order.  Option "plasma_update_long_rows" (-1, the default:
  * this rule; n >= 0: ions of n levels or more take the row form -- measurements and tests only). */
 int tardis_mc_plasma_update_path(int64_t levels);
+
+/* ---- NLTE excitation of selected species inside tardis_mc_update_plasma --------------------------------------------------------
+ * What the legacy plasma computes for a configuration with plasma.nlte.species: LevelBoltzmannFactorNLTE._calculate_general /
+ * _main_nlte_calculation for atomic data without collision_data.  With NLTE data installed, tardis_mc_update_plasma runs this stage
+ * between the Boltzmann and the partition stage; it replaces the dilute-LTE / LTE Boltzmann factors of the species' levels BEFORE the
+ * partition functions, and every later stage (Z, phi, the n_e iteration, the populations, the opacity stages) runs unchanged on them.
+ * All arithmetic is fp64 with no contraction; every product, quotient and difference is rounded on its own.
+ * For an NLTE species (an ion i of the plasma data with n levels, local index 0 .. n-1 in level order) and a shell s, per line of the
+ * species with local lower level l and upper level u (level_lower / level_upper of the line data minus ion_level_edge[i]):
+ *   j    = the mean intensity the same update stores for that (line, shell), bit for bit: j_blues_mode 0 the dilute black body of the
+ *          call's t_radiative and dilution_factor, mode 1 the j_blues of tardis_mc_radiation_field; 0.0 with coronal_approximation
+ *   beta = the resident beta_sobolev of the PREVIOUS update; 1.0 when no update has produced one since the last tardis_mc_set_opacity
+ *          (the reference's previous_beta_sobolev is None), and 1.0 with classical_nebular
+ *   r_ul = (A_ul + B_ul j) beta;   r_lu = (B_lu j) beta
+ *   M[l][u] = r_ul, M[u][l] = r_lu (the row is the destination, the column the source); every other off-diagonal entry 0.0
+ *   M[c][c] = -(the serial sum, from 0.0, of column c's off-diagonal entries in row order)
+ *       (the reference sums the whole column while its diagonal is still 0.0; adding 0.0 changes nothing)
+ *   then M[0][.] = 1.0 and b = (1, 0, ..., 0)
+ * M x = b by unblocked LU with partial pivoting, in exactly this order.  For k = 0 .. n-1: p = the lowest row index >= k with the
+ * largest |M[.][k]|; rows k and p of M and b are swapped; for i > k: l_i = M[i][k] / M[k][k]; for i, j > k: M[i][j] = M[i][j] - l_i M[k][j];
+ * for i > k: b[i] = b[i] - l_i b[k].  Back substitution, column-oriented, for j = n-1 .. 0: x[j] = b[j] / M[j][j]; for i < j:
+ * b[i] = b[i] - M[i][j] x[j].  Every entry sees its updates in the same order whatever the parallel decomposition: the device result
+ * equals a serial restatement (tests/nlte_excitation_ref.py) bit for bit.
+ *       (LAPACK's blocked dgetrf behind numpy.linalg.solve, which the reference uses, sums in another order and contracts: like the
+ *       partition functions' compensated sum above, agreement with TARDIS is to rounding, not bitwise)
+ * The solve fails (the reference's LinAlgError) when a pivot is 0.0 or not finite, when x[0] is 0.0 or when any x is not finite.
+ *   lbf[k] = (x[k] g_0) / x[0], g_0 the level_g of the species' first level
+ * The stimulated-emission factor needs no change: the existing clamp of negative values is what the reference does for the lines of
+ * NLTE species.  NOT covered: the collision matrix (atomic data with collision_data), NLTE ionization, the helium treatments, continuum.
+ * Kernels (csrc/nlte_excitation.hpp): a streaming kernel writes r_ul / r_lu of the NLTE lines; then one workgroup per (species, shell)
+ * builds and solves the system on a column-major matrix of odd leading dimension, either in its LDS (species of up to 141 levels) or in
+ * a slab of HBM per (species, shell) -- same operations, same order, same bits (csrc/nlte_plan.hpp chooses per species).  No workgroup
+ * waits on another, no atomics: two calls give identical bits. */
+typedef struct TardisMcNlteData {
+    int64_t n_species;                   /* NS */
+    const int64_t *species_ion;          /* [NS] indices into the plasma data's ions, distinct */
+    int64_t n_nlte_lines;                /* NL */
+    const int64_t *species_line_edge;    /* [NS+1]: a species' lines are contiguous in the next four arrays */
+    const int64_t *line_id;              /* [NL] indices into the resident line list */
+    const double *A_ul;                  /* [NL] */
+    const double *B_ul;                  /* [NL] */
+    const double *B_lu;                  /* [NL] */
+    int32_t coronal_approximation;       /* j = 0.0 */
+    int32_t classical_nebular;           /* beta = 1.0 */
+} TardisMcNlteData;
+
+/* The NLTE species of the resident plasma data; after tardis_mc_set_plasma_data, dropped by whatever drops the plasma data
+ * (tardis_mc_set_opacity, set_line_data, set_plasma_data); nlte_data == NULL removes it.  Everything is checked on the host before
+ * anything is indexed: TARDIS_MC_ERR_INVALID_ARGUMENT for an ion index out of range or repeated, an edge table that does not run from 0
+ * to NL, a line_id outside [0, L), a line whose levels are not both inside its species' ion, lower == upper, and a pair of levels
+ * that two lines of a species share in either direction (the reference's fancy assignment would silently keep the last);
+ * TARDIS_MC_ERR_STATE without plasma data; TARDIS_MC_ERR_UNSUPPORTED when the slabs of the global-memory form, over all shells, would
+ * exceed 1 GiB (the message names the species and the bytes; the forms follow option "nlte_lds_levels", so a later
+ * tardis_mc_update_plasma answers the same, before it touches anything, when the option has since moved a species that large into
+ * the global form).  With NLTE data installed a failed NLTE solve makes
+ * tardis_mc_update_plasma return TARDIS_MC_ERR_STATE -- the message names the species, the shell and the elimination step --; it has
+ * written only the Boltzmann factors, so, as for a failed n_e iteration, the opacity state, the electron densities and
+ * tardis_mc_get_opacity are those of before the call. */
+int tardis_mc_set_nlte_data(TardisMcContext *ctx, const TardisMcNlteData *nlte_data);
+/* The host-side check of tardis_mc_set_nlte_data on plain arrays, without a context or a device: ion_level_edge [n_ions + 1] of the
+ * plasma data, level_lower / level_upper [n_lines] of the line data.  0 or TARDIS_MC_ERR_INVALID_ARGUMENT (the message:
+ * tardis_mc_last_error(NULL)). */
+int tardis_mc_check_nlte_data(const TardisMcNlteData *nlte_data, int64_t n_ions, const int64_t *ion_level_edge, int64_t n_lines,
+                              const int64_t *level_lower, const int64_t *level_upper);
+/* The NLTE stage's results of the last tardis_mc_update_plasma: level_boltzmann_factor [K,S] (all levels, the NLTE species' rows
+ * overwritten) and relative_populations, the solutions x, [sum of n over the species][S] in species order.  Either pointer may be
+ * NULL.  TARDIS_MC_ERR_STATE unless the last successful tardis_mc_update_plasma ran the stage and its populations are still resident. */
+int tardis_mc_get_nlte(TardisMcContext *ctx, double *level_boltzmann_factor, double *relative_populations);
+/* Device time of the NLTE stage of the last tardis_mc_update_plasma, in ms: the rates kernel (j, beta -> r_ul, r_lu of every NLTE line)
+ * | the (species, shell) workgroups (matrix, elimination, substitution, write-out; a matrix that lives in LDS cannot be timed apart
+ * from its solve).  tardis_mc_last_plasma_update_ms keeps its four outputs; its Boltzmann and partition figures exclude this stage.
+ * TARDIS_MC_ERR_STATE unless the last update ran the stage. */
+int tardis_mc_last_nlte_ms(TardisMcContext *ctx, double *out_assemble_ms, double *out_solve_ms);
+/* Which form of the solve kernel a species of `levels` levels takes (csrc/nlte_plan.hpp): 0 the LDS form, 1 the global-memory form.
+ * Host only; both forms run the same operations in the same order.  Option "nlte_lds_levels" (-1, the default: this rule; n >= 0:
+ * species of n levels or more take the global form -- measurements and tests only). */
+int tardis_mc_nlte_solve_path(int64_t levels);
 
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the

@@ -151,6 +151,22 @@ class TardisMcPlasmaUpdate(C.Structure):
     ]
 
 
+class TardisMcNlteData(C.Structure):
+    """The NLTE species of the plasma update and their lines (tardis_mc_set_nlte_data)."""
+    _fields_ = [
+        ("n_species", C.c_int64),
+        ("species_ion", _pi),
+        ("n_nlte_lines", C.c_int64),
+        ("species_line_edge", _pi),
+        ("line_id", _pi),
+        ("A_ul", _pd),
+        ("B_ul", _pd),
+        ("B_lu", _pd),
+        ("coronal_approximation", C.c_int32),
+        ("classical_nebular", C.c_int32),
+    ]
+
+
 IONIZATION_MODES = {"nebular": 0, "lte": 1}
 EXCITATION_MODES = {"dilute-lte": 0, "lte": 1}
 
@@ -344,6 +360,23 @@ def marshal_plasma_data(pd) -> Marshalled:
                            _dp(f["ionization_energy"]), _dp(f["zeta_temperatures"]), _dp(f["zeta"]), _dp(f["number_density"]),
                            float(pd.chi_0), float(pd.link_t_rad_t_electron))
     return Marshalled(s, list(f.values()) + [meta, ion_edge, elem_edge])
+
+
+def marshal_nlte_data(nd) -> Marshalled:
+    """nd: an object with species_ion [NS], species_line_edge [NS+1], line_id, A_ul, B_ul, B_lu [NL] and the flags
+    coronal_approximation and classical_nebular, e.g. synthetic.NlteData.  The counts are taken from the array shapes."""
+    ion = np.ascontiguousarray(nd.species_ion, dtype=np.int64)
+    edge = np.ascontiguousarray(nd.species_line_edge, dtype=np.int64)
+    line_id = np.ascontiguousarray(nd.line_id, dtype=np.int64)
+    coef = [np.ascontiguousarray(getattr(nd, n), dtype=np.float64) for n in ("A_ul", "B_ul", "B_lu")]
+    NS, NL = len(ion), len(line_id)
+    if len(edge) != NS + 1:
+        raise ValueError("species_line_edge must have n_species + 1 entries")
+    if not all(len(a) == NL for a in coef):
+        raise ValueError("A_ul, B_ul and B_lu must have one entry per NLTE line")
+    s = TardisMcNlteData(NS, _ip(ion), NL, _ip(edge), _ip(line_id), _dp(coef[0]), _dp(coef[1]), _dp(coef[2]),
+                         int(bool(nd.coronal_approximation)), int(bool(nd.classical_nebular)))
+    return Marshalled(s, [ion, edge, line_id] + coef)
 
 
 def marshal_plasma_update(t_radiative, dilution_factor, n_shells, ionization_mode=0, excitation_mode=0,

@@ -66,6 +66,11 @@ SYMBOLS = {
     "tardis_mc_get_plasma": (_i, [_vp] * 5 + [C.POINTER(C.c_int32)]),
     "tardis_mc_last_plasma_update_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 4),
     "tardis_mc_plasma_update_path": (_i, [C.c_int64]),
+    "tardis_mc_set_nlte_data": (_i, [_vp, _vp]),
+    "tardis_mc_check_nlte_data": (_i, [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp]),
+    "tardis_mc_get_nlte": (_i, [_vp, _vp, _vp]),
+    "tardis_mc_last_nlte_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 2),
+    "tardis_mc_nlte_solve_path": (_i, [C.c_int64]),
     "tardis_mc_get_event_log": (_i, [_vp, _vp]),
     "tardis_mc_get_vpacket_log": (_i, [_vp, _vp]),
     "tardis_mc_stream_results": (_i, [_vp, _vp]),

@@ -1,0 +1,197 @@
+// nlte_excitation.hpp -- NLTE excitation of selected species inside tardis_mc_update_plasma: the level Boltzmann factors of an NLTE species
+// from the statistical equilibrium of its radiative bound-bound rates, solved per (species, shell) on the device.
+//
+// Restates LevelBoltzmannFactorNLTE._calculate_general / _main_nlte_calculation of the legacy plasma for collision_data None (fp64,
+// -ffp-contract=off keeps every product, quotient and difference a rounding of its own; the contract is spelled out in include/tardis_mc.h):
+// per line of the species r_ul = (A_ul + B_ul j) beta and r_lu = (B_lu j) beta, a rate matrix with the destination as the row, the
+// diagonal minus the serial column sum, the first row replaced by ones, b = e_0; M x = b by unblocked LU with partial pivoting and a
+// column-oriented back substitution; lbf[k] = (x[k] g_0) / x[0].
+//
+// Two stages.  nlte_rates_kernel streams the NLTE lines of a shell (grid.y = shell) and writes r_ul / r_lu [S][NL]; its j comes from the
+// device functions the line kernel and radfield_jblue_kernel evaluate (opacity_update.hpp), so it is the j the same update stores, bit for
+// bit.  nlte_solve_kernel is one 256-thread workgroup per (species, shell): it zeroes the matrix, scatters the rates (one writer per
+// entry: tardis_mc_set_nlte_data refuses a repeated pair), sums every column serially for the diagonal, eliminates and substitutes, and
+// writes lbf_t, x and a status word.  The matrix is column-major with an odd leading dimension (nlte_plan.hpp): the rank-1 update and
+// every column walk touch consecutive addresses, the row swap strides over 32 different bank pairs.  Its two forms differ only in
+// where the working set lives -- the workgroup's dynamic LDS, or a slab of HBM per (species, shell) -- and run the same operations in
+// the same order: same bits.
+//
+// An elimination step: every wave finds the pivot of column k for itself (a lane per 64 rows, then a butterfly over the wave that
+// prefers the larger |value| and, among equals, the lower row: no arrival order enters); nothing the next phase writes lies in
+// column k, so no barrier is needed before the row swap (a thread per column right of k) and the multipliers l_i (a thread per row,
+// taken from the unswapped column with the swap applied on the fly; the pivot itself goes into a vector of its own); barrier; the
+// rank-1 update (a wave per column, a lane per row) and b; barrier.  Two barriers per step, one per back-substitution step.  Every entry
+// sees its updates in the order of k whatever the decomposition.  No workgroup waits on another, no atomics: two calls give identical bits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <float.h>
+#include <limits.h>
+#include "mc_device.hpp"
+#include "mc_math.hpp"
+#include "opacity_update.hpp"
+
+namespace mc {
+
+constexpr int NLTE_J_DILUTE = 0, NLTE_J_DETAILED = 1, NLTE_J_CORONAL = 2;
+
+struct NlteRateArgs {
+    int S;
+    long long L, NL;
+    const int *line_id;                      // [NL] into the line list
+    const double *a_ul, *b_ul, *b_lu;        // [NL]
+    const double *nu_line;                   // [L]
+    const double *beta_t;                    // [S][L] of the previous update, or nullptr: 1.0
+    const double *t_rad, *w;                 // [S] the field j is evaluated with (dilute: the call's; detailed: the estimators')
+    const double *norm, *jblue_t;            // detailed: [S], [S][L]
+    double planck_coef, h, k_b, w_epsilon, c_ang;
+    int optical_window;
+    double *r_ul_t, *r_lu_t;                 // [S][NL] out
+};
+
+template <int JMODE>
+__global__ void __launch_bounds__(256) nlte_rates_kernel(NlteRateArgs a)
+{
+    const long long s = blockIdx.y;
+    double beta_rad = 0.0, ws = 0.0, ns = 0.0;
+    if (JMODE != NLTE_J_CORONAL) { beta_rad = 1 / (a.k_b * a.t_rad[s]); ws = a.w[s]; }
+    if (JMODE == NLTE_J_DETAILED) ns = a.norm[s];
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < a.NL; q += (long long)gridDim.x * blockDim.x) {
+        const long long l = a.line_id[q];
+        double j = 0.0;
+        if (JMODE == NLTE_J_DILUTE) j = dilute_black_body_j(ws, a.planck_coef, a.h, a.nu_line[l], beta_rad);
+        if (JMODE == NLTE_J_DETAILED)
+            j = detailed_j_blue(a.jblue_t[s * a.L + l], ns, a.nu_line[l], ws, beta_rad, a.planck_coef, a.h, a.w_epsilon, a.c_ang, a.optical_window);
+        const double beta = a.beta_t ? a.beta_t[s * a.L + l] : 1.0;
+        a.r_ul_t[s * a.NL + q] = (a.a_ul[q] + a.b_ul[q] * j) * beta;
+        a.r_lu_t[s * a.NL + q] = (a.b_lu[q] * j) * beta;
+    }
+}
+
+struct NlteSolveArgs {
+    int S;
+    long long K, NL, NX;
+    const int *list;                         // the species of this launch
+    const int *sp_k0, *sp_n, *sp_x0, *sp_line_edge;  // per species: first level, levels, first row of x, [NS+1] lines
+    const int *lower, *upper;                // [NL] local levels
+    const double *r_ul_t, *r_lu_t;           // [S][NL]
+    const double *g;                         // [K] level_g
+    double *lbf_t;                           // [S][K]: the species' levels are overwritten
+    double *x_t;                             // [S][NX] out
+    int *status;                             // [NS][S] out: 0, or 1 + the step of a bad pivot, n + 1 (x[0] == 0), n + 2 (x not finite)
+    double *scratch;                         // global form: the slabs
+    const long long *slab;                   // global form, per list entry: the offset (doubles) of shell 0's slab; shells follow each other
+};
+
+__device__ __forceinline__ bool nlte_finite(double v) { return fabs(v) <= DBL_MAX; }
+
+// is candidate (v, i) a better pivot than (best, bi)?  The larger |value|; NaN above everything (numpy.argmax); among equals the lower row
+__device__ __forceinline__ bool nlte_better(double v, int i, double best, int bi)
+{
+    const bool vn = v != v, bn = best != best;
+    if (vn != bn) return vn;
+    if (!vn && v != best) return v > best;
+    return i < bi;
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(256) nlte_solve_kernel(NlteSolveArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double nlte_lds[];
+    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long s = blockIdx.y;
+    const int sp = a.list[e], n = a.sp_n[sp], ld = n | 1;
+    const long long work = (long long)ld * n + 4LL * n;
+    double *M = LDS ? nlte_lds : a.scratch + a.slab[e] + s * work;
+    double *b = M + (long long)ld * n, *lv = b + n, *piv = lv + n, *x = piv + n;
+    // assemble: zero, scatter, the diagonal from the serial column sums, the row of ones
+    for (long long i = tid; i < (long long)ld * n; i += 256) M[i] = 0.0;
+    for (int i = tid; i < n; i += 256) b[i] = i == 0 ? 1.0 : 0.0;
+    __syncthreads();
+    {
+        const double *r_ul = a.r_ul_t + s * a.NL, *r_lu = a.r_lu_t + s * a.NL;
+        for (int q = a.sp_line_edge[sp] + tid; q < a.sp_line_edge[sp + 1]; q += 256) {
+            const int l = a.lower[q], u = a.upper[q];
+            M[l + (long long)u * ld] = r_ul[q];
+            M[u + (long long)l * ld] = r_lu[q];
+        }
+    }
+    __syncthreads();
+    for (int c = tid; c < n; c += 256) {
+        double *col = M + (long long)c * ld;
+        double sum = 0.0;
+        for (int r = 0; r < n; ++r)
+            if (r != c) sum += col[r];
+        col[c] = -sum;
+        col[0] = 1.0;
+    }
+    __syncthreads();
+    int code = 0;
+    for (int k = 0; k < n; ++k) {
+        const double *colk = M + (long long)k * ld;
+        // the pivot: every wave for itself
+        double best = -1.0;
+        int p = INT_MAX;
+        for (int i = k + lane; i < n; i += 64) {
+            const double v = fabs(colk[i]);
+            if (nlte_better(v, i, best, p)) { best = v; p = i; }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ov = __shfl_xor(best, off, 64);
+            const int oi = __shfl_xor(p, off, 64);
+            if (nlte_better(ov, oi, best, p)) { best = ov; p = oi; }
+        }
+        const double pv = colk[p], kk = colk[k];
+        if (pv == 0.0 || !nlte_finite(pv)) { code = k + 1; break; }  // (the same in every thread)
+        // the swap of rows k and p right of column k, the multipliers, the pivot
+        if (p != k)
+            for (int j = k + 1 + tid; j < n; j += 256) {
+                double *col = M + (long long)j * ld;
+                const double t = col[k];
+                col[k] = col[p];
+                col[p] = t;
+            }
+        for (int i = k + 1 + tid; i < n; i += 256) lv[i] = (i == p ? kk : colk[i]) / pv;
+        if (tid == 0) {
+            piv[k] = pv;
+            const double t = b[k];
+            b[k] = b[p];
+            b[p] = t;
+        }
+        __syncthreads();
+        for (int j = k + 1 + wave; j < n; j += 4) {
+            double *col = M + (long long)j * ld;
+            const double mkj = col[k];
+            for (int i = k + 1 + lane; i < n; i += 64) col[i] = col[i] - lv[i] * mkj;
+        }
+        {
+            const double bk = b[k];
+            for (int i = k + 1 + tid; i < n; i += 256) b[i] = b[i] - lv[i] * bk;
+        }
+        __syncthreads();
+    }
+    if (code == 0) {
+        for (int j = n - 1; j >= 0; --j) {
+            const double xj = b[j] / piv[j];
+            if (tid == 0) x[j] = xj;
+            const double *col = M + (long long)j * ld;
+            for (int i = tid; i < j; i += 256) b[i] = b[i] - col[i] * xj;
+            __syncthreads();
+        }
+        bool bad = false;  // (every thread reads all of x: no vote, no static LDS beside the dynamic working set)
+        for (int i = 0; i < n; ++i) bad = bad || !nlte_finite(x[i]);
+        if (bad) code = n + 2;
+        else if (x[0] == 0.0) code = n + 1;
+    }
+    if (code == 0) {
+        const int k0 = a.sp_k0[sp], x0 = a.sp_x0[sp];
+        const double g0 = a.g[k0], first = x[0];
+        for (int i = tid; i < n; i += 256) {
+            a.lbf_t[s * a.K + k0 + i] = (x[i] * g0) / first;
+            a.x_t[s * a.NX + x0 + i] = x[i];
+        }
+    }
+    if (tid == 0) a.status[(long long)sp * a.S + s] = code;
+}
+
+}  // namespace mc

@@ -1,0 +1,103 @@
+// nlte_plan.hpp -- the host's decisions of the NLTE excitation stage of tardis_mc_update_plasma as pure functions: which form of the
+// solve kernel a species takes, what the forms cost in LDS and scratch, and the check of a TardisMcNlteData before anything is indexed.
+//
+// Standard C++ only (no HIP header, no context, no device call): tests/test_nlte_excitation_host.py pins the rule through
+// tardis_mc_nlte_solve_path and the check through tardis_mc_check_nlte_data.  The kernels are in nlte_excitation.hpp.
+//
+// A species of n levels is solved per shell by one workgroup on a column-major n x n fp64 matrix of leading dimension ld = n | 1 (odd:
+// a walk along a row then visits 32 different bank pairs) and four vectors of n (b, the multipliers of a step, the pivots, x).  The
+// matrix and the vectors live either in the workgroup's LDS (PATH_LDS) or in a slab of HBM per (species, shell) (PATH_GLOBAL); the code
+// and the order of every operation are the same, so the choice changes no bit of the result, only the time.  A workgroup may declare
+// 163 840 bytes on gfx950: work_bytes(141) = 163 560 fits, work_bytes(142) does not.  Measured (profiles/nlte_excitation.txt, each
+// species alone, all 20 shells): the LDS form is ahead at every size that fits -- 0.010 against 0.012 ms at 2 levels, 0.157 / 0.255
+// at 61, 0.509 / 0.951 at 125 -- so the rule is "LDS whenever it fits".
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace nlte {
+
+constexpr int PATH_LDS = 0, PATH_GLOBAL = 1;
+constexpr long long LDS_LIMIT_BYTES = 163840;             // what one workgroup may declare on gfx950
+constexpr long long MAX_SCRATCH_BYTES = 1LL << 30;        // all slabs of the global form together, over every shell
+// LDS launches go out per size class (dynamic LDS sized for the class's largest species), so that a species of a few levels does not
+// cost the occupancy of one of a hundred
+constexpr long long LDS_CLASS_LEVELS[] = {8, 16, 32, 64, 96, 141};
+constexpr int N_LDS_CLASSES = 6;
+
+inline long long leading_dimension(long long n) { return n | 1; }
+// the matrix and the four vectors b, l, pivots, x
+inline long long work_bytes(long long n) { return n <= 0 ? 0 : 8 * (leading_dimension(n) * n + 4 * n); }
+
+// species of this many levels or more take the global form under the rule: the first size whose working set no longer fits the LDS
+constexpr long long GLOBAL_FORM_LEVELS = 142;
+
+// `threshold` < 0: the rule; otherwise species of `threshold` levels or more take the global form (option nlte_lds_levels).  A species
+// that does not fit the LDS takes the global form whatever the option says.
+inline int choose_path(long long levels, long long threshold = -1)
+{
+    const long long t = threshold < 0 ? GLOBAL_FORM_LEVELS : threshold;
+    if (levels <= 0) return PATH_LDS;
+    return levels >= t || work_bytes(levels) > LDS_LIMIT_BYTES ? PATH_GLOBAL : PATH_LDS;
+}
+
+inline int lds_class(long long levels)
+{
+    for (int c = 0; c < N_LDS_CLASSES; ++c)
+        if (levels <= LDS_CLASS_LEVELS[c]) return c;
+    return N_LDS_CLASSES - 1;
+}
+
+// What tardis_mc_set_nlte_data checks before it indexes anything, on plain arrays: the species against the ions (ion_level_edge[I+1]),
+// the edge table, the line ids against the L lines, every line's two levels against its species' ion, and the (lower, upper) pairs of
+// a species against each other.  Returns "" when the data are good, else the message.  lower_local / upper_local (may be null) receive
+// the local level indices of the NL lines.
+template <typename EdgeT, typename LevelT>
+inline std::string check_data(long long n_species, const int64_t *species_ion, long long n_nlte_lines, const int64_t *species_line_edge,
+                              const int64_t *line_id, long long n_ions, const EdgeT *ion_level_edge, long long n_lines,
+                              const LevelT *level_lower, const LevelT *level_upper, std::vector<int> *lower_local = nullptr,
+                              std::vector<int> *upper_local = nullptr)
+{
+    char buf[256];
+    auto msg = [&](const char *fmt, long long a = 0, long long b = 0, long long c = 0) { snprintf(buf, sizeof buf, fmt, a, b, c); return std::string(buf); };
+    if (n_species <= 0 || n_nlte_lines < 0 || n_species > 0x7ffffff0LL || n_nlte_lines > 0x7ffffff0LL) return msg("invalid NLTE data: %lld species, %lld lines", n_species, n_nlte_lines);
+    if (!species_ion || !species_line_edge || (n_nlte_lines > 0 && !line_id)) return msg("invalid NLTE data: a pointer is missing");
+    std::vector<char> seen((size_t)n_ions, 0);
+    for (long long sp = 0; sp < n_species; ++sp) {
+        const long long i = species_ion[sp];
+        if (i < 0 || i >= n_ions) return msg("species_ion[%lld] = %lld is no ion of the plasma data", sp, i);
+        if (seen[(size_t)i]) return msg("species_ion[%lld] = %lld is repeated", sp, i);
+        seen[(size_t)i] = 1;
+    }
+    if (species_line_edge[0] != 0 || species_line_edge[n_species] != n_nlte_lines) return msg("species_line_edge must run from 0 to n_nlte_lines");
+    for (long long sp = 0; sp < n_species; ++sp)
+        if (species_line_edge[sp + 1] < species_line_edge[sp]) return msg("species_line_edge decreases at species %lld", sp);
+    if (lower_local) lower_local->assign((size_t)n_nlte_lines, 0);
+    if (upper_local) upper_local->assign((size_t)n_nlte_lines, 0);
+    for (long long sp = 0; sp < n_species; ++sp) {
+        const long long k0 = ion_level_edge[species_ion[sp]], k1 = ion_level_edge[species_ion[sp] + 1];
+        const long long a = species_line_edge[sp], b = species_line_edge[sp + 1];
+        std::vector<std::pair<long long, long long>> pairs;
+        pairs.reserve((size_t)(b - a));
+        for (long long q = a; q < b; ++q) {
+            const long long l = line_id[q];
+            if (l < 0 || l >= n_lines) return msg("line_id[%lld] = %lld lies outside the line list", q, l);
+            const long long lo = level_lower[l], up = level_upper[l];
+            if (lo < k0 || lo >= k1 || up < k0 || up >= k1) return msg("NLTE line %lld (line %lld): its levels are not both inside the ion of species %lld", q, l, sp);
+            if (lo == up) return msg("NLTE line %lld (line %lld): lower == upper", q, l);
+            pairs.emplace_back(std::min(lo, up) - k0, std::max(lo, up) - k0);  // (u, l) writes the two entries (l, u) writes
+            if (lower_local) (*lower_local)[(size_t)q] = (int)(lo - k0);
+            if (upper_local) (*upper_local)[(size_t)q] = (int)(up - k0);
+        }
+        std::sort(pairs.begin(), pairs.end());
+        for (size_t q = 1; q < pairs.size(); ++q)
+            if (pairs[q] == pairs[q - 1]) return msg("species %lld: the pair of levels (%lld, %lld) is repeated", sp, pairs[q].first, pairs[q].second);
+    }
+    return std::string();
+}
+
+}  // namespace nlte

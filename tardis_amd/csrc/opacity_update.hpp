@@ -30,6 +30,33 @@ namespace mc {
 
 struct OpacityUpdateConsts { double coef_sobolev, t_exp, planck_coef, h, k_b; };
 
+// j of the dilute black body, W (planck_coef nu^3 / (exp(h nu beta_rad) - 1)): one spelling for the line kernel below, the detailed j_blues'
+// fallbacks and the NLTE rates (nlte_excitation.hpp), whose j have to be these bits
+__device__ __forceinline__ double dilute_black_body_j(double ws, double planck_coef, double h, double nu, double beta_rad)
+{
+    return ws * (planck_coef * (nu * nu * nu) / (mcm::exp(h * nu * beta_rad) - 1));
+}
+
+// One detailed j_blue (radfield_jblue_kernel): the normalised estimator, the dilute black body outside the optical window, w_epsilon times it
+// where the estimator is empty
+__device__ __forceinline__ double detailed_j_blue(double estimator, double norm, double nu, double ws, double beta_rad, double planck_coef, double h,
+                                                  double w_epsilon, double c_ang, int optical_window)
+{
+    const double est = estimator * norm;
+    double value = est;
+    bool outside = false;
+    if (optical_window) {
+        const double wav = c_ang / nu;  // Angstrom
+        outside = !(wav > 2500.0 && wav < 10000.0);
+    }
+    if (est == 0.0 || outside) {
+        const double planck = dilute_black_body_j(ws, planck_coef, h, nu, beta_rad);
+        value = outside ? planck : value;
+        if (est == 0.0) value = w_epsilon * planck;
+    }
+    return value;
+}
+
 // MODE0: j of the dilute black body is computed here; otherwise j_t already holds the detailed j_blues and is only read by the block kernel
 template <bool MODE0>
 __global__ void __launch_bounds__(256) opacity_line_kernel(const double *__restrict__ n_t, const int *__restrict__ level_lower,
@@ -62,7 +89,7 @@ __global__ void __launch_bounds__(256) opacity_line_kernel(const double *__restr
         sef_t[i] = sef;
         if (MODE0) {
             const double nu = nu_line[l];
-            j_t[i] = ws * (k.planck_coef * (nu * nu * nu) / (mcm::exp(k.h * nu * beta_rad) - 1));
+            j_t[i] = dilute_black_body_j(ws, k.planck_coef, k.h, nu, beta_rad);
         }
     }
 }

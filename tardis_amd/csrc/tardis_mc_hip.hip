@@ -41,6 +41,8 @@
 #include "opacity_update_plan.hpp"
 #include "plasma_update.hpp"
 #include "plasma_update_plan.hpp"
+#include "nlte_excitation.hpp"
+#include "nlte_plan.hpp"
 
 static_assert(plan::DBG_WAVE_COUNTERS == mc::WV_DBG_FLAGS, "propagate_plan.hpp repeats the wave kernel's list of counter flags");
 
@@ -344,6 +346,20 @@ struct TardisMcContext {
     long long pl_long_rows = -1;         // option plasma_update_long_rows: -1 the rule of plasma_update_plan.hpp, else the threshold itself
     long long pl_max_iterations = 1000;  // option plasma_max_iterations: bound on the passes of the electron-density iteration
     hipEvent_t ev_pl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // start | Boltzmann | partition | ionisation | populations (tardis_mc_last_plasma_update_ms)
+    // NLTE excitation (nlte_excitation.hpp).  Per set_nlte_data: the species (first level, levels, first row of x, line edges), the lines (their id in
+    // the line list, local levels, Einstein coefficients) and, per value of option nlte_lds_levels, the launches: the LDS form per size class, the
+    // global form with its slab offsets.  Per update_plasma: r_ul / r_lu [S][NL], x [S][NX], the status words [NS][S], the slabs, (mode 1) the shell work.
+    struct NlteLaunch { int first, count; size_t lds_bytes; bool global; };
+    DevBuf nl_line_id, nl_a_ul, nl_b_ul, nl_b_lu, nl_lower, nl_upper, nl_sp_k0, nl_sp_n, nl_sp_x0, nl_sp_line_edge, nl_list, nl_slab;
+    DevBuf nl_r_ul, nl_r_lu, nl_x_t, nl_status, nl_scratch, nl_work;
+    std::vector<int> nl_h_n, nl_h_ion, nl_h_status;
+    std::vector<NlteLaunch> nl_launches;
+    std::vector<int> ou_h_lower, ou_h_upper;  // host copies of the line data's levels: what set_nlte_data checks its lines against
+    bool have_nlte = false, nl_valid = false, nl_timed = false, nl_ran = false;  // (nl_valid: lbf_t and x are those of the last successful update's NLTE stage)
+    int nl_coronal = 0, nl_classical = 0;
+    long long nl_species = 0, nl_lines = 0, nl_nx = 0, nl_scratch_doubles = 0;
+    long long nl_lds_levels = -1, nl_lists_built = -2;  // option nlte_lds_levels: -1 the rule of nlte_plan.hpp, else the threshold itself
+    hipEvent_t ev_nl[3] = {nullptr, nullptr, nullptr};  // start | rates | solve (tardis_mc_last_nlte_ms)
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -644,20 +660,7 @@ __global__ void radfield_jblue_kernel(const double *__restrict__ jblue_t, const 
     const int s = blockIdx.y;
     const double beta = 1 / (k.k_b * t_rad[s]), ws = w[s], ns = norm[s];
     for (long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x; l < L; l += (long long)gridDim.x * blockDim.x) {
-        const double nu = nu_line[l];
-        const double est = jblue_t[(long long)s * L + l] * ns;
-        double value = est;
-        bool outside = false;
-        if (optical_window) {
-            const double wav = k.c_ang / nu;  // Angstrom
-            outside = !(wav > 2500.0 && wav < 10000.0);
-        }
-        if (est == 0.0 || outside) {
-            const double planck = ws * (k.planck_coef * (nu * nu * nu) / (mcm::exp(k.h * nu * beta) - 1));
-            value = outside ? planck : value;
-            if (est == 0.0) value = k.w_epsilon * planck;
-        }
-        out_t[(long long)s * L + l] = value;
+        out_t[(long long)s * L + l] = mc::detailed_j_blue(jblue_t[(long long)s * L + l], ns, nu_line[l], ws, beta, k.planck_coef, k.h, k.w_epsilon, k.c_ang, optical_window);
     }
 }
 
@@ -2059,6 +2062,10 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     ctx->drain_census.release();
     for (hipEvent_t e : ctx->ev_ou) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_pl) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ev_nl) if (e) (void)hipEventDestroy(e);
+    for (DevBuf *b : {&ctx->nl_line_id, &ctx->nl_a_ul, &ctx->nl_b_ul, &ctx->nl_b_lu, &ctx->nl_lower, &ctx->nl_upper, &ctx->nl_sp_k0, &ctx->nl_sp_n, &ctx->nl_sp_x0,
+                      &ctx->nl_sp_line_edge, &ctx->nl_list, &ctx->nl_slab, &ctx->nl_r_ul, &ctx->nl_r_lu, &ctx->nl_x_t, &ctx->nl_status, &ctx->nl_scratch, &ctx->nl_work})
+        b->release();
     for (DevBuf *b : {&ctx->pl_energy, &ctx->pl_g, &ctx->pl_meta, &ctx->pl_level_ion, &ctx->pl_ion_edge, &ctx->pl_elem_edge, &ctx->pl_charge, &ctx->pl_chi,
                       &ctx->pl_zeta_t, &ctx->pl_zeta, &ctx->pl_density, &ctx->pl_long_ions, &ctx->pl_lbf_t, &ctx->pl_z, &ctx->pl_phi, &ctx->pl_n_ion,
                       &ctx->pl_n_e, &ctx->pl_status})
@@ -2161,6 +2168,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "opacity_update_long_rows") ctx->ou_long_rows = value < 0 ? -1 : value;
     else if (n == "plasma_update_long_rows") ctx->pl_long_rows = value < 0 ? -1 : value;
     else if (n == "plasma_max_iterations") ctx->pl_max_iterations = std::max<long long>(1, value);
+    else if (n == "nlte_lds_levels") ctx->nl_lds_levels = value < 0 ? -1 : value;
     else return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return TARDIS_MC_OK;
 }
@@ -2412,6 +2420,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     ctx->h_macro = macro;
     ctx->have_line_data = ctx->ou_valid = false;  // (the line data belong to one topology: tardis_mc_set_line_data again)
     ctx->have_plasma_data = ctx->pl_valid = false;  // (... and the plasma data to one set of line data)
+    ctx->have_nlte = ctx->nl_valid = false;
     tmark("index tables int32 up");
     {   // packed macro-atom tables of the cooperative kernel
         std::vector<int> lb(2 * (macro ? L : 1), 0), rec(4 * (macro ? T : 1), 0);
@@ -3959,6 +3968,7 @@ int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
     if (!ctx->have_opacity) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity must precede set_line_data");
     ctx->have_line_data = ctx->ou_valid = false;
     ctx->have_plasma_data = ctx->pl_valid = false;  // (the plasma data sit on the levels of one set of line data)
+    ctx->have_nlte = ctx->nl_valid = false;
     const size_t L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans;
     if (d->n_lines != (int64_t)L || d->n_transitions != (int64_t)T)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "line data of %lld lines / %lld transitions, the resident opacity state has %zu / %zu",
@@ -3995,6 +4005,8 @@ int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
     if ((rc = upload(ctx, ctx->ou_level_upper, up.data(), L))) return rc;
     if (coef && (rc = upload(ctx, ctx->ou_coef, d->transition_probability_coef, T))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (lo / up are the sources of asynchronous copies)
+    ctx->ou_h_lower.swap(lo);
+    ctx->ou_h_upper.swap(up);
     ctx->ou_levels = d->n_levels;
     ctx->ou_have_coef = coef;
     ctx->ou_sobolev_coefficient = d->sobolev_coefficient;
@@ -4188,6 +4200,7 @@ int tardis_mc_set_plasma_data(TardisMcContext *ctx, const TardisMcPlasmaData *d)
     if (!ctx || !d) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_opacity || !ctx->have_line_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_line_data must precede set_plasma_data");
     ctx->have_plasma_data = ctx->pl_valid = false;
+    ctx->have_nlte = ctx->nl_valid = false;  // (the NLTE species are ions of one set of plasma data)
     if (d->n_levels != ctx->ou_levels)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "plasma data of %lld levels, the line data have %lld", (long long)d->n_levels, ctx->ou_levels);
     if (d->n_shells != ctx->n_shells)
@@ -4241,6 +4254,206 @@ int tardis_mc_set_plasma_data(TardisMcContext *ctx, const TardisMcPlasmaData *d)
     return TARDIS_MC_OK;
 }
 
+/* ---- NLTE excitation of selected species inside update_plasma (nlte_excitation.hpp) ------------------------ */
+int tardis_mc_nlte_solve_path(int64_t levels) { return nlte::choose_path((long long)levels); }
+
+int tardis_mc_check_nlte_data(const TardisMcNlteData *d, int64_t n_ions, const int64_t *ion_level_edge, int64_t n_lines, const int64_t *level_lower,
+                              const int64_t *level_upper)
+{
+    if (!d || n_ions <= 0 || !ion_level_edge || n_lines < 0 || !level_lower || !level_upper) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid NLTE data");
+    if (d->n_nlte_lines > 0 && (!d->A_ul || !d->B_ul || !d->B_lu)) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid NLTE data: a pointer is missing");
+    const std::string err = nlte::check_data((long long)d->n_species, d->species_ion, (long long)d->n_nlte_lines, d->species_line_edge, d->line_id, (long long)n_ions,
+                                             ion_level_edge, (long long)n_lines, level_lower, level_upper);
+    return err.empty() ? TARDIS_MC_OK : fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+}
+
+// The launches of the solve kernel for the current value of option nlte_lds_levels: the species of the LDS form by size class, those of the global form
+// with the offsets of their slabs.  TARDIS_MC_ERR_UNSUPPORTED when the slabs of all shells together exceed nlte::MAX_SCRATCH_BYTES.
+static int nlte_build_lists(TardisMcContext *ctx)
+{
+    const long long NS = ctx->nl_species, S = ctx->n_shells;
+    std::vector<int> list;
+    std::vector<long long> slab;
+    std::vector<TardisMcContext::NlteLaunch> launches;
+    for (int c = 0; c < nlte::N_LDS_CLASSES; ++c) {
+        const int first = (int)list.size();
+        long long largest = 0;
+        for (long long sp = 0; sp < NS; ++sp) {
+            const long long n = ctx->nl_h_n[(size_t)sp];
+            if (nlte::choose_path(n, ctx->nl_lds_levels) == nlte::PATH_LDS && nlte::lds_class(n) == c) { list.push_back((int)sp); largest = std::max(largest, n); }
+        }
+        if ((int)list.size() > first) launches.push_back({first, (int)list.size() - first, (size_t)nlte::work_bytes(largest), false});
+    }
+    slab.assign(list.size(), 0);
+    const int first = (int)list.size();
+    long long doubles = 0;
+    for (long long sp = 0; sp < NS; ++sp) {
+        const long long n = ctx->nl_h_n[(size_t)sp];
+        if (nlte::choose_path(n, ctx->nl_lds_levels) != nlte::PATH_GLOBAL) continue;
+        list.push_back((int)sp);
+        slab.push_back(doubles);
+        const long long bytes = nlte::work_bytes(n) * S;
+        if (bytes > nlte::MAX_SCRATCH_BYTES || doubles * 8 + bytes > nlte::MAX_SCRATCH_BYTES)
+            return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "NLTE species %lld (ion %d, %lld levels) needs %lld bytes of scratch over %lld shells in the global-memory form of the "
+                        "solve: with the %lld bytes of the species before it that exceeds the %lld the plan allows", sp, ctx->nl_h_ion[(size_t)sp], n, bytes, S, doubles * 8,
+                        nlte::MAX_SCRATCH_BYTES);
+        doubles += bytes / 8;
+    }
+    if ((int)list.size() > first) launches.push_back({first, (int)list.size() - first, 0, true});
+    size_t lds = 0;
+    for (const TardisMcContext::NlteLaunch &l : launches)
+        if (!l.global) lds = std::max(lds, l.lds_bytes);
+    if (lds > 65536)  // (a launch with more dynamic LDS than the default bound has to announce it: once per list, not per update)
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&mc::nlte_solve_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int rc;
+    if ((rc = upload(ctx, ctx->nl_list, list.data(), list.size()))) return rc;
+    if ((rc = upload(ctx, ctx->nl_slab, slab.data(), slab.size()))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->nl_launches.swap(launches);
+    ctx->nl_scratch_doubles = doubles;
+    ctx->nl_lists_built = ctx->nl_lds_levels;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_set_nlte_data(TardisMcContext *ctx, const TardisMcNlteData *d)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_plasma_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_plasma_data must precede set_nlte_data");
+    ctx->have_nlte = ctx->nl_valid = false;
+    if (!d) return TARDIS_MC_OK;
+    if (d->n_nlte_lines > 0 && (!d->A_ul || !d->B_ul || !d->B_lu)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid NLTE data: a pointer is missing");
+    // everything the kernels index with is checked here, on the host
+    std::vector<int> lower, upper;
+    const std::string err = nlte::check_data((long long)d->n_species, d->species_ion, (long long)d->n_nlte_lines, d->species_line_edge, d->line_id, (long long)ctx->pl_ions,
+                                             ctx->pl_h_ion_edge.data(), (long long)ctx->n_lines, ctx->ou_h_lower.data(), ctx->ou_h_upper.data(), &lower, &upper);
+    if (!err.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+    const size_t NS = (size_t)d->n_species, NL = (size_t)d->n_nlte_lines;
+    std::vector<int> k0(NS), n(NS), x0(NS), ion(NS), edge(NS + 1), line_id(NL);
+    long long nx = 0;
+    for (size_t sp = 0; sp < NS; ++sp) {
+        ion[sp] = (int)d->species_ion[sp];
+        k0[sp] = ctx->pl_h_ion_edge[(size_t)ion[sp]];
+        n[sp] = ctx->pl_h_ion_edge[(size_t)ion[sp] + 1] - k0[sp];
+        x0[sp] = (int)nx;
+        nx += n[sp];
+    }
+    for (size_t sp = 0; sp <= NS; ++sp) edge[sp] = (int)d->species_line_edge[sp];
+    for (size_t q = 0; q < NL; ++q) line_id[q] = (int)d->line_id[q];
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->nl_species = (long long)NS; ctx->nl_lines = (long long)NL; ctx->nl_nx = nx;
+    ctx->nl_h_n = n; ctx->nl_h_ion = ion;
+    int rc;
+    if ((rc = nlte_build_lists(ctx))) return rc;
+    if ((rc = upload(ctx, ctx->nl_line_id, line_id.data(), NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl_a_ul, d->A_ul, NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl_b_ul, d->B_ul, NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl_b_lu, d->B_lu, NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl_lower, lower.data(), NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl_upper, upper.data(), NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl_sp_k0, k0.data(), NS))) return rc;
+    if ((rc = upload(ctx, ctx->nl_sp_n, n.data(), NS))) return rc;
+    if ((rc = upload(ctx, ctx->nl_sp_x0, x0.data(), NS))) return rc;
+    if ((rc = upload(ctx, ctx->nl_sp_line_edge, edge.data(), NS + 1))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors are the sources of asynchronous copies)
+    ctx->nl_coronal = d->coronal_approximation != 0;
+    ctx->nl_classical = d->classical_nebular != 0;
+    ctx->have_nlte = true;
+    return TARDIS_MC_OK;
+}
+
+// What the NLTE stage needs before the update's first kernel: the launches for the current option, the buffers of a call.
+static int nlte_prepare(TardisMcContext *ctx)
+{
+    int rc;
+    if (ctx->nl_lists_built != ctx->nl_lds_levels && (rc = nlte_build_lists(ctx))) return rc;
+    const size_t S = (size_t)ctx->n_shells, NL = (size_t)ctx->nl_lines;
+    HIP_TRY(ctx, ctx->nl_r_ul.ensure(std::max<size_t>(1, NL * S) * sizeof(double)));
+    HIP_TRY(ctx, ctx->nl_r_lu.ensure(std::max<size_t>(1, NL * S) * sizeof(double)));
+    HIP_TRY(ctx, ctx->nl_x_t.ensure((size_t)ctx->nl_nx * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->nl_status.ensure((size_t)ctx->nl_species * S * sizeof(int)));
+    HIP_TRY(ctx, ctx->nl_scratch.ensure(std::max<size_t>(1, (size_t)ctx->nl_scratch_doubles) * sizeof(double)));
+    return TARDIS_MC_OK;
+}
+
+// The NLTE stage of an update, enqueued behind the Boltzmann kernel: the rates of the species' lines from the j of this update and the beta of the
+// previous one, then a workgroup per (species, shell) that overwrites the species' rows of lbf_t.  d_t / d_w: the call's (t_rad, W) on the device.
+static int nlte_stage(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p, const double *beta_t, const double *d_t, const double *d_w)
+{
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, NL = (size_t)ctx->nl_lines;
+    const double h = 6.62606957e-27, k_b = 1.3806488e-16, c = mc::C_LIGHT;  // tardis/constants.py (CODATA 2010, cgs): those of the line kernel
+    int rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_nl[0], ctx->stream));
+    mc::NlteRateArgs r{};
+    r.S = (int)S; r.L = (long long)L; r.NL = (long long)NL;
+    r.line_id = ctx->nl_line_id.as<int>(); r.a_ul = ctx->nl_a_ul.as<double>(); r.b_ul = ctx->nl_b_ul.as<double>(); r.b_lu = ctx->nl_b_lu.as<double>();
+    r.nu_line = ctx->nu_line.as<double>(); r.beta_t = beta_t; r.t_rad = d_t; r.w = d_w;
+    r.planck_coef = 2 * h / (c * c); r.h = h; r.k_b = k_b; r.w_epsilon = p->w_epsilon; r.c_ang = c * 1e8; r.optical_window = p->detailed_optical_window;
+    r.r_ul_t = ctx->nl_r_ul.as<double>(); r.r_lu_t = ctx->nl_r_lu.as<double>();
+    const int jmode = ctx->nl_coronal ? mc::NLTE_J_CORONAL : p->j_blues_mode == 1 ? mc::NLTE_J_DETAILED : mc::NLTE_J_DILUTE;
+    if (jmode == mc::NLTE_J_DETAILED) {  // the estimators' own t_rad / W / norm, as the j_blues kernel of the stages behind will compute them again
+        if ((rc = radiation_field_enqueue(ctx, p->time_of_simulation, p->volume, p->w_epsilon, p->detailed_optical_window, ctx->nl_work, nullptr))) return rc;
+        EstLayout e = est_layout(ctx->est_S, ctx->est_L, ctx->est_G, ctx->est_copies);
+        const double *work = ctx->nl_work.as<double>();
+        r.t_rad = work + S; r.w = work + 2 * S; r.norm = work + 3 * S; r.jblue_t = ctx->est.as<double>() + e.jblue;
+    }
+    if (NL > 0) {
+        const unsigned bx = (unsigned)std::min<size_t>((NL + 255) / 256, 1024);
+        auto kernel = jmode == mc::NLTE_J_CORONAL ? mc::nlte_rates_kernel<mc::NLTE_J_CORONAL>
+                      : jmode == mc::NLTE_J_DETAILED ? mc::nlte_rates_kernel<mc::NLTE_J_DETAILED> : mc::nlte_rates_kernel<mc::NLTE_J_DILUTE>;
+        hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, r);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_nl[1], ctx->stream));
+    mc::NlteSolveArgs a{};
+    a.S = (int)S; a.K = ctx->ou_levels; a.NL = (long long)NL; a.NX = ctx->nl_nx;
+    a.sp_k0 = ctx->nl_sp_k0.as<int>(); a.sp_n = ctx->nl_sp_n.as<int>(); a.sp_x0 = ctx->nl_sp_x0.as<int>(); a.sp_line_edge = ctx->nl_sp_line_edge.as<int>();
+    a.lower = ctx->nl_lower.as<int>(); a.upper = ctx->nl_upper.as<int>(); a.r_ul_t = r.r_ul_t; a.r_lu_t = r.r_lu_t; a.g = ctx->pl_g.as<double>();
+    a.lbf_t = ctx->pl_lbf_t.as<double>(); a.x_t = ctx->nl_x_t.as<double>(); a.status = ctx->nl_status.as<int>(); a.scratch = ctx->nl_scratch.as<double>();
+    for (const TardisMcContext::NlteLaunch &l : ctx->nl_launches) {
+        a.list = ctx->nl_list.as<int>() + l.first;
+        a.slab = ctx->nl_slab.as<long long>() + l.first;
+        if (l.global) hipLaunchKernelGGL(mc::nlte_solve_kernel<false>, dim3((unsigned)l.count, (unsigned)S), dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(mc::nlte_solve_kernel<true>, dim3((unsigned)l.count, (unsigned)S), dim3(256), l.lds_bytes, ctx->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_nl[2], ctx->stream));
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_nlte(TardisMcContext *ctx, double *level_boltzmann_factor, double *relative_populations)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->nl_valid || !ctx->pl_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "get_nlte needs a successful update_plasma that ran the NLTE stage");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou_levels, NX = (size_t)ctx->nl_nx;
+    auto down = [&](double *host, const double *table_t, size_t rows) -> int {  // [S][rows] -> [rows,S]
+        if (!host) return TARDIS_MC_OK;
+        HIP_TRY(ctx, ctx->staging.ensure(rows * S * sizeof(double)));
+        HIP_TRY(ctx, launch_transpose(ctx->stream, table_t, ctx->staging.as<double>(), (long long)S, (long long)rows));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, host_copy(ctx, {{(void *)host, ctx->staging.p, rows * S * sizeof(double)}}, false));
+        return TARDIS_MC_OK;
+    };
+    int rc;
+    if ((rc = down(level_boltzmann_factor, ctx->pl_lbf_t.as<double>(), K))) return rc;
+    if ((rc = down(relative_populations, ctx->nl_x_t.as<double>(), NX))) return rc;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_last_nlte_ms(TardisMcContext *ctx, double *out_assemble_ms, double *out_solve_ms)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->nl_timed || !ctx->pl_timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_plasma with an NLTE stage has been timed yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_nl[2]));
+    float a = 0.f, b = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&a, ctx->ev_nl[0], ctx->ev_nl[1]));
+    HIP_TRY(ctx, hipEventElapsedTime(&b, ctx->ev_nl[1], ctx->ev_nl[2]));
+    if (out_assemble_ms) *out_assemble_ms = a;
+    if (out_solve_ms) *out_solve_ms = b;
+    return TARDIS_MC_OK;
+}
+
 int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
 {
     if (!ctx || !p || !p->t_radiative || !p->dilution_factor) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid plasma update");
@@ -4275,6 +4488,10 @@ int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
         ctx->pl_long_rows_built = ctx->pl_long_rows;
     }
     if ((rc = opacity_update_buffers(ctx))) return rc;
+    const bool nlte = ctx->have_nlte;
+    // beta_sobolev of the previous update, read before this update's line kernel writes over it; none since the last set_opacity: 1.0
+    const double *nlte_beta = ctx->ou_valid && !ctx->nl_classical ? ctx->ou_beta_t.as<double>() : nullptr;
+    if (nlte && (rc = nlte_prepare(ctx))) return rc;
     HIP_TRY(ctx, ctx->pl_lbf_t.ensure(K * S * sizeof(double)));
     HIP_TRY(ctx, ctx->pl_z.ensure(I * S * sizeof(double)));
     HIP_TRY(ctx, ctx->pl_phi.ensure(I * S * sizeof(double)));
@@ -4283,13 +4500,17 @@ int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
     HIP_TRY(ctx, ctx->pl_status.ensure(2 * sizeof(int)));
     // Z, N and n_e are rewritten from here on; the resident n_t, the electron densities and the opacity tables only once the iteration has succeeded
     ctx->pl_valid = false;
+    ctx->nl_valid = false;
     double *d_t = ctx->ou_shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
     HIP_TRY(ctx, hipMemcpyAsync(d_t, p->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_w, p->dilution_factor, S * 8, hipMemcpyHostToDevice, ctx->stream));
+    ctx->nl_ran = ctx->nl_timed = false;
     ctx->pl_timed = false;  // (ou_timed and the ev_ou events stay the previous update's until this solve has succeeded)
     for (hipEvent_t &e : ctx->ev_ou)
         if (!e) HIP_TRY(ctx, hipEventCreate(&e));
     for (hipEvent_t &e : ctx->ev_pl)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    for (hipEvent_t &e : ctx->ev_nl)
         if (!e) HIP_TRY(ctx, hipEventCreate(&e));
     const double k_b = 1.3806488e-16, h = 6.62606957e-27, m_e = 9.10938291e-28;  // tardis/constants.py (CODATA 2010, cgs)
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
@@ -4302,6 +4523,7 @@ int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[1], ctx->stream));
+    if (nlte && (rc = nlte_stage(ctx, p, nlte_beta, d_t, d_w))) return rc;  // the NLTE species' Boltzmann factors, before anything reads them
     {
         const long long n_long = ctx->pl_n_long;
         const long long long_levels = ctx->pl_long_rows < 0 ? plup::LONG_ION_LEVELS : ctx->pl_long_rows;
@@ -4335,13 +4557,30 @@ int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
     HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[3], ctx->stream));
     int status[2] = {mc::PLASMA_NAN, 0};
     HIP_TRY(ctx, hipMemcpyAsync(status, ctx->pl_status.p, sizeof status, hipMemcpyDeviceToHost, ctx->stream));
+    if (nlte) {  // the status words of the NLTE solves, read with {status, passes}
+        ctx->nl_h_status.assign((size_t)ctx->nl_species * S, -1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->nl_h_status.data(), ctx->nl_status.p, ctx->nl_h_status.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->pl_iterations = status[1];
-    if (status[0] != mc::PLASMA_OK) {  // a failed solve: tardis_mc_last_propagate_ms reports its kernels, a matching pair of events
+    long long nlte_failed = -1;
+    if (nlte)
+        for (size_t q = 0; q < ctx->nl_h_status.size() && nlte_failed < 0; ++q)
+            if (ctx->nl_h_status[q] != 0) nlte_failed = (long long)q;
+    if (status[0] != mc::PLASMA_OK || nlte_failed >= 0) {  // a failed solve: tardis_mc_last_propagate_ms reports its kernels, a matching pair of events
         HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         ctx->timed = true;
         ctx->chunks_timed = 0;
+    }
+    if (nlte_failed >= 0) {  // (whatever the stages behind it made of the unfinished Boltzmann factors)
+        const long long sp = nlte_failed / (long long)S, shell = nlte_failed % (long long)S;
+        const int code = ctx->nl_h_status[(size_t)nlte_failed], n = ctx->nl_h_n[(size_t)sp];
+        if (code >= 1 && code <= n)
+            return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the NLTE solve of species %lld (ion %d, %d levels) in shell %lld met a zero or non-finite pivot in elimination "
+                        "step %d (singular rate matrix); the opacity state is unchanged", sp, ctx->nl_h_ion[(size_t)sp], n, shell, code - 1);
+        return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the NLTE solve of species %lld (ion %d, %d levels) in shell %lld gave %s after all %d elimination steps; the "
+                    "opacity state is unchanged", sp, ctx->nl_h_ion[(size_t)sp], n, shell, code == n + 1 ? "x[0] == 0" : "a population that is not finite", n);
     }
     if (status[0] == mc::PLASMA_NAN)
         return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the electron density became NaN in pass %d (PlasmaIonizationError); the opacity state is unchanged", status[1] + 1);
@@ -4364,6 +4603,7 @@ int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
     if ((rc = opacity_update_stages(ctx, &u))) return rc;
     ctx->pl_timed = true;
     ctx->pl_valid = true;
+    ctx->nl_ran = ctx->nl_valid = ctx->nl_timed = nlte;
     return TARDIS_MC_OK;
 }
 
@@ -4376,7 +4616,8 @@ int tardis_mc_last_plasma_update_ms(TardisMcContext *ctx, double *out_boltzmann_
     double *out[4] = {out_boltzmann_ms, out_partition_ms, out_ionization_ms, out_population_ms};
     for (int k = 0; k < 4; ++k) {
         float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_pl[k], ctx->ev_pl[k + 1]));
+        // (the NLTE stage sits between the Boltzmann and the partition stage and has events of its own: tardis_mc_last_nlte_ms)
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, k == 1 && ctx->nl_ran ? ctx->ev_nl[2] : ctx->ev_pl[k], ctx->ev_pl[k + 1]));
         if (out[k]) *out[k] = ms;
     }
     return TARDIS_MC_OK;

@@ -51,6 +51,8 @@ class Engine:
         self.n_transitions = 0
         self.line_data = None        # the object whose data set_line_data() uploaded (None after every set_opacity / run)
         self.plasma_data = None      # ... and set_plasma_data() (None after every set_opacity / set_line_data / run)
+        self.nlte_data = None        # ... and set_nlte_data() (None after whatever drops the plasma data)
+        self.n_nlte_levels = 0
         self.n_plasma_levels = self.n_ions = 0
         self.opacity_generation = 0  # bumped whenever the resident opacity tables are replaced (lazy DeviceOpacityState views check it)
         self._vpk_log = False
@@ -118,6 +120,7 @@ class Engine:
         self.resident_opacity = None  # (a failed upload leaves the tables undefined)
         self.line_data = None
         self.plasma_data = None
+        self.nlte_data = None
         self.opacity_generation += 1
         self._check(self._L.tardis_mc_set_opacity(self._h, m.ref()), "set_opacity")
         self.n_lines, self.n_shells = int(m.struct.n_lines), int(m.struct.n_shells)
@@ -133,6 +136,7 @@ class Engine:
         m = _abi.marshal_line_data(line_data, self.n_transitions)
         self.line_data = None
         self.plasma_data = None
+        self.nlte_data = None
         self._check(self._L.tardis_mc_set_line_data(self._h, m.ref()), "set_line_data")
         self.line_data = line_data
 
@@ -185,6 +189,7 @@ class Engine:
         later set_opacity() or set_line_data() drops them."""
         m = _abi.marshal_plasma_data(plasma_data)
         self.plasma_data = None
+        self.nlte_data = None
         self._check(self._L.tardis_mc_set_plasma_data(self._h, m.ref()), "set_plasma_data")
         self.n_plasma_levels, self.n_ions = int(m.struct.n_levels), int(m.struct.n_ions)
         self.plasma_data = plasma_data
@@ -235,6 +240,44 @@ class Engine:
         out = dict(zip(("boltzmann_ms", "partition_ms", "ionization_ms", "population_ms"), (x.value for x in v)))
         out.update(self.last_opacity_update_ms())
         return out
+
+    def set_nlte_data(self, nlte_data):
+        """The NLTE species of update_plasma() (`tardis_mc_set_nlte_data`), after set_plasma_data(): an object with the fields of
+        ``synthetic.NlteData`` -- the species' ions, their lines in the line list with A_ul, B_ul and B_lu, and the flags
+        coronal_approximation and classical_nebular.  From then on update_plasma() replaces the species' level Boltzmann factors by
+        those of the statistical equilibrium of the radiative rates; a failed solve is a RuntimeError with ``code`` ERR_STATE that
+        leaves the resident tables as they were.  None removes the data; whatever drops the plasma data drops them too."""
+        self.nlte_data = None
+        if nlte_data is None:
+            self._check(self._L.tardis_mc_set_nlte_data(self._h, None), "set_nlte_data")
+            return
+        m = _abi.marshal_nlte_data(nlte_data)
+        self._check(self._L.tardis_mc_set_nlte_data(self._h, m.ref()), "set_nlte_data")
+        edge = np.asarray(self.plasma_data.ion_level_edge)
+        self.n_nlte_levels = int(np.sum(np.diff(edge)[np.asarray(nlte_data.species_ion, dtype=np.int64)]))
+        self.nlte_data = nlte_data
+
+    def get_nlte(self, level_boltzmann_factor=True, relative_populations=True) -> dict:
+        """What the NLTE stage of the last update_plasma() produced (`tardis_mc_get_nlte`): level_boltzmann_factor
+        [n_levels, n_shells] (every level; the NLTE species' rows replaced) and relative_populations, the solutions x of the
+        species one after the other, [sum of their levels, n_shells]."""
+        S = self.n_shells
+        want = (("level_boltzmann_factor", level_boltzmann_factor, self.n_plasma_levels), ("relative_populations", relative_populations, self.n_nlte_levels))
+        out = {name: np.empty((rows, S)) for name, on, rows in want if on}
+        self._check(self._L.tardis_mc_get_nlte(self._h, *(out[name].ctypes.data if on else None for name, on, _ in want)), "get_nlte")
+        return out
+
+    def last_nlte_ms(self) -> dict:
+        """Device time (ms) of the NLTE stage of the last update_plasma(): {"assemble_ms" (the rates of the NLTE lines), "solve_ms"
+        (the (species, shell) workgroups: matrix, elimination, substitution)}."""
+        a, b = C.c_double(), C.c_double()
+        self._check(self._L.tardis_mc_last_nlte_ms(self._h, C.byref(a), C.byref(b)), "last_nlte_ms")
+        return {"assemble_ms": a.value, "solve_ms": b.value}
+
+    @staticmethod
+    def nlte_solve_path(levels: int) -> str:
+        """The form of the NLTE solve kernel for a species of ``levels`` levels: "lds" or "global"; csrc/nlte_plan.hpp."""
+        return ("lds", "global")[int(_lib.lib().tardis_mc_nlte_solve_path(int(levels)))]
 
     @staticmethod
     def plasma_update_path(levels: int) -> str:
@@ -419,6 +462,7 @@ class Engine:
         self.resident_opacity = None
         self.line_data = None
         self.plasma_data = None
+        self.nlte_data = None
         self.opacity_generation += 1
         self.results_generation += 1
         self.estimators_generation += 1

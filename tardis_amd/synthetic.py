@@ -392,3 +392,84 @@ def make_plasma_data(seed: int, line_data: LineData, n_shells: int, n_elements: 
         t_rad, w = 10000.0 - 150.0 * np.arange(S), 0.4 / (1.0 + 0.2 * np.arange(S))
     return PlasmaData(level_energy, level_g, level_meta, ion_level_edge, element_ion_edge, ion_charge, chi, zeta_t, zeta, number_density,
                       float(CHI_0_CA_II), 0.9, atomic_number, t_rad.copy(), w.copy())
+
+
+# 4 pi^2 e^2 / (h m_e c), CODATA 2010 cgs: B_lu = EINSTEIN_COEFFICIENT f_lu / nu (the atomic data's lines preparation)
+EINSTEIN_COEFFICIENT = 4.0 * np.pi**2 * 4.80320450e-10**2 / (6.62606957e-27 * 9.10938291e-28 * st.C_SPEED_OF_LIGHT)
+
+
+def lines_within_ions(seed: int, line_data: LineData, plasma_data: PlasmaData) -> LineData:
+    """``line_data`` with every line moved between two levels of ONE ion of ``plasma_data``, as the lines of real atomic data are
+    (make_line_data deals its lines over all levels, which is all the opacity update needs): per ion of n >= 2 levels first the n - 1
+    lines of a ladder (k, k + 1), so that every level of an ion is reached, then the remaining lines dealt to the ions in proportion to
+    their number of level pairs, each between two different levels drawn uniformly (lower index < upper index).  The statistical
+    weights follow the plasma data's level_g; everything else is kept."""
+    from dataclasses import replace
+    rng = np.random.default_rng(seed + 15485863)
+    edge = np.asarray(plasma_data.ion_level_edge, dtype=np.int64)
+    n = np.diff(edge)
+    L = len(line_data.f_lu)
+    if L < int((n - 1).sum()):
+        raise ValueError("fewer lines than the ladders of the ions need")
+    lower = np.concatenate([np.arange(a, b - 1) for a, b in zip(edge[:-1], edge[1:])]).astype(np.int64)
+    upper = lower + 1
+    rest = L - len(lower)
+    pairs = (n * (n - 1)).astype(np.float64)
+    ion = rng.choice(len(n), rest, p=pairs / pairs.sum())
+    a = rng.integers(0, n[ion])
+    b = rng.integers(0, n[ion] - 1)
+    b = np.where(b >= a, b + 1, b)
+    lower = np.concatenate((lower, edge[ion] + np.minimum(a, b)))
+    upper = np.concatenate((upper, edge[ion] + np.maximum(a, b)))
+    order = rng.permutation(L)
+    lower, upper = lower[order], upper[order]
+    g = np.asarray(plasma_data.level_g, dtype=np.float64)
+    return replace(line_data, level_lower=lower, level_upper=upper, g_lower=g[lower], g_upper=g[upper])
+
+
+@dataclass
+class NlteData:
+    """The NLTE species of Engine.set_nlte_data: their ions, their lines in the line list and the lines' Einstein coefficients."""
+    species_ion: np.ndarray         # [NS] indices into the plasma data's ions
+    species_line_edge: np.ndarray   # [NS+1]
+    line_id: np.ndarray             # [NL] indices into the line list
+    A_ul: np.ndarray                # [NL]
+    B_ul: np.ndarray                # [NL]
+    B_lu: np.ndarray                # [NL]
+    coronal_approximation: bool = False
+    classical_nebular: bool = False
+
+
+def make_nlte_data(seed: int, line_data: LineData, plasma_data: PlasmaData, species=None, coronal_approximation: bool = False,
+                   classical_nebular: bool = False, untouched_level=None) -> NlteData:
+    """The NLTE data of the ions ``species`` (indices into ``plasma_data``'s ions; None: the ion with the most levels): a species'
+    lines are those of ``line_data`` whose two levels both lie in its ion (lines_within_ions makes every line such a line), in a
+    seeded order, the first of several lines between the same two levels kept -- every pair is unique.  B_lu = C f_lu / nu with
+    C = 4 pi^2 e^2 / (h m_e c), B_ul = B_lu g_lower / g_upper, A_ul = (2 h nu^3 / c^2) B_ul: with f_lu over three decades and nu
+    over the line list the rates span the many orders of magnitude real ones do.  ``untouched_level`` = (position in species, local
+    level) drops every line of that level, which makes the species' rate matrix exactly singular."""
+    rng = np.random.default_rng(seed + 32452843)
+    edge = np.asarray(plasma_data.ion_level_edge, dtype=np.int64)
+    if species is None:
+        species = [int(np.argmax(np.diff(edge)))]
+    species = np.asarray(species, dtype=np.int64)
+    lower, upper = np.asarray(line_data.level_lower, dtype=np.int64), np.asarray(line_data.level_upper, dtype=np.int64)
+    ids, line_edge = [], [0]
+    for pos, i in enumerate(species):
+        k0, k1 = edge[i], edge[i + 1]
+        own = np.flatnonzero((lower >= k0) & (lower < k1) & (upper >= k0) & (upper < k1) & (lower != upper))
+        own = own[rng.permutation(len(own))]
+        lo, hi = np.minimum(lower[own], upper[own]), np.maximum(lower[own], upper[own])
+        _, first = np.unique(lo * (k1 - k0 + 1) * 2 + hi, return_index=True)
+        own = own[np.sort(first)]
+        if untouched_level is not None and untouched_level[0] == pos:
+            k = k0 + int(untouched_level[1])
+            own = own[(lower[own] != k) & (upper[own] != k)]
+        ids.append(own)
+        line_edge.append(line_edge[-1] + len(own))
+    line_id = np.concatenate(ids).astype(np.int64) if ids else np.zeros(0, dtype=np.int64)
+    nu = st.C_SPEED_OF_LIGHT / np.asarray(line_data.wavelength_cm, dtype=np.float64)[line_id]
+    b_lu = EINSTEIN_COEFFICIENT * np.asarray(line_data.f_lu, dtype=np.float64)[line_id] / nu
+    b_ul = b_lu * np.asarray(line_data.g_lower, dtype=np.float64)[line_id] / np.asarray(line_data.g_upper, dtype=np.float64)[line_id]
+    a_ul = (2.0 * 6.62606957e-27 * nu**3 / st.C_SPEED_OF_LIGHT**2) * b_ul
+    return NlteData(species, np.asarray(line_edge, dtype=np.int64), line_id, a_ul, b_ul, b_lu, bool(coronal_approximation), bool(classical_nebular))

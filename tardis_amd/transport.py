@@ -568,6 +568,7 @@ class MCTransportSolverHIP:
         self._engine = engine          # (default: the process-wide engine of the device)
         self.line_data = None          # static line data of update_opacity() (set_line_data)
         self.plasma_data = None        # static plasma data of update_plasma() (set_plasma_data)
+        self.nlte_data = None          # the NLTE species of update_plasma() (set_nlte_data)
 
     def set_line_data(self, line_data):
         """The atomic data update_opacity() computes the tables from (the fields of ``synthetic.LineData`` /
@@ -615,6 +616,16 @@ class MCTransportSolverHIP:
         or with the next update."""
         self.plasma_data = plasma_data
 
+    def set_nlte_data(self, nlte_data):
+        """The species update_plasma() treats in NLTE (the fields of ``synthetic.NlteData`` / ``Engine.set_nlte_data``; what
+        ``plasma.nlte.species`` is to a configuration), on the ions of set_plasma_data(); None for none.  They reach the engine as the
+        plasma data do.  update_plasma() takes no argument for it: NLTE is a property of the installed data."""
+        self.nlte_data = nlte_data
+
+    def _install_nlte(self, eng):
+        if eng.nlte_data is not self.nlte_data:
+            eng.set_nlte_data(self.nlte_data)
+
     def update_plasma(self, t_radiative, dilution_factor, ionization="nebular", excitation="dilute-lte",
                       radiative_rates_type="dilute-blackbody", *, volume=None, w_epsilon=1e-10, time_of_simulation=None):
         """The whole plasma step of an outer iteration on the device (``resident=True``): from ``t_radiative`` and ``dilution_factor``
@@ -636,6 +647,7 @@ class MCTransportSolverHIP:
             eng.set_line_data(self.line_data)
         if eng.plasma_data is not self.plasma_data:
             eng.set_plasma_data(self.plasma_data)
+        self._install_nlte(eng)
         if radiative_rates_type == "detailed":
             if time_of_simulation is None:
                 if self.transport_state is None:
@@ -717,6 +729,8 @@ class MCTransportSolverHIP:
             eng.set_line_data(self.line_data)
         if self.line_data is not None and self.plasma_data is not None and eng.plasma_data is not self.plasma_data:
             eng.set_plasma_data(self.plasma_data)
+        if self.line_data is not None and self.plasma_data is not None:
+            self._install_nlte(eng)
         eng.set_config(cfg, self.spectrum_frequency_grid, cfg.NUMBER_OF_VPACKETS)
         eng.set_option("track_last_interaction", int(self.enable_last_interaction_tracking))
         pc = ts.packet_collection
