@@ -675,7 +675,8 @@ int tardis_mc_plasma_update_path(int64_t levels);
  * The solve fails (the reference's LinAlgError) when a pivot is 0.0 or not finite, when x[0] is 0.0 or when any x is not finite.
  *   lbf[k] = (x[k] g_0) / x[0], g_0 the level_g of the species' first level
  * The stimulated-emission factor needs no change: the existing clamp of negative values is what the reference does for the lines of
- * NLTE species.  NOT covered: the collision matrix (atomic data with collision_data), NLTE ionization, the helium treatments, continuum.
+ * NLTE species.  NOT covered here: the collision matrix of atomic data with collision_data (the next section
+ * adds it); not covered at all: NLTE ionization, the helium treatments, continuum.
  * Kernels (csrc/nlte_excitation.hpp): a streaming kernel writes r_ul / r_lu of the NLTE lines; then one workgroup per (species, shell)
  * builds and solves the system on a column-major matrix of odd leading dimension, either in its LDS (species of up to 141 levels) or in
  * a slab of HBM per (species, shell) -- same operations, same order, same bits (csrc/nlte_plan.hpp chooses per species).  No workgroup
@@ -724,6 +725,71 @@ int tardis_mc_last_nlte_ms(TardisMcContext *ctx, double *out_assemble_ms, double
  * Host only; both forms run the same operations in the same order.  Option "nlte_lds_levels" (-1, the default: this rule; n >= 0:
  * species of n levels or more take the global form -- measurements and tests only). */
 int tardis_mc_nlte_solve_path(int64_t levels);
+
+/* ---- collisional rates in the NLTE excitation stage (atomic data with collision_data) -------------------------------------------
+ * What LevelBoltzmannFactorNLTE._calculate_general adds to every species' rate matrix when the atomic data carry collision_data:
+ * get_collision_matrix(species, t_electrons) * previous_electron_densities.  With collision data installed beside the NLTE data, the
+ * NLTE stage of tardis_mc_update_plasma forms, for an NLTE species with pairs, a shell s and a pair (l, u) of local level numbers of
+ * the species' ion with l < u -- all arithmetic fp64 with no contraction, exp the transport's own (mcm::exp), every product, quotient
+ * and sum a rounding of its own:
+ *   t_e   = link_t_rad_t_electron t_rad[s]   (the product the plasma stage forms; t_rad the call's t_radiative)
+ *   c_ul  = the pair's C_ul[.] interpolated linearly in t_e over collision_temperatures, by the rule stated for zeta above:
+ *           hi = clip(searchsorted(collision_temperatures, t_e, side="left"), 1, NT-1), lo = hi - 1,
+ *           slope = (y[hi] - y[lo]) / (x[hi] - x[lo]);  c_ul = slope (t_e - x[lo]) + y[lo]   (one division, one product, one sum);
+ *           a NaN result becomes 0.0 (the reference zeroes NaN after interpolating: Chianti has none at the cool end of some pairs)
+ *   c_lu  = (c_ul exp(-delta_e / t_e)) inv_g_ratio
+ *           delta_e in kelvin, as collision_data.delta_e is; inv_g_ratio = 1 / g_ratio, formed once on the host when the data are set
+ *           (the reference flips g_ratio when it builds its matrices)
+ *   n_e   = the resident electron density of shell s AT ENTRY to the call: what tardis_mc_set_opacity, tardis_mc_update_opacity or
+ *           the previous tardis_mc_update_plasma installed (the reference's previous_electron_densities)
+ *   M[l][u] = r_ul + c_ul n_e;   M[u][l] = r_lu + c_lu n_e
+ *           r as in the section above, 0.0 where the pair has no line; where a line has no collision pair the entry is r itself,
+ *           bit for bit (nothing is added to it)
+ * The diagonal (minus the serial sum of the column's off-diagonal entries), the row of ones, b, the LU factorisation, the failure
+ * rules and lbf are those of the section above, unchanged.  coronal_approximation and classical_nebular act on j and beta only, as in
+ * the reference.  A level no line reaches but a pair does no longer makes the matrix singular.
+ * Against numpy.linalg.solve the restatement (tests/nlte_collision_ref.py) differs by at most 1.7e-14 relative in a population on the
+ * test models' systems (8.6e-13 without collision data, above; bound 1e-11): to rounding, not bitwise, for the reason given there.
+ * Kernels (csrc/nlte_excitation.hpp): nlte_collision_kernel streams the pairs of a shell, finds the bracket once per workgroup, reads
+ * C_ul stored as [NT][NP] and writes c_ul / c_lu [S][NP]; nlte_solve_kernel adds c n_e of its species' pairs between the scatter of the
+ * line rates and the column sums (one writer per entry: a repeated pair is refused), in its LDS form and in its global form alike:
+ * same operations, same order, same bits.  The working set does not grow; the 141-level boundary stays.  No atomics.
+ * Without collision data installed every path produces the bits it produced before. */
+typedef struct TardisMcNlteCollisionData {
+    int64_t n_species;                   /* NS, the installed NLTE data's */
+    int64_t n_temperatures;              /* NT >= 2 */
+    const double *collision_temperatures;/* [NT] kelvin, ascending */
+    int64_t n_pairs;                     /* NP */
+    const int64_t *species_pair_edge;    /* [NS+1]: a species' pairs are contiguous in the next five arrays (an empty range: no data) */
+    const int64_t *level_lower;          /* [NP] local to the species' ion, 0 .. n-1 */
+    const int64_t *level_upper;          /* [NP] local, > level_lower */
+    const double *delta_e;               /* [NP] kelvin, finite */
+    const double *g_ratio;               /* [NP] g_lower / g_upper as collision_data has it, finite and positive */
+    const double *C_ul;                  /* [NP][NT]; NaN allowed */
+} TardisMcNlteCollisionData;
+
+/* The collision data of the installed NLTE species; after tardis_mc_set_nlte_data, dropped by whatever drops the NLTE data (a later
+ * tardis_mc_set_nlte_data, NULL included, and tardis_mc_set_opacity, set_line_data, set_plasma_data); collision_data == NULL removes
+ * it.  Everything is checked on the host before anything is indexed or uploaded: TARDIS_MC_ERR_INVALID_ARGUMENT for an n_species that
+ * is not the NLTE data's, NT < 2 or temperatures that do not ascend, an edge table that does not run from 0 to NP, a level outside the
+ * species' ion, lower >= upper, a pair repeated within a species, a g_ratio that is not finite and positive, a delta_e that is not
+ * finite, a missing pointer; TARDIS_MC_ERR_STATE without NLTE data.  Pairs sorted by (lower, upper) within a species give the solve
+ * kernel's added phase its best LDS access pattern; any order gives the same bits.
+ * With collision data installed tardis_mc_update_plasma returns TARDIS_MC_ERR_INVALID_ARGUMENT when some t_e lies outside
+ * [collision_temperatures[0], collision_temperatures[NT-1]] (scipy's interp1d bounds error; a t_e exactly on the first or last knot
+ * is inside), checked on the host from the call's t_radiative before a kernel runs: the state stays as it was. */
+int tardis_mc_set_nlte_collision_data(TardisMcContext *ctx, const TardisMcNlteCollisionData *collision_data);
+/* The host-side check of tardis_mc_set_nlte_collision_data on plain arrays, without a context or a device: n_species and
+ * species_levels [n_species] are the NLTE data's species and the level counts of their ions.  With t_radiative != NULL
+ * ([n_shells]) also the bounds rule of tardis_mc_update_plasma for link_t_rad_t_electron.  0 or TARDIS_MC_ERR_INVALID_ARGUMENT (the
+ * message: tardis_mc_last_error(NULL)). */
+int tardis_mc_check_nlte_collision_data(const TardisMcNlteCollisionData *collision_data, int64_t n_species, const int64_t *species_levels,
+                                        double link_t_rad_t_electron, int64_t n_shells, const double *t_radiative);
+/* c_ul and c_lu [NP,S] as the last tardis_mc_update_plasma formed them, before the product with n_e.  Either pointer may be NULL.
+ * TARDIS_MC_ERR_STATE unless the last successful tardis_mc_update_plasma ran the NLTE stage with collision data and its populations
+ * are still resident.  tardis_mc_last_nlte_ms keeps its two outputs: the collision kernel counts under assemble_ms, the added phase
+ * of the solve kernel under solve_ms. */
+int tardis_mc_get_nlte_collision_rates(TardisMcContext *ctx, double *c_ul, double *c_lu);
 
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the

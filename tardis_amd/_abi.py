@@ -167,6 +167,22 @@ class TardisMcNlteData(C.Structure):
     ]
 
 
+class TardisMcNlteCollisionData(C.Structure):
+    """The collision strengths of the NLTE species' level pairs (tardis_mc_set_nlte_collision_data)."""
+    _fields_ = [
+        ("n_species", C.c_int64),
+        ("n_temperatures", C.c_int64),
+        ("collision_temperatures", _pd),
+        ("n_pairs", C.c_int64),
+        ("species_pair_edge", _pi),
+        ("level_lower", _pi),
+        ("level_upper", _pi),
+        ("delta_e", _pd),
+        ("g_ratio", _pd),
+        ("C_ul", _pd),
+    ]
+
+
 IONIZATION_MODES = {"nebular": 0, "lte": 1}
 EXCITATION_MODES = {"dilute-lte": 0, "lte": 1}
 
@@ -377,6 +393,25 @@ def marshal_nlte_data(nd) -> Marshalled:
     s = TardisMcNlteData(NS, _ip(ion), NL, _ip(edge), _ip(line_id), _dp(coef[0]), _dp(coef[1]), _dp(coef[2]),
                          int(bool(nd.coronal_approximation)), int(bool(nd.classical_nebular)))
     return Marshalled(s, [ion, edge, line_id] + coef)
+
+
+def marshal_nlte_collision_data(cd) -> Marshalled:
+    """cd: an object with collision_temperatures [NT], species_pair_edge [NS+1], level_lower, level_upper, delta_e, g_ratio [NP] and
+    C_ul [NP, NT], e.g. synthetic.NlteCollisionData.  The counts are taken from the array shapes."""
+    temps = np.ascontiguousarray(cd.collision_temperatures, dtype=np.float64)
+    edge = np.ascontiguousarray(cd.species_pair_edge, dtype=np.int64)
+    lv = [np.ascontiguousarray(getattr(cd, n), dtype=np.int64) for n in ("level_lower", "level_upper")]
+    f = [np.ascontiguousarray(getattr(cd, n), dtype=np.float64) for n in ("delta_e", "g_ratio")]
+    c = np.ascontiguousarray(cd.C_ul, dtype=np.float64)
+    NS, NT, NP = len(edge) - 1, len(temps), len(lv[0])
+    if temps.ndim != 1 or edge.ndim != 1 or NS < 0:
+        raise ValueError("collision_temperatures and species_pair_edge must be vectors")
+    if not all(a.shape == (NP,) for a in lv + f):
+        raise ValueError("level_lower, level_upper, delta_e and g_ratio must have one entry per pair")
+    if c.shape != (NP, NT):
+        raise ValueError("C_ul must be [n_pairs, n_temperatures]")
+    s = TardisMcNlteCollisionData(NS, NT, _dp(temps), NP, _ip(edge), _ip(lv[0]), _ip(lv[1]), _dp(f[0]), _dp(f[1]), _dp(c))
+    return Marshalled(s, [temps, edge, c] + lv + f)
 
 
 def marshal_plasma_update(t_radiative, dilution_factor, n_shells, ionization_mode=0, excitation_mode=0,

@@ -71,6 +71,9 @@ SYMBOLS = {
     "tardis_mc_get_nlte": (_i, [_vp, _vp, _vp]),
     "tardis_mc_last_nlte_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 2),
     "tardis_mc_nlte_solve_path": (_i, [C.c_int64]),
+    "tardis_mc_set_nlte_collision_data": (_i, [_vp, _vp]),
+    "tardis_mc_check_nlte_collision_data": (_i, [_vp, C.c_int64, _vp, C.c_double, C.c_int64, _vp]),
+    "tardis_mc_get_nlte_collision_rates": (_i, [_vp, _vp, _vp]),
     "tardis_mc_get_event_log": (_i, [_vp, _vp]),
     "tardis_mc_get_vpacket_log": (_i, [_vp, _vp]),
     "tardis_mc_stream_results": (_i, [_vp, _vp]),

@@ -1,7 +1,7 @@
 // nlte_excitation.hpp -- NLTE excitation of selected species inside tardis_mc_update_plasma: the level Boltzmann factors of an NLTE species
-// from the statistical equilibrium of its radiative bound-bound rates, solved per (species, shell) on the device.
+// from the statistical equilibrium of its radiative and collisional bound-bound rates, solved per (species, shell) on the device.
 //
-// Restates LevelBoltzmannFactorNLTE._calculate_general / _main_nlte_calculation of the legacy plasma for collision_data None (fp64,
+// Restates LevelBoltzmannFactorNLTE._calculate_general / _main_nlte_calculation of the legacy plasma, collision matrix included (fp64,
 // -ffp-contract=off keeps every product, quotient and difference a rounding of its own; the contract is spelled out in include/tardis_mc.h):
 // per line of the species r_ul = (A_ul + B_ul j) beta and r_lu = (B_lu j) beta, a rate matrix with the destination as the row, the
 // diagonal minus the serial column sum, the first row replaced by ones, b = e_0; M x = b by unblocked LU with partial pivoting and a
@@ -22,6 +22,16 @@
 // taken from the unswapped column with the swap applied on the fly; the pivot itself goes into a vector of its own); barrier; the
 // rank-1 update (a wave per column, a lane per row) and b; barrier.  Two barriers per step, one per back-substitution step.  Every entry
 // sees its updates in the order of k whatever the decomposition.  No workgroup waits on another, no atomics: two calls give identical bits.
+//
+// Collisional rates (atomic data with collision_data; tardis_mc_set_nlte_collision_data).  nlte_collision_kernel streams the pairs of a
+// shell (grid.y = shell): t_e = link t_rad[s] and its bracket in the temperature grid are properties of the shell, so the first wave
+// counts the knots below t_e with one ballot per 64 knots and hands hi to the workgroup through four bytes of LDS; C_ul is stored
+// [NT][NP], so the two rows a shell reads are consecutive across lanes.  It writes c_ul / c_lu [S][NP], before the product with n_e.
+// The solve kernel then has one more phase between the scatter of the line rates and the column sums: the species' pairs add
+// c n_e[s] into M[l][u] and M[u][l] (one writer per entry: the set call refuses a repeated pair), behind a barrier of its own.  A
+// species without pairs, and every species when no collision data are installed, skips the phase and its barrier on one
+// workgroup-uniform branch.  Pairs sorted by (lower, upper) walk a row of M with consecutive upper levels: the odd leading dimension
+// spreads them over 32 bank pairs, and the transposed entry is a walk down a column.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -68,6 +78,44 @@ __global__ void __launch_bounds__(256) nlte_rates_kernel(NlteRateArgs a)
     }
 }
 
+struct NlteCollisionArgs {
+    int S, NT;
+    long long NP;
+    const double *temperatures;              // [NT] ascending
+    const double *c_t;                       // [NT][NP] C_ul
+    const double *delta_e, *inv_g_ratio;     // [NP]
+    const double *t_rad;                     // [S] the call's
+    double link;                             // link_t_rad_t_electron
+    double *c_ul_t, *c_lu_t;                 // [S][NP] out
+};
+
+__global__ void __launch_bounds__(256) nlte_collision_kernel(NlteCollisionArgs a)
+{
+    __shared__ int hi_shared;
+    const long long s = blockIdx.y;
+    const double t_e = a.link * a.t_rad[s];
+    // hi = clip(searchsorted(temperatures, t_e, side="left"), 1, NT - 1): the knots below t_e, counted by the first wave
+    if (threadIdx.x < 64) {
+        int below = 0;
+        for (int base = 0; base < a.NT; base += 64) {
+            const int i = base + (int)threadIdx.x;
+            below += __popcll(__ballot(i < a.NT && a.temperatures[i] < t_e));
+        }
+        if (threadIdx.x == 0) hi_shared = below < 1 ? 1 : (below > a.NT - 1 ? a.NT - 1 : below);
+    }
+    __syncthreads();
+    const int hi = hi_shared, lo = hi - 1;
+    const double x_lo = a.temperatures[lo], dx = a.temperatures[hi] - x_lo, dt = t_e - x_lo;
+    const double *y_lo = a.c_t + (long long)lo * a.NP, *y_hi = a.c_t + (long long)hi * a.NP;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < a.NP; q += (long long)gridDim.x * blockDim.x) {
+        const double slope = (y_hi[q] - y_lo[q]) / dx;
+        double c_ul = slope * dt + y_lo[q];
+        if (c_ul != c_ul) c_ul = 0.0;  // (the reference zeroes NaN after interpolating)
+        a.c_ul_t[s * a.NP + q] = c_ul;
+        a.c_lu_t[s * a.NP + q] = (c_ul * mcm::exp(-a.delta_e[q] / t_e)) * a.inv_g_ratio[q];
+    }
+}
+
 struct NlteSolveArgs {
     int S;
     long long K, NL, NX;
@@ -81,6 +129,12 @@ struct NlteSolveArgs {
     int *status;                             // [NS][S] out: 0, or 1 + the step of a bad pivot, n + 1 (x[0] == 0), n + 2 (x not finite)
     double *scratch;                         // global form: the slabs
     const long long *slab;                   // global form, per list entry: the offset (doubles) of shell 0's slab; shells follow each other
+    // collisional rates; sp_pair_edge == nullptr: none installed
+    long long NP;
+    const int *sp_pair_edge;                 // [NS+1] pairs per species
+    const int *pair_lower, *pair_upper;      // [NP] local levels, lower < upper
+    const double *c_ul_t, *c_lu_t;           // [S][NP]
+    const double *n_e;                       // [S] the resident electron density at entry to the call
 };
 
 __device__ __forceinline__ bool nlte_finite(double v) { return fabs(v) <= DBL_MAX; }
@@ -117,6 +171,20 @@ __global__ void __launch_bounds__(256) nlte_solve_kernel(NlteSolveArgs a)
         }
     }
     __syncthreads();
+    {   // the collisional rates of the species' pairs on top: workgroup-uniform, so the barrier is met by all threads or by none
+        const int p0 = a.sp_pair_edge ? a.sp_pair_edge[sp] : 0, p1 = a.sp_pair_edge ? a.sp_pair_edge[sp + 1] : 0;
+        if (p0 < p1) {
+            const double *c_ul = a.c_ul_t + s * a.NP, *c_lu = a.c_lu_t + s * a.NP;
+            const double ne = a.n_e[s];
+            for (int q = p0 + tid; q < p1; q += 256) {
+                const int l = a.pair_lower[q], u = a.pair_upper[q];
+                double *ul = M + l + (long long)u * ld, *lu = M + u + (long long)l * ld;
+                *ul = *ul + c_ul[q] * ne;
+                *lu = *lu + c_lu[q] * ne;
+            }
+            __syncthreads();
+        }
+    }
     for (int c = tid; c < n; c += 256) {
         double *col = M + (long long)c * ld;
         double sum = 0.0;

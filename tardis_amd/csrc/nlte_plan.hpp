@@ -3,6 +3,9 @@
 //
 // Standard C++ only (no HIP header, no context, no device call): tests/test_nlte_excitation_host.py pins the rule through
 // tardis_mc_nlte_solve_path and the check through tardis_mc_check_nlte_data.  The kernels are in nlte_excitation.hpp.
+// Likewise the check of a TardisMcNlteCollisionData and the bounds rule of its temperature grid (tests/test_nlte_collision_host.py
+// through tardis_mc_check_nlte_collision_data); the collisional rates add to entries the matrix already has, so the working set, the
+// LDS limit, the size classes and the 141-level boundary are what they were.
 //
 // A species of n levels is solved per shell by one workgroup on a column-major n x n fp64 matrix of leading dimension ld = n | 1 (odd:
 // a walk along a row then visits 32 different bank pairs) and four vectors of n (b, the multipliers of a step, the pivots, x).  The
@@ -13,6 +16,7 @@
 // at 61, 0.509 / 0.951 at 125 -- so the rule is "LDS whenever it fits".
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -98,6 +102,58 @@ inline std::string check_data(long long n_species, const int64_t *species_ion, l
             if (pairs[q] == pairs[q - 1]) return msg("species %lld: the pair of levels (%lld, %lld) is repeated", sp, pairs[q].first, pairs[q].second);
     }
     return std::string();
+}
+
+// What tardis_mc_set_nlte_collision_data checks before it indexes anything, on plain arrays: the species count against the installed
+// NLTE data's, the temperature grid, the edge table, every pair's two levels against its species' ion (species_levels[sp] levels,
+// local indices), lower < upper, the pairs of a species against each other, and delta_e / g_ratio.  C_ul is not inspected: NaN entries
+// are data (the interpolation zeroes them).  Returns "" when the data are good, else the message.
+inline std::string check_collision_data(long long n_species, long long n_nlte_species, const int64_t *species_levels, long long n_temperatures,
+                                        const double *temperatures, long long n_pairs, const int64_t *species_pair_edge, const int64_t *level_lower,
+                                        const int64_t *level_upper, const double *delta_e, const double *g_ratio, const double *c_ul)
+{
+    char buf[256];
+    auto msg = [&](const char *fmt, long long a = 0, long long b = 0, long long c = 0) { snprintf(buf, sizeof buf, fmt, a, b, c); return std::string(buf); };
+    if (n_species != n_nlte_species) return msg("collision data of %lld species, the NLTE data have %lld", n_species, n_nlte_species);
+    if (n_species <= 0 || !species_levels) return msg("invalid collision data: %lld species", n_species);
+    if (n_temperatures < 2 || n_temperatures > 0x7ffffff0LL) return msg("collision data need n_temperatures >= 2, not %lld", n_temperatures);
+    if (n_pairs < 0 || n_pairs > 0x7ffffff0LL) return msg("invalid collision data: %lld pairs", n_pairs);
+    if (!temperatures || !species_pair_edge || (n_pairs > 0 && (!level_lower || !level_upper || !delta_e || !g_ratio || !c_ul)))
+        return msg("invalid collision data: a pointer is missing");
+    for (long long t = 0; t + 1 < n_temperatures; ++t)
+        if (!(temperatures[t] < temperatures[t + 1])) return msg("collision_temperatures must ascend (entry %lld)", t + 1);
+    if (!std::isfinite(temperatures[0]) || !std::isfinite(temperatures[n_temperatures - 1])) return msg("collision_temperatures must be finite");
+    if (species_pair_edge[0] != 0 || species_pair_edge[n_species] != n_pairs) return msg("species_pair_edge must run from 0 to n_pairs");
+    for (long long sp = 0; sp < n_species; ++sp)
+        if (species_pair_edge[sp + 1] < species_pair_edge[sp]) return msg("species_pair_edge decreases at species %lld", sp);
+    for (long long sp = 0; sp < n_species; ++sp) {
+        const long long n = species_levels[sp], a = species_pair_edge[sp], b = species_pair_edge[sp + 1];
+        std::vector<std::pair<long long, long long>> pairs;
+        pairs.reserve((size_t)(b - a));
+        for (long long q = a; q < b; ++q) {
+            const long long lo = level_lower[q], up = level_upper[q];
+            if (lo < 0 || lo >= n || up < 0 || up >= n) return msg("collision pair %lld: its levels are not both inside the ion of species %lld (%lld levels)", q, sp, n);
+            if (lo >= up) return msg("collision pair %lld: lower >= upper (%lld, %lld)", q, lo, up);
+            if (!std::isfinite(delta_e[q])) return msg("collision pair %lld: delta_e is not finite", q);
+            if (!(g_ratio[q] > 0) || !std::isfinite(g_ratio[q])) return msg("collision pair %lld: g_ratio is not finite and positive", q);
+            pairs.emplace_back(lo, up);
+        }
+        std::sort(pairs.begin(), pairs.end());
+        for (size_t q = 1; q < pairs.size(); ++q)
+            if (pairs[q] == pairs[q - 1]) return msg("species %lld: the collision pair (%lld, %lld) is repeated", sp, pairs[q].first, pairs[q].second);
+    }
+    return std::string();
+}
+
+// scipy's interp1d bounds error, from the call's t_rad: the first shell whose t_e = link * t_rad[s] lies outside [t_first, t_last]
+// (a NaN lies outside), or -1.  A t_e exactly on the first or the last knot is inside.
+inline long long first_t_e_outside(double link, long long n_shells, const double *t_rad, double t_first, double t_last)
+{
+    for (long long s = 0; s < n_shells; ++s) {
+        const double t_e = link * t_rad[s];
+        if (!(t_e >= t_first && t_e <= t_last)) return s;
+    }
+    return -1;
 }
 
 }  // namespace nlte

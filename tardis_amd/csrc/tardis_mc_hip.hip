@@ -360,6 +360,12 @@ struct TardisMcContext {
     long long nl_species = 0, nl_lines = 0, nl_nx = 0, nl_scratch_doubles = 0;
     long long nl_lds_levels = -1, nl_lists_built = -2;  // option nlte_lds_levels: -1 the rule of nlte_plan.hpp, else the threshold itself
     hipEvent_t ev_nl[3] = {nullptr, nullptr, nullptr};  // start | rates | solve (tardis_mc_last_nlte_ms)
+    // Collisional rates of the NLTE species (nlte_excitation.hpp).  Per set_nlte_collision_data: the temperature grid, C_ul as [NT][NP], delta_e,
+    // 1 / g_ratio, the pairs' local levels and the species' pair edges.  Per update_plasma: c_ul / c_lu [S][NP] (tardis_mc_get_nlte_collision_rates).
+    DevBuf nc_temperatures, nc_c_t, nc_delta_e, nc_inv_g, nc_lower, nc_upper, nc_sp_pair_edge, nc_c_ul, nc_c_lu;
+    bool have_nc = false, nc_valid = false;  // (nc_valid: c_ul / c_lu are those of the last successful update)
+    long long nc_pairs = 0, nc_nt = 0;
+    double nc_t_first = 0.0, nc_t_last = 0.0;
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -2064,7 +2070,8 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     for (hipEvent_t e : ctx->ev_pl) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_nl) if (e) (void)hipEventDestroy(e);
     for (DevBuf *b : {&ctx->nl_line_id, &ctx->nl_a_ul, &ctx->nl_b_ul, &ctx->nl_b_lu, &ctx->nl_lower, &ctx->nl_upper, &ctx->nl_sp_k0, &ctx->nl_sp_n, &ctx->nl_sp_x0,
-                      &ctx->nl_sp_line_edge, &ctx->nl_list, &ctx->nl_slab, &ctx->nl_r_ul, &ctx->nl_r_lu, &ctx->nl_x_t, &ctx->nl_status, &ctx->nl_scratch, &ctx->nl_work})
+                      &ctx->nl_sp_line_edge, &ctx->nl_list, &ctx->nl_slab, &ctx->nl_r_ul, &ctx->nl_r_lu, &ctx->nl_x_t, &ctx->nl_status, &ctx->nl_scratch, &ctx->nl_work,
+                      &ctx->nc_temperatures, &ctx->nc_c_t, &ctx->nc_delta_e, &ctx->nc_inv_g, &ctx->nc_lower, &ctx->nc_upper, &ctx->nc_sp_pair_edge, &ctx->nc_c_ul, &ctx->nc_c_lu})
         b->release();
     for (DevBuf *b : {&ctx->pl_energy, &ctx->pl_g, &ctx->pl_meta, &ctx->pl_level_ion, &ctx->pl_ion_edge, &ctx->pl_elem_edge, &ctx->pl_charge, &ctx->pl_chi,
                       &ctx->pl_zeta_t, &ctx->pl_zeta, &ctx->pl_density, &ctx->pl_long_ions, &ctx->pl_lbf_t, &ctx->pl_z, &ctx->pl_phi, &ctx->pl_n_ion,
@@ -2420,7 +2427,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     ctx->h_macro = macro;
     ctx->have_line_data = ctx->ou_valid = false;  // (the line data belong to one topology: tardis_mc_set_line_data again)
     ctx->have_plasma_data = ctx->pl_valid = false;  // (... and the plasma data to one set of line data)
-    ctx->have_nlte = ctx->nl_valid = false;
+    ctx->have_nlte = ctx->nl_valid = ctx->have_nc = ctx->nc_valid = false;
     tmark("index tables int32 up");
     {   // packed macro-atom tables of the cooperative kernel
         std::vector<int> lb(2 * (macro ? L : 1), 0), rec(4 * (macro ? T : 1), 0);
@@ -3968,7 +3975,7 @@ int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
     if (!ctx->have_opacity) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity must precede set_line_data");
     ctx->have_line_data = ctx->ou_valid = false;
     ctx->have_plasma_data = ctx->pl_valid = false;  // (the plasma data sit on the levels of one set of line data)
-    ctx->have_nlte = ctx->nl_valid = false;
+    ctx->have_nlte = ctx->nl_valid = ctx->have_nc = ctx->nc_valid = false;
     const size_t L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans;
     if (d->n_lines != (int64_t)L || d->n_transitions != (int64_t)T)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "line data of %lld lines / %lld transitions, the resident opacity state has %zu / %zu",
@@ -4200,7 +4207,7 @@ int tardis_mc_set_plasma_data(TardisMcContext *ctx, const TardisMcPlasmaData *d)
     if (!ctx || !d) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_opacity || !ctx->have_line_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_line_data must precede set_plasma_data");
     ctx->have_plasma_data = ctx->pl_valid = false;
-    ctx->have_nlte = ctx->nl_valid = false;  // (the NLTE species are ions of one set of plasma data)
+    ctx->have_nlte = ctx->nl_valid = ctx->have_nc = ctx->nc_valid = false;  // (the NLTE species are ions of one set of plasma data)
     if (d->n_levels != ctx->ou_levels)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "plasma data of %lld levels, the line data have %lld", (long long)d->n_levels, ctx->ou_levels);
     if (d->n_shells != ctx->n_shells)
@@ -4319,7 +4326,7 @@ int tardis_mc_set_nlte_data(TardisMcContext *ctx, const TardisMcNlteData *d)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_plasma_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_plasma_data must precede set_nlte_data");
-    ctx->have_nlte = ctx->nl_valid = false;
+    ctx->have_nlte = ctx->nl_valid = ctx->have_nc = ctx->nc_valid = false;
     if (!d) return TARDIS_MC_OK;
     if (d->n_nlte_lines > 0 && (!d->A_ul || !d->B_ul || !d->B_lu)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid NLTE data: a pointer is missing");
     // everything the kernels index with is checked here, on the host
@@ -4361,6 +4368,84 @@ int tardis_mc_set_nlte_data(TardisMcContext *ctx, const TardisMcNlteData *d)
     return TARDIS_MC_OK;
 }
 
+/* ---- collisional rates of the NLTE species (atomic data with collision_data) ------------------------------ */
+static std::string nlte_collision_check(const TardisMcNlteCollisionData *d, long long n_nlte_species, const int64_t *species_levels)
+{
+    return nlte::check_collision_data((long long)d->n_species, n_nlte_species, species_levels, (long long)d->n_temperatures, d->collision_temperatures,
+                                      (long long)d->n_pairs, d->species_pair_edge, d->level_lower, d->level_upper, d->delta_e, d->g_ratio, d->C_ul);
+}
+
+int tardis_mc_check_nlte_collision_data(const TardisMcNlteCollisionData *d, int64_t n_species, const int64_t *species_levels, double link_t_rad_t_electron,
+                                        int64_t n_shells, const double *t_radiative)
+{
+    if (!d || !species_levels) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid collision data: a pointer is missing");
+    const std::string err = nlte_collision_check(d, (long long)n_species, species_levels);
+    if (!err.empty()) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+    if (t_radiative) {
+        const double t0 = d->collision_temperatures[0], t1 = d->collision_temperatures[d->n_temperatures - 1];
+        const long long s = nlte::first_t_e_outside(link_t_rad_t_electron, (long long)n_shells, t_radiative, t0, t1);
+        if (s >= 0)
+            return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "t_electron of shell %lld = %g lies outside the collision temperatures [%g, %g]", s,
+                        link_t_rad_t_electron * t_radiative[s], t0, t1);
+    }
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_set_nlte_collision_data(TardisMcContext *ctx, const TardisMcNlteCollisionData *d)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_nlte) return fail(ctx, TARDIS_MC_ERR_STATE, "set_nlte_data must precede set_nlte_collision_data");
+    ctx->have_nc = ctx->nc_valid = false;
+    if (!d) return TARDIS_MC_OK;
+    // everything the kernels index with is checked here, on the host
+    std::vector<int64_t> levels(ctx->nl_h_n.begin(), ctx->nl_h_n.end());
+    const std::string err = nlte_collision_check(d, ctx->nl_species, levels.data());
+    if (!err.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+    const size_t NS = (size_t)d->n_species, NP = (size_t)d->n_pairs, NT = (size_t)d->n_temperatures;
+    std::vector<int> edge(NS + 1), lower(NP), upper(NP);
+    std::vector<double> inv_g(NP), c_t(NT * NP);
+    for (size_t sp = 0; sp <= NS; ++sp) edge[sp] = (int)d->species_pair_edge[sp];
+    for (size_t q = 0; q < NP; ++q) {
+        lower[q] = (int)d->level_lower[q];
+        upper[q] = (int)d->level_upper[q];
+        inv_g[q] = 1 / d->g_ratio[q];  // (the reference flips g_ratio when it builds its matrices)
+        for (size_t t = 0; t < NT; ++t) c_t[t * NP + q] = d->C_ul[q * NT + t];  // [NP][NT] -> [NT][NP]: a shell reads two rows
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->nc_temperatures, d->collision_temperatures, NT))) return rc;
+    if ((rc = upload(ctx, ctx->nc_c_t, c_t.data(), NT * NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc_delta_e, d->delta_e, NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc_inv_g, inv_g.data(), NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc_lower, lower.data(), NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc_upper, upper.data(), NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc_sp_pair_edge, edge.data(), NS + 1))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors are the sources of asynchronous copies)
+    ctx->nc_pairs = (long long)NP; ctx->nc_nt = (long long)NT;
+    ctx->nc_t_first = d->collision_temperatures[0]; ctx->nc_t_last = d->collision_temperatures[NT - 1];
+    ctx->have_nc = true;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_nlte_collision_rates(TardisMcContext *ctx, double *c_ul, double *c_lu)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->nc_valid || !ctx->nl_valid || !ctx->pl_valid)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "get_nlte_collision_rates needs a successful update_plasma that ran the NLTE stage with collision data");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t S = (size_t)ctx->n_shells, NP = (size_t)ctx->nc_pairs;
+    if (NP == 0) return TARDIS_MC_OK;
+    for (int k = 0; k < 2; ++k) {  // [S][NP] -> [NP,S]
+        double *host = k == 0 ? c_ul : c_lu;
+        if (!host) continue;
+        HIP_TRY(ctx, ctx->staging.ensure(NP * S * sizeof(double)));
+        HIP_TRY(ctx, launch_transpose(ctx->stream, (k == 0 ? ctx->nc_c_ul : ctx->nc_c_lu).as<double>(), ctx->staging.as<double>(), (long long)S, (long long)NP));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, host_copy(ctx, {{(void *)host, ctx->staging.p, NP * S * sizeof(double)}}, false));
+    }
+    return TARDIS_MC_OK;
+}
+
 // What the NLTE stage needs before the update's first kernel: the launches for the current option, the buffers of a call.
 static int nlte_prepare(TardisMcContext *ctx)
 {
@@ -4372,6 +4457,10 @@ static int nlte_prepare(TardisMcContext *ctx)
     HIP_TRY(ctx, ctx->nl_x_t.ensure((size_t)ctx->nl_nx * S * sizeof(double)));
     HIP_TRY(ctx, ctx->nl_status.ensure((size_t)ctx->nl_species * S * sizeof(int)));
     HIP_TRY(ctx, ctx->nl_scratch.ensure(std::max<size_t>(1, (size_t)ctx->nl_scratch_doubles) * sizeof(double)));
+    if (ctx->have_nc) {
+        HIP_TRY(ctx, ctx->nc_c_ul.ensure(std::max<size_t>(1, (size_t)ctx->nc_pairs * S) * sizeof(double)));
+        HIP_TRY(ctx, ctx->nc_c_lu.ensure(std::max<size_t>(1, (size_t)ctx->nc_pairs * S) * sizeof(double)));
+    }
     return TARDIS_MC_OK;
 }
 
@@ -4403,12 +4492,26 @@ static int nlte_stage(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p, const
         hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, r);
         HIP_TRY(ctx, hipGetLastError());
     }
+    if (ctx->have_nc && ctx->nc_pairs > 0) {  // c_ul / c_lu of every pair from the call's t_rad (counted with the rates kernel: assemble_ms)
+        mc::NlteCollisionArgs c{};
+        c.S = (int)S; c.NT = (int)ctx->nc_nt; c.NP = ctx->nc_pairs;
+        c.temperatures = ctx->nc_temperatures.as<double>(); c.c_t = ctx->nc_c_t.as<double>(); c.delta_e = ctx->nc_delta_e.as<double>();
+        c.inv_g_ratio = ctx->nc_inv_g.as<double>(); c.t_rad = d_t; c.link = ctx->pl_link;
+        c.c_ul_t = ctx->nc_c_ul.as<double>(); c.c_lu_t = ctx->nc_c_lu.as<double>();
+        const unsigned bx = (unsigned)std::min<size_t>(((size_t)ctx->nc_pairs + 255) / 256, 1024);
+        hipLaunchKernelGGL(mc::nlte_collision_kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, c);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_nl[1], ctx->stream));
     mc::NlteSolveArgs a{};
     a.S = (int)S; a.K = ctx->ou_levels; a.NL = (long long)NL; a.NX = ctx->nl_nx;
     a.sp_k0 = ctx->nl_sp_k0.as<int>(); a.sp_n = ctx->nl_sp_n.as<int>(); a.sp_x0 = ctx->nl_sp_x0.as<int>(); a.sp_line_edge = ctx->nl_sp_line_edge.as<int>();
     a.lower = ctx->nl_lower.as<int>(); a.upper = ctx->nl_upper.as<int>(); a.r_ul_t = r.r_ul_t; a.r_lu_t = r.r_lu_t; a.g = ctx->pl_g.as<double>();
     a.lbf_t = ctx->pl_lbf_t.as<double>(); a.x_t = ctx->nl_x_t.as<double>(); a.status = ctx->nl_status.as<int>(); a.scratch = ctx->nl_scratch.as<double>();
+    if (ctx->have_nc && ctx->nc_pairs > 0) {  // (the resident electron density is still the previous update's: this call installs its own behind the solve)
+        a.NP = ctx->nc_pairs; a.sp_pair_edge = ctx->nc_sp_pair_edge.as<int>(); a.pair_lower = ctx->nc_lower.as<int>(); a.pair_upper = ctx->nc_upper.as<int>();
+        a.c_ul_t = ctx->nc_c_ul.as<double>(); a.c_lu_t = ctx->nc_c_lu.as<double>(); a.n_e = ctx->n_e.as<double>();
+    }
     for (const TardisMcContext::NlteLaunch &l : ctx->nl_launches) {
         a.list = ctx->nl_list.as<int>() + l.first;
         a.slab = ctx->nl_slab.as<long long>() + l.first;
@@ -4476,6 +4579,12 @@ int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
             if (!(p->t_radiative[s] >= ctx->pl_t_min && p->t_radiative[s] <= ctx->pl_t_max))
                 return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "t_radiative[%zu] = %g lies outside the zeta table [%g, %g]", s, p->t_radiative[s], ctx->pl_t_min,
                             ctx->pl_t_max);
+    if (ctx->have_nlte && ctx->have_nc) {  // scipy's interp1d bounds error of the reference's get_collision_matrix
+        const long long s = nlte::first_t_e_outside(ctx->pl_link, (long long)S, p->t_radiative, ctx->nc_t_first, ctx->nc_t_last);
+        if (s >= 0)
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "t_electron of shell %lld = %g lies outside the collision temperatures [%g, %g]", s,
+                        ctx->pl_link * p->t_radiative[s], ctx->nc_t_first, ctx->nc_t_last);
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->pl_long_rows_built != ctx->pl_long_rows) {  // which ions take the row form (plasma_update_plan.hpp)
         const std::vector<int> &edge = ctx->pl_h_ion_edge;
@@ -4500,7 +4609,7 @@ int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
     HIP_TRY(ctx, ctx->pl_status.ensure(2 * sizeof(int)));
     // Z, N and n_e are rewritten from here on; the resident n_t, the electron densities and the opacity tables only once the iteration has succeeded
     ctx->pl_valid = false;
-    ctx->nl_valid = false;
+    ctx->nl_valid = ctx->nc_valid = false;
     double *d_t = ctx->ou_shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
     HIP_TRY(ctx, hipMemcpyAsync(d_t, p->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_w, p->dilution_factor, S * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -4604,6 +4713,7 @@ int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
     ctx->pl_timed = true;
     ctx->pl_valid = true;
     ctx->nl_ran = ctx->nl_valid = ctx->nl_timed = nlte;
+    ctx->nc_valid = nlte && ctx->have_nc;
     return TARDIS_MC_OK;
 }
 

@@ -52,6 +52,8 @@ class Engine:
         self.line_data = None        # the object whose data set_line_data() uploaded (None after every set_opacity / run)
         self.plasma_data = None      # ... and set_plasma_data() (None after every set_opacity / set_line_data / run)
         self.nlte_data = None        # ... and set_nlte_data() (None after whatever drops the plasma data)
+        self.nlte_collision_data = None  # ... and set_nlte_collision_data() (None after whatever drops the NLTE data)
+        self.n_nlte_collision_pairs = 0
         self.n_nlte_levels = 0
         self.n_plasma_levels = self.n_ions = 0
         self.opacity_generation = 0  # bumped whenever the resident opacity tables are replaced (lazy DeviceOpacityState views check it)
@@ -121,6 +123,7 @@ class Engine:
         self.line_data = None
         self.plasma_data = None
         self.nlte_data = None
+        self.nlte_collision_data = None
         self.opacity_generation += 1
         self._check(self._L.tardis_mc_set_opacity(self._h, m.ref()), "set_opacity")
         self.n_lines, self.n_shells = int(m.struct.n_lines), int(m.struct.n_shells)
@@ -137,6 +140,7 @@ class Engine:
         self.line_data = None
         self.plasma_data = None
         self.nlte_data = None
+        self.nlte_collision_data = None
         self._check(self._L.tardis_mc_set_line_data(self._h, m.ref()), "set_line_data")
         self.line_data = line_data
 
@@ -190,6 +194,7 @@ class Engine:
         m = _abi.marshal_plasma_data(plasma_data)
         self.plasma_data = None
         self.nlte_data = None
+        self.nlte_collision_data = None
         self._check(self._L.tardis_mc_set_plasma_data(self._h, m.ref()), "set_plasma_data")
         self.n_plasma_levels, self.n_ions = int(m.struct.n_levels), int(m.struct.n_ions)
         self.plasma_data = plasma_data
@@ -248,6 +253,7 @@ class Engine:
         those of the statistical equilibrium of the radiative rates; a failed solve is a RuntimeError with ``code`` ERR_STATE that
         leaves the resident tables as they were.  None removes the data; whatever drops the plasma data drops them too."""
         self.nlte_data = None
+        self.nlte_collision_data = None
         if nlte_data is None:
             self._check(self._L.tardis_mc_set_nlte_data(self._h, None), "set_nlte_data")
             return
@@ -267,9 +273,34 @@ class Engine:
         self._check(self._L.tardis_mc_get_nlte(self._h, *(out[name].ctypes.data if on else None for name, on, _ in want)), "get_nlte")
         return out
 
+    def set_nlte_collision_data(self, collision_data):
+        """The collisional rates of the NLTE species (`tardis_mc_set_nlte_collision_data`), after set_nlte_data(): an object with the
+        fields of ``synthetic.NlteCollisionData`` -- a temperature grid and, per species, pairs of local levels with delta_e (kelvin),
+        g_ratio and C_ul over the grid; what ``collision_data`` is to the atomic data.  From then on update_plasma() adds
+        c_ul n_e / c_lu n_e of every pair to the species' rate matrices, n_e the electron density resident at entry to the call; an
+        electron temperature outside the grid is a RuntimeError with ``code`` ERR_INVALID_ARGUMENT that leaves the state.  None removes
+        the data; whatever drops the NLTE data (a new set_nlte_data() included) drops them too."""
+        self.nlte_collision_data = None
+        if collision_data is None:
+            self._check(self._L.tardis_mc_set_nlte_collision_data(self._h, None), "set_nlte_collision_data")
+            return
+        m = _abi.marshal_nlte_collision_data(collision_data)
+        self._check(self._L.tardis_mc_set_nlte_collision_data(self._h, m.ref()), "set_nlte_collision_data")
+        self.n_nlte_collision_pairs = int(m.struct.n_pairs)
+        self.nlte_collision_data = collision_data
+
+    def get_nlte_collision_rates(self, c_ul=True, c_lu=True) -> dict:
+        """c_ul and c_lu [n_pairs, n_shells] as the last update_plasma() formed them, before the product with the electron density
+        (`tardis_mc_get_nlte_collision_rates`)."""
+        want = (("c_ul", c_ul), ("c_lu", c_lu))
+        out = {name: np.empty((self.n_nlte_collision_pairs, self.n_shells)) for name, on in want if on}
+        self._check(self._L.tardis_mc_get_nlte_collision_rates(self._h, *(out[name].ctypes.data if on else None for name, on in want)),
+                    "get_nlte_collision_rates")
+        return out
+
     def last_nlte_ms(self) -> dict:
-        """Device time (ms) of the NLTE stage of the last update_plasma(): {"assemble_ms" (the rates of the NLTE lines), "solve_ms"
-        (the (species, shell) workgroups: matrix, elimination, substitution)}."""
+        """Device time (ms) of the NLTE stage of the last update_plasma(): {"assemble_ms" (the rates of the NLTE lines and, with
+        collision data, of the pairs), "solve_ms" (the (species, shell) workgroups: matrix, elimination, substitution)}."""
         a, b = C.c_double(), C.c_double()
         self._check(self._L.tardis_mc_last_nlte_ms(self._h, C.byref(a), C.byref(b)), "last_nlte_ms")
         return {"assemble_ms": a.value, "solve_ms": b.value}
@@ -463,6 +494,7 @@ class Engine:
         self.line_data = None
         self.plasma_data = None
         self.nlte_data = None
+        self.nlte_collision_data = None
         self.opacity_generation += 1
         self.results_generation += 1
         self.estimators_generation += 1

@@ -473,3 +473,64 @@ def make_nlte_data(seed: int, line_data: LineData, plasma_data: PlasmaData, spec
     b_ul = b_lu * np.asarray(line_data.g_lower, dtype=np.float64)[line_id] / np.asarray(line_data.g_upper, dtype=np.float64)[line_id]
     a_ul = (2.0 * 6.62606957e-27 * nu**3 / st.C_SPEED_OF_LIGHT**2) * b_ul
     return NlteData(species, np.asarray(line_edge, dtype=np.int64), line_id, a_ul, b_ul, b_lu, bool(coronal_approximation), bool(classical_nebular))
+
+
+K_BOLTZMANN = 1.3806488e-16  # erg / K, tardis/constants.py (CODATA 2010, cgs)
+
+
+@dataclass
+class NlteCollisionData:
+    """The collision strengths of Engine.set_nlte_collision_data: per NLTE species, pairs of local levels with C_ul over a
+    temperature grid (what ``collision_data`` is to the atomic data)."""
+    collision_temperatures: np.ndarray  # [NT] kelvin, ascending
+    species_pair_edge: np.ndarray       # [NS+1]; an empty range: the species has no collision data
+    level_lower: np.ndarray             # [NP] local to the species' ion
+    level_upper: np.ndarray             # [NP]
+    delta_e: np.ndarray                 # [NP] kelvin
+    g_ratio: np.ndarray                 # [NP] g_lower / g_upper
+    C_ul: np.ndarray                    # [NP, NT]; NaN where the source has no value
+
+
+def make_nlte_collision_data(seed: int, plasma_data: PlasmaData, nlte_data: NlteData, pair_fraction=1.0, n_temperatures: int = 12,
+                             nan_fraction: float = 0.1, magnitude: float = 1e-8, reach_levels=(), t_min: float = 2000.0,
+                             t_max: float = 40000.0) -> NlteCollisionData:
+    """Collision data for the species of ``nlte_data``: of a species' n (n - 1) / 2 level pairs the share ``pair_fraction`` (a number
+    for all species, or one per species; 1.0: dense, 0.0: an empty range, the species has no data), drawn with the seed and sorted
+    by (lower, upper).  ``reach_levels`` = [(position in species, local level), ...] adds the pairs of that level with every other
+    level of its ion, whatever the fraction -- the way to give rates to a level no line reaches.  delta_e = (E_upper - E_lower) /
+    k_B and g_ratio = g_lower / g_upper from the plasma data.  C_ul = ``magnitude`` times a log-normal factor of one decade per
+    pair, times (t / 1e4 K)^p with p in [-0.7, 0.3] per pair, on ``n_temperatures`` knots spaced geometrically from ``t_min`` to
+    ``t_max``; a share ``nan_fraction`` of the pairs has NaN at its first one to three knots (the cool end, where Chianti's fits
+    have none)."""
+    rng = np.random.default_rng(seed + 49979687)
+    edge = np.asarray(plasma_data.ion_level_edge, dtype=np.int64)
+    species = np.asarray(nlte_data.species_ion, dtype=np.int64)
+    NT = int(n_temperatures)
+    if NT < 2:
+        raise ValueError("n_temperatures must be at least 2")
+    fraction = np.broadcast_to(np.asarray(pair_fraction, dtype=np.float64), species.shape)
+    if np.any(fraction < 0) or np.any(fraction > 1):
+        raise ValueError("pair_fraction lies in [0, 1]")
+    temps = np.geomspace(float(t_min), float(t_max), NT)
+    energy, g = np.asarray(plasma_data.level_energy, dtype=np.float64), np.asarray(plasma_data.level_g, dtype=np.float64)
+    lower, upper, pair_edge = [], [], [0]
+    for pos, i in enumerate(species):
+        k0, n = int(edge[i]), int(edge[i + 1] - edge[i])
+        lo, up = np.triu_indices(n, 1)
+        keep = rng.random(len(lo)) < fraction[pos] if fraction[pos] < 1.0 else np.ones(len(lo), dtype=bool)
+        for where, level in reach_levels:
+            if where == pos:
+                keep |= (lo == level) | (up == level)
+        lower.append(lo[keep])  # (triu_indices is sorted by (lower, upper))
+        upper.append(up[keep])
+        pair_edge.append(pair_edge[-1] + int(keep.sum()))
+    first = np.repeat(edge[species], np.diff(pair_edge))
+    lower, upper = np.concatenate(lower).astype(np.int64), np.concatenate(upper).astype(np.int64)
+    NP = len(lower)
+    delta_e = (energy[first + upper] - energy[first + lower]) / K_BOLTZMANN
+    g_ratio = g[first + lower] / g[first + upper]
+    c_ul = magnitude * 10.0 ** rng.normal(0.0, 0.5, NP)[:, None] * (temps[None, :] / 1e4) ** rng.uniform(-0.7, 0.3, NP)[:, None]
+    holes = np.flatnonzero(rng.random(NP) < nan_fraction)
+    for q, m in zip(holes, rng.integers(1, min(3, NT - 1) + 1, len(holes))):
+        c_ul[q, :m] = np.nan
+    return NlteCollisionData(temps, np.asarray(pair_edge, dtype=np.int64), lower, upper, delta_e, g_ratio, c_ul)

@@ -569,6 +569,7 @@ class MCTransportSolverHIP:
         self.line_data = None          # static line data of update_opacity() (set_line_data)
         self.plasma_data = None        # static plasma data of update_plasma() (set_plasma_data)
         self.nlte_data = None          # the NLTE species of update_plasma() (set_nlte_data)
+        self.nlte_collision_data = None  # their collisional rates (set_nlte_collision_data)
 
     def set_line_data(self, line_data):
         """The atomic data update_opacity() computes the tables from (the fields of ``synthetic.LineData`` /
@@ -622,9 +623,17 @@ class MCTransportSolverHIP:
         plasma data do.  update_plasma() takes no argument for it: NLTE is a property of the installed data."""
         self.nlte_data = nlte_data
 
+    def set_nlte_collision_data(self, collision_data):
+        """The collisional rates of the NLTE species (the fields of ``synthetic.NlteCollisionData`` /
+        ``Engine.set_nlte_collision_data``; what ``collision_data`` is to the atomic data); None for none.  They reach the engine with
+        the NLTE data, and again on a new engine.  update_plasma() takes no argument for them either."""
+        self.nlte_collision_data = collision_data
+
     def _install_nlte(self, eng):
         if eng.nlte_data is not self.nlte_data:
             eng.set_nlte_data(self.nlte_data)
+        if self.nlte_data is not None and eng.nlte_collision_data is not self.nlte_collision_data:
+            eng.set_nlte_collision_data(self.nlte_collision_data)
 
     def update_plasma(self, t_radiative, dilution_factor, ionization="nebular", excitation="dilute-lte",
                       radiative_rates_type="dilute-blackbody", *, volume=None, w_epsilon=1e-10, time_of_simulation=None):
