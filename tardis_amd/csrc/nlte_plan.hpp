@@ -1,8 +1,10 @@
 // nlte_plan.hpp -- the host's decisions of the NLTE excitation stage of tardis_mc_update_plasma as pure functions: which form of the
-// solve kernel a species takes, what the forms cost in LDS and scratch, and the check of a TardisMcNlteData before anything is indexed.
+// solve kernel a species takes, what the forms cost in LDS and scratch, which species go into which launch, and the check of a
+// TardisMcNlteData before anything is indexed.
 //
 // Standard C++ only (no HIP header, no context, no device call): tests/test_nlte_excitation_host.py pins the rule through
-// tardis_mc_nlte_solve_path and the check through tardis_mc_check_nlte_data.  The kernels are in nlte_excitation.hpp.
+// tardis_mc_nlte_solve_path and the check through tardis_mc_check_nlte_data, tests/test_nlte_plan.py the launches through a shim around
+// plan_launches.  The kernels are in nlte_excitation.hpp.
 // Likewise the check of a TardisMcNlteCollisionData and the bounds rule of its temperature grid (tests/test_nlte_collision_host.py
 // through tardis_mc_check_nlte_collision_data); the collisional rates add to entries the matrix already has, so the working set, the
 // LDS limit, the size classes and the 141-level boundary are what they were.
@@ -54,6 +56,49 @@ inline int lds_class(long long levels)
     for (int c = 0; c < N_LDS_CLASSES; ++c)
         if (levels <= LDS_CLASS_LEVELS[c]) return c;
     return N_LDS_CLASSES - 1;
+}
+
+// The launches of the solve kernel for species of levels[sp] levels over n_shells shells and a value of option nlte_lds_levels (`threshold`,
+// as in choose_path).  `list`: the order the species are launched in; `slab`, parallel to it: the offset in doubles of a species' first slab
+// in the scratch of the global form (0 in the LDS form); a launch covers list[first .. first + count).  The LDS form goes out per size
+// class in class order, a class in index order, with the working set of its largest member as dynamic LDS; then one launch of the global
+// form in index order, a slab of work_bytes per (species, shell).  refused >= 0: that species' slabs (refused_bytes), alone or with the
+// refused_before_bytes of those before it, exceed MAX_SCRATCH_BYTES; nothing else of the plan is to be used then.
+struct Launch { int first, count; size_t lds_bytes; bool global; };
+struct LaunchPlan {
+    std::vector<int> list;
+    std::vector<long long> slab;
+    std::vector<Launch> launches;
+    long long scratch_doubles = 0, refused = -1, refused_bytes = 0, refused_before_bytes = 0;  // (scratch_doubles: all slabs of the global form)
+    size_t max_lds_bytes = 0;  // the largest dynamic LDS a launch asks for
+};
+inline LaunchPlan plan_launches(const std::vector<int> &levels, long long n_shells, long long threshold = -1)
+{
+    LaunchPlan p;
+    const int NS = (int)levels.size();
+    for (int c = 0; c < N_LDS_CLASSES; ++c) {
+        const int first = (int)p.list.size();
+        long long largest = 0;
+        for (int sp = 0; sp < NS; ++sp)
+            if (choose_path(levels[sp], threshold) == PATH_LDS && lds_class(levels[sp]) == c) { p.list.push_back(sp); largest = std::max<long long>(largest, levels[sp]); }
+        if ((int)p.list.size() > first) p.launches.push_back({first, (int)p.list.size() - first, (size_t)work_bytes(largest), false});
+        p.max_lds_bytes = std::max(p.max_lds_bytes, (size_t)work_bytes(largest));
+    }
+    p.slab.assign(p.list.size(), 0);
+    const int first = (int)p.list.size();
+    for (int sp = 0; sp < NS; ++sp) {
+        if (choose_path(levels[sp], threshold) != PATH_GLOBAL) continue;
+        p.list.push_back(sp);
+        p.slab.push_back(p.scratch_doubles);
+        const long long bytes = work_bytes(levels[sp]) * n_shells;
+        if (bytes > MAX_SCRATCH_BYTES || p.scratch_doubles * 8 + bytes > MAX_SCRATCH_BYTES) {
+            p.refused = sp; p.refused_bytes = bytes; p.refused_before_bytes = p.scratch_doubles * 8;
+            return p;
+        }
+        p.scratch_doubles += bytes / 8;
+    }
+    if ((int)p.list.size() > first) p.launches.push_back({first, (int)p.list.size() - first, 0, true});
+    return p;
 }
 
 // What tardis_mc_set_nlte_data checks before it indexes anything, on plain arrays: the species against the ions (ion_level_edge[I+1]),

@@ -65,6 +65,13 @@ struct DevBuf {
     void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
     template <typename T> T *as() const { return static_cast<T *>(p); }
 };
+// what the release() of a stage's state (TardisMcContext::ou / pl / nl / nc) is made of
+template <typename... Bufs> void release_buffers(Bufs &...bufs) { (bufs.release(), ...); }
+template <size_t N> void destroy_events(hipEvent_t (&ev)[N])
+{
+    for (hipEvent_t &e : ev)
+        if (e) { (void)hipEventDestroy(e); e = nullptr; }
+}
 
 // ---- RCCL, bound lazily
 struct Id128 { char bytes[TARDIS_MC_UNIQUE_ID_BYTES]; };
@@ -326,46 +333,57 @@ struct TardisMcContext {
     std::vector<int> h_idx[5];
     std::vector<double> h_nu;
     bool h_macro = false;
-    DevBuf ou_f_lu, ou_wave, ou_g_lower, ou_g_upper, ou_level_lower, ou_level_upper, ou_coef, ou_long_blocks;
-    DevBuf ou_n_t, ou_shell, ou_beta_t, ou_sef_t, ou_j_t;
-    bool have_line_data = false, ou_have_coef = false, ou_valid = false;  // (ou_valid: beta_t / sef_t / j_t belong to the resident tau_t / prob_t)
-    long long ou_levels = 0, ou_n_long = 0, ou_long_rows_built = -1;
-    long long ou_long_rows = -1;  // option opacity_update_long_rows: -1 the rule of opacity_update_plan.hpp, else the threshold itself
-    double ou_sobolev_coefficient = 0.0;
-    hipEvent_t ev_ou[4] = {nullptr, nullptr, nullptr, nullptr};  // start | behind the line kernel | behind the block kernels | end of the last update (tardis_mc_last_opacity_update_ms)
-    bool ou_timed = false;
+    struct OpacityUpdate {
+        DevBuf f_lu, wave, g_lower, g_upper, level_lower, level_upper, coef, long_blocks;
+        DevBuf n_t, shell, beta_t, sef_t, j_t;
+        std::vector<int> h_lower, h_upper;  // host copies of the line data's levels: what set_nlte_data checks its lines against
+        bool have = false, have_coef = false, valid = false;  // (have: line data installed; valid: beta_t / sef_t / j_t belong to the resident tau_t / prob_t)
+        long long levels = 0, n_long = 0, long_rows_built = -1;
+        long long long_rows = -1;  // option opacity_update_long_rows: -1 the rule of opacity_update_plan.hpp, else the threshold itself
+        double sobolev_coefficient = 0.0;
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start | behind the line kernel | behind the block kernels | end of the last update (tardis_mc_last_opacity_update_ms)
+        bool timed = false;
+        void release() { release_buffers(f_lu, wave, g_lower, g_upper, level_lower, level_upper, coef, long_blocks, n_t, shell, beta_t, sef_t, j_t); destroy_events(ev); }
+    } ou;
     // Plasma update (plasma_update.hpp).  Per set_plasma_data: the atomic data of the levels and ions, the map level -> ion, the list of the ions that
     // take the row form of the partition kernel.  Per update_plasma: lbf_t[S][K]; Z, phi, N [I][S]; the solved n_e [S]; {status, passes}.
-    DevBuf pl_energy, pl_g, pl_meta, pl_level_ion, pl_ion_edge, pl_elem_edge, pl_charge, pl_chi, pl_zeta_t, pl_zeta, pl_density, pl_long_ions;
-    DevBuf pl_lbf_t, pl_z, pl_phi, pl_n_ion, pl_n_e, pl_status;
-    std::vector<int> pl_h_ion_edge;
-    double pl_t_min = 0.0, pl_t_max = 0.0, pl_chi_0 = 0.0, pl_link = 0.0;
-    bool have_plasma_data = false, pl_valid = false, pl_timed = false;  // (pl_valid: Z / N / n_e belong to the resident n_t)
-    int pl_ions = 0, pl_elements = 0, pl_nt = 0, pl_iterations = 0;
-    long long pl_n_long = 0, pl_long_rows_built = -2;
-    long long pl_long_rows = -1;         // option plasma_update_long_rows: -1 the rule of plasma_update_plan.hpp, else the threshold itself
-    long long pl_max_iterations = 1000;  // option plasma_max_iterations: bound on the passes of the electron-density iteration
-    hipEvent_t ev_pl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // start | Boltzmann | partition | ionisation | populations (tardis_mc_last_plasma_update_ms)
+    struct PlasmaUpdate {
+        DevBuf energy, g, meta, level_ion, ion_edge, elem_edge, charge, chi, zeta_t, zeta, density, long_ions;
+        DevBuf lbf_t, z, phi, n_ion, n_e, status;
+        std::vector<int> h_ion_edge;
+        double t_min = 0.0, t_max = 0.0, chi_0 = 0.0, link = 0.0;
+        bool have = false, valid = false, timed = false;  // (have: plasma data installed; valid: Z / N / n_e belong to the resident n_t)
+        int ions = 0, elements = 0, nt = 0, iterations = 0;
+        long long n_long = 0, long_rows_built = -2;
+        long long long_rows = -1;         // option plasma_update_long_rows: -1 the rule of plasma_update_plan.hpp, else the threshold itself
+        long long max_iterations = 1000;  // option plasma_max_iterations: bound on the passes of the electron-density iteration
+        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // start | Boltzmann | partition | ionisation | populations (tardis_mc_last_plasma_update_ms)
+        void release() { release_buffers(energy, g, meta, level_ion, ion_edge, elem_edge, charge, chi, zeta_t, zeta, density, long_ions, lbf_t, z, phi, n_ion, n_e, status); destroy_events(ev); }
+    } pl;
     // NLTE excitation (nlte_excitation.hpp).  Per set_nlte_data: the species (first level, levels, first row of x, line edges), the lines (their id in
     // the line list, local levels, Einstein coefficients) and, per value of option nlte_lds_levels, the launches: the LDS form per size class, the
     // global form with its slab offsets.  Per update_plasma: r_ul / r_lu [S][NL], x [S][NX], the status words [NS][S], the slabs, (mode 1) the shell work.
-    struct NlteLaunch { int first, count; size_t lds_bytes; bool global; };
-    DevBuf nl_line_id, nl_a_ul, nl_b_ul, nl_b_lu, nl_lower, nl_upper, nl_sp_k0, nl_sp_n, nl_sp_x0, nl_sp_line_edge, nl_list, nl_slab;
-    DevBuf nl_r_ul, nl_r_lu, nl_x_t, nl_status, nl_scratch, nl_work;
-    std::vector<int> nl_h_n, nl_h_ion, nl_h_status;
-    std::vector<NlteLaunch> nl_launches;
-    std::vector<int> ou_h_lower, ou_h_upper;  // host copies of the line data's levels: what set_nlte_data checks its lines against
-    bool have_nlte = false, nl_valid = false, nl_timed = false, nl_ran = false;  // (nl_valid: lbf_t and x are those of the last successful update's NLTE stage)
-    int nl_coronal = 0, nl_classical = 0;
-    long long nl_species = 0, nl_lines = 0, nl_nx = 0, nl_scratch_doubles = 0;
-    long long nl_lds_levels = -1, nl_lists_built = -2;  // option nlte_lds_levels: -1 the rule of nlte_plan.hpp, else the threshold itself
-    hipEvent_t ev_nl[3] = {nullptr, nullptr, nullptr};  // start | rates | solve (tardis_mc_last_nlte_ms)
+    struct NlteExcitation {
+        DevBuf line_id, a_ul, b_ul, b_lu, lower, upper, sp_k0, sp_n, sp_x0, sp_line_edge, list, slab;
+        DevBuf r_ul, r_lu, x_t, status, scratch, work;
+        std::vector<int> h_n, h_ion, h_status;
+        std::vector<nlte::Launch> launches;
+        bool have = false, valid = false, timed = false, ran = false;  // (have: NLTE data installed; valid: lbf_t and x are those of the last successful update's NLTE stage)
+        int coronal = 0, classical = 0;
+        long long species = 0, lines = 0, nx = 0, scratch_doubles = 0;
+        long long lds_levels = -1, lists_built = -2;  // option nlte_lds_levels: -1 the rule of nlte_plan.hpp, else the threshold itself
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // start | rates | solve (tardis_mc_last_nlte_ms)
+        void release() { release_buffers(line_id, a_ul, b_ul, b_lu, lower, upper, sp_k0, sp_n, sp_x0, sp_line_edge, list, slab, r_ul, r_lu, x_t, status, scratch, work); destroy_events(ev); }
+    } nl;
     // Collisional rates of the NLTE species (nlte_excitation.hpp).  Per set_nlte_collision_data: the temperature grid, C_ul as [NT][NP], delta_e,
     // 1 / g_ratio, the pairs' local levels and the species' pair edges.  Per update_plasma: c_ul / c_lu [S][NP] (tardis_mc_get_nlte_collision_rates).
-    DevBuf nc_temperatures, nc_c_t, nc_delta_e, nc_inv_g, nc_lower, nc_upper, nc_sp_pair_edge, nc_c_ul, nc_c_lu;
-    bool have_nc = false, nc_valid = false;  // (nc_valid: c_ul / c_lu are those of the last successful update)
-    long long nc_pairs = 0, nc_nt = 0;
-    double nc_t_first = 0.0, nc_t_last = 0.0;
+    struct NlteCollisions {
+        DevBuf temperatures, c_t, delta_e, inv_g, lower, upper, sp_pair_edge, c_ul, c_lu;
+        bool have = false, valid = false;  // (have: collision data installed; valid: c_ul / c_lu are those of the last successful update)
+        long long pairs = 0, nt = 0;
+        double t_first = 0.0, t_last = 0.0;
+        void release() { release_buffers(temperatures, c_t, delta_e, inv_g, lower, upper, sp_pair_edge, c_ul, c_lu); }
+    } nc;
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -733,6 +751,54 @@ hipError_t host_copy(TardisMcContext *ctx, const std::vector<CopyJob> &jobs, boo
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// A table kept shell-major on the device, [S][rows], into the caller's [rows, S] through the staging buffer (host null: nothing to do)
+int download_transposed(TardisMcContext *ctx, double *host, const double *table_t, size_t rows)
+{
+    if (!host) return TARDIS_MC_OK;
+    const size_t S = (size_t)ctx->n_shells;
+    HIP_TRY(ctx, ctx->staging.ensure(rows * S * sizeof(double)));
+    HIP_TRY(ctx, launch_transpose(ctx->stream, table_t, ctx->staging.as<double>(), (long long)S, (long long)rows));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, host_copy(ctx, {{(void *)host, ctx->staging.p, rows * S * sizeof(double)}}, false));
+    return TARDIS_MC_OK;
+}
+
+// the events of a stage: made on first use; read as the milliseconds between neighbours, out[k] (may be null) = ev[k] .. ev[k + 1] for k < n
+template <size_t N>
+int ensure_events(TardisMcContext *ctx, hipEvent_t (&ev)[N])
+{
+    for (hipEvent_t &e : ev)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    return TARDIS_MC_OK;
+}
+int event_intervals_ms(TardisMcContext *ctx, const hipEvent_t *ev, int n, double *const *out)
+{
+    HIP_TRY(ctx, hipEventSynchronize(ev[n]));
+    for (int k = 0; k < n; ++k) {
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+        if (out[k]) *out[k] = ms;
+    }
+    return TARDIS_MC_OK;
+}
+
+// tardis/constants.py:1 (CODATA 2010, cgs), for the host side of the radiation field and of the opacity / plasma / NLTE updates; c is mc::C_LIGHT
+constexpr double H_PLANCK = 6.62606957e-27, K_BOLTZMANN = 1.3806488e-16, M_ELECTRON = 9.10938291e-28;
+
+// The resident stages of the plasma chain sit on a ladder of installed data: opacity state -> line data -> plasma data -> NLTE data -> collision data,
+// every rung in the indices of the one above it.  Whoever replaces a rung (set_opacity: what the first rung sits on) drops it and every rung below it --
+// what is installed (`have`) and what the last update computed from it (`valid`).  This is the only place that knows the order; a new stage adds its rung.
+enum Rung { RUNG_LINE_DATA, RUNG_PLASMA_DATA, RUNG_NLTE_DATA, RUNG_COLLISION_DATA };
+void drop_from(TardisMcContext *ctx, Rung rung)
+{
+    switch (rung) {
+    case RUNG_LINE_DATA: ctx->ou.have = ctx->ou.valid = false; [[fallthrough]];
+    case RUNG_PLASMA_DATA: ctx->pl.have = ctx->pl.valid = false; [[fallthrough]];
+    case RUNG_NLTE_DATA: ctx->nl.have = ctx->nl.valid = false; [[fallthrough]];
+    case RUNG_COLLISION_DATA: ctx->nc.have = ctx->nc.valid = false;
+    }
 }
 
 // the sixteen per-packet result arrays on the device / in a TardisMcResult, in one order: out_nu, out_e, nine tracker doubles, five tracker integers
@@ -2066,20 +2132,7 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     ctx->lane_save.release(); ctx->wave_save.release(); ctx->suspended_dev.release();
     for (int k = 0; k < 2; ++k) { ctx->lane_save_c[k].release(); ctx->wave_save_c[k].release(); ctx->seeded_states_c[k].release(); }
     ctx->drain_census.release();
-    for (hipEvent_t e : ctx->ev_ou) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_pl) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_nl) if (e) (void)hipEventDestroy(e);
-    for (DevBuf *b : {&ctx->nl_line_id, &ctx->nl_a_ul, &ctx->nl_b_ul, &ctx->nl_b_lu, &ctx->nl_lower, &ctx->nl_upper, &ctx->nl_sp_k0, &ctx->nl_sp_n, &ctx->nl_sp_x0,
-                      &ctx->nl_sp_line_edge, &ctx->nl_list, &ctx->nl_slab, &ctx->nl_r_ul, &ctx->nl_r_lu, &ctx->nl_x_t, &ctx->nl_status, &ctx->nl_scratch, &ctx->nl_work,
-                      &ctx->nc_temperatures, &ctx->nc_c_t, &ctx->nc_delta_e, &ctx->nc_inv_g, &ctx->nc_lower, &ctx->nc_upper, &ctx->nc_sp_pair_edge, &ctx->nc_c_ul, &ctx->nc_c_lu})
-        b->release();
-    for (DevBuf *b : {&ctx->pl_energy, &ctx->pl_g, &ctx->pl_meta, &ctx->pl_level_ion, &ctx->pl_ion_edge, &ctx->pl_elem_edge, &ctx->pl_charge, &ctx->pl_chi,
-                      &ctx->pl_zeta_t, &ctx->pl_zeta, &ctx->pl_density, &ctx->pl_long_ions, &ctx->pl_lbf_t, &ctx->pl_z, &ctx->pl_phi, &ctx->pl_n_ion,
-                      &ctx->pl_n_e, &ctx->pl_status})
-        b->release();
-    for (DevBuf *b : {&ctx->ou_f_lu, &ctx->ou_wave, &ctx->ou_g_lower, &ctx->ou_g_upper, &ctx->ou_level_lower, &ctx->ou_level_upper, &ctx->ou_coef,
-                      &ctx->ou_long_blocks, &ctx->ou_n_t, &ctx->ou_shell, &ctx->ou_beta_t, &ctx->ou_sef_t, &ctx->ou_j_t})
-        b->release();
+    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release();
     ctx->vq_req.release(); ctx->vq_items.release(); ctx->vq_count.release(); ctx->vq_jsave.release();
     if (ctx->suspended_host) (void)hipHostFree(ctx->suspended_host);
     for (hipEvent_t e : ctx->ev_post) if (e) (void)hipEventDestroy(e);
@@ -2172,10 +2225,10 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "log_sets") ctx->log_sets = (value == 1 || value == 2) ? (int)value : 0;  // 1: the estimator passes of an epoch run before the next epoch, not beside it; 0: automatic
     else if (n == "source_max_iterations") ctx->source_max_iterations = std::max<long long>(1, value);
     else if (n == "chunk_packets") ctx->chunk_packets = std::max<long long>(1024, value);
-    else if (n == "opacity_update_long_rows") ctx->ou_long_rows = value < 0 ? -1 : value;
-    else if (n == "plasma_update_long_rows") ctx->pl_long_rows = value < 0 ? -1 : value;
-    else if (n == "plasma_max_iterations") ctx->pl_max_iterations = std::max<long long>(1, value);
-    else if (n == "nlte_lds_levels") ctx->nl_lds_levels = value < 0 ? -1 : value;
+    else if (n == "opacity_update_long_rows") ctx->ou.long_rows = value < 0 ? -1 : value;
+    else if (n == "plasma_update_long_rows") ctx->pl.long_rows = value < 0 ? -1 : value;
+    else if (n == "plasma_max_iterations") ctx->pl.max_iterations = std::max<long long>(1, value);
+    else if (n == "nlte_lds_levels") ctx->nl.lds_levels = value < 0 ? -1 : value;
     else return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return TARDIS_MC_OK;
 }
@@ -2425,9 +2478,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     if ((rc = up32(4, ctx->tline, macro ? o->transition_line_id : &zero64, macro ? T : 1))) return rc;
     ctx->h_nu.assign(o->line_list_nu, o->line_list_nu + L);
     ctx->h_macro = macro;
-    ctx->have_line_data = ctx->ou_valid = false;  // (the line data belong to one topology: tardis_mc_set_line_data again)
-    ctx->have_plasma_data = ctx->pl_valid = false;  // (... and the plasma data to one set of line data)
-    ctx->have_nlte = ctx->nl_valid = ctx->have_nc = ctx->nc_valid = false;
+    drop_from(ctx, RUNG_LINE_DATA);  // (the line data belong to one topology: tardis_mc_set_line_data again)
     tmark("index tables int32 up");
     {   // packed macro-atom tables of the cooperative kernel
         std::vector<int> lb(2 * (macro ? L : 1), 0), rec(4 * (macro ? T : 1), 0);
@@ -3454,7 +3505,7 @@ static int radiation_field_enqueue(TardisMcContext *ctx, double time_of_simulati
     EstLayout e = est_layout(S, L, ctx->est_G, ctx->est_copies);
     double *base = ctx->est.as<double>();
     // constants, tardis/constants.py:1 (CODATA 2010, cgs)
-    const double h = 6.62606957e-27, k_b = 1.3806488e-16, sigma_sb = 5.670373e-5, c = mc::C_LIGHT, zeta5 = 1.0369277551433699;
+    const double h = H_PLANCK, k_b = K_BOLTZMANN, sigma_sb = 5.670373e-5, c = mc::C_LIGHT, zeta5 = 1.0369277551433699;
     const double pi = 3.141592653589793;
     RadFieldConsts k;
     k.t_rad_const = (pi * pi * pi * pi / (15 * 24 * zeta5)) * (h / k_b);
@@ -3973,9 +4024,7 @@ int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
 {
     if (!ctx || !d) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_opacity) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity must precede set_line_data");
-    ctx->have_line_data = ctx->ou_valid = false;
-    ctx->have_plasma_data = ctx->pl_valid = false;  // (the plasma data sit on the levels of one set of line data)
-    ctx->have_nlte = ctx->nl_valid = ctx->have_nc = ctx->nc_valid = false;
+    drop_from(ctx, RUNG_LINE_DATA);
     const size_t L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans;
     if (d->n_lines != (int64_t)L || d->n_transitions != (int64_t)T)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "line data of %lld lines / %lld transitions, the resident opacity state has %zu / %zu",
@@ -4004,28 +4053,28 @@ int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
-    if ((rc = upload(ctx, ctx->ou_f_lu, d->f_lu, L))) return rc;
-    if ((rc = upload(ctx, ctx->ou_wave, d->wavelength_cm, L))) return rc;
-    if ((rc = upload(ctx, ctx->ou_g_lower, d->g_lower, L))) return rc;
-    if ((rc = upload(ctx, ctx->ou_g_upper, d->g_upper, L))) return rc;
-    if ((rc = upload(ctx, ctx->ou_level_lower, lo.data(), L))) return rc;
-    if ((rc = upload(ctx, ctx->ou_level_upper, up.data(), L))) return rc;
-    if (coef && (rc = upload(ctx, ctx->ou_coef, d->transition_probability_coef, T))) return rc;
+    if ((rc = upload(ctx, ctx->ou.f_lu, d->f_lu, L))) return rc;
+    if ((rc = upload(ctx, ctx->ou.wave, d->wavelength_cm, L))) return rc;
+    if ((rc = upload(ctx, ctx->ou.g_lower, d->g_lower, L))) return rc;
+    if ((rc = upload(ctx, ctx->ou.g_upper, d->g_upper, L))) return rc;
+    if ((rc = upload(ctx, ctx->ou.level_lower, lo.data(), L))) return rc;
+    if ((rc = upload(ctx, ctx->ou.level_upper, up.data(), L))) return rc;
+    if (coef && (rc = upload(ctx, ctx->ou.coef, d->transition_probability_coef, T))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (lo / up are the sources of asynchronous copies)
-    ctx->ou_h_lower.swap(lo);
-    ctx->ou_h_upper.swap(up);
-    ctx->ou_levels = d->n_levels;
-    ctx->ou_have_coef = coef;
-    ctx->ou_sobolev_coefficient = d->sobolev_coefficient;
-    ctx->ou_long_rows_built = -2;  // (the list of the long blocks is made by the first update)
-    ctx->have_line_data = true;
+    ctx->ou.h_lower.swap(lo);
+    ctx->ou.h_upper.swap(up);
+    ctx->ou.levels = d->n_levels;
+    ctx->ou.have_coef = coef;
+    ctx->ou.sobolev_coefficient = d->sobolev_coefficient;
+    ctx->ou.long_rows_built = -2;  // (the list of the long blocks is made by the first update)
+    ctx->ou.have = true;
     return TARDIS_MC_OK;
 }
 
 // What both producers of an opacity state check before they touch anything: the call order and the j_blues_mode block of the update.
 static int opacity_update_check(TardisMcContext *ctx, const TardisMcOpacityUpdate *u)
 {
-    if (!ctx->have_opacity || !ctx->have_line_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_line_data must precede update_opacity");
+    if (!ctx->have_opacity || !ctx->ou.have) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_line_data must precede update_opacity");
     if (!ctx->have_geometry) return fail(ctx, TARDIS_MC_ERR_STATE, "update_opacity needs the geometry (time_explosion)");
     const int mode = u->j_blues_mode;
     if (mode != 0 && mode != 1) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown j_blues_mode %d", mode);
@@ -4040,27 +4089,36 @@ static int opacity_update_check(TardisMcContext *ctx, const TardisMcOpacityUpdat
     return TARDIS_MC_OK;
 }
 
+// Which segments of an edge table take the 16-lane row form of their kernel -- macro-atom blocks here, ions in the partition function, one rule with the
+// `threshold` as choose_path takes it -- uploaded into `list`, their number into `count`.
+static_assert(plup::PATH_ROW == opup::PATH_ROW && plup::LONG_ION_LEVELS == opup::LONG_BLOCK_ROWS, "the partition kernel's rule is the block kernel's");
+static int upload_row_form_list(TardisMcContext *ctx, const std::vector<int> &edge, long long threshold, DevBuf &list, long long *count)
+{
+    std::vector<int> rows;
+    for (size_t b = 0; b + 1 < edge.size(); ++b)
+        if (opup::choose_path((long long)edge[b + 1] - edge[b], threshold) == opup::PATH_ROW) rows.push_back((int)b);
+    int rc;
+    if ((rc = upload(ctx, list, rows.data(), rows.size()))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *count = (long long)rows.size();
+    return TARDIS_MC_OK;
+}
+
 // The list of the blocks that take the row form, and the buffers of an update: n_t[S][K], the [S] inputs, beta_t / sef_t / j_t [S][L].
 static int opacity_update_buffers(TardisMcContext *ctx)
 {
-    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, K = (size_t)ctx->ou_levels;
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, K = (size_t)ctx->ou.levels;
     int rc;
-    const bool blocks = ctx->ou_have_coef && ctx->h_macro && ctx->n_levels > 0;
-    if (blocks && ctx->ou_long_rows_built != ctx->ou_long_rows) {  // which blocks take the row form (opacity_update_plan.hpp)
-        const std::vector<int> &edge = ctx->h_idx[1];
-        std::vector<int> list;
-        for (size_t b = 0; b + 1 < edge.size(); ++b)
-            if (opup::choose_path((long long)edge[b + 1] - edge[b], ctx->ou_long_rows) == opup::PATH_ROW) list.push_back((int)b);
-        if ((rc = upload(ctx, ctx->ou_long_blocks, list.data(), list.size()))) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->ou_n_long = (long long)list.size();
-        ctx->ou_long_rows_built = ctx->ou_long_rows;
+    const bool blocks = ctx->ou.have_coef && ctx->h_macro && ctx->n_levels > 0;
+    if (blocks && ctx->ou.long_rows_built != ctx->ou.long_rows) {
+        if ((rc = upload_row_form_list(ctx, ctx->h_idx[1], ctx->ou.long_rows, ctx->ou.long_blocks, &ctx->ou.n_long))) return rc;
+        ctx->ou.long_rows_built = ctx->ou.long_rows;
     }
-    HIP_TRY(ctx, ctx->ou_n_t.ensure(K * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->ou_shell.ensure(4 * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->ou_beta_t.ensure(L * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->ou_sef_t.ensure(L * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->ou_j_t.ensure(L * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ou.n_t.ensure(K * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ou.shell.ensure(4 * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ou.beta_t.ensure(L * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ou.sef_t.ensure(L * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ou.j_t.ensure(L * S * sizeof(double)));
     return TARDIS_MC_OK;
 }
 
@@ -4072,104 +4130,94 @@ int tardis_mc_update_opacity(TardisMcContext *ctx, const TardisMcOpacityUpdate *
     int rc;
     if ((rc = opacity_update_check(ctx, u))) return rc;
     const int mode = u->j_blues_mode;
-    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou_levels;
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou.levels;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->sf_valid = false;
-    ctx->ou_valid = false;
-    ctx->pl_valid = false;  // (the populations are the caller's from here on)
+    ctx->ou.valid = false;
+    ctx->pl.valid = false;  // (the populations are the caller's from here on)
     if ((rc = opacity_update_buffers(ctx))) return rc;
     HIP_TRY(ctx, ctx->staging.ensure(K * S * sizeof(double)));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // populations [K,S] -> [S][K]
     HIP_TRY(ctx, host_copy(ctx, {{(void *)u->level_number_density, ctx->staging.p, K * S * sizeof(double)}}, true));
     if (u->electron_density && (rc = upload(ctx, ctx->n_e, u->electron_density, S))) return rc;
-    double *d_t = ctx->ou_shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
+    double *d_t = ctx->ou.shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
     if (mode == 0) {
         HIP_TRY(ctx, hipMemcpyAsync(d_t, u->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(d_w, u->dilution_factor, S * 8, hipMemcpyHostToDevice, ctx->stream));
     }
-    ctx->ou_timed = false;
-    for (hipEvent_t &e : ctx->ev_ou)
-        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    ctx->ou.timed = false;
+    if ((rc = ensure_events(ctx, ctx->ou.ev))) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[0], ctx->stream));
-    HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->staging.as<double>(), ctx->ou_n_t.as<double>(), (long long)K, (long long)S));
+    HIP_TRY(ctx, hipEventRecord(ctx->ou.ev[0], ctx->stream));
+    HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->staging.as<double>(), ctx->ou.n_t.as<double>(), (long long)K, (long long)S));
     return opacity_update_stages(ctx, u);
 }
 
-// Everything of an opacity update behind the populations: with n_t[S][K], the electron densities and (mode 0) t_rad / W resident and ev_start / ev_ou[0]
+// Everything of an opacity update behind the populations: with n_t[S][K], the electron densities and (mode 0) t_rad / W resident and ev_start / ou.ev[0]
 // recorded, the detailed j_blues of mode 1, the line kernel, the block kernels and the derived tables.  Shared by tardis_mc_update_opacity (populations
 // uploaded) and tardis_mc_update_plasma (populations solved on the device).
 static int opacity_update_stages(TardisMcContext *ctx, const TardisMcOpacityUpdate *u)
 {
     const int mode = u->j_blues_mode;
-    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans, K = (size_t)ctx->ou_levels;
-    const bool blocks = ctx->ou_have_coef && ctx->h_macro && ctx->n_levels > 0;
-    double *d_t = ctx->ou_shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans, K = (size_t)ctx->ou.levels;
+    const bool blocks = ctx->ou.have_coef && ctx->h_macro && ctx->n_levels > 0;
+    double *d_t = ctx->ou.shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
     int rc;
-    if (mode == 1 && (rc = radiation_field_enqueue(ctx, u->time_of_simulation, u->volume, u->w_epsilon, u->detailed_optical_window, ctx->ou_shell,
-                                                   ctx->ou_j_t.as<double>())))
+    if (mode == 1 && (rc = radiation_field_enqueue(ctx, u->time_of_simulation, u->volume, u->w_epsilon, u->detailed_optical_window, ctx->ou.shell,
+                                                   ctx->ou.j_t.as<double>())))
         return rc;
+    const double h = H_PLANCK, c = mc::C_LIGHT;
     mc::OpacityUpdateConsts k;
-    {   // constants, tardis/constants.py:1 (CODATA 2010, cgs): those of tardis_mc_radiation_field
-        const double h = 6.62606957e-27, k_b = 1.3806488e-16, c = mc::C_LIGHT;
-        k.coef_sobolev = ctx->ou_sobolev_coefficient; k.t_exp = ctx->t_exp; k.planck_coef = 2 * h / (c * c); k.h = h; k.k_b = k_b;
-    }
+    k.coef_sobolev = ctx->ou.sobolev_coefficient; k.t_exp = ctx->t_exp; k.planck_coef = 2 * h / (c * c); k.h = h; k.k_b = K_BOLTZMANN;
     {
         const unsigned bx = (unsigned)std::min<size_t>((L + 255) / 256, 1024);
         auto kernel = mode == 0 ? mc::opacity_line_kernel<true> : mc::opacity_line_kernel<false>;
-        hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->ou_n_t.as<double>(), ctx->ou_level_lower.as<int>(),
-                           ctx->ou_level_upper.as<int>(), ctx->ou_f_lu.as<double>(), ctx->ou_wave.as<double>(), ctx->ou_g_lower.as<double>(),
-                           ctx->ou_g_upper.as<double>(), ctx->nu_line.as<double>(), d_t, d_w, (long long)K, (long long)L, k, ctx->tau_t.as<double>(),
-                           ctx->ou_beta_t.as<double>(), ctx->ou_sef_t.as<double>(), ctx->ou_j_t.as<double>());
+        hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->ou.n_t.as<double>(), ctx->ou.level_lower.as<int>(),
+                           ctx->ou.level_upper.as<int>(), ctx->ou.f_lu.as<double>(), ctx->ou.wave.as<double>(), ctx->ou.g_lower.as<double>(),
+                           ctx->ou.g_upper.as<double>(), ctx->nu_line.as<double>(), d_t, d_w, (long long)K, (long long)L, k, ctx->tau_t.as<double>(),
+                           ctx->ou.beta_t.as<double>(), ctx->ou.sef_t.as<double>(), ctx->ou.j_t.as<double>());
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[1], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ou.ev[1], ctx->stream));
     if (blocks) {
-        const long long n_blocks = ctx->n_levels, n_long = ctx->ou_n_long;
-        const long long long_rows = ctx->ou_long_rows < 0 ? opup::LONG_BLOCK_ROWS : ctx->ou_long_rows;
+        const long long n_blocks = ctx->n_levels, n_long = ctx->ou.n_long;
+        const long long long_rows = ctx->ou.long_rows < 0 ? opup::LONG_BLOCK_ROWS : ctx->ou.long_rows;
         if (n_long < n_blocks) {
             const long long n = n_blocks * (long long)S;
             hipLaunchKernelGGL(mc::opacity_block_lane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->block_edge.as<int>(), (int)n_blocks,
-                               (long long)T, (long long)L, (int)S, long_rows, ctx->ou_coef.as<double>(), ctx->tline.as<int>(), ctx->ttype.as<int>(),
-                               ctx->ou_beta_t.as<double>(), ctx->ou_sef_t.as<double>(), ctx->ou_j_t.as<double>(), ctx->prob_t.as<double>());
+                               (long long)T, (long long)L, (int)S, long_rows, ctx->ou.coef.as<double>(), ctx->tline.as<int>(), ctx->ttype.as<int>(),
+                               ctx->ou.beta_t.as<double>(), ctx->ou.sef_t.as<double>(), ctx->ou.j_t.as<double>(), ctx->prob_t.as<double>());
             HIP_TRY(ctx, hipGetLastError());
         }
         if (n_long > 0) {
             const long long n = n_long * (long long)S * 16;
-            hipLaunchKernelGGL(mc::opacity_block_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ou_long_blocks.as<int>(), (int)n_long,
-                               ctx->block_edge.as<int>(), (long long)T, (long long)L, (int)S, ctx->ou_coef.as<double>(), ctx->tline.as<int>(), ctx->ttype.as<int>(),
-                               ctx->ou_beta_t.as<double>(), ctx->ou_sef_t.as<double>(), ctx->ou_j_t.as<double>(), ctx->prob_t.as<double>());
+            hipLaunchKernelGGL(mc::opacity_block_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ou.long_blocks.as<int>(), (int)n_long,
+                               ctx->block_edge.as<int>(), (long long)T, (long long)L, (int)S, ctx->ou.coef.as<double>(), ctx->tline.as<int>(), ctx->ttype.as<int>(),
+                               ctx->ou.beta_t.as<double>(), ctx->ou.sef_t.as<double>(), ctx->ou.j_t.as<double>(), ctx->prob_t.as<double>());
             HIP_TRY(ctx, hipGetLastError());
         }
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[2], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ou.ev[2], ctx->stream));
     rc = derive_opacity_tables(ctx, L, S, T, [](const char *) {});
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[3], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ou.ev[3], ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->timed = true;
     ctx->chunks_timed = 0;
-    ctx->ou_timed = true;
-    ctx->ou_valid = true;
+    ctx->ou.timed = true;
+    ctx->ou.valid = true;
     return TARDIS_MC_OK;
 }
 
 int tardis_mc_last_opacity_update_ms(TardisMcContext *ctx, double *out_line_ms, double *out_block_ms, double *out_derive_ms)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->ou_timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_opacity has been timed yet");
+    if (!ctx->ou.timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_opacity has been timed yet");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_ou[3]));
-    float a = 0.f, b = 0.f, c = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&a, ctx->ev_ou[0], ctx->ev_ou[1]));
-    HIP_TRY(ctx, hipEventElapsedTime(&b, ctx->ev_ou[1], ctx->ev_ou[2]));
-    HIP_TRY(ctx, hipEventElapsedTime(&c, ctx->ev_ou[2], ctx->ev_ou[3]));
-    if (out_line_ms) *out_line_ms = a;
-    if (out_block_ms) *out_block_ms = b;
-    if (out_derive_ms) *out_derive_ms = c;
-    return TARDIS_MC_OK;
+    double *const out[3] = {out_line_ms, out_block_ms, out_derive_ms};
+    return event_intervals_ms(ctx, ctx->ou.ev, 3, out);
 }
 
 int tardis_mc_get_opacity(TardisMcContext *ctx, double *tau_sobolev, double *transition_probabilities, double *beta_sobolev,
@@ -4177,25 +4225,17 @@ int tardis_mc_get_opacity(TardisMcContext *ctx, double *tau_sobolev, double *tra
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_opacity) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity must precede get_opacity");
-    if ((beta_sobolev || stimulated_emission_factor || j_blues) && !ctx->ou_valid)
+    if ((beta_sobolev || stimulated_emission_factor || j_blues) && !ctx->ou.valid)
         return fail(ctx, TARDIS_MC_ERR_STATE, "beta_sobolev, stimulated_emission_factor and j_blues exist only after update_opacity");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans;
-    HIP_TRY(ctx, ctx->staging.ensure(std::max(L, T) * S * sizeof(double)));
-    auto down = [&](double *host, const double *table_t, size_t rows) -> int {  // [S][rows] -> [rows,S]
-        if (!host) return TARDIS_MC_OK;
-        HIP_TRY(ctx, launch_transpose(ctx->stream, table_t, ctx->staging.as<double>(), (long long)S, (long long)rows));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, host_copy(ctx, {{(void *)host, ctx->staging.p, rows * S * sizeof(double)}}, false));
-        return TARDIS_MC_OK;
-    };
+    HIP_TRY(ctx, ctx->staging.ensure(std::max(L, T) * S * sizeof(double)));  // (the largest of them first: the staging grows once)
     int rc;
-    if ((rc = down(tau_sobolev, ctx->tau_t.as<double>(), L))) return rc;
-    if ((rc = down(transition_probabilities, ctx->prob_t.as<double>(), T))) return rc;
-    if ((rc = down(beta_sobolev, ctx->ou_beta_t.as<double>(), L))) return rc;
-    if ((rc = down(stimulated_emission_factor, ctx->ou_sef_t.as<double>(), L))) return rc;
-    if ((rc = down(j_blues, ctx->ou_j_t.as<double>(), L))) return rc;
-    return TARDIS_MC_OK;
+    if ((rc = download_transposed(ctx, tau_sobolev, ctx->tau_t.as<double>(), L))) return rc;
+    if ((rc = download_transposed(ctx, transition_probabilities, ctx->prob_t.as<double>(), T))) return rc;
+    if ((rc = download_transposed(ctx, beta_sobolev, ctx->ou.beta_t.as<double>(), L))) return rc;
+    if ((rc = download_transposed(ctx, stimulated_emission_factor, ctx->ou.sef_t.as<double>(), L))) return rc;
+    return download_transposed(ctx, j_blues, ctx->ou.j_t.as<double>(), L);
 }
 
 
@@ -4205,11 +4245,10 @@ int tardis_mc_plasma_update_path(int64_t levels) { return plup::choose_path((lon
 int tardis_mc_set_plasma_data(TardisMcContext *ctx, const TardisMcPlasmaData *d)
 {
     if (!ctx || !d) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->have_opacity || !ctx->have_line_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_line_data must precede set_plasma_data");
-    ctx->have_plasma_data = ctx->pl_valid = false;
-    ctx->have_nlte = ctx->nl_valid = ctx->have_nc = ctx->nc_valid = false;  // (the NLTE species are ions of one set of plasma data)
-    if (d->n_levels != ctx->ou_levels)
-        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "plasma data of %lld levels, the line data have %lld", (long long)d->n_levels, ctx->ou_levels);
+    if (!ctx->have_opacity || !ctx->ou.have) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_line_data must precede set_plasma_data");
+    drop_from(ctx, RUNG_PLASMA_DATA);
+    if (d->n_levels != ctx->ou.levels)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "plasma data of %lld levels, the line data have %lld", (long long)d->n_levels, ctx->ou.levels);
     if (d->n_shells != ctx->n_shells)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "plasma data of %lld shells, the resident opacity state has %d", (long long)d->n_shells, ctx->n_shells);
     if (d->n_ions <= 0 || d->n_elements <= 0 || d->n_ions > d->n_levels || d->n_elements > d->n_ions || d->n_zeta_temperatures < 2 ||
@@ -4240,24 +4279,24 @@ int tardis_mc_set_plasma_data(TardisMcContext *ctx, const TardisMcPlasmaData *d)
     for (size_t k = 0; k < K; ++k) meta[k] = d->level_metastable[k] != 0;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
-    if ((rc = upload(ctx, ctx->pl_energy, d->level_energy, K))) return rc;
-    if ((rc = upload(ctx, ctx->pl_g, d->level_g, K))) return rc;
-    if ((rc = upload(ctx, ctx->pl_meta, meta.data(), K))) return rc;
-    if ((rc = upload(ctx, ctx->pl_level_ion, level_ion.data(), K))) return rc;
-    if ((rc = upload(ctx, ctx->pl_ion_edge, ion_edge.data(), I + 1))) return rc;
-    if ((rc = upload(ctx, ctx->pl_elem_edge, elem_edge.data(), E + 1))) return rc;
-    if ((rc = upload(ctx, ctx->pl_charge, d->ion_charge, I))) return rc;
-    if ((rc = upload(ctx, ctx->pl_chi, d->ionization_energy, I))) return rc;
-    if ((rc = upload(ctx, ctx->pl_zeta_t, d->zeta_temperatures, NT))) return rc;
-    if ((rc = upload(ctx, ctx->pl_zeta, d->zeta, I * NT))) return rc;
-    if ((rc = upload(ctx, ctx->pl_density, d->number_density, E * S))) return rc;
+    if ((rc = upload(ctx, ctx->pl.energy, d->level_energy, K))) return rc;
+    if ((rc = upload(ctx, ctx->pl.g, d->level_g, K))) return rc;
+    if ((rc = upload(ctx, ctx->pl.meta, meta.data(), K))) return rc;
+    if ((rc = upload(ctx, ctx->pl.level_ion, level_ion.data(), K))) return rc;
+    if ((rc = upload(ctx, ctx->pl.ion_edge, ion_edge.data(), I + 1))) return rc;
+    if ((rc = upload(ctx, ctx->pl.elem_edge, elem_edge.data(), E + 1))) return rc;
+    if ((rc = upload(ctx, ctx->pl.charge, d->ion_charge, I))) return rc;
+    if ((rc = upload(ctx, ctx->pl.chi, d->ionization_energy, I))) return rc;
+    if ((rc = upload(ctx, ctx->pl.zeta_t, d->zeta_temperatures, NT))) return rc;
+    if ((rc = upload(ctx, ctx->pl.zeta, d->zeta, I * NT))) return rc;
+    if ((rc = upload(ctx, ctx->pl.density, d->number_density, E * S))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors are the sources of asynchronous copies)
-    ctx->pl_h_ion_edge.swap(ion_edge);
-    ctx->pl_ions = (int)I; ctx->pl_elements = (int)E; ctx->pl_nt = (int)NT;
-    ctx->pl_t_min = d->zeta_temperatures[0]; ctx->pl_t_max = d->zeta_temperatures[NT - 1];
-    ctx->pl_chi_0 = d->chi_0; ctx->pl_link = d->link_t_rad_t_electron;
-    ctx->pl_long_rows_built = -2;  // (the list of the long ions is made by the first update)
-    ctx->have_plasma_data = true;
+    ctx->pl.h_ion_edge.swap(ion_edge);
+    ctx->pl.ions = (int)I; ctx->pl.elements = (int)E; ctx->pl.nt = (int)NT;
+    ctx->pl.t_min = d->zeta_temperatures[0]; ctx->pl.t_max = d->zeta_temperatures[NT - 1];
+    ctx->pl.chi_0 = d->chi_0; ctx->pl.link = d->link_t_rad_t_electron;
+    ctx->pl.long_rows_built = -2;  // (the list of the long ions is made by the first update)
+    ctx->pl.have = true;
     return TARDIS_MC_OK;
 }
 
@@ -4274,101 +4313,85 @@ int tardis_mc_check_nlte_data(const TardisMcNlteData *d, int64_t n_ions, const i
     return err.empty() ? TARDIS_MC_OK : fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
 }
 
-// The launches of the solve kernel for the current value of option nlte_lds_levels: the species of the LDS form by size class, those of the global form
-// with the offsets of their slabs.  TARDIS_MC_ERR_UNSUPPORTED when the slabs of all shells together exceed nlte::MAX_SCRATCH_BYTES.
+// The launches of the solve kernel for the current value of option nlte_lds_levels (nlte::plan_launches), their lists uploaded.
+// TARDIS_MC_ERR_UNSUPPORTED when the slabs of all shells together exceed nlte::MAX_SCRATCH_BYTES.
 static int nlte_build_lists(TardisMcContext *ctx)
 {
-    const long long NS = ctx->nl_species, S = ctx->n_shells;
-    std::vector<int> list;
-    std::vector<long long> slab;
-    std::vector<TardisMcContext::NlteLaunch> launches;
-    for (int c = 0; c < nlte::N_LDS_CLASSES; ++c) {
-        const int first = (int)list.size();
-        long long largest = 0;
-        for (long long sp = 0; sp < NS; ++sp) {
-            const long long n = ctx->nl_h_n[(size_t)sp];
-            if (nlte::choose_path(n, ctx->nl_lds_levels) == nlte::PATH_LDS && nlte::lds_class(n) == c) { list.push_back((int)sp); largest = std::max(largest, n); }
-        }
-        if ((int)list.size() > first) launches.push_back({first, (int)list.size() - first, (size_t)nlte::work_bytes(largest), false});
-    }
-    slab.assign(list.size(), 0);
-    const int first = (int)list.size();
-    long long doubles = 0;
-    for (long long sp = 0; sp < NS; ++sp) {
-        const long long n = ctx->nl_h_n[(size_t)sp];
-        if (nlte::choose_path(n, ctx->nl_lds_levels) != nlte::PATH_GLOBAL) continue;
-        list.push_back((int)sp);
-        slab.push_back(doubles);
-        const long long bytes = nlte::work_bytes(n) * S;
-        if (bytes > nlte::MAX_SCRATCH_BYTES || doubles * 8 + bytes > nlte::MAX_SCRATCH_BYTES)
-            return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "NLTE species %lld (ion %d, %lld levels) needs %lld bytes of scratch over %lld shells in the global-memory form of the "
-                        "solve: with the %lld bytes of the species before it that exceeds the %lld the plan allows", sp, ctx->nl_h_ion[(size_t)sp], n, bytes, S, doubles * 8,
-                        nlte::MAX_SCRATCH_BYTES);
-        doubles += bytes / 8;
-    }
-    if ((int)list.size() > first) launches.push_back({first, (int)list.size() - first, 0, true});
-    size_t lds = 0;
-    for (const TardisMcContext::NlteLaunch &l : launches)
-        if (!l.global) lds = std::max(lds, l.lds_bytes);
-    if (lds > 65536)  // (a launch with more dynamic LDS than the default bound has to announce it: once per list, not per update)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&mc::nlte_solve_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long long S = ctx->n_shells;
+    nlte::LaunchPlan plan = nlte::plan_launches(ctx->nl.h_n, S, ctx->nl.lds_levels);
+    if (plan.refused >= 0)
+        return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "NLTE species %lld (ion %d, %lld levels) needs %lld bytes of scratch over %lld shells in the global-memory form of the "
+                    "solve: with the %lld bytes of the species before it that exceeds the %lld the plan allows", plan.refused, ctx->nl.h_ion[(size_t)plan.refused],
+                    (long long)ctx->nl.h_n[(size_t)plan.refused], plan.refused_bytes, S, plan.refused_before_bytes, nlte::MAX_SCRATCH_BYTES);
+    if (plan.max_lds_bytes > 65536)  // (a launch with more dynamic LDS than the default bound has to announce it: once per list, not per update)
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&mc::nlte_solve_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)plan.max_lds_bytes));
     int rc;
-    if ((rc = upload(ctx, ctx->nl_list, list.data(), list.size()))) return rc;
-    if ((rc = upload(ctx, ctx->nl_slab, slab.data(), slab.size()))) return rc;
+    if ((rc = upload(ctx, ctx->nl.list, plan.list.data(), plan.list.size()))) return rc;
+    if ((rc = upload(ctx, ctx->nl.slab, plan.slab.data(), plan.slab.size()))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->nl_launches.swap(launches);
-    ctx->nl_scratch_doubles = doubles;
-    ctx->nl_lists_built = ctx->nl_lds_levels;
+    ctx->nl.launches.swap(plan.launches);
+    ctx->nl.scratch_doubles = plan.scratch_doubles;
+    ctx->nl.lists_built = ctx->nl.lds_levels;
     return TARDIS_MC_OK;
 }
 
 int tardis_mc_set_nlte_data(TardisMcContext *ctx, const TardisMcNlteData *d)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->have_plasma_data) return fail(ctx, TARDIS_MC_ERR_STATE, "set_plasma_data must precede set_nlte_data");
-    ctx->have_nlte = ctx->nl_valid = ctx->have_nc = ctx->nc_valid = false;
+    if (!ctx->pl.have) return fail(ctx, TARDIS_MC_ERR_STATE, "set_plasma_data must precede set_nlte_data");
+    drop_from(ctx, RUNG_NLTE_DATA);
     if (!d) return TARDIS_MC_OK;
     if (d->n_nlte_lines > 0 && (!d->A_ul || !d->B_ul || !d->B_lu)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid NLTE data: a pointer is missing");
     // everything the kernels index with is checked here, on the host
     std::vector<int> lower, upper;
-    const std::string err = nlte::check_data((long long)d->n_species, d->species_ion, (long long)d->n_nlte_lines, d->species_line_edge, d->line_id, (long long)ctx->pl_ions,
-                                             ctx->pl_h_ion_edge.data(), (long long)ctx->n_lines, ctx->ou_h_lower.data(), ctx->ou_h_upper.data(), &lower, &upper);
+    const std::string err = nlte::check_data((long long)d->n_species, d->species_ion, (long long)d->n_nlte_lines, d->species_line_edge, d->line_id, (long long)ctx->pl.ions,
+                                             ctx->pl.h_ion_edge.data(), (long long)ctx->n_lines, ctx->ou.h_lower.data(), ctx->ou.h_upper.data(), &lower, &upper);
     if (!err.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
     const size_t NS = (size_t)d->n_species, NL = (size_t)d->n_nlte_lines;
     std::vector<int> k0(NS), n(NS), x0(NS), ion(NS), edge(NS + 1), line_id(NL);
     long long nx = 0;
     for (size_t sp = 0; sp < NS; ++sp) {
         ion[sp] = (int)d->species_ion[sp];
-        k0[sp] = ctx->pl_h_ion_edge[(size_t)ion[sp]];
-        n[sp] = ctx->pl_h_ion_edge[(size_t)ion[sp] + 1] - k0[sp];
+        k0[sp] = ctx->pl.h_ion_edge[(size_t)ion[sp]];
+        n[sp] = ctx->pl.h_ion_edge[(size_t)ion[sp] + 1] - k0[sp];
         x0[sp] = (int)nx;
         nx += n[sp];
     }
     for (size_t sp = 0; sp <= NS; ++sp) edge[sp] = (int)d->species_line_edge[sp];
     for (size_t q = 0; q < NL; ++q) line_id[q] = (int)d->line_id[q];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->nl_species = (long long)NS; ctx->nl_lines = (long long)NL; ctx->nl_nx = nx;
-    ctx->nl_h_n = n; ctx->nl_h_ion = ion;
+    ctx->nl.species = (long long)NS; ctx->nl.lines = (long long)NL; ctx->nl.nx = nx;
+    ctx->nl.h_n = n; ctx->nl.h_ion = ion;
     int rc;
     if ((rc = nlte_build_lists(ctx))) return rc;
-    if ((rc = upload(ctx, ctx->nl_line_id, line_id.data(), NL))) return rc;
-    if ((rc = upload(ctx, ctx->nl_a_ul, d->A_ul, NL))) return rc;
-    if ((rc = upload(ctx, ctx->nl_b_ul, d->B_ul, NL))) return rc;
-    if ((rc = upload(ctx, ctx->nl_b_lu, d->B_lu, NL))) return rc;
-    if ((rc = upload(ctx, ctx->nl_lower, lower.data(), NL))) return rc;
-    if ((rc = upload(ctx, ctx->nl_upper, upper.data(), NL))) return rc;
-    if ((rc = upload(ctx, ctx->nl_sp_k0, k0.data(), NS))) return rc;
-    if ((rc = upload(ctx, ctx->nl_sp_n, n.data(), NS))) return rc;
-    if ((rc = upload(ctx, ctx->nl_sp_x0, x0.data(), NS))) return rc;
-    if ((rc = upload(ctx, ctx->nl_sp_line_edge, edge.data(), NS + 1))) return rc;
+    if ((rc = upload(ctx, ctx->nl.line_id, line_id.data(), NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl.a_ul, d->A_ul, NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl.b_ul, d->B_ul, NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl.b_lu, d->B_lu, NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl.lower, lower.data(), NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl.upper, upper.data(), NL))) return rc;
+    if ((rc = upload(ctx, ctx->nl.sp_k0, k0.data(), NS))) return rc;
+    if ((rc = upload(ctx, ctx->nl.sp_n, n.data(), NS))) return rc;
+    if ((rc = upload(ctx, ctx->nl.sp_x0, x0.data(), NS))) return rc;
+    if ((rc = upload(ctx, ctx->nl.sp_line_edge, edge.data(), NS + 1))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors are the sources of asynchronous copies)
-    ctx->nl_coronal = d->coronal_approximation != 0;
-    ctx->nl_classical = d->classical_nebular != 0;
-    ctx->have_nlte = true;
+    ctx->nl.coronal = d->coronal_approximation != 0;
+    ctx->nl.classical = d->classical_nebular != 0;
+    ctx->nl.have = true;
     return TARDIS_MC_OK;
 }
 
 /* ---- collisional rates of the NLTE species (atomic data with collision_data) ------------------------------ */
+// scipy's interp1d bounds error of the reference's get_collision_matrix: t_e = link * t_rad of every shell against the temperature grid
+static int collision_temperature_check(TardisMcContext *ctx, double link, long long n_shells, const double *t_radiative, double t_first, double t_last)
+{
+    const long long s = nlte::first_t_e_outside(link, n_shells, t_radiative, t_first, t_last);
+    if (s < 0) return TARDIS_MC_OK;
+    return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "t_electron of shell %lld = %g lies outside the collision temperatures [%g, %g]", s, link * t_radiative[s], t_first,
+                t_last);
+}
+
 static std::string nlte_collision_check(const TardisMcNlteCollisionData *d, long long n_nlte_species, const int64_t *species_levels)
 {
     return nlte::check_collision_data((long long)d->n_species, n_nlte_species, species_levels, (long long)d->n_temperatures, d->collision_temperatures,
@@ -4381,25 +4404,20 @@ int tardis_mc_check_nlte_collision_data(const TardisMcNlteCollisionData *d, int6
     if (!d || !species_levels) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid collision data: a pointer is missing");
     const std::string err = nlte_collision_check(d, (long long)n_species, species_levels);
     if (!err.empty()) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
-    if (t_radiative) {
-        const double t0 = d->collision_temperatures[0], t1 = d->collision_temperatures[d->n_temperatures - 1];
-        const long long s = nlte::first_t_e_outside(link_t_rad_t_electron, (long long)n_shells, t_radiative, t0, t1);
-        if (s >= 0)
-            return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "t_electron of shell %lld = %g lies outside the collision temperatures [%g, %g]", s,
-                        link_t_rad_t_electron * t_radiative[s], t0, t1);
-    }
-    return TARDIS_MC_OK;
+    if (!t_radiative) return TARDIS_MC_OK;
+    return collision_temperature_check(nullptr, link_t_rad_t_electron, (long long)n_shells, t_radiative, d->collision_temperatures[0],
+                                       d->collision_temperatures[d->n_temperatures - 1]);
 }
 
 int tardis_mc_set_nlte_collision_data(TardisMcContext *ctx, const TardisMcNlteCollisionData *d)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->have_nlte) return fail(ctx, TARDIS_MC_ERR_STATE, "set_nlte_data must precede set_nlte_collision_data");
-    ctx->have_nc = ctx->nc_valid = false;
+    if (!ctx->nl.have) return fail(ctx, TARDIS_MC_ERR_STATE, "set_nlte_data must precede set_nlte_collision_data");
+    drop_from(ctx, RUNG_COLLISION_DATA);
     if (!d) return TARDIS_MC_OK;
     // everything the kernels index with is checked here, on the host
-    std::vector<int64_t> levels(ctx->nl_h_n.begin(), ctx->nl_h_n.end());
-    const std::string err = nlte_collision_check(d, ctx->nl_species, levels.data());
+    std::vector<int64_t> levels(ctx->nl.h_n.begin(), ctx->nl.h_n.end());
+    const std::string err = nlte_collision_check(d, ctx->nl.species, levels.data());
     if (!err.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
     const size_t NS = (size_t)d->n_species, NP = (size_t)d->n_pairs, NT = (size_t)d->n_temperatures;
     std::vector<int> edge(NS + 1), lower(NP), upper(NP);
@@ -4413,53 +4431,47 @@ int tardis_mc_set_nlte_collision_data(TardisMcContext *ctx, const TardisMcNlteCo
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
-    if ((rc = upload(ctx, ctx->nc_temperatures, d->collision_temperatures, NT))) return rc;
-    if ((rc = upload(ctx, ctx->nc_c_t, c_t.data(), NT * NP))) return rc;
-    if ((rc = upload(ctx, ctx->nc_delta_e, d->delta_e, NP))) return rc;
-    if ((rc = upload(ctx, ctx->nc_inv_g, inv_g.data(), NP))) return rc;
-    if ((rc = upload(ctx, ctx->nc_lower, lower.data(), NP))) return rc;
-    if ((rc = upload(ctx, ctx->nc_upper, upper.data(), NP))) return rc;
-    if ((rc = upload(ctx, ctx->nc_sp_pair_edge, edge.data(), NS + 1))) return rc;
+    if ((rc = upload(ctx, ctx->nc.temperatures, d->collision_temperatures, NT))) return rc;
+    if ((rc = upload(ctx, ctx->nc.c_t, c_t.data(), NT * NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc.delta_e, d->delta_e, NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc.inv_g, inv_g.data(), NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc.lower, lower.data(), NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc.upper, upper.data(), NP))) return rc;
+    if ((rc = upload(ctx, ctx->nc.sp_pair_edge, edge.data(), NS + 1))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors are the sources of asynchronous copies)
-    ctx->nc_pairs = (long long)NP; ctx->nc_nt = (long long)NT;
-    ctx->nc_t_first = d->collision_temperatures[0]; ctx->nc_t_last = d->collision_temperatures[NT - 1];
-    ctx->have_nc = true;
+    ctx->nc.pairs = (long long)NP; ctx->nc.nt = (long long)NT;
+    ctx->nc.t_first = d->collision_temperatures[0]; ctx->nc.t_last = d->collision_temperatures[NT - 1];
+    ctx->nc.have = true;
     return TARDIS_MC_OK;
 }
 
 int tardis_mc_get_nlte_collision_rates(TardisMcContext *ctx, double *c_ul, double *c_lu)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->nc_valid || !ctx->nl_valid || !ctx->pl_valid)
+    if (!ctx->nc.valid || !ctx->nl.valid || !ctx->pl.valid)
         return fail(ctx, TARDIS_MC_ERR_STATE, "get_nlte_collision_rates needs a successful update_plasma that ran the NLTE stage with collision data");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t S = (size_t)ctx->n_shells, NP = (size_t)ctx->nc_pairs;
+    const size_t NP = (size_t)ctx->nc.pairs;
     if (NP == 0) return TARDIS_MC_OK;
-    for (int k = 0; k < 2; ++k) {  // [S][NP] -> [NP,S]
-        double *host = k == 0 ? c_ul : c_lu;
-        if (!host) continue;
-        HIP_TRY(ctx, ctx->staging.ensure(NP * S * sizeof(double)));
-        HIP_TRY(ctx, launch_transpose(ctx->stream, (k == 0 ? ctx->nc_c_ul : ctx->nc_c_lu).as<double>(), ctx->staging.as<double>(), (long long)S, (long long)NP));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, host_copy(ctx, {{(void *)host, ctx->staging.p, NP * S * sizeof(double)}}, false));
-    }
-    return TARDIS_MC_OK;
+    int rc;
+    if ((rc = download_transposed(ctx, c_ul, ctx->nc.c_ul.as<double>(), NP))) return rc;
+    return download_transposed(ctx, c_lu, ctx->nc.c_lu.as<double>(), NP);
 }
 
 // What the NLTE stage needs before the update's first kernel: the launches for the current option, the buffers of a call.
 static int nlte_prepare(TardisMcContext *ctx)
 {
     int rc;
-    if (ctx->nl_lists_built != ctx->nl_lds_levels && (rc = nlte_build_lists(ctx))) return rc;
-    const size_t S = (size_t)ctx->n_shells, NL = (size_t)ctx->nl_lines;
-    HIP_TRY(ctx, ctx->nl_r_ul.ensure(std::max<size_t>(1, NL * S) * sizeof(double)));
-    HIP_TRY(ctx, ctx->nl_r_lu.ensure(std::max<size_t>(1, NL * S) * sizeof(double)));
-    HIP_TRY(ctx, ctx->nl_x_t.ensure((size_t)ctx->nl_nx * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->nl_status.ensure((size_t)ctx->nl_species * S * sizeof(int)));
-    HIP_TRY(ctx, ctx->nl_scratch.ensure(std::max<size_t>(1, (size_t)ctx->nl_scratch_doubles) * sizeof(double)));
-    if (ctx->have_nc) {
-        HIP_TRY(ctx, ctx->nc_c_ul.ensure(std::max<size_t>(1, (size_t)ctx->nc_pairs * S) * sizeof(double)));
-        HIP_TRY(ctx, ctx->nc_c_lu.ensure(std::max<size_t>(1, (size_t)ctx->nc_pairs * S) * sizeof(double)));
+    if (ctx->nl.lists_built != ctx->nl.lds_levels && (rc = nlte_build_lists(ctx))) return rc;
+    const size_t S = (size_t)ctx->n_shells, NL = (size_t)ctx->nl.lines;
+    HIP_TRY(ctx, ctx->nl.r_ul.ensure(std::max<size_t>(1, NL * S) * sizeof(double)));
+    HIP_TRY(ctx, ctx->nl.r_lu.ensure(std::max<size_t>(1, NL * S) * sizeof(double)));
+    HIP_TRY(ctx, ctx->nl.x_t.ensure((size_t)ctx->nl.nx * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->nl.status.ensure((size_t)ctx->nl.species * S * sizeof(int)));
+    HIP_TRY(ctx, ctx->nl.scratch.ensure(std::max<size_t>(1, (size_t)ctx->nl.scratch_doubles) * sizeof(double)));
+    if (ctx->nc.have) {
+        HIP_TRY(ctx, ctx->nc.c_ul.ensure(std::max<size_t>(1, (size_t)ctx->nc.pairs * S) * sizeof(double)));
+        HIP_TRY(ctx, ctx->nc.c_lu.ensure(std::max<size_t>(1, (size_t)ctx->nc.pairs * S) * sizeof(double)));
     }
     return TARDIS_MC_OK;
 }
@@ -4468,21 +4480,21 @@ static int nlte_prepare(TardisMcContext *ctx)
 // previous one, then a workgroup per (species, shell) that overwrites the species' rows of lbf_t.  d_t / d_w: the call's (t_rad, W) on the device.
 static int nlte_stage(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p, const double *beta_t, const double *d_t, const double *d_w)
 {
-    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, NL = (size_t)ctx->nl_lines;
-    const double h = 6.62606957e-27, k_b = 1.3806488e-16, c = mc::C_LIGHT;  // tardis/constants.py (CODATA 2010, cgs): those of the line kernel
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, NL = (size_t)ctx->nl.lines;
+    const double h = H_PLANCK, k_b = K_BOLTZMANN, c = mc::C_LIGHT;
     int rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_nl[0], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->nl.ev[0], ctx->stream));
     mc::NlteRateArgs r{};
     r.S = (int)S; r.L = (long long)L; r.NL = (long long)NL;
-    r.line_id = ctx->nl_line_id.as<int>(); r.a_ul = ctx->nl_a_ul.as<double>(); r.b_ul = ctx->nl_b_ul.as<double>(); r.b_lu = ctx->nl_b_lu.as<double>();
+    r.line_id = ctx->nl.line_id.as<int>(); r.a_ul = ctx->nl.a_ul.as<double>(); r.b_ul = ctx->nl.b_ul.as<double>(); r.b_lu = ctx->nl.b_lu.as<double>();
     r.nu_line = ctx->nu_line.as<double>(); r.beta_t = beta_t; r.t_rad = d_t; r.w = d_w;
     r.planck_coef = 2 * h / (c * c); r.h = h; r.k_b = k_b; r.w_epsilon = p->w_epsilon; r.c_ang = c * 1e8; r.optical_window = p->detailed_optical_window;
-    r.r_ul_t = ctx->nl_r_ul.as<double>(); r.r_lu_t = ctx->nl_r_lu.as<double>();
-    const int jmode = ctx->nl_coronal ? mc::NLTE_J_CORONAL : p->j_blues_mode == 1 ? mc::NLTE_J_DETAILED : mc::NLTE_J_DILUTE;
+    r.r_ul_t = ctx->nl.r_ul.as<double>(); r.r_lu_t = ctx->nl.r_lu.as<double>();
+    const int jmode = ctx->nl.coronal ? mc::NLTE_J_CORONAL : p->j_blues_mode == 1 ? mc::NLTE_J_DETAILED : mc::NLTE_J_DILUTE;
     if (jmode == mc::NLTE_J_DETAILED) {  // the estimators' own t_rad / W / norm, as the j_blues kernel of the stages behind will compute them again
-        if ((rc = radiation_field_enqueue(ctx, p->time_of_simulation, p->volume, p->w_epsilon, p->detailed_optical_window, ctx->nl_work, nullptr))) return rc;
+        if ((rc = radiation_field_enqueue(ctx, p->time_of_simulation, p->volume, p->w_epsilon, p->detailed_optical_window, ctx->nl.work, nullptr))) return rc;
         EstLayout e = est_layout(ctx->est_S, ctx->est_L, ctx->est_G, ctx->est_copies);
-        const double *work = ctx->nl_work.as<double>();
+        const double *work = ctx->nl.work.as<double>();
         r.t_rad = work + S; r.w = work + 2 * S; r.norm = work + 3 * S; r.jblue_t = ctx->est.as<double>() + e.jblue;
     }
     if (NL > 0) {
@@ -4492,265 +4504,254 @@ static int nlte_stage(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p, const
         hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, r);
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (ctx->have_nc && ctx->nc_pairs > 0) {  // c_ul / c_lu of every pair from the call's t_rad (counted with the rates kernel: assemble_ms)
+    if (ctx->nc.have && ctx->nc.pairs > 0) {  // c_ul / c_lu of every pair from the call's t_rad (counted with the rates kernel: assemble_ms)
         mc::NlteCollisionArgs c{};
-        c.S = (int)S; c.NT = (int)ctx->nc_nt; c.NP = ctx->nc_pairs;
-        c.temperatures = ctx->nc_temperatures.as<double>(); c.c_t = ctx->nc_c_t.as<double>(); c.delta_e = ctx->nc_delta_e.as<double>();
-        c.inv_g_ratio = ctx->nc_inv_g.as<double>(); c.t_rad = d_t; c.link = ctx->pl_link;
-        c.c_ul_t = ctx->nc_c_ul.as<double>(); c.c_lu_t = ctx->nc_c_lu.as<double>();
-        const unsigned bx = (unsigned)std::min<size_t>(((size_t)ctx->nc_pairs + 255) / 256, 1024);
+        c.S = (int)S; c.NT = (int)ctx->nc.nt; c.NP = ctx->nc.pairs;
+        c.temperatures = ctx->nc.temperatures.as<double>(); c.c_t = ctx->nc.c_t.as<double>(); c.delta_e = ctx->nc.delta_e.as<double>();
+        c.inv_g_ratio = ctx->nc.inv_g.as<double>(); c.t_rad = d_t; c.link = ctx->pl.link;
+        c.c_ul_t = ctx->nc.c_ul.as<double>(); c.c_lu_t = ctx->nc.c_lu.as<double>();
+        const unsigned bx = (unsigned)std::min<size_t>(((size_t)ctx->nc.pairs + 255) / 256, 1024);
         hipLaunchKernelGGL(mc::nlte_collision_kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, c);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_nl[1], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->nl.ev[1], ctx->stream));
     mc::NlteSolveArgs a{};
-    a.S = (int)S; a.K = ctx->ou_levels; a.NL = (long long)NL; a.NX = ctx->nl_nx;
-    a.sp_k0 = ctx->nl_sp_k0.as<int>(); a.sp_n = ctx->nl_sp_n.as<int>(); a.sp_x0 = ctx->nl_sp_x0.as<int>(); a.sp_line_edge = ctx->nl_sp_line_edge.as<int>();
-    a.lower = ctx->nl_lower.as<int>(); a.upper = ctx->nl_upper.as<int>(); a.r_ul_t = r.r_ul_t; a.r_lu_t = r.r_lu_t; a.g = ctx->pl_g.as<double>();
-    a.lbf_t = ctx->pl_lbf_t.as<double>(); a.x_t = ctx->nl_x_t.as<double>(); a.status = ctx->nl_status.as<int>(); a.scratch = ctx->nl_scratch.as<double>();
-    if (ctx->have_nc && ctx->nc_pairs > 0) {  // (the resident electron density is still the previous update's: this call installs its own behind the solve)
-        a.NP = ctx->nc_pairs; a.sp_pair_edge = ctx->nc_sp_pair_edge.as<int>(); a.pair_lower = ctx->nc_lower.as<int>(); a.pair_upper = ctx->nc_upper.as<int>();
-        a.c_ul_t = ctx->nc_c_ul.as<double>(); a.c_lu_t = ctx->nc_c_lu.as<double>(); a.n_e = ctx->n_e.as<double>();
+    a.S = (int)S; a.K = ctx->ou.levels; a.NL = (long long)NL; a.NX = ctx->nl.nx;
+    a.sp_k0 = ctx->nl.sp_k0.as<int>(); a.sp_n = ctx->nl.sp_n.as<int>(); a.sp_x0 = ctx->nl.sp_x0.as<int>(); a.sp_line_edge = ctx->nl.sp_line_edge.as<int>();
+    a.lower = ctx->nl.lower.as<int>(); a.upper = ctx->nl.upper.as<int>(); a.r_ul_t = r.r_ul_t; a.r_lu_t = r.r_lu_t; a.g = ctx->pl.g.as<double>();
+    a.lbf_t = ctx->pl.lbf_t.as<double>(); a.x_t = ctx->nl.x_t.as<double>(); a.status = ctx->nl.status.as<int>(); a.scratch = ctx->nl.scratch.as<double>();
+    if (ctx->nc.have && ctx->nc.pairs > 0) {  // (the resident electron density is still the previous update's: this call installs its own behind the solve)
+        a.NP = ctx->nc.pairs; a.sp_pair_edge = ctx->nc.sp_pair_edge.as<int>(); a.pair_lower = ctx->nc.lower.as<int>(); a.pair_upper = ctx->nc.upper.as<int>();
+        a.c_ul_t = ctx->nc.c_ul.as<double>(); a.c_lu_t = ctx->nc.c_lu.as<double>(); a.n_e = ctx->n_e.as<double>();
     }
-    for (const TardisMcContext::NlteLaunch &l : ctx->nl_launches) {
-        a.list = ctx->nl_list.as<int>() + l.first;
-        a.slab = ctx->nl_slab.as<long long>() + l.first;
+    for (const nlte::Launch &l : ctx->nl.launches) {
+        a.list = ctx->nl.list.as<int>() + l.first;
+        a.slab = ctx->nl.slab.as<long long>() + l.first;
         if (l.global) hipLaunchKernelGGL(mc::nlte_solve_kernel<false>, dim3((unsigned)l.count, (unsigned)S), dim3(256), 0, ctx->stream, a);
         else hipLaunchKernelGGL(mc::nlte_solve_kernel<true>, dim3((unsigned)l.count, (unsigned)S), dim3(256), l.lds_bytes, ctx->stream, a);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_nl[2], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->nl.ev[2], ctx->stream));
     return TARDIS_MC_OK;
 }
 
 int tardis_mc_get_nlte(TardisMcContext *ctx, double *level_boltzmann_factor, double *relative_populations)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->nl_valid || !ctx->pl_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "get_nlte needs a successful update_plasma that ran the NLTE stage");
+    if (!ctx->nl.valid || !ctx->pl.valid) return fail(ctx, TARDIS_MC_ERR_STATE, "get_nlte needs a successful update_plasma that ran the NLTE stage");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou_levels, NX = (size_t)ctx->nl_nx;
-    auto down = [&](double *host, const double *table_t, size_t rows) -> int {  // [S][rows] -> [rows,S]
-        if (!host) return TARDIS_MC_OK;
-        HIP_TRY(ctx, ctx->staging.ensure(rows * S * sizeof(double)));
-        HIP_TRY(ctx, launch_transpose(ctx->stream, table_t, ctx->staging.as<double>(), (long long)S, (long long)rows));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, host_copy(ctx, {{(void *)host, ctx->staging.p, rows * S * sizeof(double)}}, false));
-        return TARDIS_MC_OK;
-    };
     int rc;
-    if ((rc = down(level_boltzmann_factor, ctx->pl_lbf_t.as<double>(), K))) return rc;
-    if ((rc = down(relative_populations, ctx->nl_x_t.as<double>(), NX))) return rc;
-    return TARDIS_MC_OK;
+    if ((rc = download_transposed(ctx, level_boltzmann_factor, ctx->pl.lbf_t.as<double>(), (size_t)ctx->ou.levels))) return rc;
+    return download_transposed(ctx, relative_populations, ctx->nl.x_t.as<double>(), (size_t)ctx->nl.nx);
 }
 
 int tardis_mc_last_nlte_ms(TardisMcContext *ctx, double *out_assemble_ms, double *out_solve_ms)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->nl_timed || !ctx->pl_timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_plasma with an NLTE stage has been timed yet");
+    if (!ctx->nl.timed || !ctx->pl.timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_plasma with an NLTE stage has been timed yet");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_nl[2]));
-    float a = 0.f, b = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&a, ctx->ev_nl[0], ctx->ev_nl[1]));
-    HIP_TRY(ctx, hipEventElapsedTime(&b, ctx->ev_nl[1], ctx->ev_nl[2]));
-    if (out_assemble_ms) *out_assemble_ms = a;
-    if (out_solve_ms) *out_solve_ms = b;
+    double *const out[2] = {out_assemble_ms, out_solve_ms};
+    return event_intervals_ms(ctx, ctx->nl.ev, 2, out);
+}
+
+// Everything that can refuse the call before the device is touched: the call order, the modes, the shell bound, the bounds of the two temperature tables.
+static int plasma_update_check(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p, const TardisMcOpacityUpdate *u)
+{
+    if (!ctx->have_opacity || !ctx->ou.have || !ctx->pl.have)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity, set_line_data and set_plasma_data must precede update_plasma");
+    if ((p->ionization_mode != 0 && p->ionization_mode != 1) || (p->excitation_mode != 0 && p->excitation_mode != 1))
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown ionization_mode %d / excitation_mode %d", p->ionization_mode, p->excitation_mode);
+    int rc;
+    if ((rc = opacity_update_check(ctx, u))) return rc;
+    const size_t S = (size_t)ctx->n_shells;
+    if ((long long)S > plup::MAX_SHELLS)
+        return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "update_plasma iterates the electron density inside one workgroup: at most %lld shells", plup::MAX_SHELLS);
+    if (p->ionization_mode == 0)
+        for (size_t s = 0; s < S; ++s)
+            if (!(p->t_radiative[s] >= ctx->pl.t_min && p->t_radiative[s] <= ctx->pl.t_max))
+                return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "t_radiative[%zu] = %g lies outside the zeta table [%g, %g]", s, p->t_radiative[s], ctx->pl.t_min,
+                            ctx->pl.t_max);
+    if (ctx->nl.have && ctx->nc.have) return collision_temperature_check(ctx, ctx->pl.link, (long long)S, p->t_radiative, ctx->nc.t_first, ctx->nc.t_last);
+    return TARDIS_MC_OK;
+}
+
+// The list of the ions that take the row form, the buffers and the events of every stage.  Nothing of a previous update is written to.
+static int plasma_update_prepare(TardisMcContext *ctx)
+{
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou.levels, I = (size_t)ctx->pl.ions;
+    int rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->pl.long_rows_built != ctx->pl.long_rows) {
+        if ((rc = upload_row_form_list(ctx, ctx->pl.h_ion_edge, ctx->pl.long_rows, ctx->pl.long_ions, &ctx->pl.n_long))) return rc;
+        ctx->pl.long_rows_built = ctx->pl.long_rows;
+    }
+    if ((rc = opacity_update_buffers(ctx))) return rc;
+    if (ctx->nl.have && (rc = nlte_prepare(ctx))) return rc;
+    HIP_TRY(ctx, ctx->pl.lbf_t.ensure(K * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl.z.ensure(I * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl.phi.ensure(I * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl.n_ion.ensure(I * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl.n_e.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, ctx->pl.status.ensure(2 * sizeof(int)));
+    if ((rc = ensure_events(ctx, ctx->ou.ev))) return rc;
+    if ((rc = ensure_events(ctx, ctx->pl.ev))) return rc;
+    return ensure_events(ctx, ctx->nl.ev);
+}
+
+// The solve, enqueued: Boltzmann factors, the NLTE stage, partition functions, ionisation.  It writes the stages' own buffers -- lbf_t, x, Z, phi, N, pl.n_e,
+// the status words -- and the call's (t_rad, W); the resident n_t, the electron densities and the opacity tables wait for plasma_update_install.
+static int plasma_update_enqueue(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
+{
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou.levels, I = (size_t)ctx->pl.ions;
+    double *d_t = ctx->ou.shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
+    // beta_sobolev of the previous update, read before this update's line kernel writes over it; none since the last set_opacity: 1.0
+    const double *nlte_beta = ctx->ou.valid && !ctx->nl.classical ? ctx->ou.beta_t.as<double>() : nullptr;
+    int rc;
+    ctx->pl.valid = ctx->nl.valid = ctx->nc.valid = false;
+    HIP_TRY(ctx, hipMemcpyAsync(d_t, p->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_w, p->dilution_factor, S * 8, hipMemcpyHostToDevice, ctx->stream));
+    ctx->nl.ran = ctx->nl.timed = ctx->pl.timed = false;  // (ou.timed and the ou.ev events stay the previous update's until this solve has succeeded)
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[0], ctx->stream));
+    const unsigned bx = (unsigned)std::min<size_t>((K + 255) / 256, 1024);
+    auto kernel = p->excitation_mode == 0 ? mc::plasma_boltzmann_kernel<true> : mc::plasma_boltzmann_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->pl.energy.as<double>(), ctx->pl.g.as<double>(), ctx->pl.meta.as<int>(), d_t,
+                       d_w, (long long)K, K_BOLTZMANN, ctx->pl.lbf_t.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[1], ctx->stream));
+    if (ctx->nl.have && (rc = nlte_stage(ctx, p, nlte_beta, d_t, d_w))) return rc;  // the NLTE species' Boltzmann factors, before anything reads them
+    const long long n_long = ctx->pl.n_long;
+    if (n_long < (long long)I) {
+        const long long n = (long long)I * (long long)S;
+        hipLaunchKernelGGL(mc::plasma_partition_lane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pl.ion_edge.as<int>(), (int)I,
+                           (long long)K, (int)S, ctx->pl.long_rows < 0 ? plup::LONG_ION_LEVELS : ctx->pl.long_rows, ctx->pl.lbf_t.as<double>(), ctx->pl.z.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (n_long > 0) {
+        const long long n = n_long * (long long)S * 16;
+        hipLaunchKernelGGL(mc::plasma_partition_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pl.long_ions.as<int>(), (int)n_long,
+                           ctx->pl.ion_edge.as<int>(), (long long)K, (int)S, ctx->pl.lbf_t.as<double>(), ctx->pl.z.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[2], ctx->stream));
+    mc::PlasmaIonArgs a;
+    a.S = (int)S; a.I = (int)I; a.E = ctx->pl.elements; a.NT = ctx->pl.nt;
+    a.nebular = p->ionization_mode == 0;
+    a.max_iter = ctx->pl.max_iterations;
+    a.link = ctx->pl.link; a.chi_0 = ctx->pl.chi_0; a.k_b = K_BOLTZMANN; a.two_pi_me = 2 * M_PI * M_ELECTRON; a.hh = H_PLANCK * H_PLANCK;
+    a.element_edge = ctx->pl.elem_edge.as<int>(); a.charge = ctx->pl.charge.as<double>(); a.chi = ctx->pl.chi.as<double>();
+    a.zeta_t = ctx->pl.zeta_t.as<double>(); a.zeta = ctx->pl.zeta.as<double>(); a.density = ctx->pl.density.as<double>();
+    a.t_rad = d_t; a.w = d_w; a.z = ctx->pl.z.as<double>();
+    a.phi = ctx->pl.phi.as<double>(); a.n_ion = ctx->pl.n_ion.as<double>(); a.n_e = ctx->pl.n_e.as<double>(); a.status = ctx->pl.status.as<int>();
+    hipLaunchKernelGGL(mc::plasma_ionization_kernel, dim3(1), dim3((unsigned)((S + 63) / 64 * 64)), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[3], ctx->stream));
+    return TARDIS_MC_OK;
+}
+
+// Waits for the solve and reads {status, passes} and the status words of the NLTE solves.  A failed solve is worded here and nowhere else; its kernels are what
+// tardis_mc_last_propagate_ms then reports, between a matching pair of events.
+static int plasma_update_status(TardisMcContext *ctx)
+{
+    const long long S = ctx->n_shells;
+    int status[2] = {mc::PLASMA_NAN, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(status, ctx->pl.status.p, sizeof status, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->nl.have) {
+        ctx->nl.h_status.assign((size_t)(ctx->nl.species * S), -1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->nl.h_status.data(), ctx->nl.status.p, ctx->nl.h_status.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->pl.iterations = status[1];
+    long long nlte_failed = -1;
+    if (ctx->nl.have)
+        for (size_t q = 0; q < ctx->nl.h_status.size() && nlte_failed < 0; ++q)
+            if (ctx->nl.h_status[q] != 0) nlte_failed = (long long)q;
+    if (status[0] == mc::PLASMA_OK && nlte_failed < 0) return TARDIS_MC_OK;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->timed = true;
+    ctx->chunks_timed = 0;
+    if (nlte_failed >= 0) {  // (whatever the stages behind it made of the unfinished Boltzmann factors)
+        const long long sp = nlte_failed / S, shell = nlte_failed % S;
+        const int code = ctx->nl.h_status[(size_t)nlte_failed], n = ctx->nl.h_n[(size_t)sp];
+        if (code >= 1 && code <= n)
+            return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the NLTE solve of species %lld (ion %d, %d levels) in shell %lld met a zero or non-finite pivot in elimination "
+                        "step %d (singular rate matrix); the opacity state is unchanged", sp, ctx->nl.h_ion[(size_t)sp], n, shell, code - 1);
+        return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the NLTE solve of species %lld (ion %d, %d levels) in shell %lld gave %s after all %d elimination steps; the "
+                    "opacity state is unchanged", sp, ctx->nl.h_ion[(size_t)sp], n, shell, code == n + 1 ? "x[0] == 0" : "a population that is not finite", n);
+    }
+    if (status[0] == mc::PLASMA_NAN)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the electron density became NaN in pass %d (PlasmaIonizationError); the opacity state is unchanged", status[1] + 1);
+    return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the electron density has not converged after %d passes (option plasma_max_iterations); the opacity state is unchanged",
+                status[1]);
+}
+
+// The solve is good: the level populations into the resident n_t, the solved electron densities into the resident ones, and on them the opacity update.
+static int plasma_update_install(TardisMcContext *ctx, const TardisMcOpacityUpdate *u)
+{
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou.levels;
+    ctx->sf_valid = ctx->ou.valid = ctx->ou.timed = false;
+    const unsigned bx = (unsigned)std::min<size_t>((K + 255) / 256, 1024);
+    hipLaunchKernelGGL(mc::plasma_population_kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->pl.lbf_t.as<double>(), ctx->pl.level_ion.as<int>(),
+                       ctx->pl.z.as<double>(), ctx->pl.n_ion.as<double>(), (long long)K, (int)S, ctx->ou.n_t.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, ctx->n_e.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->n_e.p, ctx->pl.n_e.p, S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[4], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ou.ev[0], ctx->stream));
+    int rc;
+    if ((rc = opacity_update_stages(ctx, u))) return rc;
+    ctx->pl.timed = ctx->pl.valid = true;
+    ctx->nl.ran = ctx->nl.valid = ctx->nl.timed = ctx->nl.have;
+    ctx->nc.valid = ctx->nl.have && ctx->nc.have;
     return TARDIS_MC_OK;
 }
 
 int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
 {
     if (!ctx || !p || !p->t_radiative || !p->dilution_factor) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid plasma update");
-    if (!ctx->have_opacity || !ctx->have_line_data || !ctx->have_plasma_data)
-        return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity, set_line_data and set_plasma_data must precede update_plasma");
-    if ((p->ionization_mode != 0 && p->ionization_mode != 1) || (p->excitation_mode != 0 && p->excitation_mode != 1))
-        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown ionization_mode %d / excitation_mode %d", p->ionization_mode, p->excitation_mode);
-    TardisMcOpacityUpdate u{};  // the opacity stages' view of this call: no host populations, the solved electron densities installed below
+    TardisMcOpacityUpdate u{};  // the opacity stages' view of this call: no host populations, the solved electron densities installed by plasma_update_install
     u.j_blues_mode = p->j_blues_mode;
     u.t_radiative = p->t_radiative; u.dilution_factor = p->dilution_factor;
     u.time_of_simulation = p->time_of_simulation; u.volume = p->volume; u.w_epsilon = p->w_epsilon;
     u.detailed_optical_window = p->detailed_optical_window;
     int rc;
-    if ((rc = opacity_update_check(ctx, &u))) return rc;
-    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou_levels, I = (size_t)ctx->pl_ions;
-    if ((long long)S > plup::MAX_SHELLS)
-        return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "update_plasma iterates the electron density inside one workgroup: at most %lld shells", plup::MAX_SHELLS);
-    if (p->ionization_mode == 0)
-        for (size_t s = 0; s < S; ++s)
-            if (!(p->t_radiative[s] >= ctx->pl_t_min && p->t_radiative[s] <= ctx->pl_t_max))
-                return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "t_radiative[%zu] = %g lies outside the zeta table [%g, %g]", s, p->t_radiative[s], ctx->pl_t_min,
-                            ctx->pl_t_max);
-    if (ctx->have_nlte && ctx->have_nc) {  // scipy's interp1d bounds error of the reference's get_collision_matrix
-        const long long s = nlte::first_t_e_outside(ctx->pl_link, (long long)S, p->t_radiative, ctx->nc_t_first, ctx->nc_t_last);
-        if (s >= 0)
-            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "t_electron of shell %lld = %g lies outside the collision temperatures [%g, %g]", s,
-                        ctx->pl_link * p->t_radiative[s], ctx->nc_t_first, ctx->nc_t_last);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->pl_long_rows_built != ctx->pl_long_rows) {  // which ions take the row form (plasma_update_plan.hpp)
-        const std::vector<int> &edge = ctx->pl_h_ion_edge;
-        std::vector<int> list;
-        for (size_t i = 0; i + 1 < edge.size(); ++i)
-            if (plup::choose_path((long long)edge[i + 1] - edge[i], ctx->pl_long_rows) == plup::PATH_ROW) list.push_back((int)i);
-        if ((rc = upload(ctx, ctx->pl_long_ions, list.data(), list.size()))) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->pl_n_long = (long long)list.size();
-        ctx->pl_long_rows_built = ctx->pl_long_rows;
-    }
-    if ((rc = opacity_update_buffers(ctx))) return rc;
-    const bool nlte = ctx->have_nlte;
-    // beta_sobolev of the previous update, read before this update's line kernel writes over it; none since the last set_opacity: 1.0
-    const double *nlte_beta = ctx->ou_valid && !ctx->nl_classical ? ctx->ou_beta_t.as<double>() : nullptr;
-    if (nlte && (rc = nlte_prepare(ctx))) return rc;
-    HIP_TRY(ctx, ctx->pl_lbf_t.ensure(K * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->pl_z.ensure(I * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->pl_phi.ensure(I * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->pl_n_ion.ensure(I * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->pl_n_e.ensure(S * sizeof(double)));
-    HIP_TRY(ctx, ctx->pl_status.ensure(2 * sizeof(int)));
-    // Z, N and n_e are rewritten from here on; the resident n_t, the electron densities and the opacity tables only once the iteration has succeeded
-    ctx->pl_valid = false;
-    ctx->nl_valid = ctx->nc_valid = false;
-    double *d_t = ctx->ou_shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
-    HIP_TRY(ctx, hipMemcpyAsync(d_t, p->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_w, p->dilution_factor, S * 8, hipMemcpyHostToDevice, ctx->stream));
-    ctx->nl_ran = ctx->nl_timed = false;
-    ctx->pl_timed = false;  // (ou_timed and the ev_ou events stay the previous update's until this solve has succeeded)
-    for (hipEvent_t &e : ctx->ev_ou)
-        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-    for (hipEvent_t &e : ctx->ev_pl)
-        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-    for (hipEvent_t &e : ctx->ev_nl)
-        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-    const double k_b = 1.3806488e-16, h = 6.62606957e-27, m_e = 9.10938291e-28;  // tardis/constants.py (CODATA 2010, cgs)
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[0], ctx->stream));
-    {
-        const unsigned bx = (unsigned)std::min<size_t>((K + 255) / 256, 1024);
-        auto kernel = p->excitation_mode == 0 ? mc::plasma_boltzmann_kernel<true> : mc::plasma_boltzmann_kernel<false>;
-        hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->pl_energy.as<double>(), ctx->pl_g.as<double>(), ctx->pl_meta.as<int>(), d_t,
-                           d_w, (long long)K, k_b, ctx->pl_lbf_t.as<double>());
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[1], ctx->stream));
-    if (nlte && (rc = nlte_stage(ctx, p, nlte_beta, d_t, d_w))) return rc;  // the NLTE species' Boltzmann factors, before anything reads them
-    {
-        const long long n_long = ctx->pl_n_long;
-        const long long long_levels = ctx->pl_long_rows < 0 ? plup::LONG_ION_LEVELS : ctx->pl_long_rows;
-        if (n_long < (long long)I) {
-            const long long n = (long long)I * (long long)S;
-            hipLaunchKernelGGL(mc::plasma_partition_lane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pl_ion_edge.as<int>(), (int)I,
-                               (long long)K, (int)S, long_levels, ctx->pl_lbf_t.as<double>(), ctx->pl_z.as<double>());
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        if (n_long > 0) {
-            const long long n = n_long * (long long)S * 16;
-            hipLaunchKernelGGL(mc::plasma_partition_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pl_long_ions.as<int>(), (int)n_long,
-                               ctx->pl_ion_edge.as<int>(), (long long)K, (int)S, ctx->pl_lbf_t.as<double>(), ctx->pl_z.as<double>());
-            HIP_TRY(ctx, hipGetLastError());
-        }
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[2], ctx->stream));
-    {
-        mc::PlasmaIonArgs a;
-        a.S = (int)S; a.I = (int)I; a.E = ctx->pl_elements; a.NT = ctx->pl_nt;
-        a.nebular = p->ionization_mode == 0;
-        a.max_iter = ctx->pl_max_iterations;
-        a.link = ctx->pl_link; a.chi_0 = ctx->pl_chi_0; a.k_b = k_b; a.two_pi_me = 2 * M_PI * m_e; a.hh = h * h;
-        a.element_edge = ctx->pl_elem_edge.as<int>(); a.charge = ctx->pl_charge.as<double>(); a.chi = ctx->pl_chi.as<double>();
-        a.zeta_t = ctx->pl_zeta_t.as<double>(); a.zeta = ctx->pl_zeta.as<double>(); a.density = ctx->pl_density.as<double>();
-        a.t_rad = d_t; a.w = d_w; a.z = ctx->pl_z.as<double>();
-        a.phi = ctx->pl_phi.as<double>(); a.n_ion = ctx->pl_n_ion.as<double>(); a.n_e = ctx->pl_n_e.as<double>(); a.status = ctx->pl_status.as<int>();
-        hipLaunchKernelGGL(mc::plasma_ionization_kernel, dim3(1), dim3((unsigned)((S + 63) / 64 * 64)), 0, ctx->stream, a);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[3], ctx->stream));
-    int status[2] = {mc::PLASMA_NAN, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(status, ctx->pl_status.p, sizeof status, hipMemcpyDeviceToHost, ctx->stream));
-    if (nlte) {  // the status words of the NLTE solves, read with {status, passes}
-        ctx->nl_h_status.assign((size_t)ctx->nl_species * S, -1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->nl_h_status.data(), ctx->nl_status.p, ctx->nl_h_status.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->pl_iterations = status[1];
-    long long nlte_failed = -1;
-    if (nlte)
-        for (size_t q = 0; q < ctx->nl_h_status.size() && nlte_failed < 0; ++q)
-            if (ctx->nl_h_status[q] != 0) nlte_failed = (long long)q;
-    if (status[0] != mc::PLASMA_OK || nlte_failed >= 0) {  // a failed solve: tardis_mc_last_propagate_ms reports its kernels, a matching pair of events
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->timed = true;
-        ctx->chunks_timed = 0;
-    }
-    if (nlte_failed >= 0) {  // (whatever the stages behind it made of the unfinished Boltzmann factors)
-        const long long sp = nlte_failed / (long long)S, shell = nlte_failed % (long long)S;
-        const int code = ctx->nl_h_status[(size_t)nlte_failed], n = ctx->nl_h_n[(size_t)sp];
-        if (code >= 1 && code <= n)
-            return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the NLTE solve of species %lld (ion %d, %d levels) in shell %lld met a zero or non-finite pivot in elimination "
-                        "step %d (singular rate matrix); the opacity state is unchanged", sp, ctx->nl_h_ion[(size_t)sp], n, shell, code - 1);
-        return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the NLTE solve of species %lld (ion %d, %d levels) in shell %lld gave %s after all %d elimination steps; the "
-                    "opacity state is unchanged", sp, ctx->nl_h_ion[(size_t)sp], n, shell, code == n + 1 ? "x[0] == 0" : "a population that is not finite", n);
-    }
-    if (status[0] == mc::PLASMA_NAN)
-        return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the electron density became NaN in pass %d (PlasmaIonizationError); the opacity state is unchanged", status[1] + 1);
-    if (status[0] != mc::PLASMA_OK)
-        return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the electron density has not converged after %d passes (option plasma_max_iterations); the opacity state is unchanged",
-                    status[1]);
-    ctx->sf_valid = false;
-    ctx->ou_valid = false;
-    ctx->ou_timed = false;
-    {
-        const unsigned bx = (unsigned)std::min<size_t>((K + 255) / 256, 1024);
-        hipLaunchKernelGGL(mc::plasma_population_kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->pl_lbf_t.as<double>(), ctx->pl_level_ion.as<int>(),
-                           ctx->pl_z.as<double>(), ctx->pl_n_ion.as<double>(), (long long)K, (int)S, ctx->ou_n_t.as<double>());
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, ctx->n_e.ensure(S * sizeof(double)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->n_e.p, ctx->pl_n_e.p, S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_pl[4], ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_ou[0], ctx->stream));
-    if ((rc = opacity_update_stages(ctx, &u))) return rc;
-    ctx->pl_timed = true;
-    ctx->pl_valid = true;
-    ctx->nl_ran = ctx->nl_valid = ctx->nl_timed = nlte;
-    ctx->nc_valid = nlte && ctx->have_nc;
-    return TARDIS_MC_OK;
+    if ((rc = plasma_update_check(ctx, p, &u))) return rc;
+    if ((rc = plasma_update_prepare(ctx))) return rc;
+    if ((rc = plasma_update_enqueue(ctx, p))) return rc;  // into the solve's own buffers
+    if ((rc = plasma_update_status(ctx))) return rc;      // a failed solve ends here: the opacity state has not been written
+    return plasma_update_install(ctx, &u);                // n_t, n_e and the opacity tables, only now
 }
 
 int tardis_mc_last_plasma_update_ms(TardisMcContext *ctx, double *out_boltzmann_ms, double *out_partition_ms, double *out_ionization_ms, double *out_population_ms)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->pl_timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_plasma has been timed yet");
+    if (!ctx->pl.timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_plasma has been timed yet");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev_pl[4]));
-    double *out[4] = {out_boltzmann_ms, out_partition_ms, out_ionization_ms, out_population_ms};
-    for (int k = 0; k < 4; ++k) {
-        float ms = 0.f;
-        // (the NLTE stage sits between the Boltzmann and the partition stage and has events of its own: tardis_mc_last_nlte_ms)
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, k == 1 && ctx->nl_ran ? ctx->ev_nl[2] : ctx->ev_pl[k], ctx->ev_pl[k + 1]));
-        if (out[k]) *out[k] = ms;
-    }
-    return TARDIS_MC_OK;
+    double *const out[4] = {out_boltzmann_ms, out_partition_ms, out_ionization_ms, out_population_ms};
+    hipEvent_t ev[5];
+    std::copy(ctx->pl.ev, ctx->pl.ev + 5, ev);
+    int rc = event_intervals_ms(ctx, ev, 1, out);
+    if (rc) return rc;
+    // (the NLTE stage sits between the Boltzmann and the partition stage and has events of its own: tardis_mc_last_nlte_ms)
+    if (ctx->nl.ran) ev[1] = ctx->nl.ev[2];
+    return event_intervals_ms(ctx, ev + 1, 3, out + 1);
 }
 
 int tardis_mc_get_plasma(TardisMcContext *ctx, double *level_number_density, double *ion_number_density, double *partition_function, double *electron_density,
                          int32_t *iterations)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->pl_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "get_plasma needs an update_plasma since the last set_opacity / update_opacity");
+    if (!ctx->pl.valid) return fail(ctx, TARDIS_MC_ERR_STATE, "get_plasma needs an update_plasma since the last set_opacity / update_opacity");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou_levels, I = (size_t)ctx->pl_ions;
-    if (level_number_density) {  // [S][K] -> [K,S]
-        HIP_TRY(ctx, ctx->staging.ensure(K * S * sizeof(double)));
-        HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->ou_n_t.as<double>(), ctx->staging.as<double>(), (long long)S, (long long)K));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, host_copy(ctx, {{(void *)level_number_density, ctx->staging.p, K * S * sizeof(double)}}, false));
-    }
+    const size_t S = (size_t)ctx->n_shells, I = (size_t)ctx->pl.ions;
+    int rc;
+    if ((rc = download_transposed(ctx, level_number_density, ctx->ou.n_t.as<double>(), (size_t)ctx->ou.levels))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, host_copy(ctx, {{(void *)ion_number_density, ctx->pl_n_ion.p, I * S * sizeof(double)},
-                                 {(void *)partition_function, ctx->pl_z.p, I * S * sizeof(double)},
-                                 {(void *)electron_density, ctx->pl_n_e.p, S * sizeof(double)}}, false));
-    if (iterations) *iterations = ctx->pl_iterations;
+    HIP_TRY(ctx, host_copy(ctx, {{(void *)ion_number_density, ctx->pl.n_ion.p, I * S * sizeof(double)},
+                                 {(void *)partition_function, ctx->pl.z.p, I * S * sizeof(double)},
+                                 {(void *)electron_density, ctx->pl.n_e.p, S * sizeof(double)}}, false));
+    if (iterations) *iterations = ctx->pl.iterations;
     return TARDIS_MC_OK;
 }
 

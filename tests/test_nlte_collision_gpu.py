@@ -315,6 +315,43 @@ def test_removal_and_what_drops_the_data(models):
         assert eng.nlte_collision_data is None
 
 
+OK, STATE = 0, _abi.ERR_STATE
+# what one call leaves of a complete chain: get_opacity(beta_sobolev) | get_plasma | get_nlte | get_nlte_collision_rates
+LADDER = [
+    ("set_nlte_collision_data", lambda eng, m, pop: eng.set_nlte_collision_data(m.cd), (OK, OK, OK, STATE)),
+    ("set_nlte_data", lambda eng, m, pop: eng.set_nlte_data(m.nd), (OK, OK, STATE, STATE)),
+    ("set_plasma_data", lambda eng, m, pop: eng.set_plasma_data(m.pd), (OK, STATE, STATE, STATE)),
+    ("set_line_data", lambda eng, m, pop: eng.set_line_data(m.ld), (STATE, STATE, STATE, STATE)),
+    ("set_opacity", lambda eng, m, pop: eng.set_opacity(m.prob.opacity_state), (STATE, STATE, STATE, STATE)),
+    ("update_opacity", lambda eng, m, pop: eng.update_opacity(pop, t_radiative=m.t_rad, dilution_factor=m.w), (OK, STATE, STATE, STATE)),
+]
+
+
+def _code(call):
+    try:
+        call()
+    except RuntimeError as e:
+        return e.code
+    return OK
+
+
+@pytest.mark.parametrize("name,call,expect", LADDER, ids=[row[0] for row in LADDER])
+def test_the_ladder_what_each_call_invalidates(engine, models, name, call, expect):
+    """opacity -> line data -> plasma data -> NLTE data -> collision data: a call that replaces one rung drops the results that sit on
+    it and on every rung below it, and nothing above (update_opacity: the populations are the caller's from then on)."""
+    m = models["four"]
+    stage(engine, m)
+    engine.update_plasma(m.t_rad, m.w)
+    populations = engine.get_plasma()["level_number_density"]
+    getters = (lambda: engine.get_opacity(tau_sobolev=False, transition_probabilities=False, beta_sobolev=True), engine.get_plasma, engine.get_nlte,
+               engine.get_nlte_collision_rates)
+    assert tuple(_code(g) for g in getters) == (OK, OK, OK, OK)
+    call(engine, m, populations)
+    assert tuple(_code(g) for g in getters) == expect
+    if name == "set_opacity":
+        assert engine.get_opacity(transition_probabilities=False)["tau_sobolev"].shape == (engine.n_lines, engine.n_shells)
+
+
 def test_the_resident_solver_over_two_iterations(models):
     """run -> update_plasma -> run -> update_plasma with NLTE and collision data installed on the solver, against the restatement fed by
     hand: the first update on beta of ones and the opacity state's n_e, the second on the first's beta and solved n_e."""
