@@ -65,12 +65,41 @@ struct DevBuf {
     void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
     template <typename T> T *as() const { return static_cast<T *>(p); }
 };
-// what the release() of a stage's state (TardisMcContext::ou / pl / nl / nc) is made of
-template <typename... Bufs> void release_buffers(Bufs &...bufs) { (bufs.release(), ...); }
+// Function-local device scratch: a DevBuf that is freed when the function returns, on every path.  (The context's own buffers stay plain DevBufs
+// with an explicit release(): tardis_mc_destroy has to select the device first.)
+struct ScopedDevBuf : DevBuf {
+    ScopedDevBuf() = default;
+    ScopedDevBuf(const ScopedDevBuf &) = delete;
+    ScopedDevBuf &operator=(const ScopedDevBuf &) = delete;
+    ~ScopedDevBuf() { release(); }
+};
+// what the release() of a struct of the context is made of: each frees what it is given and nulls it
+void release_buffer(DevBuf &b) { b.release(); }
+template <size_t N> void release_buffer(DevBuf (&bufs)[N])
+{
+    for (DevBuf &b : bufs) b.release();
+}
+template <typename... Bufs> void release_buffers(Bufs &...bufs) { (release_buffer(bufs), ...); }
+void destroy_event(hipEvent_t &e)
+{
+    if (e) { (void)hipEventDestroy(e); e = nullptr; }
+}
 template <size_t N> void destroy_events(hipEvent_t (&ev)[N])
 {
-    for (hipEvent_t &e : ev)
-        if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    for (hipEvent_t &e : ev) destroy_event(e);
+}
+void destroy_events(std::vector<hipEvent_t> &ev)
+{
+    for (hipEvent_t &e : ev) destroy_event(e);
+    ev.clear();
+}
+void destroy_stream(hipStream_t &s)
+{
+    if (s) { (void)hipStreamDestroy(s); s = nullptr; }
+}
+template <typename T> void free_pinned(T *&p)
+{
+    if (p) { (void)hipHostFree(p); p = nullptr; }
 }
 
 // ---- RCCL, bound lazily
@@ -108,6 +137,8 @@ bool load_rccl(std::string &err)
 
 }  // namespace
 
+// The context: what several stages share at the top level, then one struct per stage -- its resources, the options that steer it, its flags, and a
+// release() that names every resource of the struct.  A resource lives in exactly one struct; tardis_mc_destroy calls the release() of each.
 struct TardisMcContext {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -117,186 +148,230 @@ struct TardisMcContext {
     bool timed = false;
     std::string err;
     hipDeviceProp_t prop{};
+    double last_post_ms = 0.0;  // estimator passes (binning + accumulation) of the last propagate call
+    double sum_seed_ms = 0.0, sum_prop_ms = 0.0, sum_post_ms = 0.0;
+    int launches = 0;
     // state flags
     bool have_geometry = false, have_opacity = false, have_config = false, have_packets = false;
     // geometry
     int n_shells = 0;
     double t_exp = 0;
     DevBuf r_inner, r_outer;
-    // opacity
+    // problem shape of the resident opacity tables
     int n_lines = 0, n_trans = 0, n_levels = 0;
-    DevBuf nu_line, tau_t, n_e, prob_t, cum_t, trans_nu, line2level, block_edge, ttype, dest, tline, staging, line_block, trans_rec, bucket_first;
-    DevBuf cum16, rec16, quad_info, line_block_c;  // compact walk tables (walk_tables.hpp)
-    DevBuf hot_sec, hot_mass, hot_flag, blk_tab;   // hot sectors of the macro-atom walk (walk_tables.hpp)
-    bool have_hot = false;
-    long long n_hot_blocks = 0;                    // blocks entered through a hot sector (diagnostic)
-    int walk_hot = -1;                             // -1: blocks whose six widest intervals cover enough (walk_hot_min_mass); 0: none; 1: every block
-    // per mille of a block's probability, mean over the shells; blocks of <= 32 / more rows.  Measured (profiles/r04_walk_hot_sectors.txt):
-    // heavy-tailed blocks -11 % whatever the thresholds (95 % of their jumps are decided by the sector); blocks of 12-24 rows with
-    // uniformly drawn probabilities (six intervals cover ~50-70 %) lose 2.5 % at 600 -- a missed probe costs a round of the walk
-    int walk_hot_min_mass = 800, walk_hot_min_mass_long = 400;
-    DevBuf tau_pfx, tau_rowsum, pfx_flag;          // v-packet screening tables (tau_prefix.hpp), built at the first SCREENING call after set_opacity (+ their negative-depth flag)
-    bool pfx_valid = false, pfx_negative = false;
-    unsigned cum16_stride = 0;
-    bool have_walk_tables = false;
-    int bucket_shift = 0, bucket_n = 0;
-    long long vpk_wave_min_packets = 100000;  // option: calls with v-packets on fine grids take the wave kernel from this many packets on (the group kernel below)
-    // Two instantiations of the lane-sweep kernel: 128 VGPRs / sixteen waves per CU / eight lines per step (A), and 166 VGPRs / twelve waves per CU /
-    // twelve lines per step (B).  A wins where the steady state dominates (1e8 packets of the configs[2] shape: B +3.8 %), B where the drain of a
-    // call's longest packets does (1.25e7 packets: -11 %; 1e5-1e6 packets of the tardis_example shape: -6 %; profiles/r05_ls_instantiations.txt):
-    // fewer steps per trace shorten the serial chain of a lone packet, and a mostly idle chip does not miss the four waves.  Option
-    // ls_waves_per_simd: 4 = A, 3 = B, 0 (default) = the engine times both on the first calls of a given (packet count, tables) and keeps the
-    // faster one -- a Monte Carlo iteration repeats the same call; per-packet results are bit-identical either way.
-    int ls_waves_per_simd = 0;
-    // Interleaved sweep table (round 6): nt_t[shell][line] = {nu_line, tau}, 16 bytes per line, rows on 128-byte boundaries -- the eight 16-byte loads of
-    // a lane-sweep step come from one run of 128 bytes instead of two runs of 64 bytes in two tables.  Option sweep_table: 0 the separate tables,
-    // 1 runs from the current line, 2 aligned runs (propagate_wave_kernel<..., NT>); built by the first propagate call after set_opacity that uses it.
-    // -1 (default) = 1 -- measured (profiles/r06_sweep_table.txt): sixteen-wave instantiation, 1e8 packets of configs[2] -1.0 ... -1.5 %, 2e7 -4 %, 1.25e7 -6 %,
-    // uniform levels -4.5 ... -6 %, configs[1] -1 ... -3 %; twelve-wave instantiation (with the lean proof) -1.7 ... -4.6 %; aligned runs (2) +2 ... +6 % on the
-    // heavy-tailed tables (a trace's first step is shorter: 8 % more steps), -5 % on the uniform ones.
-    int sweep_table = -1;
-    // Shell-sorted log (round 6; propagate_wave_kernel<..., SL>): every chunk of the line-visit log holds records of one shell, the estimator passes start with
-    // the partition by bin.  1 / -1: where the kernel has it (the production lane-sweep instantiations, <= 64 shells, partition pipeline); 0 (default) off.
-    // Measured (profiles/r06_shell_sorted_log.txt): the passes of an epoch of 2e9 records 86.5 -> 64.2 ms as priced -- and the propagation launches +4.3 %
-    // (2773 -> 2891-2904 ms per 1e8 packets) whether the slots come from ballot ranks (+3 % instructions) or from one LDS atomic (+1.5 %): net +0.6 ... +1.3 % on
-    // the headline, -2 ... -3 % only where a call's passes are not overlapped by anything (2e7 packets with log_sets 1; configs[1])
-    int log_by_shell = 0;
-    // Split launches (round 6): from the second epoch of a call on, the propagation grid is launched as TWO kernels -- the first half of the waves at once, on the
-    // engine's stream; the second half on the passes' stream, behind the estimator passes of the previous epoch.  While those passes run, the chip holds eight
-    // propagation waves per CU instead of none (the passes' 1024-thread workgroups need half a CU: they cannot be placed beside sixteen resident waves, and used to
-    // run alone at every epoch boundary: 0.37 s of a 3.1-s step); when they are over the second half follows.  Nothing in the kernel changes: the second launch
-    // gets a WaveCold whose per-wave pointers (MT19937 states, suspended lanes / waves, v-packet scratch) are offset by the first launch's wave count.
-    // MEASURED, and a clear loss (profiles/r06_split_launch.txt): parity-green, but configs[2] at 1e8 packets 3 109 -> 4 107 ms -- the passes beside eight resident
-    // waves per CU take three times as long as alone (their workgroups need 72 KB of CONTIGUOUS LDS and find it on few CUs), the second half of the grid idles
-    // meanwhile.  Option epoch_split, default 0.
-    int epoch_split = 0;
-    hipEvent_t ev_split[3] = {nullptr, nullptr, nullptr};  // the first launch's inputs are in place | start / end of the second launch
-    DevBuf nt_t;
-    bool nt_valid = false, nt_negative = false;  // (nt_negative: the table holds a negative / NaN optical depth -- the lean proof of the NT kernels does not apply)
-    unsigned nt_stride = 0;
-    // (the tuner: calls 0-4 of a key run A untimed, A, B, A, B -- each timed call with the tuner's OWN event pair, recorded only when the call was
-    // enqueued completely, so that neither another entry point's use of ev_start / ev_stop nor a failed call can leave a stale or unpaired
-    // measurement behind -- and from call 5 on B only if the faster of its two calls beat the faster of A's by >= 3 %: boxes differ by more
-    // than one noisy sample can tell apart)
-    struct { long long n = -1; int lines = 0, shells = 0, mode = 0, table = 0, wide = 0, phase = 0, pending = -1, choice = 0; double ms[2][2] = {{-1.0, -1.0}, {-1.0, -1.0}}; } ls_tune;
-    hipEvent_t ev_tune[2] = {nullptr, nullptr};
-    int vpk_wide_registers = 1;       // option: the two-waves-per-SIMD v-packet instantiation where LDS bounds the occupancy at eight waves per CU anyway
-    int bucket_lines_permille = 750;  // option: target lines per bucket x 1000 (takes effect in set_opacity)
-    long long bucket_kmin = 0;
-    bool lines_sorted = true;  // line_list_nu strictly usable by the index-based kernels (non-increasing, positive)
-    // estimators: one allocation [J | nubar | vhist | pad | jblue copy0 | edot copy0 | jblue copy1.. | edot copy1..]
-    DevBuf est;
-    size_t est_S = 0, est_L = 0, est_G = 0;
-    int est_copies = 1;
-    bool est_valid = false;
-    bool est_propagated = false;  // a propagate call has added to the estimators since they were last zeroed (the detailed mode of tardis_mc_update_opacity)
     // config
     TardisMcConfig cfg{};
     std::vector<double> grid_host;
     DevBuf grid;
-    // packets
-    long long n_packets = 0;
-    DevBuf r0, mu0, nu0, e0, seeds, out_nu, out_e;
-    DevBuf li_f64[9], li_i64[5], li_rec;  // (li_rec: the wave kernel's 64-byte tracker records, unpacked into the arrays after the propagation)
-    bool track = true;
-    bool li_valid = false;  // the last-interaction arrays are those of the last propagate call's packets (tardis_mc_packet_decomposition)
-    DevBuf dc_work;         // tardis_mc_packet_decomposition: the class table and the outputs of a call
-    // v-packet log
-    DevBuf vlog_count, vlog_packet, vlog_seq, vlog_nu, vlog_energy, vlog_mu, vlog_r;
-    long long vlog_capacity = 0;
-    bool vlog_capacity_user = false;  // set through the vpacket_log_capacity option (otherwise sized per propagate call)
-    // option vpacket_last_interaction: 24 B more per entry, behind vlog_r in its allocation (mc_device.hpp); the log consolidated on the device (vpacket_log.hpp): the per-packet
-    // counts, their offsets, the scan's tile sums, the packet-ordered columns (five, or eleven with the last interaction), the error word
-    bool vlog_li = false;
-    DevBuf vl_counts, vl_offsets, vl_tiles, vl_cols, vl_errors;
-    bool vl_valid = false;         // the last propagate call wrote a v-packet log and nothing has replaced its packets or its configuration since
-    bool vl_li = false;            // ... with the last-interaction columns
-    bool vl_consolidated = false;  // vl_cols holds that log
-    long long vl_packets = 0, vl_capacity = 0, vl_count = 0;  // packets and device capacity of that call; entries it produced (once consolidated)
-    // full r-packet tracking (option track_full, event_log.hpp): runs on the wave kernel (variant 2) where that can run the call, else on the lane kernel; the row pool, its chunk fills, {pool_next, dropped},
-    // the per-packet counts, and for tardis_mc_get_event_log the offsets, the tile sums of their scan and the packet-major columns
-    bool track_full = false;
-    long long evlog_capacity = 0;                    // option event_log_capacity: rows (0: automatic, 32 per packet)
-    long long evlog_max_bytes = 16LL << 30;          // option event_log_max_bytes: the bound on the log's device memory
-    DevBuf ev_rows, ev_fill, ev_state, ev_counts, ev_offsets, ev_tiles, ev_cols;
-    bool ev_valid = false;                           // the last propagate call wrote an event log
-    long long ev_packets = 0, ev_capacity = 0, ev_slots = 0;
-    unsigned ev_chunk_rows = 128, ev_n_chunks = 0;
     // scratch
-    DevBuf rng_state, counters, first_error, next_packet, seeded_states, problem_dev;
+    DevBuf staging, rng_state, counters, first_error, next_packet, problem_dev;
     mc::DeviceProblem problem_host{};
     long long chunk_packets = 16LL << 20;  // packets per seeded-state chunk (2496 B each) of the cooperative kernel
     // launch geometry
     int variant = -1;  // 0: lane-per-packet kernel; 1: group-per-packet kernel; 2: wave-owner kernel, group sweeps; 3: wave-owner kernel, lane sweeps; 4: wave-owner kernel with the volley queue; -1: automatic
-    bool prob_negative = false;  // a negative transition probability: the running sums are not monotone, no jump search
-    bool walk_min_active_user = false, ls_min_active_user = false;  // (set through the options: no automatic choice then)
-    int walk_min_active = 8;  // compact macro-atom walk: carry the longest chains over to the next pass once this few lanes still walk (-1: never)
-    int ls_min_active = 8, ls_max_steps = 1 << 30;  // lane sweeps: when to leave the sweep phase (propagate_wave.hpp)
     int blocks_per_cu = 16;
     int debug_flags = 0;
-    int drain_split = 0;          // wave kernel: split the drain of a call off into a launch of its own (WaveCold::drain_split); measured: -4 % at 1e7 packets, +1.3 % at 1e8 -> off
-    int walk_sector_packing = 1;  // compact walk tables: short blocks do not straddle 64-byte sectors (set before set_opacity; 0: packed at 16 bytes as in round 2)
-    int vpacket_screening = -1;  // v-packet screening on the prefix sums of tau (tau_prefix.hpp): -1 automatic, 0 off, 1 on
     int group_size = 0;  // 0: automatic (8 or 16 lanes per packet)
-    int log_tail_packets = 8;               // tail split: packets' worth of traces a lane in flight still logs after the supply has run out
-    int log_tail_split = 1;                 // plan the epochs so that the last one holds only the drain of the call (see tardis_mc_propagate)
-    int est_accumulate = 3;                 // accumulate kernel: 3 dyadic hierarchy of block sums, a lane per record (accumulate_dyadic_kernel<.., LOOP>), 2 the same with the blocks of 64 records spread over the lanes, 1 8-line block sums (accumulate_blocks_kernel), 0 one add per line visit (accumulate_kernel, index pipeline only)
-    int est_pipeline = 1;                   // line-estimator passes: 1 two-level partition of the records (estimator_partition.hpp), 0 index sort + gather (estimator_log.hpp)
-    DevBuf log_part;                        // est_pipeline 1: the scratch copy of one epoch's records, shared by both buffer sets
-    long long log_chunk_records = 0;        // records per chunk of the line-visit log's pool (0: automatic, <= 4096; tests)
-    long long log_capacity = 2500000000LL;  // upper bound of the line-visit records per epoch and buffer set of the wave kernel (24 B + 4 B + 4 B each)
-    bool log_capacity_user = false;         // set through the log_capacity option (otherwise also bounded by the free device memory)
-    // wave kernel: chunks alternate between two buffer sets / streams, so that seeding and the estimator passes of one
-    // chunk overlap the propagation of its neighbours
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_join = nullptr;
-    // tardis_mc_progress (another host thread polls while propagate blocks): the running call's packet count, whether its kernel hands
-    // packets out through next_packet over the whole call (wave kernel), whether it is complete; a stream and a pinned word of its own
-    std::atomic<long long> progress_total{0};
-    std::atomic<bool> progress_wave{false}, progress_done{true};
-    std::mutex progress_mutex;
-    hipStream_t stream_progress = nullptr;
-    hipEvent_t ev_progress_reset = nullptr;  // recorded behind the reset of next_packet at the start of a call
-    unsigned long long *progress_host = nullptr;
-    // CU partition (option pass_cus: CUs per XCD set aside for the estimator passes, 0 = off): the propagation launches of a call of several
-    // epochs run on a stream whose queue is masked to the other CUs, the passes of epoch k beside epoch k + 1 on a stream masked to these
-    int pass_cus = 0, pass_cus_built = 0;
-    hipStream_t stream_prop_m = nullptr, stream_pass_m = nullptr;
-    hipEvent_t ev_fork_m = nullptr, ev_join_m = nullptr;
-    DevBuf log_records[2], log_keys[2], log_cursor[2], log_bins[2], log_sorted[2], wave_cold_dev;
-    DevBuf seed_chk, vp_scratch;       // wave kernel: the launch records of a call's packets | the v-packet results handed from worker to owner lanes
-    DevBuf vp_park;                     // pooled volleys with carry-over: one parked v-packet per lane
-    int vp_carry_min_active = 16;       // pooled volleys: leave the volley phase once nothing waits and this few lanes still trace (0: never).  16: -7 % on the
-                                        // configs[4] shape, -5 % on the tardis_example shape + 10 v-packets, flat from 16 to 32 (profiles/r05_volley_carry.txt)
-    // wave kernel: word 397 of every packet's init_genrand sequence (lazy MT19937 seeding)
-    double last_post_ms = 0.0;  // estimator passes (binning + accumulation) of the last propagate call
-    double traces_per_packet = 0.0;  // measured by the last propagate (sizes the line-visit log of the next one)
-    double log_budget_per_packet = 128.0;  // log records reserved per packet
-    unsigned long long *events_host = nullptr;  // pinned: {events counter of the last propagate, its packet count}
-    hipEvent_t ev_events = nullptr;
-    std::vector<mc::WaveCold> wave_cold_host;
-    // wave kernel: a propagate call is a sequence of epochs over one packet supply (LaneSave, propagate_wave.hpp)
-    DevBuf lane_save, wave_save, suspended_dev;
-    // drain compaction (option drain_compact = T: waves suspend once the supply has run out and T or fewer of their lanes are left; the live lanes are packed into
-    // full waves and the rest of the call is a launch of fewer waves, beside the estimator passes): the packed grid's buffers, two sets for repeated packing
-    int drain_compact = 0;
-    int drain_pack_lanes = 64;  // live lanes per packed wave
-    int est_one_level = 1;      // the passes' partition in one pass where the (shell, tile) bins are few enough to be ranked in LDS at once (0: always two levels)
-    DevBuf lane_save_c[2], wave_save_c[2], seeded_states_c[2], drain_census;
-    int compactions = 0;  // of the last propagate call
-    DevBuf vq_req, vq_items, vq_count, vq_jsave;  // volley queue (variant 4, propagate_wave.hpp: VolleyRequest)
-    long long vq_min_items = -1;  // switch the queue off for the rest of a call once a launch requests fewer v-packets (-1: automatic)
-    int vq_min_active = 8, vq_oversubscribe = 4, vq_tracer_waves_per_simd = 6;
-    unsigned *suspended_host = nullptr;  // pinned
-    hipEvent_t ev_post[4] = {nullptr, nullptr, nullptr, nullptr};  // start / end of the estimator passes on log buffer set 0 / 1
-    bool wave_epoch_mode = false, post_pending[2] = {false, false}, prop_pending = false;
-    double sum_seed_ms = 0.0, sum_prop_ms = 0.0, sum_post_ms = 0.0;
-    int launches = 0;
-    int log_sets = 0;  // 2: the estimator passes of an epoch run beside the next launch (two log sets); 1: before it (one set); 0: 1 for calls of several epochs, 2 otherwise
+    long long vpk_wave_min_packets = 100000;  // option: calls with v-packets on fine grids take the wave kernel from this many packets on (the group kernel below)
+    int vpk_wide_registers = 1;       // option: the two-waves-per-SIMD v-packet instantiation where LDS bounds the occupancy at eight waves per CU anyway
     int last_variant = -1;  // kernel of the last propagate call (see tardis_mc_last_variant)
     int table_offsets = -1;       // option: row offsets of the cooperative kernels, -1 64-bit where S x L or S x T reaches 2^28, 0 always 32-bit, 1 always 64-bit
     int last_table_offsets = -1;  // 32 / 64: row offsets of the last propagate call's kernel (see tardis_mc_last_table_offsets)
     int waves_per_simd = 4;  // register budget hint of the cooperative kernel (2: 256 VGPRs, 3: 168, 4: 128)
+    void release()  // (the last of tardis_mc_destroy: the stages' buffers and events go before the stream they were used on)
+    {
+        release_buffers(r_inner, r_outer, grid, staging, rng_state, counters, first_error, next_packet, problem_dev);
+        destroy_event(ev_start); destroy_event(ev_stop); destroy_events(ev_chunk);
+        destroy_stream(stream);
+    }
+    // Opacity tables: what set_opacity uploads, re-laid shell-major, with the bucket index of the line list.  Per set_opacity: host copies of the five index
+    // tables (line2macro_level_upper, macro_block_edge_index, transition_type, destination_level_id, transition_line_id; int32, the staging vectors of their
+    // upload) and of the line list, from which derive_opacity_tables builds every table that depends on the probabilities, with or without the caller's pointers.
+    struct OpacityTables {
+        DevBuf nu_line, tau_t, n_e, prob_t, cum_t, trans_nu, line2level, block_edge, ttype, dest, tline, line_block, trans_rec, bucket_first;
+        int bucket_shift = 0, bucket_n = 0;
+        int bucket_lines_permille = 750;  // option: target lines per bucket x 1000 (takes effect in set_opacity)
+        long long bucket_kmin = 0;
+        bool lines_sorted = true;  // line_list_nu strictly usable by the index-based kernels (non-increasing, positive)
+        bool prob_negative = false;  // a negative transition probability: the running sums are not monotone, no jump search
+        std::vector<int> h_idx[5];
+        std::vector<double> h_nu;
+        bool h_macro = false;
+        void release() { release_buffers(nu_line, tau_t, n_e, prob_t, cum_t, trans_nu, line2level, block_edge, ttype, dest, tline, line_block, trans_rec, bucket_first); }
+    } ot;
+    // Walk tables of the macro-atom walk (walk_tables.hpp), derived from the probabilities by derive_opacity_tables
+    struct WalkTables {
+        DevBuf cum16, rec16, quad_info, line_block_c;  // compact walk tables (walk_tables.hpp)
+        DevBuf hot_sec, hot_mass, hot_flag, blk_tab;   // hot sectors of the macro-atom walk (walk_tables.hpp)
+        bool have_hot = false;
+        long long n_hot_blocks = 0;                    // blocks entered through a hot sector (diagnostic)
+        int walk_hot = -1;                             // -1: blocks whose six widest intervals cover enough (walk_hot_min_mass); 0: none; 1: every block
+        // per mille of a block's probability, mean over the shells; blocks of <= 32 / more rows.  Measured (profiles/r04_walk_hot_sectors.txt):
+        // heavy-tailed blocks -11 % whatever the thresholds (95 % of their jumps are decided by the sector); blocks of 12-24 rows with
+        // uniformly drawn probabilities (six intervals cover ~50-70 %) lose 2.5 % at 600 -- a missed probe costs a round of the walk
+        int walk_hot_min_mass = 800, walk_hot_min_mass_long = 400;
+        unsigned cum16_stride = 0;
+        bool have_walk_tables = false;
+        int walk_sector_packing = 1;  // compact walk tables: short blocks do not straddle 64-byte sectors (set before set_opacity; 0: packed at 16 bytes as in round 2)
+        void release() { release_buffers(cum16, rec16, quad_info, line_block_c, hot_sec, hot_mass, hot_flag, blk_tab); }
+    } wt;
+    struct ScreeningTables {
+        DevBuf tau_pfx, tau_rowsum, pfx_flag;          // v-packet screening tables (tau_prefix.hpp), built at the first SCREENING call after set_opacity (+ their negative-depth flag)
+        bool pfx_valid = false, pfx_negative = false;
+        int vpacket_screening = -1;  // v-packet screening on the prefix sums of tau (tau_prefix.hpp): -1 automatic, 0 off, 1 on
+        void release() { release_buffers(tau_pfx, tau_rowsum, pfx_flag); }
+    } sc;
+    struct SweepTable {
+        // Interleaved sweep table (round 6): nt_t[shell][line] = {nu_line, tau}, 16 bytes per line, rows on 128-byte boundaries -- the eight 16-byte loads of
+        // a lane-sweep step come from one run of 128 bytes instead of two runs of 64 bytes in two tables.  Option sweep_table: 0 the separate tables,
+        // 1 runs from the current line, 2 aligned runs (propagate_wave_kernel<..., NT>); built by the first propagate call after set_opacity that uses it.
+        // -1 (default) = 1 -- measured (profiles/r06_sweep_table.txt): sixteen-wave instantiation, 1e8 packets of configs[2] -1.0 ... -1.5 %, 2e7 -4 %, 1.25e7 -6 %,
+        // uniform levels -4.5 ... -6 %, configs[1] -1 ... -3 %; twelve-wave instantiation (with the lean proof) -1.7 ... -4.6 %; aligned runs (2) +2 ... +6 % on the
+        // heavy-tailed tables (a trace's first step is shorter: 8 % more steps), -5 % on the uniform ones.
+        int sweep_table = -1;
+        DevBuf nt_t;
+        bool nt_valid = false, nt_negative = false;  // (nt_negative: the table holds a negative / NaN optical depth -- the lean proof of the NT kernels does not apply)
+        unsigned nt_stride = 0;
+        void release() { release_buffers(nt_t); }
+    } sw;
+    struct Estimators {
+        // estimators: one allocation [J | nubar | vhist | pad | jblue copy0 | edot copy0 | jblue copy1.. | edot copy1..]
+        DevBuf est;
+        size_t est_S = 0, est_L = 0, est_G = 0;
+        int est_copies = 1;
+        bool est_valid = false;
+        bool est_propagated = false;  // a propagate call has added to the estimators since they were last zeroed (the detailed mode of tardis_mc_update_opacity)
+        void release() { release_buffers(est); }
+    } es;
+    // packets and the per-packet results
+    struct Packets {
+        long long n_packets = 0;
+        DevBuf r0, mu0, nu0, e0, seeds, out_nu, out_e;
+        DevBuf li_f64[9], li_i64[5], li_rec;  // (li_rec: the wave kernel's 64-byte tracker records, unpacked into the arrays after the propagation)
+        bool track = true;
+        bool li_valid = false;  // the last-interaction arrays are those of the last propagate call's packets (tardis_mc_packet_decomposition)
+        DevBuf dc_work;         // tardis_mc_packet_decomposition: the class table and the outputs of a call
+        void release() { release_buffers(r0, mu0, nu0, e0, seeds, out_nu, out_e, li_f64, li_i64, li_rec, dc_work); }
+    } pk;
+    struct VpacketLog {
+        DevBuf vlog_count, vlog_packet, vlog_seq, vlog_nu, vlog_energy, vlog_mu, vlog_r;
+        long long vlog_capacity = 0;
+        bool vlog_capacity_user = false;  // set through the vpacket_log_capacity option (otherwise sized per propagate call)
+        // option vpacket_last_interaction: 24 B more per entry, behind vlog_r in its allocation (mc_device.hpp); the log consolidated on the device (vpacket_log.hpp): the per-packet
+        // counts, their offsets, the scan's tile sums, the packet-ordered columns (five, or eleven with the last interaction), the error word
+        bool vlog_li = false;
+        DevBuf vl_counts, vl_offsets, vl_tiles, vl_cols, vl_errors;
+        bool vl_valid = false;         // the last propagate call wrote a v-packet log and nothing has replaced its packets or its configuration since
+        bool vl_li = false;            // ... with the last-interaction columns
+        bool vl_consolidated = false;  // vl_cols holds that log
+        long long vl_packets = 0, vl_capacity = 0, vl_count = 0;  // packets and device capacity of that call; entries it produced (once consolidated)
+        void release() { release_buffers(vlog_count, vlog_packet, vlog_seq, vlog_nu, vlog_energy, vlog_mu, vlog_r, vl_counts, vl_offsets, vl_tiles, vl_cols, vl_errors); }
+    } vl;
+    struct EventLog {
+        // full r-packet tracking (option track_full, event_log.hpp): runs on the wave kernel (variant 2) where that can run the call, else on the lane kernel; the row pool, its chunk fills, {pool_next, dropped},
+        // the per-packet counts, and for tardis_mc_get_event_log the offsets, the tile sums of their scan and the packet-major columns
+        bool track_full = false;
+        long long evlog_capacity = 0;                    // option event_log_capacity: rows (0: automatic, 32 per packet)
+        long long evlog_max_bytes = 16LL << 30;          // option event_log_max_bytes: the bound on the log's device memory
+        DevBuf ev_rows, ev_fill, ev_state, ev_counts, ev_offsets, ev_tiles, ev_cols;
+        bool ev_valid = false;                           // the last propagate call wrote an event log
+        long long ev_packets = 0, ev_capacity = 0, ev_slots = 0;
+        unsigned ev_chunk_rows = 128, ev_n_chunks = 0;
+        void release() { release_buffers(ev_rows, ev_fill, ev_state, ev_counts, ev_offsets, ev_tiles, ev_cols); }
+    } el;
+    // What a call of the wave kernel runs on: the line-visit log sets, the epochs' saved lanes and waves, the compaction sets, the volley queue, the
+    // second and the masked streams with their events, and the options that size or steer them
+    struct WaveResources {
+        bool walk_min_active_user = false, ls_min_active_user = false;  // (set through the options: no automatic choice then)
+        int walk_min_active = 8;  // compact macro-atom walk: carry the longest chains over to the next pass once this few lanes still walk (-1: never)
+        int ls_min_active = 8, ls_max_steps = 1 << 30;  // lane sweeps: when to leave the sweep phase (propagate_wave.hpp)
+        int drain_split = 0;          // wave kernel: split the drain of a call off into a launch of its own (WaveCold::drain_split); measured: -4 % at 1e7 packets, +1.3 % at 1e8 -> off
+        int log_tail_packets = 8;               // tail split: packets' worth of traces a lane in flight still logs after the supply has run out
+        int log_tail_split = 1;                 // plan the epochs so that the last one holds only the drain of the call (see tardis_mc_propagate)
+        int est_accumulate = 3;                 // accumulate kernel: 3 dyadic hierarchy of block sums, a lane per record (accumulate_dyadic_kernel<.., LOOP>), 2 the same with the blocks of 64 records spread over the lanes, 1 8-line block sums (accumulate_blocks_kernel), 0 one add per line visit (accumulate_kernel, index pipeline only)
+        int est_pipeline = 1;                   // line-estimator passes: 1 two-level partition of the records (estimator_partition.hpp), 0 index sort + gather (estimator_log.hpp)
+        DevBuf log_part;                        // est_pipeline 1: the scratch copy of one epoch's records, shared by both buffer sets
+        long long log_chunk_records = 0;        // records per chunk of the line-visit log's pool (0: automatic, <= 4096; tests)
+        long long log_capacity = 2500000000LL;  // upper bound of the line-visit records per epoch and buffer set of the wave kernel (24 B + 4 B + 4 B each)
+        bool log_capacity_user = false;         // set through the log_capacity option (otherwise also bounded by the free device memory)
+        // wave kernel: chunks alternate between two buffer sets / streams, so that seeding and the estimator passes of one
+        // chunk overlap the propagation of its neighbours
+        hipStream_t stream2 = nullptr;
+        hipEvent_t ev_join = nullptr;
+        // CU partition (option pass_cus: CUs per XCD set aside for the estimator passes, 0 = off): the propagation launches of a call of several
+        // epochs run on a stream whose queue is masked to the other CUs, the passes of epoch k beside epoch k + 1 on a stream masked to these
+        int pass_cus = 0, pass_cus_built = 0;
+        hipStream_t stream_prop_m = nullptr, stream_pass_m = nullptr;
+        hipEvent_t ev_fork_m = nullptr, ev_join_m = nullptr;
+        DevBuf log_records[2], log_keys[2], log_cursor[2], log_bins[2], log_sorted[2], wave_cold_dev;
+        DevBuf seed_chk, vp_scratch;       // wave kernel: the launch records of a call's packets | the v-packet results handed from worker to owner lanes
+        DevBuf vp_park;                     // pooled volleys with carry-over: one parked v-packet per lane
+        int vp_carry_min_active = 16;       // pooled volleys: leave the volley phase once nothing waits and this few lanes still trace (0: never).  16: -7 % on the
+                                            // configs[4] shape, -5 % on the tardis_example shape + 10 v-packets, flat from 16 to 32 (profiles/r05_volley_carry.txt)
+        // wave kernel: word 397 of every packet's init_genrand sequence (lazy MT19937 seeding)
+        double traces_per_packet = 0.0;  // measured by the last propagate (sizes the line-visit log of the next one)
+        double log_budget_per_packet = 128.0;  // log records reserved per packet
+        unsigned long long *events_host = nullptr;  // pinned: {events counter of the last propagate, its packet count}
+        hipEvent_t ev_events = nullptr;
+        std::vector<mc::WaveCold> wave_cold_host;
+        // wave kernel: a propagate call is a sequence of epochs over one packet supply (LaneSave, propagate_wave.hpp)
+        DevBuf lane_save, wave_save, suspended_dev;
+        // drain compaction (option drain_compact = T: waves suspend once the supply has run out and T or fewer of their lanes are left; the live lanes are packed into
+        // full waves and the rest of the call is a launch of fewer waves, beside the estimator passes): the packed grid's buffers, two sets for repeated packing
+        int drain_compact = 0;
+        int drain_pack_lanes = 64;  // live lanes per packed wave
+        int est_one_level = 1;      // the passes' partition in one pass where the (shell, tile) bins are few enough to be ranked in LDS at once (0: always two levels)
+        DevBuf lane_save_c[2], wave_save_c[2], seeded_states_c[2], drain_census;
+        int compactions = 0;  // of the last propagate call
+        DevBuf vq_req, vq_items, vq_count, vq_jsave;  // volley queue (variant 4, propagate_wave.hpp: VolleyRequest)
+        long long vq_min_items = -1;  // switch the queue off for the rest of a call once a launch requests fewer v-packets (-1: automatic)
+        int vq_min_active = 8, vq_oversubscribe = 4, vq_tracer_waves_per_simd = 6;
+        unsigned *suspended_host = nullptr;  // pinned
+        hipEvent_t ev_post[4] = {nullptr, nullptr, nullptr, nullptr};  // start / end of the estimator passes on log buffer set 0 / 1
+        bool wave_epoch_mode = false, post_pending[2] = {false, false}, prop_pending = false;
+        int log_sets = 0;  // 2: the estimator passes of an epoch run beside the next launch (two log sets); 1: before it (one set); 0: 1 for calls of several epochs, 2 otherwise
+        // Shell-sorted log (round 6; propagate_wave_kernel<..., SL>): every chunk of the line-visit log holds records of one shell, the estimator passes start with
+        // the partition by bin.  1 / -1: where the kernel has it (the production lane-sweep instantiations, <= 64 shells, partition pipeline); 0 (default) off.
+        // Measured (profiles/r06_shell_sorted_log.txt): the passes of an epoch of 2e9 records 86.5 -> 64.2 ms as priced -- and the propagation launches +4.3 %
+        // (2773 -> 2891-2904 ms per 1e8 packets) whether the slots come from ballot ranks (+3 % instructions) or from one LDS atomic (+1.5 %): net +0.6 ... +1.3 % on
+        // the headline, -2 ... -3 % only where a call's passes are not overlapped by anything (2e7 packets with log_sets 1; configs[1])
+        int log_by_shell = 0;
+        // Split launches (round 6): from the second epoch of a call on, the propagation grid is launched as TWO kernels -- the first half of the waves at once, on the
+        // engine's stream; the second half on the passes' stream, behind the estimator passes of the previous epoch.  While those passes run, the chip holds eight
+        // propagation waves per CU instead of none (the passes' 1024-thread workgroups need half a CU: they cannot be placed beside sixteen resident waves, and used to
+        // run alone at every epoch boundary: 0.37 s of a 3.1-s step); when they are over the second half follows.  Nothing in the kernel changes: the second launch
+        // gets a WaveCold whose per-wave pointers (MT19937 states, suspended lanes / waves, v-packet scratch) are offset by the first launch's wave count.
+        // MEASURED, and a clear loss (profiles/r06_split_launch.txt): parity-green, but configs[2] at 1e8 packets 3 109 -> 4 107 ms -- the passes beside eight resident
+        // waves per CU take three times as long as alone (their workgroups need 72 KB of CONTIGUOUS LDS and find it on few CUs), the second half of the grid idles
+        // meanwhile.  Option epoch_split, default 0.
+        int epoch_split = 0;
+        hipEvent_t ev_split[3] = {nullptr, nullptr, nullptr};  // the first launch's inputs are in place | start / end of the second launch
+        DevBuf seeded_states;
+        void release()
+        {
+            release_buffers(log_part, log_records, log_keys, log_cursor, log_bins, log_sorted, wave_cold_dev, seed_chk, vp_scratch, vp_park, seeded_states);
+            release_buffers(lane_save, wave_save, suspended_dev, lane_save_c, wave_save_c, seeded_states_c, drain_census, vq_req, vq_items, vq_count, vq_jsave);
+            destroy_event(ev_join); destroy_event(ev_fork_m); destroy_event(ev_join_m); destroy_event(ev_events); destroy_events(ev_post); destroy_events(ev_split);
+            destroy_stream(stream2); destroy_stream(stream_prop_m); destroy_stream(stream_pass_m);
+            free_pinned(events_host); free_pinned(suspended_host);
+        }
+    } wv;
+    struct LaneSweepTuner {
+        // Two instantiations of the lane-sweep kernel: 128 VGPRs / sixteen waves per CU / eight lines per step (A), and 166 VGPRs / twelve waves per CU /
+        // twelve lines per step (B).  A wins where the steady state dominates (1e8 packets of the configs[2] shape: B +3.8 %), B where the drain of a
+        // call's longest packets does (1.25e7 packets: -11 %; 1e5-1e6 packets of the tardis_example shape: -6 %; profiles/r05_ls_instantiations.txt):
+        // fewer steps per trace shorten the serial chain of a lone packet, and a mostly idle chip does not miss the four waves.  Option
+        // ls_waves_per_simd: 4 = A, 3 = B, 0 (default) = the engine times both on the first calls of a given (packet count, tables) and keeps the
+        // faster one -- a Monte Carlo iteration repeats the same call; per-packet results are bit-identical either way.
+        int ls_waves_per_simd = 0;
+        // (the tuner: calls 0-4 of a key run A untimed, A, B, A, B -- each timed call with the tuner's OWN event pair, recorded only when the call was
+        // enqueued completely, so that neither another entry point's use of ev_start / ev_stop nor a failed call can leave a stale or unpaired
+        // measurement behind -- and from call 5 on B only if the faster of its two calls beat the faster of A's by >= 3 %: boxes differ by more
+        // than one noisy sample can tell apart)
+        struct { long long n = -1; int lines = 0, shells = 0, mode = 0, table = 0, wide = 0, phase = 0, pending = -1, choice = 0; double ms[2][2] = {{-1.0, -1.0}, {-1.0, -1.0}}; } ls_tune;
+        hipEvent_t ev_tune[2] = {nullptr, nullptr};
+        void release() { destroy_events(ev_tune); }
+    } lt;
     // result streaming (tardis_mc_stream_results): the caller's per-packet arrays, what has been copied to them while the call ran, and the packets that were
     // in flight when their range was copied (their results are sent again by get_results)
     struct ResultStream {
@@ -306,33 +381,47 @@ struct TardisMcContext {
         long long upto = 0;        // packets [0, upto) were copied at launch boundaries
         long long n_late = 0;      // entries of the late list (may hold a packet more than once)
         unsigned late_capacity = 0;
+        DevBuf late, late_count, vals;
+        hipStream_t stream = nullptr;
+        hipEvent_t ev = nullptr;
+        unsigned long long *next_host = nullptr;  // pinned: the packet counter after a launch
+        long long min_packets = 1000000;  // a range worth sixteen copies of its own (option stream_min_packets; tests lower it)
+        void release() { release_buffers(late, late_count, vals); destroy_event(ev); destroy_stream(stream); free_pinned(next_host); }
     } rs;
-    DevBuf rs_late, rs_late_count, rs_vals;
-    hipStream_t rs_stream = nullptr;
-    hipEvent_t rs_ev = nullptr;
-    unsigned long long *rs_next_host = nullptr;  // pinned: the packet counter after a launch
-    long long rs_min_packets = 1000000;  // a range worth sixteen copies of its own (option stream_min_packets; tests lower it)
     // source function of the formal integral (source_function.hpp).  Per set_opacity: the CSR indices {lines of every upper level}, {internal rows
-    // ending in every level, with the level each leaves}, every line's emission row and its block (sf_topo_error: a line with none or several), and
+    // ending in every level, with the level each leaves}, every line's emission row and its block (topo_error: a line with none or several), and
     // the exp(-tau) table shared with the formal integral.  Per call: the level vectors e / x[2], the gathered probabilities q, the outputs.
-    DevBuf sf_lvl_ptr, sf_lvl_line, sf_in_ptr, sf_in_row, sf_in_src, sf_emit_row, sf_emit_level;
-    bool sf_topo_valid = false;
-    std::string sf_topo_error;
-    long long sf_nnz = 0;
-    DevBuf sf_exp_tau, sf_e, sf_x[2], sf_q, sf_shell, sf_conv, sf_wave, sf_att, sf_jred, sf_jblue;
-    bool sf_exp_valid = false;
-    bool sf_valid = false;                     // the resident att_S_ul / Jred_lu / Jblue_lu belong to the resident estimators and tables
-    const double *sf_c_level = nullptr;        // with sf_valid: the level rates [S][levels] of that source function (sf_e, or the sf_x the solve ended in)
-    double *sf_conv_host = nullptr;            // pinned: {max |dx|, max |x|} per shell
-    long long source_max_iterations = 20000;   // option: bound on the iterations of a solve
-    int last_source_iterations = -1;
-    // Opacity update (opacity_update.hpp).  Per set_opacity: host copies of the five index tables (line2macro_level_upper, macro_block_edge_index,
-    // transition_type, destination_level_id, transition_line_id; int32, the staging vectors of their upload) and of the line list, from which
-    // derive_opacity_tables builds every table that depends on the probabilities, with or without the caller's pointers.  Per set_line_data: the static
+    struct SourceFunction {
+        DevBuf lvl_ptr, lvl_line, in_ptr, in_row, in_src, emit_row, emit_level;
+        bool topo_valid = false;
+        std::string topo_error;
+        long long nnz = 0;
+        DevBuf exp_tau, e, x[2], q, shell, conv, wave, att, jred, jblue;
+        bool exp_valid = false;
+        bool valid = false;                     // the resident att_S_ul / Jred_lu / Jblue_lu belong to the resident estimators and tables
+        const double *c_level = nullptr;        // with valid: the level rates [S][levels] of that source function (e, or the x the solve ended in)
+        double *conv_host = nullptr;            // pinned: {max |dx|, max |x|} per shell
+        long long max_iterations = 20000;   // option: bound on the iterations of a solve
+        int last_iterations = -1;
+        void release()
+        {
+            release_buffers(lvl_ptr, lvl_line, in_ptr, in_row, in_src, emit_row, emit_level, exp_tau, e, x, q, shell, conv, wave, att, jred, jblue);
+            free_pinned(conv_host);
+        }
+    } sf;
+    // tardis_mc_progress (another host thread polls while propagate blocks): the running call's packet count, whether its kernel hands
+    // packets out through next_packet over the whole call (wave kernel), whether it is complete; a stream and a pinned word of its own
+    struct Progress {
+        std::atomic<long long> progress_total{0};
+        std::atomic<bool> progress_wave{false}, progress_done{true};
+        std::mutex progress_mutex;
+        hipStream_t stream_progress = nullptr;
+        hipEvent_t ev_progress_reset = nullptr;  // recorded behind the reset of next_packet at the start of a call
+        unsigned long long *progress_host = nullptr;
+        void release() { destroy_event(ev_progress_reset); destroy_stream(stream_progress); free_pinned(progress_host); }
+    } pg;
+    // Opacity update (opacity_update.hpp).  Per set_opacity: the host copies of the index tables and of the line list (ot.h_idx, ot.h_nu).  Per set_line_data: the static
     // line data and the list of the blocks that take the row form.  Per update_opacity: n_t[S][K], the [S] inputs, beta_t / sef_t / j_t [S][L].
-    std::vector<int> h_idx[5];
-    std::vector<double> h_nu;
-    bool h_macro = false;
     struct OpacityUpdate {
         DevBuf f_lu, wave, g_lower, g_upper, level_lower, level_upper, coef, long_blocks;
         DevBuf n_t, shell, beta_t, sef_t, j_t;
@@ -717,13 +806,13 @@ int ensure_estimators(TardisMcContext *ctx)
 {
     if (!ctx->have_opacity || !ctx->have_config) return TARDIS_MC_OK;
     size_t S = ctx->n_shells, L = ctx->n_lines, G = (size_t)ctx->cfg.n_spectrum_grid;
-    if (ctx->est_valid && ctx->est_S == S && ctx->est_L == L && ctx->est_G == G) return TARDIS_MC_OK;
-    EstLayout e = est_layout(S, L, G, ctx->est_copies);
-    HIP_TRY(ctx, ctx->est.ensure(e.total * sizeof(double)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->est.p, 0, e.total * sizeof(double), ctx->stream));
-    ctx->est_S = S; ctx->est_L = L; ctx->est_G = G;
-    ctx->est_valid = true;
-    ctx->est_propagated = false;
+    if (ctx->es.est_valid && ctx->es.est_S == S && ctx->es.est_L == L && ctx->es.est_G == G) return TARDIS_MC_OK;
+    EstLayout e = est_layout(S, L, G, ctx->es.est_copies);
+    HIP_TRY(ctx, ctx->es.est.ensure(e.total * sizeof(double)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->es.est.p, 0, e.total * sizeof(double), ctx->stream));
+    ctx->es.est_S = S; ctx->es.est_L = L; ctx->es.est_G = G;
+    ctx->es.est_valid = true;
+    ctx->es.est_propagated = false;
     return TARDIS_MC_OK;
 }
 
@@ -801,12 +890,56 @@ void drop_from(TardisMcContext *ctx, Rung rung)
     }
 }
 
+// The same for the transport side: which resident product is computed from which input.  Whoever replaces or changes an input names the cause, and every
+// product computed from it loses its flag here and nowhere else; a flag is set where its product is built.
+//   source function (sf.valid)                      <- geometry, opacity tables, estimators
+//   its topology (sf.topo_valid)                    <- opacity topology
+//   exp(-tau), screening prefix sums, sweep table   <- optical depths          (sf.exp_valid, sc.pfx_valid, sw.nt_valid: rebuilt lazily by their first user)
+//   walk tables, hot sectors                        <- transition probabilities (wt.have_walk_tables, wt.have_hot: rebuilt by derive_opacity_tables itself)
+//   per-packet results (pk.li_valid)                <- packets
+//   v-packet log (vl.vl_valid, vl.vl_consolidated)  <- packets, configuration
+//   event log, streamed results                     <- the propagate call that wrote them (el.ev_valid, rs.valid; the readers compare the packet count too)
+enum Cause {
+    GEOMETRY_REPLACED,          // tardis_mc_set_geometry
+    OPACITY_TOPOLOGY_REPLACED,  // tardis_mc_set_opacity, before it validates: a refused call drops the source function too
+    OPACITY_UPDATE_BEGINS,      // tardis_mc_update_opacity, the install stage of tardis_mc_update_plasma: tau_t / prob_t are about to be overwritten in place
+    OPACITY_VALUES_REPLACED,    // derive_opacity_tables: set_opacity, update_opacity, update_plasma
+    ESTIMATORS_CHANGED,         // tardis_mc_reset_estimators, tardis_mc_allreduce_estimators, the start of tardis_mc_source_function
+    CONFIG_REPLACED,            // tardis_mc_set_config
+    PACKETS_REPLACED,           // tardis_mc_set_packets, tardis_mc_create_blackbody_packets
+    PROPAGATE_BEGINS            // tardis_mc_propagate
+};
+void drop_products(TardisMcContext *ctx, Cause cause)
+{
+    switch (cause) {
+    case GEOMETRY_REPLACED:
+    case OPACITY_UPDATE_BEGINS:
+    case ESTIMATORS_CHANGED: ctx->sf.valid = false; break;
+    case OPACITY_TOPOLOGY_REPLACED: ctx->sf.valid = ctx->sf.topo_valid = ctx->sf.exp_valid = false; break;
+    case OPACITY_VALUES_REPLACED:
+        ctx->sf.valid = ctx->sf.exp_valid = false;
+        ctx->wt.have_walk_tables = ctx->wt.have_hot = false;
+        ctx->sc.pfx_valid = false;  // (the prefix sums of the new tau table are built by the first propagate call that traces v-packets)
+        ctx->sw.nt_valid = false;   // (likewise the interleaved sweep table: by the first call that sweeps on it)
+        break;
+    case CONFIG_REPLACED: ctx->vl.vl_valid = ctx->vl.vl_consolidated = false; break;  // (the consolidated v-packet log belongs to the configuration it was written under)
+    case PACKETS_REPLACED:
+        ctx->pk.li_valid = false;  // (the resident results are no longer those of the resident packets)
+        ctx->vl.vl_valid = ctx->vl.vl_consolidated = false;
+        break;
+    case PROPAGATE_BEGINS:
+        ctx->el.ev_valid = ctx->pk.li_valid = ctx->sf.valid = ctx->rs.valid = false;
+        ctx->vl.vl_valid = ctx->vl.vl_consolidated = false;
+        break;
+    }
+}
+
 // the sixteen per-packet result arrays on the device / in a TardisMcResult, in one order: out_nu, out_e, nine tracker doubles, five tracker integers
 void per_packet_device_arrays(TardisMcContext *ctx, void *dev[16])
 {
-    dev[0] = ctx->out_nu.p; dev[1] = ctx->out_e.p;
-    for (int k = 0; k < 9; ++k) dev[2 + k] = ctx->track ? ctx->li_f64[k].p : nullptr;
-    for (int k = 0; k < 5; ++k) dev[11 + k] = ctx->track ? ctx->li_i64[k].p : nullptr;
+    dev[0] = ctx->pk.out_nu.p; dev[1] = ctx->pk.out_e.p;
+    for (int k = 0; k < 9; ++k) dev[2 + k] = ctx->pk.track ? ctx->pk.li_f64[k].p : nullptr;
+    for (int k = 0; k < 5; ++k) dev[11 + k] = ctx->pk.track ? ctx->pk.li_i64[k].p : nullptr;
 }
 void per_packet_host_arrays(const TardisMcResult *r, void *host[16])
 {
@@ -827,40 +960,40 @@ __global__ void __launch_bounds__(256) narrow_seeds_kernel(const long long *__re
 // such a call runs the VLI instantiations of the kernels
 bool vlog_li_call(const TardisMcContext *ctx)
 {
-    return ctx->vlog_li && ctx->cfg.enable_vpacket_tracking && ctx->cfg.number_of_vpackets > 0 && ctx->vlog_capacity > 0;
+    return ctx->vl.vlog_li && ctx->cfg.enable_vpacket_tracking && ctx->cfg.number_of_vpackets > 0 && ctx->vl.vlog_capacity > 0;
 }
 
 mc::DeviceProblem make_device_problem(TardisMcContext *ctx)
 {
     mc::DeviceProblem P{};
-    P.n_packets = ctx->n_packets;
-    P.r0 = ctx->r0.as<double>(); P.mu0 = ctx->mu0.as<double>(); P.nu0 = ctx->nu0.as<double>(); P.e0 = ctx->e0.as<double>();
-    P.seeds = ctx->seeds.as<uint32_t>();
-    P.out_nu = ctx->out_nu.as<double>(); P.out_e = ctx->out_e.as<double>();
-    if (ctx->track) {
+    P.n_packets = ctx->pk.n_packets;
+    P.r0 = ctx->pk.r0.as<double>(); P.mu0 = ctx->pk.mu0.as<double>(); P.nu0 = ctx->pk.nu0.as<double>(); P.e0 = ctx->pk.e0.as<double>();
+    P.seeds = ctx->pk.seeds.as<uint32_t>();
+    P.out_nu = ctx->pk.out_nu.as<double>(); P.out_e = ctx->pk.out_e.as<double>();
+    if (ctx->pk.track) {
         double **f[] = {&P.li_radius, &P.li_nu, &P.li_energy, &P.li_before_nu, &P.li_before_mu, &P.li_before_energy,
                         &P.li_after_nu, &P.li_after_mu, &P.li_after_energy};
-        for (int k = 0; k < 9; ++k) *f[k] = ctx->li_f64[k].as<double>();
+        for (int k = 0; k < 9; ++k) *f[k] = ctx->pk.li_f64[k].as<double>();
         long long **g[] = {&P.li_shell_id, &P.li_interaction_type, &P.li_line_absorb_id, &P.li_line_emit_id,
                            &P.li_interactions_count};
-        for (int k = 0; k < 5; ++k) *g[k] = ctx->li_i64[k].as<long long>();
-        P.li_rec = ctx->li_rec.as<uint4>();
+        for (int k = 0; k < 5; ++k) *g[k] = ctx->pk.li_i64[k].as<long long>();
+        P.li_rec = ctx->pk.li_rec.as<uint4>();
     }
-    if (ctx->track_full) P.li_rec = ctx->li_rec.as<uint4>();  // (the tracked wave kernel counts rows with the tracker, TRACK on)
+    if (ctx->el.track_full) P.li_rec = ctx->pk.li_rec.as<uint4>();  // (the tracked wave kernel counts rows with the tracker, TRACK on)
     P.n_shells = ctx->n_shells;
     P.r_inner = ctx->r_inner.as<double>(); P.r_outer = ctx->r_outer.as<double>();
     P.t_exp = ctx->t_exp;
     P.n_lines = ctx->n_lines; P.n_trans = ctx->n_trans;
-    P.nu_line = ctx->nu_line.as<double>(); P.tau_t = ctx->tau_t.as<double>(); P.n_e = ctx->n_e.as<double>();
-    P.prob_t = ctx->prob_t.as<double>();
-    P.line2level = ctx->line2level.as<int>(); P.block_edge = ctx->block_edge.as<int>(); P.ttype = ctx->ttype.as<int>();
-    P.dest = ctx->dest.as<int>(); P.tline = ctx->tline.as<int>();
-    EstLayout e = est_layout(ctx->est_S, ctx->est_L, ctx->est_G, ctx->est_copies);
-    double *base = ctx->est.as<double>();
+    P.nu_line = ctx->ot.nu_line.as<double>(); P.tau_t = ctx->ot.tau_t.as<double>(); P.n_e = ctx->ot.n_e.as<double>();
+    P.prob_t = ctx->ot.prob_t.as<double>();
+    P.line2level = ctx->ot.line2level.as<int>(); P.block_edge = ctx->ot.block_edge.as<int>(); P.ttype = ctx->ot.ttype.as<int>();
+    P.dest = ctx->ot.dest.as<int>(); P.tline = ctx->ot.tline.as<int>();
+    EstLayout e = est_layout(ctx->es.est_S, ctx->es.est_L, ctx->es.est_G, ctx->es.est_copies);
+    double *base = ctx->es.est.as<double>();
     P.J = base + e.J; P.nubar = base + e.nubar; P.vhist = base + e.vhist;
     P.jblue_t = base + e.jblue; P.edot_t = base + e.edot;
     P.est_copy_stride = (long long)e.copy_stride;
-    P.n_est_copies = ctx->est_copies;
+    P.n_est_copies = ctx->es.est_copies;
     const TardisMcConfig &c = ctx->cfg;
     P.line_interaction_type = c.line_interaction_type;
     P.disable_line_scattering = c.disable_line_scattering;
@@ -877,12 +1010,12 @@ mc::DeviceProblem make_device_problem(TardisMcContext *ctx)
         P.grid_last = ctx->grid_host[c.n_spectrum_grid - 1];
         P.delta_nu = ctx->grid_host[1] - ctx->grid_host[0];
     }
-    if (c.enable_vpacket_tracking && c.number_of_vpackets > 0 && ctx->vlog_capacity > 0) {
-        P.vlog_count = ctx->vlog_count.as<unsigned long long>();
-        P.vlog_capacity = ctx->vlog_capacity;
-        P.vlog_packet = ctx->vlog_packet.as<long long>(); P.vlog_seq = ctx->vlog_seq.as<int>();
-        P.vlog_nu = ctx->vlog_nu.as<double>(); P.vlog_energy = ctx->vlog_energy.as<double>();
-        P.vlog_mu = ctx->vlog_mu.as<double>(); P.vlog_r = ctx->vlog_r.as<double>();
+    if (c.enable_vpacket_tracking && c.number_of_vpackets > 0 && ctx->vl.vlog_capacity > 0) {
+        P.vlog_count = ctx->vl.vlog_count.as<unsigned long long>();
+        P.vlog_capacity = ctx->vl.vlog_capacity;
+        P.vlog_packet = ctx->vl.vlog_packet.as<long long>(); P.vlog_seq = ctx->vl.vlog_seq.as<int>();
+        P.vlog_nu = ctx->vl.vlog_nu.as<double>(); P.vlog_energy = ctx->vl.vlog_energy.as<double>();
+        P.vlog_mu = ctx->vl.vlog_mu.as<double>(); P.vlog_r = ctx->vl.vlog_r.as<double>();
     }
     P.rng_state = ctx->rng_state.as<uint32_t>();
     P.counters = ctx->counters.as<unsigned long long>();
@@ -1008,7 +1141,7 @@ size_t wave_kernel_lds(const WaveKernelKey &k, int n_shells)  // dynamic LDS of 
 int launch_lane(TardisMcContext *ctx, const mc::DeviceProblem &P, int blocks, size_t lds)
 {
     const bool ft = P.evlog.rows != nullptr;  // full r-packet tracking: 8 ints of LDS per workgroup for the waves' append state
-    const LaneKernelFn k = find_kernel(LANE_KERNELS, LaneKernelKey{ctx->cfg.enable_full_relativity != 0, ctx->cfg.number_of_vpackets > 0, ctx->track, ft, vlog_li_call(ctx)});
+    const LaneKernelFn k = find_kernel(LANE_KERNELS, LaneKernelKey{ctx->cfg.enable_full_relativity != 0, ctx->cfg.number_of_vpackets > 0, ctx->pk.track, ft, vlog_li_call(ctx)});
     if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the lane kernel");
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds + (ft ? 32 : 0), ctx->stream, P);
     HIP_TRY(ctx, hipGetLastError());
@@ -1019,40 +1152,40 @@ int launch_lane(TardisMcContext *ctx, const mc::DeviceProblem &P, int blocks, si
 // partly filled last chunks), bound its device memory, clear the counts and the chunk fills, and point P at it.
 int setup_event_log(TardisMcContext *ctx, mc::DeviceProblem &P, long long n_waves)
 {
-    const long long n = ctx->n_packets;
+    const long long n = ctx->pk.n_packets;
     const long long row_bytes = (long long)sizeof(mc::EventRow), col_bytes = 14 * 8;  // pool row; the fourteen int64 / float64 columns
-    long long cap = ctx->evlog_capacity;
+    long long cap = ctx->el.evlog_capacity;
     const long long fixed = n * (4 + 8) + 64;  // counts, offsets
     if (cap <= 0) {  // automatic: 32 rows per packet, within the bound (a re-run with the exact count fixes an overflow)
-        const long long fit = (ctx->evlog_max_bytes - fixed) / (row_bytes + col_bytes) - n_waves * (long long)ctx->ev_chunk_rows;
+        const long long fit = (ctx->el.evlog_max_bytes - fixed) / (row_bytes + col_bytes) - n_waves * (long long)ctx->el.ev_chunk_rows;
         cap = std::max<long long>(1024, std::min<long long>(32 * std::max<long long>(n, 1), fit));
     }
-    const long long chunks = (cap + ctx->ev_chunk_rows - 1) / ctx->ev_chunk_rows + n_waves;
-    const long long slots = chunks * (long long)ctx->ev_chunk_rows;
+    const long long chunks = (cap + ctx->el.ev_chunk_rows - 1) / ctx->el.ev_chunk_rows + n_waves;
+    const long long slots = chunks * (long long)ctx->el.ev_chunk_rows;
     const long long need = slots * row_bytes + cap * col_bytes + fixed;
-    if (need > ctx->evlog_max_bytes || chunks >= (1LL << 31))
+    if (need > ctx->el.evlog_max_bytes || chunks >= (1LL << 31))
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT,
                     "full r-packet tracking: an event log of %lld rows for %lld packets needs %.2f GiB of device memory, more than the "
                     "bound of %.2f GiB (option event_log_max_bytes); propagate fewer packets per call or raise the bound",
-                    cap, n, need / 1073741824.0, ctx->evlog_max_bytes / 1073741824.0);
-    HIP_TRY(ctx, ctx->ev_rows.ensure((size_t)slots * row_bytes));
-    HIP_TRY(ctx, ctx->ev_fill.ensure((size_t)chunks * sizeof(unsigned)));
-    HIP_TRY(ctx, ctx->ev_state.ensure(2 * sizeof(unsigned long long)));
-    HIP_TRY(ctx, ctx->ev_counts.ensure((size_t)std::max<long long>(n, 1) * sizeof(int)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ev_fill.p, 0, (size_t)chunks * sizeof(unsigned), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ev_state.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ev_counts.p, 0, (size_t)std::max<long long>(n, 1) * sizeof(int), ctx->stream));
-    P.evlog.rows = ctx->ev_rows.as<mc::EventRow>();
-    P.evlog.chunk_fill = ctx->ev_fill.as<unsigned>();
-    P.evlog.pool_next = ctx->ev_state.as<unsigned>();
-    P.evlog.dropped = ctx->ev_state.as<unsigned long long>() + 1;
-    P.evlog.counts = ctx->ev_counts.as<int>();
-    P.evlog.chunk_rows = ctx->ev_chunk_rows;
+                    cap, n, need / 1073741824.0, ctx->el.evlog_max_bytes / 1073741824.0);
+    HIP_TRY(ctx, ctx->el.ev_rows.ensure((size_t)slots * row_bytes));
+    HIP_TRY(ctx, ctx->el.ev_fill.ensure((size_t)chunks * sizeof(unsigned)));
+    HIP_TRY(ctx, ctx->el.ev_state.ensure(2 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, ctx->el.ev_counts.ensure((size_t)std::max<long long>(n, 1) * sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->el.ev_fill.p, 0, (size_t)chunks * sizeof(unsigned), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->el.ev_state.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->el.ev_counts.p, 0, (size_t)std::max<long long>(n, 1) * sizeof(int), ctx->stream));
+    P.evlog.rows = ctx->el.ev_rows.as<mc::EventRow>();
+    P.evlog.chunk_fill = ctx->el.ev_fill.as<unsigned>();
+    P.evlog.pool_next = ctx->el.ev_state.as<unsigned>();
+    P.evlog.dropped = ctx->el.ev_state.as<unsigned long long>() + 1;
+    P.evlog.counts = ctx->el.ev_counts.as<int>();
+    P.evlog.chunk_rows = ctx->el.ev_chunk_rows;
     P.evlog.n_chunks = (unsigned)chunks;
-    ctx->ev_packets = n;
-    ctx->ev_capacity = cap;
-    ctx->ev_slots = slots;
-    ctx->ev_n_chunks = (unsigned)chunks;
+    ctx->el.ev_packets = n;
+    ctx->el.ev_capacity = cap;
+    ctx->el.ev_slots = slots;
+    ctx->el.ev_n_chunks = (unsigned)chunks;
     return TARDIS_MC_OK;
 }
 
@@ -1070,33 +1203,33 @@ plan::PlanInput plan_input(const TardisMcContext *ctx)
 {
     const TardisMcConfig &c = ctx->cfg;
     plan::PlanInput in{};
-    in.n_shells = ctx->n_shells; in.n_lines = ctx->n_lines; in.n_trans = ctx->n_trans; in.n_packets = ctx->n_packets;
+    in.n_shells = ctx->n_shells; in.n_lines = ctx->n_lines; in.n_trans = ctx->n_trans; in.n_packets = ctx->pk.n_packets;
     in.number_of_vpackets = c.number_of_vpackets; in.survival_probability = c.survival_probability;
     in.enable_full_relativity = c.enable_full_relativity; in.line_interaction_type = c.line_interaction_type;
-    in.lines_sorted = ctx->lines_sorted; in.prob_negative = ctx->prob_negative; in.have_walk_tables = ctx->have_walk_tables;
-    in.variant = ctx->variant; in.table_offsets = ctx->table_offsets; in.vpacket_screening = ctx->vpacket_screening;
-    in.vpk_wave_min_packets = ctx->vpk_wave_min_packets; in.track_full = ctx->track_full; in.debug_flags = ctx->debug_flags;
-    in.pfx_valid = ctx->pfx_valid; in.pfx_negative = ctx->pfx_negative;
+    in.lines_sorted = ctx->ot.lines_sorted; in.prob_negative = ctx->ot.prob_negative; in.have_walk_tables = ctx->wt.have_walk_tables;
+    in.variant = ctx->variant; in.table_offsets = ctx->table_offsets; in.vpacket_screening = ctx->sc.vpacket_screening;
+    in.vpk_wave_min_packets = ctx->vpk_wave_min_packets; in.track_full = ctx->el.track_full; in.debug_flags = ctx->debug_flags;
+    in.pfx_valid = ctx->sc.pfx_valid; in.pfx_negative = ctx->sc.pfx_negative;
     return in;
 }
 
 // the v-packet screening tables (tau_prefix.hpp): built by the first v-packet call after set_opacity that screens; a launch and a read-back of the negative-depth flag
 int build_screening_tables(TardisMcContext *ctx)
 {
-    if (ctx->pfx_valid) return TARDIS_MC_OK;
+    if (ctx->sc.pfx_valid) return TARDIS_MC_OK;
     const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines;
-    HIP_TRY(ctx, ctx->tau_pfx.ensure((S * (L + 1) + 8) * sizeof(double)));  // (+8: the four-entry windows of the screening)
-    HIP_TRY(ctx, ctx->tau_rowsum.ensure(S * sizeof(double)));
-    HIP_TRY(ctx, ctx->pfx_flag.ensure(sizeof(int)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->pfx_flag.p, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(mc::tau_prefix_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, ctx->tau_t.as<double>(), (int)L,
-                       ctx->tau_pfx.as<double>(), ctx->tau_rowsum.as<double>(), ctx->pfx_flag.as<int>());
+    HIP_TRY(ctx, ctx->sc.tau_pfx.ensure((S * (L + 1) + 8) * sizeof(double)));  // (+8: the four-entry windows of the screening)
+    HIP_TRY(ctx, ctx->sc.tau_rowsum.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, ctx->sc.pfx_flag.ensure(sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->sc.pfx_flag.p, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(mc::tau_prefix_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, ctx->ot.tau_t.as<double>(), (int)L,
+                       ctx->sc.tau_pfx.as<double>(), ctx->sc.tau_rowsum.as<double>(), ctx->sc.pfx_flag.as<int>());
     HIP_TRY(ctx, hipGetLastError());
     int neg = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&neg, ctx->pfx_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&neg, ctx->sc.pfx_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->pfx_negative = neg != 0;
-    ctx->pfx_valid = true;
+    ctx->sc.pfx_negative = neg != 0;
+    ctx->sc.pfx_valid = true;
     return TARDIS_MC_OK;
 }
 
@@ -1105,21 +1238,21 @@ int build_screening_tables(TardisMcContext *ctx)
 int build_sweep_table(TardisMcContext *ctx)
 {
     const unsigned long long stride = ((unsigned long long)ctx->n_lines + 7ull) & ~7ull;
-    if (ctx->nt_valid || stride * (unsigned long long)ctx->n_shells + 32ull >= (1ull << 28)) return TARDIS_MC_OK;
+    if (ctx->sw.nt_valid || stride * (unsigned long long)ctx->n_shells + 32ull >= (1ull << 28)) return TARDIS_MC_OK;
     const long long total = (long long)(stride * (unsigned long long)ctx->n_shells) + 32;  // (+ the slack of a step's loads behind the last row)
-    HIP_TRY(ctx, ctx->nt_t.ensure((size_t)total * 16));
-    HIP_TRY(ctx, ctx->pfx_flag.ensure(sizeof(int)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->pfx_flag.p, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(interleave_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 65536)), dim3(256), 0, ctx->stream, ctx->nu_line.as<double>(),
-                       ctx->tau_t.as<double>(), ctx->nt_t.as<double2>(), (long long)ctx->n_lines, (long long)ctx->n_shells, (long long)stride, total,
-                       ctx->pfx_flag.as<int>());
+    HIP_TRY(ctx, ctx->sw.nt_t.ensure((size_t)total * 16));
+    HIP_TRY(ctx, ctx->sc.pfx_flag.ensure(sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->sc.pfx_flag.p, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(interleave_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 65536)), dim3(256), 0, ctx->stream, ctx->ot.nu_line.as<double>(),
+                       ctx->ot.tau_t.as<double>(), ctx->sw.nt_t.as<double2>(), (long long)ctx->n_lines, (long long)ctx->n_shells, (long long)stride, total,
+                       ctx->sc.pfx_flag.as<int>());
     HIP_TRY(ctx, hipGetLastError());
     int neg = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&neg, ctx->pfx_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&neg, ctx->sc.pfx_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->nt_negative = neg != 0;
-    ctx->nt_stride = (unsigned)stride;
-    ctx->nt_valid = true;
+    ctx->sw.nt_negative = neg != 0;
+    ctx->sw.nt_stride = (unsigned)stride;
+    ctx->sw.nt_valid = true;
     return TARDIS_MC_OK;
 }
 
@@ -1127,24 +1260,24 @@ int build_sweep_table(TardisMcContext *ctx)
 // SIMD) or B (three: *ls3) -- forced by the option, or timed on the first calls of this key; call.tune_slot says which timed slot this call is, if any.
 int lane_sweep_tuner(TardisMcContext *ctx, PropagateCall &call, bool *ls3)
 {
-    auto &tn = ctx->ls_tune;
+    auto &tn = ctx->lt.ls_tune;
     const bool w64 = call.plan.w64;
     const int mode = ctx->cfg.line_interaction_type;
     *ls3 = false;
     // (a call that does not even fill the grid's lanes four times over is nothing but the drain of its longest packets: B, measured -6 % on
     // 1e5 - 1e6-packet calls of the tardis_example shape, without spending five calls of a 20-iteration run on finding that out)
-    const bool all_drain = ctx->n_packets < 4LL * 64 * 16 * call.cus;
-    if (ctx->ls_waves_per_simd == 3 || (ctx->ls_waves_per_simd == 0 && all_drain)) *ls3 = true;
-    else if (ctx->ls_waves_per_simd == 0 && ctx->pass_cus == 0) {
-        if (tn.n != ctx->n_packets || tn.lines != ctx->n_lines || tn.shells != ctx->n_shells || tn.mode != mode || tn.table != ctx->sweep_table || tn.wide != (int)w64) {
-            tn.n = ctx->n_packets; tn.lines = ctx->n_lines; tn.shells = ctx->n_shells; tn.mode = mode; tn.table = ctx->sweep_table;
+    const bool all_drain = ctx->pk.n_packets < 4LL * 64 * 16 * call.cus;
+    if (ctx->lt.ls_waves_per_simd == 3 || (ctx->lt.ls_waves_per_simd == 0 && all_drain)) *ls3 = true;
+    else if (ctx->lt.ls_waves_per_simd == 0 && ctx->wv.pass_cus == 0) {
+        if (tn.n != ctx->pk.n_packets || tn.lines != ctx->n_lines || tn.shells != ctx->n_shells || tn.mode != mode || tn.table != ctx->sw.sweep_table || tn.wide != (int)w64) {
+            tn.n = ctx->pk.n_packets; tn.lines = ctx->n_lines; tn.shells = ctx->n_shells; tn.mode = mode; tn.table = ctx->sw.sweep_table;
             tn.wide = (int)w64;
             tn.phase = 0; tn.choice = 0;
             tn.ms[0][0] = tn.ms[0][1] = tn.ms[1][0] = tn.ms[1][1] = -1.0;
         } else if (call.tune_pending >= 0) {  // the previous call of this key was a timed one: its duration (propagation + passes)
             float ms = 0.f;
-            HIP_TRY(ctx, hipEventSynchronize(ctx->ev_tune[1]));
-            HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_tune[0], ctx->ev_tune[1]));
+            HIP_TRY(ctx, hipEventSynchronize(ctx->lt.ev_tune[1]));
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->lt.ev_tune[0], ctx->lt.ev_tune[1]));
             tn.ms[call.tune_pending >> 1][call.tune_pending & 1] = ms;
         } else if (tn.phase >= 2 && tn.phase <= 5)
             tn.phase -= 1;  // the previous phase was a timed call and left no measurement (the call failed half-way): again
@@ -1161,7 +1294,7 @@ int lane_sweep_tuner(TardisMcContext *ctx, PropagateCall &call, bool *ls3)
         if (tn.phase < 6) ++tn.phase;
         if (call.tune_slot >= 0)
             for (int k = 0; k < 2; ++k)
-                if (!ctx->ev_tune[k]) HIP_TRY(ctx, hipEventCreate(&ctx->ev_tune[k]));
+                if (!ctx->lt.ev_tune[k]) HIP_TRY(ctx, hipEventCreate(&ctx->lt.ev_tune[k]));
     }
     return TARDIS_MC_OK;
 }
@@ -1184,7 +1317,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
     const bool vpk = call.vpk, full = call.full, w64 = call.plan.w64, vq = call.plan.variant == 4;
     WaveKernelKey &k = w.key;
     k = WaveKernelKey{};
-    k.full = full; k.track = ctx->track; k.vpk = vpk;
+    k.full = full; k.track = ctx->pk.track; k.vpk = vpk;
     k.lane_sweep = call.plan.variant == 3 && !full;  // (the bounds of the lane sweep are those of partial relativity)
     k.waves_per_simd = vpk ? 3 : 4;
     if (wave_kernel_lds(k, ctx->n_shells) > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
@@ -1192,7 +1325,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
     // macro-atom jumps of the wave kernel (macroatom chains and the single jump of downbranch alike): per-lane walk on the
     // compact tables (walk_tables.hpp); debug flag 8192 keeps the cooperative group scan of the fp64 running sums (macroatom) /
     // the fp64 search (downbranch), 128 the per-lane search in them (both for cross-checks)
-    w.compact_walk = c.line_interaction_type != 0 && ctx->have_walk_tables && !(ctx->debug_flags & plan::DBG_FP64_WALKS);
+    w.compact_walk = c.line_interaction_type != 0 && ctx->wt.have_walk_tables && !(ctx->debug_flags & plan::DBG_FP64_WALKS);
     // (flag 1048576: the long instantiations, for A/B; the flags that read the kernel's profiling / test counters: those are only compiled into the long ones)
     k.xwalk = (c.line_interaction_type != 0 && !w.compact_walk) || (ctx->debug_flags & (plan::DBG_LONG_INSTANTIATIONS | plan::DBG_WAVE_COUNTERS)) != 0;
     if (w64 && k.xwalk) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "the fp64 macro-atom walks have no 64-bit table offsets");
@@ -1206,7 +1339,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
     // Measured (profiles/r05_vpk_wide_registers.txt): 3727-3766 vs 4442-4450 ms per 1e7 packets of the configs[4] shape (-16 %).  Option 2 forces
     // it (then eight waves per CU whatever the LDS allows), 0 keeps the 168-VGPR instantiation.
     // (with lane sweeps: variant 3 under partial relativity)
-    if (vpk && !k.xwalk && !w64 && !ctx->track_full && (k.lane_sweep || GW == 16 || GW == 8) &&
+    if (vpk && !k.xwalk && !w64 && !ctx->el.track_full && (k.lane_sweep || GW == 16 || GW == 8) &&
         ((ctx->vpk_wide_registers == 1 && w.waves_per_cu <= 8) || ctx->vpk_wide_registers == 2))
         k.waves_per_simd = 2;
     // which lane-sweep instantiation (see ls_waves_per_simd in the context), and whether on the interleaved sweep table: the production lane-sweep instantiations only
@@ -1215,12 +1348,12 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
         int rc = lane_sweep_tuner(ctx, call, &w.ls3);
         if (rc) return rc;
         if (w.ls3) k.waves_per_simd = 3;
-        if (!w64 && ctx->sweep_table != 0) {
+        if (!w64 && ctx->sw.sweep_table != 0) {
             rc = build_sweep_table(ctx);
             if (rc) return rc;
-            if (ctx->nt_valid && !ctx->nt_negative) {
-                k.nt = (ctx->sweep_table == 2 && !w.ls3) ? 2 : 1;
-                P.nt_t = ctx->nt_t.as<double>(); P.nt_stride = ctx->nt_stride;
+            if (ctx->sw.nt_valid && !ctx->sw.nt_negative) {
+                k.nt = (ctx->sw.sweep_table == 2 && !w.ls3) ? 2 : 1;
+                P.nt_t = ctx->sw.nt_t.as<double>(); P.nt_stride = ctx->sw.nt_stride;
             }
         }
     }
@@ -1228,11 +1361,11 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
     w.tiles = std::max((ctx->n_lines + mc::EST_TILE - 1) / mc::EST_TILE, 1);
     w.n_bins = ctx->n_shells * w.tiles;
     // est_pipeline 1 (estimator_partition.hpp): needs a shell's bins and all shells to fit the partition kernel's local buckets
-    w.partition = ctx->est_pipeline == 1 && w.tiles <= mc::PART_LOCAL_BUCKETS && ctx->n_shells <= mc::PART_LOCAL_BUCKETS;
+    w.partition = ctx->wv.est_pipeline == 1 && w.tiles <= mc::PART_LOCAL_BUCKETS && ctx->n_shells <= mc::PART_LOCAL_BUCKETS;
     // the shell-sorted log: instantiated for the two production lane-sweep kernels (sixteen waves on the interleaved table, twelve on the separate ones)
-    k.shell_log = k.lane_sweep && !vpk && !k.xwalk && !w64 && !vq && w.partition && ctx->log_by_shell != 0 && ctx->n_shells <= 64 &&
+    k.shell_log = k.lane_sweep && !vpk && !k.xwalk && !w64 && !vq && w.partition && ctx->wv.log_by_shell != 0 && ctx->n_shells <= 64 &&
                   ((!w.ls3 && k.nt == 1) || (w.ls3 && k.nt == 0));
-    if (ctx->track_full) {  // the tracked instantiations: group sweeps of 16 lanes, compact walks, default register budget
+    if (ctx->el.track_full) {  // the tracked instantiations: group sweeps of 16 lanes, compact walks, default register budget
         k.full_tracking = true; k.track = true; k.width = 16;
     }
     // 64-bit row offsets: the production shapes above without the interleaved sweep table, the shell-sorted log and the two-waves-per-SIMD
@@ -1252,8 +1385,8 @@ LogMemory log_memory(const TardisMcContext *ctx)
 {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return LogMemory{false, 0.0, 0.0};
-    const double have = (double)(ctx->log_records[0].cap + ctx->log_records[1].cap + ctx->log_keys[0].cap + ctx->log_keys[1].cap +
-                                 ctx->log_sorted[0].cap + ctx->log_sorted[1].cap + ctx->log_part.cap);
+    const double have = (double)(ctx->wv.log_records[0].cap + ctx->wv.log_records[1].cap + ctx->wv.log_keys[0].cap + ctx->wv.log_keys[1].cap +
+                                 ctx->wv.log_sorted[0].cap + ctx->wv.log_sorted[1].cap + ctx->wv.log_part.cap);
     return LogMemory{true, (double)free_b + have, (double)total_b};
 }
 // bytes per record of a set's capacity: every set holds the record and its key, and its own index (the sort) or a share of the one scratch copy (the partition)
@@ -1279,33 +1412,33 @@ struct LogSizing {
 int size_line_log(TardisMcContext *ctx, const PropagateCall &call, const WaveChoice &w, long long n, int waves, bool cu_split, LogSizing &s)
 {
     const bool vpk = call.vpk, vq = call.plan.variant == 4, partition = w.partition, shell_log = w.key.shell_log;
-    long long log_capacity = ctx->log_capacity;
+    long long log_capacity = ctx->wv.log_capacity;
     // One log set or two.  Two let the passes of an epoch run on a second stream beside the next launch -- but they do not fit beside sixteen resident waves per CU,
     // so "beside" means: contending with the next launch's first 0.1 s, both slower for it.  Measured at 1e8 packets (profiles/r06_log_sets.txt): the passes before
     // the next launch, alone on the chip, are faster in total, and one set leaves room for epochs half as many again (three launches instead of five): -0.5 %.
     // So a call of many epochs uses one set; shorter calls keep two (the passes of the bulk run beside the drain of the last launch).
-    s.one_set = ctx->log_sets == 1;
-    if (ctx->log_sets == 0 && partition && !vq && !vpk && ctx->drain_split == 0 && ctx->drain_compact == 0 && ctx->epoch_split == 0 && ctx->pass_cus == 0) {
-        double two_set_capacity = (double)ctx->log_capacity;
-        if (!ctx->log_capacity_user) {
+    s.one_set = ctx->wv.log_sets == 1;
+    if (ctx->wv.log_sets == 0 && partition && !vq && !vpk && ctx->wv.drain_split == 0 && ctx->wv.drain_compact == 0 && ctx->wv.epoch_split == 0 && ctx->wv.pass_cus == 0) {
+        double two_set_capacity = (double)ctx->wv.log_capacity;
+        if (!ctx->wv.log_capacity_user) {
             const LogMemory m = log_memory(ctx);
             if (m.known) two_set_capacity = std::min(two_set_capacity, LOG_MEMORY_SHARE * m.avail / log_bytes_per_record(2, true));
         }
         // (four epochs or more with two sets; at two or three the passes of the first epochs still find room beside the last launch's drain: 4e7 packets
         // 1 292 - 1 308 ms with two sets, 1 320 - 1 351 with one)
-        const double per_packet = ctx->traces_per_packet > 0.0 ? 1.05 * ctx->traces_per_packet : ctx->log_budget_per_packet;
+        const double per_packet = ctx->wv.traces_per_packet > 0.0 ? 1.05 * ctx->wv.traces_per_packet : ctx->wv.log_budget_per_packet;
         s.one_set = (double)n * per_packet > 3.0 * two_set_capacity;
     }
-    if (s.one_set && !ctx->log_capacity_user) {
+    if (s.one_set && !ctx->wv.log_capacity_user) {
         // (the second set of an earlier, smaller call is given back first)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->stream2) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
-        ctx->log_records[1].release(); ctx->log_keys[1].release(); ctx->log_sorted[1].release(); ctx->log_bins[1].release(); ctx->log_cursor[1].release();
+        if (ctx->wv.stream2) HIP_TRY(ctx, hipStreamSynchronize(ctx->wv.stream2));
+        ctx->wv.log_records[1].release(); ctx->wv.log_keys[1].release(); ctx->wv.log_sorted[1].release(); ctx->wv.log_bins[1].release(); ctx->wv.log_cursor[1].release();
         log_capacity = 4000000000LL;
     }
     LogMemory m{false, 0.0, 0.0};
     bool asked = false;
-    if (!ctx->log_capacity_user) {
+    if (!ctx->wv.log_capacity_user) {
         // (fewer, longer epochs are faster -- 25.8 vs 24.5 Mpkt/s at 1e8 packets with 2.5e9 instead of 1.5e9 records per set
         // -- but two sets of 2.5e9 records are 160 GB)
         m = log_memory(ctx);
@@ -1313,7 +1446,7 @@ int size_line_log(TardisMcContext *ctx, const PropagateCall &call, const WaveCho
         if (m.known) log_capacity = std::min<long long>(log_capacity, (long long)(LOG_MEMORY_SHARE * m.avail / log_bytes_per_record(s.one_set ? 1 : 2, partition)));
     }
     unsigned long long cap = std::min<unsigned long long>((unsigned long long)log_capacity,
-                                                          (unsigned long long)((double)n * ctx->log_budget_per_packet) + 64ull * (unsigned long long)waves + 65536ull);
+                                                          (unsigned long long)((double)n * ctx->wv.log_budget_per_packet) + 64ull * (unsigned long long)waves + 65536ull);
     if (w.n_bins > mc::EST_MAX_BINS) cap = 0;  // too many tiles for the LDS histogram: the kernel adds its terms directly
     cap = std::min<unsigned long long>(cap, 0xfffffff0ull);
     // The log is a pool of chunks the waves take one after the other (EstimatorLog, mc_device.hpp): chunks of up to 4096 records
@@ -1326,10 +1459,10 @@ int size_line_log(TardisMcContext *ctx, const PropagateCall &call, const WaveCho
         // 2048 records are what the partition kernel stages at a time.  A caller's own log_capacity (tests) is respected: with fewer chunks than that
         // the waves that find the pool empty suspend at once and the call takes more epochs)
         const unsigned long long per_wave = shell_log ? (unsigned long long)(ctx->n_shells + 4) : 4ull;
-        s.region_capacity = ctx->log_chunk_records > 0 ? (unsigned)ctx->log_chunk_records : (shell_log ? 2048u : 4096u);
+        s.region_capacity = ctx->wv.log_chunk_records > 0 ? (unsigned)ctx->wv.log_chunk_records : (shell_log ? 2048u : 4096u);
         while (s.region_capacity > 256 && (unsigned long long)s.region_capacity * per_wave * (unsigned long long)waves > cap) s.region_capacity >>= 1;
         s.region_capacity &= ~1u;  // even: a chunk of 24-byte records then starts on a 16-byte boundary (partition_kernel stages with 16-byte loads)
-        s.n_chunks = std::max<unsigned long long>(cap / s.region_capacity, (unsigned long long)waves * ((shell_log && !ctx->log_capacity_user) ? per_wave : 1ull));
+        s.n_chunks = std::max<unsigned long long>(cap / s.region_capacity, (unsigned long long)waves * ((shell_log && !ctx->wv.log_capacity_user) ? per_wave : 1ull));
         if (s.n_chunks * s.region_capacity > 0xfffffff0ull) s.n_chunks = 0xfffffff0ull / s.region_capacity;
     }
     // Memory check: the tables are resident (set_opacity), what is left must hold the smallest log this grid runs with -- one chunk of 256 records per wave,
@@ -1345,7 +1478,7 @@ int size_line_log(TardisMcContext *ctx, const PropagateCall &call, const WaveCho
     const unsigned long long n_chunks = s.n_chunks;
     // a second buffer set (the estimator passes of an epoch overlap the next epoch) only when the call may need several epochs
     // ... or splits off its drain (WaveCold::drain_split): worth a second launch once the call is long enough for a drain to form
-    s.want_split = ctx->drain_split && !vq && !s.one_set && region_capacity > 0 && n >= 64LL * waves * 4;
+    s.want_split = ctx->wv.drain_split && !vq && !s.one_set && region_capacity > 0 && n >= 64LL * waves * 4;
     // Tail split: the last epoch of a call should hold only the DRAIN (the ~4 % of the records the longest-lived packets log
     // after the packet supply has run out, on a mostly idle chip), so that the passes over everything before it run beside the
     // drain and only the passes of the tail -- milliseconds -- are left for after the call.  The host knows the call's records
@@ -1354,25 +1487,25 @@ int size_line_log(TardisMcContext *ctx, const PropagateCall &call, const WaveCho
     // were not overlapped with anything before).  A wrong estimate only moves the boundary.
     // (the tail: what the packets in flight when the supply runs out still log -- lanes x ~8 packets' worth of traces, the mean
     // residual life of a heavy-tailed population; only for calls whose passes are worth a second launch: >= 5e8 records)
-    s.tail_records = (double)ctx->log_tail_packets * ctx->traces_per_packet * 64.0 * (double)waves;
+    s.tail_records = (double)ctx->wv.log_tail_packets * ctx->wv.traces_per_packet * 64.0 * (double)waves;
     // Measured (profiles/r04_tail_split.txt): calls whose log fits one epoch -3 ... -5 % (1e7 - 2e7 packets: their passes ran
     // after the call before); calls of several epochs +0.5 % (their passes overlap the next epoch already, the extra launch
     // costs) -- so only the former.
-    const bool one_epoch = (double)region_capacity * (double)n_chunks >= (double)n * ctx->traces_per_packet * 1.05;
-    s.tail_plan = ctx->log_tail_split && !vq && !s.one_set && region_capacity > 0 && ctx->traces_per_packet > 0.0 && one_epoch &&
-                  (double)n * ctx->traces_per_packet >= 5e8 && (double)n * ctx->traces_per_packet > 2.0 * s.tail_records;
+    const bool one_epoch = (double)region_capacity * (double)n_chunks >= (double)n * ctx->wv.traces_per_packet * 1.05;
+    s.tail_plan = ctx->wv.log_tail_split && !vq && !s.one_set && region_capacity > 0 && ctx->wv.traces_per_packet > 0.0 && one_epoch &&
+                  (double)n * ctx->wv.traces_per_packet >= 5e8 && (double)n * ctx->wv.traces_per_packet > 2.0 * s.tail_records;
     // (the second buffer set is allocated as soon as a tail split MAY be planned -- the first call of a context has no estimate yet
     // -- so that no later call of the same size allocates tens of GB in the middle of an iteration)
-    s.tail_possible = ctx->log_tail_split && !vq && !s.one_set && region_capacity > 0 && (double)n * std::max(ctx->traces_per_packet, 16.0) >= 5e8;
+    s.tail_possible = ctx->wv.log_tail_split && !vq && !s.one_set && region_capacity > 0 && (double)n * std::max(ctx->wv.traces_per_packet, 16.0) >= 5e8;
     // ... or packs the drain's live lanes into fewer waves (drain_compact): the passes of the launch before run beside the packed drain
-    s.want_compact = ctx->drain_compact > 0 && !vq && !vpk && !cu_split && !shell_log && !s.one_set && region_capacity > 0 && n > 64LL * (waves - 1) && waves >= 8;
-    const bool several_epochs = region_capacity > 0 && (unsigned long long)region_capacity * n_chunks < (unsigned long long)((double)n * ctx->log_budget_per_packet);
+    s.want_compact = ctx->wv.drain_compact > 0 && !vq && !vpk && !cu_split && !shell_log && !s.one_set && region_capacity > 0 && n > 64LL * (waves - 1) && waves >= 8;
+    const bool several_epochs = region_capacity > 0 && (unsigned long long)region_capacity * n_chunks < (unsigned long long)((double)n * ctx->wv.log_budget_per_packet);
     s.n_sets = (s.one_set || vq) ? 1 : ((s.tail_plan || s.tail_possible || s.want_split || s.want_compact || several_epochs) ? 2 : 1);
     s.set_records = (size_t)std::max<unsigned long long>((unsigned long long)region_capacity * n_chunks, 1);
     // (a two-set call on a context whose first set was sized by a larger one-set call: both sets lie in the first set's buffers -- a second allocation of
     // tens of GB costs ~1 s the first time, the memory is cleared)
-    s.set1_inside = s.n_sets == 2 && !ctx->log_records[1].p && ctx->log_records[0].cap >= 2 * s.set_records * sizeof(mc::LineVisitRecord) &&
-                    ctx->log_keys[0].cap >= 2 * s.set_records * sizeof(unsigned) && (partition || ctx->log_sorted[0].cap >= 2 * s.set_records * sizeof(unsigned));
+    s.set1_inside = s.n_sets == 2 && !ctx->wv.log_records[1].p && ctx->wv.log_records[0].cap >= 2 * s.set_records * sizeof(mc::LineVisitRecord) &&
+                    ctx->wv.log_keys[0].cap >= 2 * s.set_records * sizeof(unsigned) && (partition || ctx->wv.log_sorted[0].cap >= 2 * s.set_records * sizeof(unsigned));
     return TARDIS_MC_OK;
 }
 
@@ -1434,7 +1567,7 @@ hipError_t estimator_passes(TardisMcContext *ctx, const WaveCall &E, const mc::E
     if (lg.region_capacity == 0) return hipSuccess;
     const int cus = E.call->cus, n_bins = E.w->n_bins;
     const bool full = E.call->full, shell_log = E.w->key.shell_log;
-    unsigned *bin_count = ctx->log_bins[b].as<unsigned>(), *bin_start = bin_count + (n_bins + 1),
+    unsigned *bin_count = ctx->wv.log_bins[b].as<unsigned>(), *bin_start = bin_count + (n_bins + 1),
              *bin_fill = bin_start + (n_bins + 1), *slice_start = bin_fill + (n_bins + 1);
     hipError_t e = hipMemsetAsync(bin_count, 0, (size_t)(n_bins + 1) * sizeof(unsigned), es);
     if (e != hipSuccess) return e;
@@ -1450,19 +1583,19 @@ hipError_t estimator_passes(TardisMcContext *ctx, const WaveCall &E, const mc::E
                        lg.region_capacity, n_bins, bin_count);
     hipLaunchKernelGGL(mc::bin_scan_kernel, dim3(1), dim3(256), 0, es, bin_count, n_bins, bin_start, bin_fill, slice_start);
     if (!E.w->partition) {  // index sort: the accumulate kernel gathers the records through the sorted index
-        unsigned *sorted = log_set_ptr<unsigned>(*E.log, ctx->log_sorted, b);
+        unsigned *sorted = log_set_ptr<unsigned>(*E.log, ctx->wv.log_sorted, b);
         hipLaunchKernelGGL(mc::bin_scatter_kernel, dim3(bin_blocks), dim3(256), hist_lds, es, lg.keys, lg.region_count, lg.n_regions,
                            lg.region_capacity, n_bins, bin_fill, sorted);
-        return launch_accumulate(full, false, ctx->est_accumulate, cus, es, lg.records, sorted, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, E.P.nu_line,
+        return launch_accumulate(full, false, ctx->wv.est_accumulate, cus, es, lg.records, sorted, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, E.P.nu_line,
                                  E.P.jblue_t, E.P.edot_t);
     }
     // estimator_partition.hpp: by shell into the scratch copy, by bin back into the set's own buffer
     unsigned *shell_fill = slice_start + (n_bins + 2);
-    mc::LineVisitRecord *scratch = ctx->log_part.as<mc::LineVisitRecord>();
+    mc::LineVisitRecord *scratch = ctx->wv.log_part.as<mc::LineVisitRecord>();
     auto bits_of = [](int n) { int b = 0; while ((1 << b) < n) ++b; return b; };
     const mc::LineVisitRecord *binned = lg.records;  // what the accumulate kernel reads
     const int part_blocks = cus * 2;
-    if (!shell_log && ctx->est_one_level != 0 && n_bins <= mc::PART_LOCAL_BUCKETS) {
+    if (!shell_log && ctx->wv.est_one_level != 0 && n_bins <= mc::PART_LOCAL_BUCKETS) {
         // few bins (short line lists: 300 on the tardis_example tables): ONE partition pass, log chunks -> scratch copy by bin.  (partition_kernel<2> with
         // "one shell of n_bins tiles": every chunk's first bucket is bin 0, a staged segment ranks over all bins)
         hipLaunchKernelGGL(mc::partition_kernel<2>, dim3(part_blocks), dim3(mc::PART_THREADS), 0, es, lg.records, lg.keys, lg.region_count, lg.n_regions,
@@ -1481,7 +1614,7 @@ hipError_t estimator_passes(TardisMcContext *ctx, const WaveCall &E, const mc::E
                            (const unsigned *)nullptr, 0, 0u, bin_start + n_bins, lg.tiles_per_shell, ctx->n_lines, bits_of(mc::PART_LOCAL_BUCKETS),
                            bin_fill, lg.records);
     }
-    return launch_accumulate(full, true, ctx->est_accumulate, cus, es, binned, nullptr, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, E.P.nu_line, E.P.jblue_t,
+    return launch_accumulate(full, true, ctx->wv.est_accumulate, cus, es, binned, nullptr, bin_start, slice_start, n_bins, lg.tiles_per_shell, ctx->n_lines, E.P.nu_line, E.P.jblue_t,
                              E.P.edot_t);
 }
 
@@ -1489,13 +1622,13 @@ hipError_t estimator_passes(TardisMcContext *ctx, const WaveCall &E, const mc::E
 hipError_t rs_copy_pending(TardisMcContext *ctx, WaveCall &E)
 {
     if (E.rs_pending_hi <= E.rs_pending_lo) return hipSuccess;
-    hipError_t e = hipStreamWaitEvent(ctx->rs_stream, ctx->rs_ev, 0);
+    hipError_t e = hipStreamWaitEvent(ctx->rs.stream, ctx->rs.ev, 0);
     void *dev[16];
     per_packet_device_arrays(ctx, dev);
     const size_t off = (size_t)E.rs_pending_lo * 8, bytes = (size_t)(E.rs_pending_hi - E.rs_pending_lo) * 8;
     for (int a = 0; a < 16 && e == hipSuccess; ++a)
-        if (ctx->rs.dst[a] && dev[a]) e = hipMemcpyAsync((char *)ctx->rs.dst[a] + off, (char *)dev[a] + off, bytes, hipMemcpyDeviceToHost, ctx->rs_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->rs_stream);
+        if (ctx->rs.dst[a] && dev[a]) e = hipMemcpyAsync((char *)ctx->rs.dst[a] + off, (char *)dev[a] + off, bytes, hipMemcpyDeviceToHost, ctx->rs.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->rs.stream);
     ctx->rs.upto = E.rs_pending_hi;
     E.rs_pending_lo = E.rs_pending_hi = 0;
     return e;
@@ -1505,22 +1638,22 @@ hipError_t rs_copy_pending(TardisMcContext *ctx, WaveCall &E)
 int fill_wave_cold(TardisMcContext *ctx, const WaveCall &E, int epoch, const mc::EstimatorLog &lg, mc::WaveCold *wc_dev)
 {
     const bool vq = E.vq, vpk = E.call->vpk;
-    mc::WaveCold &wc = ctx->wave_cold_host[epoch & 1];
+    mc::WaveCold &wc = ctx->wv.wave_cold_host[epoch & 1];
     wc.P = E.P; wc.D = ctx->problem_host; wc.log = lg; wc.seeded_states = E.cur_states;
     wc.chunk_first = 0; wc.chunk_count = E.n;
-    wc.launch = ctx->seed_chk.as<mc::LaunchRec>();
-    wc.vp_scratch = ctx->vp_scratch.as<mc::VpResult>();
-    wc.vp_park = (vpk && !E.vq_on && ctx->vp_carry_min_active > 0) ? ctx->vp_park.as<mc::VpPark>() : nullptr;
-    wc.vp_carry_min_active = ctx->vp_carry_min_active; wc.vp_pad = 0;
+    wc.launch = ctx->wv.seed_chk.as<mc::LaunchRec>();
+    wc.vp_scratch = ctx->wv.vp_scratch.as<mc::VpResult>();
+    wc.vp_park = (vpk && !E.vq_on && ctx->wv.vp_carry_min_active > 0) ? ctx->wv.vp_park.as<mc::VpPark>() : nullptr;
+    wc.vp_carry_min_active = ctx->wv.vp_carry_min_active; wc.vp_pad = 0;
     wc.save = E.may_suspend ? E.cur_save : nullptr;
     wc.wsave = E.may_suspend ? E.cur_wsave : nullptr;
     wc.resume = epoch > 0 ? 1 : 0;
-    wc.drain_split = E.split_armed ? 64 : (E.compact_armed ? ctx->drain_compact : 0);  // (the most live lanes a wave whose supply has run out suspends with)
-    wc.suspended = ctx->suspended_dev.as<unsigned>();
-    wc.vq_req = E.vq_on ? ctx->vq_req.as<mc::VolleyRequest>() : nullptr;
-    wc.vq_items = E.vq_on ? ctx->vq_items.as<unsigned>() : nullptr;
-    wc.vq_count = vq ? ctx->vq_count.as<unsigned>() : nullptr;
-    wc.vq_jsave = vq ? ctx->vq_jsave.as<double>() : nullptr;
+    wc.drain_split = E.split_armed ? 64 : (E.compact_armed ? ctx->wv.drain_compact : 0);  // (the most live lanes a wave whose supply has run out suspends with)
+    wc.suspended = ctx->wv.suspended_dev.as<unsigned>();
+    wc.vq_req = E.vq_on ? ctx->wv.vq_req.as<mc::VolleyRequest>() : nullptr;
+    wc.vq_items = E.vq_on ? ctx->wv.vq_items.as<unsigned>() : nullptr;
+    wc.vq_count = vq ? ctx->wv.vq_count.as<unsigned>() : nullptr;
+    wc.vq_jsave = vq ? ctx->wv.vq_jsave.as<double>() : nullptr;
     wc.log_continue = vq ? 1 : 0;
     wc.log_gen = E.log_gen;
     HIP_TRY(ctx, store_value(E.st, wc_dev, wc));
@@ -1530,20 +1663,20 @@ int fill_wave_cold(TardisMcContext *ctx, const WaveCall &E, int epoch, const mc:
 // Split launch (see epoch_split): the same epoch for waves [waves1, waves) on the passes' stream es, behind the estimator passes of the previous epoch
 int launch_second_half(TardisMcContext *ctx, WaveCall &E, int epoch, int waves1, hipStream_t es, mc::WaveCold *wc_dev)
 {
-    const mc::WaveCold &wc = ctx->wave_cold_host[epoch & 1];
+    const mc::WaveCold &wc = ctx->wv.wave_cold_host[epoch & 1];
     mc::WaveCold wc2 = wc;  // every per-wave array starts waves1 waves further on
     wc2.seeded_states = wc.seeded_states + (size_t)waves1 * 64 * mc::WV_STATE_STRIDE;
     if (wc.save) wc2.save = wc.save + (size_t)waves1 * 64;
     if (wc.wsave) wc2.wsave = wc.wsave + waves1;
     if (wc.vp_scratch) wc2.vp_scratch = wc.vp_scratch + (size_t)waves1 * 64 * mc::VP_ROUND;
     if (wc.vp_park) wc2.vp_park = wc.vp_park + (size_t)waves1 * 64;
-    HIP_TRY(ctx, hipStreamWaitEvent(es, ctx->ev_split[0], 0));
+    HIP_TRY(ctx, hipStreamWaitEvent(es, ctx->wv.ev_split[0], 0));
     HIP_TRY(ctx, store_value(es, wc_dev + 1, wc2));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_split[1], es));
+    HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_split[1], es));
     hipLaunchKernelGGL(E.w->fn, dim3(E.waves - waves1), dim3(64), E.w->lds, es, E.hot, (const mc::WaveCold *)(wc_dev + 1));
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_split[2], es));
-    HIP_TRY(ctx, hipStreamWaitEvent(E.st, ctx->ev_split[2], 0));  // (what follows on the engine's stream -- the read-back, the next epoch -- follows both)
+    HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_split[2], es));
+    HIP_TRY(ctx, hipStreamWaitEvent(E.st, ctx->wv.ev_split[2], 0));  // (what follows on the engine's stream -- the read-back, the next epoch -- follows both)
     E.split_w2 = (double)(E.waves - waves1) / (double)E.waves;
     return TARDIS_MC_OK;
 }
@@ -1557,20 +1690,20 @@ int wave_epoch_tail_volley_queue(TardisMcContext *ctx, WaveCall &E, const mc::Es
     float ms = 0.f;
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
     ctx->sum_prop_ms += ms;
-    const bool last = ctx->suspended_host[0] == 0;
-    if (last || ctx->suspended_host[1] > 0) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_post[0], E.st));
+    const bool last = ctx->wv.suspended_host[0] == 0;
+    if (last || ctx->wv.suspended_host[1] > 0) {
+        HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_post[0], E.st));
         HIP_TRY(ctx, estimator_passes(ctx, E, lg, 0, E.st));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_post[1], E.st));
+        HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_post[1], E.st));
         HIP_TRY(ctx, hipMemsetAsync(lg.region_count, 0, (size_t)(E.log->n_chunks + 1) * sizeof(unsigned), E.st));
         ++E.log_gen;
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_post[1]));
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_post[0], ctx->ev_post[1]));
+        HIP_TRY(ctx, hipEventSynchronize(ctx->wv.ev_post[1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->wv.ev_post[0], ctx->wv.ev_post[1]));
         ctx->sum_post_ms += ms;
     }
     if (last) { E.call_complete = true; return TARDIS_MC_OK; }
-    const long long vq_min_items = ctx->vq_min_items >= 0 ? ctx->vq_min_items : (long long)E.call->cus * 4 * 64 * 8;
-    if (E.vq_on && (long long)ctx->suspended_host[4] < vq_min_items) E.vq_on = false;
+    const long long vq_min_items = ctx->wv.vq_min_items >= 0 ? ctx->wv.vq_min_items : (long long)E.call->cus * 4 * 64 * 8;
+    if (E.vq_on && (long long)ctx->wv.suspended_host[4] < vq_min_items) E.vq_on = false;
     return TARDIS_MC_OK;
 }
 
@@ -1583,20 +1716,20 @@ int wave_epoch_tail_cu_partition(TardisMcContext *ctx, WaveCall &E, const mc::Es
     float pms = 0.f;
     HIP_TRY(ctx, hipEventElapsedTime(&pms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
     ctx->sum_prop_ms += pms;
-    const bool last = *ctx->suspended_host == 0;
-    hipStream_t ps = ctx->stream_pass_m;
+    const bool last = *ctx->wv.suspended_host == 0;
+    hipStream_t ps = ctx->wv.stream_pass_m;
     if (last) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream_pass_m));
-        HIP_TRY(ctx, hipStreamWaitEvent(E.st, ctx->ev_join, 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_join, ctx->wv.stream_pass_m));
+        HIP_TRY(ctx, hipStreamWaitEvent(E.st, ctx->wv.ev_join, 0));
         ps = E.st;
     } else HIP_TRY(ctx, hipStreamWaitEvent(ps, ctx->ev_chunk[3], 0));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b], ps));
+    HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_post[2 * b], ps));
     HIP_TRY(ctx, estimator_passes(ctx, E, lg, b, ps));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b + 1], ps));
-    ctx->post_pending[b] = true;
+    HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_post[2 * b + 1], ps));
+    ctx->wv.post_pending[b] = true;
     if (last) { E.call_complete = true; return TARDIS_MC_OK; }
-    E.records_done += (double)std::min<unsigned long long>((unsigned long long)ctx->suspended_host[6], E.pool_chunks) * (double)E.log->region_capacity;
-    if (ctx->suspended_host[2] > 0) E.split_armed = false;
+    E.records_done += (double)std::min<unsigned long long>((unsigned long long)ctx->wv.suspended_host[6], E.pool_chunks) * (double)E.log->region_capacity;
+    if (ctx->wv.suspended_host[2] > 0) E.split_armed = false;
     return TARDIS_MC_OK;
 }
 
@@ -1605,31 +1738,31 @@ int wave_epoch_tail_cu_partition(TardisMcContext *ctx, WaveCall &E, const mc::Es
 int compact_drain(TardisMcContext *ctx, WaveCall &E)
 {
     hipStream_t st = E.st;
-    unsigned *cen = ctx->drain_census.as<unsigned>();
+    unsigned *cen = ctx->wv.drain_census.as<unsigned>();
     HIP_TRY(ctx, hipMemsetAsync(cen, 0, 8 * sizeof(unsigned), st));
     hipLaunchKernelGGL(mc::drain_census_kernel, dim3(E.waves_cur), dim3(64), 0, st, E.cur_save, E.cur_wsave, E.waves_cur, E.n, cen);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host + 8, cen, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->wv.suspended_host + 8, cen, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    const unsigned live = ctx->suspended_host[8], reserved = ctx->suspended_host[9], waiting = ctx->suspended_host[11];
-    const unsigned density = (unsigned)ctx->drain_pack_lanes;
+    const unsigned live = ctx->wv.suspended_host[8], reserved = ctx->wv.suspended_host[9], waiting = ctx->wv.suspended_host[11];
+    const unsigned density = (unsigned)ctx->wv.drain_pack_lanes;
     const int packed = (int)((live + density - 1u) / density);
     if (!(reserved == 0 && waiting == 0 && live > 0 && 2 * packed <= E.waves_cur)) return TARDIS_MC_OK;
-    const int g = ctx->compactions & 1;
-    HIP_TRY(ctx, ctx->lane_save_c[g].ensure((size_t)packed * 64 * sizeof(mc::LaneSave)));
-    HIP_TRY(ctx, ctx->wave_save_c[g].ensure((size_t)packed * sizeof(mc::WaveSave)));
-    HIP_TRY(ctx, ctx->seeded_states_c[g].ensure((size_t)packed * 64 * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
+    const int g = ctx->wv.compactions & 1;
+    HIP_TRY(ctx, ctx->wv.lane_save_c[g].ensure((size_t)packed * 64 * sizeof(mc::LaneSave)));
+    HIP_TRY(ctx, ctx->wv.wave_save_c[g].ensure((size_t)packed * sizeof(mc::WaveSave)));
+    HIP_TRY(ctx, ctx->wv.seeded_states_c[g].ensure((size_t)packed * 64 * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
     HIP_TRY(ctx, hipMemsetAsync(cen + 4, 0, sizeof(unsigned), st));
     hipLaunchKernelGGL(mc::drain_compact_kernel, dim3(E.waves_cur), dim3(64), 0, st, (const mc::LaneSave *)E.cur_save, (const mc::WaveSave *)E.cur_wsave,
-                       (const uint32_t *)E.cur_states, E.waves_cur, ctx->lane_save_c[g].as<mc::LaneSave>(), ctx->seeded_states_c[g].as<uint32_t>(), cen + 4, density);
+                       (const uint32_t *)E.cur_states, E.waves_cur, ctx->wv.lane_save_c[g].as<mc::LaneSave>(), ctx->wv.seeded_states_c[g].as<uint32_t>(), cen + 4, density);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(mc::drain_compact_finish_kernel, dim3((unsigned)((packed * 64 + 255) / 256)), dim3(256), 0, st, ctx->lane_save_c[g].as<mc::LaneSave>(),
-                       ctx->wave_save_c[g].as<mc::WaveSave>(), (const unsigned *)(cen + 4), E.n, density);
+    hipLaunchKernelGGL(mc::drain_compact_finish_kernel, dim3((unsigned)((packed * 64 + 255) / 256)), dim3(256), 0, st, ctx->wv.lane_save_c[g].as<mc::LaneSave>(),
+                       ctx->wv.wave_save_c[g].as<mc::WaveSave>(), (const unsigned *)(cen + 4), E.n, density);
     HIP_TRY(ctx, hipGetLastError());
-    E.cur_save = ctx->lane_save_c[g].as<mc::LaneSave>(); E.cur_wsave = ctx->wave_save_c[g].as<mc::WaveSave>(); E.cur_states = ctx->seeded_states_c[g].as<uint32_t>();
+    E.cur_save = ctx->wv.lane_save_c[g].as<mc::LaneSave>(); E.cur_wsave = ctx->wv.wave_save_c[g].as<mc::WaveSave>(); E.cur_states = ctx->wv.seeded_states_c[g].as<uint32_t>();
     E.waves_cur = packed;
-    ctx->compactions += 1;
-    if (packed < 2 * E.call->cus || (int)density <= 2 * ctx->drain_compact) E.compact_armed = false;  // (nothing left worth freeing / the packed waves would suspend again at once)
+    ctx->wv.compactions += 1;
+    if (packed < 2 * E.call->cus || (int)density <= 2 * ctx->wv.drain_compact) E.compact_armed = false;  // (nothing left worth freeing / the packed waves would suspend again at once)
     return TARDIS_MC_OK;
 }
 
@@ -1637,17 +1770,17 @@ int compact_drain(TardisMcContext *ctx, WaveCall &E)
 // list, the range [upto, handed) is unpacked now -- in front of the next launch on the same stream -- and copied by the host beside that launch
 int stream_range(TardisMcContext *ctx, WaveCall &E)
 {
-    const long long handed = (long long)std::min<unsigned long long>(*ctx->rs_next_host, (unsigned long long)E.n);
-    if (handed - ctx->rs.upto < ctx->rs_min_packets) return TARDIS_MC_OK;
+    const long long handed = (long long)std::min<unsigned long long>(*ctx->rs.next_host, (unsigned long long)E.n);
+    if (handed - ctx->rs.upto < ctx->rs.min_packets) return TARDIS_MC_OK;
     hipLaunchKernelGGL(mc::late_list_kernel, dim3(E.waves_cur), dim3(64), 0, E.st, (const mc::LaneSave *)E.cur_save, (const mc::WaveSave *)E.cur_wsave, E.waves_cur, ctx->rs.upto, handed,
-                       ctx->rs_late.as<unsigned>(), ctx->rs_late_count.as<unsigned>(), ctx->rs.late_capacity);
+                       ctx->rs.late.as<unsigned>(), ctx->rs.late_count.as<unsigned>(), ctx->rs.late_capacity);
     HIP_TRY(ctx, hipGetLastError());
-    if (ctx->track) {
+    if (ctx->pk.track) {
         const long long cnt = handed - ctx->rs.upto;
         hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, E.st, ctx->problem_host, ctx->rs.upto, cnt, (const unsigned *)nullptr);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->rs_ev, E.st));
+    HIP_TRY(ctx, hipEventRecord(ctx->rs.ev, E.st));
     E.rs_pending_lo = ctx->rs.upto; E.rs_pending_hi = handed;
     return TARDIS_MC_OK;
 }
@@ -1657,24 +1790,24 @@ int stream_range(TardisMcContext *ctx, WaveCall &E)
 int gather_late_results(TardisMcContext *ctx, long long *unpack_from)
 {
     unsigned n_late = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n_late, ctx->rs_late_count.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&n_late, ctx->rs.late_count.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (n_late > ctx->rs.late_capacity) return TARDIS_MC_OK;  // (the list overflowed -- get_results copies everything)
     ctx->rs.valid = true;
     ctx->rs.n_late = n_late;
     *unpack_from = ctx->rs.upto;
     if (n_late == 0) return TARDIS_MC_OK;
-    if (ctx->track) {
-        hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((n_late + 255) / 256), dim3(256), 0, ctx->stream, ctx->problem_host, 0LL, (long long)n_late, ctx->rs_late.as<unsigned>());
+    if (ctx->pk.track) {
+        hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((n_late + 255) / 256), dim3(256), 0, ctx->stream, ctx->problem_host, 0LL, (long long)n_late, ctx->rs.late.as<unsigned>());
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, ctx->rs_vals.ensure((size_t)16 * n_late * 8));
+    HIP_TRY(ctx, ctx->rs.vals.ensure((size_t)16 * n_late * 8));
     void *dev[16];
     per_packet_device_arrays(ctx, dev);
     for (int a = 0; a < 16; ++a)
         if (ctx->rs.dst[a] && dev[a]) {
             hipLaunchKernelGGL(mc::gather64_kernel, dim3((n_late + 255) / 256), dim3(256), 0, ctx->stream, (const unsigned long long *)dev[a],
-                               ctx->rs_late.as<unsigned>(), (long long)n_late, ctx->rs_vals.as<unsigned long long>() + (size_t)a * n_late);
+                               ctx->rs.late.as<unsigned>(), (long long)n_late, ctx->rs.vals.as<unsigned long long>() + (size_t)a * n_late);
             HIP_TRY(ctx, hipGetLastError());
         }
     return TARDIS_MC_OK;
@@ -1689,21 +1822,21 @@ int run_wave_epoch(TardisMcContext *ctx, WaveCall &E, int epoch)
     const bool vq = E.vq;
     hipStream_t st = E.st;
     const int b = s.n_sets == 2 ? (epoch & 1) : 0;
-    hipStream_t es = s.n_sets == 2 ? ctx->stream2 : st;  // the estimator passes of an epoch run beside the next epoch
-    if (ctx->post_pending[b]) {  // this buffer set was used two epochs ago: its estimator passes must be over
+    hipStream_t es = s.n_sets == 2 ? ctx->wv.stream2 : st;  // the estimator passes of an epoch run beside the next epoch
+    if (ctx->wv.post_pending[b]) {  // this buffer set was used two epochs ago: its estimator passes must be over
         float ms = 0.f;
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_post[2 * b + 1]));
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_post[2 * b], ctx->ev_post[2 * b + 1]));
+        HIP_TRY(ctx, hipEventSynchronize(ctx->wv.ev_post[2 * b + 1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->wv.ev_post[2 * b], ctx->wv.ev_post[2 * b + 1]));
         ctx->sum_post_ms += ms;
-        ctx->post_pending[b] = false;
+        ctx->wv.post_pending[b] = false;
     }
     mc::EstimatorLog lg{};
     lg.tiles_per_shell = E.w->tiles;
-    lg.records = log_set_ptr<mc::LineVisitRecord>(s, ctx->log_records, b);
-    lg.keys = log_set_ptr<unsigned>(s, ctx->log_keys, b);
+    lg.records = log_set_ptr<mc::LineVisitRecord>(s, ctx->wv.log_records, b);
+    lg.keys = log_set_ptr<unsigned>(s, ctx->wv.log_keys, b);
     E.pool_chunks = s.n_chunks;
     if (s.tail_plan) {
-        const double records_est = (double)E.n * ctx->traces_per_packet;  // (what the call will log, by the last call's measure)
+        const double records_est = (double)E.n * ctx->wv.traces_per_packet;  // (what the call will log, by the last call's measure)
         const double bulk = records_est - E.records_done - s.tail_records;  // what is left before the tail
         if (bulk > 0.0 && bulk <= (double)s.n_chunks * (double)s.region_capacity)
             E.pool_chunks = std::min<unsigned long long>(s.n_chunks, std::max<unsigned long long>((unsigned long long)waves * (E.w->key.shell_log ? (unsigned long long)(ctx->n_shells + 4) : 1ull),
@@ -1711,20 +1844,20 @@ int run_wave_epoch(TardisMcContext *ctx, WaveCall &E, int epoch)
     }
     lg.n_regions = (int)E.pool_chunks;
     lg.region_capacity = s.region_capacity;
-    lg.region_count = ctx->log_cursor[b].as<unsigned>();
+    lg.region_count = ctx->wv.log_cursor[b].as<unsigned>();
     lg.pool_next = lg.region_count + s.n_chunks;
     // (volley queue: the launches of a call go on appending to the same log regions until one of them is full)
     if (!vq || epoch == 0) HIP_TRY(ctx, hipMemsetAsync(lg.region_count, 0, (size_t)(s.n_chunks + 1) * sizeof(unsigned), st));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->suspended_dev.p, 0, 4 * sizeof(unsigned), st));
-    if (vq) HIP_TRY(ctx, hipMemsetAsync(ctx->vq_count.p, 0, 2 * sizeof(unsigned), st));
-    mc::WaveCold *wc_dev = ctx->wave_cold_dev.as<mc::WaveCold>() + 2 * (epoch & 1);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->wv.suspended_dev.p, 0, 4 * sizeof(unsigned), st));
+    if (vq) HIP_TRY(ctx, hipMemsetAsync(ctx->wv.vq_count.p, 0, 2 * sizeof(unsigned), st));
+    mc::WaveCold *wc_dev = ctx->wv.wave_cold_dev.as<mc::WaveCold>() + 2 * (epoch & 1);
     int rc = fill_wave_cold(ctx, E, epoch, lg, wc_dev);
     if (rc) return rc;
     // split launch (see epoch_split): the estimator passes of the previous epoch are queued (or running) on the second stream
     // (not the drain launch of a tail-split call: its lanes are the call's critical path, half of them would start behind the bulk's passes)
-    const bool split = ctx->epoch_split && !s.want_compact && !vq && !E.cu_masked && !s.tail_plan && s.n_sets == 2 && epoch > 0 && es != st && ctx->post_pending[b ^ 1] && waves >= 8 * cus;
+    const bool split = ctx->wv.epoch_split && !s.want_compact && !vq && !E.cu_masked && !s.tail_plan && s.n_sets == 2 && epoch > 0 && es != st && ctx->wv.post_pending[b ^ 1] && waves >= 8 * cus;
     const int waves1 = split ? waves / 2 : E.waves_cur;
-    if (split) HIP_TRY(ctx, hipEventRecord(ctx->ev_split[0], st));  // (pool, counters and argument block of this epoch are in place)
+    if (split) HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_split[0], st));  // (pool, counters and argument block of this epoch are in place)
     HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[2], st));
     hipLaunchKernelGGL(E.w->fn, dim3(waves1), dim3(64), E.w->lds, st, E.hot, (const mc::WaveCold *)wc_dev);
     HIP_TRY(ctx, hipGetLastError());
@@ -1732,28 +1865,28 @@ int run_wave_epoch(TardisMcContext *ctx, WaveCall &E, int epoch)
     if (split && (rc = launch_second_half(ctx, E, epoch, waves1, es, wc_dev))) return rc;
     if (E.vq_on) {  // the v-packets this launch requested (the item count is read on the device: an empty list costs a launch)
         const size_t geo_lds = (size_t)4 * (size_t)ctx->n_shells * sizeof(double);
-        const int tracer_waves = cus * 4 * ctx->vq_tracer_waves_per_simd;
+        const int tracer_waves = cus * 4 * ctx->wv.vq_tracer_waves_per_simd;
         if (E.call->full) hipLaunchKernelGGL(mc::vpacket_trace_kernel<true>, dim3(tracer_waves), dim3(64), geo_lds, st, (const mc::WaveCold *)wc_dev);
         else hipLaunchKernelGGL(mc::vpacket_trace_kernel<false>, dim3(tracer_waves), dim3(64), geo_lds, st, (const mc::WaveCold *)wc_dev);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[3], st));
     if (E.may_suspend) {  // (read back before the estimator passes are queued: the host learns early whether another epoch follows)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host, ctx->suspended_dev.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        if (vq) HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host + 4, ctx->vq_count.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        if (s.region_capacity > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->suspended_host + 6, lg.pool_next, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        if (E.streaming) HIP_TRY(ctx, hipMemcpyAsync(ctx->rs_next_host, ctx->next_packet.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->wv.suspended_host, ctx->wv.suspended_dev.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        if (vq) HIP_TRY(ctx, hipMemcpyAsync(ctx->wv.suspended_host + 4, ctx->wv.vq_count.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        if (s.region_capacity > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->wv.suspended_host + 6, lg.pool_next, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        if (E.streaming) HIP_TRY(ctx, hipMemcpyAsync(ctx->rs.next_host, ctx->next_packet.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4], st));
     }
     ctx->launches += 1;
     if (vq) return wave_epoch_tail_volley_queue(ctx, E, lg);
     if (E.cu_masked) return wave_epoch_tail_cu_partition(ctx, E, lg, b);
     if (es != st) HIP_TRY(ctx, hipStreamWaitEvent(es, ctx->ev_chunk[3], 0));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b], es));
+    HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_post[2 * b], es));
     HIP_TRY(ctx, estimator_passes(ctx, E, lg, b, es));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_post[2 * b + 1], es));
-    ctx->post_pending[b] = true;
-    ctx->prop_pending = true;
+    HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_post[2 * b + 1], es));
+    ctx->wv.post_pending[b] = true;
+    ctx->wv.prop_pending = true;
     if (!E.may_suspend) { E.call_complete = true; return TARDIS_MC_OK; }  // (no log: the kernel adds its terms directly and never suspends; the call stays asynchronous)
     // (result streaming: the range unpacked before this launch is copied to the caller's arrays now, while the launch runs)
     if (E.streaming) HIP_TRY(ctx, rs_copy_pending(ctx, E));
@@ -1763,15 +1896,15 @@ int run_wave_epoch(TardisMcContext *ctx, WaveCall &E, int epoch)
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
     if (E.split_w2 > 0.0) {  // a split epoch counts with the wave-weighted duration of its two launches (= the time a launch of the whole grid stands for)
         float ms2 = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms2, ctx->ev_split[1], ctx->ev_split[2]));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms2, ctx->wv.ev_split[1], ctx->wv.ev_split[2]));
         ms = (float)((1.0 - E.split_w2) * (double)ms + E.split_w2 * (double)ms2);
     }
     ctx->sum_prop_ms += ms;
-    ctx->prop_pending = false;
-    if (*ctx->suspended_host == 0) { E.call_complete = true; return TARDIS_MC_OK; }
-    E.records_done += (double)std::min<unsigned long long>((unsigned long long)ctx->suspended_host[6], E.pool_chunks) * (double)s.region_capacity;
-    if (ctx->suspended_host[2] > 0) E.split_armed = false;  // (the drain has been split off: the next launch runs to the end)
-    if (E.compact_armed && ctx->suspended_host[2] > 0 && (rc = compact_drain(ctx, E))) return rc;
+    ctx->wv.prop_pending = false;
+    if (*ctx->wv.suspended_host == 0) { E.call_complete = true; return TARDIS_MC_OK; }
+    E.records_done += (double)std::min<unsigned long long>((unsigned long long)ctx->wv.suspended_host[6], E.pool_chunks) * (double)s.region_capacity;
+    if (ctx->wv.suspended_host[2] > 0) E.split_armed = false;  // (the drain has been split off: the next launch runs to the end)
+    if (E.compact_armed && ctx->wv.suspended_host[2] > 0 && (rc = compact_drain(ctx, E))) return rc;
     if (E.streaming) return stream_range(ctx, E);
     return TARDIS_MC_OK;
 }
@@ -1781,35 +1914,35 @@ int run_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P)
 {
     const bool vpk = call.vpk, full = call.full, vq = call.plan.variant == 4;
     const int cus = call.cus;
-    const long long n = ctx->n_packets;
+    const long long n = ctx->pk.n_packets;
     const mc::DeviceProblem &F = ctx->problem_host;
     if (n >= (1LL << 31)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "more than 2^31 packets per propagate call");
     WaveChoice w{};
     int rc = choose_wave_kernel(ctx, call, P, w);
     if (rc) return rc;
     if (w.compact_walk) {
-        P.cum16 = ctx->cum16.as<unsigned short>(); P.rec16 = ctx->rec16.as<mc::WalkRec>(); P.quad_info = ctx->quad_info.as<int2>();
-        P.cum16_stride = ctx->cum16_stride;
-        P.line_block = ctx->line_block_c.as<int2>();
-        P.hot_sec = ctx->have_hot ? ctx->hot_sec.as<unsigned>() : nullptr;
-        P.blk_tab = ctx->blk_tab.as<int2>();
+        P.cum16 = ctx->wt.cum16.as<unsigned short>(); P.rec16 = ctx->wt.rec16.as<mc::WalkRec>(); P.quad_info = ctx->wt.quad_info.as<int2>();
+        P.cum16_stride = ctx->wt.cum16_stride;
+        P.line_block = ctx->wt.line_block_c.as<int2>();
+        P.hot_sec = ctx->wt.have_hot ? ctx->wt.hot_sec.as<unsigned>() : nullptr;
+        P.blk_tab = ctx->wt.blk_tab.as<int2>();
         P.hot_stride = (unsigned)(16u * (unsigned)ctx->n_levels);
     }
-    ctx->progress_wave = true;  // (one packet supply for the whole call: next_packet counts the packets handed out)
+    ctx->pg.progress_wave = true;  // (one packet supply for the whole call: next_packet counts the packets handed out)
     // (volley queue: more waves than the chip holds at once -- a wave that suspends frees its slot, and the more packets are
     // in flight the more v-packets every tracer launch has to spread over its lanes)
     // CU partition (pass_cus): only for calls long enough to run as several epochs -- the passes of an epoch then have the next one to hide behind
     const int n_xcd = 8;  // gfx950: 8 XCDs x 32 CUs; the bits of a queue's CU mask are interleaved over the XCDs (bit k -> XCD k % 8)
-    const bool cu_split = ctx->pass_cus > 0 && !vq && ctx->log_sets != 1 && cus == 32 * n_xcd && n >= 30000000LL;
-    const int cus_prop = cu_split ? cus - n_xcd * ctx->pass_cus : cus;
-    const int waves = (int)std::max<long long>(1, std::min<long long>((n + 63) / 64, (long long)cus_prop * std::min(w.waves_per_cu, w.max_waves_per_cu) * (vq ? ctx->vq_oversubscribe : 1)));
-    if (ctx->track_full) {  // (a wave leaves a partly filled chunk behind at every launch it takes part in: room for four launches)
+    const bool cu_split = ctx->wv.pass_cus > 0 && !vq && ctx->wv.log_sets != 1 && cus == 32 * n_xcd && n >= 30000000LL;
+    const int cus_prop = cu_split ? cus - n_xcd * ctx->wv.pass_cus : cus;
+    const int waves = (int)std::max<long long>(1, std::min<long long>((n + 63) / 64, (long long)cus_prop * std::min(w.waves_per_cu, w.max_waves_per_cu) * (vq ? ctx->wv.vq_oversubscribe : 1)));
+    if (ctx->el.track_full) {  // (a wave leaves a partly filled chunk behind at every launch it takes part in: room for four launches)
         rc = setup_event_log(ctx, ctx->problem_host, 4LL * waves);
         if (rc) return rc;
     }
-    if (ctx->events_host && ctx->ev_events && hipEventQuery(ctx->ev_events) == hipSuccess && ctx->events_host[1] > 0)
-        ctx->traces_per_packet = (double)ctx->events_host[0] / (double)ctx->events_host[1];
-    if (1.1 * ctx->traces_per_packet > ctx->log_budget_per_packet) ctx->log_budget_per_packet = 1.3 * ctx->traces_per_packet;
+    if (ctx->wv.events_host && ctx->wv.ev_events && hipEventQuery(ctx->wv.ev_events) == hipSuccess && ctx->wv.events_host[1] > 0)
+        ctx->wv.traces_per_packet = (double)ctx->wv.events_host[0] / (double)ctx->wv.events_host[1];
+    if (1.1 * ctx->wv.traces_per_packet > ctx->wv.log_budget_per_packet) ctx->wv.log_budget_per_packet = 1.3 * ctx->wv.traces_per_packet;
     LogSizing s{};
     rc = size_line_log(ctx, call, w, n, waves, cu_split, s);
     if (rc) return rc;
@@ -1819,69 +1952,69 @@ int run_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P)
     E.split_armed = s.want_split && !s.want_compact;
     E.compact_armed = s.want_compact;
     E.waves_cur = waves;
-    ctx->compactions = 0;
+    ctx->wv.compactions = 0;
     for (int b = 0; b < s.n_sets; ++b) {
         if (!(s.set1_inside && b == 1)) {
-            HIP_TRY(ctx, ctx->log_records[b].ensure(s.set_records * sizeof(mc::LineVisitRecord)));
-            HIP_TRY(ctx, ctx->log_keys[b].ensure(s.set_records * sizeof(unsigned)));
-            if (!w.partition) HIP_TRY(ctx, ctx->log_sorted[b].ensure(s.set_records * sizeof(unsigned)));
+            HIP_TRY(ctx, ctx->wv.log_records[b].ensure(s.set_records * sizeof(mc::LineVisitRecord)));
+            HIP_TRY(ctx, ctx->wv.log_keys[b].ensure(s.set_records * sizeof(unsigned)));
+            if (!w.partition) HIP_TRY(ctx, ctx->wv.log_sorted[b].ensure(s.set_records * sizeof(unsigned)));
         }
-        HIP_TRY(ctx, ctx->log_bins[b].ensure((size_t)(4 * (w.n_bins + 2) + ctx->n_shells + 2) * sizeof(unsigned)));
-        HIP_TRY(ctx, ctx->log_cursor[b].ensure((size_t)(s.n_chunks + 2) * sizeof(unsigned)));  // chunk counts | pool counter
+        HIP_TRY(ctx, ctx->wv.log_bins[b].ensure((size_t)(4 * (w.n_bins + 2) + ctx->n_shells + 2) * sizeof(unsigned)));
+        HIP_TRY(ctx, ctx->wv.log_cursor[b].ensure((size_t)(s.n_chunks + 2) * sizeof(unsigned)));  // chunk counts | pool counter
     }
-    if (w.partition) HIP_TRY(ctx, ctx->log_part.ensure(s.set_records * sizeof(mc::LineVisitRecord)));
-    if (s.n_sets == 2 && !ctx->stream2) {
+    if (w.partition) HIP_TRY(ctx, ctx->wv.log_part.ensure(s.set_records * sizeof(mc::LineVisitRecord)));
+    if (s.n_sets == 2 && !ctx->wv.stream2) {
         int prio_lo = 0, prio_hi = 0;  // (the estimator passes' stream: highest priority, their workgroups are dispatched first)
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_hi));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+        HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->wv.stream2, hipStreamNonBlocking, prio_hi));
+        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->wv.ev_join, hipEventDisableTiming));
     }
     E.cu_masked = cu_split && s.n_sets == 2;
-    if (E.cu_masked && ctx->pass_cus_built != ctx->pass_cus) {
-        if (ctx->stream_prop_m) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_prop_m)); HIP_TRY(ctx, hipStreamDestroy(ctx->stream_prop_m)); ctx->stream_prop_m = nullptr; }
-        if (ctx->stream_pass_m) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream_pass_m)); HIP_TRY(ctx, hipStreamDestroy(ctx->stream_pass_m)); ctx->stream_pass_m = nullptr; }
+    if (E.cu_masked && ctx->wv.pass_cus_built != ctx->wv.pass_cus) {
+        if (ctx->wv.stream_prop_m) { HIP_TRY(ctx, hipStreamSynchronize(ctx->wv.stream_prop_m)); HIP_TRY(ctx, hipStreamDestroy(ctx->wv.stream_prop_m)); ctx->wv.stream_prop_m = nullptr; }
+        if (ctx->wv.stream_pass_m) { HIP_TRY(ctx, hipStreamSynchronize(ctx->wv.stream_pass_m)); HIP_TRY(ctx, hipStreamDestroy(ctx->wv.stream_pass_m)); ctx->wv.stream_pass_m = nullptr; }
         uint32_t m_prop[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m_pass[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int bit = 0; bit < cus; ++bit) {  // the first cus_prop bits = (32 - pass_cus) CUs of every XCD
             if (bit < cus_prop) m_prop[bit >> 5] |= 1u << (bit & 31);
             else m_pass[bit >> 5] |= 1u << (bit & 31);
         }
-        HIP_TRY(ctx, hipExtStreamCreateWithCUMask(&ctx->stream_prop_m, 8, m_prop));
-        HIP_TRY(ctx, hipExtStreamCreateWithCUMask(&ctx->stream_pass_m, 8, m_pass));
-        if (!ctx->ev_fork_m) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork_m, hipEventDisableTiming));
-        if (!ctx->ev_join_m) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join_m, hipEventDisableTiming));
-        ctx->pass_cus_built = ctx->pass_cus;
+        HIP_TRY(ctx, hipExtStreamCreateWithCUMask(&ctx->wv.stream_prop_m, 8, m_prop));
+        HIP_TRY(ctx, hipExtStreamCreateWithCUMask(&ctx->wv.stream_pass_m, 8, m_pass));
+        if (!ctx->wv.ev_fork_m) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->wv.ev_fork_m, hipEventDisableTiming));
+        if (!ctx->wv.ev_join_m) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->wv.ev_join_m, hipEventDisableTiming));
+        ctx->wv.pass_cus_built = ctx->wv.pass_cus;
     }
     for (int k = 0; k < 4; ++k)
-        if (!ctx->ev_post[k]) HIP_TRY(ctx, hipEventCreate(&ctx->ev_post[k]));
+        if (!ctx->wv.ev_post[k]) HIP_TRY(ctx, hipEventCreate(&ctx->wv.ev_post[k]));
     // ---- per-lane MT19937 state buffers, launch records, suspended lanes
-    HIP_TRY(ctx, ctx->seeded_states.ensure((size_t)waves * 64 * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
-    HIP_TRY(ctx, ctx->seed_chk.ensure((size_t)std::max<long long>(n, 1) * sizeof(mc::LaunchRec)));
-    HIP_TRY(ctx, ctx->lane_save.ensure((size_t)waves * 64 * sizeof(mc::LaneSave)));
-    HIP_TRY(ctx, ctx->wave_save.ensure((size_t)waves * sizeof(mc::WaveSave)));
-    HIP_TRY(ctx, ctx->suspended_dev.ensure(4 * sizeof(unsigned)));
-    E.cur_save = ctx->lane_save.as<mc::LaneSave>(); E.cur_wsave = ctx->wave_save.as<mc::WaveSave>(); E.cur_states = ctx->seeded_states.as<uint32_t>();
-    if (s.want_compact) HIP_TRY(ctx, ctx->drain_census.ensure(8 * sizeof(unsigned)));
-    if (!ctx->suspended_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->suspended_host, 16 * sizeof(unsigned), hipHostMallocDefault));
+    HIP_TRY(ctx, ctx->wv.seeded_states.ensure((size_t)waves * 64 * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
+    HIP_TRY(ctx, ctx->wv.seed_chk.ensure((size_t)std::max<long long>(n, 1) * sizeof(mc::LaunchRec)));
+    HIP_TRY(ctx, ctx->wv.lane_save.ensure((size_t)waves * 64 * sizeof(mc::LaneSave)));
+    HIP_TRY(ctx, ctx->wv.wave_save.ensure((size_t)waves * sizeof(mc::WaveSave)));
+    HIP_TRY(ctx, ctx->wv.suspended_dev.ensure(4 * sizeof(unsigned)));
+    E.cur_save = ctx->wv.lane_save.as<mc::LaneSave>(); E.cur_wsave = ctx->wv.wave_save.as<mc::WaveSave>(); E.cur_states = ctx->wv.seeded_states.as<uint32_t>();
+    if (s.want_compact) HIP_TRY(ctx, ctx->wv.drain_census.ensure(8 * sizeof(unsigned)));
+    if (!ctx->wv.suspended_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->wv.suspended_host, 16 * sizeof(unsigned), hipHostMallocDefault));
     if (vq) {
-        HIP_TRY(ctx, ctx->vq_req.ensure((size_t)waves * 64 * sizeof(mc::VolleyRequest)));
-        HIP_TRY(ctx, ctx->vq_items.ensure((size_t)waves * 64 * mc::VP_ROUND * sizeof(unsigned)));
-        HIP_TRY(ctx, ctx->vq_count.ensure(2 * sizeof(unsigned)));
-        HIP_TRY(ctx, ctx->vq_jsave.ensure((size_t)waves * 2 * (size_t)ctx->n_shells * sizeof(double)));
+        HIP_TRY(ctx, ctx->wv.vq_req.ensure((size_t)waves * 64 * sizeof(mc::VolleyRequest)));
+        HIP_TRY(ctx, ctx->wv.vq_items.ensure((size_t)waves * 64 * mc::VP_ROUND * sizeof(unsigned)));
+        HIP_TRY(ctx, ctx->wv.vq_count.ensure(2 * sizeof(unsigned)));
+        HIP_TRY(ctx, ctx->wv.vq_jsave.ensure((size_t)waves * 2 * (size_t)ctx->n_shells * sizeof(double)));
         if ((size_t)waves * 64 >= (1u << 29)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "too many lanes for the volley queue's item words");
     }
-    if (vpk) HIP_TRY(ctx, ctx->vp_scratch.ensure((size_t)waves * 64 * mc::VP_ROUND * sizeof(mc::VpResult)));
-    if (vpk && ctx->vp_carry_min_active > 0) HIP_TRY(ctx, ctx->vp_park.ensure((size_t)waves * 64 * sizeof(mc::VpPark)));
-    HIP_TRY(ctx, ctx->wave_cold_dev.ensure(4 * sizeof(mc::WaveCold)));  // (per epoch parity: the launch's block and the second launch's of a split epoch)
-    ctx->wave_cold_host.resize(2);
-    for (hipEvent_t &e : ctx->ev_split)
+    if (vpk) HIP_TRY(ctx, ctx->wv.vp_scratch.ensure((size_t)waves * 64 * mc::VP_ROUND * sizeof(mc::VpResult)));
+    if (vpk && ctx->wv.vp_carry_min_active > 0) HIP_TRY(ctx, ctx->wv.vp_park.ensure((size_t)waves * 64 * sizeof(mc::VpPark)));
+    HIP_TRY(ctx, ctx->wv.wave_cold_dev.ensure(4 * sizeof(mc::WaveCold)));  // (per epoch parity: the launch's block and the second launch's of a split epoch)
+    ctx->wv.wave_cold_host.resize(2);
+    for (hipEvent_t &e : ctx->wv.ev_split)
         if (!e) HIP_TRY(ctx, hipEventCreate(&e));
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, st));
-    if (call.tune_slot >= 0) HIP_TRY(ctx, hipEventRecord(ctx->ev_tune[0], st));
+    if (call.tune_slot >= 0) HIP_TRY(ctx, hipEventRecord(ctx->lt.ev_tune[0], st));
     if (E.cu_masked) {  // everything of this call runs on the masked stream from here on; it is joined to the engine's stream at the end
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_fork_m, ctx->stream));
-        st = ctx->stream_prop_m;
-        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_fork_m, 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_fork_m, ctx->stream));
+        st = ctx->wv.stream_prop_m;
+        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->wv.ev_fork_m, 0));
     }
     E.st = st;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[0], st));
@@ -1889,10 +2022,10 @@ int run_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P)
         // lazy seeding: only word 397 of every start state is precomputed; the refills continue the init_genrand chains
         mc::LaunchPrepArgs la{};
         la.r0 = F.r0; la.mu0 = F.mu0; la.nu0 = F.nu0; la.e0 = F.e0; la.nu_line = P.nu_line;
-        la.seeds = ctx->seeds.as<uint32_t>();
+        la.seeds = ctx->pk.seeds.as<uint32_t>();
         la.bucket_first = P.bucket_first; la.bucket_shift = P.bucket_shift; la.bucket_n = P.bucket_n; la.n_lines = P.n_lines;
         la.bucket_kmin = P.bucket_kmin; la.t_exp = P.t_exp;
-        la.out = ctx->seed_chk.as<mc::LaunchRec>(); la.first = 0; la.count = n;
+        la.out = ctx->wv.seed_chk.as<mc::LaunchRec>(); la.first = 0; la.count = n;
         if (full) hipLaunchKernelGGL(mc::launch_prep_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, la);
         else hipLaunchKernelGGL(mc::launch_prep_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, la);
         HIP_TRY(ctx, hipGetLastError());
@@ -1906,24 +2039,24 @@ int run_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P)
     // cut-offs of the sweep / walk phases (lanes still busy when the wave moves on): 8 / 8 by default.  Where most blocks are
     // entered through hot sectors the event phase is shorter and later cut-offs pay: 12 / 12 measured -2.5 % on the heavy-tailed
     // configs[2] tables, +2 % on the uniform ones (profiles/r04_cutoffs.txt) -- hence only there, and never against an option
-    const bool mostly_hot = ctx->have_hot && 2 * ctx->n_hot_blocks > (long long)ctx->n_levels;
-    hot.ls_min_active = (!ctx->ls_min_active_user && mostly_hot) ? 12 : ctx->ls_min_active;
-    hot.ls_max_steps = ctx->ls_max_steps;
-    hot.walk_min_active = (!ctx->walk_min_active_user && mostly_hot) ? 16 : ctx->walk_min_active;  // (12 until round 6; with the leaner sweep 16: -1.2 %, profiles/r06_cutoffs.txt)
-    hot.vq_min_active = ctx->vq_min_active;
+    const bool mostly_hot = ctx->wt.have_hot && 2 * ctx->wt.n_hot_blocks > (long long)ctx->n_levels;
+    hot.ls_min_active = (!ctx->wv.ls_min_active_user && mostly_hot) ? 12 : ctx->wv.ls_min_active;
+    hot.ls_max_steps = ctx->wv.ls_max_steps;
+    hot.walk_min_active = (!ctx->wv.walk_min_active_user && mostly_hot) ? 16 : ctx->wv.walk_min_active;  // (12 until round 6; with the leaner sweep 16: -1.2 %, profiles/r06_cutoffs.txt)
+    hot.vq_min_active = ctx->wv.vq_min_active;
     hot.line_block = P.line_interaction_type != 0 ? P.line_block : nullptr;
-    ctx->post_pending[0] = ctx->post_pending[1] = false;
-    ctx->prop_pending = false;
+    ctx->wv.post_pending[0] = ctx->wv.post_pending[1] = false;
+    ctx->wv.prop_pending = false;
     // result streaming: only the plain epoch loop (no volley queue, no CU partition), with the tracker unpacking it needs done per range
-    E.streaming = call.rs_armed && !vq && !E.cu_masked && E.may_suspend && n >= ctx->rs_min_packets;
+    E.streaming = call.rs_armed && !vq && !E.cu_masked && E.may_suspend && n >= ctx->rs.min_packets;
     if (E.streaming) {
         ctx->rs.late_capacity = (unsigned)std::min<long long>(n, (long long)waves * 64 * 16);
-        HIP_TRY(ctx, ctx->rs_late.ensure((size_t)ctx->rs.late_capacity * sizeof(unsigned)));
-        HIP_TRY(ctx, ctx->rs_late_count.ensure(sizeof(unsigned)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->rs_late_count.p, 0, sizeof(unsigned), st));
-        if (!ctx->rs_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->rs_stream, hipStreamNonBlocking));
-        if (!ctx->rs_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->rs_ev, hipEventDisableTiming));
-        if (!ctx->rs_next_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->rs_next_host, sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_TRY(ctx, ctx->rs.late.ensure((size_t)ctx->rs.late_capacity * sizeof(unsigned)));
+        HIP_TRY(ctx, ctx->rs.late_count.ensure(sizeof(unsigned)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->rs.late_count.p, 0, sizeof(unsigned), st));
+        if (!ctx->rs.stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->rs.stream, hipStreamNonBlocking));
+        if (!ctx->rs.ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->rs.ev, hipEventDisableTiming));
+        if (!ctx->rs.next_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->rs.next_host, sizeof(unsigned long long), hipHostMallocDefault));
     }
     const int max_epochs = 1 << 20;
     E.vq_on = vq;
@@ -1934,19 +2067,19 @@ int run_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P)
     if (!E.call_complete)  // (packets would be left suspended in lane_save, outputs and estimators silently incomplete)
         return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: %d launches did not finish the call (waves still suspended)", max_epochs);
     if (E.cu_masked) {  // both masked streams join the engine's stream
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream_pass_m));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_join_m, st));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join_m, 0));
-    } else if (s.n_sets == 2 && (ctx->post_pending[0] || ctx->post_pending[1])) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_join, ctx->wv.stream_pass_m));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->wv.ev_join, 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_join_m, st));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->wv.ev_join_m, 0));
+    } else if (s.n_sets == 2 && (ctx->wv.post_pending[0] || ctx->wv.post_pending[1])) {
+        HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_join, ctx->wv.stream2));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->wv.ev_join, 0));
     }
-    ctx->wave_epoch_mode = true;
-    ctx->progress_done = true;  // (every packet has been handed out and has ended: the host read "nothing suspended")
+    ctx->wv.wave_epoch_mode = true;
+    ctx->pg.progress_done = true;  // (every packet has been handed out and has ended: the host read "nothing suspended")
     long long unpack_from = 0;
     if (E.streaming && ctx->rs.upto > 0 && (rc = gather_late_results(ctx, &unpack_from))) return rc;
-    if (ctx->track && n > unpack_from) {  // the wave kernel's tracker records -> the boundary's arrays
+    if (ctx->pk.track && n > unpack_from) {  // the wave kernel's tracker records -> the boundary's arrays
         hipLaunchKernelGGL(mc::tracker_unpack_kernel, dim3((unsigned)((n - unpack_from + 255) / 256)), dim3(256), 0, ctx->stream, F, unpack_from, n - unpack_from,
                            (const unsigned *)nullptr);
         HIP_TRY(ctx, hipGetLastError());
@@ -1959,22 +2092,22 @@ int run_group_kernel(TardisMcContext *ctx, const PropagateCall &call, const mc::
 {
     const bool vpk = call.vpk;
     const int cus = call.cus;
-    ctx->wave_epoch_mode = false;
-    long long chunk = std::min<long long>(std::max<long long>(ctx->n_packets, 1), ctx->chunk_packets);
-    HIP_TRY(ctx, ctx->seeded_states.ensure((size_t)chunk * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
+    ctx->wv.wave_epoch_mode = false;
+    long long chunk = std::min<long long>(std::max<long long>(ctx->pk.n_packets, 1), ctx->chunk_packets);
+    HIP_TRY(ctx, ctx->wv.seeded_states.ensure((size_t)chunk * mc::WV_STATE_STRIDE * sizeof(uint32_t)));
     // group size: 8 lanes per packet pays off when the sweeps between events are short (sparse line lists)
     const int G = ctx->group_size == 8 ? 8 : (ctx->group_size == 16 ? 16 : ((ctx->n_lines <= 100000 && !vpk) ? 8 : 16));
     const int block = 256;
     const size_t lds = G == 8 ? mc::group_kernel_lds_bytes<8, 256>(ctx->n_shells) : mc::group_kernel_lds_bytes<16, 256>(ctx->n_shells);
     if (lds > 160 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
     const int blocks_per_cu = std::max(1, std::min(std::min(ctx->blocks_per_cu, 8), (int)((160 * 1024) / lds)));
-    const GroupKernelFn k = find_kernel(GROUP_KERNELS, GroupKernelKey{call.full, ctx->track, G, block, 4, vpk, call.plan.w64, vlog_li_call(ctx)});
+    const GroupKernelFn k = find_kernel(GROUP_KERNELS, GroupKernelKey{call.full, ctx->pk.track, G, block, 4, vpk, call.plan.w64, vlog_li_call(ctx)});
     if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the group kernel");
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, st));
-    uint32_t *seeded = ctx->seeded_states.as<uint32_t>();
-    for (long long first = 0; first < ctx->n_packets; first += chunk) {
-        const long long count = std::min(chunk, ctx->n_packets - first);
+    uint32_t *seeded = ctx->wv.seeded_states.as<uint32_t>();
+    for (long long first = 0; first < ctx->pk.n_packets; first += chunk) {
+        const long long count = std::min(chunk, ctx->pk.n_packets - first);
         const int ci = ctx->chunks_timed;
         while ((int)ctx->ev_chunk.size() < 4 * (ci + 1)) {
             hipEvent_t e;
@@ -1983,7 +2116,7 @@ int run_group_kernel(TardisMcContext *ctx, const PropagateCall &call, const mc::
         }
         HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci], st));
         hipLaunchKernelGGL(mc::seed_states_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st,
-                           ctx->seeds.as<uint32_t>(), seeded, first, count, mc::MT_N);
+                           ctx->pk.seeds.as<uint32_t>(), seeded, first, count, mc::MT_N);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemsetAsync(ctx->next_packet.p, 0, sizeof(unsigned long long), st));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_chunk[4 * ci + 1], st));
@@ -2017,17 +2150,17 @@ int run_cooperative(TardisMcContext *ctx, PropagateCall &call)
     P.t_exp = F.t_exp; P.sigma_thomson = F.sigma_thomson;
     P.tc = F.t_exp * mc::C_LIGHT; P.rcp_tc = 1.0 / P.tc;
     P.r_inner = F.r_inner; P.r_outer = F.r_outer; P.nu_line = F.nu_line; P.tau_t = F.tau_t; P.n_e = F.n_e; P.prob_t = F.prob_t;
-    P.line_block = ctx->line_block.as<int2>(); P.trans_rec = ctx->trans_rec.as<int4>();
-    P.cum_t = ctx->cum_t.as<double>(); P.trans_nu = ctx->trans_nu.as<double>();
+    P.line_block = ctx->ot.line_block.as<int2>(); P.trans_rec = ctx->ot.trans_rec.as<int4>();
+    P.cum_t = ctx->ot.cum_t.as<double>(); P.trans_nu = ctx->ot.trans_nu.as<double>();
     P.jblue_t = F.jblue_t; P.edot_t = F.edot_t; P.est_copy_stride = F.est_copy_stride;
     P.next_packet = F.next_packet;
     P.n_vpackets = F.n_vpackets; P.survival_probability = F.survival_probability; P.tau_russian = F.tau_russian;
     P.spawn_start = F.spawn_start; P.spawn_end = F.spawn_end; P.grid0 = F.grid0; P.grid_last = F.grid_last;
     P.delta_nu = F.delta_nu; P.vhist = F.vhist;
-    P.bucket_first = ctx->bucket_first.as<int>(); P.bucket_shift = ctx->bucket_shift; P.bucket_n = ctx->bucket_n;
-    P.bucket_kmin = ctx->bucket_kmin;
-    P.tau_pfx = call.plan.screen_on ? ctx->tau_pfx.as<double>() : nullptr;
-    P.tau_rowsum = call.plan.screen_on ? ctx->tau_rowsum.as<double>() : nullptr;
+    P.bucket_first = ctx->ot.bucket_first.as<int>(); P.bucket_shift = ctx->ot.bucket_shift; P.bucket_n = ctx->ot.bucket_n;
+    P.bucket_kmin = ctx->ot.bucket_kmin;
+    P.tau_pfx = call.plan.screen_on ? ctx->sc.tau_pfx.as<double>() : nullptr;
+    P.tau_rowsum = call.plan.screen_on ? ctx->sc.tau_rowsum.as<double>() : nullptr;
     while ((int)ctx->ev_chunk.size() < 8) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -2043,24 +2176,24 @@ int run_cooperative(TardisMcContext *ctx, PropagateCall &call)
 int run_lane_kernel(TardisMcContext *ctx, const PropagateCall &call)
 {
     // (the context is cached: the timing queries must not report the epochs of an earlier wave-kernel call)
-    ctx->wave_epoch_mode = false;
-    ctx->post_pending[0] = ctx->post_pending[1] = false;
-    ctx->prop_pending = false;
+    ctx->wv.wave_epoch_mode = false;
+    ctx->wv.post_pending[0] = ctx->wv.post_pending[1] = false;
+    ctx->wv.prop_pending = false;
     ctx->sum_seed_ms = ctx->sum_prop_ms = ctx->sum_post_ms = 0.0;
     ctx->launches = 0;
-    long long want_blocks = (ctx->n_packets + 255) / 256;
+    long long want_blocks = (ctx->pk.n_packets + 255) / 256;
     int blocks = (int)std::max<long long>(1, std::min<long long>(want_blocks, (long long)call.cus * ctx->blocks_per_cu));
     HIP_TRY(ctx, ctx->rng_state.ensure((size_t)blocks * 256 * mc::MT_N * sizeof(uint32_t)));
     mc::DeviceProblem P = make_device_problem(ctx);
     const size_t lds = 2 * (size_t)ctx->n_shells * sizeof(double);
-    if (lds + (ctx->track_full ? 32 : 0) > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
-    if (ctx->track_full) {
+    if (lds + (ctx->el.track_full ? 32 : 0) > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
+    if (ctx->el.track_full) {
         int rc = setup_event_log(ctx, P, (long long)blocks * 4);
         if (rc) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
     ctx->chunks_timed = 0;
-    return ctx->n_packets > 0 ? launch_lane(ctx, P, blocks, lds) : TARDIS_MC_OK;
+    return ctx->pk.n_packets > 0 ? launch_lane(ctx, P, blocks, lds) : TARDIS_MC_OK;
 }
 
 }  // namespace
@@ -2098,8 +2231,8 @@ int tardis_mc_create(int device_id, TardisMcContext **out_ctx)
     if (const char *v = getenv("TARDIS_MC_VARIANT")) ctx->variant = atoi(v);
     if (const char *v = getenv("TARDIS_MC_BLOCKS_PER_CU")) ctx->blocks_per_cu = std::max(1, atoi(v));
     if (const char *v = getenv("TARDIS_MC_DEBUG_FLAGS")) ctx->debug_flags = atoi(v);
-    if (const char *v = getenv("TARDIS_MC_EST_PIPELINE")) ctx->est_pipeline = atoi(v) ? 1 : 0;
-    if (const char *v = getenv("TARDIS_MC_EST_COPIES")) ctx->est_copies = std::max(1, std::min(8, atoi(v)));
+    if (const char *v = getenv("TARDIS_MC_EST_PIPELINE")) ctx->wv.est_pipeline = atoi(v) ? 1 : 0;
+    if (const char *v = getenv("TARDIS_MC_EST_COPIES")) ctx->es.est_copies = std::max(1, std::min(8, atoi(v)));
     *out_ctx = ctx;
     return TARDIS_MC_OK;
 }
@@ -2109,58 +2242,10 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
-    DevBuf *all[] = {&ctx->r_inner, &ctx->r_outer, &ctx->nu_line, &ctx->tau_t, &ctx->n_e, &ctx->prob_t, &ctx->cum_t, &ctx->trans_nu, &ctx->line2level,
-                     &ctx->block_edge, &ctx->ttype, &ctx->dest, &ctx->tline, &ctx->staging, &ctx->line_block, &ctx->trans_rec, &ctx->bucket_first, &ctx->est, &ctx->grid, &ctx->r0,
-                     &ctx->mu0, &ctx->nu0, &ctx->e0, &ctx->seeds, &ctx->out_nu, &ctx->out_e, &ctx->vlog_count,
-                     &ctx->vlog_packet, &ctx->vlog_seq, &ctx->vlog_nu, &ctx->vlog_energy, &ctx->vlog_mu, &ctx->vlog_r,
-                     &ctx->vl_counts, &ctx->vl_offsets, &ctx->vl_tiles, &ctx->vl_cols, &ctx->vl_errors,
-                     &ctx->dc_work, &ctx->rng_state, &ctx->counters, &ctx->first_error, &ctx->next_packet, &ctx->seeded_states, &ctx->problem_dev};
-    for (DevBuf *b : all) b->release();
-    for (int b = 0; b < 2; ++b) {
-        ctx->log_records[b].release(); ctx->log_keys[b].release(); ctx->log_cursor[b].release(); ctx->log_bins[b].release();
-        ctx->log_sorted[b].release();
-    }
-    ctx->log_part.release();
-    ctx->wave_cold_dev.release();
-    ctx->seed_chk.release(); ctx->vp_scratch.release(); ctx->vp_park.release();
-    for (auto &b : ctx->li_f64) b.release();
-    for (auto &b : ctx->li_i64) b.release();
-    ctx->li_rec.release();
-    ctx->cum16.release(); ctx->rec16.release(); ctx->quad_info.release(); ctx->line_block_c.release();
-    ctx->hot_sec.release(); ctx->hot_mass.release(); ctx->hot_flag.release(); ctx->blk_tab.release();
-    ctx->tau_pfx.release(); ctx->tau_rowsum.release(); ctx->pfx_flag.release(); ctx->nt_t.release();
-    ctx->lane_save.release(); ctx->wave_save.release(); ctx->suspended_dev.release();
-    for (int k = 0; k < 2; ++k) { ctx->lane_save_c[k].release(); ctx->wave_save_c[k].release(); ctx->seeded_states_c[k].release(); }
-    ctx->drain_census.release();
+    ctx->ot.release(); ctx->wt.release(); ctx->sc.release(); ctx->sw.release(); ctx->es.release(); ctx->pk.release(); ctx->vl.release(); ctx->el.release();
+    ctx->wv.release(); ctx->lt.release(); ctx->rs.release(); ctx->sf.release(); ctx->pg.release();
     ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release();
-    ctx->vq_req.release(); ctx->vq_items.release(); ctx->vq_count.release(); ctx->vq_jsave.release();
-    if (ctx->suspended_host) (void)hipHostFree(ctx->suspended_host);
-    for (hipEvent_t e : ctx->ev_post) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_chunk) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_tune) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_split) if (e) (void)hipEventDestroy(e);
-    if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
-    if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
-    if (ctx->events_host) (void)hipHostFree(ctx->events_host);
-    if (ctx->ev_events) (void)hipEventDestroy(ctx->ev_events);
-    ctx->rs_late.release(); ctx->rs_late_count.release(); ctx->rs_vals.release();
-    for (DevBuf *b : {&ctx->sf_lvl_ptr, &ctx->sf_lvl_line, &ctx->sf_in_ptr, &ctx->sf_in_row, &ctx->sf_in_src, &ctx->sf_emit_row, &ctx->sf_emit_level, &ctx->sf_exp_tau,
-                      &ctx->sf_e, &ctx->sf_x[0], &ctx->sf_x[1], &ctx->sf_q, &ctx->sf_shell, &ctx->sf_conv, &ctx->sf_wave, &ctx->sf_att, &ctx->sf_jred, &ctx->sf_jblue})
-        b->release();
-    if (ctx->sf_conv_host) (void)hipHostFree(ctx->sf_conv_host);
-    if (ctx->rs_stream) (void)hipStreamDestroy(ctx->rs_stream);
-    if (ctx->rs_ev) (void)hipEventDestroy(ctx->rs_ev);
-    if (ctx->rs_next_host) (void)hipHostFree(ctx->rs_next_host);
-    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-    if (ctx->stream_progress) (void)hipStreamDestroy(ctx->stream_progress);
-    if (ctx->ev_progress_reset) (void)hipEventDestroy(ctx->ev_progress_reset);
-    if (ctx->progress_host) (void)hipHostFree(ctx->progress_host);
-    if (ctx->stream_prop_m) (void)hipStreamDestroy(ctx->stream_prop_m);
-    if (ctx->stream_pass_m) (void)hipStreamDestroy(ctx->stream_pass_m);
-    if (ctx->ev_fork_m) (void)hipEventDestroy(ctx->ev_fork_m);
-    if (ctx->ev_join_m) (void)hipEventDestroy(ctx->ev_join_m);
-    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    ctx->release();
     delete ctx;
 }
 
@@ -2172,58 +2257,58 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     std::string n(name);
     if (n == "variant") ctx->variant = (int)value;
     else if (n == "blocks_per_cu") ctx->blocks_per_cu = std::max(1, (int)value);
-    else if (n == "track_last_interaction") ctx->track = value != 0;
-    else if (n == "estimator_copies") { ctx->est_copies = std::max(1, std::min(8, (int)value)); ctx->est_valid = false; }
-    else if (n == "vpacket_log_capacity") { ctx->vlog_capacity = value; ctx->vlog_capacity_user = value > 0; }
-    else if (n == "track_full") ctx->track_full = value != 0;
-    else if (n == "vpacket_last_interaction") ctx->vlog_li = value != 0;
-    else if (n == "event_log_capacity") ctx->evlog_capacity = std::max<long long>(0, value);
-    else if (n == "event_log_max_bytes") ctx->evlog_max_bytes = std::max<long long>(1LL << 20, value);
+    else if (n == "track_last_interaction") ctx->pk.track = value != 0;
+    else if (n == "estimator_copies") { ctx->es.est_copies = std::max(1, std::min(8, (int)value)); ctx->es.est_valid = false; }
+    else if (n == "vpacket_log_capacity") { ctx->vl.vlog_capacity = value; ctx->vl.vlog_capacity_user = value > 0; }
+    else if (n == "track_full") ctx->el.track_full = value != 0;
+    else if (n == "vpacket_last_interaction") ctx->vl.vlog_li = value != 0;
+    else if (n == "event_log_capacity") ctx->el.evlog_capacity = std::max<long long>(0, value);
+    else if (n == "event_log_max_bytes") ctx->el.evlog_max_bytes = std::max<long long>(1LL << 20, value);
     else if (n == "debug_flags") ctx->debug_flags = (int)value;
-    else if (n == "drain_split") ctx->drain_split = value ? 1 : 0;
-    else if (n == "drain_compact") ctx->drain_compact = (int)std::max<long long>(0, std::min<long long>(48, value));
-    else if (n == "est_one_level") ctx->est_one_level = value ? 1 : 0;
-    else if (n == "drain_pack_lanes") ctx->drain_pack_lanes = (int)std::max<long long>(1, std::min<long long>(64, value));
-    else if (n == "walk_sector_packing") ctx->walk_sector_packing = value ? 1 : 0;
-    else if (n == "walk_hot") ctx->walk_hot = value < 0 ? -1 : (value ? 1 : 0);  // (like walk_sector_packing: before set_opacity)
-    else if (n == "walk_hot_min_mass") ctx->walk_hot_min_mass = (int)std::max<long long>(0, std::min<long long>(value, 1001));
-    else if (n == "walk_hot_min_mass_long") ctx->walk_hot_min_mass_long = (int)std::max<long long>(0, std::min<long long>(value, 1001));
-    else if (n == "vpacket_screening") ctx->vpacket_screening = value < 0 ? -1 : (value ? 1 : 0);
+    else if (n == "drain_split") ctx->wv.drain_split = value ? 1 : 0;
+    else if (n == "drain_compact") ctx->wv.drain_compact = (int)std::max<long long>(0, std::min<long long>(48, value));
+    else if (n == "est_one_level") ctx->wv.est_one_level = value ? 1 : 0;
+    else if (n == "drain_pack_lanes") ctx->wv.drain_pack_lanes = (int)std::max<long long>(1, std::min<long long>(64, value));
+    else if (n == "walk_sector_packing") ctx->wt.walk_sector_packing = value ? 1 : 0;
+    else if (n == "walk_hot") ctx->wt.walk_hot = value < 0 ? -1 : (value ? 1 : 0);  // (like walk_sector_packing: before set_opacity)
+    else if (n == "walk_hot_min_mass") ctx->wt.walk_hot_min_mass = (int)std::max<long long>(0, std::min<long long>(value, 1001));
+    else if (n == "walk_hot_min_mass_long") ctx->wt.walk_hot_min_mass_long = (int)std::max<long long>(0, std::min<long long>(value, 1001));
+    else if (n == "vpacket_screening") ctx->sc.vpacket_screening = value < 0 ? -1 : (value ? 1 : 0);
     else if (n == "waves_per_simd") ctx->waves_per_simd = (int)value;
     else if (n == "lane_sweep_min_active") {  // (< 0: the automatic choice again)
-        ctx->ls_min_active_user = value >= 0;
-        ctx->ls_min_active = value >= 0 ? (int)std::min<long long>(value, 63) : 8;
+        ctx->wv.ls_min_active_user = value >= 0;
+        ctx->wv.ls_min_active = value >= 0 ? (int)std::min<long long>(value, 63) : 8;
     }
-    else if (n == "lane_sweep_max_steps") ctx->ls_max_steps = (int)std::max<long long>(1, value);
-    else if (n == "vq_oversubscribe") ctx->vq_oversubscribe = (int)std::max<long long>(1, std::min<long long>(value, 64));
-    else if (n == "vq_tracer_waves_per_simd") ctx->vq_tracer_waves_per_simd = (int)std::max<long long>(1, std::min<long long>(value, 16));
-    else if (n == "vq_min_items") ctx->vq_min_items = value;
-    else if (n == "vq_min_active") ctx->vq_min_active = (int)std::max<long long>(0, std::min<long long>(value, 63));
-    else if (n == "log_tail_split") ctx->log_tail_split = value ? 1 : 0;
-    else if (n == "est_pipeline") ctx->est_pipeline = value ? 1 : 0;
-    else if (n == "pass_cus") ctx->pass_cus = (int)std::max<long long>(0, std::min<long long>(value, 16));
+    else if (n == "lane_sweep_max_steps") ctx->wv.ls_max_steps = (int)std::max<long long>(1, value);
+    else if (n == "vq_oversubscribe") ctx->wv.vq_oversubscribe = (int)std::max<long long>(1, std::min<long long>(value, 64));
+    else if (n == "vq_tracer_waves_per_simd") ctx->wv.vq_tracer_waves_per_simd = (int)std::max<long long>(1, std::min<long long>(value, 16));
+    else if (n == "vq_min_items") ctx->wv.vq_min_items = value;
+    else if (n == "vq_min_active") ctx->wv.vq_min_active = (int)std::max<long long>(0, std::min<long long>(value, 63));
+    else if (n == "log_tail_split") ctx->wv.log_tail_split = value ? 1 : 0;
+    else if (n == "est_pipeline") ctx->wv.est_pipeline = value ? 1 : 0;
+    else if (n == "pass_cus") ctx->wv.pass_cus = (int)std::max<long long>(0, std::min<long long>(value, 16));
     else if (n == "vpk_wave_min_packets") ctx->vpk_wave_min_packets = std::max<long long>(0, value);
-    else if (n == "ls_waves_per_simd") { ctx->ls_waves_per_simd = (value == 3 || value == 4) ? (int)value : 0; ctx->ls_tune.n = -1; }
-    else if (n == "epoch_split") ctx->epoch_split = value ? 1 : 0;
-    else if (n == "log_by_shell") ctx->log_by_shell = value < 0 ? -1 : (value ? 1 : 0);
-    else if (n == "stream_min_packets") ctx->rs_min_packets = std::max<long long>(64, value);
-    else if (n == "sweep_table") ctx->sweep_table = (int)std::max<long long>(-1, std::min<long long>(value, 2));
+    else if (n == "ls_waves_per_simd") { ctx->lt.ls_waves_per_simd = (value == 3 || value == 4) ? (int)value : 0; ctx->lt.ls_tune.n = -1; }
+    else if (n == "epoch_split") ctx->wv.epoch_split = value ? 1 : 0;
+    else if (n == "log_by_shell") ctx->wv.log_by_shell = value < 0 ? -1 : (value ? 1 : 0);
+    else if (n == "stream_min_packets") ctx->rs.min_packets = std::max<long long>(64, value);
+    else if (n == "sweep_table") ctx->sw.sweep_table = (int)std::max<long long>(-1, std::min<long long>(value, 2));
     else if (n == "table_offsets") ctx->table_offsets = value < 0 ? -1 : (value ? 1 : 0);
     else if (n == "vpk_wide_registers") ctx->vpk_wide_registers = (int)std::max<long long>(0, std::min<long long>(value, 2));
-    else if (n == "bucket_lines_permille") ctx->bucket_lines_permille = (int)std::max<long long>(50, std::min<long long>(value, 16000));
-    else if (n == "vp_carry_min_active") ctx->vp_carry_min_active = (int)std::max<long long>(0, std::min<long long>(value, 63));
-    else if (n == "est_accumulate") ctx->est_accumulate = (int)std::max<long long>(0, std::min<long long>(value, 3));
-    else if (n == "log_tail_packets") ctx->log_tail_packets = (int)std::max<long long>(0, std::min<long long>(value, 1000));
-    else if (n == "log_chunk_records") ctx->log_chunk_records = value <= 0 ? 0 : std::max<long long>(256, std::min<long long>(value, 1 << 20));
+    else if (n == "bucket_lines_permille") ctx->ot.bucket_lines_permille = (int)std::max<long long>(50, std::min<long long>(value, 16000));
+    else if (n == "vp_carry_min_active") ctx->wv.vp_carry_min_active = (int)std::max<long long>(0, std::min<long long>(value, 63));
+    else if (n == "est_accumulate") ctx->wv.est_accumulate = (int)std::max<long long>(0, std::min<long long>(value, 3));
+    else if (n == "log_tail_packets") ctx->wv.log_tail_packets = (int)std::max<long long>(0, std::min<long long>(value, 1000));
+    else if (n == "log_chunk_records") ctx->wv.log_chunk_records = value <= 0 ? 0 : std::max<long long>(256, std::min<long long>(value, 1 << 20));
     else if (n == "walk_min_active") {  // (-1: never carry a walk over; < -1: the automatic choice again)
-        ctx->walk_min_active_user = value >= -1;
-        ctx->walk_min_active = value >= -1 ? (int)std::min<long long>(value, 63) : 8;
+        ctx->wv.walk_min_active_user = value >= -1;
+        ctx->wv.walk_min_active = value >= -1 ? (int)std::min<long long>(value, 63) : 8;
     }
     else if (n == "group_size") ctx->group_size = (value == 4 || value == 8 || value == 16) ? (int)value : 0;
     else if (n == "pipeline_chunks") {}  // (round 1: chunks on two streams; a call of the wave kernel now runs as epochs -- accepted, ignored)
-    else if (n == "log_capacity") { ctx->log_capacity = std::max<long long>(0, value); ctx->log_capacity_user = true; }
-    else if (n == "log_sets") ctx->log_sets = (value == 1 || value == 2) ? (int)value : 0;  // 1: the estimator passes of an epoch run before the next epoch, not beside it; 0: automatic
-    else if (n == "source_max_iterations") ctx->source_max_iterations = std::max<long long>(1, value);
+    else if (n == "log_capacity") { ctx->wv.log_capacity = std::max<long long>(0, value); ctx->wv.log_capacity_user = true; }
+    else if (n == "log_sets") ctx->wv.log_sets = (value == 1 || value == 2) ? (int)value : 0;  // 1: the estimator passes of an epoch run before the next epoch, not beside it; 0: automatic
+    else if (n == "source_max_iterations") ctx->sf.max_iterations = std::max<long long>(1, value);
     else if (n == "chunk_packets") ctx->chunk_packets = std::max<long long>(1024, value);
     else if (n == "opacity_update_long_rows") ctx->ou.long_rows = value < 0 ? -1 : value;
     else if (n == "plasma_update_long_rows") ctx->pl.long_rows = value < 0 ? -1 : value;
@@ -2238,7 +2323,7 @@ int tardis_mc_set_geometry(TardisMcContext *ctx, const TardisMcGeometry *g)
     if (!ctx || !g || g->n_shells <= 0 || !g->r_inner || !g->r_outer)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid geometry");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->sf_valid = false;
+    drop_products(ctx, GEOMETRY_REPLACED);
     int rc;
     if ((rc = upload(ctx, ctx->r_inner, g->r_inner, (size_t)g->n_shells))) return rc;
     if ((rc = upload(ctx, ctx->r_outer, g->r_outer, (size_t)g->n_shells))) return rc;
@@ -2255,38 +2340,34 @@ int tardis_mc_set_geometry(TardisMcContext *ctx, const TardisMcGeometry *g)
 // copies of the index tables and of the line list, not the caller's pointers.
 static int derive_opacity_tables(TardisMcContext *ctx, const size_t L, const size_t S, const size_t T, const std::function<void(const char *)> &tmark)
 {
-    const std::vector<int> &l2l = ctx->h_idx[0], &edge = ctx->h_idx[1], &ttype = ctx->h_idx[2], &dest = ctx->h_idx[3], &tline = ctx->h_idx[4];
-    const std::vector<double> &nu = ctx->h_nu;
-    const bool macro = ctx->h_macro;
+    const std::vector<int> &l2l = ctx->ot.h_idx[0], &edge = ctx->ot.h_idx[1], &ttype = ctx->ot.h_idx[2], &dest = ctx->ot.h_idx[3], &tline = ctx->ot.h_idx[4];
+    const std::vector<double> &nu = ctx->ot.h_nu;
+    const bool macro = ctx->ot.h_macro;
     const size_t E = macro ? edge.size() : 1;
     int rc;
-    ctx->sf_valid = ctx->sf_exp_valid = false;
+    drop_products(ctx, OPACITY_VALUES_REPLACED);
     {   // running sums of the transition probabilities within their blocks (macro_cumulative_kernel)
-        HIP_TRY(ctx, ctx->cum_t.ensure((T * S + 8) * sizeof(double)));  // (+8: the jump search reads eight entries at a time)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->cum_t.p, ctx->prob_t.p, T * S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        ctx->prob_negative = false;
+        HIP_TRY(ctx, ctx->ot.cum_t.ensure((T * S + 8) * sizeof(double)));  // (+8: the jump search reads eight entries at a time)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ot.cum_t.p, ctx->ot.prob_t.p, T * S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->ot.prob_negative = false;
         if (macro && E > 1) {
-            HIP_TRY(ctx, ctx->pfx_flag.ensure(sizeof(int)));  // (a flag word the context keeps: no hipMalloc / hipFree per opacity state)
-            int *flag = ctx->pfx_flag.as<int>();
+            HIP_TRY(ctx, ctx->sc.pfx_flag.ensure(sizeof(int)));  // (a flag word the context keeps: no hipMalloc / hipFree per opacity state)
+            int *flag = ctx->sc.pfx_flag.as<int>();
             HIP_TRY(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
             const long long n = (long long)(E - 1) * (long long)S;
-            hipLaunchKernelGGL(mc::macro_cumulative_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->prob_t.as<double>(),
-                               ctx->cum_t.as<double>(), ctx->block_edge.as<int>(), (int)(E - 1), (long long)T, (int)S, flag);
+            hipLaunchKernelGGL(mc::macro_cumulative_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ot.prob_t.as<double>(),
+                               ctx->ot.cum_t.as<double>(), ctx->ot.block_edge.as<int>(), (int)(E - 1), (long long)T, (int)S, flag);
             int neg = 0;
             hipError_t e1 = hipGetLastError();
             hipError_t e2 = hipMemcpyAsync(&neg, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
             hipError_t e3 = hipStreamSynchronize(ctx->stream);
             HIP_TRY(ctx, e1); HIP_TRY(ctx, e2); HIP_TRY(ctx, e3);
-            ctx->prob_negative = neg != 0;
+            ctx->ot.prob_negative = neg != 0;
         }
     }
     tmark("running sums");
-    ctx->have_walk_tables = false;
-    ctx->have_hot = false;
-    ctx->n_hot_blocks = 0;
-    ctx->pfx_valid = false;  // (the prefix sums of the new tau table are built by the first propagate call that traces v-packets)
-    ctx->nt_valid = false;   // (likewise the interleaved sweep table: by the first call that sweeps on it)
-    if (macro && E > 1 && !ctx->prob_negative) {
+    ctx->wt.n_hot_blocks = 0;
+    if (macro && E > 1 && !ctx->ot.prob_negative) {
         // compact tables of the per-lane macro-atom walk (walk_tables.hpp): blocks at 16-byte aligned compact offsets.  The walk is
         // bound by the number of memory requests, and a block's window of running sums is fetched in 64-byte sectors: a block of
         // up to 32 entries (one window) that would straddle a sector boundary starts at the next boundary instead (the skipped
@@ -2296,7 +2377,7 @@ static int derive_opacity_tables(TardisMcContext *ctx, const size_t L, const siz
         long long tc = 0;
         for (size_t b = 0; b < n_levels; ++b) {
             const long long len = (edge[b + 1] - edge[b] + 7) / 8 * 8;
-            if (ctx->walk_sector_packing && len > 0) {
+            if (ctx->wt.walk_sector_packing && len > 0) {
                 const long long in_sector = tc & 31;  // (32 entries of 2 bytes per 64-byte sector)
                 if (in_sector != 0 && (len > 32 || in_sector + len > 32)) tc += 32 - in_sector;
             }
@@ -2310,20 +2391,20 @@ static int derive_opacity_tables(TardisMcContext *ctx, const size_t L, const siz
             // hot sectors (walk_tables.hpp): measured on the device (total width of a block's six widest intervals, per shell),
             // chosen here (mean over the shells), then built once more with the destinations' flags in place
             std::vector<unsigned char> hot(n_levels, 0);
-            if (ctx->walk_hot != 0 && n_levels < (size_t)mc::WALK_HOT) {
+            if (ctx->wt.walk_hot != 0 && n_levels < (size_t)mc::WALK_HOT) {
                 const long long nb = (long long)n_levels * (long long)S;
-                HIP_TRY(ctx, ctx->hot_sec.ensure((size_t)nb * 64));
-                HIP_TRY(ctx, ctx->hot_mass.ensure((size_t)nb * sizeof(unsigned)));
-                HIP_TRY(ctx, ctx->hot_flag.ensure(n_levels));
+                HIP_TRY(ctx, ctx->wt.hot_sec.ensure((size_t)nb * 64));
+                HIP_TRY(ctx, ctx->wt.hot_mass.ensure((size_t)nb * sizeof(unsigned)));
+                HIP_TRY(ctx, ctx->wt.hot_flag.ensure(n_levels));
                 auto launch_hot = [&](const unsigned char *flags, unsigned *mass) {
-                    hipLaunchKernelGGL(mc::walk_hot_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cum_t.as<double>(),
-                                       ctx->block_edge.as<int>(), ctx->ttype.as<int>(), ctx->dest.as<int>(), ctx->tline.as<int>(), flags,
-                                       (int)n_levels, (long long)T, (int)S, ctx->hot_sec.as<unsigned>(), mass);
+                    hipLaunchKernelGGL(mc::walk_hot_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ot.cum_t.as<double>(),
+                                       ctx->ot.block_edge.as<int>(), ctx->ot.ttype.as<int>(), ctx->ot.dest.as<int>(), ctx->ot.tline.as<int>(), flags,
+                                       (int)n_levels, (long long)T, (int)S, ctx->wt.hot_sec.as<unsigned>(), mass);
                     return hipGetLastError();
                 };
-                HIP_TRY(ctx, launch_hot(nullptr, ctx->hot_mass.as<unsigned>()));
+                HIP_TRY(ctx, launch_hot(nullptr, ctx->wt.hot_mass.as<unsigned>()));
                 std::vector<unsigned> mass((size_t)nb);
-                HIP_TRY(ctx, hipMemcpyAsync(mass.data(), ctx->hot_mass.p, (size_t)nb * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(mass.data(), ctx->wt.hot_mass.p, (size_t)nb * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
                 for (size_t b = 0; b < n_levels; ++b) {
                     const long long rows = edge[b + 1] - edge[b];
@@ -2331,21 +2412,21 @@ static int derive_opacity_tables(TardisMcContext *ctx, const size_t L, const siz
                     double m = 0.0;
                     for (size_t sh = 0; sh < S; ++sh) m += (double)mass[sh * n_levels + b];
                     m /= 65536.0 * (double)S;
-                    const double need = 1e-3 * (double)(rows > 8 * mc::WALK_WINDOW_QUADS ? ctx->walk_hot_min_mass_long : ctx->walk_hot_min_mass);
-                    if (ctx->walk_hot == 1 || m >= need) { hot[b] = 1; ctx->n_hot_blocks += 1; }
+                    const double need = 1e-3 * (double)(rows > 8 * mc::WALK_WINDOW_QUADS ? ctx->wt.walk_hot_min_mass_long : ctx->wt.walk_hot_min_mass);
+                    if (ctx->wt.walk_hot == 1 || m >= need) { hot[b] = 1; ctx->wt.n_hot_blocks += 1; }
                 }
-                if (ctx->n_hot_blocks > 0) {
-                    HIP_TRY(ctx, hipMemcpyAsync(ctx->hot_flag.p, hot.data(), n_levels, hipMemcpyHostToDevice, ctx->stream));
-                    hipLaunchKernelGGL(mc::walk_hot_flag_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, ctx->hot_flag.as<unsigned char>(), nb,
-                                       ctx->hot_sec.as<unsigned>());  // (the destinations of the first pass's records, marked; no second walk over the blocks)
+                if (ctx->wt.n_hot_blocks > 0) {
+                    HIP_TRY(ctx, hipMemcpyAsync(ctx->wt.hot_flag.p, hot.data(), n_levels, hipMemcpyHostToDevice, ctx->stream));
+                    hipLaunchKernelGGL(mc::walk_hot_flag_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, ctx->wt.hot_flag.as<unsigned char>(), nb,
+                                       ctx->wt.hot_sec.as<unsigned>());  // (the destinations of the first pass's records, marked; no second walk over the blocks)
                     HIP_TRY(ctx, hipGetLastError());
                     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                    ctx->have_hot = true;
+                    ctx->wt.have_hot = true;
                 } else {  // no block qualifies (uniform short blocks): S x levels x 64 B -- 0.5 GB at the configs[4] shape -- are not kept for nothing
-                    ctx->hot_sec.release();
-                    ctx->hot_flag.release();
+                    ctx->wt.hot_sec.release();
+                    ctx->wt.hot_flag.release();
                 }
-                ctx->hot_mass.release();  // (only the choice above read it)
+                ctx->wt.hot_mass.release();  // (only the choice above read it)
             }
             {
                 std::vector<int> bt(2 * n_levels);
@@ -2353,7 +2434,7 @@ static int derive_opacity_tables(TardisMcContext *ctx, const size_t L, const siz
                     bt[2 * b] = (int)c0[b];
                     bt[2 * b + 1] = (int)(edge[b + 1] - edge[b]);
                 }
-                if ((rc = upload(ctx, ctx->blk_tab, bt.data(), bt.size()))) return rc;
+                if ((rc = upload(ctx, ctx->wt.blk_tab, bt.data(), bt.size()))) return rc;
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             }
             std::vector<int> qi(2 * (size_t)n_quads, 0), lbc(2 * L, 0);  // (quads of the sector padding: {0, 0} -> eight 0xffff entries)
@@ -2387,18 +2468,18 @@ static int derive_opacity_tables(TardisMcContext *ctx, const size_t L, const siz
                     lbc[2 * i + 1] = (int)(edge[lvl + 1] - edge[lvl]);
                 }
             }
-            if ((rc = upload(ctx, ctx->quad_info, qi.data(), qi.size()))) return rc;
-            if ((rc = upload(ctx, ctx->rec16, r16.data(), r16.size()))) return rc;
-            if ((rc = upload(ctx, ctx->line_block_c, lbc.data(), lbc.size()))) return rc;
-            HIP_TRY(ctx, ctx->cum16.ensure((size_t)stride * S * sizeof(unsigned short)));
-            HIP_TRY(ctx, hipMemsetAsync(ctx->cum16.p, 0xff, (size_t)stride * S * sizeof(unsigned short), ctx->stream));
+            if ((rc = upload(ctx, ctx->wt.quad_info, qi.data(), qi.size()))) return rc;
+            if ((rc = upload(ctx, ctx->wt.rec16, r16.data(), r16.size()))) return rc;
+            if ((rc = upload(ctx, ctx->wt.line_block_c, lbc.data(), lbc.size()))) return rc;
+            HIP_TRY(ctx, ctx->wt.cum16.ensure((size_t)stride * S * sizeof(unsigned short)));
+            HIP_TRY(ctx, hipMemsetAsync(ctx->wt.cum16.p, 0xff, (size_t)stride * S * sizeof(unsigned short), ctx->stream));
             const long long n = n_quads * (long long)S;
-            hipLaunchKernelGGL(mc::walk_cum16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cum_t.as<double>(),
-                               ctx->quad_info.as<int2>(), n_quads, (long long)T, (int)S, (unsigned)stride, ctx->cum16.as<unsigned short>());
+            hipLaunchKernelGGL(mc::walk_cum16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ot.cum_t.as<double>(),
+                               ctx->wt.quad_info.as<int2>(), n_quads, (long long)T, (int)S, (unsigned)stride, ctx->wt.cum16.as<unsigned short>());
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the host vectors above are the sources of asynchronous copies)
-            ctx->cum16_stride = (unsigned)stride;
-            ctx->have_walk_tables = true;
+            ctx->wt.cum16_stride = (unsigned)stride;
+            ctx->wt.have_walk_tables = true;
         }
     }
     return TARDIS_MC_OK;
@@ -2412,7 +2493,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     if (o->n_lines > 0x7ffffff0LL || o->n_transitions > 0x7ffffff0LL)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "line / transition count exceeds 32-bit device indices");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->sf_valid = ctx->sf_topo_valid = ctx->sf_exp_valid = false;
+    drop_products(ctx, OPACITY_TOPOLOGY_REPLACED);
     const bool tmark_on = getenv("TARDIS_MC_TIME_OPACITY") != nullptr;  // (diagnostic: wall time of the stages of this call on stderr)
     auto tmark_t0 = std::chrono::steady_clock::now();
     const std::function<void(const char *)> tmark = [&](const char *what) {
@@ -2447,37 +2528,37 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
     tmark("validate");
     int rc;
     // (slack at the end of the line list and of the tau table: the lane sweep loads whole chunks, propagate_wave.hpp)
-    HIP_TRY(ctx, ctx->nu_line.ensure((L + 2 * mc::LS_CHUNK) * sizeof(double)));
-    if ((rc = upload(ctx, ctx->nu_line, o->line_list_nu, L))) return rc;
-    if ((rc = upload(ctx, ctx->n_e, o->electron_density, S))) return rc;
+    HIP_TRY(ctx, ctx->ot.nu_line.ensure((L + 2 * mc::LS_CHUNK) * sizeof(double)));
+    if ((rc = upload(ctx, ctx->ot.nu_line, o->line_list_nu, L))) return rc;
+    if ((rc = upload(ctx, ctx->ot.n_e, o->electron_density, S))) return rc;
     // tau [L,S] -> [S][L]
     HIP_TRY(ctx, ctx->staging.ensure(std::max(L, T) * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->tau_t.ensure((L * S + 2 * mc::LS_CHUNK) * sizeof(double)));
+    HIP_TRY(ctx, ctx->ot.tau_t.ensure((L * S + 2 * mc::LS_CHUNK) * sizeof(double)));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, host_copy(ctx, {{(void *)o->tau_sobolev, ctx->staging.p, L * S * sizeof(double)}}, true));
-    HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->staging.as<double>(), ctx->tau_t.as<double>(), (long long)L, (long long)S));
+    HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->staging.as<double>(), ctx->ot.tau_t.as<double>(), (long long)L, (long long)S));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     tmark("nu, n_e, tau up + transpose");
     // probabilities [T,S] -> [S][T]
-    HIP_TRY(ctx, ctx->prob_t.ensure(T * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ot.prob_t.ensure(T * S * sizeof(double)));
     HIP_TRY(ctx, host_copy(ctx, {{(void *)o->transition_probabilities, ctx->staging.p, T * S * sizeof(double)}}, true));
-    HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->staging.as<double>(), ctx->prob_t.as<double>(), (long long)T, (long long)S));
+    HIP_TRY(ctx, launch_transpose(ctx->stream, ctx->staging.as<double>(), ctx->ot.prob_t.as<double>(), (long long)T, (long long)S));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     tmark("probabilities up + transpose");
     static const int64_t zero64 = 0;
-    std::vector<int> (&idx32)[5] = ctx->h_idx;  // (one staging vector per table: the copies are asynchronous, ONE synchronisation below covers them all; kept for derive_opacity_tables)
+    std::vector<int> (&idx32)[5] = ctx->ot.h_idx;  // (one staging vector per table: the copies are asynchronous, ONE synchronisation below covers them all; kept for derive_opacity_tables)
     auto up32 = [&](int k, DevBuf &buf, const int64_t *host, size_t n) -> int {
         idx32[k].resize(n);
         for (size_t i = 0; i < n; ++i) idx32[k][i] = (int)host[i];
         return upload(ctx, buf, idx32[k].data(), n);
     };
-    if ((rc = up32(0, ctx->line2level, macro ? o->line2macro_level_upper : &zero64, macro ? L : 1))) return rc;
-    if ((rc = up32(1, ctx->block_edge, macro ? o->macro_block_edge_index : &zero64, macro ? E : 1))) return rc;
-    if ((rc = up32(2, ctx->ttype, macro ? o->transition_type : &zero64, macro ? T : 1))) return rc;
-    if ((rc = up32(3, ctx->dest, macro ? o->destination_level_id : &zero64, macro ? T : 1))) return rc;
-    if ((rc = up32(4, ctx->tline, macro ? o->transition_line_id : &zero64, macro ? T : 1))) return rc;
-    ctx->h_nu.assign(o->line_list_nu, o->line_list_nu + L);
-    ctx->h_macro = macro;
+    if ((rc = up32(0, ctx->ot.line2level, macro ? o->line2macro_level_upper : &zero64, macro ? L : 1))) return rc;
+    if ((rc = up32(1, ctx->ot.block_edge, macro ? o->macro_block_edge_index : &zero64, macro ? E : 1))) return rc;
+    if ((rc = up32(2, ctx->ot.ttype, macro ? o->transition_type : &zero64, macro ? T : 1))) return rc;
+    if ((rc = up32(3, ctx->ot.dest, macro ? o->destination_level_id : &zero64, macro ? T : 1))) return rc;
+    if ((rc = up32(4, ctx->ot.tline, macro ? o->transition_line_id : &zero64, macro ? T : 1))) return rc;
+    ctx->ot.h_nu.assign(o->line_list_nu, o->line_list_nu + L);
+    ctx->ot.h_macro = macro;
     drop_from(ctx, RUNG_LINE_DATA);  // (the line data belong to one topology: tardis_mc_set_line_data again)
     tmark("index tables int32 up");
     {   // packed macro-atom tables of the cooperative kernel
@@ -2498,23 +2579,23 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
                 }
             }
         }
-        if ((rc = upload(ctx, ctx->line_block, lb.data(), lb.size()))) return rc;
-        if ((rc = upload(ctx, ctx->trans_rec, rec.data(), rec.size()))) return rc;
+        if ((rc = upload(ctx, ctx->ot.line_block, lb.data(), lb.size()))) return rc;
+        if ((rc = upload(ctx, ctx->ot.trans_rec, rec.data(), rec.size()))) return rc;
         // frequency of the line every emission transition ends in, next to its record (one round trip instead of two)
         std::vector<double> tnu(macro ? T : 1, 0.0);
         if (macro)
             for (size_t t = 0; t < T; ++t)
                 if (o->transition_type[t] == -1) tnu[t] = o->line_list_nu[o->transition_line_id[t]];
-        if ((rc = upload(ctx, ctx->trans_nu, tnu.data(), tnu.size()))) return rc;
+        if ((rc = upload(ctx, ctx->ot.trans_nu, tnu.data(), tnu.size()))) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     tmark("packed tables lb / rec / tnu");
     if ((rc = derive_opacity_tables(ctx, L, S, T, tmark))) return rc;
     tmark("compact walk tables + hot sectors");
-    ctx->lines_sorted = true;
+    ctx->ot.lines_sorted = true;
     for (size_t i = 0; i < L; ++i)
-        if (!(o->line_list_nu[i] > 0.0) || (i > 0 && !(o->line_list_nu[i] <= o->line_list_nu[i - 1]))) { ctx->lines_sorted = false; break; }
-    if (ctx->lines_sorted)
+        if (!(o->line_list_nu[i] > 0.0) || (i > 0 && !(o->line_list_nu[i] <= o->line_list_nu[i - 1]))) { ctx->ot.lines_sorted = false; break; }
+    if (ctx->ot.lines_sorted)
     {   // frequency-bucket index over the (descending) line list.  Resolution: bucket_lines_permille / 1000 lines per bucket on average
         // (default 0.75; rounds 1-4: 3).  A v-packet's shell crossing pins its stopping line with a window of four lines from the
         // bucket's first line: with three lines per bucket 22 % of the crossings missed the window and walked on line by line -- in a wave
@@ -2526,7 +2607,7 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
         if (nu_lo > 0 && nu_hi >= nu_lo) {
             const double binades = std::max(1.0, std::log2(nu_hi / nu_lo));
             const double per_binade = (double)L / binades;
-            while (mbits < 22 && per_binade / (double)(1 << mbits) > 1e-3 * (double)ctx->bucket_lines_permille) ++mbits;
+            while (mbits < 22 && per_binade / (double)(1 << mbits) > 1e-3 * (double)ctx->ot.bucket_lines_permille) ++mbits;
         }
         const int shift = 52 - mbits;
         const long long kmin = (long long)(bits(nu_lo > 0 ? nu_lo : 1.0) >> shift), kmax = (long long)(bits(nu_hi > 0 ? nu_hi : 1.0) >> shift);
@@ -2539,9 +2620,9 @@ int tardis_mc_set_opacity(TardisMcContext *ctx, const TardisMcOpacity *o)
             while (i < L && (long long)(bits(o->line_list_nu[i]) >> shift) - kmin > k) ++i;
             first[(size_t)k] = (int)i;
         }
-        if ((rc = upload(ctx, ctx->bucket_first, first.data(), first.size()))) return rc;
+        if ((rc = upload(ctx, ctx->ot.bucket_first, first.data(), first.size()))) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->bucket_shift = shift; ctx->bucket_n = (int)K; ctx->bucket_kmin = kmin;
+        ctx->ot.bucket_shift = shift; ctx->ot.bucket_n = (int)K; ctx->ot.bucket_kmin = kmin;
     }
     tmark("sorted check + bucket index");
     if (ctx->have_geometry && (int)S != ctx->n_shells)
@@ -2562,7 +2643,7 @@ int tardis_mc_set_config(TardisMcContext *ctx, const TardisMcConfig *c)
     if (c->line_interaction_type < 0 || c->line_interaction_type > 2)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "line_interaction_type must be 0, 1 or 2");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->vl_valid = ctx->vl_consolidated = false;  // (the consolidated v-packet log belongs to the configuration it was written under)
+    drop_products(ctx, CONFIG_REPLACED);
     ctx->cfg = *c;
     ctx->grid_host.assign(c->spectrum_frequency_grid, c->spectrum_frequency_grid + c->n_spectrum_grid);
     ctx->cfg.spectrum_frequency_grid = ctx->grid_host.data();
@@ -2579,33 +2660,32 @@ int tardis_mc_set_packets(TardisMcContext *ctx, const TardisMcPackets *p)
         (p->n_packets > 0 && (!p->initial_radii || !p->initial_nus || !p->initial_mus || !p->initial_energies || !p->packet_seeds)))
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid packets");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->li_valid = false;  // (the resident results are no longer those of the resident packets)
-    ctx->vl_valid = ctx->vl_consolidated = false;
+    drop_products(ctx, PACKETS_REPLACED);
     const size_t P = (size_t)p->n_packets;
     int rc;
-    HIP_TRY(ctx, ctx->r0.ensure(P * 8)); HIP_TRY(ctx, ctx->mu0.ensure(P * 8)); HIP_TRY(ctx, ctx->nu0.ensure(P * 8)); HIP_TRY(ctx, ctx->e0.ensure(P * 8));
-    HIP_TRY(ctx, ctx->seeds.ensure(P * 4));
+    HIP_TRY(ctx, ctx->pk.r0.ensure(P * 8)); HIP_TRY(ctx, ctx->pk.mu0.ensure(P * 8)); HIP_TRY(ctx, ctx->pk.nu0.ensure(P * 8)); HIP_TRY(ctx, ctx->pk.e0.ensure(P * 8));
+    HIP_TRY(ctx, ctx->pk.seeds.ensure(P * 4));
     // The seeds arrive as int64 and the kernels read uint32 (np.random.seed(int) -> init_genrand(uint32)): sent as they are and narrowed on the device.  (A host
     // vector of P words -- zero-filled, then filled -- cost 100 ms of the 200 ms this call took at 1e8 packets; the extra 4 bytes per packet over the link cost 8.)
     HIP_TRY(ctx, ctx->staging.ensure(P * 8));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (nothing of an earlier call still reads the packet buffers)
-    HIP_TRY(ctx, host_copy(ctx, {{(void *)p->initial_radii, ctx->r0.p, P * 8}, {(void *)p->initial_mus, ctx->mu0.p, P * 8},
-                                      {(void *)p->initial_nus, ctx->nu0.p, P * 8}, {(void *)p->initial_energies, ctx->e0.p, P * 8},
+    HIP_TRY(ctx, host_copy(ctx, {{(void *)p->initial_radii, ctx->pk.r0.p, P * 8}, {(void *)p->initial_mus, ctx->pk.mu0.p, P * 8},
+                                      {(void *)p->initial_nus, ctx->pk.nu0.p, P * 8}, {(void *)p->initial_energies, ctx->pk.e0.p, P * 8},
                                       {(void *)p->packet_seeds, ctx->staging.p, P * 8}}, true));
     if (P > 0) {
-        hipLaunchKernelGGL(narrow_seeds_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, ctx->staging.as<long long>(), (long long)P, ctx->seeds.as<uint32_t>());
+        hipLaunchKernelGGL(narrow_seeds_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, ctx->stream, ctx->staging.as<long long>(), (long long)P, ctx->pk.seeds.as<uint32_t>());
         HIP_TRY(ctx, hipGetLastError());
     }
     (void)rc;
-    HIP_TRY(ctx, ctx->out_nu.ensure(P * sizeof(double)));
-    HIP_TRY(ctx, ctx->out_e.ensure(P * sizeof(double)));
-    if (ctx->track) {
-        for (auto &b : ctx->li_f64) HIP_TRY(ctx, b.ensure(P * sizeof(double)));
-        for (auto &b : ctx->li_i64) HIP_TRY(ctx, b.ensure(P * sizeof(long long)));
-        HIP_TRY(ctx, ctx->li_rec.ensure(P * 64));
+    HIP_TRY(ctx, ctx->pk.out_nu.ensure(P * sizeof(double)));
+    HIP_TRY(ctx, ctx->pk.out_e.ensure(P * sizeof(double)));
+    if (ctx->pk.track) {
+        for (auto &b : ctx->pk.li_f64) HIP_TRY(ctx, b.ensure(P * sizeof(double)));
+        for (auto &b : ctx->pk.li_i64) HIP_TRY(ctx, b.ensure(P * sizeof(long long)));
+        HIP_TRY(ctx, ctx->pk.li_rec.ensure(P * 64));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->n_packets = (long long)P;
+    ctx->pk.n_packets = (long long)P;
     ctx->have_packets = true;
     return TARDIS_MC_OK;
 }
@@ -2664,17 +2744,17 @@ int tardis_mc_pcg64_seed(uint64_t seed, uint64_t out_state[4])
 
 static int ensure_packet_buffers(TardisMcContext *ctx, size_t P)
 {
-    HIP_TRY(ctx, ctx->r0.ensure(P * sizeof(double)));
-    HIP_TRY(ctx, ctx->mu0.ensure(P * sizeof(double)));
-    HIP_TRY(ctx, ctx->nu0.ensure(P * sizeof(double)));
-    HIP_TRY(ctx, ctx->e0.ensure(P * sizeof(double)));
-    HIP_TRY(ctx, ctx->seeds.ensure(P * sizeof(uint32_t)));
-    HIP_TRY(ctx, ctx->out_nu.ensure(P * sizeof(double)));
-    HIP_TRY(ctx, ctx->out_e.ensure(P * sizeof(double)));
-    if (ctx->track) {
-        for (auto &b : ctx->li_f64) HIP_TRY(ctx, b.ensure(P * sizeof(double)));
-        for (auto &b : ctx->li_i64) HIP_TRY(ctx, b.ensure(P * sizeof(long long)));
-        HIP_TRY(ctx, ctx->li_rec.ensure(P * 64));
+    HIP_TRY(ctx, ctx->pk.r0.ensure(P * sizeof(double)));
+    HIP_TRY(ctx, ctx->pk.mu0.ensure(P * sizeof(double)));
+    HIP_TRY(ctx, ctx->pk.nu0.ensure(P * sizeof(double)));
+    HIP_TRY(ctx, ctx->pk.e0.ensure(P * sizeof(double)));
+    HIP_TRY(ctx, ctx->pk.seeds.ensure(P * sizeof(uint32_t)));
+    HIP_TRY(ctx, ctx->pk.out_nu.ensure(P * sizeof(double)));
+    HIP_TRY(ctx, ctx->pk.out_e.ensure(P * sizeof(double)));
+    if (ctx->pk.track) {
+        for (auto &b : ctx->pk.li_f64) HIP_TRY(ctx, b.ensure(P * sizeof(double)));
+        for (auto &b : ctx->pk.li_i64) HIP_TRY(ctx, b.ensure(P * sizeof(long long)));
+        HIP_TRY(ctx, ctx->pk.li_rec.ensure(P * 64));
     }
     return TARDIS_MC_OK;
 }
@@ -2688,8 +2768,7 @@ int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, in
         max_seed_val < 2 || (uint64_t)n_total >= (1ULL << 44))
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid packet source arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->li_valid = false;
-    ctx->vl_valid = ctx->vl_consolidated = false;
+    drop_products(ctx, PACKETS_REPLACED);
     const size_t P = (size_t)count;
     int rc = ensure_packet_buffers(ctx, P);
     if (rc) return rc;
@@ -2703,7 +2782,7 @@ int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, in
     hu128 nm = 1, np_ = 0;  // n_total-step map, composed from the set bits
     for (int j = 0; j < mc::PCG_JUMP_BITS; ++j)
         if (((uint64_t)n_total >> j) & 1) { nm = jm[j] * nm; np_ = jm[j] * np_ + jp[j]; }
-    DevBuf d_jump, d_l, d_rej, d_cnt;
+    ScopedDevBuf d_jump, d_l, d_rej, d_cnt;
     HIP_TRY(ctx, d_jump.ensure(jump.size() * sizeof(mc::PcgAffine)));
     HIP_TRY(ctx, hipMemcpyAsync(d_jump.p, jump.data(), jump.size() * sizeof(mc::PcgAffine), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, d_l.ensure((size_t)n_l * sizeof(double)));
@@ -2726,8 +2805,8 @@ int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, in
     a.kT = 1.3806488e-16 * temperature;   // tardis/constants.py:1 (CODATA 2010, cgs)
     a.h = 6.62606957e-27;
     a.energy = n_total > 0 ? 1.0 / (double)n_total : 0.0;
-    a.r0 = ctx->r0.as<double>(); a.mu0 = ctx->mu0.as<double>(); a.nu0 = ctx->nu0.as<double>(); a.e0 = ctx->e0.as<double>();
-    a.seeds = ctx->seeds.as<uint32_t>();
+    a.r0 = ctx->pk.r0.as<double>(); a.mu0 = ctx->pk.mu0.as<double>(); a.nu0 = ctx->pk.nu0.as<double>(); a.e0 = ctx->pk.e0.as<double>();
+    a.seeds = ctx->pk.seeds.as<uint32_t>();
 
     // pass 1: rejected u32 positions of the bounded-integer draw (threshold / 2^32 of all draws; none for almost every
     // run with the reference's MAX_SEED_VAL = 2^32 - 1)
@@ -2765,8 +2844,7 @@ int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, in
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    d_jump.release(); d_l.release(); d_rej.release(); d_cnt.release();
-    ctx->n_packets = count;
+    ctx->pk.n_packets = count;
     ctx->have_packets = true;
     return TARDIS_MC_OK;
 }
@@ -2777,15 +2855,15 @@ int tardis_mc_get_packets(TardisMcContext *ctx, double *initial_radii, double *i
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_packets) return fail(ctx, TARDIS_MC_ERR_STATE, "no packets resident");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t P = (size_t)ctx->n_packets;
+    const size_t P = (size_t)ctx->pk.n_packets;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (initial_radii && P) HIP_TRY(ctx, hipMemcpy(initial_radii, ctx->r0.p, P * 8, hipMemcpyDeviceToHost));
-    if (initial_nus && P) HIP_TRY(ctx, hipMemcpy(initial_nus, ctx->nu0.p, P * 8, hipMemcpyDeviceToHost));
-    if (initial_mus && P) HIP_TRY(ctx, hipMemcpy(initial_mus, ctx->mu0.p, P * 8, hipMemcpyDeviceToHost));
-    if (initial_energies && P) HIP_TRY(ctx, hipMemcpy(initial_energies, ctx->e0.p, P * 8, hipMemcpyDeviceToHost));
+    if (initial_radii && P) HIP_TRY(ctx, hipMemcpy(initial_radii, ctx->pk.r0.p, P * 8, hipMemcpyDeviceToHost));
+    if (initial_nus && P) HIP_TRY(ctx, hipMemcpy(initial_nus, ctx->pk.nu0.p, P * 8, hipMemcpyDeviceToHost));
+    if (initial_mus && P) HIP_TRY(ctx, hipMemcpy(initial_mus, ctx->pk.mu0.p, P * 8, hipMemcpyDeviceToHost));
+    if (initial_energies && P) HIP_TRY(ctx, hipMemcpy(initial_energies, ctx->pk.e0.p, P * 8, hipMemcpyDeviceToHost));
     if (packet_seeds && P) {
         std::vector<uint32_t> tmp(P);
-        HIP_TRY(ctx, hipMemcpy(tmp.data(), ctx->seeds.p, P * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(tmp.data(), ctx->pk.seeds.p, P * 4, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < P; ++i) packet_seeds[i] = (int64_t)tmp[i];
     }
     return TARDIS_MC_OK;
@@ -2795,13 +2873,13 @@ int tardis_mc_reset_estimators(TardisMcContext *ctx)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->sf_valid = false;
+    drop_products(ctx, ESTIMATORS_CHANGED);
     int rc = ensure_estimators(ctx);
     if (rc) return rc;
-    if (!ctx->est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_config must precede reset_estimators");
-    EstLayout e = est_layout(ctx->est_S, ctx->est_L, ctx->est_G, ctx->est_copies);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->est.p, 0, e.total * sizeof(double), ctx->stream));
-    ctx->est_propagated = false;
+    if (!ctx->es.est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_config must precede reset_estimators");
+    EstLayout e = est_layout(ctx->es.est_S, ctx->es.est_L, ctx->es.est_G, ctx->es.est_copies);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->es.est.p, 0, e.total * sizeof(double), ctx->stream));
+    ctx->es.est_propagated = false;
     HIP_TRY(ctx, ctx->counters.ensure(TARDIS_MC_N_COUNTERS * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, TARDIS_MC_N_COUNTERS * sizeof(unsigned long long), ctx->stream));
     return TARDIS_MC_OK;
@@ -2813,22 +2891,19 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     if (!ctx->have_geometry || !ctx->have_opacity || !ctx->have_config || !ctx->have_packets)
         return fail(ctx, TARDIS_MC_ERR_STATE, "set_geometry/set_opacity/set_config/set_packets must precede propagate");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->compactions = 0;
-    ctx->ev_valid = false;
-    ctx->li_valid = false;
-    ctx->sf_valid = false;
-    ctx->vl_valid = ctx->vl_consolidated = false;
+    ctx->wv.compactions = 0;
+    drop_products(ctx, PROPAGATE_BEGINS);
     const TardisMcConfig &c = ctx->cfg;
-    if (ctx->vlog_li && c.enable_vpacket_tracking && c.number_of_vpackets > 0 && !ctx->track && !ctx->track_full)
+    if (ctx->vl.vlog_li && c.enable_vpacket_tracking && c.number_of_vpackets > 0 && !ctx->pk.track && !ctx->el.track_full)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "the option vpacket_last_interaction needs a tracker: track_last_interaction 1 or track_full 1");
     PropagateCall call{};
     call.vpk = c.number_of_vpackets > 0;
     call.full = c.enable_full_relativity != 0;
     call.cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
     call.rs_armed = ctx->rs.armed;
-    ctx->rs.armed = false; ctx->rs.valid = false; ctx->rs.upto = 0; ctx->rs.n_late = 0;
-    call.tune_pending = ctx->ls_tune.pending;
-    ctx->ls_tune.pending = -1;
+    ctx->rs.armed = false; ctx->rs.upto = 0; ctx->rs.n_late = 0;
+    call.tune_pending = ctx->lt.ls_tune.pending;
+    ctx->lt.ls_tune.pending = -1;
     call.tune_slot = -1;
     int rc = ensure_estimators(ctx);
     if (rc) return rc;
@@ -2836,47 +2911,47 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         HIP_TRY(ctx, ctx->counters.ensure(TARDIS_MC_N_COUNTERS * sizeof(unsigned long long)));
         HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, TARDIS_MC_N_COUNTERS * sizeof(unsigned long long), ctx->stream));
     }
-    if (ctx->track) {  // (tracking may have been switched on after the packets were set)
-        const size_t P = (size_t)std::max<long long>(ctx->n_packets, 1);
-        for (auto &b : ctx->li_f64) HIP_TRY(ctx, b.ensure(P * sizeof(double)));
-        for (auto &b : ctx->li_i64) HIP_TRY(ctx, b.ensure(P * sizeof(long long)));
-        HIP_TRY(ctx, ctx->li_rec.ensure(P * 64));
+    if (ctx->pk.track) {  // (tracking may have been switched on after the packets were set)
+        const size_t P = (size_t)std::max<long long>(ctx->pk.n_packets, 1);
+        for (auto &b : ctx->pk.li_f64) HIP_TRY(ctx, b.ensure(P * sizeof(double)));
+        for (auto &b : ctx->pk.li_i64) HIP_TRY(ctx, b.ensure(P * sizeof(long long)));
+        HIP_TRY(ctx, ctx->pk.li_rec.ensure(P * 64));
     }
-    if (ctx->track_full) HIP_TRY(ctx, ctx->li_rec.ensure((size_t)std::max<long long>(ctx->n_packets, 1) * 64));
+    if (ctx->el.track_full) HIP_TRY(ctx, ctx->pk.li_rec.ensure((size_t)std::max<long long>(ctx->pk.n_packets, 1) * 64));
     // v-packet log buffers
     if (c.enable_vpacket_tracking && call.vpk) {
         // (sized for the current call: the engine is cached per process, a later, larger run must not inherit a smaller log)
-        if (!ctx->vlog_capacity_user) ctx->vlog_capacity = std::max<long long>(1024, ctx->n_packets * c.number_of_vpackets * 64);
-        size_t cap = (size_t)ctx->vlog_capacity;
-        HIP_TRY(ctx, ctx->vlog_count.ensure(sizeof(unsigned long long)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->vlog_count.p, 0, sizeof(unsigned long long), ctx->stream));
-        HIP_TRY(ctx, ctx->vlog_packet.ensure(cap * sizeof(long long)));
-        HIP_TRY(ctx, ctx->vlog_seq.ensure(cap * sizeof(int)));
-        HIP_TRY(ctx, ctx->vlog_nu.ensure(cap * sizeof(double)));
-        HIP_TRY(ctx, ctx->vlog_energy.ensure(cap * sizeof(double)));
-        HIP_TRY(ctx, ctx->vlog_mu.ensure(cap * sizeof(double)));
+        if (!ctx->vl.vlog_capacity_user) ctx->vl.vlog_capacity = std::max<long long>(1024, ctx->pk.n_packets * c.number_of_vpackets * 64);
+        size_t cap = (size_t)ctx->vl.vlog_capacity;
+        HIP_TRY(ctx, ctx->vl.vlog_count.ensure(sizeof(unsigned long long)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->vl.vlog_count.p, 0, sizeof(unsigned long long), ctx->stream));
+        HIP_TRY(ctx, ctx->vl.vlog_packet.ensure(cap * sizeof(long long)));
+        HIP_TRY(ctx, ctx->vl.vlog_seq.ensure(cap * sizeof(int)));
+        HIP_TRY(ctx, ctx->vl.vlog_nu.ensure(cap * sizeof(double)));
+        HIP_TRY(ctx, ctx->vl.vlog_energy.ensure(cap * sizeof(double)));
+        HIP_TRY(ctx, ctx->vl.vlog_mu.ensure(cap * sizeof(double)));
         // (option vpacket_last_interaction: vlog_r [cap] | before_nu [cap] | ids [cap] x 16 B in one allocation, mc_device.hpp -- what the VLI instantiations write)
-        HIP_TRY(ctx, ctx->vlog_r.ensure(cap * sizeof(double) * (vlog_li_call(ctx) ? 4 : 1)));
+        HIP_TRY(ctx, ctx->vl.vlog_r.ensure(cap * sizeof(double) * (vlog_li_call(ctx) ? 4 : 1)));
     }
     HIP_TRY(ctx, ctx->first_error.ensure(2 * sizeof(long long)));
     // (argument blocks reach the device through store_value(): consecutive propagate calls -- iterations, chunks submitted by
     // the host -- are not serialised by a stream synchronisation here)
     HIP_TRY(ctx, store_value(ctx->stream, ctx->first_error.as<FirstErrorInit>(), FirstErrorInit{{0x7fffffffffffffffLL, 0}}));
-    ctx->progress_done = false; ctx->progress_wave = false; ctx->progress_total = ctx->n_packets;
+    ctx->pg.progress_done = false; ctx->pg.progress_wave = false; ctx->pg.progress_total = ctx->pk.n_packets;
     {
-        std::lock_guard<std::mutex> lock(ctx->progress_mutex);  // (tardis_mc_progress may be reading next_packet)
+        std::lock_guard<std::mutex> lock(ctx->pg.progress_mutex);  // (tardis_mc_progress may be reading next_packet)
         HIP_TRY(ctx, ctx->next_packet.ensure(sizeof(unsigned long long)));
-        if (!ctx->ev_progress_reset) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_progress_reset, hipEventDisableTiming));
+        if (!ctx->pg.ev_progress_reset) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pg.ev_progress_reset, hipEventDisableTiming));
     }
     HIP_TRY(ctx, hipMemsetAsync(ctx->next_packet.p, 0, sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_progress_reset, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->pg.ev_progress_reset, ctx->stream));
     // which kernel (propagate_plan.hpp).  The screening tables are built by the first call whose plan screens; a negative optical depth in them
     // means no screening, and the plan is made again knowing that
     call.plan = plan::plan_propagate(plan_input(ctx));
-    if (!call.plan.error && call.plan.screen_on && !ctx->pfx_valid) {
+    if (!call.plan.error && call.plan.screen_on && !ctx->sc.pfx_valid) {
         rc = build_screening_tables(ctx);
         if (rc) return rc;
-        if (ctx->pfx_negative) call.plan = plan::plan_propagate(plan_input(ctx));
+        if (ctx->sc.pfx_negative) call.plan = plan::plan_propagate(plan_input(ctx));
     }
     if (call.plan.error) return fail(ctx, call.plan.error, "%s", call.plan.message);
     ctx->last_table_offsets = call.plan.last_table_offsets;
@@ -2884,29 +2959,29 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     rc = call.plan.cooperative ? run_cooperative(ctx, call) : run_lane_kernel(ctx, call);
     if (rc) return rc;
     {   // events per packet of this call, for the log sizing of the next one (asynchronous, pinned host memory)
-        if (!ctx->events_host) {
-            HIP_TRY(ctx, hipHostMalloc((void **)&ctx->events_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-            ctx->events_host[0] = ctx->events_host[1] = 0;
-            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_events, hipEventDisableTiming));
+        if (!ctx->wv.events_host) {
+            HIP_TRY(ctx, hipHostMalloc((void **)&ctx->wv.events_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+            ctx->wv.events_host[0] = ctx->wv.events_host[1] = 0;
+            HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->wv.ev_events, hipEventDisableTiming));
         }
-        ctx->events_host[1] = (unsigned long long)ctx->n_packets;
-        HIP_TRY(ctx, hipMemcpyAsync(&ctx->events_host[0], ctx->counters.as<unsigned long long>() + TARDIS_MC_CNT_EVENTS,
+        ctx->wv.events_host[1] = (unsigned long long)ctx->pk.n_packets;
+        HIP_TRY(ctx, hipMemcpyAsync(&ctx->wv.events_host[0], ctx->counters.as<unsigned long long>() + TARDIS_MC_CNT_EVENTS,
                                     sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_events, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->wv.ev_events, ctx->stream));
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     ctx->timed = true;
-    ctx->est_propagated = true;
+    ctx->es.est_propagated = true;
     if (call.tune_slot >= 0) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_tune[1], ctx->stream));
-        ctx->ls_tune.pending = call.tune_slot;
+        HIP_TRY(ctx, hipEventRecord(ctx->lt.ev_tune[1], ctx->stream));
+        ctx->lt.ls_tune.pending = call.tune_slot;
     }
-    ctx->ev_valid = ctx->track_full;  // (a call that failed half-way leaves no event log to read)
-    ctx->li_valid = ctx->track;
-    ctx->vl_valid = c.enable_vpacket_tracking && call.vpk && ctx->vlog_capacity > 0;
-    ctx->vl_li = vlog_li_call(ctx);
-    ctx->vl_packets = ctx->n_packets;
-    ctx->vl_capacity = ctx->vlog_capacity;
+    ctx->el.ev_valid = ctx->el.track_full;  // (a call that failed half-way leaves no event log to read)
+    ctx->pk.li_valid = ctx->pk.track;
+    ctx->vl.vl_valid = c.enable_vpacket_tracking && call.vpk && ctx->vl.vlog_capacity > 0;
+    ctx->vl.vl_li = vlog_li_call(ctx);
+    ctx->vl.vl_packets = ctx->pk.n_packets;
+    ctx->vl.vl_capacity = ctx->vl.vlog_capacity;
     return TARDIS_MC_OK;
 }
 
@@ -2915,27 +2990,27 @@ int tardis_mc_synchronize(TardisMcContext *ctx)
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->progress_done = true;
+    ctx->pg.progress_done = true;
     return TARDIS_MC_OK;
 }
 
 int tardis_mc_progress(TardisMcContext *ctx, int64_t *out_packets_started, int64_t *out_packets_total)
 {
     if (!ctx || !out_packets_started || !out_packets_total) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    const long long total = ctx->progress_total.load();
+    const long long total = ctx->pg.progress_total.load();
     *out_packets_total = total;
     *out_packets_started = 0;
-    if (ctx->progress_done.load()) { *out_packets_started = total; return TARDIS_MC_OK; }
-    if (!ctx->progress_wave.load()) return TARDIS_MC_OK;
-    std::lock_guard<std::mutex> lock(ctx->progress_mutex);
+    if (ctx->pg.progress_done.load()) { *out_packets_started = total; return TARDIS_MC_OK; }
+    if (!ctx->pg.progress_wave.load()) return TARDIS_MC_OK;
+    std::lock_guard<std::mutex> lock(ctx->pg.progress_mutex);
     if (hipSetDevice(ctx->device) != hipSuccess) return TARDIS_MC_ERR_HIP;  // (the polling thread's current device is 0 until it says otherwise)
-    if (!ctx->next_packet.p || !ctx->ev_progress_reset || hipEventQuery(ctx->ev_progress_reset) != hipSuccess) return TARDIS_MC_OK;  // (not reset yet)
-    if (!ctx->stream_progress && hipStreamCreateWithFlags(&ctx->stream_progress, hipStreamNonBlocking) != hipSuccess) return TARDIS_MC_ERR_HIP;
-    if (!ctx->progress_host && hipHostMalloc((void **)&ctx->progress_host, sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return TARDIS_MC_ERR_HIP;
-    if (hipMemcpyAsync(ctx->progress_host, ctx->next_packet.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream_progress) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream_progress) != hipSuccess)
+    if (!ctx->next_packet.p || !ctx->pg.ev_progress_reset || hipEventQuery(ctx->pg.ev_progress_reset) != hipSuccess) return TARDIS_MC_OK;  // (not reset yet)
+    if (!ctx->pg.stream_progress && hipStreamCreateWithFlags(&ctx->pg.stream_progress, hipStreamNonBlocking) != hipSuccess) return TARDIS_MC_ERR_HIP;
+    if (!ctx->pg.progress_host && hipHostMalloc((void **)&ctx->pg.progress_host, sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return TARDIS_MC_ERR_HIP;
+    if (hipMemcpyAsync(ctx->pg.progress_host, ctx->next_packet.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->pg.stream_progress) != hipSuccess ||
+        hipStreamSynchronize(ctx->pg.stream_progress) != hipSuccess)
         return TARDIS_MC_ERR_HIP;
-    *out_packets_started = (int64_t)std::min<unsigned long long>(*ctx->progress_host, (unsigned long long)std::max<long long>(total, 0));  // (a wave reserves 32 at a time)
+    *out_packets_started = (int64_t)std::min<unsigned long long>(*ctx->pg.progress_host, (unsigned long long)std::max<long long>(total, 0));  // (a wave reserves 32 at a time)
     return TARDIS_MC_OK;
 }
 
@@ -2958,21 +3033,21 @@ int tardis_mc_last_kernel_times(TardisMcContext *ctx, double *out_seed_ms, doubl
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipEventSynchronize(ctx->ev_stop));
     double seed = 0.0, prop = 0.0;
-    if (ctx->wave_epoch_mode) {  // wave kernel: launch preparation once, then one propagation launch + estimator passes per epoch
+    if (ctx->wv.wave_epoch_mode) {  // wave kernel: launch preparation once, then one propagation launch + estimator passes per epoch
         float ms = 0.f;
         HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_chunk[0], ctx->ev_chunk[1]));
         ctx->sum_seed_ms = ms;
-        if (ctx->prop_pending) {
+        if (ctx->wv.prop_pending) {
             HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_chunk[2], ctx->ev_chunk[3]));
             ctx->sum_prop_ms += ms;
-            ctx->prop_pending = false;
+            ctx->wv.prop_pending = false;
         }
         for (int b = 0; b < 2; ++b)
-            if (ctx->post_pending[b]) {
-                HIP_TRY(ctx, hipEventSynchronize(ctx->ev_post[2 * b + 1]));
-                HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_post[2 * b], ctx->ev_post[2 * b + 1]));
+            if (ctx->wv.post_pending[b]) {
+                HIP_TRY(ctx, hipEventSynchronize(ctx->wv.ev_post[2 * b + 1]));
+                HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->wv.ev_post[2 * b], ctx->wv.ev_post[2 * b + 1]));
                 ctx->sum_post_ms += ms;
-                ctx->post_pending[b] = false;
+                ctx->wv.post_pending[b] = false;
             }
         ctx->last_post_ms = ctx->sum_post_ms;
         if (out_seed_ms) *out_seed_ms = ctx->sum_seed_ms;
@@ -3011,13 +3086,13 @@ int tardis_mc_last_counters(TardisMcContext *ctx, int64_t out_counters[TARDIS_MC
     HIP_TRY(ctx, hipMemcpyAsync(cnt, ctx->counters.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < TARDIS_MC_N_COUNTERS; ++k) out_counters[k] = (int64_t)cnt[k];
-    out_counters[TARDIS_MC_CNT_PACKETS] = ctx->n_packets;
+    out_counters[TARDIS_MC_CNT_PACKETS] = ctx->pk.n_packets;
     return TARDIS_MC_OK;
 }
 
 int tardis_mc_last_variant(TardisMcContext *ctx) { return ctx ? ctx->last_variant : -1; }
 int tardis_mc_last_table_offsets(TardisMcContext *ctx) { return ctx ? ctx->last_table_offsets : -1; }
-int tardis_mc_last_compactions(TardisMcContext *ctx) { return ctx ? ctx->compactions : -1; }
+int tardis_mc_last_compactions(TardisMcContext *ctx) { return ctx ? ctx->wv.compactions : -1; }
 
 int tardis_mc_last_estimator_ms(TardisMcContext *ctx, double *out_ms)
 {
@@ -3032,11 +3107,11 @@ int tardis_mc_last_estimator_ms(TardisMcContext *ctx, double *out_ms)
 
 static int reduce_estimator_copies(TardisMcContext *ctx)
 {
-    if (ctx->est_copies <= 1) return TARDIS_MC_OK;
-    EstLayout e = est_layout(ctx->est_S, ctx->est_L, ctx->est_G, ctx->est_copies);
-    long long n = (long long)(2 * ctx->est_S * ctx->est_L);
-    hipLaunchKernelGGL(reduce_copies_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->est.as<double>() + e.jblue, n,
-                       (long long)e.copy_stride, ctx->est_copies);
+    if (ctx->es.est_copies <= 1) return TARDIS_MC_OK;
+    EstLayout e = est_layout(ctx->es.est_S, ctx->es.est_L, ctx->es.est_G, ctx->es.est_copies);
+    long long n = (long long)(2 * ctx->es.est_S * ctx->es.est_L);
+    hipLaunchKernelGGL(reduce_copies_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->es.est.as<double>() + e.jblue, n,
+                       (long long)e.copy_stride, ctx->es.est_copies);
     HIP_TRY(ctx, hipGetLastError());
     return TARDIS_MC_OK;
 }
@@ -3044,13 +3119,13 @@ static int reduce_estimator_copies(TardisMcContext *ctx)
 int tardis_mc_get_results(TardisMcContext *ctx, TardisMcResult *res)
 {
     if (!ctx || !res) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "nothing to fetch");
+    if (!ctx->es.est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "nothing to fetch");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = reduce_estimator_copies(ctx);
     if (rc) return rc;
-    const size_t P = (size_t)ctx->n_packets, S = ctx->est_S, L = ctx->est_L, G = ctx->est_G;
-    EstLayout e = est_layout(S, L, G, ctx->est_copies);
-    double *base = ctx->est.as<double>();
+    const size_t P = (size_t)ctx->pk.n_packets, S = ctx->es.est_S, L = ctx->es.est_L, G = ctx->es.est_G;
+    EstLayout e = est_layout(S, L, G, ctx->es.est_copies);
+    double *base = ctx->es.est.as<double>();
     auto d2h = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
         if (!dst || !bytes) return hipSuccess;
         return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -3078,10 +3153,10 @@ int tardis_mc_get_results(TardisMcContext *ctx, TardisMcResult *res)
             const size_t m = (size_t)ctx->rs.n_late;
             std::vector<unsigned> idx(m);
             std::vector<unsigned long long> vals(m);
-            HIP_TRY(ctx, hipMemcpy(idx.data(), ctx->rs_late.p, m * sizeof(unsigned), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(idx.data(), ctx->rs.late.p, m * sizeof(unsigned), hipMemcpyDeviceToHost));
             for (int a = 0; a < 16; ++a) {
                 if (!patch[a]) continue;
-                HIP_TRY(ctx, hipMemcpy(vals.data(), ctx->rs_vals.as<unsigned long long>() + (size_t)a * m, m * 8, hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(vals.data(), ctx->rs.vals.as<unsigned long long>() + (size_t)a * m, m * 8, hipMemcpyDeviceToHost));
                 unsigned long long *out = (unsigned long long *)host[a];
                 for (size_t j = 0; j < m; ++j) out[idx[j]] = vals[j];
             }
@@ -3109,34 +3184,34 @@ int tardis_mc_get_results(TardisMcContext *ctx, TardisMcResult *res)
     long long ferr[2] = {0x7fffffffffffffffLL, 0};
     if (ctx->first_error.p) HIP_TRY(ctx, d2h(ferr, ctx->first_error.p, sizeof ferr));
     unsigned long long vcount = 0;
-    const bool vlog = ctx->cfg.enable_vpacket_tracking && ctx->cfg.number_of_vpackets > 0 && ctx->vlog_count.p;
-    if (vlog) HIP_TRY(ctx, d2h(&vcount, ctx->vlog_count.p, sizeof vcount));
+    const bool vlog = ctx->cfg.enable_vpacket_tracking && ctx->cfg.number_of_vpackets > 0 && ctx->vl.vlog_count.p;
+    if (vlog) HIP_TRY(ctx, d2h(&vcount, ctx->vl.vlog_count.p, sizeof vcount));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < TARDIS_MC_N_COUNTERS; ++k) res->counters[k] = (int64_t)cnt[k];
-    res->counters[TARDIS_MC_CNT_PACKETS] = ctx->n_packets;
-    if (ctx->n_packets > 0) ctx->traces_per_packet = (double)cnt[TARDIS_MC_CNT_EVENTS] / (double)ctx->n_packets;
+    res->counters[TARDIS_MC_CNT_PACKETS] = ctx->pk.n_packets;
+    if (ctx->pk.n_packets > 0) ctx->wv.traces_per_packet = (double)cnt[TARDIS_MC_CNT_EVENTS] / (double)ctx->pk.n_packets;
     res->first_error_packet = -1;
     res->error_code = 0;
     if (ferr[0] != 0x7fffffffffffffffLL) {
         res->first_error_packet = ferr[0];
         double marker = 0.0;  // the failing lane stored its error code in out_nu[packet]
-        HIP_TRY(ctx, hipMemcpy(&marker, ctx->out_nu.as<double>() + ferr[0], 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(&marker, ctx->pk.out_nu.as<double>() + ferr[0], 8, hipMemcpyDeviceToHost));
         res->error_code = (int)marker;
     }
     res->vpacket_log_count = 0;
     if (vlog) {
         res->vpacket_log_count = (int64_t)vcount;
-        size_t n = (size_t)std::min<unsigned long long>(vcount, (unsigned long long)ctx->vlog_capacity);
+        size_t n = (size_t)std::min<unsigned long long>(vcount, (unsigned long long)ctx->vl.vlog_capacity);
         std::vector<long long> pk(n);
         std::vector<int> seq(n);
         std::vector<double> nu(n), en(n), mu(n), rr(n);
         if (n) {
-            HIP_TRY(ctx, hipMemcpy(pk.data(), ctx->vlog_packet.p, n * 8, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(seq.data(), ctx->vlog_seq.p, n * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(nu.data(), ctx->vlog_nu.p, n * 8, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(en.data(), ctx->vlog_energy.p, n * 8, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(mu.data(), ctx->vlog_mu.p, n * 8, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(rr.data(), ctx->vlog_r.p, n * 8, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(pk.data(), ctx->vl.vlog_packet.p, n * 8, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(seq.data(), ctx->vl.vlog_seq.p, n * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(nu.data(), ctx->vl.vlog_nu.p, n * 8, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(en.data(), ctx->vl.vlog_energy.p, n * 8, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(mu.data(), ctx->vl.vlog_mu.p, n * 8, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(rr.data(), ctx->vl.vlog_r.p, n * 8, hipMemcpyDeviceToHost));
         }
         // the reference consolidates per-packet lists in packet order (packet_collections.py:310-396)
         std::vector<size_t> order(n);
@@ -3159,8 +3234,8 @@ int tardis_mc_get_event_log(TardisMcContext *ctx, TardisMcEventLog *log)
     if (!ctx || !log) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     log->count = 0;
     log->dropped = 0;
-    if (!ctx->ev_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "no event log: the last tardis_mc_propagate ran without the option track_full");
-    if (ctx->n_packets != ctx->ev_packets)
+    if (!ctx->el.ev_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "no event log: the last tardis_mc_propagate ran without the option track_full");
+    if (ctx->pk.n_packets != ctx->el.ev_packets)
         return fail(ctx, TARDIS_MC_ERR_STATE, "no event log: the resident packets were replaced after the tracked tardis_mc_propagate");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     {   // a call in which a packet failed has no complete log (that packet's rows end at the error)
@@ -3170,37 +3245,37 @@ int tardis_mc_get_event_log(TardisMcContext *ctx, TardisMcEventLog *log)
         if (fe != 0x7fffffffffffffffLL)
             return fail(ctx, TARDIS_MC_ERR_STATE, "no event log: packet %lld of the tracked tardis_mc_propagate failed", fe);
     }
-    const long long n = ctx->ev_packets;
+    const long long n = ctx->el.ev_packets;
     const long long tiles = std::max<long long>(1, (n + mc::EV_SCAN_TILE - 1) / mc::EV_SCAN_TILE);
-    HIP_TRY(ctx, ctx->ev_offsets.ensure((size_t)(n + 1) * sizeof(long long)));
-    HIP_TRY(ctx, ctx->ev_tiles.ensure((size_t)tiles * sizeof(long long)));
-    long long *offsets = ctx->ev_offsets.as<long long>();
-    hipLaunchKernelGGL(mc::event_scan_tiles_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->ev_counts.as<int>(), n,
-                       ctx->ev_tiles.as<long long>());
-    hipLaunchKernelGGL(mc::event_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->ev_tiles.as<long long>(), tiles, offsets, n);
-    hipLaunchKernelGGL(mc::event_scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->ev_counts.as<int>(), n,
-                       ctx->ev_tiles.as<long long>(), offsets);
+    HIP_TRY(ctx, ctx->el.ev_offsets.ensure((size_t)(n + 1) * sizeof(long long)));
+    HIP_TRY(ctx, ctx->el.ev_tiles.ensure((size_t)tiles * sizeof(long long)));
+    long long *offsets = ctx->el.ev_offsets.as<long long>();
+    hipLaunchKernelGGL(mc::event_scan_tiles_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->el.ev_counts.as<int>(), n,
+                       ctx->el.ev_tiles.as<long long>());
+    hipLaunchKernelGGL(mc::event_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->el.ev_tiles.as<long long>(), tiles, offsets, n);
+    hipLaunchKernelGGL(mc::event_scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->el.ev_counts.as<int>(), n,
+                       ctx->el.ev_tiles.as<long long>(), offsets);
     HIP_TRY(ctx, hipGetLastError());
     long long total = 0;
     unsigned long long state[2] = {0, 0};  // {pool_next (low 32 bits), dropped}
     HIP_TRY(ctx, hipMemcpyAsync(&total, offsets + n, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(state, ctx->ev_state.p, sizeof state, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(state, ctx->el.ev_state.p, sizeof state, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     log->count = total;
     log->dropped = (int64_t)state[1];
     if (log->offsets) HIP_TRY(ctx, hipMemcpyAsync(log->offsets, offsets, (size_t)(n + 1) * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     // the columns only when every row is there and fits the caller's arrays (otherwise: re-run with event_log_capacity = count)
     if (state[1] == 0 && total > 0 && total <= log->capacity) {
-        HIP_TRY(ctx, ctx->ev_cols.ensure((size_t)total * 14 * 8));
-        long long *ci = ctx->ev_cols.as<long long>();
+        HIP_TRY(ctx, ctx->el.ev_cols.ensure((size_t)total * 14 * 8));
+        long long *ci = ctx->el.ev_cols.as<long long>();
         double *cf = reinterpret_cast<double *>(ci + 7 * total);
         mc::EventColumns col{ci, ci + total, ci + 2 * total, ci + 3 * total, ci + 4 * total, ci + 5 * total, ci + 6 * total,
                              cf, cf + total, cf + 2 * total, cf + 3 * total, cf + 4 * total, cf + 5 * total, cf + 6 * total};
-        const unsigned used_chunks = std::min<unsigned>((unsigned)(state[0] & 0xffffffffull), ctx->ev_n_chunks);
-        const long long n_slots = (long long)used_chunks * ctx->ev_chunk_rows;
+        const unsigned used_chunks = std::min<unsigned>((unsigned)(state[0] & 0xffffffffull), ctx->el.ev_n_chunks);
+        const long long n_slots = (long long)used_chunks * ctx->el.ev_chunk_rows;
         const int blocks = (int)std::max<long long>(1, std::min<long long>((n_slots + 255) / 256, 65536));
-        hipLaunchKernelGGL(mc::event_scatter_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->ev_rows.as<mc::EventRow>(),
-                           ctx->ev_fill.as<unsigned>(), ctx->ev_chunk_rows, n_slots, offsets, col);
+        hipLaunchKernelGGL(mc::event_scatter_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->el.ev_rows.as<mc::EventRow>(),
+                           ctx->el.ev_fill.as<unsigned>(), ctx->el.ev_chunk_rows, n_slots, offsets, col);
         HIP_TRY(ctx, hipGetLastError());
         int64_t *dst_i[7] = {log->event_id, log->interaction_type, log->status, log->shell_id, log->after_shell_id, log->line_absorb_id,
                              log->line_emit_id};
@@ -3242,9 +3317,9 @@ int tardis_mc_run(TardisMcContext *ctx, const TardisMcPackets *packets, const Ta
     // the caller's log capacity is for this call only, whichever way the call ends (the context is cached per process)
     struct VlogScope {
         TardisMcContext *c; bool was_user; long long was;
-        ~VlogScope() { c->vlog_capacity_user = was_user; if (was_user) c->vlog_capacity = was; }
-    } scope{ctx, ctx->vlog_capacity_user, ctx->vlog_capacity};
-    if (result && result->vpacket_log_capacity > 0) { ctx->vlog_capacity = result->vpacket_log_capacity; ctx->vlog_capacity_user = true; }
+        ~VlogScope() { c->vl.vlog_capacity_user = was_user; if (was_user) c->vl.vlog_capacity = was; }
+    } scope{ctx, ctx->vl.vlog_capacity_user, ctx->vl.vlog_capacity};
+    if (result && result->vpacket_log_capacity > 0) { ctx->vl.vlog_capacity = result->vpacket_log_capacity; ctx->vl.vlog_capacity_user = true; }
     if ((rc = tardis_mc_set_packets(ctx, packets))) return rc;
     if ((rc = tardis_mc_reset_estimators(ctx))) return rc;
     if (result && (rc = tardis_mc_stream_results(ctx, result))) return rc;  // (the result arrays are known from the start: filled launch by launch)
@@ -3263,14 +3338,14 @@ int tardis_mc_packet_spectrum(TardisMcContext *ctx, double time_of_simulation, d
     if (!(time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "time_of_simulation must be positive");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t B = (size_t)ctx->cfg.n_spectrum_grid - 1;
-    DevBuf work;
+    ScopedDevBuf work;
     HIP_TRY(ctx, work.ensure((2 * B + 2) * sizeof(double)));
     HIP_TRY(ctx, hipMemsetAsync(work.p, 0, (2 * B + 2) * sizeof(double), ctx->stream));
     double *w = work.as<double>();
-    if (ctx->n_packets > 0) {
-        const int blocks = (int)std::min<long long>((ctx->n_packets + 255) / 256, 4096);
-        hipLaunchKernelGGL(spectrum_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->out_nu.as<double>(), ctx->out_e.as<double>(),
-                           ctx->n_packets, ctx->grid.as<double>(), (int)ctx->cfg.n_spectrum_grid, time_of_simulation,
+    if (ctx->pk.n_packets > 0) {
+        const int blocks = (int)std::min<long long>((ctx->pk.n_packets + 255) / 256, 4096);
+        hipLaunchKernelGGL(spectrum_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->pk.out_nu.as<double>(), ctx->pk.out_e.as<double>(),
+                           ctx->pk.n_packets, ctx->grid.as<double>(), (int)ctx->cfg.n_spectrum_grid, time_of_simulation,
                            luminosity_nu_start, luminosity_nu_end, w, w + B, w + 2 * B);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -3281,7 +3356,6 @@ int tardis_mc_packet_spectrum(TardisMcContext *ctx, double time_of_simulation, d
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (out_emitted_luminosity) *out_emitted_luminosity = lum[0];
     if (out_reabsorbed_luminosity) *out_reabsorbed_luminosity = lum[1];
-    work.release();
     return TARDIS_MC_OK;
 }
 
@@ -3304,15 +3378,15 @@ static int decomposition_impl(TardisMcContext *ctx, TardisMcDecomposition *d, co
     if (d->n_classes < 1 || d->n_classes > 0x7fffffffLL)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "packet decomposition: n_classes must be in [1, 2^31)");
     if (!(d->time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "time_of_simulation must be positive");
-    if (virt && (!ctx->have_packets || !ctx->have_opacity || !ctx->have_geometry || !ctx->vl_valid || !ctx->vl_li))
+    if (virt && (!ctx->have_packets || !ctx->have_opacity || !ctx->have_geometry || !ctx->vl.vl_valid || !ctx->vl.vl_li))
         return fail(ctx, TARDIS_MC_ERR_STATE, "v-packet decomposition: no v-packet log with last-interaction columns -- it follows a completed "
                     "tardis_mc_propagate with v-packet tracking and the option vpacket_last_interaction on, before the packets or the configuration are replaced");
-    if (!virt && (!ctx->have_packets || !ctx->have_opacity || !ctx->have_geometry || !ctx->li_valid))
+    if (!virt && (!ctx->have_packets || !ctx->have_opacity || !ctx->have_geometry || !ctx->pk.li_valid))
         return fail(ctx, TARDIS_MC_ERR_STATE, "packet decomposition: no last-interaction results of the resident packets -- it follows a completed "
                     "tardis_mc_propagate with track_last_interaction on, before the packets are replaced");
     if (!ctx->have_config || ctx->cfg.n_spectrum_grid < 2) return fail(ctx, TARDIS_MC_ERR_STATE, "packet decomposition needs a spectrum grid");
     const long long C = d->n_classes, B = ctx->cfg.n_spectrum_grid - 1, S = ctx->n_shells, L = ctx->n_lines;
-    long long P = ctx->n_packets;
+    long long P = ctx->pk.n_packets;
     // the class table, narrowed to 32 bits; no class is used as an index before it has passed this check
     std::vector<int> cls((size_t)L);
     for (long long i = 0; i < L; ++i) {
@@ -3330,22 +3404,22 @@ static int decomposition_impl(TardisMcContext *ctx, TardisMcDecomposition *d, co
     }
     bool timing_open = false;  // (a consolidation inside this call is part of its device time)
     if (virt) {
-        if (!ctx->vl_consolidated) {
+        if (!ctx->vl.vl_consolidated) {
             HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
             timing_open = true;
             const int rc = consolidate_vpacket_log(ctx, "v-packet decomposition");
             if (rc) return rc;
         }
-        if (!ctx->vl_consolidated)
+        if (!ctx->vl.vl_consolidated)
             return fail(ctx, TARDIS_MC_ERR_STATE, "v-packet decomposition: the v-packet log overflowed (%lld entries, capacity %lld): run the call again with "
-                        "vpacket_log_capacity >= %lld", ctx->vl_count, ctx->vl_capacity, ctx->vl_count);
-        P = ctx->vl_count;
+                        "vpacket_log_capacity >= %lld", ctx->vl.vl_count, ctx->vl.vl_capacity, ctx->vl.vl_count);
+        P = ctx->vl.vl_count;
     }
     // one allocation: cells [(2C+2)B] doubles | shell_packets [(C+1)S] | line_emit [L] | line_absorb [L] | counts [4] | line_class [L] int32
     const size_t n_cells = (size_t)(2 * C + 2) * (size_t)B, n_shell = (size_t)(C + 1) * (size_t)S;
     const size_t n_words = n_cells + n_shell + 2 * (size_t)L + 4;
-    HIP_TRY(ctx, ctx->dc_work.ensure(n_words * 8 + (size_t)L * sizeof(int)));
-    double *cells = ctx->dc_work.as<double>();
+    HIP_TRY(ctx, ctx->pk.dc_work.ensure(n_words * 8 + (size_t)L * sizeof(int)));
+    double *cells = ctx->pk.dc_work.as<double>();
     unsigned long long *shell = reinterpret_cast<unsigned long long *>(cells + n_cells), *line_emit = shell + n_shell, *line_absorb = line_emit + L,
                        *counts = line_absorb + L;
     int *d_cls = reinterpret_cast<int *>(counts + 4);
@@ -3355,14 +3429,14 @@ static int decomposition_impl(TardisMcContext *ctx, TardisMcDecomposition *d, co
     if (P > 0) {
         mc::DecompositionArgs a{};
         if (virt) {  // the columns of the consolidated log, vl_cols: source_packet | nu | energy | mu | r | in_nu | in_r | type | in_id | out_id | shell_id
-            double *f = ctx->vl_cols.as<double>();
-            long long *g = ctx->vl_cols.as<long long>();
+            double *f = ctx->vl.vl_cols.as<double>();
+            long long *g = ctx->vl.vl_cols.as<long long>();
             a.out_nu = f + 1 * P; a.out_e = f + 2 * P; a.before_nu = f + 5 * P;
             a.type = g + 7 * P; a.absorb_id = g + 8 * P; a.emit_id = g + 9 * P; a.shell_id = g + 10 * P;
         } else {
-            a.out_nu = ctx->out_nu.as<double>(); a.out_e = ctx->out_e.as<double>(); a.before_nu = ctx->li_f64[3].as<double>();
-            a.shell_id = ctx->li_i64[0].as<long long>(); a.type = ctx->li_i64[1].as<long long>();
-            a.absorb_id = ctx->li_i64[2].as<long long>(); a.emit_id = ctx->li_i64[3].as<long long>();
+            a.out_nu = ctx->pk.out_nu.as<double>(); a.out_e = ctx->pk.out_e.as<double>(); a.before_nu = ctx->pk.li_f64[3].as<double>();
+            a.shell_id = ctx->pk.li_i64[0].as<long long>(); a.type = ctx->pk.li_i64[1].as<long long>();
+            a.absorb_id = ctx->pk.li_i64[2].as<long long>(); a.emit_id = ctx->pk.li_i64[3].as<long long>();
         }
         a.n_packets = P;
         a.line_class = d_cls; a.n_lines = L; a.n_classes = C;
@@ -3410,45 +3484,45 @@ int tardis_mc_vpacket_decomposition(TardisMcContext *ctx, TardisMcDecomposition 
 // columns are there (not when the device log overflowed: the caller then reports the count).
 static int consolidate_vpacket_log(TardisMcContext *ctx, const char *who)
 {
-    if (!ctx->vl_valid || !ctx->have_packets || ctx->n_packets != ctx->vl_packets)
+    if (!ctx->vl.vl_valid || !ctx->have_packets || ctx->pk.n_packets != ctx->vl.vl_packets)
         return fail(ctx, TARDIS_MC_ERR_STATE, "%s: no v-packet log -- it follows a completed tardis_mc_propagate with v-packet tracking, before the "
                     "packets or the configuration are replaced", who);
-    if (ctx->vl_consolidated) return TARDIS_MC_OK;
+    if (ctx->vl.vl_consolidated) return TARDIS_MC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     long long fe = 0x7fffffffffffffffLL;
     unsigned long long vcount = 0;
     if (ctx->first_error.p) HIP_TRY(ctx, hipMemcpyAsync(&fe, ctx->first_error.p, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&vcount, ctx->vlog_count.p, sizeof vcount, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&vcount, ctx->vl.vlog_count.p, sizeof vcount, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (fe != 0x7fffffffffffffffLL) return fail(ctx, TARDIS_MC_ERR_STATE, "%s: packet %lld of the last tardis_mc_propagate failed", who, fe);
-    ctx->vl_count = (long long)vcount;
-    if (ctx->vl_count > ctx->vl_capacity) return TARDIS_MC_OK;  // overflowed: only the count is known
-    const long long n = ctx->vl_packets, m = ctx->vl_count;
+    ctx->vl.vl_count = (long long)vcount;
+    if (ctx->vl.vl_count > ctx->vl.vl_capacity) return TARDIS_MC_OK;  // overflowed: only the count is known
+    const long long n = ctx->vl.vl_packets, m = ctx->vl.vl_count;
     const long long tiles = std::max<long long>(1, (n + mc::EV_SCAN_TILE - 1) / mc::EV_SCAN_TILE);
-    const int n_cols = ctx->vl_li ? 11 : 5;
-    HIP_TRY(ctx, ctx->vl_counts.ensure((size_t)std::max<long long>(n, 1) * sizeof(int)));
-    HIP_TRY(ctx, ctx->vl_offsets.ensure((size_t)(n + 1) * sizeof(long long)));
-    HIP_TRY(ctx, ctx->vl_tiles.ensure((size_t)tiles * sizeof(long long)));
-    HIP_TRY(ctx, ctx->vl_errors.ensure(sizeof(unsigned long long)));
-    HIP_TRY(ctx, ctx->vl_cols.ensure((size_t)std::max<long long>(m, 1) * n_cols * 8));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->vl_counts.p, 0, (size_t)std::max<long long>(n, 1) * sizeof(int), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->vl_errors.p, 0, sizeof(unsigned long long), ctx->stream));
+    const int n_cols = ctx->vl.vl_li ? 11 : 5;
+    HIP_TRY(ctx, ctx->vl.vl_counts.ensure((size_t)std::max<long long>(n, 1) * sizeof(int)));
+    HIP_TRY(ctx, ctx->vl.vl_offsets.ensure((size_t)(n + 1) * sizeof(long long)));
+    HIP_TRY(ctx, ctx->vl.vl_tiles.ensure((size_t)tiles * sizeof(long long)));
+    HIP_TRY(ctx, ctx->vl.vl_errors.ensure(sizeof(unsigned long long)));
+    HIP_TRY(ctx, ctx->vl.vl_cols.ensure((size_t)std::max<long long>(m, 1) * n_cols * 8));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->vl.vl_counts.p, 0, (size_t)std::max<long long>(n, 1) * sizeof(int), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->vl.vl_errors.p, 0, sizeof(unsigned long long), ctx->stream));
     const int blocks = (int)std::max<long long>(1, std::min<long long>((m + 255) / 256, 65536));
-    long long *offsets = ctx->vl_offsets.as<long long>();
-    unsigned long long *errors = ctx->vl_errors.as<unsigned long long>();
-    if (m > 0) hipLaunchKernelGGL(mc::vpacket_log_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->vlog_packet.as<long long>(), m, n, ctx->vl_counts.as<int>(), errors);
-    hipLaunchKernelGGL(mc::event_scan_tiles_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->vl_counts.as<int>(), n, ctx->vl_tiles.as<long long>());
-    hipLaunchKernelGGL(mc::event_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->vl_tiles.as<long long>(), tiles, offsets, n);
-    hipLaunchKernelGGL(mc::event_scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->vl_counts.as<int>(), n, ctx->vl_tiles.as<long long>(), offsets);
+    long long *offsets = ctx->vl.vl_offsets.as<long long>();
+    unsigned long long *errors = ctx->vl.vl_errors.as<unsigned long long>();
+    if (m > 0) hipLaunchKernelGGL(mc::vpacket_log_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->vl.vlog_packet.as<long long>(), m, n, ctx->vl.vl_counts.as<int>(), errors);
+    hipLaunchKernelGGL(mc::event_scan_tiles_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->vl.vl_counts.as<int>(), n, ctx->vl.vl_tiles.as<long long>());
+    hipLaunchKernelGGL(mc::event_scan_sums_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->vl.vl_tiles.as<long long>(), tiles, offsets, n);
+    hipLaunchKernelGGL(mc::event_scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, ctx->vl.vl_counts.as<int>(), n, ctx->vl.vl_tiles.as<long long>(), offsets);
     if (m > 0) {
-        mc::VpacketLogRaw raw{ctx->vlog_packet.as<long long>(), ctx->vlog_seq.as<int>(), ctx->vlog_nu.as<double>(), ctx->vlog_energy.as<double>(),
-                              ctx->vlog_mu.as<double>(), ctx->vlog_r.as<double>(), ctx->vl_li ? mc::vlog_last_ids(ctx->vlog_r.as<double>(), ctx->vl_capacity) : nullptr,
-                              ctx->vl_li ? mc::vlog_last_nu(ctx->vlog_r.as<double>(), ctx->vl_capacity) : nullptr};
-        double *f = ctx->vl_cols.as<double>();
-        long long *g = ctx->vl_cols.as<long long>();
+        mc::VpacketLogRaw raw{ctx->vl.vlog_packet.as<long long>(), ctx->vl.vlog_seq.as<int>(), ctx->vl.vlog_nu.as<double>(), ctx->vl.vlog_energy.as<double>(),
+                              ctx->vl.vlog_mu.as<double>(), ctx->vl.vlog_r.as<double>(), ctx->vl.vl_li ? mc::vlog_last_ids(ctx->vl.vlog_r.as<double>(), ctx->vl.vl_capacity) : nullptr,
+                              ctx->vl.vl_li ? mc::vlog_last_nu(ctx->vl.vlog_r.as<double>(), ctx->vl.vl_capacity) : nullptr};
+        double *f = ctx->vl.vl_cols.as<double>();
+        long long *g = ctx->vl.vl_cols.as<long long>();
         mc::VpacketLogColumns col{g, f + m, f + 2 * m, f + 3 * m, f + 4 * m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (ctx->vl_li) { col.li_in_nu = f + 5 * m; col.li_in_r = f + 6 * m; col.li_type = g + 7 * m; col.li_in_id = g + 8 * m; col.li_out_id = g + 9 * m; col.li_shell_id = g + 10 * m; }
-        hipLaunchKernelGGL(mc::vpacket_log_scatter_kernel, dim3(blocks), dim3(256), 0, ctx->stream, raw, m, n, m, ctx->vl_counts.as<int>(), offsets, col, errors);
+        if (ctx->vl.vl_li) { col.li_in_nu = f + 5 * m; col.li_in_r = f + 6 * m; col.li_type = g + 7 * m; col.li_in_id = g + 8 * m; col.li_out_id = g + 9 * m; col.li_shell_id = g + 10 * m; }
+        hipLaunchKernelGGL(mc::vpacket_log_scatter_kernel, dim3(blocks), dim3(256), 0, ctx->stream, raw, m, n, m, ctx->vl.vl_counts.as<int>(), offsets, col, errors);
     }
     HIP_TRY(ctx, hipGetLastError());
     unsigned long long bad = 0;
@@ -3459,7 +3533,7 @@ static int consolidate_vpacket_log(TardisMcContext *ctx, const char *who)
     if (bad != 0 || total != m)
         return fail(ctx, TARDIS_MC_ERR_STATE, "%s: the v-packet log is inconsistent (%llu entries with a packet, an ordinal or a position out of range; %lld of %lld "
                     "entries counted)", who, bad, total, m);
-    ctx->vl_consolidated = true;
+    ctx->vl.vl_consolidated = true;
     return TARDIS_MC_OK;
 }
 
@@ -3473,22 +3547,22 @@ int tardis_mc_get_vpacket_log(TardisMcContext *ctx, TardisMcVpacketLog *log)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = consolidate_vpacket_log(ctx, "v-packet log");  // (the timers of the propagate call stay as they are)
     if (rc) return rc;
-    if (!ctx->vl_li)
+    if (!ctx->vl.vl_li)
         for (void *q : li_dst)
             if (q) return fail(ctx, TARDIS_MC_ERR_STATE, "v-packet log: the last tardis_mc_propagate ran without the option vpacket_last_interaction, the six "
                                "last_interaction_* columns must be NULL");
-    const long long m = ctx->vl_count, n = ctx->vl_packets;
+    const long long m = ctx->vl.vl_count, n = ctx->vl.vl_packets;
     log->count = m;
-    if (!ctx->vl_consolidated || m > log->capacity) return TARDIS_MC_OK;  // overflow: only the count (run again with vpacket_log_capacity >= count)
+    if (!ctx->vl.vl_consolidated || m > log->capacity) return TARDIS_MC_OK;  // overflow: only the count (run again with vpacket_log_capacity >= count)
     auto d2h = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
         if (!dst || !bytes) return hipSuccess;
         return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
     };
-    HIP_TRY(ctx, d2h(log->offsets, ctx->vl_offsets.p, (size_t)(n + 1) * 8));
-    const char *cols = static_cast<const char *>(ctx->vl_cols.p);
+    HIP_TRY(ctx, d2h(log->offsets, ctx->vl.vl_offsets.p, (size_t)(n + 1) * 8));
+    const char *cols = static_cast<const char *>(ctx->vl.vl_cols.p);
     void *dst[5] = {log->source_packet, log->nus, log->energies, log->initial_mus, log->initial_rs};
     for (int k = 0; k < 5; ++k) HIP_TRY(ctx, d2h(dst[k], cols + (size_t)k * m * 8, (size_t)m * 8));
-    if (ctx->vl_li)
+    if (ctx->vl.vl_li)
         for (int k = 0; k < 6; ++k) HIP_TRY(ctx, d2h(li_dst[k], cols + (size_t)(5 + k) * m * 8, (size_t)m * 8));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TARDIS_MC_OK;
@@ -3501,9 +3575,9 @@ static int radiation_field_enqueue(TardisMcContext *ctx, double time_of_simulati
 {
     int rc = reduce_estimator_copies(ctx);
     if (rc) return rc;
-    const size_t S = ctx->est_S, L = ctx->est_L;
-    EstLayout e = est_layout(S, L, ctx->est_G, ctx->est_copies);
-    double *base = ctx->est.as<double>();
+    const size_t S = ctx->es.est_S, L = ctx->es.est_L;
+    EstLayout e = est_layout(S, L, ctx->es.est_G, ctx->es.est_copies);
+    double *base = ctx->es.est.as<double>();
     // constants, tardis/constants.py:1 (CODATA 2010, cgs)
     const double h = H_PLANCK, k_b = K_BOLTZMANN, sigma_sb = 5.670373e-5, c = mc::C_LIGHT, zeta5 = 1.0369277551433699;
     const double pi = 3.141592653589793;
@@ -3524,7 +3598,7 @@ static int radiation_field_enqueue(TardisMcContext *ctx, double time_of_simulati
     if (out_t && L > 0) {
         const unsigned bx = (unsigned)std::min<size_t>((L + 255) / 256, 1024);
         hipLaunchKernelGGL(radfield_jblue_kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, base + e.jblue,
-                           ctx->nu_line.as<double>(), d_t, d_w, d_norm, (int)S, (long long)L, k, detailed_optical_window, out_t);
+                           ctx->ot.nu_line.as<double>(), d_t, d_w, d_norm, (int)S, (long long)L, k, detailed_optical_window, out_t);
         HIP_TRY(ctx, hipGetLastError());
     }
     return TARDIS_MC_OK;
@@ -3534,19 +3608,19 @@ int tardis_mc_radiation_field(TardisMcContext *ctx, double time_of_simulation, c
                               int detailed_optical_window, double *t_radiative, double *dilution_factor, double *j_blues)
 {
     if (!ctx || !volume) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->est_valid || !ctx->have_opacity || !ctx->have_geometry)
+    if (!ctx->es.est_valid || !ctx->have_opacity || !ctx->have_geometry)
         return fail(ctx, TARDIS_MC_ERR_STATE, "radiation field update needs propagated estimators");
     if (!(time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "time_of_simulation must be positive");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t S = ctx->est_S, L = ctx->est_L;
+    const size_t S = ctx->es.est_S, L = ctx->es.est_L;
     const bool want_j = j_blues && L > 0;
-    DevBuf work, out_t;
+    ScopedDevBuf work, out_t;
     if (want_j) {
         HIP_TRY(ctx, out_t.ensure(L * S * sizeof(double)));
         HIP_TRY(ctx, ctx->staging.ensure(L * S * sizeof(double)));
     }
     int rc = radiation_field_enqueue(ctx, time_of_simulation, volume, w_epsilon, detailed_optical_window, work, want_j ? out_t.as<double>() : nullptr);
-    if (rc) { work.release(); out_t.release(); return rc; }
+    if (rc) return rc;
     const double *d_t = work.as<double>() + S, *d_w = d_t + S;
     if (t_radiative) HIP_TRY(ctx, hipMemcpyAsync(t_radiative, d_t, S * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (dilution_factor) HIP_TRY(ctx, hipMemcpyAsync(dilution_factor, d_w, S * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -3555,19 +3629,18 @@ int tardis_mc_radiation_field(TardisMcContext *ctx, double time_of_simulation, c
         HIP_TRY(ctx, hipMemcpyAsync(j_blues, ctx->staging.p, L * S * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    work.release(); out_t.release();
     return TARDIS_MC_OK;
 }
 
 // exp(-tau) in the layout of tau_t, kept until the next set_opacity: the source function and the resident formal integral after it read one table
 static int ensure_exp_tau(TardisMcContext *ctx)
 {
-    if (ctx->sf_exp_valid) return TARDIS_MC_OK;
+    if (ctx->sf.exp_valid) return TARDIS_MC_OK;
     const size_t n = (size_t)ctx->n_shells * (size_t)ctx->n_lines;
-    HIP_TRY(ctx, ctx->sf_exp_tau.ensure(n * sizeof(double)));
-    hipLaunchKernelGGL(mc::fi_exp_tau_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->tau_t.as<double>(), (long long)n, ctx->sf_exp_tau.as<double>());
+    HIP_TRY(ctx, ctx->sf.exp_tau.ensure(n * sizeof(double)));
+    hipLaunchKernelGGL(mc::fi_exp_tau_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->ot.tau_t.as<double>(), (long long)n, ctx->sf.exp_tau.as<double>());
     HIP_TRY(ctx, hipGetLastError());
-    ctx->sf_exp_valid = true;
+    ctx->sf.exp_valid = true;
     return TARDIS_MC_OK;
 }
 
@@ -3589,7 +3662,7 @@ static int formal_integral_check(TardisMcContext *ctx, bool resident, const doub
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_geometry || !ctx->have_opacity)
         return fail(ctx, TARDIS_MC_ERR_STATE, "formal integral needs set_geometry and set_opacity");
-    if (resident && !ctx->sf_valid)
+    if (resident && !ctx->sf.valid)
         return fail(ctx, TARDIS_MC_ERR_STATE, "no resident source function: tardis_mc_source_function must follow the last propagate / all-reduce");
     if (!frequencies || !have_tables || !luminosity_densities || n_frequencies < 0 || n_impact_parameters < 2 ||
         n_frequencies > (1LL << 30) || n_impact_parameters > 65535)
@@ -3605,7 +3678,7 @@ static int formal_integral_impl(TardisMcContext *ctx, const FormalIntegralInput 
     const size_t S = in.n_shells, L = (size_t)ctx->n_lines, n_nu = (size_t)n_frequencies, N = (size_t)n_impact_parameters;
     if (n_nu == 0) return TARDIS_MC_OK;
     const bool host_fed = in.exp_tau == nullptr;
-    DevBuf work;  // [exp_tau | att | jred | jblue | freqs | z | I | Lum] doubles, then sid / n_int ints (tables on the device already: none in front)
+    ScopedDevBuf work;  // [exp_tau | att | jred | jblue | freqs | z | I | Lum] doubles, then sid / n_int ints (tables on the device already: none in front)
     const size_t n_tab = host_fed ? S * L : 0;
     const size_t n_d = 4 * n_tab + n_nu + N * 2 * S + n_nu * N + n_nu;
     HIP_TRY(ctx, work.ensure(n_d * sizeof(double) + (N * 2 * S + N) * sizeof(int)));
@@ -3622,7 +3695,7 @@ static int formal_integral_impl(TardisMcContext *ctx, const FormalIntegralInput 
     const double *t_exp_tau = in.exp_tau, *t_att = in.att, *t_jred = in.jred, *t_jblue = in.jblue;
     if (host_fed) {
         if (S * L > 0)
-            hipLaunchKernelGGL(mc::fi_exp_tau_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->tau_t.as<double>(), (long long)(S * L), d_exp);
+            hipLaunchKernelGGL(mc::fi_exp_tau_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->ot.tau_t.as<double>(), (long long)(S * L), d_exp);
         t_exp_tau = d_exp; t_att = d_att; t_jred = d_jred; t_jblue = d_jblue;
     }
     hipLaunchKernelGGL(mc::fi_intersections_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, ctx->stream, (int)S,
@@ -3634,7 +3707,7 @@ static int formal_integral_impl(TardisMcContext *ctx, const FormalIntegralInput 
     a.n_shells = (int)S; a.n_lines = (int)L; a.n_nu = (int)n_nu; a.N = (int)N;
     a.t_exp = ctx->t_exp; a.inner_temperature = inner_temperature; a.radius_max = r_last[0];
     a.sigma_thomson = 6.652458734e-25;  // SIGMA_THOMSON, transport/montecarlo/configuration/constants.py:3 (astropy const13)
-    a.r_inner = in.r_inner; a.nu_line = ctx->nu_line.as<double>(); a.n_e = in.n_e;
+    a.r_inner = in.r_inner; a.nu_line = ctx->ot.nu_line.as<double>(); a.n_e = in.n_e;
     a.exp_tau = t_exp_tau; a.att_S_ul = t_att; a.Jred_lu = t_jred; a.Jblue_lu = t_jblue; a.frequencies = d_freq;
     a.z = d_z; a.sid = d_sid; a.n_int = d_nint; a.intensities_nu_p = d_I;
     HIP_TRY(ctx, ctx->counters.ensure(TARDIS_MC_N_COUNTERS * sizeof(unsigned long long)));
@@ -3651,7 +3724,6 @@ static int formal_integral_impl(TardisMcContext *ctx, const FormalIntegralInput 
     HIP_TRY(ctx, hipMemcpyAsync(luminosity_densities, d_lum, n_nu * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (intensities_nu_p) HIP_TRY(ctx, hipMemcpyAsync(intensities_nu_p, d_I, n_nu * N * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    work.release();
     return TARDIS_MC_OK;
 }
 
@@ -3660,7 +3732,7 @@ static FormalIntegralInput resident_formal_input(TardisMcContext *ctx)
 {
     FormalIntegralInput in;
     in.n_shells = (size_t)ctx->n_shells;
-    in.r_inner = ctx->r_inner.as<double>(); in.r_outer = ctx->r_outer.as<double>(); in.n_e = ctx->n_e.as<double>();
+    in.r_inner = ctx->r_inner.as<double>(); in.r_outer = ctx->r_outer.as<double>(); in.n_e = ctx->ot.n_e.as<double>();
     return in;
 }
 
@@ -3680,9 +3752,9 @@ int tardis_mc_formal_integral_resident(TardisMcContext *ctx, double inner_temper
 {
     int rc = formal_integral_check(ctx, true, frequencies, true, luminosity_densities, n_frequencies, n_impact_parameters);
     if (rc) return rc;
-    // (the source function has computed exp(-tau): set_opacity, which drops the table, drops sf_valid too)
+    // (the source function has computed exp(-tau): set_opacity, which drops the table, drops sf.valid too)
     FormalIntegralInput in = resident_formal_input(ctx);
-    in.exp_tau = ctx->sf_exp_tau.as<double>(); in.att = ctx->sf_att.as<double>(); in.jred = ctx->sf_jred.as<double>(); in.jblue = ctx->sf_jblue.as<double>();
+    in.exp_tau = ctx->sf.exp_tau.as<double>(); in.att = ctx->sf.att.as<double>(); in.jred = ctx->sf.jred.as<double>(); in.jblue = ctx->sf.jblue.as<double>();
     return formal_integral_impl(ctx, in, inner_temperature, frequencies, n_frequencies, n_impact_parameters, luminosity_densities, intensities_nu_p);
 }
 
@@ -3693,11 +3765,10 @@ struct InterpolatedSource {
     size_t n_shells = 0, table_stride = 0;  // (a table starts on a 16-byte boundary: the stride is even)
     mc::FiInterpolationGrid grid;
     std::vector<double> n_e;
-    DevBuf shells, tables, levels;
+    ScopedDevBuf shells, tables, levels;
     const double *d_dx = nullptr, *d_dxn = nullptr, *d_r_inner = nullptr, *d_r_outer = nullptr, *d_n_e = nullptr;
     const int *d_lo = nullptr, *d_hi = nullptr, *d_near = nullptr;
     double *table(int k) const { return tables.as<double>() + (size_t)k * table_stride; }  // 0 att, 1 jred, 2 jblue, 3 exp_tau
-    void release() { shells.release(); tables.release(); levels.release(); }
 };
 
 static int interpolate_check(TardisMcContext *ctx, int64_t interpolate_shells)
@@ -3710,7 +3781,7 @@ static int interpolate_check(TardisMcContext *ctx, int64_t interpolate_shells)
 }
 
 // Builds the interpolated tables of `interpolate_shells` grid points from the resident source function: records ev_start and launches the kernel(s) on
-// the context's stream, does not wait for them.  The caller releases `out`, whatever is returned.
+// the context's stream, does not wait for them.  `out` frees its scratch when it leaves the caller's scope, whatever is returned.
 static int interpolate_source(TardisMcContext *ctx, int64_t interpolate_shells, bool want_levels, InterpolatedSource &out)
 {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3718,7 +3789,7 @@ static int interpolate_source(TardisMcContext *ctx, int64_t interpolate_shells, 
     std::vector<double> r_in(S), r_out(S), n_e(S);
     HIP_TRY(ctx, hipMemcpyAsync(r_in.data(), ctx->r_inner.p, S * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(r_out.data(), ctx->r_outer.p, S * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(n_e.data(), ctx->n_e.p, S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(n_e.data(), ctx->ot.n_e.p, S * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     out.n_shells = Si;
     out.grid = mc::fi_interpolation_grid(r_in, r_out, (int)interpolate_shells);
@@ -3740,7 +3811,7 @@ static int interpolate_source(TardisMcContext *ctx, int64_t interpolate_shells, 
     mc::FiInterpolateArgs a{};
     a.L = (long long)L;
     a.lo = out.d_lo; a.hi = out.d_hi; a.near = out.d_near; a.dx = out.d_dx; a.dxn = out.d_dxn;
-    a.att = ctx->sf_att.as<double>(); a.jred = ctx->sf_jred.as<double>(); a.jblue = ctx->sf_jblue.as<double>(); a.exp_tau = ctx->sf_exp_tau.as<double>();
+    a.att = ctx->sf.att.as<double>(); a.jred = ctx->sf.jred.as<double>(); a.jblue = ctx->sf.jblue.as<double>(); a.exp_tau = ctx->sf.exp_tau.as<double>();
     a.att_i = out.table(0); a.jred_i = out.table(1); a.jblue_i = out.table(2); a.exp_tau_i = out.table(3);
     // about 2048 blocks in all, each striding over the pairs of lines of one output row
     const size_t row_blocks = std::max<size_t>(1, std::min<size_t>((L / 2 + 256) / 256, (2048 + Si - 1) / Si));
@@ -3749,7 +3820,7 @@ static int interpolate_source(TardisMcContext *ctx, int64_t interpolate_shells, 
     if (want_levels && K > 0) {
         HIP_TRY(ctx, out.levels.ensure(Si * K * sizeof(double)));
         hipLaunchKernelGGL(mc::fi_interpolate_levels_kernel, dim3((unsigned)std::min<size_t>((K + 255) / 256, 64), (unsigned)Si), dim3(256), 0, ctx->stream,
-                           out.d_lo, out.d_hi, out.d_dx, out.d_dxn, (long long)K, ctx->sf_c_level, out.levels.as<double>());
+                           out.d_lo, out.d_hi, out.d_dx, out.d_dxn, (long long)K, ctx->sf.c_level, out.levels.as<double>());
         HIP_TRY(ctx, hipGetLastError());
     }
     return TARDIS_MC_OK;
@@ -3772,7 +3843,6 @@ int tardis_mc_formal_integral_interpolated(TardisMcContext *ctx, int64_t interpo
         rc = formal_integral_impl(ctx, in, inner_temperature, frequencies, n_frequencies, n_impact_parameters, luminosity_densities, intensities_nu_p);
     }
     if (rc) (void)hipStreamSynchronize(ctx->stream);  // (nothing of the call is in flight when its scratch goes)
-    src.release();
     return rc;
 }
 
@@ -3792,7 +3862,7 @@ static int download_interpolated_source(TardisMcContext *ctx, const Interpolated
         if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k], src.table(k), Si * L * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (tau_sobolev_i)  // the rows of the resident optical depths, gathered by the copies themselves
         for (size_t j = 0; j < Si; ++j)
-            HIP_TRY(ctx, hipMemcpyAsync(tau_sobolev_i + j * L, ctx->tau_t.as<double>() + (size_t)src.grid.near[j] * L, L * 8, hipMemcpyDeviceToHost,
+            HIP_TRY(ctx, hipMemcpyAsync(tau_sobolev_i + j * L, ctx->ot.tau_t.as<double>() + (size_t)src.grid.near[j] * L, L * 8, hipMemcpyDeviceToHost,
                                         ctx->stream));
     if (e_dot_u_i && K > 0) {  // [S'][levels] -> level-major, as tardis_mc_source_function returns e_dot_u
         HIP_TRY(ctx, ctx->staging.ensure(Si * K * sizeof(double)));
@@ -3807,7 +3877,7 @@ int tardis_mc_interpolated_source(TardisMcContext *ctx, int64_t interpolate_shel
                                   double *tau_sobolev_i, double *att_S_ul_i, double *Jred_lu_i, double *Jblue_lu_i, double *e_dot_u_i)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->have_geometry || !ctx->have_opacity || !ctx->sf_valid)
+    if (!ctx->have_geometry || !ctx->have_opacity || !ctx->sf.valid)
         return fail(ctx, TARDIS_MC_ERR_STATE, "no resident source function: tardis_mc_source_function must follow the last propagate / all-reduce");
     int rc = interpolate_check(ctx, interpolate_shells);
     if (rc) return rc;
@@ -3815,7 +3885,6 @@ int tardis_mc_interpolated_source(TardisMcContext *ctx, int64_t interpolate_shel
     rc = interpolate_source(ctx, interpolate_shells, e_dot_u_i != nullptr, src);
     if (!rc) rc = download_interpolated_source(ctx, src, r_inner_i, r_outer_i, electron_density_i, tau_sobolev_i, att_S_ul_i, Jred_lu_i, Jblue_lu_i, e_dot_u_i);
     if (rc) (void)hipStreamSynchronize(ctx->stream);
-    src.release();
     return rc;
 }
 
@@ -3823,14 +3892,14 @@ int tardis_mc_interpolated_source(TardisMcContext *ctx, int64_t interpolate_shel
 // The two CSR indices and the emission row of every line, by counting sort over the index tables (once per set_opacity).
 static int build_source_topology(TardisMcContext *ctx)
 {
-    if (ctx->sf_topo_valid) return TARDIS_MC_OK;
+    if (ctx->sf.topo_valid) return TARDIS_MC_OK;
     const size_t L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans, K = (size_t)ctx->n_levels;
     std::vector<int> l2l(L), edge(K + 1), ttype(T), dest(T), tline(T);
-    HIP_TRY(ctx, hipMemcpyAsync(l2l.data(), ctx->line2level.p, L * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(edge.data(), ctx->block_edge.p, (K + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ttype.data(), ctx->ttype.p, T * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dest.data(), ctx->dest.p, T * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(tline.data(), ctx->tline.p, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(l2l.data(), ctx->ot.line2level.p, L * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(edge.data(), ctx->ot.block_edge.p, (K + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ttype.data(), ctx->ot.ttype.p, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dest.data(), ctx->ot.dest.p, T * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(tline.data(), ctx->ot.tline.p, T * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // lines by upper level (the tables were range-checked by set_opacity)
     std::vector<int> lvl_ptr(K + 1, 0), lvl_line(L);
@@ -3862,25 +3931,25 @@ static int build_source_topology(TardisMcContext *ctx)
                     in_row[(size_t)j] = t; in_src[(size_t)j] = (int)k;
                 }
     }
-    ctx->sf_topo_error.clear();
+    ctx->sf.topo_error.clear();
     for (size_t l = 0; l < L; ++l)
         if (emit_n[l] != 1) {
             char buf[128];
             snprintf(buf, sizeof buf, "line %zu has %d emission rows (transition_type -1) in the macro-atom blocks, expected one", l, emit_n[l]);
-            ctx->sf_topo_error = buf;
+            ctx->sf.topo_error = buf;
             break;
         }
     int rc;
-    if ((rc = upload(ctx, ctx->sf_lvl_ptr, lvl_ptr.data(), K + 1))) return rc;
-    if ((rc = upload(ctx, ctx->sf_lvl_line, lvl_line.data(), L))) return rc;
-    if ((rc = upload(ctx, ctx->sf_in_ptr, in_ptr.data(), K + 1))) return rc;
-    if ((rc = upload(ctx, ctx->sf_in_row, in_row.data(), in_row.size()))) return rc;
-    if ((rc = upload(ctx, ctx->sf_in_src, in_src.data(), in_src.size()))) return rc;
-    if ((rc = upload(ctx, ctx->sf_emit_row, emit_row.data(), L))) return rc;
-    if ((rc = upload(ctx, ctx->sf_emit_level, emit_level.data(), L))) return rc;
+    if ((rc = upload(ctx, ctx->sf.lvl_ptr, lvl_ptr.data(), K + 1))) return rc;
+    if ((rc = upload(ctx, ctx->sf.lvl_line, lvl_line.data(), L))) return rc;
+    if ((rc = upload(ctx, ctx->sf.in_ptr, in_ptr.data(), K + 1))) return rc;
+    if ((rc = upload(ctx, ctx->sf.in_row, in_row.data(), in_row.size()))) return rc;
+    if ((rc = upload(ctx, ctx->sf.in_src, in_src.data(), in_src.size()))) return rc;
+    if ((rc = upload(ctx, ctx->sf.emit_row, emit_row.data(), L))) return rc;
+    if ((rc = upload(ctx, ctx->sf.emit_level, emit_level.data(), L))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors go out of scope)
-    ctx->sf_nnz = (long long)nnz;
-    ctx->sf_topo_valid = true;
+    ctx->sf.nnz = (long long)nnz;
+    ctx->sf.topo_valid = true;
     return TARDIS_MC_OK;
 }
 
@@ -3888,8 +3957,8 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
                               double *att_S_ul, double *Jred_lu, double *Jblue_lu, double *e_dot_u)
 {
     if (!ctx || !volume) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    ctx->sf_valid = false;
-    if (!ctx->est_valid || !ctx->have_opacity || !ctx->have_geometry || !ctx->have_config)
+    drop_products(ctx, ESTIMATORS_CHANGED);
+    if (!ctx->es.est_valid || !ctx->have_opacity || !ctx->have_geometry || !ctx->have_config)
         return fail(ctx, TARDIS_MC_ERR_STATE, "source function needs propagated estimators");
     if (!(time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "time_of_simulation must be positive");
     const int mode = ctx->cfg.line_interaction_type;
@@ -3900,28 +3969,28 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = build_source_topology(ctx);
     if (rc) return rc;
-    if (!ctx->sf_topo_error.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", ctx->sf_topo_error.c_str());
+    if (!ctx->sf.topo_error.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", ctx->sf.topo_error.c_str());
     if ((rc = reduce_estimator_copies(ctx))) return rc;
-    const size_t S = ctx->est_S, L = ctx->est_L, K = (size_t)ctx->n_levels, T = (size_t)ctx->n_trans;
-    const long long nnz = ctx->sf_nnz;
+    const size_t S = ctx->es.est_S, L = ctx->es.est_L, K = (size_t)ctx->n_levels, T = (size_t)ctx->n_trans;
+    const long long nnz = ctx->sf.nnz;
     const bool solve = mode == TARDIS_MC_LINE_MACROATOM && nnz > 0;
-    EstLayout lay = est_layout(S, L, ctx->est_G, ctx->est_copies);
-    const double *est = ctx->est.as<double>();
-    HIP_TRY(ctx, ctx->sf_shell.ensure(3 * S * sizeof(double)));
-    HIP_TRY(ctx, ctx->sf_e.ensure(S * K * sizeof(double)));
-    HIP_TRY(ctx, ctx->sf_att.ensure(S * L * sizeof(double)));
-    HIP_TRY(ctx, ctx->sf_jred.ensure(S * L * sizeof(double)));
-    HIP_TRY(ctx, ctx->sf_jblue.ensure(S * L * sizeof(double)));
+    EstLayout lay = est_layout(S, L, ctx->es.est_G, ctx->es.est_copies);
+    const double *est = ctx->es.est.as<double>();
+    HIP_TRY(ctx, ctx->sf.shell.ensure(3 * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->sf.e.ensure(S * K * sizeof(double)));
+    HIP_TRY(ctx, ctx->sf.att.ensure(S * L * sizeof(double)));
+    HIP_TRY(ctx, ctx->sf.jred.ensure(S * L * sizeof(double)));
+    HIP_TRY(ctx, ctx->sf.jblue.ensure(S * L * sizeof(double)));
     if (solve) {
-        HIP_TRY(ctx, ctx->sf_x[0].ensure(S * K * sizeof(double)));
-        HIP_TRY(ctx, ctx->sf_x[1].ensure(S * K * sizeof(double)));
-        HIP_TRY(ctx, ctx->sf_q.ensure(S * (size_t)nnz * sizeof(double)));
-        HIP_TRY(ctx, ctx->sf_conv.ensure(2 * S * sizeof(double)));
-        if (!ctx->sf_conv_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->sf_conv_host, 2 * 4096 * sizeof(double), hipHostMallocDefault));
+        HIP_TRY(ctx, ctx->sf.x[0].ensure(S * K * sizeof(double)));
+        HIP_TRY(ctx, ctx->sf.x[1].ensure(S * K * sizeof(double)));
+        HIP_TRY(ctx, ctx->sf.q.ensure(S * (size_t)nnz * sizeof(double)));
+        HIP_TRY(ctx, ctx->sf.conv.ensure(2 * S * sizeof(double)));
+        if (!ctx->sf.conv_host) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->sf.conv_host, 2 * 4096 * sizeof(double), hipHostMallocDefault));
         if (S > 4096) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "source function: more than 4096 shells");
     }
-    if (wavelength_cm && (rc = upload(ctx, ctx->sf_wave, wavelength_cm, L))) return rc;
-    double *d_vol = ctx->sf_shell.as<double>(), *d_ne = d_vol + S, *d_nj = d_ne + S;
+    if (wavelength_cm && (rc = upload(ctx, ctx->sf.wave, wavelength_cm, L))) return rc;
+    double *d_vol = ctx->sf.shell.as<double>(), *d_ne = d_vol + S, *d_nj = d_ne + S;
     HIP_TRY(ctx, hipMemcpyAsync(d_vol, volume, S * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
     const double pi = 3.141592653589793;
@@ -3934,22 +4003,22 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
     auto row_grid = [&](int g) { return dim3((unsigned)((K * (size_t)g + 255) / 256), (unsigned)S); };
     {
         auto kernel = g_lvl == 1 ? mc::sf_level_sums_kernel<1> : (g_lvl == 4 ? mc::sf_level_sums_kernel<4> : mc::sf_level_sums_kernel<16>);
-        hipLaunchKernelGGL(kernel, row_grid(g_lvl), dim3(256), 0, ctx->stream, ctx->sf_lvl_ptr.as<int>(), ctx->sf_lvl_line.as<int>(), (int)K,
-                           (long long)L, ctx->sf_exp_tau.as<double>(), est + lay.edot, d_ne, ctx->sf_e.as<double>());
+        hipLaunchKernelGGL(kernel, row_grid(g_lvl), dim3(256), 0, ctx->stream, ctx->sf.lvl_ptr.as<int>(), ctx->sf.lvl_line.as<int>(), (int)K,
+                           (long long)L, ctx->sf.exp_tau.as<double>(), est + lay.edot, d_ne, ctx->sf.e.as<double>());
         HIP_TRY(ctx, hipGetLastError());
     }
-    const double *c_level = ctx->sf_e.as<double>();
+    const double *c_level = ctx->sf.e.as<double>();
     int iterations = 0;
     if (solve) {
         const unsigned gx = (unsigned)std::min<long long>((nnz + 255) / 256, 2048);
-        hipLaunchKernelGGL(mc::sf_gather_q_kernel, dim3(gx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->sf_in_row.as<int>(), nnz,
-                           ctx->prob_t.as<double>(), (long long)T, ctx->sf_q.as<double>());
+        hipLaunchKernelGGL(mc::sf_gather_q_kernel, dim3(gx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->sf.in_row.as<int>(), nnz,
+                           ctx->ot.prob_t.as<double>(), (long long)T, ctx->sf.q.as<double>());
         HIP_TRY(ctx, hipGetLastError());
-        // x ping-pongs between sf_x[0] and sf_x[1]; the first iteration reads e itself.  Every 16 iterations (or at the cap) the per-shell
+        // x ping-pongs between sf.x[0] and sf.x[1]; the first iteration reads e itself.  Every 16 iterations (or at the cap) the per-shell
         // {max |dx|, max |x|} of the last one come to the host.
         auto iterate = g_in == 1 ? mc::sf_iterate_kernel<1> : (g_in == 4 ? mc::sf_iterate_kernel<4> : mc::sf_iterate_kernel<16>);
-        const double *cur = ctx->sf_e.as<double>();
-        const long long cap = ctx->source_max_iterations;
+        const double *cur = ctx->sf.e.as<double>();
+        const long long cap = ctx->sf.max_iterations;
         bool converged = false, diverged = false;
         int worst = 0;
         double worst_ratio = 0.0;
@@ -3957,21 +4026,21 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
             const int n = (int)std::min<long long>(16, cap - iterations);
             const double *prev = cur;
             for (int i = 0; i < n; ++i, ++iterations) {
-                double *next = ctx->sf_x[iterations & 1].as<double>();
-                hipLaunchKernelGGL(iterate, row_grid(g_in), dim3(256), 0, ctx->stream, ctx->sf_in_ptr.as<int>(), ctx->sf_in_src.as<int>(), (int)K,
-                                   nnz, ctx->sf_q.as<double>(), ctx->sf_e.as<double>(), cur, next);
+                double *next = ctx->sf.x[iterations & 1].as<double>();
+                hipLaunchKernelGGL(iterate, row_grid(g_in), dim3(256), 0, ctx->stream, ctx->sf.in_ptr.as<int>(), ctx->sf.in_src.as<int>(), (int)K,
+                                   nnz, ctx->sf.q.as<double>(), ctx->sf.e.as<double>(), cur, next);
                 prev = cur;
                 cur = next;
             }
             HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(mc::sf_convergence_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, prev, cur, (int)K, ctx->sf_conv.as<double>());
+            hipLaunchKernelGGL(mc::sf_convergence_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, prev, cur, (int)K, ctx->sf.conv.as<double>());
             HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->sf_conv_host, ctx->sf_conv.p, 2 * S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->sf.conv_host, ctx->sf.conv.p, 2 * S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             converged = true;
             worst_ratio = -1.0;
             for (size_t s = 0; s < S; ++s) {
-                const double dx = ctx->sf_conv_host[2 * s], xm = ctx->sf_conv_host[2 * s + 1];
+                const double dx = ctx->sf.conv_host[2 * s], xm = ctx->sf.conv_host[2 * s + 1];
                 if (!(dx <= 1e-14 * xm)) converged = false;
                 const bool finite = dx == dx && xm < __builtin_huge_val();  // (NaN or infinite rates: no later iteration repairs them)
                 const double ratio = (finite && xm > 0) ? dx / xm : __builtin_huge_val();
@@ -3979,7 +4048,7 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
                 diverged |= !finite;
             }
         }
-        ctx->last_source_iterations = iterations;
+        ctx->sf.last_iterations = iterations;
         if (!converged) {
             HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
             ctx->timed = true; ctx->chunks_timed = 0;
@@ -3991,31 +4060,31 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
         }
         c_level = cur;
     } else
-        ctx->last_source_iterations = 0;
+        ctx->sf.last_iterations = 0;
     const unsigned lx = (unsigned)std::min<size_t>((L + 255) / 256, 1024);
-    hipLaunchKernelGGL(mc::sf_close_kernel, dim3(lx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->sf_emit_row.as<int>(), ctx->sf_emit_level.as<int>(),
-                       (long long)L, (long long)T, (int)K, ctx->prob_t.as<double>(), c_level, wavelength_cm ? ctx->sf_wave.as<double>() : nullptr,
-                       ctx->nu_line.as<double>(), ctx->sf_exp_tau.as<double>(), est + lay.jblue, d_nj, time_of_simulation, 4 * pi,
-                       ctx->sf_att.as<double>(), ctx->sf_jred.as<double>(), ctx->sf_jblue.as<double>());
+    hipLaunchKernelGGL(mc::sf_close_kernel, dim3(lx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->sf.emit_row.as<int>(), ctx->sf.emit_level.as<int>(),
+                       (long long)L, (long long)T, (int)K, ctx->ot.prob_t.as<double>(), c_level, wavelength_cm ? ctx->sf.wave.as<double>() : nullptr,
+                       ctx->ot.nu_line.as<double>(), ctx->sf.exp_tau.as<double>(), est + lay.jblue, d_nj, time_of_simulation, 4 * pi,
+                       ctx->sf.att.as<double>(), ctx->sf.jred.as<double>(), ctx->sf.jblue.as<double>());
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     ctx->timed = true;
     ctx->chunks_timed = 0;
-    if (att_S_ul) HIP_TRY(ctx, hipMemcpyAsync(att_S_ul, ctx->sf_att.p, S * L * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (Jred_lu) HIP_TRY(ctx, hipMemcpyAsync(Jred_lu, ctx->sf_jred.p, S * L * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (Jblue_lu) HIP_TRY(ctx, hipMemcpyAsync(Jblue_lu, ctx->sf_jblue.p, S * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (att_S_ul) HIP_TRY(ctx, hipMemcpyAsync(att_S_ul, ctx->sf.att.p, S * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (Jred_lu) HIP_TRY(ctx, hipMemcpyAsync(Jred_lu, ctx->sf.jred.p, S * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (Jblue_lu) HIP_TRY(ctx, hipMemcpyAsync(Jblue_lu, ctx->sf.jblue.p, S * L * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (e_dot_u) {  // [S][levels] -> level-major, as the reference returns it
         HIP_TRY(ctx, ctx->staging.ensure(S * K * sizeof(double)));
         HIP_TRY(ctx, launch_transpose(ctx->stream, c_level, ctx->staging.as<double>(), (long long)S, (long long)K));
         HIP_TRY(ctx, hipMemcpyAsync(e_dot_u, ctx->staging.p, S * K * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->sf_c_level = c_level;
-    ctx->sf_valid = true;
+    ctx->sf.c_level = c_level;
+    ctx->sf.valid = true;
     return TARDIS_MC_OK;
 }
 
-int tardis_mc_last_source_iterations(TardisMcContext *ctx) { return ctx ? ctx->last_source_iterations : -1; }
+int tardis_mc_last_source_iterations(TardisMcContext *ctx) { return ctx ? ctx->sf.last_iterations : -1; }
 
 /* ---- opacity update from level populations (opacity_update.hpp) --------------------------------------- */
 int tardis_mc_opacity_update_path(int64_t rows) { return opup::choose_path((long long)rows); }
@@ -4032,7 +4101,7 @@ int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
     if (d->n_levels <= 0 || d->n_levels > 0x7ffffff0LL || !d->f_lu || !d->wavelength_cm || !d->g_lower || !d->g_upper || !d->level_lower || !d->level_upper)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid line data");
     const bool coef = d->transition_probability_coef != nullptr;
-    if (coef && !ctx->h_macro)
+    if (coef && !ctx->ot.h_macro)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "transition_probability_coef given, but the resident opacity state has no macro-atom tables");
     // everything the kernels index with is checked here, on the host
     std::vector<int> lo(L), up(L);
@@ -4043,7 +4112,7 @@ int tardis_mc_set_line_data(TardisMcContext *ctx, const TardisMcLineData *d)
         up[i] = (int)d->level_upper[i];
     }
     if (coef) {
-        const std::vector<int> &ttype = ctx->h_idx[2], &tline = ctx->h_idx[4];
+        const std::vector<int> &ttype = ctx->ot.h_idx[2], &tline = ctx->ot.h_idx[4];
         if (ttype.size() != T || tline.size() != T) return fail(ctx, TARDIS_MC_ERR_STATE, "the resident index tables do not match the transition count");
         for (size_t t = 0; t < T; ++t)
             if (tline[t] < 0 || tline[t] >= (int)L) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "transition_line_id[%zu] out of range", t);
@@ -4082,7 +4151,7 @@ static int opacity_update_check(TardisMcContext *ctx, const TardisMcOpacityUpdat
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "j_blues_mode 0 needs t_radiative and dilution_factor");
     const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines;
     if (mode == 1) {
-        if (!ctx->est_valid || !ctx->est_propagated || ctx->est_S != S || ctx->est_L != L)
+        if (!ctx->es.est_valid || !ctx->es.est_propagated || ctx->es.est_S != S || ctx->es.est_L != L)
             return fail(ctx, TARDIS_MC_ERR_STATE, "j_blues_mode 1 needs propagated estimators");
         if (!u->volume || !(u->time_of_simulation > 0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "j_blues_mode 1 needs volume and a positive time_of_simulation");
     }
@@ -4109,9 +4178,9 @@ static int opacity_update_buffers(TardisMcContext *ctx)
 {
     const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, K = (size_t)ctx->ou.levels;
     int rc;
-    const bool blocks = ctx->ou.have_coef && ctx->h_macro && ctx->n_levels > 0;
+    const bool blocks = ctx->ou.have_coef && ctx->ot.h_macro && ctx->n_levels > 0;
     if (blocks && ctx->ou.long_rows_built != ctx->ou.long_rows) {
-        if ((rc = upload_row_form_list(ctx, ctx->h_idx[1], ctx->ou.long_rows, ctx->ou.long_blocks, &ctx->ou.n_long))) return rc;
+        if ((rc = upload_row_form_list(ctx, ctx->ot.h_idx[1], ctx->ou.long_rows, ctx->ou.long_blocks, &ctx->ou.n_long))) return rc;
         ctx->ou.long_rows_built = ctx->ou.long_rows;
     }
     HIP_TRY(ctx, ctx->ou.n_t.ensure(K * S * sizeof(double)));
@@ -4132,7 +4201,7 @@ int tardis_mc_update_opacity(TardisMcContext *ctx, const TardisMcOpacityUpdate *
     const int mode = u->j_blues_mode;
     const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou.levels;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->sf_valid = false;
+    drop_products(ctx, OPACITY_UPDATE_BEGINS);
     ctx->ou.valid = false;
     ctx->pl.valid = false;  // (the populations are the caller's from here on)
     if ((rc = opacity_update_buffers(ctx))) return rc;
@@ -4140,7 +4209,7 @@ int tardis_mc_update_opacity(TardisMcContext *ctx, const TardisMcOpacityUpdate *
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // populations [K,S] -> [S][K]
     HIP_TRY(ctx, host_copy(ctx, {{(void *)u->level_number_density, ctx->staging.p, K * S * sizeof(double)}}, true));
-    if (u->electron_density && (rc = upload(ctx, ctx->n_e, u->electron_density, S))) return rc;
+    if (u->electron_density && (rc = upload(ctx, ctx->ot.n_e, u->electron_density, S))) return rc;
     double *d_t = ctx->ou.shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
     if (mode == 0) {
         HIP_TRY(ctx, hipMemcpyAsync(d_t, u->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -4161,7 +4230,7 @@ static int opacity_update_stages(TardisMcContext *ctx, const TardisMcOpacityUpda
 {
     const int mode = u->j_blues_mode;
     const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans, K = (size_t)ctx->ou.levels;
-    const bool blocks = ctx->ou.have_coef && ctx->h_macro && ctx->n_levels > 0;
+    const bool blocks = ctx->ou.have_coef && ctx->ot.h_macro && ctx->n_levels > 0;
     double *d_t = ctx->ou.shell.as<double>() + S, *d_w = d_t + S;  // (the layout of radiation_field_enqueue's work: volume, t_rad, W, norm)
     int rc;
     if (mode == 1 && (rc = radiation_field_enqueue(ctx, u->time_of_simulation, u->volume, u->w_epsilon, u->detailed_optical_window, ctx->ou.shell,
@@ -4175,7 +4244,7 @@ static int opacity_update_stages(TardisMcContext *ctx, const TardisMcOpacityUpda
         auto kernel = mode == 0 ? mc::opacity_line_kernel<true> : mc::opacity_line_kernel<false>;
         hipLaunchKernelGGL(kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->ou.n_t.as<double>(), ctx->ou.level_lower.as<int>(),
                            ctx->ou.level_upper.as<int>(), ctx->ou.f_lu.as<double>(), ctx->ou.wave.as<double>(), ctx->ou.g_lower.as<double>(),
-                           ctx->ou.g_upper.as<double>(), ctx->nu_line.as<double>(), d_t, d_w, (long long)K, (long long)L, k, ctx->tau_t.as<double>(),
+                           ctx->ou.g_upper.as<double>(), ctx->ot.nu_line.as<double>(), d_t, d_w, (long long)K, (long long)L, k, ctx->ot.tau_t.as<double>(),
                            ctx->ou.beta_t.as<double>(), ctx->ou.sef_t.as<double>(), ctx->ou.j_t.as<double>());
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -4185,16 +4254,16 @@ static int opacity_update_stages(TardisMcContext *ctx, const TardisMcOpacityUpda
         const long long long_rows = ctx->ou.long_rows < 0 ? opup::LONG_BLOCK_ROWS : ctx->ou.long_rows;
         if (n_long < n_blocks) {
             const long long n = n_blocks * (long long)S;
-            hipLaunchKernelGGL(mc::opacity_block_lane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->block_edge.as<int>(), (int)n_blocks,
-                               (long long)T, (long long)L, (int)S, long_rows, ctx->ou.coef.as<double>(), ctx->tline.as<int>(), ctx->ttype.as<int>(),
-                               ctx->ou.beta_t.as<double>(), ctx->ou.sef_t.as<double>(), ctx->ou.j_t.as<double>(), ctx->prob_t.as<double>());
+            hipLaunchKernelGGL(mc::opacity_block_lane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ot.block_edge.as<int>(), (int)n_blocks,
+                               (long long)T, (long long)L, (int)S, long_rows, ctx->ou.coef.as<double>(), ctx->ot.tline.as<int>(), ctx->ot.ttype.as<int>(),
+                               ctx->ou.beta_t.as<double>(), ctx->ou.sef_t.as<double>(), ctx->ou.j_t.as<double>(), ctx->ot.prob_t.as<double>());
             HIP_TRY(ctx, hipGetLastError());
         }
         if (n_long > 0) {
             const long long n = n_long * (long long)S * 16;
             hipLaunchKernelGGL(mc::opacity_block_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ou.long_blocks.as<int>(), (int)n_long,
-                               ctx->block_edge.as<int>(), (long long)T, (long long)L, (int)S, ctx->ou.coef.as<double>(), ctx->tline.as<int>(), ctx->ttype.as<int>(),
-                               ctx->ou.beta_t.as<double>(), ctx->ou.sef_t.as<double>(), ctx->ou.j_t.as<double>(), ctx->prob_t.as<double>());
+                               ctx->ot.block_edge.as<int>(), (long long)T, (long long)L, (int)S, ctx->ou.coef.as<double>(), ctx->ot.tline.as<int>(), ctx->ot.ttype.as<int>(),
+                               ctx->ou.beta_t.as<double>(), ctx->ou.sef_t.as<double>(), ctx->ou.j_t.as<double>(), ctx->ot.prob_t.as<double>());
             HIP_TRY(ctx, hipGetLastError());
         }
     }
@@ -4231,8 +4300,8 @@ int tardis_mc_get_opacity(TardisMcContext *ctx, double *tau_sobolev, double *tra
     const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, T = (size_t)ctx->n_trans;
     HIP_TRY(ctx, ctx->staging.ensure(std::max(L, T) * S * sizeof(double)));  // (the largest of them first: the staging grows once)
     int rc;
-    if ((rc = download_transposed(ctx, tau_sobolev, ctx->tau_t.as<double>(), L))) return rc;
-    if ((rc = download_transposed(ctx, transition_probabilities, ctx->prob_t.as<double>(), T))) return rc;
+    if ((rc = download_transposed(ctx, tau_sobolev, ctx->ot.tau_t.as<double>(), L))) return rc;
+    if ((rc = download_transposed(ctx, transition_probabilities, ctx->ot.prob_t.as<double>(), T))) return rc;
     if ((rc = download_transposed(ctx, beta_sobolev, ctx->ou.beta_t.as<double>(), L))) return rc;
     if ((rc = download_transposed(ctx, stimulated_emission_factor, ctx->ou.sef_t.as<double>(), L))) return rc;
     return download_transposed(ctx, j_blues, ctx->ou.j_t.as<double>(), L);
@@ -4487,15 +4556,15 @@ static int nlte_stage(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p, const
     mc::NlteRateArgs r{};
     r.S = (int)S; r.L = (long long)L; r.NL = (long long)NL;
     r.line_id = ctx->nl.line_id.as<int>(); r.a_ul = ctx->nl.a_ul.as<double>(); r.b_ul = ctx->nl.b_ul.as<double>(); r.b_lu = ctx->nl.b_lu.as<double>();
-    r.nu_line = ctx->nu_line.as<double>(); r.beta_t = beta_t; r.t_rad = d_t; r.w = d_w;
+    r.nu_line = ctx->ot.nu_line.as<double>(); r.beta_t = beta_t; r.t_rad = d_t; r.w = d_w;
     r.planck_coef = 2 * h / (c * c); r.h = h; r.k_b = k_b; r.w_epsilon = p->w_epsilon; r.c_ang = c * 1e8; r.optical_window = p->detailed_optical_window;
     r.r_ul_t = ctx->nl.r_ul.as<double>(); r.r_lu_t = ctx->nl.r_lu.as<double>();
     const int jmode = ctx->nl.coronal ? mc::NLTE_J_CORONAL : p->j_blues_mode == 1 ? mc::NLTE_J_DETAILED : mc::NLTE_J_DILUTE;
     if (jmode == mc::NLTE_J_DETAILED) {  // the estimators' own t_rad / W / norm, as the j_blues kernel of the stages behind will compute them again
         if ((rc = radiation_field_enqueue(ctx, p->time_of_simulation, p->volume, p->w_epsilon, p->detailed_optical_window, ctx->nl.work, nullptr))) return rc;
-        EstLayout e = est_layout(ctx->est_S, ctx->est_L, ctx->est_G, ctx->est_copies);
+        EstLayout e = est_layout(ctx->es.est_S, ctx->es.est_L, ctx->es.est_G, ctx->es.est_copies);
         const double *work = ctx->nl.work.as<double>();
-        r.t_rad = work + S; r.w = work + 2 * S; r.norm = work + 3 * S; r.jblue_t = ctx->est.as<double>() + e.jblue;
+        r.t_rad = work + S; r.w = work + 2 * S; r.norm = work + 3 * S; r.jblue_t = ctx->es.est.as<double>() + e.jblue;
     }
     if (NL > 0) {
         const unsigned bx = (unsigned)std::min<size_t>((NL + 255) / 256, 1024);
@@ -4522,7 +4591,7 @@ static int nlte_stage(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p, const
     a.lbf_t = ctx->pl.lbf_t.as<double>(); a.x_t = ctx->nl.x_t.as<double>(); a.status = ctx->nl.status.as<int>(); a.scratch = ctx->nl.scratch.as<double>();
     if (ctx->nc.have && ctx->nc.pairs > 0) {  // (the resident electron density is still the previous update's: this call installs its own behind the solve)
         a.NP = ctx->nc.pairs; a.sp_pair_edge = ctx->nc.sp_pair_edge.as<int>(); a.pair_lower = ctx->nc.lower.as<int>(); a.pair_upper = ctx->nc.upper.as<int>();
-        a.c_ul_t = ctx->nc.c_ul.as<double>(); a.c_lu_t = ctx->nc.c_lu.as<double>(); a.n_e = ctx->n_e.as<double>();
+        a.c_ul_t = ctx->nc.c_ul.as<double>(); a.c_lu_t = ctx->nc.c_lu.as<double>(); a.n_e = ctx->ot.n_e.as<double>();
     }
     for (const nlte::Launch &l : ctx->nl.launches) {
         a.list = ctx->nl.list.as<int>() + l.first;
@@ -4690,13 +4759,14 @@ static int plasma_update_status(TardisMcContext *ctx)
 static int plasma_update_install(TardisMcContext *ctx, const TardisMcOpacityUpdate *u)
 {
     const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou.levels;
-    ctx->sf_valid = ctx->ou.valid = ctx->ou.timed = false;
+    drop_products(ctx, OPACITY_UPDATE_BEGINS);
+    ctx->ou.valid = ctx->ou.timed = false;
     const unsigned bx = (unsigned)std::min<size_t>((K + 255) / 256, 1024);
     hipLaunchKernelGGL(mc::plasma_population_kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->pl.lbf_t.as<double>(), ctx->pl.level_ion.as<int>(),
                        ctx->pl.z.as<double>(), ctx->pl.n_ion.as<double>(), (long long)K, (int)S, ctx->ou.n_t.as<double>());
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, ctx->n_e.ensure(S * sizeof(double)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->n_e.p, ctx->pl.n_e.p, S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, ctx->ot.n_e.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ot.n_e.p, ctx->pl.n_e.p, S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[4], ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ou.ev[0], ctx->stream));
     int rc;
@@ -4789,18 +4859,18 @@ int tardis_mc_comm_init(TardisMcContext *ctx, int rank, int world_size, const ui
 int tardis_mc_allreduce_estimators(TardisMcContext *ctx)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
-    if (!ctx->est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "no estimators allocated");
+    if (!ctx->es.est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "no estimators allocated");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->sf_valid = false;
+    drop_products(ctx, ESTIMATORS_CHANGED);
     int rc = reduce_estimator_copies(ctx);
     if (rc) return rc;
     if (!ctx->comm) {
         if (ctx->world <= 1) return TARDIS_MC_OK;  // single process, no communicator: nothing to reduce
         return fail(ctx, TARDIS_MC_ERR_STATE, "tardis_mc_comm_init has not been called");
     }
-    EstLayout e = est_layout(ctx->est_S, ctx->est_L, ctx->est_G, ctx->est_copies);
+    EstLayout e = est_layout(ctx->es.est_S, ctx->es.est_L, ctx->es.est_G, ctx->es.est_copies);
     // ncclDouble = 8, ncclSum = 0; one in-place all-reduce over [J | nu_bar | v-hist | j_blue | Edotlu]
-    int r = g_rccl.AllReduce(ctx->est.p, ctx->est.p, e.reduce_elems, 8, 0, ctx->comm, ctx->stream);
+    int r = g_rccl.AllReduce(ctx->es.est.p, ctx->es.est.p, e.reduce_elems, 8, 0, ctx->comm, ctx->stream);
     if (r != 0) return fail(ctx, TARDIS_MC_ERR_COMM, "ncclAllReduce failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
     return TARDIS_MC_OK;
 }
@@ -4814,7 +4884,7 @@ int tardis_mc_comm_check(TardisMcContext *ctx, int *out_ranks)
     *out_ranks = 0;
     if (!ctx->comm) return fail(ctx, TARDIS_MC_ERR_STATE, "tardis_mc_comm_init has not been called");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DevBuf cell;
+    ScopedDevBuf cell;
     HIP_TRY(ctx, cell.ensure(sizeof(double)));
     hipLaunchKernelGGL(comm_check_fill_kernel, dim3(1), dim3(64), 0, ctx->stream, cell.as<double>(), (double)(ctx->rank + 1));
     hipError_t e = hipGetLastError();
@@ -4822,7 +4892,6 @@ int tardis_mc_comm_check(TardisMcContext *ctx, int *out_ranks)
     double got = 0.0;
     if (e == hipSuccess && r == 0) e = hipMemcpyAsync(&got, cell.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && r == 0) e = hipStreamSynchronize(ctx->stream);
-    cell.release();
     HIP_TRY(ctx, e);
     if (r != 0) return fail(ctx, TARDIS_MC_ERR_COMM, "ncclAllReduce failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
     const double want = 0.5 * (double)ctx->world * (double)(ctx->world + 1);
@@ -4837,7 +4906,7 @@ int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const do
 {
     if (!ctx || !x || !out || n <= 0) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DevBuf dx, dy, dout, scratch;
+    ScopedDevBuf dx, dy, dout, scratch;
     size_t nx = (op == 7) ? 1 : (size_t)n;
     HIP_TRY(ctx, dx.ensure(nx * 8));
     HIP_TRY(ctx, dout.ensure((size_t)n * 8));
@@ -4850,7 +4919,6 @@ int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const do
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    dx.release(); dy.release(); dout.release(); scratch.release();
     return TARDIS_MC_OK;
 }
 
@@ -4858,7 +4926,7 @@ int tardis_mc_debug_microbench(TardisMcContext *ctx, int which, int64_t n_double
 {
     if (!ctx || !out_ms || n_doubles < 1024 || iters < 1 || blocks < 1) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DevBuf table, sink;
+    ScopedDevBuf table, sink;
     HIP_TRY(ctx, table.ensure((size_t)n_doubles * 8));
     HIP_TRY(ctx, sink.ensure(8));
     HIP_TRY(ctx, hipMemsetAsync(table.p, 0, (size_t)n_doubles * 8, ctx->stream));
@@ -4874,7 +4942,6 @@ int tardis_mc_debug_microbench(TardisMcContext *ctx, int which, int64_t n_double
     float ms = 0.f;
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
     *out_ms = ms;
-    table.release(); sink.release();
     return TARDIS_MC_OK;
 }
 
