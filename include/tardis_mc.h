@@ -680,7 +680,16 @@ int tardis_mc_plasma_update_path(int64_t levels);
  * Kernels (csrc/nlte_excitation.hpp): a streaming kernel writes r_ul / r_lu of the NLTE lines; then one workgroup per (species, shell)
  * builds and solves the system on a column-major matrix of odd leading dimension, either in its LDS (species of up to 141 levels) or in
  * a slab of HBM per (species, shell) -- same operations, same order, same bits (csrc/nlte_plan.hpp chooses per species).  No workgroup
- * waits on another, no atomics: two calls give identical bits. */
+ * waits on another, no atomics: two calls give identical bits.
+ * A species in HBM has a third form, the blocked one: a right-looking LU in panels of 32 columns.  One workgroup per (species, shell)
+ * eliminates inside a panel serially in k, multipliers kept in place below the diagonal; then workgroups all over the chip, each the
+ * owner of 32 whole columns right of the panel (b is the last of them), apply the panel's row swaps to their columns, form their part
+ * of the row block U by the recurrence u_k = ((a_k - l_k0 u_0) - l_k1 u_1) - ... and update the rows below as acc = a_ij, then
+ * acc = acc - l_ik u_kj for the panel's k in ascending order: the products are never summed first, nothing is fused, so an entry sees
+ * exactly the roundings the unblocked order gives it, in the same order, and the pivot search meets the same column.  The three forms
+ * therefore give the same bits (tests/nlte_blocked_ref.py restates the blocked order in NumPy and compares).  Launches follow each other
+ * in stream order and nothing else orders them: no workgroup waits on another, no flags, no atomics; a system that has failed is
+ * skipped by the launches behind it. */
 typedef struct TardisMcNlteData {
     int64_t n_species;                   /* NS */
     const int64_t *species_ion;          /* [NS] indices into the plasma data's ions, distinct */
@@ -723,8 +732,14 @@ int tardis_mc_get_nlte(TardisMcContext *ctx, double *level_boltzmann_factor, dou
 int tardis_mc_last_nlte_ms(TardisMcContext *ctx, double *out_assemble_ms, double *out_solve_ms);
 /* Which form of the solve kernel a species of `levels` levels takes (csrc/nlte_plan.hpp): 0 the LDS form, 1 the global-memory form.
  * Host only; both forms run the same operations in the same order.  Option "nlte_lds_levels" (-1, the default: this rule; n >= 0:
- * species of n levels or more take the global form -- measurements and tests only). */
+ * species of n levels or more take the global form -- measurements and tests only).  Where the matrix lives: a species in the
+ * blocked form answers 1. */
 int tardis_mc_nlte_solve_path(int64_t levels);
+/* Which form of the solve a species of `levels` levels takes under the rule (csrc/nlte_plan.hpp): 0 the LDS form, 1 the one-workgroup
+ * global-memory form, 2 the blocked form (panels by one workgroup, the trailing update over the whole chip).  Host only.  Option
+ * "nlte_blocked_levels" (-1, the default: this rule; n >= 0: of the species that are not in LDS those of n levels or more take the
+ * blocked form, 0: all of them -- measurements and tests only); with "nlte_lds_levels" = 0 it reaches every species. */
+int tardis_mc_nlte_solve_form(int64_t levels);
 
 /* ---- collisional rates in the NLTE excitation stage (atomic data with collision_data) -------------------------------------------
  * What LevelBoltzmannFactorNLTE._calculate_general adds to every species' rate matrix when the atomic data carry collision_data:
@@ -837,6 +852,11 @@ int tardis_mc_comm_check(TardisMcContext *ctx, int *out_ranks);
  * op: 0 x+y, 1 x*y, 2 x/y, 3 sqrt(x), 4 log(x) [engine's portable log], 5 exp(x), 6 x*y+x (un-fused),
  *     7 MT19937 doubles of seed (uint32)x[0] (n outputs), 8 floor(x), 9 x/y through the engine's exact 3-fma division. */
 int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const double *y, double *out, int64_t n);
+/* The elimination and back substitution of the blocked form of the NLTE solve on dense systems, for tests: m [n_systems][n][n]
+ * row-major, b [n_systems][n]; x [n_systems][n] (rows of a failed system are 0.0) and status [n_systems] (0, 1 + the step of a zero or
+ * non-finite pivot, n + 1: x[0] == 0, n + 2: an x that is not finite) come back.  Touches nothing resident, needs no opacity state.
+ * TARDIS_MC_ERR_UNSUPPORTED beyond the scratch bound of the global form. */
+int tardis_mc_debug_nlte_solve(TardisMcContext *ctx, int64_t n, int64_t n_systems, const double *m, const double *b, double *x, int32_t *status);
 /* Memory-system micro-benchmarks used to size the kernels (design input): which = 0 random fp64 atomics (agent
  * scope), 1 same at workgroup scope in a per-XCD slice, 2/3 the same with 16 consecutive doubles per 16 lanes,
  * 4 random 8-byte loads, 5 16-lane-coalesced loads; 15 a wide coalesced copy of the table's first half onto its second (iters

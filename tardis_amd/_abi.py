@@ -151,6 +151,10 @@ class TardisMcPlasmaUpdate(C.Structure):
     ]
 
 
+# tardis_mc_nlte_solve_form: the forms of the NLTE solve; options "nlte_lds_levels" / "nlte_blocked_levels" move their thresholds
+NLTE_FORMS = ("lds", "global", "blocked")
+
+
 class TardisMcNlteData(C.Structure):
     """The NLTE species of the plasma update and their lines (tardis_mc_set_nlte_data)."""
     _fields_ = [

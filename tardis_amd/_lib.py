@@ -71,6 +71,7 @@ SYMBOLS = {
     "tardis_mc_get_nlte": (_i, [_vp, _vp, _vp]),
     "tardis_mc_last_nlte_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 2),
     "tardis_mc_nlte_solve_path": (_i, [C.c_int64]),
+    "tardis_mc_nlte_solve_form": (_i, [C.c_int64]),
     "tardis_mc_set_nlte_collision_data": (_i, [_vp, _vp]),
     "tardis_mc_check_nlte_collision_data": (_i, [_vp, C.c_int64, _vp, C.c_double, C.c_int64, _vp]),
     "tardis_mc_get_nlte_collision_rates": (_i, [_vp, _vp, _vp]),
@@ -84,6 +85,7 @@ SYMBOLS = {
     "tardis_mc_allreduce_estimators": (_i, [_vp]),
     "tardis_mc_comm_check": (_i, [_vp, C.POINTER(_i)]),
     "tardis_mc_debug_eval": (_i, [_vp, _i, _vp, _vp, _vp, C.c_int64]),
+    "tardis_mc_debug_nlte_solve": (_i, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp]),
     "tardis_mc_debug_microbench": (_i, [_vp, _i, C.c_int64, _i, _i, C.POINTER(C.c_double)]),
 }
 

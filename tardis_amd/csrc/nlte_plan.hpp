@@ -16,6 +16,9 @@
 // 163 840 bytes on gfx950: work_bytes(141) = 163 560 fits, work_bytes(142) does not.  Measured (profiles/nlte_excitation.txt, each
 // species alone, all 20 shells): the LDS form is ahead at every size that fits -- 0.010 against 0.012 ms at 2 levels, 0.157 / 0.255
 // at 61, 0.509 / 0.951 at 125 -- so the rule is "LDS whenever it fits".
+// A species in HBM is eliminated either by its one workgroup (FORM_GLOBAL) or by the blocked form (FORM_BLOCKED: panels by one
+// workgroup, the trailing update by workgroups all over the chip); choose_form and plan_blocked below, pinned by
+// tests/test_nlte_blocked_plan.py.  Same slab, same roundings, same order: same bits again.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -99,6 +102,70 @@ inline LaunchPlan plan_launches(const std::vector<int> &levels, long long n_shel
     }
     if ((int)p.list.size() > first) p.launches.push_back({first, (int)p.list.size() - first, 0, true});
     return p;
+}
+
+// The blocked form: a species in HBM whose elimination is spread over the chip (nlte_excitation.hpp).  Panels of PANEL_COLUMNS columns are
+// factored by one workgroup per (species, shell); the trailing matrix, with b as its last column, is updated by workgroups that each own
+// a strip of TILE_COLUMNS whole columns (a row swap moves entries along a column, so a column has one owner and no workgroup waits on
+// another) and walk it in blocks of TILE_ROWS rows.  The slab is the one of the global form: same layout, same bytes, same offsets.
+constexpr int FORM_LDS = 0, FORM_GLOBAL = 1, FORM_BLOCKED = 2;
+constexpr int PANEL_COLUMNS = 32;                         // NB
+constexpr int TILE_COLUMNS = 32, TILE_ROWS = 128;         // a 256-thread workgroup holds 4 x 4 entries per thread in registers
+// species of this many levels or more, of those that are not in LDS, take the blocked form under the rule.  Measured
+// (profiles/nlte_blocked.txt, each species alone, all 20 shells, one-workgroup / blocked solve in ms): 1.61 / 0.80 at 158 levels,
+// 4.04 / 1.43 at 234, 16.5 / 3.45 at 400, 76.7 / 6.78 at 586, 513 / 20.3 at 1071 -- the blocked form is ahead at every measured size,
+// by far more than the arms' spread, and 158 is the smallest of them (the synthetic data have no ion of 142 .. 157 levels)
+constexpr long long BLOCKED_FORM_LEVELS = 158;
+
+// `lds_threshold` as in choose_path; `blocked_threshold` < 0: the rule, otherwise species of that many levels or more that are not in
+// LDS take the blocked form (option nlte_blocked_levels; 0: every one of them).  A species choose_path puts in LDS is never blocked.
+inline int choose_form(long long levels, long long lds_threshold = -1, long long blocked_threshold = -1)
+{
+    if (choose_path(levels, lds_threshold) == PATH_LDS) return FORM_LDS;
+    return levels >= (blocked_threshold < 0 ? BLOCKED_FORM_LEVELS : blocked_threshold) ? FORM_BLOCKED : FORM_GLOBAL;
+}
+
+inline long long panel_steps(long long n) { return n <= 0 ? 0 : (n + PANEL_COLUMNS - 1) / PANEL_COLUMNS; }
+// the strips of the trailing launch of the panel that starts at column c0: the columns right of the panel, and b
+inline long long trailing_strips(long long n, long long c0)
+{
+    if (c0 >= n) return 0;
+    const long long right = n - std::min<long long>(n, c0 + PANEL_COLUMNS) + 1;
+    return (right + TILE_COLUMNS - 1) / TILE_COLUMNS;
+}
+
+// The species of `plan`'s launch of the global form (if it has one), split by choose_form: `single` keeps the one-workgroup kernel,
+// `blocked` takes the blocked form; both in the plan's order, each with the slab offsets plan_launches assigned.  The blocked set is
+// eliminated in `steps` = ceil(max n / PANEL_COLUMNS) panel steps; step t (c0 = t PANEL_COLUMNS) is one panel launch of
+// (panel_x, panel_y) = (blocked species, shells) workgroups and one trailing launch of (trailing_x, trailing_y, trailing_z) = (the most
+// strips a blocked species still has, blocked species, shells).  Workgroups past a species' last panel or strip exit.
+struct BlockedStep { unsigned panel_x, panel_y, trailing_x, trailing_y, trailing_z; };
+struct BlockedPlan {
+    std::vector<int> single, blocked;
+    std::vector<long long> single_slab, blocked_slab;
+    std::vector<BlockedStep> steps;
+};
+inline BlockedPlan plan_blocked(const LaunchPlan &plan, const std::vector<int> &levels, long long n_shells, long long blocked_threshold = -1)
+{
+    BlockedPlan b;
+    long long largest = 0;
+    for (const Launch &l : plan.launches) {
+        if (!l.global) continue;
+        for (int q = l.first; q < l.first + l.count; ++q) {
+            const int sp = plan.list[(size_t)q];
+            // (a species of the global launch is not in LDS: a threshold of 0 for choose_path says so again)
+            if (choose_form(levels[(size_t)sp], 0, blocked_threshold) == FORM_BLOCKED) {
+                b.blocked.push_back(sp); b.blocked_slab.push_back(plan.slab[(size_t)q]);
+                largest = std::max<long long>(largest, levels[(size_t)sp]);
+            } else { b.single.push_back(sp); b.single_slab.push_back(plan.slab[(size_t)q]); }
+        }
+    }
+    for (long long t = 0; t < panel_steps(largest); ++t) {
+        long long strips = 0;
+        for (int sp : b.blocked) strips = std::max(strips, trailing_strips(levels[(size_t)sp], t * PANEL_COLUMNS));
+        b.steps.push_back({(unsigned)b.blocked.size(), (unsigned)n_shells, (unsigned)strips, (unsigned)b.blocked.size(), (unsigned)n_shells});
+    }
+    return b;
 }
 
 // What tardis_mc_set_nlte_data checks before it indexes anything, on plain arrays: the species against the ions (ion_level_edge[I+1]),

@@ -455,14 +455,20 @@ struct TardisMcContext {
     struct NlteExcitation {
         DevBuf line_id, a_ul, b_ul, b_lu, lower, upper, sp_k0, sp_n, sp_x0, sp_line_edge, list, slab;
         DevBuf r_ul, r_lu, x_t, status, scratch, work;
+        // the blocked form (nlte::plan_blocked): the global launch's species as [one-workgroup | blocked] with their slab offsets, and the
+        // pivot rows of the blocked systems [S][NX]
+        DevBuf form_list, form_slab, pivrow;
         std::vector<int> h_n, h_ion, h_status;
         std::vector<nlte::Launch> launches;
+        std::vector<nlte::BlockedStep> steps;
+        int n_single = 0, n_blocked = 0;
+        long long blocked_levels = -1, blocked_built = -2;  // option nlte_blocked_levels: -1 the rule of nlte_plan.hpp, else the threshold itself
         bool have = false, valid = false, timed = false, ran = false;  // (have: NLTE data installed; valid: lbf_t and x are those of the last successful update's NLTE stage)
         int coronal = 0, classical = 0;
         long long species = 0, lines = 0, nx = 0, scratch_doubles = 0;
         long long lds_levels = -1, lists_built = -2;  // option nlte_lds_levels: -1 the rule of nlte_plan.hpp, else the threshold itself
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // start | rates | solve (tardis_mc_last_nlte_ms)
-        void release() { release_buffers(line_id, a_ul, b_ul, b_lu, lower, upper, sp_k0, sp_n, sp_x0, sp_line_edge, list, slab, r_ul, r_lu, x_t, status, scratch, work); destroy_events(ev); }
+        void release() { release_buffers(line_id, a_ul, b_ul, b_lu, lower, upper, sp_k0, sp_n, sp_x0, sp_line_edge, list, slab, r_ul, r_lu, x_t, status, scratch, work, form_list, form_slab, pivrow); destroy_events(ev); }
     } nl;
     // Collisional rates of the NLTE species (nlte_excitation.hpp).  Per set_nlte_collision_data: the temperature grid, C_ul as [NT][NP], delta_e,
     // 1 / g_ratio, the pairs' local levels and the species' pair edges.  Per update_plasma: c_ul / c_lu [S][NP] (tardis_mc_get_nlte_collision_rates).
@@ -2314,6 +2320,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "plasma_update_long_rows") ctx->pl.long_rows = value < 0 ? -1 : value;
     else if (n == "plasma_max_iterations") ctx->pl.max_iterations = std::max<long long>(1, value);
     else if (n == "nlte_lds_levels") ctx->nl.lds_levels = value < 0 ? -1 : value;
+    else if (n == "nlte_blocked_levels") ctx->nl.blocked_levels = value < 0 ? -1 : value;
     else return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown option '%s'", name);
     return TARDIS_MC_OK;
 }
@@ -4371,6 +4378,7 @@ int tardis_mc_set_plasma_data(TardisMcContext *ctx, const TardisMcPlasmaData *d)
 
 /* ---- NLTE excitation of selected species inside update_plasma (nlte_excitation.hpp) ------------------------ */
 int tardis_mc_nlte_solve_path(int64_t levels) { return nlte::choose_path((long long)levels); }
+int tardis_mc_nlte_solve_form(int64_t levels) { return nlte::choose_form((long long)levels); }
 
 int tardis_mc_check_nlte_data(const TardisMcNlteData *d, int64_t n_ions, const int64_t *ion_level_edge, int64_t n_lines, const int64_t *level_lower,
                               const int64_t *level_upper)
@@ -4382,7 +4390,8 @@ int tardis_mc_check_nlte_data(const TardisMcNlteData *d, int64_t n_ions, const i
     return err.empty() ? TARDIS_MC_OK : fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
 }
 
-// The launches of the solve kernel for the current value of option nlte_lds_levels (nlte::plan_launches), their lists uploaded.
+// The launches of the solve kernel for the current values of options nlte_lds_levels and nlte_blocked_levels (nlte::plan_launches,
+// nlte::plan_blocked), their lists uploaded.
 // TARDIS_MC_ERR_UNSUPPORTED when the slabs of all shells together exceed nlte::MAX_SCRATCH_BYTES.
 static int nlte_build_lists(TardisMcContext *ctx)
 {
@@ -4398,10 +4407,20 @@ static int nlte_build_lists(TardisMcContext *ctx)
     int rc;
     if ((rc = upload(ctx, ctx->nl.list, plan.list.data(), plan.list.size()))) return rc;
     if ((rc = upload(ctx, ctx->nl.slab, plan.slab.data(), plan.slab.size()))) return rc;
+    nlte::BlockedPlan blocked = nlte::plan_blocked(plan, ctx->nl.h_n, S, ctx->nl.blocked_levels);
+    std::vector<int> form_list(blocked.single);
+    std::vector<long long> form_slab(blocked.single_slab);
+    form_list.insert(form_list.end(), blocked.blocked.begin(), blocked.blocked.end());
+    form_slab.insert(form_slab.end(), blocked.blocked_slab.begin(), blocked.blocked_slab.end());
+    if ((rc = upload(ctx, ctx->nl.form_list, form_list.data(), form_list.size()))) return rc;
+    if ((rc = upload(ctx, ctx->nl.form_slab, form_slab.data(), form_slab.size()))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->nl.launches.swap(plan.launches);
+    ctx->nl.steps.swap(blocked.steps);
+    ctx->nl.n_single = (int)blocked.single.size(); ctx->nl.n_blocked = (int)blocked.blocked.size();
     ctx->nl.scratch_doubles = plan.scratch_doubles;
     ctx->nl.lists_built = ctx->nl.lds_levels;
+    ctx->nl.blocked_built = ctx->nl.blocked_levels;
     return TARDIS_MC_OK;
 }
 
@@ -4531,17 +4550,36 @@ int tardis_mc_get_nlte_collision_rates(TardisMcContext *ctx, double *c_ul, doubl
 static int nlte_prepare(TardisMcContext *ctx)
 {
     int rc;
-    if (ctx->nl.lists_built != ctx->nl.lds_levels && (rc = nlte_build_lists(ctx))) return rc;
+    if ((ctx->nl.lists_built != ctx->nl.lds_levels || ctx->nl.blocked_built != ctx->nl.blocked_levels) && (rc = nlte_build_lists(ctx))) return rc;
     const size_t S = (size_t)ctx->n_shells, NL = (size_t)ctx->nl.lines;
     HIP_TRY(ctx, ctx->nl.r_ul.ensure(std::max<size_t>(1, NL * S) * sizeof(double)));
     HIP_TRY(ctx, ctx->nl.r_lu.ensure(std::max<size_t>(1, NL * S) * sizeof(double)));
     HIP_TRY(ctx, ctx->nl.x_t.ensure((size_t)ctx->nl.nx * S * sizeof(double)));
     HIP_TRY(ctx, ctx->nl.status.ensure((size_t)ctx->nl.species * S * sizeof(int)));
     HIP_TRY(ctx, ctx->nl.scratch.ensure(std::max<size_t>(1, (size_t)ctx->nl.scratch_doubles) * sizeof(double)));
+    if (ctx->nl.n_blocked > 0) HIP_TRY(ctx, ctx->nl.pivrow.ensure((size_t)ctx->nl.nx * S * sizeof(int)));
     if (ctx->nc.have) {
         HIP_TRY(ctx, ctx->nc.c_ul.ensure(std::max<size_t>(1, (size_t)ctx->nc.pairs * S) * sizeof(double)));
         HIP_TRY(ctx, ctx->nc.c_lu.ensure(std::max<size_t>(1, (size_t)ctx->nc.pairs * S) * sizeof(double)));
     }
+    return TARDIS_MC_OK;
+}
+
+// The elimination and the back substitution of the blocked form on assembled slabs: per panel step one panel and one trailing launch over all
+// systems of the launch, then the back substitution; stream order is the only ordering.
+static int nlte_blocked_enqueue(TardisMcContext *ctx, const mc::NlteSolveArgs &a, const std::vector<nlte::BlockedStep> &steps, int n_species, int *pivrow)
+{
+    static_assert(nlte::PANEL_COLUMNS == mc::NLTE_NB && nlte::TILE_COLUMNS == mc::NLTE_TN && nlte::TILE_ROWS == mc::NLTE_TM, "the plan and the kernels share the tile shape");
+    for (size_t t = 0; t < steps.size(); ++t) {
+        const nlte::BlockedStep &b = steps[t];
+        const int c0 = (int)t * nlte::PANEL_COLUMNS;
+        hipLaunchKernelGGL(mc::nlte_panel_kernel, dim3(b.panel_x, b.panel_y), dim3(256), 0, ctx->stream, a, pivrow, c0);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(mc::nlte_trailing_kernel, dim3(b.trailing_x, b.trailing_y, b.trailing_z), dim3(256), 0, ctx->stream, a, (const int *)pivrow, c0);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(mc::nlte_backsolve_kernel, dim3((unsigned)n_species, (unsigned)a.S), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
     return TARDIS_MC_OK;
 }
 
@@ -4596,8 +4634,21 @@ static int nlte_stage(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p, const
     for (const nlte::Launch &l : ctx->nl.launches) {
         a.list = ctx->nl.list.as<int>() + l.first;
         a.slab = ctx->nl.slab.as<long long>() + l.first;
-        if (l.global) hipLaunchKernelGGL(mc::nlte_solve_kernel<false>, dim3((unsigned)l.count, (unsigned)S), dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL(mc::nlte_solve_kernel<true>, dim3((unsigned)l.count, (unsigned)S), dim3(256), l.lds_bytes, ctx->stream, a);
+        if (l.global) {  // split by form: the one-workgroup kernel for the first n_single of form_list, the blocked form for the rest
+            a.list = ctx->nl.form_list.as<int>();
+            a.slab = ctx->nl.form_slab.as<long long>();
+            if (ctx->nl.n_single > 0) hipLaunchKernelGGL(mc::nlte_solve_kernel<false>, dim3((unsigned)ctx->nl.n_single, (unsigned)S), dim3(256), 0, ctx->stream, a);
+            HIP_TRY(ctx, hipGetLastError());
+            a.list += ctx->nl.n_single;
+            a.slab += ctx->nl.n_single;
+            if (ctx->nl.n_blocked > 0) {
+                hipLaunchKernelGGL(mc::nlte_assemble_kernel, dim3((unsigned)ctx->nl.n_blocked, (unsigned)S), dim3(256), 0, ctx->stream, a);
+                HIP_TRY(ctx, hipGetLastError());
+                if ((rc = nlte_blocked_enqueue(ctx, a, ctx->nl.steps, ctx->nl.n_blocked, ctx->nl.pivrow.as<int>()))) return rc;
+            }
+            continue;
+        }
+        hipLaunchKernelGGL(mc::nlte_solve_kernel<true>, dim3((unsigned)l.count, (unsigned)S), dim3(256), l.lds_bytes, ctx->stream, a);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(ctx->nl.ev[2], ctx->stream));
@@ -4919,6 +4970,56 @@ int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const do
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_debug_nlte_solve(TardisMcContext *ctx, int64_t n, int64_t n_systems, const double *m, const double *b, double *x, int32_t *status)
+{
+    if (!ctx || n <= 0 || n_systems <= 0 || n > 0x7ffffff0LL || n_systems > 65535 || !m || !b || !x || !status) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid debug_nlte_solve arguments");
+    const long long N = n, S = n_systems, ld = nlte::leading_dimension(N), work = nlte::work_bytes(N) / 8;
+    if (nlte::work_bytes(N) > nlte::MAX_SCRATCH_BYTES / S)
+        return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "debug_nlte_solve: %lld systems of %lld levels exceed the %lld bytes of scratch the plan allows", S, N, nlte::MAX_SCRATCH_BYTES);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // one species of n levels, a system per "shell": the slabs as nlte_assemble_kernel leaves them (column-major, ld = n | 1, b behind the matrix)
+    std::vector<double> slabs((size_t)(work * S), 0.0);
+    for (long long s = 0; s < S; ++s) {
+        double *M = slabs.data() + s * work;
+        for (long long i = 0; i < N; ++i)
+            for (long long j = 0; j < N; ++j) M[i + j * ld] = m[(s * N + i) * N + j];
+        for (long long i = 0; i < N; ++i) M[ld * N + i] = b[s * N + i];
+    }
+    const int zero = 0, levels = (int)N;
+    const long long slab0 = 0;
+    const double one = 1.0;
+    ScopedDevBuf scratch, ints, offset, g, lbf, x_t, st, pivrow;
+    HIP_TRY(ctx, scratch.ensure(slabs.size() * sizeof(double)));
+    HIP_TRY(ctx, ints.ensure(2 * sizeof(int)));
+    HIP_TRY(ctx, offset.ensure(sizeof(long long)));
+    HIP_TRY(ctx, g.ensure(sizeof(double)));
+    HIP_TRY(ctx, lbf.ensure((size_t)(N * S) * sizeof(double)));
+    HIP_TRY(ctx, x_t.ensure((size_t)(N * S) * sizeof(double)));
+    HIP_TRY(ctx, st.ensure((size_t)S * sizeof(int)));
+    HIP_TRY(ctx, pivrow.ensure((size_t)(N * S) * sizeof(int)));
+    HIP_TRY(ctx, hipMemcpyAsync(scratch.p, slabs.data(), slabs.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ints.p, &zero, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ints.as<int>() + 1, &levels, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(offset.p, &slab0, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(g.p, &one, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(st.p, 0, (size_t)S * sizeof(int), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(x_t.p, 0, (size_t)(N * S) * sizeof(double), ctx->stream));
+    mc::NlteSolveArgs a{};
+    a.S = (int)S; a.K = N; a.NX = N;
+    a.list = ints.as<int>(); a.sp_k0 = ints.as<int>(); a.sp_x0 = ints.as<int>(); a.sp_n = ints.as<int>() + 1;  // species 0: first level 0, first row of x 0
+    a.g = g.as<double>(); a.lbf_t = lbf.as<double>(); a.x_t = x_t.as<double>(); a.status = st.as<int>();
+    a.scratch = scratch.as<double>(); a.slab = offset.as<long long>();
+    std::vector<nlte::BlockedStep> steps;
+    for (long long t = 0; t < nlte::panel_steps(N); ++t)
+        steps.push_back({1u, (unsigned)S, (unsigned)nlte::trailing_strips(N, t * nlte::PANEL_COLUMNS), 1u, (unsigned)S});
+    int rc;
+    if ((rc = nlte_blocked_enqueue(ctx, a, steps, 1, pivrow.as<int>()))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(x, x_t.p, (size_t)(N * S) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(status, st.p, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TARDIS_MC_OK;
 }
 

@@ -311,6 +311,13 @@ class Engine:
         return ("lds", "global")[int(_lib.lib().tardis_mc_nlte_solve_path(int(levels)))]
 
     @staticmethod
+    def nlte_solve_form(levels: int) -> str:
+        """The form of the NLTE solve for a species of ``levels`` levels under the rule: "lds", "global" (one workgroup on a slab of
+        HBM) or "blocked" (panels by one workgroup, the trailing update over the whole chip); csrc/nlte_plan.hpp.  Options
+        ``nlte_lds_levels`` and ``nlte_blocked_levels`` move the two thresholds (measurements and tests); all forms give the same bits."""
+        return _abi.NLTE_FORMS[int(_lib.lib().tardis_mc_nlte_solve_form(int(levels)))]
+
+    @staticmethod
     def plasma_update_path(levels: int) -> str:
         """The form of update_plasma()'s partition kernel for an ion of ``levels`` levels: "lane" (one lane per (ion, shell)) or
         "row" (a 16-lane row per (ion, shell)); csrc/plasma_update_plan.hpp."""
@@ -747,6 +754,16 @@ class Engine:
         self._check(self._L.tardis_mc_debug_eval(self._h, op, x.ctypes.data, yp, out.ctypes.data, n), "debug_eval")
         return out
 
+    def debug_nlte_solve(self, m, b):
+        """The blocked form of the NLTE solve on dense systems (`tardis_mc_debug_nlte_solve`): m [systems, n, n], b [systems, n] ->
+        (x [systems, n], status [systems]: 0, 1 + the step of a bad pivot, n + 1 for x[0] == 0, n + 2 for an x that is not finite)."""
+        m, b = np.ascontiguousarray(m, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+        if m.ndim != 3 or m.shape[1] != m.shape[2] or b.shape != m.shape[:2]:
+            raise ValueError("debug_nlte_solve needs m [systems, n, n] and b [systems, n]")
+        x, status = np.empty(b.shape), np.empty(b.shape[0], dtype=np.int32)
+        self._check(self._L.tardis_mc_debug_nlte_solve(self._h, m.shape[1], m.shape[0], m.ctypes.data, b.ctypes.data, x.ctypes.data, status.ctypes.data),
+                    "debug_nlte_solve")
+        return x, status
 
     def debug_microbench(self, which: int, n_doubles: int, iters: int, blocks: int) -> float:
         v = C.c_double()

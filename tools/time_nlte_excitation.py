@@ -9,7 +9,11 @@ slabs stay under the plan's scratch cap (csrc/nlte_plan.hpp) and under --max-lev
 Arms, one process each (the parent starts them one after the other and never opens the GPU itself), in each one warm-up call, then the
 median of --reps timed calls: "plain" (no NLTE data), "lds" (the plan's rule), "global" (option nlte_lds_levels 0: every species in the
 global form), "host" (the replaced path), and "sweep": every species that fits the LDS installed alone, its solve timed in both forms --
-the measurement the rule of csrc/nlte_plan.hpp is set from.
+the measurement the rule of csrc/nlte_plan.hpp is set from.  The forms of a species in HBM, through option nlte_blocked_levels: "one_wg"
+(LDS where it fits, else one workgroup per (species, shell) on its slab), "blocked" (LDS where it fits, else the blocked form), "global"
+now meaning every species on a slab with one workgroup, and "blocked_sweep": every species that does not fit the LDS (up to
+--max-levels) installed alone, its solve timed in both forms -- the measurement BLOCKED_FORM_LEVELS is set from.  With TARDIS_MC_LIB
+naming an older build, the arms it knows ("lds", "global") time that build.
 Usage: python tools/time_nlte_excitation.py [--reps 5] [--shapes config2,tardis_example] [--max-levels 1200]"""
 import argparse
 import json
@@ -35,7 +39,10 @@ SHAPES = {
 _PLAN = open(os.path.join(ROOT, "tardis_amd", "csrc", "nlte_plan.hpp")).read()
 SCRATCH_CAP = 1 << int(re.search(r"MAX_SCRATCH_BYTES = 1LL << (\d+);", _PLAN).group(1))
 LARGEST_LDS_LEVELS = int(re.search(r"GLOBAL_FORM_LEVELS = (\d+);", _PLAN).group(1)) - 1
-ARMS = ("plain", "lds", "global", "host", "sweep")
+ARMS = ("plain", "lds", "global", "one_wg", "blocked", "host", "sweep", "blocked_sweep")
+NEVER_BLOCKED = 1 << 40  # a value of option nlte_blocked_levels no species reaches
+# options (nlte_lds_levels, nlte_blocked_levels) of an arm
+FORM_OPTIONS = {"lds": (-1, -1), "global": (0, NEVER_BLOCKED), "one_wg": (-1, NEVER_BLOCKED), "blocked": (-1, 0)}
 
 
 def median(ts):
@@ -100,6 +107,28 @@ def arm(name, which, reps, max_levels):
                 print(f"{name} {label:>10} rep {r}: " + "  ".join(f"{k} {v:9.3f}" for k, v in t.items()), flush=True)
             return {k: median([t[k] for t in times]) for k in times[0]}
 
+        def set_forms(lds_levels, blocked_levels):
+            eng.set_option("nlte_lds_levels", lds_levels)
+            if not os.environ.get("TARDIS_MC_LIB"):  # (an older build has one form for a species in HBM and no such option)
+                eng.set_option("nlte_blocked_levels", blocked_levels)
+
+        if which == "blocked_sweep":
+            out["solve_ms_by_levels"] = {}
+            seen = []
+            for i in sorted((i for i in range(len(levels)) if LARGEST_LDS_LEVELS < levels[i] <= max_levels and work_bytes(levels[i]) * S <= SCRATCH_CAP),
+                            key=lambda i: levels[i]):
+                if seen and levels[i] < 1.25 * seen[-1]:  # (sizes a quarter apart)
+                    continue
+                seen.append(int(levels[i]))
+                eng.set_nlte_data(synthetic.make_nlte_data(1, ld, pd, species=[i]))
+                row = {}
+                for form in ("one_wg", "blocked"):
+                    set_forms(*FORM_OPTIONS[form])
+                    m = timed(device, f"n={int(levels[i])} {form}")
+                    row[form] = m["solve_ms"]
+                    row[form + "_update_ms"] = m["device_ms"]
+                out["solve_ms_by_levels"][str(int(levels[i]))] = row
+            return out
         if which == "sweep":
             out["solve_ms_by_levels"] = {}
             for i in (i for i in range(len(levels)) if 2 <= levels[i] <= LARGEST_LDS_LEVELS):
@@ -109,8 +138,8 @@ def arm(name, which, reps, max_levels):
                     continue
                 eng.set_nlte_data(synthetic.make_nlte_data(1, ld, pd, species=[i]))
                 row = {}
-                for form, option in (("lds", -1), ("global", 0)):
-                    eng.set_option("nlte_lds_levels", option)
+                for form in ("lds", "global"):
+                    set_forms(*FORM_OPTIONS[form])
                     row[form] = timed(device, f"n={int(levels[i])} {form}")["solve_ms"]
                 out["solve_ms_by_levels"][str(int(levels[i]))] = row
             return out
@@ -120,7 +149,7 @@ def arm(name, which, reps, max_levels):
             return out
         if which != "plain":
             eng.set_nlte_data(nd)
-            eng.set_option("nlte_lds_levels", 0 if which == "global" else -1)
+            set_forms(*FORM_OPTIONS[which])
         out.update(timed(device, which))
     return out
 
