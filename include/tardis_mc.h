@@ -228,6 +228,10 @@ const char *tardis_mc_last_error(const TardisMcContext *ctx);   /* ctx may be NU
  * 8, or 12 where most macro-atom blocks are entered through hot sectors),
  * "walk_min_active" (macroatom walks are carried over to the next pass once this few lanes still walk; -1 never, < -1 automatic:
  * 8 / 12 likewise),
+ * "tracker_defer" (last-interaction tracker of variant 3 without v-packets: 1, the default: a packet's record of its last interaction stays on
+ * the chip and is written once, when the packet ends; 0: the record is written at every interaction, as the other variants do.  A problem of more
+ * than 2^15 shells or 2^24 - 1 lines runs as with 0.  Results do not depend on it; tardis_mc_last_tracker_defer tells what a call ran with),
+ * "tracker_pack_max_lines" (tests: problems of more lines than this run as with "tracker_defer" 0; 0, the default: only the real bound),
  * "log_tail_split" (1, the default: a call whose line-visit log fits one epoch is split where the drain of its longest-lived packets
  * begins -- "log_tail_packets" (8) packets' worth of traces per lane before the estimated end -- so that the estimator passes over
  * the bulk run beside the drain; 0 off), "log_chunk_records" (records per chunk of the log's pool, <= 4096 by default),
@@ -315,6 +319,10 @@ int tardis_mc_last_table_offsets(TardisMcContext *ctx);
  * suspends when T or fewer of its lanes still hold a packet; the live lanes of all waves are packed into full waves and the rest of the call runs as a launch of
  * fewer waves, beside the line-estimator passes of the launch before; 0 = off.  Per-packet results do not depend on it). */
 int tardis_mc_last_compactions(TardisMcContext *ctx);
+/* How the last tardis_mc_propagate kept the last-interaction tracker (option "tracker_defer"): 1 one record per packet, written when it ends;
+ * 0 a record per interaction (the option, or a problem beyond the packed widths); -1 the call ran another kernel than variant 3 without
+ * v-packets, or without a tracker, or nothing has run yet.  A packet that ended with an error leaves an empty record after a call that reports 1. */
+int tardis_mc_last_tracker_defer(TardisMcContext *ctx);
 /* Progress of the propagate call that is running (or of the last one): packets handed to the propagation kernel so far and the call's
  * packet count -- what the reference's packet progress bar shows (update_packets_pbar, modes/montecarlo_transport.py:94-120,
  * progress_bars.py).  Safe to call from ANOTHER host thread while tardis_mc_propagate blocks (it reads one device word on a stream of
@@ -850,7 +858,9 @@ int tardis_mc_comm_check(TardisMcContext *ctx, int *out_ranks);
 
 /* ---- diagnostics: element-wise device arithmetic, used by the numerics parity tests ------------------
  * op: 0 x+y, 1 x*y, 2 x/y, 3 sqrt(x), 4 log(x) [engine's portable log], 5 exp(x), 6 x*y+x (un-fused),
- *     7 MT19937 doubles of seed (uint32)x[0] (n outputs), 8 floor(x), 9 x/y through the engine's exact 3-fma division. */
+ *     7 MT19937 doubles of seed (uint32)x[0] (n outputs), 8 floor(x), 9 x/y through the engine's exact 3-fma division;
+ *     100 (tests) no arithmetic: the raw 64-byte tracker records the wave-owner kernel left for packets x[0] ... x[0] + n / 8 - 1 of the last
+ *     call, 8 doubles each: before_nu, before_mu, before_energy, radius, after_mu, then int32 pairs shell | type, absorb | emit, count | valid. */
 int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const double *y, double *out, int64_t n);
 /* The elimination and back substitution of the blocked form of the NLTE solve on dense systems, for tests: m [n_systems][n][n]
  * row-major, b [n_systems][n]; x [n_systems][n] (rows of a failed system are 0.0) and status [n_systems] (0, 1 + the step of a zero or

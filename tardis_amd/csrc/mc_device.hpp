@@ -70,6 +70,31 @@ struct EventLog {
     unsigned n_chunks;
 };
 
+// ---- the deferred last-interaction record of the wave kernel (propagate_wave.hpp, DEFER): between two interactions a lane keeps the
+// integer fields of its packet's last interaction in ONE 64-bit word of LDS -- bit 0: the interaction was a line (else electron
+// scattering), 15 bits shell, 24 bits absorbing line + 1, 24 bits emitting line + 1 (-1, "no line", packs as 0).  A problem that
+// does not fit these widths keeps the per-interaction store of the whole record (tracker_pack_fits, checked on the host).
+constexpr int TRK_PACK_SHELL_BITS = 15, TRK_PACK_LINE_BITS = 24;
+static_assert(1 + TRK_PACK_SHELL_BITS + 2 * TRK_PACK_LINE_BITS == 64, "the packed interaction is one 64-bit word");
+static_assert(IT_LINE == 2 && IT_ESCATTERING == 4, "one bit tells the two interaction types of a record apart");
+__host__ __device__ constexpr bool tracker_pack_fits(long long n_shells, long long n_lines)
+{
+    return n_shells <= (1LL << TRK_PACK_SHELL_BITS) && n_lines + 1 <= (1LL << TRK_PACK_LINE_BITS);  // (shell < n_shells; line + 1 <= n_lines)
+}
+__host__ __device__ __forceinline__ unsigned long long tracker_pack(int type, int shell, int absorb, int emit)
+{
+    return (unsigned long long)(type == IT_LINE ? 1u : 0u) | ((unsigned long long)(unsigned)shell << 1) |
+           ((unsigned long long)(unsigned)(absorb + 1) << (1 + TRK_PACK_SHELL_BITS)) |
+           ((unsigned long long)(unsigned)(emit + 1) << (1 + TRK_PACK_SHELL_BITS + TRK_PACK_LINE_BITS));
+}
+__host__ __device__ __forceinline__ void tracker_unpack(unsigned long long w, int &type, int &shell, int &absorb, int &emit)
+{
+    type = (w & 1ull) ? IT_LINE : IT_ESCATTERING;
+    shell = (int)((w >> 1) & ((1ull << TRK_PACK_SHELL_BITS) - 1ull));
+    absorb = (int)((w >> (1 + TRK_PACK_SHELL_BITS)) & ((1ull << TRK_PACK_LINE_BITS) - 1ull)) - 1;
+    emit = (int)(w >> (1 + TRK_PACK_SHELL_BITS + TRK_PACK_LINE_BITS)) - 1;
+}
+
 // Everything a propagation kernel needs, passed by value (kernarg segment -> SGPRs).
 struct DeviceProblem {
     // packets (SoA, coalesced by packet index)
@@ -82,7 +107,8 @@ struct DeviceProblem {
         *li_after_mu, *li_after_energy;
     long long *li_shell_id, *li_interaction_type, *li_line_absorb_id, *li_line_emit_id, *li_interactions_count;
     // wave kernel: one 64-byte record per packet, rewritten at every interaction (TrackerRecord, propagate_wave.hpp) and
-    // unpacked into the arrays above once the propagation is over -- one write request per interaction instead of nine
+    // unpacked into the arrays above once the propagation is over -- one write request per interaction instead of nine; the
+    // lane sweeps without v-packets write it once per packet (tracker_pack above)
     uint4 *li_rec;
     // geometry
     int n_shells;

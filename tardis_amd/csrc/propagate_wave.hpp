@@ -158,7 +158,9 @@ struct WaveCold {
     const LaunchRec *launch;  // [chunk_count] prepared packets (launch_prep_kernel)
     VpResult *vp_scratch;  // [waves][64 * VP_ROUND]
     VpPark *vp_park;       // [waves][64]; null: no carry-over
-    int vp_carry_min_active, vp_pad;  // pooled volleys: leave the volley phase once nothing waits and this few lanes still trace (0: never)
+    int vp_carry_min_active;  // pooled volleys: leave the volley phase once nothing waits and this few lanes still trace (0: never)
+    int trk_defer;            // DEFER instantiations: 1 the tracker record is stored once, when the packet ends; 0 at every interaction (option tracker_defer, or a
+                              // problem whose shells / lines do not fit tracker_pack).  Read by the event phase only, hence here and not in WaveHot
     // epochs (see LaneSave): where the lanes / waves of this grid are suspended; resume = this launch continues them
     LaneSave *save;      // [waves * 64]
     WaveSave *wsave;     // [waves]
@@ -443,6 +445,9 @@ __global__ void __launch_bounds__(256) macro_cumulative_kernel(const double *__r
 // arrays were nine requests, a quarter of all memory requests of the macroatom workload) and unpacked into the boundary's
 // arrays by tracker_unpack_kernel after the propagation.  The fields the reference fills at the end of a packet (nu, energy,
 // after_nu, after_energy) equal the packet's outputs.
+// The lane-sweep instantiations without v-packets (DEFER, propagate_wave_kernel) keep the record of the last interaction in the
+// lane's LDS instead and store it ONCE, when the packet ends: of the ~80 records a packet of the macroatom workload wrote only the
+// last one was ever read.
 struct __attribute__((aligned(16))) TrackerRecord {
     double before_nu, before_mu, before_energy, radius, after_mu;
     int shell, type, absorb, emit, count, valid;
@@ -817,6 +822,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     static_assert(NT == 0 || (LS && !VPK && !FULL), "the interleaved sweep table is read by the lane sweeps only");
     static_assert(!SL || !VPK, "the shell-sorted log is built for the instantiations without v-packets");
     static_assert(NT != 2 || WPE != 3, "aligned runs are eight lines long");
+    // DEFER: the tracker record is kept in LDS between interactions and stored once, when the packet ends (W->trk_defer != 0; else, and in every other
+    // instantiation, the whole record is stored at every interaction).  Six per-lane doubles hold it: sh.nu | sh.rcp_nu | sh.comov_nu = the packet
+    // before the interaction, sh.chi = r, sh.rcp_chi = mu after it, sh.tau_event = tracker_pack(type, shell, absorbing line, emitting line).  In these
+    // instantiations the lane sweeps and their prologue do not touch the six arrays (they use sh.d_cont0 / sh.d_boundary / s_* and registers), no volley
+    // lays its items over them (!VPK), the cooperative walk does not use them as scratch (!XWALK) and no row is taken from the record (!FT).  The
+    // order of their writes within a lane:
+    //   1. an interaction starts (epilogue of the trace): the before-values go to the first three -- the record of the previous interaction is dead from
+    //      here on: this interaction either completes and replaces it, or fails, and a failed packet gets the empty record;
+    //   2. a walk that is carried over parks inv_new | block | number drawn in the other three, in the pass of step 1 or a later one, and reads them back
+    //      at the top of the pass that resumes it;
+    //   3. the interaction completes (finish block, only once the walk is over: `!carried`): r | mu | packed word go over the walk's parking slots;
+    //   4. the packet ends in a later pass (a boundary event: nothing in between writes the six) or in this one: the record is built and stored.
+    // A suspension carries all six in LaneSave (walk_inv_new ... trk_energy), whichever of 1-4 the lane is in.
+    constexpr bool DEFER = TRACK && LS && !VPK && !FT && !XWALK;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     WaveShared &sh = *reinterpret_cast<WaveShared *>(lds_raw);
     constexpr size_t SH_BYTES = LS ? WAVE_SHARED_LS_BYTES : sizeof(WaveShared);
@@ -1028,6 +1047,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
         const EstimatorLog &log = W->log;
         uint32_t *const seeded_states = W->seeded_states;
         const long long chunk_first = W->chunk_first, chunk_count = W->chunk_count;
+        const bool deferred = DEFER && W->trk_defer != 0;  // (wave-uniform; constant through a call)
         double *const jb = P.jblue_t, *const ed = P.edot_t;
         // a pass appends at most 64 records: without room for them the wave takes the next chunk of the pool (one atomic per chunk)
         bool log_full = false;
@@ -1515,15 +1535,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     trk_count += 1 + trk_boundary;
                     trk_boundary = 0;
                     trk_any = true;
-                    TrackerRecord rec;
-                    rec.before_nu = sh.nu[lane]; rec.before_mu = sh.rcp_nu[lane]; rec.before_energy = sh.comov_nu[lane];
-                    rec.radius = p.r; rec.after_mu = p.mu;
-                    rec.shell = p.shell; rec.type = type; rec.absorb = absorb_id; rec.emit = emit_id;
-                    rec.count = trk_count; rec.valid = 1;
-                    gstore(reinterpret_cast<TrackerRecord *>(W->D.li_rec) + (chunk_first + pkt), rec);
-                    if (FT) {
-                        ev_row = true; ev_type = type; ev_shell = p.shell; ev_after = p.shell;
-                        ev_bnu = rec.before_nu; ev_bmu = rec.before_mu; ev_be = rec.before_energy; ev_absorb = absorb_id; ev_emit = emit_id;
+                    if (deferred) {  // the before-values stay where the epilogue parked them; nothing goes to memory
+                        sh.chi[lane] = p.r; sh.rcp_chi[lane] = p.mu;
+                        sh.tau_event[lane] = __longlong_as_double((long long)tracker_pack(type, p.shell, absorb_id, emit_id));  // (a bit pattern: only ever moved)
+                    } else {
+                        TrackerRecord rec;
+                        rec.before_nu = sh.nu[lane]; rec.before_mu = sh.rcp_nu[lane]; rec.before_energy = sh.comov_nu[lane];
+                        rec.radius = p.r; rec.after_mu = p.mu;
+                        rec.shell = p.shell; rec.type = type; rec.absorb = absorb_id; rec.emit = emit_id;
+                        rec.count = trk_count; rec.valid = 1;
+                        gstore(reinterpret_cast<TrackerRecord *>(W->D.li_rec) + (chunk_first + pkt), rec);
+                        if (FT) {
+                            ev_row = true; ev_type = type; ev_shell = p.shell; ev_after = p.shell;
+                            ev_bnu = rec.before_nu; ev_bmu = rec.before_mu; ev_be = rec.before_energy; ev_absorb = absorb_id; ev_emit = emit_id;
+                        }
                     }
                 }
             }
@@ -1534,18 +1559,30 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                 const long long i = chunk_first + pkt;
                 const DeviceProblem *C = &W->D;
                 if (FT) glob(C->evlog.counts)[i] = trk_count + trk_boundary;  // (rows written for the packet, also when it failed)
+                auto empty_record = []() {  // (the unpacking fills in NaN / -1 / 0)
+                    TrackerRecord rec;
+                    rec.before_nu = rec.before_mu = rec.before_energy = rec.radius = rec.after_mu = 0.0;
+                    rec.shell = rec.type = rec.absorb = rec.emit = -1; rec.count = 0; rec.valid = 0;
+                    return rec;
+                };
                 if (err) {
                     gatomic_min_i64(&C->first_error[0], i);
                     glob(C->out_nu)[i] = (double)err;
                     glob(C->out_e)[i] = -99.0;
+                    // (deferred: the failed packet's earlier interactions have left nothing in memory, and what an earlier call left there is not its own)
+                    if (deferred) gstore(reinterpret_cast<TrackerRecord *>(C->li_rec) + i, empty_record());
                 } else {
                     // set_packet_collection_output (modes/montecarlo_transport.py:70-90)
                     glob(C->out_nu)[i] = p.nu;
                     glob(C->out_e)[i] = (p.status == ST_REABSORBED) ? -p.energy : p.energy;
-                    if (TRACK && !trk_any) {  // no interaction at all: an empty record (the unpacking fills in NaN / -1 / 0)
-                        TrackerRecord rec;
-                        rec.before_nu = rec.before_mu = rec.before_energy = rec.radius = rec.after_mu = 0.0;
-                        rec.shell = rec.type = rec.absorb = rec.emit = -1; rec.count = 0; rec.valid = 0;
+                    if (TRACK && (!trk_any || deferred)) {  // no interaction at all: an empty record; deferred: the packet's one store of its record
+                        TrackerRecord rec = empty_record();
+                        if (deferred && trk_any) {  // the last interaction's, from the lane's LDS
+                            rec.before_nu = sh.nu[lane]; rec.before_mu = sh.rcp_nu[lane]; rec.before_energy = sh.comov_nu[lane];
+                            rec.radius = sh.chi[lane]; rec.after_mu = sh.rcp_chi[lane];
+                            tracker_unpack((unsigned long long)__double_as_longlong(sh.tau_event[lane]), rec.type, rec.shell, rec.absorb, rec.emit);
+                            rec.count = trk_count; rec.valid = 1;
+                        }
                         gstore(reinterpret_cast<TrackerRecord *>(C->li_rec) + i, rec);
                     }
                 }

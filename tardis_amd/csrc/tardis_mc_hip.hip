@@ -284,6 +284,12 @@ struct TardisMcContext {
     struct WaveResources {
         bool walk_min_active_user = false, ls_min_active_user = false;  // (set through the options: no automatic choice then)
         int walk_min_active = 8;  // compact macro-atom walk: carry the longest chains over to the next pass once this few lanes still walk (-1: never)
+        // last-interaction tracker of the lane sweeps without v-packets: 1 the record stays in LDS and is stored once, when the packet ends; 0 stored at every
+        // interaction (propagate_wave.hpp, DEFER).  A problem whose shells or lines do not fit tracker_pack (mc_device.hpp) takes 0 whatever the option says;
+        // tracker_pack_max_lines (tests): a lower bound on the lines that fit, 0 = the real one.  last_tracker_defer: what the last call ran with, -1 = no tracker
+        // or another kernel
+        int tracker_defer = 1, last_tracker_defer = -1;
+        long long tracker_pack_max_lines = 0;
         int ls_min_active = 8, ls_max_steps = 1 << 30;  // lane sweeps: when to leave the sweep phase (propagate_wave.hpp)
         int drain_split = 0;          // wave kernel: split the drain of a call off into a launch of its own (WaveCold::drain_split); measured: -4 % at 1e7 packets, +1.3 % at 1e8 -> off
         int log_tail_packets = 8;               // tail split: packets' worth of traces a lane in flight still logs after the supply has run out
@@ -1522,6 +1528,7 @@ struct WaveCall {
     const LogSizing *log;
     mc::GroupArgs P;
     mc::WaveHot hot;
+    int trk_defer = 0;  // the call keeps the tracker record in LDS and stores it once per packet (WaveCold::trk_defer)
     long long n;
     int waves;
     bool vq, may_suspend, cu_masked, streaming;
@@ -1650,7 +1657,7 @@ int fill_wave_cold(TardisMcContext *ctx, const WaveCall &E, int epoch, const mc:
     wc.launch = ctx->wv.seed_chk.as<mc::LaunchRec>();
     wc.vp_scratch = ctx->wv.vp_scratch.as<mc::VpResult>();
     wc.vp_park = (vpk && !E.vq_on && ctx->wv.vp_carry_min_active > 0) ? ctx->wv.vp_park.as<mc::VpPark>() : nullptr;
-    wc.vp_carry_min_active = ctx->wv.vp_carry_min_active; wc.vp_pad = 0;
+    wc.vp_carry_min_active = ctx->wv.vp_carry_min_active; wc.trk_defer = E.trk_defer;
     wc.save = E.may_suspend ? E.cur_save : nullptr;
     wc.wsave = E.may_suspend ? E.cur_wsave : nullptr;
     wc.resume = epoch > 0 ? 1 : 0;
@@ -2050,6 +2057,13 @@ int run_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P)
     hot.ls_max_steps = ctx->wv.ls_max_steps;
     hot.walk_min_active = (!ctx->wv.walk_min_active_user && mostly_hot) ? 16 : ctx->wv.walk_min_active;  // (12 until round 6; with the leaner sweep 16: -1.2 %, profiles/r06_cutoffs.txt)
     hot.vq_min_active = ctx->wv.vq_min_active;
+    {   // the deferred tracker record: only where the instantiation has it and the packed word holds every shell and line of the problem
+        const WaveKernelKey &k = w.key;
+        const bool has_defer = k.track && k.lane_sweep && !k.vpk && !k.full_tracking && !k.xwalk;
+        const bool fits = mc::tracker_pack_fits(P.n_shells, P.n_lines) && (ctx->wv.tracker_pack_max_lines <= 0 || P.n_lines <= ctx->wv.tracker_pack_max_lines);
+        E.trk_defer = (has_defer && ctx->wv.tracker_defer && fits) ? 1 : 0;  // (-> WaveCold::trk_defer of every launch of the call)
+        ctx->wv.last_tracker_defer = has_defer ? E.trk_defer : -1;
+    }
     hot.line_block = P.line_interaction_type != 0 ? P.line_block : nullptr;
     ctx->wv.post_pending[0] = ctx->wv.post_pending[1] = false;
     ctx->wv.prop_pending = false;
@@ -2310,6 +2324,8 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
         ctx->wv.walk_min_active_user = value >= -1;
         ctx->wv.walk_min_active = value >= -1 ? (int)std::min<long long>(value, 63) : 8;
     }
+    else if (n == "tracker_defer") ctx->wv.tracker_defer = value ? 1 : 0;
+    else if (n == "tracker_pack_max_lines") ctx->wv.tracker_pack_max_lines = std::max<long long>(0, value);
     else if (n == "group_size") ctx->group_size = (value == 4 || value == 8 || value == 16) ? (int)value : 0;
     else if (n == "pipeline_chunks") {}  // (round 1: chunks on two streams; a call of the wave kernel now runs as epochs -- accepted, ignored)
     else if (n == "log_capacity") { ctx->wv.log_capacity = std::max<long long>(0, value); ctx->wv.log_capacity_user = true; }
@@ -2963,6 +2979,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     if (call.plan.error) return fail(ctx, call.plan.error, "%s", call.plan.message);
     ctx->last_table_offsets = call.plan.last_table_offsets;
     ctx->last_variant = call.plan.last_variant;
+    ctx->wv.last_tracker_defer = -1;  // (the wave kernel's runner says otherwise)
     rc = call.plan.cooperative ? run_cooperative(ctx, call) : run_lane_kernel(ctx, call);
     if (rc) return rc;
     {   // events per packet of this call, for the log sizing of the next one (asynchronous, pinned host memory)
@@ -3100,6 +3117,7 @@ int tardis_mc_last_counters(TardisMcContext *ctx, int64_t out_counters[TARDIS_MC
 int tardis_mc_last_variant(TardisMcContext *ctx) { return ctx ? ctx->last_variant : -1; }
 int tardis_mc_last_table_offsets(TardisMcContext *ctx) { return ctx ? ctx->last_table_offsets : -1; }
 int tardis_mc_last_compactions(TardisMcContext *ctx) { return ctx ? ctx->wv.compactions : -1; }
+int tardis_mc_last_tracker_defer(TardisMcContext *ctx) { return ctx ? ctx->wv.last_tracker_defer : -1; }
 
 int tardis_mc_last_estimator_ms(TardisMcContext *ctx, double *out_ms)
 {
@@ -4957,6 +4975,14 @@ int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const do
 {
     if (!ctx || !x || !out || n <= 0) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (op == 100) {  // tests: the wave kernel's raw tracker records of the last call (mc::TrackerRecord, 8 doubles each), n / 8 of them from packet x[0] on
+        const long long first = (long long)x[0], count = n / 8;
+        if (n % 8 || first < 0 || first + count > ctx->pk.n_packets || !ctx->pk.li_rec.p || ctx->wv.last_tracker_defer < 0)
+            return fail(ctx, TARDIS_MC_ERR_STATE, "debug_eval: no tracker records of a wave-kernel call for packets [%lld, %lld)", first, first + count);
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(out, (const char *)ctx->pk.li_rec.p + (size_t)first * 64, (size_t)count * 64, hipMemcpyDeviceToHost));
+        return TARDIS_MC_OK;
+    }
     ScopedDevBuf dx, dy, dout, scratch;
     size_t nx = (op == 7) ? 1 : (size_t)n;
     HIP_TRY(ctx, dx.ensure(nx * 8));

@@ -376,6 +376,11 @@ class Engine:
         """How often the last propagate() packed the live lanes of its drain into fewer waves (option drain_compact)."""
         return int(self._L.tardis_mc_last_compactions(self._h))
 
+    def last_tracker_defer(self) -> int:
+        """How the last propagate() kept the last-interaction tracker (option ``tracker_defer``): 1 one record per packet, written when
+        the packet ends; 0 a record per interaction; -1 another kernel than variant 3 without v-packets, or no tracker."""
+        return int(self._L.tardis_mc_last_tracker_defer(self._h))
+
     def last_variant(self) -> int:
         """Propagation kernel of the last propagate(): 0 lane, 1 group, 2 wave + group sweeps, 3 wave + lane sweeps,
         4 wave + volley queue (v-packets traced by vpacket_trace_kernel between its launches)."""
