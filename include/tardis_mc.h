@@ -323,6 +323,17 @@ int tardis_mc_last_compactions(TardisMcContext *ctx);
  * 0 a record per interaction (the option, or a problem beyond the packed widths); -1 the call ran another kernel than variant 3 without
  * v-packets, or without a tracker, or nothing has run yet.  A packet that ended with an error leaves an empty record after a call that reports 1. */
 int tardis_mc_last_tracker_defer(TardisMcContext *ctx);
+/* The tables of compiled propagation kernels, row by row (needs no context and no device).  `table`: 0 the lane-per-packet kernel, 1 the
+ * group-per-packet kernel, 2 the wave-owner kernel.  Returns the number of rows of that table and, for 0 <= row < that number, fills `key`
+ * (may be NULL) with the row's template arguments in their order, the unused tail zero:
+ *   lane:  FULL, VPK, TRACK, FT, VLI
+ *   group: FULL, TRACK, G, BLOCK, OCC, VPK, WIDE, VLI
+ *   wave:  FULL, TRACK, G, VPK, LS, XWALK, WPE, NT, SL, FT, WIDE, VLI
+ * A `table` outside 0..2 returns TARDIS_MC_ERR_INVALID_ARGUMENT (negative). */
+int tardis_mc_kernel_table_row(int table, int row, int key[12]);
+/* Which row of which table the last tardis_mc_propagate launched: `*table` as above and `key` as tardis_mc_kernel_table_row fills it;
+ * `*table` = -1 (and a zero key) when the call was refused before it looked its kernel up, or nothing has run yet. */
+int tardis_mc_last_kernel_key(TardisMcContext *ctx, int *table, int key[12]);
 /* Progress of the propagate call that is running (or of the last one): packets handed to the propagation kernel so far and the call's
  * packet count -- what the reference's packet progress bar shows (update_packets_pbar, modes/montecarlo_transport.py:94-120,
  * progress_bars.py).  Safe to call from ANOTHER host thread while tardis_mc_propagate blocks (it reads one device word on a stream of

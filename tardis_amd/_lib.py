@@ -40,6 +40,8 @@ SYMBOLS = {
     "tardis_mc_last_table_offsets": (_i, [_vp]),
     "tardis_mc_last_compactions": (_i, [_vp]),
     "tardis_mc_last_tracker_defer": (_i, [_vp]),
+    "tardis_mc_kernel_table_row": (_i, [_i, _i, C.POINTER(_i)]),
+    "tardis_mc_last_kernel_key": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "tardis_mc_progress": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tardis_mc_get_results": (_i, [_vp, _vp]),
     "tardis_mc_pcg64_seed": (_i, [C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -1382,6 +1382,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             int *res_cnt = reinterpret_cast<int *>(sh.tau_event);
             const int gshift = lane & ~(G - 1);
             constexpr unsigned long long GMASK = (G == 16) ? 0xffffull : ((G == 8) ? 0xffull : 0xfull);
+            // (TRACK: the first three of those arrays hold the packet before the interaction, parked by the epilogue of the trace for the tracker record
+            // that the finish block writes: the lane keeps its own three over the scan and puts them back)
+            double keep_nu = 0.0, keep_mu = 0.0, keep_energy = 0.0;
+            const bool walks = __ballot(in_macro) != 0;
+            if (TRACK && walks) { keep_nu = sh.nu[lane]; keep_mu = sh.rcp_nu[lane]; keep_energy = sh.comov_nu[lane]; }
             for (;;) {
                 const unsigned long long items = __ballot(in_macro);
                 if (!items) break;
@@ -1467,6 +1472,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     }
                 }
             }
+            if (TRACK && walks) { sh.nu[lane] = keep_nu; sh.rcp_nu[lane] = keep_mu; sh.comov_nu[lane] = keep_energy; }
         }
         const bool carried = state == WS_WALK && in_macro;  // (set above, compact walk only)
         if (carried) in_macro = false;

@@ -178,6 +178,8 @@ struct TardisMcContext {
     int table_offsets = -1;       // option: row offsets of the cooperative kernels, -1 64-bit where S x L or S x T reaches 2^28, 0 always 32-bit, 1 always 64-bit
     int last_table_offsets = -1;  // 32 / 64: row offsets of the last propagate call's kernel (see tardis_mc_last_table_offsets)
     int waves_per_simd = 4;  // register budget hint of the cooperative kernel (2: 256 VGPRs, 3: 168, 4: 128)
+    int last_kernel_table = -1;   // the kernel-table row the last propagate call looked up: 0 lane, 1 group, 2 wave, -1 none ...
+    int last_kernel_key[12] = {}; // ... and its key (see tardis_mc_last_kernel_key)
     void release()  // (the last of tardis_mc_destroy: the stages' buffers and events go before the stream they were used on)
     {
         release_buffers(r_inner, r_outer, grid, staging, rng_state, counters, first_error, next_packet, problem_dev);
@@ -1142,6 +1144,50 @@ const KernelRow<WaveKernelKey, WaveKernelFn> WAVE_KERNELS[] = {  // FULL, TRACK,
 };
 #undef KROW
 
+// A key as integers, in the order of its row's template arguments (the unused tail zero): what tardis_mc_kernel_table_row and
+// tardis_mc_last_kernel_key report, and what the "no such instantiation" errors print
+constexpr int KERNEL_KEY_FIELDS = 12;
+int key_fields(const LaneKernelKey &k, int out[KERNEL_KEY_FIELDS])
+{
+    const int f[] = {k.full, k.vpk, k.track, k.full_tracking, k.vli};
+    std::fill(out, out + KERNEL_KEY_FIELDS, 0);
+    std::copy(std::begin(f), std::end(f), out);
+    return (int)(std::end(f) - std::begin(f));
+}
+int key_fields(const GroupKernelKey &k, int out[KERNEL_KEY_FIELDS])
+{
+    const int f[] = {k.full, k.track, k.width, k.block, k.occupancy, k.vpk, k.wide, k.vli};
+    std::fill(out, out + KERNEL_KEY_FIELDS, 0);
+    std::copy(std::begin(f), std::end(f), out);
+    return (int)(std::end(f) - std::begin(f));
+}
+int key_fields(const WaveKernelKey &k, int out[KERNEL_KEY_FIELDS])
+{
+    const int f[] = {k.full, k.track, k.width, k.vpk, k.lane_sweep, k.xwalk, k.waves_per_simd, k.nt, k.shell_log, k.full_tracking, k.wide, k.vli};
+    static_assert(sizeof f / sizeof f[0] == KERNEL_KEY_FIELDS, "the wave kernel's key fills the reported key");
+    std::copy(std::begin(f), std::end(f), out);
+    return KERNEL_KEY_FIELDS;
+}
+template <typename Key> std::string key_text(const Key &key)  // "(0, 1, 16, ...)"
+{
+    int f[KERNEL_KEY_FIELDS];
+    const int n = key_fields(key, f);
+    std::string s = "(";
+    for (int i = 0; i < n; ++i) s += (i ? ", " : "") + std::to_string(f[i]);
+    return s + ")";
+}
+template <typename Key> void record_kernel(TardisMcContext *ctx, int table, const Key &key)  // (-> tardis_mc_last_kernel_key)
+{
+    ctx->last_kernel_table = table;
+    key_fields(key, ctx->last_kernel_key);
+}
+template <typename Key, typename Fn, size_t N>
+int kernel_table_row(const KernelRow<Key, Fn> (&table)[N], int row, int *key)
+{
+    if (key && row >= 0 && row < (int)N) key_fields(table[row].key, key);
+    return (int)N;
+}
+
 size_t wave_kernel_lds(const WaveKernelKey &k, int n_shells)  // dynamic LDS of an instantiation of the wave kernel
 {
     if (k.shell_log) return mc::wave_kernel_lds_bytes<false, false, true, true>(n_shells);
@@ -1153,8 +1199,10 @@ size_t wave_kernel_lds(const WaveKernelKey &k, int n_shells)  // dynamic LDS of 
 int launch_lane(TardisMcContext *ctx, const mc::DeviceProblem &P, int blocks, size_t lds)
 {
     const bool ft = P.evlog.rows != nullptr;  // full r-packet tracking: 8 ints of LDS per workgroup for the waves' append state
-    const LaneKernelFn k = find_kernel(LANE_KERNELS, LaneKernelKey{ctx->cfg.enable_full_relativity != 0, ctx->cfg.number_of_vpackets > 0, ctx->pk.track, ft, vlog_li_call(ctx)});
-    if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the lane kernel");
+    const LaneKernelKey key{ctx->cfg.enable_full_relativity != 0, ctx->cfg.number_of_vpackets > 0, ctx->pk.track, ft, vlog_li_call(ctx)};
+    const LaneKernelFn k = find_kernel(LANE_KERNELS, key);
+    if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the lane kernel: FULL, VPK, TRACK, FT, VLI = %s", key_text(key).c_str());
+    record_kernel(ctx, 0, key);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds + (ft ? 32 : 0), ctx->stream, P);
     HIP_TRY(ctx, hipGetLastError());
     return TARDIS_MC_OK;
@@ -1385,7 +1433,10 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
     if (w64) { k.wide = true; if (k.width == 4) k.width = 8; }
     k.vli = vlog_li_call(ctx);
     w.fn = find_kernel(WAVE_KERNELS, k);
-    if (!w.fn) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the wave kernel");
+    if (!w.fn)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the wave kernel: FULL, TRACK, G, VPK, LS, XWALK, WPE, NT, SL, FT, WIDE, VLI = %s",
+                    key_text(k).c_str());
+    record_kernel(ctx, 2, k);
     w.lds = wave_kernel_lds(k, ctx->n_shells);
     return TARDIS_MC_OK;
 }
@@ -2121,8 +2172,11 @@ int run_group_kernel(TardisMcContext *ctx, const PropagateCall &call, const mc::
     const size_t lds = G == 8 ? mc::group_kernel_lds_bytes<8, 256>(ctx->n_shells) : mc::group_kernel_lds_bytes<16, 256>(ctx->n_shells);
     if (lds > 160 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
     const int blocks_per_cu = std::max(1, std::min(std::min(ctx->blocks_per_cu, 8), (int)((160 * 1024) / lds)));
-    const GroupKernelFn k = find_kernel(GROUP_KERNELS, GroupKernelKey{call.full, ctx->pk.track, G, block, 4, vpk, call.plan.w64, vlog_li_call(ctx)});
-    if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the group kernel");
+    const GroupKernelKey key{call.full, ctx->pk.track, G, block, 4, vpk, call.plan.w64, vlog_li_call(ctx)};
+    const GroupKernelFn k = find_kernel(GROUP_KERNELS, key);
+    if (!k)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the group kernel: FULL, TRACK, G, BLOCK, OCC, VPK, WIDE, VLI = %s", key_text(key).c_str());
+    record_kernel(ctx, 1, key);
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, st));
     uint32_t *seeded = ctx->wv.seeded_states.as<uint32_t>();
@@ -2980,6 +3034,8 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     ctx->last_table_offsets = call.plan.last_table_offsets;
     ctx->last_variant = call.plan.last_variant;
     ctx->wv.last_tracker_defer = -1;  // (the wave kernel's runner says otherwise)
+    ctx->last_kernel_table = -1;      // (the lookup of the call's kernel says otherwise)
+    std::fill(std::begin(ctx->last_kernel_key), std::end(ctx->last_kernel_key), 0);
     rc = call.plan.cooperative ? run_cooperative(ctx, call) : run_lane_kernel(ctx, call);
     if (rc) return rc;
     {   // events per packet of this call, for the log sizing of the next one (asynchronous, pinned host memory)
@@ -3118,6 +3174,22 @@ int tardis_mc_last_variant(TardisMcContext *ctx) { return ctx ? ctx->last_varian
 int tardis_mc_last_table_offsets(TardisMcContext *ctx) { return ctx ? ctx->last_table_offsets : -1; }
 int tardis_mc_last_compactions(TardisMcContext *ctx) { return ctx ? ctx->wv.compactions : -1; }
 int tardis_mc_last_tracker_defer(TardisMcContext *ctx) { return ctx ? ctx->wv.last_tracker_defer : -1; }
+
+int tardis_mc_kernel_table_row(int table, int row, int key[12])
+{
+    if (table == 0) return kernel_table_row(LANE_KERNELS, row, key);
+    if (table == 1) return kernel_table_row(GROUP_KERNELS, row, key);
+    if (table == 2) return kernel_table_row(WAVE_KERNELS, row, key);
+    return TARDIS_MC_ERR_INVALID_ARGUMENT;
+}
+
+int tardis_mc_last_kernel_key(TardisMcContext *ctx, int *table, int key[12])
+{
+    if (!ctx || !table || !key) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    *table = ctx->last_kernel_table;
+    std::copy(std::begin(ctx->last_kernel_key), std::end(ctx->last_kernel_key), key);
+    return TARDIS_MC_OK;
+}
 
 int tardis_mc_last_estimator_ms(TardisMcContext *ctx, double *out_ms)
 {

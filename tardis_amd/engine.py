@@ -381,6 +381,38 @@ class Engine:
         the packet ends; 0 a record per interaction; -1 another kernel than variant 3 without v-packets, or no tracker."""
         return int(self._L.tardis_mc_last_tracker_defer(self._h))
 
+    KERNEL_TABLES = ("lane", "group", "wave")
+    # the fields of a key, in the order of the row's template arguments (include/tardis_mc.h, tardis_mc_kernel_table_row)
+    KERNEL_KEY_FIELDS = {"lane": ("FULL", "VPK", "TRACK", "FT", "VLI"),
+                         "group": ("FULL", "TRACK", "G", "BLOCK", "OCC", "VPK", "WIDE", "VLI"),
+                         "wave": ("FULL", "TRACK", "G", "VPK", "LS", "XWALK", "WPE", "NT", "SL", "FT", "WIDE", "VLI")}
+
+    @staticmethod
+    def kernel_table(table: str) -> list:
+        """The rows of a table of compiled propagation kernels -- ``table`` "lane", "group" or "wave" -- as tuples of the rows' template
+        arguments, in the order of ``KERNEL_KEY_FIELDS[table]`` (`tardis_mc_kernel_table_row`; needs no GPU)."""
+        L, t = _lib.lib(), Engine.KERNEL_TABLES.index(table)
+        key = (C.c_int * 12)()
+        n = L.tardis_mc_kernel_table_row(t, -1, key)
+        if n < 0:
+            raise RuntimeError(f"tardis_mc_kernel_table_row({table}) failed ({n})")
+        width = len(Engine.KERNEL_KEY_FIELDS[table])
+        rows = []
+        for r in range(n):
+            L.tardis_mc_kernel_table_row(t, r, key)
+            rows.append(tuple(key[:width]))
+        return rows
+
+    def last_kernel_key(self):
+        """The kernel-table row the last propagate() launched: ("lane" | "group" | "wave", key as in kernel_table()), or (None, ()) when
+        it looked no kernel up (`tardis_mc_last_kernel_key`)."""
+        t, key = C.c_int(-1), (C.c_int * 12)()
+        self._check(self._L.tardis_mc_last_kernel_key(self._h, C.byref(t), key), "last_kernel_key")
+        if t.value < 0:
+            return None, ()
+        table = self.KERNEL_TABLES[t.value]
+        return table, tuple(key[:len(self.KERNEL_KEY_FIELDS[table])])
+
     def last_variant(self) -> int:
         """Propagation kernel of the last propagate(): 0 lane, 1 group, 2 wave + group sweeps, 3 wave + lane sweeps,
         4 wave + volley queue (v-packets traced by vpacket_trace_kernel between its launches)."""
