@@ -10,6 +10,7 @@ Engine.last_kernel_key(); the GPU test holds the two together.
 A NEW ROW OF A KERNEL TABLE NEEDS A RECIPE HERE: tests/test_kernel_table_host.py fails until `recipe` returns one for it.
 
 The module also builds the problem family, runs a recipe and holds the comparisons with the CPU oracle (the bars of tests/test_hip_parity.py).
+Further families of the same shape (`register_family`; tests/coincident_lines.py registers "clustered") run through the same recipes.
 """
 import ctypes as C
 import os
@@ -168,19 +169,28 @@ def recipe_id(rec):
 
 # ---- the problem family and its oracle runs -------------------------------------------------------------------------------------
 
-def make_problem(full, n_vpackets):
+_families = {"base": lambda prob: prob}
+
+
+def register_family(name, transform):
+    """A further problem family: `transform` changes the base problem of a configuration in place and returns it.  The shape (packets,
+    shells, lines, v-packets) stays, so the recipes hold for every family (tests/coincident_lines.py: the clustered line list)."""
+    _families[name] = transform
+
+
+def make_problem(full, n_vpackets, family="base"):
     prob = synthetic.make_problem(seed=41, n_packets=N_PACKETS, n_shells=N_SHELLS, n_lines=N_LINES, line_interaction_type="macroatom",
                                   level_sizes="heavy", n_bins=2000, n_vpackets=n_vpackets, enable_full_relativity=bool(full))
     prob.montecarlo_configuration.ENABLE_VPACKET_TRACKING = n_vpackets > 0
-    return prob
+    return _families[family](prob)
 
 
 _cases, _traces, _lane_logs = {}, {}, {}
 
 
-def case(oracle, full, n_vpackets):
+def case(oracle, full, n_vpackets, family="base"):
     """(problem, oracle result) of a configuration: MATH_PORTABLE, tracked, one thread (the v-packet log in packet order); computed once."""
-    k = (bool(full), int(n_vpackets))
+    k = (bool(full), int(n_vpackets), family)
     if k not in _cases:
         prob = make_problem(*k)
         ref = oracle.run(prob.packet_collection, prob.geometry, prob.time_explosion, prob.opacity_state, prob.montecarlo_configuration,
@@ -197,10 +207,10 @@ def sample_mix(ref):
             "last is electron scattering": int((t.interaction_type == 4).sum()), "reabsorbed": int((ref.output_energies < 0).sum())}
 
 
-def oracle_trace(oracle, full, n_vpackets):
+def oracle_trace(oracle, full, n_vpackets, family="base"):
     """The oracle's serial trace log of a configuration: {shell, first line, lines visited, type} per trace_packet, packet by packet
     (as _oracle_trace of tests/test_full_tracking_gpu.py; one row per event)."""
-    k = (bool(full), int(n_vpackets))
+    k = (bool(full), int(n_vpackets), family)
     if k not in _traces:
         prob, ref = case(oracle, *k)
         lib = oracle.lib()
@@ -250,10 +260,10 @@ def run(rec, prob, ref):
     return Run(res, row, vlog, events)
 
 
-def lane_event_log(oracle, full, n_vpackets):
+def lane_event_log(oracle, full, n_vpackets, family="base"):
     """The lane kernel's full r-packet log of a configuration (the row lane FULL, VPK, 1, 1, 0), held against the oracle's trace: the
     yardstick of the wave kernel's FT rows and, through tests/vpacket_last_interaction_ref.py, of the VLI rows.  Computed once."""
-    k = (bool(full), int(n_vpackets))
+    k = (bool(full), int(n_vpackets), family)
     if k not in _lane_logs:
         prob, ref = case(oracle, *k)
         key = (int(k[0]), int(k[1] > 0), 1, 1, 0)
