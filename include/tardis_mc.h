@@ -566,7 +566,7 @@ int tardis_mc_opacity_update_path(int64_t rows);
 
 /* ---- producer of the next iteration's populations: ion and level number densities from (t_rad, W) ------------------------------
  * What the legacy plasma computes between two iterations in its default configuration -- ionization nebular (or lte), excitation
- * dilute-lte (or lte), NLTE excitation only through the section after this one, no helium treatment, no continuum, delta_treatment unset: LevelBoltzmannFactor, PartitionFunction,
+ * dilute-lte (or lte), NLTE excitation only through the section after this one, helium_treatment recomb-nlte and delta_treatment only through tardis_mc_set_ionization_options below, no continuum: LevelBoltzmannFactor, PartitionFunction,
  * GElectron, PhiSahaLTE / PhiSahaNebular with RadiationFieldCorrection and the interpolated zeta, IonNumberDensity.calculate and
  * LevelNumberDensity -- on the device and in their operation order (fp64, no contraction, exp as the transport evaluates it, every
  * product and sum a rounding of its own).  The populations never leave the device: they are written where tardis_mc_update_opacity's
@@ -695,7 +695,7 @@ int tardis_mc_plasma_update_path(int64_t levels);
  *   lbf[k] = (x[k] g_0) / x[0], g_0 the level_g of the species' first level
  * The stimulated-emission factor needs no change: the existing clamp of negative values is what the reference does for the lines of
  * NLTE species.  NOT covered here: the collision matrix of atomic data with collision_data (the next section
- * adds it); not covered at all: NLTE ionization, the helium treatments, continuum.
+ * adds it); helium_treatment recomb-nlte: tardis_mc_set_ionization_options; not covered at all: NLTE ionization, continuum.
  * Kernels (csrc/nlte_excitation.hpp): a streaming kernel writes r_ul / r_lu of the NLTE lines; then one workgroup per (species, shell)
  * builds and solves the system on a column-major matrix of odd leading dimension, either in its LDS (species of up to 141 levels) or in
  * a slab of HBM per (species, shell) -- same operations, same order, same bits (csrc/nlte_plan.hpp chooses per species).  No workgroup
@@ -824,6 +824,73 @@ int tardis_mc_check_nlte_collision_data(const TardisMcNlteCollisionData *collisi
  * are still resident.  tardis_mc_last_nlte_ms keeps its two outputs: the collision kernel counts under assemble_ms, the added phase
  * of the solve kernel under solve_ms. */
 int tardis_mc_get_nlte_collision_rates(TardisMcContext *ctx, double *c_ul, double *c_lu);
+
+/* ---- two switches of the nebular ionisation stage: helium_treatment recomb-nlte and delta_treatment ----------------------------
+ * What the legacy plasma computes for a configuration with plasma.helium_treatment: recomb-nlte (HeliumNLTE, the He-rich models of
+ * Type Ib / IIb) and / or plasma.delta_treatment: a number.  Both are properties of the installed options, like the NLTE data:
+ * tardis_mc_update_plasma takes no argument for them.  fp64, no contraction, exp the transport's own (mcm::exp), every product and sum
+ * a rounding of its own.  Notation of the plasma section above: lbf[k] the level Boltzmann factors as the Boltzmann stage (and the NLTE
+ * stage, if any) left them -- with W on the non-metastable levels in dilute-lte --, g_e, beta_rad, t_e, zeta, delta, chi_i.
+ * delta_treatment (use_delta_treatment 1): delta = delta_treatment for every ion and shell replaces both branches of the
+ *   RadiationFieldCorrection expression; everything else of the nebular phi is unchanged; no exp is evaluated for delta.  In
+ *   ionization_mode 1 (lte) there is no delta and the switch has no effect.
+ * helium_treatment 1 (recomb-nlte): the ions a, a+1, a+2 of the element helium_element are He I, He II, He III; g1 = level_g of
+ *   He II's first level, g2 = that of He III's only level.  Once per update and shell, the relative populations hp[k] of helium's levels:
+ *     He I, first level:    0.0
+ *     He I, other levels:   (((lbf[k] (1 / (2 g1))) (1 / g_e)) (1 / (W W))) exp(chi_a beta_rad)
+ *     He II, first level:   1.0
+ *     He II, other levels:  lbf[k] (1 / g1)
+ *     He III:               (((((2 (g2 / g1)) g_e) exp(chi_(a+1) (-beta_rad))) W) ((delta_(a+1) zeta_(a+1)) + W (1 - zeta_(a+1)))) sqrt(t_e / t_rad)
+ *                           (delta_(a+1) honours use_delta_treatment)
+ *   Helium is no post-processing step: it sits INSIDE the electron-density iteration.  In every pass, after the ordinary ion
+ *   populations of all elements -- helium included -- have been formed with this pass's n_e and cut at 1e-20:
+ *     u[k] = hp[k] n_e for the levels of He I, u[k] = hp[k] for those of He II and He III
+ *     total = the serial sum of u in level order (He I, He II, He III), from 0.0
+ *     f = number_density[helium_element] / total;   v[k] = u[k] f
+ *     N[a] = the serial sum of v over He I's levels from 0.0, N[a+1] likewise over He II's, N[a+2] = v[He III]
+ *   These three rows replace the ordinary ones; the 1e-20 cut is NOT applied to them (the reference cuts before it overwrites).  The
+ *   new n_e is the serial sum over all ion rows of N_i ion_charge[i] in the order stated above, the helium rows replaced.  The NaN
+ *   vote, the 5 % rule in every shell and the averaging are unchanged.  After the iteration the populations of helium's levels are
+ *   the v of the last pass -- the pass whose n_e is handed out --, not (lbf / Z) N; all other levels as above.
+ *   tardis_mc_get_plasma then returns the replaced rows in ion_number_density, v in level_number_density and the unchanged
+ *   partition_function; the opacity stages run on these populations.
+ * Kernels (csrc/plasma_update.hpp): helium_relative_kernel, a thread per (helium level, shell), writes hp as [K_He][S] behind the NLTE
+ * stage; the ionisation kernel has a compile-time helium form in which a lane (= shell) runs the three serial sums of a pass over
+ * hp[.][s], the loads issued in batches ahead of the dependent adds, and writes v once, from the n_e it hands out; a small kernel
+ * behind the population kernel copies v over helium's levels of n_t.  With no options installed the instantiation of before runs.  No
+ * atomics: two calls give identical bits.  Not covered: helium_treatment numerical-nlte (it reads an external file), NLTE
+ * ionisation, continuum. */
+typedef struct TardisMcIonizationOptions {
+    int32_t helium_treatment;     /* 0 none, 1 recomb-nlte */
+    int32_t use_delta_treatment;  /* 0: RadiationFieldCorrection as documented above; 1: delta = delta_treatment for every ion and shell */
+    int64_t helium_element;       /* row of element_ion_edge; read only with helium_treatment 1 */
+    double  delta_treatment;      /* read only with use_delta_treatment 1; must be finite */
+} TardisMcIonizationOptions;
+
+/* The options of the resident plasma data; after tardis_mc_set_plasma_data (TARDIS_MC_ERR_STATE before it), dropped by whatever drops
+ * the plasma data (tardis_mc_set_opacity, set_line_data, set_plasma_data) and by nothing else -- tardis_mc_set_nlte_data and
+ * tardis_mc_set_nlte_collision_data keep them; options == NULL clears them.  The call clears what was installed before it validates:
+ * a refused call leaves none.  Checked on the host before anything is indexed (tardis_mc_check_ionization_options):
+ * TARDIS_MC_ERR_INVALID_ARGUMENT for an unknown helium_treatment, a delta_treatment that is not finite, a helium_element outside
+ * [0, E), a helium element without exactly three ions, ion charges other than 0, 1, 2, a He III without exactly one level; the
+ * message names which.  With options installed tardis_mc_update_plasma returns TARDIS_MC_ERR_INVALID_ARGUMENT, before the device is
+ * touched, for helium_treatment 1 with ionization_mode 1 and for helium_treatment 1 while an installed NLTE species is one of the
+ * three helium ions (both would write the same Boltzmann factors' consumers; no order is defined). */
+int tardis_mc_set_ionization_options(TardisMcContext *ctx, const TardisMcIonizationOptions *options);
+/* The host-side check of tardis_mc_set_ionization_options on plain arrays, without a context or a device: element_ion_edge
+ * [n_elements + 1], ion_level_edge and ion_charge of the plasma data (read only with helium_treatment 1).  0 or
+ * TARDIS_MC_ERR_INVALID_ARGUMENT (the message: tardis_mc_last_error(NULL)). */
+int tardis_mc_check_ionization_options(const TardisMcIonizationOptions *options, int64_t n_elements, const int64_t *element_ion_edge,
+                                       const int64_t *ion_level_edge, const double *ion_charge);
+/* Helium of the last successful tardis_mc_update_plasma: relative_population (hp) and level_number_density (the v of the pass whose
+ * n_e was handed out), [K_He,S] each, K_He the level count of the helium element.  Either pointer may be NULL.
+ * TARDIS_MC_ERR_STATE when that update ran without helium_treatment, after a failed update, and whenever tardis_mc_get_plasma
+ * answers TARDIS_MC_ERR_STATE. */
+int tardis_mc_get_helium(TardisMcContext *ctx, double *relative_population, double *level_number_density);
+/* Device time of helium_relative_kernel in the last tardis_mc_update_plasma, in ms (the helium form of the iteration counts under
+ * out_ionization_ms of tardis_mc_last_plasma_update_ms, whose partition figure excludes this kernel).  TARDIS_MC_ERR_STATE unless
+ * the last update ran with helium_treatment. */
+int tardis_mc_last_helium_ms(TardisMcContext *ctx, double *out_relative_ms);
 
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the

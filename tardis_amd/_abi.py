@@ -187,8 +187,19 @@ class TardisMcNlteCollisionData(C.Structure):
     ]
 
 
+class TardisMcIonizationOptions(C.Structure):
+    """The switches of the nebular ionisation stage (tardis_mc_set_ionization_options)."""
+    _fields_ = [
+        ("helium_treatment", C.c_int32),
+        ("use_delta_treatment", C.c_int32),
+        ("helium_element", C.c_int64),
+        ("delta_treatment", C.c_double),
+    ]
+
+
 IONIZATION_MODES = {"nebular": 0, "lte": 1}
 EXCITATION_MODES = {"dilute-lte": 0, "lte": 1}
+HELIUM_TREATMENTS = {None: 0, "none": 0, "recomb-nlte": 1}
 
 
 _LI_F64 = ("li_radius", "li_nu", "li_energy", "li_before_nu", "li_before_mu", "li_before_energy", "li_after_nu",
@@ -416,6 +427,26 @@ def marshal_nlte_collision_data(cd) -> Marshalled:
         raise ValueError("C_ul must be [n_pairs, n_temperatures]")
     s = TardisMcNlteCollisionData(NS, NT, _dp(temps), NP, _ip(edge), _ip(lv[0]), _ip(lv[1]), _dp(f[0]), _dp(f[1]), _dp(c))
     return Marshalled(s, [temps, edge, c] + lv + f)
+
+
+def marshal_ionization_options(helium_treatment=None, helium_element=None, delta_treatment=None, plasma_data=None) -> Marshalled:
+    """helium_treatment: None or "recomb-nlte" (anything else: ValueError); helium_element: the element row that is helium, None for
+    the row where ``plasma_data.atomic_number == 2`` (ValueError when there is none); delta_treatment: None for the
+    RadiationFieldCorrection expression, else the number that replaces it.  helium_element is resolved only with a helium treatment."""
+    if helium_treatment not in HELIUM_TREATMENTS:
+        raise ValueError(f"helium_treatment must be None or 'recomb-nlte', not {helium_treatment!r}")
+    helium = HELIUM_TREATMENTS[helium_treatment]
+    element = 0
+    if helium:
+        if helium_element is None:
+            rows = np.flatnonzero(np.asarray(getattr(plasma_data, "atomic_number", ()), dtype=np.int64) == 2)
+            if len(rows) == 0:
+                raise ValueError("helium_treatment needs an element with atomic_number 2 in the plasma data, or helium_element")
+            element = int(rows[0])
+        else:
+            element = int(helium_element)
+    s = TardisMcIonizationOptions(helium, int(delta_treatment is not None), element, 0.0 if delta_treatment is None else float(delta_treatment))
+    return Marshalled(s, [])
 
 
 def marshal_plasma_update(t_radiative, dilution_factor, n_shells, ionization_mode=0, excitation_mode=0,

@@ -69,6 +69,10 @@ SYMBOLS = {
     "tardis_mc_get_plasma": (_i, [_vp] * 5 + [C.POINTER(C.c_int32)]),
     "tardis_mc_last_plasma_update_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 4),
     "tardis_mc_plasma_update_path": (_i, [C.c_int64]),
+    "tardis_mc_set_ionization_options": (_i, [_vp, _vp]),
+    "tardis_mc_check_ionization_options": (_i, [_vp, C.c_int64, _vp, _vp, _vp]),
+    "tardis_mc_get_helium": (_i, [_vp, _vp, _vp]),
+    "tardis_mc_last_helium_ms": (_i, [_vp, C.POINTER(C.c_double)]),
     "tardis_mc_set_nlte_data": (_i, [_vp, _vp]),
     "tardis_mc_check_nlte_data": (_i, [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp]),
     "tardis_mc_get_nlte": (_i, [_vp, _vp, _vp]),

@@ -16,6 +16,10 @@
 // workgroup with a lane per shell: a shell's state is private, the only thing the shells share is the vote "every shell has converged",
 // taken with a workgroup barrier (__syncthreads_and / _or).  Nothing waits on another workgroup's memory.  No atomics: two calls give
 // identical bits.
+//
+// The options of tardis_mc_set_ionization_options, both compile-time forms of plasma_ionization_kernel: delta_treatment puts a number
+// in the place of delta in the phi prologue; helium_treatment recomb-nlte adds helium_relative_kernel (hp[K_He][S], shell fastest), a form whose
+// lanes run three serial sums per pass over their column of hp, and helium_population_kernel behind the population kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -99,6 +103,12 @@ struct PlasmaIonArgs {
     double *n_ion;              // [I][S] out
     double *n_e;                // [S] out: the electron density the last pass used
     int *status;                // [2] out: PLASMA_*, passes
+    // tardis_mc_set_ionization_options (zero without options)
+    double delta_treatment;     // FIXED_DELTA: delta for every ion and shell
+    int he_element, he_ion;     // the helium form: helium's element row and its first ion a
+    int he_n1, he_n2;           // levels of He I; of He I and He II together (He III is local level he_n2)
+    const double *hp;           // [K_He][S] helium_relative_kernel's relative populations
+    double *he_v;               // [K_He][S] out: the helium level populations of the pass whose n_e is handed out
 };
 
 // numpy.nan_to_num
@@ -110,7 +120,104 @@ __device__ __forceinline__ double plasma_nan_to_num(double x)
     return x;
 }
 
+// RadiationFieldCorrection with departure_coefficient 1 / W (fa = t_e / (((1 / W) W) t_rad))
+__device__ __forceinline__ double plasma_delta(double chi, double chi_0, double fa, double beta_rad, double beta_e)
+{
+    if (chi >= chi_0) return fa * mcm::exp(chi * (beta_rad - beta_e));
+    return (1 - mcm::exp(chi * beta_rad - beta_rad * chi_0)) + fa * mcm::exp(chi * beta_rad - beta_e * chi_0);
+}
+
+// zeta's bracket in the table: hi = clip(searchsorted(zeta_t, t_rad, side="left"), 1, NT - 1)
+__device__ __forceinline__ int plasma_zeta_bracket(const double *__restrict__ zeta_t, int NT, double t_rad)
+{
+    int hi = 0;
+    while (hi < NT && zeta_t[hi] < t_rad) ++hi;
+    return hi < 1 ? 1 : (hi > NT - 1 ? NT - 1 : hi);
+}
+
+struct HeliumArgs {
+    int S, NT;
+    long long K;
+    int k0, n1, n2;             // helium's first level; levels of He I; of He I and He II together (K_He = n2 + 1)
+    int ion;                    // a, the row of He I
+    int fixed_delta;
+    double delta_treatment;
+    double link, chi_0, k_b, two_pi_me, hh;
+    const double *g;            // [K]
+    const double *chi;          // [I]
+    const double *zeta_t;       // [NT]
+    const double *zeta;         // [I][NT]
+    const double *t_rad, *w;    // [S]
+    const double *lbf_t;        // [S][K]
+    double *hp;                 // [K_He][S] out
+};
+
+// The populations of helium's levels relative to the He II ground level, before the electron density enters (HeliumNLTE): a thread
+// per (helium level, shell), the shell fastest, so that the lanes of the ionisation kernel (lane = shell) read consecutive addresses.
+__global__ void __launch_bounds__(256) helium_relative_kernel(HeliumArgs a)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)(a.n2 + 1) * a.S) return;
+    const int s = (int)(e % a.S), k = (int)(e / a.S);
+    const double t_rad = a.t_rad[s], w = a.w[s];
+    const double beta_rad = 1 / (a.k_b * t_rad);
+    const double x = (a.two_pi_me / beta_rad) / a.hh;
+    const double g_e = x * sqrt(x);
+    const double g1 = a.g[a.k0 + a.n1];
+    const double lbf = a.lbf_t[(long long)s * a.K + a.k0 + k];
+    double hp;
+    if (k == 0) hp = 0.0;
+    else if (k < a.n1) hp = (((lbf * (1 / (2 * g1))) * (1 / g_e)) * (1 / (w * w))) * mcm::exp(a.chi[a.ion] * beta_rad);
+    else if (k == a.n1) hp = 1.0;
+    else if (k < a.n2) hp = lbf * (1 / g1);
+    else {
+        const int i = a.ion + 1;
+        const double g2 = a.g[a.k0 + a.n2], chi = a.chi[i];
+        const double t_e = a.link * t_rad;
+        const double beta_e = 1 / (a.k_b * t_e);
+        const int hi = plasma_zeta_bracket(a.zeta_t, a.NT, t_rad), lo = hi - 1;
+        const double x_lo = a.zeta_t[lo], dx = a.zeta_t[hi] - x_lo, dt = t_rad - x_lo;
+        const double y_lo = a.zeta[(long long)i * a.NT + lo], y_hi = a.zeta[(long long)i * a.NT + hi];
+        const double slope = (y_hi - y_lo) / dx;
+        const double zeta = slope * dt + y_lo;
+        const double fa = t_e / (((1 / w) * w) * t_rad);
+        const double delta = a.fixed_delta ? a.delta_treatment : plasma_delta(chi, a.chi_0, fa, beta_rad, beta_e);  // (no exp for a fixed delta)
+        hp = (((((2 * (g2 / g1)) * g_e) * mcm::exp(chi * (-beta_rad))) * w) * ((delta * zeta) + w * (1 - zeta))) * sqrt(t_e / t_rad);
+    }
+    a.hp[e] = hp;
+}
+
+// sum + the serial sum of a lane's u (or v) over helium's local levels k0 .. k1-1 of column s: u = hp n_e with NE (the levels of He I),
+// hp without; times f with F.  The loads do not depend on the running sum: a batch of eight is issued ahead of its eight dependent
+// adds, so a lane's chain is one add per level, not one round trip per level.
+template <bool NE, bool F>
+__device__ __forceinline__ double helium_serial_sum(const double *__restrict__ hp_s, int S, int k0, int k1, double n_e, double f, double sum)
+{
+    int k = k0;
+    for (; k + 8 <= k1; k += 8) {
+        double x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = hp_s[(long long)(k + j) * S];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            double u = NE ? x[j] * n_e : x[j];
+            if (F) u = u * f;
+            sum += u;
+        }
+    }
+    for (; k < k1; ++k) {
+        double u = NE ? hp_s[(long long)k * S] * n_e : hp_s[(long long)k * S];
+        if (F) u = u * f;
+        sum += u;
+    }
+    return sum;
+}
+
 // The Saha factors phi and IonNumberDensity.calculate.  One workgroup, lane s = shell s; lanes past S only take part in the votes.
+// HELIUM (helium_treatment recomb-nlte): every pass forms the three helium ion rows from hp and the pass's n_e and puts them in the
+// place of the Saha chain's, uncut.  FIXED_DELTA (delta_treatment): delta is the option's number, no exp is evaluated for it.
+// <false, false> is the kernel of before: it reads none of the options' arguments.
+template <bool HELIUM, bool FIXED_DELTA>
 __global__ void __launch_bounds__(1024) plasma_ionization_kernel(PlasmaIonArgs a)
 {
     const int s = threadIdx.x, S = a.S;
@@ -124,11 +231,7 @@ __global__ void __launch_bounds__(1024) plasma_ionization_kernel(PlasmaIonArgs a
         const double x = (a.two_pi_me / beta_rad) / a.hh;
         const double g_e2 = 2 * (x * sqrt(x));
         const double nb = -beta_rad;
-        // zeta's bracket in the table: hi = clip(searchsorted(zeta_t, t_rad, side="left"), 1, NT - 1)
-        int hi = 0;
-        while (hi < a.NT && a.zeta_t[hi] < t_rad) ++hi;
-        hi = hi < 1 ? 1 : (hi > a.NT - 1 ? a.NT - 1 : hi);
-        const int lo = hi - 1;
+        const int hi = plasma_zeta_bracket(a.zeta_t, a.NT, t_rad), lo = hi - 1;
         const double x_lo = a.zeta_t[lo], dx = a.zeta_t[hi] - x_lo, dt = t_rad - x_lo;
         const double fa = t_e / (((1 / w) * w) * t_rad);
         const double root = sqrt(t_e / t_rad);
@@ -141,9 +244,7 @@ __global__ void __launch_bounds__(1024) plasma_ionization_kernel(PlasmaIonArgs a
                     const double y_lo = a.zeta[(long long)i * a.NT + lo], y_hi = a.zeta[(long long)i * a.NT + hi];
                     const double slope = (y_hi - y_lo) / dx;
                     const double zeta = slope * dt + y_lo;
-                    double delta;
-                    if (chi >= a.chi_0) delta = fa * mcm::exp(chi * (beta_rad - beta_e));
-                    else delta = (1 - mcm::exp(chi * beta_rad - beta_rad * a.chi_0)) + fa * mcm::exp(chi * beta_rad - beta_e * a.chi_0);
+                    const double delta = FIXED_DELTA ? a.delta_treatment : plasma_delta(chi, a.chi_0, fa, beta_rad, beta_e);
                     phi = ((phi * w) * ((zeta * delta) + w * (1 - zeta))) * root;
                 }
                 a.phi[(long long)i * S + s] = phi;
@@ -152,11 +253,32 @@ __global__ void __launch_bounds__(1024) plasma_ionization_kernel(PlasmaIonArgs a
         for (int e = 0; e < a.E; ++e) n_e += a.density[(long long)e * S + s];
     }
     int status = PLASMA_BOUND, passes = 0;
+    const double *hp_s = HELIUM ? a.hp + s : nullptr;  // (column s of hp[K_He][S])
+    double he_f = 0.0;
     while (passes < a.max_iter) {
         double next = 0.0;
         if (on) {
+            double he_0 = 0.0, he_1 = 0.0, he_2 = 0.0;
+            if (HELIUM) {
+                // nothing here depends on the other elements' populations of this pass, only on n_e: formed first, put in place below
+                double total = helium_serial_sum<true, false>(hp_s, S, 0, a.he_n1, n_e, 0.0, 0.0);
+                total = helium_serial_sum<false, false>(hp_s, S, a.he_n1, a.he_n2 + 1, n_e, 0.0, total);
+                he_f = a.density[(long long)a.he_element * S + s] / total;
+                he_0 = helium_serial_sum<true, true>(hp_s, S, 0, a.he_n1, n_e, he_f, 0.0);
+                he_1 = helium_serial_sum<false, true>(hp_s, S, a.he_n1, a.he_n2, n_e, he_f, 0.0);
+                he_2 = hp_s[(long long)a.he_n2 * S] * he_f;
+            }
             for (int e = 0; e < a.E; ++e) {
                 const int i0 = a.element_edge[e], i1 = a.element_edge[e + 1];
+                if (HELIUM && e == a.he_element) {  // the Saha chain's three rows would be overwritten unread; no 1e-20 cut on these
+                    a.n_ion[(long long)i0 * S + s] = he_0;
+                    a.n_ion[(long long)(i0 + 1) * S + s] = he_1;
+                    a.n_ion[(long long)(i0 + 2) * S + s] = he_2;
+                    next += he_0 * a.charge[i0];
+                    next += he_1 * a.charge[i0 + 1];
+                    next += he_2 * a.charge[i0 + 2];
+                    continue;
+                }
                 // the running products land in the rows they scale below: the same lane writes and reads them
                 double cp = 1.0, sum = 0.0;
                 for (int i = i0; i + 1 < i1; ++i) {
@@ -181,6 +303,12 @@ __global__ void __launch_bounds__(1024) plasma_ionization_kernel(PlasmaIonArgs a
         if (on) n_e = 0.5 * (next + n_e);
     }
     if (on) a.n_e[s] = n_e;
+    if (HELIUM && on) {  // v of the last pass: n_e is the one it used, he_f its factor -- the same products, the same bits
+        for (int k = 0; k <= a.he_n2; ++k) {
+            const double h = hp_s[(long long)k * S];
+            a.he_v[(long long)k * S + s] = (k < a.he_n1 ? h * n_e : h) * he_f;
+        }
+    }
     if (s == 0) { a.status[0] = status; a.status[1] = passes; }
 }
 
@@ -194,6 +322,15 @@ __global__ void __launch_bounds__(256) plasma_population_kernel(const double *__
         const long long i = (long long)level_ion[k] * S + s;
         n_t[s * K + k] = (lbf_t[s * K + k] / z[i]) * n_ion[i];
     }
+}
+
+// helium's levels of n_t are the v of the iteration's last pass, not (lbf / Z) N: directly behind plasma_population_kernel
+__global__ void __launch_bounds__(256) helium_population_kernel(const double *__restrict__ v, int k0, int levels, long long K, int S, double *__restrict__ n_t)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)levels * S) return;
+    const long long s = e / levels, k = e % levels;
+    n_t[s * K + k0 + k] = v[k * S + s];
 }
 
 }  // namespace mc

@@ -447,7 +447,8 @@ struct TardisMcContext {
     struct PlasmaUpdate {
         DevBuf energy, g, meta, level_ion, ion_edge, elem_edge, charge, chi, zeta_t, zeta, density, long_ions;
         DevBuf lbf_t, z, phi, n_ion, n_e, status;
-        std::vector<int> h_ion_edge;
+        std::vector<int> h_ion_edge, h_elem_edge;
+        std::vector<double> h_charge;  // (with the edges: what set_ionization_options checks the helium element against)
         double t_min = 0.0, t_max = 0.0, chi_0 = 0.0, link = 0.0;
         bool have = false, valid = false, timed = false;  // (have: plasma data installed; valid: Z / N / n_e belong to the resident n_t)
         int ions = 0, elements = 0, nt = 0, iterations = 0;
@@ -487,6 +488,17 @@ struct TardisMcContext {
         double t_first = 0.0, t_last = 0.0;
         void release() { release_buffers(temperatures, c_t, delta_e, inv_g, lower, upper, sp_pair_edge, c_ul, c_lu); }
     } nc;
+    // The options of the ionisation stage (plasma_update.hpp).  Per set_ionization_options: the two switches and where helium sits in the plasma data.
+    // Per update_plasma with helium_treatment: hp and v, [K_He][S] each (tardis_mc_get_helium).
+    struct IonizationOptions {
+        DevBuf hp, v;
+        bool have = false, valid = false, timed = false, ran = false;  // (have: options installed; valid: hp / v are those of the last successful update)
+        int helium = 0, fixed_delta = 0;
+        double delta = 0.0;
+        int element = 0, ion = 0, k0 = 0, n1 = 0, n2 = 0;  // helium's element row and first ion; its first level; levels of He I; of He I and He II together
+        hipEvent_t ev[2] = {nullptr, nullptr};  // around helium_relative_kernel (tardis_mc_last_helium_ms)
+        void release() { release_buffers(hp, v); destroy_events(ev); }
+    } he;
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -898,7 +910,7 @@ void drop_from(TardisMcContext *ctx, Rung rung)
 {
     switch (rung) {
     case RUNG_LINE_DATA: ctx->ou.have = ctx->ou.valid = false; [[fallthrough]];
-    case RUNG_PLASMA_DATA: ctx->pl.have = ctx->pl.valid = false; [[fallthrough]];
+    case RUNG_PLASMA_DATA: ctx->pl.have = ctx->pl.valid = false; ctx->he.have = ctx->he.valid = false; [[fallthrough]];  // (the ionisation options sit beside the NLTE data, on the plasma data)
     case RUNG_NLTE_DATA: ctx->nl.have = ctx->nl.valid = false; [[fallthrough]];
     case RUNG_COLLISION_DATA: ctx->nc.have = ctx->nc.valid = false;
     }
@@ -2318,7 +2330,7 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
     ctx->ot.release(); ctx->wt.release(); ctx->sc.release(); ctx->sw.release(); ctx->es.release(); ctx->pk.release(); ctx->vl.release(); ctx->el.release();
     ctx->wv.release(); ctx->lt.release(); ctx->rs.release(); ctx->sf.release(); ctx->pg.release();
-    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release();
+    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release(); ctx->he.release();
     ctx->release();
     delete ctx;
 }
@@ -4458,11 +4470,49 @@ int tardis_mc_set_plasma_data(TardisMcContext *ctx, const TardisMcPlasmaData *d)
     if ((rc = upload(ctx, ctx->pl.density, d->number_density, E * S))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors are the sources of asynchronous copies)
     ctx->pl.h_ion_edge.swap(ion_edge);
+    ctx->pl.h_elem_edge.swap(elem_edge);
+    ctx->pl.h_charge.assign(d->ion_charge, d->ion_charge + I);
     ctx->pl.ions = (int)I; ctx->pl.elements = (int)E; ctx->pl.nt = (int)NT;
     ctx->pl.t_min = d->zeta_temperatures[0]; ctx->pl.t_max = d->zeta_temperatures[NT - 1];
     ctx->pl.chi_0 = d->chi_0; ctx->pl.link = d->link_t_rad_t_electron;
     ctx->pl.long_rows_built = -2;  // (the list of the long ions is made by the first update)
     ctx->pl.have = true;
+    return TARDIS_MC_OK;
+}
+
+/* ---- the options of the ionisation stage: helium_treatment recomb-nlte, delta_treatment (plasma_update.hpp) ---- */
+int tardis_mc_check_ionization_options(const TardisMcIonizationOptions *o, int64_t n_elements, const int64_t *element_ion_edge, const int64_t *ion_level_edge,
+                                       const double *ion_charge)
+{
+    if (!o) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid ionization options");
+    const std::string err = plup::check_ionization_options(o->helium_treatment, o->use_delta_treatment, (long long)o->helium_element, o->delta_treatment,
+                                                           (long long)n_elements, element_ion_edge, ion_level_edge, ion_charge);
+    return err.empty() ? TARDIS_MC_OK : fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+}
+
+int tardis_mc_set_ionization_options(TardisMcContext *ctx, const TardisMcIonizationOptions *o)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->pl.have) return fail(ctx, TARDIS_MC_ERR_STATE, "set_plasma_data must precede set_ionization_options");
+    ctx->he.have = ctx->he.valid = false;
+    if (!o) return TARDIS_MC_OK;
+    // everything the kernels index with is checked here, on the host
+    const std::string err = plup::check_ionization_options(o->helium_treatment, o->use_delta_treatment, (long long)o->helium_element, o->delta_treatment,
+                                                           (long long)ctx->pl.elements, ctx->pl.h_elem_edge.data(), ctx->pl.h_ion_edge.data(), ctx->pl.h_charge.data());
+    if (!err.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+    ctx->he.helium = o->helium_treatment;
+    ctx->he.fixed_delta = o->use_delta_treatment != 0;
+    ctx->he.delta = ctx->he.fixed_delta ? o->delta_treatment : 0.0;
+    ctx->he.element = ctx->he.ion = ctx->he.k0 = ctx->he.n1 = ctx->he.n2 = 0;
+    if (ctx->he.helium) {
+        const int a = ctx->pl.h_elem_edge[(size_t)o->helium_element];
+        ctx->he.element = (int)o->helium_element;
+        ctx->he.ion = a;
+        ctx->he.k0 = ctx->pl.h_ion_edge[(size_t)a];
+        ctx->he.n1 = ctx->pl.h_ion_edge[(size_t)a + 1] - ctx->he.k0;
+        ctx->he.n2 = ctx->pl.h_ion_edge[(size_t)a + 2] - ctx->he.k0;
+    }
+    ctx->he.have = true;
     return TARDIS_MC_OK;
 }
 
@@ -4771,6 +4821,15 @@ static int plasma_update_check(TardisMcContext *ctx, const TardisMcPlasmaUpdate 
         return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity, set_line_data and set_plasma_data must precede update_plasma");
     if ((p->ionization_mode != 0 && p->ionization_mode != 1) || (p->excitation_mode != 0 && p->excitation_mode != 1))
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "unknown ionization_mode %d / excitation_mode %d", p->ionization_mode, p->excitation_mode);
+    if (ctx->he.have && ctx->he.helium) {
+        if (p->ionization_mode != 0)
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "helium_treatment recomb-nlte belongs to the nebular ionisation: ionization_mode %d is refused", p->ionization_mode);
+        if (ctx->nl.have)
+            for (size_t sp = 0; sp < ctx->nl.h_ion.size(); ++sp)
+                if (ctx->nl.h_ion[sp] >= ctx->he.ion && ctx->nl.h_ion[sp] < ctx->he.ion + 3)
+                    return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "helium_treatment recomb-nlte while NLTE species %zu is the helium ion %d: both treat helium's levels, no order is defined",
+                                sp, ctx->nl.h_ion[sp]);
+    }
     int rc;
     if ((rc = opacity_update_check(ctx, u))) return rc;
     const size_t S = (size_t)ctx->n_shells;
@@ -4805,6 +4864,12 @@ static int plasma_update_prepare(TardisMcContext *ctx)
     HIP_TRY(ctx, ctx->pl.status.ensure(2 * sizeof(int)));
     if ((rc = ensure_events(ctx, ctx->ou.ev))) return rc;
     if ((rc = ensure_events(ctx, ctx->pl.ev))) return rc;
+    if (ctx->he.have && ctx->he.helium) {
+        const size_t KH = (size_t)ctx->he.n2 + 1;
+        HIP_TRY(ctx, ctx->he.hp.ensure(KH * S * sizeof(double)));
+        HIP_TRY(ctx, ctx->he.v.ensure(KH * S * sizeof(double)));
+        if ((rc = ensure_events(ctx, ctx->he.ev))) return rc;
+    }
     return ensure_events(ctx, ctx->nl.ev);
 }
 
@@ -4817,7 +4882,8 @@ static int plasma_update_enqueue(TardisMcContext *ctx, const TardisMcPlasmaUpdat
     // beta_sobolev of the previous update, read before this update's line kernel writes over it; none since the last set_opacity: 1.0
     const double *nlte_beta = ctx->ou.valid && !ctx->nl.classical ? ctx->ou.beta_t.as<double>() : nullptr;
     int rc;
-    ctx->pl.valid = ctx->nl.valid = ctx->nc.valid = false;
+    ctx->pl.valid = ctx->nl.valid = ctx->nc.valid = ctx->he.valid = false;
+    ctx->he.ran = ctx->he.timed = false;
     HIP_TRY(ctx, hipMemcpyAsync(d_t, p->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_w, p->dilution_factor, S * 8, hipMemcpyHostToDevice, ctx->stream));
     ctx->nl.ran = ctx->nl.timed = ctx->pl.timed = false;  // (ou.timed and the ou.ev events stay the previous update's until this solve has succeeded)
@@ -4830,6 +4896,23 @@ static int plasma_update_enqueue(TardisMcContext *ctx, const TardisMcPlasmaUpdat
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[1], ctx->stream));
     if (ctx->nl.have && (rc = nlte_stage(ctx, p, nlte_beta, d_t, d_w))) return rc;  // the NLTE species' Boltzmann factors, before anything reads them
+    const bool helium = ctx->he.have && ctx->he.helium;
+    const bool fixed_delta = ctx->he.have && ctx->he.fixed_delta;
+    if (helium) {  // hp of helium's levels from the Boltzmann factors as they now stand
+        mc::HeliumArgs h;
+        h.S = (int)S; h.NT = ctx->pl.nt; h.K = (long long)K;
+        h.k0 = ctx->he.k0; h.n1 = ctx->he.n1; h.n2 = ctx->he.n2; h.ion = ctx->he.ion;
+        h.fixed_delta = fixed_delta; h.delta_treatment = ctx->he.delta;
+        h.link = ctx->pl.link; h.chi_0 = ctx->pl.chi_0; h.k_b = K_BOLTZMANN; h.two_pi_me = 2 * M_PI * M_ELECTRON; h.hh = H_PLANCK * H_PLANCK;
+        h.g = ctx->pl.g.as<double>(); h.chi = ctx->pl.chi.as<double>(); h.zeta_t = ctx->pl.zeta_t.as<double>(); h.zeta = ctx->pl.zeta.as<double>();
+        h.t_rad = d_t; h.w = d_w; h.lbf_t = ctx->pl.lbf_t.as<double>(); h.hp = ctx->he.hp.as<double>();
+        const long long n = (long long)(h.n2 + 1) * (long long)S;
+        HIP_TRY(ctx, hipEventRecord(ctx->he.ev[0], ctx->stream));
+        hipLaunchKernelGGL(mc::helium_relative_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, h);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipEventRecord(ctx->he.ev[1], ctx->stream));
+        ctx->he.ran = true;
+    }
     const long long n_long = ctx->pl.n_long;
     if (n_long < (long long)I) {
         const long long n = (long long)I * (long long)S;
@@ -4853,7 +4936,15 @@ static int plasma_update_enqueue(TardisMcContext *ctx, const TardisMcPlasmaUpdat
     a.zeta_t = ctx->pl.zeta_t.as<double>(); a.zeta = ctx->pl.zeta.as<double>(); a.density = ctx->pl.density.as<double>();
     a.t_rad = d_t; a.w = d_w; a.z = ctx->pl.z.as<double>();
     a.phi = ctx->pl.phi.as<double>(); a.n_ion = ctx->pl.n_ion.as<double>(); a.n_e = ctx->pl.n_e.as<double>(); a.status = ctx->pl.status.as<int>();
-    hipLaunchKernelGGL(mc::plasma_ionization_kernel, dim3(1), dim3((unsigned)((S + 63) / 64 * 64)), 0, ctx->stream, a);
+    a.delta_treatment = fixed_delta ? ctx->he.delta : 0.0;
+    a.he_element = a.he_ion = a.he_n1 = a.he_n2 = 0; a.hp = nullptr; a.he_v = nullptr;
+    if (helium) {
+        a.he_element = ctx->he.element; a.he_ion = ctx->he.ion; a.he_n1 = ctx->he.n1; a.he_n2 = ctx->he.n2;
+        a.hp = ctx->he.hp.as<double>(); a.he_v = ctx->he.v.as<double>();
+    }
+    auto ionization_kernel = helium ? (fixed_delta ? mc::plasma_ionization_kernel<true, true> : mc::plasma_ionization_kernel<true, false>)
+                                    : (fixed_delta ? mc::plasma_ionization_kernel<false, true> : mc::plasma_ionization_kernel<false, false>);
+    hipLaunchKernelGGL(ionization_kernel, dim3(1), dim3((unsigned)((S + 63) / 64 * 64)), 0, ctx->stream, a);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[3], ctx->stream));
     return TARDIS_MC_OK;
@@ -4906,6 +4997,13 @@ static int plasma_update_install(TardisMcContext *ctx, const TardisMcOpacityUpda
     hipLaunchKernelGGL(mc::plasma_population_kernel, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->pl.lbf_t.as<double>(), ctx->pl.level_ion.as<int>(),
                        ctx->pl.z.as<double>(), ctx->pl.n_ion.as<double>(), (long long)K, (int)S, ctx->ou.n_t.as<double>());
     HIP_TRY(ctx, hipGetLastError());
+    if (ctx->he.ran) {  // helium's levels are the v of the last pass
+        const int levels = ctx->he.n2 + 1;
+        const long long n = (long long)levels * (long long)S;
+        hipLaunchKernelGGL(mc::helium_population_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->he.v.as<double>(), ctx->he.k0, levels,
+                           (long long)K, (int)S, ctx->ou.n_t.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
     HIP_TRY(ctx, ctx->ot.n_e.ensure(S * sizeof(double)));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->ot.n_e.p, ctx->pl.n_e.p, S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[4], ctx->stream));
@@ -4915,6 +5013,7 @@ static int plasma_update_install(TardisMcContext *ctx, const TardisMcOpacityUpda
     ctx->pl.timed = ctx->pl.valid = true;
     ctx->nl.ran = ctx->nl.valid = ctx->nl.timed = ctx->nl.have;
     ctx->nc.valid = ctx->nl.have && ctx->nc.have;
+    ctx->he.valid = ctx->he.timed = ctx->he.ran;
     return TARDIS_MC_OK;
 }
 
@@ -4946,6 +5045,7 @@ int tardis_mc_last_plasma_update_ms(TardisMcContext *ctx, double *out_boltzmann_
     if (rc) return rc;
     // (the NLTE stage sits between the Boltzmann and the partition stage and has events of its own: tardis_mc_last_nlte_ms)
     if (ctx->nl.ran) ev[1] = ctx->nl.ev[2];
+    if (ctx->he.ran) ev[1] = ctx->he.ev[1];  // (helium_relative_kernel, behind the NLTE stage: tardis_mc_last_helium_ms)
     return event_intervals_ms(ctx, ev + 1, 3, out + 1);
 }
 
@@ -4964,6 +5064,26 @@ int tardis_mc_get_plasma(TardisMcContext *ctx, double *level_number_density, dou
                                  {(void *)electron_density, ctx->pl.n_e.p, S * sizeof(double)}}, false));
     if (iterations) *iterations = ctx->pl.iterations;
     return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_helium(TardisMcContext *ctx, double *relative_population, double *level_number_density)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->he.valid || !ctx->pl.valid) return fail(ctx, TARDIS_MC_ERR_STATE, "get_helium needs a successful update_plasma that ran with helium_treatment");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = ((size_t)ctx->he.n2 + 1) * (size_t)ctx->n_shells * sizeof(double);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, host_copy(ctx, {{(void *)relative_population, ctx->he.hp.p, bytes}, {(void *)level_number_density, ctx->he.v.p, bytes}}, false));
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_last_helium_ms(TardisMcContext *ctx, double *out_relative_ms)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->he.timed || !ctx->pl.timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_plasma with helium_treatment has been timed yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double *const out[1] = {out_relative_ms};
+    return event_intervals_ms(ctx, ctx->he.ev, 1, out);
 }
 
 

@@ -53,6 +53,8 @@ class Engine:
         self.plasma_data = None      # ... and set_plasma_data() (None after every set_opacity / set_line_data / run)
         self.nlte_data = None        # ... and set_nlte_data() (None after whatever drops the plasma data)
         self.nlte_collision_data = None  # ... and set_nlte_collision_data() (None after whatever drops the NLTE data)
+        self.ionization_options = None   # ... and set_ionization_options(): (helium_treatment, helium_element, delta_treatment); None after whatever drops the plasma data
+        self.n_helium_levels = 0
         self.n_nlte_collision_pairs = 0
         self.n_nlte_levels = 0
         self.n_plasma_levels = self.n_ions = 0
@@ -124,6 +126,7 @@ class Engine:
         self.plasma_data = None
         self.nlte_data = None
         self.nlte_collision_data = None
+        self.ionization_options = None
         self.opacity_generation += 1
         self._check(self._L.tardis_mc_set_opacity(self._h, m.ref()), "set_opacity")
         self.n_lines, self.n_shells = int(m.struct.n_lines), int(m.struct.n_shells)
@@ -141,6 +144,7 @@ class Engine:
         self.plasma_data = None
         self.nlte_data = None
         self.nlte_collision_data = None
+        self.ionization_options = None
         self._check(self._L.tardis_mc_set_line_data(self._h, m.ref()), "set_line_data")
         self.line_data = line_data
 
@@ -195,6 +199,7 @@ class Engine:
         self.plasma_data = None
         self.nlte_data = None
         self.nlte_collision_data = None
+        self.ionization_options = None
         self._check(self._L.tardis_mc_set_plasma_data(self._h, m.ref()), "set_plasma_data")
         self.n_plasma_levels, self.n_ions = int(m.struct.n_levels), int(m.struct.n_ions)
         self.plasma_data = plasma_data
@@ -245,6 +250,40 @@ class Engine:
         out = dict(zip(("boltzmann_ms", "partition_ms", "ionization_ms", "population_ms"), (x.value for x in v)))
         out.update(self.last_opacity_update_ms())
         return out
+
+    def set_ionization_options(self, helium_treatment=None, helium_element=None, delta_treatment=None):
+        """The switches of update_plasma()'s nebular ionisation (`tardis_mc_set_ionization_options`), after set_plasma_data():
+        ``helium_treatment`` None or "recomb-nlte" (what ``plasma.helium_treatment`` is to a configuration), ``helium_element`` the
+        element row that is helium -- None: the row where ``plasma_data.atomic_number == 2``, ValueError when there is none --, and
+        ``delta_treatment`` None or the number that replaces the radiation-field correction.  All three None clears the options;
+        whatever drops the plasma data drops them too, set_nlte_data() does not."""
+        self.ionization_options = None
+        if helium_treatment is None and delta_treatment is None:
+            self._check(self._L.tardis_mc_set_ionization_options(self._h, None), "set_ionization_options")
+            return
+        m = _abi.marshal_ionization_options(helium_treatment, helium_element, delta_treatment, self.plasma_data)
+        self._check(self._L.tardis_mc_set_ionization_options(self._h, m.ref()), "set_ionization_options")
+        self.n_helium_levels = 0
+        if m.struct.helium_treatment:
+            pd, e = self.plasma_data, int(m.struct.helium_element)
+            a, b = int(pd.element_ion_edge[e]), int(pd.element_ion_edge[e + 1])
+            self.n_helium_levels = int(pd.ion_level_edge[b]) - int(pd.ion_level_edge[a])
+        self.ionization_options = (helium_treatment, helium_element, delta_treatment)
+
+    def get_helium(self, relative_population=True, level_number_density=True) -> dict:
+        """Helium of the last update_plasma() with helium_treatment (`tardis_mc_get_helium`): relative_population (the populations
+        relative to the He II ground level before the electron density enters) and level_number_density (those of the pass whose
+        electron density was handed out), [helium levels, n_shells] each."""
+        want = (("relative_population", relative_population), ("level_number_density", level_number_density))
+        out = {name: np.empty((self.n_helium_levels, self.n_shells)) for name, on in want if on}
+        self._check(self._L.tardis_mc_get_helium(self._h, *(out[name].ctypes.data if on else None for name, on in want)), "get_helium")
+        return out
+
+    def last_helium_ms(self) -> dict:
+        """Device time (ms) of the relative-population kernel of the last update_plasma() with helium_treatment: {"relative_ms"}."""
+        a = C.c_double()
+        self._check(self._L.tardis_mc_last_helium_ms(self._h, C.byref(a)), "last_helium_ms")
+        return {"relative_ms": a.value}
 
     def set_nlte_data(self, nlte_data):
         """The NLTE species of update_plasma() (`tardis_mc_set_nlte_data`), after set_plasma_data(): an object with the fields of
@@ -539,6 +578,7 @@ class Engine:
         self.plasma_data = None
         self.nlte_data = None
         self.nlte_collision_data = None
+        self.ionization_options = None
         self.opacity_generation += 1
         self.results_generation += 1
         self.estimators_generation += 1

@@ -13,7 +13,7 @@ sampler, P uniforms for mu = sqrt(z).
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace as _dataclass_replace
 
 import numpy as np
 
@@ -392,6 +392,50 @@ def make_plasma_data(seed: int, line_data: LineData, n_shells: int, n_elements: 
         t_rad, w = 10000.0 - 150.0 * np.arange(S), 0.4 / (1.0 + 0.2 * np.arange(S))
     return PlasmaData(level_energy, level_g, level_meta, ion_level_edge, element_ion_edge, ion_charge, chi, zeta_t, zeta, number_density,
                       float(CHI_0_CA_II), 0.9, atomic_number, t_rad.copy(), w.copy())
+
+
+HELIUM_IONIZATION_EV = (24.587387, 54.417763)  # He I -> He II, He II -> He III, NIST ASD
+
+
+def make_helium_plasma_data(seed: int, line_data: LineData, n_shells: int, helium_levels=(19, 10), helium_abundance: float = 0.3,
+                            **kwargs) -> PlasmaData:
+    """make_plasma_data with helium in front: element 0 has atomic_number 2 and the three ions He I, He II, He III of
+    ``helium_levels[0]``, ``helium_levels[1]`` and one level on the first levels of ``line_data``; the remaining levels are dealt to
+    the other elements exactly as make_plasma_data(seed, ..., **kwargs) deals them.  He I has its ground level and two low metastable
+    levels (the 2s states, at 0.806 and 0.839 of the ionisation energy); every other excited level of He I and He II lies between 0.78
+    and 0.98 of its ion's ionisation energy, as helium's do.  Helium takes ``helium_abundance`` of every shell's number density, the
+    other elements share the rest in make_plasma_data's proportions.  What Engine.set_ionization_options("recomb-nlte") needs."""
+    n1, n2 = (int(n) for n in helium_levels)
+    if n1 < 3 or n2 < 1:
+        raise ValueError("He I needs at least three levels, He II one")
+    KH = n1 + n2 + 1
+    rest = make_plasma_data(seed, _dataclass_replace(line_data, n_levels=int(line_data.n_levels) - KH), n_shells, **kwargs)
+    rng = np.random.default_rng(seed + 611953)
+    chi = np.array(HELIUM_IONIZATION_EV + (0.0,)) * EV
+    counts = np.array([n1, n2, 1])
+    edge = np.concatenate(([0], np.cumsum(counts)))
+    energy, meta = np.zeros(KH), np.zeros(KH, dtype=np.int32)
+    for i in range(2):
+        a, b = edge[i], edge[i + 1]
+        energy[a + 1:b] = np.sort(0.78 * chi[i] + 0.2 * chi[i] * rng.random(b - a - 1))
+        meta[a] = 1
+    energy[1:3] = np.array([0.806, 0.839]) * chi[0]
+    energy[1:n1] = np.sort(energy[1:n1])
+    meta[1:3] = 1
+    meta[edge[2]] = 1
+    g = 2.0 * rng.integers(0, 6, KH) + 1.0
+    I_rest, NT = len(rest.ion_charge), len(rest.zeta_temperatures)
+    centre, width = rng.uniform(5000.0, 30000.0, 3), rng.uniform(4000.0, 15000.0, 3)
+    zeta = 0.05 + 0.9 / (1.0 + np.exp((rest.zeta_temperatures[None, :] - centre[:, None]) / width[:, None]))
+    total = rest.number_density.sum(axis=0)
+    number_density = np.concatenate(((helium_abundance * total)[None, :], (1.0 - helium_abundance) * rest.number_density))
+    assert zeta.shape == (3, NT) and I_rest == len(rest.ion_level_edge) - 1
+    return PlasmaData(np.concatenate((energy, rest.level_energy)), np.concatenate((g, rest.level_g)), np.concatenate((meta, rest.level_metastable)),
+                      np.concatenate((edge[:-1], rest.ion_level_edge + KH)).astype(np.int64),
+                      np.concatenate(([0], rest.element_ion_edge + 3)).astype(np.int64), np.concatenate(([0.0, 1.0, 2.0], rest.ion_charge)),
+                      np.concatenate((chi, rest.ionization_energy)), rest.zeta_temperatures, np.concatenate((zeta, rest.zeta)), number_density,
+                      rest.chi_0, rest.link_t_rad_t_electron, np.concatenate(([2], rest.atomic_number)).astype(np.int64),
+                      rest.t_radiative, rest.dilution_factor)
 
 
 # 4 pi^2 e^2 / (h m_e c), CODATA 2010 cgs: B_lu = EINSTEIN_COEFFICIENT f_lu / nu (the atomic data's lines preparation)

@@ -570,6 +570,7 @@ class MCTransportSolverHIP:
         self.plasma_data = None        # static plasma data of update_plasma() (set_plasma_data)
         self.nlte_data = None          # the NLTE species of update_plasma() (set_nlte_data)
         self.nlte_collision_data = None  # their collisional rates (set_nlte_collision_data)
+        self.ionization_options = None  # (helium_treatment, helium_element, delta_treatment) of update_plasma() (set_ionization_options)
 
     def set_line_data(self, line_data):
         """The atomic data update_opacity() computes the tables from (the fields of ``synthetic.LineData`` /
@@ -629,11 +630,22 @@ class MCTransportSolverHIP:
         the NLTE data, and again on a new engine.  update_plasma() takes no argument for them either."""
         self.nlte_collision_data = collision_data
 
+    def set_ionization_options(self, helium_treatment=None, helium_element=None, delta_treatment=None):
+        """The switches of update_plasma()'s nebular ionisation (``Engine.set_ionization_options``; what ``plasma.helium_treatment:
+        recomb-nlte`` and ``plasma.delta_treatment`` are to a configuration); all None for none.  They reach the engine as the plasma
+        data do.  update_plasma() takes no argument for them: like NLTE they are a property of what is installed."""
+        if helium_treatment is None and delta_treatment is None:
+            self.ionization_options = None
+        else:
+            self.ionization_options = (helium_treatment, helium_element, delta_treatment)
+
     def _install_nlte(self, eng):
         if eng.nlte_data is not self.nlte_data:
             eng.set_nlte_data(self.nlte_data)
         if self.nlte_data is not None and eng.nlte_collision_data is not self.nlte_collision_data:
             eng.set_nlte_collision_data(self.nlte_collision_data)
+        if eng.ionization_options != self.ionization_options:
+            eng.set_ionization_options(*(self.ionization_options or (None, None, None)))
 
     def update_plasma(self, t_radiative, dilution_factor, ionization="nebular", excitation="dilute-lte",
                       radiative_rates_type="dilute-blackbody", *, volume=None, w_epsilon=1e-10, time_of_simulation=None):

@@ -7,7 +7,10 @@ every ion on one lane, and at thresholds in between (option plasma_update_long_r
 Shapes: the configs[2] tables (5e5 lines, 5e4 levels, 20 shells) and the tardis_example shape (3e4 lines, 3e3 levels, 20 shells).
 One process per arm (the parent starts them one after the other and never opens the GPU itself); in it one warm-up call, then the
 median of --reps timed calls.  Prints one line per timed call and a JSON summary.
-Usage: python tools/time_plasma_update.py [--reps 5] [--shapes config2,tardis_example] [--thresholds 0,4,8,16,32,64,-2]"""
+--helium: the arms of profiles/helium_treatment.txt instead -- on plasma data with a helium element in front (He I 50 levels, He II 30,
+He III 1: synthetic.make_helium_plasma_data) update_plasma with no options installed ("plain") and with helium_treatment recomb-nlte
+("helium"), the stage times with last_helium_ms beside them; no thresholds, no host arm.
+Usage: python tools/time_plasma_update.py [--reps 5] [--shapes config2,tardis_example] [--thresholds 0,4,8,16,32,64,-2] [--helium]"""
 import argparse
 import json
 import os
@@ -30,6 +33,7 @@ SHAPES = {
 }
 STAGES = ("boltzmann_ms", "partition_ms", "ionization_ms", "population_ms", "line_ms", "block_ms", "derive_ms")
 ALL_LANE = 1 << 40  # no ion has that many levels: every ion takes the lane form
+HELIUM_LEVELS = (50, 30)  # He I, He II of the --helium arms (He III: one level)
 
 
 def median(ts):
@@ -44,7 +48,10 @@ def arm(name, which, reps, thresholds):
     prob = synthetic.make_problem(seed=1, n_packets=16, n_shells=20, line_interaction_type="macroatom", n_lines=kw["n_lines"],
                                   level_sizes=kw["level_sizes"])
     ld = synthetic.make_line_data(1, prob.opacity_state, level_sizes=kw["level_sizes"], time_explosion=prob.time_explosion)
-    pd = synthetic.make_plasma_data(1, ld, 20, n_elements=8, largest_ion=kw["largest_ion"])
+    if which in ("plain", "helium"):
+        pd = synthetic.make_helium_plasma_data(1, ld, 20, helium_levels=HELIUM_LEVELS, n_elements=8, largest_ion=kw["largest_ion"])
+    else:
+        pd = synthetic.make_plasma_data(1, ld, 20, n_elements=8, largest_ion=kw["largest_ion"])
     levels = np.diff(pd.ion_level_edge)
     out = {"lines": int(kw["n_lines"]), "levels": int(ld.n_levels), "ions": int(len(levels)), "longest_ion": int(levels.max()),
            "ions_ge_8_levels": int((levels >= 8).sum())}
@@ -54,12 +61,16 @@ def arm(name, which, reps, thresholds):
         eng.set_config(prob.montecarlo_configuration, prob.spectrum_frequency_grid)
         eng.set_line_data(ld)
         eng.set_plasma_data(pd)
+        if which == "helium":
+            eng.set_ionization_options("recomb-nlte")
+            out["helium_levels"] = int(eng.n_helium_levels)
 
         def device():
             t0 = time.perf_counter()
             eng.update_plasma(pd.t_radiative, pd.dilution_factor)
             wall = (time.perf_counter() - t0) * 1e3
-            return dict(wall_ms=wall, device_ms=eng.last_propagate_ms(), **eng.last_plasma_update_ms())
+            extra = dict(helium_relative_ms=eng.last_helium_ms()["relative_ms"]) if which == "helium" else {}
+            return dict(wall_ms=wall, device_ms=eng.last_propagate_ms(), **eng.last_plasma_update_ms(), **extra)
 
         def host():
             t0 = time.perf_counter()
@@ -71,7 +82,7 @@ def arm(name, which, reps, thresholds):
             return dict(wall_ms=(t2 - t0) * 1e3, host_solve_ms=(t1 - t0) * 1e3, update_opacity_wall_ms=(t2 - t1) * 1e3,
                         device_ms=eng.last_propagate_ms(), **eng.last_opacity_update_ms())
 
-        fn = device if which == "device" else host
+        fn = host if which == "host" else device
         times = []
         for r in range(reps + 1):  # (rep 0: warm-up)
             t = fn()
@@ -80,6 +91,9 @@ def arm(name, which, reps, thresholds):
             print(f"{name} {which:>6} rep {r}: " + "  ".join(f"{k} {v:9.3f}" for k, v in t.items()), flush=True)
         for k in times[0]:
             out[k] = median([t[k] for t in times])
+        if which in ("plain", "helium"):
+            out["iterations"] = eng.get_plasma(False, False, False, False)["iterations"]
+            out["ionization_ms_reps"] = [round(t["ionization_ms"], 4) for t in times]
         if which == "device":
             out["iterations"] = eng.get_plasma(False, False, False, False)["iterations"]
             part = {t: [] for t in thresholds}
@@ -99,14 +113,15 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="config2,tardis_example")
     ap.add_argument("--thresholds", default="0,4,8,16,32,64,-2")
-    ap.add_argument("--arm", choices=("device", "host"), help="run one arm in this process (the parent passes it)")
+    ap.add_argument("--helium", action="store_true", help="the arms 'plain' and 'helium' on plasma data with a helium element")
+    ap.add_argument("--arm", choices=("device", "host", "plain", "helium"), help="run one arm in this process (the parent passes it)")
     args = ap.parse_args()
     thresholds = [int(t) for t in args.thresholds.split(",")]
     if args.arm:
         print(json.dumps({name: arm(name, args.arm, args.reps, thresholds) for name in args.shapes.split(",")}))
         return
     out = {}
-    for which in ("host", "device"):
+    for which in (("plain", "helium") if args.helium else ("host", "device")):
         cmd = [sys.executable, os.path.abspath(__file__), "--arm", which, "--reps", str(args.reps), "--shapes", args.shapes, "--thresholds",
                args.thresholds]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, check=True)
