@@ -232,6 +232,10 @@ const char *tardis_mc_last_error(const TardisMcContext *ctx);   /* ctx may be NU
  * the chip and is written once, when the packet ends; 0: the record is written at every interaction, as the other variants do.  A problem of more
  * than 2^15 shells or 2^24 - 1 lines runs as with 0.  Results do not depend on it; tardis_mc_last_tracker_defer tells what a call ran with),
  * "tracker_pack_max_lines" (tests: problems of more lines than this run as with "tracker_defer" 0; 0, the default: only the real bound),
+ * "rng_complete" (variant 3 without v-packets: 1: once a packet is past the first 624 words of its MT19937 stream, the wave that holds it produces the
+ * rest of the generation the packet is in at the top of a pass, 64 words per round, and the packet's refills out of that generation read 32 bytes and
+ * store nothing, csrc/mt_generation.hpp; 0: every refill regenerates its 8 words itself.  1 is the default.  Results do not depend on it;
+ * the other kernels ignore it),
  * "log_tail_split" (1, the default: a call whose line-visit log fits one epoch is split where the drain of its longest-lived packets
  * begins -- "log_tail_packets" (8) packets' worth of traces per lane before the estimated end -- so that the estimator passes over
  * the bulk run beside the drain; 0 off), "log_chunk_records" (records per chunk of the log's pool, <= 4096 by default),

@@ -26,6 +26,7 @@
 #include "estimator_log.hpp"
 #include "walk_tables.hpp"
 #include "event_log.hpp"
+#include "mt_generation.hpp"
 
 namespace mc {
 
@@ -178,6 +179,7 @@ struct WaveCold {
     int log_continue;
     int log_gen;       // generation of the log's chunk pool (the host bumps it whenever it resets the pool): a chunk held from an earlier one is gone
     double *vq_jsave;  // [waves][2 * n_shells]: the waves' J / nu_bar partial sums between the launches of a volley-queue call
+    int rng_complete;  // lane sweeps without v-packets: 1 the wave finishes a packet's MT19937 generation at the top of a pass (option rng_complete); 0 never.  Wave-uniform, as trk_defer
 };
 
 __global__ void __launch_bounds__(64) late_list_kernel(const LaneSave *__restrict__ save, const WaveSave *__restrict__ wsave, int waves, long long first, long long end,
@@ -836,6 +838,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     //   4. the packet ends in a later pass (a boundary event: nothing in between writes the six) or in this one: the record is built and stored.
     // A suspension carries all six in LaneSave (walk_inv_new ... trk_energy), whichever of 1-4 the lane is in.
     constexpr bool DEFER = TRACK && LS && !VPK && !FT && !XWALK;
+    // RNGC: a packet past its first MT19937 generation has the rest of the generation it is in produced by the whole wave at the top of a pass
+    // (mt_generation.hpp) and carries bit 17 of r_gpos from there to the wrap: its refills are then one aligned 32-byte read, no second window, no store.
+    constexpr bool RNGC = LS && !VPK;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     WaveShared &sh = *reinterpret_cast<WaveShared *>(lds_raw);
     constexpr size_t SH_BYTES = LS ? WAVE_SHARED_LS_BYTES : sizeof(WaveShared);
@@ -929,6 +934,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
         if (!((need >> lane) & 1ull)) return;
         MC_G uint32_t *st = glob(seeded_states) + ((size_t)blockIdx.x * 64 + (size_t)lane) * WV_STATE_STRIDE;  // (one state buffer per lane of the grid)
         const int k0 = r_gpos & 0x3ff;
+        if constexpr (RNGC) {
+            if (r_gpos & 0x20000) {  // the generation is complete: st[k0 .. k0+7] are the words themselves -- one aligned 32-byte read, nothing to store
+                typedef unsigned v4u __attribute__((ext_vector_type(4)));
+                const v4u lo = *reinterpret_cast<const MC_G v4u *>(st + k0), hi = *reinterpret_cast<const MC_G v4u *>(st + k0 + 4);
+                const int tail = (r_head + r_cnt) & (RING - 1);
+                ring[tail * 64 + lane] = GroupRng<8>::to_double(lo.x, lo.y);
+                ring[((tail + 1) & (RING - 1)) * 64 + lane] = GroupRng<8>::to_double(lo.z, lo.w);
+                ring[((tail + 2) & (RING - 1)) * 64 + lane] = GroupRng<8>::to_double(hi.x, hi.y);
+                ring[((tail + 3) & (RING - 1)) * 64 + lane] = GroupRng<8>::to_double(hi.z, hi.w);
+                r_cnt += 4;
+                r_gpos = (k0 + 8 == MT_N) ? 0x10000 : r_gpos + 8;  // (the wrap clears bit 17: the next generation is not complete)
+                return;
+            }
+        }
         uint32_t wa[9], wc[8];
         // (the state words a block needs are contiguous -- mt[k0 .. k0+8] and mt[k0+397 .. k0+404] mod 624 -- except for the one
         // block whose second window straddles the end of the state: four 16-byte loads instead of seventeen 4-byte ones)
@@ -1115,6 +1134,18 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             v.trk_nu = sh.nu[lane]; v.trk_mu = sh.rcp_nu[lane]; v.trk_energy = sh.comov_nu[lane];
             suspended = true;
             break;
+        }
+        if constexpr (RNGC) {
+            // packets past their first generation whose current one is not complete: the wave finishes it, one packet after the other, each
+            // 64 words per round with coalesced loads and stores (wave-uniform control flow; the loads of a packet do not wait for the stores of the one before)
+            const unsigned long long todo = W->rng_complete ? __ballot(state != WS_NEED_PACKET && state != WS_DONE && (r_gpos >> 16) == 1) : 0ull;
+            if (todo) {
+                // (inlined, straight-line: as a call it left the headline instantiation 17 instead of 7 spilled VGPRs -- everything live across a call must sit in the
+                // callee-saved half of the registers -- and no faster than before; a first inlined form with a branch per load and round: 263.  profiles/mt19937_generation_completion.txt)
+                mtg::mt_complete_generations_wave<WV_STATE_STRIDE>(glob(seeded_states) + (size_t)blockIdx.x * 64 * WV_STATE_STRIDE, todo, r_gpos & 0x3ff, lane);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the owner's refills read what other lanes of the wave have stored
+                if ((todo >> lane) & 1ull) r_gpos |= 0x20000;
+            }
         }
         // every live packet gets the draws of one pass: new direction, first macro-atom jump, next tau_event
         const bool ready = state == WS_SWEEP && !(LS && s_active);  // the prepared trace has been swept

@@ -291,6 +291,8 @@ struct TardisMcContext {
         // tracker_pack_max_lines (tests): a lower bound on the lines that fit, 0 = the real one.  last_tracker_defer: what the last call ran with, -1 = no tracker
         // or another kernel
         int tracker_defer = 1, last_tracker_defer = -1;
+        // rng_complete (lane sweeps without v-packets): the wave finishes a packet's MT19937 generation at the top of a pass, refills out of it only read
+        int rng_complete = 1;
         long long tracker_pack_max_lines = 0;
         int ls_min_active = 8, ls_max_steps = 1 << 30;  // lane sweeps: when to leave the sweep phase (propagate_wave.hpp)
         int drain_split = 0;          // wave kernel: split the drain of a call off into a launch of its own (WaveCold::drain_split); measured: -4 % at 1e7 packets, +1.3 % at 1e8 -> off
@@ -1732,6 +1734,7 @@ int fill_wave_cold(TardisMcContext *ctx, const WaveCall &E, int epoch, const mc:
     wc.vq_jsave = vq ? ctx->wv.vq_jsave.as<double>() : nullptr;
     wc.log_continue = vq ? 1 : 0;
     wc.log_gen = E.log_gen;
+    wc.rng_complete = ctx->wv.rng_complete;
     HIP_TRY(ctx, store_value(E.st, wc_dev, wc));
     return TARDIS_MC_OK;
 }
@@ -2391,6 +2394,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
         ctx->wv.walk_min_active = value >= -1 ? (int)std::min<long long>(value, 63) : 8;
     }
     else if (n == "tracker_defer") ctx->wv.tracker_defer = value ? 1 : 0;
+    else if (n == "rng_complete") ctx->wv.rng_complete = value ? 1 : 0;
     else if (n == "tracker_pack_max_lines") ctx->wv.tracker_pack_max_lines = std::max<long long>(0, value);
     else if (n == "group_size") ctx->group_size = (value == 4 || value == 8 || value == 16) ? (int)value : 0;
     else if (n == "pipeline_chunks") {}  // (round 1: chunks on two streams; a call of the wave kernel now runs as epochs -- accepted, ignored)
