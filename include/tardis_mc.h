@@ -236,6 +236,11 @@ const char *tardis_mc_last_error(const TardisMcContext *ctx);   /* ctx may be NU
  * rest of the generation the packet is in at the top of a pass, 64 words per round, and the packet's refills out of that generation read 32 bytes and
  * store nothing, csrc/mt_generation.hpp; 0: every refill regenerates its 8 words itself.  1 is the default.  Results do not depend on it;
  * the other kernels ignore it),
+ * "sweep_skip" (variant 3 without v-packets, the sixteen-wave lane sweeps on the interleaved table: a trace proves whole aligned blocks of 8 lines harmless on
+ * a coarse table of prefix sums of the optical depths, ten blocks per step, and sweeps line by line only from the block that may stop it,
+ * csrc/sweep_skip.hpp; -1, the default: automatic; 0 off; 1 on where the call allows it -- partial relativity, 32-bit table offsets, line scattering
+ * enabled, no negative or non-finite optical depth, not the shell-sorted log or the cross-check instantiations.  Results do not depend on it;
+ * tardis_mc_last_sweep_skip tells what a call ran with; debug flag 536870912 (tests) makes every skipped trace fall back to the line-by-line sweep),
  * "log_tail_split" (1, the default: a call whose line-visit log fits one epoch is split where the drain of its longest-lived packets
  * begins -- "log_tail_packets" (8) packets' worth of traces per lane before the estimated end -- so that the estimator passes over
  * the bulk run beside the drain; 0 off), "log_chunk_records" (records per chunk of the log's pool, <= 4096 by default),
@@ -316,6 +321,8 @@ int tardis_mc_last_counters(TardisMcContext *ctx, int64_t out_counters[TARDIS_MC
  * 1 group-per-packet, 2 wave-owner with group sweeps, 3 wave-owner with lane sweeps, 4 wave-owner with the volley queue;
  * -1 before the first call. */
 int tardis_mc_last_variant(TardisMcContext *ctx);
+/* Whether the lane sweeps of the last tardis_mc_propagate cleared whole blocks on the coarse table (option "sweep_skip"): 1 / 0; -1 without a context. */
+int tardis_mc_last_sweep_skip(TardisMcContext *ctx);
 /* Width of the table row offsets of the kernel the last tardis_mc_propagate ran (option "table_offsets"): 32 or 64; the lane-per-packet
  * kernel (variant 0) always reports 64; -1 before the first call. */
 int tardis_mc_last_table_offsets(TardisMcContext *ctx);

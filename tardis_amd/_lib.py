@@ -37,6 +37,7 @@ SYMBOLS = {
     "tardis_mc_last_estimator_ms": (_i, [_vp, C.POINTER(C.c_double)]),
     "tardis_mc_last_counters": (_i, [_vp, C.POINTER(C.c_int64)]),
     "tardis_mc_last_variant": (_i, [_vp]),
+    "tardis_mc_last_sweep_skip": (_i, [_vp]),
     "tardis_mc_last_table_offsets": (_i, [_vp]),
     "tardis_mc_last_compactions": (_i, [_vp]),
     "tardis_mc_last_tracker_defer": (_i, [_vp]),

@@ -15,6 +15,7 @@ constexpr int DBG_WALK_LANE_FP64 = 128;          // macro-atom jumps of the wave
 constexpr int DBG_WALK_GROUP_FP64 = 8192;        // ... the cooperative group scan of the fp64 running sums / the fp64 search (cross-check)
 constexpr int DBG_LONG_INSTANTIATIONS = 1048576; // the long (cross-check) instantiations of the wave kernel, for A/B
 constexpr int DBG_NO_SCREENING = 33554432;       // no v-packet screening whatever the option says
+constexpr int DBG_SKIP_FALLBACK = 536870912;     // block skip of the lane sweeps: every interval-mode decision counts as ambiguous, i.e. every skipped trace falls back (tests)
 // the bits that read the wave kernel's profiling / test counters or ablation switches (mc::WV_DBG_FLAGS, propagate_wave.hpp: the host file asserts that the two are equal)
 constexpr int DBG_WAVE_COUNTERS = 1 | 2 | 4 | 16 | 32 | 16384 | 32768 | 65536 | 131072 | 524288 | 2097152 | 4194304 | 8388608 | 16777216 | 134217728 | 268435456;
 constexpr int DBG_FP64_WALKS = DBG_WALK_LANE_FP64 | DBG_WALK_GROUP_FP64;  // the compact walk tables are not used
@@ -154,6 +155,23 @@ inline Plan plan_propagate(const PlanInput &in)
     p.last_variant = cooperative ? ((variant == 3 && in.enable_full_relativity) ? 2 : variant) : 0;
     if (!cooperative) p.screen_on = false;  // (the lane kernel traces line by line)
     return p;
+}
+
+// ---- the block skip of the lane sweeps (sweep_skip.hpp): whether a call's sweeps clear whole 8-line blocks on the coarse table.  Decided once the wave
+// kernel's instantiation is known: the code is compiled into ONE of them, and its proof needs what the interleaved table's lean proof needs, plus line
+// scattering (a trace without it never stops on a line: nothing to gain, and lane_exact_line's code 3 is what the interval check is about).
+struct SkipInput {
+    int sweep_skip;            // the option: -1 automatic, 0 off, 1 on where allowed
+    bool lane_sweep, vpk, full_relativity, wide, cross_check, shell_log, full_tracking;
+    int waves_per_simd, nt;    // the instantiation: waves per SIMD it is compiled for; 0 separate tables, 1 interleaved, 2 aligned runs
+    bool line_scattering;
+    bool nt_negative, pfx_negative;  // a negative or non-finite optical depth, seen by the interleaved table's / the prefix sums' builder
+};
+inline bool plan_sweep_skip(const SkipInput &in)
+{
+    if (in.sweep_skip == 0) return false;
+    return in.lane_sweep && !in.vpk && !in.full_relativity && !in.wide && !in.cross_check && !in.shell_log && !in.full_tracking && in.waves_per_simd == 4 &&
+           in.nt == 1 && in.line_scattering && !in.nt_negative && !in.pfx_negative;
 }
 
 }  // namespace plan

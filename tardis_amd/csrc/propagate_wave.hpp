@@ -27,6 +27,7 @@
 #include "walk_tables.hpp"
 #include "event_log.hpp"
 #include "mt_generation.hpp"
+#include "sweep_skip.hpp"
 
 namespace mc {
 
@@ -180,6 +181,12 @@ struct WaveCold {
     int log_gen;       // generation of the log's chunk pool (the host bumps it whenever it resets the pool): a chunk held from an earlier one is gone
     double *vq_jsave;  // [waves][2 * n_shells]: the waves' J / nu_bar partial sums between the launches of a volley-queue call
     int rng_complete;  // lane sweeps without v-packets: 1 the wave finishes a packet's MT19937 generation at the top of a pass (option rng_complete); 0 never.  Wave-uniform, as trk_defer
+    // block skip of the sixteen-wave lane sweep (sweep_skip.hpp; option sweep_skip): 0 off, 1 on, 2 on with every interval-mode decision treated as ambiguous (tests).
+    // The coarse table and the {frequency, prefix sum} table lie behind the interleaved table in its allocation: sk_ct_off, sk_pn_off in 16-byte entries from H.tau_t.
+    // Wave-uniform, as rng_complete
+    int sweep_skip;
+    unsigned sk_ct_off, sk_pn_off;
+    double sk_margin;
 };
 
 __global__ void __launch_bounds__(64) late_list_kernel(const LaneSave *__restrict__ save, const WaveSave *__restrict__ wsave, int waves, long long first, long long end,
@@ -410,6 +417,9 @@ constexpr int LS_CHUNK = 8;  // lines per lane and step (the line list and the t
 // of 10 spilled VGPRs), a 36-line trace is 4.1 instead of 5 dependent steps: propagation launches -2.4 % on configs[2] heavy (2 748 / 2 684 -> 2 652 / 2 651 ms per 1e8
 // packets), nothing either way on the uniform levels, the 1.25e7-packet call and configs[1]; twelve (29 spilled VGPRs): +3 ... +7 % (profiles/r06_lines_per_step.txt)
 constexpr int LS_CHUNK_NT = TMC_LS_CHUNK_NT;
+#ifndef TMC_SWEEP_SKIP
+#define TMC_SWEEP_SKIP 1  // (experiment switch: 0 compiles the block skip of sweep_skip.hpp out of the sixteen-wave instantiation)
+#endif
 
 // Running sums of the transition probabilities, block by block (macro_atom.py:87-97: `probability += transition_probabilities[i, shell]`
 // from block_start): one thread per (block, shell) repeats the reference's additions once per opacity state, so that a
@@ -841,6 +851,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     // RNGC: a packet past its first MT19937 generation has the rest of the generation it is in produced by the whole wave at the top of a pass
     // (mt_generation.hpp) and carries bit 17 of r_gpos from there to the wrap: its refills are then one aligned 32-byte read, no second window, no store.
     constexpr bool RNGC = LS && !VPK;
+    // SKIP: the sweep may clear whole 8-line blocks on the coarse table (sweep_skip.hpp) where W->sweep_skip says so: the sixteen-wave instantiation on the
+    // interleaved table only.  The mode of a trace is two bits of pflags (ssk::MODE_COARSE: the next step is a coarse one; ssk::MODE_INTERVAL: s_tau is an upper bound)
+    constexpr bool SKIP = TMC_SWEEP_SKIP != 0 && LS && !VPK && NT == 1 && WPE == 4 && !WIDE && !SL && !XWALK && !FULL && !FT && TMC_STRAIGHT_A == 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     WaveShared &sh = *reinterpret_cast<WaveShared *>(lds_raw);
     constexpr size_t SH_BYTES = LS ? WAVE_SHARED_LS_BYTES : sizeof(WaveShared);
@@ -1132,6 +1145,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             v.vseq = vseq; v.pred_bits = pred_bits; v.vdone = vq_done; v.pad_v0 = v.pad_v1 = v.pad_v2 = 0;
             v.walk_inv_new = sh.chi[lane]; v.walk_block = sh.rcp_chi[lane]; v.walk_event = sh.tau_event[lane]; v.pad_w = 0.0;
             v.trk_nu = sh.nu[lane]; v.trk_mu = sh.rcp_nu[lane]; v.trk_energy = sh.comov_nu[lane];
+            if constexpr (SKIP) {  // a trace in coarse or interval mode is stored as its start: it takes the same path again (sweep_skip.hpp)
+                if (s_active && (pflags & (ssk::MODE_COARSE | ssk::MODE_INTERVAL))) {
+                    v.s_line = p.next_line_id; v.s_tau = 0.0; v.pflags = (pflags & ~ssk::MODE_INTERVAL) | ssk::MODE_COARSE;
+                }
+            }
             suspended = true;
             break;
         }
@@ -2052,6 +2070,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     s_xb = ((d_boundary * p.nu) * P.rcp_tc) * (1.0 - 0x1p-40);
                     s_fast = fast && mid_range(s_kp);
                     s_active = true;
+                    if constexpr (SKIP) {
+                        if (W->sweep_skip && s_fast) pflags |= ssk::MODE_COARSE;
+                    }
                 } else {
                     sh.nu[lane] = p.nu; sh.rcp_nu[lane] = 1.0 / p.nu; sh.comov_nu[lane] = comov_nu;
                     sh.chi[lane] = chi_e; sh.rcp_chi[lane] = 1.0 / chi_e;
@@ -2095,7 +2116,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     const unsigned nt_at = s_row + (unsigned)s_line;
                     const nt2 *__restrict__ pq = reinterpret_cast<const nt2 *>(H.tau_t) + (NT == 2 ? (nt_at & ~7u) : nt_at);
                     const int k0 = NT == 2 ? (int)(nt_at & 7u) : 0;  // entries of the aligned run in front of the current line
-                    if constexpr (NT != 0) {
+                    if constexpr (SKIP) {
+                        // a lane in coarse mode: its ten loads are nine coarse entries from the block of s_line on and the {frequency, prefix sum} entry of the line
+                        // the trace started at -- same registers, same round trip as the fine lanes' ten lines
+                        unsigned at = nt_at, last = nt_at + (unsigned)(CH - 1);
+                        if (pflags & ssk::MODE_COARSE) {
+                            last = W->sk_pn_off + (unsigned)p.shell * (unsigned)(L + 1) + (unsigned)p.next_line_id;
+                            at = W->sk_ct_off + (nt_at >> 3);  // (rows are multiples of 8 entries)
+                        }
+                        const nt2 *__restrict__ pc = reinterpret_cast<const nt2 *>(H.tau_t) + at;
+#pragma unroll
+                        for (int k = 0; k < CH - 1; ++k) { const nt2 e = pc[k]; nl[k] = e.x; tl[k] = e.y; }
+                        const nt2 e = reinterpret_cast<const nt2 *>(H.tau_t)[last];
+                        nl[CH - 1] = e.x; tl[CH - 1] = e.y;
+                    } else if constexpr (NT != 0) {
 #pragma unroll
                         for (int k = 0; k < CH; ++k) { const nt2 e = pq[k]; nl[k] = e.x; tl[k] = e.y; }
                     } else {
@@ -2115,6 +2149,19 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     const int n_fast = L - 1 - s_line;  // lines of the chunk before the last line of the list
                     bool alive;
                     double f_nu, f_tau;
+                    if (SKIP && (pflags & ssk::MODE_COARSE)) {
+                        if constexpr (SKIP) {
+                            double hi;
+                            const int c = ssk::coarse_scan(nl, tl, comov, s_kp, s_xb, s_tau_event, W->sk_margin, hi);
+                            const int b = s_line >> 3;
+                            if (c == ssk::STEP) s_line = (b + ssk::ADVANCE) << 3;
+                            else if (c > 0) { s_line = (b + c) << 3; s_tau = hi; pflags ^= ssk::MODE_COARSE | ssk::MODE_INTERVAL; }
+                            else {  // the block the trace starts in: fine steps with the exact sum; (never in a later step: its first block was cleared by the one before)
+                                s_line = p.next_line_id; s_tau = 0.0; pflags &= ~ssk::MODE_COARSE;
+                            }
+                        }
+                        alive = true; f_nu = 0.0; f_tau = 0.0;
+                    } else
                     if constexpr ((WPE == 3 && !VPK) || (TMC_STRAIGHT_A != 0 && WPE == 4 && NT == 1)) {
                         // Straight-line form (the twelve-line instantiation only): the reference's serial sums of the chunk first (t[k] = optical
                         // depth in front of line k), then the four bounds of every line -- independent of each other, no exec masking, no branch
@@ -2205,6 +2252,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         double dist;
                         if (line < L) {
                             code = lane_exact_line(H, line, f_nu, f_tau, s_tau, p.nu, comov, chi, s_tau_event, d_bound, dist);
+                            if constexpr (SKIP) {
+                                // (fall back, sweep_skip.hpp: the trace again from its start, line by line -- through the "go on" path below, which adds f_tau and one line)
+                                if ((pflags & ssk::MODE_INTERVAL) && code &&
+                                    !ssk::interval_take(code, s_tau, W->sweep_skip == 2 ? __builtin_inf() : ssk::GAP_FACTOR * W->sk_margin, f_tau, chi, dist, s_tau_event)) {
+                                    code = 0; f_tau = 0.0; s_tau = 0.0; adv = p.next_line_id - s_line - 1; pflags &= ~ssk::MODE_INTERVAL;
+                                }
+                            }
                             if (!code) { s_tau = s_tau + f_tau; ++adv; }
                         } else {
                             // for-else (lines 157-172): the line list is exhausted; next_line_id is left untouched (bit 3)
@@ -2212,6 +2266,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                             const bool cont = d_cont < d_bound;
                             dist = cont ? d_cont : d_bound;
                             code = (cont ? 2 : 1) | 8;
+                            if constexpr (SKIP) {
+                                if ((pflags & ssk::MODE_INTERVAL) && cont) { code = 0; s_tau = 0.0; adv = p.next_line_id - s_line; pflags &= ~ssk::MODE_INTERVAL; }
+                            }
                         }
                         if (code) {
                             sh.d_boundary[lane] = dist; sh.res_info[lane] = code; sh.res_line[lane] = (code & 8) ? 0 : line;

@@ -33,6 +33,7 @@
 #include "formal_interpolate.hpp"
 #include "source_function.hpp"
 #include "tau_prefix.hpp"
+#include "sweep_skip.hpp"
 #include "propagate_plan.hpp"
 #include "packet_decomposition.hpp"
 #include "decomposition_plan.hpp"
@@ -234,7 +235,17 @@ struct TardisMcContext {
         DevBuf nt_t;
         bool nt_valid = false, nt_negative = false;  // (nt_negative: the table holds a negative / NaN optical depth -- the lean proof of the NT kernels does not apply)
         unsigned nt_stride = 0;
-        void release() { release_buffers(nt_t); }
+        // Block skip of the sixteen-wave lane sweep (sweep_skip.hpp).  Option sweep_skip: -1 automatic, 0 off, 1 on where the plan allows it (plan::plan_sweep_skip).
+        // Its tables lie behind the interleaved table in nt_t's allocation (the kernel reads all three from one base with 32-bit offsets): the coarse entries
+        // ct[shell][block] = {nu_last, p_end}, rows of nt_stride / 8, 16 entries of slack; then pn[shell][0 .. L] = {frequency slot, prefix sum (tau_prefix_kernel)}.  Built by
+        // the first propagate call after set_opacity that may use them (sk_valid falls with nt_valid); sk_negative: tau_prefix_kernel's flag; sk_margin: ssk::margin
+        // of the largest row sum.  last_sweep_skip: what the last propagate call ran with (tardis_mc_last_sweep_skip)
+        int sweep_skip = -1, last_sweep_skip = 0;
+        bool sk_valid = false, sk_negative = false;
+        unsigned sk_ct_off = 0, sk_pn_off = 0;
+        double sk_margin = 0.0;
+        DevBuf sk_rowsum;
+        void release() { release_buffers(nt_t, sk_rowsum); }
     } sw;
     struct Estimators {
         // estimators: one allocation [J | nubar | vhist | pad | jblue copy0 | edot copy0 | jblue copy1.. | edot copy1..]
@@ -559,6 +570,27 @@ __global__ void __launch_bounds__(256) interleave_kernel(const double *__restric
         nt[i] = make_double2((in && l < L - 1) ? nu_line[l] : -__builtin_inf(), tau);
     }
     if (neg) atomicOr(negative, 1);
+}
+
+// The block-skip tables (sweep_skip.hpp) from the interleaved table and the prefix sums, which tau_prefix_kernel has left in the second halves of pn:
+// pn[s * (L + 1) + l] = {frequency slot of line l (-inf from L - 1 on), pfx[s][l]}, l = 0 .. L;
+// ct[s * (stride / 8) + b] = {frequency slot of the last entry of block b, pfx[s][min(8 b + 8, L)]}; the slack behind the last row: {-inf, the last prefix sum}
+__global__ void __launch_bounds__(256) coarse_table_kernel(const double2 *__restrict__ nt, double2 *__restrict__ pn, double2 *__restrict__ ct, long long L,
+                                                           long long S, long long stride, long long total)
+{
+    const long long rows = stride / 8;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long s = i / rows, b = i - s * rows;
+        if (s < S) {
+            const long long e = 8 * b + 8 < L ? 8 * b + 8 : L;
+            ct[i] = make_double2(nt[s * stride + 8 * b + 7].x, pn[s * (L + 1) + e].y);
+        } else
+            ct[i] = make_double2(-__builtin_inf(), pn[(S - 1) * (L + 1) + L].y);
+    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < S * (L + 1); i += (long long)gridDim.x * blockDim.x) {
+        const long long s = i / (L + 1), l = i - s * (L + 1);
+        pn[i].x = l < L - 1 ? nt[s * stride + l].x : -__builtin_inf();
+    }
 }
 
 // Stores a launch-argument block into device memory.  The value travels in the kernel's argument buffer, which the runtime
@@ -949,6 +981,7 @@ void drop_products(TardisMcContext *ctx, Cause cause)
         ctx->wt.have_walk_tables = ctx->wt.have_hot = false;
         ctx->sc.pfx_valid = false;  // (the prefix sums of the new tau table are built by the first propagate call that traces v-packets)
         ctx->sw.nt_valid = false;   // (likewise the interleaved sweep table: by the first call that sweeps on it)
+        ctx->sw.sk_valid = false;   // (... and the block-skip tables behind it)
         break;
     case CONFIG_REPLACED: ctx->vl.vl_valid = ctx->vl.vl_consolidated = false; break;  // (the consolidated v-packet log belongs to the configuration it was written under)
     case PACKETS_REPLACED:
@@ -1307,14 +1340,23 @@ int build_screening_tables(TardisMcContext *ctx)
     return TARDIS_MC_OK;
 }
 
+// bytes of the block-skip tables (sweep_skip.hpp) behind the interleaved table: coarse entries with their slack, {frequency, prefix sum} entries
+size_t skip_table_bytes(const TardisMcContext *ctx)
+{
+    const size_t stride = ((size_t)ctx->n_lines + 7) & ~(size_t)7;
+    return ((stride / 8) * (size_t)ctx->n_shells + 16) * 16 + ((size_t)ctx->n_shells * ((size_t)ctx->n_lines + 1) + 1) * 16;
+}
+
 // the interleaved sweep table (option sweep_table): built by the first propagate call after set_opacity that uses it; like the screening tables a launch and a
 // read-back (nt_negative: the lean proof of the NT kernels does not apply).  Tables whose padded rows reach 2^28 entries have none.
-int build_sweep_table(TardisMcContext *ctx)
+// (`skip_room`: with room for the block-skip tables behind it -- the caller's plan says the call may use them)
+int build_sweep_table(TardisMcContext *ctx, bool skip_room)
 {
     const unsigned long long stride = ((unsigned long long)ctx->n_lines + 7ull) & ~7ull;
     if (ctx->sw.nt_valid || stride * (unsigned long long)ctx->n_shells + 32ull >= (1ull << 28)) return TARDIS_MC_OK;
     const long long total = (long long)(stride * (unsigned long long)ctx->n_shells) + 32;  // (+ the slack of a step's loads behind the last row)
-    HIP_TRY(ctx, ctx->sw.nt_t.ensure((size_t)total * 16));
+    HIP_TRY(ctx, ctx->sw.nt_t.ensure((size_t)total * 16 + (skip_room ? skip_table_bytes(ctx) : 0)));
+    ctx->sw.sk_valid = false;
     HIP_TRY(ctx, ctx->sc.pfx_flag.ensure(sizeof(int)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->sc.pfx_flag.p, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(interleave_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 65536)), dim3(256), 0, ctx->stream, ctx->ot.nu_line.as<double>(),
@@ -1327,6 +1369,47 @@ int build_sweep_table(TardisMcContext *ctx)
     ctx->sw.nt_negative = neg != 0;
     ctx->sw.nt_stride = (unsigned)stride;
     ctx->sw.nt_valid = true;
+    return TARDIS_MC_OK;
+}
+
+// the block-skip tables (sweep_skip.hpp): built behind a valid interleaved table by the first propagate call that may use them; two launches and a read-back of
+// the row sums and the negative-depth flag
+int build_skip_tables(TardisMcContext *ctx)
+{
+    if (ctx->sw.sk_valid || !ctx->sw.nt_valid) return TARDIS_MC_OK;
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines, stride = ctx->sw.nt_stride;
+    const size_t nt_total = stride * S + 32, ct_rows = stride / 8, ct_total = ct_rows * S + 16;
+    if (ctx->sw.nt_t.cap < nt_total * 16 + skip_table_bytes(ctx)) {  // (the table was built by a call that could not use them: again, with room)
+        ctx->sw.nt_valid = false;
+        int rc = build_sweep_table(ctx, true);
+        if (rc) return rc;
+        if (!ctx->sw.nt_valid) return TARDIS_MC_OK;
+    }
+    double2 *nt = ctx->sw.nt_t.as<double2>();
+    double2 *ct = nt + nt_total;
+    double2 *pn = ct + ct_total;
+    HIP_TRY(ctx, ctx->sw.sk_rowsum.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, ctx->sc.pfx_flag.ensure(sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->sc.pfx_flag.p, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(mc::tau_prefix_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, ctx->ot.tau_t.as<double>(), (int)L, reinterpret_cast<double *>(pn),
+                       ctx->sw.sk_rowsum.as<double>(), ctx->sc.pfx_flag.as<int>(), 2, 1);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(coarse_table_kernel, dim3((unsigned)std::min<size_t>((S * (L + 1) + 255) / 256, 65536)), dim3(256), 0, ctx->stream, (const double2 *)nt,
+                       pn, ct, (long long)L, (long long)S, (long long)stride, (long long)ct_total);
+    HIP_TRY(ctx, hipGetLastError());
+    int neg = 0;
+    std::vector<double> rowsum(S);
+    HIP_TRY(ctx, hipMemcpyAsync(&neg, ctx->sc.pfx_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rowsum.data(), ctx->sw.sk_rowsum.p, S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    double r_max = 0.0;
+    bool finite = true;
+    for (double r : rowsum) { finite = finite && r >= 0.0 && r < 1e300; if (r > r_max) r_max = r; }
+    ctx->sw.sk_negative = neg != 0 || !finite;
+    ctx->sw.sk_margin = ssk::margin((int)L, r_max);
+    ctx->sw.sk_ct_off = (unsigned)nt_total;
+    ctx->sw.sk_pn_off = (unsigned)(nt_total + ct_total);
+    ctx->sw.sk_valid = true;
     return TARDIS_MC_OK;
 }
 
@@ -1381,6 +1464,7 @@ struct WaveChoice {
     int waves_per_cu;      // what the LDS and option waves_per_simd allow (the instantiation's own bound comes on top: max_waves_per_cu)
     int max_waves_per_cu;
     bool compact_walk, ls3;
+    int sweep_skip;        // WaveCold::sweep_skip of the call's launches (plan::plan_sweep_skip)
     int tiles, n_bins;     // tiles of EST_TILE lines per shell, (shell, tile) bins of the line-visit log
     bool partition;        // est_pipeline 1 (estimator_partition.hpp): the records are grouped by shell, then by bin
 };
@@ -1423,7 +1507,11 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
         if (rc) return rc;
         if (w.ls3) k.waves_per_simd = 3;
         if (!w64 && ctx->sw.sweep_table != 0) {
-            rc = build_sweep_table(ctx);
+            // (room for the block-skip tables only where this call may end up using them: what is known of its instantiation so far, the rest assumed in favour)
+            plan::SkipInput room{};
+            room.sweep_skip = ctx->sw.sweep_skip; room.lane_sweep = true; room.full_relativity = full; room.full_tracking = ctx->el.track_full;
+            room.waves_per_simd = k.waves_per_simd; room.nt = (ctx->sw.sweep_table == 2 && !w.ls3) ? 2 : 1; room.line_scattering = !c.disable_line_scattering;
+            rc = build_sweep_table(ctx, plan::plan_sweep_skip(room));
             if (rc) return rc;
             if (ctx->sw.nt_valid && !ctx->sw.nt_negative) {
                 k.nt = (ctx->sw.sweep_table == 2 && !w.ls3) ? 2 : 1;
@@ -1439,6 +1527,23 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
     // the shell-sorted log: instantiated for the two production lane-sweep kernels (sixteen waves on the interleaved table, twelve on the separate ones)
     k.shell_log = k.lane_sweep && !vpk && !k.xwalk && !w64 && !vq && w.partition && ctx->wv.log_by_shell != 0 && ctx->n_shells <= 64 &&
                   ((!w.ls3 && k.nt == 1) || (w.ls3 && k.nt == 0));
+    // the block skip of the lane sweeps (sweep_skip.hpp): where the plan allows it; its tables are built here, and a negative optical depth in them plans again
+    w.sweep_skip = 0;
+    if (TMC_SWEEP_SKIP != 0) {  // (a build without the kernel's code reports off)
+        plan::SkipInput si{};
+        si.sweep_skip = ctx->sw.sweep_skip; si.lane_sweep = k.lane_sweep; si.vpk = vpk; si.full_relativity = full; si.wide = w64; si.cross_check = k.xwalk;
+        si.shell_log = k.shell_log; si.full_tracking = ctx->el.track_full; si.waves_per_simd = k.waves_per_simd; si.nt = k.nt;
+        si.line_scattering = !c.disable_line_scattering; si.nt_negative = ctx->sw.nt_negative; si.pfx_negative = false;
+        if (plan::plan_sweep_skip(si)) {
+            int rc = build_skip_tables(ctx);
+            if (rc) return rc;
+            // (a table built without room for them has been built again in a larger allocation: the address taken above is gone)
+            P.nt_t = ctx->sw.nt_t.as<double>(); P.nt_stride = ctx->sw.nt_stride;
+            si.pfx_negative = !ctx->sw.sk_valid || ctx->sw.sk_negative;
+            if (plan::plan_sweep_skip(si)) w.sweep_skip = (ctx->debug_flags & plan::DBG_SKIP_FALLBACK) ? 2 : 1;
+        }
+        ctx->sw.last_sweep_skip = w.sweep_skip ? 1 : 0;
+    }
     if (ctx->el.track_full) {  // the tracked instantiations: group sweeps of 16 lanes, compact walks, default register budget
         k.full_tracking = true; k.track = true; k.width = 16;
     }
@@ -1593,6 +1698,7 @@ struct WaveCall {
     const LogSizing *log;
     mc::GroupArgs P;
     mc::WaveHot hot;
+    int sweep_skip = 0; // the call's lane sweeps clear whole blocks on the coarse table (WaveCold::sweep_skip: 1, or 2 under debug flag 536870912)
     int trk_defer = 0;  // the call keeps the tracker record in LDS and stores it once per packet (WaveCold::trk_defer)
     long long n;
     int waves;
@@ -1735,6 +1841,7 @@ int fill_wave_cold(TardisMcContext *ctx, const WaveCall &E, int epoch, const mc:
     wc.log_continue = vq ? 1 : 0;
     wc.log_gen = E.log_gen;
     wc.rng_complete = ctx->wv.rng_complete;
+    wc.sweep_skip = E.sweep_skip; wc.sk_ct_off = ctx->sw.sk_ct_off; wc.sk_pn_off = ctx->sw.sk_pn_off; wc.sk_margin = ctx->sw.sk_margin;
     HIP_TRY(ctx, store_value(E.st, wc_dev, wc));
     return TARDIS_MC_OK;
 }
@@ -2127,6 +2234,7 @@ int run_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P)
         const WaveKernelKey &k = w.key;
         const bool has_defer = k.track && k.lane_sweep && !k.vpk && !k.full_tracking && !k.xwalk;
         const bool fits = mc::tracker_pack_fits(P.n_shells, P.n_lines) && (ctx->wv.tracker_pack_max_lines <= 0 || P.n_lines <= ctx->wv.tracker_pack_max_lines);
+        E.sweep_skip = w.sweep_skip;
         E.trk_defer = (has_defer && ctx->wv.tracker_defer && fits) ? 1 : 0;  // (-> WaveCold::trk_defer of every launch of the call)
         ctx->wv.last_tracker_defer = has_defer ? E.trk_defer : -1;
     }
@@ -2395,6 +2503,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     }
     else if (n == "tracker_defer") ctx->wv.tracker_defer = value ? 1 : 0;
     else if (n == "rng_complete") ctx->wv.rng_complete = value ? 1 : 0;
+    else if (n == "sweep_skip") ctx->sw.sweep_skip = (int)std::max<long long>(-1, std::min<long long>(value, 1));
     else if (n == "tracker_pack_max_lines") ctx->wv.tracker_pack_max_lines = std::max<long long>(0, value);
     else if (n == "group_size") ctx->group_size = (value == 4 || value == 8 || value == 16) ? (int)value : 0;
     else if (n == "pipeline_chunks") {}  // (round 1: chunks on two streams; a call of the wave kernel now runs as epochs -- accepted, ignored)
@@ -3049,6 +3158,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     if (call.plan.error) return fail(ctx, call.plan.error, "%s", call.plan.message);
     ctx->last_table_offsets = call.plan.last_table_offsets;
     ctx->last_variant = call.plan.last_variant;
+    ctx->sw.last_sweep_skip = 0;  // (set by choose_wave_kernel where the call's lane sweeps skip)
     ctx->wv.last_tracker_defer = -1;  // (the wave kernel's runner says otherwise)
     ctx->last_kernel_table = -1;      // (the lookup of the call's kernel says otherwise)
     std::fill(std::begin(ctx->last_kernel_key), std::end(ctx->last_kernel_key), 0);
@@ -3187,6 +3297,7 @@ int tardis_mc_last_counters(TardisMcContext *ctx, int64_t out_counters[TARDIS_MC
 }
 
 int tardis_mc_last_variant(TardisMcContext *ctx) { return ctx ? ctx->last_variant : -1; }
+int tardis_mc_last_sweep_skip(TardisMcContext *ctx) { return ctx ? ctx->sw.last_sweep_skip : -1; }
 int tardis_mc_last_table_offsets(TardisMcContext *ctx) { return ctx ? ctx->last_table_offsets : -1; }
 int tardis_mc_last_compactions(TardisMcContext *ctx) { return ctx ? ctx->wv.compactions : -1; }
 int tardis_mc_last_tracker_defer(TardisMcContext *ctx) { return ctx ? ctx->wv.last_tracker_defer : -1; }

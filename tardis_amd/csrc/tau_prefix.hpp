@@ -41,13 +41,14 @@ __device__ __forceinline__ void dd_add_dd(DD &a, const DD &b)
 }
 
 // one 256-thread workgroup per shell: pfx[s][0..L] (row stride L + 1), rowsum[s] = pfx[s][L]; *negative |= any tau < 0 (or NaN)
+// (`step`, `offset`: entry i of the output lies at pfx[i * step + offset] -- the {frequency, prefix sum} table of sweep_skip.hpp takes them as its second halves)
 __global__ void __launch_bounds__(256) tau_prefix_kernel(const double *__restrict__ tau_t, int n_lines, double *__restrict__ pfx,
-                                                         double *__restrict__ rowsum, int *__restrict__ negative)
+                                                         double *__restrict__ rowsum, int *__restrict__ negative, int step = 1, int offset = 0)
 {
     __shared__ DD part[256];
     const int s = blockIdx.x, tid = threadIdx.x;
     const double *__restrict__ row = tau_t + (size_t)s * (size_t)n_lines;
-    double *__restrict__ out = pfx + (size_t)s * (size_t)(n_lines + 1);
+    double *__restrict__ out = pfx + (size_t)s * (size_t)(n_lines + 1) * (size_t)step + (size_t)offset;
     const int per = (n_lines + 255) / 256;
     const int i0 = min(tid * per, n_lines), i1 = min(i0 + per, n_lines);
     DD acc = {0.0, 0.0};
@@ -71,10 +72,10 @@ __global__ void __launch_bounds__(256) tau_prefix_kernel(const double *__restric
     __syncthreads();
     acc = part[tid];
     for (int i = i0; i < i1; ++i) {
-        out[i] = acc.hi + acc.lo;
+        out[(size_t)i * (size_t)step] = acc.hi + acc.lo;
         dd_add(acc, row[i]);
     }
-    if (i1 == n_lines && i0 < n_lines) out[n_lines] = acc.hi + acc.lo;
+    if (i1 == n_lines && i0 < n_lines) out[(size_t)n_lines * (size_t)step] = acc.hi + acc.lo;
     if (n_lines == 0 && tid == 0) out[0] = 0.0;
     if (neg) atomicOr(negative, 1);
 }

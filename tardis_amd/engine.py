@@ -457,6 +457,11 @@ class Engine:
         4 wave + volley queue (v-packets traced by vpacket_trace_kernel between its launches)."""
         return int(self._L.tardis_mc_last_variant(self._h))
 
+    def last_sweep_skip(self) -> int:
+        """Whether the lane sweeps of the last propagate() cleared whole 8-line blocks on the coarse prefix-sum table (option
+        ``sweep_skip``): 1 or 0."""
+        return int(self._L.tardis_mc_last_sweep_skip(self._h))
+
     def last_table_offsets(self) -> int:
         """Width of the table row offsets of the last propagate()'s kernel (option ``table_offsets``): 32 or 64 (variant 0
         always 64); -1 before the first call."""
