@@ -365,6 +365,28 @@ int tardis_mc_pcg64_seed(uint64_t seed, uint64_t out_state[4]);  /* SeedSequence
 int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, int64_t first, int64_t count, double radius,
                                        double temperature, const uint64_t pcg_state[4], uint32_t max_seed_val,
                                        const double *l_array, int64_t n_l);
+/* The source of a full-relativity run: BlackBodySimpleSourceRelativistic (packet_source/black_body.py), which the reference builds when
+ * montecarlo.enable_full_relativity is set because the inner boundary is not comoving with the ejecta.  Seeds, radii, nus and every
+ * RNG stream position are those of the simple source above; only the directions and the energies differ.  With c = 2.99792458e10 and
+ * n = n_total (the GLOBAL packet count, also for a shard), in this operation order, the squares written as products, nothing fused:
+ *   beta   = (radius / time_explosion) / c
+ *   gamma  = 1.0 / sqrt(1.0 - beta*beta)
+ *   factor = (2.0*beta + 1.0) / (1.0 - beta*beta)
+ *   energy = ((1.0 / n) * factor) / gamma                         every packet
+ *   z      = rng.random(n)                                        the stream position of the simple source's direction draw
+ *   mu     = (-beta) + sqrt(((beta*beta) + ((2.0*beta) * z)) + z) p(mu) = 2 (mu + beta) / (2 beta + 1) on [0, 1]; not clamped
+ * beta = 0 gives the simple source bit for bit.  packet_seeds, mus, energies and radii are bit-exact against NumPy; the nus are
+ * bit-identical to the simple source's of the same seed.
+ * tardis_mc_relativistic_source_factors computes beta and energy on the host (no context, no device) and is where the device entry
+ * point takes them from; it returns TARDIS_MC_ERR_INVALID_ARGUMENT when radius is not finite and non-negative, time_explosion is not
+ * finite and positive, n_total < 1, or the resulting beta is not in [0, 1).
+ * tardis_mc_create_blackbody_packets_relativistic has the contract of tardis_mc_create_blackbody_packets (shards, rejected seed draws,
+ * what it invalidates) plus those argument errors, each with a message that names the offending value, raised before anything
+ * resident is touched.  time_explosion is an argument, not what tardis_mc_set_geometry left: the call has no ordering dependency. */
+int tardis_mc_relativistic_source_factors(double radius, double time_explosion, int64_t n_total, double *out_beta, double *out_energy);
+int tardis_mc_create_blackbody_packets_relativistic(TardisMcContext *ctx, int64_t n_total, int64_t first, int64_t count, double radius,
+                                                    double temperature, double time_explosion, const uint64_t pcg_state[4],
+                                                    uint32_t max_seed_val, const double *l_array, int64_t n_l);
 /* download the resident packet inputs (any pointer may be NULL) */
 int tardis_mc_get_packets(TardisMcContext *ctx, double *initial_radii, double *initial_nus, double *initial_mus,
                           double *initial_energies, int64_t *packet_seeds);

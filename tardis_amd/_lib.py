@@ -48,6 +48,9 @@ SYMBOLS = {
     "tardis_mc_pcg64_seed": (_i, [C.c_uint64, C.POINTER(C.c_uint64)]),
     "tardis_mc_create_blackbody_packets": (_i, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                                 C.POINTER(C.c_uint64), C.c_uint32, _vp, C.c_int64]),
+    "tardis_mc_relativistic_source_factors": (_i, [C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "tardis_mc_create_blackbody_packets_relativistic": (_i, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double,
+                                                             C.POINTER(C.c_uint64), C.c_uint32, _vp, C.c_int64]),
     "tardis_mc_get_packets": (_i, [_vp] * 6),
     "tardis_mc_packet_spectrum": (_i, [_vp, C.c_double, C.c_double, C.c_double, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tardis_mc_packet_decomposition": (_i, [_vp, _vp]),

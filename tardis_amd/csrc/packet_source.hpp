@@ -8,6 +8,10 @@
 //   xis          = rng.random((5, n))                          -> u64 draws  q0 + k n + i   (row-major)
 //   mus          = sqrt(rng.random(n))                         -> u64 draws  q0 + 5 n + i
 //
+// and BlackBodySimpleSourceRelativistic (black_body.py), the source of a full-relativity run: the same streams at the same positions,
+// with  z = rng.random(n),  mus = -beta + sqrt(beta^2 + 2 beta z + z)  and every energy scaled by (2 beta + 1) / (1 - beta^2) / gamma
+// (beta and that energy are computed once on the host, tardis_mc_relativistic_source_factors).
+//
 // PCG64 (XSL-RR 128/64) is a 128-bit LCG, so any draw is reachable by jump-ahead: every thread jumps straight to its
 // packet's positions (jump tables of the 2^j-step affine maps are precomputed on the host), which makes the source
 // embarrassingly parallel and lets a rank generate only its shard [first, first + count) of a global n-packet draw.
@@ -39,6 +43,7 @@ struct PacketSourceArgs {
     const double *l_array;            // cumulative sum of k^-4, k = 1 .. l_samples-1
     int n_l;
     double l_coef, radius, kT, h, energy;
+    double beta;                      // relativistic form only: v_inner_boundary / c (tardis_mc_relativistic_source_factors)
     double *r0, *mu0, *nu0, *e0;
     uint32_t *seeds;
 };
@@ -97,7 +102,10 @@ __global__ void packet_source_scan_kernel(PacketSourceArgs a, long long n_positi
     }
 }
 
-// pass 2: one thread per packet
+// pass 2: one thread per packet.  RELATIVISTIC picks the direction law at compile time, so the simple form's code is the one it
+// always was: mu = sqrt(z), or the limb-shifted  mu = -beta + sqrt(beta^2 + 2 beta z + z)  with the reference's operation order
+// (black_body.py, BlackBodySimpleSourceRelativistic.create_packet_mus).  Everything else is shared: seeds, radii, nus, stream positions
+template <bool RELATIVISTIC>
 __global__ void packet_source_kernel(PacketSourceArgs a)
 {
     const u128 s0 = make128(a.state_hi, a.state_lo);
@@ -129,7 +137,10 @@ __global__ void packet_source_kernel(PacketSourceArgs a)
         const double l_min = (double)lo + 1.0;
         const double x = -mcm::log(prod) / l_min;
         a.nu0[j] = x * a.kT / a.h;
-        a.mu0[j] = sqrt(z);
+        if constexpr (RELATIVISTIC)  // no clamp: z = 0 gives 0, z = 1 - 2^-53 gives 1; beta = 0 is sqrt(z) bit for bit
+            a.mu0[j] = (-a.beta) + sqrt(((a.beta * a.beta) + ((2.0 * a.beta) * z)) + z);
+        else
+            a.mu0[j] = sqrt(z);
         a.r0[j] = a.radius;
         a.e0[j] = a.energy;
     }

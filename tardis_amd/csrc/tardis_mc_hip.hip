@@ -2961,14 +2961,57 @@ static int ensure_packet_buffers(TardisMcContext *ctx, size_t P)
     return TARDIS_MC_OK;
 }
 
-int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, int64_t first, int64_t count, double radius,
-                                       double temperature, const uint64_t pcg_state[4], uint32_t max_seed_val,
-                                       const double *l_array, int64_t n_l)
+// beta and the per-packet energy of BlackBodySimpleSourceRelativistic, in the reference's operation order (the build has
+// -ffp-contract=off: 1 - beta*beta stays a product and a difference).  An empty string, or what is wrong with the arguments.
+static std::string relativistic_source_factors(double radius, double time_explosion, int64_t n_total, double *out_beta, double *out_energy)
+{
+    char buf[160];
+    if (!std::isfinite(radius) || radius < 0.0) {
+        snprintf(buf, sizeof buf, "relativistic packet source: radius %g is not finite and non-negative", radius);
+        return buf;
+    }
+    if (!std::isfinite(time_explosion) || !(time_explosion > 0.0)) {
+        snprintf(buf, sizeof buf, "relativistic packet source: time_explosion %g is not finite and positive", time_explosion);
+        return buf;
+    }
+    if (n_total < 1) {
+        snprintf(buf, sizeof buf, "relativistic packet source: n_total %lld is less than 1", (long long)n_total);
+        return buf;
+    }
+    const double beta = (radius / time_explosion) / mc::C_LIGHT;
+    if (!(beta >= 0.0 && beta < 1.0)) {
+        snprintf(buf, sizeof buf, "relativistic packet source: beta = radius / time_explosion / c = %g is not in [0, 1)", beta);
+        return buf;
+    }
+    const double gamma = 1.0 / std::sqrt(1.0 - beta * beta);
+    const double factor = (2.0 * beta + 1.0) / (1.0 - beta * beta);
+    *out_beta = beta;
+    *out_energy = ((1.0 / (double)n_total) * factor) / gamma;
+    return std::string();
+}
+
+int tardis_mc_relativistic_source_factors(double radius, double time_explosion, int64_t n_total, double *out_beta, double *out_energy)
+{
+    if (!out_beta || !out_energy) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "relativistic packet source: an output pointer is missing");
+    const std::string err = relativistic_source_factors(radius, time_explosion, n_total, out_beta, out_energy);
+    if (!err.empty()) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+    return TARDIS_MC_OK;
+}
+
+// both forms of the source: `time_explosion` is read only by the relativistic one
+static int create_blackbody_packets(TardisMcContext *ctx, const bool relativistic, int64_t n_total, int64_t first, int64_t count, double radius,
+                                    double temperature, double time_explosion, const uint64_t pcg_state[4], uint32_t max_seed_val,
+                                    const double *l_array, int64_t n_l)
 {
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (n_total < 0 || first < 0 || count < 0 || first + count > n_total || !pcg_state || !l_array || n_l < 1 || n_l > (1 << 24) ||
         max_seed_val < 2 || (uint64_t)n_total >= (1ULL << 44))
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid packet source arguments");
+    double beta = 0.0, energy = n_total > 0 ? 1.0 / (double)n_total : 0.0;
+    if (relativistic) {
+        const std::string err = relativistic_source_factors(radius, time_explosion, n_total, &beta, &energy);
+        if (!err.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     drop_products(ctx, PACKETS_REPLACED);
     const size_t P = (size_t)count;
@@ -3006,7 +3049,8 @@ int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, in
     a.radius = radius;
     a.kT = 1.3806488e-16 * temperature;   // tardis/constants.py:1 (CODATA 2010, cgs)
     a.h = 6.62606957e-27;
-    a.energy = n_total > 0 ? 1.0 / (double)n_total : 0.0;
+    a.energy = energy;
+    a.beta = beta;
     a.r0 = ctx->pk.r0.as<double>(); a.mu0 = ctx->pk.mu0.as<double>(); a.nu0 = ctx->pk.nu0.as<double>(); a.e0 = ctx->pk.e0.as<double>();
     a.seeds = ctx->pk.seeds.as<uint32_t>();
 
@@ -3042,13 +3086,30 @@ int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, in
     a.xi_first_u64 = (consumed_u32 + 1) / 2;
     if (count > 0) {
         const int blocks = (int)std::min<long long>((count + 255) / 256, 16384);
-        hipLaunchKernelGGL(mc::packet_source_kernel, dim3(blocks), dim3(256), 0, ctx->stream, a);
+        if (relativistic)
+            hipLaunchKernelGGL(mc::packet_source_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, a);
+        else
+            hipLaunchKernelGGL(mc::packet_source_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, a);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->pk.n_packets = count;
     ctx->have_packets = true;
     return TARDIS_MC_OK;
+}
+
+int tardis_mc_create_blackbody_packets(TardisMcContext *ctx, int64_t n_total, int64_t first, int64_t count, double radius,
+                                       double temperature, const uint64_t pcg_state[4], uint32_t max_seed_val,
+                                       const double *l_array, int64_t n_l)
+{
+    return create_blackbody_packets(ctx, false, n_total, first, count, radius, temperature, 0.0, pcg_state, max_seed_val, l_array, n_l);
+}
+
+int tardis_mc_create_blackbody_packets_relativistic(TardisMcContext *ctx, int64_t n_total, int64_t first, int64_t count, double radius,
+                                                    double temperature, double time_explosion, const uint64_t pcg_state[4],
+                                                    uint32_t max_seed_val, const double *l_array, int64_t n_l)
+{
+    return create_blackbody_packets(ctx, true, n_total, first, count, radius, temperature, time_explosion, pcg_state, max_seed_val, l_array, n_l);
 }
 
 int tardis_mc_get_packets(TardisMcContext *ctx, double *initial_radii, double *initial_nus, double *initial_mus,

@@ -607,17 +607,23 @@ class Engine:
 
     def create_blackbody_packets(self, n_packets: int, radius: float, temperature: float, base_seed: int = 23111963,
                                  seed_offset: int = 0, *, first: int = 0, count: int | None = None,
-                                 max_seed_val: int = 2**32 - 1, l_samples: int = 1000) -> None:
+                                 max_seed_val: int = 2**32 - 1, l_samples: int = 1000, time_explosion: float | None = None) -> None:
         """BlackBodySimpleSource.create_packets on the device (packet_source/base.py:195-253): the packets
         np.random.default_rng(base_seed + seed_offset) would have produced, slice [first, first+count), left resident
-        as this engine's packet inputs."""
+        as this engine's packet inputs.  With a ``time_explosion`` it is BlackBodySimpleSourceRelativistic, the source of a
+        full-relativity run: beta = radius / time_explosion / c shifts the directions and scales the energies."""
         count = n_packets - first if count is None else count
         st = (C.c_uint64 * 4)()
         self._check(self._L.tardis_mc_pcg64_seed(int(base_seed + seed_offset), st), "pcg64_seed")
         l_array = np.cumsum(np.arange(1, l_samples, dtype=np.float64) ** -4)  # black_body.py:174
-        self._check(self._L.tardis_mc_create_blackbody_packets(self._h, int(n_packets), int(first), int(count), float(radius),
-                                                               float(temperature), st, int(max_seed_val),
-                                                               l_array.ctypes.data, len(l_array)), "create_blackbody_packets")
+        if time_explosion is None:
+            self._check(self._L.tardis_mc_create_blackbody_packets(self._h, int(n_packets), int(first), int(count), float(radius),
+                                                                   float(temperature), st, int(max_seed_val),
+                                                                   l_array.ctypes.data, len(l_array)), "create_blackbody_packets")
+        else:
+            self._check(self._L.tardis_mc_create_blackbody_packets_relativistic(
+                self._h, int(n_packets), int(first), int(count), float(radius), float(temperature), float(time_explosion), st,
+                int(max_seed_val), l_array.ctypes.data, len(l_array)), "create_blackbody_packets_relativistic")
         self.n_packets = int(count)
         self.packets_generation += 1
 

@@ -37,8 +37,14 @@ class Problem:
 
 
 def black_body_packets(n_packets: int, radius: float, temperature: float, base_seed: int = DEFAULT_BASE_SEED,
-                       seed_offset: int = 0, l_samples: int = 1000, legacy_random_state=None) -> st.PacketCollection:
+                       seed_offset: int = 0, l_samples: int = 1000, legacy_random_state=None,
+                       time_explosion: float | None = None) -> st.PacketCollection:
     """Sample a packet collection at the photosphere (see module docstring for the reference lines).
+
+    ``time_explosion``: None is BlackBodySimpleSource; a number is BlackBodySimpleSourceRelativistic (black_body.py), what the
+    reference builds under ``enable_full_relativity``: with beta = radius / time_explosion / c the directions follow
+    p(mu) = 2 (mu + beta) / (2 beta + 1), mu = -beta + sqrt(beta^2 + 2 beta z + z), and every energy carries
+    (2 beta + 1) / (1 - beta^2) / gamma.  Seeds, radii, nus and stream positions are the simple source's.
 
     ``legacy_random_state``: the reference's ``legacy_mode_enabled`` source (what its own integration test runs,
     tests/test_montecarlo_main_loop.py:14-60) draws the five Planck uniforms and the direction uniforms from NumPy's GLOBAL
@@ -56,8 +62,20 @@ def black_body_packets(n_packets: int, radius: float, temperature: float, base_s
     l_min = l_array.searchsorted(xis[0] * l_coef) + 1.0
     x = -np.log(np.prod(xis[1:], 0)) / l_min
     nus = x * (st.K_BOLTZMANN * temperature) / st.H_PLANCK
-    mus = np.sqrt(draws(n_packets))
-    energies = np.ones(n_packets) / n_packets
+    if time_explosion is None:
+        mus = np.sqrt(draws(n_packets))
+        energies = np.ones(n_packets) / n_packets
+    else:  # squares as products and this parenthesisation: the device source restates it operation for operation
+        r, t = float(radius), float(time_explosion)
+        if not (np.isfinite(r) and r >= 0.0 and np.isfinite(t) and t > 0.0):
+            raise ValueError(f"relativistic source: radius {r!r} must be finite and >= 0, time_explosion {t!r} finite and > 0")
+        beta = (r / t) / st.C_SPEED_OF_LIGHT
+        if not 0.0 <= beta < 1.0:
+            raise ValueError(f"relativistic source: beta = radius / time_explosion / c = {beta!r} is not in [0, 1)")
+        gamma = 1.0 / np.sqrt(1.0 - beta * beta)
+        z = draws(n_packets)
+        mus = (-beta) + np.sqrt(((beta * beta) + ((2.0 * beta) * z)) + z)
+        energies = ((np.ones(n_packets) / n_packets) * ((2.0 * beta + 1.0) / (1.0 - beta * beta))) / gamma
     luminosity = 4 * np.pi * st.SIGMA_SB * radius**2 * temperature**4
     return st.PacketCollection(radii, nus, mus, energies, packet_seeds, luminosity)
 

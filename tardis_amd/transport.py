@@ -286,15 +286,19 @@ def montecarlo_transport_with_vpackets(packet_collection, geometry_state_numba, 
 
 class DevicePacketCollection:
     """A PacketCollection whose arrays live in the engine: the packets were drawn by the device packet source (SURVEY 8f-1,
-    BlackBodySimpleSource.create_packets, packet_source/base.py:195-253) and propagated in place.  Same attribute names as
+    BlackBodySimpleSource.create_packets, packet_source/base.py:195-253; with a ``time_explosion`` BlackBodySimpleSourceRelativistic,
+    the source of a full-relativity run) and propagated in place.  Same attribute names as
     the reference's PacketCollection (packets/packet_collections.py:13-101); a host copy of an array is made the first time it
     is read.  The engine's resident packets must still be these (a later set_packets / create_blackbody_packets on the same
     engine invalidates the un-read arrays: reading them then raises instead of returning another run's data)."""
 
-    def __init__(self, engine: Engine, n_packets: int, radius: float, temperature: float, base_seed: int, seed_offset: int):
+    def __init__(self, engine: Engine, n_packets: int, radius: float, temperature: float, base_seed: int, seed_offset: int,
+                 time_explosion: float | None = None):
         self._eng = engine
         self._n = int(n_packets)
         self.radius, self.temperature, self.base_seed, self.seed_offset = float(radius), float(temperature), int(base_seed), int(seed_offset)
+        # None: BlackBodySimpleSource; a number: BlackBodySimpleSourceRelativistic with beta = radius / time_explosion / c
+        self.time_explosion = None if time_explosion is None else float(time_explosion)
         self.radiation_field_luminosity = 4 * np.pi * st.SIGMA_SB * self.radius**2 * self.temperature**4  # base.py:255-270
         self.time_of_simulation = 1 / self.radiation_field_luminosity
         self._inputs = None
@@ -302,7 +306,8 @@ class DevicePacketCollection:
         self._pgen = self._rgen = None
 
     def _draw(self):
-        self._eng.create_blackbody_packets(self._n, self.radius, self.temperature, base_seed=self.base_seed, seed_offset=self.seed_offset)
+        kw = {} if self.time_explosion is None else {"time_explosion": self.time_explosion}  # (the simple source: today's call)
+        self._eng.create_blackbody_packets(self._n, self.radius, self.temperature, base_seed=self.base_seed, seed_offset=self.seed_offset, **kw)
         self._pgen = self._eng.packets_generation
         self._inputs = self._outputs = None
 
@@ -545,7 +550,8 @@ class MCTransportSolverHIP:
 
     ``resident=True`` is the outer-iteration form (Simulation.iterate, simulation/base.py:419-490: create packets -> run ->
     radiation field + luminosities -> plasma): everything the plasma step does not need stays in HBM.  Packets come from the
-    device packet source when ``initialize_transport_state`` is given ``n_packets`` instead of a packet collection; the
+    device packet source when ``initialize_transport_state`` is given ``n_packets`` instead of a packet collection (the
+    relativistic source under ``enable_full_relativity``, as in the reference); the
     opacity tables are re-uploaded only when the opacity object changed (TARDIS builds a new one per iteration; pass
     ``reuse_opacity=False`` if yours is mutated in place); per-packet outputs, trackers and the [L,S] line estimators are
     fetched on first access of the respective ``transport_state`` attribute; ``transport_state.packet_spectrum`` and
@@ -689,7 +695,10 @@ class MCTransportSolverHIP:
 
     def initialize_transport_state(self, packet_collection, geometry, opacity_state, time_explosion,
                                    no_of_virtual_packets=0, *, n_packets=None, iteration=0, temperature_inner=None,
-                                   base_seed=None):
+                                   base_seed=None, relativistic_source=None):
+        """``packet_collection=None`` draws the packets on the device.  ``relativistic_source``: None follows
+        ``enable_full_relativity`` as the reference's Simulation does (BlackBodySimpleSourceRelativistic under full relativity,
+        BlackBodySimpleSource otherwise); True / False force one form.  It has no meaning for a packet collection handed in."""
         cfg = self.montecarlo_configuration
         cfg.LINE_INTERACTION_TYPE = st.LINE_INTERACTION_TYPES[self.line_interaction_type]
         cfg.NUMBER_OF_VPACKETS = no_of_virtual_packets
@@ -701,8 +710,10 @@ class MCTransportSolverHIP:
             if not self.resident or n_packets is None or temperature_inner is None:
                 raise ValueError("the device packet source needs resident=True, n_packets and temperature_inner")
             seed = cfg.MONTECARLO_SEED if base_seed is None else base_seed
+            relativistic = bool(self.enable_full_relativity) if relativistic_source is None else bool(relativistic_source)
             packet_collection = DevicePacketCollection(self._eng(), n_packets, float(np.asarray(geometry.r_inner)[0]),
-                                                       temperature_inner, seed, iteration)
+                                                       temperature_inner, seed, iteration,
+                                                       time_explosion=float(time_explosion) if relativistic else None)
         ts = MonteCarloTransportState(packet_collection, geometry, opacity_state, time_explosion)
         ts.enable_full_relativity = cfg.ENABLE_FULL_RELATIVITY
         return ts
