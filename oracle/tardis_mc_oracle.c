@@ -240,6 +240,11 @@ int64_t oracle_trace_log_count(void) { return g_trace_log_n; }
 static int64_t *g_vtrace_log = NULL, g_vtrace_log_cap = 0, g_vtrace_log_n = 0;
 void oracle_set_vtrace_log(int64_t *buf, int64_t capacity_records) { g_vtrace_log = buf; g_vtrace_log_cap = capacity_records; g_vtrace_log_n = 0; }
 int64_t oracle_vtrace_log_count(void) { return g_vtrace_log_n; }
+/* analysis hook (tests/degenerate_blocks.py), single-threaded runs only: one record {shell, b0 of the block, selected row relative to b0 or -1
+ * when the block ran out, the bits of the number drawn} per jump of macro_atom_interaction */
+static int64_t *g_jump_log = NULL, g_jump_log_cap = 0, g_jump_log_n = 0;
+void oracle_set_jump_log(int64_t *buf, int64_t capacity_records) { g_jump_log = buf; g_jump_log_cap = capacity_records; g_jump_log_n = 0; }
+int64_t oracle_jump_log_count(void) { return g_jump_log_n; }
 
 static int trace_packet(const run_ctx *c, rpacket *p, mt_state *rng, double chi_cont, double *out_distance,
                         int *out_type, int64_t *out_delta, counters *cn)
@@ -335,6 +340,10 @@ static int macro_atom_interaction(const run_ctx *c, mt_state *rng, int64_t level
                 found = 1;
                 break;
             }
+        }
+        if (g_jump_log && g_jump_log_n < g_jump_log_cap) {
+            int64_t *r = g_jump_log + 4 * g_jump_log_n++;
+            r[0] = shell; r[1] = b0; r[2] = found ? tid - b0 : -1; memcpy(&r[3], &event, sizeof event);
         }
         if (!found) return TARDIS_MC_ERR_MACRO_ATOM;
     }
@@ -629,7 +638,7 @@ int oracle_mc_run(const TardisMcPackets *pk, const TardisMcGeometry *geo, const 
     if (op->n_shells != geo->n_shells) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     const int64_t P = pk->n_packets, S = op->n_shells, L = op->n_lines, G = cfg->n_spectrum_grid;
     if (n_threads < 1) n_threads = 1;
-    if (g_trace_log || g_vtrace_log) n_threads = 1; /* the analysis logs append with a plain counter: serial runs only */
+    if (g_trace_log || g_vtrace_log || g_jump_log) n_threads = 1; /* the analysis logs append with a plain counter: serial runs only */
     double *J = res->j_estimator, *nubar = res->nu_bar_estimator, *jb = res->j_blue_estimator, *ed = res->edotlu_estimator;
     double *hist = res->v_packets_energy_hist;
     int own_J = 0, own_nb = 0, own_jb = 0, own_ed = 0, own_h = 0;
