@@ -597,6 +597,68 @@ int tardis_mc_get_opacity(TardisMcContext *ctx, double *tau_sobolev, double *tra
  * (tardis_mc_set_option; -1, the default: this rule; n >= 0: blocks of n rows or more take the row form -- measurements only). */
 int tardis_mc_opacity_update_path(int64_t rows);
 
+/* ---- consumer of the resident optical depths: expansion opacity, Planck / Rosseland mean opacities and optical depths per shell ----
+ * What the inner-velocity workflow's tau integration computes from tau_sobolev [L,S] between two iterations (expansion opacity in
+ * frequency bins, its Planck and Rosseland means with electron scattering, the optical depths summed from the surface inward), here
+ * on the resident table: four vectors of S doubles come back, no [L,S] array crosses the bus.  The definition below is the contract;
+ * tests/mean_opacity_ref.py restates it serially and the device equals that bit for bit.
+ *
+ * All arithmetic is fp64 with no contraction: every product, quotient and sum is a rounding of its own.  exp is the transport's own.  The
+ * constants are those of the radiation-field section above: h, k_B, c, and planck_coef = 2h/(c c) formed as there.
+ *
+ * Bins.  L resident lines, m = bin_size >= 1.  asc[i] = line_list_nu[L-1-i] is the list in ascending order.  e = m - L mod m, so
+ * 1 <= e <= m, and n_bins = (L + e) / m.  The padded sequence is p[j] = j + 1 (Hz) for 0 <= j <= e and p[j] = asc[j-e-1] for e < j <= L + e;
+ * the padded optical depth is q[j][s] = 0.0 for j <= e and the resident tau_sobolev of that line in shell s for j > e.  Bin b has
+ * low_b = p[b m], high_b = p[(b+1) m], dnu_b = high_b - low_b, and the members j = b m + 1 .. (b+1) m: the line on the high edge belongs
+ * to the bin, the one on the low edge does not.  (NumPy: nu_p = hstack([arange(1, e + 2), asc]); low = nu_p[:-m:m], high = nu_p[m::m].)
+ *
+ * Refused on the host, before anything is launched, with TARDIS_MC_ERR_INVALID_ARGUMENT: m < 1; asc[0] <= e + 1 (the pads must lie below
+ * the list); any dnu_b == 0.0 (duplicate lines on two consecutive edges; the message names the first such bin); a t_radiative that is
+ * not finite and positive; a missing t_radiative pointer.  TARDIS_MC_ERR_STATE without a resident geometry or opacity.
+ *
+ * Per (bin, shell):  x[b][s] = the serial sum, from 0.0, over the members in ascending j of (1.0 - exp(-q[j][s]));  ct = time_explosion c;
+ *   kexp[b][s] = ((low_b / dnu_b) / ct) x[b][s].  No clamp: a negative resident tau gives the IEEE result.
+ * Weights at nu = low_b, t = t_radiative[s]:  beta = 1 / (k_B t);  E = exp((h nu) beta);  B = (planck_coef (nu nu nu)) / (E - 1);
+ *   cn = c / nu;  U = ((((B E) B) (cn cn)) / ((2 k_B) (t t)));  bd = B dnu_b;  ud = U dnu_b.  A bin where E is not finite or E - 1 == 0.0
+ *   contributes exactly 0.0 to all four sums below (the plain NumPy spelling makes the whole shell NaN there).
+ * Per shell:  kthom = electron_density[s] sigma_thomson, the resident values (sigma_thomson is the configuration's, 1e-200 with electron
+ *   scattering disabled, as the transport sees it; 6.652458734e-25 cm^2 while no configuration is resident).  Four serial sums over
+ *   the bins in ascending b from 0.0:  pn = sum bd kexp;  pd = sum bd;  rn = sum ud (1.0 / (kthom + kexp));  rd = sum ud.
+ *   kappa_planck = kthom + pn / pd;  kappa_rosseland = 1.0 / (rn / rd);  dr = r_outer[s] - r_inner[s];  the depths are summed from the
+ *   surface inward, tau[S-1] = kappa[S-1] dr[S-1], tau[s] = tau[s+1] + kappa[s] dr[s], for both means.
+ * This is the order of NumPy's reductions over an outer axis, so agreement with a plain NumPy spelling (libm exp, **-1, **2, nu**3) is
+ * to rounding, not bitwise: the largest relative deviation of the four vectors measured on the test models is 8.5e-15
+ * (tests/test_mean_opacity_host.py asserts ten times that; a single bin of thin lines deviates by more, 1.0 - exp(-tau) cancels there).
+ *
+ * tardis_mc_mean_opacity reads the resident tau table, electron densities, geometry and sigma_thomson and changes nothing resident;
+ * its scratch is released at return, as tardis_mc_formal_integral_interpolated does.  Outputs (host, any may be NULL): kappa_planck,
+ * kappa_rosseland, tau_planck, tau_rosseland [S]; kappa_expansion [n_bins,S]; bins_low, delta_nu [n_bins] (n_bins from
+ * tardis_mc_mean_opacity_bins).  No atomics: two calls give identical bits.  tardis_mc_last_propagate_ms then reports the call's kernels.
+ * Kernels in csrc/mean_opacity.hpp, the bin layout and the choice below in csrc/mean_opacity_plan.hpp. */
+typedef struct TardisMcMeanOpacity {
+    int64_t bin_size;                           /* m */
+    const double *t_radiative;                  /* [S] */
+    double *kappa_planck;                       /* [S] cm^-1, or NULL */
+    double *kappa_rosseland;                    /* [S] cm^-1, or NULL */
+    double *tau_planck;                         /* [S], or NULL */
+    double *tau_rosseland;                      /* [S], or NULL */
+    double *kappa_expansion;                    /* [n_bins,S] cm^-1, or NULL */
+    double *bins_low;                           /* [n_bins] Hz, or NULL */
+    double *delta_nu;                           /* [n_bins] Hz, or NULL */
+} TardisMcMeanOpacity;
+int tardis_mc_mean_opacity(TardisMcContext *ctx, const TardisMcMeanOpacity *request);
+/* The bin layout of a (descending) line list, host only, no context: returns n_bins, or a negative error code under the rules above
+ * (tardis_mc_last_error(NULL) then carries the message).  first_degenerate_bin (may be NULL): the first bin of width 0, -1 where there is
+ * none. */
+int64_t tardis_mc_mean_opacity_bins(int64_t n_lines, const double *line_list_nu, int64_t bin_size, int64_t *first_degenerate_bin);
+/* Device time of the stages of the last tardis_mc_mean_opacity, in ms (either pointer may be NULL): the bin kernel | the shell reduction
+ * and the final kernel.  Their sum is what tardis_mc_last_propagate_ms reports after the call.  TARDIS_MC_ERR_STATE before the first call. */
+int tardis_mc_last_mean_opacity_ms(TardisMcContext *ctx, double *out_bin_ms, double *out_reduce_ms);
+/* Which form the shell reduction takes for n_bins bins (csrc/mean_opacity_plan.hpp): 0 a lane per shell, 1 a wave per shell whose four
+ * 16-lane rows carry the four sums.  Host only; both forms add in the same order.  Option "mean_opacity_long_bins"
+ * (tardis_mc_set_option; -1, the default: this rule; n >= 0: the row form from n bins upward -- tests and measurements only). */
+int tardis_mc_mean_opacity_path(int64_t n_bins);
+
 /* ---- producer of the next iteration's populations: ion and level number densities from (t_rad, W) ------------------------------
  * What the legacy plasma computes between two iterations in its default configuration -- ionization nebular (or lte), excitation
  * dilute-lte (or lte), NLTE excitation only through the section after this one, helium_treatment recomb-nlte and delta_treatment only through tardis_mc_set_ionization_options below, no continuum: LevelBoltzmannFactor, PartitionFunction,

@@ -113,6 +113,21 @@ class TardisMcOpacityUpdate(C.Structure):
 J_BLUES_DILUTE_BLACKBODY, J_BLUES_DETAILED = 0, 1
 
 
+class TardisMcMeanOpacity(C.Structure):
+    """Request of tardis_mc_mean_opacity: bin size and radiation temperatures in, host outputs (any may be NULL)."""
+    _fields_ = [
+        ("bin_size", C.c_int64),
+        ("t_radiative", _pd),
+        ("kappa_planck", _pd),
+        ("kappa_rosseland", _pd),
+        ("tau_planck", _pd),
+        ("tau_rosseland", _pd),
+        ("kappa_expansion", _pd),
+        ("bins_low", _pd),
+        ("delta_nu", _pd),
+    ]
+
+
 class TardisMcPlasmaData(C.Structure):
     """Static plasma data of the plasma update (tardis_mc_set_plasma_data)."""
     _fields_ = [
@@ -368,6 +383,30 @@ def marshal_opacity_update(level_number_density, n_shells, electron_density=None
         setattr(s, name, _dp(a))
         keep.append(a)
     return Marshalled(s, keep)
+
+
+def marshal_mean_opacity(t_radiative, bin_size, n_shells, n_bins, want_expansion=False) -> Marshalled:
+    """The request of tardis_mc_mean_opacity with freshly allocated outputs: ``.out`` is the dict of them.  ``t_radiative`` None is
+    passed as a missing pointer (the library refuses it)."""
+    S, B = int(n_shells), int(n_bins)
+    s = TardisMcMeanOpacity()
+    s.bin_size = int(bin_size)
+    keep = []
+    if t_radiative is not None:
+        t = np.ascontiguousarray(t_radiative, dtype=np.float64)
+        if t.shape != (S,):
+            raise ValueError("t_radiative must have n_shells entries")
+        s.t_radiative = _dp(t)
+        keep.append(t)
+    out = {n: np.empty(S) for n in ("kappa_planck", "kappa_rosseland", "tau_planck", "tau_rosseland")}
+    out["bins_low"], out["delta_nu"] = np.empty(B), np.empty(B)
+    if want_expansion:
+        out["kappa_expansion"] = np.empty((B, S))
+    for name, a in out.items():
+        setattr(s, name, _dp(a))
+    m = Marshalled(s, keep + list(out.values()))
+    m.out = out
+    return m
 
 
 def marshal_plasma_data(pd) -> Marshalled:

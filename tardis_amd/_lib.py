@@ -68,6 +68,10 @@ SYMBOLS = {
     "tardis_mc_get_opacity": (_i, [_vp] * 6),
     "tardis_mc_last_opacity_update_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 3),
     "tardis_mc_opacity_update_path": (_i, [C.c_int64]),
+    "tardis_mc_mean_opacity": (_i, [_vp, _vp]),
+    "tardis_mc_mean_opacity_bins": (C.c_int64, [C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "tardis_mc_last_mean_opacity_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 2),
+    "tardis_mc_mean_opacity_path": (_i, [C.c_int64]),
     "tardis_mc_set_plasma_data": (_i, [_vp, _vp]),
     "tardis_mc_update_plasma": (_i, [_vp, _vp]),
     "tardis_mc_get_plasma": (_i, [_vp] * 5 + [C.POINTER(C.c_int32)]),

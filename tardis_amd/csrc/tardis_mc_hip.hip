@@ -40,6 +40,8 @@
 #include "vpacket_log.hpp"
 #include "opacity_update.hpp"
 #include "opacity_update_plan.hpp"
+#include "mean_opacity.hpp"
+#include "mean_opacity_plan.hpp"
 #include "plasma_update.hpp"
 #include "plasma_update_plan.hpp"
 #include "nlte_excitation.hpp"
@@ -455,6 +457,13 @@ struct TardisMcContext {
         bool timed = false;
         void release() { release_buffers(f_lu, wave, g_lower, g_upper, level_lower, level_upper, coef, long_blocks, n_t, shell, beta_t, sef_t, j_t); destroy_events(ev); }
     } ou;
+    // Mean opacities (mean_opacity.hpp): a reader of the resident tables that keeps nothing but its events -- its buffers are scratch of the call.
+    struct MeanOpacity {
+        long long long_bins = -1;  // option mean_opacity_long_bins: -1 the rule of mean_opacity_plan.hpp, else the threshold itself
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // start | behind the bin kernel | behind the reduction and the final kernel (tardis_mc_last_mean_opacity_ms)
+        bool timed = false;
+        void release() { destroy_events(ev); }
+    } mo;
     // Plasma update (plasma_update.hpp).  Per set_plasma_data: the atomic data of the levels and ions, the map level -> ion, the list of the ions that
     // take the row form of the partition kernel.  Per update_plasma: lbf_t[S][K]; Z, phi, N [I][S]; the solved n_e [S]; {status, passes}.
     struct PlasmaUpdate {
@@ -2441,7 +2450,7 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
     ctx->ot.release(); ctx->wt.release(); ctx->sc.release(); ctx->sw.release(); ctx->es.release(); ctx->pk.release(); ctx->vl.release(); ctx->el.release();
     ctx->wv.release(); ctx->lt.release(); ctx->rs.release(); ctx->sf.release(); ctx->pg.release();
-    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release(); ctx->he.release();
+    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release(); ctx->he.release(); ctx->mo.release();
     ctx->release();
     delete ctx;
 }
@@ -2513,6 +2522,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "chunk_packets") ctx->chunk_packets = std::max<long long>(1024, value);
     else if (n == "opacity_update_long_rows") ctx->ou.long_rows = value < 0 ? -1 : value;
     else if (n == "plasma_update_long_rows") ctx->pl.long_rows = value < 0 ? -1 : value;
+    else if (n == "mean_opacity_long_bins") ctx->mo.long_bins = value < 0 ? -1 : value;
     else if (n == "plasma_max_iterations") ctx->pl.max_iterations = std::max<long long>(1, value);
     else if (n == "nlte_lds_levels") ctx->nl.lds_levels = value < 0 ? -1 : value;
     else if (n == "nlte_blocked_levels") ctx->nl.blocked_levels = value < 0 ? -1 : value;
@@ -4590,6 +4600,109 @@ int tardis_mc_get_opacity(TardisMcContext *ctx, double *tau_sobolev, double *tra
     if ((rc = download_transposed(ctx, beta_sobolev, ctx->ou.beta_t.as<double>(), L))) return rc;
     if ((rc = download_transposed(ctx, stimulated_emission_factor, ctx->ou.sef_t.as<double>(), L))) return rc;
     return download_transposed(ctx, j_blues, ctx->ou.j_t.as<double>(), L);
+}
+
+/* ---- mean opacities and optical depths from the resident optical depths (mean_opacity.hpp) ------------------ */
+static_assert(mopl::ERR_INVALID_ARGUMENT == TARDIS_MC_ERR_INVALID_ARGUMENT, "mean_opacity_plan.hpp repeats the error code");
+
+int tardis_mc_mean_opacity_path(int64_t n_bins) { return mopl::choose_path((long long)n_bins); }
+
+int64_t tardis_mc_mean_opacity_bins(int64_t n_lines, const double *line_list_nu, int64_t bin_size, int64_t *first_degenerate_bin)
+{
+    mopl::Layout lay;
+    std::string msg;
+    long long first = -1;
+    const long long n = mopl::plan_bins((long long)n_lines, line_list_nu, (long long)bin_size, lay, &first, msg);
+    if (first_degenerate_bin) *first_degenerate_bin = first;
+    if (n < 0) return fail(nullptr, (int)n, "%s", msg.c_str());
+    return n;
+}
+
+int tardis_mc_mean_opacity(TardisMcContext *ctx, const TardisMcMeanOpacity *q)
+{
+    if (!ctx || !q) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid mean opacity request");
+    if (!ctx->have_geometry || !ctx->have_opacity) return fail(ctx, TARDIS_MC_ERR_STATE, "set_geometry and set_opacity must precede mean_opacity");
+    const size_t S = (size_t)ctx->n_shells, L = (size_t)ctx->n_lines;
+    if (ctx->ot.h_nu.size() != L) return fail(ctx, TARDIS_MC_ERR_STATE, "the resident line list does not match the line count");
+    // everything is refused here, on the host, before anything is allocated or launched
+    mopl::Layout lay;
+    std::string msg;
+    const long long n_bins = mopl::plan_bins((long long)L, ctx->ot.h_nu.data(), (long long)q->bin_size, lay, nullptr, msg);
+    if (n_bins < 0) return fail(ctx, (int)n_bins, "%s", msg.c_str());
+    if (!q->t_radiative) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "mean opacity: t_radiative is missing");
+    for (size_t s = 0; s < S; ++s)
+        if (!(std::isfinite(q->t_radiative[s]) && q->t_radiative[s] > 0.0))
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "mean opacity: t_radiative[%zu] = %g is not finite and positive", s, q->t_radiative[s]);
+    if (S > 65535) return fail(ctx, TARDIS_MC_ERR_UNSUPPORTED, "mean opacity: %zu shells, the bin kernel's grid takes 65535", S);
+    const size_t B = (size_t)n_bins;
+    std::vector<double> low(B), dnu(B);
+    for (size_t b = 0; b < B; ++b) {
+        low[b] = mopl::bin_low(lay, ctx->ot.h_nu.data(), (long long)b);
+        dnu[b] = mopl::bin_high(lay, ctx->ot.h_nu.data(), (long long)b) - low[b];
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ScopedDevBuf d_low, d_dnu, d_t, kexp_t, sums, out, kexp_lines;
+    const int rc = [&]() -> int {
+        int rc1;
+        if ((rc1 = upload(ctx, d_low, low.data(), B))) return rc1;
+        if ((rc1 = upload(ctx, d_dnu, dnu.data(), B))) return rc1;
+        if ((rc1 = upload(ctx, d_t, q->t_radiative, S))) return rc1;
+        HIP_TRY(ctx, kexp_t.ensure(S * B * sizeof(double)));
+        HIP_TRY(ctx, sums.ensure(4 * S * sizeof(double)));
+        HIP_TRY(ctx, out.ensure(4 * S * sizeof(double)));
+        if (q->kappa_expansion) HIP_TRY(ctx, kexp_lines.ensure(S * B * sizeof(double)));
+        int rc2;
+        ctx->mo.timed = false;
+        if ((rc2 = ensure_events(ctx, ctx->mo.ev))) return rc2;
+        const double h = H_PLANCK, c = mc::C_LIGHT;
+        mc::MeanOpacityConsts k;
+        k.ct = ctx->t_exp * c; k.planck_coef = 2 * h / (c * c); k.h = h; k.k_b = K_BOLTZMANN; k.c = c;
+        k.sigma_thomson = ctx->have_config ? ctx->cfg.sigma_thomson : 6.652458734e-25;  // (without a configuration: SIGMA_THOMSON, as the formal integral has it)
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->mo.ev[0], ctx->stream));
+        hipLaunchKernelGGL(mc::mean_opacity_bin_kernel, dim3((unsigned)((B + 255) / 256), (unsigned)S), dim3(256), 0, ctx->stream, ctx->ot.tau_t.as<double>(),
+                           (long long)L, lay.m, lay.e, n_bins, d_low.as<double>(), d_dnu.as<double>(), k.ct, kexp_t.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipEventRecord(ctx->mo.ev[1], ctx->stream));
+        if (mopl::choose_path(n_bins, ctx->mo.long_bins) == mopl::PATH_ROW)
+            hipLaunchKernelGGL(mc::mean_opacity_reduce_row_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, ctx->stream, kexp_t.as<double>(), n_bins, (int)S,
+                               d_low.as<double>(), d_dnu.as<double>(), d_t.as<double>(), ctx->ot.n_e.as<double>(), k, sums.as<double>());
+        else
+            hipLaunchKernelGGL(mc::mean_opacity_reduce_lane_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, ctx->stream, kexp_t.as<double>(), n_bins, (int)S,
+                               d_low.as<double>(), d_dnu.as<double>(), d_t.as<double>(), ctx->ot.n_e.as<double>(), k, sums.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(mc::mean_opacity_final_kernel, dim3(1), dim3(64), 0, ctx->stream, sums.as<double>(), (int)S, ctx->ot.n_e.as<double>(),
+                           ctx->r_inner.as<double>(), ctx->r_outer.as<double>(), k.sigma_thomson, out.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipEventRecord(ctx->mo.ev[2], ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+        ctx->timed = true;
+        ctx->chunks_timed = 0;
+        double *const host[4] = {q->kappa_planck, q->kappa_rosseland, q->tau_planck, q->tau_rosseland};
+        for (int v = 0; v < 4; ++v)
+            if (host[v]) HIP_TRY(ctx, hipMemcpyAsync(host[v], out.as<double>() + (size_t)v * S, S * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (q->kappa_expansion) {  // [S][n_bins] -> [n_bins, S]
+            HIP_TRY(ctx, launch_transpose(ctx->stream, kexp_t.as<double>(), kexp_lines.as<double>(), (long long)S, n_bins));
+            HIP_TRY(ctx, hipMemcpyAsync(q->kappa_expansion, kexp_lines.p, S * B * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->mo.timed = true;
+        return TARDIS_MC_OK;
+    }();
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (nothing of the call is in flight when its scratch goes)
+    if (rc) return rc;
+    if (q->bins_low) memcpy(q->bins_low, low.data(), B * 8);
+    if (q->delta_nu) memcpy(q->delta_nu, dnu.data(), B * 8);
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_last_mean_opacity_ms(TardisMcContext *ctx, double *out_bin_ms, double *out_reduce_ms)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->mo.timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no mean_opacity has been timed yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double *const out[2] = {out_bin_ms, out_reduce_ms};
+    return event_intervals_ms(ctx, ctx->mo.ev, 2, out);
 }
 
 

@@ -69,6 +69,7 @@ class Engine:
         # the opacity object whose tables are in HBM (None: unknown) -- residency is a property of the ENGINE, which several
         # solvers and the non-resident entry point may share (MCTransportSolverHIP reuses the upload only against this)
         self.resident_opacity = None
+        self.resident_geometry = None  # likewise (geometry object, time_explosion) of the last set_geometry()
         self.options = {}  # options set through set_option (name -> last value accepted by the library)
 
     # -- lifetime
@@ -116,8 +117,10 @@ class Engine:
 
     def set_geometry(self, geometry, time_explosion=None):
         m = _abi.marshal_geometry(geometry, time_explosion)
+        self.resident_geometry = None
         self._check(self._L.tardis_mc_set_geometry(self._h, m.ref()), "set_geometry")
         self.n_shells = int(m.struct.n_shells)
+        self.resident_geometry = (geometry, float(m.struct.time_explosion))
 
     def set_opacity(self, opacity_state):
         m = _abi.marshal_opacity(opacity_state)
@@ -189,6 +192,50 @@ class Engine:
         """The form of update_opacity()'s block kernel for a macro-atom block of ``rows`` transitions: "lane" (one lane per
         (block, shell)) or "row" (a 16-lane row per (block, shell)); csrc/opacity_update_plan.hpp."""
         return ("lane", "row")[int(_lib.lib().tardis_mc_opacity_update_path(int(rows)))]
+
+    def mean_opacity(self, t_radiative, bin_size=10, want_expansion=False) -> dict:
+        """The expansion opacity of the resident tau_sobolev in frequency bins of ``bin_size`` lines, its Planck and Rosseland means
+        with electron scattering and the optical depths summed from the surface inward (`tardis_mc_mean_opacity`; the header states
+        the arithmetic): {"kappa_planck", "kappa_rosseland", "tau_planck", "tau_rosseland": [n_shells]; "bins_low", "delta_nu":
+        [n_bins]; "bin_size", "n_bins"}, with ``want_expansion`` also "kappa_expansion" [n_bins, n_shells].  Needs set_geometry() and
+        an opacity state (set_opacity / update_opacity / update_plasma); changes nothing resident.  A ``bin_size`` at which a bin
+        has width 0 is refused (RuntimeError, ``code`` ERR_INVALID_ARGUMENT): see ``mean_opacity_bins``."""
+        m, L = int(bin_size), self.n_lines
+        n_bins = (L + m - L % m) // m if m >= 1 and L >= 1 else 1
+        # (before any set_geometry / set_opacity the library refuses the call: the request only has to be well formed)
+        n_shells = self.n_shells or (1 if t_radiative is None else np.size(t_radiative))
+        q = _abi.marshal_mean_opacity(t_radiative, m, n_shells, n_bins, want_expansion)
+        self._check(self._L.tardis_mc_mean_opacity(self._h, q.ref()), "mean_opacity")
+        out = dict(q.out)
+        out["bin_size"], out["n_bins"] = m, n_bins
+        return out
+
+    def last_mean_opacity_ms(self) -> dict:
+        """Device time (ms) of the stages of the last mean_opacity(): {"bin_ms" (bin kernel), "reduce_ms" (shell reduction and the
+        final kernel)}."""
+        a, b = C.c_double(), C.c_double()
+        self._check(self._L.tardis_mc_last_mean_opacity_ms(self._h, C.byref(a), C.byref(b)), "last_mean_opacity_ms")
+        return {"bin_ms": a.value, "reduce_ms": b.value}
+
+    @staticmethod
+    def mean_opacity_bins(line_list_nu, bin_size: int) -> tuple[int, int]:
+        """The bin layout of mean_opacity() for a descending line list (`tardis_mc_mean_opacity_bins`, host only): (n_bins, -1), or
+        (error code < 0, first bin of width 0 or -1) where the library refuses the size; ``mean_opacity_bins_error()`` has the text."""
+        nu = np.ascontiguousarray(line_list_nu, dtype=np.float64)
+        first = C.c_int64(-1)
+        n = _lib.lib().tardis_mc_mean_opacity_bins(len(nu), nu.ctypes.data, int(bin_size), C.byref(first))
+        return int(n), int(first.value)
+
+    @staticmethod
+    def mean_opacity_bins_error() -> str:
+        """The message of the last refusal of mean_opacity_bins() on this thread."""
+        return _lib.lib().tardis_mc_last_error(None).decode()
+
+    @staticmethod
+    def mean_opacity_path(n_bins: int) -> str:
+        """The form of mean_opacity()'s shell reduction for ``n_bins`` bins: "lane" (one lane per shell) or "row" (a wave per shell,
+        four 16-lane rows); csrc/mean_opacity_plan.hpp."""
+        return ("lane", "row")[int(_lib.lib().tardis_mc_mean_opacity_path(int(n_bins)))]
 
     def set_plasma_data(self, plasma_data):
         """The static plasma data of update_plasma() (`tardis_mc_set_plasma_data`), after set_line_data(): an object with the
@@ -579,6 +626,7 @@ class Engine:
         trackers = st.LastInteractionTrackers(P) if track_last_interaction else None
         res = _abi.ResultBuffers(P, S, L, int(mc.struct.n_spectrum_grid), None, None, trackers, cap)
         self.resident_opacity = None
+        self.resident_geometry = None
         self.line_data = None
         self.plasma_data = None
         self.nlte_data = None

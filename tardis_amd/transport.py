@@ -545,6 +545,31 @@ class MonteCarloTransportState:
             index=pd.RangeIndex(n, name="packet_id"))
 
 
+def estimate_v_inner(tau, v_inner, target=2.0 / 3.0) -> float:
+    """The inner boundary velocity at which a mean optical depth reaches ``target``: ``v_inner`` [shells] interpolated linearly in
+    ln(tau), with extrapolation, at ln(target) -- one step of an inner-velocity search on ``mean_optical_depths()``'s "tau_rosseland"
+    (or "tau_planck").  Host NumPy only.  Shells whose tau is not positive and finite are left out; the others are put in ascending
+    ln(tau) (stable), and the value follows the rule include/tardis_mc.h states for interpolate_shells:
+        hi = clip(searchsorted(x, xn, side="left"), 1, n-1), lo = hi - 1;  slope = (y[hi] - y[lo]) / (x[hi] - x[lo]);
+        v = slope * (xn - x[lo]) + y[lo]
+    ValueError when fewer than two shells are left."""
+    tau = np.asarray(tau, dtype=np.float64)
+    v = np.asarray(v_inner, dtype=np.float64)
+    if tau.shape != v.shape or tau.ndim != 1:
+        raise ValueError("tau and v_inner must be vectors of equal length")
+    ok = np.isfinite(tau) & (tau > 0.0)
+    if np.count_nonzero(ok) < 2:
+        raise ValueError("estimate_v_inner needs at least two shells with a positive finite optical depth")
+    x, y = np.log(tau[ok]), v[ok]
+    order = np.argsort(x, kind="stable")
+    x, y = x[order], y[order]
+    xn = np.log(float(target))
+    hi = int(np.clip(np.searchsorted(x, xn, side="left"), 1, len(x) - 1))
+    lo = hi - 1
+    slope = (y[hi] - y[lo]) / (x[hi] - x[lo])
+    return float(slope * (xn - x[lo]) + y[lo])
+
+
 class MCTransportSolverHIP:
     """GPU counterpart of MCTransportSolverClassic (modes/classic/solver.py:46-273), plain-array inputs.
 
@@ -577,6 +602,8 @@ class MCTransportSolverHIP:
         self.nlte_data = None          # the NLTE species of update_plasma() (set_nlte_data)
         self.nlte_collision_data = None  # their collisional rates (set_nlte_collision_data)
         self.ionization_options = None  # (helium_treatment, helium_element, delta_treatment) of update_plasma() (set_ionization_options)
+        self._mean_state = None        # what mean_optical_depths() runs on: the last initialize_transport_state()'s geometry ...
+        self._mean_opacity = None      # ... and the newest opacity state (that call's, or the handle of a later update)
 
     def set_line_data(self, line_data):
         """The atomic data update_opacity() computes the tables from (the fields of ``synthetic.LineData`` /
@@ -616,6 +643,7 @@ class MCTransportSolverHIP:
             raise ValueError(f"unknown radiative_rates_type {radiative_rates_type!r}")
         handle = DeviceOpacityState(eng, base, base.electron_density if electron_density is None else electron_density)
         eng.resident_opacity = handle
+        self._mean_opacity = handle
         return handle
 
     def set_plasma_data(self, plasma_data):
@@ -688,7 +716,41 @@ class MCTransportSolverHIP:
             raise ValueError(f"unknown radiative_rates_type {radiative_rates_type!r}")
         handle = DeviceOpacityState(eng, base, eng.get_plasma(False, False, False, True)["electron_density"])
         eng.resident_opacity = handle
+        self._mean_opacity = handle
         return handle
+
+    def mean_optical_depths(self, t_radiative, bin_size=None) -> dict:
+        """The Planck and Rosseland mean opacities and optical depths per shell of the current opacity state
+        (``Engine.mean_opacity``, ``resident=True``): the inputs of an inner-velocity search (``estimate_v_inner``) and the "where is
+        the photosphere" diagnostic, from the resident tau_sobolev -- four vectors of S doubles come back, the table stays where it
+        is.  Valid after ``update_plasma`` / ``update_opacity`` (the tables they left in the engine) and after
+        ``initialize_transport_state`` (its geometry and opacity state, uploaded here if the engine does not hold them yet, so
+        that the following run uploads nothing).  ``bin_size`` None starts at 10 lines per bin and walks upward by 1 until no bin
+        has width 0 (duplicate lines on two consecutive bin edges); the dict's "bin_size" reports the size used."""
+        if not self.resident:
+            raise RuntimeError("mean_optical_depths() needs resident=True")
+        ts = self._mean_state
+        if ts is None:
+            raise RuntimeError("mean_optical_depths() needs initialize_transport_state() first")
+        eng = self._eng()
+        geometry, t_exp = ts.geometry_state_numba, float(ts.time_explosion)
+        if eng.resident_geometry is None or eng.resident_geometry[0] is not geometry or eng.resident_geometry[1] != t_exp:
+            eng.set_geometry(geometry, t_exp)
+        op = self._mean_opacity
+        if not (eng.resident_opacity is op and (self.reuse_opacity or isinstance(op, DeviceOpacityState))):
+            if isinstance(op, DeviceOpacityState):
+                raise RuntimeError("the engine's opacity tables were replaced since this update: they are gone")
+            eng.set_opacity(op)
+        if bin_size is not None:
+            return eng.mean_opacity(t_radiative, bin_size)
+        nu = np.ascontiguousarray(op.line_list_nu, dtype=np.float64)
+        m = 10
+        while m <= len(nu):  # (one bin of all the lines, m > L, has its low edge on a pad: never degenerate)
+            n, first = Engine.mean_opacity_bins(nu, m)
+            if n >= 0 or first < 0:  # (any other refusal is the call's to report)
+                break
+            m += 1
+        return eng.mean_opacity(t_radiative, m)
 
     def _eng(self) -> Engine:
         return self._engine if self._engine is not None else get_engine(self.device_id)
@@ -716,6 +778,7 @@ class MCTransportSolverHIP:
                                                        time_explosion=float(time_explosion) if relativistic else None)
         ts = MonteCarloTransportState(packet_collection, geometry, opacity_state, time_explosion)
         ts.enable_full_relativity = cfg.ENABLE_FULL_RELATIVITY
+        self._mean_state, self._mean_opacity = ts, opacity_state
         return ts
 
     def run(self, transport_state, show_progress_bars=False):
