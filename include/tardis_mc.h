@@ -236,8 +236,9 @@ const char *tardis_mc_last_error(const TardisMcContext *ctx);   /* ctx may be NU
  * rest of the generation the packet is in at the top of a pass, 64 words per round, and the packet's refills out of that generation read 32 bytes and
  * store nothing, csrc/mt_generation.hpp; 0: every refill regenerates its 8 words itself.  1 is the default.  Results do not depend on it;
  * the other kernels ignore it),
- * "sweep_skip" (variant 3 without v-packets, the sixteen-wave lane sweeps on the interleaved table: a trace proves whole aligned blocks of 8 lines harmless on
- * a coarse table of prefix sums of the optical depths, ten blocks per step, and sweeps line by line only from the block that may stop it,
+ * "sweep_skip" (variant 3 without v-packets, the lane sweeps on the interleaved table, sixteen-wave and twelve-wave form alike ("ls_waves_per_simd"): a trace
+ * proves whole aligned blocks of 8 lines harmless on a coarse table of prefix sums of the optical depths, seven blocks per step at sixteen waves and nine at
+ * twelve, and sweeps line by line -- eight and ten lines per step -- only from the block that may stop it,
  * csrc/sweep_skip.hpp; -1, the default: automatic; 0 off; 1 on where the call allows it -- partial relativity, 32-bit table offsets, line scattering
  * enabled, no negative or non-finite optical depth, not the shell-sorted log or the cross-check instantiations.  Results do not depend on it;
  * tardis_mc_last_sweep_skip tells what a call ran with; debug flag 536870912 (tests) makes every skipped trace fall back to the line-by-line sweep),

@@ -158,7 +158,8 @@ inline Plan plan_propagate(const PlanInput &in)
 }
 
 // ---- the block skip of the lane sweeps (sweep_skip.hpp): whether a call's sweeps clear whole 8-line blocks on the coarse table.  Decided once the wave
-// kernel's instantiation is known: the code is compiled into ONE of them, and its proof needs what the interleaved table's lean proof needs, plus line
+// kernel's instantiation is known: the code is compiled into the two production lane-sweep forms on the interleaved table (sixteen waves at eight loads per step,
+// twelve waves at ten), and its proof needs what the interleaved table's lean proof needs, plus line
 // scattering (a trace without it never stops on a line: nothing to gain, and lane_exact_line's code 3 is what the interval check is about).
 struct SkipInput {
     int sweep_skip;            // the option: -1 automatic, 0 off, 1 on where allowed
@@ -166,11 +167,14 @@ struct SkipInput {
     int waves_per_simd, nt;    // the instantiation: waves per SIMD it is compiled for; 0 separate tables, 1 interleaved, 2 aligned runs
     bool line_scattering;
     bool nt_negative, pfx_negative;  // a negative or non-finite optical depth, seen by the interleaved table's / the prefix sums' builder
+    bool twelve_wave_skip;     // the build's twelve-wave instantiation on the interleaved table carries the skip as well (TMC_SWEEP_SKIP_12, propagate_wave.hpp)
 };
 inline bool plan_sweep_skip(const SkipInput &in)
 {
     if (in.sweep_skip == 0) return false;
-    return in.lane_sweep && !in.vpk && !in.full_relativity && !in.wide && !in.cross_check && !in.shell_log && !in.full_tracking && in.waves_per_simd == 4 &&
+    // (the twelve-wave form under the same conditions as the sixteen-wave one)
+    const bool instantiation = in.waves_per_simd == 4 || (in.waves_per_simd == 3 && in.twelve_wave_skip);
+    return in.lane_sweep && !in.vpk && !in.full_relativity && !in.wide && !in.cross_check && !in.shell_log && !in.full_tracking && instantiation &&
            in.nt == 1 && in.line_scattering && !in.nt_negative && !in.pfx_negative;
 }
 

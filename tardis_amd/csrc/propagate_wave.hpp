@@ -181,7 +181,7 @@ struct WaveCold {
     int log_gen;       // generation of the log's chunk pool (the host bumps it whenever it resets the pool): a chunk held from an earlier one is gone
     double *vq_jsave;  // [waves][2 * n_shells]: the waves' J / nu_bar partial sums between the launches of a volley-queue call
     int rng_complete;  // lane sweeps without v-packets: 1 the wave finishes a packet's MT19937 generation at the top of a pass (option rng_complete); 0 never.  Wave-uniform, as trk_defer
-    // block skip of the sixteen-wave lane sweep (sweep_skip.hpp; option sweep_skip): 0 off, 1 on, 2 on with every interval-mode decision treated as ambiguous (tests).
+    // block skip of the sixteen-wave and twelve-wave lane sweeps on the interleaved table (sweep_skip.hpp; option sweep_skip): 0 off, 1 on, 2 on with every interval-mode decision treated as ambiguous (tests).
     // The coarse table and the {frequency, prefix sum} table lie behind the interleaved table in its allocation: sk_ct_off, sk_pn_off in 16-byte entries from H.tau_t.
     // Wave-uniform, as rng_complete
     int sweep_skip;
@@ -413,13 +413,28 @@ constexpr int LS_CHUNK = 8;  // lines per lane and step (the line list and the t
 #ifndef TMC_LS_CHUNK_NT
 #define TMC_LS_CHUNK_NT 10
 #endif
-// ... of the sixteen-wave instantiation on the interleaved table (its slack: 32 entries).  Ten: with the lean proof the 128-VGPR budget holds two more lines (14 instead
+// ... of the sixteen-wave instantiations on the interleaved table that do NOT carry the block skip (cross-check walks, shell-sorted log; its slack: 32 entries; the
+// ones that do: LS_SKIP_LOADS_16 below).  Ten: with the lean proof the 128-VGPR budget holds two more lines (14 instead
 // of 10 spilled VGPRs), a 36-line trace is 4.1 instead of 5 dependent steps: propagation launches -2.4 % on configs[2] heavy (2 748 / 2 684 -> 2 652 / 2 651 ms per 1e8
 // packets), nothing either way on the uniform levels, the 1.25e7-packet call and configs[1]; twelve (29 spilled VGPRs): +3 ... +7 % (profiles/r06_lines_per_step.txt)
 constexpr int LS_CHUNK_NT = TMC_LS_CHUNK_NT;
 #ifndef TMC_SWEEP_SKIP
-#define TMC_SWEEP_SKIP 1  // (experiment switch: 0 compiles the block skip of sweep_skip.hpp out of the sixteen-wave instantiation)
+#define TMC_SWEEP_SKIP 1  // (experiment switch: 0 compiles the block skip of sweep_skip.hpp out of the lane-sweep instantiations)
 #endif
+#ifndef TMC_SWEEP_SKIP_12
+#define TMC_SWEEP_SKIP_12 1  // (experiment switch: 0 leaves the twelve-wave instantiation on the interleaved table without the block skip, at twelve lines per step)
+#endif
+// 16-byte loads of a step, coarse or fine, in the instantiations that carry the block skip (ssk::coarse_scan's N).  Sixteen waves: eight -- a trace is about one
+// coarse and one fine step, the fine step of interval mode starts on a block boundary and needs the eight lines of that block, one aligned 128-byte line; at ten
+// the skip cost 19 instead of 7 spilled VGPRs.  Twelve waves: ten, the widest at which the skip fits its 168 VGPRs without scratch (twelve: 7 spilled).
+// profiles/sweep_skip_widths.txt
+#ifndef TMC_SKIP_LOADS_16
+#define TMC_SKIP_LOADS_16 8
+#endif
+#ifndef TMC_SKIP_LOADS_12
+#define TMC_SKIP_LOADS_12 10
+#endif
+constexpr int LS_SKIP_LOADS_16 = TMC_SKIP_LOADS_16, LS_SKIP_LOADS_12 = TMC_SKIP_LOADS_12;
 
 // Running sums of the transition probabilities, block by block (macro_atom.py:87-97: `probability += transition_probabilities[i, shell]`
 // from block_start): one thread per (block, shell) repeats the reference's additions once per opacity state, so that a
@@ -851,9 +866,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     // RNGC: a packet past its first MT19937 generation has the rest of the generation it is in produced by the whole wave at the top of a pass
     // (mt_generation.hpp) and carries bit 17 of r_gpos from there to the wrap: its refills are then one aligned 32-byte read, no second window, no store.
     constexpr bool RNGC = LS && !VPK;
-    // SKIP: the sweep may clear whole 8-line blocks on the coarse table (sweep_skip.hpp) where W->sweep_skip says so: the sixteen-wave instantiation on the
-    // interleaved table only.  The mode of a trace is two bits of pflags (ssk::MODE_COARSE: the next step is a coarse one; ssk::MODE_INTERVAL: s_tau is an upper bound)
-    constexpr bool SKIP = TMC_SWEEP_SKIP != 0 && LS && !VPK && NT == 1 && WPE == 4 && !WIDE && !SL && !XWALK && !FULL && !FT && TMC_STRAIGHT_A == 0;
+    // SKIP: the sweep may clear whole 8-line blocks on the coarse table (sweep_skip.hpp) where W->sweep_skip says so: the sixteen-wave and the twelve-wave
+    // instantiation on the interleaved table only.  The mode of a trace is two bits of pflags (ssk::MODE_COARSE: the next step is a coarse one; ssk::MODE_INTERVAL:
+    // s_tau is an upper bound).  These instantiations run LS_SKIP_LOADS_16 / LS_SKIP_LOADS_12 loads per step, skipping or not.
+    constexpr bool SKIP = TMC_SWEEP_SKIP != 0 && LS && !VPK && NT == 1 && ((WPE == 4 && TMC_STRAIGHT_A == 0) || (WPE == 3 && TMC_SWEEP_SKIP_12 != 0)) && !WIDE && !SL &&
+                          !XWALK && !FULL && !FT;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     WaveShared &sh = *reinterpret_cast<WaveShared *>(lds_raw);
     constexpr size_t SH_BYTES = LS ? WAVE_SHARED_LS_BYTES : sizeof(WaveShared);
@@ -2110,15 +2127,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     const double *__restrict__ pn = H.nu_line + (unsigned)s_line;
                     const double *__restrict__ pt = H.tau_t + (s_row + (unsigned)s_line);
                     // (experiment: twelve lines per step in the 150-VGPR instantiation, option ls_waves_per_simd = 3; the tables carry 16 lines of slack)
-                    constexpr int CH = (WPE == 3 && !VPK) ? 12 : ((NT == 1 && WPE == 4) ? LS_CHUNK_NT : LS_CHUNK);
+                    // (the instantiations with the block skip: the width of their coarse step)
+                    constexpr int CH = SKIP ? (WPE == 3 ? LS_SKIP_LOADS_12 : LS_SKIP_LOADS_16) : ((WPE == 3 && !VPK) ? 12 : ((NT == 1 && WPE == 4) ? LS_CHUNK_NT : LS_CHUNK));
                     double nl[CH], tl[CH];
                     typedef double nt2 __attribute__((ext_vector_type(2)));
                     const unsigned nt_at = s_row + (unsigned)s_line;
                     const nt2 *__restrict__ pq = reinterpret_cast<const nt2 *>(H.tau_t) + (NT == 2 ? (nt_at & ~7u) : nt_at);
                     const int k0 = NT == 2 ? (int)(nt_at & 7u) : 0;  // entries of the aligned run in front of the current line
                     if constexpr (SKIP) {
-                        // a lane in coarse mode: its ten loads are nine coarse entries from the block of s_line on and the {frequency, prefix sum} entry of the line
-                        // the trace started at -- same registers, same round trip as the fine lanes' ten lines
+                        // a lane in coarse mode: its CH loads are CH - 1 coarse entries from the block of s_line on and the {frequency, prefix sum} entry of the line
+                        // the trace started at -- same registers, same round trip as the fine lanes' CH lines
                         unsigned at = nt_at, last = nt_at + (unsigned)(CH - 1);
                         if (pflags & ssk::MODE_COARSE) {
                             last = W->sk_pn_off + (unsigned)p.shell * (unsigned)(L + 1) + (unsigned)p.next_line_id;
@@ -2154,7 +2172,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                             double hi;
                             const int c = ssk::coarse_scan(nl, tl, comov, s_kp, s_xb, s_tau_event, W->sk_margin, hi);
                             const int b = s_line >> 3;
-                            if (c == ssk::STEP) s_line = (b + ssk::ADVANCE) << 3;
+                            if (c == CH - 1) s_line = (b + (CH - 2)) << 3;  // (all cleared: on from the LAST block, sweep_skip.hpp)
                             else if (c > 0) { s_line = (b + c) << 3; s_tau = hi; pflags ^= ssk::MODE_COARSE | ssk::MODE_INTERVAL; }
                             else {  // the block the trace starts in: fine steps with the exact sum; (never in a later step: its first block was cleared by the one before)
                                 s_line = p.next_line_id; s_tau = 0.0; pflags &= ~ssk::MODE_COARSE;

@@ -5,8 +5,9 @@
 //     ct[s][b] = { nu_last, p_end }      nu_last: the frequency slot of the block's last entry in the interleaved table (-inf for the block that holds
 //                                        line L - 1 and for everything behind it); p_end = pfx[s][min(8 b + 8, L)], pfx the double-double prefix sums
 //                                        of tau_prefix.hpp rounded once (|pfx - P| <= 2^-53 P).
-// A trace that starts at line `start` of block b0 loads STEP = 9 coarse entries from b0 on together with pn[s][start] = {frequency slot of line `start`, pfx[s][start]} -- the ten 16-byte
-// loads of a fine step -- and clears block b when
+// A trace that starts at line `start` of block b0 loads N - 1 coarse entries from b0 on together with pn[s][start] = {frequency slot of line `start`, pfx[s][start]} -- the N 16-byte
+// loads of a fine step of the instantiation: the width N is the kernel's choice (eight in the sixteen-wave form, ten in the twelve-wave one), nothing below depends
+// on it -- and clears block b when
 //     X_last < X_b                       X_last = comov_nu - nu_last
 //     RN(hi_b + x_last) < tau_event      x_last = RN(K' X_last),   hi_b = RN(RN(p_end_b - pfx[start]) + M)
 // in order, stopping at the first block that fails.
@@ -45,9 +46,10 @@
 //
 // What is shared and what is not.  coarse_scan() and interval_take() below are the code the kernel runs, compiled for host and device.  trace(), host only, is a
 // RESTATEMENT of the kernel's step logic around them (propagate_wave.hpp, sweep phase under SKIP: the mode bits, the advance after a coarse step, the fall-back,
-// the exact evaluation) with the lanes taken one at a time: tests/test_sweep_skip_host.py checks the algorithm on it, while the kernel's own glue -- the
+// the exact evaluation) with the lanes taken one at a time: tests/test_sweep_skip_host.py checks the algorithm on it (tests/test_sweep_skip_widths_host.py: at the
+// widths 8, 10 and 12), while the kernel's own glue -- the
 // arithmetic on `adv` that sends a fall-back through the go-on path, the toggle of the mode bits in pflags, the suspension that stores the start of the trace --
-// is covered by tests/test_sweep_skip_gpu.py against the oracle only.  A change to either copy has to be made in both.
+// is covered by tests/test_sweep_skip_gpu.py and tests/test_sweep_skip_widths_gpu.py against the oracle only.  A change to either copy has to be made in both.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -59,9 +61,10 @@
 namespace ssk {
 
 constexpr int BLOCK = 8;        // lines per coarse entry
-constexpr int LOADS = 10;       // 16-byte loads of a step, coarse or fine: the same registers
-constexpr int STEP = 9;         // coarse entries per step; the tenth load is pn[s][start] = {frequency slot of line `start`, pfx[s][start]}
-constexpr int ADVANCE = 8;      // a step that clears all nine goes on from its LAST block, whose hi the next step computes again
+// The width of a step is the instantiation's: N 16-byte loads, coarse or fine (the same registers) -- N - 1 coarse entries, the N-th load is pn[s][start] =
+// {frequency slot of line `start`, pfx[s][start]}; a step that clears all N - 1 goes on from its LAST block (an advance of N - 2 blocks), whose hi the next
+// step computes again.  The host restatement takes it from TraceIn::loads (DEFAULT_LOADS where that is 0), at most MAX_LOADS.
+constexpr int DEFAULT_LOADS = 10, MAX_LOADS = 16;
 constexpr double GAP_FACTOR = 8.0;
 // mode bits of a lane's pflags
 constexpr int MODE_COARSE = 8, MODE_INTERVAL = 16;
@@ -73,11 +76,14 @@ SSK_FN double margin(int n_lines, double rowsum_max)
     return rowsum_max * (1.02 * ((double)n_lines + 16.0) * 0x1p-53 + 0x1p-48);
 }
 
-// One coarse step on its ten loads (x[k], y[k]: entries 0 .. STEP - 1 the coarse ones {nu_last, p_end}, entry STEP = {nu_start, p_start}): the number of leading
-// blocks cleared (0 .. STEP); hi = the bound of the last cleared block.  None if the first line fails X >= 0 (the reference's "nu difference" error, or a close
+// One coarse step on its N loads (entries 0 .. N - 2 the coarse ones {nu_last, p_end}, entry N - 1 = {nu_start, p_start}): the number of leading
+// blocks cleared (0 .. N - 1); hi = the bound of the last cleared block.  None if the first line fails X >= 0 (the reference's "nu difference" error, or a close
 // line: to the exact evaluation).
-SSK_FN int coarse_scan(const double (&nu_last)[LOADS], const double (&p_end)[LOADS], double comov, double kp, double xb, double tau_event, double m, double &hi)
+template <int N>
+SSK_FN int coarse_scan(const double (&nu_last)[N], const double (&p_end)[N], double comov, double kp, double xb, double tau_event, double m, double &hi)
 {
+    static_assert(N >= 3, "at least two coarse entries: a full step advances by N - 2 blocks");
+    constexpr int STEP = N - 1;
     int c = 0;
     const double p_start = p_end[STEP];
     // (X_start < X_b costs a cleared first block nothing -- X_last >= X_start -- and keeps a trace that starts on the last line of the list or behind it,
@@ -122,6 +128,7 @@ struct TraceIn {
     int n_lines, start;
     double nu, comov, chi, tau_event, d_boundary, kp, xb, t_exp, m;
     int force_fallback, skip, fine_chunk;
+    int loads;  // 16-byte loads of a coarse step (coarse_scan's N); 0: DEFAULT_LOADS
 };
 // fb_gap (a trace that fell back on a line): how far tau_event lies below tau_prev + tau_line + chi * distance as the lane's upper bound sees them
 // fb_line, fb_u: the line the fall-back happened at (n_lines: behind the list) and the lane's upper bound of the sum in front of it
@@ -151,10 +158,30 @@ inline int exact_line(int L, double t_exp, int line, double nu_line, double tau_
     return stop_b ? 1 : (stop_e ? 2 : (stop_l ? 3 : (err ? 4 : 0)));
 }
 
+template <int N>
+inline int coarse_scan_n(const double *nl, const double *pe, const TraceIn &in, double &hi)
+{
+    double a[N], b[N];
+    for (int k = 0; k < N; ++k) { a[k] = nl[k]; b[k] = pe[k]; }
+    return coarse_scan<N>(a, b, in.comov, in.kp, in.xb, in.tau_event, in.m, hi);
+}
+// (the widths the kernel's instantiations and the tests use)
+inline int coarse_scan_any(int n, const double *nl, const double *pe, const TraceIn &in, double &hi)
+{
+    switch (n) {
+    case 8: return coarse_scan_n<8>(nl, pe, in, hi);
+    case 9: return coarse_scan_n<9>(nl, pe, in, hi);
+    case 10: return coarse_scan_n<10>(nl, pe, in, hi);
+    case 12: return coarse_scan_n<12>(nl, pe, in, hi);
+    default: __builtin_trap();
+    }
+}
+
 inline TraceOut trace(const TraceIn &in, const double *nu_true)
 {
     TraceOut out{};
     const int L = in.n_lines, CH = in.fine_chunk;
+    const int LOADS = in.loads ? in.loads : DEFAULT_LOADS, STEP = LOADS - 1, ADVANCE = LOADS - 2;
     int mode = in.skip ? MODE_COARSE : 0;
     int s_line = in.start;
     double s_tau = 0.0;
@@ -162,11 +189,11 @@ inline TraceOut trace(const TraceIn &in, const double *nu_true)
     for (;;) {
         if (mode & MODE_COARSE) {
             ++out.coarse_steps;
-            double nl[LOADS], pe[LOADS], hi;
+            double nl[MAX_LOADS], pe[MAX_LOADS], hi;
             const int b = s_line >> 3;
             for (int k = 0; k < STEP; ++k) { nl[k] = in.ct[2 * (b + k)]; pe[k] = in.ct[2 * (b + k) + 1]; }
             nl[STEP] = in.pn[2 * in.start]; pe[STEP] = in.pn[2 * in.start + 1];
-            const int c = coarse_scan(nl, pe, in.comov, in.kp, in.xb, in.tau_event, in.m, hi);
+            const int c = coarse_scan_any(LOADS, nl, pe, in, hi);
             const bool first = s_line == in.start;
             if (c == STEP) s_line = (b + ADVANCE) << 3;
             else if (c > 0) { s_line = (b + c) << 3; s_tau = hi; mode = MODE_INTERVAL; out.interval = 1; }

@@ -237,7 +237,7 @@ struct TardisMcContext {
         DevBuf nt_t;
         bool nt_valid = false, nt_negative = false;  // (nt_negative: the table holds a negative / NaN optical depth -- the lean proof of the NT kernels does not apply)
         unsigned nt_stride = 0;
-        // Block skip of the sixteen-wave lane sweep (sweep_skip.hpp).  Option sweep_skip: -1 automatic, 0 off, 1 on where the plan allows it (plan::plan_sweep_skip).
+        // Block skip of the sixteen-wave and the twelve-wave lane sweep on this table (sweep_skip.hpp).  Option sweep_skip: -1 automatic, 0 off, 1 on where the plan allows it (plan::plan_sweep_skip).
         // Its tables lie behind the interleaved table in nt_t's allocation (the kernel reads all three from one base with 32-bit offsets): the coarse entries
         // ct[shell][block] = {nu_last, p_end}, rows of nt_stride / 8, 16 entries of slack; then pn[shell][0 .. L] = {frequency slot, prefix sum (tau_prefix_kernel)}.  Built by
         // the first propagate call after set_opacity that may use them (sk_valid falls with nt_valid); sk_negative: tau_prefix_kernel's flag; sk_margin: ssk::margin
@@ -380,8 +380,10 @@ struct TardisMcContext {
         }
     } wv;
     struct LaneSweepTuner {
-        // Two instantiations of the lane-sweep kernel: 128 VGPRs / sixteen waves per CU / eight lines per step (A), and 166 VGPRs / twelve waves per CU /
-        // twelve lines per step (B).  A wins where the steady state dominates (1e8 packets of the configs[2] shape: B +3.8 %), B where the drain of a
+        // Two instantiations of the lane-sweep kernel: 128 VGPRs / sixteen waves per CU (A), and 168 VGPRs / twelve waves per CU (B).  On the interleaved table
+        // (the default) both carry the block skip of sweep_skip.hpp, A at eight 16-byte loads per step, coarse or fine, B at ten (propagate_wave.hpp,
+        // LS_SKIP_LOADS_16 / _12; profiles/sweep_skip_widths.txt): the tuner compares two kernels that skip.  On the separate tables A sweeps eight lines per
+        // step and B twelve, neither skips.  A wins where the steady state dominates (1e8 packets of the configs[2] shape: B +3.8 %), B where the drain of a
         // call's longest packets does (1.25e7 packets: -11 %; 1e5-1e6 packets of the tardis_example shape: -6 %; profiles/r05_ls_instantiations.txt):
         // fewer steps per trace shorten the serial chain of a lone packet, and a mostly idle chip does not miss the four waves.  Option
         // ls_waves_per_simd: 4 = A, 3 = B, 0 (default) = the engine times both on the first calls of a given (packet count, tables) and keeps the
@@ -1350,6 +1352,9 @@ int build_screening_tables(TardisMcContext *ctx)
 }
 
 // bytes of the block-skip tables (sweep_skip.hpp) behind the interleaved table: coarse entries with their slack, {frequency, prefix sum} entries
+// (the slack: a coarse step of N loads reads N - 1 coarse entries from the block of its current line on; a trace that starts behind the last line of a list of
+// 8 r lines starts at block r, so the last row's step reads N - 1 entries past the table: 7 and 9 at the widths compiled, 11 at the widest the host test runs,
+// of 16.  A fine step of up to twelve lines from line L reads 12 entries of the interleaved table's 32.)
 size_t skip_table_bytes(const TardisMcContext *ctx)
 {
     const size_t stride = ((size_t)ctx->n_lines + 7) & ~(size_t)7;
@@ -1520,6 +1525,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
             plan::SkipInput room{};
             room.sweep_skip = ctx->sw.sweep_skip; room.lane_sweep = true; room.full_relativity = full; room.full_tracking = ctx->el.track_full;
             room.waves_per_simd = k.waves_per_simd; room.nt = (ctx->sw.sweep_table == 2 && !w.ls3) ? 2 : 1; room.line_scattering = !c.disable_line_scattering;
+            room.twelve_wave_skip = TMC_SWEEP_SKIP_12 != 0;
             rc = build_sweep_table(ctx, plan::plan_sweep_skip(room));
             if (rc) return rc;
             if (ctx->sw.nt_valid && !ctx->sw.nt_negative) {
@@ -1543,6 +1549,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
         si.sweep_skip = ctx->sw.sweep_skip; si.lane_sweep = k.lane_sweep; si.vpk = vpk; si.full_relativity = full; si.wide = w64; si.cross_check = k.xwalk;
         si.shell_log = k.shell_log; si.full_tracking = ctx->el.track_full; si.waves_per_simd = k.waves_per_simd; si.nt = k.nt;
         si.line_scattering = !c.disable_line_scattering; si.nt_negative = ctx->sw.nt_negative; si.pfx_negative = false;
+        si.twelve_wave_skip = TMC_SWEEP_SKIP_12 != 0;
         if (plan::plan_sweep_skip(si)) {
             int rc = build_skip_tables(ctx);
             if (rc) return rc;
