@@ -662,7 +662,7 @@ int tardis_mc_mean_opacity_path(int64_t n_bins);
 
 /* ---- producer of the next iteration's populations: ion and level number densities from (t_rad, W) ------------------------------
  * What the legacy plasma computes between two iterations in its default configuration -- ionization nebular (or lte), excitation
- * dilute-lte (or lte), NLTE excitation only through the section after this one, helium_treatment recomb-nlte and delta_treatment only through tardis_mc_set_ionization_options below, no continuum: LevelBoltzmannFactor, PartitionFunction,
+ * dilute-lte (or lte), NLTE excitation only through the section after this one, helium_treatment recomb-nlte and delta_treatment only through tardis_mc_set_ionization_options below, the continuum rate stage only through tardis_mc_set_continuum_data below: LevelBoltzmannFactor, PartitionFunction,
  * GElectron, PhiSahaLTE / PhiSahaNebular with RadiationFieldCorrection and the interpolated zeta, IonNumberDensity.calculate and
  * LevelNumberDensity -- on the device and in their operation order (fp64, no contraction, exp as the transport evaluates it, every
  * product and sum a rounding of its own).  The populations never leave the device: they are written where tardis_mc_update_opacity's
@@ -791,7 +791,7 @@ int tardis_mc_plasma_update_path(int64_t levels);
  *   lbf[k] = (x[k] g_0) / x[0], g_0 the level_g of the species' first level
  * The stimulated-emission factor needs no change: the existing clamp of negative values is what the reference does for the lines of
  * NLTE species.  NOT covered here: the collision matrix of atomic data with collision_data (the next section
- * adds it); helium_treatment recomb-nlte: tardis_mc_set_ionization_options; not covered at all: NLTE ionization, continuum.
+ * adds it); helium_treatment recomb-nlte: tardis_mc_set_ionization_options; the continuum rate stage: tardis_mc_set_continuum_data; not covered at all: NLTE ionization, continuum transport.
  * Kernels (csrc/nlte_excitation.hpp): a streaming kernel writes r_ul / r_lu of the NLTE lines; then one workgroup per (species, shell)
  * builds and solves the system on a column-major matrix of odd leading dimension, either in its LDS (species of up to 141 levels) or in
  * a slab of HBM per (species, shell) -- same operations, same order, same bits (csrc/nlte_plan.hpp chooses per species).  No workgroup
@@ -955,7 +955,7 @@ int tardis_mc_get_nlte_collision_rates(TardisMcContext *ctx, double *c_ul, doubl
  * hp[.][s], the loads issued in batches ahead of the dependent adds, and writes v once, from the n_e it hands out; a small kernel
  * behind the population kernel copies v over helium's levels of n_t.  With no options installed the instantiation of before runs.  No
  * atomics: two calls give identical bits.  Not covered: helium_treatment numerical-nlte (it reads an external file), NLTE
- * ionisation, continuum. */
+ * ionisation, continuum transport (the photo-ionisation data and the continuum rate stage: tardis_mc_set_continuum_data below). */
 typedef struct TardisMcIonizationOptions {
     int32_t helium_treatment;     /* 0 none, 1 recomb-nlte */
     int32_t use_delta_treatment;  /* 0: RadiationFieldCorrection as documented above; 1: delta = delta_treatment for every ion and shell */
@@ -987,6 +987,113 @@ int tardis_mc_get_helium(TardisMcContext *ctx, double *relative_population, doub
  * out_ionization_ms of tardis_mc_last_plasma_update_ms, whose partition figure excludes this kernel).  TARDIS_MC_ERR_STATE unless
  * the last update ran with helium_treatment. */
 int tardis_mc_last_helium_ms(TardisMcContext *ctx, double *out_relative_ms);
+
+/* ---- photo-ionisation data and the continuum stage of tardis_mc_update_plasma: rate coefficients, chi_bf, the free-free factor ----
+ * What plasma.continuum_interaction.species adds to the legacy plasma, up to the opacity state's continuum fields: the Saha factors, the
+ * photo-ionisation, recombination and collisional-ionisation rate coefficients in the dilute black body, the resident bound-free
+ * opacity table, the free-free factor, and the function that evaluates the continuum opacity at a frequency in a shell.  It restates
+ * SahaFactor, SpontRecombRateCoeff, PhotoIonRateCoeff (dilute Planckian field), StimRecombRateCoeff, CorrPhotoIonRateCoeff,
+ * CollIonRateCoeffSeaton, CollRecombRateCoeff, BoundFreeOpacity, ff_opacity_factor, chi_continuum_calculator / chi_bf_interpolator /
+ * chi_ff_calculator.  Like NLTE it is a property of the installed data: tardis_mc_update_plasma takes no argument for it.  With
+ * continuum data installed the stage runs behind the population stage of a solve that SUCCEEDED, on that update's populations; it reads
+ * nothing of the opacity stages and writes nothing they read; it feeds back into nothing.  A failed electron-density iteration or NLTE
+ * solve returns before it.  Without continuum data no launch of the update changes.  Transport kernels do not read any of this yet.
+ * The radiation field is ALWAYS the dilute black body of the call's t_radiative and dilution_factor, also with j_blues_mode 1: the
+ * engine has no photo-ionisation estimators.
+ * fp64, no contraction, exp the transport's own (mcm::exp); every product, quotient, sum and difference a rounding of its own, in
+ * exactly the order written; the constants of the plasma section (CODATA 2010 cgs) and c = 2.99792458e10.
+ * Per shell:
+ *   t_e = link_t_rad_t_electron t_rad;   beta_e = 1 / (k_B t_e);   beta_rad = 1 / (k_B t_rad)
+ *   x = (((2 pi) m_e) / beta_e) / (h h);   g_ee = x sqrt(x)
+ *   lbf_e[k] = level_g[k] exp(level_energy[k] (-beta_e))      every level: thermal LTE -- no W, no NLTE replacement, no helium treatment
+ *   Z_e[i] = the serial sum of the ion's lbf_e in level order, from 0.0
+ * Per continuum c, its level k in ion i, the upper ion i + 1:
+ *   saha = (Z_e[i+1] / Z_e[i]) ((2 g_ee) exp(chi_i (-beta_e)));   saha == 0.0 becomes DBL_MIN
+ *   phi_ik[c] = lbf_e[k] / (saha Z_e[i])
+ * Per point p of its block, nu = nu[p]:
+ *   bfp[p] = exp((h nu) (-beta_e))
+ *   J[p] = W ((planck_coef ((nu nu) nu)) / (exp((h nu) beta_rad) - 1)),  planck_coef = (2 h) / (c c)   (the opacity stage's dilute black body)
+ *   y_sp[p] = ((((8 pi) x_sect[p]) (nu nu)) / (c c)) bfp[p]
+ *   y_g[p] = J[p] ((((4 pi) x_sect[p]) / nu) / h);   y_st[p] = y_g[p] bfp[p]
+ * Over a block [a, b):  T(y) = the serial sum from 0.0, j = a .. b-2, of ((nu[j+1] - nu[j]) (y[j+1] + y[j])) / 2.0  (numpy.trapz forms the
+ *   same terms and adds them pairwise: agreement with the reference is to rounding, not bitwise, as for the partition functions).
+ * Rates, n_i = the update's population of level k, N_up = N[i+1], n_e the solved electron density:
+ *   alpha_sp = T(y_sp) phi_ik;   gamma = T(y_g);   alpha_stim = T(y_st) phi_ik
+ *   gamma_corr = gamma - ((alpha_stim N_up) n_e) / n_i;  with n_i == 0.0: gamma_corr = gamma (THIS PROJECT'S DECISION: the reference
+ *     divides by zero there); a negative result becomes 0.0 and is counted
+ *   u0 = (nu_i / t_e) (h / k_B), nu_i the block's first frequency;   f = exp(-u0) / u0
+ *   coll_ion = ((f (1.55e13 x_sect[a])) / sqrt(t_e)) gbar,  gbar = 0.1, 0.2, 0.3 for ion_charge[i] 0, 1, >= 2
+ *   coll_recomb = coll_ion phi_ik
+ * Bound-free opacity per point:  n_lte = (phi_ik N_up) n_e;   chi_bf[p] = (n_i - n_lte bfp[p]) x_sect[p];  a negative value becomes
+ *   0.0 and is counted.  THIS PROJECT'S DECISION: the reference raises a PlasmaException on a negative value; a stage that feeds nothing
+ *   must not fail the update, so the count is reported (tardis_mc_get_continuum_opacity) and the caller decides.
+ * Free-free per shell:  q = the serial sum over ALL ion rows, in row order from 0.0, of N_i (ion_charge[i] ion_charge[i]);
+ *   ff_opacity_factor = (n_e q) / sqrt(t_e)
+ * The opacity at a frequency nu in shell s (tardis_mc_continuum_opacity; csrc/continuum_opacity.hpp holds the __device__ function):
+ *   current = the continua c, in ascending c, with nu_min[c] <= nu <= nu_max[c] (a block's first and last frequency)
+ *   per current c, on its block b[0 .. n):  hi = clip(searchsorted(b, nu, side="left"), 1, n - 1);  lo = hi - 1
+ *     interval = b[hi] - b[lo];  hw = nu - b[lo];  lw = b[hi] - nu
+ *     chi_c = ((chi_bf[hi] hw) + (chi_bf[lo] lw)) / interval;   x_c likewise from x_sect
+ *     THIS PROJECT'S DECISION: the clip at 1.  The reference indexes [-1] when nu equals a block's first frequency, a wrap-around
+ *     artefact; here that frequency takes the block's first interval and gives chi_bf[first point].
+ *   chi_bf_tot = the serial sum of chi_c in ascending c, from 0.0
+ *   chi_ff = ((FF_OPAC_CONST ff_opacity_factor[s]) / ((nu nu) nu)) (1 - exp((h nu) (-beta_e[s])))
+ *   FF_OPAC_CONST = sqrt((2 pi) / ((3 m_e) k_B)) ((4 e^6) / (((3 m_e) h) c)) with e = 4.80320451e-10 esu, e^6 = ((((e e) e) e) e) e,
+ *   evaluated once: 3.6923492443190485e+08.
+ * Kernels (csrc/continuum_rates.hpp), ONE form each: a thread per shell (t_e, the free-free factor); the LTE Boltzmann kernel and the
+ * partition kernels of the plasma stage on t_e (both partition forms add in the same order); a streaming kernel over (point, shell)
+ * for bfp and the integrands; a thread per (continuum, shell) that forms phi_ik, walks its block serially and writes the seven rate
+ * tables; a streaming kernel for chi_bf.  The clamps are counted per workgroup and the host adds the counts.  The resident chi_bf is
+ * [NP][S], the shell fastest -- what the getter returns, and the layout in which a reader in shell s touches two rows per current
+ * continuum.  No second form for long blocks is built, hence no tardis_mc_continuum_path.  No atomics: two calls give identical bits.
+ * Not covered: continuum events in transport, photo-ionisation and heating estimators (a "detailed" field for these rates), NLTE
+ * ionisation, collisional excitation, cooling rates, p_fb_deactivation, emissivities, k_packet_idx. */
+typedef struct TardisMcContinuumData {
+    int64_t n_continua;          /* NC >= 1: levels that have a cross-section table */
+    const int64_t *level;        /* [NC] indices into the plasma data's levels, strictly ascending */
+    const int64_t *block_edge;   /* [NC+1] photo_ion_block_references: 0 .. NP, every block >= 2 points */
+    int64_t n_points;            /* NP */
+    const double *nu;            /* [NP] Hz, > 0, strictly ascending inside a block; a block's first nu is the threshold nu_i */
+    const double *x_sect;        /* [NP] cm^2, finite, >= 0 */
+} TardisMcContinuumData;
+
+/* The photo-ionisation data of the resident plasma data; after tardis_mc_set_plasma_data (TARDIS_MC_ERR_STATE before it), dropped by
+ * whatever drops the plasma data (tardis_mc_set_opacity, set_line_data, set_plasma_data) and by nothing else -- tardis_mc_set_nlte_data,
+ * tardis_mc_set_nlte_collision_data and tardis_mc_set_ionization_options keep them; data == NULL removes them.  The call removes what
+ * was installed before it validates: a refused call leaves none.  Everything is checked on the host before anything is indexed or
+ * uploaded (tardis_mc_check_continuum_data). */
+int tardis_mc_set_continuum_data(TardisMcContext *ctx, const TardisMcContinuumData *data);
+/* The host-side check of tardis_mc_set_continuum_data on plain arrays, without a context or a device: n_levels = K and n_ions = I of the
+ * plasma data, ion_level_edge [I + 1], element_ion_edge (it runs from 0 to I).  0 or TARDIS_MC_ERR_INVALID_ARGUMENT, the message
+ * (tardis_mc_last_error(NULL)) naming the rule and the first offending index: a missing pointer or NC < 1; an edge table that does not
+ * run from 0 to NP or a block of fewer than 2 points; a level outside [0, K) or not strictly ascending; a level whose ion is its
+ * element's last ion (there is no upper ion); a nu that is not finite and positive or does not ascend strictly inside its block; an
+ * x_sect that is not finite or is negative. */
+int tardis_mc_check_continuum_data(const TardisMcContinuumData *data, int64_t n_levels, int64_t n_ions, const int64_t *ion_level_edge,
+                                   const int64_t *element_ion_edge);
+/* The rate coefficients of the last successful tardis_mc_update_plasma, [NC,S] each; any pointer may be NULL.  TARDIS_MC_ERR_STATE
+ * unless that update ran the continuum stage and its populations are still resident (whenever tardis_mc_get_plasma answers
+ * TARDIS_MC_ERR_STATE: before any update, after a failed one, after tardis_mc_update_opacity / set_opacity). */
+int tardis_mc_get_continuum_rates(TardisMcContext *ctx, double *phi_ik, double *alpha_sp, double *gamma, double *alpha_stim, double *gamma_corr,
+                                  double *coll_ion, double *coll_recomb);
+/* chi_bf [NP,S], ff_opacity_factor [S], the stage's t_electrons [S] and the two clamp counts of that update; any pointer may be NULL.
+ * The state rule of tardis_mc_get_continuum_rates. */
+int tardis_mc_get_continuum_opacity(TardisMcContext *ctx, double *chi_bf, double *ff_opacity_factor, double *t_electrons,
+                                    int64_t *n_negative_chi_bf, int64_t *n_negative_gamma_corr);
+/* Device time of the stage in the last tardis_mc_update_plasma, in ms: thermal (t_e, the free-free factor, lbf_e, Z_e), points (bfp and
+ * the integrands), rates, opacity (chi_bf).  tardis_mc_last_plasma_update_ms, tardis_mc_last_opacity_update_ms and the other timers keep
+ * their outputs: their figures exclude this stage.  TARDIS_MC_ERR_STATE unless the last update ran the stage. */
+int tardis_mc_last_continuum_ms(TardisMcContext *ctx, double *out_thermal_ms, double *out_points_ms, double *out_rates_ms, double *out_opacity_ms);
+
+typedef struct TardisMcContinuumQuery {
+    int64_t n;  const double *nu;  const int64_t *shell;      /* [n]; nu finite and > 0, shell in [0, S) -- checked on the host */
+    double *chi_bf_tot, *chi_ff;  int64_t *n_current;          /* [n] each, any may be NULL */
+    double *chi_bf_each, *x_sect_each;                         /* [n][NC], 0.0 where c is not current; either may be NULL (tests, small n) */
+} TardisMcContinuumQuery;
+/* The continuum opacity of the resident tables at n (frequency, shell) pairs, a thread per query, through the __device__ function of
+ * csrc/continuum_opacity.hpp.  TARDIS_MC_ERR_INVALID_ARGUMENT, before the device is touched, for a nu that is not finite and positive
+ * or a shell outside [0, S); the state rule of tardis_mc_get_continuum_rates. */
+int tardis_mc_continuum_opacity(TardisMcContext *ctx, const TardisMcContinuumQuery *query);
 
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the

@@ -212,6 +212,32 @@ class TardisMcIonizationOptions(C.Structure):
     ]
 
 
+class TardisMcContinuumData(C.Structure):
+    """The photo-ionisation cross-sections of the continuum stage (tardis_mc_set_continuum_data)."""
+    _fields_ = [
+        ("n_continua", C.c_int64),
+        ("level", _pi),
+        ("block_edge", _pi),
+        ("n_points", C.c_int64),
+        ("nu", _pd),
+        ("x_sect", _pd),
+    ]
+
+
+class TardisMcContinuumQuery(C.Structure):
+    """A batch of (frequency, shell) pairs and where their continuum opacities go (tardis_mc_continuum_opacity)."""
+    _fields_ = [
+        ("n", C.c_int64),
+        ("nu", _pd),
+        ("shell", _pi),
+        ("chi_bf_tot", _pd),
+        ("chi_ff", _pd),
+        ("n_current", _pi),
+        ("chi_bf_each", _pd),
+        ("x_sect_each", _pd),
+    ]
+
+
 IONIZATION_MODES = {"nebular": 0, "lte": 1}
 EXCITATION_MODES = {"dilute-lte": 0, "lte": 1}
 HELIUM_TREATMENTS = {None: 0, "none": 0, "recomb-nlte": 1}
@@ -486,6 +512,41 @@ def marshal_ionization_options(helium_treatment=None, helium_element=None, delta
             element = int(helium_element)
     s = TardisMcIonizationOptions(helium, int(delta_treatment is not None), element, 0.0 if delta_treatment is None else float(delta_treatment))
     return Marshalled(s, [])
+
+
+def marshal_continuum_data(cd) -> Marshalled:
+    """cd: an object with level [NC], block_edge [NC+1], nu and x_sect [NP], e.g. synthetic.ContinuumData.  The counts are taken from
+    the array shapes; what the arrays must hold is the library's to check."""
+    level = np.ascontiguousarray(cd.level, dtype=np.int64)
+    edge = np.ascontiguousarray(cd.block_edge, dtype=np.int64)
+    nu = np.ascontiguousarray(cd.nu, dtype=np.float64)
+    x = np.ascontiguousarray(cd.x_sect, dtype=np.float64)
+    if level.ndim != 1 or edge.shape != (len(level) + 1,):
+        raise ValueError("block_edge must have n_continua + 1 entries")
+    if nu.ndim != 1 or x.shape != nu.shape:
+        raise ValueError("nu and x_sect must be vectors of one length")
+    s = TardisMcContinuumData(len(level), _ip(level), _ip(edge), len(nu), _dp(nu), _dp(x))
+    return Marshalled(s, [level, edge, nu, x])
+
+
+def marshal_continuum_query(nu, shell, n_continua, each=False) -> Marshalled:
+    """The request of tardis_mc_continuum_opacity for the pairs (nu[q], shell[q]); ``m.out`` holds the output arrays: chi_bf_tot,
+    chi_ff, n_current [n] and, with ``each``, chi_bf_each and x_sect_each [n, n_continua]."""
+    nu = np.ascontiguousarray(np.atleast_1d(nu), dtype=np.float64)
+    shell = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(shell), nu.shape), dtype=np.int64)
+    if nu.ndim != 1:
+        raise ValueError("nu must be a vector")
+    n = len(nu)
+    out = {"chi_bf_tot": np.empty(n), "chi_ff": np.empty(n), "n_current": np.empty(n, dtype=np.int64)}
+    if each:
+        out["chi_bf_each"], out["x_sect_each"] = np.empty((n, int(n_continua))), np.empty((n, int(n_continua)))
+    s = TardisMcContinuumQuery()
+    s.n, s.nu, s.shell = n, _dp(nu), _ip(shell)
+    for name, a in out.items():
+        setattr(s, name, _ip(a) if a.dtype == np.int64 else _dp(a))
+    m = Marshalled(s, [nu, shell] + list(out.values()))
+    m.out = out
+    return m
 
 
 def marshal_plasma_update(t_radiative, dilution_factor, n_shells, ionization_mode=0, excitation_mode=0,

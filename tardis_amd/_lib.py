@@ -81,6 +81,12 @@ SYMBOLS = {
     "tardis_mc_check_ionization_options": (_i, [_vp, C.c_int64, _vp, _vp, _vp]),
     "tardis_mc_get_helium": (_i, [_vp, _vp, _vp]),
     "tardis_mc_last_helium_ms": (_i, [_vp, C.POINTER(C.c_double)]),
+    "tardis_mc_set_continuum_data": (_i, [_vp, _vp]),
+    "tardis_mc_check_continuum_data": (_i, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "tardis_mc_get_continuum_rates": (_i, [_vp] * 8),
+    "tardis_mc_get_continuum_opacity": (_i, [_vp] * 4 + [C.POINTER(C.c_int64)] * 2),
+    "tardis_mc_last_continuum_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 4),
+    "tardis_mc_continuum_opacity": (_i, [_vp, _vp]),
     "tardis_mc_set_nlte_data": (_i, [_vp, _vp]),
     "tardis_mc_check_nlte_data": (_i, [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp]),
     "tardis_mc_get_nlte": (_i, [_vp, _vp, _vp]),

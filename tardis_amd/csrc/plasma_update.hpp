@@ -1,6 +1,6 @@
 // plasma_update.hpp -- ion and level populations of the next iteration, solved on the device from (t_rad, W).
 //
-// Restates the legacy plasma's default configuration (ionization nebular or lte, excitation dilute-lte or lte; NLTE excitation: nlte_excitation.hpp; no continuum) in its
+// Restates the legacy plasma's default configuration (ionization nebular or lte, excitation dilute-lte or lte; NLTE excitation: nlte_excitation.hpp; the continuum stage: continuum_rates.hpp) in its
 // operation order: LevelBoltzmannFactorDiluteLTE / LTE, PartitionFunction, GElectron, PhiSahaLTE, PhiSahaNebular with
 // RadiationFieldCorrection and the interpolated zeta, IonNumberDensity.calculate and LevelNumberDensity (fp64, -ffp-contract=off keeps
 // every product and sum a rounding of its own; the formulas are spelled out in include/tardis_mc.h).

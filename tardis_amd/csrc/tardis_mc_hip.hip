@@ -46,6 +46,9 @@
 #include "plasma_update_plan.hpp"
 #include "nlte_excitation.hpp"
 #include "nlte_plan.hpp"
+#include "continuum_rates.hpp"
+#include "continuum_opacity.hpp"
+#include "continuum_plan.hpp"
 
 static_assert(plan::DBG_WAVE_COUNTERS == mc::WV_DBG_FLAGS, "propagate_plan.hpp repeats the wave kernel's list of counter flags");
 
@@ -523,6 +526,17 @@ struct TardisMcContext {
         hipEvent_t ev[2] = {nullptr, nullptr};  // around helium_relative_kernel (tardis_mc_last_helium_ms)
         void release() { release_buffers(hp, v); destroy_events(ev); }
     } he;
+    // Continuum stage (continuum_rates.hpp, continuum_opacity.hpp).  Per set_continuum_data: the continua's levels and ions, the block edges, the
+    // points' continuum, nu, x_sect and the blocks' first and last frequencies.  Per update_plasma: t_e and the free-free factor [S], lbf_e [S][K],
+    // Z_e [I][S], bfp and the three integrands [NP][S], the seven rate tables [7][NC][S], chi_bf [NP][S], the workgroups' clamp counts.
+    struct ContinuumStage {
+        DevBuf level, level_ion, block_edge, point_cont, nu, x_sect, nu_min, nu_max;
+        DevBuf t_e, ff, lbf_e, z_e, bfp, y_sp, y_g, y_st, rates, chi_bf, counts;
+        bool have = false, valid = false, timed = false, ran = false;  // (have: continuum data installed; valid: the tables are those of the last successful update)
+        long long continua = 0, points = 0;
+        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // start | thermal | points | rates | opacity (tardis_mc_last_continuum_ms)
+        void release() { release_buffers(level, level_ion, block_edge, point_cont, nu, x_sect, nu_min, nu_max, t_e, ff, lbf_e, z_e, bfp, y_sp, y_g, y_st, rates, chi_bf, counts); destroy_events(ev); }
+    } ct;
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -955,7 +969,7 @@ void drop_from(TardisMcContext *ctx, Rung rung)
 {
     switch (rung) {
     case RUNG_LINE_DATA: ctx->ou.have = ctx->ou.valid = false; [[fallthrough]];
-    case RUNG_PLASMA_DATA: ctx->pl.have = ctx->pl.valid = false; ctx->he.have = ctx->he.valid = false; [[fallthrough]];  // (the ionisation options sit beside the NLTE data, on the plasma data)
+    case RUNG_PLASMA_DATA: ctx->pl.have = ctx->pl.valid = false; ctx->he.have = ctx->he.valid = false; ctx->ct.have = ctx->ct.valid = false; [[fallthrough]];  // (the ionisation options and the continuum data sit beside the NLTE data, on the plasma data)
     case RUNG_NLTE_DATA: ctx->nl.have = ctx->nl.valid = false; [[fallthrough]];
     case RUNG_COLLISION_DATA: ctx->nc.have = ctx->nc.valid = false;
     }
@@ -2457,7 +2471,7 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
     ctx->ot.release(); ctx->wt.release(); ctx->sc.release(); ctx->sw.release(); ctx->es.release(); ctx->pk.release(); ctx->vl.release(); ctx->el.release();
     ctx->wv.release(); ctx->lt.release(); ctx->rs.release(); ctx->sf.release(); ctx->pg.release();
-    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release(); ctx->he.release(); ctx->mo.release();
+    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release(); ctx->he.release(); ctx->ct.release(); ctx->mo.release();
     ctx->release();
     delete ctx;
 }
@@ -5110,6 +5124,242 @@ int tardis_mc_last_nlte_ms(TardisMcContext *ctx, double *out_assemble_ms, double
     return event_intervals_ms(ctx, ctx->nl.ev, 2, out);
 }
 
+/* ---- continuum stage of update_plasma: photo-ionisation data, rate coefficients, chi_bf, the free-free factor (continuum_rates.hpp) ---- */
+// element_ion_edge runs from 0 to n_ions: the number of its elements, or -1 when it does not get there in ascending steps
+static long long continuum_count_elements(const int64_t *element_ion_edge, int64_t n_ions)
+{
+    if (!element_ion_edge || n_ions < 1 || element_ion_edge[0] != 0) return -1;
+    long long e = 0;
+    while (element_ion_edge[e] < n_ions) {
+        if (e >= n_ions || element_ion_edge[e + 1] <= element_ion_edge[e]) return -1;
+        ++e;
+    }
+    return element_ion_edge[e] == n_ions ? e : -1;
+}
+
+int tardis_mc_check_continuum_data(const TardisMcContinuumData *d, int64_t n_levels, int64_t n_ions, const int64_t *ion_level_edge, const int64_t *element_ion_edge)
+{
+    if (!d) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "continuum data: a pointer is missing");
+    if (!ion_level_edge || !element_ion_edge) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "continuum data: a pointer is missing (the plasma data's edge tables)");
+    const long long n_elements = continuum_count_elements(element_ion_edge, n_ions);
+    if (n_elements < 1) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "continuum data: element_ion_edge must run from 0 to n_ions in ascending steps");
+    const std::string err = cont::check_data((long long)d->n_continua, d->level, d->block_edge, (long long)d->n_points, d->nu, d->x_sect, (long long)n_levels,
+                                             (long long)n_ions, ion_level_edge, n_elements, element_ion_edge);
+    return err.empty() ? TARDIS_MC_OK : fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+}
+
+int tardis_mc_set_continuum_data(TardisMcContext *ctx, const TardisMcContinuumData *d)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->pl.have) return fail(ctx, TARDIS_MC_ERR_STATE, "set_plasma_data must precede set_continuum_data");
+    ctx->ct.have = ctx->ct.valid = false;
+    if (!d) return TARDIS_MC_OK;
+    // everything the kernels index with is checked here, on the host
+    std::vector<int> level_ion((size_t)std::max<int64_t>(d->n_continua, 1));
+    const std::string err = cont::check_data((long long)d->n_continua, d->level, d->block_edge, (long long)d->n_points, d->nu, d->x_sect, ctx->ou.levels,
+                                             (long long)ctx->pl.ions, ctx->pl.h_ion_edge.data(), (long long)ctx->pl.elements, ctx->pl.h_elem_edge.data(),
+                                             d->n_continua >= 1 && d->n_continua <= 0x7ffffff0LL ? level_ion.data() : nullptr);
+    if (!err.empty()) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", err.c_str());
+    const size_t NC = (size_t)d->n_continua, NP = (size_t)d->n_points;
+    std::vector<int> level(NC), edge(NC + 1), point_cont(NP);
+    std::vector<double> nu_min(NC), nu_max(NC);
+    for (size_t c = 0; c <= NC; ++c) edge[c] = (int)d->block_edge[c];
+    for (size_t c = 0; c < NC; ++c) {
+        level[c] = (int)d->level[c];
+        nu_min[c] = d->nu[edge[c]];
+        nu_max[c] = d->nu[edge[c + 1] - 1];
+        for (int p = edge[c]; p < edge[c + 1]; ++p) point_cont[(size_t)p] = (int)c;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->ct.level, level.data(), NC))) return rc;
+    if ((rc = upload(ctx, ctx->ct.level_ion, level_ion.data(), NC))) return rc;
+    if ((rc = upload(ctx, ctx->ct.block_edge, edge.data(), NC + 1))) return rc;
+    if ((rc = upload(ctx, ctx->ct.point_cont, point_cont.data(), NP))) return rc;
+    if ((rc = upload(ctx, ctx->ct.nu, d->nu, NP))) return rc;
+    if ((rc = upload(ctx, ctx->ct.x_sect, d->x_sect, NP))) return rc;
+    if ((rc = upload(ctx, ctx->ct.nu_min, nu_min.data(), NC))) return rc;
+    if ((rc = upload(ctx, ctx->ct.nu_max, nu_max.data(), NC))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vectors are the sources of asynchronous copies)
+    ctx->ct.continua = (long long)NC; ctx->ct.points = (long long)NP;
+    ctx->ct.have = true;
+    return TARDIS_MC_OK;
+}
+
+// The buffers and the events of the continuum stage.  Nothing of a previous update is written to.
+static int continuum_prepare(TardisMcContext *ctx)
+{
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou.levels, I = (size_t)ctx->pl.ions, NC = (size_t)ctx->ct.continua, NP = (size_t)ctx->ct.points;
+    HIP_TRY(ctx, ctx->ct.t_e.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ct.ff.ensure(S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ct.lbf_e.ensure(K * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ct.z_e.ensure(I * S * sizeof(double)));
+    for (DevBuf *b : {&ctx->ct.bfp, &ctx->ct.y_sp, &ctx->ct.y_g, &ctx->ct.y_st, &ctx->ct.chi_bf}) HIP_TRY(ctx, b->ensure(NP * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ct.rates.ensure(7 * NC * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ct.counts.ensure(2 * mc::CONTINUUM_COUNT_BLOCKS * sizeof(int)));
+    return ensure_events(ctx, ctx->ct.ev);
+}
+
+static unsigned continuum_count_blocks(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, mc::CONTINUUM_COUNT_BLOCKS); }
+
+// The continuum stage, enqueued behind the population kernels of a solve that succeeded: it reads the call's (t_rad, W), the update's n_t, N and n_e and
+// writes only its own buffers.
+static int continuum_stage(TardisMcContext *ctx)
+{
+    const size_t S = (size_t)ctx->n_shells, K = (size_t)ctx->ou.levels, I = (size_t)ctx->pl.ions;
+    const long long NC = ctx->ct.continua, NP = ctx->ct.points;
+    double *d_t = ctx->ou.shell.as<double>() + S, *d_w = d_t + S;  // (where plasma_update_enqueue put the call's t_rad and W)
+    const double h = H_PLANCK, c = mc::C_LIGHT;
+    mc::ContinuumArgs a{};
+    a.S = (int)S; a.NC = (int)NC; a.I = (int)I; a.K = (long long)K; a.NP = NP;
+    a.link = ctx->pl.link; a.k_b = K_BOLTZMANN; a.h = h; a.two_pi_me = 2 * M_PI * M_ELECTRON; a.hh = h * h;
+    a.planck_coef = 2 * h / (c * c); a.cc = c * c; a.eight_pi = 8 * M_PI; a.four_pi = 4 * M_PI; a.h_over_k = h / K_BOLTZMANN;
+    a.level = ctx->ct.level.as<int>(); a.level_ion = ctx->ct.level_ion.as<int>(); a.block_edge = ctx->ct.block_edge.as<int>();
+    a.point_cont = ctx->ct.point_cont.as<int>(); a.nu = ctx->ct.nu.as<double>(); a.x_sect = ctx->ct.x_sect.as<double>();
+    a.charge = ctx->pl.charge.as<double>(); a.chi = ctx->pl.chi.as<double>(); a.t_rad = d_t; a.w = d_w;
+    a.lbf_e = ctx->ct.lbf_e.as<double>(); a.z_e = ctx->ct.z_e.as<double>(); a.n_t = ctx->ou.n_t.as<double>(); a.n_ion = ctx->pl.n_ion.as<double>();
+    a.n_e = ctx->pl.n_e.as<double>(); a.t_e = ctx->ct.t_e.as<double>(); a.ff = ctx->ct.ff.as<double>();
+    a.bfp = ctx->ct.bfp.as<double>(); a.y_sp = ctx->ct.y_sp.as<double>(); a.y_g = ctx->ct.y_g.as<double>(); a.y_st = ctx->ct.y_st.as<double>();
+    a.rates = ctx->ct.rates.as<double>(); a.chi_bf = ctx->ct.chi_bf.as<double>(); a.counts = ctx->ct.counts.as<int>();
+    HIP_TRY(ctx, hipEventRecord(ctx->ct.ev[0], ctx->stream));
+    // thermal: t_e and the free-free factor, lbf_e = g exp(E (-beta_e)) (the LTE Boltzmann kernel on t_e), Z_e (the partition kernels of the plasma stage)
+    hipLaunchKernelGGL(mc::continuum_shell_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    const unsigned bx = (unsigned)std::min<size_t>((K + 255) / 256, 1024);
+    hipLaunchKernelGGL(mc::plasma_boltzmann_kernel<false>, dim3(bx, (unsigned)S), dim3(256), 0, ctx->stream, ctx->pl.energy.as<double>(), ctx->pl.g.as<double>(),
+                       ctx->pl.meta.as<int>(), (const double *)a.t_e, (const double *)d_w, (long long)K, K_BOLTZMANN, ctx->ct.lbf_e.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    const long long n_long = ctx->pl.n_long;
+    if (n_long < (long long)I) {
+        const long long n = (long long)I * (long long)S;
+        hipLaunchKernelGGL(mc::plasma_partition_lane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pl.ion_edge.as<int>(), (int)I,
+                           (long long)K, (int)S, ctx->pl.long_rows < 0 ? plup::LONG_ION_LEVELS : ctx->pl.long_rows, (const double *)a.lbf_e, ctx->ct.z_e.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (n_long > 0) {
+        const long long n = n_long * (long long)S * 16;
+        hipLaunchKernelGGL(mc::plasma_partition_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->pl.long_ions.as<int>(), (int)n_long,
+                           ctx->pl.ion_edge.as<int>(), (long long)K, (int)S, (const double *)a.lbf_e, ctx->ct.z_e.as<double>());
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ct.ev[1], ctx->stream));
+    hipLaunchKernelGGL(mc::continuum_point_kernel, dim3((unsigned)std::min<long long>((NP * (long long)S + 255) / 256, 65536)), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ct.ev[2], ctx->stream));
+    hipLaunchKernelGGL(mc::continuum_rate_kernel, dim3(continuum_count_blocks(NC * (long long)S)), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ct.ev[3], ctx->stream));
+    hipLaunchKernelGGL(mc::continuum_chi_kernel, dim3(continuum_count_blocks(NP * (long long)S)), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ct.ev[4], ctx->stream));
+    ctx->ct.ran = true;
+    return TARDIS_MC_OK;
+}
+
+static bool continuum_resident(const TardisMcContext *ctx) { return ctx->ct.valid && ctx->pl.valid; }
+
+int tardis_mc_get_continuum_rates(TardisMcContext *ctx, double *phi_ik, double *alpha_sp, double *gamma, double *alpha_stim, double *gamma_corr, double *coll_ion,
+                                  double *coll_recomb)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!continuum_resident(ctx)) return fail(ctx, TARDIS_MC_ERR_STATE, "get_continuum_rates needs a successful update_plasma that ran the continuum stage");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t n = (size_t)ctx->ct.continua * (size_t)ctx->n_shells;
+    double *const host[7] = {phi_ik, alpha_sp, gamma, alpha_stim, gamma_corr, coll_ion, coll_recomb};
+    std::vector<CopyJob> jobs;
+    for (int v = 0; v < 7; ++v) jobs.push_back({(void *)host[v], ctx->ct.rates.as<double>() + (size_t)v * n, n * sizeof(double)});
+    HIP_TRY(ctx, host_copy(ctx, jobs, false));
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_continuum_opacity(TardisMcContext *ctx, double *chi_bf, double *ff_opacity_factor, double *t_electrons, int64_t *n_negative_chi_bf,
+                                    int64_t *n_negative_gamma_corr)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!continuum_resident(ctx)) return fail(ctx, TARDIS_MC_ERR_STATE, "get_continuum_opacity needs a successful update_plasma that ran the continuum stage");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t S = (size_t)ctx->n_shells, NP = (size_t)ctx->ct.points, NC = (size_t)ctx->ct.continua;
+    HIP_TRY(ctx, host_copy(ctx, {{(void *)chi_bf, ctx->ct.chi_bf.p, NP * S * sizeof(double)},
+                                 {(void *)ff_opacity_factor, ctx->ct.ff.p, S * sizeof(double)},
+                                 {(void *)t_electrons, ctx->ct.t_e.p, S * sizeof(double)}}, false));
+    if (n_negative_chi_bf || n_negative_gamma_corr) {  // the workgroups' counts, added here
+        std::vector<int> counts(2 * (size_t)mc::CONTINUUM_COUNT_BLOCKS);
+        HIP_TRY(ctx, hipMemcpy(counts.data(), ctx->ct.counts.p, counts.size() * sizeof(int), hipMemcpyDeviceToHost));
+        const unsigned blocks[2] = {continuum_count_blocks((long long)(NC * S)), continuum_count_blocks((long long)(NP * S))};
+        int64_t sum[2] = {0, 0};
+        for (int v = 0; v < 2; ++v)
+            for (unsigned b = 0; b < blocks[v]; ++b) sum[v] += counts[(size_t)v * mc::CONTINUUM_COUNT_BLOCKS + b];
+        if (n_negative_gamma_corr) *n_negative_gamma_corr = sum[0];
+        if (n_negative_chi_bf) *n_negative_chi_bf = sum[1];
+    }
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_last_continuum_ms(TardisMcContext *ctx, double *out_thermal_ms, double *out_points_ms, double *out_rates_ms, double *out_opacity_ms)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->ct.timed || !ctx->pl.timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_plasma with a continuum stage has been timed yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double *const out[4] = {out_thermal_ms, out_points_ms, out_rates_ms, out_opacity_ms};
+    return event_intervals_ms(ctx, ctx->ct.ev, 4, out);
+}
+
+int tardis_mc_continuum_opacity(TardisMcContext *ctx, const TardisMcContinuumQuery *q)
+{
+    if (!ctx || !q) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid continuum query");
+    if (!continuum_resident(ctx)) return fail(ctx, TARDIS_MC_ERR_STATE, "continuum_opacity needs a successful update_plasma that ran the continuum stage");
+    if (q->n < 0 || q->n > 0x7ffffff0LL || (q->n > 0 && (!q->nu || !q->shell))) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid continuum query");
+    const size_t n = (size_t)q->n, S = (size_t)ctx->n_shells, NC = (size_t)ctx->ct.continua;
+    // everything the kernel indexes with is checked here, on the host
+    std::vector<int> shell(n);
+    for (size_t e = 0; e < n; ++e) {
+        if (!(std::isfinite(q->nu[e]) && q->nu[e] > 0.0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "continuum query: nu[%zu] = %g is not finite and positive", e, q->nu[e]);
+        if (q->shell[e] < 0 || q->shell[e] >= (int64_t)S)
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "continuum query: shell[%zu] = %lld lies outside [0, %zu)", e, (long long)q->shell[e], S);
+        shell[e] = (int)q->shell[e];
+    }
+    if (n == 0) return TARDIS_MC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ScopedDevBuf d_nu, d_shell, d_tot, d_ff, d_cur, d_chi_each, d_x_each;
+    std::vector<int> current(q->n_current ? n : 0);
+    const int rc = [&]() -> int {
+        int rc1;
+        if ((rc1 = upload(ctx, d_nu, q->nu, n))) return rc1;
+        if ((rc1 = upload(ctx, d_shell, shell.data(), n))) return rc1;
+        if (q->chi_bf_tot) HIP_TRY(ctx, d_tot.ensure(n * sizeof(double)));
+        if (q->chi_ff) HIP_TRY(ctx, d_ff.ensure(n * sizeof(double)));
+        if (q->n_current) HIP_TRY(ctx, d_cur.ensure(n * sizeof(int)));
+        if (q->chi_bf_each) HIP_TRY(ctx, d_chi_each.ensure(n * NC * sizeof(double)));
+        if (q->x_sect_each) HIP_TRY(ctx, d_x_each.ensure(n * NC * sizeof(double)));
+        mc::ContinuumTables t{};
+        t.S = (int)S; t.NC = (int)NC; t.h = H_PLANCK; t.k_b = K_BOLTZMANN;
+        t.block_edge = ctx->ct.block_edge.as<int>(); t.nu = ctx->ct.nu.as<double>(); t.x_sect = ctx->ct.x_sect.as<double>();
+        t.nu_min = ctx->ct.nu_min.as<double>(); t.nu_max = ctx->ct.nu_max.as<double>();
+        t.chi_bf = ctx->ct.chi_bf.as<double>(); t.ff = ctx->ct.ff.as<double>(); t.t_e = ctx->ct.t_e.as<double>();
+        mc::ContinuumQueryArgs k{};
+        k.n = (long long)n; k.nu = d_nu.as<double>(); k.shell = d_shell.as<int>();
+        k.chi_bf_tot = q->chi_bf_tot ? d_tot.as<double>() : nullptr; k.chi_ff = q->chi_ff ? d_ff.as<double>() : nullptr;
+        k.n_current = q->n_current ? d_cur.as<int>() : nullptr;
+        k.chi_each = q->chi_bf_each ? d_chi_each.as<double>() : nullptr; k.x_each = q->x_sect_each ? d_x_each.as<double>() : nullptr;
+        hipLaunchKernelGGL(mc::continuum_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, t, k);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, host_copy(ctx, {{(void *)q->chi_bf_tot, d_tot.p, n * sizeof(double)},
+                                     {(void *)q->chi_ff, d_ff.p, n * sizeof(double)},
+                                     {(void *)(q->n_current ? current.data() : nullptr), d_cur.p, n * sizeof(int)},
+                                     {(void *)q->chi_bf_each, d_chi_each.p, n * NC * sizeof(double)},
+                                     {(void *)q->x_sect_each, d_x_each.p, n * NC * sizeof(double)}}, false));
+        return TARDIS_MC_OK;
+    }();
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (nothing of the call is in flight when its scratch goes)
+    if (rc) return rc;
+    if (q->n_current)
+        for (size_t e = 0; e < n; ++e) q->n_current[e] = current[e];
+    return TARDIS_MC_OK;
+}
+
 // Everything that can refuse the call before the device is touched: the call order, the modes, the shell bound, the bounds of the two temperature tables.
 static int plasma_update_check(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p, const TardisMcOpacityUpdate *u)
 {
@@ -5166,6 +5416,7 @@ static int plasma_update_prepare(TardisMcContext *ctx)
         HIP_TRY(ctx, ctx->he.v.ensure(KH * S * sizeof(double)));
         if ((rc = ensure_events(ctx, ctx->he.ev))) return rc;
     }
+    if (ctx->ct.have && (rc = continuum_prepare(ctx))) return rc;
     return ensure_events(ctx, ctx->nl.ev);
 }
 
@@ -5180,6 +5431,7 @@ static int plasma_update_enqueue(TardisMcContext *ctx, const TardisMcPlasmaUpdat
     int rc;
     ctx->pl.valid = ctx->nl.valid = ctx->nc.valid = ctx->he.valid = false;
     ctx->he.ran = ctx->he.timed = false;
+    ctx->ct.valid = ctx->ct.ran = ctx->ct.timed = false;
     HIP_TRY(ctx, hipMemcpyAsync(d_t, p->t_radiative, S * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_w, p->dilution_factor, S * 8, hipMemcpyHostToDevice, ctx->stream));
     ctx->nl.ran = ctx->nl.timed = ctx->pl.timed = false;  // (ou.timed and the ou.ev events stay the previous update's until this solve has succeeded)
@@ -5303,13 +5555,15 @@ static int plasma_update_install(TardisMcContext *ctx, const TardisMcOpacityUpda
     HIP_TRY(ctx, ctx->ot.n_e.ensure(S * sizeof(double)));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->ot.n_e.p, ctx->pl.n_e.p, S * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->pl.ev[4], ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ou.ev[0], ctx->stream));
     int rc;
+    if (ctx->ct.have && (rc = continuum_stage(ctx))) return rc;  // between the two stages' events: neither timer counts it
+    HIP_TRY(ctx, hipEventRecord(ctx->ou.ev[0], ctx->stream));
     if ((rc = opacity_update_stages(ctx, u))) return rc;
     ctx->pl.timed = ctx->pl.valid = true;
     ctx->nl.ran = ctx->nl.valid = ctx->nl.timed = ctx->nl.have;
     ctx->nc.valid = ctx->nl.have && ctx->nc.have;
     ctx->he.valid = ctx->he.timed = ctx->he.ran;
+    ctx->ct.valid = ctx->ct.timed = ctx->ct.ran;
     return TARDIS_MC_OK;
 }
 

@@ -54,6 +54,8 @@ class Engine:
         self.nlte_data = None        # ... and set_nlte_data() (None after whatever drops the plasma data)
         self.nlte_collision_data = None  # ... and set_nlte_collision_data() (None after whatever drops the NLTE data)
         self.ionization_options = None   # ... and set_ionization_options(): (helium_treatment, helium_element, delta_treatment); None after whatever drops the plasma data
+        self.continuum_data = None       # ... and set_continuum_data(); None after whatever drops the plasma data
+        self.n_continua = self.n_continuum_points = 0
         self.n_helium_levels = 0
         self.n_nlte_collision_pairs = 0
         self.n_nlte_levels = 0
@@ -130,6 +132,7 @@ class Engine:
         self.nlte_data = None
         self.nlte_collision_data = None
         self.ionization_options = None
+        self.continuum_data = None
         self.opacity_generation += 1
         self._check(self._L.tardis_mc_set_opacity(self._h, m.ref()), "set_opacity")
         self.n_lines, self.n_shells = int(m.struct.n_lines), int(m.struct.n_shells)
@@ -148,6 +151,7 @@ class Engine:
         self.nlte_data = None
         self.nlte_collision_data = None
         self.ionization_options = None
+        self.continuum_data = None
         self._check(self._L.tardis_mc_set_line_data(self._h, m.ref()), "set_line_data")
         self.line_data = line_data
 
@@ -247,6 +251,7 @@ class Engine:
         self.nlte_data = None
         self.nlte_collision_data = None
         self.ionization_options = None
+        self.continuum_data = None
         self._check(self._L.tardis_mc_set_plasma_data(self._h, m.ref()), "set_plasma_data")
         self.n_plasma_levels, self.n_ions = int(m.struct.n_levels), int(m.struct.n_ions)
         self.plasma_data = plasma_data
@@ -331,6 +336,73 @@ class Engine:
         a = C.c_double()
         self._check(self._L.tardis_mc_last_helium_ms(self._h, C.byref(a)), "last_helium_ms")
         return {"relative_ms": a.value}
+
+    def set_continuum_data(self, continuum_data):
+        """The photo-ionisation cross-sections of update_plasma()'s continuum stage (`tardis_mc_set_continuum_data`), after
+        set_plasma_data(): an object with the fields of ``synthetic.ContinuumData`` -- the levels that have a cross-section table,
+        the block edges (photo_ion_block_references) and nu / x_sect of every point; what ``plasma.continuum_interaction.species``
+        is to a configuration.  From then on every successful update_plasma() leaves the rate coefficients, chi_bf and the free-free
+        factor of its populations resident (get_continuum_rates, get_continuum_opacity, continuum_opacity); nothing else of the
+        update changes.  None removes the data; whatever drops the plasma data drops them too, set_nlte_data(),
+        set_nlte_collision_data() and set_ionization_options() do not."""
+        self.continuum_data = None
+        if continuum_data is None:
+            self._check(self._L.tardis_mc_set_continuum_data(self._h, None), "set_continuum_data")
+            return
+        m = _abi.marshal_continuum_data(continuum_data)
+        self._check(self._L.tardis_mc_set_continuum_data(self._h, m.ref()), "set_continuum_data")
+        self.n_continua, self.n_continuum_points = int(m.struct.n_continua), int(m.struct.n_points)
+        self.continuum_data = continuum_data
+
+    @staticmethod
+    def check_continuum_data(continuum_data, plasma_data) -> tuple[int, str]:
+        """What set_continuum_data() would say to ``continuum_data`` on ``plasma_data`` (`tardis_mc_check_continuum_data`, host
+        only): (0, "") or (ERR_INVALID_ARGUMENT, the message naming the rule and the first offending index)."""
+        m = _abi.marshal_continuum_data(continuum_data)
+        ion_edge = np.ascontiguousarray(plasma_data.ion_level_edge, dtype=np.int64)
+        elem_edge = np.ascontiguousarray(plasma_data.element_ion_edge, dtype=np.int64)
+        L = _lib.lib()
+        rc = L.tardis_mc_check_continuum_data(m.ref(), int(ion_edge[-1]), len(ion_edge) - 1, ion_edge.ctypes.data, elem_edge.ctypes.data)
+        return int(rc), ("" if rc == 0 else L.tardis_mc_last_error(None).decode())
+
+    CONTINUUM_RATES = ("phi_ik", "alpha_sp", "gamma", "alpha_stim", "gamma_corr", "coll_ion", "coll_recomb")
+
+    def get_continuum_rates(self) -> dict:
+        """The rate coefficients of the last update_plasma() with continuum data (`tardis_mc_get_continuum_rates`): phi_ik,
+        alpha_sp, gamma, alpha_stim, gamma_corr, coll_ion and coll_recomb, [n_continua, n_shells] each."""
+        out = {name: np.empty((self.n_continua, self.n_shells)) for name in self.CONTINUUM_RATES}
+        self._check(self._L.tardis_mc_get_continuum_rates(self._h, *(out[name].ctypes.data for name in self.CONTINUUM_RATES)), "get_continuum_rates")
+        return out
+
+    def get_continuum_opacity(self, chi_bf=True) -> dict:
+        """The opacity tables of the last update_plasma() with continuum data (`tardis_mc_get_continuum_opacity`): chi_bf
+        [n_points, n_shells] (unless ``chi_bf`` is False), ff_opacity_factor and t_electrons [n_shells], and the counts
+        n_negative_chi_bf / n_negative_gamma_corr of the values the stage clamped to 0.0 (the reference raises on the first)."""
+        S = self.n_shells
+        out = {"ff_opacity_factor": np.empty(S), "t_electrons": np.empty(S)}
+        if chi_bf:
+            out["chi_bf"] = np.empty((self.n_continuum_points, S))
+        a, b = C.c_int64(-1), C.c_int64(-1)
+        self._check(self._L.tardis_mc_get_continuum_opacity(self._h, out["chi_bf"].ctypes.data if chi_bf else None, out["ff_opacity_factor"].ctypes.data,
+                                                            out["t_electrons"].ctypes.data, C.byref(a), C.byref(b)), "get_continuum_opacity")
+        out["n_negative_chi_bf"], out["n_negative_gamma_corr"] = int(a.value), int(b.value)
+        return out
+
+    def continuum_opacity(self, nu, shell, each=False) -> dict:
+        """The continuum opacity of the resident tables at the pairs (nu[q], shell[q]) (`tardis_mc_continuum_opacity`; ``shell``
+        may be one number for all): chi_bf_tot, chi_ff and n_current [n]; with ``each`` also chi_bf_each and x_sect_each
+        [n, n_continua], 0.0 where a continuum is not current at the frequency."""
+        q = _abi.marshal_continuum_query(nu, shell, self.n_continua, each)
+        self._check(self._L.tardis_mc_continuum_opacity(self._h, q.ref()), "continuum_opacity")
+        return dict(q.out)
+
+    def last_continuum_ms(self) -> dict:
+        """Device time (ms) of the continuum stage of the last update_plasma(): {"thermal_ms" (t_e, the free-free factor, the
+        thermal Boltzmann factors and partition functions), "points_ms", "rates_ms", "opacity_ms" (chi_bf)}; none of it is in
+        last_plasma_update_ms()."""
+        v = [C.c_double() for _ in range(4)]
+        self._check(self._L.tardis_mc_last_continuum_ms(self._h, *(C.byref(x) for x in v)), "last_continuum_ms")
+        return dict(zip(("thermal_ms", "points_ms", "rates_ms", "opacity_ms"), (x.value for x in v)))
 
     def set_nlte_data(self, nlte_data):
         """The NLTE species of update_plasma() (`tardis_mc_set_nlte_data`), after set_plasma_data(): an object with the fields of
@@ -632,6 +704,7 @@ class Engine:
         self.nlte_data = None
         self.nlte_collision_data = None
         self.ionization_options = None
+        self.continuum_data = None
         self.opacity_generation += 1
         self.results_generation += 1
         self.estimators_generation += 1

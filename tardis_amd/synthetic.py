@@ -596,3 +596,61 @@ def make_nlte_collision_data(seed: int, plasma_data: PlasmaData, nlte_data: Nlte
     for q, m in zip(holes, rng.integers(1, min(3, NT - 1) + 1, len(holes))):
         c_ul[q, :m] = np.nan
     return NlteCollisionData(temps, np.asarray(pair_edge, dtype=np.int64), lower, upper, delta_e, g_ratio, c_ul)
+
+
+H_PLANCK = 6.62606957e-27  # erg s, tardis/constants.py (CODATA 2010, cgs)
+
+
+@dataclass
+class ContinuumData:
+    """The photo-ionisation cross-sections of Engine.set_continuum_data: per level that has a table, a block of (nu, x_sect)
+    points (what ``photoionization_data`` is to the atomic data, with ``photo_ion_block_references`` as block_edge)."""
+    level: np.ndarray        # [NC] indices into the plasma data's levels, strictly ascending
+    block_edge: np.ndarray   # [NC+1]
+    nu: np.ndarray           # [NP] Hz, ascending inside a block; a block's first nu is the threshold
+    x_sect: np.ndarray       # [NP] cm^2
+
+
+def make_continuum_data(seed: int, plasma_data: PlasmaData, n_continua: int, points=(2, 40), levels=None, lengths=None,
+                        x_threshold: float = 6.3e-18, span=(1.5, 6.0)) -> ContinuumData:
+    """Hydrogenic photo-ionisation blocks for ``n_continua`` levels of ``plasma_data``: a level's threshold is its distance to its
+    ion's ionisation energy, nu_i = (chi_i - E_k) / h, and above it x_sect = x0 (nu_i / nu)^3 with x0 = ``x_threshold`` times a
+    log-normal factor, on a geometric grid from nu_i to nu_i times a factor drawn from ``span``.  The levels are drawn (without
+    repetition, then sorted) from those whose ion has an upper ion and that lie below the ionisation energy -- the ground levels of
+    such ions first, so that every charge takes part --, or given as ``levels``; the block lengths are drawn uniformly from
+    ``points`` = (shortest, longest), or given as ``lengths`` (one per continuum, in level order)."""
+    rng = np.random.default_rng(seed + 86028121)
+    edge = np.asarray(plasma_data.ion_level_edge, dtype=np.int64)
+    elem = np.asarray(plasma_data.element_ion_edge, dtype=np.int64)
+    chi = np.asarray(plasma_data.ionization_energy, dtype=np.float64)
+    energy = np.asarray(plasma_data.level_energy, dtype=np.float64)
+    ion = np.repeat(np.arange(len(edge) - 1), np.diff(edge))
+    NC = int(n_continua)
+    if levels is None:
+        last = np.zeros(len(edge) - 1, dtype=bool)
+        last[elem[1:] - 1] = True
+        ok = ~last[ion] & (energy < 0.999 * chi[ion])
+        ground = edge[:-1][~last]
+        ground = ground[ok[ground]]
+        rest = np.setdiff1d(np.flatnonzero(ok), ground)
+        if NC < 1 or NC > len(ground) + len(rest):
+            raise ValueError("n_continua does not fit the levels that can ionise")
+        take = ground[:NC] if NC <= len(ground) else np.concatenate((ground, rng.choice(rest, NC - len(ground), replace=False)))
+        levels = np.sort(take)
+    levels = np.asarray(levels, dtype=np.int64)
+    if len(levels) != NC:
+        raise ValueError("levels must have n_continua entries")
+    if lengths is None:
+        lengths = rng.integers(int(points[0]), int(points[1]) + 1, NC)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    if len(lengths) != NC or np.any(lengths < 2):
+        raise ValueError("lengths must have n_continua entries of at least 2")
+    nu, x = [], []
+    for k, n in zip(levels, lengths):
+        nu_i = (chi[ion[k]] - energy[k]) / H_PLANCK
+        grid = nu_i * np.geomspace(1.0, rng.uniform(*span), int(n))
+        grid[0] = nu_i
+        x0 = x_threshold * 10.0 ** rng.normal(0.0, 0.3)
+        nu.append(grid)
+        x.append(x0 * (nu_i / grid) ** 3)
+    return ContinuumData(levels, np.concatenate(([0], np.cumsum(lengths))).astype(np.int64), np.concatenate(nu), np.concatenate(x))

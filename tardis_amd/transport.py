@@ -390,13 +390,29 @@ class DeviceOpacityState:
                "destination_level_id", "transition_line_id")
     _TABLES = ("tau_sobolev", "transition_probabilities", "beta_sobolev", "stimulated_emission_factor", "j_blues")
 
-    def __init__(self, engine: Engine, base_opacity_state, electron_density):
+    def __init__(self, engine: Engine, base_opacity_state, electron_density, continuum_data=None):
         self._eng = engine
         self._gen = engine.opacity_generation
+        self._continuum = continuum_data is not None
+        # (a handle of an update with the continuum stage has no static t_electrons: it keeps the uploaded state's for the handles after it)
+        self._static_t_electrons = getattr(base_opacity_state, "_static_t_electrons", None)
+        if self._static_t_electrons is None:
+            self._static_t_electrons = base_opacity_state.t_electrons
         for n in self._STATIC:
-            setattr(self, n, getattr(base_opacity_state, n))
+            if n != "t_electrons":
+                setattr(self, n, getattr(base_opacity_state, n))
+            elif not self._continuum:  # (with the continuum stage: the stage's own, fetched with its tables)
+                self.t_electrons = self._static_t_electrons
         self.electron_density = np.ascontiguousarray(electron_density, dtype=np.float64)
         self._cache = {}
+        if self._continuum:  # an update_plasma() that ran the continuum stage: the reference's continuum fields, the static ones from the installed data
+            edge = np.ascontiguousarray(continuum_data.block_edge, dtype=np.int64)
+            self.photo_ion_block_references = edge
+            self.phot_nus = np.ascontiguousarray(continuum_data.nu, dtype=np.float64)
+            self.x_sect = np.ascontiguousarray(continuum_data.x_sect, dtype=np.float64)
+            self.photo_ion_nu_threshold_mins = self.phot_nus[edge[:-1]]
+            self.photo_ion_nu_threshold_maxs = self.phot_nus[edge[1:] - 1]
+            self.bf_threshold_list_nu = self.photo_ion_nu_threshold_mins
 
     def _table(self, name):
         if name not in self._cache:
@@ -410,6 +426,26 @@ class DeviceOpacityState:
     beta_sobolev = property(lambda self: self._table("beta_sobolev"))
     stimulated_emission_factor = property(lambda self: self._table("stimulated_emission_factor"))
     j_blues = property(lambda self: self._table("j_blues"))
+
+    _CONTINUUM_TABLES = ("chi_bf", "ff_opacity_factor", "t_electrons")
+
+    def _continuum_table(self, name):
+        if not self._continuum:
+            raise AttributeError(f"{name}: this update ran without continuum data (set_continuum_data)")
+        if name not in self._cache:
+            if self._gen != self._eng.opacity_generation:
+                raise RuntimeError("the engine's opacity tables were replaced since this update: they are gone")
+            got = self._eng.get_continuum_opacity()
+            self._cache.update({n: got[n] for n in self._CONTINUUM_TABLES})
+        return self._cache[name]
+
+    chi_bf = property(lambda self: self._continuum_table("chi_bf"))
+    ff_opacity_factor = property(lambda self: self._continuum_table("ff_opacity_factor"))
+
+    def __getattr__(self, name):  # (only reached where no instance attribute exists: t_electrons of an update with the continuum stage)
+        if name == "t_electrons" and self.__dict__.get("_continuum"):
+            return self._continuum_table("t_electrons")
+        raise AttributeError(name)
 
 
 class MonteCarloTransportState:
@@ -602,6 +638,7 @@ class MCTransportSolverHIP:
         self.nlte_data = None          # the NLTE species of update_plasma() (set_nlte_data)
         self.nlte_collision_data = None  # their collisional rates (set_nlte_collision_data)
         self.ionization_options = None  # (helium_treatment, helium_element, delta_treatment) of update_plasma() (set_ionization_options)
+        self.continuum_data = None     # the photo-ionisation cross-sections of update_plasma()'s continuum stage (set_continuum_data)
         self._mean_state = None        # what mean_optical_depths() runs on: the last initialize_transport_state()'s geometry ...
         self._mean_opacity = None      # ... and the newest opacity state (that call's, or the handle of a later update)
 
@@ -673,6 +710,21 @@ class MCTransportSolverHIP:
         else:
             self.ionization_options = (helium_treatment, helium_element, delta_treatment)
 
+    def set_continuum_data(self, continuum_data):
+        """The photo-ionisation cross-sections of update_plasma()'s continuum stage (the fields of ``synthetic.ContinuumData`` /
+        ``Engine.set_continuum_data``; what ``plasma.continuum_interaction.species`` is to a configuration); None for none.  They
+        reach the engine as the plasma data do.  With them every update_plasma() leaves the rate coefficients (continuum_rates())
+        and the continuum opacity tables (the handle's ``chi_bf``, ``ff_opacity_factor``; continuum_opacity()) of its populations."""
+        self.continuum_data = continuum_data
+
+    def continuum_rates(self) -> dict:
+        """``Engine.get_continuum_rates`` of the last update_plasma() (``resident=True``)."""
+        return self._eng().get_continuum_rates()
+
+    def continuum_opacity(self, nu, shell, each=False) -> dict:
+        """``Engine.continuum_opacity`` on the tables of the last update_plasma() (``resident=True``)."""
+        return self._eng().continuum_opacity(nu, shell, each)
+
     def _install_nlte(self, eng):
         if eng.nlte_data is not self.nlte_data:
             eng.set_nlte_data(self.nlte_data)
@@ -680,6 +732,8 @@ class MCTransportSolverHIP:
             eng.set_nlte_collision_data(self.nlte_collision_data)
         if eng.ionization_options != self.ionization_options:
             eng.set_ionization_options(*(self.ionization_options or (None, None, None)))
+        if eng.continuum_data is not self.continuum_data:
+            eng.set_continuum_data(self.continuum_data)
 
     def update_plasma(self, t_radiative, dilution_factor, ionization="nebular", excitation="dilute-lte",
                       radiative_rates_type="dilute-blackbody", *, volume=None, w_epsilon=1e-10, time_of_simulation=None):
@@ -714,7 +768,7 @@ class MCTransportSolverHIP:
             eng.update_plasma(t_radiative, dilution_factor, ionization, excitation, 0)
         else:
             raise ValueError(f"unknown radiative_rates_type {radiative_rates_type!r}")
-        handle = DeviceOpacityState(eng, base, eng.get_plasma(False, False, False, True)["electron_density"])
+        handle = DeviceOpacityState(eng, base, eng.get_plasma(False, False, False, True)["electron_density"], eng.continuum_data)
         eng.resident_opacity = handle
         self._mean_opacity = handle
         return handle
