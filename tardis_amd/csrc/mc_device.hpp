@@ -325,7 +325,8 @@ __device__ __forceinline__ bool distance_line(double nu, double r, double mu, do
 // rounded quotient (Markstein, IBM J. Res. Dev. 34, 1990) as long as a, b, y, q0 are finite and nothing over- or
 // underflows; the callers establish that range once per event (div_operands_safe) and otherwise divide normally.
 // 3 VALU instead of ~11, bit-identical to a / b (0 mismatches in 4e8 samples incl. adversarial significands on the
-// host, 2e6 on the device: tests/test_hip_parity.py::test_exact_division).
+// host, 2e6 on the device: tests/test_hip_parity.py::test_exact_division; exponents across all of mid_range and on both
+// sides of its bounds: tests/test_portable_math_gpu.py::test_exact_division_across_the_guarded_range).
 template <bool FAST>
 __device__ __forceinline__ double exact_div(double a, double b, double y)
 {

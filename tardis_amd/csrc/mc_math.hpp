@@ -5,8 +5,20 @@
 // ~1 ulp but are not the correctly rounded value, and neither is any particular libm; to make the per-packet
 // results of the kernels reproducible bit for bit on the host, both are evaluated here with an explicit
 // algorithm built only from +,-,*,fma and table look-ups (compile with -ffp-contract=off).  The result equals
-// the correctly rounded log/exp for all but ~1e-4 of arguments (measured against MPFR-style references:
-// 0 mismatches in 2.4e5 samples).
+// the correctly rounded log/exp for all but an estimated ~1e-4 of arguments.  What is asserted, against an 80-digit
+// reference from Python's `decimal` that shares nothing with the tables (tests/portable_math_ref.py), for the oracle's copy
+// in tests/test_portable_math_host.py and for this one, on the device, in tests/test_portable_math_gpu.py:
+//   * every normal result of 16 argument families (whole domain, next to k ln2/64 and (k + 1/2) ln2/64, all residues
+//     k & 63, the early returns, the table nodes j/64 and their switches, the sqrt(2) split, next to 1, all powers of
+//     two, the kernels' grid k / 2^53) equals the correctly rounded value bit for bit; one true miss is known and listed
+//     there by value, exp(2^-53) = 1 instead of 1 + 2^-52;
+//   * device == oracle bit for bit on all of them, and every generated constant equals its definition.
+//
+// Domain of log: x finite and >= 2^-1022, or exactly 0 (-> -inf).  Subnormal, negative, infinite and NaN arguments return
+// unspecified finite values.  No caller can produce them: mc::Rng::random() is a multiple of 2^-53 below 1, and the product
+// of four pcg_double draws in packet_source.hpp is 0 or at least 2^-212.
+// exp: any argument; NaN -> NaN, overflow -> +inf, deep underflow -> 0.  A result below 2^-1022 may differ from the correctly
+// rounded value by one unit (about 1 % do): the final ldexp rounds the already rounded 53-bit result a second time.
 //
 //   log x : x = 2^e m, m in [sqrt(1/2), sqrt(2));  j = round(64 m), c = j/64;
 //           log x = e ln2 + ln c + log1p((m - c)/c), ln c and 1/c tabulated in double-double.
@@ -30,7 +42,7 @@ __device__ __forceinline__ void two_sum(double a, double b, double &s, double &e
     e = (a - (s - bb)) + (b - bb);
 }
 
-// Domain: x == 0 -> -inf; otherwise x finite, normal, positive (xi in (0,1) in the kernels).
+// Domain: x == 0 -> -inf; otherwise x finite and >= 2^-1022 (see above; anything else returns an unspecified finite value).
 __device__ __forceinline__ double log(double x)
 {
     if (x == 0.0) return -__builtin_huge_val();
