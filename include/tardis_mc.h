@@ -1141,7 +1141,14 @@ int tardis_mc_comm_check(TardisMcContext *ctx, int *out_ranks);
  * op: 0 x+y, 1 x*y, 2 x/y, 3 sqrt(x), 4 log(x) [engine's portable log], 5 exp(x), 6 x*y+x (un-fused),
  *     7 MT19937 doubles of seed (uint32)x[0] (n outputs), 8 floor(x), 9 x/y through the engine's exact 3-fma division;
  *     100 (tests) no arithmetic: the raw 64-byte tracker records the wave-owner kernel left for packets x[0] ... x[0] + n / 8 - 1 of the last
- *     call, 8 doubles each: before_nu, before_mu, before_energy, radius, after_mu, then int32 pairs shell | type, absorb | emit, count | valid. */
+ *     call, 8 doubles each: before_nu, before_mu, before_energy, radius, after_mu, then int32 pairs shell | type, absorb | emit, count | valid.
+ *     101 (tests) no arithmetic: n doubles, from its double x[1] on, of the resident prefix-sum table x[0] as the kernels read it (x: two doubles, y unused):
+ *         0  the v-packet screening's prefix sums tau_pfx[S][L + 1]            1  its row sums tau_rowsum[S]
+ *         2  the block skip's pn[S][L + 1] = {frequency slot, prefix sum}, two doubles per entry
+ *         3  its coarse entries ct[S][ceil(L / 8)] = {nu_last, p_end} with the 16 slack entries behind the last row, two doubles per entry
+ *         4  its row sums sk_rowsum[S]                                        5  {its margin M, 1.0 if its builder saw a negative or non-finite depth, the padded row length}
+ *     TARDIS_MC_ERR_STATE when no propagate call has built that table for the resident opacity state (0, 1: a call that screens v-packets; 2 - 5: a call
+ *     whose plan allows the block skip), TARDIS_MC_ERR_INVALID_ARGUMENT for a range that leaves the table. */
 int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const double *y, double *out, int64_t n);
 /* The elimination and back substitution of the blocked form of the NLTE solve on dense systems, for tests: m [n_systems][n][n]
  * row-major, b [n_systems][n]; x [n_systems][n] (rows of a failed system are 0.0) and status [n_systems] (0, 1 + the step of a zero or

@@ -50,6 +50,8 @@
 // widths 8, 10 and 12), while the kernel's own glue -- the
 // arithmetic on `adv` that sends a fall-back through the go-on path, the toggle of the mode bits in pflags, the suspension that stores the start of the trace --
 // is covered by tests/test_sweep_skip_gpu.py and tests/test_sweep_skip_widths_gpu.py against the oracle only.  A change to either copy has to be made in both.
+// The host test builds its own prefix sums (one serial two-sum per row); those and the device's pn / ct / margin as the kernel reads them are held to the same exact
+// sums and to the layout above by tests/test_prefix_tables_host.py and tests/test_prefix_tables_gpu.py, which also run both copies on tables with a large M.
 #pragma once
 
 #if defined(__HIPCC__)

@@ -5725,6 +5725,35 @@ int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const do
         HIP_TRY(ctx, hipMemcpy(out, (const char *)ctx->pk.li_rec.p + (size_t)first * 64, (size_t)count * 64, hipMemcpyDeviceToHost));
         return TARDIS_MC_OK;
     }
+    if (op == 101) {  // tests: the resident prefix-sum tables as the kernels read them (tau_prefix.hpp, sweep_skip.hpp): n doubles of table x[0] from its double x[1] on
+        const long long which = (long long)x[0], first = (long long)x[1];
+        const long long S = ctx->n_shells, L = ctx->n_lines;
+        const bool screening = ctx->sc.pfx_valid && ctx->sc.tau_pfx.p && ctx->sc.tau_rowsum.p;
+        const bool skip = ctx->sw.nt_valid && ctx->sw.sk_valid && ctx->sw.nt_t.p && ctx->sw.sk_rowsum.p;
+        const double host[3] = {ctx->sw.sk_margin, ctx->sw.sk_negative ? 1.0 : 0.0, (double)ctx->sw.nt_stride};
+        const char *src = nullptr;  // (device; table 5 comes from the context)
+        long long size = 0;         // doubles
+        bool valid = false;
+        switch (which) {
+        case 0: valid = screening; src = (const char *)ctx->sc.tau_pfx.p; size = S * (L + 1); break;
+        case 1: valid = screening; src = (const char *)ctx->sc.tau_rowsum.p; size = S; break;
+        case 2: valid = skip; src = (const char *)ctx->sw.nt_t.p + (size_t)ctx->sw.sk_pn_off * 16; size = 2 * S * (L + 1); break;
+        case 3: valid = skip; src = (const char *)ctx->sw.nt_t.p + (size_t)ctx->sw.sk_ct_off * 16; size = 2 * ((long long)(ctx->sw.nt_stride / 8) * S + 16); break;
+        case 4: valid = skip; src = (const char *)ctx->sw.sk_rowsum.p; size = S; break;
+        case 5: valid = skip; size = 3; break;
+        default: return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "debug_eval: op 101 has no table %lld", which);
+        }
+        if (!valid) return fail(ctx, TARDIS_MC_ERR_STATE, "debug_eval: table %lld of op 101 is not built for the resident opacity state", which);
+        if (first < 0 || first > size || n > size - first)
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "debug_eval: doubles [%lld, %lld) of table %lld, which holds %lld", first, first + (long long)n, which, size);
+        if (which == 5) {
+            for (int64_t i = 0; i < n; ++i) out[i] = host[first + i];
+            return TARDIS_MC_OK;
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(out, src + (size_t)first * 8, (size_t)n * 8, hipMemcpyDeviceToHost));
+        return TARDIS_MC_OK;
+    }
     ScopedDevBuf dx, dy, dout, scratch;
     size_t nx = (op == 7) ? 1 : (size_t)n;
     HIP_TRY(ctx, dx.ensure(nx * 8));

@@ -14,7 +14,8 @@
 // needs exp(-tau) of the reference's own sum), is traced line by line (vp_trace / vp_shell_step, unchanged).  Two 8-byte reads per
 // shell crossing instead of ~40 optical depths.
 //
-// P is accumulated in double-double (two-sum; -ffp-contract=off) and rounded once: |P^ - P| <= 2^-53 P.  Margin of one crossing
+// P is accumulated in double-double (two-sum; -ffp-contract=off) and rounded once: |P^ - P| <= 2^-53 P (held to exact sums, up to the 2^-70 P the low word's
+// own roundings may add, by tests/test_prefix_tables_gpu.py on the resident table: profiles/prefix_tables.txt).  Margin of one crossing
 // (n lines, all tau >= 0 -- a negative optical depth anywhere switches the screening off):
 //     |serial - exact| <= 1.01 n 2^-53 (chi d + seg)        (standard bound of recursive summation)
 //     |(P^[e] - P^[start]) - seg| <= 2^-53 (P[e] + P[start]) + 2^-53 seg <= 2^-52 rowsum + 2^-53 seg

@@ -963,6 +963,17 @@ class Engine:
         self._check(self._L.tardis_mc_debug_eval(self._h, op, x.ctypes.data, yp, out.ctypes.data, n), "debug_eval")
         return out
 
+    PREFIX_TABLES = ("tau_pfx", "tau_rowsum", "pn", "ct", "sk_rowsum", "sk_state")
+
+    def debug_prefix_table(self, name: str) -> np.ndarray:
+        """A resident prefix-sum table as the kernels read it (op 101 of `tardis_mc_debug_eval`, tests): "tau_pfx" [S, L + 1] and "tau_rowsum" [S]
+        of the v-packet screening; "pn" [S, L + 1, 2] = {frequency slot, prefix sum}, "ct" [S * ceil(L / 8) + 16, 2] = {nu_last, p_end}, "sk_rowsum" [S]
+        and "sk_state" = [margin, negative, padded row length] of the block skip.  Raises when no propagate call has built the table."""
+        S, L = self.n_shells, self.n_lines
+        shape = {"tau_pfx": (S, L + 1), "tau_rowsum": (S,), "pn": (S, L + 1, 2), "ct": (S * ((L + 7) // 8) + 16, 2), "sk_rowsum": (S,), "sk_state": (3,)}[name]
+        out = self.debug_eval(101, [self.PREFIX_TABLES.index(name), 0], n=int(np.prod(shape)))
+        return out.reshape(shape)
+
     def debug_nlte_solve(self, m, b):
         """The blocked form of the NLTE solve on dense systems (`tardis_mc_debug_nlte_solve`): m [systems, n, n], b [systems, n] ->
         (x [systems, n], status [systems]: 0, 1 + the step of a bad pivot, n + 1 for x[0] == 0, n + 2 for an x that is not finite)."""

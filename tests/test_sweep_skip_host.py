@@ -142,11 +142,10 @@ extern "C" int plan_skip(int sweep_skip, int lane_sweep, int vpk, int full_relat
 _d, _i, _pi, _pd = C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)
 
 
-@pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    d = tmp_path_factory.mktemp("sweep_skip")
+def load_shim(d, source=SHIM):
+    """The shim compiled in directory `d` and bound (`source`: SHIM, or SHIM with more entry points behind it -- tests/test_prefix_tables_host.py)."""
     src, lib = d / "shim.cpp", d / "libssk.so"
-    src.write_text(SHIM)
+    src.write_text(source)
     subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I", CSRC, str(src), "-o", str(lib)], check=True)
     L = C.CDLL(str(lib))
     L.build_tables.restype, L.build_tables.argtypes = _d, [C.c_void_p, C.c_void_p, _i, _i, _d]
@@ -157,6 +156,11 @@ def shim(tmp_path_factory):
     L.kprime.restype, L.kprime.argtypes = _d, [_d, _d, _d]
     L.plan_skip.restype, L.plan_skip.argtypes = _i, [_i] * 13
     return L
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    return load_shim(tmp_path_factory.mktemp("sweep_skip"))
 
 
 N_SHELLS = 4
