@@ -1047,7 +1047,8 @@ int tardis_mc_last_helium_ms(TardisMcContext *ctx, double *out_relative_ms);
  * [NP][S], the shell fastest -- what the getter returns, and the layout in which a reader in shell s touches two rows per current
  * continuum.  No second form for long blocks is built, hence no tardis_mc_continuum_path.  No atomics: two calls give identical bits.
  * Not covered: continuum events in transport, photo-ionisation and heating estimators (a "detailed" field for these rates), NLTE
- * ionisation, collisional excitation, cooling rates, p_fb_deactivation, emissivities, k_packet_idx. */
+ * ionisation, collisional excitation, p_fb_deactivation (the cooling rates, the free-bound emission CDFs and the k-packet samplers:
+ * the section after this one). */
 typedef struct TardisMcContinuumData {
     int64_t n_continua;          /* NC >= 1: levels that have a cross-section table */
     const int64_t *level;        /* [NC] indices into the plasma data's levels, strictly ascending */
@@ -1094,6 +1095,83 @@ typedef struct TardisMcContinuumQuery {
  * csrc/continuum_opacity.hpp.  TARDIS_MC_ERR_INVALID_ARGUMENT, before the device is touched, for a nu that is not finite and positive
  * or a shell outside [0, S); the state rule of tardis_mc_get_continuum_rates. */
 int tardis_mc_continuum_opacity(TardisMcContext *ctx, const TardisMcContinuumQuery *query);
+
+/* ---- the cooling sub-stage behind the continuum stage: cooling rates, free-bound emission CDFs, the k-packet table and its samplers ----
+ * What a continuum event needs when a packet's energy becomes thermal: what the k-packet turns into, and at which frequency it comes
+ * back.  It restates SpontRecombCoolingRateCoeff, FreeBoundEmissionCDF, FreeBoundCoolingRate, CollIonCooling, FreeFreeCoolingRate,
+ * AdiabaticCoolingRate, the cumulative cooling table of the k-packet and the samplers sample_nu_free_bound / sample_nu_free_free.  The
+ * sub-stage runs whenever the continuum stage runs, behind its chi_bf kernel and on its tables (bfp, y_sp, phi_ik, coll_ion, t_e) and
+ * that update's populations; it writes only its own tables and feeds back into nothing.  Without continuum data no launch of the update
+ * changes; with them every output the update had keeps its bits.  Transport kernels do not read any of this yet.
+ * The rules of the section above: fp64, no contraction, mcm::exp and mcm::log for the two transcendental functions; every product,
+ * quotient, sum and difference a rounding of its own, in exactly the order written; every sum a serial sum from 0.0; the constants of
+ * the plasma section and c = 2.99792458e10.
+ * Per point p of continuum c (level k, ion i, upper ion i + 1, block [a, b), nu_i = nu[a]), nu = nu[p], shell s:
+ *   y_cool[p] = (y_sp[p] (h nu)) (1.0 - nu_i / nu)        (SpontRecombCoolingRateCoeff: 8 pi x h nu^3 / c^2 (1 - nu_i / nu) e^(-h nu / k T_e))
+ *   y_em[p] = (((nu nu) nu) x_sect[p]) bfp[p]             (FreeBoundEmissionCDF: the prefactors dropped, only ratios matter)
+ * Per (continuum, shell), T the serial trapezoid of the section above:
+ *   c_fb_sp = T(y_cool) phi_ik
+ *   E[a] = 0.0;  E[j+1] = E[j] + ((nu[j+1] - nu[j]) (y_em[j+1] + y_em[j])) / 2.0;   fb_emission_cdf[p] = E[p] / E[b-1]
+ *     THIS PROJECT'S DECISION: where E[b-1] is not positive and finite, the block's CDF is 0.0 at every point but the last and 1.0 at
+ *     the last, and the case is counted (n_degenerate_fb_cdf).  The reference produces NaN there.  Such a continuum has
+ *     cool_rate_fb == 0.0 wherever bfp underflowed, and is then never chosen.
+ *   cool_rate_fb = (c_fb_sp N_up) n_e                                   (FreeBoundCoolingRate)
+ *   cool_rate_coll_ion = ((coll_ion n_e) n_i) (h nu_i)                  (CollIonCooling)
+ * Per shell, q the free-free sum of the section above, time_explosion that of the resident geometry:
+ *   cool_rate_ff = ((C0_FF n_e) sqrt(t_e)) q,  C0_FF = 1.426e-27        (FreeFreeCoolingRate)
+ *   cool_rate_adiabatic = (((3.0 n_e) k_B) t_e) / time_explosion        (AdiabaticCoolingRate)
+ * The k-packet table k_cdf [2 + 2 NC][S], the shell fastest; its entries in this order: ff, adiabatic, cool_rate_fb[0 .. NC),
+ *   cool_rate_coll_ion[0 .. NC).  R[j] = the serial running sum from 0.0;  cool_rate_total = R[last];  k_cdf[j] = R[j] / cool_rate_total,
+ *   so the last entry is exactly 1.0.  A successful solve has n_e > 0, so the adiabatic entry makes the total positive.
+ *   THIS PROJECT'S DECISION: collisional-excitation cooling is NOT in the table.  It needs a coll_exc_coeff for every line, a data rung
+ *   the plasma does not have; it is the next entry to add.
+ * The samplers (csrc/kpacket_sample.hpp holds the __device__ functions; z a random number in [0, 1)):
+ *   process(shell, z):  j = min(searchsorted(k_cdf[:, s], z, side="right"), last): entry j is chosen iff k_cdf[j-1] <= z < k_cdf[j], so
+ *     an entry of zero rate is never chosen.  kind = 0 ff (j = 0), 1 adiabatic (j = 1), 2 fb (continuum j - 2), 3 coll_ion (continuum
+ *     j - 2 - NC); continuum = -1 for kinds 0 and 1.
+ *   nu_free_bound(c, shell, z), numpy.interp on the block:  hi = clip(searchsorted(cdf_block, z, side="right"), 1, n - 1);  lo = hi - 1
+ *     nu = nu[lo] + ((z - cdf[lo]) (nu[hi] - nu[lo])) / (cdf[hi] - cdf[lo]);  for z in [0, 1) the denominator is positive, also in a
+ *     degenerate block (there every z gives a frequency of the block's last interval).
+ *   nu_free_free(shell, z) = (-((k_B t_e) / h)) log(z);  z == 0.0 gives +inf, as in the reference.  (mcm::log's domain is 0 and the
+ *     normal numbers: a subnormal z gives an unspecified finite frequency, on the device and in the oracle alike.)
+ * Kernels (csrc/cooling_rates.hpp), ONE form each: a streaming kernel over (point, shell) for the two integrands; a thread per
+ * (continuum, shell), the shell fastest, that walks its block twice -- T(y_cool) and E[b-1] first, then E[p] again, in the same order and
+ * so with the same bits, written as the quotient -- and writes c_fb_sp, the two rate tables and the normalised CDF; a thread per shell
+ * that forms q, the two shell rates and walks the 2 + 2 NC entries twice in the same way.  The degenerate CDFs are counted per workgroup
+ * and the host adds the counts.  The tables are [rows][S] with adjacent lanes on adjacent shells; the samplers' bisections read a column
+ * and stride by S.  No second form for long blocks is built (the reason of the section above; profiles/cooling_rates.txt has the times).
+ * No atomics: two calls give identical bits.
+ * Not covered: collisional-excitation cooling and the coll_exc_coeff data it needs; the macro-atom continuum transition probabilities
+ * (p_fb_deactivation, the recombination / photo-ionisation / collisional rows); the choice of the absorbing continuum at a bound-free
+ * event; the photo-ionisation and heating estimators; NLTE ionisation; any reader of these tables in the propagation kernels. */
+
+/* c_fb_sp, cool_rate_fb, cool_rate_coll_ion [NC,S] and cool_rate_ff, cool_rate_adiabatic, cool_rate_total [S] of the last successful
+ * tardis_mc_update_plasma; any pointer may be NULL.  The state rule of tardis_mc_get_continuum_rates: what drops or keeps the continuum
+ * data and its tables drops or keeps these. */
+int tardis_mc_get_cooling_rates(TardisMcContext *ctx, double *c_fb_sp, double *cool_rate_fb, double *cool_rate_coll_ion, double *cool_rate_ff,
+                                double *cool_rate_adiabatic, double *cool_rate_total);
+/* fb_emission_cdf [NP,S], k_cdf [2+2NC,S] and the count of degenerate CDFs of that update; any pointer may be NULL.  The state rule of
+ * tardis_mc_get_continuum_rates. */
+int tardis_mc_get_kpacket_tables(TardisMcContext *ctx, double *fb_emission_cdf, double *k_cdf, int64_t *n_degenerate_fb_cdf);
+/* Device time of the sub-stage in the last tardis_mc_update_plasma, in ms, per kernel: points (the two integrands), blocks (c_fb_sp, the
+ * two rate tables, the CDFs), table (the shell rates and k_cdf).  Every other timer keeps its outputs: tardis_mc_last_continuum_ms,
+ * tardis_mc_last_plasma_update_ms and tardis_mc_last_opacity_update_ms exclude the sub-stage.  TARDIS_MC_ERR_STATE unless the last update
+ * ran the continuum stage. */
+int tardis_mc_last_cooling_ms(TardisMcContext *ctx, double *out_points_ms, double *out_blocks_ms, double *out_table_ms);
+
+typedef struct TardisMcKpacketQuery {
+    int64_t n;  const int64_t *shell;  const double *z_process, *z_nu;   /* [n]; shell in [0, S), both z finite and in [0, 1) -- checked on the host */
+    int64_t *kind, *continuum;  double *nu;                               /* [n] each, any may be NULL */
+    const int64_t *force_kind, *force_continuum;                          /* [n] or NULL: -1 means sample (tests reach every block with them) */
+} TardisMcKpacketQuery;
+/* n k-packets on the resident tables, a thread per query, through the __device__ functions of csrc/kpacket_sample.hpp: (kind, continuum)
+ * = process(shell, z_process), then nu = nu_free_free(shell, z_nu) for kind 0, nu_free_bound(continuum, shell, z_nu) for kind 2, and 0.0
+ * for kinds 1 and 3.  With force_kind[q] in 0 .. 3 the kind is that one and z_process[q] is not used; kinds 2 and 3 then take
+ * force_continuum[q], which must lie in [0, NC); wherever no continuum is forced (force_kind[q] of -1, 0 or 1) force_continuum[q] must
+ * be -1 (or the array NULL).  TARDIS_MC_ERR_INVALID_ARGUMENT, before the device is touched, for a shell outside [0, S), a z that is not
+ * finite or lies outside [0, 1), a force_kind outside [-1, 3] and a forced continuum outside [0, NC); the state rule of
+ * tardis_mc_get_continuum_rates. */
+int tardis_mc_kpacket_sample(TardisMcContext *ctx, const TardisMcKpacketQuery *query);
 
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the

@@ -238,6 +238,22 @@ class TardisMcContinuumQuery(C.Structure):
     ]
 
 
+class TardisMcKpacketQuery(C.Structure):
+    """A batch of k-packets and where their processes and frequencies go (tardis_mc_kpacket_sample)."""
+    _fields_ = [
+        ("n", C.c_int64),
+        ("shell", _pi),
+        ("z_process", _pd),
+        ("z_nu", _pd),
+        ("kind", _pi),
+        ("continuum", _pi),
+        ("nu", _pd),
+        ("force_kind", _pi),
+        ("force_continuum", _pi),
+    ]
+
+
+KPACKET_KINDS = {"ff": 0, "adiabatic": 1, "fb": 2, "coll_ion": 3}
 IONIZATION_MODES = {"nebular": 0, "lte": 1}
 EXCITATION_MODES = {"dilute-lte": 0, "lte": 1}
 HELIUM_TREATMENTS = {None: 0, "none": 0, "recomb-nlte": 1}
@@ -545,6 +561,31 @@ def marshal_continuum_query(nu, shell, n_continua, each=False) -> Marshalled:
     for name, a in out.items():
         setattr(s, name, _ip(a) if a.dtype == np.int64 else _dp(a))
     m = Marshalled(s, [nu, shell] + list(out.values()))
+    m.out = out
+    return m
+
+
+def marshal_kpacket_query(shell, z_process, z_nu, force_kind=None, force_continuum=None) -> Marshalled:
+    """The request of tardis_mc_kpacket_sample for the k-packets (shell[q], z_process[q], z_nu[q]); ``shell`` may be one number for
+    all.  ``force_kind`` (one number or [n]; -1 samples) sets the kind, and ``force_continuum`` (likewise; -1 where none is forced) the
+    continuum of kinds 2 and 3.  ``m.out`` holds the output arrays: kind, continuum (int64) and nu [n]."""
+    z_process = np.ascontiguousarray(np.atleast_1d(z_process), dtype=np.float64)
+    if z_process.ndim != 1:
+        raise ValueError("z_process must be a vector")
+    z_nu = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(z_nu), z_process.shape), dtype=np.float64)
+    shell = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(shell), z_process.shape), dtype=np.int64)
+    n = len(z_process)
+    out = {"kind": np.empty(n, dtype=np.int64), "continuum": np.empty(n, dtype=np.int64), "nu": np.empty(n)}
+    keep = [shell, z_process, z_nu] + list(out.values())
+    s = TardisMcKpacketQuery()
+    s.n, s.shell, s.z_process, s.z_nu = n, _ip(shell), _dp(z_process), _dp(z_nu)
+    s.kind, s.continuum, s.nu = _ip(out["kind"]), _ip(out["continuum"]), _dp(out["nu"])
+    if force_kind is not None or force_continuum is not None:
+        fk = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(-1 if force_kind is None else force_kind), z_process.shape), dtype=np.int64)
+        fc = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(-1 if force_continuum is None else force_continuum), z_process.shape), dtype=np.int64)
+        s.force_kind, s.force_continuum = _ip(fk), _ip(fc)
+        keep += [fk, fc]
+    m = Marshalled(s, keep)
     m.out = out
     return m
 

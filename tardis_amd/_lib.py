@@ -87,6 +87,10 @@ SYMBOLS = {
     "tardis_mc_get_continuum_opacity": (_i, [_vp] * 4 + [C.POINTER(C.c_int64)] * 2),
     "tardis_mc_last_continuum_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 4),
     "tardis_mc_continuum_opacity": (_i, [_vp, _vp]),
+    "tardis_mc_get_cooling_rates": (_i, [_vp] * 7),
+    "tardis_mc_get_kpacket_tables": (_i, [_vp] * 3 + [C.POINTER(C.c_int64)]),
+    "tardis_mc_last_cooling_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 3),
+    "tardis_mc_kpacket_sample": (_i, [_vp, _vp]),
     "tardis_mc_set_nlte_data": (_i, [_vp, _vp]),
     "tardis_mc_check_nlte_data": (_i, [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp]),
     "tardis_mc_get_nlte": (_i, [_vp, _vp, _vp]),

@@ -49,6 +49,8 @@
 #include "continuum_rates.hpp"
 #include "continuum_opacity.hpp"
 #include "continuum_plan.hpp"
+#include "cooling_rates.hpp"
+#include "kpacket_sample.hpp"
 
 static_assert(plan::DBG_WAVE_COUNTERS == mc::WV_DBG_FLAGS, "propagate_plan.hpp repeats the wave kernel's list of counter flags");
 
@@ -537,6 +539,14 @@ struct TardisMcContext {
         hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // start | thermal | points | rates | opacity (tardis_mc_last_continuum_ms)
         void release() { release_buffers(level, level_ion, block_edge, point_cont, nu, x_sect, nu_min, nu_max, t_e, ff, lbf_e, z_e, bfp, y_sp, y_g, y_st, rates, chi_bf, counts); destroy_events(ev); }
     } ct;
+    // Cooling sub-stage behind the continuum stage (cooling_rates.hpp, kpacket_sample.hpp), per update_plasma: the two integrands and the emission CDF
+    // [NP][S], c_fb_sp / cool_rate_fb / cool_rate_coll_ion [3][NC][S], cool_rate_ff / adiabatic / total [3][S], k_cdf [2 + 2 NC][S], the workgroups'
+    // counts of degenerate CDFs.  It has no flags of its own: it runs whenever the continuum stage runs, and ct.valid / ct.timed speak for both.
+    struct CoolingStage {
+        DevBuf y_cool, y_em, fb_cdf, rates, shell, k_cdf, counts;
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start | points | blocks | table (tardis_mc_last_cooling_ms)
+        void release() { release_buffers(y_cool, y_em, fb_cdf, rates, shell, k_cdf, counts); destroy_events(ev); }
+    } ck;
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -2471,7 +2481,7 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
     ctx->ot.release(); ctx->wt.release(); ctx->sc.release(); ctx->sw.release(); ctx->es.release(); ctx->pk.release(); ctx->vl.release(); ctx->el.release();
     ctx->wv.release(); ctx->lt.release(); ctx->rs.release(); ctx->sf.release(); ctx->pg.release();
-    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release(); ctx->he.release(); ctx->ct.release(); ctx->mo.release();
+    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release(); ctx->he.release(); ctx->ct.release(); ctx->ck.release(); ctx->mo.release();
     ctx->release();
     delete ctx;
 }
@@ -5197,10 +5207,44 @@ static int continuum_prepare(TardisMcContext *ctx)
     for (DevBuf *b : {&ctx->ct.bfp, &ctx->ct.y_sp, &ctx->ct.y_g, &ctx->ct.y_st, &ctx->ct.chi_bf}) HIP_TRY(ctx, b->ensure(NP * S * sizeof(double)));
     HIP_TRY(ctx, ctx->ct.rates.ensure(7 * NC * S * sizeof(double)));
     HIP_TRY(ctx, ctx->ct.counts.ensure(2 * mc::CONTINUUM_COUNT_BLOCKS * sizeof(int)));
+    // the cooling sub-stage behind it (cooling_rates.hpp)
+    for (DevBuf *b : {&ctx->ck.y_cool, &ctx->ck.y_em, &ctx->ck.fb_cdf}) HIP_TRY(ctx, b->ensure(NP * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ck.rates.ensure(3 * NC * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ck.shell.ensure(3 * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ck.k_cdf.ensure((2 + 2 * NC) * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->ck.counts.ensure(mc::CONTINUUM_COUNT_BLOCKS * sizeof(int)));
+    int rc;
+    if ((rc = ensure_events(ctx, ctx->ck.ev))) return rc;
     return ensure_events(ctx, ctx->ct.ev);
 }
 
 static unsigned continuum_count_blocks(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, mc::CONTINUUM_COUNT_BLOCKS); }
+
+// The cooling sub-stage, enqueued behind the continuum stage's last kernel and event: it reads that stage's bfp, y_sp, phi_ik, coll_ion and t_e, the update's
+// n_t, N and n_e and the geometry's time_explosion, and writes only its own buffers.
+static int cooling_stage(TardisMcContext *ctx, const mc::ContinuumArgs &c)
+{
+    const long long ncs = (long long)c.NC * c.S;
+    mc::CoolingArgs a{};
+    a.S = c.S; a.NC = c.NC; a.I = c.I; a.K = c.K; a.NP = c.NP;
+    a.h = c.h; a.k_b = c.k_b; a.time_explosion = ctx->t_exp;
+    a.level = c.level; a.level_ion = c.level_ion; a.block_edge = c.block_edge; a.point_cont = c.point_cont; a.nu = c.nu; a.x_sect = c.x_sect;
+    a.charge = c.charge; a.bfp = c.bfp; a.y_sp = c.y_sp; a.phi_ik = c.rates; a.coll_ion = c.rates + 5 * ncs; a.t_e = c.t_e;
+    a.n_t = c.n_t; a.n_ion = c.n_ion; a.n_e = c.n_e;
+    a.y_cool = ctx->ck.y_cool.as<double>(); a.y_em = ctx->ck.y_em.as<double>(); a.rates = ctx->ck.rates.as<double>(); a.fb_cdf = ctx->ck.fb_cdf.as<double>();
+    a.shell = ctx->ck.shell.as<double>(); a.k_cdf = ctx->ck.k_cdf.as<double>(); a.counts = ctx->ck.counts.as<int>();
+    HIP_TRY(ctx, hipEventRecord(ctx->ck.ev[0], ctx->stream));
+    hipLaunchKernelGGL(mc::cooling_point_kernel, dim3((unsigned)std::min<long long>((a.NP * (long long)a.S + 255) / 256, 65536)), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ck.ev[1], ctx->stream));
+    hipLaunchKernelGGL(mc::cooling_block_kernel, dim3(continuum_count_blocks(ncs)), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ck.ev[2], ctx->stream));
+    hipLaunchKernelGGL(mc::cooling_table_kernel, dim3((unsigned)((a.S + 63) / 64)), dim3(64), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ck.ev[3], ctx->stream));
+    return TARDIS_MC_OK;
+}
 
 // The continuum stage, enqueued behind the population kernels of a solve that succeeded: it reads the call's (t_rad, W), the update's n_t, N and n_e and
 // writes only its own buffers.
@@ -5252,6 +5296,8 @@ static int continuum_stage(TardisMcContext *ctx)
     hipLaunchKernelGGL(mc::continuum_chi_kernel, dim3(continuum_count_blocks(NP * (long long)S)), dim3(256), 0, ctx->stream, a);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ct.ev[4], ctx->stream));
+    int rc;
+    if ((rc = cooling_stage(ctx, a))) return rc;  // behind the stage's last event: tardis_mc_last_continuum_ms does not count it
     ctx->ct.ran = true;
     return TARDIS_MC_OK;
 }
@@ -5357,6 +5403,114 @@ int tardis_mc_continuum_opacity(TardisMcContext *ctx, const TardisMcContinuumQue
     if (rc) return rc;
     if (q->n_current)
         for (size_t e = 0; e < n; ++e) q->n_current[e] = current[e];
+    return TARDIS_MC_OK;
+}
+
+/* ---- cooling sub-stage behind the continuum stage: cooling rates, emission CDFs, the k-packet table and its samplers (cooling_rates.hpp, kpacket_sample.hpp) ---- */
+int tardis_mc_get_cooling_rates(TardisMcContext *ctx, double *c_fb_sp, double *cool_rate_fb, double *cool_rate_coll_ion, double *cool_rate_ff,
+                                double *cool_rate_adiabatic, double *cool_rate_total)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!continuum_resident(ctx)) return fail(ctx, TARDIS_MC_ERR_STATE, "get_cooling_rates needs a successful update_plasma that ran the continuum stage");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t S = (size_t)ctx->n_shells, n = (size_t)ctx->ct.continua * S;
+    double *const per_continuum[3] = {c_fb_sp, cool_rate_fb, cool_rate_coll_ion};
+    double *const per_shell[3] = {cool_rate_ff, cool_rate_adiabatic, cool_rate_total};
+    std::vector<CopyJob> jobs;
+    for (int v = 0; v < 3; ++v) jobs.push_back({(void *)per_continuum[v], ctx->ck.rates.as<double>() + (size_t)v * n, n * sizeof(double)});
+    for (int v = 0; v < 3; ++v) jobs.push_back({(void *)per_shell[v], ctx->ck.shell.as<double>() + (size_t)v * S, S * sizeof(double)});
+    HIP_TRY(ctx, host_copy(ctx, jobs, false));
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_kpacket_tables(TardisMcContext *ctx, double *fb_emission_cdf, double *k_cdf, int64_t *n_degenerate_fb_cdf)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!continuum_resident(ctx)) return fail(ctx, TARDIS_MC_ERR_STATE, "get_kpacket_tables needs a successful update_plasma that ran the continuum stage");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t S = (size_t)ctx->n_shells, NP = (size_t)ctx->ct.points, NC = (size_t)ctx->ct.continua;
+    HIP_TRY(ctx, host_copy(ctx, {{(void *)fb_emission_cdf, ctx->ck.fb_cdf.p, NP * S * sizeof(double)},
+                                 {(void *)k_cdf, ctx->ck.k_cdf.p, (2 + 2 * NC) * S * sizeof(double)}}, false));
+    if (n_degenerate_fb_cdf) {  // the workgroups' counts, added here
+        std::vector<int> counts((size_t)mc::CONTINUUM_COUNT_BLOCKS);
+        HIP_TRY(ctx, hipMemcpy(counts.data(), ctx->ck.counts.p, counts.size() * sizeof(int), hipMemcpyDeviceToHost));
+        int64_t sum = 0;
+        for (unsigned b = 0; b < continuum_count_blocks((long long)(NC * S)); ++b) sum += counts[b];
+        *n_degenerate_fb_cdf = sum;
+    }
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_last_cooling_ms(TardisMcContext *ctx, double *out_points_ms, double *out_blocks_ms, double *out_table_ms)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->ct.timed || !ctx->pl.timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no update_plasma with a continuum stage has been timed yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double *const out[3] = {out_points_ms, out_blocks_ms, out_table_ms};
+    return event_intervals_ms(ctx, ctx->ck.ev, 3, out);
+}
+
+int tardis_mc_kpacket_sample(TardisMcContext *ctx, const TardisMcKpacketQuery *q)
+{
+    if (!ctx || !q) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid k-packet query");
+    if (!continuum_resident(ctx)) return fail(ctx, TARDIS_MC_ERR_STATE, "kpacket_sample needs a successful update_plasma that ran the continuum stage");
+    if (q->n < 0 || q->n > 0x7ffffff0LL || (q->n > 0 && (!q->shell || !q->z_process || !q->z_nu))) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid k-packet query");
+    const size_t n = (size_t)q->n, S = (size_t)ctx->n_shells;
+    const int64_t NC = (int64_t)ctx->ct.continua;
+    // everything the kernel indexes with is checked here, on the host
+    std::vector<int> shell(n), force_kind(q->force_kind ? n : 0), force_continuum(q->force_kind ? n : 0);
+    for (size_t e = 0; e < n; ++e) {
+        if (q->shell[e] < 0 || q->shell[e] >= (int64_t)S)
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "k-packet query: shell[%zu] = %lld lies outside [0, %zu)", e, (long long)q->shell[e], S);
+        shell[e] = (int)q->shell[e];
+        if (!(q->z_process[e] >= 0.0 && q->z_process[e] < 1.0))
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "k-packet query: z_process[%zu] = %g lies outside [0, 1)", e, q->z_process[e]);
+        if (!(q->z_nu[e] >= 0.0 && q->z_nu[e] < 1.0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "k-packet query: z_nu[%zu] = %g lies outside [0, 1)", e, q->z_nu[e]);
+        const int64_t kind = q->force_kind ? q->force_kind[e] : -1, forced = q->force_continuum ? q->force_continuum[e] : -1;
+        if (kind < -1 || kind > 3) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "k-packet query: force_kind[%zu] = %lld lies outside [-1, 3]", e, (long long)kind);
+        if (kind >= 2 && (forced < 0 || forced >= NC))
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "k-packet query: force_continuum[%zu] = %lld lies outside [0, %lld)", e, (long long)forced, (long long)NC);
+        if (kind < 2 && forced != -1)
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "k-packet query: force_continuum[%zu] = %lld, but force_kind[%zu] = %lld has no continuum to force (-1)", e,
+                        (long long)forced, e, (long long)kind);
+        if (q->force_kind) { force_kind[e] = (int)kind; force_continuum[e] = (int)forced; }
+    }
+    if (n == 0) return TARDIS_MC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ScopedDevBuf d_shell, d_zp, d_zn, d_fk, d_fc, d_kind, d_cont, d_nu;
+    std::vector<int> kind(q->kind ? n : 0), cont(q->continuum ? n : 0);
+    const int rc = [&]() -> int {
+        int rc1;
+        if ((rc1 = upload(ctx, d_shell, shell.data(), n))) return rc1;
+        if ((rc1 = upload(ctx, d_zp, q->z_process, n))) return rc1;
+        if ((rc1 = upload(ctx, d_zn, q->z_nu, n))) return rc1;
+        if (q->force_kind && (rc1 = upload(ctx, d_fk, force_kind.data(), n))) return rc1;
+        if (q->force_kind && (rc1 = upload(ctx, d_fc, force_continuum.data(), n))) return rc1;
+        if (q->kind) HIP_TRY(ctx, d_kind.ensure(n * sizeof(int)));
+        if (q->continuum) HIP_TRY(ctx, d_cont.ensure(n * sizeof(int)));
+        if (q->nu) HIP_TRY(ctx, d_nu.ensure(n * sizeof(double)));
+        mc::KpacketTables t{};
+        t.S = (int)S; t.NC = (int)NC; t.h = H_PLANCK; t.k_b = K_BOLTZMANN;
+        t.block_edge = ctx->ct.block_edge.as<int>(); t.nu = ctx->ct.nu.as<double>(); t.fb_cdf = ctx->ck.fb_cdf.as<double>();
+        t.k_cdf = ctx->ck.k_cdf.as<double>(); t.t_e = ctx->ct.t_e.as<double>();
+        mc::KpacketQueryArgs k{};
+        k.n = (long long)n; k.shell = d_shell.as<int>(); k.z_process = d_zp.as<double>(); k.z_nu = d_zn.as<double>();
+        k.force_kind = q->force_kind ? d_fk.as<int>() : nullptr; k.force_continuum = q->force_kind ? d_fc.as<int>() : nullptr;
+        k.kind = q->kind ? d_kind.as<int>() : nullptr; k.continuum = q->continuum ? d_cont.as<int>() : nullptr; k.nu = q->nu ? d_nu.as<double>() : nullptr;
+        hipLaunchKernelGGL(mc::kpacket_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, t, k);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, host_copy(ctx, {{(void *)(q->kind ? kind.data() : nullptr), d_kind.p, n * sizeof(int)},
+                                     {(void *)(q->continuum ? cont.data() : nullptr), d_cont.p, n * sizeof(int)},
+                                     {(void *)q->nu, d_nu.p, n * sizeof(double)}}, false));
+        return TARDIS_MC_OK;
+    }();
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (nothing of the call is in flight when its scratch goes)
+    if (rc) return rc;
+    for (size_t e = 0; e < n && q->kind; ++e) q->kind[e] = kind[e];
+    for (size_t e = 0; e < n && q->continuum; ++e) q->continuum[e] = cont[e];
     return TARDIS_MC_OK;
 }
 

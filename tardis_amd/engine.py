@@ -404,6 +404,51 @@ class Engine:
         self._check(self._L.tardis_mc_last_continuum_ms(self._h, *(C.byref(x) for x in v)), "last_continuum_ms")
         return dict(zip(("thermal_ms", "points_ms", "rates_ms", "opacity_ms"), (x.value for x in v)))
 
+    COOLING_RATES = ("c_fb_sp", "cool_rate_fb", "cool_rate_coll_ion")
+    COOLING_SHELL_RATES = ("cool_rate_ff", "cool_rate_adiabatic", "cool_rate_total")
+
+    def get_cooling_rates(self) -> dict:
+        """The cooling rates of the last update_plasma() with continuum data (`tardis_mc_get_cooling_rates`): c_fb_sp, cool_rate_fb
+        and cool_rate_coll_ion [n_continua, n_shells]; cool_rate_ff, cool_rate_adiabatic and cool_rate_total [n_shells].
+        Collisional-excitation cooling is not part of the total."""
+        out = {name: np.empty((self.n_continua, self.n_shells)) for name in self.COOLING_RATES}
+        out.update({name: np.empty(self.n_shells) for name in self.COOLING_SHELL_RATES})
+        self._check(self._L.tardis_mc_get_cooling_rates(self._h, *(out[name].ctypes.data for name in self.COOLING_RATES + self.COOLING_SHELL_RATES)),
+                    "get_cooling_rates")
+        return out
+
+    def get_kpacket_tables(self, fb_emission_cdf=True) -> dict:
+        """The tables the k-packet samplers read (`tardis_mc_get_kpacket_tables`): fb_emission_cdf [n_points, n_shells] (unless
+        ``fb_emission_cdf`` is False), k_cdf [2 + 2 n_continua, n_shells] -- its entries: ff, adiabatic, the continua's free-bound
+        rates, their collisional-ionisation rates -- and n_degenerate_fb_cdf, the number of (continuum, shell) whose emission integral
+        was not positive and finite (their CDF is 0.0 up to the last point and 1.0 there; the reference produces NaN)."""
+        S = self.n_shells
+        out = {"k_cdf": np.empty((2 + 2 * self.n_continua, S))}
+        if fb_emission_cdf:
+            out["fb_emission_cdf"] = np.empty((self.n_continuum_points, S))
+        a = C.c_int64(-1)
+        self._check(self._L.tardis_mc_get_kpacket_tables(self._h, out["fb_emission_cdf"].ctypes.data if fb_emission_cdf else None, out["k_cdf"].ctypes.data,
+                                                         C.byref(a)), "get_kpacket_tables")
+        out["n_degenerate_fb_cdf"] = int(a.value)
+        return out
+
+    def kpacket_sample(self, shell, z_process, z_nu, force_kind=None, force_continuum=None) -> dict:
+        """What the k-packets (shell[q], z_process[q], z_nu[q]) turn into on the resident tables (`tardis_mc_kpacket_sample`; ``shell``
+        may be one number for all): kind (0 ff, 1 adiabatic, 2 fb, 3 coll_ion; ``_abi.KPACKET_KINDS``), continuum (-1 for kinds 0 and 1)
+        and nu [n] -- the free-free or free-bound frequency at z_nu for kinds 0 and 2, 0.0 for kinds 1 and 3.  Both z lie in [0, 1).
+        ``force_kind`` / ``force_continuum`` (one number or [n], -1: sample) set the kind and, for kinds 2 and 3, the continuum."""
+        q = _abi.marshal_kpacket_query(shell, z_process, z_nu, force_kind, force_continuum)
+        self._check(self._L.tardis_mc_kpacket_sample(self._h, q.ref()), "kpacket_sample")
+        return dict(q.out)
+
+    def last_cooling_ms(self) -> dict:
+        """Device time (ms) of the cooling sub-stage of the last update_plasma(), per kernel: {"points_ms" (the two integrands),
+        "blocks_ms" (c_fb_sp, the rate tables, the emission CDFs), "table_ms" (the shell rates and k_cdf)}; none of it is in
+        last_continuum_ms() or last_plasma_update_ms()."""
+        v = [C.c_double() for _ in range(3)]
+        self._check(self._L.tardis_mc_last_cooling_ms(self._h, *(C.byref(x) for x in v)), "last_cooling_ms")
+        return dict(zip(("points_ms", "blocks_ms", "table_ms"), (x.value for x in v)))
+
     def set_nlte_data(self, nlte_data):
         """The NLTE species of update_plasma() (`tardis_mc_set_nlte_data`), after set_plasma_data(): an object with the fields of
         ``synthetic.NlteData`` -- the species' ions, their lines in the line list with A_ul, B_ul and B_lu, and the flags

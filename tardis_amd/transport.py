@@ -442,6 +442,21 @@ class DeviceOpacityState:
     chi_bf = property(lambda self: self._continuum_table("chi_bf"))
     ff_opacity_factor = property(lambda self: self._continuum_table("ff_opacity_factor"))
 
+    _KPACKET_TABLES = ("fb_emission_cdf", "k_cdf")
+
+    def _kpacket_table(self, name):  # (the cooling sub-stage's tables: one fetch of their own, under the same rule)
+        if not self._continuum:
+            raise AttributeError(f"{name}: this update ran without continuum data (set_continuum_data)")
+        if name not in self._cache:
+            if self._gen != self._eng.opacity_generation:
+                raise RuntimeError("the engine's opacity tables were replaced since this update: they are gone")
+            got = self._eng.get_kpacket_tables()
+            self._cache.update({n: got[n] for n in self._KPACKET_TABLES})
+        return self._cache[name]
+
+    fb_emission_cdf = property(lambda self: self._kpacket_table("fb_emission_cdf"))
+    k_cdf = property(lambda self: self._kpacket_table("k_cdf"))
+
     def __getattr__(self, name):  # (only reached where no instance attribute exists: t_electrons of an update with the continuum stage)
         if name == "t_electrons" and self.__dict__.get("_continuum"):
             return self._continuum_table("t_electrons")
@@ -724,6 +739,14 @@ class MCTransportSolverHIP:
     def continuum_opacity(self, nu, shell, each=False) -> dict:
         """``Engine.continuum_opacity`` on the tables of the last update_plasma() (``resident=True``)."""
         return self._eng().continuum_opacity(nu, shell, each)
+
+    def cooling_rates(self) -> dict:
+        """``Engine.get_cooling_rates`` of the last update_plasma() (``resident=True``)."""
+        return self._eng().get_cooling_rates()
+
+    def kpacket_sample(self, shell, z_process, z_nu, force_kind=None, force_continuum=None) -> dict:
+        """``Engine.kpacket_sample`` on the tables of the last update_plasma() (``resident=True``)."""
+        return self._eng().kpacket_sample(shell, z_process, z_nu, force_kind, force_continuum)
 
     def _install_nlte(self, eng):
         if eng.nlte_data is not self.nlte_data:
