@@ -242,6 +242,10 @@ const char *tardis_mc_last_error(const TardisMcContext *ctx);   /* ctx may be NU
  * csrc/sweep_skip.hpp; -1, the default: automatic; 0 off; 1 on where the call allows it -- partial relativity, 32-bit table offsets, line scattering
  * enabled, no negative or non-finite optical depth, not the shell-sorted log or the cross-check instantiations.  Results do not depend on it;
  * tardis_mc_last_sweep_skip tells what a call ran with; debug flag 536870912 (tests) makes every skipped trace fall back to the line-by-line sweep),
+ * "sweep_start_held" (calls whose lane sweeps run with "sweep_skip" only, ignored elsewhere: 1: an emission that a hot sector of the macro-atom walk decided
+ * reads its line's frequency from the skip's {frequency, prefix sum} table together with the neighbouring entry, the start entry of the trace that
+ * follows, and that trace's coarse steps do not load the entry again; 0: the frequency is read from the interleaved table and every trace loads its
+ * start entry; -1, the default: automatic, on where the call's sweeps skip.  Results and work counters do not depend on it),
  * "log_tail_split" (1, the default: a call whose line-visit log fits one epoch is split where the drain of its longest-lived packets
  * begins -- "log_tail_packets" (8) packets' worth of traces per lane before the estimated end -- so that the estimator passes over
  * the bulk run beside the drain; 0 off), "log_chunk_records" (records per chunk of the log's pool, <= 4096 by default),

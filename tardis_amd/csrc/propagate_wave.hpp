@@ -187,6 +187,9 @@ struct WaveCold {
     int sweep_skip;
     unsigned sk_ct_off, sk_pn_off;
     double sk_margin;
+    // 1 (option sweep_start_held, only where sweep_skip is on): an emission decided by a hot sector of the walk reads its line's frequency from the {frequency,
+    // prefix sum} table together with the next entry, the start entry of the coming trace, which the lane keeps (ssk::MODE_START_HELD).  Wave-uniform
+    int sweep_start_held;
 };
 
 __global__ void __launch_bounds__(64) late_list_kernel(const LaneSave *__restrict__ save, const WaveSave *__restrict__ wsave, int waves, long long first, long long end,
@@ -868,7 +871,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     constexpr bool RNGC = LS && !VPK;
     // SKIP: the sweep may clear whole 8-line blocks on the coarse table (sweep_skip.hpp) where W->sweep_skip says so: the sixteen-wave and the twelve-wave
     // instantiation on the interleaved table only.  The mode of a trace is two bits of pflags (ssk::MODE_COARSE: the next step is a coarse one; ssk::MODE_INTERVAL:
-    // s_tau is an upper bound).  These instantiations run LS_SKIP_LOADS_16 / LS_SKIP_LOADS_12 loads per step, skipping or not.
+    // s_tau is an upper bound) and, where W->sweep_start_held says so, a third (ssk::MODE_START_HELD: the lane brought the start entry of its trace along from the
+    // walk's read of the emission line).  These instantiations run LS_SKIP_LOADS_16 / LS_SKIP_LOADS_12 loads per step, skipping or not.
     constexpr bool SKIP = TMC_SWEEP_SKIP != 0 && LS && !VPK && NT == 1 && ((WPE == 4 && TMC_STRAIGHT_A == 0) || (WPE == 3 && TMC_SWEEP_SKIP_12 != 0)) && !WIDE && !SL &&
                           !XWALK && !FULL && !FT;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1164,7 +1168,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             v.trk_nu = sh.nu[lane]; v.trk_mu = sh.rcp_nu[lane]; v.trk_energy = sh.comov_nu[lane];
             if constexpr (SKIP) {  // a trace in coarse or interval mode is stored as its start: it takes the same path again (sweep_skip.hpp)
                 if (s_active && (pflags & (ssk::MODE_COARSE | ssk::MODE_INTERVAL))) {
-                    v.s_line = p.next_line_id; v.s_tau = 0.0; v.pflags = (pflags & ~ssk::MODE_INTERVAL) | ssk::MODE_COARSE;
+                    v.s_line = p.next_line_id; v.s_tau = 0.0; v.pflags = (pflags & ~(ssk::MODE_INTERVAL | ssk::MODE_START_HELD)) | ssk::MODE_COARSE;  // (the start entry: loaded again)
                 }
             }
             suspended = true;
@@ -1425,10 +1429,27 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                 } else if (nxt == 2) {
                     const int2 bt = gload(P.blk_tab + nxt_arg);
                     mb0 = bt.x; mb1 = bt.y;
-                } else if (nxt == 3)
-                    emit_nu_walk = (NT != 0 && emit < L - 1) ? glob(P.nt_t)[2u * ((unsigned)p.shell * P.nt_stride + (unsigned)emit)]
-                                                             : glob(P.nu_line)[(unsigned)emit];  // (the sector the coming sweep starts in; the interleaved table
-                                                                                                  // holds -inf in the frequency slot of the last line)
+                } else if (nxt == 3) {
+                    if constexpr (SKIP) {
+                        // The coming trace starts at line emit + 1 with a coarse step, which reads nothing of the interleaved table but the entry pn[shell][emit + 1] =
+                        // {frequency slot, prefix sum} of its first line.  pn[shell][emit].x is the double nt_t[shell][emit].x holds, and the two entries are
+                        // neighbours (one 64-byte sector three times in four): both are read here, and the second stays with the lane -- in s_xb and s_tau, dead from
+                        // the end of a sweep to the prologue of the next trace, which runs in this pass -- as the start entry of that trace (ssk::MODE_START_HELD;
+                        // its coarse steps do not load it).  pflags' other bits are dead here as well: the prologue writes them anew.
+                        if (W->sweep_start_held && emit < L - 1) {
+                            typedef double nt2 __attribute__((ext_vector_type(2)));
+                            const MC_G nt2 *__restrict__ pe = reinterpret_cast<const MC_G nt2 *>(glob(H.tau_t)) + (W->sk_pn_off + (unsigned)p.shell * (unsigned)(L + 1) + (unsigned)emit);
+                            const nt2 e0 = pe[0], e1 = pe[1];
+                            emit_nu_walk = e0.x;
+                            s_xb = e1.x; s_tau = e1.y;
+                            pflags |= ssk::MODE_START_HELD;
+                        } else  // (the option off, or the last line: the sector a line-by-line sweep starts in; -inf in the frequency slot of the last line)
+                            emit_nu_walk = emit < L - 1 ? glob(P.nt_t)[2u * ((unsigned)p.shell * P.nt_stride + (unsigned)emit)] : glob(P.nu_line)[(unsigned)emit];
+                    } else
+                        emit_nu_walk = (NT != 0 && emit < L - 1) ? glob(P.nt_t)[2u * ((unsigned)p.shell * P.nt_stride + (unsigned)emit)]
+                                                                 : glob(P.nu_line)[(unsigned)emit];  // (the sector the coming sweep starts in; the interleaved table
+                                                                                                      // holds -inf in the frequency slot of the last line)
+                }
             }
             if (in_macro) {  // carried over
                 state = WS_WALK;
@@ -2078,17 +2099,35 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                 ++events;
                 const bool fast = mid_range(p.nu) && mid_range(chi_e) && mid_range(tau_event) && mid_range(p.energy) &&
                                   mid_range(p.r) && mid_range(comov_nu) && mid_range(P.t_exp) && !(DBG && (P.debug_flags & 4));
-                pflags = (fast ? 1 : 0) | ((delta + 1) << 1);
+                if constexpr (SKIP) pflags = (fast ? 1 : 0) | ((delta + 1) << 1) | (pflags & ssk::MODE_START_HELD);  // (the walk of this pass left {nu_start, p_start} in s_xb, s_tau)
+                else pflags = (fast ? 1 : 0) | ((delta + 1) << 1);
                 if (LS) {
                     sh.d_cont0[lane] = chi_e; sh.d_boundary[lane] = d_boundary;
                     s_tau_event = tau_event;
-                    s_tau = 0.0; s_line = p.next_line_id; s_row = NT != 0 ? (row_t<WIDE>)((unsigned)p.shell * P.nt_stride) : row_of<WIDE>(p.shell, L);
-                    s_kp = ((chi_e * P.tc) / p.nu) * (1.0 + 0x1p-40);
-                    s_xb = ((d_boundary * p.nu) * P.rcp_tc) * (1.0 - 0x1p-40);
-                    s_fast = fast && mid_range(s_kp);
-                    s_active = true;
                     if constexpr (SKIP) {
-                        if (W->sweep_skip && s_fast) pflags |= ssk::MODE_COARSE;
+                        const bool start_held = (pflags & ssk::MODE_START_HELD) != 0;
+                        const double held_nu = s_xb, held_p = s_tau;
+                        pflags &= ~ssk::MODE_START_HELD;
+                        s_tau = 0.0; s_line = p.next_line_id; s_row = (row_t<WIDE>)((unsigned)p.shell * P.nt_stride);
+                        s_kp = ((chi_e * P.tc) / p.nu) * (1.0 + 0x1p-40);
+                        s_xb = ((d_boundary * p.nu) * P.rcp_tc) * (1.0 - 0x1p-40);
+                        s_fast = fast && mid_range(s_kp);
+                        s_active = true;
+                        if (W->sweep_skip && s_fast) {
+                            if (start_held) {
+                                // coarse_scan's start guard, here: same operands (comov_nu = p.nu * dop, s_xb), same decision.  A trace that fails it takes fine
+                                // steps from its first line on, which is where coarse_scan returning 0 sends it; one that passes keeps p_start in s_tau, which no
+                                // coarse step reads (it is written when the lane leaves coarse mode).  A trace outside mid_range drops the entry
+                                const double x_start = comov_nu - held_nu;
+                                if (x_start >= 0.0 && x_start < s_xb) { pflags |= ssk::MODE_COARSE | ssk::MODE_START_HELD; s_tau = held_p; }
+                            } else pflags |= ssk::MODE_COARSE;
+                        }
+                    } else {
+                        s_tau = 0.0; s_line = p.next_line_id; s_row = NT != 0 ? (row_t<WIDE>)((unsigned)p.shell * P.nt_stride) : row_of<WIDE>(p.shell, L);
+                        s_kp = ((chi_e * P.tc) / p.nu) * (1.0 + 0x1p-40);
+                        s_xb = ((d_boundary * p.nu) * P.rcp_tc) * (1.0 - 0x1p-40);
+                        s_fast = fast && mid_range(s_kp);
+                        s_active = true;
                     }
                 } else {
                     sh.nu[lane] = p.nu; sh.rcp_nu[lane] = 1.0 / p.nu; sh.comov_nu[lane] = comov_nu;
@@ -2145,8 +2184,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                         const nt2 *__restrict__ pc = reinterpret_cast<const nt2 *>(H.tau_t) + at;
 #pragma unroll
                         for (int k = 0; k < CH - 1; ++k) { const nt2 e = pc[k]; nl[k] = e.x; tl[k] = e.y; }
-                        const nt2 e = reinterpret_cast<const nt2 *>(H.tau_t)[last];
-                        nl[CH - 1] = e.x; tl[CH - 1] = e.y;
+                        // A lane that holds the start entry of its trace (ssk::MODE_START_HELD, which implies coarse mode) does not load it: p_start waits in s_tau, and
+                        // coarse_scan does not look at the frequency.  (The form matters: with the held value written in front of the conditional load -- one register
+                        // pair defined on both paths -- the twelve-wave instantiation spilled 94 VGPRs and the sixteen-wave one 19 instead of 5; a value that is
+                        // nobody's in particular for the lanes that skip the load and a select behind it leave the allocation as it was.)
+                        const bool held = (pflags & ssk::MODE_START_HELD) != 0;
+                        double e_nu = __builtin_nondeterministic_value(e_nu), e_p = __builtin_nondeterministic_value(e_p);
+                        if (!held) { const nt2 e = reinterpret_cast<const nt2 *>(H.tau_t)[last]; e_nu = e.x; e_p = e.y; }
+                        nl[CH - 1] = e_nu; tl[CH - 1] = held ? s_tau : e_p;
                     } else if constexpr (NT != 0) {
 #pragma unroll
                         for (int k = 0; k < CH; ++k) { const nt2 e = pq[k]; nl[k] = e.x; tl[k] = e.y; }
@@ -2170,12 +2215,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
                     if (SKIP && (pflags & ssk::MODE_COARSE)) {
                         if constexpr (SKIP) {
                             double hi;
-                            const int c = ssk::coarse_scan(nl, tl, comov, s_kp, s_xb, s_tau_event, W->sk_margin, hi);
+                            const int c = ssk::coarse_scan(nl, tl, comov, s_kp, s_xb, s_tau_event, W->sk_margin, hi, (pflags & ssk::MODE_START_HELD) != 0);
                             const int b = s_line >> 3;
-                            if (c == CH - 1) s_line = (b + (CH - 2)) << 3;  // (all cleared: on from the LAST block, sweep_skip.hpp)
-                            else if (c > 0) { s_line = (b + c) << 3; s_tau = hi; pflags ^= ssk::MODE_COARSE | ssk::MODE_INTERVAL; }
+                            if (c == CH - 1) s_line = (b + (CH - 2)) << 3;  // (all cleared: on from the LAST block, sweep_skip.hpp; a held p_start stays in s_tau)
+                            else if (c > 0) { s_line = (b + c) << 3; s_tau = hi; pflags = (pflags & ~(ssk::MODE_COARSE | ssk::MODE_START_HELD)) | ssk::MODE_INTERVAL; }
                             else {  // the block the trace starts in: fine steps with the exact sum; (never in a later step: its first block was cleared by the one before)
-                                s_line = p.next_line_id; s_tau = 0.0; pflags &= ~ssk::MODE_COARSE;
+                                s_line = p.next_line_id; s_tau = 0.0; pflags &= ~(ssk::MODE_COARSE | ssk::MODE_START_HELD);
                             }
                         }
                         alive = true; f_nu = 0.0; f_tau = 0.0;

@@ -70,6 +70,13 @@ constexpr int DEFAULT_LOADS = 10, MAX_LOADS = 16;
 constexpr double GAP_FACTOR = 8.0;
 // mode bits of a lane's pflags
 constexpr int MODE_COARSE = 8, MODE_INTERVAL = 16;
+// MODE_START_HELD ("start entry in registers", option sweep_start_held): the trace follows an emission that a hot sector of the walk decided.  The walk's read of
+// the emission line's frequency fetched pn[s][emit] and its neighbour pn[s][emit + 1] = pn[s][start] together, so the lane brings {nu_start, p_start} along: the
+// prologue of the trace evaluates the start guard of coarse_scan (same operands: comov, xb, nu_start) and gives a trace that fails it no MODE_COARSE -- what
+// coarse_scan returning 0 in the first step leads to -- and the coarse steps take p_start from the lane (`held`) and do not issue their N-th load.  Set with
+// MODE_COARSE only; cleared when the lane leaves coarse mode, falls back or is suspended (a resumed lane loads the entry as every other trace does).
+// trace() restates it (TraceIn::start_held); tests/test_sweep_start_held_host.py holds the held path to the reference's loop and to the load path.
+constexpr int MODE_START_HELD = 32;
 
 struct Entry { double nu_last, p_end; };
 
@@ -81,8 +88,11 @@ SSK_FN double margin(int n_lines, double rowsum_max)
 // One coarse step on its N loads (entries 0 .. N - 2 the coarse ones {nu_last, p_end}, entry N - 1 = {nu_start, p_start}): the number of leading
 // blocks cleared (0 .. N - 1); hi = the bound of the last cleared block.  None if the first line fails X >= 0 (the reference's "nu difference" error, or a close
 // line: to the exact evaluation).
+// held (MODE_START_HELD): the start guard has been evaluated already, on the same operands, and held; p_end[N - 1] is the lane's own p_start and nu_last[N - 1] is
+// not looked at (the entry was not loaded).
 template <int N>
-SSK_FN int coarse_scan(const double (&nu_last)[N], const double (&p_end)[N], double comov, double kp, double xb, double tau_event, double m, double &hi)
+SSK_FN int coarse_scan(const double (&nu_last)[N], const double (&p_end)[N], double comov, double kp, double xb, double tau_event, double m, double &hi,
+                       bool held = false)
 {
     static_assert(N >= 3, "at least two coarse entries: a full step advances by N - 2 blocks");
     constexpr int STEP = N - 1;
@@ -91,7 +101,7 @@ SSK_FN int coarse_scan(const double (&nu_last)[N], const double (&p_end)[N], dou
     // (X_start < X_b costs a cleared first block nothing -- X_last >= X_start -- and keeps a trace that starts on the last line of the list or behind it,
     // whose frequency slot holds -inf, out of the coarse entries: behind the row's last block they are the next row's)
     const double x_start = comov - nu_last[STEP];
-    bool alive = x_start >= 0.0 && x_start < xb;
+    bool alive = held || (x_start >= 0.0 && x_start < xb);
     double h_keep = 0.0;
 #if defined(__HIPCC__)
 #pragma unroll
@@ -131,10 +141,14 @@ struct TraceIn {
     double nu, comov, chi, tau_event, d_boundary, kp, xb, t_exp, m;
     int force_fallback, skip, fine_chunk;
     int loads;  // 16-byte loads of a coarse step (coarse_scan's N); 0: DEFAULT_LOADS
+    // MODE_START_HELD: the trace follows an emission whose walk fetched pn[start] = {held_nu, held_p} (start_held != 0: the prologue's guard, no N-th load)
+    int start_held;
+    double held_nu, held_p;
 };
 // fb_gap (a trace that fell back on a line): how far tau_event lies below tau_prev + tau_line + chi * distance as the lane's upper bound sees them
 // fb_line, fb_u: the line the fall-back happened at (n_lines: behind the list) and the lane's upper bound of the sum in front of it
-struct TraceOut { int code, line; double dist; int fell_back, coarse_steps, fine_steps, interval, fb_code; double fb_gap; int fb_line; double fb_u; };
+// start_loads: the coarse steps that loaded pn[start] (their N-th load); guard_failed: a held start entry failed the prologue's guard (no coarse step at all)
+struct TraceOut { int code, line; double dist; int fell_back, coarse_steps, fine_steps, interval, fb_code; double fb_gap; int fb_line; double fb_u; int start_loads, guard_failed; };
 
 constexpr double C_LIGHT_ = 2.99792458e10, MISS_ = 1e99, CLOSE_ = 1e-14;
 inline int exact_line(int L, double t_exp, int line, double nu_line, double tau_line, double tau_prev, double nu, double comov_nu, double chi, double tau_event,
@@ -161,20 +175,20 @@ inline int exact_line(int L, double t_exp, int line, double nu_line, double tau_
 }
 
 template <int N>
-inline int coarse_scan_n(const double *nl, const double *pe, const TraceIn &in, double &hi)
+inline int coarse_scan_n(const double *nl, const double *pe, const TraceIn &in, double &hi, bool held)
 {
     double a[N], b[N];
     for (int k = 0; k < N; ++k) { a[k] = nl[k]; b[k] = pe[k]; }
-    return coarse_scan<N>(a, b, in.comov, in.kp, in.xb, in.tau_event, in.m, hi);
+    return coarse_scan<N>(a, b, in.comov, in.kp, in.xb, in.tau_event, in.m, hi, held);
 }
 // (the widths the kernel's instantiations and the tests use)
-inline int coarse_scan_any(int n, const double *nl, const double *pe, const TraceIn &in, double &hi)
+inline int coarse_scan_any(int n, const double *nl, const double *pe, const TraceIn &in, double &hi, bool held = false)
 {
     switch (n) {
-    case 8: return coarse_scan_n<8>(nl, pe, in, hi);
-    case 9: return coarse_scan_n<9>(nl, pe, in, hi);
-    case 10: return coarse_scan_n<10>(nl, pe, in, hi);
-    case 12: return coarse_scan_n<12>(nl, pe, in, hi);
+    case 8: return coarse_scan_n<8>(nl, pe, in, hi, held);
+    case 9: return coarse_scan_n<9>(nl, pe, in, hi, held);
+    case 10: return coarse_scan_n<10>(nl, pe, in, hi, held);
+    case 12: return coarse_scan_n<12>(nl, pe, in, hi, held);
     default: __builtin_trap();
     }
 }
@@ -187,6 +201,11 @@ inline TraceOut trace(const TraceIn &in, const double *nu_true)
     int mode = in.skip ? MODE_COARSE : 0;
     int s_line = in.start;
     double s_tau = 0.0;
+    if (in.skip && in.start_held) {  // the prologue: coarse_scan's start guard on the entry the lane brought along; p_start waits in s_tau
+        const double x_start = in.comov - in.held_nu;
+        if (x_start >= 0.0 && x_start < in.xb) { mode |= MODE_START_HELD; s_tau = in.held_p; }
+        else { mode = 0; out.guard_failed = 1; }
+    }
     const double g = in.force_fallback ? __builtin_inf() : GAP_FACTOR * in.m;
     for (;;) {
         if (mode & MODE_COARSE) {
@@ -194,12 +213,14 @@ inline TraceOut trace(const TraceIn &in, const double *nu_true)
             double nl[MAX_LOADS], pe[MAX_LOADS], hi;
             const int b = s_line >> 3;
             for (int k = 0; k < STEP; ++k) { nl[k] = in.ct[2 * (b + k)]; pe[k] = in.ct[2 * (b + k) + 1]; }
-            nl[STEP] = in.pn[2 * in.start]; pe[STEP] = in.pn[2 * in.start + 1];
-            const int c = coarse_scan_any(LOADS, nl, pe, in, hi);
+            const bool held = (mode & MODE_START_HELD) != 0;
+            if (held) { nl[STEP] = 0.0; pe[STEP] = s_tau; }
+            else { nl[STEP] = in.pn[2 * in.start]; pe[STEP] = in.pn[2 * in.start + 1]; ++out.start_loads; }
+            const int c = coarse_scan_any(LOADS, nl, pe, in, hi, held);
             const bool first = s_line == in.start;
             if (c == STEP) s_line = (b + ADVANCE) << 3;
             else if (c > 0) { s_line = (b + c) << 3; s_tau = hi; mode = MODE_INTERVAL; out.interval = 1; }
-            else if (first) mode = 0;
+            else if (first) { s_tau = 0.0; mode = 0; }
             else { s_line = in.start; s_tau = 0.0; mode = 0; out.fell_back = 1; }
             continue;
         }

@@ -248,6 +248,9 @@ struct TardisMcContext {
         // the first propagate call after set_opacity that may use them (sk_valid falls with nt_valid); sk_negative: tau_prefix_kernel's flag; sk_margin: ssk::margin
         // of the largest row sum.  last_sweep_skip: what the last propagate call ran with (tardis_mc_last_sweep_skip)
         int sweep_skip = -1, last_sweep_skip = 0;
+        // Option sweep_start_held (ssk::MODE_START_HELD: the walk's read of an emission line's frequency brings the start entry of the coming trace along): -1 automatic
+        // (SWEEP_START_HELD_AUTO where the call's sweeps skip), 0 off, 1 on where the call's sweeps skip
+        int sweep_start_held = -1;
         bool sk_valid = false, sk_negative = false;
         unsigned sk_ct_off = 0, sk_pn_off = 0;
         double sk_margin = 0.0;
@@ -1375,6 +1378,9 @@ int build_screening_tables(TardisMcContext *ctx)
     return TARDIS_MC_OK;
 }
 
+// what option sweep_start_held = -1 stands for (profiles/sweep_start_held.txt)
+constexpr int SWEEP_START_HELD_AUTO = 1;
+
 // bytes of the block-skip tables (sweep_skip.hpp) behind the interleaved table: coarse entries with their slack, {frequency, prefix sum} entries
 // (the slack: a coarse step of N loads reads N - 1 coarse entries from the block of its current line on; a trace that starts behind the last line of a list of
 // 8 r lines starts at block r, so the last row's step reads N - 1 entries past the table: 7 and 9 at the widths compiled, 11 at the widest the host test runs,
@@ -1881,6 +1887,7 @@ int fill_wave_cold(TardisMcContext *ctx, const WaveCall &E, int epoch, const mc:
     wc.log_continue = vq ? 1 : 0;
     wc.log_gen = E.log_gen;
     wc.rng_complete = ctx->wv.rng_complete;
+    wc.sweep_start_held = (E.sweep_skip && (ctx->sw.sweep_start_held < 0 ? SWEEP_START_HELD_AUTO : ctx->sw.sweep_start_held)) ? 1 : 0;
     wc.sweep_skip = E.sweep_skip; wc.sk_ct_off = ctx->sw.sk_ct_off; wc.sk_pn_off = ctx->sw.sk_pn_off; wc.sk_margin = ctx->sw.sk_margin;
     HIP_TRY(ctx, store_value(E.st, wc_dev, wc));
     return TARDIS_MC_OK;
@@ -2544,6 +2551,7 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "tracker_defer") ctx->wv.tracker_defer = value ? 1 : 0;
     else if (n == "rng_complete") ctx->wv.rng_complete = value ? 1 : 0;
     else if (n == "sweep_skip") ctx->sw.sweep_skip = (int)std::max<long long>(-1, std::min<long long>(value, 1));
+    else if (n == "sweep_start_held") ctx->sw.sweep_start_held = (int)std::max<long long>(-1, std::min<long long>(value, 1));
     else if (n == "tracker_pack_max_lines") ctx->wv.tracker_pack_max_lines = std::max<long long>(0, value);
     else if (n == "group_size") ctx->group_size = (value == 4 || value == 8 || value == 16) ? (int)value : 0;
     else if (n == "pipeline_chunks") {}  // (round 1: chunks on two streams; a call of the wave kernel now runs as epochs -- accepted, ignored)
