@@ -470,7 +470,10 @@ int tardis_mc_formal_integral(TardisMcContext *ctx, double inner_temperature, co
  * Per shell s:  Edotlu = (1 / (time_of_simulation volume[s])) (1 - exp(-tau)) Edotlu_estimator;  e_dot_u[k] = its sum over the lines
  * with upper level k;  C = e_dot_u (downbranch) or the solution of (I - Q_s)^T C = e_dot_u (macroatom; Q_s[i][j] = sum of the
  * probabilities of the rows of block i with transition_type >= 0 and destination level j), found by the fixed-point iteration
- * C <- e_dot_u + Q_s^T C until max|dC| <= 1e-14 max|C| in every shell, tested every 16 iterations (option "source_max_iterations");
+ * C <- e_dot_u + Q_s^T C from C = e_dot_u until an iteration has changed no level of any shell, tested every 16 iterations (option
+ * "source_max_iterations").  With non-negative estimators, depths and probabilities the iterates never decrease, so the iteration ends, at the
+ * fixed point of the rounded map: every C[k] is then within (r + n + 3) 2^-53 B[k] of the exact solution to first order, r the longest row of
+ * Q_s^T, n the most lines on a level, B = (I - Q_s^T)^-1 C -- relative to the level itself, however weak beside the others of its shell;
  * att_S_ul[s][l] = wave[l] (prob[s][t] C[k]) time_of_simulation / (4 pi) for the emission row t (transition_type -1) of line l, in
  * block k;  Jblue_lu[s][l] = j_blue_estimator[s][l] c t_exp / (4 pi time_of_simulation volume[s]) (bit for bit the j_blues of
  * tardis_mc_radiation_field where the estimator is non-zero);  Jred_lu = Jblue_lu exp(-tau) + att_S_ul.
@@ -1237,6 +1240,12 @@ int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const do
  * non-finite pivot, n + 1: x[0] == 0, n + 2: an x that is not finite) come back.  Touches nothing resident, needs no opacity state.
  * TARDIS_MC_ERR_UNSUPPORTED beyond the scratch bound of the global form. */
 int tardis_mc_debug_nlte_solve(TardisMcContext *ctx, int64_t n, int64_t n_systems, const double *m, const double *b, double *x, int32_t *status);
+/* Plants the line estimators that tardis_mc_source_function reads, for tests: j_blue and edotlu are host arrays [n_lines][n_shells], the layout
+ * in which tardis_mc_get_results returns them.  They become copy 0 of the two resident tables and every other copy ("estimator_copies") is zeroed;
+ * J, nu_bar and the v-packet histogram keep their values.  Needs a resident opacity state and configuration (TARDIS_MC_ERR_STATE otherwise), allocates
+ * the estimators as tardis_mc_reset_estimators would if no call has yet, drops what tardis_mc_reset_estimators drops (the resident source function)
+ * and leaves the context, as far as tardis_mc_source_function is concerned, as a tardis_mc_propagate would.  No propagate path reads or calls it. */
+int tardis_mc_debug_set_line_estimators(TardisMcContext *ctx, const double *j_blue, const double *edotlu);
 /* Memory-system micro-benchmarks used to size the kernels (design input): which = 0 random fp64 atomics (agent
  * scope), 1 same at workgroup scope in a per-XCD slice, 2/3 the same with 16 consecutive doubles per 16 lanes,
  * 4 random 8-byte loads, 5 16-lane-coalesced loads; 15 a wide coalesced copy of the table's first half onto its second (iters

@@ -111,6 +111,7 @@ SYMBOLS = {
     "tardis_mc_comm_check": (_i, [_vp, C.POINTER(_i)]),
     "tardis_mc_debug_eval": (_i, [_vp, _i, _vp, _vp, _vp, C.c_int64]),
     "tardis_mc_debug_nlte_solve": (_i, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp]),
+    "tardis_mc_debug_set_line_estimators": (_i, [_vp, _vp, _vp]),
     "tardis_mc_debug_microbench": (_i, [_vp, _i, C.c_int64, _i, _i, C.POINTER(C.c_double)]),
 }
 

@@ -22,6 +22,13 @@
 // then a fixed butterfly adds the G partial sums; rows of more than SF_LONG_STEPS * G entries are left to the whole wave,
 // which sums them the same way with G = 64.  The order of every sum is therefore a function of the index alone and
 // results are bit-identical from run to run.
+//
+// Stop rule.  The host reads sf_convergence_kernel's {max |dx|, max |x|} per shell every 16 iterations and ends the solve when max |dx| == 0
+// in every shell: the last iteration changed no level.  With non-negative e and q every operation of an iteration is monotone in x, x_1 >= x_0 = e,
+// and so x_n never decreases in any component: the iteration cannot circle and ends exactly at the fixed point of the ROUNDED map, which lies
+// within (r + n + 3) 2^-53 B_k of the exact C_k (r the longest incoming row, n the most lines on a level, B = (I - Q^T)^-1 C).  No
+// norm over the levels enters the rule: a weak ion beside a strong one is converged relative to itself.  (Negative estimators, depths or
+// probabilities void the argument; an iteration that then never settles ends at the bound on the iterations, as an error.)
 // fp64 throughout; -ffp-contract=off keeps every product and sum a rounding of its own.
 #pragma once
 #include <hip/hip_runtime.h>

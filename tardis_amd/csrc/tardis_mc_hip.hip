@@ -4349,7 +4349,7 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
                            ctx->ot.prob_t.as<double>(), (long long)T, ctx->sf.q.as<double>());
         HIP_TRY(ctx, hipGetLastError());
         // x ping-pongs between sf.x[0] and sf.x[1]; the first iteration reads e itself.  Every 16 iterations (or at the cap) the per-shell
-        // {max |dx|, max |x|} of the last one come to the host.
+        // {max |dx|, max |x|} of the last one come to the host; the solve ends when the last iteration changed no level of any shell.
         auto iterate = g_in == 1 ? mc::sf_iterate_kernel<1> : (g_in == 4 ? mc::sf_iterate_kernel<4> : mc::sf_iterate_kernel<16>);
         const double *cur = ctx->sf.e.as<double>();
         const long long cap = ctx->sf.max_iterations;
@@ -4375,7 +4375,7 @@ int tardis_mc_source_function(TardisMcContext *ctx, double time_of_simulation, c
             worst_ratio = -1.0;
             for (size_t s = 0; s < S; ++s) {
                 const double dx = ctx->sf.conv_host[2 * s], xm = ctx->sf.conv_host[2 * s + 1];
-                if (!(dx <= 1e-14 * xm)) converged = false;
+                if (!(dx == 0)) converged = false;  // (the stop rule: no level of the shell has changed, see source_function.hpp)
                 const bool finite = dx == dx && xm < __builtin_huge_val();  // (NaN or infinite rates: no later iteration repairs them)
                 const double ratio = (finite && xm > 0) ? dx / xm : __builtin_huge_val();
                 if (dx != 0 && ratio > worst_ratio) { worst_ratio = ratio; worst = (int)s; }
@@ -5929,6 +5929,32 @@ int tardis_mc_debug_eval(TardisMcContext *ctx, int op, const double *x, const do
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_debug_set_line_estimators(TardisMcContext *ctx, const double *j_blue, const double *edotlu)
+{
+    if (!ctx || !j_blue || !edotlu) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid debug_set_line_estimators arguments");
+    if (!ctx->have_opacity || !ctx->have_config)
+        return fail(ctx, TARDIS_MC_ERR_STATE, "debug_set_line_estimators: set_opacity and set_config must precede it");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    drop_products(ctx, ESTIMATORS_CHANGED);
+    int rc = ensure_estimators(ctx);  // (allocated and zeroed if no call has done so yet: as tardis_mc_propagate finds them)
+    if (rc) return rc;
+    const size_t S = ctx->es.est_S, L = ctx->es.est_L;
+    EstLayout e = est_layout(S, L, ctx->es.est_G, ctx->es.est_copies);
+    // [n_lines, n_shells] -> copy 0 of the two shell-major tables, which lie one behind the other; the other copies are zeroed
+    std::vector<double> tables(2 * S * L);
+    for (size_t l = 0; l < L; ++l)
+        for (size_t s = 0; s < S; ++s) {
+            tables[s * L + l] = j_blue[l * S + s];
+            tables[S * L + s * L + l] = edotlu[l * S + s];
+        }
+    double *base = ctx->es.est.as<double>();
+    HIP_TRY(ctx, hipMemcpyAsync(base + e.jblue, tables.data(), 2 * S * L * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (ctx->es.est_copies > 1)
+        HIP_TRY(ctx, hipMemsetAsync(base + e.jblue + e.copy_stride, 0, (size_t)(ctx->es.est_copies - 1) * e.copy_stride * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the staging vector goes out of scope)
     return TARDIS_MC_OK;
 }
 

@@ -1030,6 +1030,15 @@ class Engine:
                     "debug_nlte_solve")
         return x, status
 
+    def debug_set_line_estimators(self, j_blue, edotlu):
+        """Plants the line estimators source_function() reads (`tardis_mc_debug_set_line_estimators`, for tests): j_blue and edotlu
+        [n_lines, n_shells] as get_results() returns them, after set_opacity() and set_config()."""
+        jb, ed = np.ascontiguousarray(j_blue, dtype=np.float64), np.ascontiguousarray(edotlu, dtype=np.float64)
+        if jb.shape != (self.n_lines, self.n_shells) or ed.shape != jb.shape:
+            raise ValueError("debug_set_line_estimators needs j_blue and edotlu [n_lines, n_shells]")
+        self._check(self._L.tardis_mc_debug_set_line_estimators(self._h, jb.ctypes.data, ed.ctypes.data), "debug_set_line_estimators")
+        self.estimators_generation += 1
+
     def debug_microbench(self, which: int, n_doubles: int, iters: int, blocks: int) -> float:
         v = C.c_double()
         self._check(self._L.tardis_mc_debug_microbench(self._h, which, n_doubles, iters, blocks, C.byref(v)), "microbench")

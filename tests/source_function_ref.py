@@ -5,7 +5,7 @@ tardis_mc_source_function (tests/test_source_function_gpu.py); a helper module, 
 
 All 2-D inputs use the reference's [lines or transitions, shells] layout.  ``solver``: "dense" (numpy.linalg.solve of
 (I - Q)^T per shell, for tables of at most about 3e3 levels), "fixed_point" (x <- e + Q^T x from x = e until
-max|dx| <= 1e-14 max|x|, the iteration the device runs, with a sparse matvec) or "none" (downbranch: C = e_dot_u).
+x no longer changes, the iteration the device runs, with a sparse matvec) or "none" (downbranch: C = e_dot_u).
 """
 import numpy as np
 import pandas as pd
@@ -28,15 +28,16 @@ def jump_matrix(opacity_state, shell):
                          shape=(n_levels, n_levels)).tocsr()
 
 
-def fixed_point(Q, e, max_iterations=20000, rtol=1e-14):
-    """x <- e + Q^T x from x = e; returns (x, iterations)."""
+def fixed_point(Q, e, max_iterations=20000):
+    """x <- e + Q^T x from x = e until an iteration changes no component (the device's rule; with e, Q >= 0 the iterates never decrease, so
+    the iteration ends, at the fixed point of the rounded map); returns (x, iterations)."""
     QT = Q.T.tocsr()
     x = e.copy()
     for it in range(1, max_iterations + 1):
         x_new = e + QT @ x
-        dx = np.abs(x_new - x).max()
+        same = np.array_equal(x_new, x)
         x = x_new
-        if dx <= rtol * np.abs(x).max():
+        if same:
             return x, it
     raise RuntimeError(f"fixed point not converged after {max_iterations} iterations")
 
