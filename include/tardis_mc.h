@@ -33,7 +33,12 @@ extern "C" {
 #define TARDIS_MC_ABI_VERSION 2  /* 2 (round 6): + tardis_mc_comm_check, tardis_mc_stream_results, tardis_mc_streamed_packets, tardis_mc_last_compactions, microbench 15;
                                     * additive since: tardis_mc_formal_integral_interpolated, tardis_mc_interpolated_source,
                                     * tardis_mc_packet_decomposition, tardis_mc_decomposition_path, option "vpacket_last_interaction",
-                                    * TardisMcVpacketLog, tardis_mc_get_vpacket_log, tardis_mc_vpacket_decomposition */
+                                    * TardisMcVpacketLog, tardis_mc_get_vpacket_log, tardis_mc_vpacket_decomposition;
+                                    * the plasma, NLTE, continuum and cooling entry points; TardisMcBfEstimatorSetup and the eight
+                                    * tardis_mc_*bf_estimator* / tardis_mc_get_segment_log / tardis_mc_debug_bf_accumulate entry points, the
+                                    * options "bf_estimators", "segment_log_*", "continuum_field".  The number stays 2 for these additions, as for
+                                    * the earlier ones: the suite pins it, and nothing that existed changed.  A build older than a binding
+                                    * therefore fails when the binding looks a new symbol up, not at the version check. */
 
 enum {
     TARDIS_MC_OK = 0,
@@ -1005,8 +1010,9 @@ int tardis_mc_last_helium_ms(TardisMcContext *ctx, double *out_relative_ms);
  * continuum data installed the stage runs behind the population stage of a solve that SUCCEEDED, on that update's populations; it reads
  * nothing of the opacity stages and writes nothing they read; it feeds back into nothing.  A failed electron-density iteration or NLTE
  * solve returns before it.  Without continuum data no launch of the update changes.  Transport kernels do not read any of this yet.
- * The radiation field is ALWAYS the dilute black body of the call's t_radiative and dilution_factor, also with j_blues_mode 1: the
- * engine has no photo-ionisation estimators.
+ * The radiation field is the dilute black body of the call's t_radiative and dilution_factor, also with j_blues_mode 1, unless the
+ * option "continuum_field" is 1: then gamma and alpha_stim come from the transport's photo-ionisation estimators (the section after the
+ * cooling sub-stage).
  * fp64, no contraction, exp the transport's own (mcm::exp); every product, quotient, sum and difference a rounding of its own, in
  * exactly the order written; the constants of the plasma section (CODATA 2010 cgs) and c = 2.99792458e10.
  * Per shell:
@@ -1053,7 +1059,7 @@ int tardis_mc_last_helium_ms(TardisMcContext *ctx, double *out_relative_ms);
  * tables; a streaming kernel for chi_bf.  The clamps are counted per workgroup and the host adds the counts.  The resident chi_bf is
  * [NP][S], the shell fastest -- what the getter returns, and the layout in which a reader in shell s touches two rows per current
  * continuum.  No second form for long blocks is built, hence no tardis_mc_continuum_path.  No atomics: two calls give identical bits.
- * Not covered: continuum events in transport, photo-ionisation and heating estimators (a "detailed" field for these rates), NLTE
+ * Not covered: continuum events in transport, NLTE
  * ionisation, collisional excitation, p_fb_deactivation (the cooling rates, the free-bound emission CDFs and the k-packet samplers:
  * the section after this one). */
 typedef struct TardisMcContinuumData {
@@ -1150,7 +1156,7 @@ int tardis_mc_continuum_opacity(TardisMcContext *ctx, const TardisMcContinuumQue
  * No atomics: two calls give identical bits.
  * Not covered: collisional-excitation cooling and the coll_exc_coeff data it needs; the macro-atom continuum transition probabilities
  * (p_fb_deactivation, the recombination / photo-ionisation / collisional rows); the choice of the absorbing continuum at a bound-free
- * event; the photo-ionisation and heating estimators; NLTE ionisation; any reader of these tables in the propagation kernels. */
+ * event; NLTE ionisation; any reader of these tables in the propagation kernels. */
 
 /* c_fb_sp, cool_rate_fb, cool_rate_coll_ion [NC,S] and cool_rate_ff, cool_rate_adiabatic, cool_rate_total [S] of the last successful
  * tardis_mc_update_plasma; any pointer may be NULL.  The state rule of tardis_mc_get_continuum_rates: what drops or keeps the continuum
@@ -1179,6 +1185,76 @@ typedef struct TardisMcKpacketQuery {
  * finite or lies outside [0, 1), a force_kind outside [-1, 3] and a forced continuum outside [0, NC); the state rule of
  * tardis_mc_get_continuum_rates. */
 int tardis_mc_kpacket_sample(TardisMcContext *ctx, const TardisMcKpacketQuery *query);
+
+/* ---- photo-ionisation and heating estimators from the transport, on the device (csrc/bf_estimators.hpp) ----
+ * The continuum stage's gamma and alpha_stim integrate the dilute black body; this is the field the packets actually carried.  The
+ * formulas below restate update_bound_free_estimators, and PhotoIonRateCoeff / StimRecombRateCoeff with estimators, of the reference;
+ * the reference tree was not at hand, so they are this header's contract, with ONE decision of this project named below.
+ * Option "bf_estimators" (0/1, default 0).  With it a propagate call runs on the instantiations that full tracking runs on -- the
+ * wave-owner kernel with group sweeps (variant 2) where "track_full" would, else the lane kernel (variant 0); variants 1, 3 and 4 are not
+ * instrumented -- and logs one 24-byte record {comov_nu, ed, shell} per move of a packet:
+ *   comov_nu = nu doppler_factor,  comov_energy = energy doppler_factor  (the values of the J / nu_bar update of that move)
+ *   ed = comov_energy distance,  distance = the trace's distance BEFORE full relativity scales it by the Doppler factor: under partial
+ *   relativity ed is bit for bit the term added to J, and ed comov_nu the term added to nu_bar.
+ *   THIS PROJECT'S DECISION: a move of length zero writes no record (it would add 0.0 to the four sums and 1 to the statistics only):
+ *   the statistics count the moves of positive length.
+ * The records go to a pool of chunks with the event log's mechanics (csrc/event_log.hpp: one claim function for both logs); event rows
+ * stay tied to "track_full": a call with the estimators on and full tracking off writes segment records only, both may be on together.
+ * "segment_log_capacity" (records; 0 = automatic, 96 per packet; the pool's chunks have the event log's size, 128 records, and like that
+ * log's pool it holds one more chunk per wave and launch than the capacity asks for), "segment_log_max_bytes" (default 16 GiB; a call over
+ * it, or one whose pool would reach 2^32 slots, fails with TARDIS_MC_ERR_INVALID_ARGUMENT like "event_log_max_bytes"), "segment_log_keep" (tests: the
+ * records stay readable through tardis_mc_get_segment_log).  With the option off every launch, every instantiation chosen and every
+ * per-packet bit is as before.  With it on and no tardis_mc_set_bf_estimators, tardis_mc_propagate fails with TARDIS_MC_ERR_STATE before
+ * it launches anything.
+ * The accumulate pass runs at the end of every tardis_mc_propagate that logged, on the context's stream behind the last propagation
+ * launch (tardis_mc_synchronize covers it), and consumes the log.  Five tables [NC,S], the shell fastest: photo_ion, stim_recomb,
+ * bf_heating, stim_recomb_cooling (float64) and statistics (int64).  They accumulate across propagate calls as J does;
+ * tardis_mc_reset_estimators zeroes them.  fp64, no contraction, exp = mcm::exp, every operation a rounding of its own in the order
+ * written; h and k_B of the plasma section.  Per record (nu, ed, s):
+ *   beta_e = 1 / (k_B t_e[s]);   bfac = exp((h nu) (-beta_e))
+ * per continuum c that is current (nu_min[c] <= nu <= nu_max[c]), x_c interpolated exactly as tardis_mc_continuum_opacity does (the
+ * same __device__ function), nu_i = the block's first frequency:
+ *   inc = (ed x_c) / nu;   heat = (ed x_c) (1.0 - nu_i / nu)
+ *   photo_ion[c,s] += inc;  stim_recomb[c,s] += inc bfac;  bf_heating[c,s] += heat;  stim_recomb_cooling[c,s] += heat bfac;  statistics[c,s] += 1
+ * Every term is non-negative; the order of a cell's sum is not specified (fp64 atomics), the statistics are exact.
+ * Kernels: the record slots grouped by shell with the three grouping kernels of csrc/estimator_log.hpp; then a workgroup per (shell,
+ * slice of <= 65536 records) that stages batches of records in LDS (the staging thread computes bfac), every thread owning continua
+ * whose bounds and five sums it keeps in registers, and one set of fp64 atomics per thread and slice.  The continua are served 256 at a
+ * time, a pass over the slice each: bfac is computed once per record and PASS, i.e. ceil(NC / 256) times.  More than 36864 shells are
+ * refused (the grouping's LDS histogram).  Measured on an MI355X: profiles/bf_estimators.txt.
+ * Rates:  norm[s] = 1.0 / ((time_of_simulation volume[s]) h);  gamma_est = photo_ion norm;  stim_est = stim_recomb norm.
+ * Option "continuum_field": 0 (default) the dilute black body; 1: the continuum stage of tardis_mc_update_plasma takes
+ * gamma = gamma_est[c,s] and alpha_stim = stim_est[c,s] phi_ik instead of T(y_g) and T(y_st) phi_ik; gamma_corr by the same expression,
+ * alpha_sp, coll_*, chi_bf and the cooling sub-stage unchanged; TARDIS_MC_ERR_STATE from tardis_mc_update_plasma when continuum data are
+ * installed and no rates are resident.  With the option 0 every output of the update keeps its bits.
+ * Not covered: the heating estimators feed no rate yet; tardis_mc_allreduce_estimators does not carry the tables (ranks add their
+ * downloads); variants 1, 3 and 4. */
+typedef struct TardisMcBfEstimatorSetup {
+    const double *t_electrons;   /* [S] K, finite and > 0: an explicit input -- the continuum stage's own t_e is dropped by tardis_mc_update_opacity */
+} TardisMcBfEstimatorSetup;
+/* Installs t_electrons and the zeroed tables; setup == NULL switches the estimators off and frees the tables.  TARDIS_MC_ERR_STATE
+ * without installed continuum data or geometry; TARDIS_MC_ERR_INVALID_ARGUMENT for a temperature that is not finite and positive.
+ * Whatever drops the continuum data drops this, and so does a geometry with another number of shells. */
+int tardis_mc_set_bf_estimators(TardisMcContext *ctx, const TardisMcBfEstimatorSetup *setup);
+/* The host-side check of tardis_mc_set_bf_estimators, without a context or a device: 0 or TARDIS_MC_ERR_INVALID_ARGUMENT, the message
+ * (tardis_mc_last_error(NULL)) naming the first offending index. */
+int tardis_mc_check_bf_estimator_setup(const TardisMcBfEstimatorSetup *setup, int64_t n_shells);
+/* The five tables [NC,S] and the records logged / dropped since the last reset; any pointer may be NULL.  With n_dropped > 0 it returns
+ * TARDIS_MC_ERR_STATE after writing the two counts only: raise "segment_log_capacity" or split the packets (the run is deterministic). */
+int tardis_mc_get_bf_estimators(TardisMcContext *ctx, double *photo_ion, double *stim_recomb, double *bf_heating, double *stim_recomb_cooling,
+                                int64_t *statistics, int64_t *n_records, int64_t *n_dropped);
+/* Tests: the records of the last tardis_mc_propagate, in no particular order; needs "segment_log_keep" (else TARDIS_MC_ERR_STATE).
+ * *count is always written; the columns (any may be NULL) only when count <= capacity. */
+int tardis_mc_get_segment_log(TardisMcContext *ctx, double *nu, double *ed, int64_t *shell, int64_t capacity, int64_t *count);
+/* Tests: the accumulate pass alone on n caller-supplied records (checked on the host: nu finite and > 0, ed finite, shell in [0, S))
+ * into the resident tables; the records count as logged. */
+int tardis_mc_debug_bf_accumulate(TardisMcContext *ctx, int64_t n, const double *nu, const double *ed, const int64_t *shell);
+/* Device time of the last accumulate pass in ms: grouping the slots by shell, accumulating.  Excluded from every other timer. */
+int tardis_mc_last_bf_estimator_ms(TardisMcContext *ctx, double *out_group_ms, double *out_accumulate_ms);
+/* gamma_est and stim_est [NC,S] from the resident tables (volume [S], cm^3; both inputs finite and > 0); resident, and they survive
+ * tardis_mc_reset_estimators.  The getter: TARDIS_MC_ERR_STATE before the first call. */
+int tardis_mc_bf_estimator_rates(TardisMcContext *ctx, double time_of_simulation, const double *volume);
+int tardis_mc_get_bf_estimator_rates(TardisMcContext *ctx, double *gamma_est, double *stim_est);
 
 /* The full r-packet log of the last tardis_mc_propagate (option "track_full"), after tardis_mc_get_results: an exclusive scan of the
  * per-packet row counts into offsets, then the rows scattered packet-major into the caller's columns.  TARDIS_MC_ERR_STATE when the

@@ -224,6 +224,11 @@ class TardisMcContinuumData(C.Structure):
     ]
 
 
+class TardisMcBfEstimatorSetup(C.Structure):
+    """The electron temperatures of the photo-ionisation estimators (tardis_mc_set_bf_estimators)."""
+    _fields_ = [("t_electrons", _pd)]
+
+
 class TardisMcContinuumQuery(C.Structure):
     """A batch of (frequency, shell) pairs and where their continuum opacities go (tardis_mc_continuum_opacity)."""
     _fields_ = [
@@ -543,6 +548,13 @@ def marshal_continuum_data(cd) -> Marshalled:
         raise ValueError("nu and x_sect must be vectors of one length")
     s = TardisMcContinuumData(len(level), _ip(level), _ip(edge), len(nu), _dp(nu), _dp(x))
     return Marshalled(s, [level, edge, nu, x])
+
+
+def marshal_bf_estimator_setup(t_electrons, n_shells) -> Marshalled:
+    t = np.ascontiguousarray(t_electrons, dtype=np.float64)
+    if t.shape != (int(n_shells),):
+        raise ValueError("t_electrons must be [n_shells]")
+    return Marshalled(TardisMcBfEstimatorSetup(_dp(t)), [t])
 
 
 def marshal_continuum_query(nu, shell, n_continua, each=False) -> Marshalled:

@@ -91,6 +91,14 @@ SYMBOLS = {
     "tardis_mc_get_kpacket_tables": (_i, [_vp] * 3 + [C.POINTER(C.c_int64)]),
     "tardis_mc_last_cooling_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 3),
     "tardis_mc_kpacket_sample": (_i, [_vp, _vp]),
+    "tardis_mc_set_bf_estimators": (_i, [_vp, _vp]),
+    "tardis_mc_check_bf_estimator_setup": (_i, [_vp, C.c_int64]),
+    "tardis_mc_get_bf_estimators": (_i, [_vp] * 6 + [C.POINTER(C.c_int64)] * 2),
+    "tardis_mc_get_segment_log": (_i, [_vp] * 4 + [C.c_int64, C.POINTER(C.c_int64)]),
+    "tardis_mc_debug_bf_accumulate": (_i, [_vp, C.c_int64, _vp, _vp, _vp]),
+    "tardis_mc_last_bf_estimator_ms": (_i, [_vp] + [C.POINTER(C.c_double)] * 2),
+    "tardis_mc_bf_estimator_rates": (_i, [_vp, C.c_double, _vp]),
+    "tardis_mc_get_bf_estimator_rates": (_i, [_vp, _vp, _vp]),
     "tardis_mc_set_nlte_data": (_i, [_vp, _vp]),
     "tardis_mc_check_nlte_data": (_i, [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp]),
     "tardis_mc_get_nlte": (_i, [_vp, _vp, _vp]),

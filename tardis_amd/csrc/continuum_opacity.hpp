@@ -36,6 +36,28 @@ struct ContinuumOpacity {
     int n_current;
 };
 
+// The bracket of nu in a current block b[0 .. n): hi = clip(searchsorted(b, nu, "left"), 1, n - 1), lo = hi - 1, and the three differences of the linear
+// interpolation; continuum_interpolate gives ((v_hi hw) + (v_lo lw)) / interval.  Shared by continuum_opacity below and the accumulate pass of the
+// photo-ionisation estimators (bf_estimators.hpp).
+struct ContinuumBracket {
+    int hi;
+    double hw, lw, interval;
+};
+__device__ __forceinline__ ContinuumBracket continuum_bracket(const double *b, int n, double nu)
+{
+    int lo_i = 0, hi_i = n;  // searchsorted(b, nu, side="left"): the first index with b[index] >= nu
+    while (lo_i < hi_i) {
+        const int mid = (lo_i + hi_i) >> 1;
+        if (b[mid] < nu) lo_i = mid + 1; else hi_i = mid;
+    }
+    ContinuumBracket k;
+    k.hi = lo_i < 1 ? 1 : (lo_i > n - 1 ? n - 1 : lo_i);
+    const int lo = k.hi - 1;
+    k.interval = b[k.hi] - b[lo]; k.hw = nu - b[lo]; k.lw = b[k.hi] - nu;
+    return k;
+}
+__device__ __forceinline__ double continuum_interpolate(const ContinuumBracket &k, double v_hi, double v_lo) { return ((v_hi * k.hw) + (v_lo * k.lw)) / k.interval; }
+
 // chi_bf_tot, chi_ff and the number of current continua at nu in shell s.  chi_each / x_each (either may be null) receive, with stride
 // `each_stride` between continua, the contribution and the interpolated cross-section of every continuum, 0.0 where it is not current.
 __device__ __forceinline__ ContinuumOpacity continuum_opacity(const ContinuumTables &t, double nu, int s, double *chi_each, double *x_each, long long each_stride)
@@ -47,17 +69,10 @@ __device__ __forceinline__ ContinuumOpacity continuum_opacity(const ContinuumTab
         double chi_c = 0.0, x_c = 0.0;
         if (t.nu_min[c] <= nu && nu <= t.nu_max[c]) {
             const int p0 = t.block_edge[c], n = t.block_edge[c + 1] - p0;
-            const double *b = t.nu + p0;
-            int lo_i = 0, hi_i = n;  // searchsorted(b, nu, side="left"): the first index with b[index] >= nu
-            while (lo_i < hi_i) {
-                const int mid = (lo_i + hi_i) >> 1;
-                if (b[mid] < nu) lo_i = mid + 1; else hi_i = mid;
-            }
-            const int hi = lo_i < 1 ? 1 : (lo_i > n - 1 ? n - 1 : lo_i), lo = hi - 1;
-            const double interval = b[hi] - b[lo], hw = nu - b[lo], lw = b[hi] - nu;
-            const double chi_hi = t.chi_bf[(long long)(p0 + hi) * t.S + s], chi_lo = t.chi_bf[(long long)(p0 + lo) * t.S + s];
-            chi_c = ((chi_hi * hw) + (chi_lo * lw)) / interval;
-            x_c = ((t.x_sect[p0 + hi] * hw) + (t.x_sect[p0 + lo] * lw)) / interval;
+            const ContinuumBracket k = continuum_bracket(t.nu + p0, n, nu);
+            const int hi = k.hi, lo = hi - 1;
+            chi_c = continuum_interpolate(k, t.chi_bf[(long long)(p0 + hi) * t.S + s], t.chi_bf[(long long)(p0 + lo) * t.S + s]);
+            x_c = continuum_interpolate(k, t.x_sect[p0 + hi], t.x_sect[p0 + lo]);
             out.chi_bf_tot += chi_c;
             ++out.n_current;
         }

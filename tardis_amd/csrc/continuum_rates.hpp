@@ -52,6 +52,7 @@ struct ContinuumArgs {
     double *rates;            // [7][NC][S] out: phi_ik, alpha_sp, gamma, alpha_stim, gamma_corr, coll_ion, coll_recomb
     double *chi_bf;           // [NP][S] out
     int *counts;              // [2][CONTINUUM_COUNT_BLOCKS] out: negative gamma_corr | negative chi_bf, per workgroup
+    const double *gamma_est, *stim_est;  // [NC][S] option continuum_field 1: the transport's photo-ionisation estimators (bf_estimators.hpp); null: the dilute black body
 };
 
 // the sum of a workgroup's per-thread counts, written by thread 0 (integers: the order of the additions changes nothing)
@@ -133,7 +134,8 @@ __global__ void __launch_bounds__(256) continuum_rate_kernel(ContinuumArgs a)
             t_st += (d * (st_hi + st_lo)) / 2.0;
             nu_lo = nu_hi; sp_lo = sp_hi; g_lo = g_hi; st_lo = st_hi;
         }
-        const double alpha_sp = t_sp * phi, gamma = t_g, alpha_stim = t_st * phi;
+        // (continuum_field 1: the field the packets carried instead of the two integrals over the dilute black body; everything else as before)
+        const double alpha_sp = t_sp * phi, gamma = a.gamma_est ? a.gamma_est[e] : t_g, alpha_stim = (a.stim_est ? a.stim_est[e] : t_st) * phi;
         const double n_i = a.n_t[(long long)s * a.K + k], n_up = a.n_ion[(long long)(i + 1) * S + s], n_e = a.n_e[s];
         double gamma_corr = gamma;
         if (n_i != 0.0) gamma_corr = gamma - ((alpha_stim * n_up) * n_e) / n_i;

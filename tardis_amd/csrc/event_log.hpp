@@ -32,56 +32,94 @@ __device__ __forceinline__ void event_log_wave_init(volatile int *ws)
     ws[1] = 0;
 }
 
+// The slot of a record in a chunk pool (EventLog / SegmentLog: chunk_fill, pool_next, dropped, chunk_rows, n_chunks), shared by every appender.
+// `mask`: the lanes that append now (all of them execute this call); `mine`: this lane is one of them; chunk / used: the wave's open chunk
+// and the records in it, updated here (the same values in every lane).  Returns the slot, -1 for a lane that does not append or whose
+// record is dropped because the pool is empty (counted in *dropped).
+struct PoolSlot { long long slot; int chunk; unsigned used; };
+template <typename Log>
+__device__ __forceinline__ PoolSlot chunk_pool_claim(const Log &L, unsigned long long mask, bool mine, int chunk, unsigned used)
+{
+    const unsigned n = (unsigned)__popcll(mask);
+    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+    const int leader = __ffsll((long long)mask) - 1;
+    const bool first = mine && rank == 0;
+    const unsigned room = chunk >= 0 ? L.chunk_rows - used : 0u;
+    int fresh = -2;
+    if (n > room && chunk != -2) {
+        int c = 0;
+        if (first) {
+            if (chunk >= 0) glob(L.chunk_fill)[chunk] = L.chunk_rows;
+            c = (int)gatomic_add_u32(L.pool_next, 1u);
+        }
+        c = __shfl(c, leader);
+        fresh = (unsigned)c < L.n_chunks ? c : -2;
+    }
+    PoolSlot out;
+    out.slot = -1;
+    if (mine) {
+        if (rank < room) out.slot = (long long)chunk * L.chunk_rows + used + rank;
+        else if (fresh >= 0) out.slot = (long long)fresh * L.chunk_rows + (rank - room);
+    }
+    const unsigned long long lost = __ballot(mine && out.slot < 0);
+    if (first && lost) gatomic_add_u64(L.dropped, (unsigned long long)__popcll(lost));
+    if (n > room) { out.chunk = fresh; out.used = fresh >= 0 ? n - room : 0u; }
+    else { out.chunk = chunk; out.used = used + n; }
+    return out;
+}
+
+// The lane kernel's appenders: the lanes of a divergent wave append at different times, so the wave's {open chunk, records used} live in LDS;
+// every active lane appends.
+template <typename Log>
+__device__ __forceinline__ long long chunk_pool_claim_lds(const Log &L, volatile int *ws)
+{
+    const unsigned long long mask = __ballot(1);
+    const PoolSlot s = chunk_pool_claim(L, mask, true, ws[0], (unsigned)ws[1]);
+    if ((int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) { ws[0] = s.chunk; ws[1] = (int)s.used; }
+    return s.slot;
+}
+
+__device__ __forceinline__ void event_row_store(EventRow *row, long long packet, int event_id, int type, int status, int shell, int after_shell,
+                                                double radius, double b_nu, double b_mu, double b_e, double a_nu, double a_mu, double a_e, int absorb,
+                                                int emit)
+{
+    double2 *d = reinterpret_cast<double2 *>(row);
+    d[0] = make_double2(radius, b_nu);
+    d[1] = make_double2(b_mu, b_e);
+    d[2] = make_double2(a_nu, a_mu);
+    d[3] = make_double2(a_e, __longlong_as_double(packet));
+    int4 *q = reinterpret_cast<int4 *>(d + 4);
+    q[0] = make_int4(event_id, shell, after_shell, absorb);
+    q[1] = make_int4(emit, type | (status << 8), 0, 0);
+}
+
 // Append one row per active lane.  Called from one site per event, whatever the event's type.
 __device__ __forceinline__ void event_log_append(const EventLog &L, volatile int *ws, long long packet, int event_id, int type,
                                                  int status, int shell, int after_shell, double radius, double b_nu,
                                                  double b_mu, double b_e, double a_nu, double a_mu, double a_e, int absorb,
                                                  int emit)
 {
-    const unsigned long long mask = __ballot(1);
-    const unsigned n = (unsigned)__popcll(mask);
-    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-    const int leader = __ffsll((long long)mask) - 1;
-    const int chunk = ws[0];
-    const unsigned used = (unsigned)ws[1];
-    const unsigned room = chunk >= 0 ? L.chunk_rows - used : 0u;
-    int fresh = -2;
-    if (n > room && chunk != -2) {
-        int c = 0;
-        if (rank == 0) {
-            if (chunk >= 0) L.chunk_fill[chunk] = L.chunk_rows;
-            c = (int)atomicAdd(L.pool_next, 1u);
-        }
-        c = __shfl(c, leader);
-        fresh = (unsigned)c < L.n_chunks ? c : -2;
-    }
-    long long slot = -1;
-    if (rank < room) slot = (long long)chunk * L.chunk_rows + used + rank;
-    else if (fresh >= 0) slot = (long long)fresh * L.chunk_rows + (rank - room);
-    const unsigned long long lost = __ballot(slot < 0);
-    if (slot >= 0) {
-        double2 *d = reinterpret_cast<double2 *>(L.rows + slot);
-        d[0] = make_double2(radius, b_nu);
-        d[1] = make_double2(b_mu, b_e);
-        d[2] = make_double2(a_nu, a_mu);
-        d[3] = make_double2(a_e, __longlong_as_double(packet));
-        int4 *q = reinterpret_cast<int4 *>(d + 4);
-        q[0] = make_int4(event_id, shell, after_shell, absorb);
-        q[1] = make_int4(emit, type | (status << 8), 0, 0);
-    }
-    if (rank == 0) {
-        if (lost) atomicAdd(L.dropped, (unsigned long long)__popcll(lost));
-        if (n > room) {
-            ws[0] = fresh;
-            ws[1] = fresh >= 0 ? (int)(n - room) : 0;
-        } else {
-            ws[1] = (int)(used + n);
-        }
-    }
+    const long long slot = chunk_pool_claim_lds(L, ws);
+    if (slot >= 0) event_row_store(L.rows + slot, packet, event_id, type, status, shell, after_shell, radius, b_nu, b_mu, b_e, a_nu, a_mu, a_e, absorb, emit);
+}
+
+// The segment log of the photo-ionisation estimators: one record and its key
+__device__ __forceinline__ void segment_record_store(const SegmentLog &L, long long slot, double comov_nu, double ed, int shell)
+{
+    SegmentRecord rec;
+    rec.comov_nu = comov_nu; rec.ed = ed; rec.shell = shell; rec.pad = 0;
+    gstore(L.recs + slot, rec);
+    glob(L.keys)[slot] = (unsigned)shell;
+}
+__device__ __forceinline__ void segment_log_append(const SegmentLog &L, volatile int *ws, double comov_nu, double ed, int shell)
+{
+    const long long slot = chunk_pool_claim_lds(L, ws);
+    if (slot >= 0) segment_record_store(L, slot, comov_nu, ed, shell);
 }
 
 // At the end of the kernel (wave converged): the fill of the wave's open chunk.
-__device__ __forceinline__ void event_log_wave_close(const EventLog &L, volatile int *ws)
+template <typename Log>
+__device__ __forceinline__ void event_log_wave_close(const Log &L, volatile int *ws)
 {
     if ((threadIdx.x & 63) == 0 && ws[0] >= 0) L.chunk_fill[ws[0]] = (unsigned)ws[1];
 }

@@ -70,6 +70,24 @@ struct EventLog {
     unsigned n_chunks;
 };
 
+// The segment log of the photo-ionisation estimators (bf_estimators.hpp): one 24-byte record per move of positive length, appended to a
+// pool of chunks with the event log's mechanics (event_log.hpp: chunk_pool_claim); keys[slot] = the record's shell, what the grouping
+// kernels of estimator_log.hpp read.
+struct __attribute__((aligned(8))) SegmentRecord {
+    double comov_nu, ed;               // the comoving frequency of the move; comov_energy * distance (the distance before the FULL scaling)
+    int shell, pad;
+};
+static_assert(sizeof(SegmentRecord) == 24, "segment record layout");
+struct SegmentLog {
+    SegmentRecord *recs;               // [n_chunks][chunk_rows]; null: the estimators are off
+    unsigned *keys;                    // [n_chunks][chunk_rows]
+    unsigned *chunk_fill;              // [n_chunks]
+    unsigned *pool_next;
+    unsigned long long *dropped;
+    unsigned chunk_rows;               // (>= 64, as the event log's)
+    unsigned n_chunks;
+};
+
 // ---- the deferred last-interaction record of the wave kernel (propagate_wave.hpp, DEFER): between two interactions a lane keeps the
 // integer fields of its packet's last interaction in ONE 64-bit word of LDS -- bit 0: the interaction was a line (else electron
 // scattering), 15 bits shell, 24 bits absorbing line + 1, 24 bits emitting line + 1 (-1, "no line", packs as 0).  A problem that
@@ -151,7 +169,8 @@ struct DeviceProblem {
     unsigned long long *next_packet;  // work counter for persistent scheduling
     int debug_flags;                  // profiling experiments only: 1 = skip j_blue/Edotlu atomics, 2 = skip J/nu_bar
     EstimatorLog log;                 // line-visit log of the cooperative kernels (capacity 0: they add their terms directly)
-    EventLog evlog;                   // full r-packet tracking (lane kernel only; last, so that no other field moves)
+    EventLog evlog;                   // full r-packet tracking (behind everything older, so that no other field moves)
+    SegmentLog seglog;                // segment log of the photo-ionisation estimators (likewise)
 };
 
 // Slim by-value argument block of the cooperative kernel: only what the inner loops touch stays in SGPRs; everything

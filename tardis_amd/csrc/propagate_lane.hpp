@@ -92,9 +92,11 @@ __device__ int trace_packet(const DeviceProblem &P, Packet &p, Rng &rng, double 
 }
 
 // ---- move_r_packet + update_estimators_bulk (packets/movement.py:31-76; radfield_estimator_calcs.py:25-53)
-template <bool FULL>
+// FT with a segment log (P.seglog.recs, bf_estimators.hpp): a move of positive length appends {comov_nu, comov_energy * distance, shell} -- the distance
+// before the FULL scaling; under partial relativity the very term added to J (seg_ws: the wave's append state in LDS)
+template <bool FULL, bool FT = false>
 __device__ __forceinline__ void move_r_packet(const DeviceProblem &P, Packet &p, double distance, double *lds_J,
-                                              double *lds_nubar)
+                                              double *lds_nubar, volatile int *seg_ws = nullptr)
 {
     double velocity = p.r / P.t_exp;
     double dop = doppler_factor<FULL>(velocity, p.mu);
@@ -105,6 +107,7 @@ __device__ __forceinline__ void move_r_packet(const DeviceProblem &P, Packet &p,
         p.r = new_r;
         double comov_nu = p.nu * dop;
         double comov_energy = p.energy * dop;
+        if (FT && P.seglog.recs) segment_log_append(P.seglog, seg_ws, comov_nu, comov_energy * distance, p.shell);
         if (FULL) distance *= dop;
         if (!(P.debug_flags & 2)) {
             atomicAdd(&lds_J[p.shell], comov_energy * distance);
@@ -321,7 +324,8 @@ __device__ int trace_vpacket_volley(const DeviceProblem &P, const Packet &p, Rng
 }
 
 // ---- packet_propagation (classic/packet_propagation.py:52-318)
-// FT: full r-packet tracking -- one event_log.hpp row per trace_packet outcome (ev_ws: the wave's append state in LDS)
+// FT: full r-packet tracking -- one event_log.hpp row per trace_packet outcome where P.evlog.rows is set (ev_ws: the wave's append state in LDS) -- and / or
+// the segment log of the photo-ionisation estimators where P.seglog.recs is (its append state: ev_ws + 8)
 template <bool FULL, bool VPK, bool TRACK, bool FT = false, bool VLI = false>
 __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, double *lds_J, double *lds_nubar, double *jb,
                              double *ed, LaneCounters &cn, volatile int *ev_ws = nullptr)
@@ -372,7 +376,7 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
         double distance;
         int type, delta;
         if ((err = trace_packet<FULL>(P, p, rng, chi_e, jb, ed, distance, type, delta, cn))) return err;
-        move_r_packet<FULL>(P, p, distance, lds_J, lds_nubar);
+        move_r_packet<FULL, FT>(P, p, distance, lds_J, lds_nubar, FT ? ev_ws + 8 : nullptr);
         double ev_nu = 0.0, ev_mu = 0.0, ev_e = 0.0;
         int ev_shell = 0, ev_line = 0;
         if (FT) { ev_nu = p.nu; ev_mu = p.mu; ev_e = p.energy; ev_shell = p.shell; ev_line = p.next_line_id; }
@@ -405,7 +409,7 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
                 trk.interaction_type = IT_ESCATTERING;
             }
         }
-        if (FT) {  // one append site for the three outcomes
+        if (FT && P.evlog.rows) {  // one append site for the three outcomes
             const bool bnd = type == IT_BOUNDARY;
             event_log_append(P.evlog, ev_ws, i, n_ev, type, p.status, ev_shell, bnd ? ev_shell + delta : ev_shell, p.r, ev_nu,
                              ev_mu, ev_e, p.nu, p.mu, p.energy, type == IT_LINE ? ev_line : -1,
@@ -423,7 +427,7 @@ __device__ int propagate_one(const DeviceProblem &P, long long i, Rng &rng, doub
     // set_packet_collection_output (modes/montecarlo_transport.py:70-90)
     P.out_nu[i] = p.nu;
     P.out_e[i] = (p.status == ST_REABSORBED) ? -p.energy : p.energy;
-    if (FT) P.evlog.counts[i] = n_ev;
+    if (FT && P.evlog.rows) P.evlog.counts[i] = n_ev;
     if (TRACK) {
         P.li_radius[i] = trk.radius; P.li_nu[i] = trk.nu; P.li_energy[i] = trk.energy;
         P.li_before_nu[i] = trk.before_nu; P.li_before_mu[i] = trk.before_mu; P.li_before_energy[i] = trk.before_energy;
@@ -448,9 +452,9 @@ __global__ void __launch_bounds__(256) propagate_lane_kernel(DeviceProblem P)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *lds_J = lds, *lds_nubar = lds + P.n_shells;
     for (int s = threadIdx.x; s < 2 * P.n_shells; s += blockDim.x) lds[s] = 0.0;
-    // FT: after J / nu_bar, two ints per wave (the launch adds 8 * 4 bytes of LDS)
+    // FT: after J / nu_bar, two ints per wave for the event log, then two per wave for the segment log (the launch adds 16 * 4 bytes of LDS)
     volatile int *ev_ws = FT ? reinterpret_cast<volatile int *>(lds + 2 * P.n_shells) + 2 * (threadIdx.x >> 6) : nullptr;
-    if (FT && (threadIdx.x & 63) == 0) event_log_wave_init(ev_ws);
+    if (FT && (threadIdx.x & 63) == 0) { event_log_wave_init(ev_ws); event_log_wave_init(ev_ws + 8); }
     __syncthreads();
 
     const long long n_threads = (long long)gridDim.x * blockDim.x;
@@ -475,7 +479,8 @@ __global__ void __launch_bounds__(256) propagate_lane_kernel(DeviceProblem P)
         }
     }
     __syncthreads();
-    if (FT) event_log_wave_close(P.evlog, ev_ws);
+    if (FT && P.evlog.rows) event_log_wave_close(P.evlog, ev_ws);
+    if (FT && P.seglog.recs) event_log_wave_close(P.seglog, ev_ws + 8);
     for (int s = threadIdx.x; s < P.n_shells; s += blockDim.x) {
         if (lds_J[s] != 0.0) atomic_add_f64(&P.J[s], lds_J[s]);
         if (lds_nubar[s] != 0.0) atomic_add_f64(&P.nubar[s], lds_nubar[s]);

@@ -39,6 +39,8 @@ struct PlanInput {
     int debug_flags;
     // the screening tables: whether they are built, and whether they then hold a negative optical depth
     bool pfx_valid, pfx_negative;
+    // option bf_estimators (the segment log of the photo-ionisation estimators): lives in the instantiations full tracking runs on, and routes as track_full does
+    bool bf_estimators;
 };
 
 struct Plan {
@@ -113,8 +115,9 @@ inline Plan plan_propagate(const PlanInput &in)
     if (in.prob_negative && variant == 4) variant = 1;
     // full r-packet tracking: the wave-owner kernel with group sweeps (variant 2, its default launch shape) where it can run the call --
     // sorted lines, monotone probabilities, no surviving v-packets, at most 32 v-packets, the compact walk tables, no cross-check flags --
-    // else the lane kernel (variants 1, 3 and 4 are not instrumented)
-    if (in.track_full) {
+    // else the lane kernel (variants 1, 3 and 4 are not instrumented).  The segment log of the photo-ionisation estimators sits in the same instantiations.
+    const bool instrumented = in.track_full || in.bf_estimators;
+    if (instrumented) {
         const bool wave_ok = in.lines_sorted && !in.prob_negative && !(vpk && (in.number_of_vpackets > 32 || in.survival_probability > 0.0)) &&
                              (in.line_interaction_type == 0 || in.have_walk_tables) && !(in.debug_flags & DBG_WAVE_CROSS_CHECK) && in.n_packets < (1LL << 31);
         variant = (wave_ok && variant != 0) ? 2 : 0;
@@ -136,7 +139,7 @@ inline Plan plan_propagate(const PlanInput &in)
             if (in.variant >= 0)
                 return plan_error(p, "n_shells * n_lines reaches 2^32: the line-visit log of the wave kernels (variants 2-4) "
                                      "indexes (shell, line) in 32 bits; use variant 1 or the automatic variant");
-            if (in.track_full) { cooperative = false; variant = 0; }  // (the group kernel has no full tracking)
+            if (instrumented) { cooperative = false; variant = 0; }  // (the group kernel has no full tracking)
             else { variant = 1; w64 = true; }
         } else if (is_wave(variant) && in.line_interaction_type != 0 && !in.have_walk_tables) {
             // (the compact walk tables were not built for these tables: the fp64 walks are only in the 32-bit cross-check instantiations)

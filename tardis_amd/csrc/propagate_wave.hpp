@@ -842,7 +842,8 @@ __device__ __forceinline__ int vp_screen_step(const GroupArgs &P, Draw &&draw, i
 // profiles/r04_estimator_partition.txt) is gone.
 // VLI: the v-packet log entries also carry the r-packet's last interaction (option vpacket_last_interaction); needs VPK and TRACK
 // FT: full r-packet tracking (event_log.hpp) -- one row per trace outcome, the row's ordinal from trk_count + trk_boundary (which travel
-// with the lane through suspensions, epochs and drain compaction); needs TRACK
+// with the lane through suspensions, epochs and drain compaction); needs TRACK.  The rows are written where W->D.evlog.rows is set; where
+// W->D.seglog.recs is, every move of positive length appends a record to the segment log of the photo-ionisation estimators (bf_estimators.hpp).
 template <bool FULL, bool TRACK, int G, bool VPK, bool LS = false, bool XWALK = true, int WPE = (VPK ? 3 : 4), int NT = 0, bool SL = false,
           bool FT = false, bool WIDE = false, bool VLI = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) propagate_wave_kernel(WaveHot H, const WaveCold *__restrict__ W)
@@ -926,6 +927,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     // FT: the wave's open chunk of the event-row pool (wave-uniform; closed when the wave leaves the launch) and this lane's row of the pass
     int ev_chunk = -1;  // -1: none yet; -2: the pool is empty
     unsigned ev_used = 0;
+    int seg_chunk = -1;  // likewise, of the segment log
+    unsigned seg_used = 0;
     bool ev_row = false;
     int ev_type = 0, ev_shell = 0, ev_after = 0, ev_absorb = -1, ev_emit = -1;
     double ev_bnu = 0.0, ev_bmu = 0.0, ev_be = 0.0;
@@ -1257,6 +1260,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             }
         }
         TMC_SEC(0)
+        // ---- the segment log: a record per finished trace that moves (the wave is converged here; the values are those of the J update below)
+        if (FT && W->D.seglog.recs) {
+            const bool seg = ready && !err && distance > 0.0;
+            const unsigned long long m = __ballot(seg);
+            if (m) {
+                const SegmentLog &L = W->D.seglog;
+                const PoolSlot ps = chunk_pool_claim(L, m, seg, seg_chunk, seg_used);
+                if (ps.slot >= 0) segment_record_store(L, ps.slot, p.nu * dop, (p.energy * dop) * distance, p.shell);
+                seg_chunk = ps.chunk; seg_used = ps.used;
+            }
+        }
         // ---- epilogue of the finished traces: move, estimators, boundary / scattering
         if (ready && !err) {
             // move_r_packet + update_estimators_bulk (packets/movement.py:31-76)
@@ -1651,7 +1665,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             if (err || p.status != ST_IN_PROCESS) {
                 const long long i = chunk_first + pkt;
                 const DeviceProblem *C = &W->D;
-                if (FT) glob(C->evlog.counts)[i] = trk_count + trk_boundary;  // (rows written for the packet, also when it failed)
+                if (FT && C->evlog.rows) glob(C->evlog.counts)[i] = trk_count + trk_boundary;  // (rows written for the packet, also when it failed)
                 auto empty_record = []() {  // (the unpacking fills in NaN / -1 / 0)
                     TrackerRecord rec;
                     rec.before_nu = rec.before_mu = rec.before_energy = rec.radius = rec.after_mu = 0.0;
@@ -1684,39 +1698,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
         }
         // ---- full tracking: the rows of this pass's finished events, ranked inside the wave's open chunk (the wave is converged here)
         if (FT) {
-            const unsigned long long m = __ballot(ev_row);
+            const unsigned long long m = W->D.evlog.rows ? __ballot(ev_row) : 0ull;
             if (m) {
                 const EventLog &L = W->D.evlog;
-                const unsigned n = (unsigned)__popcll(m);
-                const unsigned rank = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                const unsigned room = ev_chunk >= 0 ? L.chunk_rows - ev_used : 0u;
-                int fresh = -2;
-                if (n > room && ev_chunk != -2) {
-                    unsigned c = 0;
-                    if (lane == 0) {
-                        if (ev_chunk >= 0) glob(L.chunk_fill)[ev_chunk] = L.chunk_rows;
-                        c = gatomic_add_u32(L.pool_next, 1u);
-                    }
-                    c = (unsigned)__builtin_amdgcn_readfirstlane((int)c);
-                    fresh = c < L.n_chunks ? (int)c : -2;
-                }
-                long long slot = -1;
-                if (rank < room) slot = (long long)ev_chunk * L.chunk_rows + ev_used + rank;
-                else if (fresh >= 0) slot = (long long)fresh * L.chunk_rows + (rank - room);
-                if (ev_row && slot >= 0) {
-                    double2 *d = reinterpret_cast<double2 *>(L.rows + slot);
-                    d[0] = make_double2(p.r, ev_bnu);
-                    d[1] = make_double2(ev_bmu, ev_be);
-                    d[2] = make_double2(p.nu, p.mu);
-                    d[3] = make_double2(p.energy, __longlong_as_double(chunk_first + pkt));
-                    int4 *q = reinterpret_cast<int4 *>(d + 4);
-                    q[0] = make_int4(trk_count + trk_boundary - 1, ev_shell, ev_after, ev_absorb);
-                    q[1] = make_int4(ev_emit, ev_type | (p.status << 8), 0, 0);
-                }
-                const unsigned long long lost = __ballot(ev_row && slot < 0);
-                if (lane == 0 && lost) gatomic_add_u64(L.dropped, (unsigned long long)__popcll(lost));
-                if (n > room) { ev_chunk = fresh; ev_used = fresh >= 0 ? n - room : 0u; }
-                else ev_used += n;
+                const PoolSlot ps = chunk_pool_claim(L, m, ev_row, ev_chunk, ev_used);
+                if (ps.slot >= 0)
+                    event_row_store(L.rows + ps.slot, chunk_first + pkt, trk_count + trk_boundary - 1, ev_type, p.status, ev_shell, ev_after, p.r, ev_bnu, ev_bmu,
+                                    ev_be, p.nu, p.mu, p.energy, ev_absorb, ev_emit);
+                ev_chunk = ps.chunk; ev_used = ps.used;
             }
             ev_row = false;
         }
@@ -2407,6 +2396,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 
     if (!SL && lane == 0 && W->log.region_capacity > 0 && log_chunk >= 0) glob(W->log.region_count)[log_chunk] = min(log_used, W->log.region_capacity);
     if (FT && lane == 0 && ev_chunk >= 0) glob(W->D.evlog.chunk_fill)[ev_chunk] = ev_used;
+    if (FT && lane == 0 && seg_chunk >= 0) glob(W->D.seglog.chunk_fill)[seg_chunk] = seg_used;
     if (SL && W->log.region_capacity > 0)
         for (int s = lane; s < H.n_shells; s += 64)
             if (lds_lchunk[s] >= 0) glob(W->log.region_count)[lds_lchunk[s]] = min(lds_lused[s], W->log.region_capacity);

@@ -24,6 +24,7 @@
 #include "mc_device.hpp"
 #include "propagate_lane.hpp"
 #include "event_log.hpp"
+#include "bf_estimators.hpp"
 #include "propagate_group.hpp"
 #include "estimator_log.hpp"
 #include "estimator_partition.hpp"
@@ -550,6 +551,23 @@ struct TardisMcContext {
         hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start | points | blocks | table (tardis_mc_last_cooling_ms)
         void release() { release_buffers(y_cool, y_em, fb_cdf, rates, shell, k_cdf, counts); destroy_events(ev); }
     } ck;
+    // Photo-ionisation and heating estimators (bf_estimators.hpp).  Per set_bf_estimators: t_e [S] and the zeroed tables [5][NC][S] with {records, dropped}.
+    // Per propagate call with the option on: the segment log's pool (records, keys, chunk fills, {pool_next, dropped}) and the pass's grouping
+    // (bin counts / starts / fills / slice starts, the sorted slots).  Per bf_estimator_rates: gamma_est | stim_est [2][NC][S].
+    struct BfEstimators {
+        bool on = false;                                 // option bf_estimators
+        long long seg_capacity = 0;                      // option segment_log_capacity: records (0: automatic, 96 per packet)
+        long long seg_max_bytes = 16LL << 30;            // option segment_log_max_bytes: the bound on the log's device memory
+        bool seg_keep = false;                           // option segment_log_keep (tests): tardis_mc_get_segment_log may read the last call's records
+        int continuum_field = 0;                         // option continuum_field: 0 the dilute black body, 1 the estimators' rates
+        DevBuf t_e, tables, totals, rates;
+        DevBuf seg_recs, seg_keys, seg_fill, seg_state, seg_sorted, seg_bins;
+        bool have = false, rates_valid = false, seg_valid = false, timed = false;
+        long long seg_slots = 0;
+        unsigned seg_n_chunks = 0;
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // start | grouped | accumulated (tardis_mc_last_bf_estimator_ms)
+        void release() { release_buffers(t_e, tables, totals, rates, seg_recs, seg_keys, seg_fill, seg_state, seg_sorted, seg_bins); destroy_events(ev); }
+    } bf;
     // RCCL
     void *comm = nullptr;
     int rank = 0, world = 1;
@@ -982,7 +1000,7 @@ void drop_from(TardisMcContext *ctx, Rung rung)
 {
     switch (rung) {
     case RUNG_LINE_DATA: ctx->ou.have = ctx->ou.valid = false; [[fallthrough]];
-    case RUNG_PLASMA_DATA: ctx->pl.have = ctx->pl.valid = false; ctx->he.have = ctx->he.valid = false; ctx->ct.have = ctx->ct.valid = false; [[fallthrough]];  // (the ionisation options and the continuum data sit beside the NLTE data, on the plasma data)
+    case RUNG_PLASMA_DATA: ctx->pl.have = ctx->pl.valid = false; ctx->he.have = ctx->he.valid = false; ctx->ct.have = ctx->ct.valid = false; ctx->bf.have = ctx->bf.rates_valid = false; [[fallthrough]];  // (the ionisation options and the continuum data sit beside the NLTE data, on the plasma data; the photo-ionisation estimators on the continuum data)
     case RUNG_NLTE_DATA: ctx->nl.have = ctx->nl.valid = false; [[fallthrough]];
     case RUNG_COLLISION_DATA: ctx->nc.have = ctx->nc.valid = false;
     }
@@ -1027,7 +1045,7 @@ void drop_products(TardisMcContext *ctx, Cause cause)
         ctx->vl.vl_valid = ctx->vl.vl_consolidated = false;
         break;
     case PROPAGATE_BEGINS:
-        ctx->el.ev_valid = ctx->pk.li_valid = ctx->sf.valid = ctx->rs.valid = false;
+        ctx->el.ev_valid = ctx->pk.li_valid = ctx->sf.valid = ctx->rs.valid = ctx->bf.seg_valid = false;
         ctx->vl.vl_valid = ctx->vl.vl_consolidated = false;
         break;
     }
@@ -1078,7 +1096,7 @@ mc::DeviceProblem make_device_problem(TardisMcContext *ctx)
         for (int k = 0; k < 5; ++k) *g[k] = ctx->pk.li_i64[k].as<long long>();
         P.li_rec = ctx->pk.li_rec.as<uint4>();
     }
-    if (ctx->el.track_full) P.li_rec = ctx->pk.li_rec.as<uint4>();  // (the tracked wave kernel counts rows with the tracker, TRACK on)
+    if (ctx->el.track_full || ctx->bf.on) P.li_rec = ctx->pk.li_rec.as<uint4>();  // (the tracked wave kernel counts rows with the tracker, TRACK on)
     P.n_shells = ctx->n_shells;
     P.r_inner = ctx->r_inner.as<double>(); P.r_outer = ctx->r_outer.as<double>();
     P.t_exp = ctx->t_exp;
@@ -1283,12 +1301,12 @@ size_t wave_kernel_lds(const WaveKernelKey &k, int n_shells)  // dynamic LDS of 
 
 int launch_lane(TardisMcContext *ctx, const mc::DeviceProblem &P, int blocks, size_t lds)
 {
-    const bool ft = P.evlog.rows != nullptr;  // full r-packet tracking: 8 ints of LDS per workgroup for the waves' append state
+    const bool ft = P.evlog.rows != nullptr || P.seglog.recs != nullptr;  // full r-packet tracking and / or the segment log: 8 ints of LDS per workgroup and log for the waves' append state
     const LaneKernelKey key{ctx->cfg.enable_full_relativity != 0, ctx->cfg.number_of_vpackets > 0, ctx->pk.track, ft, vlog_li_call(ctx)};
     const LaneKernelFn k = find_kernel(LANE_KERNELS, key);
     if (!k) return fail(ctx, TARDIS_MC_ERR_STATE, "propagate: no such instantiation of the lane kernel: FULL, VPK, TRACK, FT, VLI = %s", key_text(key).c_str());
     record_kernel(ctx, 0, key);
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds + (ft ? 32 : 0), ctx->stream, P);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds + (ft ? 64 : 0), ctx->stream, P);
     HIP_TRY(ctx, hipGetLastError());
     return TARDIS_MC_OK;
 }
@@ -1334,6 +1352,88 @@ int setup_event_log(TardisMcContext *ctx, mc::DeviceProblem &P, long long n_wave
     return TARDIS_MC_OK;
 }
 
+// The segment log of the photo-ionisation estimators (option bf_estimators): sized like the event log -- the records the caller asked for (automatic: 96 per
+// packet) plus one chunk per wave and launch for the partly filled last chunks -- with a key and a sorted slot per record for the pass.  The grouping
+// kernels index the slots in 32 bits and keep a histogram of the shells in LDS.
+int setup_segment_log(TardisMcContext *ctx, mc::DeviceProblem &P, long long n_waves)
+{
+    const long long n = ctx->pk.n_packets, chunk_rows = (long long)ctx->el.ev_chunk_rows;
+    const long long slot_bytes = (long long)sizeof(mc::SegmentRecord) + 2 * (long long)sizeof(unsigned);  // record, key, sorted slot
+    const long long cap = ctx->bf.seg_capacity > 0 ? ctx->bf.seg_capacity : std::max<long long>(1024, 96 * std::max<long long>(n, 1));
+    const long long chunks = (cap + chunk_rows - 1) / chunk_rows + n_waves;
+    const long long slots = chunks * chunk_rows;
+    const long long need = slots * slot_bytes + chunks * (long long)sizeof(unsigned);
+    if (need > ctx->bf.seg_max_bytes)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT,
+                    "photo-ionisation estimators: a segment log of %lld records for %lld packets needs %.2f GiB of device memory, more than the bound of "
+                    "%.2f GiB (option segment_log_max_bytes); propagate fewer packets per call or raise the bound",
+                    cap, n, need / 1073741824.0, ctx->bf.seg_max_bytes / 1073741824.0);
+    if (slots >= (1LL << 32))  // (with it: fewer than 2^31 chunks, of at least 64 records each)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT,
+                    "photo-ionisation estimators: a segment log of %lld records for %lld packets has %lld slots, and the pass indexes the slots in 32 bits; "
+                    "propagate fewer packets per call", cap, n, slots);
+    if (ctx->n_shells > mc::EST_MAX_BINS)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "photo-ionisation estimators: more than %d shells (the pass groups the records by shell in LDS)", mc::EST_MAX_BINS);
+    HIP_TRY(ctx, ctx->bf.seg_recs.ensure((size_t)slots * sizeof(mc::SegmentRecord)));
+    HIP_TRY(ctx, ctx->bf.seg_keys.ensure((size_t)slots * sizeof(unsigned)));
+    HIP_TRY(ctx, ctx->bf.seg_sorted.ensure((size_t)slots * sizeof(unsigned)));
+    HIP_TRY(ctx, ctx->bf.seg_fill.ensure((size_t)chunks * sizeof(unsigned)));
+    HIP_TRY(ctx, ctx->bf.seg_state.ensure(2 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->bf.seg_fill.p, 0, (size_t)chunks * sizeof(unsigned), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->bf.seg_state.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    P.seglog.recs = ctx->bf.seg_recs.as<mc::SegmentRecord>();
+    P.seglog.keys = ctx->bf.seg_keys.as<unsigned>();
+    P.seglog.chunk_fill = ctx->bf.seg_fill.as<unsigned>();
+    P.seglog.pool_next = ctx->bf.seg_state.as<unsigned>();
+    P.seglog.dropped = ctx->bf.seg_state.as<unsigned long long>() + 1;
+    P.seglog.chunk_rows = (unsigned)chunk_rows;
+    P.seglog.n_chunks = (unsigned)chunks;
+    ctx->problem_host.seglog = P.seglog;  // (what the pass behind the call and tardis_mc_get_segment_log read)
+    ctx->bf.seg_slots = slots;
+    ctx->bf.seg_n_chunks = (unsigned)chunks;
+    return TARDIS_MC_OK;
+}
+
+// The accumulate pass of the photo-ionisation estimators (bf_estimators.hpp) on a pool of records -- a call's segment log, or the one chunk of
+// tardis_mc_debug_bf_accumulate -- into the resident tables: the slots grouped by shell, the slices accumulated, the two totals advanced.
+int bf_accumulate_pass(TardisMcContext *ctx, const mc::SegmentRecord *recs, const unsigned *keys, const unsigned *chunk_fill, int n_chunks, unsigned chunk_rows,
+                       const unsigned long long *dropped)
+{
+    const int S = ctx->n_shells;
+    int rc;
+    if ((rc = ensure_events(ctx, ctx->bf.ev))) return rc;
+    HIP_TRY(ctx, ctx->bf.seg_sorted.ensure((size_t)n_chunks * chunk_rows * sizeof(unsigned)));
+    HIP_TRY(ctx, ctx->bf.seg_bins.ensure(4 * ((size_t)S + 1) * sizeof(unsigned)));
+    unsigned *bin_count = ctx->bf.seg_bins.as<unsigned>(), *bin_start = bin_count + (S + 1), *bin_fill = bin_start + (S + 1), *slice_start = bin_fill + (S + 1);
+    unsigned *sorted = ctx->bf.seg_sorted.as<unsigned>();
+    const unsigned blocks = (unsigned)std::max(1, std::min(n_chunks, 1024));
+    const size_t hist = (size_t)S * sizeof(unsigned);
+    HIP_TRY(ctx, hipEventRecord(ctx->bf.ev[0], ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(bin_count, 0, ((size_t)S + 1) * sizeof(unsigned), ctx->stream));
+    hipLaunchKernelGGL(mc::bin_count_kernel, dim3(blocks), dim3(256), hist, ctx->stream, keys, chunk_fill, n_chunks, chunk_rows, S, bin_count);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(mc::bin_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, (const unsigned *)bin_count, S, bin_start, bin_fill, slice_start);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(mc::bin_scatter_kernel, dim3(blocks), dim3(256), hist, ctx->stream, keys, chunk_fill, n_chunks, chunk_rows, S, bin_fill, sorted);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->bf.ev[1], ctx->stream));
+    mc::BfAccumulateArgs a{};
+    a.S = S; a.NC = (int)ctx->ct.continua; a.h = H_PLANCK; a.k_b = K_BOLTZMANN;
+    a.block_edge = ctx->ct.block_edge.as<int>(); a.nu = ctx->ct.nu.as<double>(); a.x_sect = ctx->ct.x_sect.as<double>();
+    a.nu_min = ctx->ct.nu_min.as<double>(); a.nu_max = ctx->ct.nu_max.as<double>(); a.t_e = ctx->bf.t_e.as<double>();
+    a.recs = recs; a.sorted_index = sorted; a.bin_start = bin_start; a.slice_start = slice_start; a.tables = ctx->bf.tables.as<double>();
+    // (a workgroup per slice, grid-stride beyond: the slices are at most records / EST_SLICE + S)
+    const long long max_slices = ((long long)n_chunks * chunk_rows) / mc::EST_SLICE + S;
+    const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+    hipLaunchKernelGGL(mc::bf_accumulate_kernel, dim3((unsigned)std::max<long long>(1, std::min<long long>(max_slices, 8LL * cus))), dim3(mc::BF_THREADS), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(mc::bf_totals_kernel, dim3(1), dim3(1), 0, ctx->stream, (const unsigned *)(bin_start + S), dropped, ctx->bf.totals.as<unsigned long long>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->bf.ev[2], ctx->stream));
+    ctx->bf.timed = true;
+    return TARDIS_MC_OK;
+}
+
 // ---- tardis_mc_propagate: what the entry point hands to the runner of its call (run_lane_kernel / run_group_kernel / run_wave_kernel)
 struct PropagateCall {
     plan::Plan plan;
@@ -1354,6 +1454,7 @@ plan::PlanInput plan_input(const TardisMcContext *ctx)
     in.lines_sorted = ctx->ot.lines_sorted; in.prob_negative = ctx->ot.prob_negative; in.have_walk_tables = ctx->wt.have_walk_tables;
     in.variant = ctx->variant; in.table_offsets = ctx->table_offsets; in.vpacket_screening = ctx->sc.vpacket_screening;
     in.vpk_wave_min_packets = ctx->vpk_wave_min_packets; in.track_full = ctx->el.track_full; in.debug_flags = ctx->debug_flags;
+    in.bf_estimators = ctx->bf.on;
     in.pfx_valid = ctx->sc.pfx_valid; in.pfx_negative = ctx->sc.pfx_negative;
     return in;
 }
@@ -1541,7 +1642,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
     // Measured (profiles/r05_vpk_wide_registers.txt): 3727-3766 vs 4442-4450 ms per 1e7 packets of the configs[4] shape (-16 %).  Option 2 forces
     // it (then eight waves per CU whatever the LDS allows), 0 keeps the 168-VGPR instantiation.
     // (with lane sweeps: variant 3 under partial relativity)
-    if (vpk && !k.xwalk && !w64 && !ctx->el.track_full && (k.lane_sweep || GW == 16 || GW == 8) &&
+    if (vpk && !k.xwalk && !w64 && !ctx->el.track_full && !ctx->bf.on && (k.lane_sweep || GW == 16 || GW == 8) &&
         ((ctx->vpk_wide_registers == 1 && w.waves_per_cu <= 8) || ctx->vpk_wide_registers == 2))
         k.waves_per_simd = 2;
     // which lane-sweep instantiation (see ls_waves_per_simd in the context), and whether on the interleaved sweep table: the production lane-sweep instantiations only
@@ -1553,7 +1654,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
         if (!w64 && ctx->sw.sweep_table != 0) {
             // (room for the block-skip tables only where this call may end up using them: what is known of its instantiation so far, the rest assumed in favour)
             plan::SkipInput room{};
-            room.sweep_skip = ctx->sw.sweep_skip; room.lane_sweep = true; room.full_relativity = full; room.full_tracking = ctx->el.track_full;
+            room.sweep_skip = ctx->sw.sweep_skip; room.lane_sweep = true; room.full_relativity = full; room.full_tracking = ctx->el.track_full || ctx->bf.on;
             room.waves_per_simd = k.waves_per_simd; room.nt = (ctx->sw.sweep_table == 2 && !w.ls3) ? 2 : 1; room.line_scattering = !c.disable_line_scattering;
             room.twelve_wave_skip = TMC_SWEEP_SKIP_12 != 0;
             rc = build_sweep_table(ctx, plan::plan_sweep_skip(room));
@@ -1577,7 +1678,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
     if (TMC_SWEEP_SKIP != 0) {  // (a build without the kernel's code reports off)
         plan::SkipInput si{};
         si.sweep_skip = ctx->sw.sweep_skip; si.lane_sweep = k.lane_sweep; si.vpk = vpk; si.full_relativity = full; si.wide = w64; si.cross_check = k.xwalk;
-        si.shell_log = k.shell_log; si.full_tracking = ctx->el.track_full; si.waves_per_simd = k.waves_per_simd; si.nt = k.nt;
+        si.shell_log = k.shell_log; si.full_tracking = ctx->el.track_full || ctx->bf.on; si.waves_per_simd = k.waves_per_simd; si.nt = k.nt;
         si.line_scattering = !c.disable_line_scattering; si.nt_negative = ctx->sw.nt_negative; si.pfx_negative = false;
         si.twelve_wave_skip = TMC_SWEEP_SKIP_12 != 0;
         if (plan::plan_sweep_skip(si)) {
@@ -1590,7 +1691,7 @@ int choose_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs 
         }
         ctx->sw.last_sweep_skip = w.sweep_skip ? 1 : 0;
     }
-    if (ctx->el.track_full) {  // the tracked instantiations: group sweeps of 16 lanes, compact walks, default register budget
+    if (ctx->el.track_full || ctx->bf.on) {  // the tracked instantiations: group sweeps of 16 lanes, compact walks, default register budget
         k.full_tracking = true; k.track = true; k.width = 16;
     }
     // 64-bit row offsets: the production shapes above without the interleaved sweep table, the shell-sorted log and the two-waves-per-SIMD
@@ -2173,6 +2274,7 @@ int run_wave_kernel(TardisMcContext *ctx, PropagateCall &call, mc::GroupArgs &P)
         rc = setup_event_log(ctx, ctx->problem_host, 4LL * waves);
         if (rc) return rc;
     }
+    if (ctx->bf.on && (rc = setup_segment_log(ctx, ctx->problem_host, 4LL * waves))) return rc;
     if (ctx->wv.events_host && ctx->wv.ev_events && hipEventQuery(ctx->wv.ev_events) == hipSuccess && ctx->wv.events_host[1] > 0)
         ctx->wv.traces_per_packet = (double)ctx->wv.events_host[0] / (double)ctx->wv.events_host[1];
     if (1.1 * ctx->wv.traces_per_packet > ctx->wv.log_budget_per_packet) ctx->wv.log_budget_per_packet = 1.3 * ctx->wv.traces_per_packet;
@@ -2430,9 +2532,13 @@ int run_lane_kernel(TardisMcContext *ctx, const PropagateCall &call)
     HIP_TRY(ctx, ctx->rng_state.ensure((size_t)blocks * 256 * mc::MT_N * sizeof(uint32_t)));
     mc::DeviceProblem P = make_device_problem(ctx);
     const size_t lds = 2 * (size_t)ctx->n_shells * sizeof(double);
-    if (lds + (ctx->el.track_full ? 32 : 0) > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
+    if (lds + ((ctx->el.track_full || ctx->bf.on) ? 64 : 0) > 64 * 1024) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "n_shells too large for the LDS J/nu_bar accumulator");
     if (ctx->el.track_full) {
         int rc = setup_event_log(ctx, P, (long long)blocks * 4);
+        if (rc) return rc;
+    }
+    if (ctx->bf.on) {
+        int rc = setup_segment_log(ctx, P, (long long)blocks * 4);
         if (rc) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
@@ -2488,7 +2594,7 @@ void tardis_mc_destroy(TardisMcContext *ctx)
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
     ctx->ot.release(); ctx->wt.release(); ctx->sc.release(); ctx->sw.release(); ctx->es.release(); ctx->pk.release(); ctx->vl.release(); ctx->el.release();
     ctx->wv.release(); ctx->lt.release(); ctx->rs.release(); ctx->sf.release(); ctx->pg.release();
-    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release(); ctx->he.release(); ctx->ct.release(); ctx->ck.release(); ctx->mo.release();
+    ctx->ou.release(); ctx->pl.release(); ctx->nl.release(); ctx->nc.release(); ctx->he.release(); ctx->ct.release(); ctx->ck.release(); ctx->bf.release(); ctx->mo.release();
     ctx->release();
     delete ctx;
 }
@@ -2508,6 +2614,14 @@ int tardis_mc_set_option(TardisMcContext *ctx, const char *name, long long value
     else if (n == "vpacket_last_interaction") ctx->vl.vlog_li = value != 0;
     else if (n == "event_log_capacity") ctx->el.evlog_capacity = std::max<long long>(0, value);
     else if (n == "event_log_max_bytes") ctx->el.evlog_max_bytes = std::max<long long>(1LL << 20, value);
+    else if (n == "bf_estimators") ctx->bf.on = value != 0;
+    else if (n == "segment_log_capacity") ctx->bf.seg_capacity = std::max<long long>(0, value);
+    else if (n == "segment_log_max_bytes") ctx->bf.seg_max_bytes = std::max<long long>(1LL << 20, value);
+    else if (n == "segment_log_keep") ctx->bf.seg_keep = value != 0;
+    else if (n == "continuum_field") {
+        if (value != 0 && value != 1) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "option continuum_field is 0 (the dilute black body) or 1 (the estimators' rates)");
+        ctx->bf.continuum_field = (int)value;
+    }
     else if (n == "debug_flags") ctx->debug_flags = (int)value;
     else if (n == "drain_split") ctx->wv.drain_split = value ? 1 : 0;
     else if (n == "drain_compact") ctx->wv.drain_compact = (int)std::max<long long>(0, std::min<long long>(48, value));
@@ -2575,6 +2689,7 @@ int tardis_mc_set_geometry(TardisMcContext *ctx, const TardisMcGeometry *g)
         return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid geometry");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     drop_products(ctx, GEOMETRY_REPLACED);
+    if ((int)g->n_shells != ctx->n_shells) ctx->bf.have = ctx->bf.rates_valid = false;  // (the photo-ionisation estimators' tables are [NC][S])
     int rc;
     if ((rc = upload(ctx, ctx->r_inner, g->r_inner, (size_t)g->n_shells))) return rc;
     if ((rc = upload(ctx, ctx->r_outer, g->r_outer, (size_t)g->n_shells))) return rc;
@@ -3191,6 +3306,10 @@ int tardis_mc_reset_estimators(TardisMcContext *ctx)
     if (!ctx->es.est_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "set_opacity and set_config must precede reset_estimators");
     EstLayout e = est_layout(ctx->es.est_S, ctx->es.est_L, ctx->es.est_G, ctx->es.est_copies);
     HIP_TRY(ctx, hipMemsetAsync(ctx->es.est.p, 0, e.total * sizeof(double), ctx->stream));
+    if (ctx->bf.have && ctx->ct.have) {  // (the rates of tardis_mc_bf_estimator_rates stay)
+        HIP_TRY(ctx, hipMemsetAsync(ctx->bf.tables.p, 0, (size_t)mc::BF_TABLES * (size_t)ctx->ct.continua * (size_t)ctx->n_shells * sizeof(double), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->bf.totals.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    }
     ctx->es.est_propagated = false;
     HIP_TRY(ctx, ctx->counters.ensure(TARDIS_MC_N_COUNTERS * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, TARDIS_MC_N_COUNTERS * sizeof(unsigned long long), ctx->stream));
@@ -3202,6 +3321,8 @@ int tardis_mc_propagate(TardisMcContext *ctx)
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->have_geometry || !ctx->have_opacity || !ctx->have_config || !ctx->have_packets)
         return fail(ctx, TARDIS_MC_ERR_STATE, "set_geometry/set_opacity/set_config/set_packets must precede propagate");
+    if (ctx->bf.on && !(ctx->bf.have && ctx->ct.have))
+        return fail(ctx, TARDIS_MC_ERR_STATE, "the option bf_estimators needs tardis_mc_set_bf_estimators (after set_continuum_data) before propagate");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->wv.compactions = 0;
     drop_products(ctx, PROPAGATE_BEGINS);
@@ -3229,7 +3350,7 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         for (auto &b : ctx->pk.li_i64) HIP_TRY(ctx, b.ensure(P * sizeof(long long)));
         HIP_TRY(ctx, ctx->pk.li_rec.ensure(P * 64));
     }
-    if (ctx->el.track_full) HIP_TRY(ctx, ctx->pk.li_rec.ensure((size_t)std::max<long long>(ctx->pk.n_packets, 1) * 64));
+    if (ctx->el.track_full || ctx->bf.on) HIP_TRY(ctx, ctx->pk.li_rec.ensure((size_t)std::max<long long>(ctx->pk.n_packets, 1) * 64));
     // v-packet log buffers
     if (c.enable_vpacket_tracking && call.vpk) {
         // (sized for the current call: the engine is cached per process, a later, larger run must not inherit a smaller log)
@@ -3293,6 +3414,12 @@ int tardis_mc_propagate(TardisMcContext *ctx)
         ctx->lt.ls_tune.pending = call.tune_slot;
     }
     ctx->el.ev_valid = ctx->el.track_full;  // (a call that failed half-way leaves no event log to read)
+    if (ctx->bf.on && ctx->pk.n_packets > 0) {  // the accumulate pass, behind the last launch and behind every existing timer's last event; it consumes the log
+        const mc::SegmentLog &L = ctx->problem_host.seglog;
+        rc = bf_accumulate_pass(ctx, L.recs, L.keys, L.chunk_fill, (int)L.n_chunks, L.chunk_rows, L.dropped);
+        if (rc) return rc;
+        ctx->bf.seg_valid = ctx->bf.seg_keep;
+    }
     ctx->pk.li_valid = ctx->pk.track;
     ctx->vl.vl_valid = c.enable_vpacket_tracking && call.vpk && ctx->vl.vlog_capacity > 0;
     ctx->vl.vl_li = vlog_li_call(ctx);
@@ -5171,6 +5298,7 @@ int tardis_mc_set_continuum_data(TardisMcContext *ctx, const TardisMcContinuumDa
     if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
     if (!ctx->pl.have) return fail(ctx, TARDIS_MC_ERR_STATE, "set_plasma_data must precede set_continuum_data");
     ctx->ct.have = ctx->ct.valid = false;
+    ctx->bf.have = ctx->bf.rates_valid = false;  // (whatever drops the continuum data drops the estimators on it)
     if (!d) return TARDIS_MC_OK;
     // everything the kernels index with is checked here, on the host
     std::vector<int> level_ion((size_t)std::max<int64_t>(d->n_continua, 1));
@@ -5273,6 +5401,10 @@ static int continuum_stage(TardisMcContext *ctx)
     a.n_e = ctx->pl.n_e.as<double>(); a.t_e = ctx->ct.t_e.as<double>(); a.ff = ctx->ct.ff.as<double>();
     a.bfp = ctx->ct.bfp.as<double>(); a.y_sp = ctx->ct.y_sp.as<double>(); a.y_g = ctx->ct.y_g.as<double>(); a.y_st = ctx->ct.y_st.as<double>();
     a.rates = ctx->ct.rates.as<double>(); a.chi_bf = ctx->ct.chi_bf.as<double>(); a.counts = ctx->ct.counts.as<int>();
+    if (ctx->bf.continuum_field == 1) {  // (tardis_mc_update_plasma has checked that the rates are resident)
+        a.gamma_est = ctx->bf.rates.as<double>();
+        a.stim_est = a.gamma_est + NC * (long long)S;
+    }
     HIP_TRY(ctx, hipEventRecord(ctx->ct.ev[0], ctx->stream));
     // thermal: t_e and the free-free factor, lbf_e = g exp(E (-beta_e)) (the LTE Boltzmann kernel on t_e), Z_e (the partition kernels of the plasma stage)
     hipLaunchKernelGGL(mc::continuum_shell_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, ctx->stream, a);
@@ -5739,6 +5871,8 @@ int tardis_mc_update_plasma(TardisMcContext *ctx, const TardisMcPlasmaUpdate *p)
     u.detailed_optical_window = p->detailed_optical_window;
     int rc;
     if ((rc = plasma_update_check(ctx, p, &u))) return rc;
+    if (ctx->ct.have && ctx->bf.continuum_field == 1 && !(ctx->bf.have && ctx->bf.rates_valid))
+        return fail(ctx, TARDIS_MC_ERR_STATE, "update_plasma: the option continuum_field is 1 and no estimator rates are resident (tardis_mc_bf_estimator_rates)");
     if ((rc = plasma_update_prepare(ctx))) return rc;
     if ((rc = plasma_update_enqueue(ctx, p))) return rc;  // into the solve's own buffers
     if ((rc = plasma_update_status(ctx))) return rc;      // a failed solve ends here: the opacity state has not been written
@@ -5796,6 +5930,176 @@ int tardis_mc_last_helium_ms(TardisMcContext *ctx, double *out_relative_ms)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     double *const out[1] = {out_relative_ms};
     return event_intervals_ms(ctx, ctx->he.ev, 1, out);
+}
+
+/* ---- photo-ionisation and heating estimators from the transport's segment log (bf_estimators.hpp) ---- */
+int tardis_mc_check_bf_estimator_setup(const TardisMcBfEstimatorSetup *setup, int64_t n_shells)
+{
+    if (!setup || !setup->t_electrons) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "bf estimator setup: a pointer is missing");
+    if (n_shells < 1) return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "bf estimator setup: n_shells = %lld is not positive", (long long)n_shells);
+    for (int64_t s = 0; s < n_shells; ++s)
+        if (!(std::isfinite(setup->t_electrons[s]) && setup->t_electrons[s] > 0.0))
+            return fail(nullptr, TARDIS_MC_ERR_INVALID_ARGUMENT, "bf estimator setup: t_electrons[%lld] = %g is not finite and positive", (long long)s, setup->t_electrons[s]);
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_set_bf_estimators(TardisMcContext *ctx, const TardisMcBfEstimatorSetup *setup)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!setup) {  // off: the tables go
+        ctx->bf.have = ctx->bf.rates_valid = ctx->bf.seg_valid = false;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        release_buffers(ctx->bf.t_e, ctx->bf.tables, ctx->bf.totals, ctx->bf.rates);
+        return TARDIS_MC_OK;
+    }
+    if (!ctx->have_geometry || !ctx->ct.have) return fail(ctx, TARDIS_MC_ERR_STATE, "set_geometry and set_continuum_data must precede set_bf_estimators");
+    const size_t S = (size_t)ctx->n_shells, NC = (size_t)ctx->ct.continua;
+    if (tardis_mc_check_bf_estimator_setup(setup, (int64_t)S)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "%s", g_create_error.c_str());
+    // (a refused call has changed nothing up to here; from here on the previous setup, its tables and its rates are gone)
+    ctx->bf.have = ctx->bf.rates_valid = ctx->bf.seg_valid = false;
+    int rc;
+    if ((rc = upload(ctx, ctx->bf.t_e, setup->t_electrons, S))) return rc;
+    HIP_TRY(ctx, ctx->bf.tables.ensure(mc::BF_TABLES * NC * S * sizeof(double)));
+    HIP_TRY(ctx, ctx->bf.totals.ensure(2 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, ctx->bf.rates.ensure(2 * NC * S * sizeof(double)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->bf.tables.p, 0, mc::BF_TABLES * NC * S * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->bf.totals.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the caller's array is the source of an asynchronous copy)
+    ctx->bf.have = true;
+    return TARDIS_MC_OK;
+}
+
+static bool bf_resident(const TardisMcContext *ctx) { return ctx->bf.have && ctx->ct.have; }
+
+int tardis_mc_get_bf_estimators(TardisMcContext *ctx, double *photo_ion, double *stim_recomb, double *bf_heating, double *stim_recomb_cooling, int64_t *statistics,
+                                int64_t *n_records, int64_t *n_dropped)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!bf_resident(ctx)) return fail(ctx, TARDIS_MC_ERR_STATE, "get_bf_estimators needs tardis_mc_set_bf_estimators");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned long long totals[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpy(totals, ctx->bf.totals.p, sizeof totals, hipMemcpyDeviceToHost));
+    if (n_records) *n_records = (int64_t)totals[0];
+    if (n_dropped) *n_dropped = (int64_t)totals[1];
+    if (totals[1] > 0)
+        return fail(ctx, TARDIS_MC_ERR_STATE,
+                    "photo-ionisation estimators: %llu segment records were dropped (%llu logged) since the last reset: the tables are incomplete; raise the option "
+                    "segment_log_capacity or propagate fewer packets per call (the run is deterministic)", totals[1], totals[0]);
+    const size_t n = (size_t)ctx->ct.continua * (size_t)ctx->n_shells;
+    void *const host[mc::BF_TABLES] = {photo_ion, stim_recomb, bf_heating, stim_recomb_cooling, statistics};
+    std::vector<CopyJob> jobs;
+    for (int v = 0; v < mc::BF_TABLES; ++v) jobs.push_back({host[v], ctx->bf.tables.as<double>() + (size_t)v * n, n * sizeof(double)});
+    HIP_TRY(ctx, host_copy(ctx, jobs, false));
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_segment_log(TardisMcContext *ctx, double *nu, double *ed, int64_t *shell, int64_t capacity, int64_t *count)
+{
+    if (!ctx || !count || capacity < 0) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid segment log request");
+    if (!ctx->bf.seg_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "no segment log: the last tardis_mc_propagate ran without the options bf_estimators and segment_log_keep");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const mc::SegmentLog &L = ctx->problem_host.seglog;
+    std::vector<unsigned> fill(L.n_chunks);
+    HIP_TRY(ctx, hipMemcpy(fill.data(), L.chunk_fill, fill.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    int64_t total = 0;
+    for (unsigned f : fill) total += std::min(f, L.chunk_rows);
+    *count = total;
+    if (total > capacity || total == 0) return TARDIS_MC_OK;  // (the columns only when they fit the caller's arrays)
+    std::vector<mc::SegmentRecord> chunk(L.chunk_rows);
+    int64_t j = 0;
+    for (unsigned c = 0; c < L.n_chunks; ++c) {
+        const unsigned f = std::min(fill[c], L.chunk_rows);
+        if (!f) continue;
+        HIP_TRY(ctx, hipMemcpy(chunk.data(), L.recs + (size_t)c * L.chunk_rows, f * sizeof(mc::SegmentRecord), hipMemcpyDeviceToHost));
+        for (unsigned k = 0; k < f; ++k, ++j) {
+            if (nu) nu[j] = chunk[k].comov_nu;
+            if (ed) ed[j] = chunk[k].ed;
+            if (shell) shell[j] = chunk[k].shell;
+        }
+    }
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_debug_bf_accumulate(TardisMcContext *ctx, int64_t n, const double *nu, const double *ed, const int64_t *shell)
+{
+    if (!ctx || n < 0 || n > 0x7ffffff0LL || (n > 0 && (!nu || !ed || !shell))) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid segment records");
+    if (!bf_resident(ctx)) return fail(ctx, TARDIS_MC_ERR_STATE, "debug_bf_accumulate needs tardis_mc_set_bf_estimators");
+    if (ctx->n_shells > mc::EST_MAX_BINS)
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "photo-ionisation estimators: more than %d shells (the pass groups the records by shell in LDS)", mc::EST_MAX_BINS);
+    // everything the kernels index with is checked here, on the host
+    std::vector<mc::SegmentRecord> recs((size_t)n);
+    std::vector<unsigned> keys((size_t)n);
+    for (int64_t e = 0; e < n; ++e) {
+        if (!(std::isfinite(nu[e]) && nu[e] > 0.0)) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "segment records: nu[%lld] = %g is not finite and positive", (long long)e, nu[e]);
+        if (!std::isfinite(ed[e])) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "segment records: ed[%lld] = %g is not finite", (long long)e, ed[e]);
+        if (shell[e] < 0 || shell[e] >= (int64_t)ctx->n_shells)
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "segment records: shell[%lld] = %lld lies outside [0, %d)", (long long)e, (long long)shell[e], ctx->n_shells);
+        recs[(size_t)e].comov_nu = nu[e]; recs[(size_t)e].ed = ed[e]; recs[(size_t)e].shell = (int)shell[e]; recs[(size_t)e].pad = 0;
+        keys[(size_t)e] = (unsigned)shell[e];
+    }
+    if (n == 0) return TARDIS_MC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->bf.seg_valid = false;  // (the pass takes the sorted-slot buffer of the last call's log)
+    ScopedDevBuf d_recs, d_keys, d_fill;
+    const unsigned fill = (unsigned)n;
+    const int rc = [&]() -> int {
+        int rc1;
+        if ((rc1 = upload(ctx, d_recs, recs.data(), (size_t)n))) return rc1;
+        if ((rc1 = upload(ctx, d_keys, keys.data(), (size_t)n))) return rc1;
+        if ((rc1 = upload(ctx, d_fill, &fill, 1))) return rc1;
+        return bf_accumulate_pass(ctx, d_recs.as<mc::SegmentRecord>(), d_keys.as<unsigned>(), d_fill.as<unsigned>(), 1, fill, nullptr);  // one chunk holds them all
+    }();
+    (void)hipStreamSynchronize(ctx->stream);  // (nothing of the call is in flight when its scratch and the staging vectors go)
+    return rc;
+}
+
+int tardis_mc_last_bf_estimator_ms(TardisMcContext *ctx, double *out_group_ms, double *out_accumulate_ms)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!ctx->bf.timed) return fail(ctx, TARDIS_MC_ERR_STATE, "no accumulate pass of the photo-ionisation estimators has been timed yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double *const out[2] = {out_group_ms, out_accumulate_ms};
+    return event_intervals_ms(ctx, ctx->bf.ev, 2, out);
+}
+
+int tardis_mc_bf_estimator_rates(TardisMcContext *ctx, double time_of_simulation, const double *volume)
+{
+    if (!ctx || !volume) return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "invalid estimator rates request");
+    if (!bf_resident(ctx)) return fail(ctx, TARDIS_MC_ERR_STATE, "bf_estimator_rates needs tardis_mc_set_bf_estimators");
+    if (!(std::isfinite(time_of_simulation) && time_of_simulation > 0.0))
+        return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "bf_estimator_rates: time_of_simulation = %g is not finite and positive", time_of_simulation);
+    const size_t S = (size_t)ctx->n_shells;
+    for (size_t s = 0; s < S; ++s)
+        if (!(std::isfinite(volume[s]) && volume[s] > 0.0))
+            return fail(ctx, TARDIS_MC_ERR_INVALID_ARGUMENT, "bf_estimator_rates: volume[%zu] = %g is not finite and positive", s, volume[s]);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->bf.rates_valid = false;
+    ScopedDevBuf d_volume;
+    const long long cells = ctx->ct.continua * (long long)S;
+    int rc = upload(ctx, d_volume, volume, S);
+    if (!rc) {
+        hipLaunchKernelGGL(mc::bf_rates_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, (int)S, cells, time_of_simulation, H_PLANCK,
+                           d_volume.as<double>(), ctx->bf.tables.as<double>(), ctx->bf.rates.as<double>());
+        if (hipGetLastError() != hipSuccess) rc = fail(ctx, TARDIS_MC_ERR_HIP, "bf_rates_kernel failed to launch");
+    }
+    (void)hipStreamSynchronize(ctx->stream);  // (the scratch and the caller's array outlive the call's work)
+    if (rc) return rc;
+    ctx->bf.rates_valid = true;
+    return TARDIS_MC_OK;
+}
+
+int tardis_mc_get_bf_estimator_rates(TardisMcContext *ctx, double *gamma_est, double *stim_est)
+{
+    if (!ctx) return TARDIS_MC_ERR_INVALID_ARGUMENT;
+    if (!bf_resident(ctx) || !ctx->bf.rates_valid) return fail(ctx, TARDIS_MC_ERR_STATE, "get_bf_estimator_rates needs tardis_mc_bf_estimator_rates");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t n = (size_t)ctx->ct.continua * (size_t)ctx->n_shells;
+    HIP_TRY(ctx, host_copy(ctx, {{(void *)gamma_est, ctx->bf.rates.p, n * sizeof(double)}, {(void *)stim_est, ctx->bf.rates.as<double>() + n, n * sizeof(double)}}, false));
+    return TARDIS_MC_OK;
 }
 
 

@@ -55,6 +55,7 @@ class Engine:
         self.nlte_collision_data = None  # ... and set_nlte_collision_data() (None after whatever drops the NLTE data)
         self.ionization_options = None   # ... and set_ionization_options(): (helium_treatment, helium_element, delta_treatment); None after whatever drops the plasma data
         self.continuum_data = None       # ... and set_continuum_data(); None after whatever drops the plasma data
+        self.bf_t_electrons = None       # ... and set_bf_estimators(); None after whatever drops the continuum data
         self.n_continua = self.n_continuum_points = 0
         self.n_helium_levels = 0
         self.n_nlte_collision_pairs = 0
@@ -121,6 +122,8 @@ class Engine:
         m = _abi.marshal_geometry(geometry, time_explosion)
         self.resident_geometry = None
         self._check(self._L.tardis_mc_set_geometry(self._h, m.ref()), "set_geometry")
+        if int(m.struct.n_shells) != self.n_shells:
+            self.bf_t_electrons = None  # (the library drops the estimator setup with the shell count)
         self.n_shells = int(m.struct.n_shells)
         self.resident_geometry = (geometry, float(m.struct.time_explosion))
 
@@ -133,6 +136,7 @@ class Engine:
         self.nlte_collision_data = None
         self.ionization_options = None
         self.continuum_data = None
+        self.bf_t_electrons = None
         self.opacity_generation += 1
         self._check(self._L.tardis_mc_set_opacity(self._h, m.ref()), "set_opacity")
         self.n_lines, self.n_shells = int(m.struct.n_lines), int(m.struct.n_shells)
@@ -152,6 +156,7 @@ class Engine:
         self.nlte_collision_data = None
         self.ionization_options = None
         self.continuum_data = None
+        self.bf_t_electrons = None
         self._check(self._L.tardis_mc_set_line_data(self._h, m.ref()), "set_line_data")
         self.line_data = line_data
 
@@ -252,6 +257,7 @@ class Engine:
         self.nlte_collision_data = None
         self.ionization_options = None
         self.continuum_data = None
+        self.bf_t_electrons = None
         self._check(self._L.tardis_mc_set_plasma_data(self._h, m.ref()), "set_plasma_data")
         self.n_plasma_levels, self.n_ions = int(m.struct.n_levels), int(m.struct.n_ions)
         self.plasma_data = plasma_data
@@ -346,6 +352,7 @@ class Engine:
         update changes.  None removes the data; whatever drops the plasma data drops them too, set_nlte_data(),
         set_nlte_collision_data() and set_ionization_options() do not."""
         self.continuum_data = None
+        self.bf_t_electrons = None
         if continuum_data is None:
             self._check(self._L.tardis_mc_set_continuum_data(self._h, None), "set_continuum_data")
             return
@@ -448,6 +455,89 @@ class Engine:
         v = [C.c_double() for _ in range(3)]
         self._check(self._L.tardis_mc_last_cooling_ms(self._h, *(C.byref(x) for x in v)), "last_cooling_ms")
         return dict(zip(("points_ms", "blocks_ms", "table_ms"), (x.value for x in v)))
+
+    # -- photo-ionisation and heating estimators from the transport (option "bf_estimators")
+    BF_ESTIMATORS = ("photo_ion", "stim_recomb", "bf_heating", "stim_recomb_cooling")
+
+    def set_bf_estimators(self, t_electrons):
+        """The electron temperatures [n_shells] of the photo-ionisation estimators (`tardis_mc_set_bf_estimators`), after
+        set_continuum_data(): installs them and the zeroed tables.  With option "bf_estimators" 1 every propagate() then logs one
+        record per move of positive length and adds it to the tables (get_bf_estimators).  None switches the estimators off.
+        Whatever drops the continuum data drops this."""
+        self.bf_t_electrons = None
+        if t_electrons is None:
+            self._check(self._L.tardis_mc_set_bf_estimators(self._h, None), "set_bf_estimators")
+            return
+        m = _abi.marshal_bf_estimator_setup(t_electrons, self.n_shells)
+        self._check(self._L.tardis_mc_set_bf_estimators(self._h, m.ref()), "set_bf_estimators")
+        self.bf_t_electrons = m.keep[0]
+
+    @staticmethod
+    def check_bf_estimator_setup(t_electrons) -> tuple[int, str]:
+        """What set_bf_estimators() would say to ``t_electrons`` (`tardis_mc_check_bf_estimator_setup`, host only): (0, "") or
+        (ERR_INVALID_ARGUMENT, the message naming the first offending index)."""
+        t = np.ascontiguousarray(t_electrons, dtype=np.float64)
+        m = _abi.marshal_bf_estimator_setup(t, len(t))
+        L = _lib.lib()
+        rc = L.tardis_mc_check_bf_estimator_setup(m.ref(), len(t))
+        return int(rc), ("" if rc == 0 else L.tardis_mc_last_error(None).decode())
+
+    def get_bf_estimators(self) -> dict:
+        """The estimator tables (`tardis_mc_get_bf_estimators`): photo_ion, stim_recomb, bf_heating, stim_recomb_cooling (float64)
+        and statistics (int64), [n_continua, n_shells] each, with n_records / n_dropped since the last reset_estimators().  With
+        dropped records the RuntimeError (``code`` ERR_STATE) carries the two counts as ``n_records`` / ``n_dropped``."""
+        shape = (self.n_continua, self.n_shells)
+        out = {name: np.empty(shape) for name in self.BF_ESTIMATORS}
+        out["statistics"] = np.empty(shape, dtype=np.int64)
+        a, b = C.c_int64(-1), C.c_int64(-1)
+        rc = self._L.tardis_mc_get_bf_estimators(self._h, *(out[name].ctypes.data for name in self.BF_ESTIMATORS + ("statistics",)), C.byref(a), C.byref(b))
+        try:
+            self._check(rc, "get_bf_estimators")
+        except RuntimeError as e:
+            e.n_records, e.n_dropped = int(a.value), int(b.value)
+            raise
+        out["n_records"], out["n_dropped"] = int(a.value), int(b.value)
+        return out
+
+    def get_segment_log(self) -> dict:
+        """Tests: the segment records of the last propagate() (`tardis_mc_get_segment_log`; needs option "segment_log_keep"), in no
+        particular order: {"nu", "ed" (float64), "shell" (int64)}."""
+        n = C.c_int64(-1)
+        self._check(self._L.tardis_mc_get_segment_log(self._h, None, None, None, 0, C.byref(n)), "get_segment_log")
+        out = {"nu": np.empty(n.value), "ed": np.empty(n.value), "shell": np.empty(n.value, dtype=np.int64)}
+        if n.value:
+            self._check(self._L.tardis_mc_get_segment_log(self._h, out["nu"].ctypes.data, out["ed"].ctypes.data, out["shell"].ctypes.data, n.value, C.byref(n)),
+                        "get_segment_log")
+        return out
+
+    def debug_bf_accumulate(self, nu, ed, shell) -> None:
+        """Tests: the accumulate pass alone on caller-supplied records (`tardis_mc_debug_bf_accumulate`), into the resident tables."""
+        nu = np.ascontiguousarray(nu, dtype=np.float64)
+        ed = np.ascontiguousarray(ed, dtype=np.float64)
+        shell = np.ascontiguousarray(np.broadcast_to(np.asarray(shell, dtype=np.int64), nu.shape))
+        if ed.shape != nu.shape or nu.ndim != 1:
+            raise ValueError("nu, ed and shell are one-dimensional and of one length")
+        self._check(self._L.tardis_mc_debug_bf_accumulate(self._h, len(nu), nu.ctypes.data, ed.ctypes.data, shell.ctypes.data), "debug_bf_accumulate")
+        self.estimators_generation += 1
+
+    def last_bf_estimator_ms(self) -> dict:
+        """Device time (ms) of the last accumulate pass: {"group_ms" (the record slots grouped by shell), "accumulate_ms"}; none of
+        it is in any other timer."""
+        v = [C.c_double() for _ in range(2)]
+        self._check(self._L.tardis_mc_last_bf_estimator_ms(self._h, *(C.byref(x) for x in v)), "last_bf_estimator_ms")
+        return dict(zip(("group_ms", "accumulate_ms"), (x.value for x in v)))
+
+    def bf_estimator_rates(self, time_of_simulation, volume) -> dict:
+        """gamma_est and stim_est [n_continua, n_shells] from the resident tables (`tardis_mc_bf_estimator_rates`): photo_ion and
+        stim_recomb times 1 / ((time_of_simulation volume[s]) h).  They stay resident -- through reset_estimators() too -- for
+        update_plasma() under option "continuum_field" 1."""
+        volume = np.ascontiguousarray(volume, dtype=np.float64)
+        if volume.shape != (self.n_shells,):
+            raise ValueError("volume must be [n_shells]")
+        self._check(self._L.tardis_mc_bf_estimator_rates(self._h, float(time_of_simulation), volume.ctypes.data), "bf_estimator_rates")
+        out = {name: np.empty((self.n_continua, self.n_shells)) for name in ("gamma_est", "stim_est")}
+        self._check(self._L.tardis_mc_get_bf_estimator_rates(self._h, out["gamma_est"].ctypes.data, out["stim_est"].ctypes.data), "get_bf_estimator_rates")
+        return out
 
     def set_nlte_data(self, nlte_data):
         """The NLTE species of update_plasma() (`tardis_mc_set_nlte_data`), after set_plasma_data(): an object with the fields of
@@ -750,6 +840,7 @@ class Engine:
         self.nlte_collision_data = None
         self.ionization_options = None
         self.continuum_data = None
+        self.bf_t_electrons = None
         self.opacity_generation += 1
         self.results_generation += 1
         self.estimators_generation += 1

@@ -654,3 +654,35 @@ def make_continuum_data(seed: int, plasma_data: PlasmaData, n_continua: int, poi
         nu.append(grid)
         x.append(x0 * (nu_i / grid) ** 3)
     return ContinuumData(levels, np.concatenate(([0], np.cumsum(lengths))).astype(np.int64), np.concatenate(nu), np.concatenate(x))
+
+
+def comoving_frequency_range(problem: Problem) -> tuple[float, float]:
+    """An interval that holds every comoving frequency a packet of ``problem`` can have on a move: a packet's frequency is its
+    initial one or, after an interaction, a Doppler shift of a line's or of its own comoving one, and every Doppler factor lies
+    within 1 -+ beta of the outer edge -- widened by three such factors on either side."""
+    beta = float(problem.geometry.v_outer[-1]) / st.C_SPEED_OF_LIGHT
+    nus = np.concatenate((np.asarray(problem.packet_collection.initial_nus, dtype=np.float64),
+                          np.asarray(problem.opacity_state.line_list_nu, dtype=np.float64)))
+    return float(nus.min() * (1.0 - beta) ** 3), float(nus.max() * (1.0 + beta) ** 3)
+
+
+def make_covering_continuum_data(plasma_data: PlasmaData, blocks) -> ContinuumData:
+    """Continuum blocks laid where the caller wants them -- e.g. over comoving_frequency_range(), so that some continua are current
+    for a run's packets (the hydrogenic thresholds of make_continuum_data lie far above a 1e4-K photosphere's frequencies).
+    ``blocks``: a sequence of (nu, x_sect) array pairs, nu ascending strictly; block c goes to the c-th level of ``plasma_data``,
+    in level order, whose ion has an upper ion -- the frequencies then have nothing to do with the levels' energies: for the
+    estimators of the transport, not for physics."""
+    edge = np.asarray(plasma_data.ion_level_edge, dtype=np.int64)
+    elem = np.asarray(plasma_data.element_ion_edge, dtype=np.int64)
+    ion = np.repeat(np.arange(len(edge) - 1), np.diff(edge))
+    last = np.zeros(len(edge) - 1, dtype=bool)
+    last[elem[1:] - 1] = True
+    levels = np.flatnonzero(~last[ion])[:len(blocks)]
+    if len(levels) != len(blocks):
+        raise ValueError("more blocks than levels that can ionise")
+    nu = [np.asarray(b[0], dtype=np.float64) for b in blocks]
+    x = [np.asarray(b[1], dtype=np.float64) for b in blocks]
+    if any(a.ndim != 1 or len(a) < 2 or a.shape != b.shape or np.any(np.diff(a) <= 0) for a, b in zip(nu, x)):
+        raise ValueError("a block is (nu, x_sect): two vectors of one length >= 2, nu ascending strictly")
+    lengths = [len(a) for a in nu]
+    return ContinuumData(levels.astype(np.int64), np.concatenate(([0], np.cumsum(lengths))).astype(np.int64), np.concatenate(nu), np.concatenate(x))

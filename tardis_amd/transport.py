@@ -654,6 +654,8 @@ class MCTransportSolverHIP:
         self.nlte_collision_data = None  # their collisional rates (set_nlte_collision_data)
         self.ionization_options = None  # (helium_treatment, helium_element, delta_treatment) of update_plasma() (set_ionization_options)
         self.continuum_data = None     # the photo-ionisation cross-sections of update_plasma()'s continuum stage (set_continuum_data)
+        self.bf_t_electrons = None     # enable_bf_estimators(): the electron temperatures of the photo-ionisation estimators; None = off
+        self._plasma_t_electrons = None  # the continuum stage's t_e of the last update_plasma()
         self._mean_state = None        # what mean_optical_depths() runs on: the last initialize_transport_state()'s geometry ...
         self._mean_opacity = None      # ... and the newest opacity state (that call's, or the handle of a later update)
 
@@ -732,6 +734,26 @@ class MCTransportSolverHIP:
         and the continuum opacity tables (the handle's ``chi_bf``, ``ff_opacity_factor``; continuum_opacity()) of its populations."""
         self.continuum_data = continuum_data
 
+    def enable_bf_estimators(self, t_electrons=None):
+        """Photo-ionisation and heating estimators from the next runs' transport (``resident=True``, continuum data installed; option
+        "bf_estimators" / ``Engine.set_bf_estimators``): every run then logs its packets' moves and leaves the five tables of
+        bf_estimators().  ``t_electrons`` [shells]; None: the continuum stage's own of the last update_plasma()
+        (link_t_rad_t_electron t_radiative, kept from that call: a later update_opacity() drops the stage's tables).  ``False`` switches the estimators off again."""
+        if not self.resident:
+            raise RuntimeError("enable_bf_estimators() needs resident=True")
+        if t_electrons is False:
+            self.bf_t_electrons = None
+            return
+        if t_electrons is None:
+            t_electrons = self._plasma_t_electrons
+            if t_electrons is None:
+                raise RuntimeError("enable_bf_estimators() needs t_electrons, or an update_plasma() with continuum data before it")
+        self.bf_t_electrons = np.array(t_electrons, dtype=np.float64)
+
+    def bf_estimators(self) -> dict:
+        """``Engine.get_bf_estimators`` of the last run with enable_bf_estimators() (``resident=True``)."""
+        return self._eng().get_bf_estimators()
+
     def continuum_rates(self) -> dict:
         """``Engine.get_continuum_rates`` of the last update_plasma() (``resident=True``)."""
         return self._eng().get_continuum_rates()
@@ -759,16 +781,21 @@ class MCTransportSolverHIP:
             eng.set_continuum_data(self.continuum_data)
 
     def update_plasma(self, t_radiative, dilution_factor, ionization="nebular", excitation="dilute-lte",
-                      radiative_rates_type="dilute-blackbody", *, volume=None, w_epsilon=1e-10, time_of_simulation=None):
+                      radiative_rates_type="dilute-blackbody", *, volume=None, w_epsilon=1e-10, time_of_simulation=None,
+                      continuum_field="dilute-blackbody"):
         """The whole plasma step of an outer iteration on the device (``resident=True``): from ``t_radiative`` and ``dilution_factor``
         [shells] -- e.g. what ``transport_state.radiation_field()`` returned, damped by the caller -- the level populations and the
         electron density of the legacy plasma's ``ionization`` "nebular" / "lte" and ``excitation`` "dilute-lte" / "lte", and from them
         the opacity state as update_opacity() computes it.  No [levels, shells] or [lines, shells] array is passed.  Returns a
         ``DeviceOpacityState`` whose ``electron_density`` is the solved one -- S doubles, downloaded here and not on first access, so
         that no later update, successful or failed, can take it away --; it becomes the engine's resident opacity.  A failed solve
-        (RuntimeError, ``code`` ERR_STATE) leaves the engine's resident opacity, and the handle describing it, as they were."""
+        (RuntimeError, ``code`` ERR_STATE) leaves the engine's resident opacity, and the handle describing it, as they were.
+        ``continuum_field`` "estimators": the continuum stage's gamma and alpha_stim follow the last run's photo-ionisation estimators
+        (enable_bf_estimators(); needs ``volume``, and ``time_of_simulation`` or a run) instead of the dilute black body."""
         if not self.resident:
             raise RuntimeError("update_plasma() needs resident=True")
+        if continuum_field not in ("dilute-blackbody", "estimators"):
+            raise ValueError(f"unknown continuum_field {continuum_field!r}")
         if self.line_data is None or self.plasma_data is None:
             raise RuntimeError("update_plasma() needs set_line_data() and set_plasma_data() first")
         eng = self._eng()
@@ -780,6 +807,15 @@ class MCTransportSolverHIP:
         if eng.plasma_data is not self.plasma_data:
             eng.set_plasma_data(self.plasma_data)
         self._install_nlte(eng)
+        if continuum_field == "estimators":
+            if volume is None:
+                raise ValueError('continuum_field="estimators" needs volume')
+            if time_of_simulation is None:
+                if self.transport_state is None:
+                    raise RuntimeError('continuum_field="estimators" needs a run, or time_of_simulation')
+                time_of_simulation = self.transport_state.time_of_simulation
+            eng.bf_estimator_rates(time_of_simulation, volume)
+        eng.set_option("continuum_field", int(continuum_field == "estimators"))
         if radiative_rates_type == "detailed":
             if time_of_simulation is None:
                 if self.transport_state is None:
@@ -792,6 +828,10 @@ class MCTransportSolverHIP:
         else:
             raise ValueError(f"unknown radiative_rates_type {radiative_rates_type!r}")
         handle = DeviceOpacityState(eng, base, eng.get_plasma(False, False, False, True)["electron_density"], eng.continuum_data)
+        # (the continuum stage's t_e = link_t_rad_t_electron t_rad, one rounding per shell: what enable_bf_estimators() defaults to; formed here,
+        # nothing is fetched -- a later update_opacity() drops the stage's own)
+        self._plasma_t_electrons = (float(self.plasma_data.link_t_rad_t_electron) * np.array(t_radiative, dtype=np.float64)
+                                    if eng.continuum_data is not None else None)
         eng.resident_opacity = handle
         self._mean_opacity = handle
         return handle
@@ -905,6 +945,14 @@ class MCTransportSolverHIP:
             self._install_nlte(eng)
         eng.set_config(cfg, self.spectrum_frequency_grid, cfg.NUMBER_OF_VPACKETS)
         eng.set_option("track_last_interaction", int(self.enable_last_interaction_tracking))
+        if self.bf_t_electrons is not None:
+            if eng.continuum_data is None:
+                raise RuntimeError("enable_bf_estimators() needs set_line_data(), set_plasma_data() and set_continuum_data()")
+            if eng.bf_t_electrons is None or not np.array_equal(eng.bf_t_electrons, self.bf_t_electrons):
+                eng.set_bf_estimators(self.bf_t_electrons)
+            eng.set_option("bf_estimators", 1)
+        elif getattr(eng, "options", {}).get("bf_estimators"):  # (the engine is shared: another solver may have left the option on)
+            eng.set_option("bf_estimators", 0)
         pc = ts.packet_collection
         device_packets = isinstance(pc, DevicePacketCollection)
         if device_packets:
